@@ -10,9 +10,12 @@ decompress every FCZ record back to SoA atoms (round trip). Workload at N=1 = BA
 N>1: every rank owns its own 1M-chain shard (weak scaling); the data path has no collective, the ranks
 only exchange the output index (per-record lengths -> global offsets) over RCCL after compressing.
 
-Prints ONE JSON line on rank 0 (contract in the task description) with `roofline` (dominant kernel,
-HIP-event time measured here) and `cpu_baseline` (the reference's own CPU path, oracle/_ref, timed on a
-bounded sample of the same chains on this host).
+Prints ONE JSON line on rank 0: `metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step` and the workload's
+`config`. A plain run sets up, warms up, times --steps steps and prints that line, nothing more. With --full it then runs
+every other leg and check as well and adds them to the line: `roofline` (dominant kernel, HIP-event time measured here),
+`cpu_baseline` (the reference's own CPU path, oracle/_ref, timed on a bounded sample of the same chains on this host),
+parity against the oracle, the alternate numerics, the secondary shapes, the PDB / ingest / extract / end_to_end legs and
+the host-pointer leg. --dump-outputs DIR writes what the last timed step computed (a fixed, seeded sample) as .npy files.
 """
 from __future__ import annotations
 
@@ -77,7 +80,17 @@ def parse_args():
     ap.add_argument("--mixed", action="store_true",
                     help="BASELINE configs[4] stand-in: log-normal chain lengths (mu = ln 250, sigma = 0.6, clipped to [16, 2700]) "
                          "instead of the fixed --residues; not the headline workload")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run every other leg and check (alternate numerics, secondary shapes, properties, "
+                         "PDB / ingest / extract, end_to_end, parity against the oracle, CPU baseline, roofline, host-pointer leg) and "
+                         "report them in the line; without it the run times the headline steps and reports them only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (FCZ records and decoded atoms of a fixed, seeded sample of rank 0's "
+                         "chains) to DIR/<name>.npy as float32 / float64, for comparing two builds output for output")
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    return a
 
 
 def generate_resident(n_chains, n_res, anchor, chunk, device, seed_base, mixed=False):
@@ -470,6 +483,47 @@ def span_ms(codec):
         ms, n = codec.kernel_time(name)
         out[name] = (ms / n) if n else 0.0
     return out
+
+
+DUMP_CHAINS = 256                 # chains of the --dump-outputs sample
+DUMP_SEED = 0x5EED                # its generator seed: the same chains in every run of the same arguments
+DUMP_BUDGET = 48 << 20            # bytes of .npy data at most (the chains of the sample are kept while they fit)
+
+
+def _gather_ranges(src, off, ix):
+    """src[off[i]:off[i + 1]] for every i of ix, concatenated on the device -> (values, lengths); off int64"""
+    lo, n = off[ix], off[ix + 1] - off[ix]
+    start = torch.cumsum(n, 0) - n
+    pos = torch.repeat_interleave(lo - start, n) + torch.arange(int(n.sum()), device=src.device)
+    return src[pos], n
+
+
+def dump_outputs(path, w):
+    """what the last timed step handed its caller -- the FCZ records (bytes, lengths, status) and the decoded atoms (x / y / z,
+    per-residue B-factors and residue codes, counts) -- for a fixed, seeded sample of the rank's chains, as DIR/<name>.npy in
+    float32 / float64 (the whole batch is tens of GB). Every value is exact in its type: bytes and codes are small integers."""
+    C = w.C
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(C, size=min(C, DUMP_CHAINS), replace=False))
+    ix = torch.from_numpy(idx).to(w.dev)
+    off = w.off_dev
+    res_off = w.res_off_dev.to(torch.int64) & 0xFFFFFFFF            # uint32 counts carried in torch int32
+    atom_off = w.atom_off_dev.to(torch.int64) & 0xFFFFFFFF
+    # the chains of the sample are kept in order while their arrays fit the budget
+    cost = ((off[ix + 1] - off[ix]) * 4 + (atom_off[ix + 1] - atom_off[ix]) * 12 + (res_off[ix + 1] - res_off[ix]) * 8 + 40).cpu().numpy()
+    keep = max(1, int(np.searchsorted(np.cumsum(cost), DUMP_BUDGET, side="right")))
+    idx, ix = idx[:keep], ix[:keep]
+    rec, rec_len = _gather_ranges(w.blob_dev, off, ix)
+    out = {"chain_index": idx.astype(np.int64), "fcz_record_len": rec_len, "fcz_bytes": rec, "status": w.status_dev[ix]}
+    for k in ("x", "y", "z"):
+        out[k], n_atoms = _gather_ranges(w.out_t[k], atom_off, ix)
+    for k in ("bfac_res", "res_code"):
+        out[k], n_res = _gather_ranges(w.out_t[k], res_off, ix)
+    out["atoms_per_chain"], out["residues_per_chain"] = n_atoms, n_res
+    os.makedirs(path, exist_ok=True)
+    for k, v in out.items():
+        v = v.cpu().numpy() if torch.is_tensor(v) else v
+        np.save(os.path.join(path, f"{k}.npy"), v.astype(np.float64 if v.dtype == np.int64 else np.float32))
+    return {"dir": path, "chains": int(len(idx)), "files": sorted(f"{k}.npy" for k in out)}
 
 
 def cif_from_pdb_text(pdb: bytes, entry_id: str) -> bytes:
@@ -1407,6 +1461,38 @@ def note(msg):
         print(f"[bench {time.perf_counter() - _T0:7.1f}s] {msg}", file=sys.stderr, flush=True)
 
 
+def headline_fields(args, w, dt, world, ktime, group_note, preflight_note, backend):
+    """the line's headline part: the timed steps, the workload, and the per-kernel rates the timed steps' own HIP events give"""
+    C, R, M, n_res = w.C, w.R, w.M, args.residues
+    A = M / R                                   # atoms per residue
+    compress_ms = ktime["compress_index"] + ktime["compress_angles"] + ktime["compress_pack"]
+    dec_ms = ktime["decompress_backbone"] + ktime["decompress_index"] + ktime["decompress_sidechain"]
+    return {
+        "metric": "residues/sec compress+decompress, 350-aa chains; bit-exact FCZ; 1/2/4/8 GPUs",
+        "value": R * world * args.steps / dt, "unit": "residues/s (round trip: each residue compressed and decompressed once)",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3,
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32/f64 + u8 bitpack",
+        "data": "synthetic",
+        "config": {"workload": (f"{C} synthetic mixed-length chains per GPU (log-normal, mean {R / C:.0f} residues), "
+                                if args.mixed else f"{C} synthetic {n_res}-residue chains per GPU, ")
+                               + f"compress+decompress, anchor -b {args.anchor}",
+                   "chains_per_gpu": C, "residues_per_chain": round(R / C, 1) if args.mixed else n_res, "atoms_per_residue": round(A, 3),
+                   "fcz_bytes_per_residue": round(w.fcz_bytes / R, 3), "parallelism": f"chain-sharded x{world}, no data-path collective",
+                   "index_exchange": group_note or f"record lengths gathered on rank 0 over RCCL inside every step ({world}-rank group)",
+                   "preflight": preflight_note, "host_cpus": effective_cores(), "host_threads_per_rank": max(1, effective_cores() // max(1, world)),
+                   "seed_base": args.seed_base, "backend": backend,
+                   # how to read a --gpus N line of this bench, and of the product drivers, on a CPU quota that does not grow with N
+                   "expected_bound_at_n_gpus": ("this step: inputs resident in HBM, no host stage, one small gather per step -> weak scaling, per-rank rate = the 1-GPU rate; "
+                                                "the CPU baseline and the parity checkers run on rank 0's host cores only. The product drivers (end_to_end / "
+                                                "python -m foldcomp_amd --gpus N) divide the host's CPU quota between the ranks' reader threads (sharded_cli.host_threads): "
+                                                "one engine needs ~16 threads to fill one GPU's link, so on a 16-CPU quota an 8-rank directory -> database run is "
+                                                "reader-thread-bound (2 threads per engine), not GPU- or xGMI-bound")},
+        "compress_residues_per_s": R / (compress_ms * 1e-3) if compress_ms else None,
+        "decompress_residues_per_s": R / (dec_ms * 1e-3) if dec_ms else None,
+        "numerics": args.numerics, "full": bool(args.full),
+    }
+
+
 def main():
     args = parse_args()
     cmd = self_launch_command(args.gpus, sys.argv[1:], os.environ)
@@ -1494,7 +1580,7 @@ def main():
     for _ in range(args.warmup):
         step()
     codec.synchronize(); torch.cuda.synchronize()
-    warm_csum = w.checksum() if (args.warmup and not args.no_parity) else None
+    warm_csum = w.checksum() if (args.full and args.warmup and not args.no_parity) else None
     codec.enable_timing(True); codec.reset_timing()
     # the timed region: exactly --steps steps between barrier + synchronize pairs, max over ranks
     comm.barrier()
@@ -1511,6 +1597,20 @@ def main():
     # per-kernel device time (HIP events on the codec's own stream)
     ktime = span_ms(codec)
     note(f"headline timed: {dt / args.steps * 1e3:.2f} ms/step")
+    # the outputs of the last timed step, before any leg below reuses the buffers
+    dumped = dump_outputs(args.dump_outputs, w) if (args.dump_outputs and rank == 0) else None
+    if dumped:
+        note(f"dumped {dumped['chains']} chains' outputs to {dumped['dir']}")
+    headline = headline_fields(args, w, dt, world, ktime, group_note, preflight_note, backend)
+    if not args.full:
+        # a plain run reports the timed steps only; every other leg and check runs with --full
+        if rank == 0:
+            emit_line(headline)
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+        codec.close()
+        return
     alt = alt_numerics_leg(args, codec, w, dev, comm, args.numerics,
                            ktime["compress_sizes"] + ktime["compress_index"] + ktime["compress_angles"] + ktime["compress_pack"])
     note(f"alt numerics ({alt['mode']}) done: decompress {alt['decompress_ms']} ms")
@@ -1784,31 +1884,10 @@ def main():
             except Exception as e:   # noqa: BLE001
                 hostb = {"failed": repr(e)[-400:]}
             note("host-pointer (PCIe-inclusive) leg done")
-        total_res = R * world * args.steps
         line = {
-            "metric": "residues/sec compress+decompress, 350-aa chains; bit-exact FCZ; 1/2/4/8 GPUs",
-            "value": total_res / dt, "unit": "residues/s (round trip: each residue compressed and decompressed once)",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3,
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32/f64 + u8 bitpack",
-            "data": "synthetic",
-            "config": {"workload": (f"{C} synthetic mixed-length chains per GPU (log-normal, mean {R / C:.0f} residues), "
-                                    if args.mixed else f"{C} synthetic {n_res}-residue chains per GPU, ")
-                                   + f"compress+decompress, anchor -b {args.anchor}",
-                       "chains_per_gpu": C, "residues_per_chain": round(R / C, 1) if args.mixed else n_res, "atoms_per_residue": round(A, 3),
-                       "fcz_bytes_per_residue": round(fcz_per_res, 3), "parallelism": f"chain-sharded x{world}, no data-path collective",
-                       "index_exchange": group_note or f"record lengths gathered on rank 0 over RCCL inside every step ({world}-rank group)",
-                       "preflight": preflight_note, "host_cpus": effective_cores(), "host_threads_per_rank": max(1, effective_cores() // max(1, world)),
-                       "seed_base": args.seed_base, "backend": backend,
-                       # how to read a --gpus N line of this bench, and of the product drivers, on a CPU quota that does not grow with N
-                       "expected_bound_at_n_gpus": ("this step: inputs resident in HBM, no host stage, one small gather per step -> weak scaling, per-rank rate = the 1-GPU rate; "
-                                                    "the CPU baseline and the parity checkers run on rank 0's host cores only. The product drivers (end_to_end / "
-                                                    "python -m foldcomp_amd --gpus N) divide the host's CPU quota between the ranks' reader threads (sharded_cli.host_threads): "
-                                                    "one engine needs ~16 threads to fill one GPU's link, so on a 16-CPU quota an 8-rank directory -> database run is "
-                                                    "reader-thread-bound (2 threads per engine), not GPU- or xGMI-bound")},
-            "compress_residues_per_s": R / (ktime["compress"] * 1e-3) if ktime["compress"] else None,
-            "decompress_residues_per_s": R / (dec_ms * 1e-3) if dec_ms else None,
+            **headline,
             "roofline": roofline, "cpu_baseline": cpu, "parity": parity, "properties": props,
-            "numerics": args.numerics, "alt_numerics": alt,
+            "alt_numerics": alt,
             "decompress_only": legs[0] if legs else None, "mixed": legs[1] if legs else None, "pdb_text": pdb, "extract": ext, "end_to_end": e2e,
             "host_boundary": hostb,
         }

@@ -25,8 +25,72 @@ REF_SO = os.path.join(ORACLE_DIR, "_ref", "libfoldcomp_ref.so")
 GOLDEN = os.path.join(ROOT, "tests", "golden")
 REFERENCE_TEST_DIR = "/root/reference/test"
 
+GOLDEN_PART_BYTES = 900 << 10      # tests/golden/reference_vectors_<i>.npz: each part below the 1 MiB limit of a committed file
+
 _oracle = None
 _ref = None
+
+
+class GoldenVectors:
+    """the parts tests/golden/reference_vectors_<i>.npz read as one archive (z[key], key in z, z.files): the vectors are stored
+    split, every case whole in one part, so that no file passes 1 MiB"""
+
+    def __init__(self, paths):
+        self._parts = [np.load(p) for p in paths]
+        self._where = {k: z for z in self._parts for k in z.files}
+        self.files = list(self._where)
+
+    def __getitem__(self, key):
+        return self._where[key][key]
+
+    def __contains__(self, key):
+        return key in self._where
+
+    def keys(self):
+        return list(self.files)
+
+    def close(self):
+        for z in self._parts:
+            z.close()
+
+
+def load_golden_vectors() -> GoldenVectors:
+    import glob
+    paths = sorted(glob.glob(os.path.join(GOLDEN, "reference_vectors_*.npz")), key=lambda p: int(p[:-4].rsplit("_", 1)[1]))
+    if not paths:
+        raise FileNotFoundError(os.path.join(GOLDEN, "reference_vectors_<i>.npz"))
+    return GoldenVectors(paths)
+
+
+def save_golden_vectors(out: dict) -> List[str]:
+    """write `out` as tests/golden/reference_vectors_<i>.npz: cases (the key up to the first '/') in order, a new part whenever the
+    compressed part would pass GOLDEN_PART_BYTES"""
+    import glob
+    import io
+
+    def packed(items):
+        b = io.BytesIO()
+        np.savez_compressed(b, **dict(items))
+        return b.getvalue()
+
+    groups = {}
+    for k, v in out.items():
+        groups.setdefault(k.split("/")[0], []).append((k, v))
+    parts, cur = [], []
+    for items in groups.values():
+        if cur and len(packed(cur + items)) > GOLDEN_PART_BYTES:
+            parts.append(cur)
+            cur = []
+        cur = cur + items
+    parts.append(cur)
+    for old in glob.glob(os.path.join(GOLDEN, "reference_vectors_*.npz")):
+        os.remove(old)
+    paths = []
+    for i, items in enumerate(parts):
+        paths.append(os.path.join(GOLDEN, f"reference_vectors_{i}.npz"))
+        with open(paths[-1], "wb") as fh:
+            fh.write(packed(items))
+    return paths
 
 
 def build_oracle():

@@ -16,8 +16,8 @@ def pytest_configure(config):
 
 @pytest.fixture(scope="session")
 def golden():
-    path = os.path.join(ROOT, "tests", "golden", "reference_vectors.npz")
-    z = np.load(path)
+    import _harness as H
+    z = H.load_golden_vectors()
     index = bytes(z["index"]).decode().split("\n")
     return z, index
 

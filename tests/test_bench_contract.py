@@ -19,6 +19,15 @@ def test_defaults_are_the_headline_workload(monkeypatch):
     a = b.parse_args()
     assert a.gpus == 1 and a.chains == 1_000_000 and a.residues == 350 and a.anchor == 25 and not a.mixed
     assert a.steps >= 1 and a.warmup >= 1
+    # a plain run times the headline only: the other legs and the output dump are asked for
+    assert a.full is False and a.dump_outputs is None
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--steps", "7", "--dump-outputs", "out"])
+    a = b.parse_args()
+    assert a.full is True and a.steps == 7 and a.dump_outputs == "out"
+    import pytest
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "0"])
+    with pytest.raises(SystemExit):
+        b.parse_args()
 
 
 def test_traffic_table_covers_the_reported_kernels():
@@ -117,7 +126,8 @@ def test_bench_mmcif_rendering_holds_the_same_atoms():
     b = _bench()
     from foldcomp_amd.structure import parse_pdb_gemmi, parse_structure_gemmi
     from test_host_cpp import _pdb_text
-    z = np.load(os.path.join(ROOT, "tests", "golden", "reference_vectors.npz"))
+    import _harness as H
+    z = H.load_golden_vectors()
     for name in ("syn:len26", "syn:len129", "pdb:test_af"):
         pdb = _pdb_text(z, name).encode()
         cif = b.cif_from_pdb_text(pdb, "ENTRY1")

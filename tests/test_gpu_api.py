@@ -215,7 +215,6 @@ def test_iterating_a_database_runs_in_gpu_batches_behind_the_per_entry_surface(t
     finally:
         FoldcompDatabase.READAHEAD = old
     print(f"  a GPU call per entry: {per_entry:.0f} entries/s -> the window is {rate / per_entry:.1f}x")
-    with open(os.path.join(os.environ.get("GRAFT_REPO_ROOT", "."), "gpurun_out", "r6_python_iter.json"), "w") as fh:
-        json.dump({"entries": n, "residues_per_entry": n_res, "readahead": old, "entries_per_s": round(rate, 1), "residues_per_s": round(rate * n_res),
-                   "per_entry_gpu_call_entries_per_s": round(per_entry, 1), "reference_per_entry_loop_entries_per_s": ref["entries_per_s"],
-                   "speedup_vs_reference_loop": round(rate / ref["entries_per_s"], 1)}, fh)
+    print(json.dumps({"entries": n, "residues_per_entry": n_res, "readahead": old, "entries_per_s": round(rate, 1), "residues_per_s": round(rate * n_res),
+                      "per_entry_gpu_call_entries_per_s": round(per_entry, 1), "reference_per_entry_loop_entries_per_s": ref["entries_per_s"],
+                      "speedup_vs_reference_loop": round(rate / ref["entries_per_s"], 1)}))

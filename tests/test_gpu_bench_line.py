@@ -1,5 +1,6 @@
-"""bench.py as the driver runs it (a subprocess, one JSON line on stdout), at a size that finishes in seconds: every object the
-contract and DESIGN.md §6 name must be present, parity flags true, the host-pointer leg byte-identical to the resident path."""
+"""bench.py as the driver runs it (a subprocess, one JSON line on stdout), at a size that finishes in seconds: with --full every object
+the contract and DESIGN.md §6 name must be present, parity flags true, the host-pointer leg byte-identical to the resident path; a
+plain run carries the headline only, and --dump-outputs writes the same outputs in every run."""
 import json
 import os
 import subprocess
@@ -16,7 +17,7 @@ def line():
     env = dict(os.environ)
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--chains", "16384", "--steps", "2", "--warmup", "1",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--chains", "16384", "--steps", "2", "--warmup", "1",
            "--cpu-sample", "512", "--parity-chains", "512", "--pdb-sample", "1024", "--mixed-chains", "6000", "--mixed-steps", "1",
            "--e2e-files", "384", "--e2e-passes", "8", "--host-chains", "4096"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
@@ -131,7 +132,7 @@ def test_two_rank_line_is_creditable():
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     env["FCZ_BENCH_BACKEND"] = "gloo"
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--chains", "8192", "--steps", "2", "--warmup", "1",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--chains", "8192", "--steps", "2", "--warmup", "1",
            "--cpu-sample", "512", "--parity-chains", "700", "--parity-chunk", "256", "--pdb-sample", "0", "--mixed-chains", "3000",
            "--mixed-steps", "1", "--e2e-files", "0", "--host-chains", "0"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
@@ -146,3 +147,44 @@ def test_two_rank_line_is_creditable():
     assert ln["properties"]["ranks_checked"] == 2 and ln["properties"]["deterministic"] and ln["properties"]["residue_counts_round_trip"]
     assert ln["mixed"]["parity"]["ranks_checked"] == 2 and ln["mixed"]["parity"]["fcz_bit_exact"] and ln["mixed"]["parity"]["coords_bit_exact"]
     assert abs(ln["value"] - 2 * 8192 * 350 / (ln["ms_per_step"] * 1e-3)) / ln["value"] < 1e-6
+
+
+def _plain_run(tmp_path, tag):
+    env = dict(os.environ)
+    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
+        env.pop(k, None)
+    out_dir = tmp_path / tag
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--chains", "16384", "--steps", "3", "--warmup", "1",
+           "--dump-outputs", str(out_dir)]
+    r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    out = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(out) == 1, r.stdout[-2000:]
+    return json.loads(out[0]), out_dir
+
+
+def test_plain_run_and_dumped_outputs(tmp_path):
+    """a plain run: the headline fields, exactly --steps timed steps, none of the --full legs; --dump-outputs writes the last timed
+    step's records and decoded atoms of a seeded sample as float32 / float64 .npy, identical from run to run"""
+    import numpy as np
+    a, da = _plain_run(tmp_path, "a")
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "n_gpus", "steps", "warmup", "config"):
+        assert k in a, k
+    assert a["steps"] == 3 and a["warmup"] == 1 and a["full"] is False and a["value"] > 0 and a["higher_is_better"] is True
+    assert abs(a["value"] - 16384 * 350 / (a["ms_per_step"] * 1e-3)) / a["value"] < 1e-6
+    for k in ("roofline", "cpu_baseline", "parity", "properties", "alt_numerics", "mixed", "end_to_end", "host_boundary"):
+        assert k not in a, k
+    b, db = _plain_run(tmp_path, "b")
+    names = sorted(p.name for p in da.iterdir())
+    assert names == sorted(p.name for p in db.iterdir())
+    assert {"fcz_bytes.npy", "fcz_record_len.npy", "x.npy", "y.npy", "z.npy", "bfac_res.npy", "chain_index.npy"} <= set(names)
+    assert sum((da / n).stat().st_size for n in names) <= 64 << 20
+    arrs = {}
+    for n in names:
+        x, y = np.load(da / n), np.load(db / n)
+        assert x.dtype in (np.float32, np.float64), (n, x.dtype)
+        assert x.dtype == y.dtype and np.array_equal(x.view(np.uint8), y.view(np.uint8)), n
+        arrs[n[:-4]] = x
+    assert len(arrs["chain_index"]) > 0 and (arrs["status"] == 0).all()
+    assert arrs["fcz_record_len"].sum() == len(arrs["fcz_bytes"]) and arrs["atoms_per_chain"].sum() == len(arrs["x"])
+    assert arrs["residues_per_chain"].sum() == len(arrs["bfac_res"]) and (arrs["residues_per_chain"] == 350).all()

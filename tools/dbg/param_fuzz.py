@@ -37,7 +37,7 @@ def mutated(records, rng, per_record=24):
 
 
 def run(seed, codec=None, per_record=24):
-    z = np.load(os.path.join(ROOT, "tests", "golden", "reference_vectors.npz"))
+    z = H.load_golden_vectors()
     index = bytes(z["index"]).decode().split("\n")
     recs = golden_records((z, index))
     rng = np.random.default_rng(seed)

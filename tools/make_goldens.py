@@ -2,7 +2,7 @@
 """Mint golden vectors from the REAL reference (oracle/_ref/libfoldcomp_ref.so, built from
 /root/reference/src by oracle/build_ref.sh) and from the reference's own test fixtures.
 
-Runs in the build container only. Output: tests/golden/reference_vectors.npz (data only: inputs as SoA
+Runs in the build container only. Output: tests/golden/reference_vectors_<i>.npz (data only: inputs as SoA
 arrays and the reference's outputs; no reference source text).
 
 Cases
@@ -155,6 +155,5 @@ for name, b, thr in cases:
     add_batch_case(name, b, thr)
 
 out["index"] = np.frombuffer("\n".join(index).encode(), np.uint8)
-path = os.path.join(ROOT, "tests", "golden", "reference_vectors.npz")
-np.savez_compressed(path, **out)
-print("wrote", path, os.path.getsize(path), "bytes;", len(index), "cases")
+paths = H.save_golden_vectors(out)
+print("wrote", len(paths), "parts,", sum(os.path.getsize(p) for p in paths), "bytes;", len(index), "cases")

@@ -23,7 +23,7 @@ PY
 done
 cat $OUT/pmc.txt
 # (same call) the two-rank sharded decompress BEFORE the write-once change: its exchange_and_splice_s against engine_s
-cd $REPO && python bench.py --chains 65536 --steps 1 --warmup 0 --cpu-sample 0 --no-parity --mixed-chains 0 --pdb-sample 0 --host-chains 0 --e2e-files 8192 > $OUT/e2e_before.json 2> $OUT/e2e_before.err
+cd $REPO && python bench.py --full --chains 65536 --steps 1 --warmup 0 --cpu-sample 0 --no-parity --mixed-chains 0 --pdb-sample 0 --host-chains 0 --e2e-files 8192 > $OUT/e2e_before.json 2> $OUT/e2e_before.err
 python - <<'PY'
 import json
 d = json.load(open("gpurun_out/r5_ring/e2e_before.json"))

@@ -4,7 +4,7 @@ TAG=$1; shift
 OUT=gpurun_out/rows_$TAG.txt; : > $OUT
 run() { # lib, label, bench args...
   local lib=$1 label=$2; shift 2
-  FCZ_HIP_LIB=$PWD/$lib python bench.py "$@" --steps 3 --warmup 1 --cpu-sample 0 --pdb-sample 0 --mixed-chains 0 --e2e-files 0 --host-chains 0 > /tmp/ab.json 2> /tmp/ab.err || { echo "$lib $label FAILED" >> $OUT; tail -3 /tmp/ab.err >> $OUT; return; }
+  FCZ_HIP_LIB=$PWD/$lib python bench.py --full "$@" --steps 3 --warmup 1 --cpu-sample 0 --pdb-sample 0 --mixed-chains 0 --e2e-files 0 --host-chains 0 > /tmp/ab.json 2> /tmp/ab.err || { echo "$lib $label FAILED" >> $OUT; tail -3 /tmp/ab.err >> $OUT; return; }
   python - "$lib" "$label" >> $OUT <<'PY'
 import json, sys
 d = json.load(open("/tmp/ab.json")); k = d["roofline"]["kernel_ms"]; p = d.get("parity") or {}

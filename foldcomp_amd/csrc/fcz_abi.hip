@@ -1179,12 +1179,12 @@ int fcz_decompress_batch_dev(fcz_ctx* ctx, const uint8_t* blob_dev, const uint64
         // persistent grid: as many wavefronts as the chip keeps in flight (FCZ_BACKBONE_MIN_WAVES per SIMD), one ring slot each --
         // 2 048 x 107.5 KB = 220 MB at the headline batch whatever its size, and a slot is rewritten by the wavefront's next
         // group instead of being left behind dirty (one slot per group was 1.68 GB at 1 M chains)
-        const uint32_t resident = FCZ_BB_PERSIST ? (uint32_t)ctx->n_cu * 4u * FCZ_BACKBONE_MIN_WAVES : groups;
+        const uint32_t resident = (uint32_t)ctx->n_cu * 4u * FCZ_BACKBONE_MIN_WAVES;
         const uint32_t blocks0 = std::min(groups, resident);
         rc = ctx->fwd.ensure(sizeof(v3) * (size_t)std::max<uint32_t>(blocks0, 1) * slot_atoms + 64); if (rc) return rc;
         rc = ctx->wring.ensure(sizeof(float) * (size_t)std::max<uint32_t>(blocks0, 1) * slot_trig); if (rc) return rc;
         uint32_t* next_group = (uint32_t*)(ctx->fwd.as<uint8_t>() + sizeof(v3) * (size_t)std::max<uint32_t>(blocks0, 1) * slot_atoms);
-        if (FCZ_BB_PERSIST && groups) HIP_TRY(hipMemsetAsync(next_group, 0, sizeof(uint32_t), ctx->stream));
+        if (groups) HIP_TRY(hipMemsetAsync(next_group, 0, sizeof(uint32_t), ctx->stream));
         {
             span_guard g(ctx, "decompress_backbone");
             if (groups)
@@ -1388,48 +1388,3 @@ extern "C" int fcz_selftest_math(fcz_ctx* ctx, int mode, uint32_t start_bits, ui
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return FCZ_OK;
 }
-
-
-#ifdef FCZ_CW_TIMING
-// measurement aid: read and clear the phase counters of k_compress_angles_w
-extern "C" int fcz_debug_cw_timing(unsigned long long* out8) {
-    unsigned long long z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    if (hipDeviceSynchronize() != hipSuccess) return -1;
-    if (hipMemcpyFromSymbol(out8, HIP_SYMBOL(fcz::g_cw_timing), sizeof(z)) != hipSuccess) return -1;
-    if (hipMemcpyToSymbol(HIP_SYMBOL(fcz::g_cw_timing), z, sizeof(z)) != hipSuccess) return -1;
-    return 0;
-}
-#endif
-
-#ifdef FCZ_SC_TIMING
-// measurement aid: read and clear the phase counters of k_sidechain
-extern "C" int fcz_debug_sc_timing(unsigned long long* out12) {
-    unsigned long long z[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    if (hipDeviceSynchronize() != hipSuccess) return -1;
-    if (hipMemcpyFromSymbol(out12, HIP_SYMBOL(fcz::g_sc_timing), sizeof(z)) != hipSuccess) return -1;
-    if (hipMemcpyToSymbol(HIP_SYMBOL(fcz::g_sc_timing), z, sizeof(z)) != hipSuccess) return -1;
-    return 0;
-}
-#endif
-
-#ifdef FCZ_BB_TIMING
-// measurement aid: read and clear the phase counters of k_backbone<0>
-extern "C" int fcz_debug_bb_timing(unsigned long long* out8) {
-    unsigned long long z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    if (hipDeviceSynchronize() != hipSuccess) return -1;
-    if (hipMemcpyFromSymbol(out8, HIP_SYMBOL(fcz::g_bb_timing), sizeof(z)) != hipSuccess) return -1;
-    if (hipMemcpyToSymbol(HIP_SYMBOL(fcz::g_bb_timing), z, sizeof(z)) != hipSuccess) return -1;
-    return 0;
-}
-#endif
-
-#ifdef FCZ_IG_TIMING
-// measurement aid: read and clear the phase counters of k_ingest_parse
-extern "C" int fcz_debug_ig_timing(unsigned long long* out8) {
-    unsigned long long z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    if (hipDeviceSynchronize() != hipSuccess) return -1;
-    if (hipMemcpyFromSymbol(out8, HIP_SYMBOL(fcz::g_ig_timing), sizeof(z)) != hipSuccess) return -1;
-    if (hipMemcpyToSymbol(HIP_SYMBOL(fcz::g_ig_timing), z, sizeof(z)) != hipSuccess) return -1;
-    return 0;
-}
-#endif

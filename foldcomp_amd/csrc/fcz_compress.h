@@ -179,13 +179,46 @@ __global__ __launch_bounds__(BLOCK) void k_compress_index(fcz_chain_batch in, co
 // =====================================================================================================================
 // k_compress_angles
 // =====================================================================================================================
-struct alignas(16) compress_lds {
-    float4 atom[CK_CAP + 1];                    // {x, y, z, code bits}; [CK_ZERO] = zeros
-    uint16_t idx[FCZ_MAX_RES_ATOMS][CK_TILE + 8];   // [canonical slot][residue in tile] -> atom record (row CK_TILE.. = successor)
+// per-residue-code tables of both angle kernels, per block, read-only after init_residue_tables
+struct alignas(16) compress_tables_lds {
+    uint8_t slot_of[FCZ_N_RES_CODES][40];       // atom code -> canonical slot, 255 = not in residue
+    uint16_t prev[FCZ_N_RES_CODES][FCZ_MAX_RES_ATOMS];
+    uint8_t natoms[32];
     // Atom orders a residue is recognised in without a per-atom name lookup, per residue code, 16 bytes each:
     //   canon[j] = atom code of canonical slot j,  altc[j] = atom code at position j of the alternative order (what AlphaFold
     //   files and `decompress -a` use),  inv[sl] = position of canonical slot sl in the alternative order
     uint32_t ord_canon[FCZ_N_RES_CODES][4], ord_altc[FCZ_N_RES_CODES][4], ord_inv[FCZ_N_RES_CODES][4];
+};
+// the block's prologue: fills T from the constant tables; every thread of the block calls it, T is ready on return
+__device__ __forceinline__ void init_residue_tables(compress_tables_lds& T) {
+    const int t = threadIdx.x;
+    for (int i = t; i < FCZ_N_RES_CODES * 40; i += BLOCK) (&T.slot_of[0][0])[i] = 255;
+    if (t < 32) T.natoms[t] = fcz_res_natoms[t < 24 ? t : 23];
+    __syncthreads();
+    for (int i = t; i < FCZ_N_RES_CODES * FCZ_MAX_RES_ATOMS; i += BLOCK) {
+        const int rc = i / FCZ_MAX_RES_ATOMS, j = i % FCZ_MAX_RES_ATOMS;
+        if (j < fcz_res_natoms[rc]) T.slot_of[rc][fcz_res_atom[rc][j]] = (uint8_t)j;
+        T.prev[rc][j] = fcz_res_prev[rc][j];
+    }
+    if (t < FCZ_N_RES_CODES) {
+        const int rc = t, na = fcz_res_natoms[rc];
+        uint32_t can[4] = {0, 0, 0, 0}, alt[4] = {0, 0, 0, 0}, inv[4] = {0, 0, 0, 0};
+        for (int j = 0; j < 16; j++) {
+            const bool inr = j < na;
+            const uint32_t aj = inr ? fcz_res_alt_slot[rc][j] : 0u;
+            can[j >> 2] |= (inr ? (uint32_t)fcz_res_atom[rc][j] : 0xffu) << (8 * (j & 3));
+            alt[j >> 2] |= (inr ? (uint32_t)fcz_res_atom[rc][aj] : 0xffu) << (8 * (j & 3));
+            if (inr) inv[aj >> 2] |= (uint32_t)j << (8 * (aj & 3));
+        }
+        for (int d = 0; d < 4; d++) { T.ord_canon[rc][d] = can[d]; T.ord_altc[rc][d] = alt[d]; T.ord_inv[rc][d] = inv[d]; }
+    }
+    __syncthreads();
+}
+
+struct alignas(16) compress_lds {
+    float4 atom[CK_CAP + 1];                    // {x, y, z, code bits}; [CK_ZERO] = zeros
+    uint16_t idx[FCZ_MAX_RES_ATOMS][CK_TILE + 8];   // [canonical slot][residue in tile] -> atom record (row CK_TILE.. = successor)
+    compress_tables_lds T;
     unsigned long long sc_addr[CK_TILE];        // res_sc_addr of the tile's residues
     uint32_t olo[CK_TILE + 2];                  // atom_off of residues 0..CK_TILE+1 of the tile (clamped)
     uint16_t scpre[CK_TILE];                    // pass-local exclusive prefix of side-chain torsion counts
@@ -193,9 +226,6 @@ struct alignas(16) compress_lds {
     uint8_t item_res[CK_TILE * 11];             // side-chain item -> residue in tile
     uint32_t wave_tot[WAVES_PER_BLOCK];
     uint32_t first_bad;
-    uint8_t slot_of[FCZ_N_RES_CODES][40];       // atom code -> canonical slot, 255 = not in residue
-    uint16_t prev[FCZ_N_RES_CODES][FCZ_MAX_RES_ATOMS];
-    uint8_t natoms[32];
 };
 
 __device__ __forceinline__ v3 tile_atom(const compress_lds& L, uint32_t res, uint32_t slot) {
@@ -229,28 +259,8 @@ void k_compress_angles(fcz_chain_batch in, uint32_t n_tiles_all, const uint32_t*
     auto tile_of = [&](uint32_t k) -> uint32_t { return tile_list ? tile_list[k < n_tiles ? k : (n_tiles ? n_tiles - 1 : 0)] : k; };
     __shared__ compress_lds L;
     const int t = threadIdx.x, wave = t >> 6, lane = t & 63;
-    for (int i = t; i < FCZ_N_RES_CODES * 40; i += BLOCK) (&L.slot_of[0][0])[i] = 255;
-    if (t < 32) L.natoms[t] = fcz_res_natoms[t < 24 ? t : 23];
     if (t == 0) L.atom[CK_ZERO] = float4{0.f, 0.f, 0.f, 0.f};
-    __syncthreads();
-    for (int i = t; i < FCZ_N_RES_CODES * FCZ_MAX_RES_ATOMS; i += BLOCK) {
-        const int rc = i / FCZ_MAX_RES_ATOMS, j = i % FCZ_MAX_RES_ATOMS;
-        if (j < fcz_res_natoms[rc]) L.slot_of[rc][fcz_res_atom[rc][j]] = (uint8_t)j;
-        L.prev[rc][j] = fcz_res_prev[rc][j];
-    }
-    if (t < FCZ_N_RES_CODES) {
-        const int rc = t, na = fcz_res_natoms[rc];
-        uint32_t can[4] = {0, 0, 0, 0}, alt[4] = {0, 0, 0, 0}, inv[4] = {0, 0, 0, 0};
-        for (int j = 0; j < 16; j++) {
-            const bool in = j < na;
-            const uint32_t aj = in ? fcz_res_alt_slot[rc][j] : 0u;
-            can[j >> 2] |= (in ? (uint32_t)fcz_res_atom[rc][j] : 0xffu) << (8 * (j & 3));
-            alt[j >> 2] |= (in ? (uint32_t)fcz_res_atom[rc][aj] : 0xffu) << (8 * (j & 3));
-            if (in) inv[aj >> 2] |= (uint32_t)j << (8 * (aj & 3));
-        }
-        for (int d = 0; d < 4; d++) { L.ord_canon[rc][d] = can[d]; L.ord_altc[rc][d] = alt[d]; L.ord_inv[rc][d] = inv[d]; }
-    }
-    __syncthreads();
+    init_residue_tables(L.T);
 
     const uint32_t R = in.n_residues;
     const size_t Rz = R;
@@ -412,7 +422,7 @@ void k_compress_angles(fcz_chain_batch in, uint32_t n_tiles_all, const uint32_t*
                 // Known order? The residue's first natoms codes equal the canonical list or the alternative-order list (four
                 // dword compares each). Then slot sl sits at lo + sl, resp. lo + inv[sl]: fourteen stores, no per-atom lookup.
                 // Names are distinct within a residue type, so "first atom of each name" is exactly that whatever follows.
-                const uint32_t na = L.natoms[rc];
+                const uint32_t na = L.T.natoms[rc];
                 uint32_t pk[4] = {0u, 0u, 0u, 0u};
 #pragma unroll
                 for (int j = 0; j < 16; j++) pk[j >> 2] |= (codes[j] & 0xffu) << (8 * (j & 3));
@@ -421,20 +431,20 @@ void k_compress_angles(fcz_chain_batch in, uint32_t n_tiles_all, const uint32_t*
                 for (int d = 0; d < 4; d++) {
                     const int vb = (int)na - 4 * d;                                       // bytes of this dword that belong to the residue
                     const uint32_t m = vb >= 4 ? 0xffffffffu : (vb <= 0 ? 0u : (1u << (8 * vb)) - 1u);
-                    dc |= (pk[d] ^ L.ord_canon[rc][d]) & m; da |= (pk[d] ^ L.ord_altc[rc][d]) & m;
+                    dc |= (pk[d] ^ L.T.ord_canon[rc][d]) & m; da |= (pk[d] ^ L.T.ord_altc[rc][d]) & m;
                 }
                 const bool is_can = dc == 0u && hi - lo >= na, is_alt = da == 0u && hi - lo >= na;
                 if (is_can || is_alt) {
 #pragma unroll
                     for (int sl = 0; sl < FCZ_MAX_RES_ATOMS; sl++) {
-                        const uint32_t pos = is_can ? (uint32_t)sl : ((L.ord_inv[rc][sl >> 2] >> (8 * (sl & 3))) & 0xffu);
+                        const uint32_t pos = is_can ? (uint32_t)sl : ((L.T.ord_inv[rc][sl >> 2] >> (8 * (sl & 3))) & 0xffu);
                         L.idx[sl][rr] = (uint16_t)((uint32_t)sl < na ? lo + pos : (uint32_t)CK_ZERO);
                     }
                     continue;
                 }
                 uint32_t slots[16];
 #pragma unroll
-                for (int j = 0; j < 16; j++) slots[j] = (codes[j] < 40u) ? L.slot_of[rc][codes[j]] : 255u;
+                for (int j = 0; j < 16; j++) slots[j] = (codes[j] < 40u) ? L.T.slot_of[rc][codes[j]] : 255u;
                 // every slot starts at the zero record; then descending j, so that the first occurrence of a name is
                 // the write that lands last (LDS operations of one wave execute in issue order)
 #pragma unroll
@@ -447,7 +457,7 @@ void k_compress_angles(fcz_chain_batch in, uint32_t n_tiles_all, const uint32_t*
                 }
                 for (uint32_t i = lo + 16; i < hi; i++) {   // residues with more than 16 atoms (explicit hydrogens)
                     const uint32_t code = __float_as_uint(L.atom[i].w);
-                    const uint32_t sl = code < 40u ? L.slot_of[rc][code] : 255u;
+                    const uint32_t sl = code < 40u ? L.T.slot_of[rc][code] : 255u;
                     if (sl != 255u && !((filled >> sl) & 1u)) { filled |= 1u << sl; L.idx[sl][rr] = (uint16_t)i; }
                 }
             }
@@ -455,7 +465,7 @@ void k_compress_angles(fcz_chain_batch in, uint32_t n_tiles_all, const uint32_t*
             // ---- side-chain item numbering of the pass: block scan of the per-residue torsion counts ----
             const bool mine = (uint32_t)t >= s && (uint32_t)t < e;
             const bool my_win = mine && (L.sc_addr[t] & CK_LAST) == 0;
-            const uint32_t my_cnt = mine ? (uint32_t)L.natoms[L.rc[t]] - 3u : 0u;
+            const uint32_t my_cnt = mine ? (uint32_t)L.T.natoms[L.rc[t]] - 3u : 0u;
             uint32_t inc = my_cnt;
 #pragma unroll
             for (int d = 1; d < WAVE; d <<= 1) { const uint32_t u = __shfl_up(inc, d, WAVE); if (lane >= d) inc += u; }
@@ -481,11 +491,7 @@ void k_compress_angles(fcz_chain_batch in, uint32_t n_tiles_all, const uint32_t*
             // same bits; a bond angle's vectors a - b are the exact negatives of the dihedrals' b - a, and negation commutes
             // with every rounding involved), then the double part runs once per item (q uniform: one copy of its code).
             float bb0 = 0.f, bb1 = 0.f, bb2 = 0.f, bb3 = 0.f, bb4 = 0.f, bb5 = 0.f;
-#ifdef FCZ_ABL_NO_BB      // timing experiment only: the kernel without its backbone items
-            if (false) {
-#else
             if (my_win) {
-#endif
                 const v3 N0 = tile_atom(L, (uint32_t)t, 0), CA0 = tile_atom(L, (uint32_t)t, 1), C0 = tile_atom(L, (uint32_t)t, 2);
                 const v3 N1 = tile_atom(L, (uint32_t)t + 1u, 0), CA1 = tile_atom(L, (uint32_t)t + 1u, 1), C1 = tile_atom(L, (uint32_t)t + 1u, 2);
                 const v3 e0 = vsub(CA0, N0), e1 = vsub(C0, CA0), e2 = vsub(N1, C0), e3 = vsub(CA1, N1), e4 = vsub(C1, CA1);
@@ -517,14 +523,11 @@ void k_compress_angles(fcz_chain_batch in, uint32_t n_tiles_all, const uint32_t*
             for (uint32_t i = 0; i < 11; i++) {
                 const uint32_t ts = (uint32_t)t + i * BLOCK;
                 if (i * BLOCK >= n_sc) break;
-#ifdef FCZ_ABL_NO_SC      // timing experiment only: the kernel without its side-chain items
-                break;
-#endif
                 uint32_t q = 0;
                 if (ts < n_sc) {
                     const uint32_t res = L.item_res[ts];
                     const uint32_t j = 3 + ts - L.scpre[res];
-                    const uint32_t pk = L.prev[L.rc[res]][j];
+                    const uint32_t pk = L.T.prev[L.rc[res]][j];
                     const v3 a = tile_atom(L, res, pk & 15u), b = tile_atom(L, res, (pk >> 4) & 15u), cc = tile_atom(L, res, (pk >> 8) & 15u);
                     const v3 d = tile_atom(L, res, j);
                     q = sidechain_torsion_byte(a, b, cc, d) & 0xffu;   // src/foldcomp.cpp:532-538
@@ -598,12 +601,6 @@ struct alignas(16) compress_wave_lds {
     uint32_t sc_rel[CW_ROWS];                   // res_sc_addr of the row minus that of row 0
     uint8_t item_res[CW_RES * 11 + 11];         // side-chain item -> row
 };
-struct alignas(16) compress_tables_lds {        // per block, read-only after the prologue
-    uint8_t slot_of[FCZ_N_RES_CODES][40];
-    uint16_t prev[FCZ_N_RES_CODES][FCZ_MAX_RES_ATOMS];
-    uint8_t natoms[32];
-    uint32_t ord_canon[FCZ_N_RES_CODES][4], ord_altc[FCZ_N_RES_CODES][4], ord_inv[FCZ_N_RES_CODES][4];
-};
 
 // ordering point inside one wavefront: LDS operations of a wavefront execute in issue order, so all that is needed is that the
 // compiler keeps the memory operations on their side of it
@@ -620,13 +617,6 @@ __device__ __forceinline__ v3 wtile_rec(const compress_wave_lds& W, uint32_t lo,
     return v3{a.x, a.y, a.z};
 }
 
-#ifdef FCZ_CW_TIMING
-// measurement aid (not built into the product): wavefront-cycles spent between the phase boundaries of k_compress_angles_w
-__device__ unsigned long long g_cw_timing[8];
-#define CW_STAMP(i) { const unsigned long long now_ = __builtin_readcyclecounter(); tacc[i] += now_ - tlast; tlast = now_; }
-#else
-#define CW_STAMP(i)
-#endif
 __global__ __launch_bounds__(BLOCK, 3)
 void k_compress_angles_w(fcz_chain_batch in, uint32_t n_wtiles, const uint64_t* __restrict__ res_sc_addr, uint8_t* __restrict__ out,
                          float* __restrict__ ang, uint32_t* __restrict__ tile_flags, uint32_t* __restrict__ tile_list, uint32_t* __restrict__ tile_count,
@@ -634,27 +624,7 @@ void k_compress_angles_w(fcz_chain_batch in, uint32_t n_wtiles, const uint64_t* 
     __shared__ compress_wave_lds WL[WAVES_PER_BLOCK];
     __shared__ compress_tables_lds T;
     const int t = threadIdx.x, wave = t >> 6, lane = t & 63;
-    for (int i = t; i < FCZ_N_RES_CODES * 40; i += BLOCK) (&T.slot_of[0][0])[i] = 255;
-    if (t < 32) T.natoms[t] = fcz_res_natoms[t < 24 ? t : 23];
-    __syncthreads();
-    for (int i = t; i < FCZ_N_RES_CODES * FCZ_MAX_RES_ATOMS; i += BLOCK) {
-        const int rc = i / FCZ_MAX_RES_ATOMS, j = i % FCZ_MAX_RES_ATOMS;
-        if (j < fcz_res_natoms[rc]) T.slot_of[rc][fcz_res_atom[rc][j]] = (uint8_t)j;
-        T.prev[rc][j] = fcz_res_prev[rc][j];
-    }
-    if (t < FCZ_N_RES_CODES) {
-        const int rc = t, na = fcz_res_natoms[rc];
-        uint32_t can[4] = {0, 0, 0, 0}, alt[4] = {0, 0, 0, 0}, inv[4] = {0, 0, 0, 0};
-        for (int j = 0; j < 16; j++) {
-            const bool inr = j < na;
-            const uint32_t aj = inr ? fcz_res_alt_slot[rc][j] : 0u;
-            can[j >> 2] |= (inr ? (uint32_t)fcz_res_atom[rc][j] : 0xffu) << (8 * (j & 3));
-            alt[j >> 2] |= (inr ? (uint32_t)fcz_res_atom[rc][aj] : 0xffu) << (8 * (j & 3));
-            if (inr) inv[aj >> 2] |= (uint32_t)j << (8 * (aj & 3));
-        }
-        for (int d = 0; d < 4; d++) { T.ord_canon[rc][d] = can[d]; T.ord_altc[rc][d] = alt[d]; T.ord_inv[rc][d] = inv[d]; }
-    }
-    __syncthreads();                             // the only block-level synchronisation of the kernel
+    init_residue_tables(T);                      // the only block-level synchronisation of the kernel
 
     compress_wave_lds& W = WL[wave];
     const uint32_t R = in.n_residues;
@@ -672,9 +642,6 @@ void k_compress_angles_w(fcz_chain_batch in, uint32_t n_wtiles, const uint64_t* 
     };
     const uint32_t wt0 = blockIdx.x * WAVES_PER_BLOCK + (uint32_t)wave;
     wmeta cur = load_meta(wt0 < n_wtiles ? wt0 : 0u), nxt = cur;
-#ifdef FCZ_CW_TIMING
-    unsigned long long tacc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tlast = __builtin_readcyclecounter();
-#endif
     for (uint32_t wt = wt0; wt < n_wtiles; wt += n_waves, cur = nxt) {
         const uint32_t r_lo = wt * CW_RES;
         const size_t r = (size_t)r_lo + (size_t)lane;
@@ -697,7 +664,6 @@ void k_compress_angles_w(fcz_chain_batch in, uint32_t n_wtiles, const uint64_t* 
             continue;
         }
         wave_sync();          // the previous tile's last LDS reads are issued before anything is overwritten
-        CW_STAMP(0)
         // ---- stage: atoms of the tile (record per lane and round), codes (dword of four per lane and round) ----
         const uint32_t rc = (in_r && rc_g < 24u) ? rc_g : 23u;
         const uint32_t lo = olo_g - a0, hi = ohi_g - a0;
@@ -751,7 +717,6 @@ void k_compress_angles_w(fcz_chain_batch in, uint32_t n_wtiles, const uint64_t* 
                 if ((nonfinite_f32(a.x) | nonfinite_f32(a.y) | nonfinite_f32(a.z)) && code8[i] != 255u) flag_nonfinite_atom(in, a0 + i, nonfinite);
             }
         }
-        CW_STAMP(1)
         // ---- slot table row of this lane's residue ----
         const uint32_t na = T.natoms[rc];
         uint32_t row0;        // positions of N, CA, C (bytes 0..2)
@@ -806,7 +771,6 @@ void k_compress_angles_w(fcz_chain_batch in, uint32_t n_wtiles, const uint64_t* 
         for (uint32_t j = 0; j < my_cnt; j++) W.item_res[my_pre + j] = (uint8_t)lane;
         const uint32_t row0_next = (uint32_t)__shfl_down((int)row0, 1, WAVE);
         wave_sync();
-        CW_STAMP(2)
         // ---- backbone items of the window (this row, next row): shared ingredients as in k_compress_angles ----
         float bb0 = 0.f, bb1 = 0.f, bb2 = 0.f, bb3 = 0.f, bb4 = 0.f, bb5 = 0.f;
         if (my_win) {
@@ -833,7 +797,6 @@ void k_compress_angles_w(fcz_chain_batch in, uint32_t n_wtiles, const uint64_t* 
             float* ap = ang + r;
             ap[0] = bb0; ap[Rz] = bb1; ap[2 * Rz] = bb2; ap[3 * Rz] = bb3; ap[4 * Rz] = bb4; ap[5 * Rz] = bb5;
         }
-        CW_STAMP(3)
         // ---- side-chain torsion bytes: flat item list, lane = item; each byte leaves as soon as it exists (consecutive items
         //      are consecutive bytes of the record's side-chain section) ----
 #pragma unroll FCZ_CW_UNROLL_SC
@@ -852,12 +815,135 @@ void k_compress_angles_w(fcz_chain_batch in, uint32_t n_wtiles, const uint64_t* 
                 out[base0 + W.sc_rel[res] + jj] = (uint8_t)sidechain_torsion_byte(a, b, cc, d);
             }
         }
-        CW_STAMP(4)
-        CW_STAMP(5)
     }
-#ifdef FCZ_CW_TIMING
-    if (lane == 0) for (int i = 0; i < 8; i++) atomicAdd(&g_cw_timing[i], tacc[i]);
-#endif
+}
+
+// ---- the FCZ record of one chain: the pieces both pack kernels write it with; the reductions between them are the callers' ----
+// Chain-level validation (the reference aborts on these inputs), FCZ_E_* codes in order of precedence. nResidue is a uint16 and
+// nAnchor a uint8 in the header (src/foldcomp.h:120-125): the reference would write wrapped values. Non-finite: flag_nonfinite_atom.
+__device__ __forceinline__ int check_chain(uint32_t c, uint32_t n, uint32_t thr, const uint32_t* __restrict__ nonfinite) {
+    int bad = (n < 2) ? FCZ_E_TOO_SHORT : (thr < 1 ? FCZ_E_INVALID_ARG : 0);
+    if (!bad && (n > 65535u || n / thr + 2u > 255u)) bad = FCZ_E_INVALID_ARG;
+    if (!bad && ((nonfinite[c >> 5] >> (c & 31u)) & 1u)) bad = FCZ_E_NONFINITE;
+    return bad;
+}
+// One residue (span = atoms of it and its successor, bf = CA B-factor): the lane's first failure stays in `bad`; -> side-chain torsions
+__device__ __forceinline__ uint32_t check_residue(int& bad, uint32_t rc, uint32_t span, float bf) {
+    if (!res_code_ok(rc)) bad = bad ? bad : FCZ_E_RESIDUE;
+    // a residue and its successor must fit the staging buffer of k_compress_angles (not a protein otherwise)
+    if (span > (uint32_t)CK_CAP) bad = bad ? bad : FCZ_E_INVALID_ARG;
+    if (nonfinite_f32(bf)) bad = bad ? bad : FCZ_E_NONFINITE;
+    return fcz_res_natoms[rc < 24 ? rc : 23] - 3;
+}
+
+// Anchor sl of a chain of n residues from residue r0 (Foldcomp::_setAnchor src/foldcomp.cpp:745-761, written :1045-1059): N, CA,
+// C are the first atoms of those names in the residue. keep: the bond angle of the first anchor goes to *keep_at.
+__device__ __forceinline__ void write_anchor(const fcz_chain_batch& in, uint32_t r0, uint32_t n, uint32_t n_anchor, uint32_t interval,
+                                             uint32_t sl, uint8_t* rec, const rec_layout& RL, bool keep, float* keep_at) {
+    const uint32_t k = (sl + 1 < n_anchor) ? sl * interval : n - 1;
+    const uint32_t lo = in.atom_off[r0 + k], hi = in.atom_off[r0 + k + 1];
+    // the first 8 atom codes in one batch of loads (N, CA, C lead every residue of a normal file); a serial scan
+    // with one dependent load per atom only when a name is still missing after those
+    uint32_t at[3] = {0xffffffffu, 0xffffffffu, 0xffffffffu};
+    uint32_t codes[8];
+#pragma unroll
+    for (int j = 0; j < 8; j++) codes[j] = (lo + j < hi) ? (uint32_t)in.atom_code[lo + j] : 255u;
+#pragma unroll
+    for (int j = 7; j >= 0; j--) {
+        at[0] = codes[j] == 0u ? lo + j : at[0];
+        at[1] = codes[j] == 1u ? lo + j : at[1];
+        at[2] = codes[j] == 2u ? lo + j : at[2];
+    }
+    if (__builtin_expect(at[0] == 0xffffffffu || at[1] == 0xffffffffu || at[2] == 0xffffffffu, 0)) {
+        for (uint32_t i = lo + 8; i < hi; i++) {
+            const uint32_t code = in.atom_code[i];
+            if (code == 0u && at[0] == 0xffffffffu) at[0] = i;
+            if (code == 1u && at[1] == 0xffffffffu) at[1] = i;
+            if (code == 2u && at[2] == 0xffffffffu) at[2] = i;
+        }
+    }
+    v3 p[3];
+#pragma unroll
+    for (int q = 0; q < 3; q++) {
+        const bool have = at[q] != 0xffffffffu;
+        const uint32_t i = have ? at[q] : lo;   // any valid index; masked below
+        const bool ok = have && lo < hi;
+        p[q] = ok ? v3{in.x[i], in.y[i], in.z[i]} : v3{0.f, 0.f, 0.f};
+    }
+    uint8_t* q = rec + RL.o_anchor + 36 * sl;
+    st_f32(q, p[0].x); st_f32(q + 4, p[0].y); st_f32(q + 8, p[0].z);
+    st_f32(q + 12, p[1].x); st_f32(q + 16, p[1].y); st_f32(q + 20, p[1].z);
+    st_f32(q + 24, p[2].x); st_f32(q + 28, p[2].y); st_f32(q + 32, p[2].z);
+    st_u32(rec + RL.o_aidx + 4 * sl, k);
+    if (keep) *keep_at = bond_angle_deg(p[0], p[1], p[2]);
+}
+
+struct quant7 { float min[7], disc[7], cont[7]; };   // Discretizer (src/discretizer.cpp:22-33) of arrays 0..5 (angles), 6 (B-factors)
+// Quantiser q from the array's extrema (lo, hi: std::min_element / max_element, the callers' reductions) and its element 0 (first).
+// Those start from element 0 and replace it only when a comparison says so: a NaN there stays (nothing compares below or above it),
+// a NaN anywhere else is never picked -- which is what fminf / fmaxf reductions give. A NaN at the head is minimum and maximum at
+// once, and x86-64 hands its bits through the subtraction and the division (NaN - NaN = the first operand, quiet already): the
+// record's header holds those bits twice (acos_deg_exact makes them: negative from a NaN cosine, positive from one beyond +-1).
+__device__ __forceinline__ void finish_quant(quant7& Q, int q, float first, float lo, float hi) {
+    const float nbins[7] = {4095.0f, 4095.0f, 2047.0f, 255.0f, 255.0f, 255.0f, 255.0f};
+    Q.min[q] = lo; Q.disc[q] = nbins[q] / (hi - lo); Q.cont[q] = (hi - lo) / nbins[q];
+    if (__builtin_expect(first != first, 0)) { Q.min[q] = first; Q.disc[q] = first; Q.cont[q] = first; }
+}
+
+// Residue k of a chain of m + 1 (src/foldcomp.cpp:582-601, convertBackboneChainToBytes :33-52): the packed 8-byte word (residue
+// code, the six backbone angles of window k; the last residue has no window) and the B-factor byte
+__device__ __forceinline__ void write_residue(uint8_t* rec, const rec_layout& RL, const quant7& Q, uint32_t k, uint32_t m, uint32_t res,
+                                              float v0, float v1, float v2, float v3_, float v4, float v5, float v6) {
+    uint32_t om = 0, ps = 0, ph = 0, b1 = 0, b2 = 0, b3 = 0;
+    if (k < m) {
+        ph = quant_round(v0, Q.min[0], Q.disc[0]) & 0xfffu;
+        ps = quant_round(v1, Q.min[1], Q.disc[1]) & 0xfffu;
+        om = quant_round(v2, Q.min[2], Q.disc[2]) & 0x7ffu;
+        b3 = quant_round(v3_, Q.min[3], Q.disc[3]) & 0xffu;
+        b1 = quant_round(v4, Q.min[4], Q.disc[4]) & 0xffu;
+        b2 = quant_round(v5, Q.min[5], Q.disc[5]) & 0xffu;
+    }
+    const uint32_t w0 = ((res & 0x1fu) << 3) | (om >> 8), w1 = om & 0xffu, w2 = ps >> 4,
+                   w3 = ((ps & 0xfu) << 4) | (ph >> 8), w4 = ph & 0xffu;
+    const uint64_t word = (uint64_t)w0 | ((uint64_t)w1 << 8) | ((uint64_t)w2 << 16) | ((uint64_t)w3 << 24) |
+                          ((uint64_t)w4 << 32) | ((uint64_t)b1 << 40) | ((uint64_t)b2 << 48) | ((uint64_t)b3 << 56);
+    st_u64(rec + RL.o_words + 8 * (size_t)k, word);
+    rec[RL.o_tbytes + k] = (uint8_t)quant_round(v6, Q.min[6], Q.disc[6]);
+}
+
+// the header's inputs, loaded by the callers ahead of the angle work
+struct chain_head { int32_t first_res, first_atom; char chain; uint32_t a_first, a_end, rc_first, rc_last; };
+// Header (CompressedFileHeader src/foldcomp.h:118-136; get_header src/foldcomp.cpp:1340), OXT (src/foldcomp.cpp:474-482: the last
+// atom of the span), the B-factor quantiser, status FCZ_OK
+__device__ __forceinline__ void write_header(const fcz_chain_batch& in, uint32_t c, uint32_t n, uint32_t n_anchor, uint32_t nsc, uint32_t title_len,
+                                             const chain_head& H, const quant7& Q, uint8_t* rec, const rec_layout& RL, int32_t* __restrict__ status) {
+    rec[0] = 'F'; rec[1] = 'C'; rec[2] = 'M'; rec[3] = 'P';
+    uint8_t* h = rec + 4;
+    st_u16(h + 0, n);
+    st_u16(h + 2, H.a_end - H.a_first);
+    st_u16(h + 4, (uint32_t)H.first_res);
+    st_u16(h + 6, (uint32_t)H.first_atom);
+    h[8] = (uint8_t)n_anchor;
+    h[9] = (uint8_t)H.chain;
+    h[10] = 0; h[11] = 0;  // struct padding: the reference leaves it uninitialised
+    st_u32(h + 12, nsc);
+    h[16] = (uint8_t)fcz_res1[H.rc_first];
+    h[17] = (uint8_t)fcz_res1[H.rc_last];
+    h[18] = 0; h[19] = 0;
+    st_u32(h + 20, title_len);
+    // a NaN among the angle parameters is the NaN of the chain's first angle, carried unchanged (finish_quant)
+#pragma unroll
+    for (int q = 0; q < 6; q++) { st_f32(h + 24 + 4 * q, Q.min[q]); st_f32(h + 48 + 4 * q, Q.cont[q]); }
+    const uint32_t la = H.a_end - 1;
+    const bool has_oxt = H.a_end > H.a_first && in.atom_code[la] == FCZ_ATOM_OXT;
+    uint8_t* o = rec + RL.o_oxt;
+    o[0] = has_oxt ? 1 : 0;
+    st_f32(o + 1, has_oxt ? in.x[la] : 0.0f);
+    st_f32(o + 5, has_oxt ? in.y[la] : 0.0f);
+    st_f32(o + 9, has_oxt ? in.z[la] : 0.0f);
+    st_f32(rec + RL.o_tmp, Q.min[6]);
+    st_f32(rec + RL.o_tmp + 4, Q.cont[6]);
+    if (status) status[c] = FCZ_OK;
 }
 
 // =====================================================================================================================
@@ -876,10 +962,8 @@ __device__ __forceinline__ void compress_pack_chain(const fcz_chain_batch& in, c
     const uint32_t thr = (uint32_t)in.anchor_threshold;
     uint8_t* rec = out + out_off[c];
     const uint32_t rec_size = (uint32_t)(out_off[c + 1] - out_off[c]);
-    const int32_t h_first_res = in.first_res_index[c], h_first_atom = in.first_atom_index[c];
-    const char h_chain = in.chain_id[c];
-    const uint32_t a_first = in.atom_off[r0], a_end = in.atom_off[r0 + n];
-    const uint32_t h_rc_first = n ? in.res_code[r0] : 23u, h_rc_last = n ? in.res_code[r0 + n - 1] : 23u;
+    const chain_head H{in.first_res_index[c], in.first_atom_index[c], in.chain_id[c],
+                       in.atom_off[r0], in.atom_off[r0 + n], n ? in.res_code[r0] : 23u, n ? in.res_code[r0 + n - 1] : 23u};
 
     // ---- every load of a normal chain (<= 384 residues) is issued here, unconditionally and from clamped indices, so
     //      that validation, anchors and quantisation do not each pay a memory round trip ----
@@ -915,27 +999,15 @@ __device__ __forceinline__ void compress_pack_chain(const fcz_chain_batch& in, c
         }
     }
 
-    // ---- validation (the reference aborts on these inputs) + total side-chain torsion count ----
-    int bad = (n < 2) ? FCZ_E_TOO_SHORT : (thr < 1 ? FCZ_E_INVALID_ARG : 0);
-    // nResidue is a uint16 and nAnchor a uint8 in the header (src/foldcomp.h:120-125): a chain beyond them would get a record
-    // whose layout uses the full values and whose header holds wrapped ones (the reference writes exactly that, unreadable)
-    if (!bad && (n > 65535u || n / thr + 2u > 255u)) bad = FCZ_E_INVALID_ARG;
+    // ---- validation + total side-chain torsion count ----
+    int bad = check_chain(c, n, thr, nonfinite);
     uint32_t nsc = 0;
-    // a non-finite coordinate of a named atom (found by the angle kernels) or CA B-factor: refused, see flag_nonfinite_atom
-    if (!bad && ((nonfinite[c >> 5] >> (c & 31u)) & 1u)) bad = FCZ_E_NONFINITE;
-    auto check = [&](uint32_t rc, uint32_t span, float bf) {
-        if (!res_code_ok(rc)) bad = bad ? bad : FCZ_E_RESIDUE;
-        // a residue and its successor must fit the staging buffer of k_compress_angles (not a protein otherwise)
-        if (span > (uint32_t)CK_CAP) bad = bad ? bad : FCZ_E_INVALID_ARG;
-        if (nonfinite_f32(bf)) bad = bad ? bad : FCZ_E_NONFINITE;
-        nsc += fcz_res_natoms[rc < 24 ? rc : 23] - 3;
-    };
     if (small) {
 #pragma unroll
-        for (int u = 0; u < U; u++) if ((uint32_t)(u * WAVE + lane) < n) check(rcs[u], o2[u] - o0[u], va[6][u]);
+        for (int u = 0; u < U; u++) if ((uint32_t)(u * WAVE + lane) < n) nsc += check_residue(bad, rcs[u], o2[u] - o0[u], va[6][u]);
     } else if (U > 1) {
         for (uint32_t k = lane; k < n; k += WAVE)
-            check(in.res_code[r0 + k], in.atom_off[r0 + (k + 2 < n ? k + 2 : n)] - in.atom_off[r0 + k], in.bfac_ca[r0 + k]);
+            nsc += check_residue(bad, in.res_code[r0 + k], in.atom_off[r0 + (k + 2 < n ? k + 2 : n)] - in.atom_off[r0 + k], in.bfac_ca[r0 + k]);
     }
 #pragma unroll
     for (int d = WAVE / 2; d > 0; d >>= 1) { int o = __shfl_xor(bad, d, WAVE); bad = o < bad ? o : bad; }
@@ -950,78 +1022,17 @@ __device__ __forceinline__ void compress_pack_chain(const fcz_chain_batch& in, c
     const uint32_t interval = n / (n_anchor - 1);
     const rec_layout RL = make_layout(n, n_anchor, title_len, nsc);
 
-    // ---- anchors (Foldcomp::_setAnchor src/foldcomp.cpp:745-761, written :1045-1059): one lane per anchor; N, CA, C are
-    //      the first atoms of those names in the residue ----
-    for (uint32_t sl = lane; sl < n_anchor; sl += WAVE) {
-        const uint32_t k = (sl + 1 < n_anchor) ? sl * interval : n - 1;
-        const uint32_t lo = in.atom_off[r0 + k], hi = in.atom_off[r0 + k + 1];
-        // the first 8 atom codes in one batch of loads (N, CA, C lead every residue of a normal file); a serial scan
-        // with one dependent load per atom only when a name is still missing after those
-        uint32_t at[3] = {0xffffffffu, 0xffffffffu, 0xffffffffu};
-        uint32_t codes[8];
-#pragma unroll
-        for (int j = 0; j < 8; j++) codes[j] = (lo + j < hi) ? (uint32_t)in.atom_code[lo + j] : 255u;
-#pragma unroll
-        for (int j = 7; j >= 0; j--) {
-            at[0] = codes[j] == 0u ? lo + j : at[0];
-            at[1] = codes[j] == 1u ? lo + j : at[1];
-            at[2] = codes[j] == 2u ? lo + j : at[2];
-        }
-        if (__builtin_expect((at[0] & at[1] & at[2]) == 0xffffffffu || at[0] == 0xffffffffu || at[1] == 0xffffffffu || at[2] == 0xffffffffu, 0)) {
-            for (uint32_t i = lo + 8; i < hi; i++) {
-                const uint32_t code = in.atom_code[i];
-                if (code == 0u && at[0] == 0xffffffffu) at[0] = i;
-                if (code == 1u && at[1] == 0xffffffffu) at[1] = i;
-                if (code == 2u && at[2] == 0xffffffffu) at[2] = i;
-            }
-        }
-        v3 p[3];
-#pragma unroll
-        for (int q = 0; q < 3; q++) {
-            const bool have = at[q] != 0xffffffffu;
-            const uint32_t i = have ? at[q] : lo;   // any valid index; masked below
-            const bool ok = have && lo < hi;
-            p[q] = ok ? v3{in.x[i], in.y[i], in.z[i]} : v3{0.f, 0.f, 0.f};
-        }
-        uint8_t* q = rec + RL.o_anchor + 36 * sl;
-        st_f32(q, p[0].x); st_f32(q + 4, p[0].y); st_f32(q + 8, p[0].z);
-        st_f32(q + 12, p[1].x); st_f32(q + 16, p[1].y); st_f32(q + 20, p[1].z);
-        st_f32(q + 24, p[2].x); st_f32(q + 28, p[2].y); st_f32(q + 32, p[2].z);
-        st_u32(rec + RL.o_aidx + 4 * sl, k);
-        if (keep_first_angle && sl == 0) a_arr[3 * R + (n - 1)] = bond_angle_deg(p[0], p[1], p[2]);
-    }
+    // ---- anchors: one lane per anchor ----
+    for (uint32_t sl = lane; sl < n_anchor; sl += WAVE)
+        write_anchor(in, r0, n, n_anchor, interval, sl, rec, RL, keep_first_angle && sl == 0, a_arr + 3 * R + (n - 1));
 
-    // ---- per-chain quantiser parameters (Discretizer::Discretizer src/discretizer.cpp:22-33), then the
-    //      packed words (src/foldcomp.cpp:582-601, convertBackboneChainToBytes :33-52) + B-factor bytes ----
+    // ---- per-chain quantiser parameters, then the packed words + B-factor bytes ----
     const float kInf = __builtin_huge_valf();
-    float qmin[7], qdisc[7], qcont[7];
-    const float nbins[7] = {4095.0f, 4095.0f, 2047.0f, 255.0f, 255.0f, 255.0f, 255.0f};
-    auto pack_store = [&](uint32_t k, uint32_t res, float v0, float v1, float v2, float v3_, float v4, float v5, float v6) {
-        uint32_t om = 0, ps = 0, ph = 0, b1 = 0, b2 = 0, b3 = 0;
-        if (k < m) {
-            ph = quant_round(v0, qmin[0], qdisc[0]) & 0xfffu;
-            ps = quant_round(v1, qmin[1], qdisc[1]) & 0xfffu;
-            om = quant_round(v2, qmin[2], qdisc[2]) & 0x7ffu;
-            b3 = quant_round(v3_, qmin[3], qdisc[3]) & 0xffu;
-            b1 = quant_round(v4, qmin[4], qdisc[4]) & 0xffu;
-            b2 = quant_round(v5, qmin[5], qdisc[5]) & 0xffu;
-        }
-        const uint32_t w0 = ((res & 0x1fu) << 3) | (om >> 8), w1 = om & 0xffu, w2 = ps >> 4,
-                       w3 = ((ps & 0xfu) << 4) | (ph >> 8), w4 = ph & 0xffu;
-        const uint64_t word = (uint64_t)w0 | ((uint64_t)w1 << 8) | ((uint64_t)w2 << 16) | ((uint64_t)w3 << 24) |
-                              ((uint64_t)w4 << 32) | ((uint64_t)b1 << 40) | ((uint64_t)b2 << 48) | ((uint64_t)b3 << 56);
-        st_u64(rec + RL.o_words + 8 * (size_t)k, word);
-        rec[RL.o_tbytes + k] = (uint8_t)quant_round(v6, qmin[6], qdisc[6]);
-    };
-    // first = element 0 of the array (wave-uniform). std::min_element / max_element start from it and replace it only when a
-    // comparison says so: a NaN there stays (nothing compares below or above it), a NaN anywhere else is never picked -- which is
-    // what the fminf / fmaxf reductions give
+    quant7 Q;
+    // std::min_element / max_element keep the first of equal elements: only when an extremum is a zero does that need the positions
     auto finish_q = [&](int q, float first, float lo, float hi, const float* src, uint32_t cntq, int mode) {
         if (__builtin_expect(lo == 0.0f || hi == 0.0f, 0)) { const lo_hi e = first_extrema(src, cntq, lane, mode); lo = e.lo; hi = e.hi; }
-        qmin[q] = lo; qdisc[q] = nbins[q] / (hi - lo); qcont[q] = (hi - lo) / nbins[q];
-        // a NaN at the head is minimum and maximum at once, and x86-64 hands its bits through the subtraction and the division
-        // (NaN - NaN = the first operand, quiet already): the record's header holds those bits twice (acos_deg_exact makes them)
-        if (__builtin_expect(first != first, 0)) { qmin[q] = first; qdisc[q] = first; qcont[q] = first; }
+        finish_quant(Q, q, first, lo, hi);
     };
     if (small) {
         // everything of the chain is in registers already: no reload for the quantisation pass
@@ -1050,7 +1061,7 @@ __device__ __forceinline__ void compress_pack_chain(const fcz_chain_batch& in, c
 #pragma unroll
         for (int u = 0; u < U; u++) {
             const uint32_t k = u * WAVE + lane;
-            if (k < n) pack_store(k, rcs[u], va[0][u], va[1][u], va[2][u], va[3][u], va[4][u], va[5][u], va[6][u]);
+            if (k < n) write_residue(rec, RL, Q, k, m, rcs[u], va[0][u], va[1][u], va[2][u], va[3][u], va[4][u], va[5][u], va[6][u]);
             __builtin_amdgcn_sched_barrier(0);   // one word at a time: interleaving all of them only inflates the live set
         }
     } else if (U > 1) {
@@ -1102,7 +1113,7 @@ __device__ __forceinline__ void compress_pack_chain(const fcz_chain_batch& in, c
             for (int u = 0; u < U; u++) {
                 if (b0 + (uint32_t)(u * WAVE) >= n) continue;
                 const uint32_t k = b0 + u * WAVE + lane;
-                if (k < n) pack_store(k, rcs[u], va[0][u], va[1][u], va[2][u], va[3][u], va[4][u], va[5][u], va[6][u]);
+                if (k < n) write_residue(rec, RL, Q, k, m, rcs[u], va[0][u], va[1][u], va[2][u], va[3][u], va[4][u], va[5][u], va[6][u]);
                 __builtin_amdgcn_sched_barrier(0);
             }
         }
@@ -1110,41 +1121,8 @@ __device__ __forceinline__ void compress_pack_chain(const fcz_chain_batch& in, c
 
     for (uint32_t i = lane; i < title_len; i += WAVE) rec[RL.o_title + i] = (uint8_t)in.titles[in.title_off[c] + i];
 
-    // ---- header (CompressedFileHeader src/foldcomp.h:118-136; get_header src/foldcomp.cpp:1340) ----
-    if (lane == 0) {
-        rec[0] = 'F'; rec[1] = 'C'; rec[2] = 'M'; rec[3] = 'P';
-        uint8_t* h = rec + 4;
-        st_u16(h + 0, n);
-        st_u16(h + 2, a_end - a_first);
-        st_u16(h + 4, (uint32_t)h_first_res);
-        st_u16(h + 6, (uint32_t)h_first_atom);
-        h[8] = (uint8_t)n_anchor;
-        h[9] = (uint8_t)h_chain;
-        h[10] = 0; h[11] = 0;  // struct padding: the reference leaves it uninitialised
-        st_u32(h + 12, nsc);
-        h[16] = (uint8_t)fcz_res1[h_rc_first];
-        h[17] = (uint8_t)fcz_res1[h_rc_last];
-        h[18] = 0; h[19] = 0;
-        st_u32(h + 20, title_len);
-        // a NaN among the angle parameters is the NaN of the chain's first angle with the bits x86-64 / glibc give it (acos_deg_exact:
-        // negative from a NaN cosine, positive from a cosine beyond +-1), carried unchanged through the quantiser (finish_q)
-        auto x86_nan = [](float v) { return v; };
-#pragma unroll
-        for (int q = 0; q < 6; q++) { st_f32(h + 24 + 4 * q, x86_nan(qmin[q])); st_f32(h + 48 + 4 * q, x86_nan(qcont[q])); }
-        // OXT (src/foldcomp.cpp:474-482): the last atom of the span
-        const uint32_t la = a_end - 1;
-        const bool has_oxt = a_end > a_first && in.atom_code[la] == FCZ_ATOM_OXT;
-        uint8_t* o = rec + RL.o_oxt;
-        o[0] = has_oxt ? 1 : 0;
-        st_f32(o + 1, has_oxt ? in.x[la] : 0.0f);
-        st_f32(o + 5, has_oxt ? in.y[la] : 0.0f);
-        st_f32(o + 9, has_oxt ? in.z[la] : 0.0f);
-        st_f32(rec + RL.o_tmp, qmin[6]);
-        st_f32(rec + RL.o_tmp + 4, qcont[6]);
-        if (status) status[c] = FCZ_OK;
-    }
+    if (lane == 0) write_header(in, c, n, n_anchor, nsc, title_len, H, Q, rec, RL, status);
 }
-
 
 // =====================================================================================================================
 // Several short chains per wavefront: one chain per G-lane group (G = 16: a DPP row, four chains to a wavefront)
@@ -1154,7 +1132,8 @@ __device__ __forceinline__ void compress_pack_chain(const fcz_chain_batch& in, c
 // chain's length. Here the lanes of a group carry their own chain's scalars, so that cost is shared by the four chains of the
 // wavefront; the reductions stay inside a group (four DPP steps cover a row of 16). A chain longer than the group takes several
 // rounds of G residues (lane sub holds residues sub, sub + G, ...): every chain of up to 64 residues goes four to a wavefront.
-// Same arithmetic, same order, same first-occurrence rules as compress_pack_chain (the results are the same bits).
+// The record is written by the same pieces as compress_pack_chain's; only the reductions are the group's own, with the same
+// first-occurrence rules (the results are the same bits).
 template <int G> __device__ __forceinline__ float grp_min_f32(float v) {
     v = __builtin_fminf(v, dpp_f32<0xB1, 0xf>(v)); v = __builtin_fminf(v, dpp_f32<0x4E, 0xf>(v));
     v = __builtin_fminf(v, dpp_f32<0x141, 0xf>(v)); v = __builtin_fminf(v, dpp_f32<0x140, 0xf>(v));
@@ -1202,12 +1181,10 @@ __device__ __forceinline__ void compress_pack_rows(const fcz_chain_batch& in, co
     const uint32_t thr = (uint32_t)in.anchor_threshold;
     uint8_t* rec = out + out_off[c];
     const uint32_t rec_size = (uint32_t)(out_off[c + 1] - out_off[c]);
-    const int32_t h_first_res = in.first_res_index[c], h_first_atom = in.first_atom_index[c];
-    const char h_chain = in.chain_id[c];
     const size_t R = in.n_residues;
-    const uint32_t a_first = in.atom_off[r0], a_end = in.atom_off[r0 + n];
     const uint32_t rl = r0 + (n ? n - 1 : 0);
-    const uint32_t h_rc_first = in.res_code[r0 < R ? r0 : R - 1], h_rc_last = in.res_code[rl < R ? rl : R - 1];
+    const chain_head H{in.first_res_index[c], in.first_atom_index[c], in.chain_id[c],
+                       in.atom_off[r0], in.atom_off[r0 + n], in.res_code[r0 < R ? r0 : R - 1], in.res_code[rl < R ? rl : R - 1]};
     const uint32_t m = n ? n - 1 : 0;
     float* a_arr = ang + (r0 < R ? r0 : (R ? R - 1 : 0));
     // ---- the group's values: every load issued up front from clamped indices ----
@@ -1232,21 +1209,11 @@ __device__ __forceinline__ void compress_pack_rows(const fcz_chain_batch& in, co
         va[3][u] = dec_angle<3>(va[3][u]); va[4][u] = dec_angle<4>(va[4][u]); va[5][u] = dec_angle<5>(va[5][u]);
     }
 
-    // ---- validation, as compress_pack_chain orders it ----
-    int bad = (n < 2) ? FCZ_E_TOO_SHORT : (thr < 1 ? FCZ_E_INVALID_ARG : 0);
-    if (!bad && (n > 65535u || n / thr + 2u > 255u)) bad = FCZ_E_INVALID_ARG;
-    if (!bad && ((nonfinite[c >> 5] >> (c & 31u)) & 1u)) bad = FCZ_E_NONFINITE;
+    // ---- validation + total side-chain torsion count ----
+    int bad = check_chain(c, n, thr, nonfinite);
     uint32_t nsc = 0;
 #pragma unroll
-    for (int u = 0; u < U; u++) {
-        const uint32_t k = (uint32_t)u * G + sub;
-        if (k < n) {
-            if (!res_code_ok(rcs[u])) bad = bad ? bad : FCZ_E_RESIDUE;
-            if (o2[u] - o0[u] > (uint32_t)CK_CAP) bad = bad ? bad : FCZ_E_INVALID_ARG;
-            if (nonfinite_f32(va[6][u])) bad = bad ? bad : FCZ_E_NONFINITE;
-            nsc += fcz_res_natoms[rcs[u] < 24 ? rcs[u] : 23] - 3;
-        }
-    }
+    for (int u = 0; u < U; u++) if ((uint32_t)u * G + sub < n) nsc += check_residue(bad, rcs[u], o2[u] - o0[u], va[6][u]);
     bad = grp_min_i32<G>(bad);
     nsc = grp_sum_u32<G>(nsc);
     {
@@ -1260,49 +1227,13 @@ __device__ __forceinline__ void compress_pack_rows(const fcz_chain_batch& in, co
     const uint32_t interval = n / (n_anchor - 1);
     const rec_layout RL = make_layout(n, n_anchor, title_len, nsc);
 
-    // ---- anchors (Foldcomp::_setAnchor src/foldcomp.cpp:745-761, written :1045-1059): one lane per anchor ----
-    for (uint32_t sl = sub; __any(on && sl < n_anchor); sl += G) {
-        if (!(on && sl < n_anchor)) continue;
-        const uint32_t ka = (sl + 1 < n_anchor) ? sl * interval : n - 1;
-        const uint32_t lo = in.atom_off[r0 + ka], hi = in.atom_off[r0 + ka + 1];
-        uint32_t at[3] = {0xffffffffu, 0xffffffffu, 0xffffffffu};
-        uint32_t codes[8];
-#pragma unroll
-        for (int j = 0; j < 8; j++) codes[j] = (lo + j < hi) ? (uint32_t)in.atom_code[lo + j] : 255u;
-#pragma unroll
-        for (int j = 7; j >= 0; j--) {
-            at[0] = codes[j] == 0u ? lo + j : at[0];
-            at[1] = codes[j] == 1u ? lo + j : at[1];
-            at[2] = codes[j] == 2u ? lo + j : at[2];
-        }
-        if (__builtin_expect(at[0] == 0xffffffffu || at[1] == 0xffffffffu || at[2] == 0xffffffffu, 0)) {
-            for (uint32_t i = lo + 8; i < hi; i++) {
-                const uint32_t code = in.atom_code[i];
-                if (code == 0u && at[0] == 0xffffffffu) at[0] = i;
-                if (code == 1u && at[1] == 0xffffffffu) at[1] = i;
-                if (code == 2u && at[2] == 0xffffffffu) at[2] = i;
-            }
-        }
-        v3 p[3];
-#pragma unroll
-        for (int q = 0; q < 3; q++) {
-            const bool have = at[q] != 0xffffffffu;
-            const uint32_t i = have ? at[q] : lo;
-            const bool ok = have && lo < hi;
-            p[q] = ok ? v3{in.x[i], in.y[i], in.z[i]} : v3{0.f, 0.f, 0.f};
-        }
-        uint8_t* q = rec + RL.o_anchor + 36 * sl;
-        st_f32(q, p[0].x); st_f32(q + 4, p[0].y); st_f32(q + 8, p[0].z);
-        st_f32(q + 12, p[1].x); st_f32(q + 16, p[1].y); st_f32(q + 20, p[1].z);
-        st_f32(q + 24, p[2].x); st_f32(q + 28, p[2].y); st_f32(q + 32, p[2].z);
-        st_u32(rec + RL.o_aidx + 4 * sl, ka);
-        if (keep_first_angle && sl == 0) a_arr[3 * R + (n - 1)] = bond_angle_deg(p[0], p[1], p[2]);
-    }
+    // ---- anchors: one lane per anchor ----
+    for (uint32_t sl = sub; __any(on && sl < n_anchor); sl += G)
+        if (on && sl < n_anchor) write_anchor(in, r0, n, n_anchor, interval, sl, rec, RL, keep_first_angle && sl == 0, a_arr + 3 * R + (n - 1));
 
-    // ---- per-chain quantiser parameters (Discretizer::Discretizer src/discretizer.cpp:22-33) ----
+    // ---- per-chain quantiser parameters ----
     const float kInf = __builtin_huge_valf();
-    float qmin[7], qdisc[7], qcont[7];
-    const float nbins[7] = {4095.0f, 4095.0f, 2047.0f, 255.0f, 255.0f, 255.0f, 255.0f};
+    quant7 Q;
 #pragma unroll
     for (int q = 0; q < 7; q++) {
         const uint32_t cntq = (q < 6) ? m : n;
@@ -1324,12 +1255,9 @@ __device__ __forceinline__ void compress_pack_rows(const fcz_chain_batch& in, co
             const lo_hi e = grp_first_extrema<G>(mn, mx);
             if (lo == 0.0f || hi == 0.0f) { lo = e.lo; hi = e.hi; }
         }
-        qmin[q] = lo; qdisc[q] = nbins[q] / (hi - lo); qcont[q] = (hi - lo) / nbins[q];
-        // a NaN at the head is minimum and maximum at once, and x86-64 hands its bits through the subtraction and the division
-        // (NaN - NaN = the first operand, quiet already): the record's header holds those bits twice (acos_deg_exact makes them)
-        if (__builtin_expect(first != first, 0)) { qmin[q] = first; qdisc[q] = first; qcont[q] = first; }
+        finish_quant(Q, q, first, lo, hi);
     }
-    // ---- the packed words (src/foldcomp.cpp:582-601, convertBackboneChainToBytes :33-52) + B-factor bytes ----
+    // ---- the packed words + B-factor bytes ----
 #pragma unroll
     for (int u = 0; u < U; u++) {
         const uint32_t k = (uint32_t)u * G + sub;
@@ -1337,59 +1265,14 @@ __device__ __forceinline__ void compress_pack_rows(const fcz_chain_batch& in, co
 #pragma unroll
             for (int q = 0; q < 6; q++) a_arr[(size_t)q * R + k] = va[q][u];
         }
-        if (on && k < n) {
-            uint32_t om = 0, ps = 0, ph = 0, b1 = 0, b2 = 0, b3 = 0;
-            if (k < m) {
-                ph = quant_round(va[0][u], qmin[0], qdisc[0]) & 0xfffu;
-                ps = quant_round(va[1][u], qmin[1], qdisc[1]) & 0xfffu;
-                om = quant_round(va[2][u], qmin[2], qdisc[2]) & 0x7ffu;
-                b3 = quant_round(va[3][u], qmin[3], qdisc[3]) & 0xffu;
-                b1 = quant_round(va[4][u], qmin[4], qdisc[4]) & 0xffu;
-                b2 = quant_round(va[5][u], qmin[5], qdisc[5]) & 0xffu;
-            }
-            const uint32_t w0 = ((rcs[u] & 0x1fu) << 3) | (om >> 8), w1 = om & 0xffu, w2 = ps >> 4,
-                           w3 = ((ps & 0xfu) << 4) | (ph >> 8), w4 = ph & 0xffu;
-            const uint64_t word = (uint64_t)w0 | ((uint64_t)w1 << 8) | ((uint64_t)w2 << 16) | ((uint64_t)w3 << 24) |
-                                  ((uint64_t)w4 << 32) | ((uint64_t)b1 << 40) | ((uint64_t)b2 << 48) | ((uint64_t)b3 << 56);
-            st_u64(rec + RL.o_words + 8 * (size_t)k, word);
-            rec[RL.o_tbytes + k] = (uint8_t)quant_round(va[6][u], qmin[6], qdisc[6]);
-        }
+        if (on && k < n) write_residue(rec, RL, Q, k, m, rcs[u], va[0][u], va[1][u], va[2][u], va[3][u], va[4][u], va[5][u], va[6][u]);
     }
     {
         const uint32_t tlim = on ? title_len : 0u;
         const uint32_t t0 = in.title_off[c];
         for (uint32_t i = sub; __any(i < tlim); i += G) if (i < tlim) rec[RL.o_title + i] = (uint8_t)in.titles[t0 + i];
     }
-    // ---- header (CompressedFileHeader src/foldcomp.h:118-136; get_header src/foldcomp.cpp:1340) ----
-    if (on && sub == 0) {
-        rec[0] = 'F'; rec[1] = 'C'; rec[2] = 'M'; rec[3] = 'P';
-        uint8_t* h = rec + 4;
-        st_u16(h + 0, n);
-        st_u16(h + 2, a_end - a_first);
-        st_u16(h + 4, (uint32_t)h_first_res);
-        st_u16(h + 6, (uint32_t)h_first_atom);
-        h[8] = (uint8_t)n_anchor;
-        h[9] = (uint8_t)h_chain;
-        h[10] = 0; h[11] = 0;
-        st_u32(h + 12, nsc);
-        h[16] = (uint8_t)fcz_res1[h_rc_first];
-        h[17] = (uint8_t)fcz_res1[h_rc_last];
-        h[18] = 0; h[19] = 0;
-        st_u32(h + 20, title_len);
-        auto x86_nan = [](float v) { return v; };          // (the bits acos_deg_exact gave the chain's first angle: see k_compress_pack)
-#pragma unroll
-        for (int q = 0; q < 6; q++) { st_f32(h + 24 + 4 * q, x86_nan(qmin[q])); st_f32(h + 48 + 4 * q, x86_nan(qcont[q])); }
-        const uint32_t la = a_end - 1;
-        const bool has_oxt = a_end > a_first && in.atom_code[la] == FCZ_ATOM_OXT;
-        uint8_t* o = rec + RL.o_oxt;
-        o[0] = has_oxt ? 1 : 0;
-        st_f32(o + 1, has_oxt ? in.x[la] : 0.0f);
-        st_f32(o + 5, has_oxt ? in.y[la] : 0.0f);
-        st_f32(o + 9, has_oxt ? in.z[la] : 0.0f);
-        st_f32(rec + RL.o_tmp, qmin[6]);
-        st_f32(rec + RL.o_tmp + 4, qcont[6]);
-        if (status) status[c] = FCZ_OK;
-    }
+    if (on && sub == 0) write_header(in, c, n, n_anchor, nsc, title_len, H, Q, rec, RL, status);
 }
 
 // Chains of 2 .. CP_SHORT residues belong to k_compress_pack_rows, everything else (incl. what is refused) to k_compress_pack.
@@ -1397,9 +1280,6 @@ __device__ __forceinline__ void compress_pack_rows(const fcz_chain_batch& in, co
 #define FCZ_PACK_ROWS_MAX_ROUNDS 8     // chains of up to 16 x this many residues go four to a wavefront (8: up to 128; 202 VGPRs for that class)
 #endif
 constexpr uint32_t CP_SHORT = 16u * FCZ_PACK_ROWS_MAX_ROUNDS;
-#ifndef FCZ_PACK_CLASSES
-#define FCZ_PACK_CLASSES 1
-#endif
 
 
 __global__ __launch_bounds__(BLOCK, 3) void k_compress_pack(fcz_chain_batch in, const uint64_t* __restrict__ out_off, uint8_t* __restrict__ out,
@@ -1410,13 +1290,10 @@ __global__ __launch_bounds__(BLOCK, 3) void k_compress_pack(fcz_chain_batch in, 
     if (c >= in.n_chains) return;
     const uint32_t r0 = in.res_off[c], n = in.res_off[c + 1] - r0;
     if (n >= 2 && n <= CP_SHORT) return;                      // k_compress_pack_rows'
-#if FCZ_PACK_CLASSES
     // rounds of 64 residues held in registers, by length class (wave-uniform): a 100-residue chain does not issue the loads,
     // reductions and stores of a 350-residue one
     if (n <= 4u * WAVE) compress_pack_chain<4>(in, c, r0, n, out_off, out, status, ang, keep_first_angle, nonfinite);
-    else
-#endif
-    compress_pack_chain<6>(in, c, r0, n, out_off, out, status, ang, keep_first_angle, nonfinite);
+    else compress_pack_chain<6>(in, c, r0, n, out_off, out, status, ang, keep_first_angle, nonfinite);
 }
 
 // Short chains (2 .. CP_SHORT residues: peptides, fragments, the low end of a metagenomic set). One wavefront per chain costs a

@@ -42,11 +42,7 @@ constexpr uint32_t CRC_POLY = 0xEDB88320u;       // CRC-32 (RFC 1952 section 8),
 
 // status of a member (0 = inflated and verified); everything else: the caller's zlib decides (fcz_hip.h FCZ_INFLATE_*)
 constexpr int32_t ST_OK = 0, ST_HEADER = 1, ST_BLOCK = 2, ST_CODE = 3, ST_SIZE = 4, ST_INPUT = 5, ST_CHECK = 6;
-#ifdef FCZ_INFLATE_DEBUG
-#define INF_FAIL(code) ((code) | (__LINE__ << 8))    // where the member was refused (tests print it)
-#else
 #define INF_FAIL(code) (code)
-#endif
 
 // ---- CRC-32 arithmetic in the reflected representation (x^0 = 0x80000000; multiplying by x = one shift right) ----
 constexpr uint32_t crc_xstep(uint32_t v) { return (v >> 1) ^ ((v & 1u) ? CRC_POLY : 0u); }
@@ -329,9 +325,6 @@ struct sink {
         crc = crc_mul(xr, crc) ^ r;                                 // (the first round multiplies a zero)
     }
     __device__ __forceinline__ void flush_one() {                   // q - flushed >= ROUND
-#ifdef FCZ_INFLATE_ABL_NOFLUSH
-        flushed += ROUND; return;     // measurement build: nothing leaves the ring, no CRC
-#endif
         if (flushed >= q0) round<true>(flushed, flushed + ROUND); else round<false>(flushed, flushed + ROUND);
         flushed += ROUND;
     }
@@ -346,9 +339,6 @@ struct sink {
 __device__ __forceinline__ void lz_copy(sink& sk, lds_t& L, uint32_t lane, uint32_t p, uint32_t len, uint32_t dist, uint32_t reach) {
     const uint32_t src = p - dist;
     wave_fence();
-#ifdef FCZ_INFLATE_ABL_NOFAR
-    reach = 0xffffffffu;              // measurement build: every match through the ring (wrong text beyond its reach; the time is the answer)
-#endif
     if (__builtin_expect(dist <= reach, 1)) {
         if (__builtin_expect(len <= 64u && dist >= len, 1)) {
             uint8_t v = 0;
@@ -465,13 +455,7 @@ __device__ __forceinline__ int32_t decode_body(const bitreader& br, sink& sk, ld
         const uint32_t ld = len | (dist << 9);
         const uint32_t pos = sk.q + ex;
         const bool okm = !is_len || (dist >= ex + len && dist <= pos - sk.q0);
-#if defined(FCZ_INFLATE_ABL_NOCOPY)
-        if (false) {
-#elif defined(FCZ_INFLATE_ABL_ALLBYTE)
-        if (true) {                   // measurement build: every window takes the lane = byte form (wrong text beyond its conditions)
-#else
         if (__builtin_expect(tot <= 64u && __ballot(mine && !okm) == 0ull, 1)) {
-#endif
             L.own[lane] = 0;
             wave_fence();
             if (mine && ex < 64u) L.own[ex] = (uint8_t)(lane + 1u);
@@ -480,11 +464,7 @@ __device__ __forceinline__ int32_t decode_body(const bitreader& br, sink& sk, ld
             const uint32_t old = (uint32_t)__shfl((int)ld, (int)k, WAVE), oe = (uint32_t)__shfl((int)e, (int)k, WAVE);
             const uint32_t od = old >> 9;
             const bool act = lane < tot, omatch = ((oe >> 6) & 3u) == 1u;
-#ifdef FCZ_INFLATE_ABL_NOFAR
-            const bool isfar = false;
-#else
             const bool isfar = act && omatch && od > REACH;
-#endif
             const uint64_t fm = __ballot(isfar);
             if (fm) {
                 // (rounds this wavefront stored: acknowledged at vmcnt(0). Every lane loads -- the others the member's first byte --
@@ -501,9 +481,6 @@ __device__ __forceinline__ int32_t decode_body(const bitreader& br, sink& sk, ld
         } else {
             if (mine && !is_len) L.ring[pos & RMASK] = (uint8_t)(e >> 8);
             uint64_t mm = on & __ballot(is_len);
-#ifdef FCZ_INFLATE_ABL_NOCOPY
-            mm = 0;                   // measurement build: no match is copied (wrong text; the time is the answer)
-#endif
             while (mm) {
                 const uint32_t k = (uint32_t)__builtin_ctzll(mm);
                 mm &= mm - 1ull;

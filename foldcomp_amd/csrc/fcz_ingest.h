@@ -206,13 +206,6 @@ struct ingest_lds {
 };
 __device__ __forceinline__ uint32_t ig_hash(uint32_t k) { return (k * 0x9E3779B1u) >> 24; }
 
-#ifdef FCZ_IG_TIMING
-// measurement aid (not built into the product): wavefront-cycles in the parts of k_ingest_parse
-__device__ unsigned long long g_ig_timing[8];
-#define IG_STAMP(i) { const unsigned long long now_ = __builtin_readcyclecounter(); tacc[i] += now_ - tlast; tlast = now_; }
-#else
-#define IG_STAMP(i)
-#endif
 // ---- k_ingest_parse --------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(WAVE) void k_ingest_parse(const uint8_t* __restrict__ text, const uint64_t* __restrict__ file_off, uint32_t n_files,
                                                        uint64_t text_bytes, const uint64_t* __restrict__ abase, ingest_scratch T,
@@ -247,9 +240,6 @@ __global__ __launch_bounds__(WAVE) void k_ingest_parse(const uint8_t* __restrict
         return -1;
     };
 
-#ifdef FCZ_IG_TIMING
-    unsigned long long tacc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tlast = __builtin_readcyclecounter();
-#endif
     const uint64_t f0 = file_off[f], f1 = file_off[f + 1];
     const uint8_t* base = text + f0;
     const uint64_t flen = f1 - f0;
@@ -521,7 +511,6 @@ __global__ __launch_bounds__(WAVE) void k_ingest_parse(const uint8_t* __restrict
         }
     };
     load_chunk(0);
-    IG_STAMP(0)
     // (a file that is marked for the host is not read any further: nothing of it is used)
     for (uint64_t c0 = 0; c0 < flen && !ended && status == FCZ_OK; c0 += IG_CHUNK) {
         // ---- stage the chunk: the tail of the previous window moves to the front, then the chunk's 16 coalesced dwords per lane,
@@ -537,7 +526,6 @@ __global__ __launch_bounds__(WAVE) void k_ingest_parse(const uint8_t* __restrict
             c0_staged = c0;
             load_chunk(c0 + IG_CHUNK);                                         // the next chunk is on its way
         }
-        IG_STAMP(1)
         // ---- line ends of the chunk: every lane looks at its 64 staged bytes ----
         const uint64_t my = c0 + 64ull * (uint64_t)lane;     // file-relative start of this lane's 64 bytes
         // one bit per byte: the 0x80 flags of a dword's four bytes are gathered into a nibble by one multiplication
@@ -570,7 +558,6 @@ __global__ __launch_bounds__(WAVE) void k_ingest_parse(const uint8_t* __restrict
         if (__any(nul != 0u)) status = FCZ_INGEST_HOST_FIELD;
         uint32_t total;
         uint32_t ord = wave_excl_scan_dpp(cnt, &total);
-        IG_STAMP(2)
         // chunks with more line ends than the table holds (blank-line runs) go through it in rounds
         for (uint32_t r0 = 0; r0 < total || r0 == 0; r0 += IG_LINES) {
             uint32_t o = ord;
@@ -580,7 +567,6 @@ __global__ __launch_bounds__(WAVE) void k_ingest_parse(const uint8_t* __restrict
                 o++;
             }
             __builtin_amdgcn_wave_barrier();
-            IG_STAMP(3)
             const uint32_t n_here = total - r0 < (uint32_t)IG_LINES ? total - r0 : (uint32_t)IG_LINES;
             for (uint32_t k0 = 0; k0 < n_here; k0 += WAVE) {
                 const uint32_t k = k0 + (uint32_t)lane;
@@ -592,7 +578,6 @@ __global__ __launch_bounds__(WAVE) void k_ingest_parse(const uint8_t* __restrict
             }
             if (n_here) line_start = c0 + S.line_end[n_here - 1] + 1;
             __builtin_amdgcn_wave_barrier();
-            IG_STAMP(4)
             if (total == 0) break;
         }
     }
@@ -609,10 +594,6 @@ __global__ __launch_bounds__(WAVE) void k_ingest_parse(const uint8_t* __restrict
         n_kept[f] = status == FCZ_OK ? kept : 0u;
         file_status[f] = status;
     }
-#ifdef FCZ_IG_TIMING
-    IG_STAMP(5)
-    if (lane == 0) for (int i = 0; i < 8; i++) atomicAdd(&g_ig_timing[i], tacc[i]);
-#endif
 }
 
 // ---- k_ingest_frags -----------------------------------------------------------------------------------------------------

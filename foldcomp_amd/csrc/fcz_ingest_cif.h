@@ -64,12 +64,6 @@ struct cif_lds {
     int8_t pos[CIF_NCOL + 1];
 };
 
-#ifdef FCZ_CIF_TIMING
-// measurement aid (not built into the product): wavefront-cycles in the parts of k_ingest_parse_cif, in g_ig_timing (FCZ_IG_TIMING)
-#define CIF_STAMP(i) { const unsigned long long now_ = __builtin_readcyclecounter(); tacc[i] += now_ - tlast; tlast = now_; }
-#else
-#define CIF_STAMP(i)
-#endif
 __device__ __forceinline__ bool cif_is_ws(uint32_t c) { return c == ' ' || c == '\t' || c == '\r'; }
 __device__ __forceinline__ uint32_t cif_lower(uint32_t c) { return (c - 'A' < 26u) ? c + 32u : c; }
 
@@ -103,9 +97,6 @@ __global__ __launch_bounds__(WAVE) void k_ingest_parse_cif(const uint8_t* __rest
     if (lane <= CIF_NCOL) S.pos[lane] = -1;
     __builtin_amdgcn_wave_barrier();
 
-#ifdef FCZ_CIF_TIMING
-    unsigned long long tacc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tlast = __builtin_readcyclecounter();
-#endif
     const uint64_t A0 = abase[f];
     const uint32_t cap = (uint32_t)(abase[f + 1] - A0);
     uint8_t* tbuf = titles + (size_t)f * IG_TITLE_CAP;
@@ -200,7 +191,6 @@ __global__ __launch_bounds__(WAVE) void k_ingest_parse_cif(const uint8_t* __rest
                 }
             }
         }
-        CIF_STAMP(3)
         // (b) token bounds: a token starts where a character follows a blank (or the line's start), ends at the next blank. With a
         //     token's start in a register its first characters are fetched at once (two tokens per round trip) and looked at:
         //     a quote opens a string (the character-by-character lexer takes the line), '#' a comment, '$' a frame reference, '_' a
@@ -246,7 +236,6 @@ __global__ __launch_bounds__(WAVE) void k_ingest_parse_cif(const uint8_t* __rest
             if (comment) { ntok = 0; slow = false; bad = false; tag_like = 0; kw_first = 0; }   // (what a comment holds is nobody's business)
             else if (ntok > (uint32_t)CIF_MAXTOK) slow = true;              // (the character-by-character lexer counts any number of tokens)
         }
-        CIF_STAMP(4)
         // (d) the character-by-character lexer for the lines that hold a quoted string (or more tokens than the table)
         if (__any(slow && !bad)) {
             if (slow && !bad) {
@@ -298,7 +287,6 @@ __global__ __launch_bounds__(WAVE) void k_ingest_parse_cif(const uint8_t* __rest
         if (bad) cls = CL_BAD;
         if (__any(cls == CL_BAD)) { dead = true; return; }
         in_text = in_text ^ ((__builtin_popcountll(m_semi) & 1) != 0);
-        CIF_STAMP(5)
         // ---- 2. the grammar over the step's lines, in order (uniform) ----
         unsigned long long rowmask = 0;
         const unsigned long long m_on = __ballot(on);
@@ -406,7 +394,6 @@ __global__ __launch_bounds__(WAVE) void k_ingest_parse_cif(const uint8_t* __rest
                 if (in_as) { dead = true; break; }
             }
         }
-        CIF_STAMP(6)
         if (dead) return;
         // ---- 3. the _atom_site rows of the step leave as row records: where the line starts, the bounds of the fourteen fields ----
         if (rowmask == 0ull) return;
@@ -443,7 +430,6 @@ __global__ __launch_bounds__(WAVE) void k_ingest_parse_cif(const uint8_t* __rest
             }
         }
         nrows += n_new;
-        CIF_STAMP(7)
     };
 
     // ---- the chunk walk of k_ingest_parse: coalesced loads a chunk ahead, staged in LDS behind the previous chunk's tail ----
@@ -460,7 +446,6 @@ __global__ __launch_bounds__(WAVE) void k_ingest_parse_cif(const uint8_t* __rest
         }
     };
     load_chunk(0);
-    CIF_STAMP(0)
     uint64_t c0 = 0;
     for (; c0 < flen && !dead; c0 += IG_CHUNK) {
         {
@@ -474,7 +459,6 @@ __global__ __launch_bounds__(WAVE) void k_ingest_parse_cif(const uint8_t* __rest
             c0_staged = c0;
             load_chunk(c0 + IG_CHUNK);
         }
-        CIF_STAMP(1)
         const uint64_t my = c0 + 64ull * (uint64_t)lane;
         uint32_t nl_lo = 0, nl_hi = 0, z_lo = 0, z_hi = 0;
         {
@@ -517,7 +501,6 @@ __global__ __launch_bounds__(WAVE) void k_ingest_parse_cif(const uint8_t* __rest
                 const uint64_t le = on ? c0 + S.line_end[k] : 0;
                 const uint64_t ls = on ? (k == 0 ? line_start : c0 + S.line_end[k - 1] + 1) : 0;
                 const long long rel = (long long)ls - (long long)c0;
-                CIF_STAMP(2)
                 do_lines(on, ls, le, (on && rel >= -(long long)IG_BACK) ? (int)(IG_BACK + rel) : -1);
             }
             if (n_here) line_start = c0 + S.line_end[n_here - 1] + 1;
@@ -540,9 +523,6 @@ __global__ __launch_bounds__(WAVE) void k_ingest_parse_cif(const uint8_t* __rest
         title_len[f] = tlen;
         cif_rows[f] = nrows + 1u;                                          // the file's status stays "to the host" until its rows are read
     }
-#ifdef FCZ_CIF_TIMING
-    if (lane == 0) for (int i = 0; i < 8; i++) atomicAdd(&g_ig_timing[i], tacc[i]);
-#endif
 }
 
 // ---- the rows of the files k_ingest_parse_cif took: wavefront = file, lane = row record ----

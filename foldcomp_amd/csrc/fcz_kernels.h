@@ -533,9 +533,6 @@ __global__ __launch_bounds__(1024) void k_sizes_apply(const uint32_t* __restrict
 #ifndef FCZ_BACKBONE_MIN_WAVES
 #define FCZ_BACKBONE_MIN_WAVES 2
 #endif
-#ifndef FCZ_BB_PERSIST
-#define FCZ_BB_PERSIST 1
-#endif
 // Backbone reconstruction, one wavefront per group of 64 consecutive entries, lane = chain.
 // Reference: segment loop of Foldcomp::decompress (src/foldcomp.cpp:814-858): per anchor segment a forward
 // NeRF (reconstructBackboneAtoms :167-246), then reconstructBackboneReverse (:248-273: bond angles re-measured
@@ -561,26 +558,6 @@ struct backbone_lds {
 //         torsion trig of segment s parked in ring slot (group, s);
 // MODE 2: one block per (group, segment): reverse pass + blend of that segment from its slot -- the segments of a chain
 //         run side by side.
-#ifdef FCZ_BB_TIMING
-// measurement aid (not built into the product): wavefront-cycles in the parts of k_backbone
-__device__ unsigned long long g_bb_timing[8];
-#define BB_STAMP(i) { const unsigned long long now_ = __builtin_readcyclecounter(); tacc[i] += now_ - tlast; tlast = now_; }
-#else
-#define BB_STAMP(i)
-#endif
-// Measurement builds (results wrong by design, the time is the answer; profiles/r6_ab_ring_ablation.txt): the same instruction stream
-// with the ring rows folded into a window of a few rows per wavefront that stays in the L2 -- FCZ_ABL_NO_RING: forward atoms and
-// torsion trig; FCZ_ABL_NO_TRING: the trig ring only. What k_backbone would gain if its 120 B/residue of ring traffic cost nothing.
-#if defined(FCZ_ABL_NO_RING)
-#define BB_RROW(x) ((x) & 7)
-#define BB_TROW(x) ((x) & 15)
-#elif defined(FCZ_ABL_NO_TRING)
-#define BB_RROW(x) (x)
-#define BB_TROW(x) ((x) & 15)
-#else
-#define BB_RROW(x) (x)
-#define BB_TROW(x) (x)
-#endif
 // one group of 64 chains (lane = chain) of k_backbone; `home` = the ring slot of a MODE 0 wavefront (its block index: the grid is
 // persistent, so the ring is as large as the wavefronts in flight, not as the batch)
 template <int MODE>
@@ -590,9 +567,6 @@ __device__ __forceinline__ void backbone_group(
         const uint32_t* __restrict__ res_off, const uint32_t* __restrict__ perm, v3* __restrict__ ring,
         float* __restrict__ tring, uint32_t ring_rows, uint32_t seg_slots, v3* __restrict__ bb) {
     const int lane = threadIdx.x;
-#ifdef FCZ_BB_TIMING
-    unsigned long long tacc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tlast = __builtin_readcyclecounter();
-#endif
     const uint32_t slot = grp * WAVE + lane;
     const uint32_t c = slot < n_slots ? perm[slot] : n_entries;   // chains grouped by length, longest first
     const bool valid = c < n_entries && res_off[c + 1] != res_off[c];
@@ -645,7 +619,6 @@ __device__ __forceinline__ void backbone_group(
     long long win = -1;           // window index (chain-major atom index / BW) this lane is filling, -1 = none
     int w_lo = 0, w_hi = 0;       // filled slots [w_lo, w_hi) of that window (registers; published to LDS at a flush)
     auto flush = [&]() {
-        BB_STAMP(3)
         S.lo[lane] = w_lo; S.hi[lane] = w_hi;
         __builtin_amdgcn_wave_barrier();
 #pragma unroll 4
@@ -660,7 +633,6 @@ __device__ __forceinline__ void backbone_group(
         __builtin_amdgcn_wave_barrier();
         w_lo = 0; w_hi = 0;
         win = -1;
-        BB_STAMP(4)
     };
     auto emit = [&](bool on, long long bi, v3 a) {       // every lane calls (wave-uniform control flow)
         const long long w = on ? bi / BW : win;
@@ -673,7 +645,6 @@ __device__ __forceinline__ void backbone_group(
         }
     };
     const uint32_t s_begin = (MODE == 2) ? seg_only : 0u, s_end = (MODE == 2) ? seg_only + 1 : maxseg;
-    BB_STAMP(0)
     for (uint32_t s = s_begin; s < s_end; s++) {
         const bool act = s < nseg;
         const int len = act ? next - first + 1 : 0;
@@ -692,7 +663,6 @@ __device__ __forceinline__ void backbone_group(
             A0 = ld_v3(anc); A1 = ld_v3(anc + 12); A2 = ld_v3(anc + 24);   // next anchor: carry + reverse start
             if (MODE != 2) { Rg[0] = p0; Rg[WAVE] = p1; Rg[2 * WAVE] = p2; }
         }
-        BB_STAMP(1)
         // ---- forward NeRF of the segment ----
         // (ANY: a chain of the wavefront has quantiser parameters that can make an angle of 120 radians or more -- a record no
         //  compressor writes --: the same step with the sine / cosine that takes any float, any_wild is wave-uniform)
@@ -704,13 +674,13 @@ __device__ __forceinline__ void backbone_group(
             float s_psi, c_psi, s_om, c_om, s_phi, c_phi;
             if (ANY) { sincosf_pair_any(deg2rad(w.psi), &s_psi, &c_psi); sincosf_pair_any(deg2rad(w.omega), &s_om, &c_om); sincosf_pair_any(deg2rad(w.phi), &s_phi, &c_phi); }
             else { sincosf_pair(deg2rad(w.psi), &s_psi, &c_psi); sincosf_pair(deg2rad(w.omega), &s_om, &c_om); sincosf_pair(deg2rad(w.phi), &s_phi, &c_phi); }
-            float* Tw = Tg + (size_t)BB_TROW(6 * i) * WAVE;
+            float* Tw = Tg + (size_t)(6 * i) * WAVE;
             Tw[0] = c_psi; Tw[WAVE] = s_psi; Tw[2 * WAVE] = c_om; Tw[3 * WAVE] = s_om; Tw[4 * WAVE] = c_phi; Tw[5 * WAVE] = s_phi;
             const v3 N = place_atom_d2(p0, p1, p2, nerf_d2_trig_t<ANY>((float)1.3311, w.can, c_psi, s_psi));
             const float l_nca = (w.res != FCZ_RES_PRO) ? (float)1.4581 : (float)1.353;  // src/foldcomp.cpp:204-212
             const v3 CA = place_atom_d2(p1, p2, N, nerf_d2_trig_t<ANY>(l_nca, w.cna, c_om, s_om));
             const v3 C = place_atom_d2(p2, N, CA, nerf_d2_trig_t<ANY>((float)1.5281, w.nca, c_phi, s_phi));
-            Rg[(size_t)BB_RROW(3 * i + 3) * WAVE] = N; Rg[(size_t)BB_RROW(3 * i + 4) * WAVE] = CA; Rg[(size_t)BB_RROW(3 * i + 5) * WAVE] = C;
+            Rg[(size_t)(3 * i + 3) * WAVE] = N; Rg[(size_t)(3 * i + 4) * WAVE] = CA; Rg[(size_t)(3 * i + 5) * WAVE] = C;
             p0 = N; p1 = CA; p2 = C;
             w_cur = w_nxt; w_nxt = w_pre; wp += 8;
         };
@@ -718,7 +688,6 @@ __device__ __forceinline__ void backbone_group(
             if (i + 1 >= len) continue;
             if (__builtin_expect(any_wild, 0)) forward_step(i, std::true_type{}); else forward_step(i, std::false_type{});
         }
-        BB_STAMP(2)
         // ---- reverse NeRF + blend of the same segment ----
         const int T = 3 * len;
         const float Tf = (float)T;
@@ -742,8 +711,8 @@ __device__ __forceinline__ void backbone_group(
         v3 fa{0.f, 0.f, 0.f}, fb = fa, fc = fa;
         if (MODE != 1 && wi0 >= 0) {
 #pragma unroll
-            for (int u = 0; u < 6; u++) tq[u] = Tg[(size_t)(BB_TROW(6 * wi0) + u) * WAVE];
-            fa = Rg[(size_t)BB_RROW(3 * wi0 + 2) * WAVE]; fb = Rg[(size_t)BB_RROW(3 * wi0 + 1) * WAVE]; fc = Rg[(size_t)BB_RROW(3 * wi0) * WAVE];
+            for (int u = 0; u < 6; u++) tq[u] = Tg[(size_t)((6 * wi0) + u) * WAVE];
+            fa = Rg[(size_t)(3 * wi0 + 2) * WAVE]; fb = Rg[(size_t)(3 * wi0 + 1) * WAVE]; fc = Rg[(size_t)(3 * wi0) * WAVE];
         }
         for (int wi = maxlen - 2; MODE != 1 && wi >= 0; wi--) {       // wave-uniform trip count; lanes join when wi <= len-2
             const bool on = wi <= wi0;
@@ -754,8 +723,8 @@ __device__ __forceinline__ void backbone_group(
             if (on) {
                 const int wn = wi > 0 ? wi - 1 : 0;
 #pragma unroll
-                for (int u = 0; u < 6; u++) tn[u] = Tg[(size_t)(BB_TROW(6 * wn) + u) * WAVE];
-                na = Rg[(size_t)BB_RROW(3 * wn + 2) * WAVE]; nb = Rg[(size_t)BB_RROW(3 * wn + 1) * WAVE]; nc = Rg[(size_t)BB_RROW(3 * wn) * WAVE];
+                for (int u = 0; u < 6; u++) tn[u] = Tg[(size_t)((6 * wn) + u) * WAVE];
+                na = Rg[(size_t)(3 * wn + 2) * WAVE]; nb = Rg[(size_t)(3 * wn + 1) * WAVE]; nc = Rg[(size_t)(3 * wn) * WAVE];
             }
 #pragma unroll
             for (int q = 2; q >= 0; q--) {
@@ -785,15 +754,11 @@ __device__ __forceinline__ void backbone_group(
             p0 = c0; p1 = c1; p2 = c2;
             first = next; next = next2;
         }
-        BB_STAMP(3)
     }
     if (MODE != 1 && __any(win >= 0)) flush();
-#ifdef FCZ_BB_TIMING
-    if (MODE == 0 && lane == 0) for (int i = 0; i < 8; i++) atomicAdd(&g_bb_timing[i], tacc[i]);
-#endif
 }
 
-// MODE 0 runs as a persistent grid (FCZ_BB_PERSIST): n_cu x 8 wavefronts, the first round of groups by block index, every later
+// MODE 0 runs as a persistent grid: n_cu x 8 wavefronts, the first round of groups by block index, every later
 // one from a counter (groups are in length order, longest first), ring slot = block index. MODE 1 / 2: one block per group /
 // (group, segment). n_groups and next_group are only read by MODE 0.
 template <int MODE>
@@ -803,7 +768,7 @@ __global__ __launch_bounds__(WAVE, FCZ_BACKBONE_MIN_WAVES) void k_backbone(
         float* __restrict__ tring, uint32_t ring_rows, uint32_t seg_slots, v3* __restrict__ bb,
         uint32_t n_groups, uint32_t* __restrict__ next_group) {
     __shared__ backbone_lds S;
-    if (MODE == 0 && FCZ_BB_PERSIST) {
+    if (MODE == 0) {
         uint32_t grp = blockIdx.x;
         while (grp < n_groups) {
             backbone_group<MODE>(S, grp, 0u, blockIdx.x, blob, off, n_entries, n_slots, res_off, perm, ring, tring, ring_rows, seg_slots, bb);

@@ -304,13 +304,6 @@ struct sidechain_lds {
 #define FCZ_SIDECHAIN_MIN_BLOCKS 4
 #endif
 
-#ifdef FCZ_SC_TIMING
-// measurement aid (not built into the product): wavefront-cycles between the phase boundaries of k_sidechain
-__device__ unsigned long long g_sc_timing[12];
-#define SC_STAMP(i) { const unsigned long long now_ = __builtin_readcyclecounter(); tacc[i] += now_ - tlast; tlast = now_; }
-#else
-#define SC_STAMP(i)
-#endif
 // res_aoff has n_res + 1 entries (the last one = total atoms). FAST: placements in plain float arithmetic
 // (FCZ_NUMERICS_FAST, place_atom_d2_fast); the tables (torsion bytes, ideal geometry) are the exact ones either way.
 // tile_res = residues per tile: 256 (tile_list == nullptr: every tile of the batch), or 128 for the tiles a 256-residue launch
@@ -420,9 +413,6 @@ void k_sidechain(uint32_t n_res, uint32_t n_tiles, uint32_t tile_res, const uint
     if (blockIdx.x >= n_units) return;
     res_in nxt = load_res(unit_tile(blockIdx.x));
     null_stores();
-#ifdef FCZ_SC_TIMING
-    unsigned long long tacc[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, tlast = __builtin_readcyclecounter();
-#endif
     for (uint32_t unit = blockIdx.x; unit < n_units; unit += gridDim.x) {
         const uint32_t tile = unit_tile(unit);
         const uint32_t r = tile * tile_res + (uint32_t)t;
@@ -444,7 +434,6 @@ void k_sidechain(uint32_t n_res, uint32_t n_tiles, uint32_t tile_res, const uint
         {
             const bool act = r < n_res && (uint32_t)t < tile_res;
             uint32_t rc = 23, na = 0;
-            SC_STAMP(0)
             if (act) {
                 const uint32_t ap = cur.a - A0;
                 const v3 b0 = cur.b0, b1 = cur.b1, b2 = cur.b2;
@@ -478,7 +467,6 @@ void k_sidechain(uint32_t n_res, uint32_t n_tiles, uint32_t tile_res, const uint
                 // the chain's OXT (already written by k_res_index) lies inside this tile's output range: the write-back skips it
                 if (cur.a_next - cur.a - na == 1) S.stage[0][ap + na] = __uint_as_float(SC_SKIP);
             }
-            SC_STAMP(1)
             // ---- per-depth work lists: block-wide exclusive scan of the packed per-depth counts ----
             // (six 10-bit fields: the two 30-bit halves never carry into each other, so they scan as two dwords on the DPP network)
             const unsigned long long mine = act ? S.dcnt[rc] : 0ull;
@@ -488,7 +476,6 @@ void k_sidechain(uint32_t n_res, uint32_t n_tiles, uint32_t tile_res, const uint
             const unsigned long long inc = (((unsigned long long)(e_hi + m_hi)) << 30) | (unsigned long long)(e_lo + m_lo);
             if (lane == WAVE - 1) S.wave_tot[wave] = inc;
             __syncthreads();
-            SC_STAMP(2)
             unsigned long long pre = inc - mine, total = 0;
 #pragma unroll
             for (int w = 0; w < WAVES_PER_BLOCK; w++) { const unsigned long long v = S.wave_tot[w]; if (w < wave) pre += v; total += v; }
@@ -510,9 +497,7 @@ void k_sidechain(uint32_t n_res, uint32_t n_tiles, uint32_t tile_res, const uint
                 }
             }
             if (t == 0) S.dstart[SC_DEPTHS] = ds;
-            SC_STAMP(3)
             __syncthreads();
-            SC_STAMP(4)
             // ---- items, depth by depth ----
 #pragma unroll 1
             for (int d = 0; d < SC_DEPTHS; d++) {
@@ -537,9 +522,7 @@ void k_sidechain(uint32_t n_res, uint32_t n_tiles, uint32_t tile_res, const uint
                     S.stage[0][po] = p.x; S.stage[1][po] = p.y; S.stage[2][po] = p.z;
                     if (out.atom_code) out.atom_code[A0 + po] = (uint8_t)(G.meta >> 16);
                 }
-                SC_STAMP(5)
                 __syncthreads();
-                SC_STAMP(6)
             }
             // ---- write-back: the tile's atoms are one contiguous range of the output arrays ----
             {
@@ -558,14 +541,9 @@ void k_sidechain(uint32_t n_res, uint32_t n_tiles, uint32_t tile_res, const uint
                     __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(S.stage[2][i]), rz, off, 0, 0);
                 }
             }
-            SC_STAMP(7)
             __syncthreads();
-            SC_STAMP(8)
         }
     }
-#ifdef FCZ_SC_TIMING
-    if (lane == 0) for (int i = 0; i < 12; i++) atomicAdd(&g_sc_timing[i], tacc[i]);
-#endif
 }
 
 }  // namespace fcz

@@ -30,9 +30,3 @@ if bad.numel():
     # distribution of max dev per chain vs length
 percs = torch.quantile(dev[::97].float(), torch.tensor([0.5, 0.9, 0.99, 0.999], device="cuda:0"))
 print("quantiles 50/90/99/99.9:", percs.tolist())
-
-for part in ("1", "2"):
-    os.environ["FCZ_DEBUG_FAST_PARTS"] = part
-    codec.set_numerics(True); w.decompress(); codec.synchronize(); codec.set_numerics(False)
-    dv = torch.stack([(w.out_t[k] - exact[k]).abs() for k in ("x", "y", "z")]).max(0).values
-    print("parts", part, "max", float(dv.max()), "n>0.02", int((dv > 0.02).sum()), "n>1e-3", int((dv > 1e-3).sum()))

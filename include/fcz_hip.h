@@ -192,7 +192,14 @@ int fcz_decompress_batch(fcz_ctx* ctx, const uint8_t* blob, const uint64_t* off,
 
 /* Device-resident variants. fcz_decompress_sizes_dev fills res_off_dev/atom_off_dev (n+1 each)
  * and returns the totals through pinned host words after a stream sync (the only sync on this path:
- * the caller needs R and M to allocate outputs). */
+ * the caller needs R and M to allocate outputs).
+ * The ctx remembers that pass -- the totals, the order of the entries by length, their residue codes -- for ONE
+ * following fcz_decompress_batch_dev call that names the same blob_dev, off_dev and n; that call then runs no sizes
+ * pass of its own. The memo is keyed on the pointers, not on the bytes behind them: the records must not change
+ * between a sizes call and the batch call that follows it on the same pointers (rewrite them and the batch call
+ * decodes the new bytes with the old lengths and codes: undefined output). A batch call on other
+ * pointers or another n, and every entry point that stages records through the ctx, drop the memo; a batch call without a preceding sizes call, with
+ * res_off_dev / atom_off_dev computed elsewhere (fcz_decompress_sizes, another ctx), runs its own pass. */
 int fcz_decompress_sizes_dev(fcz_ctx* ctx, const uint8_t* blob_dev, const uint64_t* off_dev, uint32_t n,
                              uint32_t* res_off_dev, uint32_t* atom_off_dev,
                              uint32_t* total_res, uint32_t* total_atoms);

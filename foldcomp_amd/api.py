@@ -240,6 +240,29 @@ class FoldcompDatabase:
             for r in decompress_many(ents):
                 yield r
 
+    def tensor_batches(self, batch_size: int = 1024, *, layout="atom37", max_len: Optional[int] = None, device="cuda:0",
+                       sort_by_length: bool = False):
+        """Generator over the database (its `ids` selection when it has one) in batches of dense model-input tensors on the GPU:
+        the dicts of foldcomp_amd.tensors.decode_tensors, each with `names` (the records' titles) and `index` (int64 array: the
+        entries' positions in this database, what db[i] takes). sort_by_length orders every window of 16 * batch_size entries by
+        residue count (from the record headers) before it is cut into batches, so that a batch pads little; `index` undoes it."""
+        from .tensors import decode_tensors
+        batch_size = int(batch_size)
+        if batch_size < 1:
+            raise ValueError("batch_size must be at least 1")
+        window = 16 * batch_size if sort_by_length else batch_size
+        for start in range(0, len(self), window):
+            idx = np.arange(start, min(start + window, len(self)), dtype=np.int64)
+            ents = [self._entry(int(i)) for i in idx]
+            order = np.arange(len(ents))
+            if sort_by_length:
+                order = np.argsort(np.asarray([fczfile.residue_count(e) for e in ents], np.int64), kind="stable")
+            for b in range(0, len(ents), batch_size):
+                sel = order[b:b + batch_size]
+                d = decode_tensors([ents[k] for k in sel], layout=layout, max_len=max_len, device=device)
+                d["index"] = idx[sel]
+                yield d
+
     def close(self):
         self._win = None
         if self._reader is not None:

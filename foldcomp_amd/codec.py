@@ -15,7 +15,19 @@ from typing import Optional
 import numpy as np
 
 from . import _lib
-from .structure import CAtomsOut, CChainBatch, CEntryInfo, ChainBatch, batch_as_c
+from .structure import CAtomsOut, CChainBatch, CDenseOut, CEntryInfo, ChainBatch, batch_as_c
+
+
+DENSE_LAYOUTS = {"atom37": 0, "atom14": 1, "backbone4": 2}     # enum fcz_dense_layout
+
+
+def dense_layout(layout) -> int:
+    """layout name (or enum value) -> enum fcz_dense_layout"""
+    if layout in DENSE_LAYOUTS:
+        return DENSE_LAYOUTS[layout]
+    if isinstance(layout, int) and layout in DENSE_LAYOUTS.values():
+        return layout
+    raise ValueError(f"unknown dense layout {layout!r}: one of {', '.join(DENSE_LAYOUTS)}")
 
 
 class Codec:
@@ -107,6 +119,35 @@ class Codec:
                                                      atom_off.ctypes.data, int(alt_order), ctypes.byref(out)),
                        "fcz_decompress_batch")
         return dict(x=x, y=y, z=z, bfac_res=bf, res_code=rc, atom_code=ac, res_off=res_off, atom_off=atom_off, info=info)
+
+    def decompress_dense(self, blob: np.ndarray, off: np.ndarray, layout="atom37", max_len: Optional[int] = None):
+        """FCZ entries -> dense padded arrays on the host (fcz_decompress_dense): pos float32 [n, L, A, 3], mask bool [n, L, A],
+        aatype uint8 [n, L] (20 = unknown / padding), plddt float32 [n, L], res_index int32 [n, L], length uint32 [n] (uncropped;
+        0 = the entry did not decode), status int32 [n]. L = max_len, or the longest entry of the batch; longer entries are cropped."""
+        blob = np.ascontiguousarray(blob, np.uint8)
+        off = np.ascontiguousarray(off, np.uint64)
+        n = len(off) - 1
+        lay = dense_layout(layout)
+        A = self.lib.fcz_dense_width(lay)
+        if max_len is not None and int(max_len) < 1:
+            raise ValueError("max_len must be at least 1")
+        L = ctypes.c_uint32(0)
+        status = np.zeros(max(n, 1), np.int32)
+        if max_len is None:
+            _lib.check(self.lib.fcz_decompress_dense(self.ctx, blob.ctypes.data, off.ctypes.data, n, lay, 0, ctypes.byref(L), None,
+                                                     status.ctypes.data), "fcz_decompress_dense")
+        else:
+            L.value = int(max_len)
+        Lv = int(L.value)
+        d = dict(pos=np.zeros((n, Lv, A, 3), np.float32), mask=np.zeros((n, Lv, A), np.uint8), aatype=np.full((n, Lv), 20, np.uint8),
+                 plddt=np.zeros((n, Lv), np.float32), res_index=np.zeros((n, Lv), np.int32), length=np.zeros(n, np.uint32))
+        if n and Lv:
+            out = CDenseOut(*(d[k].ctypes.data for k in ("pos", "mask", "aatype", "plddt", "res_index", "length")))
+            _lib.check(self.lib.fcz_decompress_dense(self.ctx, blob.ctypes.data, off.ctypes.data, n, lay, Lv, None, ctypes.byref(out),
+                                                     status.ctypes.data), "fcz_decompress_dense")
+        d["mask"] = d["mask"].view(np.bool_)
+        d["status"] = status[:n]
+        return d
 
     def decompress_pdb(self, blob: np.ndarray, off: np.ndarray, alt_order: bool = False, nul_terminated: bool = False):
         """FCZ entries -> (list of PDB texts as bytes, per-entry status); decoding and text formatting both on the GPU.

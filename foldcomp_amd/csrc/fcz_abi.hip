@@ -29,6 +29,7 @@
 #include "fcz_ingest.h"
 #include "fcz_ingest_cif.h"
 #include "fcz_inflate.h"
+#include "fcz_dense.h"
 
 // second, host-side instance of the generated tables (integer metadata for sizes/validation)
 namespace host_tab {
@@ -1269,6 +1270,132 @@ int fcz_decompress_batch(fcz_ctx* ctx, const uint8_t* blob, const uint64_t* off,
         HIP_TRY(hipMemcpyAsync(out->bfac_res, dv.bfac_res, sizeof(float) * (size_t)R, hipMemcpyDeviceToHost, ctx->stream));
         if (out->res_code) HIP_TRY(hipMemcpyAsync(out->res_code, dv.res_code, (size_t)R, hipMemcpyDeviceToHost, ctx->stream));
     }
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return FCZ_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// dense model-input tensors of decoded chains (fcz_dense.h; the reference stops at Foldcomp::decompress, src/foldcomp.cpp:779)
+// ------------------------------------------------------------------------------------------------
+// atom37: the slot is the position of the atom's NAME in this list (what AlphaFold / OpenFold call atom_types)
+static const char* const DENSE_ATOM37[37] = {"N", "CA", "C", "CB", "O", "CG", "CG1", "CG2", "OG", "OG1", "SG", "CD", "CD1", "CD2", "ND1", "ND2",
+                                             "OD1", "OD2", "SD", "CE", "CE1", "CE2", "CE3", "NE", "NE1", "NE2", "OE1", "OE2", "CH2", "NH1", "NH2",
+                                             "OH", "CZ", "CZ2", "CZ3", "NZ", "OXT"};
+
+int fcz_dense_width(int layout) {
+    return layout == FCZ_DENSE_ATOM37 ? 37 : layout == FCZ_DENSE_ATOM14 ? 14 : layout == FCZ_DENSE_BACKBONE4 ? 4 : -1;
+}
+
+int fcz_dense_slot(int layout, int rc, int ac) {
+    if (fcz_dense_width(layout) < 0 || rc < 0 || rc >= FCZ_N_RES_CODES || ac < 0 || ac >= FCZ_N_ATOM_CODES) return -1;
+    if (ac == FCZ_ATOM_OXT) return layout == FCZ_DENSE_ATOM37 ? 36 : -1;     // the chain's last atom: no residue's table lists it
+    int j = 0;
+    while (j < host_tab::h_res_natoms[rc] && host_tab::h_res_atom[rc][j] != ac) j++;
+    if (j == host_tab::h_res_natoms[rc]) return -1;                          // the residue has no such atom
+    if (layout == FCZ_DENSE_ATOM14) return j;                                // canonical position inside the residue
+    if (layout == FCZ_DENSE_BACKBONE4) return ac < 4 ? ac : -1;              // N, CA, C, O are the codes 0 .. 3
+    for (int s = 0; s < 37; s++) if (strcmp(DENSE_ATOM37[s], host_tab::h_atom_name[ac]) == 0) return s;
+    return -1;
+}
+
+// the kernel's table: slot -> position among the residue's decoded atoms, for the order they were decoded in
+static dense_table dense_make_table(int layout, int alt_order) {
+    dense_table t;
+    memset(t.inv, 255, sizeof t.inv);
+    const int A = fcz_dense_width(layout);
+    for (int rc = 0; rc < FCZ_N_RES_CODES; rc++)
+        for (int j = 0; j < host_tab::h_res_natoms[rc]; j++) {
+            const int slot = fcz_dense_slot(layout, rc, fcz_res_code_atom(rc, j, alt_order));
+            if (slot >= 0) t.inv[rc * A + slot] = (uint8_t)j;
+        }
+    return t;
+}
+
+int fcz_dense_dev(fcz_ctx* ctx, const uint8_t* blob_dev, const uint64_t* off_dev, uint32_t n, const uint32_t* res_off_dev,
+                  const uint32_t* atom_off_dev, const fcz_atoms_out* atoms_dev, int alt_order, int layout, uint32_t L,
+                  const fcz_dense_out* out_dev) {
+    if (!ctx || !blob_dev || !off_dev || !res_off_dev || !atom_off_dev || !atoms_dev || !out_dev) return FCZ_E_INVALID_ARG;
+    if (!atoms_dev->x || !atoms_dev->y || !atoms_dev->z || !atoms_dev->bfac_res || !atoms_dev->res_code) return FCZ_E_INVALID_ARG;
+    if (fcz_dense_width(layout) < 0 || L == 0 || !out_dev->pos || !out_dev->mask) return FCZ_E_INVALID_ARG;
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (n == 0) return FCZ_OK;
+    const dense_table tab = dense_make_table(layout, alt_order ? 1 : 0);
+    const dense_args g{off_dev, res_off_dev, atom_off_dev, atoms_dev->x, atoms_dev->y, atoms_dev->z, atoms_dev->bfac_res, atoms_dev->res_code,
+                       out_dev->pos, out_dev->mask, out_dev->aatype, out_dev->plddt, out_dev->res_index, out_dev->length};
+    const uint32_t tiles_per_entry = grid_for(L, DN_TILE);
+    const uint64_t n_tiles = (uint64_t)n * tiles_per_entry;                  // every index behind it is 64-bit: n * L * A may pass 2^32
+    const uint32_t blocks = (uint32_t)std::min<uint64_t>(n_tiles, (uint64_t)ctx->n_cu * 32u);
+    span_guard sg(ctx, "dense");
+    if (layout == FCZ_DENSE_ATOM37) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_dense<37>), dim3(blocks), dim3(BLOCK), 0, ctx->stream, blob_dev, g, n, L, tiles_per_entry, n_tiles, tab);
+    else if (layout == FCZ_DENSE_ATOM14) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_dense<14>), dim3(blocks), dim3(BLOCK), 0, ctx->stream, blob_dev, g, n, L, tiles_per_entry, n_tiles, tab);
+    else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_dense<4>), dim3(blocks), dim3(BLOCK), 0, ctx->stream, blob_dev, g, n, L, tiles_per_entry, n_tiles, tab);
+    HIP_TRY(hipGetLastError());
+    return FCZ_OK;
+}
+
+int fcz_decompress_dense(fcz_ctx* ctx, const uint8_t* blob, const uint64_t* off, uint32_t n, int layout, uint32_t L, uint32_t* L_out,
+                         const fcz_dense_out* out, int32_t* status) {
+    const int A = fcz_dense_width(layout);
+    if (!ctx || !blob || !off || A < 0 || (!out && !L_out) || (out && (!out->pos || !out->mask))) return FCZ_E_INVALID_ARG;
+    HIP_TRY(hipSetDevice(ctx->device));
+    ctx->sizes_fresh = false;   // the staging buffers the cache is keyed on are about to be rewritten
+    if (n == 0) { if (L_out) *L_out = L; return FCZ_OK; }
+    const uint64_t blob_bytes = off[n];
+    int rc;
+    if ((rc = ctx->stage[0].ensure(std::max<uint64_t>(blob_bytes, 16)))) return rc;
+    if ((rc = ctx->stage[1].ensure(sizeof(uint64_t) * ((size_t)n + 1)))) return rc;
+    if ((rc = ctx->stage[2].ensure(sizeof(uint32_t) * ((size_t)n + 1)))) return rc;
+    if ((rc = ctx->stage[3].ensure(sizeof(uint32_t) * ((size_t)n + 1)))) return rc;
+    HIP_TRY(hipMemcpyAsync(ctx->stage[0].p, blob, blob_bytes, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(ctx->stage[1].p, off, sizeof(uint64_t) * ((size_t)n + 1), hipMemcpyHostToDevice, ctx->stream));
+    uint32_t R = 0, M = 0;
+    rc = fcz_decompress_sizes_dev(ctx, ctx->stage[0].as<uint8_t>(), ctx->stage[1].as<uint64_t>(), n, ctx->stage[2].as<uint32_t>(),
+                                  ctx->stage[3].as<uint32_t>(), &R, &M);
+    if (rc) return rc;
+    std::vector<uint32_t> res_off((size_t)n + 1);
+    HIP_TRY(hipMemcpyAsync(res_off.data(), ctx->stage[2].p, sizeof(uint32_t) * ((size_t)n + 1), hipMemcpyDeviceToHost, ctx->stream));
+    if (status)   // per-entry status of the sizes pass (cnt layout: 2 x n counts, then n status words)
+        HIP_TRY(hipMemcpyAsync(status, ctx->cnt.as<uint32_t>() + 2 * (size_t)n, sizeof(int32_t) * n, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    uint32_t longest = 0;
+    for (uint32_t i = 0; i < n; i++) longest = std::max(longest, res_off[i + 1] - res_off[i]);
+    if (L == 0) L = longest;
+    if (L_out) *L_out = L;
+    if (!out) { ctx->sizes_fresh = false; return FCZ_OK; }
+    if (L == 0) {               // no entry decodes and no width was asked for: the padded arrays are empty
+        ctx->sizes_fresh = false;
+        if (out->length) memset(out->length, 0, sizeof(uint32_t) * n);
+        return FCZ_OK;
+    }
+    for (int i = 4; i < 7; i++) if ((rc = ctx->stage[i].ensure(std::max<size_t>(sizeof(float) * (size_t)M, 16)))) return rc;
+    if ((rc = ctx->stage[7].ensure(std::max<size_t>(sizeof(float) * (size_t)R, 16)))) return rc;
+    if ((rc = ctx->stage[8].ensure(std::max<size_t>((size_t)R, 16)))) return rc;
+    fcz_atoms_out dv;
+    dv.x = ctx->stage[4].as<float>(); dv.y = ctx->stage[5].as<float>(); dv.z = ctx->stage[6].as<float>();
+    dv.bfac_res = ctx->stage[7].as<float>(); dv.res_code = ctx->stage[8].as<uint8_t>(); dv.atom_code = nullptr;
+    if (R) {
+        rc = fcz_decompress_batch_dev(ctx, ctx->stage[0].as<uint8_t>(), ctx->stage[1].as<uint64_t>(), n, ctx->stage[2].as<uint32_t>(),
+                                      ctx->stage[3].as<uint32_t>(), 0, &dv);
+        if (rc) return rc;
+    }
+    ctx->sizes_fresh = false;
+    const size_t rows = (size_t)n * L;
+    const size_t bytes[6] = {rows * A * 3 * sizeof(float), rows * A, out->aatype ? rows : 0, out->plddt ? rows * sizeof(float) : 0,
+                             out->res_index ? rows * sizeof(int32_t) : 0, out->length ? sizeof(uint32_t) * n : 0};
+    void* host[6] = {out->pos, out->mask, out->aatype, out->plddt, out->res_index, out->length};
+    void* dev[6];
+    for (int i = 0; i < 6; i++) {
+        dev[i] = nullptr;
+        if (!bytes[i]) continue;
+        if ((rc = ctx->stage[10 + i].ensure(bytes[i]))) return rc;
+        dev[i] = ctx->stage[10 + i].p;
+    }
+    const fcz_dense_out dd{(float*)dev[0], (uint8_t*)dev[1], (uint8_t*)dev[2], (float*)dev[3], (int32_t*)dev[4], (uint32_t*)dev[5]};
+    rc = fcz_dense_dev(ctx, ctx->stage[0].as<uint8_t>(), ctx->stage[1].as<uint64_t>(), n, ctx->stage[2].as<uint32_t>(),
+                       ctx->stage[3].as<uint32_t>(), &dv, 0, layout, L, &dd);
+    if (rc) return rc;
+    for (int i = 0; i < 6; i++)
+        if (bytes[i]) HIP_TRY(hipMemcpyAsync(host[i], dev[i], bytes[i], hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return FCZ_OK;
 }

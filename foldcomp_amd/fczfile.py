@@ -85,6 +85,13 @@ def record_size(raw) -> int:
     return 76 + 4 * raw[12] + tl + 36 * raw[12] + 13 + 8 * n + nsc + 8 + n
 
 
+def residue_count(raw) -> int:
+    """header.nResidue of the record that starts at raw[0], 0 when raw does not start with an FCZ header"""
+    if len(raw) < 76 or bytes(raw[:4]) != MAGIC:
+        return 0
+    return struct.unpack_from("<H", raw, 4)[0]
+
+
 def unpack_fields(rec: FczRecord):
     """-> dict of uint32 arrays (convertBytesToBackboneChain, src/foldcomp.cpp:60-77)"""
     w = rec.words.astype(np.uint32)

@@ -963,6 +963,11 @@ class CAtomsOut(ctypes.Structure):
                 ("bfac_res", ctypes.c_void_p), ("res_code", ctypes.c_void_p), ("atom_code", ctypes.c_void_p)]
 
 
+class CDenseOut(ctypes.Structure):
+    _fields_ = [("pos", ctypes.c_void_p), ("mask", ctypes.c_void_p), ("aatype", ctypes.c_void_p),
+                ("plddt", ctypes.c_void_p), ("res_index", ctypes.c_void_p), ("length", ctypes.c_void_p)]
+
+
 class CEntryInfo(ctypes.Structure):
     _fields_ = [("n_residues", ctypes.c_uint32), ("n_atoms_out", ctypes.c_uint32),
                 ("n_atoms_header", ctypes.c_uint32), ("first_res_index", ctypes.c_int32),

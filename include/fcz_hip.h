@@ -15,6 +15,7 @@
  *   Foldcomp::decompress(vector<AtomCoordinate>&)          fcz_decompress_batch / fcz_decompress_batch_dev
  *     src/foldcomp.cpp:779
  *   Foldcomp::checkValidity()        src/foldcomp.cpp:1492   fcz_check
+ *   (none: the reference stops at the flat atom vector)    fcz_dense_dev / fcz_decompress_dense
  *
  * Batch-first: one call handles C independent chains ("one wavefront per chain" on the device).
  * Data layout is structure-of-arrays; all offsets are element indices, not bytes, unless noted.
@@ -238,6 +239,52 @@ int fcz_decompress_pdb_fetch(fcz_ctx* ctx, uint8_t* text_out);
 int fcz_decompress_pdb_sizes(fcz_ctx* ctx, const uint8_t* blob, const uint64_t* off, uint32_t n, int alt_order,
                              uint64_t* text_off, int32_t* status);
 
+/* ---- dense model-input tensors ------------------------------------------------------------------ */
+/* Decoded chains as the padded arrays protein models read (atom37 / atom14 coordinates with a mask, residue types, pLDDT), built
+ * on the device from what fcz_decompress_batch_dev filled: no text, no host copy of the result. They stand beside
+ * Foldcomp::decompress (src/foldcomp.cpp:779), which ends at a flat vector<AtomCoordinate>; the reference has no dense output.
+ * Layouts (A = fcz_dense_width): the slot of an atom depends on its name and its residue only, never on the order the atoms were
+ * decoded in (alt_order tells the call which order atoms_dev holds; the tensors are the same either way).
+ *   FCZ_DENSE_ATOM37    A = 37  slot = position of the atom's name in
+ *                               N CA C CB O CG CG1 CG2 OG OG1 SG CD CD1 CD2 ND1 ND2 OD1 OD2 SD CE CE1 CE2 CE3 NE NE1 NE2 OE1 OE2
+ *                               CH2 NH1 NH2 OH CZ CZ2 CZ3 NZ OXT; the chain's OXT goes to slot 36 of its last residue
+ *   FCZ_DENSE_ATOM14    A = 14  slot j = the atom fcz_res_code_atom(res_code, j, 0) names; the OXT is dropped
+ *   FCZ_DENSE_BACKBONE4 A = 4   N, CA, C, O; everything else is dropped
+ * Outputs for n entries padded (or cropped) to L residues, row-major, caller-owned; every byte of every array is written:
+ *   pos [n][L][A][3] float32 coordinates, 0.0f where mask is 0       mask [n][L][A] uint8   1 where the decoder emitted the atom
+ *   aatype [n][L] uint8      min(res_code, 20); padding 20           plddt [n][L] float32   bfac_res; padding 0
+ *   res_index [n][L] int32   first_res_index + l; padding 0          length [n] uint32      residues of the entry, UNCROPPED
+ * An entry longer than L keeps its first L residues (its OXT leaves with its last residue); an entry the decoder skips
+ * (fcz_entry_info.status != FCZ_OK) has length 0 and padding only. aatype, plddt, res_index, length may be NULL (not wanted).
+ * Sizes: every index is 64-bit -- n * L * A may exceed 2^32 elements (a pos array beyond 16 GiB); nothing wraps. */
+enum fcz_dense_layout { FCZ_DENSE_ATOM37 = 0, FCZ_DENSE_ATOM14 = 1, FCZ_DENSE_BACKBONE4 = 2 };
+typedef struct fcz_dense_out {
+    float*    pos;          /* [n][L][A][3] */
+    uint8_t*  mask;         /* [n][L][A] */
+    uint8_t*  aatype;       /* [n][L] optional */
+    float*    plddt;        /* [n][L] optional */
+    int32_t*  res_index;    /* [n][L] optional */
+    uint32_t* length;       /* [n] optional */
+} fcz_dense_out;
+/* pure host: 37 / 14 / 4, -1 for an unknown layout */
+int fcz_dense_width(int layout);
+/* pure host, the table the kernel uses: slot of atom_code in a residue of res_code, -1 when the residue has no such atom, the
+ * layout no slot for it, or a code is out of range (atom code 255, residue codes outside 0 .. 23) */
+int fcz_dense_slot(int layout, int res_code, int atom_code);
+/* Device-resident: every pointer (those inside atoms_dev / out_dev too) a device pointer; atoms_dev = what
+ * fcz_decompress_batch_dev filled for the same entries and offsets (x, y, z, bfac_res, res_code required), as for
+ * fcz_pdb_format_dev. Enqueued on the ctx stream, no synchronisation. Unknown layout, L == 0, NULL pos or mask:
+ * FCZ_E_INVALID_ARG, nothing launched; n == 0: FCZ_OK. */
+int fcz_dense_dev(fcz_ctx* ctx, const uint8_t* blob_dev, const uint64_t* off_dev, uint32_t n,
+                  const uint32_t* res_off_dev, const uint32_t* atom_off_dev, const fcz_atoms_out* atoms_dev, int alt_order,
+                  int layout, uint32_t L, const fcz_dense_out* out_dev);
+/* Host-pointer convenience: records in, dense host arrays out; decodes through the ctx like fcz_decompress_batch
+ * (Foldcomp::read + Foldcomp::decompress, src/foldcomp.cpp:904 / :779, for every entry). L = 0: the longest entry of the batch;
+ * the width used comes back through *L_out (may be NULL), so a first call with out = NULL sizes the arrays. status[n] (may be
+ * NULL) receives the per-entry fcz_status. */
+int fcz_decompress_dense(fcz_ctx* ctx, const uint8_t* blob, const uint64_t* off, uint32_t n, int layout, uint32_t L,
+                         uint32_t* L_out, const fcz_dense_out* out, int32_t* status);
+
 /* ---- structure ingest: PDB / mmCIF text -> fcz_chain_batch on the device ----------------------------- */
 /* What the reference's driver does to every input file before Foldcomp::compress (src/main.cpp:455-508): StructureReader
  * (src/structure_reader.cpp:31-61; the fixed-column ATOM / HETATM record as foldcomp/foldcomp.cxx:259-278 reads it),
@@ -383,7 +430,7 @@ int fcz_check(const uint8_t* entry, uint64_t len);
 /* Accumulated device time (ms, HIP events on the ctx stream) and launch count of the named kernel
  * group since the last reset: "compress_sizes", "compress_index", "compress_angles", "compress_pack",
  * "decompress_sizes", "decompress_backbone", "decompress_index", "decompress_sidechain", "pdb_sizes", "pdb_format", "extract_sizes", "extract",
- * "ingest_parse", "ingest_parse_cif", "ingest_rows_cif", "ingest_frags", "ingest_fill", "inflate". */
+ * "ingest_parse", "ingest_parse_cif", "ingest_rows_cif", "ingest_frags", "ingest_fill", "inflate", "dense". */
 int  fcz_ctx_enable_timing(fcz_ctx* ctx, int enable);
 int  fcz_ctx_kernel_time(fcz_ctx* ctx, const char* name, double* ms, uint64_t* launches);
 void fcz_ctx_reset_timing(fcz_ctx* ctx);

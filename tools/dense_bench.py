@@ -1,0 +1,192 @@
+#!/usr/bin/env python3
+"""Measurements of the dense-tensor path -> one JSON document.
+
+  1. k_dense by HIP events (fcz_ctx_kernel_time group "dense": median of 9 calls after 3 warm-up calls) for 65 536 x 350-residue
+     synthetic chains and a 100 000-chain mixed-length batch, all three layouts, as read + written bytes per second beside
+     fcz_selftest_copy's figure taken in the same process (the project's ceiling for a streaming kernel);
+  2. the same kernel beside the decode it follows (decompress_backbone + decompress_index + decompress_sidechain of the same batch);
+  3. entries per second of FoldcompDatabase.tensor_batches(1024, sort_by_length=True) over a database of 350-residue chains beside
+     the route through PDB text (foldcomp.open iteration, a numpy column parse into atom37, one upload per batch), and the largest
+     coordinate difference between the two.
+
+    python tools/dense_bench.py --out profiles/dense_layout.json [--lib other/libfcz_hip.so label]
+"""
+import argparse
+import ctypes
+import json
+import os
+import statistics
+import sys
+import tempfile
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import numpy as np
+import torch
+
+ATOM37 = ["N", "CA", "C", "CB", "O", "CG", "CG1", "CG2", "OG", "OG1", "SG", "CD", "CD1", "CD2", "ND1", "ND2", "OD1", "OD2", "SD", "CE",
+          "CE1", "CE2", "CE3", "NE", "NE1", "NE2", "OE1", "OE2", "CH2", "NH1", "NH2", "OH", "CZ", "CZ2", "CZ3", "NZ", "OXT"]
+LAYOUTS = (("atom37", 0, 37), ("atom14", 1, 14), ("backbone4", 2, 4))
+
+
+def kernel_case(codec, bench, name, n_chains, n_res, mixed, L_cap, dev):
+    from foldcomp_amd import _lib
+    from foldcomp_amd.structure import CDenseOut
+    d = bench.generate_resident(n_chains, n_res, 25, 32768, dev, seed_base=0, mixed=mixed)
+    w = bench.Workload(codec, d, dev)
+    w.compress(); codec.synchronize()
+    del d
+    lens = None
+    res = {"case": name, "chains": n_chains, "layouts": {}}
+    codec.enable_timing(True)
+    decode = []
+    for _ in range(3 + 9):
+        codec.reset_timing()
+        w.decompress(); codec.synchronize()
+        decode.append(sum(codec.kernel_time(g)[0] for g in ("decompress_backbone", "decompress_index", "decompress_sidechain")))
+    decode_ms = statistics.median(decode[3:])
+    lens = np.diff(w.res_off_dev.cpu().numpy().view(np.uint32).astype(np.int64))
+    L = int(min(lens.max(), L_cap))
+    res.update(residues=int(lens.sum()), longest=int(lens.max()), L=L, decode_kernels_ms=decode_ms)
+    for lname, lay, A in LAYOUTS:
+        n = n_chains
+        pos = torch.empty((n, L, A, 3), dtype=torch.float32, device=dev); mask = torch.empty((n, L, A), dtype=torch.uint8, device=dev)
+        aatype = torch.empty((n, L), dtype=torch.uint8, device=dev); plddt = torch.empty((n, L), dtype=torch.float32, device=dev)
+        res_index = torch.empty((n, L), dtype=torch.int32, device=dev); length = torch.empty(n, dtype=torch.int32, device=dev)
+        out = CDenseOut(*(t.data_ptr() for t in (pos, mask, aatype, plddt, res_index, length)))
+        torch.cuda.synchronize()
+        ms = []
+        for _ in range(3 + 9):
+            codec.reset_timing()
+            _lib.check(codec.lib.fcz_dense_dev(codec.ctx, w.blob_dev.data_ptr(), w.off_dev.data_ptr(), n, w.res_off_dev.data_ptr(),
+                                               w.atom_off_dev.data_ptr(), ctypes.byref(w.cout), 0, lay, L, ctypes.byref(out)), "fcz_dense_dev")
+            codec.synchronize()
+            ms.append(codec.kernel_time("dense")[0])
+        med = statistics.median(ms[3:])
+        atoms = int(mask.sum(dtype=torch.int64))
+        kept = int(np.minimum(lens, L).sum())
+        written = n * L * (A * 13 + 9) + 4 * n
+        read = 12 * atoms + 5 * kept + 8 * n
+        res["layouts"][lname] = dict(dense_ms=med, dense_ms_min=min(ms[3:]), dense_ms_max=max(ms[3:]), bytes_written=written, bytes_read=read,
+                                     gb_per_s=(written + read) / (med * 1e-3) / 1e9, padding_fraction=1.0 - kept / (n * L),
+                                     share_of_decode_plus_dense=med / (med + decode_ms))
+        del pos, mask, aatype, plddt, res_index, length
+        torch.cuda.empty_cache()
+    codec.enable_timing(False)
+    del w
+    torch.cuda.empty_cache()
+    return res
+
+
+def parse_atom37(pdb: str):
+    """the PDB text of one entry -> (pos [n_res, 37, 3] float32, mask [n_res, 37]) by plain numpy column slices"""
+    raw = pdb.encode("latin-1")
+    a0 = raw.index(b"ATOM  ")
+    a1 = raw.rindex(b"TER")
+    rows = np.frombuffer(raw[a0:a1], np.uint8).reshape(-1, 81)
+    def col(lo, hi, dt): return np.ascontiguousarray(rows[:, lo:hi]).view(f"S{hi - lo}")[:, 0].astype(dt)
+    xyz = np.stack([col(30, 38, np.float32), col(38, 46, np.float32), col(46, 54, np.float32)], 1)
+    name = np.char.strip(col(12, 16, "S4"))
+    resn = col(22, 26, np.int64)
+    slot = np.asarray([ATOM37.index(s.decode()) for s in name])
+    is_oxt = slot == 36
+    row = resn - resn[0]
+    if is_oxt.any():
+        row[is_oxt] = row[~is_oxt].max()
+    n_res = int(row.max()) + 1
+    pos = np.zeros((n_res, 37, 3), np.float32); mask = np.zeros((n_res, 37), np.uint8)
+    pos[row, slot] = xyz; mask[row, slot] = 1
+    return pos, mask
+
+
+def user_level(codec, bench, n_entries, dev):
+    import foldcomp
+    from foldcomp_amd import api
+    from foldcomp_amd.database import DatabaseWriter
+    api.set_codec(codec)
+    d = bench.generate_resident(n_entries, 350, 25, 32768, dev, seed_base=0)
+    w = bench.Workload(codec, d, dev)
+    w.compress(); codec.synchronize()
+    blob = w.blob_dev.cpu().numpy(); off = w.off_dev.cpu().numpy()
+    del w, d
+    torch.cuda.empty_cache()
+    out = {"entries": n_entries, "residues_per_entry": 350, "batch_size": 1024}
+    with tempfile.TemporaryDirectory() as tmp:
+        path = os.path.join(tmp, "db")
+        wr = DatabaseWriter(path)
+        for i in range(n_entries):
+            wr.append(blob[int(off[i]):int(off[i + 1])].tobytes(), i, f"e{i}")
+        wr.close()
+        dense = {}
+        for rep in range(2):                                  # the second pass is the measured one (first: allocator, page cache)
+            torch.cuda.synchronize(); t0 = time.perf_counter()
+            with foldcomp.open(path) as db:
+                for b in db.tensor_batches(1024, sort_by_length=True):
+                    if rep == 1 and len(dense) < 2:
+                        dense[int(b["index"][0])] = (b["pos"][0].cpu().numpy(), b["mask"][0].cpu().numpy())
+            torch.cuda.synchronize(); t_new = time.perf_counter() - t0
+        worst = 0.0
+        for rep in range(1):
+            t0 = time.perf_counter()
+            with foldcomp.open(path) as db:
+                batch = []
+                for i, (name, pdb) in enumerate(db):
+                    pos, mask = parse_atom37(pdb)
+                    if i in dense:
+                        m = dense[i][1][:len(mask)].astype(bool)
+                        assert np.array_equal(m, mask.astype(bool))
+                        worst = max(worst, float(np.abs(dense[i][0][:len(pos)].astype(np.float64) - pos)[m].max()))
+                    batch.append((pos, mask))
+                    if len(batch) == 1024 or i == len(db) - 1:
+                        L = max(len(p) for p, _ in batch)
+                        P = np.zeros((len(batch), L, 37, 3), np.float32); M = np.zeros((len(batch), L, 37), np.uint8)
+                        for j, (p, m) in enumerate(batch):
+                            P[j, :len(p)] = p; M[j, :len(m)] = m
+                        tp, tm = torch.from_numpy(P).to(dev), torch.from_numpy(M).to(dev)
+                        batch = []
+            torch.cuda.synchronize(); t_old = time.perf_counter() - t0
+    api.set_codec(None)
+    out.update(tensor_batches_entries_per_s=n_entries / t_new, text_route_entries_per_s=n_entries / t_old,
+               ratio=t_old / t_new, max_abs_coordinate_difference=worst, entries_compared=len(dense))
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--label", default="")
+    ap.add_argument("--skip-user-level", action="store_true")
+    ap.add_argument("--db-entries", type=int, default=20000)
+    ap.add_argument("--mixed-chains", type=int, default=100000)
+    ap.add_argument("--mixed-max-len", type=int, default=1024, help="L of the mixed batch (longer chains are cropped): 100 000 x 2 700 x 444 B does not fit")
+    args = ap.parse_args()
+    torch.cuda.init()
+    dev = torch.device("cuda:0")
+    import bench
+    from foldcomp_amd import _lib
+    from foldcomp_amd.codec import Codec
+    codec = Codec(0)
+    gbs = ctypes.c_double(0)
+    _lib.check(codec.lib.fcz_selftest_copy(codec.ctx, ctypes.c_uint64(1 << 30), 10, ctypes.byref(gbs)), "fcz_selftest_copy")
+    doc = {"label": args.label, "library": _lib.LIB_PATH if os.environ.get("FCZ_HIP_LIB") else "foldcomp_amd/libfcz_hip.so",
+           "device": torch.cuda.get_device_name(0), "copy_ceiling_gb_per_s": gbs.value, "method": "HIP events on the ctx stream, median of 9 after 3 warm-up calls",
+           "kernel": [kernel_case(codec, bench, "65536 x 350", 65536, 350, False, 1 << 30, dev),
+                      kernel_case(codec, bench, f"{args.mixed_chains} mixed (L capped at {args.mixed_max_len})", args.mixed_chains, 0, True, args.mixed_max_len, dev)]}
+    for c in doc["kernel"]:
+        for v in c["layouts"].values():
+            v["fraction_of_copy_ceiling"] = v["gb_per_s"] / gbs.value
+    if not args.skip_user_level:
+        doc["user_level"] = user_level(codec, bench, args.db_entries, dev)
+    codec.close()
+    text = json.dumps(doc, indent=1)
+    print(text)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(text + "\n")
+
+
+if __name__ == "__main__":
+    main()

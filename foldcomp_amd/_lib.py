@@ -9,7 +9,7 @@ from __future__ import annotations
 import ctypes
 import os
 
-from .structure import CAtomsOut, CChainBatch, CDenseOut, CEntryInfo, CIngestResult
+from .structure import CAtomsOut, CChainBatch, CDenseIn, CDenseOut, CEntryInfo, CIngestResult
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # FCZ_HIP_LIB selects another build of the same library (A/B timing of kernel variants); it is still a HIP build
@@ -73,6 +73,12 @@ def load():
         "fcz_dense_slot": (i32, [i32, i32, i32]),
         "fcz_dense_dev": (i32, [vp, vp, vp, u32, vp, vp, PO, i32, i32, u32, ctypes.POINTER(CDenseOut)]),
         "fcz_decompress_dense": (i32, [vp, vp, vp, u32, i32, u32, ctypes.POINTER(u32), ctypes.POINTER(CDenseOut), vp]),
+        "fcz_undense_dev": (i32, [vp, ctypes.POINTER(CDenseIn), u32, u32, i32, i32, PB, vp, vp]),
+        "fcz_undense_fetch": (i32, [vp, PB, vp]),
+        "fcz_compress_dense_begin_dev": (i32, [vp, ctypes.POINTER(CDenseIn), u32, u32, i32, i32, vp, ctypes.POINTER(u64)]),
+        "fcz_compress_dense_fetch_dev": (i32, [vp, vp, vp, vp]),
+        "fcz_compress_dense_begin": (i32, [vp, ctypes.POINTER(CDenseIn), u32, u32, i32, i32, vp, ctypes.POINTER(u64)]),
+        "fcz_compress_dense_fetch": (i32, [vp, vp, vp, vp]),
         "fcz_extract_sizes": (i32, [vp, vp, u32, i32, i32, vp]),
         "fcz_extract": (i32, [vp, vp, vp, u32, i32, i32, vp, vp]),
         "fcz_extract_sizes_dev": (i32, [vp, vp, vp, u32, i32, i32, vp]),
@@ -109,7 +115,9 @@ EXPORTS = ["fcz_ctx_create", "fcz_ctx_destroy", "fcz_ctx_stream", "fcz_ctx_synch
            "fcz_compress_angles", "fcz_compress_sizes_dev", "fcz_compress_batch_dev", "fcz_decompress_sizes", "fcz_decompress_batch",
            "fcz_decompress_sizes_dev", "fcz_decompress_batch_dev", "fcz_pdb_sizes_dev", "fcz_pdb_format_dev",
            "fcz_decompress_pdb_begin", "fcz_decompress_pdb_fetch", "fcz_decompress_pdb_sizes",
-           "fcz_dense_width", "fcz_dense_slot", "fcz_dense_dev", "fcz_decompress_dense", "fcz_extract_sizes", "fcz_extract",
+           "fcz_dense_width", "fcz_dense_slot", "fcz_dense_dev", "fcz_decompress_dense", "fcz_undense_dev", "fcz_undense_fetch",
+           "fcz_compress_dense_begin_dev", "fcz_compress_dense_fetch_dev", "fcz_compress_dense_begin", "fcz_compress_dense_fetch",
+           "fcz_extract_sizes", "fcz_extract",
            "fcz_extract_sizes_dev", "fcz_extract_dev", "fcz_ingest_pdb_dev", "fcz_ingest_pdb_begin", "fcz_ingest_pdb_fetch", "fcz_ingest_chain_names_fetch",
            "fcz_compress_pdb_begin", "fcz_compress_pdb_fetch", "fcz_inflate_sizes", "fcz_inflate_dev", "fcz_inflate",
            "fcz_ingest_gz_begin", "fcz_compress_gz_begin", "fcz_check", "fcz_ctx_enable_timing",

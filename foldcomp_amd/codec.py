@@ -15,7 +15,7 @@ from typing import Optional
 import numpy as np
 
 from . import _lib
-from .structure import CAtomsOut, CChainBatch, CDenseOut, CEntryInfo, ChainBatch, batch_as_c
+from .structure import CAtomsOut, CChainBatch, CDenseIn, CDenseOut, CEntryInfo, ChainBatch, batch_as_c
 
 
 DENSE_LAYOUTS = {"atom37": 0, "atom14": 1, "backbone4": 2}     # enum fcz_dense_layout
@@ -148,6 +148,67 @@ class Codec:
         d["mask"] = d["mask"].view(np.bool_)
         d["status"] = status[:n]
         return d
+
+    def _dense_in(self, pos, mask, aatype, length, plddt, layout, first_res_index, chain_id, titles):
+        """numpy arrays of one dense batch, checked against each other -> (CDenseIn of host pointers, n, L, layout enum, keep-alive)"""
+        lay = dense_layout(layout)
+        A = self.lib.fcz_dense_width(lay)
+        pos = np.ascontiguousarray(pos, np.float32)
+        if pos.ndim != 4 or pos.shape[2:] != (A, 3):
+            raise ValueError(f"pos must be [n, L, {A}, 3] for layout {layout!r}, not {tuple(pos.shape)}")
+        n, L = int(pos.shape[0]), int(pos.shape[1])
+        mask = np.ascontiguousarray(mask)
+        mask = mask.view(np.uint8) if mask.dtype == np.bool_ else np.ascontiguousarray(mask, np.uint8)
+        aatype = np.ascontiguousarray(aatype, np.uint8)
+        length = np.asarray(length)
+        if length.size and (length.astype(np.int64) < 0).any():
+            raise ValueError("length must not be negative")
+        length = np.ascontiguousarray(length, np.uint32)
+        if mask.shape != (n, L, A) or aatype.shape != (n, L) or length.shape != (n,):
+            raise ValueError(f"mask {mask.shape}, aatype {aatype.shape}, length {length.shape} do not fit pos {tuple(pos.shape)}")
+        keep = [pos, mask, aatype, length]
+        s = CDenseIn(pos.ctypes.data, mask.ctypes.data, aatype.ctypes.data, length.ctypes.data)
+
+        def per(a, dtype, shape, what):
+            a = np.ascontiguousarray(a, dtype)
+            if a.shape != shape:
+                raise ValueError(f"{what} must have shape {shape}, not {a.shape}")
+            keep.append(a)
+            return a.ctypes.data
+
+        if plddt is not None:
+            s.plddt = per(plddt, np.float32, (n, L), "plddt")
+        if first_res_index is not None:
+            s.first_res_index = per(first_res_index, np.int32, (n,), "first_res_index")
+        if chain_id is not None:
+            ids = [ord(c) if isinstance(c, str) else int(c) for c in chain_id]
+            s.chain_id = per(ids, np.uint8, (n,), "chain_id")
+        if titles is not None:
+            tb = [t.encode("latin-1", "replace") if isinstance(t, str) else bytes(t) for t in titles]
+            if len(tb) != n:
+                raise ValueError(f"{len(tb)} titles for {n} chains")
+            toff = np.zeros(n + 1, np.uint32)
+            toff[1:] = np.cumsum([len(t) for t in tb])
+            tt = np.frombuffer(b"".join(tb) or b"\0", np.uint8)
+            keep += [toff, tt]
+            s.titles, s.title_off = tt.ctypes.data, toff.ctypes.data
+        return s, n, L, lay, keep
+
+    def compress_dense(self, pos, mask, aatype, length, plddt=None, *, layout="atom37", first_res_index=None, chain_id=None, titles=None,
+                       anchor_threshold: int = 25):
+        """dense padded arrays on the host -> (blob uint8[...], off uint64[n + 1], status int32[n]): fcz_compress_dense_begin /
+        _fetch, the gather into the codec's flat batch and the codec both on the GPU. pos [n, L, A, 3] float32, mask [n, L, A] (bool
+        or uint8), aatype [n, L], length [n], plddt [n, L] or None (0). Rows behind length[c] and atoms whose mask is 0 are never
+        read as data. A refused chain (status != 0; include/fcz_hip.h, fcz_dense_in) leaves zeros in its record range."""
+        s, n, L, lay, keep = self._dense_in(pos, mask, aatype, length, plddt, layout, first_res_index, chain_id, titles)
+        if n == 0:
+            return np.zeros(0, np.uint8), np.zeros(1, np.uint64), np.zeros(0, np.int32)
+        counts = np.zeros(3, np.uint32); nbytes = ctypes.c_uint64(0)
+        _lib.check(self.lib.fcz_compress_dense_begin(self.ctx, ctypes.byref(s), n, L, lay, int(anchor_threshold), counts.ctypes.data,
+                                                     ctypes.byref(nbytes)), "fcz_compress_dense_begin")
+        off = np.zeros(n + 1, np.uint64); st = np.zeros(n, np.int32); blob = np.zeros(max(int(nbytes.value), 1), np.uint8)
+        _lib.check(self.lib.fcz_compress_dense_fetch(self.ctx, off.ctypes.data, st.ctypes.data, blob.ctypes.data), "fcz_compress_dense_fetch")
+        return blob[:int(nbytes.value)], off, st
 
     def decompress_pdb(self, blob: np.ndarray, off: np.ndarray, alt_order: bool = False, nul_terminated: bool = False):
         """FCZ entries -> (list of PDB texts as bytes, per-entry status); decoding and text formatting both on the GPU.

@@ -30,6 +30,7 @@
 #include "fcz_ingest_cif.h"
 #include "fcz_inflate.h"
 #include "fcz_dense.h"
+#include "fcz_undense.h"
 
 // second, host-side instance of the generated tables (integer metadata for sizes/validation)
 namespace host_tab {
@@ -119,6 +120,11 @@ struct fcz_ctx {
     uint64_t ig_fcz_bytes = 0;
     // inflate in front of the ingest: the files' bytes as they came over the link, their offsets / kinds / text offsets / statuses
     dev_buf gz_raw, gz_off, gz_kind, gz_toff, gz_status;
+    // dense tensors -> batch (fcz_undense.h): scratch, the resident batch of the last undense call and its per-chain verdicts
+    dev_buf ud[8];
+    fcz_chain_batch ud_batch{};
+    const int32_t* ud_status = nullptr;
+    uint64_t ud_fcz_bytes = 0;
     std::vector<timed_span> spans;
     std::map<std::string, std::pair<double, uint64_t>> acc;
 };
@@ -239,6 +245,7 @@ void fcz_ctx_destroy(fcz_ctx* c) {
     for (auto& b : c->stage) b.release();
     for (auto& b : c->ig) b.release();
     c->gz_raw.release(); c->gz_off.release(); c->gz_kind.release(); c->gz_toff.release(); c->gz_status.release();
+    for (auto& b : c->ud) b.release();
     if (c->pinned) (void)hipHostFree(c->pinned);
     if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
     if (c->ev_join) (void)hipEventDestroy(c->ev_join);
@@ -794,8 +801,9 @@ int fcz_ingest_pdb_fetch(fcz_ctx* ctx, const fcz_chain_batch* hb, uint32_t* chai
     return FCZ_OK;
 }
 
-// the compress half of fcz_compress_pdb_begin / fcz_compress_gz_begin: sizes, then the codec, on the batch the ingest left in the ctx
-static int compress_resident_batch(fcz_ctx* ctx, uint64_t* fcz_bytes);
+// the compress half of fcz_compress_pdb_begin / fcz_compress_gz_begin / fcz_compress_dense_begin: sizes, then the codec, on a batch
+// an earlier stage left in the ctx; the records stay in stage[13] (offsets), [14] (bytes), [15] (status)
+static int compress_resident_batch(fcz_ctx* ctx, const fcz_chain_batch& b, uint64_t* kept_bytes, uint64_t* fcz_bytes);
 
 int fcz_compress_pdb_begin(fcz_ctx* ctx, const uint8_t* text, const uint64_t* file_off, uint32_t n_files, const char* names, const uint32_t* name_off,
                            const uint32_t* stem_len, int anchor_threshold, int flags, uint32_t counts[5], uint64_t* fcz_bytes) {
@@ -803,7 +811,7 @@ int fcz_compress_pdb_begin(fcz_ctx* ctx, const uint8_t* text, const uint64_t* fi
     *fcz_bytes = 0; if (ctx) ctx->ig_fcz_bytes = 0;
     int rc = fcz_ingest_pdb_begin(ctx, text, file_off, n_files, names, name_off, stem_len, anchor_threshold, flags, counts);
     if (rc) return rc;
-    return compress_resident_batch(ctx, fcz_bytes);
+    return compress_resident_batch(ctx, ctx->ig_res.batch, &ctx->ig_fcz_bytes, fcz_bytes);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -909,12 +917,11 @@ int fcz_compress_gz_begin(fcz_ctx* ctx, const uint8_t* data, const uint64_t* fil
     *fcz_bytes = 0; if (ctx) ctx->ig_fcz_bytes = 0;
     int rc = fcz_ingest_gz_begin(ctx, data, file_off, n_files, is_gz, names, name_off, stem_len, anchor_threshold, flags, counts);
     if (rc) return rc;
-    return compress_resident_batch(ctx, fcz_bytes);
+    return compress_resident_batch(ctx, ctx->ig_res.batch, &ctx->ig_fcz_bytes, fcz_bytes);
 }
 
-static int compress_resident_batch(fcz_ctx* ctx, uint64_t* fcz_bytes) {
+static int compress_resident_batch(fcz_ctx* ctx, const fcz_chain_batch& b, uint64_t* kept_bytes, uint64_t* fcz_bytes) {
     int rc;
-    const fcz_chain_batch& b = ctx->ig_res.batch;
     const uint32_t C = b.n_chains;
     if (C == 0) return FCZ_OK;
     if ((rc = ctx->stage[13].ensure(8 * ((size_t)C + 1))) || (rc = ctx->stage[15].ensure(4 * (size_t)C))) return rc;
@@ -925,7 +932,7 @@ static int compress_resident_batch(fcz_ctx* ctx, uint64_t* fcz_bytes) {
     const uint64_t bytes = *tot;
     if ((rc = ctx->stage[14].ensure(std::max<uint64_t>(bytes, 16)))) return rc;
     if ((rc = fcz_compress_batch_dev(ctx, &b, ctx->stage[13].as<uint64_t>(), ctx->stage[14].as<uint8_t>(), ctx->stage[15].as<int32_t>()))) return rc;
-    ctx->ig_fcz_bytes = bytes; *fcz_bytes = bytes;
+    *kept_bytes = bytes; *fcz_bytes = bytes;
     return FCZ_OK;
 }
 
@@ -1398,6 +1405,200 @@ int fcz_decompress_dense(fcz_ctx* ctx, const uint8_t* blob, const uint64_t* off,
         if (bytes[i]) HIP_TRY(hipMemcpyAsync(host[i], dev[i], bytes[i], hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return FCZ_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// dense tensors -> fcz_chain_batch -> FCZ records (fcz_undense.h; beside Foldcomp::compress, src/foldcomp.cpp:562, which takes
+// the flat atom list these entry points build)
+// ------------------------------------------------------------------------------------------------
+// the kernels' table: canonical position -> slot of the layout
+static undense_table undense_make_table(int layout) {
+    undense_table t;
+    memset(t.slot, 255, sizeof t.slot);
+    for (int rc = 0; rc < FCZ_N_RES_CODES; rc++)
+        for (int j = 0; j < host_tab::h_res_natoms[rc]; j++) {
+            const int slot = fcz_dense_slot(layout, rc, fcz_res_code_atom(rc, j, 0));
+            if (slot >= 0) t.slot[rc * FCZ_MAX_RES_ATOMS + j] = (uint8_t)slot;
+        }
+    return t;
+}
+
+static bool undense_args_ok(const fcz_ctx* ctx, const fcz_dense_in* in, uint32_t n, uint32_t L, int layout, int anchor_threshold) {
+    if (!ctx || fcz_dense_width(layout) < 0 || L == 0 || anchor_threshold <= 0) return false;
+    if (n == 0) return true;
+    return in && in->pos && in->mask && in->aatype && in->length && (!in->titles == !in->title_off);
+}
+
+int fcz_undense_dev(fcz_ctx* ctx, const fcz_dense_in* in, uint32_t n, uint32_t L, int layout, int anchor_threshold,
+                    fcz_chain_batch* out, uint32_t counts[3], int32_t* chain_status_dev) {
+    if (!undense_args_ok(ctx, in, n, L, layout, anchor_threshold) || !out || !counts) return FCZ_E_INVALID_ARG;
+    HIP_TRY(hipSetDevice(ctx->device));
+    memset(out, 0, sizeof *out);
+    memset(&ctx->ud_batch, 0, sizeof ctx->ud_batch);
+    ctx->ud_status = nullptr;
+    counts[0] = counts[1] = counts[2] = 0;
+    out->anchor_threshold = ctx->ud_batch.anchor_threshold = anchor_threshold;
+    if (n == 0) return FCZ_OK;
+    enum { U_ROWS, U_CHAIN, U_OUT_A, U_OUT_R, U_OUT_C };
+    const size_t C = n, rows = C * (size_t)L;
+    // per chain: residues, atoms, status, flags (overflow of the two scans) | res_off, first atom of the chain
+    const size_t ch_nres = 0, ch_natoms = 4 * C, ch_status = 8 * C, ch_flags = 12 * C, ch_resoff = ch_flags + 16, ch_aoff = ch_resoff + 4 * (C + 1);
+    int rc;
+    if ((rc = ctx->ud[U_ROWS].ensure(2 * rows + 16)) || (rc = ctx->ud[U_CHAIN].ensure(ch_aoff + 4 * (C + 1)))) return rc;
+    char* bc = (char*)ctx->ud[U_CHAIN].p;
+    uint16_t* row_word = ctx->ud[U_ROWS].as<uint16_t>();
+    uint32_t* n_res = (uint32_t*)(bc + ch_nres); uint32_t* n_atoms = (uint32_t*)(bc + ch_natoms); int32_t* status = (int32_t*)(bc + ch_status);
+    uint32_t* ovf = (uint32_t*)(bc + ch_flags); uint32_t* res_off = (uint32_t*)(bc + ch_resoff); uint32_t* chain_aoff = (uint32_t*)(bc + ch_aoff);
+    const undense_table tab = undense_make_table(layout);
+    const undense_in g{in->pos, in->mask, in->aatype, in->length, in->plddt};
+    HIP_TRY(hipMemsetAsync(ovf, 0, 16, ctx->stream));
+    {
+        span_guard sg(ctx, "undense");
+        const dim3 grid(std::min<uint32_t>(n, (uint32_t)ctx->n_cu * 16u));
+        if (layout == FCZ_DENSE_ATOM37) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_undense_count<37>), grid, dim3(BLOCK), 0, ctx->stream, g, n, L, tab, row_word, n_res, n_atoms, status);
+        else if (layout == FCZ_DENSE_ATOM14) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_undense_count<14>), grid, dim3(BLOCK), 0, ctx->stream, g, n, L, tab, row_word, n_res, n_atoms, status);
+        else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_undense_count<4>), grid, dim3(BLOCK), 0, ctx->stream, g, n, L, tab, row_word, n_res, n_atoms, status);
+    }
+    if ((rc = device_scan<uint32_t>(ctx, n_res, res_off, n, ovf)) || (rc = device_scan<uint32_t>(ctx, n_atoms, chain_aoff, n, ovf))) return rc;
+    HIP_TRY(hipGetLastError());
+    uint32_t* pin = ctx->pinned + 16;   // [16] residues, [17] atoms, [18] overflow
+    HIP_TRY(hipMemcpyAsync(&pin[0], res_off + n, 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(&pin[1], chain_aoff + n, 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(&pin[2], ovf, 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (chain_status_dev) HIP_TRY(hipMemcpyAsync(chain_status_dev, status, 4 * C, hipMemcpyDeviceToDevice, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    if (pin[2]) return FCZ_E_INVALID_ARG;                      // the flat batch counts residues and atoms in 32 bits: split the call
+    const uint32_t R = pin[0], M = pin[1];
+    // the batch arrays: [atoms] x y z code | [residues + 1] atom_off, [residues] bfac code | [chains] first residue, first atom,
+    // [chains + 1] zero title offsets, [chains] chain id
+    const size_t oa_y = 4 * (size_t)M, oa_z = 8 * (size_t)M, oa_c = 12 * (size_t)M;
+    const size_t or_bf = 4 * ((size_t)R + 1), or_rc = or_bf + 4 * (size_t)R;
+    const size_t oc_fa = 4 * C, oc_tit = 8 * C, oc_id = oc_tit + 4 * (C + 1);
+    if ((rc = ctx->ud[U_OUT_A].ensure(13 * (size_t)M + 16)) || (rc = ctx->ud[U_OUT_R].ensure(or_rc + R + 16)) || (rc = ctx->ud[U_OUT_C].ensure(oc_id + C + 16))) return rc;
+    char* ba = (char*)ctx->ud[U_OUT_A].p; char* br = (char*)ctx->ud[U_OUT_R].p; char* bm = (char*)ctx->ud[U_OUT_C].p;
+    const undense_out o{(uint32_t*)br, (float*)ba, (float*)(ba + oa_y), (float*)(ba + oa_z), (uint8_t*)(ba + oa_c), (uint8_t*)(br + or_rc), (float*)(br + or_bf)};
+    HIP_TRY(hipMemsetAsync(o.atom_off, 0, 4, ctx->stream));    // (a batch without residues: atom_off[0] has no writer)
+    if (!in->title_off) HIP_TRY(hipMemsetAsync(bm + oc_tit, 0, 4 * (C + 1), ctx->stream));
+    if (!in->first_res_index || !in->first_atom_index || !in->chain_id)
+        hipLaunchKernelGGL(k_undense_defaults, dim3(grid_for(n, BLOCK)), dim3(BLOCK), 0, ctx->stream, n, in->first_res_index ? nullptr : (int32_t*)bm,
+                           in->first_atom_index ? nullptr : (int32_t*)(bm + oc_fa), in->chain_id ? nullptr : bm + oc_id);
+    if (R) {
+        span_guard sg(ctx, "undense");
+        const uint32_t tiles_per_chain = grid_for(L, DN_TILE);
+        const uint64_t n_tiles = (uint64_t)n * tiles_per_chain;  // every index into the dense arrays is 64-bit: n * L * A * 3 may pass 2^32
+        const dim3 grid((uint32_t)std::min<uint64_t>(n_tiles, (uint64_t)ctx->n_cu * 16u));
+        if (layout == FCZ_DENSE_ATOM37) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_undense_fill<37>), grid, dim3(BLOCK), 0, ctx->stream, g, L, tiles_per_chain, n_tiles, tab, (const uint16_t*)row_word, (const uint32_t*)res_off, (const uint32_t*)chain_aoff, o);
+        else if (layout == FCZ_DENSE_ATOM14) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_undense_fill<14>), grid, dim3(BLOCK), 0, ctx->stream, g, L, tiles_per_chain, n_tiles, tab, (const uint16_t*)row_word, (const uint32_t*)res_off, (const uint32_t*)chain_aoff, o);
+        else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_undense_fill<4>), grid, dim3(BLOCK), 0, ctx->stream, g, L, tiles_per_chain, n_tiles, tab, (const uint16_t*)row_word, (const uint32_t*)res_off, (const uint32_t*)chain_aoff, o);
+    }
+    HIP_TRY(hipGetLastError());
+    fcz_chain_batch& b = ctx->ud_batch;
+    b.n_chains = n; b.n_residues = R; b.n_atoms = M; b.anchor_threshold = anchor_threshold;
+    b.res_off = res_off; b.atom_off = o.atom_off; b.x = o.x; b.y = o.y; b.z = o.z; b.atom_code = o.atom_code; b.res_code = o.res_code; b.bfac_ca = o.bfac_ca;
+    b.first_res_index = in->first_res_index ? in->first_res_index : (const int32_t*)bm;
+    b.first_atom_index = in->first_atom_index ? in->first_atom_index : (const int32_t*)(bm + oc_fa);
+    b.chain_id = in->chain_id ? in->chain_id : bm + oc_id;
+    b.title_off = in->title_off ? in->title_off : (const uint32_t*)(bm + oc_tit);
+    b.titles = in->titles ? in->titles : bm + oc_tit;         // (no title has a byte: any valid pointer)
+    ctx->ud_status = status;
+    counts[0] = n; counts[1] = R; counts[2] = M;
+    *out = b;
+    return FCZ_OK;
+}
+
+int fcz_undense_fetch(fcz_ctx* ctx, const fcz_chain_batch* hb, int32_t* chain_status) {
+    if (!ctx) return FCZ_E_INVALID_ARG;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const fcz_chain_batch& d = ctx->ud_batch;
+    const size_t C = d.n_chains, R = d.n_residues, M = d.n_atoms;
+    if (C == 0) return FCZ_OK;
+    if (hb) {
+        uint32_t TB = 0;
+        HIP_TRY(hipMemcpyAsync(&TB, d.title_off + C, 4, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        auto cp = [&](const void* dst, const void* src, size_t bytes) -> int {
+            if (!bytes) return FCZ_OK;
+            if (!dst) return FCZ_E_INVALID_ARG;
+            HIP_TRY(hipMemcpyAsync(const_cast<void*>(dst), src, bytes, hipMemcpyDeviceToHost, ctx->stream));
+            return FCZ_OK;
+        };
+        int rc;
+        if ((rc = cp(hb->res_off, d.res_off, 4 * (C + 1))) || (rc = cp(hb->atom_off, d.atom_off, 4 * (R + 1))) || (rc = cp(hb->x, d.x, 4 * M)) ||
+            (rc = cp(hb->y, d.y, 4 * M)) || (rc = cp(hb->z, d.z, 4 * M)) || (rc = cp(hb->atom_code, d.atom_code, M)) || (rc = cp(hb->res_code, d.res_code, R)) ||
+            (rc = cp(hb->bfac_ca, d.bfac_ca, 4 * R)) || (rc = cp(hb->first_res_index, d.first_res_index, 4 * C)) ||
+            (rc = cp(hb->first_atom_index, d.first_atom_index, 4 * C)) || (rc = cp(hb->chain_id, d.chain_id, C)) || (rc = cp(hb->titles, d.titles, TB)) ||
+            (rc = cp(hb->title_off, d.title_off, 4 * (C + 1))))
+            return rc;
+    }
+    if (chain_status) HIP_TRY(hipMemcpyAsync(chain_status, ctx->ud_status, 4 * C, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return FCZ_OK;
+}
+
+int fcz_compress_dense_begin_dev(fcz_ctx* ctx, const fcz_dense_in* in, uint32_t n, uint32_t L, int layout, int anchor_threshold,
+                                 uint32_t counts[3], uint64_t* fcz_bytes) {
+    if (!fcz_bytes || !counts || !undense_args_ok(ctx, in, n, L, layout, anchor_threshold)) return FCZ_E_INVALID_ARG;
+    *fcz_bytes = 0; ctx->ud_fcz_bytes = 0;
+    fcz_chain_batch b;
+    int rc = fcz_undense_dev(ctx, in, n, L, layout, anchor_threshold, &b, counts, nullptr);
+    if (rc || n == 0) return rc;
+    ctx->sizes_fresh = false;   // staging buffers are rewritten
+    if ((rc = compress_resident_batch(ctx, ctx->ud_batch, &ctx->ud_fcz_bytes, fcz_bytes))) return rc;
+    hipLaunchKernelGGL(k_undense_merge_status, dim3(grid_for(n, BLOCK)), dim3(BLOCK), 0, ctx->stream, n, ctx->ud_status, ctx->stage[15].as<int32_t>());
+    HIP_TRY(hipGetLastError());
+    return FCZ_OK;
+}
+
+static int compress_dense_fetch(fcz_ctx* ctx, uint64_t* out_off, int32_t* status, uint8_t* blob, hipMemcpyKind kind) {
+    if (!ctx) return FCZ_E_INVALID_ARG;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const uint32_t C = ctx->ud_batch.n_chains;
+    if (C) {
+        if (out_off) HIP_TRY(hipMemcpyAsync(out_off, ctx->stage[13].p, 8 * ((size_t)C + 1), kind, ctx->stream));
+        if (status) HIP_TRY(hipMemcpyAsync(status, ctx->stage[15].p, 4 * (size_t)C, kind, ctx->stream));
+        if (ctx->ud_fcz_bytes) {
+            if (!blob) return FCZ_E_INVALID_ARG;
+            HIP_TRY(hipMemcpyAsync(blob, ctx->stage[14].p, ctx->ud_fcz_bytes, kind, ctx->stream));
+        }
+    } else if (out_off) {
+        if (kind == hipMemcpyDeviceToHost) out_off[0] = 0; else HIP_TRY(hipMemsetAsync(out_off, 0, 8, ctx->stream));
+    }
+    if (kind == hipMemcpyDeviceToHost) HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return FCZ_OK;
+}
+
+int fcz_compress_dense_fetch_dev(fcz_ctx* ctx, uint64_t* out_off_dev, int32_t* status_dev, uint8_t* blob_dev) {
+    return compress_dense_fetch(ctx, out_off_dev, status_dev, blob_dev, hipMemcpyDeviceToDevice);
+}
+
+int fcz_compress_dense_begin(fcz_ctx* ctx, const fcz_dense_in* in, uint32_t n, uint32_t L, int layout, int anchor_threshold,
+                             uint32_t counts[3], uint64_t* fcz_bytes) {
+    if (!fcz_bytes || !counts || !undense_args_ok(ctx, in, n, L, layout, anchor_threshold)) return FCZ_E_INVALID_ARG;
+    *fcz_bytes = 0; ctx->ud_fcz_bytes = 0;
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (n == 0) return fcz_compress_dense_begin_dev(ctx, in, 0, L, layout, anchor_threshold, counts, fcz_bytes);
+    ctx->sizes_fresh = false;   // staging buffers are rewritten
+    const size_t C = n, rows = C * (size_t)L, A = (size_t)fcz_dense_width(layout);
+    const size_t title_bytes = in->title_off ? in->title_off[n] : 0;
+    const void* host[10] = {in->pos, in->mask, in->aatype, in->length, in->plddt, in->first_res_index, in->first_atom_index, in->chain_id,
+                            in->titles, in->title_off};
+    const size_t bytes[10] = {rows * A * 3 * sizeof(float), rows * A, rows, 4 * C, rows * sizeof(float), 4 * C, 4 * C, C, title_bytes, 4 * (C + 1)};
+    const void* dev[10];
+    for (int i = 0; i < 10; i++) {
+        dev[i] = nullptr;
+        if (!host[i]) continue;
+        int rc = ctx->stage[i].ensure(std::max<size_t>(bytes[i], 16));
+        if (rc) return rc;
+        dev[i] = ctx->stage[i].p;
+        if (bytes[i]) HIP_TRY(hipMemcpyAsync(ctx->stage[i].p, host[i], bytes[i], hipMemcpyHostToDevice, ctx->stream));
+    }
+    const fcz_dense_in dv{(const float*)dev[0], (const uint8_t*)dev[1], (const uint8_t*)dev[2], (const uint32_t*)dev[3], (const float*)dev[4],
+                          (const int32_t*)dev[5], (const int32_t*)dev[6], (const char*)dev[7], (const char*)dev[8], (const uint32_t*)dev[9]};
+    return fcz_compress_dense_begin_dev(ctx, &dv, n, L, layout, anchor_threshold, counts, fcz_bytes);
+}
+
+int fcz_compress_dense_fetch(fcz_ctx* ctx, uint64_t* out_off, int32_t* status, uint8_t* blob) {
+    return compress_dense_fetch(ctx, out_off, status, blob, hipMemcpyDeviceToHost);
 }
 
 // ------------------------------------------------------------------------------------------------

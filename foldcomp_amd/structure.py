@@ -968,6 +968,13 @@ class CDenseOut(ctypes.Structure):
                 ("plddt", ctypes.c_void_p), ("res_index", ctypes.c_void_p), ("length", ctypes.c_void_p)]
 
 
+class CDenseIn(ctypes.Structure):
+    """fcz_dense_in (include/fcz_hip.h): dense tensors + per-chain header fields handed to the undense / compress_dense calls"""
+    _fields_ = [("pos", ctypes.c_void_p), ("mask", ctypes.c_void_p), ("aatype", ctypes.c_void_p), ("length", ctypes.c_void_p),
+                ("plddt", ctypes.c_void_p), ("first_res_index", ctypes.c_void_p), ("first_atom_index", ctypes.c_void_p),
+                ("chain_id", ctypes.c_void_p), ("titles", ctypes.c_void_p), ("title_off", ctypes.c_void_p)]
+
+
 class CEntryInfo(ctypes.Structure):
     _fields_ = [("n_residues", ctypes.c_uint32), ("n_atoms_out", ctypes.c_uint32),
                 ("n_atoms_header", ctypes.c_uint32), ("first_res_index", ctypes.c_int32),

@@ -1,12 +1,15 @@
-"""FCZ records -> dense padded model-input tensors that never leave the GPU.
+"""FCZ records <-> dense padded model-input tensors that never leave the GPU.
 
     decode_tensors(entries) -> dict(pos [n, L, A, 3] float32, mask [n, L, A] bool, aatype [n, L] uint8, plddt [n, L] float32,
                                     res_index [n, L] int32, length [n] int32, names list[str])
+    encode_tensors(that dict, or the tensors as keywords) -> [fcz, ...]
 
 What a structure model's data loader wants from a Foldcomp database (atom37 / atom14 coordinates with a mask, residue types,
 pLDDT), without the PDB text `foldcomp.decompress` returns and without a host copy of the result: the records go up once, torch
 allocates the outputs, and fcz_decompress_sizes_dev / fcz_decompress_batch_dev / fcz_dense_dev (include/fcz_hip.h) fill them in
-place. The coordinates are the decoder's float32 values bit for bit (the text keeps three decimals).
+place. The coordinates are the decoder's float32 values bit for bit (the text keeps three decimals). The way back
+(fcz_compress_dense_begin_dev / _fetch_dev) gathers the masked atoms into the codec's flat batch and compresses it where the tensors
+lie: only the records and their offsets come to the host.
 
 torch is imported inside the functions only: `import foldcomp` does not touch it.
 """
@@ -19,9 +22,9 @@ import numpy as np
 
 from . import _lib, api, fczfile
 from .codec import Codec, dense_layout
-from .structure import CAtomsOut, CDenseOut
+from .structure import CAtomsOut, CDenseIn, CDenseOut
 
-__all__ = ["decode_tensors"]
+__all__ = ["decode_tensors", "encode_tensors"]
 
 
 def _torch_device(device):
@@ -122,3 +125,121 @@ def decode_tensors(entries: Sequence[bytes], *, layout="atom37", max_len: Option
                                    ctypes.byref(atoms), 0, lay, L, ctypes.byref(dense)), "fcz_dense_dev")
     c.synchronize()
     return result(L, *out)
+
+
+_WIDTH_LAYOUT = {37: "atom37", 14: "atom14", 4: "backbone4"}
+
+
+def encode_tensors(batch=None, *, names=None, layout=None, anchor_residue_threshold: int = 25, codec: Optional[Codec] = None,
+                   skip_bad: bool = False, **tensors) -> list:
+    """dense tensors on the GPU -> [fcz bytes, ...], one record per chain.
+
+    `batch` is the dict decode_tensors / FoldcompDatabase.tensor_batches return, as it is (its `names` become the records' titles,
+    res_index[:, 0] the first residue number), or the tensors come as keywords: pos [n, L, A, 3] float32, mask [n, L, A] bool or
+    uint8, aatype [n, L] uint8, length [n] int32 / int64, and optionally plddt [n, L] float32 (default 0) and res_index [n, L] or
+    first_res_index [n] (default 1). `names` given here wins over the dict's. layout: inferred from A (37 / 14 / 4) when None.
+
+    Of row l of chain c only l < length[c] counts, and of its atoms only those whose mask is set in a slot the residue type owns;
+    everything else may hold anything. A chain the codec refuses (aatype > 20, a residue without N, CA and C, length above L,
+    fewer than two residues, a NaN or an infinity in a present atom) raises foldcomp.error, or gives None under skip_bad=True.
+
+    The tensors must be contiguous and lie on the codec's device. Ordering against torch is decode_tensors': torch's current stream
+    is synchronised before the codec's calls, the codec's stream before the function returns. Only the records, their offsets and
+    the per-chain status come to the host.
+    """
+    if not isinstance(anchor_residue_threshold, int):
+        raise TypeError("anchor_residue_threshold must be an integer")
+    d = dict(batch) if batch is not None else {}
+    d.update(tensors)
+    for k in ("pos", "mask", "aatype", "length"):
+        if d.get(k) is None:
+            raise TypeError(f"encode_tensors needs the tensor {k!r}")
+    c = codec or api.default_codec()
+    try:
+        import torch
+    except ImportError as e:
+        raise api.error(f"encode_tensors needs PyTorch (ROCm build): {e}") from None
+    pos = d["pos"]
+    if not isinstance(pos, torch.Tensor):
+        raise api.error("encode_tensors takes torch tensors on the GPU (numpy arrays: Codec.compress_dense)")
+    if pos.device.type != "cuda" or pos.device.index != int(c.device):
+        raise api.error(f"encode_tensors: pos lies on {pos.device}, the codec works on cuda:{int(c.device)}; "
+                        "the records are built where the tensors are and there is no CPU path")
+    dev = pos.device
+    if pos.dim() != 4 or pos.shape[3] != 3 or pos.dtype != torch.float32:
+        raise ValueError(f"pos must be float32 [n, L, A, 3], not {pos.dtype} {tuple(pos.shape)}")
+    n, L, A = int(pos.shape[0]), int(pos.shape[1]), int(pos.shape[2])
+    if layout is None:
+        if A not in _WIDTH_LAYOUT:
+            raise ValueError(f"no dense layout has {A} slots per residue (37, 14 or 4)")
+        layout = _WIDTH_LAYOUT[A]
+    lay = dense_layout(layout)
+    if c.lib.fcz_dense_width(lay) != A:
+        raise ValueError(f"layout {layout!r} has {c.lib.fcz_dense_width(lay)} slots per residue, pos has {A}")
+    names = d.get("names") if names is None else names
+    if names is not None and len(names) != n:
+        raise ValueError(f"{len(names)} names for {n} chains")
+
+    def on_device(key, t, shape, dtypes):
+        if not isinstance(t, torch.Tensor) or t.device != dev:
+            where = t.device if isinstance(t, torch.Tensor) else type(t).__name__
+            raise api.error(f"encode_tensors: {key} lies on {where}, pos on {dev}; every tensor must be on the codec's device")
+        if tuple(t.shape) != shape or t.dtype not in dtypes:
+            raise ValueError(f"{key} must be {' / '.join(str(x) for x in dtypes)} {shape}, not {t.dtype} {tuple(t.shape)}")
+        if not t.is_contiguous():
+            raise ValueError(f"encode_tensors: {key} must be contiguous")
+        return t
+
+    on_device("pos", pos, (n, L, A, 3), (torch.float32,))
+    mask = on_device("mask", d["mask"], (n, L, A), (torch.bool, torch.uint8))
+    aatype = on_device("aatype", d["aatype"], (n, L), (torch.uint8,))
+    length = on_device("length", d["length"], (n,), (torch.int32, torch.int64))
+    plddt = on_device("plddt", d["plddt"], (n, L), (torch.float32,)) if d.get("plddt") is not None else None
+    first = None
+    if d.get("first_res_index") is not None:
+        first = on_device("first_res_index", d["first_res_index"], (n,), (torch.int32, torch.int64)).to(torch.int32)
+    elif d.get("res_index") is not None and L:
+        first = on_device("res_index", d["res_index"], (n, L), (torch.int32,))[:, 0].contiguous()
+    if n == 0:
+        return []
+    if L == 0:
+        raise ValueError("encode_tensors: the tensors have no rows (L = 0)")
+    if bool((length < 0).any()):
+        raise ValueError("length must not be negative")
+    keep = [mask.view(torch.uint8), length.to(torch.int32)]         # (int32 >= 0 and uint32 share their bits)
+    s = CDenseIn(pos.data_ptr(), keep[0].data_ptr(), aatype.data_ptr(), keep[1].data_ptr())
+    if plddt is not None:
+        s.plddt = plddt.data_ptr()
+    if first is not None:
+        keep.append(first)
+        s.first_res_index = first.data_ptr()
+    if names is not None:
+        tb = [str(t).encode("latin-1", "replace") for t in names]
+        toff = np.zeros(n + 1, np.uint32)
+        toff[1:] = np.cumsum([len(t) for t in tb])
+        keep += [torch.from_numpy(np.frombuffer(b"".join(tb) + b"\0", np.uint8).copy()).to(dev),
+                 torch.from_numpy(toff.view(np.int32)).to(dev)]
+        s.titles, s.title_off = keep[-2].data_ptr(), keep[-1].data_ptr()
+    torch.cuda.current_stream(dev).synchronize()
+    counts = np.zeros(3, np.uint32)
+    nbytes = ctypes.c_uint64(0)
+    _lib.check(c.lib.fcz_compress_dense_begin_dev(c.ctx, ctypes.byref(s), n, L, lay, int(anchor_residue_threshold), counts.ctypes.data,
+                                                  ctypes.byref(nbytes)), "fcz_compress_dense_begin_dev")
+    blob_t = torch.empty(max(int(nbytes.value), 1), dtype=torch.uint8, device=dev)
+    off_t = torch.empty(n + 1, dtype=torch.int64, device=dev)
+    st_t = torch.empty(n, dtype=torch.int32, device=dev)
+    torch.cuda.current_stream(dev).synchronize()
+    _lib.check(c.lib.fcz_compress_dense_fetch_dev(c.ctx, off_t.data_ptr(), st_t.data_ptr(), blob_t.data_ptr()), "fcz_compress_dense_fetch_dev")
+    c.synchronize()
+    off = off_t.cpu().numpy()
+    st = st_t.cpu().numpy()
+    blob = blob_t.cpu().numpy()
+    out = []
+    for i in range(n):
+        if st[i] != 0:
+            if not skip_bad:
+                raise api.error(f"Error compressing chain {i}: " + c.lib.fcz_status_string(int(st[i])).decode())
+            out.append(None)
+        else:
+            out.append(blob[int(off[i]):int(off[i + 1])].tobytes())
+    return out

@@ -16,6 +16,7 @@
  *     src/foldcomp.cpp:779
  *   Foldcomp::checkValidity()        src/foldcomp.cpp:1492   fcz_check
  *   (none: the reference stops at the flat atom vector)    fcz_dense_dev / fcz_decompress_dense
+ *   (none: Foldcomp::compress starts from the flat list)   fcz_undense_dev / fcz_compress_dense_begin[_dev]
  *
  * Batch-first: one call handles C independent chains ("one wavefront per chain" on the device).
  * Data layout is structure-of-arrays; all offsets are element indices, not bytes, unless noted.
@@ -285,6 +286,74 @@ int fcz_dense_dev(fcz_ctx* ctx, const uint8_t* blob_dev, const uint64_t* off_dev
 int fcz_decompress_dense(fcz_ctx* ctx, const uint8_t* blob, const uint64_t* off, uint32_t n, int layout, uint32_t L,
                          uint32_t* L_out, const fcz_dense_out* out, int32_t* status);
 
+/* ---- dense model-input tensors -> fcz_chain_batch -> FCZ records ---------------------------------------- */
+/* The way back: n chains held as the padded arrays above (a model's predictions, a filtered or re-cropped set, what fcz_dense_dev
+ * wrote) become the flat structure-of-arrays batch fcz_compress_sizes_dev / fcz_compress_batch_dev take, on the device. These entry
+ * points stand in front of Foldcomp::compress (src/foldcomp.cpp:562; preprocess :450), which starts from a flat
+ * span<AtomCoordinate>; the reference has no dense input.
+ * Input (layouts and A as above; every array row-major and naturally aligned):
+ *   pos [n][L][A][3] float32, mask [n][L][A] uint8 (any non-zero byte = present), aatype [n][L] uint8, length [n] uint32: required
+ *   plddt [n][L] float32: optional, NULL = 0 (the residue's B-factor, bfac_ca)
+ *   first_res_index [n] (NULL = 1), first_atom_index [n] (NULL = 1), chain_id [n] (NULL = 'A'), titles + title_off [n + 1] (byte
+ *   offsets; both or neither, NULL = empty titles): the header fields of the records.
+ * Contract:
+ *   residue codes    aatype 0 .. 19 = A R N D C Q E G H I L K M F P S T W Y V = residue codes 0 .. 19 (what fcz_dense_dev wrote);
+ *                    20 = UNK (code 23); a larger value refuses the chain (FCZ_E_RESIDUE).
+ *   atoms            of row l < length[c]: the slots with mask != 0 that the residue's type owns in the layout (fcz_dense_slot), in
+ *                    the canonical order fcz_res_code_atom(res_code, j, 0). A set mask byte in a slot the type does not own is
+ *                    ignored; UNK owns N, CA, C only; backbone4 gives N, CA, C, O.
+ *   missing atoms    a side-chain atom whose mask is 0 is absent from the batch; the compress kernels read the all-zero record
+ *                    for it, as the reference does (findFirstAtomCoords, src/sidechain.cpp:140-147).
+ *   OXT              atom37 only: slot 36 of row length[c] - 1, when its mask is set, becomes the chain's last atom (code 36, inside
+ *                    the last residue's atom range). A set slot 36 on any other row is ignored. atom14 / backbone4: no OXT.
+ *   never data       pos where mask == 0, and every array in rows l >= length[c], may hold NaN, infinities or garbage: nothing of
+ *                    it reaches the batch or raises FCZ_E_NONFINITE. A non-finite value in a present atom or in the plddt of a row
+ *                    l < length[c] is refused by the compress kernels as for any batch (FCZ_E_NONFINITE).
+ *   refusals         per chain; the call succeeds and the neighbours are untouched. length[c] > L or > 65535: FCZ_E_INVALID_ARG;
+ *                    aatype > 20, or a row l < length[c] without all of N, CA and C: FCZ_E_RESIDUE. A refused chain keeps its place
+ *                    in the batch with ZERO residues and atoms (its title and header fields stay): its record range has the size
+ *                    fcz_compress_sizes gives a chain without residues and is filled with zeros, as for every chain the pack
+ *                    kernels refuse. length[c] < 2 is not refused here: the chain enters the batch as it is and the compress
+ *                    kernels answer FCZ_E_TOO_SHORT. fcz_compress_dense_* report the refusal of this stage in status[c] in place
+ *                    of the FCZ_E_TOO_SHORT the empty range would earn.
+ *   sizes            every index into the dense arrays is 64-bit (n * L * A * 3 may pass 2^32). The flat batch counts in 32 bits:
+ *                    when the chains' residues or atoms sum beyond 2^32 - 1 the call returns FCZ_E_INVALID_ARG before the batch
+ *                    is allocated or filled (the sums exist only after the counting pass over the masks).
+ * Bad arguments (NULL ctx, unknown layout, L == 0, anchor_threshold <= 0, NULL pos / mask / aatype / length, titles without
+ * title_off or the reverse): FCZ_E_INVALID_ARG, nothing launched; n == 0: FCZ_OK. */
+typedef struct fcz_dense_in {
+    const float*    pos;              /* [n][L][A][3] */
+    const uint8_t*  mask;             /* [n][L][A] */
+    const uint8_t*  aatype;           /* [n][L] */
+    const uint32_t* length;           /* [n] */
+    const float*    plddt;            /* [n][L] optional */
+    const int32_t*  first_res_index;  /* [n] optional */
+    const int32_t*  first_atom_index; /* [n] optional */
+    const char*     chain_id;         /* [n] optional */
+    const char*     titles;           /* optional, with title_off */
+    const uint32_t* title_off;        /* [n + 1] */
+} fcz_dense_in;
+/* Device-resident: every pointer inside in_dev a device pointer. *out = the batch in HBM, as fcz_ingest_pdb_dev leaves one: its
+ * arrays are owned by the ctx and valid until its next undense call, except the header fields and titles the caller passed, which
+ * the batch refers to where they are (keep them until the compress calls have run). counts = {chains, residues, atoms};
+ * chain_status_dev[n] (may be NULL) receives FCZ_OK or the refusal of this stage. One stream synchronisation (the totals). */
+int fcz_undense_dev(fcz_ctx* ctx, const fcz_dense_in* in_dev, uint32_t n, uint32_t L, int layout, int anchor_threshold,
+                    fcz_chain_batch* out, uint32_t counts[3], int32_t* chain_status_dev);
+/* the resident batch of the last undense call copied to the host (every pointer of host_batch caller-allocated for its counts, titles
+ * for title_off[n] bytes; the struct's const is cast away; NULL = not wanted) and its per-chain verdicts (may be NULL) */
+int fcz_undense_fetch(fcz_ctx* ctx, const fcz_chain_batch* host_batch, int32_t* chain_status);
+/* Tensors in, FCZ records out: fcz_undense_dev + fcz_compress_sizes_dev + fcz_compress_batch_dev on the resident batch, begin / fetch
+ * as fcz_compress_pdb_begin / _fetch because the blob's size is known only after the sizes pass. begin(): counts as above,
+ * *fcz_bytes = size of the blob; fetch(): record offsets out_off[n + 1], per-chain status[n] (either may be NULL), then the blob.
+ * _dev: device pointers in, and the records are copied device-to-device into caller-allocated buffers (torch tensors) on the ctx
+ * stream, no synchronisation in fetch. Without _dev: host pointers, for numpy callers and tests. */
+int fcz_compress_dense_begin_dev(fcz_ctx* ctx, const fcz_dense_in* in_dev, uint32_t n, uint32_t L, int layout, int anchor_threshold,
+                                 uint32_t counts[3], uint64_t* fcz_bytes);
+int fcz_compress_dense_fetch_dev(fcz_ctx* ctx, uint64_t* out_off_dev, int32_t* status_dev, uint8_t* blob_dev);
+int fcz_compress_dense_begin(fcz_ctx* ctx, const fcz_dense_in* in, uint32_t n, uint32_t L, int layout, int anchor_threshold,
+                             uint32_t counts[3], uint64_t* fcz_bytes);
+int fcz_compress_dense_fetch(fcz_ctx* ctx, uint64_t* out_off, int32_t* status, uint8_t* blob);
+
 /* ---- structure ingest: PDB / mmCIF text -> fcz_chain_batch on the device ----------------------------- */
 /* What the reference's driver does to every input file before Foldcomp::compress (src/main.cpp:455-508): StructureReader
  * (src/structure_reader.cpp:31-61; the fixed-column ATOM / HETATM record as foldcomp/foldcomp.cxx:259-278 reads it),
@@ -430,7 +499,8 @@ int fcz_check(const uint8_t* entry, uint64_t len);
 /* Accumulated device time (ms, HIP events on the ctx stream) and launch count of the named kernel
  * group since the last reset: "compress_sizes", "compress_index", "compress_angles", "compress_pack",
  * "decompress_sizes", "decompress_backbone", "decompress_index", "decompress_sidechain", "pdb_sizes", "pdb_format", "extract_sizes", "extract",
- * "ingest_parse", "ingest_parse_cif", "ingest_rows_cif", "ingest_frags", "ingest_fill", "inflate", "dense". */
+ * "ingest_parse", "ingest_parse_cif", "ingest_rows_cif", "ingest_frags", "ingest_fill", "inflate", "dense", "undense" (the counting and the fill
+ * kernel of fcz_undense_dev: two launches per call). */
 int  fcz_ctx_enable_timing(fcz_ctx* ctx, int enable);
 int  fcz_ctx_kernel_time(fcz_ctx* ctx, const char* name, double* ms, uint64_t* launches);
 void fcz_ctx_reset_timing(fcz_ctx* ctx);

@@ -9,6 +9,7 @@
 #include <cstring>
 #include <map>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "fcz_kernels.h"
@@ -54,9 +55,13 @@ using namespace fcz;
 
 namespace {
 
+// a device allocation that only grows; freed with its owner
 struct dev_buf {
     void* p = nullptr;
     size_t cap = 0;
+    dev_buf() = default;
+    dev_buf(const dev_buf&) = delete; dev_buf& operator=(const dev_buf&) = delete;
+    ~dev_buf() { if (p) (void)hipFree(p); }
     int ensure(size_t bytes) {
         if (bytes <= cap) return FCZ_OK;
         if (p) (void)hipFree(p);
@@ -66,42 +71,87 @@ struct dev_buf {
         cap = want;
         return FCZ_OK;
     }
-    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
-    template <class T> T* as() { return reinterpret_cast<T*>(p); }
+    template <class T> T* as() const { return reinterpret_cast<T*>(p); }
 };
 
 struct timed_span { std::string name; hipEvent_t a, b; };
+
+// fcz_ctx::pool, the staging of the host-pointer entry points: the names a buffer has, one per role. Roles that share a buffer are
+// never live together (table in fcz_ctx). REC_*: uploaded FCZ records (n + 1 u64 offsets), their res_off / atom_off (n + 1 u32) and
+// the fcz_atoms_out decoded from them; FILES_*: structure files of an ingest call; BATCH_IN / DENSE_IN / DENSE_OUT: first of the 13
+// arrays of a fcz_chain_batch, the 10 of a fcz_dense_in, the 6 of a fcz_dense_out, in the struct's order; KEPT_*: the records a
+// *_begin call leaves for its fetch (C + 1 u64 offsets, the bytes, C i32 status)
+enum { REC_BLOB, REC_OFF, REC_RES_OFF, REC_ATOM_OFF, REC_X, REC_Y, REC_Z, REC_BFAC, REC_RES_CODE, REC_ATOM_CODE,
+       FILES_TEXT = 0, FILES_OFF, FILES_NAMES, FILES_NAME_OFF, FILES_STEM_LEN, BATCH_IN = 0, DENSE_IN = 0, DENSE_OUT = 10,
+       KEPT_OFF = 13, KEPT_BYTES, KEPT_STATUS, POOL_COUNT };
+
+// what the device reports to the host in the middle of a call: one pinned allocation, a member per reader
+struct pinned_words {
+    sizes_totals sizes;                                                                     // run_entry_sizes (one copy of the device's struct)
+    struct { uint32_t chains, residues, atoms, title_bytes, overflow, refused; } ingest;    // fcz_ingest_pdb_dev
+    uint64_t record_bytes;                                                                  // compress_resident_batch
+    struct { uint32_t residues, atoms, overflow; } undense;                                 // fcz_undense_dev
+};
+
+// fcz_ctx::ig, the buffers of the structure ingest: scratch atom table and per-file lists of fcz_ingest_pdb_dev, then (B_OUT_*) the
+// arrays of the resident batch, which fcz_ingest_pdb_fetch / fcz_compress_pdb_fetch read until the next ingest call
+enum { B_CAP, B_ABASE, B_NAME, B_RESN, B_SERIAL, B_RESSEQ, B_X, B_Y, B_Z, B_B, B_CHAIN, B_ACODE, B_RCODE, B_RFIRST, B_RBFAC, B_RCODE2,
+       B_TITLES, B_TLEN, B_NKEPT, B_STATUS, B_FRAGS, B_NFRAGS, B_TOTC, B_TOTR, B_TOTA, B_TOTT, B_USESTEM, B_OFFC, B_OFFR, B_OFFA, B_OFFT,
+       B_REFUSED, B_NREF, B_OUT_A, B_OUT_R, B_OUT_C, B_OUT_T, B_CIFROWS, B_COUNT };
+// fcz_ctx::ud, the buffers of fcz_undense_dev: per-row words, per-chain counts / verdicts / offsets, then (U_OUT_*) the arrays of
+// the resident batch, which fcz_undense_fetch reads until the next undense call
+enum { U_ROWS, U_CHAIN, U_OUT_A, U_OUT_R, U_OUT_C, U_COUNT };
 
 }  // namespace
 
 struct fcz_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
-    // scratch
-    dev_buf ang;        // compress: 6 x R floats
+    // scratch of the device entry points: dead when the call that filled it returns, unless it says otherwise
+    dev_buf ang;        // compress: 6 x R floats (read once more by fcz_compress_angles)
     dev_buf sizes;      // compress: C x u64
     dev_buf scan_tmp;   // block partials of the device scans
-    dev_buf codes;      // decompress: residue codes, one byte per residue at (record offset >> 3) + k (k_entry_sizes -> k_res_index)
+    dev_buf codes;      // decompress: residue codes, one byte per residue at (record offset >> 3) + k (k_entry_sizes -> k_res_index); kept for the sizes memo
     dev_buf res_sc_addr; // compress: residue -> output byte offset of its side-chain torsion bytes
-    dev_buf tile_work;   // compress: per 256-residue tile flag + list + count of the tiles left to the block-tile kernel
+    // one layout per direction, each derived in one place. fcz_compress_batch_dev: [n_tiles] flag per 256-residue tile, [n_tiles] list and
+    // [4] count of the tiles left to the block-tile kernel, then one bit per chain (a batch without residues: the bits alone).
+    // fcz_decompress_batch_dev: [4] count and [2 x n_tiles] list of the half tiles the first k_sidechain launch leaves to the second
+    dev_buf tile_work;
     // decompress: the totals and the length order computed by fcz_decompress_sizes_dev are reused by the
     // fcz_decompress_batch_dev call that follows on the same entries
     const void* sized_blob = nullptr; const void* sized_off = nullptr; uint32_t sized_n = 0, sized_R = 0, sized_maxseg = 0, sized_maxnseg = 0, sized_nlong = 0;
     bool sizes_fresh = false;
-    dev_buf cnt;        // decompress: 2 x n u32 counts (residues, atoms) + n i32 status + n u32 segment info
+    dev_buf cnt;        // decompress: 2 x n u32 counts (residues, atoms) + n i32 status (cnt_status) + n u32 segment info; kept for the sizes memo
     dev_buf fwd;        // decompress: per-group ring of forward atoms (one segment deep)
     dev_buf wring;      // decompress: per-group ring of cos/sin of the segment's torsions
     dev_buf fwd_long, wring_long;   // decompress: the same per (group, segment) for the long chains' split form
     dev_buf bb;         // decompress: blended backbone
-    dev_buf len_perm;   // decompress: entries ordered by residue count (n u32) + bucket counters (2 x LEN_BUCKETS + 1)
+    dev_buf len_perm;   // decompress: entries ordered by residue count (n u32) + bucket counters (2 x LEN_BUCKETS + 1); kept for the sizes memo
     dev_buf res_aoff;   // decompress: residue -> first output atom
     dev_buf res_rc;     // decompress: residue -> residue code
     dev_buf res_sc;     // decompress: residue -> its side-chain torsion bytes, 3 x R dwords
-    // staging for the host-pointer entry points
-    dev_buf stage[20];
-    dev_buf pdb_size, pdb_off, pdb_text;   // PDB text: per-entry sizes, offsets (n+1 u64), the text of the last begin() call
+    dev_buf sizes_res_off;   // decompress: the res_off of a batch call that has to run its own sizes pass (ensure_sizes)
+    dev_buf selftest_out;    // fcz_selftest_math
+    dev_buf fast_scratch;    // decompress, FCZ_NUMERICS_FAST: forward atoms of segments longer than one chunk
+    // Staging of the host-pointer entry points. Every entry point that writes it calls claim_staging first. Nothing outlives the call
+    // that wrote it but KEPT_*, which a begin leaves for its fetch: any later call that writes 13 .. 15 ends that.
+    //   entry point                                 writes pool[]                               left for a fetch
+    //   fcz_decompress_batch                        REC_* 0 .. 9
+    //   fcz_decompress_pdb_begin / _sizes           REC_* 0 .. 8                                (pdb_text, pdb_bytes)
+    //   fcz_extract                                 REC_BLOB, REC_OFF
+    //   fcz_decompress_dense                        REC_* 0 .. 8, DENSE_OUT 10 .. 15
+    //   fcz_compress_batch                          BATCH_IN 0 .. 12, KEPT_* 13 .. 15
+    //   fcz_inflate                                 FILES_TEXT
+    //   fcz_ingest_pdb_begin / fcz_ingest_gz_begin  FILES_* 0 .. 4 (gz: no FILES_OFF, gz_toff)      (ig[], ig_res, ig_counts)
+    //   fcz_compress_pdb_begin / _gz_begin          the same, then KEPT_* 13 .. 15              KEPT_*, ig_fcz_bytes (+ ig[], ig_res)
+    //   fcz_compress_dense_begin                    DENSE_IN 0 .. 9, then KEPT_* 13 .. 15       KEPT_*, ud_fcz_bytes (+ ud_batch)
+    //   fcz_compress_dense_begin_dev                KEPT_* 13 .. 15                             KEPT_*, ud_fcz_bytes (+ ud_batch)
+    dev_buf pool[POOL_COUNT];
+    // PDB text / extracted data: per-entry sizes (any call), offsets (n + 1 u64) and the text of the last fcz_decompress_pdb_begin,
+    // which fcz_decompress_pdb_fetch reads: live until the next fcz_decompress_pdb_begin / _sizes or fcz_extract
+    dev_buf pdb_size, pdb_off, pdb_text;
     uint64_t pdb_bytes = 0;
-    uint32_t* pinned = nullptr;  // 16 words
+    pinned_words* pinned = nullptr;
     hipStream_t stream2 = nullptr;   // long chains of a decompress batch run beside the rest
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     int n_cu = 256;
@@ -112,19 +162,20 @@ struct fcz_ctx {
     // leaves out stages of the call so that ONE kernel fills the device for seconds (1 backbone, 2 residue index, 4 side chains;
     // unset = all). The outputs are then stale by construction: never set outside a profiling run.
     unsigned profile_stages = 7u;
-    dev_buf fast_scratch;   // decompress, FCZ_NUMERICS_FAST: forward atoms of segments longer than one chunk
-    // structure ingest: scratch atom table, per-file lists, the resident batch of the last ingest call
-    dev_buf ig[40];
+    // structure ingest: its buffers, and the resident batch of the last ingest call as pointers into them (live until the next ingest call)
+    dev_buf ig[B_COUNT];
     fcz_ingest_result ig_res{};
     uint32_t ig_counts[5] = {0, 0, 0, 0, 0};
-    uint64_t ig_fcz_bytes = 0;
+    uint64_t ig_fcz_bytes = 0;       // size of KEPT_BYTES after fcz_compress_pdb_begin / _gz_begin
     // inflate in front of the ingest: the files' bytes as they came over the link, their offsets / kinds / text offsets / statuses
+    // (fcz_inflate, fcz_ingest_gz_begin: dead when the call returns)
     dev_buf gz_raw, gz_off, gz_kind, gz_toff, gz_status;
-    // dense tensors -> batch (fcz_undense.h): scratch, the resident batch of the last undense call and its per-chain verdicts
-    dev_buf ud[8];
+    // dense tensors -> batch (fcz_undense.h): its buffers, the resident batch of the last undense call and its per-chain verdicts as
+    // pointers into them -- and, for the optional arrays the caller gave, into the caller's (live until the next undense call)
+    dev_buf ud[U_COUNT];
     fcz_chain_batch ud_batch{};
     const int32_t* ud_status = nullptr;
-    uint64_t ud_fcz_bytes = 0;
+    uint64_t ud_fcz_bytes = 0;       // size of KEPT_BYTES after fcz_compress_dense_begin[_dev]
     std::vector<timed_span> spans;
     std::map<std::string, std::pair<double, uint64_t>> acc;
 };
@@ -167,6 +218,63 @@ int device_scan(fcz_ctx* ctx, const T* in, T* out, uint32_t n, uint32_t* overflo
     hipLaunchKernelGGL(HIP_KERNEL_NAME(k_scan_reduce<T>), dim3(nb), dim3(1024), 0, ctx->stream, n, in, part);
     hipLaunchKernelGGL(k_scan_u64, dim3(1), dim3(1024), 0, ctx->stream, nb, (const uint64_t*)part, (uint64_t*)part_ex);
     hipLaunchKernelGGL(HIP_KERNEL_NAME(k_scan_apply<T>), dim3(nb), dim3(1024), 0, ctx->stream, n, in, part_ex, out, overflow);
+    return FCZ_OK;
+}
+
+// Called by every entry point before it writes fcz_ctx::pool: the sizes memo may be keyed on buffers of the pool (an entry point that
+// sized the records it uploaded and decoded none), so it is dropped here and never outlives their contents.
+void claim_staging(fcz_ctx* ctx) { ctx->sizes_fresh = false; }
+
+// the arrays every reader of decoded atoms needs (atom_code is optional everywhere, res_code for the decoder that writes them)
+bool atoms_out_ok(const fcz_atoms_out* a, bool need_res_code = true) {
+    return a && a->x && a->y && a->z && a->bfac_res && (a->res_code || !need_res_code);
+}
+
+// per-entry status of the last sizes pass over n entries (cnt: 2 x n counts, then n status words, then n segment words)
+int32_t* cnt_status(fcz_ctx* ctx, uint32_t n) { return ctx->cnt.as<int32_t>() + 2 * (size_t)n; }
+
+// f(std::integral_constant<int, A>) for the width A of a dense layout that fcz_dense_width has accepted
+template <class F> void dispatch_layout(int layout, F&& f) {
+    if (layout == FCZ_DENSE_ATOM37) f(std::integral_constant<int, 37>{});
+    else if (layout == FCZ_DENSE_ATOM14) f(std::integral_constant<int, 14>{});
+    else f(std::integral_constant<int, 4>{});
+}
+
+// f(i, a.member, b.member, bytes) for the 13 arrays of a fcz_chain_batch in the order of BATCH_IN, until one does not return FCZ_OK;
+// a and b are batches with the counts of n and TB title bytes
+template <class A, class B, class F> int each_batch_array(A& a, B& b, const fcz_chain_batch& n, size_t TB, F f) {
+    const size_t C = n.n_chains, R = n.n_residues, M = n.n_atoms;
+    int rc;
+    if ((rc = f(0, a.res_off, b.res_off, 4 * (C + 1))) || (rc = f(1, a.atom_off, b.atom_off, 4 * (R + 1))) || (rc = f(2, a.x, b.x, 4 * M)) ||
+        (rc = f(3, a.y, b.y, 4 * M)) || (rc = f(4, a.z, b.z, 4 * M)) || (rc = f(5, a.atom_code, b.atom_code, M)) || (rc = f(6, a.res_code, b.res_code, R)) ||
+        (rc = f(7, a.bfac_ca, b.bfac_ca, 4 * R)) || (rc = f(8, a.first_res_index, b.first_res_index, 4 * C)) ||
+        (rc = f(9, a.first_atom_index, b.first_atom_index, 4 * C)) || (rc = f(10, a.chain_id, b.chain_id, C)) || (rc = f(11, a.titles, b.titles, TB)) ||
+        (rc = f(12, a.title_off, b.title_off, 4 * (C + 1))))
+        return rc;
+    return FCZ_OK;
+}
+// resident batch d -> the host arrays hb names (every array that has an element must be named)
+int fetch_batch(fcz_ctx* ctx, const fcz_chain_batch& hb, const fcz_chain_batch& d, size_t TB) {
+    return each_batch_array(hb, d, d, TB, [&](int, auto* dst, auto* src, size_t bytes) -> int {
+        if (!bytes) return FCZ_OK;
+        if (!dst) return FCZ_E_INVALID_ARG;
+        HIP_TRY(hipMemcpyAsync(const_cast<void*>((const void*)dst), src, bytes, hipMemcpyDeviceToHost, ctx->stream));
+        return FCZ_OK;
+    });
+}
+
+// the resident records of the last *_begin call (C chains, n_bytes) -> out_off[C + 1], status[C] (either may be null), blob; kind: to the host or the device
+int fetch_resident(fcz_ctx* ctx, uint32_t C, uint64_t n_bytes, uint64_t* out_off, int32_t* status, uint8_t* blob, hipMemcpyKind kind) {
+    if (C) {
+        if (out_off) HIP_TRY(hipMemcpyAsync(out_off, ctx->pool[KEPT_OFF].p, 8 * ((size_t)C + 1), kind, ctx->stream));
+        if (status) HIP_TRY(hipMemcpyAsync(status, ctx->pool[KEPT_STATUS].p, 4 * (size_t)C, kind, ctx->stream));
+        if (n_bytes) {
+            if (!blob) return FCZ_E_INVALID_ARG;
+            HIP_TRY(hipMemcpyAsync(blob, ctx->pool[KEPT_BYTES].p, n_bytes, kind, ctx->stream));
+        }
+    } else if (out_off) {
+        if (kind == hipMemcpyDeviceToHost) out_off[0] = 0; else HIP_TRY(hipMemsetAsync(out_off, 0, 8, ctx->stream));
+    }
     return FCZ_OK;
 }
 
@@ -228,7 +336,7 @@ int fcz_ctx_create(int device, fcz_ctx** out) {
     hipDeviceProp_t prop;
     c->n_cu = (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
     if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) { delete c; return FCZ_E_HIP; }
-    if (hipHostMalloc((void**)&c->pinned, 128, hipHostMallocDefault) != hipSuccess) { (void)hipStreamDestroy(c->stream); delete c; return FCZ_E_HIP; }
+    if (hipHostMalloc((void**)&c->pinned, sizeof(pinned_words), hipHostMallocDefault) != hipSuccess) { (void)hipStreamDestroy(c->stream); delete c; return FCZ_E_HIP; }
     if (hipStreamCreateWithFlags(&c->stream2, hipStreamNonBlocking) != hipSuccess ||
         hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming) != hipSuccess) { fcz_ctx_destroy(c); return FCZ_E_HIP; }
@@ -241,17 +349,13 @@ void fcz_ctx_destroy(fcz_ctx* c) {
     (void)hipSetDevice(c->device);
     drain_spans(c);
     (void)hipStreamSynchronize(c->stream);
-    c->ang.release(); c->res_sc_addr.release(); c->tile_work.release(); c->sizes.release(); c->scan_tmp.release(); c->codes.release(); c->cnt.release(); c->fwd.release(); c->bb.release(); c->wring.release(); c->fwd_long.release(); c->wring_long.release(); c->res_aoff.release(); c->len_perm.release(); c->pdb_size.release(); c->pdb_off.release(); c->pdb_text.release(); c->res_rc.release(); c->res_sc.release(); c->fast_scratch.release();
-    for (auto& b : c->stage) b.release();
-    for (auto& b : c->ig) b.release();
-    c->gz_raw.release(); c->gz_off.release(); c->gz_kind.release(); c->gz_toff.release(); c->gz_status.release();
-    for (auto& b : c->ud) b.release();
+    if (c->stream2) (void)hipStreamSynchronize(c->stream2);
     if (c->pinned) (void)hipHostFree(c->pinned);
     if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
     if (c->ev_join) (void)hipEventDestroy(c->ev_join);
-    if (c->stream2) { (void)hipStreamSynchronize(c->stream2); (void)hipStreamDestroy(c->stream2); }
+    if (c->stream2) (void)hipStreamDestroy(c->stream2);
     (void)hipStreamDestroy(c->stream);
-    delete c;
+    delete c;                                   // the device buffers go with it
 }
 
 void* fcz_ctx_stream(fcz_ctx* c) { return c ? (void*)c->stream : nullptr; }
@@ -271,8 +375,7 @@ int fcz_ctx_synchronize(fcz_ctx* c) {
 // ------------------------------------------------------------------------------------------------
 static int pdb_sizes_impl(fcz_ctx* ctx, const uint8_t* blob_dev, const uint64_t* off_dev, uint32_t n, const uint32_t* res_off_dev,
                           const uint32_t* atom_off_dev, const fcz_atoms_out* atoms_dev, uint32_t pad, uint64_t* text_off_dev) {
-    if (!ctx || !blob_dev || !off_dev || !res_off_dev || !atom_off_dev || !atoms_dev || !text_off_dev) return FCZ_E_INVALID_ARG;
-    if (!atoms_dev->x || !atoms_dev->y || !atoms_dev->z || !atoms_dev->bfac_res || !atoms_dev->res_code) return FCZ_E_INVALID_ARG;
+    if (!ctx || !blob_dev || !off_dev || !res_off_dev || !atom_off_dev || !atoms_out_ok(atoms_dev) || !text_off_dev) return FCZ_E_INVALID_ARG;
     HIP_TRY(hipSetDevice(ctx->device));
     int rc = ctx->pdb_size.ensure(sizeof(uint64_t) * (size_t)std::max<uint32_t>(n, 1)); if (rc) return rc;
     span_guard g(ctx, "pdb_sizes");
@@ -290,8 +393,7 @@ int fcz_pdb_sizes_dev(fcz_ctx* ctx, const uint8_t* blob_dev, const uint64_t* off
 int fcz_pdb_format_dev(fcz_ctx* ctx, const uint8_t* blob_dev, const uint64_t* off_dev, uint32_t n, const uint32_t* res_off_dev,
                        const uint32_t* atom_off_dev, const fcz_atoms_out* atoms_dev, int alt_order, const uint64_t* text_off_dev,
                        uint8_t* text_dev) {
-    if (!ctx || !blob_dev || !off_dev || !res_off_dev || !atom_off_dev || !atoms_dev || !text_off_dev || !text_dev) return FCZ_E_INVALID_ARG;
-    if (!atoms_dev->x || !atoms_dev->y || !atoms_dev->z || !atoms_dev->bfac_res || !atoms_dev->res_code) return FCZ_E_INVALID_ARG;
+    if (!ctx || !blob_dev || !off_dev || !res_off_dev || !atom_off_dev || !atoms_out_ok(atoms_dev) || !text_off_dev || !text_dev) return FCZ_E_INVALID_ARG;
     HIP_TRY(hipSetDevice(ctx->device));
     if (n == 0) return FCZ_OK;
     span_guard g(ctx, "pdb_format");
@@ -301,47 +403,54 @@ int fcz_pdb_format_dev(fcz_ctx* ctx, const uint8_t* blob_dev, const uint64_t* of
     return FCZ_OK;
 }
 
+// The records of a host-pointer call -> pool[REC_BLOB], [REC_OFF]; with R and M also the sizes pass over them into [REC_RES_OFF] /
+// [REC_ATOM_OFF] (*R residues, *M atoms, the per-entry status at cnt_status()) ...
+static int upload_records(fcz_ctx* ctx, const uint8_t* blob, const uint64_t* off, uint32_t n, uint32_t* R = nullptr, uint32_t* M = nullptr) {
+    int rc;
+    if ((rc = ctx->pool[REC_BLOB].ensure(std::max<uint64_t>(off[n], 16))) || (rc = ctx->pool[REC_OFF].ensure(sizeof(uint64_t) * ((size_t)n + 1)))) return rc;
+    if (R && ((rc = ctx->pool[REC_RES_OFF].ensure(sizeof(uint32_t) * ((size_t)n + 1))) || (rc = ctx->pool[REC_ATOM_OFF].ensure(sizeof(uint32_t) * ((size_t)n + 1))))) return rc;
+    HIP_TRY(hipMemcpyAsync(ctx->pool[REC_BLOB].p, blob, off[n], hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(ctx->pool[REC_OFF].p, off, sizeof(uint64_t) * ((size_t)n + 1), hipMemcpyHostToDevice, ctx->stream));
+    if (!R) return FCZ_OK;
+    return fcz_decompress_sizes_dev(ctx, ctx->pool[REC_BLOB].as<uint8_t>(), ctx->pool[REC_OFF].as<uint64_t>(), n, ctx->pool[REC_RES_OFF].as<uint32_t>(),
+                                    ctx->pool[REC_ATOM_OFF].as<uint32_t>(), R, M);
+}
+// ... the fcz_atoms_out of R residues and M atoms staged beside them ...
+static int stage_atoms(fcz_ctx* ctx, uint32_t R, uint32_t M, bool atom_code, fcz_atoms_out* dv) {
+    int rc;
+    for (dev_buf* b : {&ctx->pool[REC_X], &ctx->pool[REC_Y], &ctx->pool[REC_Z]}) if ((rc = b->ensure(std::max<size_t>(sizeof(float) * (size_t)M, 16)))) return rc;
+    if ((rc = ctx->pool[REC_BFAC].ensure(std::max<size_t>(sizeof(float) * (size_t)R, 16))) || (rc = ctx->pool[REC_RES_CODE].ensure(std::max<size_t>((size_t)R, 16)))) return rc;
+    if (atom_code && (rc = ctx->pool[REC_ATOM_CODE].ensure(std::max<size_t>((size_t)M, 16)))) return rc;
+    *dv = {ctx->pool[REC_X].as<float>(), ctx->pool[REC_Y].as<float>(), ctx->pool[REC_Z].as<float>(), ctx->pool[REC_BFAC].as<float>(), ctx->pool[REC_RES_CODE].as<uint8_t>(),
+           atom_code ? ctx->pool[REC_ATOM_CODE].as<uint8_t>() : nullptr};
+    return FCZ_OK;
+}
+// ... and the decode into them
+static int decode_records(fcz_ctx* ctx, uint32_t n, int alt_order, const fcz_atoms_out* dv) {
+    return fcz_decompress_batch_dev(ctx, ctx->pool[REC_BLOB].as<uint8_t>(), ctx->pool[REC_OFF].as<uint64_t>(), n, ctx->pool[REC_RES_OFF].as<uint32_t>(),
+                                    ctx->pool[REC_ATOM_OFF].as<uint32_t>(), alt_order, dv);
+}
+
 // Host-pointer convenience: FCZ entries in, PDB text out, everything in between on the device. begin() leaves the text in
 // the ctx and reports the per-entry text offsets; fetch() copies it out.
 static int pdb_begin_impl(fcz_ctx* ctx, const uint8_t* blob, const uint64_t* off, uint32_t n, int alt_order, uint64_t* text_off,
                           int32_t* status, bool format) {
     if (!ctx || !blob || !off || !text_off) return FCZ_E_INVALID_ARG;
     HIP_TRY(hipSetDevice(ctx->device));
+    claim_staging(ctx);
     const uint32_t pad = (alt_order & FCZ_PDB_NUL_TERMINATED) ? 1u : 0u;   // every entry followed by one NUL (a database record)
     alt_order &= FCZ_PDB_ALT_ORDER;
     ctx->pdb_bytes = 0;
-    ctx->sizes_fresh = false;   // the staging buffers the cache is keyed on are about to be rewritten
     if (n == 0) { text_off[0] = 0; return FCZ_OK; }
-    const uint64_t blob_bytes = off[n];
-    int rc;
-    if ((rc = ctx->stage[0].ensure(std::max<uint64_t>(blob_bytes, 16)))) return rc;
-    if ((rc = ctx->stage[1].ensure(sizeof(uint64_t) * ((size_t)n + 1)))) return rc;
-    if ((rc = ctx->stage[2].ensure(sizeof(uint32_t) * ((size_t)n + 1)))) return rc;
-    if ((rc = ctx->stage[3].ensure(sizeof(uint32_t) * ((size_t)n + 1)))) return rc;
-    HIP_TRY(hipMemcpyAsync(ctx->stage[0].p, blob, blob_bytes, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(ctx->stage[1].p, off, sizeof(uint64_t) * ((size_t)n + 1), hipMemcpyHostToDevice, ctx->stream));
     uint32_t R = 0, M = 0;
-    rc = fcz_decompress_sizes_dev(ctx, ctx->stage[0].as<uint8_t>(), ctx->stage[1].as<uint64_t>(), n, ctx->stage[2].as<uint32_t>(),
-                                  ctx->stage[3].as<uint32_t>(), &R, &M);
-    if (rc) return rc;
-    if (status) {   // per-entry status of the sizes pass (cnt layout: 2 x n counts, then n status words)
-        HIP_TRY(hipMemcpyAsync(status, ctx->cnt.as<uint32_t>() + 2 * (size_t)n, sizeof(int32_t) * n, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    for (int i = 4; i < 7; i++) if ((rc = ctx->stage[i].ensure(std::max<size_t>(sizeof(float) * (size_t)M, 16)))) return rc;
-    if ((rc = ctx->stage[7].ensure(std::max<size_t>(sizeof(float) * (size_t)R, 16)))) return rc;
-    if ((rc = ctx->stage[8].ensure(std::max<size_t>((size_t)R, 16)))) return rc;
+    int rc = upload_records(ctx, blob, off, n, &R, &M); if (rc) return rc;
+    if (status) HIP_TRY(hipMemcpyAsync(status, cnt_status(ctx, n), sizeof(int32_t) * n, hipMemcpyDeviceToHost, ctx->stream));
     fcz_atoms_out dv;
-    dv.x = ctx->stage[4].as<float>(); dv.y = ctx->stage[5].as<float>(); dv.z = ctx->stage[6].as<float>();
-    dv.bfac_res = ctx->stage[7].as<float>(); dv.res_code = ctx->stage[8].as<uint8_t>(); dv.atom_code = nullptr;
+    if ((rc = stage_atoms(ctx, R, M, false, &dv))) return rc;
     if ((rc = ctx->pdb_off.ensure(sizeof(uint64_t) * ((size_t)n + 1)))) return rc;
-    if (R) {
-        rc = fcz_decompress_batch_dev(ctx, ctx->stage[0].as<uint8_t>(), ctx->stage[1].as<uint64_t>(), n, ctx->stage[2].as<uint32_t>(),
-                                      ctx->stage[3].as<uint32_t>(), alt_order, &dv);
-        if (rc) return rc;
-    }
-    ctx->sizes_fresh = false;
-    rc = pdb_sizes_impl(ctx, ctx->stage[0].as<uint8_t>(), ctx->stage[1].as<uint64_t>(), n, ctx->stage[2].as<uint32_t>(),
-                        ctx->stage[3].as<uint32_t>(), &dv, pad, ctx->pdb_off.as<uint64_t>());
+    if (R && (rc = decode_records(ctx, n, alt_order, &dv))) return rc;
+    rc = pdb_sizes_impl(ctx, ctx->pool[REC_BLOB].as<uint8_t>(), ctx->pool[REC_OFF].as<uint64_t>(), n, ctx->pool[REC_RES_OFF].as<uint32_t>(),
+                        ctx->pool[REC_ATOM_OFF].as<uint32_t>(), &dv, pad, ctx->pdb_off.as<uint64_t>());
     if (rc) return rc;
     HIP_TRY(hipMemcpyAsync(text_off, ctx->pdb_off.p, sizeof(uint64_t) * ((size_t)n + 1), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
@@ -349,8 +458,8 @@ static int pdb_begin_impl(fcz_ctx* ctx, const uint8_t* blob, const uint64_t* off
     ctx->pdb_bytes = text_off[n];
     if ((rc = ctx->pdb_text.ensure(std::max<uint64_t>(ctx->pdb_bytes, 16)))) return rc;
     if (pad && ctx->pdb_bytes) HIP_TRY(hipMemsetAsync(ctx->pdb_text.p, 0, ctx->pdb_bytes, ctx->stream));   // the terminators: the format pass writes the text around them
-    return fcz_pdb_format_dev(ctx, ctx->stage[0].as<uint8_t>(), ctx->stage[1].as<uint64_t>(), n, ctx->stage[2].as<uint32_t>(),
-                              ctx->stage[3].as<uint32_t>(), &dv, alt_order, ctx->pdb_off.as<uint64_t>(), ctx->pdb_text.as<uint8_t>());
+    return fcz_pdb_format_dev(ctx, ctx->pool[REC_BLOB].as<uint8_t>(), ctx->pool[REC_OFF].as<uint64_t>(), n, ctx->pool[REC_RES_OFF].as<uint32_t>(),
+                              ctx->pool[REC_ATOM_OFF].as<uint32_t>(), &dv, alt_order, ctx->pdb_off.as<uint64_t>(), ctx->pdb_text.as<uint8_t>());
 }
 
 int fcz_decompress_pdb_begin(fcz_ctx* ctx, const uint8_t* blob, const uint64_t* off, uint32_t n, int alt_order, uint64_t* text_off,
@@ -415,17 +524,13 @@ int fcz_extract(fcz_ctx* ctx, const uint8_t* blob, const uint64_t* off, uint32_t
     HIP_TRY(hipSetDevice(ctx->device));
     if (n == 0 || data_off[n] == 0) return FCZ_OK;
     if (!data_out) return FCZ_E_INVALID_ARG;
-    ctx->sizes_fresh = false;   // staging buffers are rewritten
-    const uint64_t blob_bytes = off[n], data_bytes = data_off[n];
-    int rc;
-    if ((rc = ctx->stage[0].ensure(std::max<uint64_t>(blob_bytes, 16)))) return rc;
-    if ((rc = ctx->stage[1].ensure(sizeof(uint64_t) * ((size_t)n + 1)))) return rc;
-    if ((rc = ctx->pdb_off.ensure(sizeof(uint64_t) * ((size_t)n + 1)))) return rc;
+    claim_staging(ctx);
+    const uint64_t data_bytes = data_off[n];
+    int rc = ctx->pdb_off.ensure(sizeof(uint64_t) * ((size_t)n + 1)); if (rc) return rc;
     if ((rc = ctx->pdb_text.ensure(std::max<uint64_t>(data_bytes, 16)))) return rc;
-    HIP_TRY(hipMemcpyAsync(ctx->stage[0].p, blob, blob_bytes, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(ctx->stage[1].p, off, sizeof(uint64_t) * ((size_t)n + 1), hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = upload_records(ctx, blob, off, n))) return rc;
     HIP_TRY(hipMemcpyAsync(ctx->pdb_off.p, data_off, sizeof(uint64_t) * ((size_t)n + 1), hipMemcpyHostToDevice, ctx->stream));
-    rc = fcz_extract_dev(ctx, ctx->stage[0].as<uint8_t>(), ctx->stage[1].as<uint64_t>(), n, mode, digits, ctx->pdb_off.as<uint64_t>(),
+    rc = fcz_extract_dev(ctx, ctx->pool[REC_BLOB].as<uint8_t>(), ctx->pool[REC_OFF].as<uint64_t>(), n, mode, digits, ctx->pdb_off.as<uint64_t>(),
                          ctx->pdb_text.as<uint8_t>());
     if (rc) return rc;
     HIP_TRY(hipMemcpyAsync(data_out, ctx->pdb_text.p, data_bytes, hipMemcpyDeviceToHost, ctx->stream));
@@ -486,12 +591,12 @@ int fcz_compress_batch_dev(fcz_ctx* ctx, const fcz_chain_batch* in, const uint64
     rc = ctx->res_sc_addr.ensure(sizeof(uint64_t) * (size_t)std::max<uint32_t>(in->n_residues, 1));
     if (rc) return rc;
     const dim3 per_chain(grid_for(in->n_chains, WAVES_PER_BLOCK));
-    const size_t nf_words = ((size_t)in->n_chains + 31) / 32;
-    uint32_t* nonfinite = nullptr;
     {
         span_guard g(ctx, "compress_index");
         hipLaunchKernelGGL(k_compress_index, dim3(grid_for(in->n_chains, GROUPS_PER_BLOCK)), dim3(BLOCK), 0, ctx->stream, *in, out_off_dev, ctx->res_sc_addr.as<uint64_t>());
     }
+    const size_t nf_words = ((size_t)in->n_chains + 31) / 32;
+    uint32_t* nonfinite = nullptr;         // one bit per chain: a named atom with a NaN / infinite coordinate (set by the angle kernels)
     if (in->n_residues) {
         // wavefront-private tiles first; what does not fit them (atom-rich stretches, the tail of the arrays) is listed per
         // 256-residue tile and taken by the block-tile kernel, which handles every special case
@@ -500,7 +605,7 @@ int fcz_compress_batch_dev(fcz_ctx* ctx, const fcz_chain_batch* in, const uint64
         const uint32_t n_wtiles = grid_for(in->n_residues, CW_RES);
         rc = ctx->tile_work.ensure(sizeof(uint32_t) * (2 * (size_t)n_tiles + 4 + nf_words)); if (rc) return rc;
         uint32_t* flags = ctx->tile_work.as<uint32_t>(); uint32_t* list = flags + n_tiles; uint32_t* count = list + n_tiles;
-        nonfinite = count + 4;             // one bit per chain: a named atom with a NaN / infinite coordinate (set by the angle kernels)
+        nonfinite = count + 4;
         HIP_TRY(hipMemsetAsync(flags, 0, sizeof(uint32_t) * (2 * (size_t)n_tiles + 4 + nf_words), ctx->stream));
         const uint32_t blocks_w = std::min<uint32_t>(grid_for(n_wtiles, WAVES_PER_BLOCK), (uint32_t)ctx->n_cu * 3u * FCZ_CW_GRID_FACTOR);
         hipLaunchKernelGGL(k_compress_angles_w, dim3(blocks_w), dim3(BLOCK), 0, ctx->stream, *in, n_wtiles, ctx->res_sc_addr.as<uint64_t>(), out_dev,
@@ -515,27 +620,26 @@ int fcz_compress_batch_dev(fcz_ctx* ctx, const fcz_chain_batch* in, const uint64
     }
     {
         span_guard g(ctx, "compress_pack");
-        hipLaunchKernelGGL(k_compress_pack, per_chain, dim3(BLOCK), 0, ctx->stream, *in, out_off_dev, out_dev, status_dev,
-                           ctx->ang.as<float>(), ctx->keep_first_angle ? 1 : 0, (const uint32_t*)nonfinite);
+        auto pack = [&](auto kernel, dim3 grid) {
+            hipLaunchKernelGGL(kernel, grid, dim3(BLOCK), 0, ctx->stream, *in, out_off_dev, out_dev, status_dev, ctx->ang.as<float>(),
+                               ctx->keep_first_angle ? 1 : 0, (const uint32_t*)nonfinite);
+        };
+        pack(k_compress_pack, per_chain);
         // chains of 2 .. 128 residues (k_compress_pack leaves them): four to a wavefront, a persistent grid over chunks of 16 chains
         // (one launch per length class -- 2..16, 17..32, 33..64, 65..128 residues in 1, 2, 4, 8 rounds of 16 -- each a scan of the chunks' lengths)
-        const uint32_t rows_blocks = std::min<uint32_t>(grid_for(grid_for(in->n_chains, CP_CHUNK), WAVES_PER_BLOCK), (uint32_t)ctx->n_cu * 4u);
+        const dim3 rows_blocks(std::min<uint32_t>(grid_for(grid_for(in->n_chains, CP_CHUNK), WAVES_PER_BLOCK), (uint32_t)ctx->n_cu * 4u));
         // (every class launch is tied to the bound k_compress_pack skips by: a build with fewer rounds must not run a class twice)
         static_assert(FCZ_PACK_ROWS_MAX_ROUNDS == 1 || FCZ_PACK_ROWS_MAX_ROUNDS == 2 || FCZ_PACK_ROWS_MAX_ROUNDS == 4 || FCZ_PACK_ROWS_MAX_ROUNDS == 8,
                       "k_compress_pack_rows has the classes of 1, 2, 4 and 8 rounds");
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_compress_pack_rows<1>), dim3(rows_blocks), dim3(BLOCK), 0, ctx->stream, *in, out_off_dev, out_dev, status_dev,
-                           ctx->ang.as<float>(), ctx->keep_first_angle ? 1 : 0, (const uint32_t*)nonfinite);
+        pack(HIP_KERNEL_NAME(k_compress_pack_rows<1>), rows_blocks);
 #if FCZ_PACK_ROWS_MAX_ROUNDS >= 2
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_compress_pack_rows<2>), dim3(rows_blocks), dim3(BLOCK), 0, ctx->stream, *in, out_off_dev, out_dev, status_dev,
-                           ctx->ang.as<float>(), ctx->keep_first_angle ? 1 : 0, (const uint32_t*)nonfinite);
+        pack(HIP_KERNEL_NAME(k_compress_pack_rows<2>), rows_blocks);
 #endif
 #if FCZ_PACK_ROWS_MAX_ROUNDS >= 4
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_compress_pack_rows<4>), dim3(rows_blocks), dim3(BLOCK), 0, ctx->stream, *in, out_off_dev, out_dev, status_dev,
-                           ctx->ang.as<float>(), ctx->keep_first_angle ? 1 : 0, (const uint32_t*)nonfinite);
+        pack(HIP_KERNEL_NAME(k_compress_pack_rows<4>), rows_blocks);
 #endif
 #if FCZ_PACK_ROWS_MAX_ROUNDS >= 8
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_compress_pack_rows<8>), dim3(rows_blocks), dim3(BLOCK), 0, ctx->stream, *in, out_off_dev, out_dev, status_dev,
-                           ctx->ang.as<float>(), ctx->keep_first_angle ? 1 : 0, (const uint32_t*)nonfinite);
+        pack(HIP_KERNEL_NAME(k_compress_pack_rows<8>), rows_blocks);
 #endif
     }
     HIP_TRY(hipGetLastError());
@@ -546,44 +650,32 @@ int fcz_compress_batch(fcz_ctx* ctx, const fcz_chain_batch* in, const uint64_t* 
     if (!ctx || !in || !out_off || !out) return FCZ_E_INVALID_ARG;
     if (in->anchor_threshold <= 0) return FCZ_E_INVALID_ARG;
     HIP_TRY(hipSetDevice(ctx->device));
-    const uint32_t C = in->n_chains, R = in->n_residues, M = in->n_atoms;
+    const uint32_t C = in->n_chains;
     if (C == 0) return FCZ_OK;
-    const uint32_t TL = in->title_off[C];
+    claim_staging(ctx);
     const uint64_t out_bytes = out_off[C];
     // the side-chain byte addresses handed from k_compress_index to the angle kernels keep 39 bits (fcz_compress.h, sc_addr_put):
     // a blob of 512 GB or more is refused, not truncated (no device holds one: a device-resident out_dev cannot reach the limit)
     if (out_bytes >= (1ull << 39)) return FCZ_E_INVALID_ARG;
-    struct item { const void* src; size_t bytes; };
-    const item items[] = {
-        {in->res_off, sizeof(uint32_t) * (C + 1)}, {in->atom_off, sizeof(uint32_t) * (R + 1)},
-        {in->x, sizeof(float) * M}, {in->y, sizeof(float) * M}, {in->z, sizeof(float) * M},
-        {in->atom_code, (size_t)M}, {in->res_code, (size_t)R}, {in->bfac_ca, sizeof(float) * R},
-        {in->first_res_index, sizeof(int32_t) * C}, {in->first_atom_index, sizeof(int32_t) * C},
-        {in->chain_id, (size_t)C}, {in->titles, (size_t)TL}, {in->title_off, sizeof(uint32_t) * (C + 1)},
-        {out_off, sizeof(uint64_t) * (C + 1)},
-    };
-    void* d[14];
-    for (int i = 0; i < 14; i++) {
-        int rc = ctx->stage[i].ensure(std::max<size_t>(items[i].bytes, 16));
-        if (rc) return rc;
-        d[i] = ctx->stage[i].p;
-        if (items[i].bytes) HIP_TRY(hipMemcpyAsync(d[i], items[i].src, items[i].bytes, hipMemcpyHostToDevice, ctx->stream));
-    }
-    int rc = ctx->stage[14].ensure(std::max<uint64_t>(out_bytes, 16)); if (rc) return rc;
-    rc = ctx->stage[15].ensure(sizeof(int32_t) * C); if (rc) return rc;
-    fcz_chain_batch dv = *in;
-    dv.res_off = (const uint32_t*)d[0]; dv.atom_off = (const uint32_t*)d[1];
-    dv.x = (const float*)d[2]; dv.y = (const float*)d[3]; dv.z = (const float*)d[4];
-    dv.atom_code = (const uint8_t*)d[5]; dv.res_code = (const uint8_t*)d[6]; dv.bfac_ca = (const float*)d[7];
-    dv.first_res_index = (const int32_t*)d[8]; dv.first_atom_index = (const int32_t*)d[9];
-    dv.chain_id = (const char*)d[10]; dv.titles = (const char*)d[11]; dv.title_off = (const uint32_t*)d[12];
-    rc = fcz_compress_batch_dev(ctx, &dv, (const uint64_t*)d[13], ctx->stage[14].as<uint8_t>(), ctx->stage[15].as<int32_t>());
+    fcz_chain_batch dv = *in;               // the batch with its pointers on the device
+    int rc = each_batch_array(dv, *in, *in, in->title_off[C], [&](int i, auto& dst, auto* src, size_t bytes) -> int {
+        dev_buf& b = ctx->pool[BATCH_IN + i];
+        int e = b.ensure(std::max<size_t>(bytes, 16)); if (e) return e;
+        if (bytes) HIP_TRY(hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, ctx->stream));
+        dst = b.as<std::remove_pointer_t<std::decay_t<decltype(dst)>>>();
+        return FCZ_OK;
+    });
     if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(out, ctx->stage[14].p, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    if ((rc = ctx->pool[KEPT_OFF].ensure(sizeof(uint64_t) * ((size_t)C + 1)))) return rc;
+    HIP_TRY(hipMemcpyAsync(ctx->pool[KEPT_OFF].p, out_off, sizeof(uint64_t) * ((size_t)C + 1), hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = ctx->pool[KEPT_BYTES].ensure(std::max<uint64_t>(out_bytes, 16))) || (rc = ctx->pool[KEPT_STATUS].ensure(sizeof(int32_t) * C))) return rc;
+    rc = fcz_compress_batch_dev(ctx, &dv, ctx->pool[KEPT_OFF].as<uint64_t>(), ctx->pool[KEPT_BYTES].as<uint8_t>(), ctx->pool[KEPT_STATUS].as<int32_t>());
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(out, ctx->pool[KEPT_BYTES].p, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
     std::vector<int32_t> st_host;
     int32_t* st = status;
     if (!st) { st_host.resize(C); st = st_host.data(); }
-    HIP_TRY(hipMemcpyAsync(st, ctx->stage[15].p, sizeof(int32_t) * C, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(st, ctx->pool[KEPT_STATUS].p, sizeof(int32_t) * C, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     int worst = FCZ_OK;
     for (uint32_t c = 0; c < C; c++) if (st[c] != FCZ_OK) worst = st[c];
@@ -608,6 +700,24 @@ int fcz_compress_angles(fcz_ctx* ctx, const fcz_chain_batch* in, float* angles_o
     return FCZ_OK;
 }
 
+// the compress half of fcz_compress_pdb_begin / fcz_compress_gz_begin / fcz_compress_dense_begin: sizes, then the codec, on a batch
+// an earlier stage left in the ctx; the records stay in pool[KEPT_*] for the fetch, their size in *kept_bytes
+static int compress_resident_batch(fcz_ctx* ctx, const fcz_chain_batch& b, uint64_t* kept_bytes, uint64_t* fcz_bytes) {
+    int rc;
+    const uint32_t C = b.n_chains;
+    if (C == 0) return FCZ_OK;
+    dev_buf* k = ctx->pool;
+    if ((rc = k[KEPT_OFF].ensure(8 * ((size_t)C + 1))) || (rc = k[KEPT_STATUS].ensure(4 * (size_t)C))) return rc;
+    if ((rc = fcz_compress_sizes_dev(ctx, &b, k[KEPT_OFF].as<uint64_t>()))) return rc;
+    HIP_TRY(hipMemcpyAsync(&ctx->pinned->record_bytes, k[KEPT_OFF].as<uint64_t>() + C, 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    const uint64_t bytes = ctx->pinned->record_bytes;
+    if ((rc = k[KEPT_BYTES].ensure(std::max<uint64_t>(bytes, 16)))) return rc;
+    if ((rc = fcz_compress_batch_dev(ctx, &b, k[KEPT_OFF].as<uint64_t>(), k[KEPT_BYTES].as<uint8_t>(), k[KEPT_STATUS].as<int32_t>()))) return rc;
+    *kept_bytes = bytes; *fcz_bytes = bytes;
+    return FCZ_OK;
+}
+
 
 // ------------------------------------------------------------------------------------------------
 // structure ingest: PDB text -> fcz_chain_batch on the device (fcz_ingest.h)
@@ -628,9 +738,6 @@ int fcz_ingest_pdb_dev(fcz_ctx* ctx, const uint8_t* text_dev, const uint64_t* fi
     if (cap64 >> 32) return FCZ_E_INVALID_ARG;                 // atom offsets are 32-bit: split the batch
     const size_t cap = (size_t)cap64, F = n_files;
     int rc;
-    enum { B_CAP, B_ABASE, B_NAME, B_RESN, B_SERIAL, B_RESSEQ, B_X, B_Y, B_Z, B_B, B_CHAIN, B_ACODE, B_RCODE, B_RFIRST, B_RBFAC, B_RCODE2,
-           B_TITLES, B_TLEN, B_NKEPT, B_STATUS, B_FRAGS, B_NFRAGS, B_TOTC, B_TOTR, B_TOTA, B_TOTT, B_USESTEM, B_OFFC, B_OFFR, B_OFFA, B_OFFT,
-           B_REFUSED, B_NREF, B_OUT_A, B_OUT_R, B_OUT_C, B_OUT_T, B_CIFROWS };
     auto need = [&](int i, size_t bytes) { return ctx->ig[i].ensure(std::max<size_t>(bytes, 16)); };
     if ((rc = need(B_CAP, 8 * F)) || (rc = need(B_ABASE, 8 * (F + 1))) || (rc = need(B_NAME, 4 * cap)) || (rc = need(B_RESN, 4 * cap)) ||
         (rc = need(B_SERIAL, 4 * cap)) || (rc = need(B_RESSEQ, 4 * cap)) || (rc = need(B_X, 4 * cap)) || (rc = need(B_Y, 4 * cap)) ||
@@ -680,15 +787,15 @@ int fcz_ingest_pdb_dev(fcz_ctx* ctx, const uint8_t* text_dev, const uint64_t* fi
     if ((rc = device_scan<uint32_t>(ctx, tot.chains, (uint32_t*)P(B_OFFC), n_files, ovf)) || (rc = device_scan<uint32_t>(ctx, tot.residues, (uint32_t*)P(B_OFFR), n_files, ovf)) ||
         (rc = device_scan<uint32_t>(ctx, tot.atoms, (uint32_t*)P(B_OFFA), n_files, ovf)) || (rc = device_scan<uint32_t>(ctx, tot.title_bytes, (uint32_t*)P(B_OFFT), n_files, ovf)))
         return rc;
-    uint32_t* pin = ctx->pinned + 8;    // [8..11] totals, [12] overflow
-    HIP_TRY(hipMemcpyAsync(&pin[0], (uint32_t*)P(B_OFFC) + n_files, 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(&pin[1], (uint32_t*)P(B_OFFR) + n_files, 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(&pin[2], (uint32_t*)P(B_OFFA) + n_files, 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(&pin[3], (uint32_t*)P(B_OFFT) + n_files, 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(&pin[4], ovf, 4, hipMemcpyDeviceToHost, ctx->stream));
+    auto& pin = ctx->pinned->ingest;
+    HIP_TRY(hipMemcpyAsync(&pin.chains, (uint32_t*)P(B_OFFC) + n_files, 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(&pin.residues, (uint32_t*)P(B_OFFR) + n_files, 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(&pin.atoms, (uint32_t*)P(B_OFFA) + n_files, 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(&pin.title_bytes, (uint32_t*)P(B_OFFT) + n_files, 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(&pin.overflow, ovf, 4, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
-    if (pin[4]) return FCZ_E_INVALID_ARG;
-    const uint32_t C = pin[0], R = pin[1], M = pin[2], TB = pin[3];
+    if (pin.overflow) return FCZ_E_INVALID_ARG;
+    const uint32_t C = pin.chains, R = pin.residues, M = pin.atoms, TB = pin.title_bytes;
     // the batch arrays: [atoms] x y z code | [residues + 1] atom_off, [residues] code bfac | [chains (+1)] ... | titles
     const size_t oa_x = 0, oa_y = 4 * (size_t)M, oa_z = 8 * (size_t)M, oa_c = 12 * (size_t)M;
     const size_t or_off = 0, or_bf = 4 * ((size_t)R + 1), or_rc = or_bf + 4 * (size_t)R;
@@ -710,7 +817,7 @@ int fcz_ingest_pdb_dev(fcz_ctx* ctx, const uint8_t* text_dev, const uint64_t* fi
                            (uint32_t*)P(B_REFUSED), (uint32_t*)P(B_NREF));
     }
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(&pin[5], P(B_NREF), 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(&pin.refused, P(B_NREF), 4, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     fcz_ingest_result& r = ctx->ig_res;
     r.batch.n_chains = C; r.batch.n_residues = R; r.batch.n_atoms = M; r.batch.anchor_threshold = anchor_threshold;
@@ -719,36 +826,9 @@ int fcz_ingest_pdb_dev(fcz_ctx* ctx, const uint8_t* text_dev, const uint64_t* fi
     r.batch.first_res_index = O.first_res; r.batch.first_atom_index = O.first_atom; r.batch.chain_id = O.chain_id;
     r.batch.titles = O.titles; r.batch.title_off = O.title_off;
     r.chain_file = O.chain_file; r.chain_meta = O.chain_meta; r.chain_name4 = O.chain_name4; r.file_status = (const int32_t*)P(B_STATUS); r.refused = (const uint32_t*)P(B_REFUSED);
-    r.n_files = n_files; r.n_refused = pin[5];
-    ctx->ig_counts[0] = C; ctx->ig_counts[1] = R; ctx->ig_counts[2] = M; ctx->ig_counts[3] = TB; ctx->ig_counts[4] = pin[5];
+    r.n_files = n_files; r.n_refused = pin.refused;
+    ctx->ig_counts[0] = C; ctx->ig_counts[1] = R; ctx->ig_counts[2] = M; ctx->ig_counts[3] = TB; ctx->ig_counts[4] = pin.refused;
     *out = r;
-    return FCZ_OK;
-}
-
-int fcz_ingest_pdb_begin(fcz_ctx* ctx, const uint8_t* text, const uint64_t* file_off, uint32_t n_files, const char* names, const uint32_t* name_off,
-                         const uint32_t* stem_len, int anchor_threshold, int flags, uint32_t counts[5]) {
-    if (!ctx || !counts || anchor_threshold <= 0) return FCZ_E_INVALID_ARG;
-    if (n_files && (!text || !file_off || !names || !name_off || !stem_len)) return FCZ_E_INVALID_ARG;
-    HIP_TRY(hipSetDevice(ctx->device));
-    ctx->sizes_fresh = false;   // staging buffers are rewritten
-    memset(counts, 0, 5 * sizeof(uint32_t));
-    if (n_files == 0) { memset(&ctx->ig_res, 0, sizeof ctx->ig_res); memset(ctx->ig_counts, 0, sizeof ctx->ig_counts); return FCZ_OK; }
-    const uint64_t text_bytes = file_off[n_files];
-    const uint32_t name_bytes = name_off[n_files];
-    int rc;
-    if ((rc = ctx->stage[0].ensure(std::max<uint64_t>(text_bytes, 16))) || (rc = ctx->stage[1].ensure(8 * ((size_t)n_files + 1))) ||
-        (rc = ctx->stage[2].ensure(std::max<size_t>(name_bytes, 16))) || (rc = ctx->stage[3].ensure(4 * ((size_t)n_files + 1))) || (rc = ctx->stage[4].ensure(4 * (size_t)n_files)))
-        return rc;
-    HIP_TRY(hipMemcpyAsync(ctx->stage[0].p, text, text_bytes, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(ctx->stage[1].p, file_off, 8 * ((size_t)n_files + 1), hipMemcpyHostToDevice, ctx->stream));
-    if (name_bytes) HIP_TRY(hipMemcpyAsync(ctx->stage[2].p, names, name_bytes, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(ctx->stage[3].p, name_off, 4 * ((size_t)n_files + 1), hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(ctx->stage[4].p, stem_len, 4 * (size_t)n_files, hipMemcpyHostToDevice, ctx->stream));
-    fcz_ingest_result res;
-    rc = fcz_ingest_pdb_dev(ctx, ctx->stage[0].as<uint8_t>(), ctx->stage[1].as<uint64_t>(), n_files, text_bytes, ctx->stage[2].as<char>(),
-                            ctx->stage[3].as<uint32_t>(), ctx->stage[4].as<uint32_t>(), anchor_threshold, flags, &res);
-    if (rc) return rc;
-    memcpy(counts, ctx->ig_counts, sizeof ctx->ig_counts);
     return FCZ_OK;
 }
 
@@ -777,41 +857,10 @@ int fcz_ingest_chain_names_fetch(fcz_ctx* ctx, uint32_t* chain_name4) {
 int fcz_ingest_pdb_fetch(fcz_ctx* ctx, const fcz_chain_batch* hb, uint32_t* chain_file, uint32_t* chain_meta, int32_t* file_status, uint32_t* refused) {
     if (!ctx) return FCZ_E_INVALID_ARG;
     HIP_TRY(hipSetDevice(ctx->device));
-    const fcz_ingest_result& r = ctx->ig_res;
-    const fcz_chain_batch& d = r.batch;
-    const size_t C = d.n_chains, R = d.n_residues, M = d.n_atoms, TB = ctx->ig_counts[3];
-    if (hb && r.n_files) {
-        auto cp = [&](const void* dst, const void* src, size_t bytes) -> int {
-            if (!bytes) return FCZ_OK;
-            if (!dst) return FCZ_E_INVALID_ARG;
-            HIP_TRY(hipMemcpyAsync(const_cast<void*>(dst), src, bytes, hipMemcpyDeviceToHost, ctx->stream));
-            return FCZ_OK;
-        };
-        int rc;
-        if ((rc = cp(hb->res_off, d.res_off, 4 * (C + 1))) || (rc = cp(hb->atom_off, d.atom_off, 4 * (R + 1))) || (rc = cp(hb->x, d.x, 4 * M)) ||
-            (rc = cp(hb->y, d.y, 4 * M)) || (rc = cp(hb->z, d.z, 4 * M)) || (rc = cp(hb->atom_code, d.atom_code, M)) || (rc = cp(hb->res_code, d.res_code, R)) ||
-            (rc = cp(hb->bfac_ca, d.bfac_ca, 4 * R)) || (rc = cp(hb->first_res_index, d.first_res_index, 4 * C)) ||
-            (rc = cp(hb->first_atom_index, d.first_atom_index, 4 * C)) || (rc = cp(hb->chain_id, d.chain_id, C)) || (rc = cp(hb->titles, d.titles, TB)) ||
-            (rc = cp(hb->title_off, d.title_off, 4 * (C + 1))))
-            return rc;
-    }
-    int rc = ingest_fetch_meta(ctx, chain_file, chain_meta, file_status, refused);
-    if (rc) return rc;
+    int rc = (hb && ctx->ig_res.n_files) ? fetch_batch(ctx, *hb, ctx->ig_res.batch, ctx->ig_counts[3]) : FCZ_OK; if (rc) return rc;
+    if ((rc = ingest_fetch_meta(ctx, chain_file, chain_meta, file_status, refused))) return rc;
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return FCZ_OK;
-}
-
-// the compress half of fcz_compress_pdb_begin / fcz_compress_gz_begin / fcz_compress_dense_begin: sizes, then the codec, on a batch
-// an earlier stage left in the ctx; the records stay in stage[13] (offsets), [14] (bytes), [15] (status)
-static int compress_resident_batch(fcz_ctx* ctx, const fcz_chain_batch& b, uint64_t* kept_bytes, uint64_t* fcz_bytes);
-
-int fcz_compress_pdb_begin(fcz_ctx* ctx, const uint8_t* text, const uint64_t* file_off, uint32_t n_files, const char* names, const uint32_t* name_off,
-                           const uint32_t* stem_len, int anchor_threshold, int flags, uint32_t counts[5], uint64_t* fcz_bytes) {
-    if (!fcz_bytes) return FCZ_E_INVALID_ARG;
-    *fcz_bytes = 0; if (ctx) ctx->ig_fcz_bytes = 0;
-    int rc = fcz_ingest_pdb_begin(ctx, text, file_off, n_files, names, name_off, stem_len, anchor_threshold, flags, counts);
-    if (rc) return rc;
-    return compress_resident_batch(ctx, ctx->ig_res.batch, &ctx->ig_fcz_bytes, fcz_bytes);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -851,19 +900,19 @@ int fcz_inflate_dev(fcz_ctx* ctx, const uint8_t* gz_dev, const uint64_t* gz_off_
     return FCZ_OK;
 }
 
-// the files' bytes -> ctx->gz_raw, their text -> ctx->stage[0] (text offsets in ctx->gz_toff, statuses in ctx->gz_status)
-static int inflate_into_stage(fcz_ctx* ctx, const uint8_t* data, const uint64_t* file_off, uint32_t n, const uint8_t* kind, const uint64_t* text_off) {
+// the files' bytes -> ctx->gz_raw, their text -> ctx->pool[FILES_TEXT] (text offsets in ctx->gz_toff, statuses in ctx->gz_status)
+static int inflate_into_text(fcz_ctx* ctx, const uint8_t* data, const uint64_t* file_off, uint32_t n, const uint8_t* kind, const uint64_t* text_off) {
     const uint64_t raw_bytes = file_off[n], text_bytes = text_off[n];
     int rc;
     if ((rc = ctx->gz_raw.ensure(std::max<uint64_t>(raw_bytes, 16))) || (rc = ctx->gz_off.ensure(8 * ((size_t)n + 1))) || (rc = ctx->gz_kind.ensure(std::max<size_t>(n, 16))) ||
-        (rc = ctx->gz_toff.ensure(8 * ((size_t)n + 1))) || (rc = ctx->gz_status.ensure(4 * (size_t)n + 16)) || (rc = ctx->stage[0].ensure(std::max<uint64_t>(text_bytes, 16))))
+        (rc = ctx->gz_toff.ensure(8 * ((size_t)n + 1))) || (rc = ctx->gz_status.ensure(4 * (size_t)n + 16)) || (rc = ctx->pool[FILES_TEXT].ensure(std::max<uint64_t>(text_bytes, 16))))
         return rc;
     if (raw_bytes) HIP_TRY(hipMemcpyAsync(ctx->gz_raw.p, data, raw_bytes, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(hipMemcpyAsync(ctx->gz_off.p, file_off, 8 * ((size_t)n + 1), hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(hipMemcpyAsync(ctx->gz_toff.p, text_off, 8 * ((size_t)n + 1), hipMemcpyHostToDevice, ctx->stream));
     if (kind) HIP_TRY(hipMemcpyAsync(ctx->gz_kind.p, kind, n, hipMemcpyHostToDevice, ctx->stream));
     return fcz_inflate_dev(ctx, ctx->gz_raw.as<uint8_t>(), ctx->gz_off.as<uint64_t>(), n, kind ? ctx->gz_kind.as<uint8_t>() : nullptr,
-                           ctx->gz_toff.as<uint64_t>(), ctx->stage[0].as<uint8_t>(), ctx->gz_status.as<int32_t>());
+                           ctx->gz_toff.as<uint64_t>(), ctx->pool[FILES_TEXT].as<uint8_t>(), ctx->gz_status.as<int32_t>());
 }
 
 int fcz_inflate(fcz_ctx* ctx, const uint8_t* gz, const uint64_t* gz_off, uint32_t n, const uint8_t* kind, const uint64_t* text_off,
@@ -872,85 +921,85 @@ int fcz_inflate(fcz_ctx* ctx, const uint8_t* gz, const uint64_t* gz_off, uint32_
     if (n == 0) return FCZ_OK;
     if (!gz || !gz_off || !text_off || !status || (text_off[n] && !text)) return FCZ_E_INVALID_ARG;
     HIP_TRY(hipSetDevice(ctx->device));
-    ctx->sizes_fresh = false;   // staging buffers are rewritten
-    int rc = inflate_into_stage(ctx, gz, gz_off, n, kind, text_off);
-    if (rc) return rc;
-    if (text_off[n]) HIP_TRY(hipMemcpyAsync(text, ctx->stage[0].p, text_off[n], hipMemcpyDeviceToHost, ctx->stream));
+    claim_staging(ctx);
+    int rc = inflate_into_text(ctx, gz, gz_off, n, kind, text_off); if (rc) return rc;
+    if (text_off[n]) HIP_TRY(hipMemcpyAsync(text, ctx->pool[FILES_TEXT].p, text_off[n], hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipMemcpyAsync(status, ctx->gz_status.p, 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return FCZ_OK;
 }
 
-int fcz_ingest_gz_begin(fcz_ctx* ctx, const uint8_t* data, const uint64_t* file_off, uint32_t n_files, const uint8_t* is_gz, const char* names,
-                        const uint32_t* name_off, const uint32_t* stem_len, int anchor_threshold, int flags, uint32_t counts[5]) {
+// fcz_ingest_pdb_begin / fcz_compress_pdb_begin (gz false: data is text) and fcz_ingest_gz_begin / fcz_compress_gz_begin (gz true: the
+// files as they lie on disk, inflated on the device first); with fcz_bytes the resident batch is compressed too
+static int ingest_begin(fcz_ctx* ctx, const uint8_t* data, const uint64_t* file_off, uint32_t n_files, bool gz, const uint8_t* is_gz, const char* names,
+                        const uint32_t* name_off, const uint32_t* stem_len, int anchor_threshold, int flags, uint32_t counts[5], uint64_t* fcz_bytes) {
     if (!ctx || !counts || anchor_threshold <= 0) return FCZ_E_INVALID_ARG;
     if (n_files && (!data || !file_off || !names || !name_off || !stem_len)) return FCZ_E_INVALID_ARG;
     HIP_TRY(hipSetDevice(ctx->device));
-    ctx->sizes_fresh = false;   // staging buffers are rewritten
+    claim_staging(ctx);
     memset(counts, 0, 5 * sizeof(uint32_t));
     if (n_files == 0) { memset(&ctx->ig_res, 0, sizeof ctx->ig_res); memset(ctx->ig_counts, 0, sizeof ctx->ig_counts); return FCZ_OK; }
-    std::vector<uint64_t> text_off((size_t)n_files + 1);
-    int rc = fcz_inflate_sizes(data, file_off, n_files, is_gz, text_off.data());
-    if (rc) return rc;
-    if ((rc = inflate_into_stage(ctx, data, file_off, n_files, is_gz, text_off.data()))) return rc;
+    dev_buf* f = ctx->pool;
+    int rc;
+    uint64_t text_bytes = file_off[n_files];
+    if (gz) {
+        std::vector<uint64_t> text_off((size_t)n_files + 1);
+        if ((rc = fcz_inflate_sizes(data, file_off, n_files, is_gz, text_off.data()))) return rc;
+        if ((rc = inflate_into_text(ctx, data, file_off, n_files, is_gz, text_off.data()))) return rc;
+        text_bytes = text_off[n_files];
+    } else {
+        if ((rc = f[FILES_TEXT].ensure(std::max<uint64_t>(text_bytes, 16))) || (rc = f[FILES_OFF].ensure(8 * ((size_t)n_files + 1)))) return rc;
+        HIP_TRY(hipMemcpyAsync(f[FILES_TEXT].p, data, text_bytes, hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(hipMemcpyAsync(f[FILES_OFF].p, file_off, 8 * ((size_t)n_files + 1), hipMemcpyHostToDevice, ctx->stream));
+    }
     const uint32_t name_bytes = name_off[n_files];
-    if ((rc = ctx->stage[2].ensure(std::max<size_t>(name_bytes, 16))) || (rc = ctx->stage[3].ensure(4 * ((size_t)n_files + 1))) || (rc = ctx->stage[4].ensure(4 * (size_t)n_files)))
-        return rc;
-    if (name_bytes) HIP_TRY(hipMemcpyAsync(ctx->stage[2].p, names, name_bytes, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(ctx->stage[3].p, name_off, 4 * ((size_t)n_files + 1), hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(ctx->stage[4].p, stem_len, 4 * (size_t)n_files, hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = f[FILES_NAMES].ensure(std::max<size_t>(name_bytes, 16))) || (rc = f[FILES_NAME_OFF].ensure(4 * ((size_t)n_files + 1))) || (rc = f[FILES_STEM_LEN].ensure(4 * (size_t)n_files))) return rc;
+    if (name_bytes) HIP_TRY(hipMemcpyAsync(f[FILES_NAMES].p, names, name_bytes, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(f[FILES_NAME_OFF].p, name_off, 4 * ((size_t)n_files + 1), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(f[FILES_STEM_LEN].p, stem_len, 4 * (size_t)n_files, hipMemcpyHostToDevice, ctx->stream));
     fcz_ingest_result res;
-    rc = fcz_ingest_pdb_dev(ctx, ctx->stage[0].as<uint8_t>(), ctx->gz_toff.as<uint64_t>(), n_files, text_off[n_files], ctx->stage[2].as<char>(),
-                            ctx->stage[3].as<uint32_t>(), ctx->stage[4].as<uint32_t>(), anchor_threshold, flags, &res);
+    rc = fcz_ingest_pdb_dev(ctx, f[FILES_TEXT].as<uint8_t>(), gz ? ctx->gz_toff.as<uint64_t>() : f[FILES_OFF].as<uint64_t>(), n_files, text_bytes,
+                            f[FILES_NAMES].as<char>(), f[FILES_NAME_OFF].as<uint32_t>(), f[FILES_STEM_LEN].as<uint32_t>(), anchor_threshold, flags, &res);
     if (rc) return rc;
-    // a member the device did not inflate left blanks (no atoms): the FILE goes back to the caller's zlib and reader
-    hipLaunchKernelGGL(inflate::k_inflate_merge_status, dim3(grid_for(n_files, 256)), dim3(256), 0, ctx->stream, ctx->gz_status.as<int32_t>(), n_files,
-                       (int32_t)FCZ_INGEST_HOST_GZIP, const_cast<int32_t*>(ctx->ig_res.file_status));
-    HIP_TRY(hipGetLastError());
+    if (gz) {   // a member the device did not inflate left blanks (no atoms): the FILE goes back to the caller's zlib and reader
+        hipLaunchKernelGGL(inflate::k_inflate_merge_status, dim3(grid_for(n_files, 256)), dim3(256), 0, ctx->stream, ctx->gz_status.as<int32_t>(), n_files,
+                           (int32_t)FCZ_INGEST_HOST_GZIP, ctx->ig[B_STATUS].as<int32_t>());
+        HIP_TRY(hipGetLastError());
+    }
     memcpy(counts, ctx->ig_counts, sizeof ctx->ig_counts);
-    return FCZ_OK;
+    return fcz_bytes ? compress_resident_batch(ctx, ctx->ig_res.batch, &ctx->ig_fcz_bytes, fcz_bytes) : FCZ_OK;
+}
+
+int fcz_ingest_pdb_begin(fcz_ctx* ctx, const uint8_t* text, const uint64_t* file_off, uint32_t n_files, const char* names, const uint32_t* name_off,
+                         const uint32_t* stem_len, int anchor_threshold, int flags, uint32_t counts[5]) {
+    return ingest_begin(ctx, text, file_off, n_files, false, nullptr, names, name_off, stem_len, anchor_threshold, flags, counts, nullptr);
+}
+
+int fcz_ingest_gz_begin(fcz_ctx* ctx, const uint8_t* data, const uint64_t* file_off, uint32_t n_files, const uint8_t* is_gz, const char* names,
+                        const uint32_t* name_off, const uint32_t* stem_len, int anchor_threshold, int flags, uint32_t counts[5]) {
+    return ingest_begin(ctx, data, file_off, n_files, true, is_gz, names, name_off, stem_len, anchor_threshold, flags, counts, nullptr);
+}
+
+int fcz_compress_pdb_begin(fcz_ctx* ctx, const uint8_t* text, const uint64_t* file_off, uint32_t n_files, const char* names, const uint32_t* name_off,
+                           const uint32_t* stem_len, int anchor_threshold, int flags, uint32_t counts[5], uint64_t* fcz_bytes) {
+    if (!fcz_bytes) return FCZ_E_INVALID_ARG;
+    *fcz_bytes = 0; if (ctx) ctx->ig_fcz_bytes = 0;
+    return ingest_begin(ctx, text, file_off, n_files, false, nullptr, names, name_off, stem_len, anchor_threshold, flags, counts, fcz_bytes);
 }
 
 int fcz_compress_gz_begin(fcz_ctx* ctx, const uint8_t* data, const uint64_t* file_off, uint32_t n_files, const uint8_t* is_gz, const char* names,
                           const uint32_t* name_off, const uint32_t* stem_len, int anchor_threshold, int flags, uint32_t counts[5], uint64_t* fcz_bytes) {
     if (!fcz_bytes) return FCZ_E_INVALID_ARG;
     *fcz_bytes = 0; if (ctx) ctx->ig_fcz_bytes = 0;
-    int rc = fcz_ingest_gz_begin(ctx, data, file_off, n_files, is_gz, names, name_off, stem_len, anchor_threshold, flags, counts);
-    if (rc) return rc;
-    return compress_resident_batch(ctx, ctx->ig_res.batch, &ctx->ig_fcz_bytes, fcz_bytes);
-}
-
-static int compress_resident_batch(fcz_ctx* ctx, const fcz_chain_batch& b, uint64_t* kept_bytes, uint64_t* fcz_bytes) {
-    int rc;
-    const uint32_t C = b.n_chains;
-    if (C == 0) return FCZ_OK;
-    if ((rc = ctx->stage[13].ensure(8 * ((size_t)C + 1))) || (rc = ctx->stage[15].ensure(4 * (size_t)C))) return rc;
-    if ((rc = fcz_compress_sizes_dev(ctx, &b, ctx->stage[13].as<uint64_t>()))) return rc;
-    uint64_t* tot = reinterpret_cast<uint64_t*>(ctx->pinned + 14);
-    HIP_TRY(hipMemcpyAsync(tot, ctx->stage[13].as<uint64_t>() + C, 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    const uint64_t bytes = *tot;
-    if ((rc = ctx->stage[14].ensure(std::max<uint64_t>(bytes, 16)))) return rc;
-    if ((rc = fcz_compress_batch_dev(ctx, &b, ctx->stage[13].as<uint64_t>(), ctx->stage[14].as<uint8_t>(), ctx->stage[15].as<int32_t>()))) return rc;
-    *kept_bytes = bytes; *fcz_bytes = bytes;
-    return FCZ_OK;
+    return ingest_begin(ctx, data, file_off, n_files, true, is_gz, names, name_off, stem_len, anchor_threshold, flags, counts, fcz_bytes);
 }
 
 int fcz_compress_pdb_fetch(fcz_ctx* ctx, uint64_t* out_off, int32_t* status, uint32_t* chain_file, uint32_t* chain_meta, int32_t* file_status,
                            uint32_t* refused, uint8_t* blob) {
     if (!ctx) return FCZ_E_INVALID_ARG;
     HIP_TRY(hipSetDevice(ctx->device));
-    const uint32_t C = ctx->ig_res.batch.n_chains;
-    if (C) {
-        if (out_off) HIP_TRY(hipMemcpyAsync(out_off, ctx->stage[13].p, 8 * ((size_t)C + 1), hipMemcpyDeviceToHost, ctx->stream));
-        if (status) HIP_TRY(hipMemcpyAsync(status, ctx->stage[15].p, 4 * (size_t)C, hipMemcpyDeviceToHost, ctx->stream));
-        if (ctx->ig_fcz_bytes) {
-            if (!blob) return FCZ_E_INVALID_ARG;
-            HIP_TRY(hipMemcpyAsync(blob, ctx->stage[14].p, ctx->ig_fcz_bytes, hipMemcpyDeviceToHost, ctx->stream));
-        }
-    } else if (out_off) out_off[0] = 0;
-    int rc = ingest_fetch_meta(ctx, chain_file, chain_meta, file_status, refused);
-    if (rc) return rc;
+    int rc = fetch_resident(ctx, ctx->ig_res.batch.n_chains, ctx->ig_fcz_bytes, out_off, status, blob, hipMemcpyDeviceToHost); if (rc) return rc;
+    if ((rc = ingest_fetch_meta(ctx, chain_file, chain_meta, file_status, refused))) return rc;
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return FCZ_OK;
 }
@@ -1039,10 +1088,11 @@ int fcz_check(const uint8_t* e, uint64_t len) {
 // The sizes pass of the decompress path: per-entry validation and counts (k_entry_sizes), then -- in three launches -- their
 // exclusive prefixes, the longest anchor segment of the batch (sizes the ring of k_backbone), the totals, and the entries ordered by
 // residue count for k_backbone (counting sort, longest first): k_sizes_reduce / _mid / _apply (fcz_kernels.h). The totals come
-// back as ONE 32-byte copy into pinned host words after one stream synchronisation. atom_off_dev may be null (prefix not needed).
+// back as ONE 32-byte copy into ctx->pinned->sizes after one stream synchronisation. atom_off_dev may be null (prefix not needed).
 static int run_entry_sizes(fcz_ctx* ctx, const uint8_t* blob_dev, const uint64_t* off_dev, uint32_t n, uint32_t* res_off_dev,
                            uint32_t* atom_off_dev) {
-    for (int k = 0; k < 8; k++) ctx->pinned[k] = 0;
+    sizes_totals& tot = ctx->pinned->sizes;
+    tot = sizes_totals{};
     if (n == 0) {
         HIP_TRY(hipMemsetAsync(res_off_dev, 0, 4, ctx->stream));
         if (atom_off_dev) HIP_TRY(hipMemsetAsync(atom_off_dev, 0, 4, ctx->stream));
@@ -1050,7 +1100,7 @@ static int run_entry_sizes(fcz_ctx* ctx, const uint8_t* blob_dev, const uint64_t
         return FCZ_OK;
     }
     int rc = ctx->cnt.ensure(sizeof(uint32_t) * 4 * (size_t)n); if (rc) return rc;
-    uint32_t* cr = ctx->cnt.as<uint32_t>(); uint32_t* ca = cr + n; int32_t* st = (int32_t*)(ca + n); uint32_t* seg = (uint32_t*)(st + n);
+    uint32_t* cr = ctx->cnt.as<uint32_t>(); uint32_t* ca = cr + n; int32_t* st = cnt_status(ctx, n); uint32_t* seg = (uint32_t*)(st + n);
     // len_perm: [perm n][hist LEN_BUCKETS][cursor LEN_BUCKETS + 1][pad][maxseg 2][pad 2][totals 8]
     if ((rc = ctx->len_perm.ensure(sizeof(uint32_t) * ((size_t)n + 2 * LEN_BUCKETS + 16)))) return rc;
     uint32_t* perm = ctx->len_perm.as<uint32_t>(); uint32_t* hist = perm + n; uint32_t* cursor = hist + LEN_BUCKETS;
@@ -1069,15 +1119,14 @@ static int run_entry_sizes(fcz_ctx* ctx, const uint8_t* blob_dev, const uint64_t
         hipLaunchKernelGGL(k_sizes_mid, dim3(1), dim3(1024), 0, ctx->stream, nb, part_r, part_a, hist, cursor, maxseg, totals, off_dev + n);
         hipLaunchKernelGGL(k_sizes_apply, dim3(nb), dim3(1024), 0, ctx->stream, cr, ca, n, part_r, part_a, res_off_dev, atom_off_dev, cursor, perm);
         HIP_TRY(hipGetLastError());
-        // pinned: [0] residues [1] atoms [3] longest segment [4] most segments [5] long chains [6] offset overflow; [2], [7] code slots
-        HIP_TRY(hipMemcpyAsync(&ctx->pinned[0], totals, sizeof(sizes_totals), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(hipMemcpyAsync(&tot, totals, sizeof(sizes_totals), hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(hipStreamSynchronize(ctx->stream));
-        const uint64_t need = (uint64_t)ctx->pinned[2] | ((uint64_t)ctx->pinned[7] << 32);
+        const uint64_t need = (uint64_t)tot.codes_lo | ((uint64_t)tot.codes_hi << 32);
         if (need <= ctx->codes.cap) break;
         if (attempt == 1) return FCZ_E_HIP;
         if ((rc = ctx->codes.ensure((size_t)(need + need / 8)))) return rc;
     }
-    if (ctx->pinned[6]) return FCZ_E_INVALID_ARG;   // 2^32 residues or atoms in one batch: split it
+    if (tot.overflow) return FCZ_E_INVALID_ARG;   // 2^32 residues or atoms in one batch: split it
     return FCZ_OK;
 }
 
@@ -1091,11 +1140,12 @@ int fcz_decompress_sizes_dev(fcz_ctx* ctx, const uint8_t* blob_dev, const uint64
         int rc = run_entry_sizes(ctx, blob_dev, off_dev, n, res_off_dev, atom_off_dev);
         if (rc) return rc;
     }
-    if (total_res) *total_res = ctx->pinned[0];
-    if (total_atoms) *total_atoms = ctx->pinned[1];
+    const sizes_totals& tot = ctx->pinned->sizes;
+    if (total_res) *total_res = tot.residues;
+    if (total_atoms) *total_atoms = tot.atoms;
     // the fcz_decompress_batch_dev call that follows on the same entries reuses the totals and the length order
     ctx->sized_blob = blob_dev; ctx->sized_off = off_dev; ctx->sized_n = n;
-    ctx->sized_R = ctx->pinned[0]; ctx->sized_maxseg = ctx->pinned[3]; ctx->sized_maxnseg = ctx->pinned[4]; ctx->sized_nlong = ctx->pinned[5];
+    ctx->sized_R = tot.residues; ctx->sized_maxseg = tot.max_seg; ctx->sized_maxnseg = tot.max_nseg; ctx->sized_nlong = tot.n_long;
     ctx->sizes_fresh = true;
     return FCZ_OK;
 }
@@ -1109,17 +1159,17 @@ static int ensure_sizes(fcz_ctx* ctx, const uint8_t* blob_dev, const uint64_t* o
         return FCZ_OK;
     }
     ctx->sizes_fresh = false;   // the pass below overwrites what a remembered sizes call left (length order, residue codes)
-    int rc = ctx->stage[16].ensure(sizeof(uint32_t) * ((size_t)n + 1)); if (rc) return rc;
-    if ((rc = run_entry_sizes(ctx, blob_dev, off_dev, n, ctx->stage[16].as<uint32_t>(), nullptr))) return rc;
-    *total_res = ctx->pinned[0]; *max_seg_len = ctx->pinned[3]; *max_nseg = ctx->pinned[4]; *n_long = ctx->pinned[5];
+    int rc = ctx->sizes_res_off.ensure(sizeof(uint32_t) * ((size_t)n + 1)); if (rc) return rc;
+    if ((rc = run_entry_sizes(ctx, blob_dev, off_dev, n, ctx->sizes_res_off.as<uint32_t>(), nullptr))) return rc;
+    const sizes_totals& tot = ctx->pinned->sizes;
+    *total_res = tot.residues; *max_seg_len = tot.max_seg; *max_nseg = tot.max_nseg; *n_long = tot.n_long;
     return FCZ_OK;
 }
 
 int fcz_decompress_batch_dev(fcz_ctx* ctx, const uint8_t* blob_dev, const uint64_t* off_dev, uint32_t n,
                              const uint32_t* res_off_dev, const uint32_t* atom_off_dev, int alt_order,
                              const fcz_atoms_out* out_dev) {
-    if (!ctx || !blob_dev || !off_dev || !res_off_dev || !atom_off_dev || !out_dev) return FCZ_E_INVALID_ARG;
-    if (!out_dev->x || !out_dev->y || !out_dev->z || !out_dev->bfac_res) return FCZ_E_INVALID_ARG;
+    if (!ctx || !blob_dev || !off_dev || !res_off_dev || !atom_off_dev || !atoms_out_ok(out_dev, false)) return FCZ_E_INVALID_ARG;
     HIP_TRY(hipSetDevice(ctx->device));
     if (n == 0) return FCZ_OK;
     uint32_t R = 0, max_seg = 0, max_nseg = 0, n_long = 0;
@@ -1242,31 +1292,19 @@ int fcz_decompress_batch(fcz_ctx* ctx, const uint8_t* blob, const uint64_t* off,
                          const uint32_t* atom_off, int alt_order, const fcz_atoms_out* out) {
     if (!ctx || !blob || !off || !res_off || !atom_off || !out) return FCZ_E_INVALID_ARG;
     HIP_TRY(hipSetDevice(ctx->device));
-    ctx->sizes_fresh = false;   // the staging buffers the cache is keyed on are about to be rewritten
+    claim_staging(ctx);
     if (n == 0) return FCZ_OK;
-    const uint64_t blob_bytes = off[n];
-    const uint32_t R = res_off[n], M = atom_off[n];
     int rc;
-    if ((rc = ctx->stage[0].ensure(std::max<uint64_t>(blob_bytes, 16)))) return rc;
-    if ((rc = ctx->stage[1].ensure(sizeof(uint64_t) * ((size_t)n + 1)))) return rc;
-    if ((rc = ctx->stage[2].ensure(sizeof(uint32_t) * ((size_t)n + 1)))) return rc;
-    if ((rc = ctx->stage[3].ensure(sizeof(uint32_t) * ((size_t)n + 1)))) return rc;
-    for (int i = 4; i < 7; i++) if ((rc = ctx->stage[i].ensure(std::max<size_t>(sizeof(float) * (size_t)M, 16)))) return rc;
-    if ((rc = ctx->stage[7].ensure(std::max<size_t>(sizeof(float) * (size_t)R, 16)))) return rc;
-    if ((rc = ctx->stage[8].ensure(std::max<size_t>((size_t)R, 16)))) return rc;
-    if ((rc = ctx->stage[9].ensure(std::max<size_t>((size_t)M, 16)))) return rc;
-    HIP_TRY(hipMemcpyAsync(ctx->stage[0].p, blob, blob_bytes, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(ctx->stage[1].p, off, sizeof(uint64_t) * ((size_t)n + 1), hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(ctx->stage[2].p, res_off, sizeof(uint32_t) * ((size_t)n + 1), hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(ctx->stage[3].p, atom_off, sizeof(uint32_t) * ((size_t)n + 1), hipMemcpyHostToDevice, ctx->stream));
+    const uint32_t R = res_off[n], M = atom_off[n];
     fcz_atoms_out dv;
-    dv.x = ctx->stage[4].as<float>(); dv.y = ctx->stage[5].as<float>(); dv.z = ctx->stage[6].as<float>();
-    dv.bfac_res = ctx->stage[7].as<float>();
-    dv.res_code = out->res_code ? ctx->stage[8].as<uint8_t>() : nullptr;
-    dv.atom_code = out->atom_code ? ctx->stage[9].as<uint8_t>() : nullptr;
-    rc = fcz_decompress_batch_dev(ctx, ctx->stage[0].as<uint8_t>(), ctx->stage[1].as<uint64_t>(), n, ctx->stage[2].as<uint32_t>(),
-                                  ctx->stage[3].as<uint32_t>(), alt_order, &dv);
-    if (rc) return rc;
+    if ((rc = ctx->pool[REC_RES_OFF].ensure(sizeof(uint32_t) * ((size_t)n + 1))) || (rc = ctx->pool[REC_ATOM_OFF].ensure(sizeof(uint32_t) * ((size_t)n + 1))) ||
+        (rc = stage_atoms(ctx, R, M, true, &dv)) || (rc = upload_records(ctx, blob, off, n)))
+        return rc;
+    HIP_TRY(hipMemcpyAsync(ctx->pool[REC_RES_OFF].p, res_off, sizeof(uint32_t) * ((size_t)n + 1), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(ctx->pool[REC_ATOM_OFF].p, atom_off, sizeof(uint32_t) * ((size_t)n + 1), hipMemcpyHostToDevice, ctx->stream));
+    if (!out->res_code) dv.res_code = nullptr;
+    if (!out->atom_code) dv.atom_code = nullptr;
+    if ((rc = decode_records(ctx, n, alt_order, &dv))) return rc;
     if (M) {
         HIP_TRY(hipMemcpyAsync(out->x, dv.x, sizeof(float) * (size_t)M, hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(hipMemcpyAsync(out->y, dv.y, sizeof(float) * (size_t)M, hipMemcpyDeviceToHost, ctx->stream));
@@ -1321,8 +1359,7 @@ static dense_table dense_make_table(int layout, int alt_order) {
 int fcz_dense_dev(fcz_ctx* ctx, const uint8_t* blob_dev, const uint64_t* off_dev, uint32_t n, const uint32_t* res_off_dev,
                   const uint32_t* atom_off_dev, const fcz_atoms_out* atoms_dev, int alt_order, int layout, uint32_t L,
                   const fcz_dense_out* out_dev) {
-    if (!ctx || !blob_dev || !off_dev || !res_off_dev || !atom_off_dev || !atoms_dev || !out_dev) return FCZ_E_INVALID_ARG;
-    if (!atoms_dev->x || !atoms_dev->y || !atoms_dev->z || !atoms_dev->bfac_res || !atoms_dev->res_code) return FCZ_E_INVALID_ARG;
+    if (!ctx || !blob_dev || !off_dev || !res_off_dev || !atom_off_dev || !atoms_out_ok(atoms_dev) || !out_dev) return FCZ_E_INVALID_ARG;
     if (fcz_dense_width(layout) < 0 || L == 0 || !out_dev->pos || !out_dev->mask) return FCZ_E_INVALID_ARG;
     HIP_TRY(hipSetDevice(ctx->device));
     if (n == 0) return FCZ_OK;
@@ -1333,9 +1370,9 @@ int fcz_dense_dev(fcz_ctx* ctx, const uint8_t* blob_dev, const uint64_t* off_dev
     const uint64_t n_tiles = (uint64_t)n * tiles_per_entry;                  // every index behind it is 64-bit: n * L * A may pass 2^32
     const uint32_t blocks = (uint32_t)std::min<uint64_t>(n_tiles, (uint64_t)ctx->n_cu * 32u);
     span_guard sg(ctx, "dense");
-    if (layout == FCZ_DENSE_ATOM37) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_dense<37>), dim3(blocks), dim3(BLOCK), 0, ctx->stream, blob_dev, g, n, L, tiles_per_entry, n_tiles, tab);
-    else if (layout == FCZ_DENSE_ATOM14) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_dense<14>), dim3(blocks), dim3(BLOCK), 0, ctx->stream, blob_dev, g, n, L, tiles_per_entry, n_tiles, tab);
-    else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_dense<4>), dim3(blocks), dim3(BLOCK), 0, ctx->stream, blob_dev, g, n, L, tiles_per_entry, n_tiles, tab);
+    dispatch_layout(layout, [&](auto A) {
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_dense<decltype(A)::value>), dim3(blocks), dim3(BLOCK), 0, ctx->stream, blob_dev, g, n, L, tiles_per_entry, n_tiles, tab);
+    });
     HIP_TRY(hipGetLastError());
     return FCZ_OK;
 }
@@ -1345,47 +1382,26 @@ int fcz_decompress_dense(fcz_ctx* ctx, const uint8_t* blob, const uint64_t* off,
     const int A = fcz_dense_width(layout);
     if (!ctx || !blob || !off || A < 0 || (!out && !L_out) || (out && (!out->pos || !out->mask))) return FCZ_E_INVALID_ARG;
     HIP_TRY(hipSetDevice(ctx->device));
-    ctx->sizes_fresh = false;   // the staging buffers the cache is keyed on are about to be rewritten
+    claim_staging(ctx);
     if (n == 0) { if (L_out) *L_out = L; return FCZ_OK; }
-    const uint64_t blob_bytes = off[n];
-    int rc;
-    if ((rc = ctx->stage[0].ensure(std::max<uint64_t>(blob_bytes, 16)))) return rc;
-    if ((rc = ctx->stage[1].ensure(sizeof(uint64_t) * ((size_t)n + 1)))) return rc;
-    if ((rc = ctx->stage[2].ensure(sizeof(uint32_t) * ((size_t)n + 1)))) return rc;
-    if ((rc = ctx->stage[3].ensure(sizeof(uint32_t) * ((size_t)n + 1)))) return rc;
-    HIP_TRY(hipMemcpyAsync(ctx->stage[0].p, blob, blob_bytes, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(ctx->stage[1].p, off, sizeof(uint64_t) * ((size_t)n + 1), hipMemcpyHostToDevice, ctx->stream));
     uint32_t R = 0, M = 0;
-    rc = fcz_decompress_sizes_dev(ctx, ctx->stage[0].as<uint8_t>(), ctx->stage[1].as<uint64_t>(), n, ctx->stage[2].as<uint32_t>(),
-                                  ctx->stage[3].as<uint32_t>(), &R, &M);
-    if (rc) return rc;
+    int rc = upload_records(ctx, blob, off, n, &R, &M); if (rc) return rc;
     std::vector<uint32_t> res_off((size_t)n + 1);
-    HIP_TRY(hipMemcpyAsync(res_off.data(), ctx->stage[2].p, sizeof(uint32_t) * ((size_t)n + 1), hipMemcpyDeviceToHost, ctx->stream));
-    if (status)   // per-entry status of the sizes pass (cnt layout: 2 x n counts, then n status words)
-        HIP_TRY(hipMemcpyAsync(status, ctx->cnt.as<uint32_t>() + 2 * (size_t)n, sizeof(int32_t) * n, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(res_off.data(), ctx->pool[REC_RES_OFF].p, sizeof(uint32_t) * ((size_t)n + 1), hipMemcpyDeviceToHost, ctx->stream));
+    if (status) HIP_TRY(hipMemcpyAsync(status, cnt_status(ctx, n), sizeof(int32_t) * n, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     uint32_t longest = 0;
     for (uint32_t i = 0; i < n; i++) longest = std::max(longest, res_off[i + 1] - res_off[i]);
     if (L == 0) L = longest;
     if (L_out) *L_out = L;
-    if (!out) { ctx->sizes_fresh = false; return FCZ_OK; }
+    if (!out) return FCZ_OK;
     if (L == 0) {               // no entry decodes and no width was asked for: the padded arrays are empty
-        ctx->sizes_fresh = false;
         if (out->length) memset(out->length, 0, sizeof(uint32_t) * n);
         return FCZ_OK;
     }
-    for (int i = 4; i < 7; i++) if ((rc = ctx->stage[i].ensure(std::max<size_t>(sizeof(float) * (size_t)M, 16)))) return rc;
-    if ((rc = ctx->stage[7].ensure(std::max<size_t>(sizeof(float) * (size_t)R, 16)))) return rc;
-    if ((rc = ctx->stage[8].ensure(std::max<size_t>((size_t)R, 16)))) return rc;
     fcz_atoms_out dv;
-    dv.x = ctx->stage[4].as<float>(); dv.y = ctx->stage[5].as<float>(); dv.z = ctx->stage[6].as<float>();
-    dv.bfac_res = ctx->stage[7].as<float>(); dv.res_code = ctx->stage[8].as<uint8_t>(); dv.atom_code = nullptr;
-    if (R) {
-        rc = fcz_decompress_batch_dev(ctx, ctx->stage[0].as<uint8_t>(), ctx->stage[1].as<uint64_t>(), n, ctx->stage[2].as<uint32_t>(),
-                                      ctx->stage[3].as<uint32_t>(), 0, &dv);
-        if (rc) return rc;
-    }
-    ctx->sizes_fresh = false;
+    if ((rc = stage_atoms(ctx, R, M, false, &dv))) return rc;
+    if (R && (rc = decode_records(ctx, n, 0, &dv))) return rc;
     const size_t rows = (size_t)n * L;
     const size_t bytes[6] = {rows * A * 3 * sizeof(float), rows * A, out->aatype ? rows : 0, out->plddt ? rows * sizeof(float) : 0,
                              out->res_index ? rows * sizeof(int32_t) : 0, out->length ? sizeof(uint32_t) * n : 0};
@@ -1394,12 +1410,12 @@ int fcz_decompress_dense(fcz_ctx* ctx, const uint8_t* blob, const uint64_t* off,
     for (int i = 0; i < 6; i++) {
         dev[i] = nullptr;
         if (!bytes[i]) continue;
-        if ((rc = ctx->stage[10 + i].ensure(bytes[i]))) return rc;
-        dev[i] = ctx->stage[10 + i].p;
+        if ((rc = ctx->pool[DENSE_OUT + i].ensure(bytes[i]))) return rc;
+        dev[i] = ctx->pool[DENSE_OUT + i].p;
     }
     const fcz_dense_out dd{(float*)dev[0], (uint8_t*)dev[1], (uint8_t*)dev[2], (float*)dev[3], (int32_t*)dev[4], (uint32_t*)dev[5]};
-    rc = fcz_dense_dev(ctx, ctx->stage[0].as<uint8_t>(), ctx->stage[1].as<uint64_t>(), n, ctx->stage[2].as<uint32_t>(),
-                       ctx->stage[3].as<uint32_t>(), &dv, 0, layout, L, &dd);
+    rc = fcz_dense_dev(ctx, ctx->pool[REC_BLOB].as<uint8_t>(), ctx->pool[REC_OFF].as<uint64_t>(), n, ctx->pool[REC_RES_OFF].as<uint32_t>(),
+                       ctx->pool[REC_ATOM_OFF].as<uint32_t>(), &dv, 0, layout, L, &dd);
     if (rc) return rc;
     for (int i = 0; i < 6; i++)
         if (bytes[i]) HIP_TRY(hipMemcpyAsync(host[i], dev[i], bytes[i], hipMemcpyDeviceToHost, ctx->stream));
@@ -1439,7 +1455,6 @@ int fcz_undense_dev(fcz_ctx* ctx, const fcz_dense_in* in, uint32_t n, uint32_t L
     counts[0] = counts[1] = counts[2] = 0;
     out->anchor_threshold = ctx->ud_batch.anchor_threshold = anchor_threshold;
     if (n == 0) return FCZ_OK;
-    enum { U_ROWS, U_CHAIN, U_OUT_A, U_OUT_R, U_OUT_C };
     const size_t C = n, rows = C * (size_t)L;
     // per chain: residues, atoms, status, flags (overflow of the two scans) | res_off, first atom of the chain
     const size_t ch_nres = 0, ch_natoms = 4 * C, ch_status = 8 * C, ch_flags = 12 * C, ch_resoff = ch_flags + 16, ch_aoff = ch_resoff + 4 * (C + 1);
@@ -1455,20 +1470,20 @@ int fcz_undense_dev(fcz_ctx* ctx, const fcz_dense_in* in, uint32_t n, uint32_t L
     {
         span_guard sg(ctx, "undense");
         const dim3 grid(std::min<uint32_t>(n, (uint32_t)ctx->n_cu * 16u));
-        if (layout == FCZ_DENSE_ATOM37) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_undense_count<37>), grid, dim3(BLOCK), 0, ctx->stream, g, n, L, tab, row_word, n_res, n_atoms, status);
-        else if (layout == FCZ_DENSE_ATOM14) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_undense_count<14>), grid, dim3(BLOCK), 0, ctx->stream, g, n, L, tab, row_word, n_res, n_atoms, status);
-        else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_undense_count<4>), grid, dim3(BLOCK), 0, ctx->stream, g, n, L, tab, row_word, n_res, n_atoms, status);
+        dispatch_layout(layout, [&](auto A) {
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_undense_count<decltype(A)::value>), grid, dim3(BLOCK), 0, ctx->stream, g, n, L, tab, row_word, n_res, n_atoms, status);
+        });
     }
     if ((rc = device_scan<uint32_t>(ctx, n_res, res_off, n, ovf)) || (rc = device_scan<uint32_t>(ctx, n_atoms, chain_aoff, n, ovf))) return rc;
     HIP_TRY(hipGetLastError());
-    uint32_t* pin = ctx->pinned + 16;   // [16] residues, [17] atoms, [18] overflow
-    HIP_TRY(hipMemcpyAsync(&pin[0], res_off + n, 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(&pin[1], chain_aoff + n, 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(&pin[2], ovf, 4, hipMemcpyDeviceToHost, ctx->stream));
+    auto& pin = ctx->pinned->undense;
+    HIP_TRY(hipMemcpyAsync(&pin.residues, res_off + n, 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(&pin.atoms, chain_aoff + n, 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(&pin.overflow, ovf, 4, hipMemcpyDeviceToHost, ctx->stream));
     if (chain_status_dev) HIP_TRY(hipMemcpyAsync(chain_status_dev, status, 4 * C, hipMemcpyDeviceToDevice, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
-    if (pin[2]) return FCZ_E_INVALID_ARG;                      // the flat batch counts residues and atoms in 32 bits: split the call
-    const uint32_t R = pin[0], M = pin[1];
+    if (pin.overflow) return FCZ_E_INVALID_ARG;                // the flat batch counts residues and atoms in 32 bits: split the call
+    const uint32_t R = pin.residues, M = pin.atoms;
     // the batch arrays: [atoms] x y z code | [residues + 1] atom_off, [residues] bfac code | [chains] first residue, first atom,
     // [chains + 1] zero title offsets, [chains] chain id
     const size_t oa_y = 4 * (size_t)M, oa_z = 8 * (size_t)M, oa_c = 12 * (size_t)M;
@@ -1487,9 +1502,10 @@ int fcz_undense_dev(fcz_ctx* ctx, const fcz_dense_in* in, uint32_t n, uint32_t L
         const uint32_t tiles_per_chain = grid_for(L, DN_TILE);
         const uint64_t n_tiles = (uint64_t)n * tiles_per_chain;  // every index into the dense arrays is 64-bit: n * L * A * 3 may pass 2^32
         const dim3 grid((uint32_t)std::min<uint64_t>(n_tiles, (uint64_t)ctx->n_cu * 16u));
-        if (layout == FCZ_DENSE_ATOM37) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_undense_fill<37>), grid, dim3(BLOCK), 0, ctx->stream, g, L, tiles_per_chain, n_tiles, tab, (const uint16_t*)row_word, (const uint32_t*)res_off, (const uint32_t*)chain_aoff, o);
-        else if (layout == FCZ_DENSE_ATOM14) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_undense_fill<14>), grid, dim3(BLOCK), 0, ctx->stream, g, L, tiles_per_chain, n_tiles, tab, (const uint16_t*)row_word, (const uint32_t*)res_off, (const uint32_t*)chain_aoff, o);
-        else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_undense_fill<4>), grid, dim3(BLOCK), 0, ctx->stream, g, L, tiles_per_chain, n_tiles, tab, (const uint16_t*)row_word, (const uint32_t*)res_off, (const uint32_t*)chain_aoff, o);
+        dispatch_layout(layout, [&](auto A) {
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_undense_fill<decltype(A)::value>), grid, dim3(BLOCK), 0, ctx->stream, g, L, tiles_per_chain, n_tiles, tab,
+                               (const uint16_t*)row_word, (const uint32_t*)res_off, (const uint32_t*)chain_aoff, o);
+        });
     }
     HIP_TRY(hipGetLastError());
     fcz_chain_batch& b = ctx->ud_batch;
@@ -1510,25 +1526,14 @@ int fcz_undense_fetch(fcz_ctx* ctx, const fcz_chain_batch* hb, int32_t* chain_st
     if (!ctx) return FCZ_E_INVALID_ARG;
     HIP_TRY(hipSetDevice(ctx->device));
     const fcz_chain_batch& d = ctx->ud_batch;
-    const size_t C = d.n_chains, R = d.n_residues, M = d.n_atoms;
+    const size_t C = d.n_chains;
     if (C == 0) return FCZ_OK;
     if (hb) {
         uint32_t TB = 0;
         HIP_TRY(hipMemcpyAsync(&TB, d.title_off + C, 4, hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(hipStreamSynchronize(ctx->stream));
-        auto cp = [&](const void* dst, const void* src, size_t bytes) -> int {
-            if (!bytes) return FCZ_OK;
-            if (!dst) return FCZ_E_INVALID_ARG;
-            HIP_TRY(hipMemcpyAsync(const_cast<void*>(dst), src, bytes, hipMemcpyDeviceToHost, ctx->stream));
-            return FCZ_OK;
-        };
-        int rc;
-        if ((rc = cp(hb->res_off, d.res_off, 4 * (C + 1))) || (rc = cp(hb->atom_off, d.atom_off, 4 * (R + 1))) || (rc = cp(hb->x, d.x, 4 * M)) ||
-            (rc = cp(hb->y, d.y, 4 * M)) || (rc = cp(hb->z, d.z, 4 * M)) || (rc = cp(hb->atom_code, d.atom_code, M)) || (rc = cp(hb->res_code, d.res_code, R)) ||
-            (rc = cp(hb->bfac_ca, d.bfac_ca, 4 * R)) || (rc = cp(hb->first_res_index, d.first_res_index, 4 * C)) ||
-            (rc = cp(hb->first_atom_index, d.first_atom_index, 4 * C)) || (rc = cp(hb->chain_id, d.chain_id, C)) || (rc = cp(hb->titles, d.titles, TB)) ||
-            (rc = cp(hb->title_off, d.title_off, 4 * (C + 1))))
-            return rc;
+        int rc = fetch_batch(ctx, *hb, d, TB);
+        if (rc) return rc;
     }
     if (chain_status) HIP_TRY(hipMemcpyAsync(chain_status, ctx->ud_status, 4 * C, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
@@ -1542,9 +1547,9 @@ int fcz_compress_dense_begin_dev(fcz_ctx* ctx, const fcz_dense_in* in, uint32_t 
     fcz_chain_batch b;
     int rc = fcz_undense_dev(ctx, in, n, L, layout, anchor_threshold, &b, counts, nullptr);
     if (rc || n == 0) return rc;
-    ctx->sizes_fresh = false;   // staging buffers are rewritten
+    claim_staging(ctx);
     if ((rc = compress_resident_batch(ctx, ctx->ud_batch, &ctx->ud_fcz_bytes, fcz_bytes))) return rc;
-    hipLaunchKernelGGL(k_undense_merge_status, dim3(grid_for(n, BLOCK)), dim3(BLOCK), 0, ctx->stream, n, ctx->ud_status, ctx->stage[15].as<int32_t>());
+    hipLaunchKernelGGL(k_undense_merge_status, dim3(grid_for(n, BLOCK)), dim3(BLOCK), 0, ctx->stream, n, ctx->ud_status, ctx->pool[KEPT_STATUS].as<int32_t>());
     HIP_TRY(hipGetLastError());
     return FCZ_OK;
 }
@@ -1552,17 +1557,8 @@ int fcz_compress_dense_begin_dev(fcz_ctx* ctx, const fcz_dense_in* in, uint32_t 
 static int compress_dense_fetch(fcz_ctx* ctx, uint64_t* out_off, int32_t* status, uint8_t* blob, hipMemcpyKind kind) {
     if (!ctx) return FCZ_E_INVALID_ARG;
     HIP_TRY(hipSetDevice(ctx->device));
-    const uint32_t C = ctx->ud_batch.n_chains;
-    if (C) {
-        if (out_off) HIP_TRY(hipMemcpyAsync(out_off, ctx->stage[13].p, 8 * ((size_t)C + 1), kind, ctx->stream));
-        if (status) HIP_TRY(hipMemcpyAsync(status, ctx->stage[15].p, 4 * (size_t)C, kind, ctx->stream));
-        if (ctx->ud_fcz_bytes) {
-            if (!blob) return FCZ_E_INVALID_ARG;
-            HIP_TRY(hipMemcpyAsync(blob, ctx->stage[14].p, ctx->ud_fcz_bytes, kind, ctx->stream));
-        }
-    } else if (out_off) {
-        if (kind == hipMemcpyDeviceToHost) out_off[0] = 0; else HIP_TRY(hipMemsetAsync(out_off, 0, 8, ctx->stream));
-    }
+    int rc = fetch_resident(ctx, ctx->ud_batch.n_chains, ctx->ud_fcz_bytes, out_off, status, blob, kind);
+    if (rc) return rc;
     if (kind == hipMemcpyDeviceToHost) HIP_TRY(hipStreamSynchronize(ctx->stream));
     return FCZ_OK;
 }
@@ -1577,7 +1573,8 @@ int fcz_compress_dense_begin(fcz_ctx* ctx, const fcz_dense_in* in, uint32_t n, u
     *fcz_bytes = 0; ctx->ud_fcz_bytes = 0;
     HIP_TRY(hipSetDevice(ctx->device));
     if (n == 0) return fcz_compress_dense_begin_dev(ctx, in, 0, L, layout, anchor_threshold, counts, fcz_bytes);
-    ctx->sizes_fresh = false;   // staging buffers are rewritten
+    claim_staging(ctx);
+    int rc;
     const size_t C = n, rows = C * (size_t)L, A = (size_t)fcz_dense_width(layout);
     const size_t title_bytes = in->title_off ? in->title_off[n] : 0;
     const void* host[10] = {in->pos, in->mask, in->aatype, in->length, in->plddt, in->first_res_index, in->first_atom_index, in->chain_id,
@@ -1587,10 +1584,9 @@ int fcz_compress_dense_begin(fcz_ctx* ctx, const fcz_dense_in* in, uint32_t n, u
     for (int i = 0; i < 10; i++) {
         dev[i] = nullptr;
         if (!host[i]) continue;
-        int rc = ctx->stage[i].ensure(std::max<size_t>(bytes[i], 16));
-        if (rc) return rc;
-        dev[i] = ctx->stage[i].p;
-        if (bytes[i]) HIP_TRY(hipMemcpyAsync(ctx->stage[i].p, host[i], bytes[i], hipMemcpyHostToDevice, ctx->stream));
+        if ((rc = ctx->pool[DENSE_IN + i].ensure(std::max<size_t>(bytes[i], 16)))) return rc;
+        dev[i] = ctx->pool[DENSE_IN + i].p;
+        if (bytes[i]) HIP_TRY(hipMemcpyAsync(ctx->pool[DENSE_IN + i].p, host[i], bytes[i], hipMemcpyHostToDevice, ctx->stream));
     }
     const fcz_dense_in dv{(const float*)dev[0], (const uint8_t*)dev[1], (const uint8_t*)dev[2], (const uint32_t*)dev[3], (const float*)dev[4],
                           (const int32_t*)dev[5], (const int32_t*)dev[6], (const char*)dev[7], (const char*)dev[8], (const uint32_t*)dev[9]};
@@ -1708,11 +1704,11 @@ extern "C" int fcz_selftest_math(fcz_ctx* ctx, int mode, uint32_t start_bits, ui
     if (!ctx || !out_host || mode < 0 || mode > 13) return FCZ_E_INVALID_ARG;
     HIP_TRY(hipSetDevice(ctx->device));
     if (count == 0) return FCZ_OK;
-    int rc = ctx->stage[17].ensure(sizeof(float) * (size_t)count); if (rc) return rc;
+    int rc = ctx->selftest_out.ensure(sizeof(float) * (size_t)count); if (rc) return rc;
     hipLaunchKernelGGL(fcz::k_selftest_math, dim3(grid_for(count, 256)), dim3(256), 0, ctx->stream, mode, start_bits, stride, count,
-                       ctx->stage[17].as<float>());
+                       ctx->selftest_out.as<float>());
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(out_host, ctx->stage[17].p, sizeof(float) * (size_t)count, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(out_host, ctx->selftest_out.p, sizeof(float) * (size_t)count, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return FCZ_OK;
 }

@@ -9,7 +9,9 @@ import zlib
 import numpy as np
 import pytest
 
+import _dense as D
 import _harness as H
+import _undense as U
 from _cases import entries_blob
 from _devpath import DevRecords, compress_dev
 from foldcomp_amd import synthetic
@@ -64,6 +66,8 @@ class _Calls:
         self.gold_names = [n for n in self.index if f"{n}/pdb0" in self.z.files and f"{n}/fcz" in self.z.files][:12]
         self.gold = [self.z[f"{n}/fcz"].tobytes() for n in self.gold_names]
         self.fast = False
+        self.gold_flat = H.oracle_decompress(*entries_blob(self.gold))              # the atoms the dense tensors are filled from
+        self.dense_want, self.undense_want = {}, {}
 
     # -- codec calls against the oracle
     def compress(self, key, dev=False):
@@ -123,7 +127,50 @@ class _Calls:
         d = DevRecords(blob, off).decompress(self.codec)                              # R == 0 through the device entry points: sizes, then batch
         assert not d["res_off"].any() and not d["atom_off"].any() and len(d["x"]) == 0
 
+    def encode_dense(self, key, layout):
+        """dense tensors in where other entry points stage records; leaves resident records for its fetch"""
+        b = self.batches[key]
+        L = int(np.diff(b.res_off.astype(np.int64)).max())
+        titles = [bytes(b.titles[int(b.title_off[c]):int(b.title_off[c + 1])]).decode("latin-1") for c in range(b.n_chains)]
+        d = U.dense_from_batch(b, layout, L)
+        if (key, layout) not in self.undense_want:
+            eb, refusal = U.batch_expected(d["pos"], d["mask"], d["aatype"], d["length"], layout, plddt=d["plddt"],
+                                           first_res_index=d["first_res_index"], chain_id=b.chain_id, titles=titles,
+                                           anchor_threshold=int(b.anchor_threshold))
+            blob, off, ost = H.oracle_compress(eb, n_threads=1)
+            st = U.expected_status(refusal, ost)
+            # the expectation comes from the builder + oracle for every layout. Where the tensors hold every atom the records must also be
+            # the batch's own; that holds for atom37 only: all_atoms_have_slots lets a chain's closing OXT pass in any layout, but
+            # atom14 has no slot for it, so its tensors drop the atom and the records differ from the batch's own
+            if layout == "atom37" and U.all_atoms_have_slots(b, layout):
+                assert np.array_equal(off, self.oracle[key][1]) and blob.tobytes() == self.oracle[key][0].tobytes()
+            self.undense_want[key, layout] = (blob, off, st)
+        wblob, woff, wst = self.undense_want[key, layout]
+        blob, off, st = self.codec.compress_dense(d["pos"], d["mask"], d["aatype"], d["length"], d["plddt"], layout=layout,
+                                                  first_res_index=d["first_res_index"], chain_id=b.chain_id, titles=titles,
+                                                  anchor_threshold=int(b.anchor_threshold))
+        assert not wst.any() and np.array_equal(st, wst) and np.array_equal(off, woff) and blob.tobytes() == wblob.tobytes()
+
     # -- the other entry points against the reference's goldens
+    def decode_dense(self, layout, crop=False):
+        """the golden records as dense tensors; cropped: one row less than the longest entry has (other staging sizes)"""
+        fields = [D.record_fields(f) for f in self.gold]
+        L = max(len(seq) for seq, _, _ in fields) - (1 if crop else 0)
+        if (layout, L) not in self.dense_want:
+            o, per = self.gold_flat, []
+            for i, (seq, first, has_oxt) in enumerate(fields):
+                a0, a1, r0 = int(o["atom_off"][i]), int(o["atom_off"][i + 1]), int(o["res_off"][i])
+                xyz = np.stack([o["x"][a0:a1], o["y"][a0:a1], o["z"][a0:a1]], 1)
+                per.append(D.dense_expected(xyz, seq, first, has_oxt, layout, L, plddt=o["bfac_res"][r0:r0 + len(seq)]))
+            self.dense_want[layout, L] = D.stack_expected(per, L, D.WIDTH[layout])
+        want = self.dense_want[layout, L]
+        got = self.codec.decompress_dense(*entries_blob(self.gold), layout=layout, max_len=L if crop else None)
+        assert not got["status"].any() and got["pos"].shape == (len(self.gold), L, D.WIDTH[layout], 3)
+        for k in ("pos", "plddt"):
+            assert np.array_equal(D.bits(got[k]), D.bits(want[k])), (layout, L, k)
+        for k in ("mask", "aatype", "res_index", "length"):
+            assert np.array_equal(got[k].astype(np.int64), want[k].astype(np.int64)), (layout, L, k)
+
     def pdb_text(self, alt=False):
         blob, off = entries_blob(self.gold)
         texts, status = self.codec.decompress_pdb(blob, off)
@@ -160,6 +207,19 @@ class _Calls:
             rec = r["blob"][int(r["off"][i]):int(r["off"][i + 1])].tobytes()
             assert _no_title(rec) == _no_title(self.z[f"{n}/fcz"].tobytes()), n
 
+    def compress_gz(self):
+        """three gzip members and two plain texts: the inflate stage writes the text the ingest reads"""
+        cases, texts, names = self._texts()
+        files, is_gz = [], [1, 0, 1, 1, 0]
+        for t, gz, lvl in zip(texts, is_gz, (6, 6, 1, 9, 6)):
+            c = zlib.compressobj(lvl, zlib.DEFLATED, 31)
+            files.append(c.compress(t) + c.flush() if gz else t)
+        r = self.codec.compress_gz(files, names, is_gz=is_gz)
+        assert (r["status"] == 0).all() and (r["file_status"] == 0).all() and len(r["refused"]) == 0
+        for i, n in enumerate(cases):
+            rec = r["blob"][int(r["off"][i]):int(r["off"][i + 1])].tobytes()
+            assert _no_title(rec) == _no_title(self.z[f"{n}/fcz"].tobytes()), n
+
     def ingest_pdb(self):
         cases, texts, names = self._texts()
         b, cfile, cmeta, fstat, refused = self.codec.ingest_pdb(texts, names)
@@ -171,7 +231,8 @@ class _Calls:
 
 
 def _sequence(seed):
-    """fixed opening (the orders the issue names), then seeded draws: 40 .. 60 calls"""
+    """fixed opening (the orders the issue names), then seeded draws, then the dense and gzip entry points, each beside a call that
+    uses the same staging buffers differently: 40 .. 70 calls"""
     seq = [("compress", "large"), ("decompress", "large"), ("decompress", "tiny"), ("compress", "tiny"), ("decompress", "large", True),
            ("decompress", "long"), ("decompress", "small"), ("decompress", "long", True), ("compress", "rich"), ("compress", "small"),
            ("decompress", "rich"), ("decompress", "small", True), ("numerics", True), ("decompress", "large"), ("decompress", "tiny"),
@@ -193,6 +254,9 @@ def _sequence(seed):
             fast = not fast; seq.append(("numerics", fast))
         else:
             seq.append([("empty",), ("all_refused",), ("pdb_text",), ("extract", int(rng.integers(1, 5))), ("inflate",), ("compress_pdb",)][int(rng.integers(0, 6))])
+    # (not among the draws: the history above stays what it was)
+    seq += [("encode_dense", "small", "atom37"), ("decompress", "tiny"), ("decode_dense", "atom37"), ("pdb_text",), ("compress_gz",),
+            ("encode_dense", "small", "atom14"), ("decode_dense", "atom14"), ("decode_dense", "atom37", True)]
     seq += [("numerics", False), ("decompress", "large", True), ("decompress", "tiny")]
     return seq
 
@@ -202,7 +266,7 @@ def test_results_do_not_depend_on_what_the_ctx_did_before(golden):
     torch.cuda.init()
     from foldcomp_amd.codec import Codec
     seq = _sequence(20261016)
-    assert 40 <= len(seq) <= 60
+    assert 40 <= len(seq) <= 70
     codec = Codec(0)
     try:
         calls = _Calls(codec, golden)

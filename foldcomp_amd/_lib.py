@@ -9,7 +9,7 @@ from __future__ import annotations
 import ctypes
 import os
 
-from .structure import CAtomsOut, CChainBatch, CDenseIn, CDenseOut, CEntryInfo, CIngestResult
+from .structure import CAtomsOut, CChainBatch, CDenseIn, CDenseOut, CEntryInfo, CIngestResult, CPackedOut
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # FCZ_HIP_LIB selects another build of the same library (A/B timing of kernel variants); it is still a HIP build
@@ -73,6 +73,11 @@ def load():
         "fcz_dense_slot": (i32, [i32, i32, i32]),
         "fcz_dense_dev": (i32, [vp, vp, vp, u32, vp, vp, PO, i32, i32, u32, ctypes.POINTER(CDenseOut)]),
         "fcz_decompress_dense": (i32, [vp, vp, vp, u32, i32, u32, ctypes.POINTER(u32), ctypes.POINTER(CDenseOut), vp]),
+        "fcz_dense_packed_dev": (i32, [vp, vp, vp, u32, vp, vp, PO, i32, i32, ctypes.POINTER(CPackedOut)]),
+        "fcz_decompress_dense_packed": (i32, [vp, vp, vp, u32, i32, ctypes.POINTER(u32), vp, ctypes.POINTER(CPackedOut), vp]),
+        "fcz_undense_packed_dev": (i32, [vp, ctypes.POINTER(CDenseIn), vp, u32, u32, i32, i32, PB, vp, vp]),
+        "fcz_compress_dense_packed_begin_dev": (i32, [vp, ctypes.POINTER(CDenseIn), vp, u32, u32, i32, i32, vp, ctypes.POINTER(u64)]),
+        "fcz_compress_dense_packed_begin": (i32, [vp, ctypes.POINTER(CDenseIn), vp, u32, u32, i32, i32, vp, ctypes.POINTER(u64)]),
         "fcz_undense_dev": (i32, [vp, ctypes.POINTER(CDenseIn), u32, u32, i32, i32, PB, vp, vp]),
         "fcz_undense_fetch": (i32, [vp, PB, vp]),
         "fcz_compress_dense_begin_dev": (i32, [vp, ctypes.POINTER(CDenseIn), u32, u32, i32, i32, vp, ctypes.POINTER(u64)]),
@@ -117,6 +122,8 @@ EXPORTS = ["fcz_ctx_create", "fcz_ctx_destroy", "fcz_ctx_stream", "fcz_ctx_synch
            "fcz_decompress_pdb_begin", "fcz_decompress_pdb_fetch", "fcz_decompress_pdb_sizes",
            "fcz_dense_width", "fcz_dense_slot", "fcz_dense_dev", "fcz_decompress_dense", "fcz_undense_dev", "fcz_undense_fetch",
            "fcz_compress_dense_begin_dev", "fcz_compress_dense_fetch_dev", "fcz_compress_dense_begin", "fcz_compress_dense_fetch",
+           "fcz_dense_packed_dev", "fcz_decompress_dense_packed", "fcz_undense_packed_dev", "fcz_compress_dense_packed_begin_dev",
+           "fcz_compress_dense_packed_begin",
            "fcz_extract_sizes", "fcz_extract",
            "fcz_extract_sizes_dev", "fcz_extract_dev", "fcz_ingest_pdb_dev", "fcz_ingest_pdb_begin", "fcz_ingest_pdb_fetch", "fcz_ingest_chain_names_fetch",
            "fcz_compress_pdb_begin", "fcz_compress_pdb_fetch", "fcz_inflate_sizes", "fcz_inflate_dev", "fcz_inflate",

@@ -241,25 +241,32 @@ class FoldcompDatabase:
                 yield r
 
     def tensor_batches(self, batch_size: int = 1024, *, layout="atom37", max_len: Optional[int] = None, device="cuda:0",
-                       sort_by_length: bool = False):
+                       sort_by_length: bool = False, packed: bool = False, max_residues: Optional[int] = None):
         """Generator over the database (its `ids` selection when it has one) in batches of dense model-input tensors on the GPU:
         the dicts of foldcomp_amd.tensors.decode_tensors, each with `names` (the records' titles) and `index` (int64 array: the
         entries' positions in this database, what db[i] takes). sort_by_length orders every window of 16 * batch_size entries by
-        residue count (from the record headers) before it is cut into batches, so that a batch pads little; `index` undoes it."""
+        residue count (from the record headers) before it is cut into batches, so that a batch pads little; `index` undoes it.
+        packed=True yields the packed dicts (decode_tensors(packed=True): no padding, no crop, cu_seqlens), and max_residues then
+        cuts the batches by a residue budget (cut_batches): a batch closes before the entry that would take it over the budget
+        or at batch_size entries; an entry longer than the budget forms a batch of its own."""
         from .tensors import decode_tensors
         batch_size = int(batch_size)
         if batch_size < 1:
             raise ValueError("batch_size must be at least 1")
+        check_batch_cut(packed, max_len, max_residues)
         window = 16 * batch_size if sort_by_length else batch_size
+        if max_residues is not None:
+            window = 16 * batch_size                    # (a budget closes batches early: read ahead as the sort does)
         for start in range(0, len(self), window):
             idx = np.arange(start, min(start + window, len(self)), dtype=np.int64)
             ents = [self._entry(int(i)) for i in idx]
-            order = np.arange(len(ents))
-            if sort_by_length:
-                order = np.argsort(np.asarray([fczfile.residue_count(e) for e in ents], np.int64), kind="stable")
-            for b in range(0, len(ents), batch_size):
-                sel = order[b:b + batch_size]
-                d = decode_tensors([ents[k] for k in sel], layout=layout, max_len=max_len, device=device)
+            lens = [fczfile.residue_count(e) for e in ents] if sort_by_length or max_residues is not None else [0] * len(ents)
+            for sel in cut_batches(lens, batch_size, max_residues, sort_by_length):
+                sel = np.asarray(sel, np.int64)
+                if packed:
+                    d = decode_tensors([ents[k] for k in sel], layout=layout, device=device, packed=True)
+                else:
+                    d = decode_tensors([ents[k] for k in sel], layout=layout, max_len=max_len, device=device)
                 d["index"] = idx[sel]
                 yield d
 
@@ -274,6 +281,42 @@ class FoldcompDatabase:
 
     def __exit__(self, *a):
         self.close()
+
+
+def check_batch_cut(packed, max_len, max_residues):
+    """the argument rules of tensor_batches that need no database and no GPU"""
+    if max_residues is not None and not packed:
+        raise ValueError("max_residues cuts packed batches: pass packed=True (a padded batch is sized by batch_size and max_len)")
+    if max_residues is not None and int(max_residues) < 1:
+        raise ValueError("max_residues must be at least 1")
+    if packed and max_len is not None:
+        raise ValueError("max_len crops to a common length; the packed form keeps every residue (packed=True takes no max_len)")
+
+
+def cut_batches(lengths, batch_size: int, max_residues: Optional[int] = None, sort_by_length: bool = False) -> list:
+    """Positions 0 .. len(lengths) - 1 of one window cut into batches -> list of lists of positions, every position once.
+
+    The positions are taken in their own order, or by residue count (stable) under sort_by_length. A batch closes at batch_size
+    entries, and, with max_residues, before the entry that would take its residues over the budget; an entry longer than the
+    budget forms a batch of its own (nothing is cropped or dropped). Pure: what tensor_batches does with the record headers'
+    residue counts."""
+    batch_size = int(batch_size)
+    if batch_size < 1:
+        raise ValueError("batch_size must be at least 1")
+    if max_residues is not None and int(max_residues) < 1:
+        raise ValueError("max_residues must be at least 1")
+    lengths = [int(x) for x in lengths]
+    order = sorted(range(len(lengths)), key=lengths.__getitem__) if sort_by_length else list(range(len(lengths)))   # (sorted is stable)
+    out, cur, total = [], [], 0
+    for k in order:
+        if cur and (len(cur) == batch_size or (max_residues is not None and total + lengths[k] > int(max_residues))):
+            out.append(cur)
+            cur, total = [], 0
+        cur.append(k)
+        total += lengths[k]
+    if cur:
+        out.append(cur)
+    return out
 
 
 def open(path, *, ids=None, decompress=True, err_on_missing=False) -> FoldcompDatabase:  # noqa: A001

@@ -15,7 +15,7 @@ from typing import Optional
 import numpy as np
 
 from . import _lib
-from .structure import CAtomsOut, CChainBatch, CDenseIn, CDenseOut, CEntryInfo, ChainBatch, batch_as_c
+from .structure import CAtomsOut, CChainBatch, CDenseIn, CDenseOut, CEntryInfo, ChainBatch, CPackedOut, batch_as_c
 
 
 DENSE_LAYOUTS = {"atom37": 0, "atom14": 1, "backbone4": 2}     # enum fcz_dense_layout
@@ -120,17 +120,39 @@ class Codec:
                        "fcz_decompress_batch")
         return dict(x=x, y=y, z=z, bfac_res=bf, res_code=rc, atom_code=ac, res_off=res_off, atom_off=atom_off, info=info)
 
-    def decompress_dense(self, blob: np.ndarray, off: np.ndarray, layout="atom37", max_len: Optional[int] = None):
+    def decompress_dense(self, blob: np.ndarray, off: np.ndarray, layout="atom37", max_len: Optional[int] = None, packed: bool = False):
         """FCZ entries -> dense padded arrays on the host (fcz_decompress_dense): pos float32 [n, L, A, 3], mask bool [n, L, A],
         aatype uint8 [n, L] (20 = unknown / padding), plddt float32 [n, L], res_index int32 [n, L], length uint32 [n] (uncropped;
-        0 = the entry did not decode), status int32 [n]. L = max_len, or the longest entry of the batch; longer entries are cropped."""
+        0 = the entry did not decode), status int32 [n]. L = max_len, or the longest entry of the batch; longer entries are cropped.
+        packed=True (fcz_decompress_dense_packed): the rows of all entries back to back, pos [R, A, 3], mask [R, A], aatype, plddt,
+        res_index, chain_index int32 [R], row_off uint32 [n + 1] (the cu_seqlens), length, status; no padding and no crop, so no max_len."""
         blob = np.ascontiguousarray(blob, np.uint8)
         off = np.ascontiguousarray(off, np.uint64)
         n = len(off) - 1
         lay = dense_layout(layout)
         A = self.lib.fcz_dense_width(lay)
+        if packed and max_len is not None:
+            raise ValueError("max_len crops to a common length; the packed form keeps every residue (packed=True takes no max_len)")
         if max_len is not None and int(max_len) < 1:
             raise ValueError("max_len must be at least 1")
+        if packed:
+            R = ctypes.c_uint32(0)
+            status = np.zeros(max(n, 1), np.int32)
+            row_off = np.zeros(n + 1, np.uint32)
+            if n:
+                _lib.check(self.lib.fcz_decompress_dense_packed(self.ctx, blob.ctypes.data, off.ctypes.data, n, lay, ctypes.byref(R), row_off.ctypes.data,
+                                                                None, status.ctypes.data), "fcz_decompress_dense_packed")
+            Rv = int(R.value)
+            d = dict(pos=np.zeros((Rv, A, 3), np.float32), mask=np.zeros((Rv, A), np.uint8), aatype=np.zeros(Rv, np.uint8), plddt=np.zeros(Rv, np.float32),
+                     res_index=np.zeros(Rv, np.int32), chain_index=np.zeros(Rv, np.int32), length=np.zeros(n, np.uint32))
+            if n and Rv:
+                out = CPackedOut(*(d[k].ctypes.data for k in ("pos", "mask", "aatype", "plddt", "res_index", "chain_index", "length")))
+                _lib.check(self.lib.fcz_decompress_dense_packed(self.ctx, blob.ctypes.data, off.ctypes.data, n, lay, None, None, ctypes.byref(out),
+                                                                None), "fcz_decompress_dense_packed")
+            d["mask"] = d["mask"].view(np.bool_)
+            d["row_off"] = row_off
+            d["status"] = status[:n]
+            return d
         L = ctypes.c_uint32(0)
         status = np.zeros(max(n, 1), np.int32)
         if max_len is None:
@@ -206,6 +228,61 @@ class Codec:
         counts = np.zeros(3, np.uint32); nbytes = ctypes.c_uint64(0)
         _lib.check(self.lib.fcz_compress_dense_begin(self.ctx, ctypes.byref(s), n, L, lay, int(anchor_threshold), counts.ctypes.data,
                                                      ctypes.byref(nbytes)), "fcz_compress_dense_begin")
+        off = np.zeros(n + 1, np.uint64); st = np.zeros(n, np.int32); blob = np.zeros(max(int(nbytes.value), 1), np.uint8)
+        _lib.check(self.lib.fcz_compress_dense_fetch(self.ctx, off.ctypes.data, st.ctypes.data, blob.ctypes.data), "fcz_compress_dense_fetch")
+        return blob[:int(nbytes.value)], off, st
+
+    def compress_dense_packed(self, pos, mask, aatype, row_off, plddt=None, *, layout="atom37", first_res_index=None, chain_id=None, titles=None,
+                              anchor_threshold: int = 25):
+        """packed dense arrays on the host -> (blob, off uint64[n + 1], status int32[n]): fcz_compress_dense_packed_begin / fcz_compress_dense_fetch.
+        pos [R, A, 3] float32, mask [R, A], aatype [R], plddt [R] or None, row_off [n + 1]: chain c is rows row_off[c] .. row_off[c + 1] - 1.
+        The contract is compress_dense's; a chain whose range runs backwards, leaves the R rows or holds more than 65 535 of them is refused."""
+        lay = dense_layout(layout)
+        A = self.lib.fcz_dense_width(lay)
+        pos = np.ascontiguousarray(pos, np.float32)
+        if pos.ndim != 3 or pos.shape[1:] != (A, 3):
+            raise ValueError(f"pos must be [R, {A}, 3] for layout {layout!r}, not {tuple(pos.shape)}")
+        R = int(pos.shape[0])
+        row_off = np.asarray(row_off)
+        if row_off.ndim != 1 or len(row_off) < 1:
+            raise ValueError("row_off must be [n + 1]")
+        if (row_off.astype(np.int64) < 0).any() or (row_off.astype(np.int64) > 2 ** 32 - 1).any():
+            raise ValueError("row_off must fit unsigned 32 bits")
+        n = len(row_off) - 1
+        # the padded checker over [1, R]: shapes, dtypes, per-chain header fields (its length and L are not handed on)
+        s, _, _, _, keep = self._dense_in(pos[None], np.asarray(mask)[None], np.asarray(aatype)[None], np.zeros(1, np.uint32),
+                                          None if plddt is None else np.asarray(plddt)[None], layout, None, None, None)
+        s.length = None
+        ro = np.ascontiguousarray(row_off, np.uint32)
+        keep.append(ro)
+
+        def per(a, dtype, what):
+            a = np.ascontiguousarray(a, dtype)
+            if a.shape != (n,):
+                raise ValueError(f"{what} must have shape {(n,)}, not {a.shape}")
+            keep.append(a)
+            return a.ctypes.data
+
+        if first_res_index is not None:
+            s.first_res_index = per(first_res_index, np.int32, "first_res_index")
+        if chain_id is not None:
+            s.chain_id = per([ord(c) if isinstance(c, str) else int(c) for c in chain_id], np.uint8, "chain_id")
+        if titles is not None:
+            tb = [t.encode("latin-1", "replace") if isinstance(t, str) else bytes(t) for t in titles]
+            if len(tb) != n:
+                raise ValueError(f"{len(tb)} titles for {n} chains")
+            toff = np.zeros(n + 1, np.uint32)
+            toff[1:] = np.cumsum([len(t) for t in tb])
+            tt = np.frombuffer(b"".join(tb) or b"\0", np.uint8)
+            keep += [toff, tt]
+            s.titles, s.title_off = tt.ctypes.data, toff.ctypes.data
+        if n == 0:
+            return np.zeros(0, np.uint8), np.zeros(1, np.uint64), np.zeros(0, np.int32)
+        if R == 0:
+            raise ValueError("compress_dense_packed: the arrays have no rows (R = 0)")
+        counts = np.zeros(3, np.uint32); nbytes = ctypes.c_uint64(0)
+        _lib.check(self.lib.fcz_compress_dense_packed_begin(self.ctx, ctypes.byref(s), ro.ctypes.data, n, R, lay, int(anchor_threshold),
+                                                            counts.ctypes.data, ctypes.byref(nbytes)), "fcz_compress_dense_packed_begin")
         off = np.zeros(n + 1, np.uint64); st = np.zeros(n, np.int32); blob = np.zeros(max(int(nbytes.value), 1), np.uint8)
         _lib.check(self.lib.fcz_compress_dense_fetch(self.ctx, off.ctypes.data, st.ctypes.data, blob.ctypes.data), "fcz_compress_dense_fetch")
         return blob[:int(nbytes.value)], off, st

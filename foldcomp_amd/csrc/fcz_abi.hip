@@ -79,11 +79,12 @@ struct timed_span { std::string name; hipEvent_t a, b; };
 // fcz_ctx::pool, the staging of the host-pointer entry points: the names a buffer has, one per role. Roles that share a buffer are
 // never live together (table in fcz_ctx). REC_*: uploaded FCZ records (n + 1 u64 offsets), their res_off / atom_off (n + 1 u32) and
 // the fcz_atoms_out decoded from them; FILES_*: structure files of an ingest call; BATCH_IN / DENSE_IN / DENSE_OUT: first of the 13
-// arrays of a fcz_chain_batch, the 10 of a fcz_dense_in, the 6 of a fcz_dense_out, in the struct's order; KEPT_*: the records a
-// *_begin call leaves for its fetch (C + 1 u64 offsets, the bytes, C i32 status)
+// arrays of a fcz_chain_batch, the 10 of a fcz_dense_in (slot 3, length, holds row_off [n + 1] in the packed form), the 6 of a
+// fcz_dense_out, the 7 of a fcz_packed_out (PACKED_OUT .. PACKED_OUT_LAST), in the struct's order; KEPT_*: the records a *_begin
+// call leaves for its fetch (C + 1 u64 offsets, the bytes, C i32 status)
 enum { REC_BLOB, REC_OFF, REC_RES_OFF, REC_ATOM_OFF, REC_X, REC_Y, REC_Z, REC_BFAC, REC_RES_CODE, REC_ATOM_CODE,
        FILES_TEXT = 0, FILES_OFF, FILES_NAMES, FILES_NAME_OFF, FILES_STEM_LEN, BATCH_IN = 0, DENSE_IN = 0, DENSE_OUT = 10,
-       KEPT_OFF = 13, KEPT_BYTES, KEPT_STATUS, POOL_COUNT };
+       PACKED_OUT = 10, KEPT_OFF = 13, KEPT_BYTES, KEPT_STATUS, PACKED_OUT_LAST, POOL_COUNT };
 
 // what the device reports to the host in the middle of a call: one pinned allocation, a member per reader
 struct pinned_words {
@@ -140,12 +141,14 @@ struct fcz_ctx {
     //   fcz_decompress_pdb_begin / _sizes           REC_* 0 .. 8                                (pdb_text, pdb_bytes)
     //   fcz_extract                                 REC_BLOB, REC_OFF
     //   fcz_decompress_dense                        REC_* 0 .. 8, DENSE_OUT 10 .. 15
+    //   fcz_decompress_dense_packed                 REC_* 0 .. 8, PACKED_OUT 10 .. 16
     //   fcz_compress_batch                          BATCH_IN 0 .. 12, KEPT_* 13 .. 15
     //   fcz_inflate                                 FILES_TEXT
     //   fcz_ingest_pdb_begin / fcz_ingest_gz_begin  FILES_* 0 .. 4 (gz: no FILES_OFF, gz_toff)      (ig[], ig_res, ig_counts)
     //   fcz_compress_pdb_begin / _gz_begin          the same, then KEPT_* 13 .. 15              KEPT_*, ig_fcz_bytes (+ ig[], ig_res)
     //   fcz_compress_dense_begin                    DENSE_IN 0 .. 9, then KEPT_* 13 .. 15       KEPT_*, ud_fcz_bytes (+ ud_batch)
     //   fcz_compress_dense_begin_dev                KEPT_* 13 .. 15                             KEPT_*, ud_fcz_bytes (+ ud_batch)
+    //   fcz_compress_dense_packed_begin[_dev]       as the two above (DENSE_IN 3 = row_off)     the same
     dev_buf pool[POOL_COUNT];
     // PDB text / extracted data: per-entry sizes (any call), offsets (n + 1 u64) and the text of the last fcz_decompress_pdb_begin,
     // which fcz_decompress_pdb_fetch reads: live until the next fcz_decompress_pdb_begin / _sizes or fcz_extract
@@ -1377,6 +1380,67 @@ int fcz_dense_dev(fcz_ctx* ctx, const uint8_t* blob_dev, const uint64_t* off_dev
     return FCZ_OK;
 }
 
+int fcz_dense_packed_dev(fcz_ctx* ctx, const uint8_t* blob_dev, const uint64_t* off_dev, uint32_t n, const uint32_t* res_off_dev,
+                         const uint32_t* atom_off_dev, const fcz_atoms_out* atoms_dev, int alt_order, int layout, const fcz_packed_out* out_dev) {
+    if (!ctx || !blob_dev || !off_dev || !res_off_dev || !atom_off_dev || !atoms_out_ok(atoms_dev) || !out_dev) return FCZ_E_INVALID_ARG;
+    if (fcz_dense_width(layout) < 0 || !out_dev->pos || !out_dev->mask) return FCZ_E_INVALID_ARG;
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (n == 0) return FCZ_OK;
+    const dense_table tab = dense_make_table(layout, alt_order ? 1 : 0);
+    const dense_args g{off_dev, res_off_dev, atom_off_dev, atoms_dev->x, atoms_dev->y, atoms_dev->z, atoms_dev->bfac_res, atoms_dev->res_code,
+                       out_dev->pos, out_dev->mask, out_dev->aatype, out_dev->plddt, out_dev->res_index, out_dev->length};
+    // the tiles are counted on the device (res_off[n] / DN_TILE): at most 1 024 per entry, a record holds 65 535 residues
+    const uint32_t blocks = (uint32_t)std::min<uint64_t>((uint64_t)n * 1024u, (uint64_t)ctx->n_cu * 32u);
+    span_guard sg(ctx, "dense");
+    dispatch_layout(layout, [&](auto A) {
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_dense_packed<decltype(A)::value>), dim3(blocks), dim3(BLOCK), 0, ctx->stream, blob_dev, g, out_dev->chain_index, n, tab);
+    });
+    HIP_TRY(hipGetLastError());
+    return FCZ_OK;
+}
+
+int fcz_decompress_dense_packed(fcz_ctx* ctx, const uint8_t* blob, const uint64_t* off, uint32_t n, int layout, uint32_t* R_out, uint32_t* row_off,
+                                const fcz_packed_out* out, int32_t* status) {
+    const int A = fcz_dense_width(layout);
+    if (!ctx || !blob || !off || A < 0 || (!out && !R_out) || (out && (!out->pos || !out->mask))) return FCZ_E_INVALID_ARG;
+    HIP_TRY(hipSetDevice(ctx->device));
+    claim_staging(ctx);
+    if (R_out) *R_out = 0;
+    if (n == 0) { if (row_off) row_off[0] = 0; return FCZ_OK; }
+    uint32_t R = 0, M = 0;
+    int rc = upload_records(ctx, blob, off, n, &R, &M); if (rc) return rc;
+    if (row_off) HIP_TRY(hipMemcpyAsync(row_off, ctx->pool[REC_RES_OFF].p, sizeof(uint32_t) * ((size_t)n + 1), hipMemcpyDeviceToHost, ctx->stream));
+    if (status) HIP_TRY(hipMemcpyAsync(status, cnt_status(ctx, n), sizeof(int32_t) * n, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    if (R_out) *R_out = R;
+    if (!out) return FCZ_OK;
+    if (R == 0) {               // no entry decodes: no row
+        if (out->length) memset(out->length, 0, sizeof(uint32_t) * n);
+        return FCZ_OK;
+    }
+    fcz_atoms_out dv;
+    if ((rc = stage_atoms(ctx, R, M, false, &dv)) || (rc = decode_records(ctx, n, 0, &dv))) return rc;
+    const size_t rows = R;
+    const size_t bytes[7] = {rows * A * 3 * sizeof(float), rows * A, out->aatype ? rows : 0, out->plddt ? rows * sizeof(float) : 0,
+                             out->res_index ? rows * sizeof(int32_t) : 0, out->chain_index ? rows * sizeof(int32_t) : 0, out->length ? sizeof(uint32_t) * n : 0};
+    void* host[7] = {out->pos, out->mask, out->aatype, out->plddt, out->res_index, out->chain_index, out->length};
+    void* dev[7];
+    for (int i = 0; i < 7; i++) {
+        dev[i] = nullptr;
+        if (!bytes[i]) continue;
+        if ((rc = ctx->pool[PACKED_OUT + i].ensure(bytes[i]))) return rc;
+        dev[i] = ctx->pool[PACKED_OUT + i].p;
+    }
+    const fcz_packed_out dd{(float*)dev[0], (uint8_t*)dev[1], (uint8_t*)dev[2], (float*)dev[3], (int32_t*)dev[4], (int32_t*)dev[5], (uint32_t*)dev[6]};
+    rc = fcz_dense_packed_dev(ctx, ctx->pool[REC_BLOB].as<uint8_t>(), ctx->pool[REC_OFF].as<uint64_t>(), n, ctx->pool[REC_RES_OFF].as<uint32_t>(),
+                              ctx->pool[REC_ATOM_OFF].as<uint32_t>(), &dv, 0, layout, &dd);
+    if (rc) return rc;
+    for (int i = 0; i < 7; i++)
+        if (bytes[i]) HIP_TRY(hipMemcpyAsync(host[i], dev[i], bytes[i], hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return FCZ_OK;
+}
+
 int fcz_decompress_dense(fcz_ctx* ctx, const uint8_t* blob, const uint64_t* off, uint32_t n, int layout, uint32_t L, uint32_t* L_out,
                          const fcz_dense_out* out, int32_t* status) {
     const int A = fcz_dense_width(layout);
@@ -1444,10 +1508,17 @@ static bool undense_args_ok(const fcz_ctx* ctx, const fcz_dense_in* in, uint32_t
     if (n == 0) return true;
     return in && in->pos && in->mask && in->aatype && in->length && (!in->titles == !in->title_off);
 }
+// the packed form: row_off in place of length and L
+static bool undense_packed_args_ok(const fcz_ctx* ctx, const fcz_dense_in* in, const uint32_t* row_off, uint32_t n, int layout, int anchor_threshold) {
+    if (!ctx || fcz_dense_width(layout) < 0 || anchor_threshold <= 0) return false;
+    if (n == 0) return true;
+    return in && in->pos && in->mask && in->aatype && row_off && (!in->titles == !in->title_off);
+}
 
-int fcz_undense_dev(fcz_ctx* ctx, const fcz_dense_in* in, uint32_t n, uint32_t L, int layout, int anchor_threshold,
-                    fcz_chain_batch* out, uint32_t counts[3], int32_t* chain_status_dev) {
-    if (!undense_args_ok(ctx, in, n, L, layout, anchor_threshold) || !out || !counts) return FCZ_E_INVALID_ARG;
+// fcz_undense_dev and fcz_undense_packed_dev: row_off == NULL is the padded form [n][L], otherwise chain c = rows row_off[c] ..
+// row_off[c + 1] of R (arguments checked by the caller)
+static int undense_rows(fcz_ctx* ctx, const fcz_dense_in* in, uint32_t n, uint32_t L, const uint32_t* row_off, uint32_t R_in, int layout,
+                        int anchor_threshold, fcz_chain_batch* out, uint32_t counts[3], int32_t* chain_status_dev) {
     HIP_TRY(hipSetDevice(ctx->device));
     memset(out, 0, sizeof *out);
     memset(&ctx->ud_batch, 0, sizeof ctx->ud_batch);
@@ -1455,26 +1526,37 @@ int fcz_undense_dev(fcz_ctx* ctx, const fcz_dense_in* in, uint32_t n, uint32_t L
     counts[0] = counts[1] = counts[2] = 0;
     out->anchor_threshold = ctx->ud_batch.anchor_threshold = anchor_threshold;
     if (n == 0) return FCZ_OK;
-    const size_t C = n, rows = C * (size_t)L;
-    // per chain: residues, atoms, status, flags (overflow of the two scans) | res_off, first atom of the chain
+    const size_t C = n, rows = row_off ? (size_t)R_in : C * (size_t)L;
+    // per chain: residues, atoms, status, flags (overflow of the scans) | res_off, first atom of the chain | packed: tiles, first tile
     const size_t ch_nres = 0, ch_natoms = 4 * C, ch_status = 8 * C, ch_flags = 12 * C, ch_resoff = ch_flags + 16, ch_aoff = ch_resoff + 4 * (C + 1);
+    const size_t ch_tiles = ch_aoff + 4 * (C + 1), ch_toff = ch_tiles + 4 * C;
     int rc;
-    if ((rc = ctx->ud[U_ROWS].ensure(2 * rows + 16)) || (rc = ctx->ud[U_CHAIN].ensure(ch_aoff + 4 * (C + 1)))) return rc;
+    if ((rc = ctx->ud[U_ROWS].ensure(2 * rows + 16)) || (rc = ctx->ud[U_CHAIN].ensure(ch_toff + 4 * (C + 1)))) return rc;
     char* bc = (char*)ctx->ud[U_CHAIN].p;
     uint16_t* row_word = ctx->ud[U_ROWS].as<uint16_t>();
     uint32_t* n_res = (uint32_t*)(bc + ch_nres); uint32_t* n_atoms = (uint32_t*)(bc + ch_natoms); int32_t* status = (int32_t*)(bc + ch_status);
     uint32_t* ovf = (uint32_t*)(bc + ch_flags); uint32_t* res_off = (uint32_t*)(bc + ch_resoff); uint32_t* chain_aoff = (uint32_t*)(bc + ch_aoff);
+    uint32_t* chain_tiles = (uint32_t*)(bc + ch_tiles); uint32_t* tile_off = (uint32_t*)(bc + ch_toff);
     const undense_table tab = undense_make_table(layout);
     const undense_in g{in->pos, in->mask, in->aatype, in->length, in->plddt};
+    const uint32_t tiles_per_chain = grid_for(L, DN_TILE);
+    const ud_padded padded{in->length, L, tiles_per_chain, (uint64_t)n * tiles_per_chain};   // every index into the dense arrays is 64-bit: n * L * A * 3 may pass 2^32
+    const ud_packed packed{row_off, R_in, n, tile_off};
     HIP_TRY(hipMemsetAsync(ovf, 0, 16, ctx->stream));
     {
         span_guard sg(ctx, "undense");
         const dim3 grid(std::min<uint32_t>(n, (uint32_t)ctx->n_cu * 16u));
         dispatch_layout(layout, [&](auto A) {
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_undense_count<decltype(A)::value>), grid, dim3(BLOCK), 0, ctx->stream, g, n, L, tab, row_word, n_res, n_atoms, status);
+            if (row_off)
+                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_undense_count<decltype(A)::value, ud_packed>), grid, dim3(BLOCK), 0, ctx->stream, g, n, packed, tab, row_word,
+                                   n_res, n_atoms, status, chain_tiles);
+            else
+                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_undense_count<decltype(A)::value, ud_padded>), grid, dim3(BLOCK), 0, ctx->stream, g, n, padded, tab, row_word,
+                                   n_res, n_atoms, status, (uint32_t*)nullptr);
         });
     }
     if ((rc = device_scan<uint32_t>(ctx, n_res, res_off, n, ovf)) || (rc = device_scan<uint32_t>(ctx, n_atoms, chain_aoff, n, ovf))) return rc;
+    if (row_off && (rc = device_scan<uint32_t>(ctx, chain_tiles, tile_off, n))) return rc;   // (at most residues / 64 + n tiles: no overflow the first scan does not see)
     HIP_TRY(hipGetLastError());
     auto& pin = ctx->pinned->undense;
     HIP_TRY(hipMemcpyAsync(&pin.residues, res_off + n, 4, hipMemcpyDeviceToHost, ctx->stream));
@@ -1499,12 +1581,16 @@ int fcz_undense_dev(fcz_ctx* ctx, const fcz_dense_in* in, uint32_t n, uint32_t L
                            in->first_atom_index ? nullptr : (int32_t*)(bm + oc_fa), in->chain_id ? nullptr : bm + oc_id);
     if (R) {
         span_guard sg(ctx, "undense");
-        const uint32_t tiles_per_chain = grid_for(L, DN_TILE);
-        const uint64_t n_tiles = (uint64_t)n * tiles_per_chain;  // every index into the dense arrays is 64-bit: n * L * A * 3 may pass 2^32
+        // (packed: the tiles are counted on the device only; at most one per 64 residues and one more per chain)
+        const uint64_t n_tiles = row_off ? (uint64_t)R / DN_TILE + n : padded.tiles;
         const dim3 grid((uint32_t)std::min<uint64_t>(n_tiles, (uint64_t)ctx->n_cu * 16u));
         dispatch_layout(layout, [&](auto A) {
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_undense_fill<decltype(A)::value>), grid, dim3(BLOCK), 0, ctx->stream, g, L, tiles_per_chain, n_tiles, tab,
-                               (const uint16_t*)row_word, (const uint32_t*)res_off, (const uint32_t*)chain_aoff, o);
+            if (row_off)
+                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_undense_fill<decltype(A)::value, ud_packed>), grid, dim3(BLOCK), 0, ctx->stream, g, packed, tab,
+                                   (const uint16_t*)row_word, (const uint32_t*)res_off, (const uint32_t*)chain_aoff, o);
+            else
+                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_undense_fill<decltype(A)::value, ud_padded>), grid, dim3(BLOCK), 0, ctx->stream, g, padded, tab,
+                                   (const uint16_t*)row_word, (const uint32_t*)res_off, (const uint32_t*)chain_aoff, o);
         });
     }
     HIP_TRY(hipGetLastError());
@@ -1520,6 +1606,18 @@ int fcz_undense_dev(fcz_ctx* ctx, const fcz_dense_in* in, uint32_t n, uint32_t L
     counts[0] = n; counts[1] = R; counts[2] = M;
     *out = b;
     return FCZ_OK;
+}
+
+int fcz_undense_dev(fcz_ctx* ctx, const fcz_dense_in* in, uint32_t n, uint32_t L, int layout, int anchor_threshold,
+                    fcz_chain_batch* out, uint32_t counts[3], int32_t* chain_status_dev) {
+    if (!undense_args_ok(ctx, in, n, L, layout, anchor_threshold) || !out || !counts) return FCZ_E_INVALID_ARG;
+    return undense_rows(ctx, in, n, L, nullptr, 0, layout, anchor_threshold, out, counts, chain_status_dev);
+}
+
+int fcz_undense_packed_dev(fcz_ctx* ctx, const fcz_dense_in* in, const uint32_t* row_off_dev, uint32_t n, uint32_t R, int layout,
+                           int anchor_threshold, fcz_chain_batch* out, uint32_t counts[3], int32_t* chain_status_dev) {
+    if (!undense_packed_args_ok(ctx, in, row_off_dev, n, layout, anchor_threshold) || !out || !counts) return FCZ_E_INVALID_ARG;
+    return undense_rows(ctx, in, n, 1, row_off_dev, R, layout, anchor_threshold, out, counts, chain_status_dev);
 }
 
 int fcz_undense_fetch(fcz_ctx* ctx, const fcz_chain_batch* hb, int32_t* chain_status) {
@@ -1540,18 +1638,30 @@ int fcz_undense_fetch(fcz_ctx* ctx, const fcz_chain_batch* hb, int32_t* chain_st
     return FCZ_OK;
 }
 
-int fcz_compress_dense_begin_dev(fcz_ctx* ctx, const fcz_dense_in* in, uint32_t n, uint32_t L, int layout, int anchor_threshold,
-                                 uint32_t counts[3], uint64_t* fcz_bytes) {
-    if (!fcz_bytes || !counts || !undense_args_ok(ctx, in, n, L, layout, anchor_threshold)) return FCZ_E_INVALID_ARG;
+// fcz_compress_dense_begin_dev and its packed form (row_off_dev != NULL), arguments checked by the caller
+static int compress_dense_rows(fcz_ctx* ctx, const fcz_dense_in* in, uint32_t n, uint32_t L, const uint32_t* row_off_dev, uint32_t R, int layout,
+                               int anchor_threshold, uint32_t counts[3], uint64_t* fcz_bytes) {
     *fcz_bytes = 0; ctx->ud_fcz_bytes = 0;
     fcz_chain_batch b;
-    int rc = fcz_undense_dev(ctx, in, n, L, layout, anchor_threshold, &b, counts, nullptr);
+    int rc = undense_rows(ctx, in, n, L, row_off_dev, R, layout, anchor_threshold, &b, counts, nullptr);
     if (rc || n == 0) return rc;
     claim_staging(ctx);
     if ((rc = compress_resident_batch(ctx, ctx->ud_batch, &ctx->ud_fcz_bytes, fcz_bytes))) return rc;
     hipLaunchKernelGGL(k_undense_merge_status, dim3(grid_for(n, BLOCK)), dim3(BLOCK), 0, ctx->stream, n, ctx->ud_status, ctx->pool[KEPT_STATUS].as<int32_t>());
     HIP_TRY(hipGetLastError());
     return FCZ_OK;
+}
+
+int fcz_compress_dense_begin_dev(fcz_ctx* ctx, const fcz_dense_in* in, uint32_t n, uint32_t L, int layout, int anchor_threshold,
+                                 uint32_t counts[3], uint64_t* fcz_bytes) {
+    if (!fcz_bytes || !counts || !undense_args_ok(ctx, in, n, L, layout, anchor_threshold)) return FCZ_E_INVALID_ARG;
+    return compress_dense_rows(ctx, in, n, L, nullptr, 0, layout, anchor_threshold, counts, fcz_bytes);
+}
+
+int fcz_compress_dense_packed_begin_dev(fcz_ctx* ctx, const fcz_dense_in* in, const uint32_t* row_off_dev, uint32_t n, uint32_t R, int layout,
+                                        int anchor_threshold, uint32_t counts[3], uint64_t* fcz_bytes) {
+    if (!fcz_bytes || !counts || !undense_packed_args_ok(ctx, in, row_off_dev, n, layout, anchor_threshold)) return FCZ_E_INVALID_ARG;
+    return compress_dense_rows(ctx, in, n, 1, row_off_dev, R, layout, anchor_threshold, counts, fcz_bytes);
 }
 
 static int compress_dense_fetch(fcz_ctx* ctx, uint64_t* out_off, int32_t* status, uint8_t* blob, hipMemcpyKind kind) {
@@ -1567,19 +1677,14 @@ int fcz_compress_dense_fetch_dev(fcz_ctx* ctx, uint64_t* out_off_dev, int32_t* s
     return compress_dense_fetch(ctx, out_off_dev, status_dev, blob_dev, hipMemcpyDeviceToDevice);
 }
 
-int fcz_compress_dense_begin(fcz_ctx* ctx, const fcz_dense_in* in, uint32_t n, uint32_t L, int layout, int anchor_threshold,
-                             uint32_t counts[3], uint64_t* fcz_bytes) {
-    if (!fcz_bytes || !counts || !undense_args_ok(ctx, in, n, L, layout, anchor_threshold)) return FCZ_E_INVALID_ARG;
-    *fcz_bytes = 0; ctx->ud_fcz_bytes = 0;
-    HIP_TRY(hipSetDevice(ctx->device));
-    if (n == 0) return fcz_compress_dense_begin_dev(ctx, in, 0, L, layout, anchor_threshold, counts, fcz_bytes);
-    claim_staging(ctx);
+// the host arrays of a fcz_dense_in of `rows` rows -> DENSE_IN 0 .. 9 (slot 3: length [n], or row_off [n + 1] of the packed form) -> *dv
+static int upload_dense_in(fcz_ctx* ctx, const fcz_dense_in* in, const uint32_t* row_off, uint32_t n, size_t rows, int layout, fcz_dense_in* dv) {
     int rc;
-    const size_t C = n, rows = C * (size_t)L, A = (size_t)fcz_dense_width(layout);
+    const size_t C = n, A = (size_t)fcz_dense_width(layout);
     const size_t title_bytes = in->title_off ? in->title_off[n] : 0;
-    const void* host[10] = {in->pos, in->mask, in->aatype, in->length, in->plddt, in->first_res_index, in->first_atom_index, in->chain_id,
-                            in->titles, in->title_off};
-    const size_t bytes[10] = {rows * A * 3 * sizeof(float), rows * A, rows, 4 * C, rows * sizeof(float), 4 * C, 4 * C, C, title_bytes, 4 * (C + 1)};
+    const void* host[10] = {in->pos, in->mask, in->aatype, row_off ? row_off : in->length, in->plddt, in->first_res_index, in->first_atom_index,
+                            in->chain_id, in->titles, in->title_off};
+    const size_t bytes[10] = {rows * A * 3 * sizeof(float), rows * A, rows, row_off ? 4 * (C + 1) : 4 * C, rows * sizeof(float), 4 * C, 4 * C, C, title_bytes, 4 * (C + 1)};
     const void* dev[10];
     for (int i = 0; i < 10; i++) {
         dev[i] = nullptr;
@@ -1588,9 +1693,35 @@ int fcz_compress_dense_begin(fcz_ctx* ctx, const fcz_dense_in* in, uint32_t n, u
         dev[i] = ctx->pool[DENSE_IN + i].p;
         if (bytes[i]) HIP_TRY(hipMemcpyAsync(ctx->pool[DENSE_IN + i].p, host[i], bytes[i], hipMemcpyHostToDevice, ctx->stream));
     }
-    const fcz_dense_in dv{(const float*)dev[0], (const uint8_t*)dev[1], (const uint8_t*)dev[2], (const uint32_t*)dev[3], (const float*)dev[4],
-                          (const int32_t*)dev[5], (const int32_t*)dev[6], (const char*)dev[7], (const char*)dev[8], (const uint32_t*)dev[9]};
+    *dv = {(const float*)dev[0], (const uint8_t*)dev[1], (const uint8_t*)dev[2], (const uint32_t*)dev[3], (const float*)dev[4],
+           (const int32_t*)dev[5], (const int32_t*)dev[6], (const char*)dev[7], (const char*)dev[8], (const uint32_t*)dev[9]};
+    return FCZ_OK;
+}
+
+int fcz_compress_dense_begin(fcz_ctx* ctx, const fcz_dense_in* in, uint32_t n, uint32_t L, int layout, int anchor_threshold,
+                             uint32_t counts[3], uint64_t* fcz_bytes) {
+    if (!fcz_bytes || !counts || !undense_args_ok(ctx, in, n, L, layout, anchor_threshold)) return FCZ_E_INVALID_ARG;
+    *fcz_bytes = 0; ctx->ud_fcz_bytes = 0;
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (n == 0) return fcz_compress_dense_begin_dev(ctx, in, 0, L, layout, anchor_threshold, counts, fcz_bytes);
+    claim_staging(ctx);
+    fcz_dense_in dv;
+    int rc = upload_dense_in(ctx, in, nullptr, n, (size_t)n * L, layout, &dv);
+    if (rc) return rc;
     return fcz_compress_dense_begin_dev(ctx, &dv, n, L, layout, anchor_threshold, counts, fcz_bytes);
+}
+
+int fcz_compress_dense_packed_begin(fcz_ctx* ctx, const fcz_dense_in* in, const uint32_t* row_off, uint32_t n, uint32_t R, int layout,
+                                    int anchor_threshold, uint32_t counts[3], uint64_t* fcz_bytes) {
+    if (!fcz_bytes || !counts || !undense_packed_args_ok(ctx, in, row_off, n, layout, anchor_threshold)) return FCZ_E_INVALID_ARG;
+    *fcz_bytes = 0; ctx->ud_fcz_bytes = 0;
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (n == 0) return fcz_compress_dense_packed_begin_dev(ctx, in, row_off, 0, R, layout, anchor_threshold, counts, fcz_bytes);
+    claim_staging(ctx);
+    fcz_dense_in dv;
+    int rc = upload_dense_in(ctx, in, row_off, n, R, layout, &dv);
+    if (rc) return rc;
+    return fcz_compress_dense_packed_begin_dev(ctx, &dv, dv.length, n, R, layout, anchor_threshold, counts, fcz_bytes);
 }
 
 int fcz_compress_dense_fetch(fcz_ctx* ctx, uint64_t* out_off, int32_t* status, uint8_t* blob) {

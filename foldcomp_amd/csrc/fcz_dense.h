@@ -171,4 +171,118 @@ __global__ __launch_bounds__(BLOCK) void k_dense(const uint8_t* __restrict__ blo
     }
 }
 
+// ---- packed form: rows of all entries back to back, no padding (include/fcz_hip.h, fcz_packed_out) ----------------------------
+//
+//   k_dense_packed<A>   persistent blocks over tiles of DN_TILE consecutive rows of the FLAT row space 0 .. R - 1, R = res_off[n]
+//                       read in the kernel (the entry point knows it only on the device). A tile may span any number of entries:
+//                       every row finds its entry by a binary search of res_off (entries without rows are passed over by it), and
+//                       its first atom restarts at atom_off[e] for every entry that begins inside the tile -- a chain's OXT lies
+//                       between its last residue's atoms and the next entry's first. The tile's atoms, OXTs included, are still
+//                       ONE contiguous range of x / y / z: staged once, up to DN_TILE chain ends wide. Every row keeps the clamp
+//                       against its own entry's atom range. length[e] has no tile of its own: a grid-stride loop over n writes it.
+
+constexpr uint32_t DN_PACKED_ATOMS = DN_MAX_ATOMS + DN_TILE;      // atoms a packed tile can hold: every row may end a chain
+
+// the entry of flat row r: the largest e in [lo, n) with res_off[e] <= r (res_off[lo] <= r < res_off[n])
+__device__ __forceinline__ uint32_t dn_entry_of(const uint32_t* __restrict__ res_off, uint32_t lo, uint32_t n, uint32_t r) {
+    uint32_t hi = n;
+    while (hi - lo > 1u) {
+        const uint32_t mid = lo + ((hi - lo) >> 1);
+        if (res_off[mid] <= r) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+template <int A>
+__global__ __launch_bounds__(BLOCK) void k_dense_packed(const uint8_t* __restrict__ blob, dense_args g, int32_t* __restrict__ chain_index,
+                                                        uint32_t n_entries, dense_table tab) {
+    __shared__ float s_xyz[3][DN_PACKED_ATOMS];
+    __shared__ uint32_t s_pk[DN_TILE];                 // tile-local first atom | atoms of the row's entry inside the staging << 10 | residue code << 20 | OXT << 25
+    __shared__ uint32_t s_part[WAVES_PER_BLOCK];       // per-wave sums of the atoms of the first entry in front of the tile
+    __shared__ uint32_t s_end[3];                      // end of the tile's atom range: value, "add the prefix" flag, clamp
+    __shared__ uint8_t s_inv[FCZ_N_RES_CODES * A];
+    __shared__ uint8_t s_na[FCZ_N_RES_CODES];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const uint32_t R = g.res_off[n_entries];
+    const uint32_t n_tiles = R / DN_TILE + (R % DN_TILE ? 1u : 0u);
+    if (g.length)
+        for (uint64_t e = (uint64_t)blockIdx.x * BLOCK + tid; e < n_entries; e += (uint64_t)gridDim.x * BLOCK) g.length[e] = g.res_off[e + 1] - g.res_off[e];
+    if (blockIdx.x >= n_tiles) return;
+    for (uint32_t i = tid; i < FCZ_N_RES_CODES * A; i += BLOCK) s_inv[i] = tab.inv[i];
+    if (tid < FCZ_N_RES_CODES) s_na[tid] = fcz_res_natoms[tid];
+    __syncthreads();
+    for (uint32_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+        const uint32_t t0 = tile * DN_TILE;
+        const uint32_t rows = R - t0 < DN_TILE ? R - t0 : DN_TILE;              // every row of a packed tile holds a residue
+        const uint32_t e0 = dn_entry_of(g.res_off, 0u, n_entries, t0);          // the entry of the tile's first row
+        float* pos = g.pos + (uint64_t)t0 * (uint64_t)(A * 3);
+        uint8_t* mask = g.mask + (uint64_t)t0 * (uint64_t)A;
+        // atoms of entry e0 in front of the tile (block sum); per row: its entry, its first atom (scan by wavefront 0, restarted
+        // at atom_off[e] where an entry begins inside the tile)
+        uint32_t part = 0;
+        for (uint32_t k = g.res_off[e0] + tid; k < t0; k += BLOCK) { const uint32_t rc = g.res_code[k]; part += s_na[rc < 24u ? rc : 23u]; }
+        part = wave_sum(part);
+        if (lane == 0) s_part[wave] = part;
+        uint32_t my_e = 0, my_l = 0, my_rc = 23, my_na = 0, my_first = 0, my_aend = 0;
+        bool my_last = false;
+        if (wave == 0) {
+            const bool act = lane < rows;
+            const uint32_t r = t0 + (act ? lane : 0u);
+            my_e = dn_entry_of(g.res_off, e0, n_entries, r);
+            const uint32_t rs = g.res_off[my_e];
+            my_l = r - rs;
+            my_last = act && r + 1u == g.res_off[my_e + 1];
+            if (act) { my_rc = g.res_code[r]; if (my_rc >= 24u) my_rc = 23u; my_na = s_na[my_rc]; }
+            uint32_t tot;
+            const uint32_t ex = wave_excl_scan(my_na, (int)lane, &tot);
+            const uint32_t ex_start = __shfl(ex, (int)(rs > t0 ? rs - t0 : 0u), WAVE);   // the scan at the entry's first row in the tile
+            my_aend = g.atom_off[my_e + 1];
+            my_first = g.atom_off[my_e] + (ex - ex_start);                     // (+ the prefix for the rows of e0, below)
+            if (lane == rows - 1u) { s_end[0] = my_last ? my_aend : my_first + my_na; s_end[1] = (my_e == e0 && !my_last) ? 1u : 0u; s_end[2] = my_aend; }
+        }
+        __syncthreads();
+        const uint32_t pre = s_part[0] + s_part[1] + s_part[2] + s_part[3];
+        const uint32_t g0 = g.atom_off[e0] + pre;                              // first atom of the tile's first row
+        uint32_t g1 = s_end[0] + (s_end[1] ? pre : 0u);                        // behind the last row's atoms (and its chain's OXT)
+        if (g1 > s_end[2]) g1 = s_end[2];                                      // (a read never leaves the last entry's atom range)
+        const uint32_t count = g1 > g0 ? (g1 - g0 < DN_PACKED_ATOMS ? g1 - g0 : DN_PACKED_ATOMS) : 0u;
+        for (uint32_t i = tid; i < count; i += BLOCK) { s_xyz[0][i] = g.x[g0 + i]; s_xyz[1][i] = g.y[g0 + i]; s_xyz[2][i] = g.z[g0 + i]; }
+        if (wave == 0) {
+            if (my_e == e0) my_first += pre;
+            uint32_t first = my_first - g0;                                    // (wraps for inconsistent offsets: clamped, selects nothing)
+            if (first > 1023u) first = 1023u;
+            uint32_t lim = my_aend > g0 ? my_aend - g0 : 0u;                   // the row's entry ends here: base + i < aend, per entry
+            if (lim > count) lim = count;
+            // the chain's OXT: the entry has one more atom than its residues own; slot 36 of its last row in atom37
+            const bool oxt = A == 37 && my_last && my_aend == my_first + my_na + 1u && first + my_na < count;
+            s_pk[lane] = lane < rows ? (first | (lim << 10) | (my_rc << 20) | (oxt ? 1u << 25 : 0u)) : 0u;
+        }
+        __syncthreads();
+        auto src = [&](uint32_t lr, uint32_t a) -> uint32_t {                   // LDS index of the atom in slot (lr, a), ~0u = none
+            const uint32_t pk = s_pk[lr], first = pk & 1023u, rc = (pk >> 20) & 31u;
+            if (A == 37 && a == 36u) return ((pk >> 25) & 1u) ? first + s_na[rc] : 0xFFFFFFFFu;
+            const uint32_t j = s_inv[rc * (uint32_t)A + a];
+            const uint32_t i = first + j;
+            return (j != 255u && i < ((pk >> 10) & 1023u)) ? i : 0xFFFFFFFFu;
+        };
+        dn_emit(pos, rows * (uint32_t)(A * 3), [&](uint32_t t) {
+            const uint32_t s = t / 3u, c = t - 3u * s, lr = s / (uint32_t)A, a = s - lr * (uint32_t)A;
+            const uint32_t i = src(lr, a);
+            return i != 0xFFFFFFFFu ? s_xyz[c][i] : 0.0f;
+        });
+        dn_emit(mask, rows * (uint32_t)A, [&](uint32_t s) {
+            const uint32_t lr = s / (uint32_t)A, a = s - lr * (uint32_t)A;
+            return (uint8_t)(src(lr, a) != 0xFFFFFFFFu ? 1 : 0);
+        });
+        if (tid < rows) {   // wavefront 0: lane = row
+            const uint64_t r = (uint64_t)t0 + tid;
+            if (g.aatype) g.aatype[r] = (uint8_t)(my_rc < 20u ? my_rc : 20u);
+            if (g.plddt) g.plddt[r] = g.bfac[r];
+            if (g.res_index) g.res_index[r] = (int32_t)(ld_u16(blob + g.off[my_e] + 8) + my_l);
+            if (chain_index) chain_index[r] = (int32_t)my_e;
+        }
+        __syncthreads();   // the next tile rewrites the staging
+    }
+}
+
 }  // namespace fcz

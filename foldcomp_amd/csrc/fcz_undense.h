@@ -19,6 +19,11 @@
 //                       so a wavefront's stores to x / y / z / atom_code cover one contiguous range.
 //
 // Nothing is read as data where mask == 0 or behind length[c]: such bytes are staged with their row at most, never selected.
+//
+// Where a chain's rows lie is the kernels' template parameter: ud_padded (chain c = rows c * L .. of [n][L], length[c] of them; tile t
+// = chain t / tiles_per_chain) or ud_packed (chain c = rows row_off[c] .. row_off[c + 1] of [R]; its tiles are tile_off[c] ..
+// tile_off[c + 1], the scan of the per-chain tile counts the counting pass leaves, searched by the fill pass). The row words are
+// indexed by the row of the input either way.
 #pragma once
 #include "fcz_dense.h"
 
@@ -33,6 +38,40 @@ struct undense_table { uint8_t slot[FCZ_N_RES_CODES * FCZ_MAX_RES_ATOMS]; };
 
 struct undense_in { const float* pos; const uint8_t* mask; const uint8_t* aatype; const uint32_t* length; const float* plddt; };
 struct undense_out { uint32_t* atom_off; float* x; float* y; float* z; uint8_t* atom_code; uint8_t* res_code; float* bfac_ca; };
+
+// the padded form [n][L]: rows of chain c, and the chain and first row of a tile of the fill pass
+struct ud_padded {
+    static constexpr bool packed = false;
+    const uint32_t* length; uint32_t L, tiles_per_chain; uint64_t tiles;
+    __device__ __forceinline__ uint64_t base(uint32_t c) const { return (uint64_t)c * L; }
+    __device__ __forceinline__ uint32_t len(uint32_t c, bool* refused) const {   // (nResidue is a uint16 in the record's header)
+        const uint32_t v = length[c];
+        *refused = v > L || v > 65535u;
+        return v;
+    }
+    __device__ __forceinline__ uint64_t n_tiles() const { return tiles; }
+    __device__ __forceinline__ void tile(uint64_t t, uint32_t* c, uint32_t* l0) const {
+        *c = (uint32_t)(t / tiles_per_chain);
+        *l0 = (uint32_t)(t - (uint64_t)*c * tiles_per_chain) * DN_TILE;
+    }
+};
+// the packed form [R]: chain c = rows row_off[c] .. row_off[c + 1]; refused when the range runs backwards, leaves the R rows the
+// caller has, or is longer than a record can say
+struct ud_packed {
+    static constexpr bool packed = true;
+    const uint32_t* row_off; uint32_t R, n; const uint32_t* tile_off;
+    __device__ __forceinline__ uint64_t base(uint32_t c) const { return row_off[c]; }
+    __device__ __forceinline__ uint32_t len(uint32_t c, bool* refused) const {
+        const uint32_t b = row_off[c], e = row_off[c + 1];
+        *refused = e < b || e > R || e - b > 65535u;
+        return *refused ? 0u : e - b;
+    }
+    __device__ __forceinline__ uint64_t n_tiles() const { return tile_off[n]; }
+    __device__ __forceinline__ void tile(uint64_t t, uint32_t* c, uint32_t* l0) const {
+        *c = dn_entry_of(tile_off, 0u, n, (uint32_t)t);                         // (chains without tiles are passed over)
+        *l0 = ((uint32_t)t - tile_off[*c]) * DN_TILE;
+    }
+};
 
 __device__ __forceinline__ uint32_t ud_res_code(uint32_t aatype) { return aatype < 20u ? aatype : (uint32_t)FCZ_RES_UNK; }
 
@@ -52,9 +91,10 @@ template <class T> __device__ __forceinline__ void ud_stage(const T* __restrict_
     if (threadIdx.x < count - tail0) img[tail0 + threadIdx.x] = p[tail0 + threadIdx.x];
 }
 
-template <int A>
-__global__ __launch_bounds__(BLOCK) void k_undense_count(undense_in g, uint32_t n, uint32_t L, undense_table tab, uint16_t* __restrict__ row_word,
-                                                         uint32_t* __restrict__ n_res, uint32_t* __restrict__ n_atoms, int32_t* __restrict__ status) {
+template <int A, class RA>
+__global__ __launch_bounds__(BLOCK) void k_undense_count(undense_in g, uint32_t n, RA ra, undense_table tab, uint16_t* __restrict__ row_word,
+                                                         uint32_t* __restrict__ n_res, uint32_t* __restrict__ n_atoms, int32_t* __restrict__ status,
+                                                         uint32_t* __restrict__ chain_tiles) {
     __shared__ __attribute__((aligned(16))) uint8_t s_mask[UD_COUNT_ROWS * A + 16];
     __shared__ uint8_t s_slot[FCZ_N_RES_CODES * FCZ_MAX_RES_ATOMS];
     __shared__ uint8_t s_na[FCZ_N_RES_CODES];
@@ -64,13 +104,14 @@ __global__ __launch_bounds__(BLOCK) void k_undense_count(undense_in g, uint32_t 
     if (tid < FCZ_N_RES_CODES) s_na[tid] = fcz_res_natoms[tid];
     __syncthreads();
     for (uint32_t c = blockIdx.x; c < n; c += gridDim.x) {
-        const uint32_t len_in = g.length[c];
-        const bool too_long = len_in > L || len_in > 65535u;      // (nResidue is a uint16 in the record's header)
+        bool too_long;
+        const uint32_t len_in = ra.len(c, &too_long);
         const uint32_t len = too_long ? 0u : len_in;
+        const uint64_t chain_row = ra.base(c);
         uint32_t cnt = 0, bad = 0;
         for (uint32_t l0 = 0; l0 < len; l0 += UD_COUNT_ROWS) {
             const uint32_t rows = len - l0 < UD_COUNT_ROWS ? len - l0 : UD_COUNT_ROWS;
-            const uint64_t row0 = (uint64_t)c * L + l0;
+            const uint64_t row0 = chain_row + l0;
             const uint8_t* mp = g.mask + row0 * (uint64_t)A;
             uint8_t* img = s_mask + ud_misalign(mp);
             const uint32_t aa = tid < rows ? (uint32_t)g.aatype[row0 + tid] : 0u;
@@ -87,9 +128,11 @@ __global__ __launch_bounds__(BLOCK) void k_undense_count(undense_in g, uint32_t 
                 }
                 // N, CA, C are the canonical positions 0, 1, 2 of every residue code
                 if (aa > 20u || (w & 7u) != 7u) bad = 1;
-                if (A == 37 && l0 + tid + 1u == len && m[36]) w |= UD_OXT_BIT;
-                row_word[row0 + tid] = (uint16_t)w;
-                cnt += __popc(w);
+                const uint32_t oxt = (A == 37 && l0 + tid + 1u == len && m[36]) ? UD_OXT_BIT : 0u;
+                // (packed: chains may share rows, and a row that ends one chain may lie inside another -- the OXT is counted here
+                // and found again by the fill pass from the chain's atom count, the row's word says nothing of it)
+                row_word[row0 + tid] = (uint16_t)(RA::packed ? w : w | oxt);
+                cnt += __popc(w | oxt);
             }
             __syncthreads();   // the next tile rewrites the staging
         }
@@ -100,13 +143,14 @@ __global__ __launch_bounds__(BLOCK) void k_undense_count(undense_in g, uint32_t 
             const uint32_t total = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
             const int st = too_long ? FCZ_E_INVALID_ARG : ((s_bad[0] | s_bad[1] | s_bad[2] | s_bad[3]) ? FCZ_E_RESIDUE : FCZ_OK);
             n_res[c] = st ? 0u : len; n_atoms[c] = st ? 0u : total; status[c] = st;
+            if constexpr (RA::packed) chain_tiles[c] = st ? 0u : (len + DN_TILE - 1u) / DN_TILE;
         }
         __syncthreads();
     }
 }
 
-template <int A>
-__global__ __launch_bounds__(BLOCK) void k_undense_fill(undense_in g, uint32_t L, uint32_t tiles_per_chain, uint64_t n_tiles, undense_table tab,
+template <int A, class RA>
+__global__ __launch_bounds__(BLOCK) void k_undense_fill(undense_in g, RA ra, undense_table tab,
                                                         const uint16_t* __restrict__ row_word, const uint32_t* __restrict__ res_off,
                                                         const uint32_t* __restrict__ chain_atom_off, undense_out o) {
     __shared__ __attribute__((aligned(16))) float s_pos[DN_TILE * A * 3 + 4];
@@ -120,13 +164,14 @@ __global__ __launch_bounds__(BLOCK) void k_undense_fill(undense_in g, uint32_t L
         s_code[i] = fcz_res_atom[i / FCZ_MAX_RES_ATOMS][i % FCZ_MAX_RES_ATOMS];
     }
     __syncthreads();
+    const uint64_t n_tiles = ra.n_tiles();
     for (uint64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-        const uint32_t c = (uint32_t)(tile / tiles_per_chain);
-        const uint32_t l0 = (uint32_t)(tile - (uint64_t)c * tiles_per_chain) * DN_TILE;
+        uint32_t c, l0;
+        ra.tile(tile, &c, &l0);
         const uint32_t r0 = res_off[c], ne = res_off[c + 1] - r0;               // ne <= L; 0 for a refused chain
         if (l0 >= ne) continue;                                                 // padding only: two offsets loaded, nothing else
         const uint32_t nv = ne - l0 < DN_TILE ? ne - l0 : DN_TILE;              // rows of the tile that hold a residue
-        const uint64_t chain_row = (uint64_t)c * L, row0 = chain_row + l0;
+        const uint64_t chain_row = ra.base(c), row0 = chain_row + l0;
         const float* pp = g.pos + row0 * (uint64_t)(A * 3);
         float* img = s_pos + ud_misalign(pp);
         ud_stage(pp, nv * (uint32_t)(A * 3), img);
@@ -156,7 +201,10 @@ __global__ __launch_bounds__(BLOCK) void k_undense_fill(undense_in g, uint32_t L
         }
         for (uint32_t it = tid; it < nv * UD_ITEMS; it += BLOCK) {
             const uint32_t lr = it / UD_ITEMS, j = it - lr * UD_ITEMS;
-            const uint32_t pk = s_pk[lr], w = pk & 0xFFFFu;
+            const uint32_t pk = s_pk[lr];
+            uint32_t w = pk & 0xFFFFu;
+            if constexpr (RA::packed)     // the chain's OXT: its last row, and the chain has one more atom than its rows' words own
+                if (A == 37 && l0 + lr + 1u == ne && base + s_first[lr] + (uint32_t)__popc(w) + 1u == aend) w |= UD_OXT_BIT;
             if (!((w >> j) & 1u)) continue;
             const uint32_t rc = pk >> 16;
             const bool oxt = j == (uint32_t)FCZ_MAX_RES_ATOMS;                    // set for atom37 only

@@ -968,6 +968,12 @@ class CDenseOut(ctypes.Structure):
                 ("plddt", ctypes.c_void_p), ("res_index", ctypes.c_void_p), ("length", ctypes.c_void_p)]
 
 
+class CPackedOut(ctypes.Structure):
+    """fcz_packed_out (include/fcz_hip.h): the packed dense arrays, rows of all entries back to back"""
+    _fields_ = [("pos", ctypes.c_void_p), ("mask", ctypes.c_void_p), ("aatype", ctypes.c_void_p), ("plddt", ctypes.c_void_p),
+                ("res_index", ctypes.c_void_p), ("chain_index", ctypes.c_void_p), ("length", ctypes.c_void_p)]
+
+
 class CDenseIn(ctypes.Structure):
     """fcz_dense_in (include/fcz_hip.h): dense tensors + per-chain header fields handed to the undense / compress_dense calls"""
     _fields_ = [("pos", ctypes.c_void_p), ("mask", ctypes.c_void_p), ("aatype", ctypes.c_void_p), ("length", ctypes.c_void_p),

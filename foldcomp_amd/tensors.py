@@ -1,8 +1,10 @@
-"""FCZ records <-> dense padded model-input tensors that never leave the GPU.
+"""FCZ records <-> dense padded or packed model-input tensors that never leave the GPU.
 
     decode_tensors(entries) -> dict(pos [n, L, A, 3] float32, mask [n, L, A] bool, aatype [n, L] uint8, plddt [n, L] float32,
                                     res_index [n, L] int32, length [n] int32, names list[str])
-    encode_tensors(that dict, or the tensors as keywords) -> [fcz, ...]
+    decode_tensors(entries, packed=True) -> dict(pos [R, A, 3], mask [R, A], aatype [R], plddt [R], res_index [R], chain_index [R],
+                                    cu_seqlens [n + 1] int32, length [n] int32, names, max_seqlen int): no padding, no crop
+    encode_tensors(either dict, or the tensors as keywords) -> [fcz, ...]
 
 What a structure model's data loader wants from a Foldcomp database (atom37 / atom14 coordinates with a mask, residue types,
 pLDDT), without the PDB text `foldcomp.decompress` returns and without a host copy of the result: the records go up once, torch
@@ -22,7 +24,7 @@ import numpy as np
 
 from . import _lib, api, fczfile
 from .codec import Codec, dense_layout
-from .structure import CAtomsOut, CDenseIn, CDenseOut
+from .structure import CAtomsOut, CDenseIn, CDenseOut, CPackedOut
 
 __all__ = ["decode_tensors", "encode_tensors"]
 
@@ -56,7 +58,7 @@ def _title(entry: bytes) -> str:
 
 
 def decode_tensors(entries: Sequence[bytes], *, layout="atom37", max_len: Optional[int] = None, device="cuda:0",
-                   codec: Optional[Codec] = None) -> dict:
+                   codec: Optional[Codec] = None, packed: bool = False) -> dict:
     """[fcz, ...] -> dict of torch tensors on `device` plus `names` (the records' titles, a Python list).
 
     layout: "atom37" (A = 37, AlphaFold / OpenFold atom order, the chain's OXT in slot 36 of its last residue), "atom14" (A = 14,
@@ -65,6 +67,11 @@ def decode_tensors(entries: Sequence[bytes], *, layout="atom37", max_len: Option
     0 .. 19 in the order A R N D C Q E G H I L K M F P S T W Y V, 20 for anything else and for padding; plddt and res_index are 0
     in the padding. An entry that does not decode has length 0, name "" when it has no readable header, and padding only.
     length is int32 (torch has no arithmetic on unsigned 32-bit integers).
+
+    packed=True: the rows of all entries back to back instead (fcz_dense_packed_dev): pos [R, A, 3], mask [R, A], aatype, plddt,
+    res_index, chain_index [R] (the entry number of the row), cu_seqlens [n + 1] int32 (row cu_seqlens[e] + l is residue l of entry
+    e), length [n], names and max_seqlen (a Python int). R counts the residues of the entries that decode: one that does not has no
+    row (length 0). Nothing is padded or cropped, so max_len with packed=True is a ValueError.
 
     Ordering against torch: the uploads and allocations are made on torch's current stream, which is synchronised before the
     codec's calls; the codec works on its own stream, which is synchronised before the tensors are returned. No output byte
@@ -76,11 +83,22 @@ def decode_tensors(entries: Sequence[bytes], *, layout="atom37", max_len: Option
         raise api.error(f"decode_tensors: the codec works on device {c.device}, the tensors were asked for on {dev}")
     lay = dense_layout(layout)
     A = c.lib.fcz_dense_width(lay)
+    if packed and max_len is not None:
+        raise ValueError("max_len crops to a common length; the packed form keeps every residue (packed=True takes no max_len)")
     if max_len is not None and int(max_len) < 1:
         raise ValueError("max_len must be at least 1")
     entries = [bytes(e) for e in entries]
     n = len(entries)
     names = [_title(e) for e in entries]
+
+    def packed_result(R, cu_seqlens, max_seqlen):
+        out = (torch.empty((R, A, 3), dtype=torch.float32, device=dev), torch.empty((R, A), dtype=torch.uint8, device=dev),
+               torch.empty(R, dtype=torch.uint8, device=dev), torch.empty(R, dtype=torch.float32, device=dev),
+               torch.empty(R, dtype=torch.int32, device=dev), torch.empty(R, dtype=torch.int32, device=dev),
+               torch.zeros(n, dtype=torch.int32, device=dev))
+        pos, mask, aatype, plddt, res_index, chain_index, length = out
+        return out, dict(pos=pos, mask=mask.view(torch.bool), aatype=aatype, plddt=plddt, res_index=res_index, chain_index=chain_index,
+                         cu_seqlens=cu_seqlens, length=length, names=names, max_seqlen=int(max_seqlen))
 
     def result(L, pos, mask, aatype, plddt, res_index, length):
         return dict(pos=pos, mask=mask.view(torch.bool), aatype=aatype, plddt=plddt, res_index=res_index, length=length, names=names)
@@ -91,6 +109,8 @@ def decode_tensors(entries: Sequence[bytes], *, layout="atom37", max_len: Option
                 torch.empty((n, L), dtype=torch.int32, device=dev), torch.zeros(n, dtype=torch.int32, device=dev))
 
     if n == 0:
+        if packed:
+            return packed_result(0, torch.zeros(1, dtype=torch.int32, device=dev), 0)[1]
         L = int(max_len or 0)
         return result(L, *alloc(L))
     off = np.zeros(n + 1, np.uint64)
@@ -104,6 +124,8 @@ def decode_tensors(entries: Sequence[bytes], *, layout="atom37", max_len: Option
     R, M = ctypes.c_uint32(0), ctypes.c_uint32(0)
     _lib.check(c.lib.fcz_decompress_sizes_dev(c.ctx, blob_t.data_ptr(), off_t.data_ptr(), n, res_off_t.data_ptr(), atom_off_t.data_ptr(),
                                               ctypes.byref(R), ctypes.byref(M)), "fcz_decompress_sizes_dev")
+    if packed:
+        return _decode_packed(c, torch, dev, lay, n, int(R.value), int(M.value), blob_t, off_t, res_off_t, atom_off_t, packed_result)
     if max_len is None:
         ro = res_off_t.cpu().numpy().view(np.uint32).astype(np.int64)      # n + 1 offsets: the only words that come back
         L = int(np.diff(ro).max())
@@ -127,6 +149,28 @@ def decode_tensors(entries: Sequence[bytes], *, layout="atom37", max_len: Option
     return result(L, *out)
 
 
+def _decode_packed(c, torch, dev, lay, n, R, M, blob_t, off_t, res_off_t, atom_off_t, packed_result):
+    """the packed leg of decode_tensors behind fcz_decompress_sizes_dev: R and M are its totals, res_off_t becomes cu_seqlens"""
+    if R > 2 ** 31 - 1:
+        raise api.error(f"decode_tensors: {R} residues do not fit the int32 cu_seqlens; split the batch")
+    ro = res_off_t.cpu().numpy().view(np.uint32).astype(np.int64)          # n + 1 offsets: the only words that come back
+    out, d = packed_result(R, res_off_t, int(np.diff(ro).max()))
+    if R == 0:                                                             # nothing decodes: no row, length stays 0
+        return d
+    x, y, z = (torch.empty(max(M, 1), dtype=torch.float32, device=dev) for _ in range(3))
+    bfac = torch.empty(R, dtype=torch.float32, device=dev)
+    res_code = torch.empty(R, dtype=torch.uint8, device=dev)
+    atoms = CAtomsOut(x.data_ptr(), y.data_ptr(), z.data_ptr(), bfac.data_ptr(), res_code.data_ptr(), None)
+    dense = CPackedOut(*(t.data_ptr() for t in out))
+    torch.cuda.current_stream(dev).synchronize()
+    _lib.check(c.lib.fcz_decompress_batch_dev(c.ctx, blob_t.data_ptr(), off_t.data_ptr(), n, res_off_t.data_ptr(), atom_off_t.data_ptr(),
+                                              0, ctypes.byref(atoms)), "fcz_decompress_batch_dev")
+    _lib.check(c.lib.fcz_dense_packed_dev(c.ctx, blob_t.data_ptr(), off_t.data_ptr(), n, res_off_t.data_ptr(), atom_off_t.data_ptr(),
+                                          ctypes.byref(atoms), 0, lay, ctypes.byref(dense)), "fcz_dense_packed_dev")
+    c.synchronize()
+    return d
+
+
 _WIDTH_LAYOUT = {37: "atom37", 14: "atom14", 4: "backbone4"}
 
 
@@ -138,6 +182,11 @@ def encode_tensors(batch=None, *, names=None, layout=None, anchor_residue_thresh
     res_index[:, 0] the first residue number), or the tensors come as keywords: pos [n, L, A, 3] float32, mask [n, L, A] bool or
     uint8, aatype [n, L] uint8, length [n] int32 / int64, and optionally plddt [n, L] float32 (default 0) and res_index [n, L] or
     first_res_index [n] (default 1). `names` given here wins over the dict's. layout: inferred from A (37 / 14 / 4) when None.
+
+    The packed form (decode_tensors(packed=True)) is recognised by a 3-D pos [R, A, 3] together with cu_seqlens [n + 1] int32 /
+    int64: mask [R, A], aatype [R], plddt [R], and res_index [R] (its value at every chain's first row is the first residue
+    number) or first_res_index [n]. Chain c is rows cu_seqlens[c] .. cu_seqlens[c + 1] - 1; `length` is not read. A chain whose
+    range runs backwards, leaves the R rows or holds more than 65 535 of them is refused like the others below.
 
     Of row l of chain c only l < length[c] counts, and of its atoms only those whose mask is set in a slot the residue type owns;
     everything else may hold anything. A chain the codec refuses (aatype > 20, a residue without N, CA and C, length above L,
@@ -151,7 +200,8 @@ def encode_tensors(batch=None, *, names=None, layout=None, anchor_residue_thresh
         raise TypeError("anchor_residue_threshold must be an integer")
     d = dict(batch) if batch is not None else {}
     d.update(tensors)
-    for k in ("pos", "mask", "aatype", "length"):
+    is_packed = d.get("cu_seqlens") is not None and getattr(d.get("pos"), "ndim", 4) == 3
+    for k in ("pos", "mask", "aatype", "cu_seqlens" if is_packed else "length"):
         if d.get(k) is None:
             raise TypeError(f"encode_tensors needs the tensor {k!r}")
     c = codec or api.default_codec()
@@ -166,9 +216,17 @@ def encode_tensors(batch=None, *, names=None, layout=None, anchor_residue_thresh
         raise api.error(f"encode_tensors: pos lies on {pos.device}, the codec works on cuda:{int(c.device)}; "
                         "the records are built where the tensors are and there is no CPU path")
     dev = pos.device
-    if pos.dim() != 4 or pos.shape[3] != 3 or pos.dtype != torch.float32:
+    if is_packed:
+        if pos.shape[2] != 3 or pos.dtype != torch.float32:
+            raise ValueError(f"pos must be float32 [R, A, 3] beside cu_seqlens, not {pos.dtype} {tuple(pos.shape)}")
+        cu = d["cu_seqlens"]
+        if not isinstance(cu, torch.Tensor) or cu.dim() != 1 or cu.shape[0] < 1:
+            raise ValueError("cu_seqlens must be a tensor [n + 1]")
+        n, L, A = int(cu.shape[0]) - 1, int(pos.shape[0]), int(pos.shape[1])          # (L: the rows of the packed arrays, R)
+    elif pos.dim() != 4 or pos.shape[3] != 3 or pos.dtype != torch.float32:
         raise ValueError(f"pos must be float32 [n, L, A, 3], not {pos.dtype} {tuple(pos.shape)}")
-    n, L, A = int(pos.shape[0]), int(pos.shape[1]), int(pos.shape[2])
+    else:
+        n, L, A = int(pos.shape[0]), int(pos.shape[1]), int(pos.shape[2])
     if layout is None:
         if A not in _WIDTH_LAYOUT:
             raise ValueError(f"no dense layout has {A} slots per residue (37, 14 or 4)")
@@ -190,24 +248,31 @@ def encode_tensors(batch=None, *, names=None, layout=None, anchor_residue_thresh
             raise ValueError(f"encode_tensors: {key} must be contiguous")
         return t
 
-    on_device("pos", pos, (n, L, A, 3), (torch.float32,))
-    mask = on_device("mask", d["mask"], (n, L, A), (torch.bool, torch.uint8))
-    aatype = on_device("aatype", d["aatype"], (n, L), (torch.uint8,))
-    length = on_device("length", d["length"], (n,), (torch.int32, torch.int64))
-    plddt = on_device("plddt", d["plddt"], (n, L), (torch.float32,)) if d.get("plddt") is not None else None
+    rows = (L,) if is_packed else (n, L)
+    on_device("pos", pos, rows + (A, 3), (torch.float32,))
+    mask = on_device("mask", d["mask"], rows + (A,), (torch.bool, torch.uint8))
+    aatype = on_device("aatype", d["aatype"], rows, (torch.uint8,))
+    length = on_device("cu_seqlens" if is_packed else "length", d["cu_seqlens" if is_packed else "length"], (n + 1,) if is_packed else (n,),
+                       (torch.int32, torch.int64))
+    plddt = on_device("plddt", d["plddt"], rows, (torch.float32,)) if d.get("plddt") is not None else None
     first = None
     if d.get("first_res_index") is not None:
         first = on_device("first_res_index", d["first_res_index"], (n,), (torch.int32, torch.int64)).to(torch.int32)
     elif d.get("res_index") is not None and L:
-        first = on_device("res_index", d["res_index"], (n, L), (torch.int32,))[:, 0].contiguous()
+        ri = on_device("res_index", d["res_index"], rows, (torch.int32,))
+        # (packed: a chain without rows may start at R; its record is refused or empty, any row serves)
+        first = ri[length[:-1].to(torch.int64).clamp(0, L - 1)].contiguous() if is_packed else ri[:, 0].contiguous()
     if n == 0:
         return []
     if L == 0:
         raise ValueError("encode_tensors: the tensors have no rows (L = 0)")
     if bool((length < 0).any()):
-        raise ValueError("length must not be negative")
-    keep = [mask.view(torch.uint8), length.to(torch.int32)]         # (int32 >= 0 and uint32 share their bits)
-    s = CDenseIn(pos.data_ptr(), keep[0].data_ptr(), aatype.data_ptr(), keep[1].data_ptr())
+        raise ValueError(("cu_seqlens" if is_packed else "length") + " must not be negative")
+    if is_packed and length.dtype == torch.int64 and bool((length > 2 ** 32 - 1).any()):
+        raise ValueError("cu_seqlens must fit 32 bits")
+    # (int32 >= 0 and uint32 share their bits; an int64 offset above 2^31 keeps its low word, which is its value)
+    keep = [mask.view(torch.uint8), length.to(torch.int32)]
+    s = CDenseIn(pos.data_ptr(), keep[0].data_ptr(), aatype.data_ptr(), None if is_packed else keep[1].data_ptr())
     if plddt is not None:
         s.plddt = plddt.data_ptr()
     if first is not None:
@@ -223,8 +288,12 @@ def encode_tensors(batch=None, *, names=None, layout=None, anchor_residue_thresh
     torch.cuda.current_stream(dev).synchronize()
     counts = np.zeros(3, np.uint32)
     nbytes = ctypes.c_uint64(0)
-    _lib.check(c.lib.fcz_compress_dense_begin_dev(c.ctx, ctypes.byref(s), n, L, lay, int(anchor_residue_threshold), counts.ctypes.data,
-                                                  ctypes.byref(nbytes)), "fcz_compress_dense_begin_dev")
+    if is_packed:
+        _lib.check(c.lib.fcz_compress_dense_packed_begin_dev(c.ctx, ctypes.byref(s), keep[1].data_ptr(), n, L, lay, int(anchor_residue_threshold),
+                                                             counts.ctypes.data, ctypes.byref(nbytes)), "fcz_compress_dense_packed_begin_dev")
+    else:
+        _lib.check(c.lib.fcz_compress_dense_begin_dev(c.ctx, ctypes.byref(s), n, L, lay, int(anchor_residue_threshold), counts.ctypes.data,
+                                                      ctypes.byref(nbytes)), "fcz_compress_dense_begin_dev")
     blob_t = torch.empty(max(int(nbytes.value), 1), dtype=torch.uint8, device=dev)
     off_t = torch.empty(n + 1, dtype=torch.int64, device=dev)
     st_t = torch.empty(n, dtype=torch.int32, device=dev)

@@ -15,8 +15,9 @@
  *   Foldcomp::decompress(vector<AtomCoordinate>&)          fcz_decompress_batch / fcz_decompress_batch_dev
  *     src/foldcomp.cpp:779
  *   Foldcomp::checkValidity()        src/foldcomp.cpp:1492   fcz_check
- *   (none: the reference stops at the flat atom vector)    fcz_dense_dev / fcz_decompress_dense
- *   (none: Foldcomp::compress starts from the flat list)   fcz_undense_dev / fcz_compress_dense_begin[_dev]
+ *   (none: the reference stops at the flat atom vector)    fcz_dense_dev / fcz_decompress_dense, fcz_dense_packed_dev / fcz_decompress_dense_packed
+ *   (none: Foldcomp::compress starts from the flat list)   fcz_undense_dev / fcz_compress_dense_begin[_dev], fcz_undense_packed_dev /
+ *                                                          fcz_compress_dense_packed_begin[_dev]
  *
  * Batch-first: one call handles C independent chains ("one wavefront per chain" on the device).
  * Data layout is structure-of-arrays; all offsets are element indices, not bytes, unless noted.
@@ -286,6 +287,42 @@ int fcz_dense_dev(fcz_ctx* ctx, const uint8_t* blob_dev, const uint64_t* off_dev
 int fcz_decompress_dense(fcz_ctx* ctx, const uint8_t* blob, const uint64_t* off, uint32_t n, int layout, uint32_t L,
                          uint32_t* L_out, const fcz_dense_out* out, int32_t* status);
 
+/* ---- packed dense tensors: rows of all entries back to back, no padding ------------------------------ */
+/* The same tensors for a batch of mixed lengths, as varlen models and token-budget loaders read them: no common L, no padding row
+ * and no crop. Like the padded form they stand beside Foldcomp::decompress (src/foldcomp.cpp:779); the reference has no such output.
+ * For n entries, R = res_off[n] (what fcz_decompress_sizes_dev leaves on the device and reports as *total_res) is the number of
+ * residues of the entries the decoder accepts; an entry it skips has ZERO rows. Row res_off[e] + l is residue l of entry e, so
+ * res_off itself is the cu_seqlens of the batch: no second copy is written.
+ *   pos [R][A][3] float32     mask [R][A] uint8     aatype [R] uint8     plddt [R] float32     res_index [R] int32
+ *   chain_index [R] int32     the entry number e of the row (segment reductions, block-diagonal attention masks)
+ *   length [n] uint32         residues of the entry, 0 for a skipped one
+ * aatype, plddt, res_index, chain_index, length may be NULL (not wanted). A slot's value follows the padded rules: the
+ * fcz_dense_slot table, the chain's OXT in slot 36 of its last row in atom37, pos 0.0f where mask is 0, aatype min(res_code, 20),
+ * res_index first_res_index + l. Every byte of rows 0 .. R - 1 of every requested array is written exactly once and nothing outside
+ * them; R == 0 writes length only. Every index is 64-bit (R * 111 floats passes 2^32 at 38.7 M residues). */
+typedef struct fcz_packed_out {
+    float*    pos;          /* [R][A][3] */
+    uint8_t*  mask;         /* [R][A] */
+    uint8_t*  aatype;       /* [R] optional */
+    float*    plddt;        /* [R] optional */
+    int32_t*  res_index;    /* [R] optional */
+    int32_t*  chain_index;  /* [R] optional */
+    uint32_t* length;       /* [n] optional */
+} fcz_packed_out;
+/* Device-resident, beside fcz_dense_dev and with its arguments but L: every pointer a device pointer, atoms_dev = what
+ * fcz_decompress_batch_dev filled for the same entries and offsets, the arrays of out_dev allocated for the R rows the sizes call
+ * reported. Enqueued on the ctx stream, no synchronisation: the kernel reads R from res_off_dev[n]. Unknown layout, NULL pos or
+ * mask (or any other required pointer): FCZ_E_INVALID_ARG, nothing launched; n == 0: FCZ_OK. */
+int fcz_dense_packed_dev(fcz_ctx* ctx, const uint8_t* blob_dev, const uint64_t* off_dev, uint32_t n,
+                         const uint32_t* res_off_dev, const uint32_t* atom_off_dev, const fcz_atoms_out* atoms_dev, int alt_order,
+                         int layout, const fcz_packed_out* out_dev);
+/* Host-pointer convenience, beside fcz_decompress_dense (Foldcomp::read + Foldcomp::decompress, src/foldcomp.cpp:904 / :779, for
+ * every entry): records in, packed host arrays out. *R_out (may be NULL when out is given) receives R and row_off[n + 1] (may be
+ * NULL) the row offsets, so a first call with out = NULL sizes the arrays. status[n] (may be NULL) receives the per-entry
+ * fcz_status. NULL ctx / blob / off, unknown layout, out and R_out both NULL, out with NULL pos or mask: FCZ_E_INVALID_ARG. */
+int fcz_decompress_dense_packed(fcz_ctx* ctx, const uint8_t* blob, const uint64_t* off, uint32_t n, int layout,
+                                uint32_t* R_out, uint32_t* row_off, const fcz_packed_out* out, int32_t* status);
+
 /* ---- dense model-input tensors -> fcz_chain_batch -> FCZ records ---------------------------------------- */
 /* The way back: n chains held as the padded arrays above (a model's predictions, a filtered or re-cropped set, what fcz_dense_dev
  * wrote) become the flat structure-of-arrays batch fcz_compress_sizes_dev / fcz_compress_batch_dev take, on the device. These entry
@@ -353,6 +390,20 @@ int fcz_compress_dense_fetch_dev(fcz_ctx* ctx, uint64_t* out_off_dev, int32_t* s
 int fcz_compress_dense_begin(fcz_ctx* ctx, const fcz_dense_in* in, uint32_t n, uint32_t L, int layout, int anchor_threshold,
                              uint32_t counts[3], uint64_t* fcz_bytes);
 int fcz_compress_dense_fetch(fcz_ctx* ctx, uint64_t* out_off, int32_t* status, uint8_t* blob);
+/* The packed form of the three calls above, in front of Foldcomp::compress (src/foldcomp.cpp:562) like them: chain c occupies rows
+ * row_off[c] .. row_off[c + 1] - 1 of pos [R][A][3], mask [R][A], aatype [R] and plddt [R] (in->length is not read and may be
+ * NULL); R is the number of rows the caller's arrays have. The fcz_dense_in contract holds unchanged (residue codes, missing
+ * atoms, the OXT in slot 36 of the chain's LAST row, never data, refusals, 32-bit totals), with these refusals per chain, each
+ * answered with FCZ_E_INVALID_ARG and zero residues, the neighbours untouched and nothing read outside rows 0 .. R - 1:
+ * row_off[c + 1] < row_off[c]; row_off[c + 1] > R; a length above 65535. Chains may share rows. fcz_undense_fetch and
+ * fcz_compress_dense_fetch[_dev] serve both forms. Bad arguments (NULL ctx, unknown layout, anchor_threshold <= 0, NULL pos / mask /
+ * aatype / row_off, titles without title_off or the reverse): FCZ_E_INVALID_ARG, nothing launched; n == 0: FCZ_OK. */
+int fcz_undense_packed_dev(fcz_ctx* ctx, const fcz_dense_in* in_dev, const uint32_t* row_off_dev, uint32_t n, uint32_t R, int layout,
+                           int anchor_threshold, fcz_chain_batch* out, uint32_t counts[3], int32_t* chain_status_dev);
+int fcz_compress_dense_packed_begin_dev(fcz_ctx* ctx, const fcz_dense_in* in_dev, const uint32_t* row_off_dev, uint32_t n, uint32_t R,
+                                        int layout, int anchor_threshold, uint32_t counts[3], uint64_t* fcz_bytes);
+int fcz_compress_dense_packed_begin(fcz_ctx* ctx, const fcz_dense_in* in, const uint32_t* row_off, uint32_t n, uint32_t R,
+                                    int layout, int anchor_threshold, uint32_t counts[3], uint64_t* fcz_bytes);
 
 /* ---- structure ingest: PDB / mmCIF text -> fcz_chain_batch on the device ----------------------------- */
 /* What the reference's driver does to every input file before Foldcomp::compress (src/main.cpp:455-508): StructureReader
@@ -500,7 +551,7 @@ int fcz_check(const uint8_t* entry, uint64_t len);
  * group since the last reset: "compress_sizes", "compress_index", "compress_angles", "compress_pack",
  * "decompress_sizes", "decompress_backbone", "decompress_index", "decompress_sidechain", "pdb_sizes", "pdb_format", "extract_sizes", "extract",
  * "ingest_parse", "ingest_parse_cif", "ingest_rows_cif", "ingest_frags", "ingest_fill", "inflate", "dense", "undense" (the counting and the fill
- * kernel of fcz_undense_dev: two launches per call). */
+ * kernel of fcz_undense_dev: two launches per call). The packed entry points are timed under the same two groups. */
 int  fcz_ctx_enable_timing(fcz_ctx* ctx, int enable);
 int  fcz_ctx_kernel_time(fcz_ctx* ctx, const char* name, double* ms, uint64_t* launches);
 void fcz_ctx_reset_timing(fcz_ctx* ctx);

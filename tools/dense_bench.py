@@ -9,7 +9,11 @@
      the route through PDB text (foldcomp.open iteration, a numpy column parse into atom37, one upload per batch), and the largest
      coordinate difference between the two.
 
+  4. the packed form (k_dense_packed) on the same two batches in the same process, right behind the padded call
+     of every layout: same method, same group "dense", bytes per second beside the same copy figure, and packed over padded time.
+
     python tools/dense_bench.py --out profiles/dense_layout.json [--lib other/libfcz_hip.so label]
+    python tools/dense_bench.py --skip-user-level --out profiles/dense_packed.json
 """
 import argparse
 import ctypes
@@ -33,7 +37,7 @@ LAYOUTS = (("atom37", 0, 37), ("atom14", 1, 14), ("backbone4", 2, 4))
 
 def kernel_case(codec, bench, name, n_chains, n_res, mixed, L_cap, dev):
     from foldcomp_amd import _lib
-    from foldcomp_amd.structure import CDenseOut
+    from foldcomp_amd.structure import CDenseOut, CPackedOut
     d = bench.generate_resident(n_chains, n_res, 25, 32768, dev, seed_base=0, mixed=mixed)
     w = bench.Workload(codec, d, dev)
     w.compress(); codec.synchronize()
@@ -73,6 +77,30 @@ def kernel_case(codec, bench, name, n_chains, n_res, mixed, L_cap, dev):
                                      gb_per_s=(written + read) / (med * 1e-3) / 1e9, padding_fraction=1.0 - kept / (n * L),
                                      share_of_decode_plus_dense=med / (med + decode_ms))
         del pos, mask, aatype, plddt, res_index, length
+        torch.cuda.empty_cache()
+        # the packed form of the same batch: R rows, nothing cropped
+        R = int(lens.sum())
+        pk = (torch.empty((R, A, 3), dtype=torch.float32, device=dev), torch.empty((R, A), dtype=torch.uint8, device=dev),
+              torch.empty(R, dtype=torch.uint8, device=dev), torch.empty(R, dtype=torch.float32, device=dev), torch.empty(R, dtype=torch.int32, device=dev),
+              torch.empty(R, dtype=torch.int32, device=dev), torch.empty(n, dtype=torch.int32, device=dev))
+        pout = CPackedOut(*(t.data_ptr() for t in pk))
+        torch.cuda.synchronize()
+        pms = []
+        for _ in range(3 + 9):
+            codec.reset_timing()
+            _lib.check(codec.lib.fcz_dense_packed_dev(codec.ctx, w.blob_dev.data_ptr(), w.off_dev.data_ptr(), n, w.res_off_dev.data_ptr(),
+                                                      w.atom_off_dev.data_ptr(), ctypes.byref(w.cout), 0, lay, ctypes.byref(pout)), "fcz_dense_packed_dev")
+            codec.synchronize()
+            pms.append(codec.kernel_time("dense")[0])
+        pmed = statistics.median(pms[3:])
+        p_atoms = int(pk[1].sum(dtype=torch.int64))
+        p_written = R * (A * 13 + 13) + 4 * n
+        p_read = 12 * p_atoms + 5 * R + 8 * n
+        padded = res["layouts"][lname]
+        padded["packed"] = dict(dense_ms=pmed, dense_ms_min=min(pms[3:]), dense_ms_max=max(pms[3:]), rows=R, bytes_written=p_written, bytes_read=p_read,
+                                gb_per_s=(p_written + p_read) / (pmed * 1e-3) / 1e9, time_over_padded=pmed / med,
+                                padded_spread=(max(ms[3:]) - min(ms[3:])) / med)
+        del pk
         torch.cuda.empty_cache()
     codec.enable_timing(False)
     del w
@@ -177,6 +205,7 @@ def main():
     for c in doc["kernel"]:
         for v in c["layouts"].values():
             v["fraction_of_copy_ceiling"] = v["gb_per_s"] / gbs.value
+            v["packed"]["fraction_of_copy_ceiling"] = v["packed"]["gb_per_s"] / gbs.value
     if not args.skip_user_level:
         doc["user_level"] = user_level(codec, bench, args.db_entries, dev)
     codec.close()

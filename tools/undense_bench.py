@@ -9,7 +9,11 @@
   3. entries per second of foldcomp.encode_tensors on batches of 1 024 chains of 350 residues beside the route that exists without
      it: tensors to the host, PDB text written in Python, foldcomp.compress_many.
 
+  4. the packed form (fcz_undense_packed_dev) on the same two batches in the same process, right behind the
+     padded call of every layout: the same group, the same method, packed over padded time. No chain is refused for its length there.
+
     python tools/undense_bench.py --out profiles/undense.json
+    python tools/undense_bench.py --skip-user-level --out profiles/undense_packed.json
 """
 import argparse
 import ctypes
@@ -43,6 +47,20 @@ def dense_tensors(codec, w, n, L, lay, A, dev):
     torch.cuda.synchronize()
     _lib.check(codec.lib.fcz_dense_dev(codec.ctx, w.blob_dev.data_ptr(), w.off_dev.data_ptr(), n, w.res_off_dev.data_ptr(),
                                        w.atom_off_dev.data_ptr(), ctypes.byref(w.cout), 0, lay, L, ctypes.byref(out)), "fcz_dense_dev")
+    codec.synchronize()
+    return t
+
+
+def packed_tensors(codec, w, n, R, lay, A, dev):
+    """the workload's records decoded into packed tensors of the layout (fcz_dense_packed_dev)"""
+    from foldcomp_amd import _lib
+    from foldcomp_amd.structure import CPackedOut
+    t = dict(pos=torch.empty((R, A, 3), dtype=torch.float32, device=dev), mask=torch.empty((R, A), dtype=torch.uint8, device=dev),
+             aatype=torch.empty(R, dtype=torch.uint8, device=dev), plddt=torch.empty(R, dtype=torch.float32, device=dev))
+    out = CPackedOut(t["pos"].data_ptr(), t["mask"].data_ptr(), t["aatype"].data_ptr(), t["plddt"].data_ptr(), None, None, None)
+    torch.cuda.synchronize()
+    _lib.check(codec.lib.fcz_dense_packed_dev(codec.ctx, w.blob_dev.data_ptr(), w.off_dev.data_ptr(), n, w.res_off_dev.data_ptr(),
+                                              w.atom_off_dev.data_ptr(), ctypes.byref(w.cout), 0, lay, ctypes.byref(out)), "fcz_dense_packed_dev")
     codec.synchronize()
     return t
 
@@ -86,6 +104,27 @@ def kernel_case(codec, bench, name, n_chains, n_res, mixed, L_cap, dev):
         res["layouts"][lname] = dict(undense_ms=med, undense_ms_min=min(ms[3:]), undense_ms_max=max(ms[3:]), residues=R, atoms=M, bytes_read=read,
                                      bytes_written=written, gb_per_s=(read + written) / (med * 1e-3) / 1e9, residues_per_s=R / (med * 1e-3),
                                      compress_kernels_ms=comp_ms, share_of_undense_plus_compress=med / (med + comp_ms), fcz_bytes=int(nbytes.value))
+        del t
+        torch.cuda.empty_cache()
+        # the packed form of the same batch: every chain, whatever its length; row_off is the decoder's res_off
+        Rp = int(lens.sum())
+        t = packed_tensors(codec, w, n, Rp, lay, A, dev)
+        s = CDenseIn(t["pos"].data_ptr(), t["mask"].data_ptr(), t["aatype"].data_ptr(), None, t["plddt"].data_ptr())
+        pms = []
+        for _ in range(3 + 9):
+            codec.reset_timing()
+            _lib.check(codec.lib.fcz_undense_packed_dev(codec.ctx, ctypes.byref(s), w.res_off_dev.data_ptr(), n, Rp, lay, 25, ctypes.byref(out),
+                                                        counts.ctypes.data, None), "fcz_undense_packed_dev")
+            codec.synchronize()
+            pms.append(codec.kernel_time("undense")[0])
+        pmed = statistics.median(pms[3:])
+        R2, M2 = int(counts[1]), int(counts[2])
+        p_read = R2 * (A * 13 + 2 + 4 + 4) + 8 * n
+        p_written = 13 * M2 + 9 * R2 + 2 * R2 + 16 * n
+        res["layouts"][lname]["packed"] = dict(undense_ms=pmed, undense_ms_min=min(pms[3:]), undense_ms_max=max(pms[3:]), residues=R2, atoms=M2,
+                                               bytes_read=p_read, bytes_written=p_written, gb_per_s=(p_read + p_written) / (pmed * 1e-3) / 1e9,
+                                               residues_per_s=R2 / (pmed * 1e-3), ms_per_residue_over_padded=(pmed / R2) / (med / R),
+                                               padded_spread=(max(ms[3:]) - min(ms[3:])) / med)
         del t
         torch.cuda.empty_cache()
     codec.enable_timing(False)
@@ -166,6 +205,7 @@ def main():
     for c in doc["kernel"]:
         for v in c["layouts"].values():
             v["fraction_of_copy_ceiling"] = v["gb_per_s"] / gbs.value
+            v["packed"]["fraction_of_copy_ceiling"] = v["packed"]["gb_per_s"] / gbs.value
     if not args.skip_user_level:
         doc["user_level"] = user_level(codec, bench, args.entries, args.text_entries, dev)
     codec.close()

@@ -5,7 +5,9 @@
 """
 from .api import (FoldcompDatabase, FoldcompError, compress, compress_many, decompress, decompress_many, error, get_data,
                   open, split_pdb_by_chain)
-from .tensors import decode_tensors, encode_tensors
+from .codec import ANGLE_COLUMNS
+from .tensors import decode_angles, decode_tensors, encode_tensors
 
 __all__ = ["compress", "decompress", "get_data", "open", "error", "FoldcompError", "FoldcompDatabase", "compress_many",
-           "decompress_many", "split_pdb_by_chain", "decode_tensors", "encode_tensors"]
+           "decompress_many", "split_pdb_by_chain", "decode_tensors", "encode_tensors", "decode_angles",
+           "ANGLE_COLUMNS"]

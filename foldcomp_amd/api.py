@@ -241,14 +241,16 @@ class FoldcompDatabase:
                 yield r
 
     def tensor_batches(self, batch_size: int = 1024, *, layout="atom37", max_len: Optional[int] = None, device="cuda:0",
-                       sort_by_length: bool = False, packed: bool = False, max_residues: Optional[int] = None):
+                       sort_by_length: bool = False, packed: bool = False, max_residues: Optional[int] = None,
+                       angles: bool = False):
         """Generator over the database (its `ids` selection when it has one) in batches of dense model-input tensors on the GPU:
         the dicts of foldcomp_amd.tensors.decode_tensors, each with `names` (the records' titles) and `index` (int64 array: the
         entries' positions in this database, what db[i] takes). sort_by_length orders every window of 16 * batch_size entries by
         residue count (from the record headers) before it is cut into batches, so that a batch pads little; `index` undoes it.
         packed=True yields the packed dicts (decode_tensors(packed=True): no padding, no crop, cu_seqlens), and max_residues then
         cuts the batches by a residue budget (cut_batches): a batch closes before the entry that would take it over the budget
-        or at batch_size entries; an entry longer than the budget forms a batch of its own."""
+        or at batch_size entries; an entry longer than the budget forms a batch of its own. angles=True adds `angles` and
+        `angle_mask` to every dict (decode_tensors(angles=True))."""
         from .tensors import decode_tensors
         batch_size = int(batch_size)
         if batch_size < 1:
@@ -264,9 +266,9 @@ class FoldcompDatabase:
             for sel in cut_batches(lens, batch_size, max_residues, sort_by_length):
                 sel = np.asarray(sel, np.int64)
                 if packed:
-                    d = decode_tensors([ents[k] for k in sel], layout=layout, device=device, packed=True)
+                    d = decode_tensors([ents[k] for k in sel], layout=layout, device=device, packed=True, angles=angles)
                 else:
-                    d = decode_tensors([ents[k] for k in sel], layout=layout, max_len=max_len, device=device)
+                    d = decode_tensors([ents[k] for k in sel], layout=layout, max_len=max_len, device=device, angles=angles)
                 d["index"] = idx[sel]
                 yield d
 

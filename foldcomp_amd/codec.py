@@ -18,6 +18,8 @@ from . import _lib
 from .structure import CAtomsOut, CChainBatch, CDenseIn, CDenseOut, CEntryInfo, ChainBatch, CPackedOut, batch_as_c
 
 
+# the columns of the angle tensors (FCZ_ANGLE_COLUMNS, include/fcz_hip.h), degrees
+ANGLE_COLUMNS = ("phi", "psi", "omega", "n_ca_c", "ca_c_n", "c_n_ca", "chi1", "chi2", "chi3", "chi4")
 DENSE_LAYOUTS = {"atom37": 0, "atom14": 1, "backbone4": 2}     # enum fcz_dense_layout
 
 
@@ -168,6 +170,44 @@ class Codec:
             _lib.check(self.lib.fcz_decompress_dense(self.ctx, blob.ctypes.data, off.ctypes.data, n, lay, Lv, None, ctypes.byref(out),
                                                      status.ctypes.data), "fcz_decompress_dense")
         d["mask"] = d["mask"].view(np.bool_)
+        d["status"] = status[:n]
+        return d
+
+    def decompress_angles(self, blob: np.ndarray, off: np.ndarray, L: int = 0, packed: bool = False):
+        """FCZ entries -> the record's internal coordinates on the host (fcz_decompress_angles): angles float32 [n, L, 10] in degrees
+        (ANGLE_COLUMNS), angle_mask bool [n, L, 10], status int32 [n]; L = 0: the longest entry of the batch, longer entries are
+        cropped. packed=True (fcz_decompress_angles_packed): angles [R, 10], angle_mask [R, 10], row_off uint32 [n + 1]; no L.
+        The sizes pass and the angle kernel only: nothing is reconstructed."""
+        blob = np.ascontiguousarray(blob, np.uint8)
+        off = np.ascontiguousarray(off, np.uint64)
+        n = len(off) - 1
+        if packed and L:
+            raise ValueError("L crops to a common length; the packed form keeps every residue (packed=True takes no L)")
+        if int(L) < 0:
+            raise ValueError("L must not be negative")
+        W = len(ANGLE_COLUMNS)
+        width = ctypes.c_uint32(int(L))
+        status = np.zeros(max(n, 1), np.int32)
+        row_off = np.zeros(n + 1, np.uint32)
+
+        def call(angles, mask, st):
+            if packed:
+                _lib.check(self.lib.fcz_decompress_angles_packed(self.ctx, blob.ctypes.data, off.ctypes.data, n, ctypes.byref(width), row_off.ctypes.data,
+                                                                 angles, mask, st), "fcz_decompress_angles_packed")
+            else:
+                _lib.check(self.lib.fcz_decompress_angles(self.ctx, blob.ctypes.data, off.ctypes.data, n, int(L), ctypes.byref(width), angles, mask, st),
+                           "fcz_decompress_angles")
+
+        if n:
+            call(None, None, status.ctypes.data)
+        Wd = int(width.value)
+        shape = (Wd, W) if packed else (n, Wd, W)
+        d = dict(angles=np.zeros(shape, np.float32), angle_mask=np.zeros(shape, np.uint8))
+        if n and Wd:
+            call(d["angles"].ctypes.data, d["angle_mask"].ctypes.data, None)
+        d["angle_mask"] = d["angle_mask"].view(np.bool_)
+        if packed:
+            d["row_off"] = row_off
         d["status"] = status[:n]
         return d
 

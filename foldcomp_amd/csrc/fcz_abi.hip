@@ -32,6 +32,7 @@
 #include "fcz_inflate.h"
 #include "fcz_dense.h"
 #include "fcz_undense.h"
+#include "fcz_angles.h"
 
 // second, host-side instance of the generated tables (integer metadata for sizes/validation)
 namespace host_tab {
@@ -40,6 +41,7 @@ namespace host_tab {
 #define FCZ_TABLE_QUAL static const
 #define FCZ_T(name) h_##name
 #include "aa_tables.inc"
+#include "aa_tables_chi.inc"
 }  // namespace host_tab
 
 using namespace fcz;
@@ -80,11 +82,11 @@ struct timed_span { std::string name; hipEvent_t a, b; };
 // never live together (table in fcz_ctx). REC_*: uploaded FCZ records (n + 1 u64 offsets), their res_off / atom_off (n + 1 u32) and
 // the fcz_atoms_out decoded from them; FILES_*: structure files of an ingest call; BATCH_IN / DENSE_IN / DENSE_OUT: first of the 13
 // arrays of a fcz_chain_batch, the 10 of a fcz_dense_in (slot 3, length, holds row_off [n + 1] in the packed form), the 6 of a
-// fcz_dense_out, the 7 of a fcz_packed_out (PACKED_OUT .. PACKED_OUT_LAST), in the struct's order; KEPT_*: the records a *_begin
+// fcz_dense_out, the 7 of a fcz_packed_out (PACKED_OUT .. PACKED_OUT_LAST), in the struct's order; ANGLES_OUT: the angles and their mask; KEPT_*: the records a *_begin
 // call leaves for its fetch (C + 1 u64 offsets, the bytes, C i32 status)
 enum { REC_BLOB, REC_OFF, REC_RES_OFF, REC_ATOM_OFF, REC_X, REC_Y, REC_Z, REC_BFAC, REC_RES_CODE, REC_ATOM_CODE,
        FILES_TEXT = 0, FILES_OFF, FILES_NAMES, FILES_NAME_OFF, FILES_STEM_LEN, BATCH_IN = 0, DENSE_IN = 0, DENSE_OUT = 10,
-       PACKED_OUT = 10, KEPT_OFF = 13, KEPT_BYTES, KEPT_STATUS, PACKED_OUT_LAST, POOL_COUNT };
+       PACKED_OUT = 10, ANGLES_OUT = 10, KEPT_OFF = 13, KEPT_BYTES, KEPT_STATUS, PACKED_OUT_LAST, POOL_COUNT };
 
 // what the device reports to the host in the middle of a call: one pinned allocation, a member per reader
 struct pinned_words {
@@ -142,6 +144,7 @@ struct fcz_ctx {
     //   fcz_extract                                 REC_BLOB, REC_OFF
     //   fcz_decompress_dense                        REC_* 0 .. 8, DENSE_OUT 10 .. 15
     //   fcz_decompress_dense_packed                 REC_* 0 .. 8, PACKED_OUT 10 .. 16
+    //   fcz_decompress_angles[_packed]              REC_* 0 .. 3, ANGLES_OUT 10 .. 11
     //   fcz_compress_batch                          BATCH_IN 0 .. 12, KEPT_* 13 .. 15
     //   fcz_inflate                                 FILES_TEXT
     //   fcz_ingest_pdb_begin / fcz_ingest_gz_begin  FILES_* 0 .. 4 (gz: no FILES_OFF, gz_toff)      (ig[], ig_res, ig_counts)
@@ -1485,6 +1488,82 @@ int fcz_decompress_dense(fcz_ctx* ctx, const uint8_t* blob, const uint64_t* off,
         if (bytes[i]) HIP_TRY(hipMemcpyAsync(host[i], dev[i], bytes[i], hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return FCZ_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// torsion-angle tensors straight from the record bytes (fcz_angles.h; the dequantisation of Foldcomp::decompress, src/foldcomp.cpp:784-804)
+// ------------------------------------------------------------------------------------------------
+int fcz_chi_atom(int rc, int k) {
+    if (rc < 0 || rc >= FCZ_N_RES_CODES || k < 0 || k >= 4) return -1;
+    const int slot = host_tab::h_res_chi_slot[rc][k];
+    return slot ? host_tab::h_res_atom[rc][slot] : -1;
+}
+
+int fcz_angles_dev(fcz_ctx* ctx, const uint8_t* blob_dev, const uint64_t* off_dev, uint32_t n, const uint32_t* res_off_dev, uint32_t L,
+                   float* angles_dev, uint8_t* mask_dev) {
+    if (!ctx || !blob_dev || !off_dev || !res_off_dev || !angles_dev || !mask_dev || L == 0) return FCZ_E_INVALID_ARG;
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (n == 0) return FCZ_OK;
+    // one wavefront per entry on a persistent grid
+    const uint32_t blocks = std::min<uint32_t>(grid_for(n, WAVES_PER_BLOCK), (uint32_t)ctx->n_cu * 32u);
+    span_guard sg(ctx, "angles");
+    hipLaunchKernelGGL(k_angles, dim3(blocks), dim3(BLOCK), 0, ctx->stream, blob_dev, off_dev, res_off_dev, n, L, angles_dev, mask_dev);
+    HIP_TRY(hipGetLastError());
+    return FCZ_OK;
+}
+
+int fcz_angles_packed_dev(fcz_ctx* ctx, const uint8_t* blob_dev, const uint64_t* off_dev, uint32_t n, const uint32_t* res_off_dev,
+                          float* angles_dev, uint8_t* mask_dev) {
+    if (!ctx || !blob_dev || !off_dev || !res_off_dev || !angles_dev || !mask_dev) return FCZ_E_INVALID_ARG;
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (n == 0) return FCZ_OK;
+    const uint32_t blocks = std::min<uint32_t>(grid_for(n, WAVES_PER_BLOCK), (uint32_t)ctx->n_cu * 32u);
+    span_guard sg(ctx, "angles");
+    hipLaunchKernelGGL(k_angles_packed, dim3(blocks), dim3(BLOCK), 0, ctx->stream, blob_dev, off_dev, res_off_dev, n, angles_dev, mask_dev);
+    HIP_TRY(hipGetLastError());
+    return FCZ_OK;
+}
+
+// the two host-pointer forms; width_out is L_out (padded) or R_out (packed)
+static int decompress_angles_impl(fcz_ctx* ctx, const uint8_t* blob, const uint64_t* off, uint32_t n, bool packed, uint32_t L, uint32_t* width_out,
+                                  uint32_t* row_off, float* angles, uint8_t* mask, int32_t* status) {
+    if (!ctx || !blob || !off || (!angles != !mask) || (!angles && !width_out)) return FCZ_E_INVALID_ARG;
+    HIP_TRY(hipSetDevice(ctx->device));
+    claim_staging(ctx);
+    if (width_out) *width_out = packed ? 0u : L;
+    if (n == 0) { if (row_off) row_off[0] = 0; return FCZ_OK; }
+    uint32_t R = 0, M = 0;
+    int rc = upload_records(ctx, blob, off, n, &R, &M); if (rc) return rc;
+    std::vector<uint32_t> res_off((size_t)n + 1);
+    HIP_TRY(hipMemcpyAsync(res_off.data(), ctx->pool[REC_RES_OFF].p, sizeof(uint32_t) * ((size_t)n + 1), hipMemcpyDeviceToHost, ctx->stream));
+    if (status) HIP_TRY(hipMemcpyAsync(status, cnt_status(ctx, n), sizeof(int32_t) * n, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    if (row_off) memcpy(row_off, res_off.data(), sizeof(uint32_t) * ((size_t)n + 1));
+    if (!packed && L == 0)
+        for (uint32_t i = 0; i < n; i++) L = std::max(L, res_off[i + 1] - res_off[i]);
+    if (width_out) *width_out = packed ? R : L;
+    const size_t rows = packed ? (size_t)R : (size_t)n * L;
+    if (!angles || rows == 0) return FCZ_OK;                      // a sizing call, or no row to fill
+    const size_t elems = rows * FCZ_ANGLE_COLUMNS;
+    if ((rc = ctx->pool[ANGLES_OUT].ensure(elems * sizeof(float))) || (rc = ctx->pool[ANGLES_OUT + 1].ensure(elems))) return rc;
+    const uint8_t* b = ctx->pool[REC_BLOB].as<uint8_t>(); const uint64_t* o = ctx->pool[REC_OFF].as<uint64_t>(); const uint32_t* ro = ctx->pool[REC_RES_OFF].as<uint32_t>();
+    rc = packed ? fcz_angles_packed_dev(ctx, b, o, n, ro, ctx->pool[ANGLES_OUT].as<float>(), ctx->pool[ANGLES_OUT + 1].as<uint8_t>())
+                : fcz_angles_dev(ctx, b, o, n, ro, L, ctx->pool[ANGLES_OUT].as<float>(), ctx->pool[ANGLES_OUT + 1].as<uint8_t>());
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(angles, ctx->pool[ANGLES_OUT].p, elems * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(mask, ctx->pool[ANGLES_OUT + 1].p, elems, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return FCZ_OK;
+}
+
+int fcz_decompress_angles(fcz_ctx* ctx, const uint8_t* blob, const uint64_t* off, uint32_t n, uint32_t L, uint32_t* L_out, float* angles,
+                          uint8_t* mask, int32_t* status) {
+    return decompress_angles_impl(ctx, blob, off, n, false, L, L_out, nullptr, angles, mask, status);
+}
+
+int fcz_decompress_angles_packed(fcz_ctx* ctx, const uint8_t* blob, const uint64_t* off, uint32_t n, uint32_t* R_out, uint32_t* row_off,
+                                 float* angles, uint8_t* mask, int32_t* status) {
+    return decompress_angles_impl(ctx, blob, off, n, true, 0u, R_out, row_off, angles, mask, status);
 }
 
 // ------------------------------------------------------------------------------------------------

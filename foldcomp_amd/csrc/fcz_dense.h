@@ -54,14 +54,15 @@ template <class V, class T> __device__ __forceinline__ void dn_store(T* p, V v) 
 }
 
 // `count` elements of T at p, element t = val(t): 16-byte stores over the aligned middle of the range, single elements in
-// front of it and behind it. Lane = 16 consecutive bytes, consecutive lanes = consecutive addresses.
-template <class T, class F> __device__ __forceinline__ void dn_emit(T* p, uint32_t count, F val) {
+// front of it and behind it. Lane = 16 consecutive bytes, consecutive lanes = consecutive addresses. The work is shared by `stride`
+// threads, this one being number idx of them: a block (the default) or one wavefront (idx = lane, stride = WAVE).
+template <class T, class F> __device__ __forceinline__ void dn_emit(T* p, uint32_t count, F val, const uint32_t idx = threadIdx.x, const uint32_t stride = BLOCK) {
     constexpr uint32_t PER = 16 / sizeof(T);
     const uint32_t mis = (uint32_t)((uintptr_t)p & 15u) / (uint32_t)sizeof(T);
     uint32_t head = (PER - mis) % PER;
     if (head > count) head = count;
     const uint32_t body = (count - head) / PER, tail0 = head + body * PER;
-    for (uint32_t q = threadIdx.x; q < body; q += BLOCK) {
+    for (uint32_t q = idx; q < body; q += stride) {
         const uint32_t t = head + q * PER;
         if constexpr (sizeof(T) == 4) {
             dn_f4 v;
@@ -76,8 +77,8 @@ template <class T, class F> __device__ __forceinline__ void dn_emit(T* p, uint32
             dn_store(p + t, v);
         }
     }
-    if (threadIdx.x < head) p[threadIdx.x] = val(threadIdx.x);
-    if (threadIdx.x < count - tail0) p[tail0 + threadIdx.x] = val(tail0 + threadIdx.x);
+    if (idx < head) p[idx] = val(idx);
+    if (idx < count - tail0) p[tail0 + idx] = val(tail0 + idx);
 }
 
 template <int A>

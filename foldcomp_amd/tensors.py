@@ -5,6 +5,8 @@
     decode_tensors(entries, packed=True) -> dict(pos [R, A, 3], mask [R, A], aatype [R], plddt [R], res_index [R], chain_index [R],
                                     cu_seqlens [n + 1] int32, length [n] int32, names, max_seqlen int): no padding, no crop
     encode_tensors(either dict, or the tensors as keywords) -> [fcz, ...]
+    decode_angles(entries) -> dict(angles [n, L, 10] float32 degrees, angle_mask [n, L, 10] bool, aatype [n, L] uint8, length [n] int32,
+                                   names list[str]); packed=True: angles [R, 10], angle_mask [R, 10], aatype [R], cu_seqlens, max_seqlen
 
 What a structure model's data loader wants from a Foldcomp database (atom37 / atom14 coordinates with a mask, residue types,
 pLDDT), without the PDB text `foldcomp.decompress` returns and without a host copy of the result: the records go up once, torch
@@ -23,10 +25,11 @@ from typing import Optional, Sequence
 import numpy as np
 
 from . import _lib, api, fczfile
-from .codec import Codec, dense_layout
+from ._aa_tables import RES1
+from .codec import ANGLE_COLUMNS, Codec, dense_layout
 from .structure import CAtomsOut, CDenseIn, CDenseOut, CPackedOut
 
-__all__ = ["decode_tensors", "encode_tensors"]
+__all__ = ["decode_tensors", "encode_tensors", "decode_angles"]
 
 
 def _torch_device(device):
@@ -57,8 +60,115 @@ def _title(entry: bytes) -> str:
         return ""
 
 
+def _upload_and_size(c, torch, dev, entries):
+    """records -> (blob, off, res_off, atom_off) tensors on dev with fcz_decompress_sizes_dev run over them, and its totals R, M"""
+    n = len(entries)
+    off = np.zeros(n + 1, np.uint64)
+    off[1:] = np.cumsum([len(e) for e in entries])
+    # (16 spare bytes behind the last record: the decoder's dword loads of a record's last bytes stay inside the allocation)
+    blob_t = torch.from_numpy(np.frombuffer(b"".join(entries) + bytes(16), np.uint8).copy()).to(dev)
+    off_t = torch.from_numpy(off.view(np.int64)).to(dev)
+    res_off_t = torch.empty(n + 1, dtype=torch.int32, device=dev)
+    atom_off_t = torch.empty(n + 1, dtype=torch.int32, device=dev)
+    torch.cuda.current_stream(dev).synchronize()
+    R, M = ctypes.c_uint32(0), ctypes.c_uint32(0)
+    _lib.check(c.lib.fcz_decompress_sizes_dev(c.ctx, blob_t.data_ptr(), off_t.data_ptr(), n, res_off_t.data_ptr(), atom_off_t.data_ptr(),
+                                              ctypes.byref(R), ctypes.byref(M)), "fcz_decompress_sizes_dev")
+    return blob_t, off_t, res_off_t, atom_off_t, int(R.value), int(M.value)
+
+
+def _angles_into(c, torch, dev, n, blob_t, off_t, res_off_t, L, R=None):
+    """the angle tensors of a sized batch (fcz_angles_dev, or fcz_angles_packed_dev when R is given), enqueued on the codec's stream:
+    the caller synchronises. It reads the records and res_off only, and leaves the sizes memo to the decode that may follow."""
+    shape = (R, len(ANGLE_COLUMNS)) if R is not None else (n, L, len(ANGLE_COLUMNS))
+    ang = torch.empty(shape, dtype=torch.float32, device=dev)
+    msk = torch.empty(shape, dtype=torch.uint8, device=dev)
+    if ang.numel():
+        torch.cuda.current_stream(dev).synchronize()
+        if R is not None:
+            _lib.check(c.lib.fcz_angles_packed_dev(c.ctx, blob_t.data_ptr(), off_t.data_ptr(), n, res_off_t.data_ptr(), ang.data_ptr(), msk.data_ptr()),
+                       "fcz_angles_packed_dev")
+        else:
+            _lib.check(c.lib.fcz_angles_dev(c.ctx, blob_t.data_ptr(), off_t.data_ptr(), n, res_off_t.data_ptr(), L, ang.data_ptr(), msk.data_ptr()),
+                       "fcz_angles_dev")
+    return dict(angles=ang, angle_mask=msk.view(torch.bool))
+
+
+def _aatype_rows(entry: bytes, n_res: int) -> np.ndarray:
+    """aatype of the first n_res residues of a record that decodes, from its bytes: min(residue code, 20) with the decoder's codes
+    (residue 0: header.firstResidue)"""
+    rec = fczfile.parse(entry)
+    rc = rec.res_codes[:n_res].astype(np.uint8)
+    if n_res:
+        rc[0] = RES1.index(rec.first_residue) if rec.first_residue in RES1 else 23
+    return np.minimum(rc, 20).astype(np.uint8)
+
+
+def decode_angles(entries: Sequence[bytes], *, max_len: Optional[int] = None, packed: bool = False, device="cuda:0",
+                  codec: Optional[Codec] = None) -> dict:
+    """[fcz, ...] -> the records' internal coordinates as torch tensors on `device`, without reconstructing an atom: the sizes pass
+    and fcz_angles_dev only (include/fcz_hip.h).
+
+    angles [n, L, 10] float32 in degrees, columns foldcomp.ANGLE_COLUMNS (phi, psi, omega, the bond angles N-CA-C / CA-C-N(+1) /
+    C-N(+1)-CA(+1), chi1 .. chi4); angle_mask [n, L, 10] bool, False where the record holds no such value (phi and N-CA-C of the
+    first residue, psi / omega and the two bond angles behind the last, a chi the residue type does not have, padding), and the
+    angle is 0 there. omega in row l is the peptide bond BEHIND residue l. The values are the floats the decoder places atoms with.
+    aatype [n, L] uint8 and length [n] int32 as decode_tensors gives them, names the titles. L = max_len, or the longest entry; a
+    longer entry is cropped. packed=True: angles [R, 10], angle_mask [R, 10], aatype [R], cu_seqlens [n + 1] int32 and max_seqlen;
+    no padding, no crop, no max_len. An entry that does not decode has length 0 and no value. Argument errors and the ordering
+    against torch are decode_tensors'.
+
+    Host work: the angles never visit the host, but `names` and `aatype` are read from the record bytes here, one record at a time
+    in Python (a header parse and one byte per residue, uploaded as one array). For large batches that loop, not the kernel, is
+    what the call costs; a loader that has aatype already, or wants the angles beside coordinates, takes decode_tensors(angles=True),
+    whose aatype comes from the decode."""
+    torch, dev = _torch_device(device)
+    c = codec or api.default_codec()
+    if int(c.device) != dev.index:
+        raise api.error(f"decode_angles: the codec works on device {c.device}, the tensors were asked for on {dev}")
+    if packed and max_len is not None:
+        raise ValueError("max_len crops to a common length; the packed form keeps every residue (packed=True takes no max_len)")
+    if max_len is not None and int(max_len) < 1:
+        raise ValueError("max_len must be at least 1")
+    entries = [bytes(e) for e in entries]
+    n = len(entries)
+    names = [_title(e) for e in entries]
+    W = len(ANGLE_COLUMNS)
+    if n == 0:
+        length = torch.zeros(0, dtype=torch.int32, device=dev)
+        if packed:
+            return dict(angles=torch.empty((0, W), dtype=torch.float32, device=dev), angle_mask=torch.empty((0, W), dtype=torch.bool, device=dev),
+                        aatype=torch.empty(0, dtype=torch.uint8, device=dev), length=length, names=names,
+                        cu_seqlens=torch.zeros(1, dtype=torch.int32, device=dev), max_seqlen=0)
+        L = int(max_len or 0)
+        return dict(angles=torch.empty((0, L, W), dtype=torch.float32, device=dev), angle_mask=torch.empty((0, L, W), dtype=torch.bool, device=dev),
+                    aatype=torch.empty((0, L), dtype=torch.uint8, device=dev), length=length, names=names)
+    blob_t, off_t, res_off_t, _, R, _ = _upload_and_size(c, torch, dev, entries)
+    if packed and R > 2 ** 31 - 1:
+        raise api.error(f"decode_angles: {R} residues do not fit the int32 cu_seqlens; split the batch")
+    ro = res_off_t.cpu().numpy().view(np.uint32).astype(np.int64)          # n + 1 offsets: the only words that come back
+    lens = np.diff(ro)
+    L = int(lens.max()) if max_len is None else int(max_len)
+    if packed:
+        aatype = np.zeros(R, np.uint8)
+        for e, k, r0 in zip(entries, lens, ro):
+            aatype[r0:r0 + k] = _aatype_rows(e, int(k)) if k else 0
+        d = _angles_into(c, torch, dev, n, blob_t, off_t, res_off_t, 0, R)
+        d.update(cu_seqlens=res_off_t, max_seqlen=int(lens.max()))
+    else:
+        aatype = np.full((n, L), 20, np.uint8)
+        for i, (e, k) in enumerate(zip(entries, lens)):
+            k = min(int(k), L)
+            if k:
+                aatype[i, :k] = _aatype_rows(e, k)
+        d = _angles_into(c, torch, dev, n, blob_t, off_t, res_off_t, L)
+    d.update(aatype=torch.from_numpy(aatype).to(dev), length=torch.from_numpy(lens.astype(np.int32)).to(dev), names=names)
+    c.synchronize()
+    return d
+
+
 def decode_tensors(entries: Sequence[bytes], *, layout="atom37", max_len: Optional[int] = None, device="cuda:0",
-                   codec: Optional[Codec] = None, packed: bool = False) -> dict:
+                   codec: Optional[Codec] = None, packed: bool = False, angles: bool = False) -> dict:
     """[fcz, ...] -> dict of torch tensors on `device` plus `names` (the records' titles, a Python list).
 
     layout: "atom37" (A = 37, AlphaFold / OpenFold atom order, the chain's OXT in slot 36 of its last residue), "atom14" (A = 14,
@@ -108,24 +218,24 @@ def decode_tensors(entries: Sequence[bytes], *, layout="atom37", max_len: Option
                 torch.empty((n, L), dtype=torch.uint8, device=dev), torch.empty((n, L), dtype=torch.float32, device=dev),
                 torch.empty((n, L), dtype=torch.int32, device=dev), torch.zeros(n, dtype=torch.int32, device=dev))
 
+    def no_angles(*rows):
+        W = len(ANGLE_COLUMNS)
+        return dict(angles=torch.empty(rows + (W,), dtype=torch.float32, device=dev), angle_mask=torch.empty(rows + (W,), dtype=torch.bool, device=dev))
+
     if n == 0:
         if packed:
-            return packed_result(0, torch.zeros(1, dtype=torch.int32, device=dev), 0)[1]
+            d = packed_result(0, torch.zeros(1, dtype=torch.int32, device=dev), 0)[1]
+            return dict(d, **no_angles(0)) if angles else d
         L = int(max_len or 0)
-        return result(L, *alloc(L))
-    off = np.zeros(n + 1, np.uint64)
-    off[1:] = np.cumsum([len(e) for e in entries])
-    # (16 spare bytes behind the last record: the decoder's dword loads of a record's last bytes stay inside the allocation)
-    blob_t = torch.from_numpy(np.frombuffer(b"".join(entries) + bytes(16), np.uint8).copy()).to(dev)
-    off_t = torch.from_numpy(off.view(np.int64)).to(dev)
-    res_off_t = torch.empty(n + 1, dtype=torch.int32, device=dev)
-    atom_off_t = torch.empty(n + 1, dtype=torch.int32, device=dev)
-    torch.cuda.current_stream(dev).synchronize()
-    R, M = ctypes.c_uint32(0), ctypes.c_uint32(0)
-    _lib.check(c.lib.fcz_decompress_sizes_dev(c.ctx, blob_t.data_ptr(), off_t.data_ptr(), n, res_off_t.data_ptr(), atom_off_t.data_ptr(),
-                                              ctypes.byref(R), ctypes.byref(M)), "fcz_decompress_sizes_dev")
+        d = result(L, *alloc(L))
+        return dict(d, **no_angles(0, L)) if angles else d
+    blob_t, off_t, res_off_t, atom_off_t, Rv, Mv = _upload_and_size(c, torch, dev, entries)
+    R, M = ctypes.c_uint32(Rv), ctypes.c_uint32(Mv)
     if packed:
-        return _decode_packed(c, torch, dev, lay, n, int(R.value), int(M.value), blob_t, off_t, res_off_t, atom_off_t, packed_result)
+        # (the angle call is enqueued in front of the decode and leaves it the sizes memo; _decode_packed synchronises the codec)
+        extra = _angles_into(c, torch, dev, n, blob_t, off_t, res_off_t, 0, Rv) if angles else {}
+        d = _decode_packed(c, torch, dev, lay, n, Rv, Mv, blob_t, off_t, res_off_t, atom_off_t, packed_result)
+        return dict(d, **extra)
     if max_len is None:
         ro = res_off_t.cpu().numpy().view(np.uint32).astype(np.int64)      # n + 1 offsets: the only words that come back
         L = int(np.diff(ro).max())
@@ -133,7 +243,8 @@ def decode_tensors(entries: Sequence[bytes], *, layout="atom37", max_len: Option
         L = int(max_len)
     out = alloc(L)
     if L == 0:                                                             # nothing decodes and no width was asked for
-        return result(L, *out)
+        return dict(result(L, *out), **no_angles(n, 0)) if angles else result(L, *out)
+    extra = _angles_into(c, torch, dev, n, blob_t, off_t, res_off_t, L) if angles else {}
     x, y, z = (torch.empty(max(M.value, 1), dtype=torch.float32, device=dev) for _ in range(3))
     bfac = torch.empty(max(R.value, 1), dtype=torch.float32, device=dev)
     res_code = torch.empty(max(R.value, 1), dtype=torch.uint8, device=dev)
@@ -146,7 +257,7 @@ def decode_tensors(entries: Sequence[bytes], *, layout="atom37", max_len: Option
     _lib.check(c.lib.fcz_dense_dev(c.ctx, blob_t.data_ptr(), off_t.data_ptr(), n, res_off_t.data_ptr(), atom_off_t.data_ptr(),
                                    ctypes.byref(atoms), 0, lay, L, ctypes.byref(dense)), "fcz_dense_dev")
     c.synchronize()
-    return result(L, *out)
+    return dict(result(L, *out), **extra)
 
 
 def _decode_packed(c, torch, dev, lay, n, R, M, blob_t, off_t, res_off_t, atom_off_t, packed_result):

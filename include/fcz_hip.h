@@ -16,6 +16,8 @@
  *     src/foldcomp.cpp:779
  *   Foldcomp::checkValidity()        src/foldcomp.cpp:1492   fcz_check
  *   (none: the reference stops at the flat atom vector)    fcz_dense_dev / fcz_decompress_dense, fcz_dense_packed_dev / fcz_decompress_dense_packed
+ *   Foldcomp::decompress, the dequantisation :784-804     fcz_angles_dev / fcz_angles_packed_dev, fcz_decompress_angles[_packed]
+ *     (get_data's FCZ branch, foldcomp/foldcomp.cxx)
  *   (none: Foldcomp::compress starts from the flat list)   fcz_undense_dev / fcz_compress_dense_begin[_dev], fcz_undense_packed_dev /
  *                                                          fcz_compress_dense_packed_begin[_dev]
  *
@@ -323,6 +325,54 @@ int fcz_dense_packed_dev(fcz_ctx* ctx, const uint8_t* blob_dev, const uint64_t* 
 int fcz_decompress_dense_packed(fcz_ctx* ctx, const uint8_t* blob, const uint64_t* off, uint32_t n, int layout,
                                 uint32_t* R_out, uint32_t* row_off, const fcz_packed_out* out, int32_t* status);
 
+/* ---- torsion-angle tensors: the record's internal coordinates, no reconstruction ------------------------ */
+/* What Foldcomp::decompress dequantises before it places an atom (src/foldcomp.cpp:784-804: the backbone torsions and bond angles of
+ * every packed word; :338-369 for the side-chain torsion bytes) and the FCZ branch of foldcomp.cxx's get_data returns as Python lists
+ * (phi / psi / omega / bond_angles; it omits the side-chain torsions), as tensors for a whole batch. The values come straight from
+ * the record bytes: no atom is decoded, no coordinate kernel runs, and they are the very floats the decoder places atoms with.
+ * Per residue row FCZ_ANGLE_COLUMNS float32 in degrees and as many mask bytes (1 = the record holds the value). For entry e with
+ * n residues, row l:
+ *   0 phi    C(l-1)-N-CA-C                 `phi` of word l-1      1 <= l <= n-1
+ *   1 psi    N-CA-C-N(l+1)                 `psi` of word l        l <= n-2
+ *   2 omega  CA-C-N(l+1)-CA(l+1)           `omega` of word l      l <= n-2     (the peptide bond BEHIND residue l)
+ *   3 N-CA-C at l                          `n_ca_c` of word l-1   1 <= l <= n-1
+ *   4 CA-C-N(l+1)                          `ca_c_n` of word l     l <= n-2
+ *   5 C-N(l+1)-CA(l+1)                     `c_n_ca` of word l     l <= n-2
+ *   6 .. 9 chi1 .. chi4                    the side-chain torsion byte of the atom fcz_chi_atom names, where the type has that chi
+ * Word k holds psi of k, omega of k -> k+1, and phi and N-CA-C of k+1 (src/foldcomp.cpp:784-841); residue 0's N-CA-C is not in the
+ * format, and the fields of word n-1 are not angles and never reach the output. Columns 0 .. 5 are dequantised with the header's six
+ * min / cont_f pairs, the chis with the fixed-angle quantiser (FixedAngleDiscretizer(255), src/discretizer.h:89-106). The residue
+ * code that selects the chi atoms is the decoder's (residue 0: header.firstResidue). Where the mask is 0 the value is 0.0f.
+ *   padded   angles [n][L][10], mask [n][L][10]: an entry longer than L keeps its first L rows (row L-1 of a cropped entry still has
+ *            psi and omega: word L-1 exists); rows behind an entry's length, and all L rows of an entry the decoder skips, are 0 / 0.
+ *   packed   angles [R][10], mask [R][10] over the rows of res_off (R = res_off[n]); a skipped entry has no row.
+ * Every byte of both arrays is written exactly once and nothing outside them; every index is 64-bit. */
+#define FCZ_ANGLE_COLUMNS 10
+/* pure host: atom code of the atom whose torsion is chi k + 1 (k = 0 .. 3) of a residue of res_code, -1 when the type has no such
+ * chi (ALA, GLY, codes 20 .. 23) or an argument is out of range. The atom's predecessors in the reference's src/amino_acid.h are
+ * the standard chi quadruple's first three atoms. */
+int fcz_chi_atom(int res_code, int k);
+/* Device-resident, beside Foldcomp::decompress (src/foldcomp.cpp:784-804) and the FCZ branch of foldcomp.cxx's get_data: every pointer
+ * a device pointer, res_off_dev what fcz_decompress_sizes_dev left for the same entries. Enqueued on the ctx stream, no
+ * synchronisation. The calls read only their arguments: nothing of a decode, nothing the ctx keeps -- the same output before and
+ * after a fcz_decompress_batch_dev on the same pointers, and the sizes memo stays as it was. A NULL pointer, or L == 0 in the padded
+ * form: FCZ_E_INVALID_ARG, nothing launched; n == 0: FCZ_OK. */
+int fcz_angles_dev(fcz_ctx* ctx, const uint8_t* blob_dev, const uint64_t* off_dev, uint32_t n, const uint32_t* res_off_dev,
+                   uint32_t L, float* angles_dev, uint8_t* mask_dev);
+int fcz_angles_packed_dev(fcz_ctx* ctx, const uint8_t* blob_dev, const uint64_t* off_dev, uint32_t n, const uint32_t* res_off_dev,
+                          float* angles_dev, uint8_t* mask_dev);
+/* Host-pointer conveniences, shaped like fcz_decompress_dense / fcz_decompress_dense_packed (Foldcomp::read, src/foldcomp.cpp:904,
+ * then the dequantisation of Foldcomp::decompress, :784-804, for every entry; the batched form of get_data's FCZ branch in
+ * foldcomp.cxx): records in, host arrays out, the sizes pass and the angle kernel only. Padded: L = 0 is the longest entry of the
+ * batch, the width used comes back through *L_out (may be NULL). Packed: *R_out (may be NULL) receives R and row_off[n + 1] (may be
+ * NULL) the row offsets. angles and mask both NULL: a sizing call (L_out / R_out required). status[n] (may be NULL) receives the
+ * per-entry fcz_status. NULL ctx / blob / off, one of angles / mask without the other, neither of them nor L_out / R_out:
+ * FCZ_E_INVALID_ARG. */
+int fcz_decompress_angles(fcz_ctx* ctx, const uint8_t* blob, const uint64_t* off, uint32_t n, uint32_t L, uint32_t* L_out,
+                          float* angles, uint8_t* mask, int32_t* status);
+int fcz_decompress_angles_packed(fcz_ctx* ctx, const uint8_t* blob, const uint64_t* off, uint32_t n, uint32_t* R_out, uint32_t* row_off,
+                                 float* angles, uint8_t* mask, int32_t* status);
+
 /* ---- dense model-input tensors -> fcz_chain_batch -> FCZ records ---------------------------------------- */
 /* The way back: n chains held as the padded arrays above (a model's predictions, a filtered or re-cropped set, what fcz_dense_dev
  * wrote) become the flat structure-of-arrays batch fcz_compress_sizes_dev / fcz_compress_batch_dev take, on the device. These entry
@@ -551,7 +601,8 @@ int fcz_check(const uint8_t* entry, uint64_t len);
  * group since the last reset: "compress_sizes", "compress_index", "compress_angles", "compress_pack",
  * "decompress_sizes", "decompress_backbone", "decompress_index", "decompress_sidechain", "pdb_sizes", "pdb_format", "extract_sizes", "extract",
  * "ingest_parse", "ingest_parse_cif", "ingest_rows_cif", "ingest_frags", "ingest_fill", "inflate", "dense", "undense" (the counting and the fill
- * kernel of fcz_undense_dev: two launches per call). The packed entry points are timed under the same two groups. */
+ * kernel of fcz_undense_dev: two launches per call), "angles" (fcz_angles_dev). Every packed entry point is timed under the group
+ * of its padded form: fcz_dense_packed_dev under "dense", fcz_undense_packed_dev under "undense", fcz_angles_packed_dev under "angles". */
 int  fcz_ctx_enable_timing(fcz_ctx* ctx, int enable);
 int  fcz_ctx_kernel_time(fcz_ctx* ctx, const char* name, double* ms, uint64_t* launches);
 void fcz_ctx_reset_timing(fcz_ctx* ctx);

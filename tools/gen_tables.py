@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Generate foldcomp_amd/csrc/aa_tables.h and foldcomp_amd/_aa_tables.py.
+"""Generate foldcomp_amd/csrc/aa_tables.h (+ aa_tables.inc, aa_tables_chi.inc) and foldcomp_amd/_aa_tables.py.
 
 Run in the build container only (needs /root/reference). The amino-acid geometry of the
 reference is *data* (ideal bond lengths/angles after Peptide Builder), held in
@@ -23,6 +23,16 @@ REF = "/root/reference/src/amino_acid.h"
 RES3 = ["ALA","ARG","ASN","ASP","CYS","GLN","GLU","GLY","HIS","ILE","LEU","LYS","MET",
         "PHE","PRO","SER","THR","TRP","TYR","VAL","ASX","GLX","STP","UNK"]
 RES1 = "ARNDCQEGHILKMFPSTWYVBZ*X"
+# chi k of a residue type = the side-chain torsion that places this atom: its predecessor triple in src/amino_acid.h is the
+# standard chi quadruple's first three atoms (N CA CB / CA CB CG / ...). Types not listed, and codes 20 .. 23, have no chi.
+CHI_ATOMS = [
+    dict(ARG="CG", ASN="CG", ASP="CG", GLN="CG", GLU="CG", HIS="CG", LEU="CG", LYS="CG", MET="CG", PHE="CG", PRO="CG", TRP="CG",
+         TYR="CG", CYS="SG", ILE="CG1", VAL="CG1", SER="OG", THR="OG1"),
+    dict(ARG="CD", GLN="CD", GLU="CD", LYS="CD", PRO="CD", ASN="OD1", ASP="OD1", HIS="ND1", ILE="CD1", LEU="CD1", PHE="CD1",
+         TRP="CD1", TYR="CD1", MET="SD"),
+    dict(ARG="NE", GLN="OE1", GLU="OE1", LYS="CE", MET="CE"),
+    dict(ARG="CZ", LYS="NZ"),
+]
 
 def parse():
     src = open(REF).read()
@@ -105,6 +115,18 @@ def main():
             else:
                 prow.append([0, 0, 0]); lrow.append(0); grow.append(0)
         prev.append(prow); blen.append(lrow); bang.append(grow)
+    # chi_slot[rc][k] = canonical slot of the atom chi k places (its torsion byte is number slot - 3 of the residue), 0 = no such chi
+    chis = []
+    for r in RES3:
+        row = []
+        for k in range(4):
+            a = CHI_ATOMS[k].get(r)
+            if a is None: row.append(0); continue
+            al = aas[r]["atoms"]; pre = aas[r]["side"][a]
+            if k == 0: assert pre[:2] == ["N", "CA"], (r, a, pre)
+            else: assert pre[1:] == [aas[r]["side"][CHI_ATOMS[k - 1][r]][2], CHI_ATOMS[k - 1][r]], (r, a, pre)   # the chain N CA CB CG ... continues
+            row.append(al.index(a))
+        chis.append(row)
     ntors = [max(n - 3, 0) for n in natoms]
     assert ntors[:20] == [2,8,5,5,3,6,6,1,7,5,5,6,5,8,4,3,4,11,9,4], ntors
 
@@ -130,6 +152,7 @@ def main():
     h("#define FCZ_T(name) fcz_##name")
     h("#endif")
     h('#include "aa_tables.inc"')
+    h('#include "aa_tables_chi.inc"')
     open("foldcomp_amd/csrc/aa_tables.h", "w").write("\n".join(hdr) + "\n")
 
     out = []
@@ -156,6 +179,18 @@ def main():
     tab2("res_bang_bits", "uint32_t", bang, lambda v: "0x%08xu" % v)
     open("foldcomp_amd/csrc/aa_tables.inc", "w").write("\n".join(out) + "\n")
 
+    # a file of its own: aa_tables.inc is part of the hash that ties profiles/traffic.json to the codec kernels' sources
+    # (bench.py KERNEL_SOURCES), and no kernel measured there reads this table
+    out = []
+    w = out.append
+    w("// GENERATED by tools/gen_tables.py -- do not edit. Included by aa_tables.h behind aa_tables.inc (no include guard on purpose).")
+    w("// chi1 .. chi4: canonical slot of the atom whose side-chain torsion is chi k (0 = the residue type has no such chi)")
+    w("FCZ_TABLE_QUAL uint8_t FCZ_T(res_chi_slot)[FCZ_N_RES_CODES][4] = {")
+    for r, row in zip(RES3, chis):
+        w("  {%s}, // %s" % (",".join(map(str, row)), r))
+    w("};")
+    open("foldcomp_amd/csrc/aa_tables_chi.inc", "w").write("\n".join(out) + "\n")
+
     py = []
     py.append('"""GENERATED by tools/gen_tables.py -- do not edit."""')
     py.append("RES3 = %r" % RES3)
@@ -164,6 +199,8 @@ def main():
     py.append("RES_NATOMS = %r" % natoms)
     py.append("RES_ATOMS = %r" % [row[:n] for row, n in zip(atoms, natoms)])
     py.append("RES_ALT_SLOT = %r" % [row[:n] for row, n in zip(alts, natoms)])
+    py.append("RES_PREV = %r" % [[tuple(p) for p in row[:n]] for row, n in zip(prev, natoms)])
+    py.append("RES_CHI_SLOT = %r" % chis)
     open("foldcomp_amd/_aa_tables.py", "w").write("\n".join(py) + "\n")
     print("atom codes:", names)
 

@@ -242,7 +242,7 @@ class FoldcompDatabase:
 
     def tensor_batches(self, batch_size: int = 1024, *, layout="atom37", max_len: Optional[int] = None, device="cuda:0",
                        sort_by_length: bool = False, packed: bool = False, max_residues: Optional[int] = None,
-                       angles: bool = False):
+                       angles: bool = False, crop: Optional[str] = None, seed: Optional[int] = None):
         """Generator over the database (its `ids` selection when it has one) in batches of dense model-input tensors on the GPU:
         the dicts of foldcomp_amd.tensors.decode_tensors, each with `names` (the records' titles) and `index` (int64 array: the
         entries' positions in this database, what db[i] takes). sort_by_length orders every window of 16 * batch_size entries by
@@ -250,12 +250,18 @@ class FoldcompDatabase:
         packed=True yields the packed dicts (decode_tensors(packed=True): no padding, no crop, cu_seqlens), and max_residues then
         cuts the batches by a residue budget (cut_batches): a batch closes before the entry that would take it over the budget
         or at batch_size entries; an entry longer than the budget forms a batch of its own. angles=True adds `angles` and
-        `angle_mask` to every dict (decode_tensors(angles=True))."""
+        `angle_mask` to every dict (decode_tensors(angles=True)). crop="start" / "center" / "random" with max_len=L keeps a window
+        of L residues of every longer entry (decode_tensors(crop=...)) and adds `crop_start` to every dict; "random" draws from ONE
+        generator for the whole iteration, seeded once with `seed` (None: from the system), so the same seed gives the same crops."""
         from .tensors import decode_tensors
         batch_size = int(batch_size)
         if batch_size < 1:
             raise ValueError("batch_size must be at least 1")
         check_batch_cut(packed, max_len, max_residues)
+        if crop is not None and not isinstance(crop, str):
+            raise ValueError("tensor_batches takes crop='start', 'center' or 'random' (per-entry starts belong to one batch: decode_tensors)")
+        check_crop(crop, max_len, packed)
+        gen = None
         window = 16 * batch_size if sort_by_length else batch_size
         if max_residues is not None:
             window = 16 * batch_size                    # (a budget closes batches early: read ahead as the sort does)
@@ -268,7 +274,12 @@ class FoldcompDatabase:
                 if packed:
                     d = decode_tensors([ents[k] for k in sel], layout=layout, device=device, packed=True, angles=angles)
                 else:
-                    d = decode_tensors([ents[k] for k in sel], layout=layout, max_len=max_len, device=device, angles=angles)
+                    if crop == "random" and gen is None:
+                        import torch
+                        gen = torch.Generator(device=device)
+                        gen.manual_seed(int(seed)) if seed is not None else gen.seed()
+                    d = decode_tensors([ents[k] for k in sel], layout=layout, max_len=max_len, device=device, angles=angles, crop=crop,
+                                       generator=gen)
                 d["index"] = idx[sel]
                 yield d
 
@@ -293,6 +304,21 @@ def check_batch_cut(packed, max_len, max_residues):
         raise ValueError("max_residues must be at least 1")
     if packed and max_len is not None:
         raise ValueError("max_len crops to a common length; the packed form keeps every residue (packed=True takes no max_len)")
+
+
+CROP_MODES = ("start", "center", "random")
+
+
+def check_crop(crop, max_len, packed):
+    """the argument rules of crop= (decode_tensors, decode_angles, tensor_batches) that need no records and no GPU"""
+    if crop is None:
+        return
+    if isinstance(crop, str) and crop not in CROP_MODES:
+        raise ValueError(f"crop must be one of {CROP_MODES} or per-entry starts [n], not {crop!r}")
+    if packed:
+        raise ValueError("crop keeps a window of max_len rows per entry; the packed form keeps every residue (packed=True takes no crop)")
+    if max_len is None:
+        raise ValueError("crop needs max_len: the window is max_len residues long")
 
 
 def cut_batches(lengths, batch_size: int, max_residues: Optional[int] = None, sort_by_length: bool = False) -> list:

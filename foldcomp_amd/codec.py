@@ -122,17 +122,40 @@ class Codec:
                        "fcz_decompress_batch")
         return dict(x=x, y=y, z=z, bfac_res=bf, res_code=rc, atom_code=ac, res_off=res_off, atom_off=atom_off, info=info)
 
-    def decompress_dense(self, blob: np.ndarray, off: np.ndarray, layout="atom37", max_len: Optional[int] = None, packed: bool = False):
+    @staticmethod
+    def _window_starts(start, n: int) -> np.ndarray:
+        """per-entry first residues of a windowed call -> uint32 [n]"""
+        st = np.asarray(start)
+        if st.shape != (n,) or st.dtype.kind not in "iu":
+            raise ValueError(f"start must be {n} integers, one per entry, not {st.dtype} {st.shape}")
+        if n and (st.astype(np.int64) < 0).any() or n and (st.astype(np.uint64) > 2 ** 32 - 1).any():
+            raise ValueError("start must fit unsigned 32 bits")
+        return np.ascontiguousarray(st, np.uint32)
+
+    def decompress_dense(self, blob: np.ndarray, off: np.ndarray, layout="atom37", max_len: Optional[int] = None, packed: bool = False,
+                         start=None):
         """FCZ entries -> dense padded arrays on the host (fcz_decompress_dense): pos float32 [n, L, A, 3], mask bool [n, L, A],
         aatype uint8 [n, L] (20 = unknown / padding), plddt float32 [n, L], res_index int32 [n, L], length uint32 [n] (uncropped;
         0 = the entry did not decode), status int32 [n]. L = max_len, or the longest entry of the batch; longer entries are cropped.
         packed=True (fcz_decompress_dense_packed): the rows of all entries back to back, pos [R, A, 3], mask [R, A], aatype, plddt,
-        res_index, chain_index int32 [R], row_off uint32 [n + 1] (the cu_seqlens), length, status; no padding and no crop, so no max_len."""
+        res_index, chain_index int32 [R], row_off uint32 [n + 1] (the cu_seqlens), length, status; no padding and no crop, so no max_len.
+        start [n] (fcz_decompress_dense_window): row l of entry e holds its residue start[e] + l, or padding when it has none; length
+        stays uncropped. Not with packed=True."""
         blob = np.ascontiguousarray(blob, np.uint8)
         off = np.ascontiguousarray(off, np.uint64)
         n = len(off) - 1
         lay = dense_layout(layout)
         A = self.lib.fcz_dense_width(lay)
+        if start is not None and packed:
+            raise ValueError("start keeps a window of rows per entry; the packed form keeps every residue (packed=True takes no start)")
+        st = None if start is None else self._window_starts(start, n)
+
+        def padded(L, L_out, out, status):
+            if st is None:
+                _lib.check(self.lib.fcz_decompress_dense(self.ctx, blob.ctypes.data, off.ctypes.data, n, lay, L, L_out, out, status), "fcz_decompress_dense")
+            else:
+                _lib.check(self.lib.fcz_decompress_dense_window(self.ctx, blob.ctypes.data, off.ctypes.data, n, lay, L, st.ctypes.data, L_out, out, status),
+                           "fcz_decompress_dense_window")
         if packed and max_len is not None:
             raise ValueError("max_len crops to a common length; the packed form keeps every residue (packed=True takes no max_len)")
         if max_len is not None and int(max_len) < 1:
@@ -158,8 +181,7 @@ class Codec:
         L = ctypes.c_uint32(0)
         status = np.zeros(max(n, 1), np.int32)
         if max_len is None:
-            _lib.check(self.lib.fcz_decompress_dense(self.ctx, blob.ctypes.data, off.ctypes.data, n, lay, 0, ctypes.byref(L), None,
-                                                     status.ctypes.data), "fcz_decompress_dense")
+            padded(0, ctypes.byref(L), None, status.ctypes.data)
         else:
             L.value = int(max_len)
         Lv = int(L.value)
@@ -167,20 +189,25 @@ class Codec:
                  plddt=np.zeros((n, Lv), np.float32), res_index=np.zeros((n, Lv), np.int32), length=np.zeros(n, np.uint32))
         if n and Lv:
             out = CDenseOut(*(d[k].ctypes.data for k in ("pos", "mask", "aatype", "plddt", "res_index", "length")))
-            _lib.check(self.lib.fcz_decompress_dense(self.ctx, blob.ctypes.data, off.ctypes.data, n, lay, Lv, None, ctypes.byref(out),
-                                                     status.ctypes.data), "fcz_decompress_dense")
+            padded(Lv, None, ctypes.byref(out), status.ctypes.data)
         d["mask"] = d["mask"].view(np.bool_)
         d["status"] = status[:n]
         return d
 
-    def decompress_angles(self, blob: np.ndarray, off: np.ndarray, L: int = 0, packed: bool = False):
+    def decompress_angles(self, blob: np.ndarray, off: np.ndarray, L: int = 0, packed: bool = False, start=None):
         """FCZ entries -> the record's internal coordinates on the host (fcz_decompress_angles): angles float32 [n, L, 10] in degrees
         (ANGLE_COLUMNS), angle_mask bool [n, L, 10], status int32 [n]; L = 0: the longest entry of the batch, longer entries are
         cropped. packed=True (fcz_decompress_angles_packed): angles [R, 10], angle_mask [R, 10], row_off uint32 [n + 1]; no L.
-        The sizes pass and the angle kernel only: nothing is reconstructed."""
+        The sizes pass and the angle kernel only: nothing is reconstructed.
+        start [n] (fcz_decompress_angles_window): row l of entry e holds its residue start[e] + l, or zeros when it has none, and the
+        dict gains aatype uint8 [n, L] (20 in the padding). Not with packed=True."""
         blob = np.ascontiguousarray(blob, np.uint8)
         off = np.ascontiguousarray(off, np.uint64)
         n = len(off) - 1
+        if start is not None and packed:
+            raise ValueError("start keeps a window of rows per entry; the packed form keeps every residue (packed=True takes no start)")
+        st = None if start is None else self._window_starts(start, n)
+        aatype = None
         if packed and L:
             raise ValueError("L crops to a common length; the packed form keeps every residue (packed=True takes no L)")
         if int(L) < 0:
@@ -190,12 +217,16 @@ class Codec:
         status = np.zeros(max(n, 1), np.int32)
         row_off = np.zeros(n + 1, np.uint32)
 
-        def call(angles, mask, st):
+        def call(angles, mask, status):
             if packed:
                 _lib.check(self.lib.fcz_decompress_angles_packed(self.ctx, blob.ctypes.data, off.ctypes.data, n, ctypes.byref(width), row_off.ctypes.data,
-                                                                 angles, mask, st), "fcz_decompress_angles_packed")
+                                                                 angles, mask, status), "fcz_decompress_angles_packed")
+            elif st is not None:
+                _lib.check(self.lib.fcz_decompress_angles_window(self.ctx, blob.ctypes.data, off.ctypes.data, n, int(L), st.ctypes.data, ctypes.byref(width),
+                                                                 angles, mask, None if aatype is None else aatype.ctypes.data, status),
+                           "fcz_decompress_angles_window")
             else:
-                _lib.check(self.lib.fcz_decompress_angles(self.ctx, blob.ctypes.data, off.ctypes.data, n, int(L), ctypes.byref(width), angles, mask, st),
+                _lib.check(self.lib.fcz_decompress_angles(self.ctx, blob.ctypes.data, off.ctypes.data, n, int(L), ctypes.byref(width), angles, mask, status),
                            "fcz_decompress_angles")
 
         if n:
@@ -203,6 +234,8 @@ class Codec:
         Wd = int(width.value)
         shape = (Wd, W) if packed else (n, Wd, W)
         d = dict(angles=np.zeros(shape, np.float32), angle_mask=np.zeros(shape, np.uint8))
+        if st is not None:
+            d["aatype"] = aatype = np.full((n, Wd), 20, np.uint8)
         if n and Wd:
             call(d["angles"].ctypes.data, d["angle_mask"].ctypes.data, None)
         d["angle_mask"] = d["angle_mask"].view(np.bool_)

@@ -82,11 +82,12 @@ struct timed_span { std::string name; hipEvent_t a, b; };
 // never live together (table in fcz_ctx). REC_*: uploaded FCZ records (n + 1 u64 offsets), their res_off / atom_off (n + 1 u32) and
 // the fcz_atoms_out decoded from them; FILES_*: structure files of an ingest call; BATCH_IN / DENSE_IN / DENSE_OUT: first of the 13
 // arrays of a fcz_chain_batch, the 10 of a fcz_dense_in (slot 3, length, holds row_off [n + 1] in the packed form), the 6 of a
-// fcz_dense_out, the 7 of a fcz_packed_out (PACKED_OUT .. PACKED_OUT_LAST), in the struct's order; ANGLES_OUT: the angles and their mask; KEPT_*: the records a *_begin
-// call leaves for its fetch (C + 1 u64 offsets, the bytes, C i32 status)
+// fcz_dense_out, the 7 of a fcz_packed_out (PACKED_OUT .. PACKED_OUT_LAST), in the struct's order; ANGLES_OUT: the angles, their mask and
+// (windowed form) aatype; WINDOW_START: the n u32 starts of a windowed host call; KEPT_*: the records a *_begin call leaves for its fetch
+// (C + 1 u64 offsets, the bytes, C i32 status)
 enum { REC_BLOB, REC_OFF, REC_RES_OFF, REC_ATOM_OFF, REC_X, REC_Y, REC_Z, REC_BFAC, REC_RES_CODE, REC_ATOM_CODE,
        FILES_TEXT = 0, FILES_OFF, FILES_NAMES, FILES_NAME_OFF, FILES_STEM_LEN, BATCH_IN = 0, DENSE_IN = 0, DENSE_OUT = 10,
-       PACKED_OUT = 10, ANGLES_OUT = 10, KEPT_OFF = 13, KEPT_BYTES, KEPT_STATUS, PACKED_OUT_LAST, POOL_COUNT };
+       PACKED_OUT = 10, ANGLES_OUT = 10, KEPT_OFF = 13, KEPT_BYTES, KEPT_STATUS, PACKED_OUT_LAST, WINDOW_START = PACKED_OUT_LAST, POOL_COUNT };
 
 // what the device reports to the host in the middle of a call: one pinned allocation, a member per reader
 struct pinned_words {
@@ -145,6 +146,8 @@ struct fcz_ctx {
     //   fcz_decompress_dense                        REC_* 0 .. 8, DENSE_OUT 10 .. 15
     //   fcz_decompress_dense_packed                 REC_* 0 .. 8, PACKED_OUT 10 .. 16
     //   fcz_decompress_angles[_packed]              REC_* 0 .. 3, ANGLES_OUT 10 .. 11
+    //   fcz_decompress_dense_window                 REC_* 0 .. 8, DENSE_OUT 10 .. 15, WINDOW_START 16
+    //   fcz_decompress_angles_window                REC_* 0 .. 3, ANGLES_OUT 10 .. 12, WINDOW_START 16
     //   fcz_compress_batch                          BATCH_IN 0 .. 12, KEPT_* 13 .. 15
     //   fcz_inflate                                 FILES_TEXT
     //   fcz_ingest_pdb_begin / fcz_ingest_gz_begin  FILES_* 0 .. 4 (gz: no FILES_OFF, gz_toff)      (ig[], ig_res, ig_counts)
@@ -1362,9 +1365,10 @@ static dense_table dense_make_table(int layout, int alt_order) {
     return t;
 }
 
-int fcz_dense_dev(fcz_ctx* ctx, const uint8_t* blob_dev, const uint64_t* off_dev, uint32_t n, const uint32_t* res_off_dev,
-                  const uint32_t* atom_off_dev, const fcz_atoms_out* atoms_dev, int alt_order, int layout, uint32_t L,
-                  const fcz_dense_out* out_dev) {
+// fcz_dense_dev (k_dense) and fcz_dense_window_dev (window: k_dense_window with start_dev, which may be NULL)
+static int dense_rows(fcz_ctx* ctx, const uint8_t* blob_dev, const uint64_t* off_dev, uint32_t n, const uint32_t* res_off_dev,
+                      const uint32_t* atom_off_dev, const fcz_atoms_out* atoms_dev, int alt_order, int layout, uint32_t L, bool window,
+                      const uint32_t* start_dev, const fcz_dense_out* out_dev) {
     if (!ctx || !blob_dev || !off_dev || !res_off_dev || !atom_off_dev || !atoms_out_ok(atoms_dev) || !out_dev) return FCZ_E_INVALID_ARG;
     if (fcz_dense_width(layout) < 0 || L == 0 || !out_dev->pos || !out_dev->mask) return FCZ_E_INVALID_ARG;
     HIP_TRY(hipSetDevice(ctx->device));
@@ -1377,10 +1381,26 @@ int fcz_dense_dev(fcz_ctx* ctx, const uint8_t* blob_dev, const uint64_t* off_dev
     const uint32_t blocks = (uint32_t)std::min<uint64_t>(n_tiles, (uint64_t)ctx->n_cu * 32u);
     span_guard sg(ctx, "dense");
     dispatch_layout(layout, [&](auto A) {
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_dense<decltype(A)::value>), dim3(blocks), dim3(BLOCK), 0, ctx->stream, blob_dev, g, n, L, tiles_per_entry, n_tiles, tab);
+        if (window)
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_dense_window<decltype(A)::value>), dim3(blocks), dim3(BLOCK), 0, ctx->stream, blob_dev, g, start_dev, n, L,
+                               tiles_per_entry, n_tiles, tab);
+        else
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_dense<decltype(A)::value>), dim3(blocks), dim3(BLOCK), 0, ctx->stream, blob_dev, g, n, L, tiles_per_entry, n_tiles, tab);
     });
     HIP_TRY(hipGetLastError());
     return FCZ_OK;
+}
+
+int fcz_dense_dev(fcz_ctx* ctx, const uint8_t* blob_dev, const uint64_t* off_dev, uint32_t n, const uint32_t* res_off_dev,
+                  const uint32_t* atom_off_dev, const fcz_atoms_out* atoms_dev, int alt_order, int layout, uint32_t L,
+                  const fcz_dense_out* out_dev) {
+    return dense_rows(ctx, blob_dev, off_dev, n, res_off_dev, atom_off_dev, atoms_dev, alt_order, layout, L, false, nullptr, out_dev);
+}
+
+int fcz_dense_window_dev(fcz_ctx* ctx, const uint8_t* blob_dev, const uint64_t* off_dev, uint32_t n, const uint32_t* res_off_dev,
+                         const uint32_t* atom_off_dev, const fcz_atoms_out* atoms_dev, int alt_order, int layout, uint32_t L,
+                         const uint32_t* start_dev, const fcz_dense_out* out_dev) {
+    return dense_rows(ctx, blob_dev, off_dev, n, res_off_dev, atom_off_dev, atoms_dev, alt_order, layout, L, true, start_dev, out_dev);
 }
 
 int fcz_dense_packed_dev(fcz_ctx* ctx, const uint8_t* blob_dev, const uint64_t* off_dev, uint32_t n, const uint32_t* res_off_dev,
@@ -1444,8 +1464,9 @@ int fcz_decompress_dense_packed(fcz_ctx* ctx, const uint8_t* blob, const uint64_
     return FCZ_OK;
 }
 
-int fcz_decompress_dense(fcz_ctx* ctx, const uint8_t* blob, const uint64_t* off, uint32_t n, int layout, uint32_t L, uint32_t* L_out,
-                         const fcz_dense_out* out, int32_t* status) {
+// fcz_decompress_dense and fcz_decompress_dense_window (window: the starts of the host array `start`, which may be NULL)
+static int decompress_dense_impl(fcz_ctx* ctx, const uint8_t* blob, const uint64_t* off, uint32_t n, int layout, uint32_t L, bool window,
+                                 const uint32_t* start, uint32_t* L_out, const fcz_dense_out* out, int32_t* status) {
     const int A = fcz_dense_width(layout);
     if (!ctx || !blob || !off || A < 0 || (!out && !L_out) || (out && (!out->pos || !out->mask))) return FCZ_E_INVALID_ARG;
     HIP_TRY(hipSetDevice(ctx->device));
@@ -1481,13 +1502,29 @@ int fcz_decompress_dense(fcz_ctx* ctx, const uint8_t* blob, const uint64_t* off,
         dev[i] = ctx->pool[DENSE_OUT + i].p;
     }
     const fcz_dense_out dd{(float*)dev[0], (uint8_t*)dev[1], (uint8_t*)dev[2], (float*)dev[3], (int32_t*)dev[4], (uint32_t*)dev[5]};
-    rc = fcz_dense_dev(ctx, ctx->pool[REC_BLOB].as<uint8_t>(), ctx->pool[REC_OFF].as<uint64_t>(), n, ctx->pool[REC_RES_OFF].as<uint32_t>(),
-                       ctx->pool[REC_ATOM_OFF].as<uint32_t>(), &dv, 0, layout, L, &dd);
+    const uint32_t* start_dev = nullptr;
+    if (window && start) {
+        if ((rc = ctx->pool[WINDOW_START].ensure(sizeof(uint32_t) * n))) return rc;
+        HIP_TRY(hipMemcpyAsync(ctx->pool[WINDOW_START].p, start, sizeof(uint32_t) * n, hipMemcpyHostToDevice, ctx->stream));
+        start_dev = ctx->pool[WINDOW_START].as<uint32_t>();
+    }
+    rc = dense_rows(ctx, ctx->pool[REC_BLOB].as<uint8_t>(), ctx->pool[REC_OFF].as<uint64_t>(), n, ctx->pool[REC_RES_OFF].as<uint32_t>(),
+                    ctx->pool[REC_ATOM_OFF].as<uint32_t>(), &dv, 0, layout, L, window, start_dev, &dd);
     if (rc) return rc;
     for (int i = 0; i < 6; i++)
         if (bytes[i]) HIP_TRY(hipMemcpyAsync(host[i], dev[i], bytes[i], hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return FCZ_OK;
+}
+
+int fcz_decompress_dense(fcz_ctx* ctx, const uint8_t* blob, const uint64_t* off, uint32_t n, int layout, uint32_t L, uint32_t* L_out,
+                         const fcz_dense_out* out, int32_t* status) {
+    return decompress_dense_impl(ctx, blob, off, n, layout, L, false, nullptr, L_out, out, status);
+}
+
+int fcz_decompress_dense_window(fcz_ctx* ctx, const uint8_t* blob, const uint64_t* off, uint32_t n, int layout, uint32_t L, const uint32_t* start,
+                                uint32_t* L_out, const fcz_dense_out* out, int32_t* status) {
+    return decompress_dense_impl(ctx, blob, off, n, layout, L, true, start, L_out, out, status);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1512,6 +1549,19 @@ int fcz_angles_dev(fcz_ctx* ctx, const uint8_t* blob_dev, const uint64_t* off_de
     return FCZ_OK;
 }
 
+int fcz_angles_window_dev(fcz_ctx* ctx, const uint8_t* blob_dev, const uint64_t* off_dev, uint32_t n, const uint32_t* res_off_dev, uint32_t L,
+                          const uint32_t* start_dev, float* angles_dev, uint8_t* mask_dev, uint8_t* aatype_dev) {
+    if (!ctx || !blob_dev || !off_dev || !res_off_dev || !angles_dev || !mask_dev || L == 0) return FCZ_E_INVALID_ARG;
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (n == 0) return FCZ_OK;
+    const uint32_t blocks = std::min<uint32_t>(grid_for(n, WAVES_PER_BLOCK), (uint32_t)ctx->n_cu * 32u);
+    span_guard sg(ctx, "angles");
+    hipLaunchKernelGGL(k_angles_window, dim3(blocks), dim3(BLOCK), 0, ctx->stream, blob_dev, off_dev, res_off_dev, n, L, start_dev, angles_dev, mask_dev,
+                       aatype_dev);
+    HIP_TRY(hipGetLastError());
+    return FCZ_OK;
+}
+
 int fcz_angles_packed_dev(fcz_ctx* ctx, const uint8_t* blob_dev, const uint64_t* off_dev, uint32_t n, const uint32_t* res_off_dev,
                           float* angles_dev, uint8_t* mask_dev) {
     if (!ctx || !blob_dev || !off_dev || !res_off_dev || !angles_dev || !mask_dev) return FCZ_E_INVALID_ARG;
@@ -1524,9 +1574,11 @@ int fcz_angles_packed_dev(fcz_ctx* ctx, const uint8_t* blob_dev, const uint64_t*
     return FCZ_OK;
 }
 
-// the two host-pointer forms; width_out is L_out (padded) or R_out (packed)
+// the three host-pointer forms; width_out is L_out (padded, windowed) or R_out (packed); window: the starts of the host array `start`
+// (may be NULL) and the optional host array aatype
 static int decompress_angles_impl(fcz_ctx* ctx, const uint8_t* blob, const uint64_t* off, uint32_t n, bool packed, uint32_t L, uint32_t* width_out,
-                                  uint32_t* row_off, float* angles, uint8_t* mask, int32_t* status) {
+                                  uint32_t* row_off, float* angles, uint8_t* mask, int32_t* status, bool window = false, const uint32_t* start = nullptr,
+                                  uint8_t* aatype = nullptr) {
     if (!ctx || !blob || !off || (!angles != !mask) || (!angles && !width_out)) return FCZ_E_INVALID_ARG;
     HIP_TRY(hipSetDevice(ctx->device));
     claim_staging(ctx);
@@ -1547,8 +1599,20 @@ static int decompress_angles_impl(fcz_ctx* ctx, const uint8_t* blob, const uint6
     const size_t elems = rows * FCZ_ANGLE_COLUMNS;
     if ((rc = ctx->pool[ANGLES_OUT].ensure(elems * sizeof(float))) || (rc = ctx->pool[ANGLES_OUT + 1].ensure(elems))) return rc;
     const uint8_t* b = ctx->pool[REC_BLOB].as<uint8_t>(); const uint64_t* o = ctx->pool[REC_OFF].as<uint64_t>(); const uint32_t* ro = ctx->pool[REC_RES_OFF].as<uint32_t>();
-    rc = packed ? fcz_angles_packed_dev(ctx, b, o, n, ro, ctx->pool[ANGLES_OUT].as<float>(), ctx->pool[ANGLES_OUT + 1].as<uint8_t>())
-                : fcz_angles_dev(ctx, b, o, n, ro, L, ctx->pool[ANGLES_OUT].as<float>(), ctx->pool[ANGLES_OUT + 1].as<uint8_t>());
+    if (window) {
+        const uint32_t* start_dev = nullptr;
+        if (start) {
+            if ((rc = ctx->pool[WINDOW_START].ensure(sizeof(uint32_t) * n))) return rc;
+            HIP_TRY(hipMemcpyAsync(ctx->pool[WINDOW_START].p, start, sizeof(uint32_t) * n, hipMemcpyHostToDevice, ctx->stream));
+            start_dev = ctx->pool[WINDOW_START].as<uint32_t>();
+        }
+        if (aatype && (rc = ctx->pool[ANGLES_OUT + 2].ensure(rows))) return rc;
+        rc = fcz_angles_window_dev(ctx, b, o, n, ro, L, start_dev, ctx->pool[ANGLES_OUT].as<float>(), ctx->pool[ANGLES_OUT + 1].as<uint8_t>(),
+                                   aatype ? ctx->pool[ANGLES_OUT + 2].as<uint8_t>() : nullptr);
+        if (!rc && aatype) HIP_TRY(hipMemcpyAsync(aatype, ctx->pool[ANGLES_OUT + 2].p, rows, hipMemcpyDeviceToHost, ctx->stream));
+    } else
+        rc = packed ? fcz_angles_packed_dev(ctx, b, o, n, ro, ctx->pool[ANGLES_OUT].as<float>(), ctx->pool[ANGLES_OUT + 1].as<uint8_t>())
+                    : fcz_angles_dev(ctx, b, o, n, ro, L, ctx->pool[ANGLES_OUT].as<float>(), ctx->pool[ANGLES_OUT + 1].as<uint8_t>());
     if (rc) return rc;
     HIP_TRY(hipMemcpyAsync(angles, ctx->pool[ANGLES_OUT].p, elems * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipMemcpyAsync(mask, ctx->pool[ANGLES_OUT + 1].p, elems, hipMemcpyDeviceToHost, ctx->stream));
@@ -1559,6 +1623,11 @@ static int decompress_angles_impl(fcz_ctx* ctx, const uint8_t* blob, const uint6
 int fcz_decompress_angles(fcz_ctx* ctx, const uint8_t* blob, const uint64_t* off, uint32_t n, uint32_t L, uint32_t* L_out, float* angles,
                           uint8_t* mask, int32_t* status) {
     return decompress_angles_impl(ctx, blob, off, n, false, L, L_out, nullptr, angles, mask, status);
+}
+
+int fcz_decompress_angles_window(fcz_ctx* ctx, const uint8_t* blob, const uint64_t* off, uint32_t n, uint32_t L, const uint32_t* start,
+                                 uint32_t* L_out, float* angles, uint8_t* mask, uint8_t* aatype, int32_t* status) {
+    return decompress_angles_impl(ctx, blob, off, n, false, L, L_out, nullptr, angles, mask, status, true, start, aatype);
 }
 
 int fcz_decompress_angles_packed(fcz_ctx* ctx, const uint8_t* blob, const uint64_t* off, uint32_t n, uint32_t* R_out, uint32_t* row_off,

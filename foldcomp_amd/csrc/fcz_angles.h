@@ -7,6 +7,10 @@
 //
 //   k_angles          padded: angles [n][L][10], mask [n][L][10]; rows behind an entry's length (and a skipped entry's L rows): zeros
 //   k_angles_packed   packed: angles [R][10], mask [R][10] over the rows of res_off; a skipped entry has no row
+//   k_angles_window   padded with a per-entry first residue start[e] (a crop at an offset) and an optional aatype [n][L]: the wavefront
+//                     first walks the start[e] residues in front of its window, 64 per step, for their torsion-byte total -- one byte
+//                     per residue (the code sits in the word's first byte), nothing stored -- takes word start - 1 as its carry, and
+//                     runs the same tile loop from there. The window's first row has phi and N-CA-C when start >= 1.
 //
 // One wavefront per entry, a persistent grid over the entries. The wavefront walks its entry in tiles of 64 rows, lane = residue:
 // word l (psi, omega and the two bond angles behind residue l) is the lane's own 8-byte load, word l - 1 (phi and N-CA-C of l) comes
@@ -35,9 +39,12 @@ struct angles_lds {
     uint8_t nsc[FCZ_N_RES_CODES];                                  // side-chain torsion bytes of the code: natoms - 3
 };
 
-// all rows of entry e: rows_total rows at row `row_base` of the output (padded: L rows at e * L; packed: the entry's own at res_off[e])
+// all rows of entry e: rows_total rows at row `row_base` of the output (padded: L rows at e * L; packed: the entry's own at res_off[e]).
+// WIN: row l holds residue min(start, ne) + l, and aatype (may be NULL) receives min(code, 20) per residue row, 20 per padding row.
+template <bool WIN>
 __device__ __forceinline__ void angles_entry(angles_lds& S, const uint32_t wave, const uint32_t lane, const uint8_t* __restrict__ rec, uint32_t ne,
-                                             const uint32_t rows_total, const uint64_t row_base, float* __restrict__ angles, uint8_t* __restrict__ mask) {
+                                             const uint32_t rows_total, const uint64_t row_base, float* __restrict__ angles, uint8_t* __restrict__ mask,
+                                             const uint32_t start = 0, uint8_t* __restrict__ aatype = nullptr) {
     float* sv = S.val[wave];
     uint8_t* sm = S.msk[wave];
     float* const A = angles + row_base * (uint64_t)AN_COLS;
@@ -53,10 +60,24 @@ __device__ __forceinline__ void angles_entry(angles_lds& S, const uint32_t wave,
     }
     const uint8_t* words = rec + v.L.o_words;
     const uint8_t* scb = rec + v.L.o_sc;
-    const uint32_t len = ne < rows_total ? ne : rows_total;        // rows that hold a residue (padded: cropped to L)
+    const uint32_t w0 = WIN ? (start < ne ? start : ne) : 0u;      // first residue of the window: w0 + l never wraps
+    const uint32_t len = ne - w0 < rows_total ? ne - w0 : rows_total;   // rows that hold a residue (padded: cropped to L)
     const float cont = (180.0f - (-180.0f)) / 255.0f;              // FixedAngleDiscretizer(255), src/discretizer.h:89-106
     uint32_t run = 0;                                              // torsion bytes of the residues in front of the tile
-    uint32_t carry_lo = 0, carry_hi = 0;                           // word l0 - 1
+    uint32_t carry_lo = 0, carry_hi = 0;                           // word w0 + l0 - 1
+    if constexpr (WIN) {
+        for (uint32_t k0 = 0; k0 < w0; k0 += AN_TILE) {            // the residues in front of the window: their codes only
+            const uint32_t k = k0 + lane;
+            uint32_t na = 0;
+            if (k < w0) {
+                uint32_t rc = k == 0 ? rc_first : (uint32_t)words[8 * (size_t)k] >> 3;
+                if (rc >= 24u) rc = 23u;
+                na = S.nsc[rc];
+            }
+            run += wave_sum(na);
+        }
+        if (w0 >= 1u) { const uint64_t c = ld_u64(words + 8 * (size_t)(w0 - 1u)); carry_lo = (uint32_t)c; carry_hi = (uint32_t)(c >> 32); }
+    }
     for (uint32_t l0 = 0; l0 < rows_total; l0 += AN_TILE) {
         const uint32_t rows = rows_total - l0 < AN_TILE ? rows_total - l0 : AN_TILE;
         float* const At = A + (uint64_t)l0 * AN_COLS;
@@ -64,10 +85,11 @@ __device__ __forceinline__ void angles_entry(angles_lds& S, const uint32_t wave,
         if (l0 >= len) {   // padding only: constants, no loads
             dn_emit(At, rows * AN_COLS, [](uint32_t) { return 0.0f; }, lane, WAVE);
             dn_emit(Mt, rows * AN_COLS, [](uint32_t) { return (uint8_t)0; }, lane, WAVE);
+            if constexpr (WIN) { if (aatype && lane < rows) aatype[row_base + l0 + lane] = 20; }
             continue;
         }
-        const uint32_t l = l0 + lane;
-        const bool has = l < len;
+        const uint32_t l = w0 + l0 + lane;                         // residue of the lane
+        const bool has = l0 + lane < len;
         const uint64_t w = has ? ld_u64(words + 8 * (size_t)l) : 0ull;
         const uint32_t w_lo = (uint32_t)w, w_hi = (uint32_t)(w >> 32);
         uint32_t p_lo = (uint32_t)__shfl_up((int)w_lo, 1, WAVE), p_hi = (uint32_t)__shfl_up((int)w_hi, 1, WAVE);
@@ -103,6 +125,7 @@ __device__ __forceinline__ void angles_entry(angles_lds& S, const uint32_t wave,
             sv[lane * AN_COLS + c] = on[c] ? val[c] : 0.0f;
             sm[lane * AN_COLS + c] = on[c] ? (uint8_t)1 : (uint8_t)0;
         }
+        if constexpr (WIN) { if (aatype && lane < rows) aatype[row_base + l0 + lane] = (uint8_t)(has && rc < 20u ? rc : 20u); }
         wave_sync();                       // the rows of all lanes are in LDS
         dn_emit(At, rows * AN_COLS, [&](uint32_t t) { return sv[t]; }, lane, WAVE);
         dn_emit(Mt, rows * AN_COLS, [&](uint32_t t) { return sm[t]; }, lane, WAVE);
@@ -110,9 +133,10 @@ __device__ __forceinline__ void angles_entry(angles_lds& S, const uint32_t wave,
     }
 }
 
-template <bool PACKED>
+template <bool PACKED, bool WIN = false>
 __device__ __forceinline__ void angles_grid(const uint8_t* __restrict__ blob, const uint64_t* __restrict__ off, const uint32_t* __restrict__ res_off,
-                                            uint32_t n_entries, uint32_t L, float* __restrict__ angles, uint8_t* __restrict__ mask) {
+                                            uint32_t n_entries, uint32_t L, float* __restrict__ angles, uint8_t* __restrict__ mask,
+                                            const uint32_t* __restrict__ start = nullptr, uint8_t* __restrict__ aatype = nullptr) {
     __shared__ angles_lds S;
     const uint32_t tid = threadIdx.x, lane = tid & 63u;
     const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6));
@@ -126,7 +150,8 @@ __device__ __forceinline__ void angles_grid(const uint8_t* __restrict__ blob, co
     for (uint64_t e = (uint64_t)blockIdx.x * WAVES_PER_BLOCK + wave; e < n_entries; e += n_waves) {
         const uint32_t r0 = res_off[e], ne = res_off[e + 1] - r0;
         if (PACKED && ne == 0u) continue;                          // a skipped entry has no row
-        angles_entry(S, wave, lane, blob + off[e], ne, PACKED ? ne : L, PACKED ? (uint64_t)r0 : e * (uint64_t)L, angles, mask);
+        if constexpr (WIN) angles_entry<true>(S, wave, lane, blob + off[e], ne, L, e * (uint64_t)L, angles, mask, start ? start[e] : 0u, aatype);
+        else angles_entry<false>(S, wave, lane, blob + off[e], ne, PACKED ? ne : L, PACKED ? (uint64_t)r0 : e * (uint64_t)L, angles, mask);
     }
 }
 
@@ -137,6 +162,11 @@ __global__ __launch_bounds__(BLOCK) void k_angles(const uint8_t* __restrict__ bl
 __global__ __launch_bounds__(BLOCK) void k_angles_packed(const uint8_t* __restrict__ blob, const uint64_t* __restrict__ off, const uint32_t* __restrict__ res_off,
                                                          uint32_t n_entries, float* __restrict__ angles, uint8_t* __restrict__ mask) {
     angles_grid<true>(blob, off, res_off, n_entries, 0u, angles, mask);
+}
+__global__ __launch_bounds__(BLOCK) void k_angles_window(const uint8_t* __restrict__ blob, const uint64_t* __restrict__ off, const uint32_t* __restrict__ res_off,
+                                                         uint32_t n_entries, uint32_t L, const uint32_t* __restrict__ start, float* __restrict__ angles,
+                                                         uint8_t* __restrict__ mask, uint8_t* __restrict__ aatype) {
+    angles_grid<false, true>(blob, off, res_off, n_entries, L, angles, mask, start, aatype);
 }
 
 }  // namespace fcz

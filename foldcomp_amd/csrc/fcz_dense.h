@@ -15,6 +15,7 @@
 //                source of slot (l, a) is then LDS[first_atom[l] + inv[res_code[l]][a]]; inv is the constant table the host
 //                builds for the layout and the decode order (fcz_dense_slot) and hands over by value.
 //                A tile past the entry's end (padding, a skipped entry) loads two offsets and stores constants.
+//   k_dense_window<A>   the same tile loop with the entry's row origin moved by a per-entry start (a crop at an offset), below.
 //
 // The per-residue first-atom offset is not taken from a pass of its own: that pass needs a buffer of one word per residue of the
 // batch, and the device entry point knows the batch's residue count only on the device (no synchronisation on this path). The
@@ -81,9 +82,11 @@ template <class T, class F> __device__ __forceinline__ void dn_emit(T* p, uint32
     if (idx < count - tail0) p[tail0 + idx] = val(tail0 + idx);
 }
 
-template <int A>
-__global__ __launch_bounds__(BLOCK) void k_dense(const uint8_t* __restrict__ blob, dense_args g, uint32_t n_entries, uint32_t L,
-                                                 uint32_t tiles_per_entry, uint64_t n_tiles, dense_table tab) {
+// the tile loop of k_dense (WIN = false: start is not read) and of k_dense_window (WIN = true: row l of entry e holds residue
+// w0 + l, w0 = min(start[e], the entry's length); start == NULL is all zeros)
+template <int A, bool WIN>
+__device__ __forceinline__ void dense_tiles(const uint8_t* __restrict__ blob, const dense_args g, const uint32_t* __restrict__ start, uint32_t L,
+                                            uint32_t tiles_per_entry, uint64_t n_tiles, const dense_table tab) {
     __shared__ float s_xyz[3][DN_MAX_ATOMS + 1];
     __shared__ uint32_t s_pk[DN_TILE];                 // tile-local first atom | residue code << 16
     __shared__ uint32_t s_part[WAVES_PER_BLOCK + 1];   // per-wave sums of the atoms in front of the tile; [4] = atoms of the tile
@@ -97,7 +100,10 @@ __global__ __launch_bounds__(BLOCK) void k_dense(const uint8_t* __restrict__ blo
         const uint32_t e = (uint32_t)(tile / tiles_per_entry);
         const uint32_t l0 = (uint32_t)(tile - (uint64_t)e * tiles_per_entry) * DN_TILE;
         const uint32_t r0 = g.res_off[e], ne = g.res_off[e + 1] - r0;
-        const uint32_t len = ne < L ? ne : L;                                  // rows of the entry that hold a residue (cropped to L)
+        // first residue of the window, clamped to the entry's length: w0 + l never wraps, a start at or behind the end leaves padding only
+        uint32_t w0 = 0;
+        if constexpr (WIN) { w0 = start ? start[e] : 0u; if (w0 > ne) w0 = ne; }
+        const uint32_t len = ne - w0 < L ? ne - w0 : L;                      // rows of the entry that hold a residue (cropped to L)
         const uint32_t rows = L - l0 < DN_TILE ? L - l0 : DN_TILE;             // rows of the tile
         const uint32_t nv = l0 < len ? (len - l0 < DN_TILE ? len - l0 : DN_TILE) : 0u;   // of them, rows that hold a residue
         const uint64_t row0 = (uint64_t)e * L + l0;
@@ -116,13 +122,13 @@ __global__ __launch_bounds__(BLOCK) void k_dense(const uint8_t* __restrict__ blo
         }
         // atoms of the entry in front of the tile (block sum), first atom of every residue of the tile (scan by wavefront 0)
         uint32_t part = 0;
-        for (uint32_t k = tid; k < l0; k += BLOCK) { const uint32_t rc = g.res_code[r0 + k]; part += s_na[rc < 24u ? rc : 23u]; }
+        for (uint32_t k = tid; k < w0 + l0; k += BLOCK) { const uint32_t rc = g.res_code[r0 + k]; part += s_na[rc < 24u ? rc : 23u]; }
         part = wave_sum(part);
         if (lane == 0) s_part[wave] = part;
         uint32_t my_rc = 23;
         if (wave == 0) {
             uint32_t na = 0;
-            if (lane < nv) { my_rc = g.res_code[r0 + l0 + lane]; if (my_rc >= 24u) my_rc = 23u; na = s_na[my_rc]; }
+            if (lane < nv) { my_rc = g.res_code[r0 + w0 + l0 + lane]; if (my_rc >= 24u) my_rc = 23u; na = s_na[my_rc]; }
             uint32_t tot;
             const uint32_t ex = wave_excl_scan(na, (int)lane, &tot);
             s_pk[lane] = ex | (my_rc << 16);
@@ -140,7 +146,7 @@ __global__ __launch_bounds__(BLOCK) void k_dense(const uint8_t* __restrict__ blo
         }
         // the chain's OXT: the decoder's last atom when the entry has one more atom than its residues own; slot 36 of the last
         // residue in atom37, no slot elsewhere (and none when the crop dropped the last residue)
-        const bool last_here = l0 + nv == ne;
+        const bool last_here = w0 + l0 + nv == ne;
         const bool oxt = A == 37 && last_here && aend - a0 == pre + count + 1u;
         const uint32_t oxt_row = oxt ? nv - 1u : 0xFFFFFFFFu;
         if (oxt && tid < 3) s_xyz[tid][DN_MAX_ATOMS] = (tid == 0 ? g.x : tid == 1 ? g.y : g.z)[aend - 1u];
@@ -165,11 +171,28 @@ __global__ __launch_bounds__(BLOCK) void k_dense(const uint8_t* __restrict__ blo
         if (tid < rows) {   // wavefront 0: lane = row, my_rc is the row's residue code
             const bool res = tid < nv;
             if (g.aatype) g.aatype[row0 + tid] = (uint8_t)(res && my_rc < 20u ? my_rc : 20u);
-            if (g.plddt) g.plddt[row0 + tid] = res ? g.bfac[r0 + l0 + tid] : 0.0f;
-            if (g.res_index) g.res_index[row0 + tid] = res ? (int32_t)(ld_u16(blob + g.off[e] + 8) + l0 + tid) : 0;
+            if (g.plddt) g.plddt[row0 + tid] = res ? g.bfac[r0 + w0 + l0 + tid] : 0.0f;
+            if (g.res_index) g.res_index[row0 + tid] = res ? (int32_t)(ld_u16(blob + g.off[e] + 8) + w0 + l0 + tid) : 0;
         }
         __syncthreads();   // the next tile rewrites the staging
     }
+}
+
+template <int A>
+__global__ __launch_bounds__(BLOCK) void k_dense(const uint8_t* __restrict__ blob, dense_args g, uint32_t n_entries, uint32_t L,
+                                                 uint32_t tiles_per_entry, uint64_t n_tiles, dense_table tab) {
+    dense_tiles<A, false>(blob, g, nullptr, L, tiles_per_entry, n_tiles, tab);
+}
+
+//   k_dense_window<A>   k_dense with a per-entry row origin (include/fcz_hip.h, fcz_dense_window_dev): the tile is still 64 output
+//                       rows of one entry and one contiguous byte range of every output array; the residues read, the block's prefix
+//                       sum in front of the tile and the test for the chain's last residue move by start[e]. The prefix now runs over
+//                       start + l0 bytes whatever l0 is: a window at the end of a 2 700-residue chain reads 2.7 KB of residue codes
+//                       per tile from L2, 9 % of the tile's 30 KB of stores.
+template <int A>
+__global__ __launch_bounds__(BLOCK) void k_dense_window(const uint8_t* __restrict__ blob, dense_args g, const uint32_t* __restrict__ start,
+                                                        uint32_t n_entries, uint32_t L, uint32_t tiles_per_entry, uint64_t n_tiles, dense_table tab) {
+    dense_tiles<A, true>(blob, g, start, L, tiles_per_entry, n_tiles, tab);
 }
 
 // ---- packed form: rows of all entries back to back, no padding (include/fcz_hip.h, fcz_packed_out) ----------------------------

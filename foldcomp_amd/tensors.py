@@ -7,6 +7,9 @@
     encode_tensors(either dict, or the tensors as keywords) -> [fcz, ...]
     decode_angles(entries) -> dict(angles [n, L, 10] float32 degrees, angle_mask [n, L, 10] bool, aatype [n, L] uint8, length [n] int32,
                                    names list[str]); packed=True: angles [R, 10], angle_mask [R, 10], aatype [R], cu_seqlens, max_seqlen
+    decode_tensors / decode_angles(entries, max_len=L, crop="start" | "center" | "random" | starts [n]) -> the same padded dicts
+                                   with row l of entry e = its residue crop_start[e] + l, plus crop_start [n] int32
+    crop_starts(length, L, how, generator) -> the starts of such a crop, on the device the lengths lie on
 
 What a structure model's data loader wants from a Foldcomp database (atom37 / atom14 coordinates with a mask, residue types,
 pLDDT), without the PDB text `foldcomp.decompress` returns and without a host copy of the result: the records go up once, torch
@@ -29,7 +32,47 @@ from ._aa_tables import RES1
 from .codec import ANGLE_COLUMNS, Codec, dense_layout
 from .structure import CAtomsOut, CDenseIn, CDenseOut, CPackedOut
 
-__all__ = ["decode_tensors", "encode_tensors", "decode_angles"]
+__all__ = ["decode_tensors", "encode_tensors", "decode_angles", "crop_starts"]
+
+
+def crop_starts(length, L: int, how, generator=None):
+    """first kept residue of every entry for a window of L rows -> int32 tensor [n] on the device of `length` (torch tensor [n] of
+    residue counts, any device, `cpu` included). Pure: no codec, no host copy of a device tensor.
+
+    how: "start": 0; "center": max(len - L, 0) // 2; "random": uniform over the integers 0 .. max(len - L, 0), drawn from
+    `generator` (a torch.Generator on any device; None: torch's default one of the lengths' device) -- an entry no longer than L
+    starts at 0; or the starts themselves, an integer tensor / array / sequence [n]: a negative one is a ValueError where the
+    values lie on the host, and values on a device are clamped to 0 .. 2^31 - 1 unseen (a start at or behind the entry's length
+    gives padding only, so the upper clamp changes nothing)."""
+    import torch
+    n = int(length.shape[0])
+    L = int(L)
+    if L < 1:
+        raise ValueError("max_len must be at least 1")
+    if not isinstance(how, str):
+        if isinstance(how, torch.Tensor):
+            st, on_host, integers = how, how.device.type == "cpu", not (how.dtype.is_floating_point or how.dtype.is_complex or how.dtype == torch.bool)
+        else:
+            a = np.asarray(how)
+            integers = a.dtype.kind in "iu"
+            st, on_host = torch.from_numpy(np.minimum(a, 2 ** 31 - 1).astype(np.int64) if integers else np.zeros(a.shape)), True
+        if tuple(st.shape) != (n,) or not integers:
+            raise ValueError(f"crop must be {n} integer starts, one per entry, not {getattr(how, 'dtype', type(how).__name__)} {tuple(st.shape)}")
+        if on_host and n and bool((st < 0).any()):
+            raise ValueError("crop starts must not be negative")
+        return st.to(length.device).clamp(0, 2 ** 31 - 1).to(torch.int32).contiguous()
+    if how not in api.CROP_MODES:
+        raise ValueError(f"crop must be one of {api.CROP_MODES} or per-entry starts [n], not {how!r}")
+    span = (length.to(torch.int64) - L).clamp_(min=0)                       # the last start that keeps the window inside the entry
+    if how == "start":
+        st = torch.zeros_like(span)
+    elif how == "center":
+        st = span // 2
+    else:
+        gdev = generator.device if generator is not None else length.device
+        u = torch.rand(n, generator=generator, dtype=torch.float64, device=gdev).to(length.device)
+        st = torch.minimum((u * (span + 1).to(torch.float64)).floor().to(torch.int64), span)   # (u < 1: the minimum guards the rounding alone)
+    return st.to(torch.int32).contiguous()
 
 
 def _torch_device(device):
@@ -77,12 +120,22 @@ def _upload_and_size(c, torch, dev, entries):
     return blob_t, off_t, res_off_t, atom_off_t, int(R.value), int(M.value)
 
 
-def _angles_into(c, torch, dev, n, blob_t, off_t, res_off_t, L, R=None):
+def _angles_into(c, torch, dev, n, blob_t, off_t, res_off_t, L, R=None, start_t=None, aatype=False):
     """the angle tensors of a sized batch (fcz_angles_dev, or fcz_angles_packed_dev when R is given), enqueued on the codec's stream:
-    the caller synchronises. It reads the records and res_off only, and leaves the sizes memo to the decode that may follow."""
+    the caller synchronises. It reads the records and res_off only, and leaves the sizes memo to the decode that may follow.
+    Padded, with start_t (int32 [n] on dev) or aatype=True: fcz_angles_window_dev, the dict then holds `aatype` [n, L] too."""
     shape = (R, len(ANGLE_COLUMNS)) if R is not None else (n, L, len(ANGLE_COLUMNS))
     ang = torch.empty(shape, dtype=torch.float32, device=dev)
     msk = torch.empty(shape, dtype=torch.uint8, device=dev)
+    if R is None and (start_t is not None or aatype):
+        aa = torch.full((n, L), 20, dtype=torch.uint8, device=dev) if aatype else None
+        if ang.numel():
+            torch.cuda.current_stream(dev).synchronize()
+            _lib.check(c.lib.fcz_angles_window_dev(c.ctx, blob_t.data_ptr(), off_t.data_ptr(), n, res_off_t.data_ptr(), L,
+                                                   None if start_t is None else start_t.data_ptr(), ang.data_ptr(), msk.data_ptr(),
+                                                   None if aa is None else aa.data_ptr()), "fcz_angles_window_dev")
+        d = dict(angles=ang, angle_mask=msk.view(torch.bool))
+        return dict(d, aatype=aa) if aatype else d
     if ang.numel():
         torch.cuda.current_stream(dev).synchronize()
         if R is not None:
@@ -104,8 +157,13 @@ def _aatype_rows(entry: bytes, n_res: int) -> np.ndarray:
     return np.minimum(rc, 20).astype(np.uint8)
 
 
+def _entry_lengths(res_off_t):
+    """residue counts [n] int32 on the device: the diff of the res_off that is there already (uint32 bits; a count fits 16)"""
+    return res_off_t[1:] - res_off_t[:-1]
+
+
 def decode_angles(entries: Sequence[bytes], *, max_len: Optional[int] = None, packed: bool = False, device="cuda:0",
-                  codec: Optional[Codec] = None) -> dict:
+                  codec: Optional[Codec] = None, crop=None, generator=None) -> dict:
     """[fcz, ...] -> the records' internal coordinates as torch tensors on `device`, without reconstructing an atom: the sizes pass
     and fcz_angles_dev only (include/fcz_hip.h).
 
@@ -118,10 +176,16 @@ def decode_angles(entries: Sequence[bytes], *, max_len: Optional[int] = None, pa
     no padding, no crop, no max_len. An entry that does not decode has length 0 and no value. Argument errors and the ordering
     against torch are decode_tensors'.
 
-    Host work: the angles never visit the host, but `names` and `aatype` are read from the record bytes here, one record at a time
-    in Python (a header parse and one byte per residue, uploaded as one array). For large batches that loop, not the kernel, is
-    what the call costs; a loader that has aatype already, or wants the angles beside coordinates, takes decode_tensors(angles=True),
-    whose aatype comes from the decode."""
+    crop (with max_len=L, not with packed): "start", "center", "random" (drawn from `generator`, a torch.Generator) or the starts
+    [n] themselves, as crop_starts takes them: row l of entry e then holds its residue crop_start[e] + l, bit for bit the row the
+    uncropped call gives it (row 0 of a window that starts inside the chain has phi and N-CA-C), and the dict gains crop_start
+    [n] int32. The starts are computed on the device from res_off.
+
+    Host work: the angles never visit the host. In the padded form aatype is written by the angle kernel itself
+    (fcz_angles_window_dev) and only `names` is read from the record headers in Python. The packed form still reads aatype from
+    the record bytes here, one record at a time (one byte per residue, uploaded as one array): for large packed batches that
+    loop, not the kernel, is what the call costs, and decode_tensors(packed=True, angles=True) takes aatype from the decode."""
+    api.check_crop(crop, max_len, packed)
     torch, dev = _torch_device(device)
     c = codec or api.default_codec()
     if int(c.device) != dev.index:
@@ -141,34 +205,36 @@ def decode_angles(entries: Sequence[bytes], *, max_len: Optional[int] = None, pa
                         aatype=torch.empty(0, dtype=torch.uint8, device=dev), length=length, names=names,
                         cu_seqlens=torch.zeros(1, dtype=torch.int32, device=dev), max_seqlen=0)
         L = int(max_len or 0)
-        return dict(angles=torch.empty((0, L, W), dtype=torch.float32, device=dev), angle_mask=torch.empty((0, L, W), dtype=torch.bool, device=dev),
-                    aatype=torch.empty((0, L), dtype=torch.uint8, device=dev), length=length, names=names)
+        d = dict(angles=torch.empty((0, L, W), dtype=torch.float32, device=dev), angle_mask=torch.empty((0, L, W), dtype=torch.bool, device=dev),
+                 aatype=torch.empty((0, L), dtype=torch.uint8, device=dev), length=length, names=names)
+        return d if crop is None else dict(d, crop_start=crop_starts(length, L, crop, generator))
     blob_t, off_t, res_off_t, _, R, _ = _upload_and_size(c, torch, dev, entries)
     if packed and R > 2 ** 31 - 1:
         raise api.error(f"decode_angles: {R} residues do not fit the int32 cu_seqlens; split the batch")
+    if not packed:
+        length = _entry_lengths(res_off_t)
+        L = int(length.max()) if max_len is None else int(max_len)         # (no max_len: one word comes back)
+        start_t = None if crop is None else crop_starts(length, L, crop, generator)
+        d = _angles_into(c, torch, dev, n, blob_t, off_t, res_off_t, L, start_t=start_t, aatype=True)
+        d.update(length=length, names=names)
+        if crop is not None:
+            d["crop_start"] = start_t
+        c.synchronize()
+        return d
     ro = res_off_t.cpu().numpy().view(np.uint32).astype(np.int64)          # n + 1 offsets: the only words that come back
     lens = np.diff(ro)
-    L = int(lens.max()) if max_len is None else int(max_len)
-    if packed:
-        aatype = np.zeros(R, np.uint8)
-        for e, k, r0 in zip(entries, lens, ro):
-            aatype[r0:r0 + k] = _aatype_rows(e, int(k)) if k else 0
-        d = _angles_into(c, torch, dev, n, blob_t, off_t, res_off_t, 0, R)
-        d.update(cu_seqlens=res_off_t, max_seqlen=int(lens.max()))
-    else:
-        aatype = np.full((n, L), 20, np.uint8)
-        for i, (e, k) in enumerate(zip(entries, lens)):
-            k = min(int(k), L)
-            if k:
-                aatype[i, :k] = _aatype_rows(e, k)
-        d = _angles_into(c, torch, dev, n, blob_t, off_t, res_off_t, L)
+    aatype = np.zeros(R, np.uint8)
+    for e, k, r0 in zip(entries, lens, ro):
+        aatype[r0:r0 + k] = _aatype_rows(e, int(k)) if k else 0
+    d = _angles_into(c, torch, dev, n, blob_t, off_t, res_off_t, 0, R)
+    d.update(cu_seqlens=res_off_t, max_seqlen=int(lens.max()))
     d.update(aatype=torch.from_numpy(aatype).to(dev), length=torch.from_numpy(lens.astype(np.int32)).to(dev), names=names)
     c.synchronize()
     return d
 
 
 def decode_tensors(entries: Sequence[bytes], *, layout="atom37", max_len: Optional[int] = None, device="cuda:0",
-                   codec: Optional[Codec] = None, packed: bool = False, angles: bool = False) -> dict:
+                   codec: Optional[Codec] = None, packed: bool = False, angles: bool = False, crop=None, generator=None) -> dict:
     """[fcz, ...] -> dict of torch tensors on `device` plus `names` (the records' titles, a Python list).
 
     layout: "atom37" (A = 37, AlphaFold / OpenFold atom order, the chain's OXT in slot 36 of its last residue), "atom14" (A = 14,
@@ -183,10 +249,19 @@ def decode_tensors(entries: Sequence[bytes], *, layout="atom37", max_len: Option
     e), length [n], names and max_seqlen (a Python int). R counts the residues of the entries that decode: one that does not has no
     row (length 0). Nothing is padded or cropped, so max_len with packed=True is a ValueError.
 
+    crop (with max_len=L; a ValueError without it or with packed=True) keeps a window of L residues at an offset instead of the
+    first L: "start" (offset 0), "center" (max(len - L, 0) // 2), "random" (uniform over 0 .. max(len - L, 0), drawn from
+    `generator`, a torch.Generator) or the starts [n] themselves (crop_starts). Row l of entry e then holds its residue
+    crop_start[e] + l -- bit for bit the row the uncropped call gives that residue -- or padding when the entry has no such
+    residue; the OXT appears only in a window that reaches the chain's last residue, res_index counts on from the start, `length`
+    stays the full size, and the dict gains crop_start [n] int32. The starts are computed on the device from res_off
+    (fcz_dense_window_dev reads them there); with angles=True both calls use the same starts. crop=None: the dict has no new key.
+
     Ordering against torch: the uploads and allocations are made on torch's current stream, which is synchronised before the
     codec's calls; the codec works on its own stream, which is synchronised before the tensors are returned. No output byte
     visits the host.
     """
+    api.check_crop(crop, max_len, packed)
     torch, dev = _torch_device(device)
     c = codec or api.default_codec()
     if int(c.device) != dev.index:
@@ -228,6 +303,8 @@ def decode_tensors(entries: Sequence[bytes], *, layout="atom37", max_len: Option
             return dict(d, **no_angles(0)) if angles else d
         L = int(max_len or 0)
         d = result(L, *alloc(L))
+        if crop is not None:
+            d["crop_start"] = crop_starts(d["length"], L, crop, generator)
         return dict(d, **no_angles(0, L)) if angles else d
     blob_t, off_t, res_off_t, atom_off_t, Rv, Mv = _upload_and_size(c, torch, dev, entries)
     R, M = ctypes.c_uint32(Rv), ctypes.c_uint32(Mv)
@@ -244,7 +321,10 @@ def decode_tensors(entries: Sequence[bytes], *, layout="atom37", max_len: Option
     out = alloc(L)
     if L == 0:                                                             # nothing decodes and no width was asked for
         return dict(result(L, *out), **no_angles(n, 0)) if angles else result(L, *out)
-    extra = _angles_into(c, torch, dev, n, blob_t, off_t, res_off_t, L) if angles else {}
+    start_t = None if crop is None else crop_starts(_entry_lengths(res_off_t), L, crop, generator)
+    extra = _angles_into(c, torch, dev, n, blob_t, off_t, res_off_t, L, start_t=start_t) if angles else {}
+    if crop is not None:
+        extra["crop_start"] = start_t
     x, y, z = (torch.empty(max(M.value, 1), dtype=torch.float32, device=dev) for _ in range(3))
     bfac = torch.empty(max(R.value, 1), dtype=torch.float32, device=dev)
     res_code = torch.empty(max(R.value, 1), dtype=torch.uint8, device=dev)
@@ -254,8 +334,12 @@ def decode_tensors(entries: Sequence[bytes], *, layout="atom37", max_len: Option
     if R.value:
         _lib.check(c.lib.fcz_decompress_batch_dev(c.ctx, blob_t.data_ptr(), off_t.data_ptr(), n, res_off_t.data_ptr(), atom_off_t.data_ptr(),
                                                   0, ctypes.byref(atoms)), "fcz_decompress_batch_dev")
-    _lib.check(c.lib.fcz_dense_dev(c.ctx, blob_t.data_ptr(), off_t.data_ptr(), n, res_off_t.data_ptr(), atom_off_t.data_ptr(),
-                                   ctypes.byref(atoms), 0, lay, L, ctypes.byref(dense)), "fcz_dense_dev")
+    if crop is None:
+        _lib.check(c.lib.fcz_dense_dev(c.ctx, blob_t.data_ptr(), off_t.data_ptr(), n, res_off_t.data_ptr(), atom_off_t.data_ptr(),
+                                       ctypes.byref(atoms), 0, lay, L, ctypes.byref(dense)), "fcz_dense_dev")
+    else:
+        _lib.check(c.lib.fcz_dense_window_dev(c.ctx, blob_t.data_ptr(), off_t.data_ptr(), n, res_off_t.data_ptr(), atom_off_t.data_ptr(),
+                                              ctypes.byref(atoms), 0, lay, L, start_t.data_ptr(), ctypes.byref(dense)), "fcz_dense_window_dev")
     c.synchronize()
     return dict(result(L, *out), **extra)
 

@@ -15,8 +15,10 @@
  *   Foldcomp::decompress(vector<AtomCoordinate>&)          fcz_decompress_batch / fcz_decompress_batch_dev
  *     src/foldcomp.cpp:779
  *   Foldcomp::checkValidity()        src/foldcomp.cpp:1492   fcz_check
- *   (none: the reference stops at the flat atom vector)    fcz_dense_dev / fcz_decompress_dense, fcz_dense_packed_dev / fcz_decompress_dense_packed
- *   Foldcomp::decompress, the dequantisation :784-804     fcz_angles_dev / fcz_angles_packed_dev, fcz_decompress_angles[_packed]
+ *   (none: the reference stops at the flat atom vector)    fcz_dense_dev / fcz_decompress_dense, fcz_dense_packed_dev / fcz_decompress_dense_packed,
+ *                                                          fcz_dense_window_dev / fcz_decompress_dense_window
+ *   Foldcomp::decompress, the dequantisation :784-804     fcz_angles_dev / fcz_angles_packed_dev, fcz_decompress_angles[_packed],
+ *                                                          fcz_angles_window_dev / fcz_decompress_angles_window
  *     (get_data's FCZ branch, foldcomp/foldcomp.cxx)
  *   (none: Foldcomp::compress starts from the flat list)   fcz_undense_dev / fcz_compress_dense_begin[_dev], fcz_undense_packed_dev /
  *                                                          fcz_compress_dense_packed_begin[_dev]
@@ -289,6 +291,26 @@ int fcz_dense_dev(fcz_ctx* ctx, const uint8_t* blob_dev, const uint64_t* off_dev
 int fcz_decompress_dense(fcz_ctx* ctx, const uint8_t* blob, const uint64_t* off, uint32_t n, int layout, uint32_t L,
                          uint32_t* L_out, const fcz_dense_out* out, int32_t* status);
 
+/* ---- a per-entry residue window of the padded tensors: a crop at an offset ------------------------------ */
+/* Beside fcz_dense_dev, which can only keep an entry's FIRST L residues (like it, beside Foldcomp::decompress, src/foldcomp.cpp:779;
+ * the reference has no dense output and no crop). start_dev[e] (uint32, device data, [n]) is the first residue of entry e that is
+ * kept: row l of the output holds residue start[e] + l when that is below the entry's length, and is a padding row otherwise. A row
+ * that holds a residue equals, bit for bit, row start[e] + l of what fcz_dense_dev writes at L = the longest entry; a padding row is
+ * its padding row. So the atom37 OXT (slot 36) appears only when the window contains the entry's last residue, res_index is
+ * first_res_index + start[e] + l, and length[e] stays the UNCROPPED residue count. start[e] >= length is no error (the starts are
+ * device data: no entry point can check them on the host): all L rows are padding, 0xFFFFFFFF included -- start[e] + l never wraps.
+ * A skipped entry is padding only. start_dev == NULL means all zeros: the output is then byte-identical to fcz_dense_dev's.
+ * Arguments, refusals, stream and sizes are fcz_dense_dev's; the time goes to its "dense" group. */
+int fcz_dense_window_dev(fcz_ctx* ctx, const uint8_t* blob_dev, const uint64_t* off_dev, uint32_t n,
+                         const uint32_t* res_off_dev, const uint32_t* atom_off_dev, const fcz_atoms_out* atoms_dev, int alt_order,
+                         int layout, uint32_t L, const uint32_t* start_dev, const fcz_dense_out* out_dev);
+/* Host-pointer convenience, beside fcz_decompress_dense and shaped like it (Foldcomp::read + Foldcomp::decompress,
+ * src/foldcomp.cpp:904 / :779, for every entry): start[n] is a host array (NULL: all zeros). L = 0 is the longest entry of the
+ * batch, the width used comes back through *L_out, and a first call with out = NULL sizes the arrays. Refusals are
+ * fcz_decompress_dense's. */
+int fcz_decompress_dense_window(fcz_ctx* ctx, const uint8_t* blob, const uint64_t* off, uint32_t n, int layout, uint32_t L,
+                                const uint32_t* start, uint32_t* L_out, const fcz_dense_out* out, int32_t* status);
+
 /* ---- packed dense tensors: rows of all entries back to back, no padding ------------------------------ */
 /* The same tensors for a batch of mixed lengths, as varlen models and token-budget loaders read them: no common L, no padding row
  * and no crop. Like the padded form they stand beside Foldcomp::decompress (src/foldcomp.cpp:779); the reference has no such output.
@@ -372,6 +394,22 @@ int fcz_decompress_angles(fcz_ctx* ctx, const uint8_t* blob, const uint64_t* off
                           float* angles, uint8_t* mask, int32_t* status);
 int fcz_decompress_angles_packed(fcz_ctx* ctx, const uint8_t* blob, const uint64_t* off, uint32_t n, uint32_t* R_out, uint32_t* row_off,
                                  float* angles, uint8_t* mask, int32_t* status);
+/* The per-entry residue window of the padded angle tensors, beside fcz_angles_dev (the dequantisation of Foldcomp::decompress,
+ * src/foldcomp.cpp:784-804) and with the rule of fcz_dense_window_dev: row l holds residue start_dev[e] + l of entry e, bit for bit
+ * the row fcz_angles_dev writes for that residue at L = the longest entry, or zeros when the entry has no such residue. Row 0 of a
+ * window with start >= 1 therefore HAS phi and N-CA-C (word start - 1 exists), and the last row of a window that ends inside the chain
+ * has psi, omega and the two bond angles behind it. start[e] at or behind the entry's length (0xFFFFFFFF included), or a skipped
+ * entry: all L rows are 0 / 0. start_dev == NULL means all zeros: angles and mask are byte-identical to fcz_angles_dev's.
+ * aatype_dev (may be NULL) receives [n][L] uint8: min(residue code, 20) with the decoder's codes (residue 0: header.firstResidue) in
+ * a residue row, 20 in a padding row -- what fcz_dense_dev writes as aatype, without a decode. Like fcz_angles_dev the call reads
+ * only its arguments; its refusals, stream and "angles" timing group are fcz_angles_dev's. */
+int fcz_angles_window_dev(fcz_ctx* ctx, const uint8_t* blob_dev, const uint64_t* off_dev, uint32_t n, const uint32_t* res_off_dev,
+                          uint32_t L, const uint32_t* start_dev, float* angles_dev, uint8_t* mask_dev, uint8_t* aatype_dev);
+/* Host-pointer convenience, beside fcz_decompress_angles and shaped like it (Foldcomp::read, src/foldcomp.cpp:904, then the
+ * dequantisation of :784-804): start[n] is a host array (NULL: all zeros), aatype [n][L] may be NULL. L = 0 is the longest entry;
+ * angles and mask both NULL: a sizing call (L_out required). Refusals are fcz_decompress_angles'. */
+int fcz_decompress_angles_window(fcz_ctx* ctx, const uint8_t* blob, const uint64_t* off, uint32_t n, uint32_t L, const uint32_t* start,
+                                 uint32_t* L_out, float* angles, uint8_t* mask, uint8_t* aatype, int32_t* status);
 
 /* ---- dense model-input tensors -> fcz_chain_batch -> FCZ records ---------------------------------------- */
 /* The way back: n chains held as the padded arrays above (a model's predictions, a filtered or re-cropped set, what fcz_dense_dev
@@ -601,8 +639,9 @@ int fcz_check(const uint8_t* entry, uint64_t len);
  * group since the last reset: "compress_sizes", "compress_index", "compress_angles", "compress_pack",
  * "decompress_sizes", "decompress_backbone", "decompress_index", "decompress_sidechain", "pdb_sizes", "pdb_format", "extract_sizes", "extract",
  * "ingest_parse", "ingest_parse_cif", "ingest_rows_cif", "ingest_frags", "ingest_fill", "inflate", "dense", "undense" (the counting and the fill
- * kernel of fcz_undense_dev: two launches per call), "angles" (fcz_angles_dev). Every packed entry point is timed under the group
- * of its padded form: fcz_dense_packed_dev under "dense", fcz_undense_packed_dev under "undense", fcz_angles_packed_dev under "angles". */
+ * kernel of fcz_undense_dev: two launches per call), "angles" (fcz_angles_dev). Every packed or windowed entry point is timed under the
+ * group of its padded form: fcz_dense_packed_dev and fcz_dense_window_dev under "dense", fcz_undense_packed_dev under "undense",
+ * fcz_angles_packed_dev and fcz_angles_window_dev under "angles". */
 int  fcz_ctx_enable_timing(fcz_ctx* ctx, int enable);
 int  fcz_ctx_kernel_time(fcz_ctx* ctx, const char* name, double* ms, uint64_t* launches);
 void fcz_ctx_reset_timing(fcz_ctx* ctx);

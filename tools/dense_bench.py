@@ -12,7 +12,12 @@
   4. the packed form (k_dense_packed) on the same two batches in the same process, right behind the padded call
      of every layout: same method, same group "dense", bytes per second beside the same copy figure, and packed over padded time.
 
+  5. the windowed form (k_dense_window) on the mixed batch: atom37, L = 256, random starts (crop_starts with a
+     seeded generator), right behind the L = 1 024 call of fcz_dense_dev in the same process: same method, same group "dense", and
+     windowed over padded time beside the ratio of the bytes the two calls write.
+
     python tools/dense_bench.py --out profiles/dense_layout.json [--lib other/libfcz_hip.so label]
+    python tools/dense_bench.py --skip-user-level --mixed-only --out profiles/dense_window.json
     python tools/dense_bench.py --skip-user-level --out profiles/dense_packed.json
 """
 import argparse
@@ -35,8 +40,8 @@ ATOM37 = ["N", "CA", "C", "CB", "O", "CG", "CG1", "CG2", "OG", "OG1", "SG", "CD"
 LAYOUTS = (("atom37", 0, 37), ("atom14", 1, 14), ("backbone4", 2, 4))
 
 
-def kernel_case(codec, bench, name, n_chains, n_res, mixed, L_cap, dev):
-    from foldcomp_amd import _lib
+def kernel_case(codec, bench, name, n_chains, n_res, mixed, L_cap, dev, window_L=0):
+    from foldcomp_amd import _lib, tensors
     from foldcomp_amd.structure import CDenseOut, CPackedOut
     d = bench.generate_resident(n_chains, n_res, 25, 32768, dev, seed_base=0, mixed=mixed)
     w = bench.Workload(codec, d, dev)
@@ -78,6 +83,39 @@ def kernel_case(codec, bench, name, n_chains, n_res, mixed, L_cap, dev):
                                      share_of_decode_plus_dense=med / (med + decode_ms))
         del pos, mask, aatype, plddt, res_index, length
         torch.cuda.empty_cache()
+        if window_L and lname == "atom37":
+            # a window of window_L rows at a random start per entry, right behind the padded call
+            Lw = int(window_L)
+            gen = torch.Generator(device=dev); gen.manual_seed(1)
+            start = tensors.crop_starts(torch.from_numpy(lens.astype(np.int32)).to(dev), Lw, "random", gen)
+            wo = (torch.empty((n, Lw, A, 3), dtype=torch.float32, device=dev), torch.empty((n, Lw, A), dtype=torch.uint8, device=dev),
+                  torch.empty((n, Lw), dtype=torch.uint8, device=dev), torch.empty((n, Lw), dtype=torch.float32, device=dev),
+                  torch.empty((n, Lw), dtype=torch.int32, device=dev), torch.empty(n, dtype=torch.int32, device=dev))
+            wout = CDenseOut(*(t.data_ptr() for t in wo))
+            torch.cuda.synchronize()
+            wms = []
+            for _ in range(3 + 9):
+                codec.reset_timing()
+                _lib.check(codec.lib.fcz_dense_window_dev(codec.ctx, w.blob_dev.data_ptr(), w.off_dev.data_ptr(), n, w.res_off_dev.data_ptr(),
+                                                          w.atom_off_dev.data_ptr(), ctypes.byref(w.cout), 0, lay, Lw, start.data_ptr(), ctypes.byref(wout)),
+                           "fcz_dense_window_dev")
+                codec.synchronize()
+                wms.append(codec.kernel_time("dense")[0])
+            wmed = statistics.median(wms[3:])
+            st = start.cpu().numpy().astype(np.int64)
+            kept_w = np.minimum(lens - st, Lw)
+            w_kept = int(kept_w.sum())
+            w_written = n * Lw * (A * 13 + 9) + 4 * n
+            # (the prefix in front of a tile: one byte per residue in front of it, per tile that holds a residue)
+            tiles = -(-kept_w // 64)
+            w_prefix = int((st * tiles + 32 * tiles * (tiles - 1)).sum())
+            w_read = 12 * int(wo[1].sum(dtype=torch.int64)) + 5 * w_kept + 12 * n + w_prefix
+            res["layouts"][lname]["window"] = dict(L=Lw, dense_ms=wmed, dense_ms_min=min(wms[3:]), dense_ms_max=max(wms[3:]), bytes_written=w_written,
+                                                   bytes_read=w_read, prefix_bytes_read=w_prefix, gb_per_s=(w_written + w_read) / (wmed * 1e-3) / 1e9,
+                                                   padding_fraction=1.0 - w_kept / (n * Lw), entries_moved=int((st > 0).sum()),
+                                                   time_over_padded=wmed / med, bytes_written_over_padded=w_written / written)
+            del wo, start
+            torch.cuda.empty_cache()
         # the packed form of the same batch: R rows, nothing cropped
         R = int(lens.sum())
         pk = (torch.empty((R, A, 3), dtype=torch.float32, device=dev), torch.empty((R, A), dtype=torch.uint8, device=dev),
@@ -188,6 +226,8 @@ def main():
     ap.add_argument("--skip-user-level", action="store_true")
     ap.add_argument("--db-entries", type=int, default=20000)
     ap.add_argument("--mixed-chains", type=int, default=100000)
+    ap.add_argument("--window-len", type=int, default=256, help="L of the windowed leg on the mixed batch (atom37, random starts); 0 leaves it out")
+    ap.add_argument("--mixed-only", action="store_true", help="leave out the 65 536 x 350 case")
     ap.add_argument("--mixed-max-len", type=int, default=1024, help="L of the mixed batch (longer chains are cropped): 100 000 x 2 700 x 444 B does not fit")
     args = ap.parse_args()
     torch.cuda.init()
@@ -200,12 +240,15 @@ def main():
     _lib.check(codec.lib.fcz_selftest_copy(codec.ctx, ctypes.c_uint64(1 << 30), 10, ctypes.byref(gbs)), "fcz_selftest_copy")
     doc = {"label": args.label, "library": _lib.LIB_PATH if os.environ.get("FCZ_HIP_LIB") else "foldcomp_amd/libfcz_hip.so",
            "device": torch.cuda.get_device_name(0), "copy_ceiling_gb_per_s": gbs.value, "method": "HIP events on the ctx stream, median of 9 after 3 warm-up calls",
-           "kernel": [kernel_case(codec, bench, "65536 x 350", 65536, 350, False, 1 << 30, dev),
-                      kernel_case(codec, bench, f"{args.mixed_chains} mixed (L capped at {args.mixed_max_len})", args.mixed_chains, 0, True, args.mixed_max_len, dev)]}
+           "kernel": ([] if args.mixed_only else [kernel_case(codec, bench, "65536 x 350", 65536, 350, False, 1 << 30, dev)]) +
+                     [kernel_case(codec, bench, f"{args.mixed_chains} mixed (L capped at {args.mixed_max_len})", args.mixed_chains, 0, True, args.mixed_max_len, dev,
+                                  window_L=args.window_len)]}
     for c in doc["kernel"]:
         for v in c["layouts"].values():
             v["fraction_of_copy_ceiling"] = v["gb_per_s"] / gbs.value
             v["packed"]["fraction_of_copy_ceiling"] = v["packed"]["gb_per_s"] / gbs.value
+            if "window" in v:
+                v["window"]["fraction_of_copy_ceiling"] = v["window"]["gb_per_s"] / gbs.value
     if not args.skip_user_level:
         doc["user_level"] = user_level(codec, bench, args.db_entries, dev)
     codec.close()

@@ -6,8 +6,8 @@
 from .api import (FoldcompDatabase, FoldcompError, compress, compress_many, decompress, decompress_many, error, get_data,
                   open, split_pdb_by_chain)
 from .codec import ANGLE_COLUMNS
-from .tensors import decode_angles, decode_tensors, encode_tensors
+from .tensors import decode_angles, decode_tensors, encode_tensors, neighbor_graph
 
 __all__ = ["compress", "decompress", "get_data", "open", "error", "FoldcompError", "FoldcompDatabase", "compress_many",
-           "decompress_many", "split_pdb_by_chain", "decode_tensors", "encode_tensors", "decode_angles",
+           "decompress_many", "split_pdb_by_chain", "decode_tensors", "encode_tensors", "decode_angles", "neighbor_graph",
            "ANGLE_COLUMNS"]

@@ -20,7 +20,7 @@ import numpy as np
 from . import fczfile
 from ._aa_tables import RES1, RES3
 from . import _lib
-from .codec import Codec
+from .codec import Codec, dense_layout
 from .database import DatabaseReader
 from .structure import (Chain, MultipleChainsError, StructureError, build_batch, parse_pdb, remove_alternative_position)
 
@@ -242,7 +242,8 @@ class FoldcompDatabase:
 
     def tensor_batches(self, batch_size: int = 1024, *, layout="atom37", max_len: Optional[int] = None, device="cuda:0",
                        sort_by_length: bool = False, packed: bool = False, max_residues: Optional[int] = None,
-                       angles: bool = False, crop: Optional[str] = None, seed: Optional[int] = None):
+                       angles: bool = False, crop: Optional[str] = None, seed: Optional[int] = None,
+                       neighbors: Optional[int] = None, neighbor_atom="CA"):
         """Generator over the database (its `ids` selection when it has one) in batches of dense model-input tensors on the GPU:
         the dicts of foldcomp_amd.tensors.decode_tensors, each with `names` (the records' titles) and `index` (int64 array: the
         entries' positions in this database, what db[i] takes). sort_by_length orders every window of 16 * batch_size entries by
@@ -252,8 +253,13 @@ class FoldcompDatabase:
         or at batch_size entries; an entry longer than the budget forms a batch of its own. angles=True adds `angles` and
         `angle_mask` to every dict (decode_tensors(angles=True)). crop="start" / "center" / "random" with max_len=L keeps a window
         of L residues of every longer entry (decode_tensors(crop=...)) and adds `crop_start` to every dict; "random" draws from ONE
-        generator for the whole iteration, seeded once with `seed` (None: from the system), so the same seed gives the same crops."""
+        generator for the whole iteration, seeded once with `seed` (None: from the system), so the same seed gives the same crops.
+        neighbors=k adds the k-nearest-neighbour graph of every chain, `nbr_index` / `nbr_dist`, on the sites of `neighbor_atom`
+        (decode_tensors(neighbors=k)); like the other argument rules, a bad k or atom raises at the first next(), before a record
+        is read."""
         from .tensors import decode_tensors
+        if neighbors is not None:
+            check_neighbors(neighbors, neighbor_atom, {0: 37, 1: 14, 2: 4}[dense_layout(layout)])
         batch_size = int(batch_size)
         if batch_size < 1:
             raise ValueError("batch_size must be at least 1")
@@ -272,14 +278,15 @@ class FoldcompDatabase:
             for sel in cut_batches(lens, batch_size, max_residues, sort_by_length):
                 sel = np.asarray(sel, np.int64)
                 if packed:
-                    d = decode_tensors([ents[k] for k in sel], layout=layout, device=device, packed=True, angles=angles)
+                    d = decode_tensors([ents[k] for k in sel], layout=layout, device=device, packed=True, angles=angles,
+                                       neighbors=neighbors, neighbor_atom=neighbor_atom)
                 else:
                     if crop == "random" and gen is None:
                         import torch
                         gen = torch.Generator(device=device)
                         gen.manual_seed(int(seed)) if seed is not None else gen.seed()
                     d = decode_tensors([ents[k] for k in sel], layout=layout, max_len=max_len, device=device, angles=angles, crop=crop,
-                                       generator=gen)
+                                       generator=gen, neighbors=neighbors, neighbor_atom=neighbor_atom)
                 d["index"] = idx[sel]
                 yield d
 
@@ -319,6 +326,31 @@ def check_crop(crop, max_len, packed):
         raise ValueError("crop keeps a window of max_len rows per entry; the packed form keeps every residue (packed=True takes no crop)")
     if max_len is None:
         raise ValueError("crop needs max_len: the window is max_len residues long")
+
+
+# slot of the named atom per layout width (atom37: N CA C CB ..; atom14: N CA C O CB ..; backbone4: N CA C O -- no CB)
+NEIGHBOR_ATOMS = {"CA": {37: 1, 14: 1, 4: 1}, "CB": {37: 3, 14: 4}}
+MAX_NEIGHBORS = 64
+
+
+def check_neighbors(k, atom, width=None):
+    """the argument rules of neighbors= / neighbor_graph that need no tensors' device and no GPU -> the slot (None while the
+    layout width A is unknown): k an integer 1 .. 64; atom "CA", "CB" (atom37 / atom14 only) or an integer slot 0 .. A - 1"""
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= MAX_NEIGHBORS:
+        raise ValueError(f"k must be an integer 1 .. {MAX_NEIGHBORS}, not {k!r}")
+    if isinstance(atom, str):
+        if atom not in NEIGHBOR_ATOMS:
+            raise ValueError(f"atom must be one of {', '.join(NEIGHBOR_ATOMS)} or an integer slot, not {atom!r}")
+        if width is None:
+            return None
+        if width not in NEIGHBOR_ATOMS[atom]:
+            raise ValueError(f"a layout of {width} slots per residue has no {atom}")
+        return NEIGHBOR_ATOMS[atom][width]
+    if isinstance(atom, bool) or not isinstance(atom, (int, np.integer)) or not 0 <= int(atom) < (37 if width is None else width):
+        raise ValueError(f"atom must be 'CA', 'CB' or a slot 0 .. {(37 if width is None else width) - 1}, not {atom!r}")
+    if width is not None and width not in (37, 14, 4):
+        raise ValueError(f"no dense layout has {width} slots per residue (37, 14 or 4)")
+    return int(atom)
 
 
 def cut_batches(lengths, batch_size: int, max_residues: Optional[int] = None, sort_by_length: bool = False) -> list:

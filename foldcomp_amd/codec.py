@@ -194,6 +194,44 @@ class Codec:
         d["status"] = status[:n]
         return d
 
+    def neighbors(self, pos: np.ndarray, mask: np.ndarray, k: int, slot: int, length=None, row_off=None):
+        """dense arrays on the host -> the k-nearest-neighbour graph of every chain on the sites at `slot` (fcz_knn, or
+        fcz_knn_packed when row_off is given): index int32 [n, L, k] / [R, k] (-1 = none) and dist float32 of the same shape.
+        pos float32 [n, L, A, 3] with mask [n, L, A] and optionally length [n]; or pos [R, A, 3], mask [R, A], row_off [n + 1]."""
+        pos = np.ascontiguousarray(pos, np.float32)
+        packed = row_off is not None
+        if pos.ndim != (3 if packed else 4) or pos.shape[-1] != 3 or pos.shape[-2] not in (37, 14, 4):
+            raise ValueError(f"pos must be float32 {'[R, A, 3]' if packed else '[n, L, A, 3]'} with A = 37, 14 or 4, not {pos.shape}")
+        A = pos.shape[-2]
+        lay = {37: 0, 14: 1, 4: 2}[A]
+        mask = np.ascontiguousarray(mask)
+        if mask.shape != pos.shape[:-1] or mask.dtype not in (np.bool_, np.uint8):
+            raise ValueError(f"mask must be bool / uint8 {pos.shape[:-1]}, not {mask.dtype} {mask.shape}")
+        k, slot = int(k), int(slot)
+        if not 1 <= k <= 64 or not 0 <= slot < A:
+            raise ValueError(f"k must be 1 .. 64 and slot 0 .. {A - 1}")
+        bound = None
+        if packed:
+            bound = np.ascontiguousarray(row_off, np.uint32)
+            n, rows = len(bound) - 1, pos.shape[0]
+            if bound.ndim != 1 or n < 0:
+                raise ValueError("row_off must be [n + 1]")
+            if rows > 2 ** 31 - 1:
+                raise ValueError("the packed index holds global rows as int32: at most 2^31 - 1 rows")
+        else:
+            n, rows = pos.shape[0], pos.shape[1]
+            if length is not None:
+                bound = np.ascontiguousarray(length, np.uint32)
+                if bound.shape != (n,):
+                    raise ValueError(f"length must be [{n}], not {bound.shape}")
+        index = np.full(pos.shape[:-2] + (k,), -1, np.int32)
+        dist = np.zeros(pos.shape[:-2] + (k,), np.float32)
+        if index.size:
+            fn = self.lib.fcz_knn_packed if packed else self.lib.fcz_knn
+            _lib.check(fn(self.ctx, pos.ctypes.data, mask.ctypes.data, None if bound is None else bound.ctypes.data, n, rows, lay, slot, k,
+                          index.ctypes.data, dist.ctypes.data), "fcz_knn_packed" if packed else "fcz_knn")
+        return dict(index=index, dist=dist)
+
     def decompress_angles(self, blob: np.ndarray, off: np.ndarray, L: int = 0, packed: bool = False, start=None):
         """FCZ entries -> the record's internal coordinates on the host (fcz_decompress_angles): angles float32 [n, L, 10] in degrees
         (ANGLE_COLUMNS), angle_mask bool [n, L, 10], status int32 [n]; L = 0: the longest entry of the batch, longer entries are

@@ -32,6 +32,7 @@
 #include "fcz_inflate.h"
 #include "fcz_dense.h"
 #include "fcz_undense.h"
+#include "fcz_knn.h"
 #include "fcz_angles.h"
 
 // second, host-side instance of the generated tables (integer metadata for sizes/validation)
@@ -136,6 +137,7 @@ struct fcz_ctx {
     dev_buf res_sc;     // decompress: residue -> its side-chain torsion bytes, 3 x R dwords
     dev_buf sizes_res_off;   // decompress: the res_off of a batch call that has to run its own sizes pass (ensure_sizes)
     dev_buf selftest_out;    // fcz_selftest_math
+    dev_buf knn_tiles;       // fcz_knn_packed_dev: n u64 tile counts, then their n + 1 offsets
     dev_buf fast_scratch;    // decompress, FCZ_NUMERICS_FAST: forward atoms of segments longer than one chunk
     // Staging of the host-pointer entry points. Every entry point that writes it calls claim_staging first. Nothing outlives the call
     // that wrote it but KEPT_*, which a begin leaves for its fetch: any later call that writes 13 .. 15 ends that.
@@ -155,6 +157,7 @@ struct fcz_ctx {
     //   fcz_compress_dense_begin                    DENSE_IN 0 .. 9, then KEPT_* 13 .. 15       KEPT_*, ud_fcz_bytes (+ ud_batch)
     //   fcz_compress_dense_begin_dev                KEPT_* 13 .. 15                             KEPT_*, ud_fcz_bytes (+ ud_batch)
     //   fcz_compress_dense_packed_begin[_dev]       as the two above (DENSE_IN 3 = row_off)     the same
+    //   fcz_knn / fcz_knn_packed                    DENSE_IN 0, 1, 3 (pos, mask, length / row_off), DENSE_OUT 10 .. 11 (index, dist)
     dev_buf pool[POOL_COUNT];
     // PDB text / extracted data: per-entry sizes (any call), offsets (n + 1 u64) and the text of the last fcz_decompress_pdb_begin,
     // which fcz_decompress_pdb_fetch reads: live until the next fcz_decompress_pdb_begin / _sizes or fcz_extract
@@ -1633,6 +1636,102 @@ int fcz_decompress_angles_window(fcz_ctx* ctx, const uint8_t* blob, const uint64
 int fcz_decompress_angles_packed(fcz_ctx* ctx, const uint8_t* blob, const uint64_t* off, uint32_t n, uint32_t* R_out, uint32_t* row_off,
                                  float* angles, uint8_t* mask, int32_t* status) {
     return decompress_angles_impl(ctx, blob, off, n, true, 0u, R_out, row_off, angles, mask, status);
+}
+
+// ------------------------------------------------------------------------------------------------
+// k-nearest-neighbour residue graph of dense tensors (fcz_knn.h; no counterpart in the reference)
+// ------------------------------------------------------------------------------------------------
+int fcz_knn_pass(void) { return (int)KNN_PASS; }
+
+static bool knn_args_ok(const fcz_ctx* ctx, const float* pos, const uint8_t* mask, int layout, int slot, uint32_t k, const int32_t* index, const float* dist) {
+    return ctx && pos && mask && index && dist && fcz_dense_width(layout) > 0 && slot >= 0 && slot < fcz_dense_width(layout) && k >= 1 && k <= KNN_MAX_K;
+}
+
+// fcz_knn_dev (row_off_dev == NULL: bound_dev is length [n] or NULL, rows = L) and fcz_knn_packed_dev (bound_dev = row_off [n + 1], rows = R)
+static int knn_rows(fcz_ctx* ctx, const float* pos_dev, const uint8_t* mask_dev, const uint32_t* bound_dev, bool packed, uint32_t n, uint32_t rows,
+                    int layout, int slot, uint32_t k, int32_t* index_dev, float* dist_dev) {
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (rows == 0 || (n == 0 && !packed)) return FCZ_OK;
+    const knn_args g{pos_dev, mask_dev, bound_dev, n, rows, (uint32_t)fcz_dense_width(layout), (uint32_t)slot, k, index_dev, dist_dev};
+    const uint32_t max_blocks = (uint32_t)ctx->n_cu * 16u;
+    uint64_t* tile_off = nullptr;
+    if (packed && n) {
+        int rc = ctx->knn_tiles.ensure(sizeof(uint64_t) * (2 * (size_t)n + 1)); if (rc) return rc;
+        tile_off = ctx->knn_tiles.as<uint64_t>() + n;
+    }
+    const uint32_t tiles_per_entry = (uint32_t)(((uint64_t)rows + KNN_TILE - 1) / KNN_TILE);   // (rows + 255 may pass 2^32)
+    span_guard sg(ctx, "knn");
+    uint64_t blocks;
+    if (packed) {
+        hipLaunchKernelGGL(k_knn_fill, dim3((uint32_t)std::min<uint64_t>(((uint64_t)rows + BLOCK - 1) / BLOCK, max_blocks)), dim3(BLOCK), 0, ctx->stream, g);
+        if (n == 0) { HIP_TRY(hipGetLastError()); return FCZ_OK; }
+        hipLaunchKernelGGL(k_knn_tiles, dim3(std::min(grid_for(n, BLOCK), max_blocks)), dim3(BLOCK), 0, ctx->stream, g, ctx->knn_tiles.as<uint64_t>());
+        int rc = device_scan<uint64_t>(ctx, ctx->knn_tiles.as<uint64_t>(), tile_off, n); if (rc) return rc;
+        blocks = std::min<uint64_t>((uint64_t)rows / KNN_TILE + n, max_blocks);   // the tiles are counted on the device: at most this many
+    } else {
+        blocks = std::min<uint64_t>((uint64_t)n * tiles_per_entry, max_blocks);
+    }
+    auto launch = [&](auto KCAP) {
+        if (packed)
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_knn<decltype(KCAP)::value, true>), dim3((uint32_t)blocks), dim3(BLOCK), 0, ctx->stream, g, tile_off, 0u, (uint64_t)0);
+        else
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_knn<decltype(KCAP)::value, false>), dim3((uint32_t)blocks), dim3(BLOCK), 0, ctx->stream, g, (const uint64_t*)nullptr,
+                               tiles_per_entry, (uint64_t)n * tiles_per_entry);
+    };
+    if (k <= 16) launch(std::integral_constant<int, 16>{});
+    else if (k <= 32) launch(std::integral_constant<int, 32>{});
+    else if (k <= 48) launch(std::integral_constant<int, 48>{});
+    else launch(std::integral_constant<int, 64>{});
+    HIP_TRY(hipGetLastError());
+    return FCZ_OK;
+}
+
+int fcz_knn_dev(fcz_ctx* ctx, const float* pos_dev, const uint8_t* mask_dev, const uint32_t* length_dev, uint32_t n, uint32_t L, int layout, int slot,
+                uint32_t k, int32_t* index_dev, float* dist_dev) {
+    if (!knn_args_ok(ctx, pos_dev, mask_dev, layout, slot, k, index_dev, dist_dev) || L == 0) return FCZ_E_INVALID_ARG;
+    return knn_rows(ctx, pos_dev, mask_dev, length_dev, false, n, L, layout, slot, k, index_dev, dist_dev);
+}
+
+int fcz_knn_packed_dev(fcz_ctx* ctx, const float* pos_dev, const uint8_t* mask_dev, const uint32_t* row_off_dev, uint32_t n, uint32_t R, int layout,
+                       int slot, uint32_t k, int32_t* index_dev, float* dist_dev) {
+    if (!knn_args_ok(ctx, pos_dev, mask_dev, layout, slot, k, index_dev, dist_dev) || (n && !row_off_dev) || R > 0x7FFFFFFFu) return FCZ_E_INVALID_ARG;   // (index holds global rows as int32)
+    return knn_rows(ctx, pos_dev, mask_dev, row_off_dev, true, n, R, layout, slot, k, index_dev, dist_dev);
+}
+
+// fcz_knn and fcz_knn_packed: the host arrays through DENSE_IN 0, 1, 3 and DENSE_OUT 10, 11
+static int knn_host(fcz_ctx* ctx, const float* pos, const uint8_t* mask, const uint32_t* bound, bool packed, uint32_t n, uint32_t rows_per, int layout,
+                    int slot, uint32_t k, int32_t* index, float* dist) {
+    HIP_TRY(hipSetDevice(ctx->device));
+    claim_staging(ctx);
+    const size_t rows = packed ? (size_t)rows_per : (size_t)n * rows_per, A = (size_t)fcz_dense_width(layout);
+    if (rows == 0) return FCZ_OK;
+    const size_t nb = bound ? sizeof(uint32_t) * ((size_t)n + (packed ? 1 : 0)) : 0, no = rows * k * sizeof(int32_t);
+    int rc;
+    if ((rc = ctx->pool[DENSE_IN].ensure(rows * A * 3 * sizeof(float))) || (rc = ctx->pool[DENSE_IN + 1].ensure(rows * A)) ||
+        (rc = ctx->pool[DENSE_IN + 3].ensure(nb)) || (rc = ctx->pool[DENSE_OUT].ensure(no)) || (rc = ctx->pool[DENSE_OUT + 1].ensure(no)))
+        return rc;
+    HIP_TRY(hipMemcpyAsync(ctx->pool[DENSE_IN].p, pos, rows * A * 3 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(ctx->pool[DENSE_IN + 1].p, mask, rows * A, hipMemcpyHostToDevice, ctx->stream));
+    if (nb) HIP_TRY(hipMemcpyAsync(ctx->pool[DENSE_IN + 3].p, bound, nb, hipMemcpyHostToDevice, ctx->stream));
+    rc = knn_rows(ctx, ctx->pool[DENSE_IN].as<float>(), ctx->pool[DENSE_IN + 1].as<uint8_t>(), nb ? ctx->pool[DENSE_IN + 3].as<uint32_t>() : nullptr, packed, n,
+                  rows_per, layout, slot, k, ctx->pool[DENSE_OUT].as<int32_t>(), ctx->pool[DENSE_OUT + 1].as<float>());
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(index, ctx->pool[DENSE_OUT].p, no, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(dist, ctx->pool[DENSE_OUT + 1].p, no, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return FCZ_OK;
+}
+
+int fcz_knn(fcz_ctx* ctx, const float* pos, const uint8_t* mask, const uint32_t* length, uint32_t n, uint32_t L, int layout, int slot, uint32_t k,
+            int32_t* index, float* dist) {
+    if (!knn_args_ok(ctx, pos, mask, layout, slot, k, index, dist) || L == 0) return FCZ_E_INVALID_ARG;
+    return knn_host(ctx, pos, mask, length, false, n, L, layout, slot, k, index, dist);
+}
+
+int fcz_knn_packed(fcz_ctx* ctx, const float* pos, const uint8_t* mask, const uint32_t* row_off, uint32_t n, uint32_t R, int layout, int slot, uint32_t k,
+                   int32_t* index, float* dist) {
+    if (!knn_args_ok(ctx, pos, mask, layout, slot, k, index, dist) || (n && !row_off) || R > 0x7FFFFFFFu) return FCZ_E_INVALID_ARG;
+    return knn_host(ctx, pos, mask, row_off, true, n, R, layout, slot, k, index, dist);
 }
 
 // ------------------------------------------------------------------------------------------------

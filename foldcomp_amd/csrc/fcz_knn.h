@@ -1,0 +1,183 @@
+// fcz_knn.h -- dense tensors -> k-nearest-neighbour residue graph (index [rows][k] int32, dist [rows][k] float32) on the device.
+// The reference has no such output (Foldcomp::decompress, src/foldcomp.cpp:779, ends at a flat vector<AtomCoordinate>); the call
+// stands beside it like the dense ones and reads what fcz_dense_dev / fcz_dense_packed_dev write (include/fcz_hip.h, fcz_knn_dev).
+//
+// The contract (include/fcz_hip.h): a row is a SITE when it lies inside its chain, its mask at the slot is set and its three
+// coordinates there are finite. d2 = (dx*dx + dy*dy) + dz*dz in float32, every operation rounded, no FMA. The neighbours of site i
+// are the other sites of its chain in the order of the 64-bit key (bits of d2 << 32) | j: d2 >= 0 orders as an unsigned integer,
+// j makes the order total, so the list does not depend on the order the candidates are met in.
+//
+//   k_knn<KCAP, PACKED>   persistent blocks over QUERY TILES of KNN_TILE = 256 rows of one chain, a lane per query. The chain's
+//                         sites are staged in LDS in passes of KNN_PASS chain rows (SoA x / y / z and the compacted row number;
+//                         slots are handed out by an LDS counter -- the order inside a pass is free, see above), and every lane
+//                         sweeps the pass: one broadcast LDS read per candidate, eight float operations, one 64-bit compare
+//                         against the worst key it keeps. The KCAP best keys of a lane are a sorted list in REGISTERS: an
+//                         accepted key goes through KCAP compare-exchange steps with static indices (a list indexed by a
+//                         variable would go to scratch, a list in LDS costs the CU's shared LDS cycles on every insertion),
+//                         and the steps run only when some lane of the wavefront accepts. KCAP = 16 / 32 / 48 / 64 is the
+//                         smallest that holds k. A wavefront without a query skips the sweep and keeps the barriers.
+//                         The L x L matrix is never written: HBM sees the slot's 12 bytes per row and the [rows][k] outputs.
+//                         Padded form: tile -> (entry, tile of the entry) by division; every row of the entry is written,
+//                         -1 / 0 where it is no site. Packed form: the chains' tile counts are scanned on the device
+//                         (k_knn_tiles, device_scan) and a tile finds its chain by binary search, as k_dense_packed's rows do.
+//   k_knn_fill            packed form only, in front of k_knn: -1 / 0 into every row that no chain is seen to cover (a search of
+//                         row_off that a hostile row_off may mislead: a covered row it misses is rewritten by k_knn behind it).
+//
+// Every index that scales with rows * k or rows * A is 64-bit. A chain's range is clamped to the R rows that exist and a range
+// that runs backwards is empty, so no read leaves pos / mask whatever row_off holds.
+#pragma once
+#include "fcz_dense.h"
+
+namespace fcz {
+
+constexpr uint32_t KNN_TILE = BLOCK;        // query rows per tile (a lane per query)
+constexpr uint32_t KNN_PASS = 2048;         // chain rows staged per candidate pass: 32 KiB of LDS
+constexpr uint32_t KNN_MAX_K = 64;
+constexpr uint64_t KNN_NONE = ~0ull;        // no neighbour: above every key (its d2 half is a NaN pattern)
+
+typedef int32_t knn_i4 __attribute__((ext_vector_type(4)));
+typedef float knn_f4 __attribute__((ext_vector_type(4)));
+
+struct knn_args {
+    const float* pos; const uint8_t* mask;
+    const uint32_t* bound;                  // padded: length [n] or NULL; packed: row_off [n + 1]
+    uint32_t n, L;                          // padded: rows per entry; packed: L = R, the rows of the arrays
+    uint32_t A, slot, k;
+    int32_t* index; float* dist;
+};
+
+// chain e: its first row in the arrays, the rows that may hold a site, the rows k_knn writes
+template <bool PACKED>
+__device__ __forceinline__ void knn_chain(const knn_args& g, uint32_t e, uint64_t* row0, uint32_t* len, uint32_t* rows) {
+    if constexpr (PACKED) {
+        uint32_t lo = g.bound[e], hi = g.bound[e + 1];
+        if (lo > g.L) lo = g.L;
+        if (hi > g.L) hi = g.L;
+        *row0 = lo; *len = hi > lo ? hi - lo : 0u; *rows = *len;
+    } else {
+        const uint32_t le = g.bound ? g.bound[e] : g.L;
+        *row0 = (uint64_t)e * g.L; *len = le < g.L ? le : g.L; *rows = g.L;
+    }
+}
+
+// the slot's coordinates of array row r -> true when the row is a site (mask set, three finite values)
+__device__ __forceinline__ bool knn_site(const knn_args& g, uint64_t r, float* x, float* y, float* z) {
+    if (g.mask[r * g.A + g.slot] == 0) return false;
+    const float* p = g.pos + (r * g.A + g.slot) * 3u;
+    *x = p[0]; *y = p[1]; *z = p[2];
+    return isfinite(*x) && isfinite(*y) && isfinite(*z);
+}
+
+__device__ __forceinline__ void knn_decode(uint64_t key, uint32_t base, int32_t* idx, float* d) {
+    const bool none = key == KNN_NONE;
+    *idx = none ? -1 : (int32_t)(base + (uint32_t)key);
+    // the double square root of a float, rounded to float, is the correctly rounded float square root
+    *d = none ? 0.0f : (float)sqrt((double)__uint_as_float((uint32_t)(key >> 32)));
+}
+
+// packed form: tiles of every chain, for the scan that gives each tile its chain
+__global__ __launch_bounds__(BLOCK) void k_knn_tiles(knn_args g, uint64_t* __restrict__ tiles) {
+    for (uint64_t e = (uint64_t)blockIdx.x * BLOCK + threadIdx.x; e < g.n; e += (uint64_t)gridDim.x * BLOCK) {
+        uint64_t row0; uint32_t len, rows;
+        knn_chain<true>(g, (uint32_t)e, &row0, &len, &rows);
+        tiles[e] = rows / KNN_TILE + (rows % KNN_TILE ? 1u : 0u);
+    }
+}
+
+__global__ __launch_bounds__(BLOCK) void k_knn_fill(knn_args g) {
+    for (uint64_t r = (uint64_t)blockIdx.x * BLOCK + threadIdx.x; r < g.L; r += (uint64_t)gridDim.x * BLOCK) {
+        bool covered = false;
+        if (g.n) {
+            const uint32_t e = dn_entry_of(g.bound, 0u, g.n, (uint32_t)r);
+            covered = g.bound[e] <= r && r < g.bound[e + 1];          // (r < R: chain e's clamped range holds the row)
+        }
+        if (covered) continue;
+        for (uint32_t s = 0; s < g.k; s++) { g.index[r * g.k + s] = -1; g.dist[r * g.k + s] = 0.0f; }
+    }
+}
+
+template <int KCAP, bool PACKED>
+__global__ __launch_bounds__(BLOCK) void k_knn(knn_args g, const uint64_t* __restrict__ tile_off, uint32_t tiles_per_entry, uint64_t n_tiles_padded) {
+    __shared__ float s_x[KNN_PASS], s_y[KNN_PASS], s_z[KNN_PASS];
+    __shared__ uint32_t s_j[KNN_PASS];
+    __shared__ uint32_t s_count;
+    const uint32_t tid = threadIdx.x;
+    const uint64_t n_tiles = PACKED ? tile_off[g.n] : n_tiles_padded;
+    const bool wide = (g.k & 3u) == 0 && (((uintptr_t)g.index | (uintptr_t)g.dist) & 15u) == 0;   // 16-byte stores of four columns
+    for (uint64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+        uint32_t e, t;
+        if constexpr (PACKED) {   // the largest e with tile_off[e] <= tile: a chain that has tiles
+            uint32_t lo = 0, hi = g.n;
+            while (hi - lo > 1u) { const uint32_t mid = lo + ((hi - lo) >> 1); if (tile_off[mid] <= tile) lo = mid; else hi = mid; }
+            e = lo; t = (uint32_t)(tile - tile_off[e]);
+        } else {
+            e = (uint32_t)(tile / tiles_per_entry); t = (uint32_t)(tile - (uint64_t)e * tiles_per_entry);
+        }
+        uint64_t row0; uint32_t len, rows;
+        knn_chain<PACKED>(g, e, &row0, &len, &rows);
+        const uint64_t q = (uint64_t)t * KNN_TILE + tid;              // this lane's row of the chain
+        float qx = 0.0f, qy = 0.0f, qz = 0.0f;
+        const bool query = q < len && knn_site(g, row0 + q, &qx, &qy, &qz);
+        const uint32_t qj = (uint32_t)q;
+        uint64_t list[KCAP];
+#pragma unroll
+        for (int s = 0; s < KCAP; s++) list[s] = KNN_NONE;
+        for (uint32_t c0 = 0; c0 < len;) {
+            const uint32_t c1 = len - c0 < KNN_PASS ? len : c0 + KNN_PASS;
+            if (tid == 0) s_count = 0;
+            __syncthreads();
+            for (uint64_t r = (uint64_t)c0 + tid; r < c1; r += BLOCK) {
+                float x, y, z;
+                if (knn_site(g, row0 + r, &x, &y, &z)) {
+                    const uint32_t i = atomicAdd(&s_count, 1u);       // (< KNN_PASS: one slot per row of the pass)
+                    s_x[i] = x; s_y[i] = y; s_z[i] = z; s_j[i] = (uint32_t)r;
+                }
+            }
+            __syncthreads();
+            const uint32_t count = s_count;
+            if (__any(query)) {
+                for (uint32_t c = 0; c < count; c++) {
+                    const uint32_t j = s_j[c];
+                    const float dx = __fsub_rn(s_x[c], qx), dy = __fsub_rn(s_y[c], qy), dz = __fsub_rn(s_z[c], qz);
+                    const float d2 = __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
+                    uint64_t key = ((uint64_t)__float_as_uint(d2) << 32) | j;
+                    if (!query || j == qj) key = KNN_NONE;
+                    if (__any(key < list[KCAP - 1])) {
+#pragma unroll
+                        for (int s = 0; s < KCAP; s++) {              // sorted insertion: the key sinks to its place, the worst falls out
+                            const uint64_t o = list[s];
+                            const bool lt = key < o;
+                            list[s] = lt ? key : o;
+                            key = lt ? o : key;
+                        }
+                    }
+                }
+            }
+            __syncthreads();                                          // the next pass (or tile) rewrites the staging
+            c0 = c1;
+        }
+        if (q < rows) {
+            const uint32_t base = PACKED ? (uint32_t)row0 : 0u;
+            const uint64_t o = (row0 + q) * (uint64_t)g.k;
+            if (wide) {
+#pragma unroll
+                for (int s = 0; s < KCAP; s += 4)
+                    if ((uint32_t)s < g.k) {
+                        knn_i4 vi; knn_f4 vd; int32_t i; float d;
+                        knn_decode(list[s], base, &i, &d); vi.x = i; vd.x = d;
+                        knn_decode(list[s + 1], base, &i, &d); vi.y = i; vd.y = d;
+                        knn_decode(list[s + 2], base, &i, &d); vi.z = i; vd.z = d;
+                        knn_decode(list[s + 3], base, &i, &d); vi.w = i; vd.w = d;
+                        *reinterpret_cast<knn_i4*>(g.index + o + s) = vi;
+                        *reinterpret_cast<knn_f4*>(g.dist + o + s) = vd;
+                    }
+            } else {
+#pragma unroll
+                for (int s = 0; s < KCAP; s++)
+                    if ((uint32_t)s < g.k) knn_decode(list[s], base, &g.index[o + s], &g.dist[o + s]);
+            }
+        }
+    }
+}
+
+}  // namespace fcz

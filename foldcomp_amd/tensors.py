@@ -10,6 +10,8 @@
     decode_tensors / decode_angles(entries, max_len=L, crop="start" | "center" | "random" | starts [n]) -> the same padded dicts
                                    with row l of entry e = its residue crop_start[e] + l, plus crop_start [n] int32
     crop_starts(length, L, how, generator) -> the starts of such a crop, on the device the lengths lie on
+    neighbor_graph(either dict, or the tensors as keywords, k=48, atom="CA") -> dict(nbr_index [.., k] int32, nbr_dist [.., k] float32):
+                                   the k nearest CA / CB sites of every residue inside its chain; decode_tensors(neighbors=k) adds them
 
 What a structure model's data loader wants from a Foldcomp database (atom37 / atom14 coordinates with a mask, residue types,
 pLDDT), without the PDB text `foldcomp.decompress` returns and without a host copy of the result: the records go up once, torch
@@ -32,7 +34,7 @@ from ._aa_tables import RES1
 from .codec import ANGLE_COLUMNS, Codec, dense_layout
 from .structure import CAtomsOut, CDenseIn, CDenseOut, CPackedOut
 
-__all__ = ["decode_tensors", "encode_tensors", "decode_angles", "crop_starts"]
+__all__ = ["decode_tensors", "encode_tensors", "decode_angles", "crop_starts", "neighbor_graph"]
 
 
 def crop_starts(length, L: int, how, generator=None):
@@ -234,7 +236,8 @@ def decode_angles(entries: Sequence[bytes], *, max_len: Optional[int] = None, pa
 
 
 def decode_tensors(entries: Sequence[bytes], *, layout="atom37", max_len: Optional[int] = None, device="cuda:0",
-                   codec: Optional[Codec] = None, packed: bool = False, angles: bool = False, crop=None, generator=None) -> dict:
+                   codec: Optional[Codec] = None, packed: bool = False, angles: bool = False, crop=None, generator=None,
+                   neighbors: Optional[int] = None, neighbor_atom="CA") -> dict:
     """[fcz, ...] -> dict of torch tensors on `device` plus `names` (the records' titles, a Python list).
 
     layout: "atom37" (A = 37, AlphaFold / OpenFold atom order, the chain's OXT in slot 36 of its last residue), "atom14" (A = 14,
@@ -257,11 +260,19 @@ def decode_tensors(entries: Sequence[bytes], *, layout="atom37", max_len: Option
     stays the full size, and the dict gains crop_start [n] int32. The starts are computed on the device from res_off
     (fcz_dense_window_dev reads them there); with angles=True both calls use the same starts. crop=None: the dict has no new key.
 
+    neighbors=k (1 .. 64) adds the k-nearest-neighbour graph of the tensors just written, in either form, with no host round trip
+    (fcz_knn_dev / fcz_knn_packed_dev on the codec's stream behind the dense call): nbr_index [n, L, k] / [R, k] int32 and nbr_dist
+    float32, as neighbor_graph describes them, on the sites of neighbor_atom ("CA", "CB" or a slot). With crop the graph is the
+    window's own. neighbors=None: the dict has no new key.
+
     Ordering against torch: the uploads and allocations are made on torch's current stream, which is synchronised before the
     codec's calls; the codec works on its own stream, which is synchronised before the tensors are returned. No output byte
     visits the host.
     """
     api.check_crop(crop, max_len, packed)
+    nbr = None
+    if neighbors is not None:
+        nbr = (int(neighbors), api.check_neighbors(neighbors, neighbor_atom, _LAYOUT_WIDTH[dense_layout(layout)]))
     torch, dev = _torch_device(device)
     c = codec or api.default_codec()
     if int(c.device) != dev.index:
@@ -297,12 +308,17 @@ def decode_tensors(entries: Sequence[bytes], *, layout="atom37", max_len: Option
         W = len(ANGLE_COLUMNS)
         return dict(angles=torch.empty(rows + (W,), dtype=torch.float32, device=dev), angle_mask=torch.empty(rows + (W,), dtype=torch.bool, device=dev))
 
+    def nbr_alloc(*rows):   # neighbors=None: no key
+        if nbr is None:
+            return {}
+        return dict(nbr_index=torch.empty(rows + (nbr[0],), dtype=torch.int32, device=dev), nbr_dist=torch.empty(rows + (nbr[0],), dtype=torch.float32, device=dev))
+
     if n == 0:
         if packed:
-            d = packed_result(0, torch.zeros(1, dtype=torch.int32, device=dev), 0)[1]
+            d = dict(packed_result(0, torch.zeros(1, dtype=torch.int32, device=dev), 0)[1], **nbr_alloc(0))
             return dict(d, **no_angles(0)) if angles else d
         L = int(max_len or 0)
-        d = result(L, *alloc(L))
+        d = dict(result(L, *alloc(L)), **nbr_alloc(0, L))
         if crop is not None:
             d["crop_start"] = crop_starts(d["length"], L, crop, generator)
         return dict(d, **no_angles(0, L)) if angles else d
@@ -311,7 +327,7 @@ def decode_tensors(entries: Sequence[bytes], *, layout="atom37", max_len: Option
     if packed:
         # (the angle call is enqueued in front of the decode and leaves it the sizes memo; _decode_packed synchronises the codec)
         extra = _angles_into(c, torch, dev, n, blob_t, off_t, res_off_t, 0, Rv) if angles else {}
-        d = _decode_packed(c, torch, dev, lay, n, Rv, Mv, blob_t, off_t, res_off_t, atom_off_t, packed_result)
+        d = _decode_packed(c, torch, dev, lay, n, Rv, Mv, blob_t, off_t, res_off_t, atom_off_t, packed_result, nbr, nbr_alloc)
         return dict(d, **extra)
     if max_len is None:
         ro = res_off_t.cpu().numpy().view(np.uint32).astype(np.int64)      # n + 1 offsets: the only words that come back
@@ -320,11 +336,12 @@ def decode_tensors(entries: Sequence[bytes], *, layout="atom37", max_len: Option
         L = int(max_len)
     out = alloc(L)
     if L == 0:                                                             # nothing decodes and no width was asked for
-        return dict(result(L, *out), **no_angles(n, 0)) if angles else result(L, *out)
+        return dict(result(L, *out), **nbr_alloc(n, 0), **no_angles(n, 0)) if angles else dict(result(L, *out), **nbr_alloc(n, 0))
     start_t = None if crop is None else crop_starts(_entry_lengths(res_off_t), L, crop, generator)
     extra = _angles_into(c, torch, dev, n, blob_t, off_t, res_off_t, L, start_t=start_t) if angles else {}
     if crop is not None:
         extra["crop_start"] = start_t
+    extra.update(nbr_alloc(n, L))
     x, y, z = (torch.empty(max(M.value, 1), dtype=torch.float32, device=dev) for _ in range(3))
     bfac = torch.empty(max(R.value, 1), dtype=torch.float32, device=dev)
     res_code = torch.empty(max(R.value, 1), dtype=torch.uint8, device=dev)
@@ -340,16 +357,22 @@ def decode_tensors(entries: Sequence[bytes], *, layout="atom37", max_len: Option
     else:
         _lib.check(c.lib.fcz_dense_window_dev(c.ctx, blob_t.data_ptr(), off_t.data_ptr(), n, res_off_t.data_ptr(), atom_off_t.data_ptr(),
                                               ctypes.byref(atoms), 0, lay, L, start_t.data_ptr(), ctypes.byref(dense)), "fcz_dense_window_dev")
+    if nbr is not None:   # (a window's padding rows have a cleared mask: no length; otherwise the length the dense call just wrote)
+        _lib.check(c.lib.fcz_knn_dev(c.ctx, out[0].data_ptr(), out[1].data_ptr(), out[5].data_ptr() if crop is None else None, n, L, lay, nbr[1], nbr[0],
+                                     extra["nbr_index"].data_ptr(), extra["nbr_dist"].data_ptr()), "fcz_knn_dev")
     c.synchronize()
     return dict(result(L, *out), **extra)
 
 
-def _decode_packed(c, torch, dev, lay, n, R, M, blob_t, off_t, res_off_t, atom_off_t, packed_result):
-    """the packed leg of decode_tensors behind fcz_decompress_sizes_dev: R and M are its totals, res_off_t becomes cu_seqlens"""
+def _decode_packed(c, torch, dev, lay, n, R, M, blob_t, off_t, res_off_t, atom_off_t, packed_result, nbr=None, nbr_alloc=None):
+    """the packed leg of decode_tensors behind fcz_decompress_sizes_dev: R and M are its totals, res_off_t becomes cu_seqlens;
+    nbr = (k, slot): the neighbour graph of the rows behind the dense call (nbr_alloc makes its tensors)"""
     if R > 2 ** 31 - 1:
         raise api.error(f"decode_tensors: {R} residues do not fit the int32 cu_seqlens; split the batch")
     ro = res_off_t.cpu().numpy().view(np.uint32).astype(np.int64)          # n + 1 offsets: the only words that come back
     out, d = packed_result(R, res_off_t, int(np.diff(ro).max()))
+    if nbr is not None:
+        d.update(nbr_alloc(R))
     if R == 0:                                                             # nothing decodes: no row, length stays 0
         return d
     x, y, z = (torch.empty(max(M, 1), dtype=torch.float32, device=dev) for _ in range(3))
@@ -362,11 +385,99 @@ def _decode_packed(c, torch, dev, lay, n, R, M, blob_t, off_t, res_off_t, atom_o
                                               0, ctypes.byref(atoms)), "fcz_decompress_batch_dev")
     _lib.check(c.lib.fcz_dense_packed_dev(c.ctx, blob_t.data_ptr(), off_t.data_ptr(), n, res_off_t.data_ptr(), atom_off_t.data_ptr(),
                                           ctypes.byref(atoms), 0, lay, ctypes.byref(dense)), "fcz_dense_packed_dev")
+    if nbr is not None:
+        _lib.check(c.lib.fcz_knn_packed_dev(c.ctx, out[0].data_ptr(), out[1].data_ptr(), res_off_t.data_ptr(), n, R, lay, nbr[1], nbr[0],
+                                            d["nbr_index"].data_ptr(), d["nbr_dist"].data_ptr()), "fcz_knn_packed_dev")
     c.synchronize()
     return d
 
 
 _WIDTH_LAYOUT = {37: "atom37", 14: "atom14", 4: "backbone4"}
+_LAYOUT_WIDTH = {0: 37, 1: 14, 2: 4}                                        # enum fcz_dense_layout -> A (fcz_dense_width)
+
+
+def neighbor_graph(batch=None, *, k: int = 48, atom="CA", codec: Optional[Codec] = None, **tensors) -> dict:
+    """dense tensors on the GPU -> dict(nbr_index, nbr_dist): the k nearest sites of every residue inside its own chain.
+
+    `batch` is the dict decode_tensors / tensor_batches return, padded or packed, or the tensors come as keywords: pos
+    [n, L, A, 3] float32 and mask [n, L, A] bool or uint8, optionally length [n]; or the packed pos [R, A, 3], mask [R, A] with
+    cu_seqlens [n + 1] int32 / int64 (recognised as encode_tensors does). atom: "CA", "CB" (atom37 / atom14) or an integer slot;
+    the layout is inferred from A. A row is a site when it lies inside its chain, its mask at that slot is set and its
+    coordinates there are finite; everything else may hold anything. nbr_index [n, L, k] int32 is the row of the neighbour inside
+    the entry (padded) or [R, k] the global row (packed), nearest first, ties by row number; nbr_dist float32 the distance;
+    -1 / 0.0 where there is no such neighbour (fewer than k other sites, a row that is no site). The distances are
+    sqrt((dx*dx + dy*dy) + dz*dz) in float32, so the result is reproducible bit for bit.
+
+    Padded: `length` is used when the dict has no crop_start (a window's padding rows carry a cleared mask and `length` is the
+    uncropped size). Packed: cu_seqlens must be non-decreasing and end at R (checked on the device). The tensors must be contiguous
+    and lie on the codec's device; ordering against torch is decode_tensors'. k and atom are checked first, without a device."""
+    d = dict(batch) if batch is not None else {}
+    d.update(tensors)
+    pos = d.get("pos")
+    shape = tuple(getattr(pos, "shape", ()))
+    is_packed = d.get("cu_seqlens") is not None and len(shape) == 3
+    slot = api.check_neighbors(k, atom, shape[-2] if len(shape) in (3, 4) else None)
+    k = int(k)
+    for key in ("pos", "mask"):
+        if d.get(key) is None:
+            raise TypeError(f"neighbor_graph needs the tensor {key!r}")
+    c = codec or api.default_codec()
+    try:
+        import torch
+    except ImportError as e:
+        raise api.error(f"neighbor_graph needs PyTorch (ROCm build): {e}") from None
+    if not isinstance(pos, torch.Tensor):
+        raise api.error("neighbor_graph takes torch tensors on the GPU (numpy arrays: Codec.neighbors)")
+    if pos.device.type != "cuda" or pos.device.index != int(c.device):
+        raise api.error(f"neighbor_graph: pos lies on {pos.device}, the codec works on cuda:{int(c.device)}; there is no CPU path")
+    dev = pos.device
+    if len(shape) != (3 if is_packed else 4) or shape[-1] != 3 or pos.dtype != torch.float32:
+        raise ValueError(f"pos must be float32 [n, L, A, 3], or [R, A, 3] beside cu_seqlens, not {pos.dtype} {shape}")
+    A = shape[-2]
+    lay = dense_layout(_WIDTH_LAYOUT[A])
+
+    def on_device(key, t, want, dtypes):
+        if not isinstance(t, torch.Tensor) or t.device != dev:
+            where = t.device if isinstance(t, torch.Tensor) else type(t).__name__
+            raise api.error(f"neighbor_graph: {key} lies on {where}, pos on {dev}; every tensor must be on the codec's device")
+        if tuple(t.shape) != want or t.dtype not in dtypes:
+            raise ValueError(f"{key} must be {' / '.join(str(x) for x in dtypes)} {want}, not {t.dtype} {tuple(t.shape)}")
+        if not t.is_contiguous():
+            raise ValueError(f"neighbor_graph: {key} must be contiguous")
+        return t
+
+    on_device("pos", pos, shape, (torch.float32,))
+    mask = on_device("mask", d["mask"], shape[:-1], (torch.bool, torch.uint8)).view(torch.uint8)
+    index = torch.empty(shape[:-2] + (k,), dtype=torch.int32, device=dev)
+    dist = torch.empty(shape[:-2] + (k,), dtype=torch.float32, device=dev)
+    out = dict(nbr_index=index, nbr_dist=dist)
+    if is_packed:
+        cu = d["cu_seqlens"]
+        if not isinstance(cu, torch.Tensor) or cu.dim() != 1 or cu.shape[0] < 1:
+            raise ValueError("cu_seqlens must be a tensor [n + 1]")
+        n, R = int(cu.shape[0]) - 1, shape[0]
+        cu = on_device("cu_seqlens", cu, (n + 1,), (torch.int32, torch.int64))
+        if bool((cu[1:] < cu[:-1]).any()) or bool(cu[0] < 0) or int(cu[-1]) != R:
+            raise ValueError(f"cu_seqlens must be non-decreasing and end at the {R} rows of pos")
+        bound = cu.to(torch.int32)
+        if R == 0:
+            return out
+        torch.cuda.current_stream(dev).synchronize()
+        _lib.check(c.lib.fcz_knn_packed_dev(c.ctx, pos.data_ptr(), mask.data_ptr(), bound.data_ptr(), n, R, lay, slot, k, index.data_ptr(), dist.data_ptr()),
+                   "fcz_knn_packed_dev")
+    else:
+        n, L = shape[0], shape[1]
+        bound = None
+        if d.get("length") is not None and d.get("crop_start") is None:
+            # (int32 >= 0 and uint32 share their bits; a negative length reads as a large one and is clamped to L)
+            bound = on_device("length", d["length"], (n,), (torch.int32, torch.int64)).clamp(min=0).to(torch.int32)
+        if n == 0 or L == 0:
+            return out
+        torch.cuda.current_stream(dev).synchronize()
+        _lib.check(c.lib.fcz_knn_dev(c.ctx, pos.data_ptr(), mask.data_ptr(), None if bound is None else bound.data_ptr(), n, L, lay, slot, k,
+                                     index.data_ptr(), dist.data_ptr()), "fcz_knn_dev")
+    c.synchronize()
+    return out
 
 
 def encode_tensors(batch=None, *, names=None, layout=None, anchor_residue_threshold: int = 25, codec: Optional[Codec] = None,

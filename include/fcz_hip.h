@@ -17,6 +17,7 @@
  *   Foldcomp::checkValidity()        src/foldcomp.cpp:1492   fcz_check
  *   (none: the reference stops at the flat atom vector)    fcz_dense_dev / fcz_decompress_dense, fcz_dense_packed_dev / fcz_decompress_dense_packed,
  *                                                          fcz_dense_window_dev / fcz_decompress_dense_window
+ *   (none: no neighbour graph of the decoded chain)        fcz_knn_dev / fcz_knn_packed_dev, fcz_knn / fcz_knn_packed
  *   Foldcomp::decompress, the dequantisation :784-804     fcz_angles_dev / fcz_angles_packed_dev, fcz_decompress_angles[_packed],
  *                                                          fcz_angles_window_dev / fcz_decompress_angles_window
  *     (get_data's FCZ branch, foldcomp/foldcomp.cxx)
@@ -347,6 +348,45 @@ int fcz_dense_packed_dev(fcz_ctx* ctx, const uint8_t* blob_dev, const uint64_t* 
 int fcz_decompress_dense_packed(fcz_ctx* ctx, const uint8_t* blob, const uint64_t* off, uint32_t n, int layout,
                                 uint32_t* R_out, uint32_t* row_off, const fcz_packed_out* out, int32_t* status);
 
+/* ---- k-nearest-neighbour residue graph of the dense tensors ---------------------------------------------- */
+/* The neighbour lists graph models start from (the k nearest CA or CB sites of every residue), built on the device from the dense
+ * tensors above without the L x L distance matrix. The reference has no such output: like the dense calls these stand beside
+ * Foldcomp::decompress (src/foldcomp.cpp:779) and read what fcz_dense_dev / fcz_dense_window_dev / fcz_dense_packed_dev wrote, or
+ * any tensors of those shapes. Padded: pos [n][L][A][3] float32, mask [n][L][A] uint8, length [n] uint32 (may be NULL). Packed:
+ * pos [R][A][3], mask [R][A], row_off [n + 1] uint32. A = fcz_dense_width(layout), slot in 0 .. A - 1 (CA is slot 1 in every
+ * layout, CB slot 3 in atom37 and slot 4 in atom14), 1 <= k <= 64.
+ *   site        row l of chain e is a site when it lies inside the chain (padded: l < min(length[e], L), or l < L when length is
+ *               NULL; packed: row_off[e] <= row < row_off[e + 1], both clamped to R, a range that runs backwards being empty),
+ *               mask[row][slot] != 0, and the three coordinates at the slot are finite. Rows outside the chain and pos under a
+ *               cleared mask are never read as data: they may hold anything, so a window batch needs no length.
+ *   distance    for sites i, j of one chain: dx = xj - xi, dy, dz in float32, d2 = (dx*dx + dy*dy) + dz*dz, every operation rounded
+ *               to float32, no FMA; d2 may be +inf.
+ *   neighbours  of site i: the other sites j of its chain ordered by (bits of d2 as uint32, j) ascending, the first
+ *               min(k, sites - 1) of them, in that order.
+ *   index [rows][k] int32    j as a row of the entry (padded, 0 .. L - 1) or as the global row row_off[e] + j (packed)
+ *   dist  [rows][k] float32  the correctly rounded float32 square root of d2
+ * rows = n * L (padded) or R (packed). Unused columns, rows that are no site and packed rows no chain covers hold index -1 and
+ * dist 0.0f. Every byte of both outputs is written whatever the inputs hold, nothing outside them is written, and nothing outside
+ * pos / mask / length / row_off is read, whatever row_off holds (ranges that overlap are each computed; which of them a shared
+ * row's list belongs to is then unspecified). Every index that scales with rows * k or rows * A is 64-bit.
+ * Candidates are staged per chain in passes of fcz_knn_pass() rows (pure host; 0 would mean no passes): a chain longer than that
+ * takes several, with the same result. Enqueued on the ctx stream, no synchronisation (the packed form keeps n + n + 1 words of
+ * scratch in the ctx). FCZ_E_INVALID_ARG with nothing launched: NULL ctx / pos / mask / index / dist, NULL row_off with n > 0,
+ * unknown layout, slot outside the layout's width, k outside 1 .. 64, L == 0,
+ * packed R above 2^31 - 1 (index holds global rows as int32; the padded form holds rows of the entry, any n * L).
+ * n == 0 or R == 0: FCZ_OK (packed, n == 0 < R: every row is uncovered and is filled). The time goes to a group of its own,
+ * "knn", for both forms. */
+int fcz_knn_pass(void);
+int fcz_knn_dev(fcz_ctx* ctx, const float* pos_dev, const uint8_t* mask_dev, const uint32_t* length_dev, uint32_t n, uint32_t L,
+                int layout, int slot, uint32_t k, int32_t* index_dev, float* dist_dev);
+int fcz_knn_packed_dev(fcz_ctx* ctx, const float* pos_dev, const uint8_t* mask_dev, const uint32_t* row_off_dev, uint32_t n,
+                       uint32_t R, int layout, int slot, uint32_t k, int32_t* index_dev, float* dist_dev);
+/* Host-pointer conveniences: the same arrays on the host, staged through the ctx like fcz_decompress_dense; synchronous. */
+int fcz_knn(fcz_ctx* ctx, const float* pos, const uint8_t* mask, const uint32_t* length, uint32_t n, uint32_t L, int layout,
+            int slot, uint32_t k, int32_t* index, float* dist);
+int fcz_knn_packed(fcz_ctx* ctx, const float* pos, const uint8_t* mask, const uint32_t* row_off, uint32_t n, uint32_t R,
+                   int layout, int slot, uint32_t k, int32_t* index, float* dist);
+
 /* ---- torsion-angle tensors: the record's internal coordinates, no reconstruction ------------------------ */
 /* What Foldcomp::decompress dequantises before it places an atom (src/foldcomp.cpp:784-804: the backbone torsions and bond angles of
  * every packed word; :338-369 for the side-chain torsion bytes) and the FCZ branch of foldcomp.cxx's get_data returns as Python lists
@@ -639,7 +679,7 @@ int fcz_check(const uint8_t* entry, uint64_t len);
  * group since the last reset: "compress_sizes", "compress_index", "compress_angles", "compress_pack",
  * "decompress_sizes", "decompress_backbone", "decompress_index", "decompress_sidechain", "pdb_sizes", "pdb_format", "extract_sizes", "extract",
  * "ingest_parse", "ingest_parse_cif", "ingest_rows_cif", "ingest_frags", "ingest_fill", "inflate", "dense", "undense" (the counting and the fill
- * kernel of fcz_undense_dev: two launches per call), "angles" (fcz_angles_dev). Every packed or windowed entry point is timed under the
+ * kernel of fcz_undense_dev: two launches per call), "angles" (fcz_angles_dev), "knn" (fcz_knn_dev and fcz_knn_packed_dev). Every other packed or windowed entry point is timed under the
  * group of its padded form: fcz_dense_packed_dev and fcz_dense_window_dev under "dense", fcz_undense_packed_dev under "undense",
  * fcz_angles_packed_dev and fcz_angles_window_dev under "angles". */
 int  fcz_ctx_enable_timing(fcz_ctx* ctx, int enable);

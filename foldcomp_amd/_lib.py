@@ -84,6 +84,11 @@ def load():
         "fcz_knn_packed_dev": (i32, [vp, vp, vp, vp, u32, u32, i32, i32, u32, vp, vp]),
         "fcz_knn": (i32, [vp, vp, vp, vp, u32, u32, i32, i32, u32, vp, vp]),
         "fcz_knn_packed": (i32, [vp, vp, vp, vp, u32, u32, i32, i32, u32, vp, vp]),
+        "fcz_frames_width": (i32, [i32]),
+        "fcz_frame_atom": (i32, [i32, i32, i32]),
+        "fcz_frame_ambiguous": (i32, [i32, i32]),
+        "fcz_frames_dev": (i32, [vp, vp, vp, vp, vp, u32, u32, i32, i32, vp, vp, vp]),
+        "fcz_frames": (i32, [vp, vp, vp, vp, vp, u32, u32, i32, i32, vp, vp, vp]),
         "fcz_chi_atom": (i32, [i32, i32]),
         "fcz_angles_dev": (i32, [vp, vp, vp, u32, vp, u32, vp, vp]),
         "fcz_angles_packed_dev": (i32, [vp, vp, vp, u32, vp, vp, vp]),
@@ -141,6 +146,7 @@ EXPORTS = ["fcz_ctx_create", "fcz_ctx_destroy", "fcz_ctx_stream", "fcz_ctx_synch
            "fcz_chi_atom", "fcz_angles_dev", "fcz_angles_packed_dev", "fcz_decompress_angles", "fcz_decompress_angles_packed",
            "fcz_dense_window_dev", "fcz_decompress_dense_window", "fcz_angles_window_dev", "fcz_decompress_angles_window",
            "fcz_knn_pass", "fcz_knn_dev", "fcz_knn_packed_dev", "fcz_knn", "fcz_knn_packed",
+           "fcz_frames_width", "fcz_frame_atom", "fcz_frame_ambiguous", "fcz_frames_dev", "fcz_frames",
            "fcz_extract_sizes", "fcz_extract",
            "fcz_extract_sizes_dev", "fcz_extract_dev", "fcz_ingest_pdb_dev", "fcz_ingest_pdb_begin", "fcz_ingest_pdb_fetch", "fcz_ingest_chain_names_fetch",
            "fcz_compress_pdb_begin", "fcz_compress_pdb_fetch", "fcz_inflate_sizes", "fcz_inflate_dev", "fcz_inflate",

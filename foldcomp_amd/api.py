@@ -243,7 +243,7 @@ class FoldcompDatabase:
     def tensor_batches(self, batch_size: int = 1024, *, layout="atom37", max_len: Optional[int] = None, device="cuda:0",
                        sort_by_length: bool = False, packed: bool = False, max_residues: Optional[int] = None,
                        angles: bool = False, crop: Optional[str] = None, seed: Optional[int] = None,
-                       neighbors: Optional[int] = None, neighbor_atom="CA"):
+                       neighbors: Optional[int] = None, neighbor_atom="CA", frames: Optional[str] = None):
         """Generator over the database (its `ids` selection when it has one) in batches of dense model-input tensors on the GPU:
         the dicts of foldcomp_amd.tensors.decode_tensors, each with `names` (the records' titles) and `index` (int64 array: the
         entries' positions in this database, what db[i] takes). sort_by_length orders every window of 16 * batch_size entries by
@@ -256,8 +256,11 @@ class FoldcompDatabase:
         generator for the whole iteration, seeded once with `seed` (None: from the system), so the same seed gives the same crops.
         neighbors=k adds the k-nearest-neighbour graph of every chain, `nbr_index` / `nbr_dist`, on the sites of `neighbor_atom`
         (decode_tensors(neighbors=k)); like the other argument rules, a bad k or atom raises at the first next(), before a record
-        is read."""
+        is read. frames="backbone" | "all" adds the rigid frames `rot` / `trans` / `frame_mask` (decode_tensors(frames=...)), checked
+        at the first next() too."""
         from .tensors import decode_tensors
+        if frames is not None:
+            check_frames(frames)
         if neighbors is not None:
             check_neighbors(neighbors, neighbor_atom, {0: 37, 1: 14, 2: 4}[dense_layout(layout)])
         batch_size = int(batch_size)
@@ -279,14 +282,14 @@ class FoldcompDatabase:
                 sel = np.asarray(sel, np.int64)
                 if packed:
                     d = decode_tensors([ents[k] for k in sel], layout=layout, device=device, packed=True, angles=angles,
-                                       neighbors=neighbors, neighbor_atom=neighbor_atom)
+                                       neighbors=neighbors, neighbor_atom=neighbor_atom, frames=frames)
                 else:
                     if crop == "random" and gen is None:
                         import torch
                         gen = torch.Generator(device=device)
                         gen.manual_seed(int(seed)) if seed is not None else gen.seed()
                     d = decode_tensors([ents[k] for k in sel], layout=layout, max_len=max_len, device=device, angles=angles, crop=crop,
-                                       generator=gen, neighbors=neighbors, neighbor_atom=neighbor_atom)
+                                       generator=gen, neighbors=neighbors, neighbor_atom=neighbor_atom, frames=frames)
                 d["index"] = idx[sel]
                 yield d
 
@@ -351,6 +354,28 @@ def check_neighbors(k, atom, width=None):
     if width is not None and width not in (37, 14, 4):
         raise ValueError(f"no dense layout has {width} slots per residue (37, 14 or 4)")
     return int(atom)
+
+
+# the rigid groups of groups="all", indexed like AlphaFold / OpenFold rigidgroups_gt_frames (include/fcz_hip.h, fcz_frames_dev)
+FRAME_GROUPS = ("backbone", "unused_1", "unused_2", "psi", "chi1", "chi2", "chi3", "chi4")
+FRAME_GROUP_SETS = {"backbone": 0, "all": 1}                                 # enum fcz_frame_groups
+
+
+def check_frames(groups, has_aatype=True):
+    """the argument rules of frames= / rigid_frames that need no device -> enum fcz_frame_groups: "backbone" or "all"; "all" reads
+    the residue types"""
+    if not isinstance(groups, str) or groups not in FRAME_GROUP_SETS:
+        raise ValueError(f"groups must be one of {', '.join(repr(g) for g in FRAME_GROUP_SETS)}, not {groups!r}")
+    if groups == "all" and not has_aatype:
+        raise ValueError("groups='all' needs aatype: the chi groups depend on the residue type")
+    return FRAME_GROUP_SETS[groups]
+
+
+def frame_ambiguous():
+    """bool [21, 8]: table[aatype] is rigidgroups_group_is_ambiguous -- the groups whose frame has an alternative, rot @ diag(1, -1, -1),
+    under the 180-degree symmetric renamings (chi2 of ASP, PHE, TYR; chi3 of GLU); row 20 (any other type) has none"""
+    lib = _lib.load()
+    return np.array([[bool(lib.fcz_frame_ambiguous(t, g)) if t < 20 else False for g in range(8)] for t in range(21)], dtype=bool)
 
 
 def cut_batches(lengths, batch_size: int, max_residues: Optional[int] = None, sort_by_length: bool = False) -> list:

@@ -232,6 +232,51 @@ class Codec:
                           index.ctypes.data, dist.ctypes.data), "fcz_knn_packed" if packed else "fcz_knn")
         return dict(index=index, dist=dist)
 
+    def frames(self, pos: np.ndarray, mask: np.ndarray, aatype=None, length=None, layout=None, groups="backbone"):
+        """dense arrays on the host -> the rigid frames of every residue (fcz_frames): rot float32 [.., 3, 3], trans [.., 3] and
+        frame_mask bool [..] for groups="backbone", [.., 8, 3, 3] / [.., 8, 3] / [.., 8] for "all" (which needs aatype). pos float32
+        [n, L, A, 3] with mask [n, L, A], aatype [n, L] and optionally length [n]; or the packed pos [R, A, 3], mask [R, A], aatype [R].
+        layout: inferred from A when None."""
+        pos = np.ascontiguousarray(pos, np.float32)
+        if pos.ndim not in (3, 4) or pos.shape[-1] != 3 or pos.shape[-2] not in (37, 14, 4):
+            raise ValueError(f"pos must be float32 [n, L, A, 3] or [R, A, 3] with A = 37, 14 or 4, not {pos.shape}")
+        A = pos.shape[-2]
+        lay = {37: 0, 14: 1, 4: 2}[A]
+        if layout is not None and dense_layout(layout) != lay:
+            raise ValueError(f"layout {layout!r} does not have {A} slots per residue")
+        if groups not in ("backbone", "all"):
+            raise ValueError(f"groups must be 'backbone' or 'all', not {groups!r}")
+        fgroups = 1 if groups == "all" else 0
+        mask = np.ascontiguousarray(mask)
+        if mask.shape != pos.shape[:-1] or mask.dtype not in (np.bool_, np.uint8):
+            raise ValueError(f"mask must be bool / uint8 {pos.shape[:-1]}, not {mask.dtype} {mask.shape}")
+        rows = pos.shape[:-2]
+        if aatype is None:
+            if fgroups:
+                raise ValueError("groups='all' needs aatype: the chi groups depend on the residue type")
+        else:
+            aatype = np.ascontiguousarray(aatype, np.uint8)
+            if aatype.shape != rows:
+                raise ValueError(f"aatype must be uint8 {rows}, not {aatype.shape}")
+        n, L = (1, rows[0]) if len(rows) == 1 else rows
+        bound = None
+        if length is not None:
+            if len(rows) == 1:
+                raise ValueError("the packed form takes no length")
+            bound = np.ascontiguousarray(length, np.uint32)
+            if bound.shape != (n,):
+                raise ValueError(f"length must be [{n}], not {bound.shape}")
+        g = (8,) if fgroups else ()
+        rot = np.zeros(rows + g + (3, 3), np.float32)
+        rot[..., 0, 0] = rot[..., 1, 1] = rot[..., 2, 2] = 1.0
+        trans = np.zeros(rows + g + (3,), np.float32)
+        fm = np.zeros(rows + g, np.uint8)
+        if fm.size:
+            _lib.check(self.lib.fcz_frames(self.ctx, pos.ctypes.data, mask.ctypes.data, None if aatype is None else aatype.ctypes.data,
+                                           None if bound is None else bound.ctypes.data, n, L, lay, fgroups, rot.ctypes.data, trans.ctypes.data,
+                                           fm.ctypes.data), "fcz_frames")
+        return dict(rot=rot, trans=trans, frame_mask=fm.view(np.bool_))
+
     def decompress_angles(self, blob: np.ndarray, off: np.ndarray, L: int = 0, packed: bool = False, start=None):
         """FCZ entries -> the record's internal coordinates on the host (fcz_decompress_angles): angles float32 [n, L, 10] in degrees
         (ANGLE_COLUMNS), angle_mask bool [n, L, 10], status int32 [n]; L = 0: the longest entry of the batch, longer entries are

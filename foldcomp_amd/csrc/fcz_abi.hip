@@ -33,6 +33,7 @@
 #include "fcz_dense.h"
 #include "fcz_undense.h"
 #include "fcz_knn.h"
+#include "fcz_frames.h"
 #include "fcz_angles.h"
 
 // second, host-side instance of the generated tables (integer metadata for sizes/validation)
@@ -158,6 +159,7 @@ struct fcz_ctx {
     //   fcz_compress_dense_begin_dev                KEPT_* 13 .. 15                             KEPT_*, ud_fcz_bytes (+ ud_batch)
     //   fcz_compress_dense_packed_begin[_dev]       as the two above (DENSE_IN 3 = row_off)     the same
     //   fcz_knn / fcz_knn_packed                    DENSE_IN 0, 1, 3 (pos, mask, length / row_off), DENSE_OUT 10 .. 11 (index, dist)
+    //   fcz_frames                                  DENSE_IN 0 .. 3 (pos, mask, aatype, length), DENSE_OUT 10 .. 12 (rot, trans, frame_mask)
     dev_buf pool[POOL_COUNT];
     // PDB text / extracted data: per-entry sizes (any call), offsets (n + 1 u64) and the text of the last fcz_decompress_pdb_begin,
     // which fcz_decompress_pdb_fetch reads: live until the next fcz_decompress_pdb_begin / _sizes or fcz_extract
@@ -1732,6 +1734,106 @@ int fcz_knn_packed(fcz_ctx* ctx, const float* pos, const uint8_t* mask, const ui
                    int32_t* index, float* dist) {
     if (!knn_args_ok(ctx, pos, mask, layout, slot, k, index, dist) || (n && !row_off) || R > 0x7FFFFFFFu) return FCZ_E_INVALID_ARG;
     return knn_host(ctx, pos, mask, row_off, true, n, R, layout, slot, k, index, dist);
+}
+
+// ------------------------------------------------------------------------------------------------
+// rigid frames of dense tensors (fcz_frames.h; no counterpart in the reference)
+// ------------------------------------------------------------------------------------------------
+int fcz_frames_width(int groups) { return groups == FCZ_FRAMES_BACKBONE ? 1 : groups == FCZ_FRAMES_ALL ? 8 : -1; }
+
+int fcz_frame_atom(int rc, int group, int j) {
+    if (rc < 0 || rc >= FCZ_N_RES_CODES || group < 0 || group >= (int)FR_GROUPS || j < 0 || j > 2) return -1;
+    static const int backbone[3] = {2, 1, 0}, psi[3] = {1, 2, 3};             // (C, CA, N) and (CA, C, O): atom codes 0 .. 3 are N, CA, C, O
+    if (group == 0) return backbone[j];
+    if (group == 3) return psi[j];
+    if (group < 4) return -1;
+    const int k = group - 4;
+    if (fcz_chi_atom(rc, k) < 0) return -1;
+    const int c = k + 1 + j;                                                  // position in the chain N, CA, CB, X1 .. X4
+    return c == 0 ? 0 : c == 1 ? 1 : c == 2 ? 4 : fcz_chi_atom(rc, c - 3);    // (atom code 4 is CB)
+}
+
+int fcz_frame_ambiguous(int rc, int group) {
+    // the types whose chi ends in two atoms that a 180-degree turn exchanges: ASP OD1 / OD2, PHE and TYR CD1 / CD2 (chi2), GLU OE1 / OE2 (chi3)
+    return ((rc == 3 || rc == 13 || rc == 18) && group == 5) || (rc == 6 && group == 6) ? 1 : 0;
+}
+
+// the kernel's table: slots of the three defining atoms per (type, group) in the layout
+static frames_table frames_make_table(int layout) {
+    frames_table t;
+    memset(t.slot, 255, sizeof t.slot);
+    for (int ty = 0; ty < (int)FR_TYPES; ty++)
+        for (int g = 0; g < (int)FR_GROUPS; g++) {
+            if (g >= 4 && ty >= 20) continue;
+            int s[3];
+            bool all = true;
+            for (int j = 0; j < 3; j++) {
+                const int ac = fcz_frame_atom(ty < 20 ? ty : 0, g, j);
+                // N, CA, C, O have the same slot in every type: groups 0 and 3 are read through ALA, so a type without an O of its own keeps them
+                s[j] = ac < 0 ? -1 : fcz_dense_slot(layout, g < 4 ? 0 : ty, ac);
+                all = all && s[j] >= 0;
+            }
+            if (all) for (int j = 0; j < 3; j++) t.slot[ty][g][j] = (uint8_t)s[j];
+        }
+    return t;
+}
+
+static bool frames_args_ok(const fcz_ctx* ctx, const float* pos, const uint8_t* mask, const uint8_t* aatype, uint32_t L, int layout, int groups,
+                           const float* rot, const float* trans, const uint8_t* frame_mask) {
+    return ctx && pos && mask && rot && trans && frame_mask && fcz_dense_width(layout) > 0 && fcz_frames_width(groups) > 0 &&
+           (aatype || groups == FCZ_FRAMES_BACKBONE) && L != 0;
+}
+
+static int frames_rows(fcz_ctx* ctx, const float* pos_dev, const uint8_t* mask_dev, const uint8_t* aatype_dev, const uint32_t* length_dev, uint32_t n,
+                       uint32_t L, int layout, int groups, float* rot_dev, float* trans_dev, uint8_t* frame_mask_dev) {
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (n == 0) return FCZ_OK;
+    const frames_args g{pos_dev, mask_dev, aatype_dev, length_dev, (uint64_t)n * L, L, rot_dev, trans_dev, frame_mask_dev};
+    const uint32_t G = (uint32_t)fcz_frames_width(groups), T = FR_ITEMS / G;
+    const uint64_t n_tiles = (g.rows + T - 1) / T;
+    const uint32_t blocks = (uint32_t)std::min<uint64_t>(n_tiles, (uint64_t)ctx->n_cu * 8u);
+    const frames_table tab = frames_make_table(layout);
+    span_guard sg(ctx, "frames");
+    dispatch_layout(layout, [&](auto A) {
+        if (G == 1) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_frames<decltype(A)::value, 1>), dim3(blocks), dim3(BLOCK), 0, ctx->stream, g, n_tiles, tab);
+        else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_frames<decltype(A)::value, 8>), dim3(blocks), dim3(BLOCK), 0, ctx->stream, g, n_tiles, tab);
+    });
+    HIP_TRY(hipGetLastError());
+    return FCZ_OK;
+}
+
+int fcz_frames_dev(fcz_ctx* ctx, const float* pos_dev, const uint8_t* mask_dev, const uint8_t* aatype_dev, const uint32_t* length_dev, uint32_t n, uint32_t L,
+                   int layout, int groups, float* rot_dev, float* trans_dev, uint8_t* frame_mask_dev) {
+    if (!frames_args_ok(ctx, pos_dev, mask_dev, aatype_dev, L, layout, groups, rot_dev, trans_dev, frame_mask_dev)) return FCZ_E_INVALID_ARG;
+    return frames_rows(ctx, pos_dev, mask_dev, aatype_dev, length_dev, n, L, layout, groups, rot_dev, trans_dev, frame_mask_dev);
+}
+
+// the host arrays through DENSE_IN 0 .. 3 and DENSE_OUT 10 .. 12
+int fcz_frames(fcz_ctx* ctx, const float* pos, const uint8_t* mask, const uint8_t* aatype, const uint32_t* length, uint32_t n, uint32_t L, int layout,
+               int groups, float* rot, float* trans, uint8_t* frame_mask) {
+    if (!frames_args_ok(ctx, pos, mask, aatype, L, layout, groups, rot, trans, frame_mask)) return FCZ_E_INVALID_ARG;
+    HIP_TRY(hipSetDevice(ctx->device));
+    claim_staging(ctx);
+    const size_t rows = (size_t)n * L, A = (size_t)fcz_dense_width(layout), G = (size_t)fcz_frames_width(groups);
+    if (rows == 0) return FCZ_OK;
+    const size_t in_bytes[4] = {rows * A * 3 * sizeof(float), rows * A, aatype ? rows : 0, length ? sizeof(uint32_t) * (size_t)n : 0};
+    const void* in_host[4] = {pos, mask, aatype, length};
+    const size_t out_bytes[3] = {rows * G * 9 * sizeof(float), rows * G * 3 * sizeof(float), rows * G};
+    void* out_host[3] = {rot, trans, frame_mask};
+    int rc;
+    for (int i = 0; i < 4; i++) {
+        if ((rc = ctx->pool[DENSE_IN + i].ensure(in_bytes[i]))) return rc;
+        if (in_bytes[i]) HIP_TRY(hipMemcpyAsync(ctx->pool[DENSE_IN + i].p, in_host[i], in_bytes[i], hipMemcpyHostToDevice, ctx->stream));
+    }
+    for (int i = 0; i < 3; i++)
+        if ((rc = ctx->pool[DENSE_OUT + i].ensure(out_bytes[i]))) return rc;
+    rc = frames_rows(ctx, ctx->pool[DENSE_IN].as<float>(), ctx->pool[DENSE_IN + 1].as<uint8_t>(), aatype ? ctx->pool[DENSE_IN + 2].as<uint8_t>() : nullptr,
+                     length ? ctx->pool[DENSE_IN + 3].as<uint32_t>() : nullptr, n, L, layout, groups, ctx->pool[DENSE_OUT].as<float>(),
+                     ctx->pool[DENSE_OUT + 1].as<float>(), ctx->pool[DENSE_OUT + 2].as<uint8_t>());
+    if (rc) return rc;
+    for (int i = 0; i < 3; i++) HIP_TRY(hipMemcpyAsync(out_host[i], ctx->pool[DENSE_OUT + i].p, out_bytes[i], hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return FCZ_OK;
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -12,6 +12,8 @@
     crop_starts(length, L, how, generator) -> the starts of such a crop, on the device the lengths lie on
     neighbor_graph(either dict, or the tensors as keywords, k=48, atom="CA") -> dict(nbr_index [.., k] int32, nbr_dist [.., k] float32):
                                    the k nearest CA / CB sites of every residue inside its chain; decode_tensors(neighbors=k) adds them
+    rigid_frames(either dict, or the tensors as keywords, groups="backbone" | "all") -> dict(rot [.., 3, 3], trans [.., 3], frame_mask):
+                                   every residue's backbone frame, or the eight rigid groups; decode_tensors(frames=...) adds them
 
 What a structure model's data loader wants from a Foldcomp database (atom37 / atom14 coordinates with a mask, residue types,
 pLDDT), without the PDB text `foldcomp.decompress` returns and without a host copy of the result: the records go up once, torch
@@ -34,7 +36,7 @@ from ._aa_tables import RES1
 from .codec import ANGLE_COLUMNS, Codec, dense_layout
 from .structure import CAtomsOut, CDenseIn, CDenseOut, CPackedOut
 
-__all__ = ["decode_tensors", "encode_tensors", "decode_angles", "crop_starts", "neighbor_graph"]
+__all__ = ["decode_tensors", "encode_tensors", "decode_angles", "crop_starts", "neighbor_graph", "rigid_frames"]
 
 
 def crop_starts(length, L: int, how, generator=None):
@@ -237,7 +239,7 @@ def decode_angles(entries: Sequence[bytes], *, max_len: Optional[int] = None, pa
 
 def decode_tensors(entries: Sequence[bytes], *, layout="atom37", max_len: Optional[int] = None, device="cuda:0",
                    codec: Optional[Codec] = None, packed: bool = False, angles: bool = False, crop=None, generator=None,
-                   neighbors: Optional[int] = None, neighbor_atom="CA") -> dict:
+                   neighbors: Optional[int] = None, neighbor_atom="CA", frames: Optional[str] = None) -> dict:
     """[fcz, ...] -> dict of torch tensors on `device` plus `names` (the records' titles, a Python list).
 
     layout: "atom37" (A = 37, AlphaFold / OpenFold atom order, the chain's OXT in slot 36 of its last residue), "atom14" (A = 14,
@@ -265,6 +267,11 @@ def decode_tensors(entries: Sequence[bytes], *, layout="atom37", max_len: Option
     float32, as neighbor_graph describes them, on the sites of neighbor_atom ("CA", "CB" or a slot). With crop the graph is the
     window's own. neighbors=None: the dict has no new key.
 
+    frames="backbone" | "all" adds the rigid frames of the tensors just written, in either form, with no host round trip
+    (fcz_frames_dev on the codec's stream behind the dense call): rot [n, L, 3, 3] / [R, 3, 3], trans [.., 3] float32 and frame_mask
+    [..] bool for "backbone", rot [.., 8, 3, 3], trans [.., 8, 3], frame_mask [.., 8] for "all", as rigid_frames describes them.
+    frames=None: the dict has no new key.
+
     Ordering against torch: the uploads and allocations are made on torch's current stream, which is synchronised before the
     codec's calls; the codec works on its own stream, which is synchronised before the tensors are returned. No output byte
     visits the host.
@@ -273,6 +280,7 @@ def decode_tensors(entries: Sequence[bytes], *, layout="atom37", max_len: Option
     nbr = None
     if neighbors is not None:
         nbr = (int(neighbors), api.check_neighbors(neighbors, neighbor_atom, _LAYOUT_WIDTH[dense_layout(layout)]))
+    fgroups = None if frames is None else api.check_frames(frames)
     torch, dev = _torch_device(device)
     c = codec or api.default_codec()
     if int(c.device) != dev.index:
@@ -313,12 +321,15 @@ def decode_tensors(entries: Sequence[bytes], *, layout="atom37", max_len: Option
             return {}
         return dict(nbr_index=torch.empty(rows + (nbr[0],), dtype=torch.int32, device=dev), nbr_dist=torch.empty(rows + (nbr[0],), dtype=torch.float32, device=dev))
 
+    def frames_alloc(*rows):   # frames=None: no key
+        return {} if fgroups is None else _frames_alloc(torch, dev, rows, fgroups)
+
     if n == 0:
         if packed:
-            d = dict(packed_result(0, torch.zeros(1, dtype=torch.int32, device=dev), 0)[1], **nbr_alloc(0))
+            d = dict(packed_result(0, torch.zeros(1, dtype=torch.int32, device=dev), 0)[1], **nbr_alloc(0), **frames_alloc(0))
             return dict(d, **no_angles(0)) if angles else d
         L = int(max_len or 0)
-        d = dict(result(L, *alloc(L)), **nbr_alloc(0, L))
+        d = dict(result(L, *alloc(L)), **nbr_alloc(0, L), **frames_alloc(0, L))
         if crop is not None:
             d["crop_start"] = crop_starts(d["length"], L, crop, generator)
         return dict(d, **no_angles(0, L)) if angles else d
@@ -327,7 +338,7 @@ def decode_tensors(entries: Sequence[bytes], *, layout="atom37", max_len: Option
     if packed:
         # (the angle call is enqueued in front of the decode and leaves it the sizes memo; _decode_packed synchronises the codec)
         extra = _angles_into(c, torch, dev, n, blob_t, off_t, res_off_t, 0, Rv) if angles else {}
-        d = _decode_packed(c, torch, dev, lay, n, Rv, Mv, blob_t, off_t, res_off_t, atom_off_t, packed_result, nbr, nbr_alloc)
+        d = _decode_packed(c, torch, dev, lay, n, Rv, Mv, blob_t, off_t, res_off_t, atom_off_t, packed_result, nbr, nbr_alloc, fgroups, frames_alloc)
         return dict(d, **extra)
     if max_len is None:
         ro = res_off_t.cpu().numpy().view(np.uint32).astype(np.int64)      # n + 1 offsets: the only words that come back
@@ -336,12 +347,14 @@ def decode_tensors(entries: Sequence[bytes], *, layout="atom37", max_len: Option
         L = int(max_len)
     out = alloc(L)
     if L == 0:                                                             # nothing decodes and no width was asked for
-        return dict(result(L, *out), **nbr_alloc(n, 0), **no_angles(n, 0)) if angles else dict(result(L, *out), **nbr_alloc(n, 0))
+        d = dict(result(L, *out), **nbr_alloc(n, 0), **frames_alloc(n, 0))
+        return dict(d, **no_angles(n, 0)) if angles else d
     start_t = None if crop is None else crop_starts(_entry_lengths(res_off_t), L, crop, generator)
     extra = _angles_into(c, torch, dev, n, blob_t, off_t, res_off_t, L, start_t=start_t) if angles else {}
     if crop is not None:
         extra["crop_start"] = start_t
     extra.update(nbr_alloc(n, L))
+    extra.update(frames_alloc(n, L))
     x, y, z = (torch.empty(max(M.value, 1), dtype=torch.float32, device=dev) for _ in range(3))
     bfac = torch.empty(max(R.value, 1), dtype=torch.float32, device=dev)
     res_code = torch.empty(max(R.value, 1), dtype=torch.uint8, device=dev)
@@ -360,19 +373,26 @@ def decode_tensors(entries: Sequence[bytes], *, layout="atom37", max_len: Option
     if nbr is not None:   # (a window's padding rows have a cleared mask: no length; otherwise the length the dense call just wrote)
         _lib.check(c.lib.fcz_knn_dev(c.ctx, out[0].data_ptr(), out[1].data_ptr(), out[5].data_ptr() if crop is None else None, n, L, lay, nbr[1], nbr[0],
                                      extra["nbr_index"].data_ptr(), extra["nbr_dist"].data_ptr()), "fcz_knn_dev")
+    if fgroups is not None:   # (as above: a window needs no length)
+        _lib.check(c.lib.fcz_frames_dev(c.ctx, out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(), out[5].data_ptr() if crop is None else None, n, L,
+                                        lay, fgroups, extra["rot"].data_ptr(), extra["trans"].data_ptr(), extra["frame_mask"].data_ptr()), "fcz_frames_dev")
     c.synchronize()
     return dict(result(L, *out), **extra)
 
 
-def _decode_packed(c, torch, dev, lay, n, R, M, blob_t, off_t, res_off_t, atom_off_t, packed_result, nbr=None, nbr_alloc=None):
+def _decode_packed(c, torch, dev, lay, n, R, M, blob_t, off_t, res_off_t, atom_off_t, packed_result, nbr=None, nbr_alloc=None, fgroups=None,
+                   frames_alloc=None):
     """the packed leg of decode_tensors behind fcz_decompress_sizes_dev: R and M are its totals, res_off_t becomes cu_seqlens;
-    nbr = (k, slot): the neighbour graph of the rows behind the dense call (nbr_alloc makes its tensors)"""
+    nbr = (k, slot): the neighbour graph of the rows behind the dense call (nbr_alloc makes its tensors); fgroups: their rigid
+    frames (frames_alloc makes the tensors)"""
     if R > 2 ** 31 - 1:
         raise api.error(f"decode_tensors: {R} residues do not fit the int32 cu_seqlens; split the batch")
     ro = res_off_t.cpu().numpy().view(np.uint32).astype(np.int64)          # n + 1 offsets: the only words that come back
     out, d = packed_result(R, res_off_t, int(np.diff(ro).max()))
     if nbr is not None:
         d.update(nbr_alloc(R))
+    if fgroups is not None:
+        d.update(frames_alloc(R))
     if R == 0:                                                             # nothing decodes: no row, length stays 0
         return d
     x, y, z = (torch.empty(max(M, 1), dtype=torch.float32, device=dev) for _ in range(3))
@@ -388,6 +408,9 @@ def _decode_packed(c, torch, dev, lay, n, R, M, blob_t, off_t, res_off_t, atom_o
     if nbr is not None:
         _lib.check(c.lib.fcz_knn_packed_dev(c.ctx, out[0].data_ptr(), out[1].data_ptr(), res_off_t.data_ptr(), n, R, lay, nbr[1], nbr[0],
                                             d["nbr_index"].data_ptr(), d["nbr_dist"].data_ptr()), "fcz_knn_packed_dev")
+    if fgroups is not None:   # (the packed form: one entry of R rows, no length)
+        _lib.check(c.lib.fcz_frames_dev(c.ctx, out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(), None, 1, R, lay, fgroups,
+                                        d["rot"].data_ptr(), d["trans"].data_ptr(), d["frame_mask"].data_ptr()), "fcz_frames_dev")
     c.synchronize()
     return d
 
@@ -476,6 +499,87 @@ def neighbor_graph(batch=None, *, k: int = 48, atom="CA", codec: Optional[Codec]
         torch.cuda.current_stream(dev).synchronize()
         _lib.check(c.lib.fcz_knn_dev(c.ctx, pos.data_ptr(), mask.data_ptr(), None if bound is None else bound.data_ptr(), n, L, lay, slot, k,
                                      index.data_ptr(), dist.data_ptr()), "fcz_knn_dev")
+    c.synchronize()
+    return out
+
+
+def _frames_alloc(torch, dev, rows, fgroups):
+    """the three output tensors of fcz_frames_dev for the leading shape `rows`; frame_mask is written as 0 / 1 bytes"""
+    g = () if fgroups == 0 else (8,)
+    return dict(rot=torch.empty(tuple(rows) + g + (3, 3), dtype=torch.float32, device=dev),
+                trans=torch.empty(tuple(rows) + g + (3,), dtype=torch.float32, device=dev),
+                frame_mask=torch.empty(tuple(rows) + g, dtype=torch.uint8, device=dev).view(torch.bool))
+
+
+def rigid_frames(batch=None, *, groups="backbone", codec: Optional[Codec] = None, **tensors) -> dict:
+    """dense tensors on the GPU -> dict(rot, trans, frame_mask): every residue as rigid transforms, global = rot @ local + trans.
+
+    `batch` is the dict decode_tensors / tensor_batches return, padded or packed, or the tensors come as keywords: pos
+    [n, L, A, 3] float32, mask [n, L, A] bool or uint8, aatype [n, L] uint8 (needed for "all"), optionally length [n]; or the packed
+    pos [R, A, 3], mask [R, A], aatype [R] (recognised by the shape of pos: frames use atoms of their own row only, so cu_seqlens is
+    not read). groups="backbone": rot [n, L, 3, 3], trans [n, L, 3], frame_mask [n, L] bool -- AlphaFold's Algorithm 21 on (N, CA,
+    C): origin CA, x axis CA -> C, N in the xy half-plane y > 0. groups="all": rot [n, L, 8, 3, 3], trans [n, L, 8, 3], frame_mask
+    [n, L, 8], indexed like rigidgroups_gt_frames (FRAME_GROUPS: backbone, two unused groups, psi, chi1 .. chi4);
+    frame_ambiguous()[aatype] tells which of them have a 180-degree alternative, rot @ diag(1, -1, -1). The packed form has [R]
+    in place of [n, L]. A group exists where the row lies inside its chain, the type and the layout have its three atoms, their
+    masks are set, their coordinates finite and they are neither coincident nor collinear; elsewhere rot is the identity, trans 0,
+    frame_mask False. The arithmetic is float32 in a fixed order (include/fcz_hip.h), so the result is reproducible bit for bit.
+
+    Padded: `length` is used when the dict has no crop_start (as neighbor_graph does). The tensors must be contiguous and lie on
+    the codec's device; ordering against torch is decode_tensors'. groups is checked first, without a device."""
+    d = dict(batch) if batch is not None else {}
+    d.update(tensors)
+    fgroups = api.check_frames(groups, d.get("aatype") is not None)
+    pos = d.get("pos")
+    for key in ("pos", "mask"):
+        if d.get(key) is None:
+            raise TypeError(f"rigid_frames needs the tensor {key!r}")
+    shape = tuple(getattr(pos, "shape", ()))
+    if len(shape) not in (3, 4) or shape[-1] != 3 or shape[-2] not in _WIDTH_LAYOUT:
+        raise ValueError(f"pos must be float32 [n, L, A, 3] or [R, A, 3] with A = 37, 14 or 4, not {shape}")
+    c = codec or api.default_codec()
+    try:
+        import torch
+    except ImportError as e:
+        raise api.error(f"rigid_frames needs PyTorch (ROCm build): {e}") from None
+    if not isinstance(pos, torch.Tensor):
+        raise api.error("rigid_frames takes torch tensors on the GPU (numpy arrays: Codec.frames)")
+    if pos.device.type != "cuda" or pos.device.index != int(c.device):
+        raise api.error(f"rigid_frames: pos lies on {pos.device}, the codec works on cuda:{int(c.device)}; there is no CPU path")
+    dev = pos.device
+    lay = dense_layout(_WIDTH_LAYOUT[shape[-2]])
+    rows = shape[:-2]
+
+    def on_device(key, t, want, dtypes):
+        if not isinstance(t, torch.Tensor) or t.device != dev:
+            where = t.device if isinstance(t, torch.Tensor) else type(t).__name__
+            raise api.error(f"rigid_frames: {key} lies on {where}, pos on {dev}; every tensor must be on the codec's device")
+        if tuple(t.shape) != want or t.dtype not in dtypes:
+            raise ValueError(f"{key} must be {' / '.join(str(x) for x in dtypes)} {want}, not {t.dtype} {tuple(t.shape)}")
+        if not t.is_contiguous():
+            raise ValueError(f"rigid_frames: {key} must be contiguous")
+        return t
+
+    on_device("pos", pos, shape, (torch.float32,))
+    mask = on_device("mask", d["mask"], shape[:-1], (torch.bool, torch.uint8)).view(torch.uint8)
+    aatype = None
+    if fgroups != 0:
+        aatype = on_device("aatype", d["aatype"], rows, (torch.uint8,))
+    out = _frames_alloc(torch, dev, rows, fgroups)
+    if len(rows) == 1:
+        n, L, bound = 1, rows[0], None
+    else:
+        n, L = rows
+        bound = None
+        if d.get("length") is not None and d.get("crop_start") is None:
+            # (int32 >= 0 and uint32 share their bits; a negative length is no row)
+            bound = on_device("length", d["length"], (n,), (torch.int32, torch.int64)).clamp(min=0, max=2 ** 31 - 1).to(torch.int32)
+    if n == 0 or L == 0:
+        return out
+    torch.cuda.current_stream(dev).synchronize()
+    _lib.check(c.lib.fcz_frames_dev(c.ctx, pos.data_ptr(), mask.data_ptr(), None if aatype is None else aatype.data_ptr(),
+                                    None if bound is None else bound.data_ptr(), n, L, lay, fgroups, out["rot"].data_ptr(), out["trans"].data_ptr(),
+                                    out["frame_mask"].data_ptr()), "fcz_frames_dev")
     c.synchronize()
     return out
 

@@ -18,6 +18,7 @@
  *   (none: the reference stops at the flat atom vector)    fcz_dense_dev / fcz_decompress_dense, fcz_dense_packed_dev / fcz_decompress_dense_packed,
  *                                                          fcz_dense_window_dev / fcz_decompress_dense_window
  *   (none: no neighbour graph of the decoded chain)        fcz_knn_dev / fcz_knn_packed_dev, fcz_knn / fcz_knn_packed
+ *   (none: no rigid frames of the decoded chain)           fcz_frames_dev / fcz_frames
  *   Foldcomp::decompress, the dequantisation :784-804     fcz_angles_dev / fcz_angles_packed_dev, fcz_decompress_angles[_packed],
  *                                                          fcz_angles_window_dev / fcz_decompress_angles_window
  *     (get_data's FCZ branch, foldcomp/foldcomp.cxx)
@@ -451,6 +452,69 @@ int fcz_angles_window_dev(fcz_ctx* ctx, const uint8_t* blob_dev, const uint64_t*
 int fcz_decompress_angles_window(fcz_ctx* ctx, const uint8_t* blob, const uint64_t* off, uint32_t n, uint32_t L, const uint32_t* start,
                                  uint32_t* L_out, float* angles, uint8_t* mask, uint8_t* aatype, int32_t* status);
 
+/* ---- rigid frames of the dense tensors: backbone, psi and chi groups per residue -------------------------- */
+/* What frame-based models start from (invariant-point attention and FAPE, SE(3) diffusion, local-frame edge features): every
+ * residue as rigid transforms, global = rot * local + trans, built on the device from the dense tensors above. The reference has no
+ * such output; like the dense calls these stand beside Foldcomp::decompress (src/foldcomp.cpp:779) and read what fcz_dense_dev /
+ * fcz_dense_window_dev / fcz_dense_packed_dev wrote, or any tensors of those shapes.
+ * Inputs, rows = n * L: pos [rows][A][3] float32, mask [rows][A] uint8, aatype [rows] uint8 (types 0 .. 19 in the dense tensors'
+ * order = residue codes 0 .. 19; every other value is a type without chi groups), length [n] uint32 or NULL. A =
+ * fcz_dense_width(layout). The PACKED form is n = 1, L = R, length = NULL: frames use atoms of their own row only, so there is no
+ * second entry point.
+ * groups selects the output width G = fcz_frames_width(groups):
+ *   FCZ_FRAMES_BACKBONE  G = 1  group 0 only; aatype may be NULL
+ *   FCZ_FRAMES_ALL       G = 8  indexed like AlphaFold / OpenFold rigidgroups_gt_frames: 0 backbone, 1 and 2 unused (they never
+ *                               exist), 3 psi, 4 .. 7 chi1 .. chi4
+ * Every group has three defining atoms (a0, a1, a2) = fcz_frame_atom(type, group, 0 .. 2), two vectors and the origin t = a1:
+ *   group 0 backbone     (C, CA, N)                    v1 = a0 - a1 = C - CA               v2 = a2 - a1 = N - CA    t = CA
+ *   group 3 psi          (CA, C, O)                    v1 = a1 - a0 = C - CA               v2 = a2 - a1 = O - C     t = C
+ *   group 4 + k, k < 4   (c[k+1], c[k+2], c[k+3])      v1 = a1 - a0 = c[k+2] - c[k+1]      v2 = a2 - a1             t = c[k+2]
+ * where c is the chain N, CA, CB, X1, X2, X3, X4 and Xi the atom fcz_chi_atom(type, i - 1) names: chi1 has origin CB, its x axis
+ * runs CA -> CB and X1 lies in the xy half-plane y > 0. So a1 is always the origin, a2 always the atom that fixes the xy plane
+ * (local (x, y > 0, 0)), and a0 the other atom on the x axis: at local (+|v1|, 0, 0) for group 0, at (-|v1|, 0, 0) for the others.
+ * N, CA, C, O have the same slot in every type, so groups 0 and 3 are defined for every aatype value and every layout; the chi
+ * groups for types 0 .. 19 in atom37 and atom14 (backbone4 has no slot for them).
+ * A group EXISTS for a row when the row lies inside its chain (l < min(length[e], L), or always when length is NULL), the type has
+ * the group, the layout has a slot for all three atoms, their three masks are set, their nine coordinates are finite, and both
+ * norms below are finite and > 0. All arithmetic is float32, every operation rounded, no FMA, in exactly this order:
+ *   n1 = sqrt((v1x*v1x + v1y*v1y) + v1z*v1z)          e1 = v1 / n1            (three divisions)
+ *   d  = (e1x*v2x + e1y*v2y) + e1z*v2z                 u  = v2 - e1*d          (ux = v2x - e1x*d, ...)
+ *   n2 = sqrt((ux*ux + uy*uy) + uz*uz)                 e2 = u / n2
+ *   e3 = e1 x e2     (e3x = e1y*e2z - e1z*e2y, e3y = e1z*e2x - e1x*e2z, e3z = e1x*e2y - e1y*e2x)
+ * with sqrt and / the correctly rounded float32 results. Outputs, caller-owned, every byte written:
+ *   rot [rows][G][3][3] float32   rot[i][j] = e_(j+1)[i]: the columns are the axes
+ *   trans [rows][G][3] float32    the origin atom's bits
+ *   frame_mask [rows][G] uint8    1 where the group exists
+ * Where a group does not exist rot is the identity, trans 0 and the mask 0: groups 1 and 2, padding rows, rows at or behind
+ * length (whatever pos / mask / aatype hold there: they are not read as data), a NaN atom, coincident (n1 = 0) or collinear
+ * (n2 = 0) atoms, norms that overflow. For group 0 this is AlphaFold supplement Algorithm 21 on (N, CA, C); for the others it is
+ * from_3_points(neg_x = a0, origin = a1, xy_plane = a2) on the last three atoms of the chi quadruple. Negating both e1 and e3 is
+ * exact, so OpenFold's axis flip of group 0 is the same frame.
+ * Ambiguity is a table, not an output: fcz_frame_ambiguous is 1 for group 5 of ASP, PHE, TYR and group 6 of GLU, whose plane atom
+ * a2 has a partner (OD1 / OD2, CD1 / CD2, OE1 / OE2) that a 180-degree turn about the group's x axis exchanges with it. Renaming the
+ * pair keeps e1 and t and negates the in-plane direction e2, hence e3 = e1 x e2 too: the alternative frame is rot * diag(1, -1, -1)
+ * with the same trans. It is not written.
+ * Every index that scales with rows * A or rows * G is 64-bit. The time goes to the group "frames". */
+enum fcz_frame_groups { FCZ_FRAMES_BACKBONE = 0, FCZ_FRAMES_ALL = 1 };
+/* pure host: 1 / 8, -1 for an unknown value */
+int fcz_frames_width(int groups);
+/* pure host: atom code of defining atom j = 0 .. 2 of `group` (0 .. 7) in a residue of res_code (0 .. 23), in the order above: j = 1
+ * the origin, j = 2 the atom that fixes the xy plane, j = 0 the other atom on the x axis (the tail of v1 for every group but 0,
+ * where it is the head C). -1 when the type has no such group (groups 1, 2; a chi the type lacks) or an argument is out of range.
+ * Groups 0 and 3 answer (C, CA, N) and (CA, C, O) for all 24 codes. The slot is fcz_dense_slot(layout, res_code, atom) for the chi
+ * groups and the type-independent slot of N / CA / C / O (fcz_dense_slot(layout, 0, atom)) for groups 0 and 3. */
+int fcz_frame_atom(int res_code, int group, int j);
+/* pure host: 1 where the group's frame is ambiguous under the symmetric renamings above, else 0 (out-of-range arguments too) */
+int fcz_frame_ambiguous(int res_code, int group);
+/* Device-resident: every pointer a device pointer. Enqueued on the ctx stream, no synchronisation. NULL ctx / pos / mask / rot /
+ * trans / frame_mask, NULL aatype with FCZ_FRAMES_ALL, unknown layout or groups, L == 0: FCZ_E_INVALID_ARG, nothing launched;
+ * n == 0: FCZ_OK. */
+int fcz_frames_dev(fcz_ctx* ctx, const float* pos_dev, const uint8_t* mask_dev, const uint8_t* aatype_dev, const uint32_t* length_dev,
+                   uint32_t n, uint32_t L, int layout, int groups, float* rot_dev, float* trans_dev, uint8_t* frame_mask_dev);
+/* Host-pointer convenience: the same arrays on the host, staged through the ctx like fcz_knn; synchronous. */
+int fcz_frames(fcz_ctx* ctx, const float* pos, const uint8_t* mask, const uint8_t* aatype, const uint32_t* length, uint32_t n, uint32_t L,
+               int layout, int groups, float* rot, float* trans, uint8_t* frame_mask);
+
 /* ---- dense model-input tensors -> fcz_chain_batch -> FCZ records ---------------------------------------- */
 /* The way back: n chains held as the padded arrays above (a model's predictions, a filtered or re-cropped set, what fcz_dense_dev
  * wrote) become the flat structure-of-arrays batch fcz_compress_sizes_dev / fcz_compress_batch_dev take, on the device. These entry
@@ -679,7 +743,7 @@ int fcz_check(const uint8_t* entry, uint64_t len);
  * group since the last reset: "compress_sizes", "compress_index", "compress_angles", "compress_pack",
  * "decompress_sizes", "decompress_backbone", "decompress_index", "decompress_sidechain", "pdb_sizes", "pdb_format", "extract_sizes", "extract",
  * "ingest_parse", "ingest_parse_cif", "ingest_rows_cif", "ingest_frags", "ingest_fill", "inflate", "dense", "undense" (the counting and the fill
- * kernel of fcz_undense_dev: two launches per call), "angles" (fcz_angles_dev), "knn" (fcz_knn_dev and fcz_knn_packed_dev). Every other packed or windowed entry point is timed under the
+ * kernel of fcz_undense_dev: two launches per call), "angles" (fcz_angles_dev), "knn" (fcz_knn_dev and fcz_knn_packed_dev), "frames" (fcz_frames_dev). Every other packed or windowed entry point is timed under the
  * group of its padded form: fcz_dense_packed_dev and fcz_dense_window_dev under "dense", fcz_undense_packed_dev under "undense",
  * fcz_angles_packed_dev and fcz_angles_window_dev under "angles". */
 int  fcz_ctx_enable_timing(fcz_ctx* ctx, int enable);

@@ -36,7 +36,7 @@ def load():
             f"{LIB_PATH} is missing: build the HIP extension first (python -c 'import __graft_entry__ as g; g.build()' "
             "or make -C foldcomp_amd/csrc). foldcomp_amd has no CPU fallback.")
     lib = ctypes.CDLL(LIB_PATH)
-    vp, u32, i32, u64 = ctypes.c_void_p, ctypes.c_uint32, ctypes.c_int, ctypes.c_uint64
+    vp, u32, i32, u64, f32 = ctypes.c_void_p, ctypes.c_uint32, ctypes.c_int, ctypes.c_uint64, ctypes.c_float
     PB, PO = ctypes.POINTER(CChainBatch), ctypes.POINTER(CAtomsOut)
     sig = {
         "fcz_ctx_create": (i32, [i32, ctypes.POINTER(vp)]),
@@ -84,6 +84,12 @@ def load():
         "fcz_knn_packed_dev": (i32, [vp, vp, vp, vp, u32, u32, i32, i32, u32, vp, vp]),
         "fcz_knn": (i32, [vp, vp, vp, vp, u32, u32, i32, i32, u32, vp, vp]),
         "fcz_knn_packed": (i32, [vp, vp, vp, vp, u32, u32, i32, i32, u32, vp, vp]),
+        "fcz_lddt_pass": (i32, []),
+        "fcz_lddt_c2": (f32, [f32]),
+        "fcz_lddt_dev": (i32, [vp, vp, vp, vp, vp, vp, u32, u32, i32, i32, f32, vp, vp, vp, vp]),
+        "fcz_lddt_packed_dev": (i32, [vp, vp, vp, vp, vp, vp, u32, u32, i32, i32, f32, vp, vp, vp, vp]),
+        "fcz_lddt": (i32, [vp, vp, vp, vp, vp, vp, u32, u32, i32, i32, f32, vp, vp, vp, vp]),
+        "fcz_lddt_packed": (i32, [vp, vp, vp, vp, vp, vp, u32, u32, i32, i32, f32, vp, vp, vp, vp]),
         "fcz_frames_width": (i32, [i32]),
         "fcz_frame_atom": (i32, [i32, i32, i32]),
         "fcz_frame_ambiguous": (i32, [i32, i32]),
@@ -146,6 +152,7 @@ EXPORTS = ["fcz_ctx_create", "fcz_ctx_destroy", "fcz_ctx_stream", "fcz_ctx_synch
            "fcz_chi_atom", "fcz_angles_dev", "fcz_angles_packed_dev", "fcz_decompress_angles", "fcz_decompress_angles_packed",
            "fcz_dense_window_dev", "fcz_decompress_dense_window", "fcz_angles_window_dev", "fcz_decompress_angles_window",
            "fcz_knn_pass", "fcz_knn_dev", "fcz_knn_packed_dev", "fcz_knn", "fcz_knn_packed",
+           "fcz_lddt_pass", "fcz_lddt_c2", "fcz_lddt_dev", "fcz_lddt_packed_dev", "fcz_lddt", "fcz_lddt_packed",
            "fcz_frames_width", "fcz_frame_atom", "fcz_frame_ambiguous", "fcz_frames_dev", "fcz_frames",
            "fcz_extract_sizes", "fcz_extract",
            "fcz_extract_sizes_dev", "fcz_extract_dev", "fcz_ingest_pdb_dev", "fcz_ingest_pdb_begin", "fcz_ingest_pdb_fetch", "fcz_ingest_chain_names_fetch",

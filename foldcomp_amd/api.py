@@ -356,6 +356,33 @@ def check_neighbors(k, atom, width=None):
     return int(atom)
 
 
+LDDT_THRESHOLDS = (0.5, 1.0, 2.0, 4.0)
+
+
+def check_lddt(cutoff, thresholds, atom, width=None):
+    """the argument rules of lddt that need no tensors' device and no GPU -> (slot, cutoff, thresholds): cutoff a finite number > 0,
+    thresholds four numbers, none NaN (None: 0.5, 1, 2, 4), all three as float32 values; atom as check_neighbors reads it (the slot
+    is None while the layout width A is unknown)"""
+    slot = check_neighbors(1, atom, width)
+
+    def number(v):
+        return not isinstance(v, (bool, np.bool_)) and isinstance(v, (int, float, np.integer, np.floating))
+
+    with np.errstate(over="ignore"):
+        if not number(cutoff) or not np.isfinite(np.float32(cutoff)) or not np.float32(cutoff) > 0:
+            raise ValueError(f"cutoff must be a finite number > 0 (as float32), not {cutoff!r}")
+    if thresholds is None:
+        thresholds = LDDT_THRESHOLDS
+    try:
+        th = tuple(thresholds)
+    except TypeError:
+        raise ValueError(f"thresholds must be four numbers, not {thresholds!r}") from None
+    if len(th) != 4 or not all(number(v) and not np.isnan(v) for v in th):
+        raise ValueError(f"thresholds must be four numbers, none of them NaN, not {thresholds!r}")
+    with np.errstate(over="ignore"):
+        return slot, float(np.float32(cutoff)), tuple(float(np.float32(v)) for v in th)
+
+
 # the rigid groups of groups="all", indexed like AlphaFold / OpenFold rigidgroups_gt_frames (include/fcz_hip.h, fcz_frames_dev)
 FRAME_GROUPS = ("backbone", "unused_1", "unused_2", "psi", "chi1", "chi2", "chi3", "chi4")
 FRAME_GROUP_SETS = {"backbone": 0, "all": 1}                                 # enum fcz_frame_groups

@@ -232,6 +232,66 @@ class Codec:
                           index.ctypes.data, dist.ctypes.data), "fcz_knn_packed" if packed else "fcz_knn")
         return dict(index=index, dist=dist)
 
+    def lddt(self, pos_true: np.ndarray, mask_true: np.ndarray, pos_pred: np.ndarray, mask_pred=None, slot: int = 1, length=None, row_off=None,
+             cutoff: float = 15.0, thresholds=None):
+        """two sets of dense arrays of one shape on the host -> the per-residue lDDT of `pred` against `true` on the sites at `slot`
+        (fcz_lddt, or fcz_lddt_packed when row_off is given): score float32 [n, L] / [R], pairs int32 and hits int32 of the same shape,
+        score = hits / (4 * pairs), 0 where a row has no pair. pos float32 [n, L, A, 3] with mask [n, L, A] and optionally length [n];
+        or pos [R, A, 3], mask [R, A], row_off [n + 1]. mask_pred=None: every slot of pred is present. These are counts: the result
+        is reproducible bit for bit and not differentiable."""
+        pos_true = np.ascontiguousarray(pos_true, np.float32)
+        pos_pred = np.ascontiguousarray(pos_pred, np.float32)
+        packed = row_off is not None
+        if pos_true.ndim != (3 if packed else 4) or pos_true.shape[-1] != 3 or pos_true.shape[-2] not in (37, 14, 4):
+            raise ValueError(f"pos_true must be float32 {'[R, A, 3]' if packed else '[n, L, A, 3]'} with A = 37, 14 or 4, not {pos_true.shape}")
+        if pos_pred.shape != pos_true.shape:
+            raise ValueError(f"pos_pred must have the shape of pos_true, {pos_true.shape}, not {pos_pred.shape}")
+        A = pos_true.shape[-2]
+        lay = {37: 0, 14: 1, 4: 2}[A]
+        masks = []
+        for name, m in (("mask_true", mask_true), ("mask_pred", mask_pred)):
+            if m is not None:
+                m = np.ascontiguousarray(m)
+                if m.shape != pos_true.shape[:-1] or m.dtype not in (np.bool_, np.uint8):
+                    raise ValueError(f"{name} must be bool / uint8 {pos_true.shape[:-1]}, not {m.dtype} {m.shape}")
+            masks.append(m)
+        if masks[0] is None:
+            raise ValueError("mask_true is needed")
+        slot = int(slot)
+        if not 0 <= slot < A:
+            raise ValueError(f"slot must be 0 .. {A - 1}")
+        cutoff = np.float32(cutoff)
+        if not np.isfinite(cutoff) or not cutoff > 0:
+            raise ValueError("cutoff must be finite and > 0")
+        th = None
+        if thresholds is not None:
+            th = np.ascontiguousarray(thresholds, np.float32)
+            if th.shape != (4,) or np.isnan(th).any():
+                raise ValueError("thresholds must be four numbers, none of them NaN")
+        bound = None
+        if packed:
+            bound = np.ascontiguousarray(row_off, np.uint32)
+            n, rows = len(bound) - 1, pos_true.shape[0]
+            if bound.ndim != 1 or n < 0:
+                raise ValueError("row_off must be [n + 1]")
+        else:
+            n, rows = pos_true.shape[0], pos_true.shape[1]
+            if length is not None:
+                bound = np.ascontiguousarray(length, np.uint32)
+                if bound.shape != (n,):
+                    raise ValueError(f"length must be [{n}], not {bound.shape}")
+        if rows > 2 ** 29:
+            raise ValueError("hits must fit int32: at most 2^29 rows per chain")
+        score = np.zeros(pos_true.shape[:-2], np.float32)
+        pairs = np.zeros(pos_true.shape[:-2], np.int32)
+        hits = np.zeros(pos_true.shape[:-2], np.int32)
+        if score.size:
+            fn = self.lib.fcz_lddt_packed if packed else self.lib.fcz_lddt
+            _lib.check(fn(self.ctx, pos_true.ctypes.data, masks[0].ctypes.data, pos_pred.ctypes.data, None if masks[1] is None else masks[1].ctypes.data,
+                          None if bound is None else bound.ctypes.data, n, rows, lay, slot, float(cutoff), None if th is None else th.ctypes.data,
+                          score.ctypes.data, pairs.ctypes.data, hits.ctypes.data), "fcz_lddt_packed" if packed else "fcz_lddt")
+        return dict(score=score, pairs=pairs, hits=hits)
+
     def frames(self, pos: np.ndarray, mask: np.ndarray, aatype=None, length=None, layout=None, groups="backbone"):
         """dense arrays on the host -> the rigid frames of every residue (fcz_frames): rot float32 [.., 3, 3], trans [.., 3] and
         frame_mask bool [..] for groups="backbone", [.., 8, 3, 3] / [.., 8, 3] / [.., 8] for "all" (which needs aatype). pos float32

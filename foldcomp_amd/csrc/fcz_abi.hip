@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -33,6 +34,7 @@
 #include "fcz_dense.h"
 #include "fcz_undense.h"
 #include "fcz_knn.h"
+#include "fcz_lddt.h"
 #include "fcz_frames.h"
 #include "fcz_angles.h"
 
@@ -86,9 +88,9 @@ struct timed_span { std::string name; hipEvent_t a, b; };
 // arrays of a fcz_chain_batch, the 10 of a fcz_dense_in (slot 3, length, holds row_off [n + 1] in the packed form), the 6 of a
 // fcz_dense_out, the 7 of a fcz_packed_out (PACKED_OUT .. PACKED_OUT_LAST), in the struct's order; ANGLES_OUT: the angles, their mask and
 // (windowed form) aatype; WINDOW_START: the n u32 starts of a windowed host call; KEPT_*: the records a *_begin call leaves for its fetch
-// (C + 1 u64 offsets, the bytes, C i32 status)
+// (C + 1 u64 offsets, the bytes, C i32 status); LDDT_PRED: pos and mask of the second tensor batch of fcz_lddt, LDDT_OUT: score, pairs, hits
 enum { REC_BLOB, REC_OFF, REC_RES_OFF, REC_ATOM_OFF, REC_X, REC_Y, REC_Z, REC_BFAC, REC_RES_CODE, REC_ATOM_CODE,
-       FILES_TEXT = 0, FILES_OFF, FILES_NAMES, FILES_NAME_OFF, FILES_STEM_LEN, BATCH_IN = 0, DENSE_IN = 0, DENSE_OUT = 10,
+       FILES_TEXT = 0, FILES_OFF, FILES_NAMES, FILES_NAME_OFF, FILES_STEM_LEN, BATCH_IN = 0, DENSE_IN = 0, LDDT_PRED = 4, DENSE_OUT = 10, LDDT_OUT = 10,
        PACKED_OUT = 10, ANGLES_OUT = 10, KEPT_OFF = 13, KEPT_BYTES, KEPT_STATUS, PACKED_OUT_LAST, WINDOW_START = PACKED_OUT_LAST, POOL_COUNT };
 
 // what the device reports to the host in the middle of a call: one pinned allocation, a member per reader
@@ -138,7 +140,7 @@ struct fcz_ctx {
     dev_buf res_sc;     // decompress: residue -> its side-chain torsion bytes, 3 x R dwords
     dev_buf sizes_res_off;   // decompress: the res_off of a batch call that has to run its own sizes pass (ensure_sizes)
     dev_buf selftest_out;    // fcz_selftest_math
-    dev_buf knn_tiles;       // fcz_knn_packed_dev: n u64 tile counts, then their n + 1 offsets
+    dev_buf knn_tiles;       // fcz_knn_packed_dev, fcz_lddt_packed_dev (chain_tile_scan): n u64 tile counts, then their n + 1 offsets
     dev_buf fast_scratch;    // decompress, FCZ_NUMERICS_FAST: forward atoms of segments longer than one chunk
     // Staging of the host-pointer entry points. Every entry point that writes it calls claim_staging first. Nothing outlives the call
     // that wrote it but KEPT_*, which a begin leaves for its fetch: any later call that writes 13 .. 15 ends that.
@@ -159,6 +161,7 @@ struct fcz_ctx {
     //   fcz_compress_dense_begin_dev                KEPT_* 13 .. 15                             KEPT_*, ud_fcz_bytes (+ ud_batch)
     //   fcz_compress_dense_packed_begin[_dev]       as the two above (DENSE_IN 3 = row_off)     the same
     //   fcz_knn / fcz_knn_packed                    DENSE_IN 0, 1, 3 (pos, mask, length / row_off), DENSE_OUT 10 .. 11 (index, dist)
+    //   fcz_lddt / fcz_lddt_packed                  DENSE_IN 0, 1, 3 (pos_true, mask_true, length / row_off), LDDT_PRED 4 .. 5 (pos_pred, mask_pred), LDDT_OUT 10 .. 12
     //   fcz_frames                                  DENSE_IN 0 .. 3 (pos, mask, aatype, length), DENSE_OUT 10 .. 12 (rot, trans, frame_mask)
     dev_buf pool[POOL_COUNT];
     // PDB text / extracted data: per-entry sizes (any call), offsets (n + 1 u64) and the text of the last fcz_decompress_pdb_begin,
@@ -1649,6 +1652,32 @@ static bool knn_args_ok(const fcz_ctx* ctx, const float* pos, const uint8_t* mas
     return ctx && pos && mask && index && dist && fcz_dense_width(layout) > 0 && slot >= 0 && slot < fcz_dense_width(layout) && k >= 1 && k <= KNN_MAX_K;
 }
 
+// The query tiles of a per-chain sweep (fcz_chains.h) and the blocks that run them. Padded: n * tiles_per_entry tiles. Packed (n > 0):
+// reserve() makes room for n tile counts and their n + 1 offsets in ctx->knn_tiles, scan() counts them on the device behind whatever
+// the caller has enqueued -- the scratch is dead when the sweep that reads tile_off has run, so the sweeps share it.
+struct chain_tiles {
+    uint64_t* tile_off = nullptr; uint32_t tiles_per_entry = 0; uint64_t n_padded = 0, blocks = 0;
+    int reserve(fcz_ctx* ctx, bool packed, uint32_t n, uint32_t rows) {
+        const uint32_t max_blocks = (uint32_t)ctx->n_cu * 16u;
+        tiles_per_entry = (uint32_t)(((uint64_t)rows + CHAIN_TILE - 1) / CHAIN_TILE);   // (rows + 255 may pass 2^32)
+        if (packed) {
+            int rc = ctx->knn_tiles.ensure(sizeof(uint64_t) * (2 * (size_t)n + 1)); if (rc) return rc;
+            tile_off = ctx->knn_tiles.as<uint64_t>() + n;
+            tiles_per_entry = 0;
+            blocks = std::min<uint64_t>((uint64_t)rows / CHAIN_TILE + n, max_blocks);   // the tiles are counted on the device: at most this many
+        } else {
+            n_padded = (uint64_t)n * tiles_per_entry;
+            blocks = std::min<uint64_t>(n_padded, max_blocks);
+        }
+        return FCZ_OK;
+    }
+    int scan(fcz_ctx* ctx, const uint32_t* row_off_dev, uint32_t n, uint32_t R) {
+        const uint32_t max_blocks = (uint32_t)ctx->n_cu * 16u;
+        hipLaunchKernelGGL(k_chain_tiles, dim3(std::min(grid_for(n, BLOCK), max_blocks)), dim3(BLOCK), 0, ctx->stream, row_off_dev, n, R, ctx->knn_tiles.as<uint64_t>());
+        return device_scan<uint64_t>(ctx, ctx->knn_tiles.as<uint64_t>(), tile_off, n);
+    }
+};
+
 // fcz_knn_dev (row_off_dev == NULL: bound_dev is length [n] or NULL, rows = L) and fcz_knn_packed_dev (bound_dev = row_off [n + 1], rows = R)
 static int knn_rows(fcz_ctx* ctx, const float* pos_dev, const uint8_t* mask_dev, const uint32_t* bound_dev, bool packed, uint32_t n, uint32_t rows,
                     int layout, int slot, uint32_t k, int32_t* index_dev, float* dist_dev) {
@@ -1656,29 +1685,20 @@ static int knn_rows(fcz_ctx* ctx, const float* pos_dev, const uint8_t* mask_dev,
     if (rows == 0 || (n == 0 && !packed)) return FCZ_OK;
     const knn_args g{pos_dev, mask_dev, bound_dev, n, rows, (uint32_t)fcz_dense_width(layout), (uint32_t)slot, k, index_dev, dist_dev};
     const uint32_t max_blocks = (uint32_t)ctx->n_cu * 16u;
-    uint64_t* tile_off = nullptr;
-    if (packed && n) {
-        int rc = ctx->knn_tiles.ensure(sizeof(uint64_t) * (2 * (size_t)n + 1)); if (rc) return rc;
-        tile_off = ctx->knn_tiles.as<uint64_t>() + n;
-    }
-    const uint32_t tiles_per_entry = (uint32_t)(((uint64_t)rows + KNN_TILE - 1) / KNN_TILE);   // (rows + 255 may pass 2^32)
+    chain_tiles ct;
+    if (!packed || n) { int rc = ct.reserve(ctx, packed, n, rows); if (rc) return rc; }
     span_guard sg(ctx, "knn");
-    uint64_t blocks;
     if (packed) {
         hipLaunchKernelGGL(k_knn_fill, dim3((uint32_t)std::min<uint64_t>(((uint64_t)rows + BLOCK - 1) / BLOCK, max_blocks)), dim3(BLOCK), 0, ctx->stream, g);
         if (n == 0) { HIP_TRY(hipGetLastError()); return FCZ_OK; }
-        hipLaunchKernelGGL(k_knn_tiles, dim3(std::min(grid_for(n, BLOCK), max_blocks)), dim3(BLOCK), 0, ctx->stream, g, ctx->knn_tiles.as<uint64_t>());
-        int rc = device_scan<uint64_t>(ctx, ctx->knn_tiles.as<uint64_t>(), tile_off, n); if (rc) return rc;
-        blocks = std::min<uint64_t>((uint64_t)rows / KNN_TILE + n, max_blocks);   // the tiles are counted on the device: at most this many
-    } else {
-        blocks = std::min<uint64_t>((uint64_t)n * tiles_per_entry, max_blocks);
+        int rc = ct.scan(ctx, bound_dev, n, rows); if (rc) return rc;
     }
     auto launch = [&](auto KCAP) {
         if (packed)
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_knn<decltype(KCAP)::value, true>), dim3((uint32_t)blocks), dim3(BLOCK), 0, ctx->stream, g, tile_off, 0u, (uint64_t)0);
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_knn<decltype(KCAP)::value, true>), dim3((uint32_t)ct.blocks), dim3(BLOCK), 0, ctx->stream, g, ct.tile_off, 0u, (uint64_t)0);
         else
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_knn<decltype(KCAP)::value, false>), dim3((uint32_t)blocks), dim3(BLOCK), 0, ctx->stream, g, (const uint64_t*)nullptr,
-                               tiles_per_entry, (uint64_t)n * tiles_per_entry);
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_knn<decltype(KCAP)::value, false>), dim3((uint32_t)ct.blocks), dim3(BLOCK), 0, ctx->stream, g, (const uint64_t*)nullptr,
+                               ct.tiles_per_entry, ct.n_padded);
     };
     if (k <= 16) launch(std::integral_constant<int, 16>{});
     else if (k <= 32) launch(std::integral_constant<int, 32>{});
@@ -1734,6 +1754,112 @@ int fcz_knn_packed(fcz_ctx* ctx, const float* pos, const uint8_t* mask, const ui
                    int32_t* index, float* dist) {
     if (!knn_args_ok(ctx, pos, mask, layout, slot, k, index, dist) || (n && !row_off) || R > 0x7FFFFFFFu) return FCZ_E_INVALID_ARG;
     return knn_host(ctx, pos, mask, row_off, true, n, R, layout, slot, k, index, dist);
+}
+
+// ------------------------------------------------------------------------------------------------
+// per-residue lDDT of two dense tensor batches (fcz_lddt.h; no counterpart in the reference)
+// ------------------------------------------------------------------------------------------------
+int fcz_lddt_pass(void) { return (int)LDDT_PASS; }
+float fcz_lddt_c2(float cutoff) { return std::isfinite(cutoff) && cutoff > 0.0f ? lddt_c2(cutoff) : NAN; }
+
+static const float LDDT_THRESHOLDS[4] = {0.5f, 1.0f, 2.0f, 4.0f};
+
+// rows: L (padded) or R (packed)
+static bool lddt_args_ok(const fcz_ctx* ctx, const float* pos_true, const uint8_t* mask_true, const float* pos_pred, int layout, int slot, float cutoff,
+                         const float* thresholds, uint32_t rows, const float* score, const int32_t* pairs, const int32_t* hits) {
+    if (!ctx || !pos_true || !mask_true || !pos_pred || !score || !pairs || !hits) return false;
+    if (fcz_dense_width(layout) <= 0 || slot < 0 || slot >= fcz_dense_width(layout)) return false;
+    if (!std::isfinite(cutoff) || !(cutoff > 0.0f) || rows > LDDT_MAX_ROWS) return false;
+    if (thresholds) for (int t = 0; t < 4; t++) if (std::isnan(thresholds[t])) return false;
+    return true;
+}
+
+// fcz_lddt_dev (bound_dev is length [n] or NULL, rows = L) and fcz_lddt_packed_dev (bound_dev = row_off [n + 1], rows = R)
+static int lddt_rows(fcz_ctx* ctx, const float* pos_true_dev, const uint8_t* mask_true_dev, const float* pos_pred_dev, const uint8_t* mask_pred_dev,
+                     const uint32_t* bound_dev, bool packed, uint32_t n, uint32_t rows, int layout, int slot, float cutoff, const float* thresholds,
+                     float* score_dev, int32_t* pairs_dev, int32_t* hits_dev) {
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (rows == 0 || (n == 0 && !packed)) return FCZ_OK;
+    const float* th = thresholds ? thresholds : LDDT_THRESHOLDS;
+    const lddt_args g{pos_true_dev, mask_true_dev, pos_pred_dev, mask_pred_dev, bound_dev, n, rows, (uint32_t)fcz_dense_width(layout), (uint32_t)slot,
+                      lddt_c2(cutoff), th[0], th[1], th[2], th[3], score_dev, pairs_dev, hits_dev};
+    const uint32_t max_blocks = (uint32_t)ctx->n_cu * 16u;
+    chain_tiles ct;
+    if (!packed || n) { int rc = ct.reserve(ctx, packed, n, rows); if (rc) return rc; }
+    span_guard sg(ctx, "lddt");
+    if (packed) {
+        hipLaunchKernelGGL(k_lddt_fill, dim3((uint32_t)std::min<uint64_t>(((uint64_t)rows + BLOCK - 1) / BLOCK, max_blocks)), dim3(BLOCK), 0, ctx->stream, g);
+        if (n == 0) { HIP_TRY(hipGetLastError()); return FCZ_OK; }
+        int rc = ct.scan(ctx, bound_dev, n, rows); if (rc) return rc;
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_lddt<true>), dim3((uint32_t)ct.blocks), dim3(BLOCK), 0, ctx->stream, g, ct.tile_off, 0u, (uint64_t)0);
+    } else {
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_lddt<false>), dim3((uint32_t)ct.blocks), dim3(BLOCK), 0, ctx->stream, g, (const uint64_t*)nullptr, ct.tiles_per_entry,
+                           ct.n_padded);
+    }
+    HIP_TRY(hipGetLastError());
+    return FCZ_OK;
+}
+
+int fcz_lddt_dev(fcz_ctx* ctx, const float* pos_true_dev, const uint8_t* mask_true_dev, const float* pos_pred_dev, const uint8_t* mask_pred_dev,
+                 const uint32_t* length_dev, uint32_t n, uint32_t L, int layout, int slot, float cutoff, const float* thresholds, float* score_dev,
+                 int32_t* pairs_dev, int32_t* hits_dev) {
+    if (!lddt_args_ok(ctx, pos_true_dev, mask_true_dev, pos_pred_dev, layout, slot, cutoff, thresholds, L, score_dev, pairs_dev, hits_dev) || L == 0)
+        return FCZ_E_INVALID_ARG;
+    return lddt_rows(ctx, pos_true_dev, mask_true_dev, pos_pred_dev, mask_pred_dev, length_dev, false, n, L, layout, slot, cutoff, thresholds, score_dev,
+                     pairs_dev, hits_dev);
+}
+
+int fcz_lddt_packed_dev(fcz_ctx* ctx, const float* pos_true_dev, const uint8_t* mask_true_dev, const float* pos_pred_dev, const uint8_t* mask_pred_dev,
+                        const uint32_t* row_off_dev, uint32_t n, uint32_t R, int layout, int slot, float cutoff, const float* thresholds, float* score_dev,
+                        int32_t* pairs_dev, int32_t* hits_dev) {
+    if (!lddt_args_ok(ctx, pos_true_dev, mask_true_dev, pos_pred_dev, layout, slot, cutoff, thresholds, R, score_dev, pairs_dev, hits_dev) ||
+        (n && !row_off_dev))
+        return FCZ_E_INVALID_ARG;
+    return lddt_rows(ctx, pos_true_dev, mask_true_dev, pos_pred_dev, mask_pred_dev, row_off_dev, true, n, R, layout, slot, cutoff, thresholds, score_dev,
+                     pairs_dev, hits_dev);
+}
+
+// fcz_lddt and fcz_lddt_packed: the host arrays through DENSE_IN 0, 1, 3, LDDT_PRED 4, 5 and LDDT_OUT 10 .. 12
+static int lddt_host(fcz_ctx* ctx, const float* pos_true, const uint8_t* mask_true, const float* pos_pred, const uint8_t* mask_pred, const uint32_t* bound,
+                     bool packed, uint32_t n, uint32_t rows_per, int layout, int slot, float cutoff, const float* thresholds, float* score, int32_t* pairs,
+                     int32_t* hits) {
+    HIP_TRY(hipSetDevice(ctx->device));
+    claim_staging(ctx);
+    const size_t rows = packed ? (size_t)rows_per : (size_t)n * rows_per, A = (size_t)fcz_dense_width(layout);
+    if (rows == 0) return FCZ_OK;
+    const size_t nb = bound ? sizeof(uint32_t) * ((size_t)n + (packed ? 1 : 0)) : 0, np = rows * A * 3 * sizeof(float), nm = rows * A, no = rows * 4;
+    int rc;
+    if ((rc = ctx->pool[DENSE_IN].ensure(np)) || (rc = ctx->pool[DENSE_IN + 1].ensure(nm)) || (rc = ctx->pool[DENSE_IN + 3].ensure(nb)) ||
+        (rc = ctx->pool[LDDT_PRED].ensure(np)) || (rc = ctx->pool[LDDT_PRED + 1].ensure(mask_pred ? nm : 0)) || (rc = ctx->pool[LDDT_OUT].ensure(no)) ||
+        (rc = ctx->pool[LDDT_OUT + 1].ensure(no)) || (rc = ctx->pool[LDDT_OUT + 2].ensure(no)))
+        return rc;
+    HIP_TRY(hipMemcpyAsync(ctx->pool[DENSE_IN].p, pos_true, np, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(ctx->pool[DENSE_IN + 1].p, mask_true, nm, hipMemcpyHostToDevice, ctx->stream));
+    if (nb) HIP_TRY(hipMemcpyAsync(ctx->pool[DENSE_IN + 3].p, bound, nb, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(ctx->pool[LDDT_PRED].p, pos_pred, np, hipMemcpyHostToDevice, ctx->stream));
+    if (mask_pred) HIP_TRY(hipMemcpyAsync(ctx->pool[LDDT_PRED + 1].p, mask_pred, nm, hipMemcpyHostToDevice, ctx->stream));
+    rc = lddt_rows(ctx, ctx->pool[DENSE_IN].as<float>(), ctx->pool[DENSE_IN + 1].as<uint8_t>(), ctx->pool[LDDT_PRED].as<float>(),
+                   mask_pred ? ctx->pool[LDDT_PRED + 1].as<uint8_t>() : nullptr, nb ? ctx->pool[DENSE_IN + 3].as<uint32_t>() : nullptr, packed, n, rows_per,
+                   layout, slot, cutoff, thresholds, ctx->pool[LDDT_OUT].as<float>(), ctx->pool[LDDT_OUT + 1].as<int32_t>(), ctx->pool[LDDT_OUT + 2].as<int32_t>());
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(score, ctx->pool[LDDT_OUT].p, no, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(pairs, ctx->pool[LDDT_OUT + 1].p, no, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(hits, ctx->pool[LDDT_OUT + 2].p, no, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return FCZ_OK;
+}
+
+int fcz_lddt(fcz_ctx* ctx, const float* pos_true, const uint8_t* mask_true, const float* pos_pred, const uint8_t* mask_pred, const uint32_t* length,
+             uint32_t n, uint32_t L, int layout, int slot, float cutoff, const float* thresholds, float* score, int32_t* pairs, int32_t* hits) {
+    if (!lddt_args_ok(ctx, pos_true, mask_true, pos_pred, layout, slot, cutoff, thresholds, L, score, pairs, hits) || L == 0) return FCZ_E_INVALID_ARG;
+    return lddt_host(ctx, pos_true, mask_true, pos_pred, mask_pred, length, false, n, L, layout, slot, cutoff, thresholds, score, pairs, hits);
+}
+
+int fcz_lddt_packed(fcz_ctx* ctx, const float* pos_true, const uint8_t* mask_true, const float* pos_pred, const uint8_t* mask_pred, const uint32_t* row_off,
+                    uint32_t n, uint32_t R, int layout, int slot, float cutoff, const float* thresholds, float* score, int32_t* pairs, int32_t* hits) {
+    if (!lddt_args_ok(ctx, pos_true, mask_true, pos_pred, layout, slot, cutoff, thresholds, R, score, pairs, hits) || (n && !row_off))
+        return FCZ_E_INVALID_ARG;
+    return lddt_host(ctx, pos_true, mask_true, pos_pred, mask_pred, row_off, true, n, R, layout, slot, cutoff, thresholds, score, pairs, hits);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -34,6 +34,12 @@ constexpr uint32_t DN_MAX_WIDTH = 37;
 #define FCZ_DENSE_NT 1
 #endif
 
+// what the readers of the dense tensors state their float32 contracts with (fcz_knn.h, fcz_frames.h, fcz_lddt.h): the correctly rounded
+// float32 quotient and square root. double has more than 2 * 24 + 2 bits, so the double result rounded to float is the float result
+// rounded once.
+__host__ __device__ __forceinline__ float f32_div_rn(float a, float b) { return (float)((double)a / (double)b); }
+__host__ __device__ __forceinline__ float f32_sqrt_rn(float a) { return (float)sqrt((double)a); }
+
 typedef float dn_f4 __attribute__((ext_vector_type(4)));
 typedef uint32_t dn_u4 __attribute__((ext_vector_type(4)));
 

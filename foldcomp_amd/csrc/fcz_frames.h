@@ -41,10 +41,6 @@ struct frames_args {
     float* rot; float* trans; uint8_t* frame_mask;
 };
 
-// the correctly rounded float32 quotient and square root: double has more than 2 * 24 + 2 bits, so rounding twice is exact
-__device__ __forceinline__ float fr_div(float a, float b) { return (float)((double)a / (double)b); }
-__device__ __forceinline__ float fr_sqrt(float a) { return (float)sqrt((double)a); }
-
 // `count` elements of T from src into LDS dst, rows of ROW elements, element t wanted when live(t): 16-byte loads over the aligned
 // middle of the range (a piece is loaded when an element of it is wanted: its last one and one per ROW elements are asked, which
 // meets every row the piece touches), single elements around it
@@ -137,12 +133,12 @@ __global__ __launch_bounds__(BLOCK) void k_frames(frames_args g, uint64_t n_tile
                         const float v1y = bb ? __fsub_rn(py, oy) : __fsub_rn(oy, py);
                         const float v1z = bb ? __fsub_rn(pz, oz) : __fsub_rn(oz, pz);
                         const float v2x = __fsub_rn(qx, ox), v2y = __fsub_rn(qy, oy), v2z = __fsub_rn(qz, oz);
-                        const float n1 = fr_sqrt(__fadd_rn(__fadd_rn(__fmul_rn(v1x, v1x), __fmul_rn(v1y, v1y)), __fmul_rn(v1z, v1z)));
-                        const float e1x = fr_div(v1x, n1), e1y = fr_div(v1y, n1), e1z = fr_div(v1z, n1);
+                        const float n1 = f32_sqrt_rn(__fadd_rn(__fadd_rn(__fmul_rn(v1x, v1x), __fmul_rn(v1y, v1y)), __fmul_rn(v1z, v1z)));
+                        const float e1x = f32_div_rn(v1x, n1), e1y = f32_div_rn(v1y, n1), e1z = f32_div_rn(v1z, n1);
                         const float d = __fadd_rn(__fadd_rn(__fmul_rn(e1x, v2x), __fmul_rn(e1y, v2y)), __fmul_rn(e1z, v2z));
                         const float ux = __fsub_rn(v2x, __fmul_rn(e1x, d)), uy = __fsub_rn(v2y, __fmul_rn(e1y, d)), uz = __fsub_rn(v2z, __fmul_rn(e1z, d));
-                        const float n2 = fr_sqrt(__fadd_rn(__fadd_rn(__fmul_rn(ux, ux), __fmul_rn(uy, uy)), __fmul_rn(uz, uz)));
-                        const float e2x = fr_div(ux, n2), e2y = fr_div(uy, n2), e2z = fr_div(uz, n2);
+                        const float n2 = f32_sqrt_rn(__fadd_rn(__fadd_rn(__fmul_rn(ux, ux), __fmul_rn(uy, uy)), __fmul_rn(uz, uz)));
+                        const float e2x = f32_div_rn(ux, n2), e2y = f32_div_rn(uy, n2), e2z = f32_div_rn(uz, n2);
                         ok = fin && isfinite(n1) && n1 > 0.0f && isfinite(n2) && n2 > 0.0f;
                         if (ok) {
                             r00 = e1x; r10 = e1y; r20 = e1z;

@@ -19,18 +19,19 @@
 //                         The L x L matrix is never written: HBM sees the slot's 12 bytes per row and the [rows][k] outputs.
 //                         Padded form: tile -> (entry, tile of the entry) by division; every row of the entry is written,
 //                         -1 / 0 where it is no site. Packed form: the chains' tile counts are scanned on the device
-//                         (k_knn_tiles, device_scan) and a tile finds its chain by binary search, as k_dense_packed's rows do.
+//                         (k_chain_tiles, device_scan) and a tile finds its chain by binary search (fcz_chains.h, shared
+//                         with fcz_lddt.h).
 //   k_knn_fill            packed form only, in front of k_knn: -1 / 0 into every row that no chain is seen to cover (a search of
 //                         row_off that a hostile row_off may mislead: a covered row it misses is rewritten by k_knn behind it).
 //
 // Every index that scales with rows * k or rows * A is 64-bit. A chain's range is clamped to the R rows that exist and a range
 // that runs backwards is empty, so no read leaves pos / mask whatever row_off holds.
 #pragma once
-#include "fcz_dense.h"
+#include "fcz_chains.h"
 
 namespace fcz {
 
-constexpr uint32_t KNN_TILE = BLOCK;        // query rows per tile (a lane per query)
+constexpr uint32_t KNN_TILE = CHAIN_TILE;   // query rows per tile (a lane per query)
 constexpr uint32_t KNN_PASS = 2048;         // chain rows staged per candidate pass: 32 KiB of LDS
 constexpr uint32_t KNN_MAX_K = 64;
 constexpr uint64_t KNN_NONE = ~0ull;        // no neighbour: above every key (its d2 half is a NaN pattern)
@@ -49,15 +50,7 @@ struct knn_args {
 // chain e: its first row in the arrays, the rows that may hold a site, the rows k_knn writes
 template <bool PACKED>
 __device__ __forceinline__ void knn_chain(const knn_args& g, uint32_t e, uint64_t* row0, uint32_t* len, uint32_t* rows) {
-    if constexpr (PACKED) {
-        uint32_t lo = g.bound[e], hi = g.bound[e + 1];
-        if (lo > g.L) lo = g.L;
-        if (hi > g.L) hi = g.L;
-        *row0 = lo; *len = hi > lo ? hi - lo : 0u; *rows = *len;
-    } else {
-        const uint32_t le = g.bound ? g.bound[e] : g.L;
-        *row0 = (uint64_t)e * g.L; *len = le < g.L ? le : g.L; *rows = g.L;
-    }
+    chain_range<PACKED>(g.bound, g.L, e, row0, len, rows);
 }
 
 // the slot's coordinates of array row r -> true when the row is a site (mask set, three finite values)
@@ -71,27 +64,12 @@ __device__ __forceinline__ bool knn_site(const knn_args& g, uint64_t r, float* x
 __device__ __forceinline__ void knn_decode(uint64_t key, uint32_t base, int32_t* idx, float* d) {
     const bool none = key == KNN_NONE;
     *idx = none ? -1 : (int32_t)(base + (uint32_t)key);
-    // the double square root of a float, rounded to float, is the correctly rounded float square root
-    *d = none ? 0.0f : (float)sqrt((double)__uint_as_float((uint32_t)(key >> 32)));
-}
-
-// packed form: tiles of every chain, for the scan that gives each tile its chain
-__global__ __launch_bounds__(BLOCK) void k_knn_tiles(knn_args g, uint64_t* __restrict__ tiles) {
-    for (uint64_t e = (uint64_t)blockIdx.x * BLOCK + threadIdx.x; e < g.n; e += (uint64_t)gridDim.x * BLOCK) {
-        uint64_t row0; uint32_t len, rows;
-        knn_chain<true>(g, (uint32_t)e, &row0, &len, &rows);
-        tiles[e] = rows / KNN_TILE + (rows % KNN_TILE ? 1u : 0u);
-    }
+    *d = none ? 0.0f : f32_sqrt_rn(__uint_as_float((uint32_t)(key >> 32)));
 }
 
 __global__ __launch_bounds__(BLOCK) void k_knn_fill(knn_args g) {
     for (uint64_t r = (uint64_t)blockIdx.x * BLOCK + threadIdx.x; r < g.L; r += (uint64_t)gridDim.x * BLOCK) {
-        bool covered = false;
-        if (g.n) {
-            const uint32_t e = dn_entry_of(g.bound, 0u, g.n, (uint32_t)r);
-            covered = g.bound[e] <= r && r < g.bound[e + 1];          // (r < R: chain e's clamped range holds the row)
-        }
-        if (covered) continue;
+        if (chain_covers(g.bound, g.n, r)) continue;
         for (uint32_t s = 0; s < g.k; s++) { g.index[r * g.k + s] = -1; g.dist[r * g.k + s] = 0.0f; }
     }
 }
@@ -106,13 +84,7 @@ __global__ __launch_bounds__(BLOCK) void k_knn(knn_args g, const uint64_t* __res
     const bool wide = (g.k & 3u) == 0 && (((uintptr_t)g.index | (uintptr_t)g.dist) & 15u) == 0;   // 16-byte stores of four columns
     for (uint64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
         uint32_t e, t;
-        if constexpr (PACKED) {   // the largest e with tile_off[e] <= tile: a chain that has tiles
-            uint32_t lo = 0, hi = g.n;
-            while (hi - lo > 1u) { const uint32_t mid = lo + ((hi - lo) >> 1); if (tile_off[mid] <= tile) lo = mid; else hi = mid; }
-            e = lo; t = (uint32_t)(tile - tile_off[e]);
-        } else {
-            e = (uint32_t)(tile / tiles_per_entry); t = (uint32_t)(tile - (uint64_t)e * tiles_per_entry);
-        }
+        chain_of_tile<PACKED>(tile_off, g.n, tiles_per_entry, tile, &e, &t);
         uint64_t row0; uint32_t len, rows;
         knn_chain<PACKED>(g, e, &row0, &len, &rows);
         const uint64_t q = (uint64_t)t * KNN_TILE + tid;              // this lane's row of the chain

@@ -12,6 +12,8 @@
     crop_starts(length, L, how, generator) -> the starts of such a crop, on the device the lengths lie on
     neighbor_graph(either dict, or the tensors as keywords, k=48, atom="CA") -> dict(nbr_index [.., k] int32, nbr_dist [.., k] float32):
                                    the k nearest CA / CB sites of every residue inside its chain; decode_tensors(neighbors=k) adds them
+    lddt(pred, true, atom="CA", cutoff=15.0) -> dict(lddt [..] float32, lddt_pairs, lddt_hits int32, lddt_chain [n] float32): the per-residue
+                                   lDDT of predicted coordinates against a decoded batch, and its chain mean
     rigid_frames(either dict, or the tensors as keywords, groups="backbone" | "all") -> dict(rot [.., 3, 3], trans [.., 3], frame_mask):
                                    every residue's backbone frame, or the eight rigid groups; decode_tensors(frames=...) adds them
 
@@ -36,7 +38,7 @@ from ._aa_tables import RES1
 from .codec import ANGLE_COLUMNS, Codec, dense_layout
 from .structure import CAtomsOut, CDenseIn, CDenseOut, CPackedOut
 
-__all__ = ["decode_tensors", "encode_tensors", "decode_angles", "crop_starts", "neighbor_graph", "rigid_frames"]
+__all__ = ["decode_tensors", "encode_tensors", "decode_angles", "crop_starts", "neighbor_graph", "rigid_frames", "lddt"]
 
 
 def crop_starts(length, L: int, how, generator=None):
@@ -460,47 +462,134 @@ def neighbor_graph(batch=None, *, k: int = 48, atom="CA", codec: Optional[Codec]
     lay = dense_layout(_WIDTH_LAYOUT[A])
 
     def on_device(key, t, want, dtypes):
-        if not isinstance(t, torch.Tensor) or t.device != dev:
-            where = t.device if isinstance(t, torch.Tensor) else type(t).__name__
-            raise api.error(f"neighbor_graph: {key} lies on {where}, pos on {dev}; every tensor must be on the codec's device")
-        if tuple(t.shape) != want or t.dtype not in dtypes:
-            raise ValueError(f"{key} must be {' / '.join(str(x) for x in dtypes)} {want}, not {t.dtype} {tuple(t.shape)}")
-        if not t.is_contiguous():
-            raise ValueError(f"neighbor_graph: {key} must be contiguous")
-        return t
+        return _on_device(torch, "neighbor_graph", dev, key, t, want, dtypes)
 
     on_device("pos", pos, shape, (torch.float32,))
     mask = on_device("mask", d["mask"], shape[:-1], (torch.bool, torch.uint8)).view(torch.uint8)
     index = torch.empty(shape[:-2] + (k,), dtype=torch.int32, device=dev)
     dist = torch.empty(shape[:-2] + (k,), dtype=torch.float32, device=dev)
     out = dict(nbr_index=index, nbr_dist=dist)
+    n, rows, bound = _chain_bound(torch, "neighbor_graph", dev, d, shape, is_packed)
+    if n == 0 and not is_packed or rows == 0:
+        return out
+    torch.cuda.current_stream(dev).synchronize()
+    if is_packed:
+        _lib.check(c.lib.fcz_knn_packed_dev(c.ctx, pos.data_ptr(), mask.data_ptr(), bound.data_ptr(), n, rows, lay, slot, k, index.data_ptr(), dist.data_ptr()),
+                   "fcz_knn_packed_dev")
+    else:
+        _lib.check(c.lib.fcz_knn_dev(c.ctx, pos.data_ptr(), mask.data_ptr(), None if bound is None else bound.data_ptr(), n, rows, lay, slot, k,
+                                     index.data_ptr(), dist.data_ptr()), "fcz_knn_dev")
+    c.synchronize()
+    return out
+
+
+def _on_device(torch, what, dev, key, t, want, dtypes):
+    """tensor `key` of the call `what`: on the device `dev`, of the shape `want`, one of `dtypes`, contiguous"""
+    if not isinstance(t, torch.Tensor) or t.device != dev:
+        where = t.device if isinstance(t, torch.Tensor) else type(t).__name__
+        raise api.error(f"{what}: {key} lies on {where}, pos on {dev}; every tensor must be on the codec's device")
+    if tuple(t.shape) != want or t.dtype not in dtypes:
+        raise ValueError(f"{key} must be {' / '.join(str(x) for x in dtypes)} {want}, not {t.dtype} {tuple(t.shape)}")
+    if not t.is_contiguous():
+        raise ValueError(f"{what}: {key} must be contiguous")
+    return t
+
+
+def _chain_bound(torch, what, dev, d, shape, is_packed):
+    """the chains of the dense dict `d` whose pos has `shape` -> (n, rows, bound): packed, rows = R and bound = cu_seqlens as int32
+    (non-decreasing and ending at R, checked on the device); padded, rows = L and bound = length as int32, or None when the dict has
+    none or carries crop_start (a window's padding rows carry a cleared mask and `length` is the uncropped size)"""
     if is_packed:
         cu = d["cu_seqlens"]
         if not isinstance(cu, torch.Tensor) or cu.dim() != 1 or cu.shape[0] < 1:
             raise ValueError("cu_seqlens must be a tensor [n + 1]")
         n, R = int(cu.shape[0]) - 1, shape[0]
-        cu = on_device("cu_seqlens", cu, (n + 1,), (torch.int32, torch.int64))
+        cu = _on_device(torch, what, dev, "cu_seqlens", cu, (n + 1,), (torch.int32, torch.int64))
         if bool((cu[1:] < cu[:-1]).any()) or bool(cu[0] < 0) or int(cu[-1]) != R:
             raise ValueError(f"cu_seqlens must be non-decreasing and end at the {R} rows of pos")
-        bound = cu.to(torch.int32)
-        if R == 0:
-            return out
+        return n, R, cu.to(torch.int32)
+    n, L = shape[0], shape[1]
+    bound = None
+    if d.get("length") is not None and d.get("crop_start") is None:
+        # (int32 >= 0 and uint32 share their bits; a negative length reads as a large one and is clamped to L)
+        bound = _on_device(torch, what, dev, "length", d["length"], (n,), (torch.int32, torch.int64)).clamp(min=0).to(torch.int32)
+    return n, L, bound
+
+
+def lddt(pred, true, *, atom="CA", cutoff: float = 15.0, thresholds=(0.5, 1.0, 2.0, 4.0), codec: Optional[Codec] = None) -> dict:
+    """predicted coordinates against true ones, both dense tensors on the GPU -> dict(lddt, lddt_pairs, lddt_hits, lddt_chain): the
+    per-residue lDDT on the sites of one atom, with no superposition and no L x L matrix.
+
+    `true` is the dict decode_tensors / tensor_batches return, padded (pos [n, L, A, 3], mask [n, L, A], optionally length [n]) or
+    packed (pos [R, A, 3], mask [R, A], cu_seqlens [n + 1]), recognised as neighbor_graph recognises them; `length` is ignored when
+    the dict carries crop_start. `pred` is a dict with `pos` and optionally `mask` (none: every atom predicted), or just the pos
+    tensor, of the same shape. atom: "CA", "CB" (atom37 / atom14) or an integer slot. A row is a site when it lies inside its chain,
+    both masks at the slot are set and its six coordinates are finite. For a site i the pairs are the other sites j of its chain
+    with d_true(i, j) < cutoff; a pair scores one hit for every threshold that |d_true - d_pred| lies under.
+        lddt        [n, L] / [R] float32   hits / (4 * pairs), 0 where the row is no site or has no pair
+        lddt_pairs  int32, lddt_hits int32 the two counts
+        lddt_chain  [n] float32            sum of hits / (4 * sum of pairs) over the chain's rows (in float64 from int64 sums, so
+                                           exact whatever the order), 0 where the chain has no pair
+    Distances are sqrt((dx*dx + dy*dy) + dz*dz) in float32 and the counters integers, so the result is reproducible bit for bit.
+    It is NOT differentiable: it returns counts (a training target or a validation metric, not a loss).
+
+    The tensors must be contiguous and lie on the codec's device; ordering against torch is decode_tensors'. cutoff, thresholds,
+    atom and shapes that differ are checked first, without torch or a device (api.check_lddt)."""
+    t = dict(true) if isinstance(true, dict) else {"pos": true}
+    p = dict(pred) if isinstance(pred, dict) else {"pos": pred}
+    pos = t.get("pos")
+    shape = tuple(getattr(pos, "shape", ()))
+    is_packed = t.get("cu_seqlens") is not None and len(shape) == 3
+    slot, cutoff, th = api.check_lddt(cutoff, thresholds, atom, shape[-2] if len(shape) in (3, 4) else None)
+    for name, d, keys in (("true", t, ("pos", "mask")), ("pred", p, ("pos",))):
+        for key in keys:
+            if d.get(key) is None:
+                raise TypeError(f"lddt needs the tensor {key!r} of {name}")
+    ppos, pmask = p["pos"], p.get("mask")
+    if tuple(getattr(ppos, "shape", ())) != shape:
+        raise ValueError(f"pred pos must have the shape of true pos, {shape}, not {tuple(getattr(ppos, 'shape', ()))}")
+    if pmask is not None and tuple(getattr(pmask, "shape", ())) != shape[:-1]:
+        raise ValueError(f"pred mask must have the shape of true mask, {shape[:-1]}, not {tuple(getattr(pmask, 'shape', ()))}")
+    c = codec or api.default_codec()
+    try:
+        import torch
+    except ImportError as e:
+        raise api.error(f"lddt needs PyTorch (ROCm build): {e}") from None
+    if not isinstance(pos, torch.Tensor):
+        raise api.error("lddt takes torch tensors on the GPU (numpy arrays: Codec.lddt)")
+    if pos.device.type != "cuda" or pos.device.index != int(c.device):
+        raise api.error(f"lddt: pos lies on {pos.device}, the codec works on cuda:{int(c.device)}; there is no CPU path")
+    dev = pos.device
+    if len(shape) != (3 if is_packed else 4) or shape[-1] != 3 or pos.dtype != torch.float32:
+        raise ValueError(f"pos must be float32 [n, L, A, 3], or [R, A, 3] beside cu_seqlens, not {pos.dtype} {shape}")
+    lay = dense_layout(_WIDTH_LAYOUT[shape[-2]])
+    _on_device(torch, "lddt", dev, "pos", pos, shape, (torch.float32,))
+    mask = _on_device(torch, "lddt", dev, "mask", t["mask"], shape[:-1], (torch.bool, torch.uint8)).view(torch.uint8)
+    _on_device(torch, "lddt", dev, "pred pos", ppos, shape, (torch.float32,))
+    if pmask is not None:
+        pmask = _on_device(torch, "lddt", dev, "pred mask", pmask, shape[:-1], (torch.bool, torch.uint8)).view(torch.uint8)
+    n, rows, bound = _chain_bound(torch, "lddt", dev, t, shape, is_packed)
+    if rows > 2 ** 29:
+        raise ValueError("lddt_hits must fit int32: at most 2^29 rows per chain")
+    score = torch.zeros(shape[:-2], dtype=torch.float32, device=dev)
+    pairs = torch.zeros(shape[:-2], dtype=torch.int32, device=dev)
+    hits = torch.zeros(shape[:-2], dtype=torch.int32, device=dev)
+    if score.numel():
+        th_c = (ctypes.c_float * 4)(*th)
         torch.cuda.current_stream(dev).synchronize()
-        _lib.check(c.lib.fcz_knn_packed_dev(c.ctx, pos.data_ptr(), mask.data_ptr(), bound.data_ptr(), n, R, lay, slot, k, index.data_ptr(), dist.data_ptr()),
-                   "fcz_knn_packed_dev")
+        fn, name = (c.lib.fcz_lddt_packed_dev, "fcz_lddt_packed_dev") if is_packed else (c.lib.fcz_lddt_dev, "fcz_lddt_dev")
+        _lib.check(fn(c.ctx, pos.data_ptr(), mask.data_ptr(), ppos.data_ptr(), None if pmask is None else pmask.data_ptr(),
+                      None if bound is None else bound.data_ptr(), n, rows, lay, slot, cutoff, ctypes.addressof(th_c), score.data_ptr(), pairs.data_ptr(),
+                      hits.data_ptr()), name)
+        c.synchronize()
+    if is_packed:   # a cumulative sum differenced at cu_seqlens
+        zero = torch.zeros(1, dtype=torch.int64, device=dev)
+        at = bound.to(torch.int64)
+        ch, cp = (torch.cat([zero, x.to(torch.int64).cumsum(0)])[at].diff() for x in (hits, pairs))
     else:
-        n, L = shape[0], shape[1]
-        bound = None
-        if d.get("length") is not None and d.get("crop_start") is None:
-            # (int32 >= 0 and uint32 share their bits; a negative length reads as a large one and is clamped to L)
-            bound = on_device("length", d["length"], (n,), (torch.int32, torch.int64)).clamp(min=0).to(torch.int32)
-        if n == 0 or L == 0:
-            return out
-        torch.cuda.current_stream(dev).synchronize()
-        _lib.check(c.lib.fcz_knn_dev(c.ctx, pos.data_ptr(), mask.data_ptr(), None if bound is None else bound.data_ptr(), n, L, lay, slot, k,
-                                     index.data_ptr(), dist.data_ptr()), "fcz_knn_dev")
-    c.synchronize()
-    return out
+        ch, cp = hits.to(torch.int64).sum(dim=1), pairs.to(torch.int64).sum(dim=1)
+    chain = torch.where(cp > 0, ch.to(torch.float64) / (4 * cp).clamp(min=1).to(torch.float64), torch.zeros((), dtype=torch.float64, device=dev))
+    return dict(lddt=score, lddt_pairs=pairs, lddt_hits=hits, lddt_chain=chain.to(torch.float32))
 
 
 def _frames_alloc(torch, dev, rows, fgroups):

@@ -18,6 +18,7 @@
  *   (none: the reference stops at the flat atom vector)    fcz_dense_dev / fcz_decompress_dense, fcz_dense_packed_dev / fcz_decompress_dense_packed,
  *                                                          fcz_dense_window_dev / fcz_decompress_dense_window
  *   (none: no neighbour graph of the decoded chain)        fcz_knn_dev / fcz_knn_packed_dev, fcz_knn / fcz_knn_packed
+ *   (none: no score of one structure against another)      fcz_lddt_dev / fcz_lddt_packed_dev, fcz_lddt / fcz_lddt_packed
  *   (none: no rigid frames of the decoded chain)           fcz_frames_dev / fcz_frames
  *   Foldcomp::decompress, the dequantisation :784-804     fcz_angles_dev / fcz_angles_packed_dev, fcz_decompress_angles[_packed],
  *                                                          fcz_angles_window_dev / fcz_decompress_angles_window
@@ -388,6 +389,56 @@ int fcz_knn(fcz_ctx* ctx, const float* pos, const uint8_t* mask, const uint32_t*
 int fcz_knn_packed(fcz_ctx* ctx, const float* pos, const uint8_t* mask, const uint32_t* row_off, uint32_t n, uint32_t R,
                    int layout, int slot, uint32_t k, int32_t* index, float* dist);
 
+/* ---- per-residue lDDT of two dense tensor batches --------------------------------------------------------- */
+/* The superposition-free score of predicted coordinates against true ones (Mariani et al. 2013; the lDDT-CA a pLDDT head is trained
+ * on), per residue, for a whole batch on the device without the L x L distance matrices. The reference has no such output: like
+ * fcz_knn_dev these stand beside Foldcomp::decompress (src/foldcomp.cpp:779) and read what the dense calls wrote, or any tensors of
+ * those shapes. Two tensors of ONE shape and layout: pos_true / mask_true and pos_pred / mask_pred (mask_pred may be NULL: every
+ * slot present). Padded: pos [n][L][A][3] float32, mask [n][L][A] uint8, length [n] uint32 (may be NULL). Packed: pos [R][A][3],
+ * mask [R][A], row_off [n + 1] uint32. A = fcz_dense_width(layout), slot in 0 .. A - 1 as for fcz_knn_dev, cutoff float32 (15 is
+ * the usual inclusion radius), thresholds: four float32 on the HOST in every form (NULL: 0.5, 1, 2, 4).
+ *   site        row l of chain e is a site when it lies inside the chain (fcz_knn_dev's rules: padded l < min(length[e], L), or
+ *               l < L when length is NULL; packed row_off[e] <= row < row_off[e + 1], both clamped to R, a range that runs
+ *               backwards being empty), mask_true[row][slot] != 0, mask_pred[row][slot] != 0 (if a mask was given) and all six
+ *               coordinates at the slot are finite. Nothing else is read as data: rows outside the chain and pos under a cleared
+ *               mask may hold anything.
+ *   distances   for sites i, j of one chain and each of the two tensors: d2 = (dx*dx + dy*dy) + dz*dz in float32, every operation
+ *               rounded, no FMA (fcz_knn_dev's d2); d = the correctly rounded float32 square root of d2.
+ *   pairs       j counts for i when j != i and d_true(i, j) < cutoff, compared in float32; a d_true of +inf is no pair.
+ *               pairs[i] = the number of such j.
+ *   hits        diff = |d_true - d_pred|, one rounded float32 subtraction; hits[i] = sum over the pairs j and the four thresholds t
+ *               of [diff < thresholds[t]]. A NaN or +inf diff (a d_pred of +inf) is a pair with no hit.
+ *   score [rows] float32     (float)hits / (float)(4 * pairs), a single rounded float32 division; 0.0 where pairs == 0
+ *   pairs [rows] int32, hits [rows] int32
+ * rows = n * L (padded) or R (packed). Rows that are no site, rows behind length and packed rows no chain covers hold 0 / 0 / 0.
+ * Every byte of the three outputs is written whatever the inputs hold, nothing outside them is written, and nothing outside the
+ * inputs is read, whatever row_off holds (ranges that overlap are each computed; which of them a shared row's values belong to is
+ * then unspecified). Every index that scales with rows * A is 64-bit. The counters are integers, so the result does not depend on
+ * any order of evaluation: it is reproducible bit for bit. It is NOT differentiable: these are counts.
+ * Candidates are staged per chain in passes of fcz_lddt_pass() rows (pure host, > 0): a longer chain takes several, with the same
+ * result. fcz_lddt_c2(cutoff) (pure host) is the bound the kernel compares d2_true with: the smallest float32 whose correctly
+ * rounded root is >= cutoff, so that d2_true < c2 <=> d_true < cutoff (+inf when no finite d2 reaches the cutoff; NaN for a cutoff
+ * the calls refuse). Enqueued on the ctx stream, no synchronisation (the packed form shares fcz_knn_packed_dev's scratch in the
+ * ctx). FCZ_E_INVALID_ARG with nothing launched: NULL ctx / pos_true / mask_true / pos_pred / score / pairs / hits, NULL row_off
+ * with n > 0, unknown layout, slot outside the layout's width, L == 0, a cutoff that is not finite and > 0, a threshold that is NaN,
+ * L (padded) or R (packed) above 2^29 (hits must fit int32). n == 0 or R == 0: FCZ_OK (packed, n == 0 < R: every row is uncovered
+ * and is filled). The time goes to a group of its own, "lddt", for both forms. */
+int fcz_lddt_pass(void);
+float fcz_lddt_c2(float cutoff);
+int fcz_lddt_dev(fcz_ctx* ctx, const float* pos_true_dev, const uint8_t* mask_true_dev, const float* pos_pred_dev,
+                 const uint8_t* mask_pred_dev, const uint32_t* length_dev, uint32_t n, uint32_t L, int layout, int slot, float cutoff,
+                 const float* thresholds, float* score_dev, int32_t* pairs_dev, int32_t* hits_dev);
+int fcz_lddt_packed_dev(fcz_ctx* ctx, const float* pos_true_dev, const uint8_t* mask_true_dev, const float* pos_pred_dev,
+                        const uint8_t* mask_pred_dev, const uint32_t* row_off_dev, uint32_t n, uint32_t R, int layout, int slot,
+                        float cutoff, const float* thresholds, float* score_dev, int32_t* pairs_dev, int32_t* hits_dev);
+/* Host-pointer conveniences: the same arrays on the host, staged through the ctx like fcz_knn; synchronous. */
+int fcz_lddt(fcz_ctx* ctx, const float* pos_true, const uint8_t* mask_true, const float* pos_pred, const uint8_t* mask_pred,
+             const uint32_t* length, uint32_t n, uint32_t L, int layout, int slot, float cutoff, const float* thresholds,
+             float* score, int32_t* pairs, int32_t* hits);
+int fcz_lddt_packed(fcz_ctx* ctx, const float* pos_true, const uint8_t* mask_true, const float* pos_pred, const uint8_t* mask_pred,
+                    const uint32_t* row_off, uint32_t n, uint32_t R, int layout, int slot, float cutoff, const float* thresholds,
+                    float* score, int32_t* pairs, int32_t* hits);
+
 /* ---- torsion-angle tensors: the record's internal coordinates, no reconstruction ------------------------ */
 /* What Foldcomp::decompress dequantises before it places an atom (src/foldcomp.cpp:784-804: the backbone torsions and bond angles of
  * every packed word; :338-369 for the side-chain torsion bytes) and the FCZ branch of foldcomp.cxx's get_data returns as Python lists
@@ -743,7 +794,7 @@ int fcz_check(const uint8_t* entry, uint64_t len);
  * group since the last reset: "compress_sizes", "compress_index", "compress_angles", "compress_pack",
  * "decompress_sizes", "decompress_backbone", "decompress_index", "decompress_sidechain", "pdb_sizes", "pdb_format", "extract_sizes", "extract",
  * "ingest_parse", "ingest_parse_cif", "ingest_rows_cif", "ingest_frags", "ingest_fill", "inflate", "dense", "undense" (the counting and the fill
- * kernel of fcz_undense_dev: two launches per call), "angles" (fcz_angles_dev), "knn" (fcz_knn_dev and fcz_knn_packed_dev), "frames" (fcz_frames_dev). Every other packed or windowed entry point is timed under the
+ * kernel of fcz_undense_dev: two launches per call), "angles" (fcz_angles_dev), "knn" (fcz_knn_dev and fcz_knn_packed_dev), "lddt" (fcz_lddt_dev and fcz_lddt_packed_dev), "frames" (fcz_frames_dev). Every other packed or windowed entry point is timed under the
  * group of its padded form: fcz_dense_packed_dev and fcz_dense_window_dev under "dense", fcz_undense_packed_dev under "undense",
  * fcz_angles_packed_dev and fcz_angles_window_dev under "angles". */
 int  fcz_ctx_enable_timing(fcz_ctx* ctx, int enable);

@@ -7,8 +7,9 @@ from .api import (FoldcompDatabase, FoldcompError, compress, compress_many, deco
                   open, split_pdb_by_chain)
 from .api import FRAME_GROUPS, frame_ambiguous
 from .codec import ANGLE_COLUMNS
-from .tensors import decode_angles, decode_tensors, encode_tensors, lddt, neighbor_graph, rigid_frames
+from .tensors import apply_transform, decode_angles, decode_tensors, encode_tensors, lddt, neighbor_graph, rigid_frames, superpose
 
 __all__ = ["compress", "decompress", "get_data", "open", "error", "FoldcompError", "FoldcompDatabase", "compress_many",
            "decompress_many", "split_pdb_by_chain", "decode_tensors", "encode_tensors", "decode_angles", "neighbor_graph", "lddt",
+           "superpose", "apply_transform",
            "rigid_frames", "frame_ambiguous", "FRAME_GROUPS", "ANGLE_COLUMNS"]

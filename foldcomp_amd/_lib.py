@@ -9,7 +9,7 @@ from __future__ import annotations
 import ctypes
 import os
 
-from .structure import CAtomsOut, CChainBatch, CDenseIn, CDenseOut, CEntryInfo, CIngestResult, CPackedOut
+from .structure import CAtomsOut, CChainBatch, CDenseIn, CDenseOut, CEntryInfo, CIngestResult, CPackedOut, CSuperposeOut
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # FCZ_HIP_LIB selects another build of the same library (A/B timing of kernel variants); it is still a HIP build
@@ -90,6 +90,14 @@ def load():
         "fcz_lddt_packed_dev": (i32, [vp, vp, vp, vp, vp, vp, u32, u32, i32, i32, f32, vp, vp, vp, vp]),
         "fcz_lddt": (i32, [vp, vp, vp, vp, vp, vp, u32, u32, i32, i32, f32, vp, vp, vp, vp]),
         "fcz_lddt_packed": (i32, [vp, vp, vp, vp, vp, vp, u32, u32, i32, i32, f32, vp, vp, vp, vp]),
+        "fcz_superpose_dev": (i32, [vp, vp, vp, vp, vp, vp, u32, u32, i32, i32, ctypes.POINTER(CSuperposeOut)]),
+        "fcz_superpose_packed_dev": (i32, [vp, vp, vp, vp, vp, vp, u32, u32, i32, i32, ctypes.POINTER(CSuperposeOut)]),
+        "fcz_superpose": (i32, [vp, vp, vp, vp, vp, vp, u32, u32, i32, i32, ctypes.POINTER(CSuperposeOut)]),
+        "fcz_superpose_packed": (i32, [vp, vp, vp, vp, vp, vp, u32, u32, i32, i32, ctypes.POINTER(CSuperposeOut)]),
+        "fcz_superpose_apply_dev": (i32, [vp, vp, vp, vp, u32, u32, i32, vp, vp, vp]),
+        "fcz_superpose_apply_packed_dev": (i32, [vp, vp, vp, vp, u32, u32, i32, vp, vp, vp]),
+        "fcz_superpose_apply": (i32, [vp, vp, vp, vp, u32, u32, i32, vp, vp, vp]),
+        "fcz_superpose_apply_packed": (i32, [vp, vp, vp, vp, u32, u32, i32, vp, vp, vp]),
         "fcz_frames_width": (i32, [i32]),
         "fcz_frame_atom": (i32, [i32, i32, i32]),
         "fcz_frame_ambiguous": (i32, [i32, i32]),
@@ -153,6 +161,8 @@ EXPORTS = ["fcz_ctx_create", "fcz_ctx_destroy", "fcz_ctx_stream", "fcz_ctx_synch
            "fcz_dense_window_dev", "fcz_decompress_dense_window", "fcz_angles_window_dev", "fcz_decompress_angles_window",
            "fcz_knn_pass", "fcz_knn_dev", "fcz_knn_packed_dev", "fcz_knn", "fcz_knn_packed",
            "fcz_lddt_pass", "fcz_lddt_c2", "fcz_lddt_dev", "fcz_lddt_packed_dev", "fcz_lddt", "fcz_lddt_packed",
+           "fcz_superpose_dev", "fcz_superpose_packed_dev", "fcz_superpose", "fcz_superpose_packed",
+           "fcz_superpose_apply_dev", "fcz_superpose_apply_packed_dev", "fcz_superpose_apply", "fcz_superpose_apply_packed",
            "fcz_frames_width", "fcz_frame_atom", "fcz_frame_ambiguous", "fcz_frames_dev", "fcz_frames",
            "fcz_extract_sizes", "fcz_extract",
            "fcz_extract_sizes_dev", "fcz_extract_dev", "fcz_ingest_pdb_dev", "fcz_ingest_pdb_begin", "fcz_ingest_pdb_fetch", "fcz_ingest_chain_names_fetch",

@@ -383,6 +383,22 @@ def check_lddt(cutoff, thresholds, atom, width=None):
         return slot, float(np.float32(cutoff)), tuple(float(np.float32(v)) for v in th)
 
 
+GDT_THRESHOLDS = (0.5, 1.0, 2.0, 4.0, 8.0)                                  # the five counters of gdt_counts (include/fcz_hip.h, fcz_superpose_dev)
+
+
+def check_superpose(atom, shape, pred_shape, pred_mask_shape=None):
+    """the argument rules of superpose that need no torch and no GPU -> the slot (None while the layout width A is unknown): atom as
+    check_lddt reads it, against the width of `shape`, the shape of true's pos; pred's pos must have that shape, and pred's mask, when
+    there is one (pred_mask_shape is not None), the shape without its last axis"""
+    shape = tuple(shape)
+    slot = check_neighbors(1, atom, shape[-2] if len(shape) in (3, 4) else None)
+    if tuple(pred_shape) != shape:
+        raise ValueError(f"pred pos must have the shape of true pos, {shape}, not {tuple(pred_shape)}")
+    if pred_mask_shape is not None and tuple(pred_mask_shape) != shape[:-1]:
+        raise ValueError(f"pred mask must have the shape of true mask, {shape[:-1]}, not {tuple(pred_mask_shape)}")
+    return slot
+
+
 # the rigid groups of groups="all", indexed like AlphaFold / OpenFold rigidgroups_gt_frames (include/fcz_hip.h, fcz_frames_dev)
 FRAME_GROUPS = ("backbone", "unused_1", "unused_2", "psi", "chi1", "chi2", "chi3", "chi4")
 FRAME_GROUP_SETS = {"backbone": 0, "all": 1}                                 # enum fcz_frame_groups

@@ -15,7 +15,7 @@ from typing import Optional
 import numpy as np
 
 from . import _lib
-from .structure import CAtomsOut, CChainBatch, CDenseIn, CDenseOut, CEntryInfo, ChainBatch, CPackedOut, batch_as_c
+from .structure import CAtomsOut, CChainBatch, CDenseIn, CDenseOut, CEntryInfo, ChainBatch, CPackedOut, CSuperposeOut, batch_as_c
 
 
 # the columns of the angle tensors (FCZ_ANGLE_COLUMNS, include/fcz_hip.h), degrees
@@ -291,6 +291,85 @@ class Codec:
                           None if bound is None else bound.ctypes.data, n, rows, lay, slot, float(cutoff), None if th is None else th.ctypes.data,
                           score.ctypes.data, pairs.ctypes.data, hits.ctypes.data), "fcz_lddt_packed" if packed else "fcz_lddt")
         return dict(score=score, pairs=pairs, hits=hits)
+
+    @staticmethod
+    def _chain_rows(pos, packed, length, row_off):
+        """the chains of dense host arrays -> (n, rows, bound): row_off [n + 1] over the R rows, or length [n] / None over L"""
+        if packed:
+            bound = np.ascontiguousarray(row_off, np.uint32)
+            if bound.ndim != 1 or len(bound) < 1:
+                raise ValueError("row_off must be [n + 1]")
+            n, rows = len(bound) - 1, pos.shape[0]
+        else:
+            n, rows, bound = pos.shape[0], pos.shape[1], None
+            if length is not None:
+                bound = np.ascontiguousarray(length, np.uint32)
+                if bound.shape != (n,):
+                    raise ValueError(f"length must be [{n}], not {bound.shape}")
+        if rows > 2 ** 31 - 1:
+            raise ValueError("at most 2^31 - 1 rows per chain")
+        return n, rows, bound
+
+    def superpose(self, pos_true: np.ndarray, mask_true: np.ndarray, pos_pred: np.ndarray, mask_pred=None, slot: int = 1, length=None, row_off=None):
+        """two sets of dense arrays of one shape on the host -> the least-squares superposition of every chain of `pred` onto `true`
+        on the sites at `slot` (fcz_superpose, or fcz_superpose_packed when row_off is given): rot float32 [n, 3, 3] and trans [n, 3]
+        (x_true ~ rot @ x_pred + trans), rmsd [n], sites int32 [n], gdt_counts int32 [n, 5] (dev <= 0.5, 1, 2, 4, 8), tm [n] (the
+        TM-score at this superposition, a lower bound of the maximised one) and dev float32 [n, L] / [R], every site's deviation.
+        The arrays are those of Codec.lddt. The sums are float64 in a fixed order: reproducible bit for bit, not differentiable."""
+        pos_true = np.ascontiguousarray(pos_true, np.float32)
+        pos_pred = np.ascontiguousarray(pos_pred, np.float32)
+        packed = row_off is not None
+        if pos_true.ndim != (3 if packed else 4) or pos_true.shape[-1] != 3 or pos_true.shape[-2] not in (37, 14, 4):
+            raise ValueError(f"pos_true must be float32 {'[R, A, 3]' if packed else '[n, L, A, 3]'} with A = 37, 14 or 4, not {pos_true.shape}")
+        if pos_pred.shape != pos_true.shape:
+            raise ValueError(f"pos_pred must have the shape of pos_true, {pos_true.shape}, not {pos_pred.shape}")
+        A = pos_true.shape[-2]
+        lay = {37: 0, 14: 1, 4: 2}[A]
+        masks = []
+        for name, m in (("mask_true", mask_true), ("mask_pred", mask_pred)):
+            if m is not None:
+                m = np.ascontiguousarray(m)
+                if m.shape != pos_true.shape[:-1] or m.dtype not in (np.bool_, np.uint8):
+                    raise ValueError(f"{name} must be bool / uint8 {pos_true.shape[:-1]}, not {m.dtype} {m.shape}")
+            masks.append(m)
+        if masks[0] is None:
+            raise ValueError("mask_true is needed")
+        slot = int(slot)
+        if not 0 <= slot < A:
+            raise ValueError(f"slot must be 0 .. {A - 1}")
+        n, rows, bound = self._chain_rows(pos_true, packed, length, row_off)
+        d = dict(rot=np.tile(np.eye(3, dtype=np.float32), (n, 1, 1)), trans=np.zeros((n, 3), np.float32), rmsd=np.zeros(n, np.float32),
+                 sites=np.zeros(n, np.int32), gdt_counts=np.zeros((n, 5), np.int32), tm=np.zeros(n, np.float32), dev=np.zeros(pos_true.shape[:-2], np.float32))
+        if n and rows:
+            out = CSuperposeOut(*(d[k].ctypes.data for k in ("rot", "trans", "rmsd", "sites", "gdt_counts", "tm", "dev")))
+            fn = self.lib.fcz_superpose_packed if packed else self.lib.fcz_superpose
+            _lib.check(fn(self.ctx, pos_true.ctypes.data, masks[0].ctypes.data, pos_pred.ctypes.data, None if masks[1] is None else masks[1].ctypes.data,
+                          None if bound is None else bound.ctypes.data, n, rows, lay, slot, ctypes.byref(out)), "fcz_superpose_packed" if packed else "fcz_superpose")
+        return d
+
+    def apply_transform(self, pos: np.ndarray, rot: np.ndarray, trans: np.ndarray, mask=None, length=None, row_off=None):
+        """dense coordinates on the host moved by one rigid transform per chain (fcz_superpose_apply, or fcz_superpose_apply_packed
+        when row_off is given) -> pos_out float32 of the shape of pos: rot[e] @ x + trans[e] for every slot whose mask is set (None:
+        every slot) in the rows of chain e, 0 elsewhere; float32 in the order x' = ((r00 x + r01 y) + r02 z) + tx."""
+        pos = np.ascontiguousarray(pos, np.float32)
+        packed = row_off is not None
+        if pos.ndim != (3 if packed else 4) or pos.shape[-1] != 3 or pos.shape[-2] not in (37, 14, 4):
+            raise ValueError(f"pos must be float32 {'[R, A, 3]' if packed else '[n, L, A, 3]'} with A = 37, 14 or 4, not {pos.shape}")
+        lay = {37: 0, 14: 1, 4: 2}[pos.shape[-2]]
+        if mask is not None:
+            mask = np.ascontiguousarray(mask)
+            if mask.shape != pos.shape[:-1] or mask.dtype not in (np.bool_, np.uint8):
+                raise ValueError(f"mask must be bool / uint8 {pos.shape[:-1]}, not {mask.dtype} {mask.shape}")
+        n, rows, bound = self._chain_rows(pos, packed, length, row_off)
+        rot, trans = np.ascontiguousarray(rot, np.float32), np.ascontiguousarray(trans, np.float32)
+        if rot.shape != (n, 3, 3) or trans.shape != (n, 3):
+            raise ValueError(f"rot must be [{n}, 3, 3] and trans [{n}, 3], one transform per chain, not {rot.shape} and {trans.shape}")
+        out = np.zeros(pos.shape, np.float32)
+        if n and out.size:
+            fn = self.lib.fcz_superpose_apply_packed if packed else self.lib.fcz_superpose_apply
+            _lib.check(fn(self.ctx, pos.ctypes.data, None if mask is None else mask.ctypes.data, None if bound is None else bound.ctypes.data, n, rows, lay,
+                          rot.ctypes.data, trans.ctypes.data, out.ctypes.data), "fcz_superpose_apply_packed" if packed else "fcz_superpose_apply")
+        return out
 
     def frames(self, pos: np.ndarray, mask: np.ndarray, aatype=None, length=None, layout=None, groups="backbone"):
         """dense arrays on the host -> the rigid frames of every residue (fcz_frames): rot float32 [.., 3, 3], trans [.., 3] and

@@ -35,6 +35,7 @@
 #include "fcz_undense.h"
 #include "fcz_knn.h"
 #include "fcz_lddt.h"
+#include "fcz_superpose.h"
 #include "fcz_frames.h"
 #include "fcz_angles.h"
 
@@ -88,9 +89,12 @@ struct timed_span { std::string name; hipEvent_t a, b; };
 // arrays of a fcz_chain_batch, the 10 of a fcz_dense_in (slot 3, length, holds row_off [n + 1] in the packed form), the 6 of a
 // fcz_dense_out, the 7 of a fcz_packed_out (PACKED_OUT .. PACKED_OUT_LAST), in the struct's order; ANGLES_OUT: the angles, their mask and
 // (windowed form) aatype; WINDOW_START: the n u32 starts of a windowed host call; KEPT_*: the records a *_begin call leaves for its fetch
-// (C + 1 u64 offsets, the bytes, C i32 status); LDDT_PRED: pos and mask of the second tensor batch of fcz_lddt, LDDT_OUT: score, pairs, hits
+// (C + 1 u64 offsets, the bytes, C i32 status); LDDT_PRED: pos and mask of the second tensor batch of fcz_lddt, LDDT_OUT: score, pairs, hits;
+// SUPERPOSE_OUT: the seven arrays of a fcz_superpose_out in the struct's order; APPLY_ROT, APPLY_TRANS, APPLY_OUT: the transforms and the moved
+// coordinates of fcz_superpose_apply (its pos and mask go through LDDT_PRED)
 enum { REC_BLOB, REC_OFF, REC_RES_OFF, REC_ATOM_OFF, REC_X, REC_Y, REC_Z, REC_BFAC, REC_RES_CODE, REC_ATOM_CODE,
-       FILES_TEXT = 0, FILES_OFF, FILES_NAMES, FILES_NAME_OFF, FILES_STEM_LEN, BATCH_IN = 0, DENSE_IN = 0, LDDT_PRED = 4, DENSE_OUT = 10, LDDT_OUT = 10,
+       FILES_TEXT = 0, FILES_OFF, FILES_NAMES, FILES_NAME_OFF, FILES_STEM_LEN, BATCH_IN = 0, DENSE_IN = 0, LDDT_PRED = 4, DENSE_OUT = 10, LDDT_OUT = 10, SUPERPOSE_OUT = 10,
+       APPLY_ROT = 10, APPLY_TRANS, APPLY_OUT,
        PACKED_OUT = 10, ANGLES_OUT = 10, KEPT_OFF = 13, KEPT_BYTES, KEPT_STATUS, PACKED_OUT_LAST, WINDOW_START = PACKED_OUT_LAST, POOL_COUNT };
 
 // what the device reports to the host in the middle of a call: one pinned allocation, a member per reader
@@ -140,7 +144,7 @@ struct fcz_ctx {
     dev_buf res_sc;     // decompress: residue -> its side-chain torsion bytes, 3 x R dwords
     dev_buf sizes_res_off;   // decompress: the res_off of a batch call that has to run its own sizes pass (ensure_sizes)
     dev_buf selftest_out;    // fcz_selftest_math
-    dev_buf knn_tiles;       // fcz_knn_packed_dev, fcz_lddt_packed_dev (chain_tile_scan): n u64 tile counts, then their n + 1 offsets
+    dev_buf knn_tiles;       // fcz_knn_packed_dev, fcz_lddt_packed_dev, fcz_superpose_apply_packed_dev (chain_tile_scan): n u64 tile counts, then their n + 1 offsets
     dev_buf fast_scratch;    // decompress, FCZ_NUMERICS_FAST: forward atoms of segments longer than one chunk
     // Staging of the host-pointer entry points. Every entry point that writes it calls claim_staging first. Nothing outlives the call
     // that wrote it but KEPT_*, which a begin leaves for its fetch: any later call that writes 13 .. 15 ends that.
@@ -162,6 +166,8 @@ struct fcz_ctx {
     //   fcz_compress_dense_packed_begin[_dev]       as the two above (DENSE_IN 3 = row_off)     the same
     //   fcz_knn / fcz_knn_packed                    DENSE_IN 0, 1, 3 (pos, mask, length / row_off), DENSE_OUT 10 .. 11 (index, dist)
     //   fcz_lddt / fcz_lddt_packed                  DENSE_IN 0, 1, 3 (pos_true, mask_true, length / row_off), LDDT_PRED 4 .. 5 (pos_pred, mask_pred), LDDT_OUT 10 .. 12
+    //   fcz_superpose / fcz_superpose_packed        DENSE_IN 0, 1, 3 and LDDT_PRED 4 .. 5 as fcz_lddt, SUPERPOSE_OUT 10 .. 16
+    //   fcz_superpose_apply[_packed]                LDDT_PRED 4 .. 5 (pos, mask), DENSE_IN 3 (length / row_off), APPLY_ROT 10, APPLY_TRANS 11, APPLY_OUT 12
     //   fcz_frames                                  DENSE_IN 0 .. 3 (pos, mask, aatype, length), DENSE_OUT 10 .. 12 (rot, trans, frame_mask)
     dev_buf pool[POOL_COUNT];
     // PDB text / extracted data: per-entry sizes (any call), offsets (n + 1 u64) and the text of the last fcz_decompress_pdb_begin,
@@ -1860,6 +1866,186 @@ int fcz_lddt_packed(fcz_ctx* ctx, const float* pos_true, const uint8_t* mask_tru
     if (!lddt_args_ok(ctx, pos_true, mask_true, pos_pred, layout, slot, cutoff, thresholds, R, score, pairs, hits) || (n && !row_off))
         return FCZ_E_INVALID_ARG;
     return lddt_host(ctx, pos_true, mask_true, pos_pred, mask_pred, row_off, true, n, R, layout, slot, cutoff, thresholds, score, pairs, hits);
+}
+
+// ------------------------------------------------------------------------------------------------
+// least-squares superposition of two dense tensor batches (fcz_superpose.h; no counterpart in the reference)
+// ------------------------------------------------------------------------------------------------
+// rows: L (padded) or R (packed)
+static bool superpose_args_ok(const fcz_ctx* ctx, const float* pos_true, const uint8_t* mask_true, const float* pos_pred, int layout, int slot, uint32_t rows,
+                              const fcz_superpose_out* out) {
+    if (!ctx || !pos_true || !mask_true || !pos_pred || !out || !out->rot || !out->trans) return false;
+    if (fcz_dense_width(layout) <= 0 || slot < 0 || slot >= fcz_dense_width(layout)) return false;
+    return rows <= SUPERPOSE_MAX_ROWS;
+}
+
+// fcz_superpose_dev (bound_dev is length [n] or NULL, rows = L) and fcz_superpose_packed_dev (bound_dev = row_off [n + 1], rows = R)
+static int superpose_rows(fcz_ctx* ctx, const float* pos_true_dev, const uint8_t* mask_true_dev, const float* pos_pred_dev, const uint8_t* mask_pred_dev,
+                          const uint32_t* bound_dev, bool packed, uint32_t n, uint32_t rows, int layout, int slot, const fcz_superpose_out& o) {
+    HIP_TRY(hipSetDevice(ctx->device));
+    const bool fill = packed && rows && o.dev;
+    if (n == 0 && !fill) return FCZ_OK;
+    const superpose_args g{pos_true_dev, mask_true_dev, pos_pred_dev, mask_pred_dev, bound_dev, n, rows, (uint32_t)fcz_dense_width(layout), (uint32_t)slot,
+                           o.rot, o.trans, o.rmsd, o.sites, o.gdt_counts, o.tm, o.dev};
+    const uint32_t max_blocks = (uint32_t)ctx->n_cu * 16u;
+    span_guard sg(ctx, "superpose");
+    if (fill)
+        hipLaunchKernelGGL(k_superpose_fill, dim3((uint32_t)std::min<uint64_t>(((uint64_t)rows + BLOCK - 1) / BLOCK, max_blocks)), dim3(BLOCK), 0, ctx->stream, g);
+    if (n) {
+        const dim3 grid(std::min(grid_for(n, WAVES_PER_BLOCK), max_blocks));
+        if (packed) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_superpose<true>), grid, dim3(BLOCK), 0, ctx->stream, g);
+        else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_superpose<false>), grid, dim3(BLOCK), 0, ctx->stream, g);
+    }
+    HIP_TRY(hipGetLastError());
+    return FCZ_OK;
+}
+
+int fcz_superpose_dev(fcz_ctx* ctx, const float* pos_true_dev, const uint8_t* mask_true_dev, const float* pos_pred_dev, const uint8_t* mask_pred_dev,
+                      const uint32_t* length_dev, uint32_t n, uint32_t L, int layout, int slot, const fcz_superpose_out* out_dev) {
+    if (!superpose_args_ok(ctx, pos_true_dev, mask_true_dev, pos_pred_dev, layout, slot, L, out_dev) || L == 0) return FCZ_E_INVALID_ARG;
+    return superpose_rows(ctx, pos_true_dev, mask_true_dev, pos_pred_dev, mask_pred_dev, length_dev, false, n, L, layout, slot, *out_dev);
+}
+
+int fcz_superpose_packed_dev(fcz_ctx* ctx, const float* pos_true_dev, const uint8_t* mask_true_dev, const float* pos_pred_dev, const uint8_t* mask_pred_dev,
+                             const uint32_t* row_off_dev, uint32_t n, uint32_t R, int layout, int slot, const fcz_superpose_out* out_dev) {
+    if (!superpose_args_ok(ctx, pos_true_dev, mask_true_dev, pos_pred_dev, layout, slot, R, out_dev) || (n && !row_off_dev)) return FCZ_E_INVALID_ARG;
+    return superpose_rows(ctx, pos_true_dev, mask_true_dev, pos_pred_dev, mask_pred_dev, row_off_dev, true, n, R, layout, slot, *out_dev);
+}
+
+static bool superpose_apply_args_ok(const fcz_ctx* ctx, const float* pos, int layout, uint32_t rows, const float* rot, const float* trans, const float* pos_out) {
+    return ctx && pos && rot && trans && pos_out && fcz_dense_width(layout) > 0 && rows <= SUPERPOSE_MAX_ROWS;
+}
+
+// fcz_superpose_apply_dev (rows = L) and fcz_superpose_apply_packed_dev (rows = R)
+static int superpose_apply_rows(fcz_ctx* ctx, const float* pos_dev, const uint8_t* mask_dev, const uint32_t* bound_dev, bool packed, uint32_t n, uint32_t rows,
+                                int layout, const float* rot_dev, const float* trans_dev, float* pos_out_dev) {
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (rows == 0 || (n == 0 && !packed)) return FCZ_OK;
+    const superpose_apply_args g{pos_dev, mask_dev, bound_dev, n, rows, rot_dev, trans_dev, pos_out_dev};
+    const uint32_t max_blocks = (uint32_t)ctx->n_cu * 16u;
+    chain_tiles ct;
+    if (!packed || n) { int rc = ct.reserve(ctx, packed, n, rows); if (rc) return rc; }
+    span_guard sg(ctx, "superpose");
+    int rc = FCZ_OK;
+    dispatch_layout(layout, [&](auto W) {
+        constexpr int A = decltype(W)::value;
+        if (packed) {
+            const uint64_t floats = (uint64_t)rows * (A * 3u);
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_superpose_apply_fill<A>), dim3((uint32_t)std::min<uint64_t>((floats + BLOCK - 1) / BLOCK, max_blocks)), dim3(BLOCK), 0,
+                               ctx->stream, g);
+            if (n == 0) return;
+            if ((rc = ct.scan(ctx, bound_dev, n, rows))) return;
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_superpose_apply<A, true>), dim3((uint32_t)ct.blocks), dim3(BLOCK), 0, ctx->stream, g, ct.tile_off, 0u, (uint64_t)0);
+        } else {
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_superpose_apply<A, false>), dim3((uint32_t)ct.blocks), dim3(BLOCK), 0, ctx->stream, g, (const uint64_t*)nullptr,
+                               ct.tiles_per_entry, ct.n_padded);
+        }
+    });
+    if (rc) return rc;
+    HIP_TRY(hipGetLastError());
+    return FCZ_OK;
+}
+
+int fcz_superpose_apply_dev(fcz_ctx* ctx, const float* pos_dev, const uint8_t* mask_dev, const uint32_t* length_dev, uint32_t n, uint32_t L, int layout,
+                            const float* rot_dev, const float* trans_dev, float* pos_out_dev) {
+    if (!superpose_apply_args_ok(ctx, pos_dev, layout, L, rot_dev, trans_dev, pos_out_dev) || L == 0) return FCZ_E_INVALID_ARG;
+    return superpose_apply_rows(ctx, pos_dev, mask_dev, length_dev, false, n, L, layout, rot_dev, trans_dev, pos_out_dev);
+}
+
+int fcz_superpose_apply_packed_dev(fcz_ctx* ctx, const float* pos_dev, const uint8_t* mask_dev, const uint32_t* row_off_dev, uint32_t n, uint32_t R, int layout,
+                                   const float* rot_dev, const float* trans_dev, float* pos_out_dev) {
+    if (!superpose_apply_args_ok(ctx, pos_dev, layout, R, rot_dev, trans_dev, pos_out_dev) || (n && !row_off_dev)) return FCZ_E_INVALID_ARG;
+    return superpose_apply_rows(ctx, pos_dev, mask_dev, row_off_dev, true, n, R, layout, rot_dev, trans_dev, pos_out_dev);
+}
+
+// fcz_superpose and fcz_superpose_packed: the host arrays through DENSE_IN 0, 1, 3, LDDT_PRED 4, 5 and SUPERPOSE_OUT 10 .. 16
+static int superpose_host(fcz_ctx* ctx, const float* pos_true, const uint8_t* mask_true, const float* pos_pred, const uint8_t* mask_pred, const uint32_t* bound,
+                          bool packed, uint32_t n, uint32_t rows_per, int layout, int slot, const fcz_superpose_out& out) {
+    HIP_TRY(hipSetDevice(ctx->device));
+    claim_staging(ctx);
+    const size_t rows = packed ? (size_t)rows_per : (size_t)n * rows_per, A = (size_t)fcz_dense_width(layout);
+    if (n == 0 && rows == 0) return FCZ_OK;
+    const size_t nb = bound ? sizeof(uint32_t) * ((size_t)n + (packed ? 1 : 0)) : 0, np = rows * A * 3 * sizeof(float), nm = rows * A;
+    void* host[7] = {out.rot, out.trans, out.rmsd, out.sites, out.gdt_counts, out.tm, out.dev};
+    const size_t bytes[7] = {36 * (size_t)n, 12 * (size_t)n, 4 * (size_t)n, 4 * (size_t)n, 20 * (size_t)n, 4 * (size_t)n, 4 * rows};
+    int rc;
+    if ((rc = ctx->pool[DENSE_IN].ensure(np)) || (rc = ctx->pool[DENSE_IN + 1].ensure(nm)) || (rc = ctx->pool[DENSE_IN + 3].ensure(nb)) ||
+        (rc = ctx->pool[LDDT_PRED].ensure(np)) || (rc = ctx->pool[LDDT_PRED + 1].ensure(mask_pred ? nm : 0)))
+        return rc;
+    void* d[7];
+    for (int i = 0; i < 7; i++) {
+        if ((rc = ctx->pool[SUPERPOSE_OUT + i].ensure(host[i] ? bytes[i] : 0))) return rc;
+        d[i] = host[i] ? ctx->pool[SUPERPOSE_OUT + i].p : nullptr;
+    }
+    if (np) {
+        HIP_TRY(hipMemcpyAsync(ctx->pool[DENSE_IN].p, pos_true, np, hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(hipMemcpyAsync(ctx->pool[DENSE_IN + 1].p, mask_true, nm, hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(hipMemcpyAsync(ctx->pool[LDDT_PRED].p, pos_pred, np, hipMemcpyHostToDevice, ctx->stream));
+        if (mask_pred) HIP_TRY(hipMemcpyAsync(ctx->pool[LDDT_PRED + 1].p, mask_pred, nm, hipMemcpyHostToDevice, ctx->stream));
+    }
+    if (nb) HIP_TRY(hipMemcpyAsync(ctx->pool[DENSE_IN + 3].p, bound, nb, hipMemcpyHostToDevice, ctx->stream));
+    // (R == 0 with chains: the arrays have no allocation and every chain is empty, so nothing of them is read)
+    const fcz_superpose_out o{(float*)d[0], (float*)d[1], (float*)d[2], (int32_t*)d[3], (int32_t*)d[4], (float*)d[5], (float*)d[6]};
+    rc = superpose_rows(ctx, ctx->pool[DENSE_IN].as<float>(), ctx->pool[DENSE_IN + 1].as<uint8_t>(), ctx->pool[LDDT_PRED].as<float>(),
+                        mask_pred && np ? ctx->pool[LDDT_PRED + 1].as<uint8_t>() : nullptr, nb ? ctx->pool[DENSE_IN + 3].as<uint32_t>() : nullptr, packed, n,
+                        rows_per, layout, slot, o);
+    if (rc) return rc;
+    for (int i = 0; i < 7; i++)
+        if (host[i] && bytes[i]) HIP_TRY(hipMemcpyAsync(host[i], d[i], bytes[i], hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return FCZ_OK;
+}
+
+int fcz_superpose(fcz_ctx* ctx, const float* pos_true, const uint8_t* mask_true, const float* pos_pred, const uint8_t* mask_pred, const uint32_t* length,
+                  uint32_t n, uint32_t L, int layout, int slot, const fcz_superpose_out* out) {
+    if (!superpose_args_ok(ctx, pos_true, mask_true, pos_pred, layout, slot, L, out) || L == 0) return FCZ_E_INVALID_ARG;
+    return superpose_host(ctx, pos_true, mask_true, pos_pred, mask_pred, length, false, n, L, layout, slot, *out);
+}
+
+int fcz_superpose_packed(fcz_ctx* ctx, const float* pos_true, const uint8_t* mask_true, const float* pos_pred, const uint8_t* mask_pred, const uint32_t* row_off,
+                         uint32_t n, uint32_t R, int layout, int slot, const fcz_superpose_out* out) {
+    if (!superpose_args_ok(ctx, pos_true, mask_true, pos_pred, layout, slot, R, out) || (n && !row_off)) return FCZ_E_INVALID_ARG;
+    return superpose_host(ctx, pos_true, mask_true, pos_pred, mask_pred, row_off, true, n, R, layout, slot, *out);
+}
+
+// fcz_superpose_apply and fcz_superpose_apply_packed: the host arrays through LDDT_PRED 4, 5, DENSE_IN 3 and APPLY_ROT, APPLY_TRANS, APPLY_OUT
+static int superpose_apply_host(fcz_ctx* ctx, const float* pos, const uint8_t* mask, const uint32_t* bound, bool packed, uint32_t n, uint32_t rows_per,
+                                int layout, const float* rot, const float* trans, float* pos_out) {
+    HIP_TRY(hipSetDevice(ctx->device));
+    claim_staging(ctx);
+    const size_t rows = packed ? (size_t)rows_per : (size_t)n * rows_per, A = (size_t)fcz_dense_width(layout);
+    if (rows == 0) return FCZ_OK;
+    const size_t nb = bound ? sizeof(uint32_t) * ((size_t)n + (packed ? 1 : 0)) : 0, np = rows * A * 3 * sizeof(float), nm = rows * A;
+    int rc;
+    if ((rc = ctx->pool[LDDT_PRED].ensure(np)) || (rc = ctx->pool[LDDT_PRED + 1].ensure(mask ? nm : 0)) || (rc = ctx->pool[DENSE_IN + 3].ensure(nb)) ||
+        (rc = ctx->pool[APPLY_ROT].ensure(36 * (size_t)n + 4)) || (rc = ctx->pool[APPLY_TRANS].ensure(12 * (size_t)n + 4)) || (rc = ctx->pool[APPLY_OUT].ensure(np)))
+        return rc;
+    HIP_TRY(hipMemcpyAsync(ctx->pool[LDDT_PRED].p, pos, np, hipMemcpyHostToDevice, ctx->stream));
+    if (mask) HIP_TRY(hipMemcpyAsync(ctx->pool[LDDT_PRED + 1].p, mask, nm, hipMemcpyHostToDevice, ctx->stream));
+    if (nb) HIP_TRY(hipMemcpyAsync(ctx->pool[DENSE_IN + 3].p, bound, nb, hipMemcpyHostToDevice, ctx->stream));
+    if (n) {
+        HIP_TRY(hipMemcpyAsync(ctx->pool[APPLY_ROT].p, rot, 36 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(hipMemcpyAsync(ctx->pool[APPLY_TRANS].p, trans, 12 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+    }
+    rc = superpose_apply_rows(ctx, ctx->pool[LDDT_PRED].as<float>(), mask ? ctx->pool[LDDT_PRED + 1].as<uint8_t>() : nullptr,
+                              nb ? ctx->pool[DENSE_IN + 3].as<uint32_t>() : nullptr, packed, n, rows_per, layout, ctx->pool[APPLY_ROT].as<float>(),
+                              ctx->pool[APPLY_TRANS].as<float>(), ctx->pool[APPLY_OUT].as<float>());
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(pos_out, ctx->pool[APPLY_OUT].p, np, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return FCZ_OK;
+}
+
+int fcz_superpose_apply(fcz_ctx* ctx, const float* pos, const uint8_t* mask, const uint32_t* length, uint32_t n, uint32_t L, int layout, const float* rot,
+                        const float* trans, float* pos_out) {
+    if (!superpose_apply_args_ok(ctx, pos, layout, L, rot, trans, pos_out) || L == 0) return FCZ_E_INVALID_ARG;
+    return superpose_apply_host(ctx, pos, mask, length, false, n, L, layout, rot, trans, pos_out);
+}
+
+int fcz_superpose_apply_packed(fcz_ctx* ctx, const float* pos, const uint8_t* mask, const uint32_t* row_off, uint32_t n, uint32_t R, int layout, const float* rot,
+                               const float* trans, float* pos_out) {
+    if (!superpose_apply_args_ok(ctx, pos, layout, R, rot, trans, pos_out) || (n && !row_off)) return FCZ_E_INVALID_ARG;
+    return superpose_apply_host(ctx, pos, mask, row_off, true, n, R, layout, rot, trans, pos_out);
 }
 
 // ------------------------------------------------------------------------------------------------

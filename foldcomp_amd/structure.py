@@ -974,6 +974,12 @@ class CPackedOut(ctypes.Structure):
                 ("res_index", ctypes.c_void_p), ("chain_index", ctypes.c_void_p), ("length", ctypes.c_void_p)]
 
 
+class CSuperposeOut(ctypes.Structure):
+    """fcz_superpose_out (include/fcz_hip.h): the outputs of the superposition calls; all but rot and trans may be None"""
+    _fields_ = [("rot", ctypes.c_void_p), ("trans", ctypes.c_void_p), ("rmsd", ctypes.c_void_p), ("sites", ctypes.c_void_p),
+                ("gdt_counts", ctypes.c_void_p), ("tm", ctypes.c_void_p), ("dev", ctypes.c_void_p)]
+
+
 class CDenseIn(ctypes.Structure):
     """fcz_dense_in (include/fcz_hip.h): dense tensors + per-chain header fields handed to the undense / compress_dense calls"""
     _fields_ = [("pos", ctypes.c_void_p), ("mask", ctypes.c_void_p), ("aatype", ctypes.c_void_p), ("length", ctypes.c_void_p),

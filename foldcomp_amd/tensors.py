@@ -14,6 +14,9 @@
                                    the k nearest CA / CB sites of every residue inside its chain; decode_tensors(neighbors=k) adds them
     lddt(pred, true, atom="CA", cutoff=15.0) -> dict(lddt [..] float32, lddt_pairs, lddt_hits int32, lddt_chain [n] float32): the per-residue
                                    lDDT of predicted coordinates against a decoded batch, and its chain mean
+    superpose(pred, true, atom="CA", apply=False) -> dict(rot [n, 3, 3], trans [n, 3], rmsd [n], sites [n], dev [..], gdt_counts [n, 5],
+                                   gdt_ts, gdt_ha, tm [n]): the least-squares superposition of every chain of pred onto true;
+                                   apply=True adds pos_aligned; apply_transform(pos, rot, trans, batch) is that step alone
     rigid_frames(either dict, or the tensors as keywords, groups="backbone" | "all") -> dict(rot [.., 3, 3], trans [.., 3], frame_mask):
                                    every residue's backbone frame, or the eight rigid groups; decode_tensors(frames=...) adds them
 
@@ -36,9 +39,9 @@ import numpy as np
 from . import _lib, api, fczfile
 from ._aa_tables import RES1
 from .codec import ANGLE_COLUMNS, Codec, dense_layout
-from .structure import CAtomsOut, CDenseIn, CDenseOut, CPackedOut
+from .structure import CAtomsOut, CDenseIn, CDenseOut, CPackedOut, CSuperposeOut
 
-__all__ = ["decode_tensors", "encode_tensors", "decode_angles", "crop_starts", "neighbor_graph", "rigid_frames", "lddt"]
+__all__ = ["decode_tensors", "encode_tensors", "decode_angles", "crop_starts", "neighbor_graph", "rigid_frames", "lddt", "superpose", "apply_transform"]
 
 
 def crop_starts(length, L: int, how, generator=None):
@@ -590,6 +593,150 @@ def lddt(pred, true, *, atom="CA", cutoff: float = 15.0, thresholds=(0.5, 1.0, 2
         ch, cp = hits.to(torch.int64).sum(dim=1), pairs.to(torch.int64).sum(dim=1)
     chain = torch.where(cp > 0, ch.to(torch.float64) / (4 * cp).clamp(min=1).to(torch.float64), torch.zeros((), dtype=torch.float64, device=dev))
     return dict(lddt=score, lddt_pairs=pairs, lddt_hits=hits, lddt_chain=chain.to(torch.float32))
+
+
+def _apply_transform(c, pos, mask, rot, trans, n, rows, bound, is_packed, lay, out):
+    """fcz_superpose_apply_dev / _packed_dev on checked device tensors into `out`, enqueued on the codec's stream"""
+    if n == 0:                                                                # (packed rows without a chain: covered by none)
+        out.zero_()
+    elif out.numel():
+        fn, name = (c.lib.fcz_superpose_apply_packed_dev, "fcz_superpose_apply_packed_dev") if is_packed else (c.lib.fcz_superpose_apply_dev, "fcz_superpose_apply_dev")
+        _lib.check(fn(c.ctx, pos.data_ptr(), None if mask is None else mask.data_ptr(), None if bound is None else bound.data_ptr(), n, rows, lay,
+                      rot.data_ptr(), trans.data_ptr(), out.data_ptr()), name)
+
+
+def superpose(pred, true, *, atom="CA", apply: bool = False, codec: Optional[Codec] = None) -> dict:
+    """predicted coordinates against true ones, both dense tensors on the GPU -> the least-squares (Kabsch) superposition of every
+    chain of `pred` onto `true` on the sites of one atom, and the scores that depend on it.
+
+    The inputs are lddt's: `true` is the dict decode_tensors / tensor_batches return, padded or packed (`length` is ignored when the
+    dict carries crop_start); `pred` is a dict with `pos` and optionally `mask`, or just the pos tensor, of the same shape. atom:
+    "CA", "CB" (atom37 / atom14) or an integer slot. A row is a site by lddt's rule. Per chain, from float64 sums in a fixed order
+    (include/fcz_hip.h, fcz_superpose_dev), so two calls, or the padded and the packed form, give the same bits:
+        rot [n, 3, 3], trans [n, 3] float32   x_true ~ rot @ x_pred + trans (rigid_frames' convention); rot is a proper rotation
+        rmsd [n] float32                      the RMSD of the sites after the superposition
+        sites [n] int32                       the number of sites
+        dev [n, L] / [R] float32              every site's deviation after the superposition, 0 where the row is no site
+        gdt_counts [n, 5] int32               the sites with dev <= 0.5, 1, 2, 4, 8
+        gdt_ts, gdt_ha [n] float32            the mean fraction at 1, 2, 4, 8 and at 0.5, 1, 2, 4 (in float64 from the integers)
+        tm [n] float32                        the TM-score AT THIS SUPERPOSITION, normalised by the sites: a lower bound of what
+                                              TM-score programs report, which search for the superposition that maximises it
+    A chain without sites gets the identity, 0 and scores of 0; one site the identity rotation; two or collinear sites a minimiser.
+    apply=True adds pos_aligned, pred's pos moved onto true (apply_transform), enqueued behind the solve with no host round trip.
+    It is NOT differentiable. The tensors must be contiguous and lie on the codec's device; ordering against torch is
+    decode_tensors'. atom and shapes that differ are checked first, without torch or a device (api.check_superpose)."""
+    t = dict(true) if isinstance(true, dict) else {"pos": true}
+    p = dict(pred) if isinstance(pred, dict) else {"pos": pred}
+    pos = t.get("pos")
+    shape = tuple(getattr(pos, "shape", ()))
+    is_packed = t.get("cu_seqlens") is not None and len(shape) == 3
+    for name, d, keys in (("true", t, ("pos", "mask")), ("pred", p, ("pos",))):
+        for key in keys:
+            if d.get(key) is None:
+                raise TypeError(f"superpose needs the tensor {key!r} of {name}")
+    ppos, pmask = p["pos"], p.get("mask")
+    slot = api.check_superpose(atom, shape, getattr(ppos, "shape", ()), None if pmask is None else getattr(pmask, "shape", ()))
+    c = codec or api.default_codec()
+    try:
+        import torch
+    except ImportError as e:
+        raise api.error(f"superpose needs PyTorch (ROCm build): {e}") from None
+    if not isinstance(pos, torch.Tensor):
+        raise api.error("superpose takes torch tensors on the GPU (numpy arrays: Codec.superpose)")
+    if pos.device.type != "cuda" or pos.device.index != int(c.device):
+        raise api.error(f"superpose: pos lies on {pos.device}, the codec works on cuda:{int(c.device)}; there is no CPU path")
+    dev = pos.device
+    if len(shape) != (3 if is_packed else 4) or shape[-1] != 3 or pos.dtype != torch.float32:
+        raise ValueError(f"pos must be float32 [n, L, A, 3], or [R, A, 3] beside cu_seqlens, not {pos.dtype} {shape}")
+    lay = dense_layout(_WIDTH_LAYOUT[shape[-2]])
+    _on_device(torch, "superpose", dev, "pos", pos, shape, (torch.float32,))
+    mask = _on_device(torch, "superpose", dev, "mask", t["mask"], shape[:-1], (torch.bool, torch.uint8)).view(torch.uint8)
+    _on_device(torch, "superpose", dev, "pred pos", ppos, shape, (torch.float32,))
+    if pmask is not None:
+        pmask = _on_device(torch, "superpose", dev, "pred mask", pmask, shape[:-1], (torch.bool, torch.uint8)).view(torch.uint8)
+    n, rows, bound = _chain_bound(torch, "superpose", dev, t, shape, is_packed)
+    if rows > 2 ** 31 - 1:
+        raise ValueError("sites must fit int32: at most 2^31 - 1 rows per chain")
+    out = dict(rot=torch.empty((n, 3, 3), dtype=torch.float32, device=dev), trans=torch.empty((n, 3), dtype=torch.float32, device=dev),
+               rmsd=torch.empty((n,), dtype=torch.float32, device=dev), sites=torch.empty((n,), dtype=torch.int32, device=dev),
+               dev=torch.zeros(shape[:-2], dtype=torch.float32, device=dev), gdt_counts=torch.empty((n, 5), dtype=torch.int32, device=dev),
+               tm=torch.empty((n,), dtype=torch.float32, device=dev))
+    if apply:
+        out["pos_aligned"] = torch.empty_like(ppos)
+    solve = bool(n and rows)
+    if n and not solve:                                                       # chains of no rows: what a chain without sites gets
+        out["rot"].copy_(torch.eye(3, device=dev).expand(n, 3, 3))
+        for k in ("trans", "rmsd", "sites", "gdt_counts", "tm"):
+            out[k].zero_()
+    torch.cuda.current_stream(dev).synchronize()
+    if solve:
+        s = CSuperposeOut(*(out[k].data_ptr() for k in ("rot", "trans", "rmsd", "sites", "gdt_counts", "tm", "dev")))
+        fn, name = (c.lib.fcz_superpose_packed_dev, "fcz_superpose_packed_dev") if is_packed else (c.lib.fcz_superpose_dev, "fcz_superpose_dev")
+        _lib.check(fn(c.ctx, pos.data_ptr(), mask.data_ptr(), ppos.data_ptr(), None if pmask is None else pmask.data_ptr(),
+                      None if bound is None else bound.data_ptr(), n, rows, lay, slot, ctypes.byref(s)), name)
+    if apply:
+        _apply_transform(c, ppos, pmask, out["rot"], out["trans"], n, rows, bound, is_packed, lay, out["pos_aligned"])
+    c.synchronize()
+    counts, S = out["gdt_counts"].to(torch.float64), out["sites"].to(torch.float64).clamp(min=1.0)
+    out["gdt_ts"] = (counts[:, 1:5].sum(dim=1) / (4.0 * S)).to(torch.float32)
+    out["gdt_ha"] = (counts[:, 0:4].sum(dim=1) / (4.0 * S)).to(torch.float32)
+    return out
+
+
+def apply_transform(pos, rot, trans, batch=None, *, mask=None, length=None, cu_seqlens=None, codec: Optional[Codec] = None):
+    """dense coordinates on the GPU moved by one rigid transform per chain -> pos_out of the shape of pos: rot[e] @ x + trans[e] for
+    every slot whose mask is set (mask=None: every slot) in the rows of chain e, 0 elsewhere. The apply step of superpose alone, for
+    transforms that came from elsewhere.
+
+    pos [n, L, A, 3] float32, or the packed [R, A, 3] beside cu_seqlens [n + 1]; rot [n, 3, 3], trans [n, 3] float32. The chains come
+    from `batch`, a dict as decode_tensors returns (its length, ignored beside crop_start, or its cu_seqlens; its mask is NOT used:
+    it says which atoms the target has, not which were predicted), or from the keywords length / cu_seqlens. pos may also be a dict
+    with `pos` and optionally `mask`. The arithmetic is float32 in a fixed order, x' = ((r00 x + r01 y) + r02 z) + tx with every
+    operation rounded (include/fcz_hip.h, fcz_superpose_apply_dev), so numpy reproduces it bit for bit."""
+    if isinstance(pos, dict):
+        mask = pos.get("mask") if mask is None else mask
+        pos = pos.get("pos")
+    d = {k: batch[k] for k in ("length", "cu_seqlens", "crop_start") if batch is not None and batch.get(k) is not None}
+    if length is not None:
+        d["length"] = length
+    if cu_seqlens is not None:
+        d["cu_seqlens"] = cu_seqlens
+    if pos is None:
+        raise TypeError("apply_transform needs the tensor 'pos'")
+    shape = tuple(getattr(pos, "shape", ()))
+    is_packed = d.get("cu_seqlens") is not None and len(shape) == 3
+    if len(shape) != (3 if is_packed else 4) or shape[-1] != 3 or shape[-2] not in _WIDTH_LAYOUT:
+        raise ValueError(f"pos must be float32 [n, L, A, 3], or [R, A, 3] beside cu_seqlens, with A = 37, 14 or 4, not {shape}")
+    n = (int(getattr(d["cu_seqlens"], "shape", (1,))[0]) - 1) if is_packed else shape[0]
+    for key, v, want in (("rot", rot, (n, 3, 3)), ("trans", trans, (n, 3))):
+        if tuple(getattr(v, "shape", ())) != want:
+            raise ValueError(f"{key} must be float32 {want}, one transform per chain, not {tuple(getattr(v, 'shape', ()))}")
+    if mask is not None and tuple(getattr(mask, "shape", ())) != shape[:-1]:
+        raise ValueError(f"mask must have the shape {shape[:-1]}, not {tuple(getattr(mask, 'shape', ()))}")
+    c = codec or api.default_codec()
+    try:
+        import torch
+    except ImportError as e:
+        raise api.error(f"apply_transform needs PyTorch (ROCm build): {e}") from None
+    if not isinstance(pos, torch.Tensor):
+        raise api.error("apply_transform takes torch tensors on the GPU (numpy arrays: Codec.apply_transform)")
+    if pos.device.type != "cuda" or pos.device.index != int(c.device):
+        raise api.error(f"apply_transform: pos lies on {pos.device}, the codec works on cuda:{int(c.device)}; there is no CPU path")
+    dev = pos.device
+    lay = dense_layout(_WIDTH_LAYOUT[shape[-2]])
+    _on_device(torch, "apply_transform", dev, "pos", pos, shape, (torch.float32,))
+    _on_device(torch, "apply_transform", dev, "rot", rot, (n, 3, 3), (torch.float32,))
+    _on_device(torch, "apply_transform", dev, "trans", trans, (n, 3), (torch.float32,))
+    if mask is not None:
+        mask = _on_device(torch, "apply_transform", dev, "mask", mask, shape[:-1], (torch.bool, torch.uint8)).view(torch.uint8)
+    n, rows, bound = _chain_bound(torch, "apply_transform", dev, d, shape, is_packed)
+    if rows > 2 ** 31 - 1:
+        raise ValueError("at most 2^31 - 1 rows per chain")
+    out = torch.empty_like(pos)
+    torch.cuda.current_stream(dev).synchronize()
+    _apply_transform(c, pos, mask, rot, trans, n, rows, bound, is_packed, lay, out)
+    c.synchronize()
+    return out
 
 
 def _frames_alloc(torch, dev, rows, fgroups):

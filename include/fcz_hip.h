@@ -19,6 +19,8 @@
  *                                                          fcz_dense_window_dev / fcz_decompress_dense_window
  *   (none: no neighbour graph of the decoded chain)        fcz_knn_dev / fcz_knn_packed_dev, fcz_knn / fcz_knn_packed
  *   (none: no score of one structure against another)      fcz_lddt_dev / fcz_lddt_packed_dev, fcz_lddt / fcz_lddt_packed
+ *   (none: `rmsd` compares two files unsuperposed)         fcz_superpose_dev / fcz_superpose_packed_dev, fcz_superpose_apply_dev /
+ *                                                          fcz_superpose_apply_packed_dev and their host forms
  *   (none: no rigid frames of the decoded chain)           fcz_frames_dev / fcz_frames
  *   Foldcomp::decompress, the dequantisation :784-804     fcz_angles_dev / fcz_angles_packed_dev, fcz_decompress_angles[_packed],
  *                                                          fcz_angles_window_dev / fcz_decompress_angles_window
@@ -439,6 +441,84 @@ int fcz_lddt_packed(fcz_ctx* ctx, const float* pos_true, const uint8_t* mask_tru
                     const uint32_t* row_off, uint32_t n, uint32_t R, int layout, int slot, float cutoff, const float* thresholds,
                     float* score, int32_t* pairs, int32_t* hits);
 
+/* ---- least-squares (Kabsch) superposition of two dense tensor batches ------------------------------------ */
+/* The superposition-based half of what a validation loop logs, per chain, for a whole batch on the device: the rigid motion that
+ * lays the prediction onto the target, the RMSD after it, the GDT counts, a TM-score at that superposition, every site's
+ * deviation, and (fcz_superpose_apply_dev) the prediction moved onto the target. The reference has no such output (its `rmsd` is
+ * the unsuperposed sum over two files): like fcz_lddt_dev these stand beside Foldcomp::decompress (src/foldcomp.cpp:779). The inputs
+ * are fcz_lddt_dev's: two tensors of ONE shape and layout, pos_true / mask_true and pos_pred / mask_pred (mask_pred may be NULL:
+ * every slot present), padded with length [n] (may be NULL) or packed with row_off [n + 1], a layout and a slot. A row is a SITE by
+ * exactly fcz_lddt_dev's rule (inside its chain, both masks set at the slot, six finite coordinates); nothing else is read as data.
+ * For chain e with S sites a_i (pred) and b_i (true), all in float64, every operation rounded, no FMA:
+ *   centroids   ca, cb = the sums over the sites divided by S (the centroid first, the centring second)
+ *   M           sum (a_i - ca)(b_i - cb)^T, centred
+ *   R           the proper rotation (det = +1) that minimises sum |R (a_i - ca) - (b_i - cb)|^2: the unit eigenvector of the largest
+ *               eigenvalue of Horn's symmetric 4 x 4 quaternion matrix of M (Horn 1987), found by cyclic Jacobi sweeps from the
+ *               identity; of equal largest eigenvalues the first. A quaternion always gives a proper rotation: there is no
+ *               determinant fix-up. t = cb - R ca.
+ *   dev_i       |R a_i + t - b_i|, with x' = ((r00 x + r01 y) + r02 z) + tx and d2 = (dx dx + dy dy) + dz dz, from the float64 R, t
+ * Per chain, float32 unless stated, each value rounded once from float64:
+ *   rot [n][3][3], trans [n][3]   R and t: x_true ~ rot @ x_pred + trans, the convention of fcz_frames_dev
+ *   rmsd [n]                      sqrt(sum dev^2 / S)
+ *   sites [n] int32               S
+ *   gdt_counts [n][5] int32       the sites with dev <= 0.5, 1, 2, 4, 8 (compared in float64). GDT-TS is the mean of the fractions
+ *                                 at 1, 2, 4, 8 and GDT-HA of those at 0.5, 1, 2, 4: integers over S, left to the caller
+ *   tm [n]                        (1 / S) sum 1 / (1 + (dev_i / d0)^2), d0 = max(1.24 cbrt(S - 15) - 1.8, 0.5) for S > 15, else 0.5:
+ *                                 the TM-score AT THE LEAST-SQUARES SUPERPOSITION, normalised by the sites. It is a lower bound of
+ *                                 what TM-score programs report, which maximise the sum over superpositions.
+ * Per row: dev [rows] float32, dev_i rounded once; 0 where the row is no site, lies behind length, or (packed) is covered by no chain.
+ * rows = n * L (padded) or R (packed). Degenerate chains fall out of the solver: S = 0 gives the identity, trans 0 and every score 0;
+ * S = 1 the identity rotation (Horn's matrix is zero and Jacobi leaves the identity), trans = b - a and rmsd 0; two sites or
+ * collinear sites give A minimiser (it is not unique; rot is still a proper rotation and rmsd / dev are well defined).
+ * Reproducibility: a sum over the sites has a fixed order -- lane l of the chain's 64-lane wavefront adds its rows l, l + 64, .. in
+ * ascending order, then an xor-butterfly over the lanes (distances 32, 16, .. 1) -- so the result depends on neither the launch
+ * geometry nor the form: two runs give the same bits, and padded against packed gives the same bits. Against another float64
+ * implementation it agrees to rounding, not on bits. It is NOT differentiable.
+ * All of rmsd, sites, gdt_counts, tm and dev may be NULL (not wanted); rot and trans are required. Every byte of the outputs given
+ * is written whatever the inputs hold, nothing outside them is written, and nothing outside the inputs is read, whatever row_off
+ * holds (ranges that overlap are each computed; which of them a shared row's dev belongs to is then unspecified). Every index that
+ * scales with rows * A is 64-bit. Enqueued on the ctx stream, no synchronisation, no scratch. FCZ_E_INVALID_ARG with nothing
+ * launched: NULL ctx / pos_true / mask_true / pos_pred / out / out->rot / out->trans, NULL row_off with n > 0, unknown layout, slot
+ * outside the layout's width, L == 0, L (padded) or R (packed) above 2^31 - 1 (sites is int32). n == 0: FCZ_OK (packed, n == 0 < R:
+ * every row is uncovered and dev is filled). The time goes to a group of its own, "superpose", for all the calls of this block. */
+typedef struct fcz_superpose_out {
+    float*   rot;           /* [n][3][3] */
+    float*   trans;         /* [n][3] */
+    float*   rmsd;          /* [n] optional */
+    int32_t* sites;         /* [n] optional */
+    int32_t* gdt_counts;    /* [n][5] optional */
+    float*   tm;            /* [n] optional */
+    float*   dev;           /* [n][L] / [R] optional */
+} fcz_superpose_out;
+int fcz_superpose_dev(fcz_ctx* ctx, const float* pos_true_dev, const uint8_t* mask_true_dev, const float* pos_pred_dev,
+                      const uint8_t* mask_pred_dev, const uint32_t* length_dev, uint32_t n, uint32_t L, int layout, int slot,
+                      const fcz_superpose_out* out_dev);
+int fcz_superpose_packed_dev(fcz_ctx* ctx, const float* pos_true_dev, const uint8_t* mask_true_dev, const float* pos_pred_dev,
+                             const uint8_t* mask_pred_dev, const uint32_t* row_off_dev, uint32_t n, uint32_t R, int layout, int slot,
+                             const fcz_superpose_out* out_dev);
+/* The transform applied to the WHOLE prediction: pos_out[row][a] = rot_e @ pos[row][a] + trans_e for every slot a whose mask is set
+ * (mask NULL: every slot) in rows inside chain e, and 0 elsewhere (cleared slots, rows behind length, packed rows no chain covers):
+ * every byte of pos_out, of the shape of pos, is written. It is computed in float32 from the float32 rot / trans in a stated order,
+ * every operation rounded, no FMA: x' = ((r00 x + r01 y) + r02 z) + tx, and y', z' alike from rows 1 and 2, so a caller reproduces
+ * it bit for bit from the transform. rot [n][3][3] and trans [n][3] may be any transforms, not only ones fcz_superpose_dev wrote.
+ * pos and pos_out need no alignment beyond float's and must not overlap. Refusals and the n == 0 rule are those above (there is no
+ * slot). Enqueued on the ctx stream (the packed form shares fcz_knn_packed_dev's scratch in the ctx). */
+int fcz_superpose_apply_dev(fcz_ctx* ctx, const float* pos_dev, const uint8_t* mask_dev, const uint32_t* length_dev, uint32_t n,
+                            uint32_t L, int layout, const float* rot_dev, const float* trans_dev, float* pos_out_dev);
+int fcz_superpose_apply_packed_dev(fcz_ctx* ctx, const float* pos_dev, const uint8_t* mask_dev, const uint32_t* row_off_dev,
+                                   uint32_t n, uint32_t R, int layout, const float* rot_dev, const float* trans_dev,
+                                   float* pos_out_dev);
+/* Host-pointer conveniences: the same arrays on the host, staged through the ctx like fcz_lddt; synchronous. */
+int fcz_superpose(fcz_ctx* ctx, const float* pos_true, const uint8_t* mask_true, const float* pos_pred, const uint8_t* mask_pred,
+                  const uint32_t* length, uint32_t n, uint32_t L, int layout, int slot, const fcz_superpose_out* out);
+int fcz_superpose_packed(fcz_ctx* ctx, const float* pos_true, const uint8_t* mask_true, const float* pos_pred,
+                         const uint8_t* mask_pred, const uint32_t* row_off, uint32_t n, uint32_t R, int layout, int slot,
+                         const fcz_superpose_out* out);
+int fcz_superpose_apply(fcz_ctx* ctx, const float* pos, const uint8_t* mask, const uint32_t* length, uint32_t n, uint32_t L,
+                        int layout, const float* rot, const float* trans, float* pos_out);
+int fcz_superpose_apply_packed(fcz_ctx* ctx, const float* pos, const uint8_t* mask, const uint32_t* row_off, uint32_t n, uint32_t R,
+                               int layout, const float* rot, const float* trans, float* pos_out);
+
 /* ---- torsion-angle tensors: the record's internal coordinates, no reconstruction ------------------------ */
 /* What Foldcomp::decompress dequantises before it places an atom (src/foldcomp.cpp:784-804: the backbone torsions and bond angles of
  * every packed word; :338-369 for the side-chain torsion bytes) and the FCZ branch of foldcomp.cxx's get_data returns as Python lists
@@ -794,7 +874,7 @@ int fcz_check(const uint8_t* entry, uint64_t len);
  * group since the last reset: "compress_sizes", "compress_index", "compress_angles", "compress_pack",
  * "decompress_sizes", "decompress_backbone", "decompress_index", "decompress_sidechain", "pdb_sizes", "pdb_format", "extract_sizes", "extract",
  * "ingest_parse", "ingest_parse_cif", "ingest_rows_cif", "ingest_frags", "ingest_fill", "inflate", "dense", "undense" (the counting and the fill
- * kernel of fcz_undense_dev: two launches per call), "angles" (fcz_angles_dev), "knn" (fcz_knn_dev and fcz_knn_packed_dev), "lddt" (fcz_lddt_dev and fcz_lddt_packed_dev), "frames" (fcz_frames_dev). Every other packed or windowed entry point is timed under the
+ * kernel of fcz_undense_dev: two launches per call), "angles" (fcz_angles_dev), "knn" (fcz_knn_dev and fcz_knn_packed_dev), "lddt" (fcz_lddt_dev and fcz_lddt_packed_dev), "superpose" (fcz_superpose_dev, fcz_superpose_apply_dev and their packed forms), "frames" (fcz_frames_dev). Every other packed or windowed entry point is timed under the
  * group of its padded form: fcz_dense_packed_dev and fcz_dense_window_dev under "dense", fcz_undense_packed_dev under "undense",
  * fcz_angles_packed_dev and fcz_angles_window_dev under "angles". */
 int  fcz_ctx_enable_timing(fcz_ctx* ctx, int enable);

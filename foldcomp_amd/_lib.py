@@ -90,6 +90,13 @@ def load():
         "fcz_lddt_packed_dev": (i32, [vp, vp, vp, vp, vp, vp, u32, u32, i32, i32, f32, vp, vp, vp, vp]),
         "fcz_lddt": (i32, [vp, vp, vp, vp, vp, vp, u32, u32, i32, i32, f32, vp, vp, vp, vp]),
         "fcz_lddt_packed": (i32, [vp, vp, vp, vp, vp, vp, u32, u32, i32, i32, f32, vp, vp, vp, vp]),
+        "fcz_hbond_pass": (i32, []),
+        "fcz_hbond_dev": (i32, [vp, vp, vp, vp, vp, u32, u32, i32, vp, vp, vp, vp]),
+        "fcz_hbond_packed_dev": (i32, [vp, vp, vp, vp, vp, u32, u32, i32, vp, vp, vp, vp]),
+        "fcz_dssp_labels_dev": (i32, [vp, vp, vp, vp, vp, u32, u32, i32, vp, vp, vp, vp]),
+        "fcz_dssp_labels_packed_dev": (i32, [vp, vp, vp, vp, vp, u32, u32, i32, vp, vp, vp, vp]),
+        "fcz_dssp": (i32, [vp, vp, vp, vp, vp, u32, u32, i32, vp, vp, vp, vp, vp, vp]),
+        "fcz_dssp_packed": (i32, [vp, vp, vp, vp, vp, u32, u32, i32, vp, vp, vp, vp, vp, vp]),
         "fcz_superpose_dev": (i32, [vp, vp, vp, vp, vp, vp, u32, u32, i32, i32, ctypes.POINTER(CSuperposeOut)]),
         "fcz_superpose_packed_dev": (i32, [vp, vp, vp, vp, vp, vp, u32, u32, i32, i32, ctypes.POINTER(CSuperposeOut)]),
         "fcz_superpose": (i32, [vp, vp, vp, vp, vp, vp, u32, u32, i32, i32, ctypes.POINTER(CSuperposeOut)]),
@@ -161,6 +168,7 @@ EXPORTS = ["fcz_ctx_create", "fcz_ctx_destroy", "fcz_ctx_stream", "fcz_ctx_synch
            "fcz_dense_window_dev", "fcz_decompress_dense_window", "fcz_angles_window_dev", "fcz_decompress_angles_window",
            "fcz_knn_pass", "fcz_knn_dev", "fcz_knn_packed_dev", "fcz_knn", "fcz_knn_packed",
            "fcz_lddt_pass", "fcz_lddt_c2", "fcz_lddt_dev", "fcz_lddt_packed_dev", "fcz_lddt", "fcz_lddt_packed",
+           "fcz_hbond_pass", "fcz_hbond_dev", "fcz_hbond_packed_dev", "fcz_dssp_labels_dev", "fcz_dssp_labels_packed_dev", "fcz_dssp", "fcz_dssp_packed",
            "fcz_superpose_dev", "fcz_superpose_packed_dev", "fcz_superpose", "fcz_superpose_packed",
            "fcz_superpose_apply_dev", "fcz_superpose_apply_packed_dev", "fcz_superpose_apply", "fcz_superpose_apply_packed",
            "fcz_frames_width", "fcz_frame_atom", "fcz_frame_ambiguous", "fcz_frames_dev", "fcz_frames",

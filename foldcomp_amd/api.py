@@ -243,7 +243,8 @@ class FoldcompDatabase:
     def tensor_batches(self, batch_size: int = 1024, *, layout="atom37", max_len: Optional[int] = None, device="cuda:0",
                        sort_by_length: bool = False, packed: bool = False, max_residues: Optional[int] = None,
                        angles: bool = False, crop: Optional[str] = None, seed: Optional[int] = None,
-                       neighbors: Optional[int] = None, neighbor_atom="CA", frames: Optional[str] = None):
+                       neighbors: Optional[int] = None, neighbor_atom="CA", frames: Optional[str] = None,
+                       secondary_structure: bool = False):
         """Generator over the database (its `ids` selection when it has one) in batches of dense model-input tensors on the GPU:
         the dicts of foldcomp_amd.tensors.decode_tensors, each with `names` (the records' titles) and `index` (int64 array: the
         entries' positions in this database, what db[i] takes). sort_by_length orders every window of 16 * batch_size entries by
@@ -257,8 +258,10 @@ class FoldcompDatabase:
         neighbors=k adds the k-nearest-neighbour graph of every chain, `nbr_index` / `nbr_dist`, on the sites of `neighbor_atom`
         (decode_tensors(neighbors=k)); like the other argument rules, a bad k or atom raises at the first next(), before a record
         is read. frames="backbone" | "all" adds the rigid frames `rot` / `trans` / `frame_mask` (decode_tensors(frames=...)), checked
-        at the first next() too."""
+        at the first next() too. secondary_structure=True adds the DSSP labels `ss` / `ss_mask` of every chain
+        (decode_tensors(secondary_structure=True))."""
         from .tensors import decode_tensors
+        check_secondary_structure_flag(secondary_structure)
         if frames is not None:
             check_frames(frames)
         if neighbors is not None:
@@ -282,14 +285,15 @@ class FoldcompDatabase:
                 sel = np.asarray(sel, np.int64)
                 if packed:
                     d = decode_tensors([ents[k] for k in sel], layout=layout, device=device, packed=True, angles=angles,
-                                       neighbors=neighbors, neighbor_atom=neighbor_atom, frames=frames)
+                                       neighbors=neighbors, neighbor_atom=neighbor_atom, frames=frames, secondary_structure=secondary_structure)
                 else:
                     if crop == "random" and gen is None:
                         import torch
                         gen = torch.Generator(device=device)
                         gen.manual_seed(int(seed)) if seed is not None else gen.seed()
                     d = decode_tensors([ents[k] for k in sel], layout=layout, max_len=max_len, device=device, angles=angles, crop=crop,
-                                       generator=gen, neighbors=neighbors, neighbor_atom=neighbor_atom, frames=frames)
+                                       generator=gen, neighbors=neighbors, neighbor_atom=neighbor_atom, frames=frames,
+                                       secondary_structure=secondary_structure)
                 d["index"] = idx[sel]
                 yield d
 
@@ -397,6 +401,48 @@ def check_superpose(atom, shape, pred_shape, pred_mask_shape=None):
     if pred_mask_shape is not None and tuple(pred_mask_shape) != shape[:-1]:
         raise ValueError(f"pred mask must have the shape of true mask, {shape[:-1]}, not {tuple(pred_mask_shape)}")
     return slot
+
+
+# the labels of `ss`, in the order of their codes (include/fcz_hip.h, fcz_dssp_labels_dev), and the usual reduction to three states
+# (helix 0: H, G, I; strand 1: E, B; coil 2: the rest) as a table to index with `ss`
+SS_CLASSES = ("-", "H", "B", "E", "G", "I", "T", "S")
+SS3_OF_SS8 = np.array([2, 0, 1, 1, 0, 0, 2, 2], np.uint8)
+HBOND_TABLES = (("hbond_acc_index", "int32"), ("hbond_acc_energy", "float32"), ("hbond_don_index", "int32"), ("hbond_don_energy", "float32"))
+
+
+def check_secondary_structure_flag(flag):
+    """secondary_structure= of decode_tensors / tensor_batches is a switch"""
+    if not isinstance(flag, (bool, np.bool_)):
+        raise ValueError(f"secondary_structure must be True or False, not {flag!r}")
+
+
+def check_dssp(what, d, hbonds=None):
+    """the argument rules of backbone_hbonds / secondary_structure that need no torch and no GPU, on the dict `d` of tensors or
+    arrays (anything with a shape) -> (shape of pos, packed): pos [n, L, A, 3], or [R, A, 3] beside cu_seqlens, with A = 37, 14 or
+    4; mask of pos's shape without its last axis; aatype, when given, without its last two; hbonds, when given, a dict of the two
+    acceptor tables [.., 2]"""
+    for key in ("pos", "mask"):
+        if d.get(key) is None:
+            raise TypeError(f"{what} needs the tensor {key!r}")
+    shape = tuple(getattr(d["pos"], "shape", ()))
+    packed = d.get("cu_seqlens") is not None and len(shape) == 3
+    if len(shape) != (3 if packed else 4) or shape[-1] != 3 or shape[-2] not in (37, 14, 4):
+        raise ValueError(f"pos must be float32 [n, L, A, 3], or [R, A, 3] beside cu_seqlens, with A = 37, 14 or 4, not {shape}")
+    if tuple(getattr(d["mask"], "shape", ())) != shape[:-1]:
+        raise ValueError(f"mask must have the shape {shape[:-1]}, not {tuple(getattr(d['mask'], 'shape', ()))}")
+    if d.get("aatype") is not None and tuple(getattr(d["aatype"], "shape", ())) != shape[:-2]:
+        raise ValueError(f"aatype must have the shape {shape[:-2]}, not {tuple(getattr(d['aatype'], 'shape', ()))}")
+    if max(shape[:-2], default=0) > 2 ** 31 - 1:
+        raise ValueError("the H-bond tables hold rows as int32: at most 2^31 - 1 rows")
+    if hbonds is not None:
+        if not isinstance(hbonds, dict):
+            raise TypeError(f"hbonds must be a dict of the tables backbone_hbonds returns, not {type(hbonds).__name__}")
+        for key in ("hbond_acc_index", "hbond_acc_energy"):
+            if hbonds.get(key) is None:
+                raise TypeError(f"hbonds needs the table {key!r}")
+            if tuple(getattr(hbonds[key], "shape", ())) != shape[:-2] + (2,):
+                raise ValueError(f"{key} must have the shape {shape[:-2] + (2,)}, not {tuple(getattr(hbonds[key], 'shape', ()))}")
+    return shape, packed
 
 
 # the rigid groups of groups="all", indexed like AlphaFold / OpenFold rigidgroups_gt_frames (include/fcz_hip.h, fcz_frames_dev)

@@ -292,6 +292,38 @@ class Codec:
                           score.ctypes.data, pairs.ctypes.data, hits.ctypes.data), "fcz_lddt_packed" if packed else "fcz_lddt")
         return dict(score=score, pairs=pairs, hits=hits)
 
+    def secondary_structure(self, pos: np.ndarray, mask: np.ndarray, aatype=None, length=None, row_off=None):
+        """dense arrays on the host -> the DSSP labels and backbone hydrogen bonds of every chain (fcz_dssp, or fcz_dssp_packed when
+        row_off is given): ss uint8 [n, L] / [R] (codes in the order of foldcomp.SS_CLASSES), ss_mask bool, and the tables
+        hbond_acc_index / hbond_don_index int32 [.., 2] (-1 = none) with hbond_acc_energy / hbond_don_energy float32. pos float32
+        [n, L, A, 3] with mask [n, L, A], optionally aatype [n, L] uint8 (proline has no amide hydrogen) and length [n]; or pos
+        [R, A, 3], mask [R, A], aatype [R], row_off [n + 1]. Reproducible bit for bit, not differentiable."""
+        pos = np.ascontiguousarray(pos, np.float32)
+        packed = row_off is not None
+        if pos.ndim != (3 if packed else 4) or pos.shape[-1] != 3 or pos.shape[-2] not in (37, 14, 4):
+            raise ValueError(f"pos must be float32 {'[R, A, 3]' if packed else '[n, L, A, 3]'} with A = 37, 14 or 4, not {pos.shape}")
+        lay = {37: 0, 14: 1, 4: 2}[pos.shape[-2]]
+        mask = np.ascontiguousarray(mask)
+        if mask.shape != pos.shape[:-1] or mask.dtype not in (np.bool_, np.uint8):
+            raise ValueError(f"mask must be bool / uint8 {pos.shape[:-1]}, not {mask.dtype} {mask.shape}")
+        lead = pos.shape[:-2]
+        if aatype is not None:
+            aatype = np.ascontiguousarray(aatype)
+            if aatype.shape != lead or aatype.dtype != np.uint8:
+                raise ValueError(f"aatype must be uint8 {lead}, not {aatype.dtype} {aatype.shape}")
+        n, rows, bound = self._chain_rows(pos, packed, length, row_off)
+        out = dict(ss=np.zeros(lead, np.uint8), ss_mask=np.zeros(lead, np.uint8),
+                   hbond_acc_index=np.full(lead + (2,), -1, np.int32), hbond_acc_energy=np.zeros(lead + (2,), np.float32),
+                   hbond_don_index=np.full(lead + (2,), -1, np.int32), hbond_don_energy=np.zeros(lead + (2,), np.float32))
+        if out["ss"].size:
+            fn = self.lib.fcz_dssp_packed if packed else self.lib.fcz_dssp
+            _lib.check(fn(self.ctx, pos.ctypes.data, mask.ctypes.data, None if aatype is None else aatype.ctypes.data,
+                          None if bound is None else bound.ctypes.data, n, rows, lay, out["hbond_acc_index"].ctypes.data,
+                          out["hbond_acc_energy"].ctypes.data, out["hbond_don_index"].ctypes.data, out["hbond_don_energy"].ctypes.data,
+                          out["ss"].ctypes.data, out["ss_mask"].ctypes.data), "fcz_dssp_packed" if packed else "fcz_dssp")
+        out["ss_mask"] = out["ss_mask"].view(np.bool_)
+        return out
+
     @staticmethod
     def _chain_rows(pos, packed, length, row_off):
         """the chains of dense host arrays -> (n, rows, bound): row_off [n + 1] over the R rows, or length [n] / None over L"""

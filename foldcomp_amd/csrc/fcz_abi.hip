@@ -35,6 +35,7 @@
 #include "fcz_undense.h"
 #include "fcz_knn.h"
 #include "fcz_lddt.h"
+#include "fcz_dssp.h"
 #include "fcz_superpose.h"
 #include "fcz_frames.h"
 #include "fcz_angles.h"
@@ -90,10 +91,11 @@ struct timed_span { std::string name; hipEvent_t a, b; };
 // fcz_dense_out, the 7 of a fcz_packed_out (PACKED_OUT .. PACKED_OUT_LAST), in the struct's order; ANGLES_OUT: the angles, their mask and
 // (windowed form) aatype; WINDOW_START: the n u32 starts of a windowed host call; KEPT_*: the records a *_begin call leaves for its fetch
 // (C + 1 u64 offsets, the bytes, C i32 status); LDDT_PRED: pos and mask of the second tensor batch of fcz_lddt, LDDT_OUT: score, pairs, hits;
+// DSSP_OUT: acc_index, acc_energy, don_index, don_energy, ss, ss_mask of fcz_dssp;
 // SUPERPOSE_OUT: the seven arrays of a fcz_superpose_out in the struct's order; APPLY_ROT, APPLY_TRANS, APPLY_OUT: the transforms and the moved
 // coordinates of fcz_superpose_apply (its pos and mask go through LDDT_PRED)
 enum { REC_BLOB, REC_OFF, REC_RES_OFF, REC_ATOM_OFF, REC_X, REC_Y, REC_Z, REC_BFAC, REC_RES_CODE, REC_ATOM_CODE,
-       FILES_TEXT = 0, FILES_OFF, FILES_NAMES, FILES_NAME_OFF, FILES_STEM_LEN, BATCH_IN = 0, DENSE_IN = 0, LDDT_PRED = 4, DENSE_OUT = 10, LDDT_OUT = 10, SUPERPOSE_OUT = 10,
+       FILES_TEXT = 0, FILES_OFF, FILES_NAMES, FILES_NAME_OFF, FILES_STEM_LEN, BATCH_IN = 0, DENSE_IN = 0, LDDT_PRED = 4, DENSE_OUT = 10, LDDT_OUT = 10, SUPERPOSE_OUT = 10, DSSP_OUT = 10,
        APPLY_ROT = 10, APPLY_TRANS, APPLY_OUT,
        PACKED_OUT = 10, ANGLES_OUT = 10, KEPT_OFF = 13, KEPT_BYTES, KEPT_STATUS, PACKED_OUT_LAST, WINDOW_START = PACKED_OUT_LAST, POOL_COUNT };
 
@@ -145,6 +147,7 @@ struct fcz_ctx {
     dev_buf sizes_res_off;   // decompress: the res_off of a batch call that has to run its own sizes pass (ensure_sizes)
     dev_buf selftest_out;    // fcz_selftest_math
     dev_buf knn_tiles;       // fcz_knn_packed_dev, fcz_lddt_packed_dev, fcz_superpose_apply_packed_dev (chain_tile_scan): n u64 tile counts, then their n + 1 offsets
+    dev_buf dssp_flags;      // fcz_dssp_labels_dev / _packed_dev: a byte per row (k_dssp_flags -> k_dssp_labels)
     dev_buf fast_scratch;    // decompress, FCZ_NUMERICS_FAST: forward atoms of segments longer than one chunk
     // Staging of the host-pointer entry points. Every entry point that writes it calls claim_staging first. Nothing outlives the call
     // that wrote it but KEPT_*, which a begin leaves for its fetch: any later call that writes 13 .. 15 ends that.
@@ -168,6 +171,7 @@ struct fcz_ctx {
     //   fcz_lddt / fcz_lddt_packed                  DENSE_IN 0, 1, 3 (pos_true, mask_true, length / row_off), LDDT_PRED 4 .. 5 (pos_pred, mask_pred), LDDT_OUT 10 .. 12
     //   fcz_superpose / fcz_superpose_packed        DENSE_IN 0, 1, 3 and LDDT_PRED 4 .. 5 as fcz_lddt, SUPERPOSE_OUT 10 .. 16
     //   fcz_superpose_apply[_packed]                LDDT_PRED 4 .. 5 (pos, mask), DENSE_IN 3 (length / row_off), APPLY_ROT 10, APPLY_TRANS 11, APPLY_OUT 12
+    //   fcz_dssp / fcz_dssp_packed                  DENSE_IN 0 .. 3 (pos, mask, aatype, length / row_off), DSSP_OUT 10 .. 15 (the four tables, ss, ss_mask)
     //   fcz_frames                                  DENSE_IN 0 .. 3 (pos, mask, aatype, length), DENSE_OUT 10 .. 12 (rot, trans, frame_mask)
     dev_buf pool[POOL_COUNT];
     // PDB text / extracted data: per-entry sizes (any call), offsets (n + 1 u64) and the text of the last fcz_decompress_pdb_begin,
@@ -1866,6 +1870,151 @@ int fcz_lddt_packed(fcz_ctx* ctx, const float* pos_true, const uint8_t* mask_tru
     if (!lddt_args_ok(ctx, pos_true, mask_true, pos_pred, layout, slot, cutoff, thresholds, R, score, pairs, hits) || (n && !row_off))
         return FCZ_E_INVALID_ARG;
     return lddt_host(ctx, pos_true, mask_true, pos_pred, mask_pred, row_off, true, n, R, layout, slot, cutoff, thresholds, score, pairs, hits);
+}
+
+// ------------------------------------------------------------------------------------------------
+// backbone hydrogen bonds and DSSP secondary structure of dense tensors (fcz_dssp.h; no counterpart in the reference)
+// ------------------------------------------------------------------------------------------------
+int fcz_hbond_pass(void) { return (int)HBOND_PASS; }
+
+// rows: L (padded) or R (packed); out: every output pointer of the call
+static bool dssp_args_ok(const fcz_ctx* ctx, const float* pos, const uint8_t* mask, int layout, uint32_t rows, std::initializer_list<const void*> out) {
+    if (!ctx || !pos || !mask || fcz_dense_width(layout) <= 0 || rows > DSSP_MAX_ROWS) return false;
+    for (const void* p : out) if (!p) return false;
+    return true;
+}
+
+static dssp_args dssp_pack(const float* pos, const uint8_t* mask, const uint8_t* aatype, const uint32_t* bound, uint32_t n, uint32_t rows, int layout) {
+    dssp_args g{};
+    g.pos = pos; g.mask = mask; g.aatype = aatype; g.bound = bound; g.n = n; g.L = rows;
+    g.A = (uint32_t)fcz_dense_width(layout); g.o_slot = layout == FCZ_DENSE_ATOM37 ? 4u : 3u;
+    return g;
+}
+
+// fcz_hbond_dev (bound_dev is length [n] or NULL, rows = L) and fcz_hbond_packed_dev (bound_dev = row_off [n + 1], rows = R)
+static int hbond_rows(fcz_ctx* ctx, const float* pos_dev, const uint8_t* mask_dev, const uint8_t* aatype_dev, const uint32_t* bound_dev, bool packed, uint32_t n,
+                      uint32_t rows, int layout, int32_t* acc_index_dev, float* acc_energy_dev, int32_t* don_index_dev, float* don_energy_dev) {
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (rows == 0 || (n == 0 && !packed)) return FCZ_OK;
+    dssp_args g = dssp_pack(pos_dev, mask_dev, aatype_dev, bound_dev, n, rows, layout);
+    g.acc_index = acc_index_dev; g.acc_energy = acc_energy_dev; g.don_index = don_index_dev; g.don_energy = don_energy_dev;
+    const uint32_t max_blocks = (uint32_t)ctx->n_cu * 16u;
+    chain_tiles ct;
+    if (!packed || n) { int rc = ct.reserve(ctx, packed, n, rows); if (rc) return rc; }
+    span_guard sg(ctx, "dssp");
+    if (packed) {
+        hipLaunchKernelGGL(k_dssp_fill, dim3((uint32_t)std::min<uint64_t>(((uint64_t)rows + BLOCK - 1) / BLOCK, max_blocks)), dim3(BLOCK), 0, ctx->stream, g, 1);
+        if (n == 0) { HIP_TRY(hipGetLastError()); return FCZ_OK; }
+        int rc = ct.scan(ctx, bound_dev, n, rows); if (rc) return rc;
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_hbond<true>), dim3((uint32_t)ct.blocks), dim3(BLOCK), 0, ctx->stream, g, ct.tile_off, 0u, (uint64_t)0);
+    } else {
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_hbond<false>), dim3((uint32_t)ct.blocks), dim3(BLOCK), 0, ctx->stream, g, (const uint64_t*)nullptr, ct.tiles_per_entry,
+                           ct.n_padded);
+    }
+    HIP_TRY(hipGetLastError());
+    return FCZ_OK;
+}
+
+// fcz_dssp_labels_dev and fcz_dssp_labels_packed_dev: the flags of every row into ctx->dssp_flags, then the labels from them and the table
+static int dssp_label_rows(fcz_ctx* ctx, const float* pos_dev, const uint8_t* mask_dev, const uint8_t* aatype_dev, const uint32_t* bound_dev, bool packed,
+                           uint32_t n, uint32_t rows, int layout, const int32_t* acc_index_dev, const float* acc_energy_dev, uint8_t* ss_dev, uint8_t* ss_mask_dev) {
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (rows == 0 || (n == 0 && !packed)) return FCZ_OK;
+    dssp_args g = dssp_pack(pos_dev, mask_dev, aatype_dev, bound_dev, n, rows, layout);
+    g.acc_index = const_cast<int32_t*>(acc_index_dev); g.acc_energy = const_cast<float*>(acc_energy_dev); g.ss = ss_dev; g.ss_mask = ss_mask_dev;
+    const uint32_t max_blocks = (uint32_t)ctx->n_cu * 16u;
+    chain_tiles ct;
+    if (!packed || n) {
+        int rc = ct.reserve(ctx, packed, n, rows); if (rc) return rc;
+        if ((rc = ctx->dssp_flags.ensure(packed ? (size_t)rows : (size_t)n * rows))) return rc;
+        g.flags = ctx->dssp_flags.as<uint8_t>();
+    }
+    span_guard sg(ctx, "dssp");
+    if (packed) {
+        hipLaunchKernelGGL(k_dssp_fill, dim3((uint32_t)std::min<uint64_t>(((uint64_t)rows + BLOCK - 1) / BLOCK, max_blocks)), dim3(BLOCK), 0, ctx->stream, g, 2);
+        if (n == 0) { HIP_TRY(hipGetLastError()); return FCZ_OK; }
+        int rc = ct.scan(ctx, bound_dev, n, rows); if (rc) return rc;
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_dssp_flags<true>), dim3((uint32_t)ct.blocks), dim3(BLOCK), 0, ctx->stream, g, ct.tile_off, 0u, (uint64_t)0);
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_dssp_labels<true>), dim3((uint32_t)ct.blocks), dim3(BLOCK), 0, ctx->stream, g, ct.tile_off, 0u, (uint64_t)0);
+    } else {
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_dssp_flags<false>), dim3((uint32_t)ct.blocks), dim3(BLOCK), 0, ctx->stream, g, (const uint64_t*)nullptr, ct.tiles_per_entry,
+                           ct.n_padded);
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_dssp_labels<false>), dim3((uint32_t)ct.blocks), dim3(BLOCK), 0, ctx->stream, g, (const uint64_t*)nullptr, ct.tiles_per_entry,
+                           ct.n_padded);
+    }
+    HIP_TRY(hipGetLastError());
+    return FCZ_OK;
+}
+
+int fcz_hbond_dev(fcz_ctx* ctx, const float* pos_dev, const uint8_t* mask_dev, const uint8_t* aatype_dev, const uint32_t* length_dev, uint32_t n, uint32_t L,
+                  int layout, int32_t* acc_index_dev, float* acc_energy_dev, int32_t* don_index_dev, float* don_energy_dev) {
+    if (!dssp_args_ok(ctx, pos_dev, mask_dev, layout, L, {acc_index_dev, acc_energy_dev, don_index_dev, don_energy_dev}) || L == 0) return FCZ_E_INVALID_ARG;
+    return hbond_rows(ctx, pos_dev, mask_dev, aatype_dev, length_dev, false, n, L, layout, acc_index_dev, acc_energy_dev, don_index_dev, don_energy_dev);
+}
+
+int fcz_hbond_packed_dev(fcz_ctx* ctx, const float* pos_dev, const uint8_t* mask_dev, const uint8_t* aatype_dev, const uint32_t* row_off_dev, uint32_t n,
+                         uint32_t R, int layout, int32_t* acc_index_dev, float* acc_energy_dev, int32_t* don_index_dev, float* don_energy_dev) {
+    if (!dssp_args_ok(ctx, pos_dev, mask_dev, layout, R, {acc_index_dev, acc_energy_dev, don_index_dev, don_energy_dev}) || (n && !row_off_dev))
+        return FCZ_E_INVALID_ARG;
+    return hbond_rows(ctx, pos_dev, mask_dev, aatype_dev, row_off_dev, true, n, R, layout, acc_index_dev, acc_energy_dev, don_index_dev, don_energy_dev);
+}
+
+int fcz_dssp_labels_dev(fcz_ctx* ctx, const float* pos_dev, const uint8_t* mask_dev, const uint8_t* aatype_dev, const uint32_t* length_dev, uint32_t n,
+                        uint32_t L, int layout, const int32_t* acc_index_dev, const float* acc_energy_dev, uint8_t* ss_dev, uint8_t* ss_mask_dev) {
+    if (!dssp_args_ok(ctx, pos_dev, mask_dev, layout, L, {acc_index_dev, acc_energy_dev, ss_dev, ss_mask_dev}) || L == 0) return FCZ_E_INVALID_ARG;
+    return dssp_label_rows(ctx, pos_dev, mask_dev, aatype_dev, length_dev, false, n, L, layout, acc_index_dev, acc_energy_dev, ss_dev, ss_mask_dev);
+}
+
+int fcz_dssp_labels_packed_dev(fcz_ctx* ctx, const float* pos_dev, const uint8_t* mask_dev, const uint8_t* aatype_dev, const uint32_t* row_off_dev, uint32_t n,
+                               uint32_t R, int layout, const int32_t* acc_index_dev, const float* acc_energy_dev, uint8_t* ss_dev, uint8_t* ss_mask_dev) {
+    if (!dssp_args_ok(ctx, pos_dev, mask_dev, layout, R, {acc_index_dev, acc_energy_dev, ss_dev, ss_mask_dev}) || (n && !row_off_dev)) return FCZ_E_INVALID_ARG;
+    return dssp_label_rows(ctx, pos_dev, mask_dev, aatype_dev, row_off_dev, true, n, R, layout, acc_index_dev, acc_energy_dev, ss_dev, ss_mask_dev);
+}
+
+// fcz_dssp and fcz_dssp_packed: the host arrays through DENSE_IN 0 .. 3 and DSSP_OUT 10 .. 15, both steps
+static int dssp_host(fcz_ctx* ctx, const float* pos, const uint8_t* mask, const uint8_t* aatype, const uint32_t* bound, bool packed, uint32_t n, uint32_t rows_per,
+                     int layout, int32_t* acc_index, float* acc_energy, int32_t* don_index, float* don_energy, uint8_t* ss, uint8_t* ss_mask) {
+    HIP_TRY(hipSetDevice(ctx->device));
+    claim_staging(ctx);
+    const size_t rows = packed ? (size_t)rows_per : (size_t)n * rows_per, A = (size_t)fcz_dense_width(layout);
+    if (rows == 0) return FCZ_OK;
+    const size_t nb = bound ? sizeof(uint32_t) * ((size_t)n + (packed ? 1 : 0)) : 0, np = rows * A * 3 * sizeof(float), nm = rows * A, nt = rows * 2 * 4;
+    int rc;
+    if ((rc = ctx->pool[DENSE_IN].ensure(np)) || (rc = ctx->pool[DENSE_IN + 1].ensure(nm)) || (rc = ctx->pool[DENSE_IN + 2].ensure(aatype ? rows : 0)) ||
+        (rc = ctx->pool[DENSE_IN + 3].ensure(nb)))
+        return rc;
+    for (int k = 0; k < 4; k++) if ((rc = ctx->pool[DSSP_OUT + k].ensure(nt))) return rc;
+    if ((rc = ctx->pool[DSSP_OUT + 4].ensure(rows)) || (rc = ctx->pool[DSSP_OUT + 5].ensure(rows))) return rc;
+    HIP_TRY(hipMemcpyAsync(ctx->pool[DENSE_IN].p, pos, np, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(ctx->pool[DENSE_IN + 1].p, mask, nm, hipMemcpyHostToDevice, ctx->stream));
+    if (aatype) HIP_TRY(hipMemcpyAsync(ctx->pool[DENSE_IN + 2].p, aatype, rows, hipMemcpyHostToDevice, ctx->stream));
+    if (nb) HIP_TRY(hipMemcpyAsync(ctx->pool[DENSE_IN + 3].p, bound, nb, hipMemcpyHostToDevice, ctx->stream));
+    const float* pos_dev = ctx->pool[DENSE_IN].as<float>();
+    const uint8_t* mask_dev = ctx->pool[DENSE_IN + 1].as<uint8_t>();
+    const uint8_t* aatype_dev = aatype ? ctx->pool[DENSE_IN + 2].as<uint8_t>() : nullptr;
+    const uint32_t* bound_dev = nb ? ctx->pool[DENSE_IN + 3].as<uint32_t>() : nullptr;
+    rc = hbond_rows(ctx, pos_dev, mask_dev, aatype_dev, bound_dev, packed, n, rows_per, layout, ctx->pool[DSSP_OUT].as<int32_t>(), ctx->pool[DSSP_OUT + 1].as<float>(),
+                    ctx->pool[DSSP_OUT + 2].as<int32_t>(), ctx->pool[DSSP_OUT + 3].as<float>());
+    if (rc) return rc;
+    rc = dssp_label_rows(ctx, pos_dev, mask_dev, aatype_dev, bound_dev, packed, n, rows_per, layout, ctx->pool[DSSP_OUT].as<int32_t>(),
+                         ctx->pool[DSSP_OUT + 1].as<float>(), ctx->pool[DSSP_OUT + 4].as<uint8_t>(), ctx->pool[DSSP_OUT + 5].as<uint8_t>());
+    if (rc) return rc;
+    void* host[6] = {acc_index, acc_energy, don_index, don_energy, ss, ss_mask};
+    for (int k = 0; k < 6; k++) HIP_TRY(hipMemcpyAsync(host[k], ctx->pool[DSSP_OUT + k].p, k < 4 ? nt : rows, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return FCZ_OK;
+}
+
+int fcz_dssp(fcz_ctx* ctx, const float* pos, const uint8_t* mask, const uint8_t* aatype, const uint32_t* length, uint32_t n, uint32_t L, int layout,
+             int32_t* acc_index, float* acc_energy, int32_t* don_index, float* don_energy, uint8_t* ss, uint8_t* ss_mask) {
+    if (!dssp_args_ok(ctx, pos, mask, layout, L, {acc_index, acc_energy, don_index, don_energy, ss, ss_mask}) || L == 0) return FCZ_E_INVALID_ARG;
+    return dssp_host(ctx, pos, mask, aatype, length, false, n, L, layout, acc_index, acc_energy, don_index, don_energy, ss, ss_mask);
+}
+
+int fcz_dssp_packed(fcz_ctx* ctx, const float* pos, const uint8_t* mask, const uint8_t* aatype, const uint32_t* row_off, uint32_t n, uint32_t R, int layout,
+                    int32_t* acc_index, float* acc_energy, int32_t* don_index, float* don_energy, uint8_t* ss, uint8_t* ss_mask) {
+    if (!dssp_args_ok(ctx, pos, mask, layout, R, {acc_index, acc_energy, don_index, don_energy, ss, ss_mask}) || (n && !row_off)) return FCZ_E_INVALID_ARG;
+    return dssp_host(ctx, pos, mask, aatype, row_off, true, n, R, layout, acc_index, acc_energy, don_index, don_energy, ss, ss_mask);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -17,6 +17,10 @@
     superpose(pred, true, atom="CA", apply=False) -> dict(rot [n, 3, 3], trans [n, 3], rmsd [n], sites [n], dev [..], gdt_counts [n, 5],
                                    gdt_ts, gdt_ha, tm [n]): the least-squares superposition of every chain of pred onto true;
                                    apply=True adds pos_aligned; apply_transform(pos, rot, trans, batch) is that step alone
+    backbone_hbonds(either dict, or the tensors as keywords) -> dict(hbond_acc_index, hbond_acc_energy, hbond_don_index, hbond_don_energy
+                                   [.., 2]): DSSP's four H-bond columns, the two best acceptors and donors of every residue
+    secondary_structure(either dict, or the tensors as keywords) -> dict(ss [..] uint8, ss_mask [..] bool, the four tables): the DSSP
+                                   label of every residue (foldcomp.SS_CLASSES); decode_tensors(secondary_structure=True) adds ss / ss_mask
     rigid_frames(either dict, or the tensors as keywords, groups="backbone" | "all") -> dict(rot [.., 3, 3], trans [.., 3], frame_mask):
                                    every residue's backbone frame, or the eight rigid groups; decode_tensors(frames=...) adds them
 
@@ -41,7 +45,8 @@ from ._aa_tables import RES1
 from .codec import ANGLE_COLUMNS, Codec, dense_layout
 from .structure import CAtomsOut, CDenseIn, CDenseOut, CPackedOut, CSuperposeOut
 
-__all__ = ["decode_tensors", "encode_tensors", "decode_angles", "crop_starts", "neighbor_graph", "rigid_frames", "lddt", "superpose", "apply_transform"]
+__all__ = ["decode_tensors", "encode_tensors", "decode_angles", "crop_starts", "neighbor_graph", "rigid_frames", "lddt", "superpose", "apply_transform",
+           "backbone_hbonds", "secondary_structure"]
 
 
 def crop_starts(length, L: int, how, generator=None):
@@ -244,7 +249,8 @@ def decode_angles(entries: Sequence[bytes], *, max_len: Optional[int] = None, pa
 
 def decode_tensors(entries: Sequence[bytes], *, layout="atom37", max_len: Optional[int] = None, device="cuda:0",
                    codec: Optional[Codec] = None, packed: bool = False, angles: bool = False, crop=None, generator=None,
-                   neighbors: Optional[int] = None, neighbor_atom="CA", frames: Optional[str] = None) -> dict:
+                   neighbors: Optional[int] = None, neighbor_atom="CA", frames: Optional[str] = None,
+                   secondary_structure: bool = False) -> dict:
     """[fcz, ...] -> dict of torch tensors on `device` plus `names` (the records' titles, a Python list).
 
     layout: "atom37" (A = 37, AlphaFold / OpenFold atom order, the chain's OXT in slot 36 of its last residue), "atom14" (A = 14,
@@ -277,6 +283,11 @@ def decode_tensors(entries: Sequence[bytes], *, layout="atom37", max_len: Option
     [..] bool for "backbone", rot [.., 8, 3, 3], trans [.., 8, 3], frame_mask [.., 8] for "all", as rigid_frames describes them.
     frames=None: the dict has no new key.
 
+    secondary_structure=True adds the DSSP labels of the tensors just written, in either form, with no host round trip
+    (fcz_hbond_dev and fcz_dssp_labels_dev on the codec's stream behind the dense call): ss [n, L] / [R] uint8 and ss_mask bool, as
+    secondary_structure describes them (which also returns the H-bond tables). With crop the labels are the window's own.
+    False: the dict has no new key.
+
     Ordering against torch: the uploads and allocations are made on torch's current stream, which is synchronised before the
     codec's calls; the codec works on its own stream, which is synchronised before the tensors are returned. No output byte
     visits the host.
@@ -286,6 +297,8 @@ def decode_tensors(entries: Sequence[bytes], *, layout="atom37", max_len: Option
     if neighbors is not None:
         nbr = (int(neighbors), api.check_neighbors(neighbors, neighbor_atom, _LAYOUT_WIDTH[dense_layout(layout)]))
     fgroups = None if frames is None else api.check_frames(frames)
+    api.check_secondary_structure_flag(secondary_structure)
+    want_ss = bool(secondary_structure)
     torch, dev = _torch_device(device)
     c = codec or api.default_codec()
     if int(c.device) != dev.index:
@@ -329,12 +342,15 @@ def decode_tensors(entries: Sequence[bytes], *, layout="atom37", max_len: Option
     def frames_alloc(*rows):   # frames=None: no key
         return {} if fgroups is None else _frames_alloc(torch, dev, rows, fgroups)
 
+    def ss_alloc(*rows):   # secondary_structure=False: no key
+        return _ss_alloc(torch, dev, rows) if want_ss else {}
+
     if n == 0:
         if packed:
-            d = dict(packed_result(0, torch.zeros(1, dtype=torch.int32, device=dev), 0)[1], **nbr_alloc(0), **frames_alloc(0))
+            d = dict(packed_result(0, torch.zeros(1, dtype=torch.int32, device=dev), 0)[1], **nbr_alloc(0), **frames_alloc(0), **ss_alloc(0))
             return dict(d, **no_angles(0)) if angles else d
         L = int(max_len or 0)
-        d = dict(result(L, *alloc(L)), **nbr_alloc(0, L), **frames_alloc(0, L))
+        d = dict(result(L, *alloc(L)), **nbr_alloc(0, L), **frames_alloc(0, L), **ss_alloc(0, L))
         if crop is not None:
             d["crop_start"] = crop_starts(d["length"], L, crop, generator)
         return dict(d, **no_angles(0, L)) if angles else d
@@ -343,7 +359,8 @@ def decode_tensors(entries: Sequence[bytes], *, layout="atom37", max_len: Option
     if packed:
         # (the angle call is enqueued in front of the decode and leaves it the sizes memo; _decode_packed synchronises the codec)
         extra = _angles_into(c, torch, dev, n, blob_t, off_t, res_off_t, 0, Rv) if angles else {}
-        d = _decode_packed(c, torch, dev, lay, n, Rv, Mv, blob_t, off_t, res_off_t, atom_off_t, packed_result, nbr, nbr_alloc, fgroups, frames_alloc)
+        d = _decode_packed(c, torch, dev, lay, n, Rv, Mv, blob_t, off_t, res_off_t, atom_off_t, packed_result, nbr, nbr_alloc, fgroups, frames_alloc,
+                           ss_alloc)
         return dict(d, **extra)
     if max_len is None:
         ro = res_off_t.cpu().numpy().view(np.uint32).astype(np.int64)      # n + 1 offsets: the only words that come back
@@ -352,7 +369,7 @@ def decode_tensors(entries: Sequence[bytes], *, layout="atom37", max_len: Option
         L = int(max_len)
     out = alloc(L)
     if L == 0:                                                             # nothing decodes and no width was asked for
-        d = dict(result(L, *out), **nbr_alloc(n, 0), **frames_alloc(n, 0))
+        d = dict(result(L, *out), **nbr_alloc(n, 0), **frames_alloc(n, 0), **ss_alloc(n, 0))
         return dict(d, **no_angles(n, 0)) if angles else d
     start_t = None if crop is None else crop_starts(_entry_lengths(res_off_t), L, crop, generator)
     extra = _angles_into(c, torch, dev, n, blob_t, off_t, res_off_t, L, start_t=start_t) if angles else {}
@@ -360,6 +377,8 @@ def decode_tensors(entries: Sequence[bytes], *, layout="atom37", max_len: Option
         extra["crop_start"] = start_t
     extra.update(nbr_alloc(n, L))
     extra.update(frames_alloc(n, L))
+    extra.update(ss_alloc(n, L))
+    tables = _hbond_alloc(torch, dev, (n, L)) if want_ss else None
     x, y, z = (torch.empty(max(M.value, 1), dtype=torch.float32, device=dev) for _ in range(3))
     bfac = torch.empty(max(R.value, 1), dtype=torch.float32, device=dev)
     res_code = torch.empty(max(R.value, 1), dtype=torch.uint8, device=dev)
@@ -381,15 +400,17 @@ def decode_tensors(entries: Sequence[bytes], *, layout="atom37", max_len: Option
     if fgroups is not None:   # (as above: a window needs no length)
         _lib.check(c.lib.fcz_frames_dev(c.ctx, out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(), out[5].data_ptr() if crop is None else None, n, L,
                                         lay, fgroups, extra["rot"].data_ptr(), extra["trans"].data_ptr(), extra["frame_mask"].data_ptr()), "fcz_frames_dev")
+    if want_ss:   # (as above: a window needs no length)
+        _dssp_into(c, out[0], out[1], out[2], out[5] if crop is None else None, n, L, lay, False, tables, extra)
     c.synchronize()
     return dict(result(L, *out), **extra)
 
 
 def _decode_packed(c, torch, dev, lay, n, R, M, blob_t, off_t, res_off_t, atom_off_t, packed_result, nbr=None, nbr_alloc=None, fgroups=None,
-                   frames_alloc=None):
+                   frames_alloc=None, ss_alloc=None):
     """the packed leg of decode_tensors behind fcz_decompress_sizes_dev: R and M are its totals, res_off_t becomes cu_seqlens;
     nbr = (k, slot): the neighbour graph of the rows behind the dense call (nbr_alloc makes its tensors); fgroups: their rigid
-    frames (frames_alloc makes the tensors)"""
+    frames (frames_alloc makes the tensors); ss_alloc: the DSSP labels of the rows, or no key"""
     if R > 2 ** 31 - 1:
         raise api.error(f"decode_tensors: {R} residues do not fit the int32 cu_seqlens; split the batch")
     ro = res_off_t.cpu().numpy().view(np.uint32).astype(np.int64)          # n + 1 offsets: the only words that come back
@@ -398,6 +419,9 @@ def _decode_packed(c, torch, dev, lay, n, R, M, blob_t, off_t, res_off_t, atom_o
         d.update(nbr_alloc(R))
     if fgroups is not None:
         d.update(frames_alloc(R))
+    ss = ss_alloc(R) if ss_alloc is not None else {}
+    d.update(ss)
+    tables = _hbond_alloc(torch, dev, (R,)) if ss and R else None
     if R == 0:                                                             # nothing decodes: no row, length stays 0
         return d
     x, y, z = (torch.empty(max(M, 1), dtype=torch.float32, device=dev) for _ in range(3))
@@ -416,6 +440,8 @@ def _decode_packed(c, torch, dev, lay, n, R, M, blob_t, off_t, res_off_t, atom_o
     if fgroups is not None:   # (the packed form: one entry of R rows, no length)
         _lib.check(c.lib.fcz_frames_dev(c.ctx, out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(), None, 1, R, lay, fgroups,
                                         d["rot"].data_ptr(), d["trans"].data_ptr(), d["frame_mask"].data_ptr()), "fcz_frames_dev")
+    if ss:
+        _dssp_into(c, out[0], out[1], out[2], res_off_t, n, R, lay, True, tables, ss)
     c.synchronize()
     return d
 
@@ -737,6 +763,115 @@ def apply_transform(pos, rot, trans, batch=None, *, mask=None, length=None, cu_s
     _apply_transform(c, pos, mask, rot, trans, n, rows, bound, is_packed, lay, out)
     c.synchronize()
     return out
+
+
+def _hbond_alloc(torch, dev, rows):
+    """the four H-bond tables for the leading shape `rows`"""
+    return {k: torch.empty(tuple(rows) + (2,), dtype=getattr(torch, dt), device=dev) for k, dt in api.HBOND_TABLES}
+
+
+def _ss_alloc(torch, dev, rows):
+    """ss and ss_mask for the leading shape `rows`; ss_mask is written as 0 / 1 bytes"""
+    return dict(ss=torch.empty(tuple(rows), dtype=torch.uint8, device=dev), ss_mask=torch.empty(tuple(rows), dtype=torch.uint8, device=dev).view(torch.bool))
+
+
+def _hbonds_into(c, pos, mask, aatype, bound, n, rows, lay, is_packed, tables):
+    """fcz_hbond_dev / _packed_dev on checked device tensors into the four `tables`, enqueued on the codec's stream"""
+    fn, name = (c.lib.fcz_hbond_packed_dev, "fcz_hbond_packed_dev") if is_packed else (c.lib.fcz_hbond_dev, "fcz_hbond_dev")
+    _lib.check(fn(c.ctx, pos.data_ptr(), mask.data_ptr(), None if aatype is None else aatype.data_ptr(), None if bound is None else bound.data_ptr(),
+                  n, rows, lay, *(tables[k].data_ptr() for k, _ in api.HBOND_TABLES)), name)
+
+
+def _labels_into(c, pos, mask, aatype, bound, n, rows, lay, is_packed, tables, out):
+    """fcz_dssp_labels_dev / _packed_dev from the acceptor tables of `tables` into out["ss"], out["ss_mask"], enqueued alike"""
+    fn, name = (c.lib.fcz_dssp_labels_packed_dev, "fcz_dssp_labels_packed_dev") if is_packed else (c.lib.fcz_dssp_labels_dev, "fcz_dssp_labels_dev")
+    _lib.check(fn(c.ctx, pos.data_ptr(), mask.data_ptr(), None if aatype is None else aatype.data_ptr(), None if bound is None else bound.data_ptr(),
+                  n, rows, lay, tables["hbond_acc_index"].data_ptr(), tables["hbond_acc_energy"].data_ptr(), out["ss"].data_ptr(),
+                  out["ss_mask"].data_ptr()), name)
+
+
+def _dssp_into(c, pos, mask, aatype, bound, n, rows, lay, is_packed, tables, out):
+    """both steps behind one another on the codec's stream"""
+    _hbonds_into(c, pos, mask, aatype, bound, n, rows, lay, is_packed, tables)
+    _labels_into(c, pos, mask, aatype, bound, n, rows, lay, is_packed, tables, out)
+
+
+def _dssp_inputs(what, batch, tensors, codec, hbonds=None):
+    """the checked inputs of backbone_hbonds / secondary_structure -> (c, torch, dev, pos, mask, aatype, lead, n, rows, bound,
+    is_packed, lay, hbonds)"""
+    d = dict(batch) if batch is not None else {}
+    d.update(tensors)
+    shape, is_packed = api.check_dssp(what, d, hbonds)
+    pos = d["pos"]
+    c = codec or api.default_codec()
+    try:
+        import torch
+    except ImportError as e:
+        raise api.error(f"{what} needs PyTorch (ROCm build): {e}") from None
+    if not isinstance(pos, torch.Tensor):
+        raise api.error(f"{what} takes torch tensors on the GPU (numpy arrays: Codec.secondary_structure)")
+    if pos.device.type != "cuda" or pos.device.index != int(c.device):
+        raise api.error(f"{what}: pos lies on {pos.device}, the codec works on cuda:{int(c.device)}; there is no CPU path")
+    dev = pos.device
+    lay = dense_layout(_WIDTH_LAYOUT[shape[-2]])
+    lead = shape[:-2]
+    _on_device(torch, what, dev, "pos", pos, shape, (torch.float32,))
+    mask = _on_device(torch, what, dev, "mask", d["mask"], shape[:-1], (torch.bool, torch.uint8)).view(torch.uint8)
+    aatype = None if d.get("aatype") is None else _on_device(torch, what, dev, "aatype", d["aatype"], lead, (torch.uint8,))
+    if hbonds is not None:
+        hbonds = dict(hbonds)
+        for key, dt in api.HBOND_TABLES[:2]:
+            hbonds[key] = _on_device(torch, what, dev, key, hbonds[key], lead + (2,), (getattr(torch, dt),))
+    n, rows, bound = _chain_bound(torch, what, dev, d, shape, is_packed)
+    return c, torch, dev, pos, mask, aatype, lead, n, rows, bound, is_packed, lay, hbonds
+
+
+def backbone_hbonds(batch=None, *, codec: Optional[Codec] = None, **tensors) -> dict:
+    """dense tensors on the GPU -> DSSP's four hydrogen-bond columns: the two best acceptors of every residue's N-H and the two best
+    donors onto its C=O, inside its own chain, with no L x L array.
+
+    `batch` is the dict decode_tensors / tensor_batches return, padded or packed, or the tensors come as keywords, recognised as
+    neighbor_graph recognises them: pos [n, L, A, 3] float32, mask [n, L, A], optionally aatype [n, L] uint8 (a proline has no
+    amide hydrogen; none: no row is proline) and length [n]; or the packed pos [R, A, 3], mask [R, A], aatype [R] with cu_seqlens
+    [n + 1]. `length` is ignored beside crop_start. Only N, CA, C and O are read, so the three layouts give the same result.
+        hbond_acc_index [.., 2] int32, hbond_acc_energy [.., 2] float32   the acceptors of the row's N-H, lowest energy first
+        hbond_don_index, hbond_don_energy                                 the donors onto the row's C=O
+    An index is the row inside the entry (padded) or the global row (packed), as nbr_index; -1 / 0.0 where there is none. The
+    energy is Kabsch and Sander's electrostatic one in kcal/mol (include/fcz_hip.h, fcz_hbond_dev), in float32 with every operation
+    rounded and no rounding to 0.001; an entry is listed when its energy is below 0, and is a hydrogen bond when below -0.5.
+    Reproducible bit for bit; NOT differentiable. The shapes are checked first, without torch or a device (api.check_dssp)."""
+    c, torch, dev, pos, mask, aatype, lead, n, rows, bound, is_packed, lay, _ = _dssp_inputs("backbone_hbonds", batch, tensors, codec)
+    out = _hbond_alloc(torch, dev, lead)
+    if out["hbond_acc_index"].numel():
+        torch.cuda.current_stream(dev).synchronize()
+        _hbonds_into(c, pos, mask, aatype, bound, n, rows, lay, is_packed, out)
+        c.synchronize()
+    return out
+
+
+def secondary_structure(batch=None, *, hbonds: Optional[dict] = None, codec: Optional[Codec] = None, **tensors) -> dict:
+    """dense tensors on the GPU -> the DSSP secondary structure of every residue (Kabsch & Sander 1983) and the hydrogen bonds it
+    rests on.
+
+    The inputs are backbone_hbonds'. hbonds: a dict with hbond_acc_index and hbond_acc_energy [.., 2] to label from instead of
+    computing them (what backbone_hbonds returned, or tables edited since); the labels depend on the acceptor table alone.
+        ss [n, L] / [R] uint8      the code of the label in foldcomp.SS_CLASSES = ("-", "H", "B", "E", "G", "I", "T", "S");
+                                   foldcomp.SS3_OF_SS8[ss] reduces it to helix 0 / strand 1 / coil 2
+        ss_mask bool               True where the row has N, CA, C and O: elsewhere ss is 0 and means nothing
+        hbond_* [.., 2]            the four tables (with hbonds=: the tables given)
+    The priority is the 1983 one, H > B, E > G > I > T > S; the rules are in include/fcz_hip.h (fcz_dssp_labels_dev). Sheet labels,
+    bridge partners, accessibility and bonds between chains are not computed. A cropped window's labels are the window's own: a
+    strand whose partner lies outside the window is not seen. Reproducible bit for bit; NOT differentiable."""
+    c, torch, dev, pos, mask, aatype, lead, n, rows, bound, is_packed, lay, hbonds = _dssp_inputs("secondary_structure", batch, tensors, codec, hbonds)
+    tables = _hbond_alloc(torch, dev, lead) if hbonds is None else hbonds
+    out = _ss_alloc(torch, dev, lead)
+    if out["ss"].numel():
+        torch.cuda.current_stream(dev).synchronize()
+        if hbonds is None:
+            _hbonds_into(c, pos, mask, aatype, bound, n, rows, lay, is_packed, tables)
+        _labels_into(c, pos, mask, aatype, bound, n, rows, lay, is_packed, tables, out)
+        c.synchronize()
+    return dict(out, **tables)
 
 
 def _frames_alloc(torch, dev, rows, fgroups):

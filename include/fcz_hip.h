@@ -19,6 +19,7 @@
  *                                                          fcz_dense_window_dev / fcz_decompress_dense_window
  *   (none: no neighbour graph of the decoded chain)        fcz_knn_dev / fcz_knn_packed_dev, fcz_knn / fcz_knn_packed
  *   (none: no score of one structure against another)      fcz_lddt_dev / fcz_lddt_packed_dev, fcz_lddt / fcz_lddt_packed
+ *   (none: no secondary structure)                         fcz_hbond_dev, fcz_dssp_labels_dev, fcz_dssp (+ _packed forms)
  *   (none: `rmsd` compares two files unsuperposed)         fcz_superpose_dev / fcz_superpose_packed_dev, fcz_superpose_apply_dev /
  *                                                          fcz_superpose_apply_packed_dev and their host forms
  *   (none: no rigid frames of the decoded chain)           fcz_frames_dev / fcz_frames
@@ -440,6 +441,86 @@ int fcz_lddt(fcz_ctx* ctx, const float* pos_true, const uint8_t* mask_true, cons
 int fcz_lddt_packed(fcz_ctx* ctx, const float* pos_true, const uint8_t* mask_true, const float* pos_pred, const uint8_t* mask_pred,
                     const uint32_t* row_off, uint32_t n, uint32_t R, int layout, int slot, float cutoff, const float* thresholds,
                     float* score, int32_t* pairs, int32_t* hits);
+
+/* ---- backbone hydrogen bonds and DSSP secondary structure of the dense tensors ------------------------------ */
+/* The per-residue secondary structure of Kabsch & Sander (1983) and the backbone hydrogen bonds it rests on, for a whole batch on
+ * the device without an L x L array. The reference has no such output: like fcz_knn_dev these stand beside Foldcomp::decompress
+ * (src/foldcomp.cpp:779) and read what the dense calls wrote, or any tensors of those shapes. Padded: pos [n][L][A][3] float32, mask
+ * [n][L][A] uint8, aatype [n][L] uint8 or NULL (no row is proline), length [n] uint32 (may be NULL). Packed: pos [R][A][3], mask
+ * [R][A], aatype [R] or NULL, row_off [n + 1] uint32. A = fcz_dense_width(layout); only N, CA, C, O are read: slots 0, 1, 2, 4 in
+ * atom37 and 0, 1, 2, 3 in atom14 and backbone4, so the three layouts give the same bits. All arithmetic is float32 with every
+ * operation rounded, no FMA; d2 = (dx*dx + dy*dy) + dz*dz and d = the correctly rounded float32 root of d2 (fcz_knn_dev's d2);
+ * a / b is the correctly rounded float32 quotient.
+ *   backbone row  row r lies inside its chain (fcz_knn_dev's rules for length / row_off), its mask is set at N, CA, C and O and
+ *                 those twelve coordinates are finite. Nothing else is read as data.
+ *   break         there is a break behind row r when r or r + 1 is no backbone row of the chain or d(C[r], N[r+1]) > 2.5f.
+ *                 "No break in a .. b" (a <= b rows of the chain): no break behind any of a .. b - 1.
+ *   amide H       row r has one when r and r - 1 are backbone rows of the chain, there is no break behind r - 1, aatype[r] != 14
+ *                 (proline) and d(C[r-1], O[r-1]) != 0: H = N[r] + (C[r-1] - O[r-1]) / d(C[r-1], O[r-1]), per component one
+ *                 subtraction, one division, one addition.
+ *   energy        of donor i (a row with H) and acceptor j (a backbone row of the same chain, j != i, j != i - 1) with
+ *                 d2(CA[i], CA[j]) < 81.0f: with dON = d(O[j], N[i]), dCH = d(C[j], H[i]), dOH = d(O[j], H[i]), dCN = d(C[j], N[i]),
+ *                 E = -9.9f when any of the four is < 0.5f, else E = 27.888f * (((1/dON + 1/dCH) - 1/dOH) - 1/dCN), raised to -9.9f
+ *                 when below it. The energy COUNTS when E < 0 (a NaN does not); a HYDROGEN BOND is E < -0.5f. DSSP's rounding of
+ *                 E to 0.001 is not done.
+ *   tables        acc_index [rows][2] int32, acc_energy [rows][2] float32: the two acceptors of the row's N-H whose energies count,
+ *                 ordered by (E, row) ascending; don_index, don_energy: the two donors onto the row's C=O, alike. The order is
+ *                 total, so the tables do not depend on any order of evaluation. An index is the row inside the entry (padded,
+ *                 0 .. L - 1) or the global row (packed), as fcz_knn_dev's; an empty slot holds -1 / 0.0f.
+ *   bond(d, a)    a is one of the two entries of acc_index[d] and its acc_energy < -0.5f. The labels use bond() only.
+ *   turn_n(i)     n = 3, 4, 5: bond(i + n, i) and no break in i .. i + n.
+ *   H             turn_4(i - 1) and turn_4(i) make rows i .. i + 3 H.
+ *   bridge (i, j) i >= 1, j >= i + 3, rows i - 1, i + 1, j - 1, j + 1 inside the chain, no break in i - 1 .. i + 1 nor in
+ *                 j - 1 .. j + 1; PARALLEL when (bond(i+1, j) and bond(j, i-1)) or (bond(j+1, i) and bond(i, j-1)), ANTIPARALLEL
+ *                 when (bond(i+1, j-1) and bond(j+1, i-1)) or (bond(j, i) and bond(i, j)). The two kinds are kept apart: a pair
+ *                 may be a bridge of both.
+ *   ladder        a maximal run of bridges of one kind: (i, j), (i+1, j+1), .. parallel; (i, j), (i+1, j-1), .. antiparallel.
+ *   bulge link    ladders X, Y of one kind, gi = ib(Y) - ie(X), gj = jb(Y) - je(X) (parallel) or je(X) - jb(Y) (antiparallel), with
+ *                 (ie, je) the last bridge of X and (ib, jb) the first of Y: 0 < gi < 6, 0 < gj < 6, gi < 3 or gj < 3, no break in
+ *                 ie .. ib and none between je and jb.
+ *   E             every row of a ladder of two or more bridges, every row of a bulge-linked ladder, and the rows ie .. ib and
+ *                 between je and jb of a link. B: the rows of a ladder of one bridge that is not linked. A row that is both is E.
+ *                 Neither overwrites H.
+ *   G             turn_3(i - 1) and turn_3(i) with none of rows i .. i + 2 labelled H, B or E make those rows G.
+ *   I             turn_5(i - 1) and turn_5(i) with none of rows i .. i + 4 labelled H, B, E or G make those rows I.
+ *   T             a row still unlabelled with turn_n(r - k) for some n and 1 <= k < n.
+ *   S             a row still unlabelled, no break in r - 2 .. r + 2, and dot < 0.34202015f * (|u| * |v|) for u = CA[r] - CA[r-2],
+ *                 v = CA[r+2] - CA[r], dot = (ux*vx + uy*vy) + uz*vz, |u| = sqrt((ux*ux + uy*uy) + uz*uz): a bend above 70 degrees.
+ *   ss [rows] uint8       0 .. 7 in the order "-HBEGITS" (the 1983 priority H > B, E > G > I > T > S); 0 on every row that is
+ *                         no backbone row
+ *   ss_mask [rows] uint8  1 on backbone rows, else 0
+ * rows = n * L (padded) or R (packed). Rows behind length and packed rows no chain covers hold -1 / 0.0f, ss 0 and ss_mask 0. Every
+ * byte of the outputs is written whatever the inputs hold, nothing outside them is written, and nothing outside the inputs is read,
+ * whatever row_off or a given acceptor table holds (an index of the table is compared, or checked against the chain's range before
+ * a row is read through it; ranges that overlap are each computed and a shared row's values are then unspecified). Every index that
+ * scales with rows * A is 64-bit.
+ * fcz_hbond_dev writes the four tables. Candidates are staged per chain in passes of fcz_hbond_pass() rows (pure host, > 0): a
+ * longer chain takes several, with the same result. fcz_dssp_labels_dev reads pos, mask and the two ACCEPTOR tables (any tables of
+ * that shape, not only ones fcz_hbond_dev wrote; aatype is accepted and not read) and writes ss and ss_mask; it recomputes no energy.
+ * Enqueued on the ctx stream, no synchronisation (the packed forms share fcz_knn_packed_dev's scratch in the ctx; the label calls
+ * keep a byte per row of scratch there). FCZ_E_INVALID_ARG with nothing launched: NULL ctx / pos / mask / any table or output, NULL
+ * row_off with n > 0, unknown layout, L == 0, L (padded) or R (packed) above 2^31 - 1 (the indices are int32). n == 0 or R == 0:
+ * FCZ_OK (packed, n == 0 < R: every row is uncovered and is filled). The time goes to a group of its own, "dssp", for all the calls
+ * of this block. The results are integers and selected energies: reproducible bit for bit, NOT differentiable. */
+int fcz_hbond_pass(void);
+int fcz_hbond_dev(fcz_ctx* ctx, const float* pos_dev, const uint8_t* mask_dev, const uint8_t* aatype_dev, const uint32_t* length_dev,
+                  uint32_t n, uint32_t L, int layout, int32_t* acc_index_dev, float* acc_energy_dev, int32_t* don_index_dev,
+                  float* don_energy_dev);
+int fcz_hbond_packed_dev(fcz_ctx* ctx, const float* pos_dev, const uint8_t* mask_dev, const uint8_t* aatype_dev,
+                         const uint32_t* row_off_dev, uint32_t n, uint32_t R, int layout, int32_t* acc_index_dev, float* acc_energy_dev,
+                         int32_t* don_index_dev, float* don_energy_dev);
+int fcz_dssp_labels_dev(fcz_ctx* ctx, const float* pos_dev, const uint8_t* mask_dev, const uint8_t* aatype_dev,
+                        const uint32_t* length_dev, uint32_t n, uint32_t L, int layout, const int32_t* acc_index_dev,
+                        const float* acc_energy_dev, uint8_t* ss_dev, uint8_t* ss_mask_dev);
+int fcz_dssp_labels_packed_dev(fcz_ctx* ctx, const float* pos_dev, const uint8_t* mask_dev, const uint8_t* aatype_dev,
+                               const uint32_t* row_off_dev, uint32_t n, uint32_t R, int layout, const int32_t* acc_index_dev,
+                               const float* acc_energy_dev, uint8_t* ss_dev, uint8_t* ss_mask_dev);
+/* Host-pointer conveniences: the same arrays on the host, staged through the ctx like fcz_lddt, both steps; synchronous. */
+int fcz_dssp(fcz_ctx* ctx, const float* pos, const uint8_t* mask, const uint8_t* aatype, const uint32_t* length, uint32_t n, uint32_t L,
+             int layout, int32_t* acc_index, float* acc_energy, int32_t* don_index, float* don_energy, uint8_t* ss, uint8_t* ss_mask);
+int fcz_dssp_packed(fcz_ctx* ctx, const float* pos, const uint8_t* mask, const uint8_t* aatype, const uint32_t* row_off, uint32_t n,
+                    uint32_t R, int layout, int32_t* acc_index, float* acc_energy, int32_t* don_index, float* don_energy, uint8_t* ss,
+                    uint8_t* ss_mask);
 
 /* ---- least-squares (Kabsch) superposition of two dense tensor batches ------------------------------------ */
 /* The superposition-based half of what a validation loop logs, per chain, for a whole batch on the device: the rigid motion that

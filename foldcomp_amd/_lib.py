@@ -97,6 +97,12 @@ def load():
         "fcz_dssp_labels_packed_dev": (i32, [vp, vp, vp, vp, vp, u32, u32, i32, vp, vp, vp, vp]),
         "fcz_dssp": (i32, [vp, vp, vp, vp, vp, u32, u32, i32, vp, vp, vp, vp, vp, vp]),
         "fcz_dssp_packed": (i32, [vp, vp, vp, vp, vp, u32, u32, i32, vp, vp, vp, vp, vp, vp]),
+        "fcz_sasa_pass": (i32, []),
+        "fcz_sasa_default_radii": (i32, [i32, vp]),
+        "fcz_sasa_dev": (i32, [vp, vp, vp, vp, vp, u32, u32, i32, vp, f32, vp, u32, vp, vp, vp]),
+        "fcz_sasa_packed_dev": (i32, [vp, vp, vp, vp, vp, u32, u32, i32, vp, f32, vp, u32, vp, vp, vp]),
+        "fcz_sasa": (i32, [vp, vp, vp, vp, vp, u32, u32, i32, vp, f32, vp, u32, vp, vp, vp]),
+        "fcz_sasa_packed": (i32, [vp, vp, vp, vp, vp, u32, u32, i32, vp, f32, vp, u32, vp, vp, vp]),
         "fcz_superpose_dev": (i32, [vp, vp, vp, vp, vp, vp, u32, u32, i32, i32, ctypes.POINTER(CSuperposeOut)]),
         "fcz_superpose_packed_dev": (i32, [vp, vp, vp, vp, vp, vp, u32, u32, i32, i32, ctypes.POINTER(CSuperposeOut)]),
         "fcz_superpose": (i32, [vp, vp, vp, vp, vp, vp, u32, u32, i32, i32, ctypes.POINTER(CSuperposeOut)]),
@@ -169,6 +175,7 @@ EXPORTS = ["fcz_ctx_create", "fcz_ctx_destroy", "fcz_ctx_stream", "fcz_ctx_synch
            "fcz_knn_pass", "fcz_knn_dev", "fcz_knn_packed_dev", "fcz_knn", "fcz_knn_packed",
            "fcz_lddt_pass", "fcz_lddt_c2", "fcz_lddt_dev", "fcz_lddt_packed_dev", "fcz_lddt", "fcz_lddt_packed",
            "fcz_hbond_pass", "fcz_hbond_dev", "fcz_hbond_packed_dev", "fcz_dssp_labels_dev", "fcz_dssp_labels_packed_dev", "fcz_dssp", "fcz_dssp_packed",
+           "fcz_sasa_pass", "fcz_sasa_default_radii", "fcz_sasa_dev", "fcz_sasa_packed_dev", "fcz_sasa", "fcz_sasa_packed",
            "fcz_superpose_dev", "fcz_superpose_packed_dev", "fcz_superpose", "fcz_superpose_packed",
            "fcz_superpose_apply_dev", "fcz_superpose_apply_packed_dev", "fcz_superpose_apply", "fcz_superpose_apply_packed",
            "fcz_frames_width", "fcz_frame_atom", "fcz_frame_ambiguous", "fcz_frames_dev", "fcz_frames",

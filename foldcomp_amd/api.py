@@ -244,7 +244,7 @@ class FoldcompDatabase:
                        sort_by_length: bool = False, packed: bool = False, max_residues: Optional[int] = None,
                        angles: bool = False, crop: Optional[str] = None, seed: Optional[int] = None,
                        neighbors: Optional[int] = None, neighbor_atom="CA", frames: Optional[str] = None,
-                       secondary_structure: bool = False):
+                       secondary_structure: bool = False, sasa: bool = False):
         """Generator over the database (its `ids` selection when it has one) in batches of dense model-input tensors on the GPU:
         the dicts of foldcomp_amd.tensors.decode_tensors, each with `names` (the records' titles) and `index` (int64 array: the
         entries' positions in this database, what db[i] takes). sort_by_length orders every window of 16 * batch_size entries by
@@ -259,9 +259,11 @@ class FoldcompDatabase:
         (decode_tensors(neighbors=k)); like the other argument rules, a bad k or atom raises at the first next(), before a record
         is read. frames="backbone" | "all" adds the rigid frames `rot` / `trans` / `frame_mask` (decode_tensors(frames=...)), checked
         at the first next() too. secondary_structure=True adds the DSSP labels `ss` / `ss_mask` of every chain
-        (decode_tensors(secondary_structure=True))."""
+        (decode_tensors(secondary_structure=True)). sasa=True adds the solvent accessibility `sasa` / `rsa` / `sasa_mask` of every
+        residue (decode_tensors(sasa=True))."""
         from .tensors import decode_tensors
         check_secondary_structure_flag(secondary_structure)
+        check_sasa_flag(sasa)
         if frames is not None:
             check_frames(frames)
         if neighbors is not None:
@@ -285,7 +287,8 @@ class FoldcompDatabase:
                 sel = np.asarray(sel, np.int64)
                 if packed:
                     d = decode_tensors([ents[k] for k in sel], layout=layout, device=device, packed=True, angles=angles,
-                                       neighbors=neighbors, neighbor_atom=neighbor_atom, frames=frames, secondary_structure=secondary_structure)
+                                       neighbors=neighbors, neighbor_atom=neighbor_atom, frames=frames, secondary_structure=secondary_structure,
+                                       sasa=sasa)
                 else:
                     if crop == "random" and gen is None:
                         import torch
@@ -293,7 +296,7 @@ class FoldcompDatabase:
                         gen.manual_seed(int(seed)) if seed is not None else gen.seed()
                     d = decode_tensors([ents[k] for k in sel], layout=layout, max_len=max_len, device=device, angles=angles, crop=crop,
                                        generator=gen, neighbors=neighbors, neighbor_atom=neighbor_atom, frames=frames,
-                                       secondary_structure=secondary_structure)
+                                       secondary_structure=secondary_structure, sasa=sasa)
                 d["index"] = idx[sel]
                 yield d
 
@@ -443,6 +446,65 @@ def check_dssp(what, d, hbonds=None):
             if tuple(getattr(hbonds[key], "shape", ())) != shape[:-2] + (2,):
                 raise ValueError(f"{key} must have the shape {shape[:-2] + (2,)}, not {tuple(getattr(hbonds[key], 'shape', ()))}")
     return shape, packed
+
+
+# Solvent accessibility (include/fcz_hip.h, fcz_sasa_dev). MAX_ASA: the theoretical maximum accessible surface of a residue in
+# Gly-X-Gly (Tien et al. 2013, PLoS ONE 8:e80635) in square Angstrom, in aatype order A R N D C Q E G H I L K M F P S T W Y V; 0 for
+# index 20 (no such maximum: rsa is 0 there).
+MAX_ASA = np.array([129, 274, 195, 193, 167, 225, 223, 104, 224, 197, 201, 236, 224, 240, 159, 155, 172, 285, 263, 174, 0], np.float32)
+SASA_MAX_POINTS = 1024
+SASA_PROBE = 1.4
+SASA_POINTS = 128
+
+
+def sphere_points(n):
+    """n directions on the unit sphere as float32 [n, 3]: the golden spiral z_k = 1 - (2 k + 1) / n at the angle k * pi * (3 - sqrt(5)),
+    computed in float64 and rounded once. The default surface points of solvent_accessibility."""
+    n = int(n)
+    if not 1 <= n <= SASA_MAX_POINTS:
+        raise ValueError(f"n must be 1 .. {SASA_MAX_POINTS}, not {n}")
+    k = np.arange(n, dtype=np.float64)
+    z = 1.0 - (2.0 * k + 1.0) / n
+    r = np.sqrt(1.0 - z * z)
+    phi = k * (np.pi * (3.0 - np.sqrt(5.0)))
+    return np.stack([r * np.cos(phi), r * np.sin(phi), z], axis=1).astype(np.float32)
+
+
+def check_sasa_flag(flag):
+    """sasa= of decode_tensors / tensor_batches is a switch"""
+    if not isinstance(flag, (bool, np.bool_)):
+        raise ValueError(f"sasa must be True or False, not {flag!r}")
+
+
+def check_sasa(what, d, probe=SASA_PROBE, n_points=SASA_POINTS, points=None, radii="bondi"):
+    """the argument rules of solvent_accessibility that need no torch and no GPU, on the dict `d` of tensors or arrays -> (shape of
+    pos, packed, points float32 [P, 3], radii float32 [21, A] or None for the library's default): check_dssp's rules for pos, mask
+    and aatype; atom14 needs aatype (a slot's atom depends on the type there); probe finite and not negative; 1 .. 1024 points"""
+    shape, packed = check_dssp(what, d)
+    A = shape[-2]
+    if A == 14 and d.get("aatype") is None:
+        raise ValueError(f"{what}: atom14 needs aatype (which atom a slot holds depends on the residue type)")
+    probe = float(probe)
+    if not np.isfinite(probe) or probe < 0:
+        raise ValueError(f"probe must be finite and not negative, not {probe}")
+    if points is None:
+        points = sphere_points(n_points)
+    else:
+        points = np.ascontiguousarray(np.asarray(points.cpu() if hasattr(points, "cpu") else points), np.float32)
+        if points.ndim != 2 or points.shape[1] != 3 or not 1 <= points.shape[0] <= SASA_MAX_POINTS:
+            raise ValueError(f"points must be float32 [P, 3] with 1 <= P <= {SASA_MAX_POINTS}, not {points.shape}")
+    if isinstance(radii, str):
+        if radii != "bondi":
+            raise ValueError(f"radii must be 'bondi' or an array [21, {A}], not {radii!r}")
+        table = None
+    else:
+        table = np.ascontiguousarray(np.asarray(radii), np.float32)
+        if table.shape != (21, A):
+            raise ValueError(f"radii must have the shape (21, {A}), not {table.shape}")
+        R = (table + np.float32(probe))[table != 0]
+        if not ((R >= 0.5) & (R < 8.0)).all():
+            raise ValueError("every non-zero radius plus the probe must lie in [0.5, 8)")
+    return shape, packed, points, table
 
 
 # the rigid groups of groups="all", indexed like AlphaFold / OpenFold rigidgroups_gt_frames (include/fcz_hip.h, fcz_frames_dev)

@@ -324,6 +324,48 @@ class Codec:
         out["ss_mask"] = out["ss_mask"].view(np.bool_)
         return out
 
+    def solvent_accessibility(self, pos: np.ndarray, mask: np.ndarray, aatype=None, length=None, row_off=None, *, probe: float = 1.4,
+                              n_points: int = 128, points=None, radii="bondi"):
+        """dense arrays on the host -> the Shrake-Rupley solvent accessibility of every residue (fcz_sasa, or fcz_sasa_packed when
+        row_off is given): sasa float32 [n, L] / [R] in square Angstrom, rsa float32 (sasa / foldcomp.MAX_ASA[aatype]; 0 without
+        aatype, where the maximum is 0 or sasa_mask is off), sasa_mask bool (the row has an atom) and sasa_points int16 [.., A], the
+        exposed points of every atom slot. pos float32 [n, L, A, 3] with mask [n, L, A], aatype [n, L] uint8 (needed for atom14) and
+        optionally length [n]; or pos [R, A, 3], mask [R, A], aatype [R], row_off [n + 1]. probe, n_points, points and radii are
+        foldcomp.solvent_accessibility's. Reproducible bit for bit, not differentiable."""
+        from . import api
+        pos = np.ascontiguousarray(pos, np.float32)
+        packed = row_off is not None
+        if pos.ndim != (3 if packed else 4) or pos.shape[-1] != 3 or pos.shape[-2] not in (37, 14, 4):
+            raise ValueError(f"pos must be float32 {'[R, A, 3]' if packed else '[n, L, A, 3]'} with A = 37, 14 or 4, not {pos.shape}")
+        lay = {37: 0, 14: 1, 4: 2}[pos.shape[-2]]
+        mask = np.ascontiguousarray(mask)
+        if mask.shape != pos.shape[:-1] or mask.dtype not in (np.bool_, np.uint8):
+            raise ValueError(f"mask must be bool / uint8 {pos.shape[:-1]}, not {mask.dtype} {mask.shape}")
+        lead = pos.shape[:-2]
+        if aatype is not None:
+            aatype = np.ascontiguousarray(aatype)
+            if aatype.shape != lead or aatype.dtype != np.uint8:
+                raise ValueError(f"aatype must be uint8 {lead}, not {aatype.dtype} {aatype.shape}")
+        d = dict(pos=pos, mask=mask, aatype=aatype)
+        if packed:
+            d["cu_seqlens"] = row_off
+        _, _, pts, table = api.check_sasa("Codec.solvent_accessibility", d, probe, n_points, points, radii)
+        n, rows, bound = self._chain_rows(pos, packed, length, row_off)
+        out = dict(sasa=np.zeros(lead, np.float32), rsa=np.zeros(lead, np.float32), sasa_mask=np.zeros(lead, np.uint8),
+                   sasa_points=np.zeros(lead + (pos.shape[-2],), np.int16))
+        if out["sasa"].size:
+            fn = self.lib.fcz_sasa_packed if packed else self.lib.fcz_sasa
+            _lib.check(fn(self.ctx, pos.ctypes.data, mask.ctypes.data, None if aatype is None else aatype.ctypes.data,
+                          None if bound is None else bound.ctypes.data, n, rows, lay, None if table is None else table.ctypes.data, float(probe),
+                          pts.ctypes.data, len(pts), out["sasa_points"].ctypes.data, out["sasa"].ctypes.data, out["sasa_mask"].ctypes.data),
+                       "fcz_sasa_packed" if packed else "fcz_sasa")
+        out["sasa_mask"] = out["sasa_mask"].view(np.bool_)
+        if aatype is not None:
+            mx = api.MAX_ASA[np.minimum(aatype, 20)]
+            ok = (mx > 0) & out["sasa_mask"]
+            out["rsa"][ok] = out["sasa"][ok] / mx[ok]
+        return out
+
     @staticmethod
     def _chain_rows(pos, packed, length, row_off):
         """the chains of dense host arrays -> (n, rows, bound): row_off [n + 1] over the R rows, or length [n] / None over L"""

@@ -36,6 +36,7 @@
 #include "fcz_knn.h"
 #include "fcz_lddt.h"
 #include "fcz_dssp.h"
+#include "fcz_sasa.h"
 #include "fcz_superpose.h"
 #include "fcz_frames.h"
 #include "fcz_angles.h"
@@ -91,11 +92,12 @@ struct timed_span { std::string name; hipEvent_t a, b; };
 // fcz_dense_out, the 7 of a fcz_packed_out (PACKED_OUT .. PACKED_OUT_LAST), in the struct's order; ANGLES_OUT: the angles, their mask and
 // (windowed form) aatype; WINDOW_START: the n u32 starts of a windowed host call; KEPT_*: the records a *_begin call leaves for its fetch
 // (C + 1 u64 offsets, the bytes, C i32 status); LDDT_PRED: pos and mask of the second tensor batch of fcz_lddt, LDDT_OUT: score, pairs, hits;
-// DSSP_OUT: acc_index, acc_energy, don_index, don_energy, ss, ss_mask of fcz_dssp;
+// DSSP_OUT: acc_index, acc_energy, don_index, don_energy, ss, ss_mask of fcz_dssp; SASA_POINTS: the directions of fcz_sasa, SASA_OUT: sasa_points, sasa, sasa_mask;
 // SUPERPOSE_OUT: the seven arrays of a fcz_superpose_out in the struct's order; APPLY_ROT, APPLY_TRANS, APPLY_OUT: the transforms and the moved
 // coordinates of fcz_superpose_apply (its pos and mask go through LDDT_PRED)
 enum { REC_BLOB, REC_OFF, REC_RES_OFF, REC_ATOM_OFF, REC_X, REC_Y, REC_Z, REC_BFAC, REC_RES_CODE, REC_ATOM_CODE,
        FILES_TEXT = 0, FILES_OFF, FILES_NAMES, FILES_NAME_OFF, FILES_STEM_LEN, BATCH_IN = 0, DENSE_IN = 0, LDDT_PRED = 4, DENSE_OUT = 10, LDDT_OUT = 10, SUPERPOSE_OUT = 10, DSSP_OUT = 10,
+       SASA_POINTS = 4, SASA_OUT = 10,
        APPLY_ROT = 10, APPLY_TRANS, APPLY_OUT,
        PACKED_OUT = 10, ANGLES_OUT = 10, KEPT_OFF = 13, KEPT_BYTES, KEPT_STATUS, PACKED_OUT_LAST, WINDOW_START = PACKED_OUT_LAST, POOL_COUNT };
 
@@ -146,7 +148,7 @@ struct fcz_ctx {
     dev_buf res_sc;     // decompress: residue -> its side-chain torsion bytes, 3 x R dwords
     dev_buf sizes_res_off;   // decompress: the res_off of a batch call that has to run its own sizes pass (ensure_sizes)
     dev_buf selftest_out;    // fcz_selftest_math
-    dev_buf knn_tiles;       // fcz_knn_packed_dev, fcz_lddt_packed_dev, fcz_superpose_apply_packed_dev (chain_tile_scan): n u64 tile counts, then their n + 1 offsets
+    dev_buf knn_tiles;       // fcz_knn_packed_dev, fcz_lddt_packed_dev, fcz_superpose_apply_packed_dev (chain_tile_scan), fcz_sasa_packed_dev (sasa_tiles): n u64 tile counts, then their n + 1 offsets
     dev_buf dssp_flags;      // fcz_dssp_labels_dev / _packed_dev: a byte per row (k_dssp_flags -> k_dssp_labels)
     dev_buf fast_scratch;    // decompress, FCZ_NUMERICS_FAST: forward atoms of segments longer than one chunk
     // Staging of the host-pointer entry points. Every entry point that writes it calls claim_staging first. Nothing outlives the call
@@ -173,6 +175,7 @@ struct fcz_ctx {
     //   fcz_superpose_apply[_packed]                LDDT_PRED 4 .. 5 (pos, mask), DENSE_IN 3 (length / row_off), APPLY_ROT 10, APPLY_TRANS 11, APPLY_OUT 12
     //   fcz_dssp / fcz_dssp_packed                  DENSE_IN 0 .. 3 (pos, mask, aatype, length / row_off), DSSP_OUT 10 .. 15 (the four tables, ss, ss_mask)
     //   fcz_frames                                  DENSE_IN 0 .. 3 (pos, mask, aatype, length), DENSE_OUT 10 .. 12 (rot, trans, frame_mask)
+    //   fcz_sasa / fcz_sasa_packed                  DENSE_IN 0 .. 3 (pos, mask, aatype, length / row_off), SASA_POINTS 4, SASA_OUT 10 .. 12 (sasa_points, sasa, sasa_mask)
     dev_buf pool[POOL_COUNT];
     // PDB text / extracted data: per-entry sizes (any call), offsets (n + 1 u64) and the text of the last fcz_decompress_pdb_begin,
     // which fcz_decompress_pdb_fetch reads: live until the next fcz_decompress_pdb_begin / _sizes or fcz_extract
@@ -2015,6 +2018,173 @@ int fcz_dssp_packed(fcz_ctx* ctx, const float* pos, const uint8_t* mask, const u
                     int32_t* acc_index, float* acc_energy, int32_t* don_index, float* don_energy, uint8_t* ss, uint8_t* ss_mask) {
     if (!dssp_args_ok(ctx, pos, mask, layout, R, {acc_index, acc_energy, don_index, don_energy, ss, ss_mask}) || (n && !row_off)) return FCZ_E_INVALID_ARG;
     return dssp_host(ctx, pos, mask, aatype, row_off, true, n, R, layout, acc_index, acc_energy, don_index, don_energy, ss, ss_mask);
+}
+
+// ------------------------------------------------------------------------------------------------
+// per-residue solvent accessibility of dense tensors (fcz_sasa.h; no counterpart in the reference)
+// ------------------------------------------------------------------------------------------------
+int fcz_sasa_pass(void) { return (int)SASA_PASS; }
+
+// Bondi's radius of the element an atom's name begins with; 0: no such element among the twenty types
+static float sasa_element_radius(const char* name) {
+    switch (name[0]) { case 'C': return 1.70f; case 'N': return 1.55f; case 'O': return 1.52f; case 'S': return 1.80f; default: return 0.0f; }
+}
+
+int fcz_sasa_default_radii(int layout, float* out) {
+    const int A = fcz_dense_width(layout);
+    if (A <= 0 || !out) return FCZ_E_INVALID_ARG;
+    float own[FCZ_N_RES_CODES][DN_MAX_WIDTH] = {}, any[DN_MAX_WIDTH] = {};    // per residue code, and over all of them
+    for (int rc = 0; rc < FCZ_N_RES_CODES; rc++)
+        for (int j = 0; j < host_tab::h_res_natoms[rc]; j++) {
+            const int ac = host_tab::h_res_atom[rc][j], slot = fcz_dense_slot(layout, rc, ac);
+            if (slot >= 0) own[rc][slot] = any[slot] = sasa_element_radius(host_tab::h_atom_name[ac]);
+        }
+    // atom14: a slot's atom depends on the type (row 20: the backbone-only codes). atom37 / backbone4: a slot holds the same atom in
+    // every type, so every row is the same and the mask alone says which atoms a residue has. OXT is in no residue's table: 0.
+    for (int ty = 0; ty < (int)SASA_TYPES; ty++)
+        for (int a = 0; a < A; a++) out[ty * A + a] = layout == FCZ_DENSE_ATOM14 ? own[ty][a] : any[a];
+    return FCZ_OK;
+}
+
+// rows: L (padded) or R (packed). Fills tab from radius_table (NULL: the default) when everything is acceptable.
+static bool sasa_args_ok(const fcz_ctx* ctx, const float* pos, const uint8_t* mask, const uint8_t* aatype, int layout, uint32_t rows, const float* radius_table,
+                         float probe, const float* points, uint32_t n_points, std::initializer_list<const void*> out, sasa_table* tab) {
+    const int A = fcz_dense_width(layout);
+    if (!ctx || !pos || !mask || !points || A <= 0 || rows > SASA_MAX_ROWS) return false;
+    for (const void* p : out) if (!p) return false;
+    if (n_points < 1 || n_points > SASA_MAX_POINTS || !std::isfinite(probe) || probe < 0.0f) return false;
+    if (layout == FCZ_DENSE_ATOM14 && !aatype) return false;                  // a slot's atom depends on the type there
+    memset(tab->radius, 0, sizeof tab->radius);
+    if (radius_table) memcpy(tab->radius, radius_table, sizeof(float) * SASA_TYPES * (size_t)A);
+    else if (fcz_sasa_default_radii(layout, tab->radius) != FCZ_OK) return false;
+    for (int i = 0; i < (int)SASA_TYPES * A; i++) {
+        const float r = tab->radius[i];
+        if (r == 0.0f) continue;                                              // no atom in this slot
+        const volatile float R = r + probe;                                   // (one float32 addition, as the kernel's)
+        if (!(R >= 0.5f && R < 8.0f)) return false;                           // (a NaN radius ends here)
+    }
+    return true;
+}
+
+// The query tiles of the accessibility sweep: chain_tiles with SASA_TILE_ROWS rows a tile (fcz_sasa.h), in the same scratch.
+struct sasa_tiles {
+    uint64_t* tile_off = nullptr; uint32_t tiles_per_entry = 0; uint64_t n_padded = 0, blocks = 0;
+    int reserve(fcz_ctx* ctx, bool packed, uint32_t n, uint32_t rows) {
+        const uint32_t max_blocks = (uint32_t)ctx->n_cu * 16u;
+        tiles_per_entry = (uint32_t)(((uint64_t)rows + SASA_TILE_ROWS - 1) / SASA_TILE_ROWS);
+        if (packed) {
+            int rc = ctx->knn_tiles.ensure(sizeof(uint64_t) * (2 * (size_t)n + 1)); if (rc) return rc;
+            tile_off = ctx->knn_tiles.as<uint64_t>() + n;
+            tiles_per_entry = 0;
+            blocks = std::min<uint64_t>((uint64_t)rows / SASA_TILE_ROWS + n, max_blocks);   // the tiles are counted on the device: at most this many
+        } else {
+            n_padded = (uint64_t)n * tiles_per_entry;
+            blocks = std::min<uint64_t>(n_padded, max_blocks);
+        }
+        return FCZ_OK;
+    }
+    int scan(fcz_ctx* ctx, const uint32_t* row_off_dev, uint32_t n, uint32_t R) {
+        const uint32_t max_blocks = (uint32_t)ctx->n_cu * 16u;
+        hipLaunchKernelGGL(k_sasa_tiles, dim3(std::min(grid_for(n, BLOCK), max_blocks)), dim3(BLOCK), 0, ctx->stream, row_off_dev, n, R, ctx->knn_tiles.as<uint64_t>());
+        return device_scan<uint64_t>(ctx, ctx->knn_tiles.as<uint64_t>(), tile_off, n);
+    }
+};
+
+// fcz_sasa_dev (bound_dev is length [n] or NULL, rows = L) and fcz_sasa_packed_dev (bound_dev = row_off [n + 1], rows = R)
+static int sasa_rows(fcz_ctx* ctx, const float* pos_dev, const uint8_t* mask_dev, const uint8_t* aatype_dev, const uint32_t* bound_dev, bool packed, uint32_t n,
+                     uint32_t rows, int layout, const sasa_table& tab, float probe, const float* points_dev, uint32_t n_points, int16_t* sasa_points_dev,
+                     float* sasa_dev, uint8_t* sasa_mask_dev) {
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (rows == 0 || (n == 0 && !packed)) return FCZ_OK;
+    sasa_args g{};
+    g.pos = pos_dev; g.mask = mask_dev; g.aatype = aatype_dev; g.bound = bound_dev; g.n = n; g.L = rows;
+    g.A = (uint32_t)fcz_dense_width(layout); g.P = n_points; g.probe = probe; g.points = points_dev;
+    g.scale = 0x1.921fb54442d18p+3 / (double)n_points;                        // 4 pi / P: one double division
+    g.sasa_points = sasa_points_dev; g.sasa = sasa_dev; g.sasa_mask = sasa_mask_dev;
+    const uint32_t max_blocks = (uint32_t)ctx->n_cu * 16u;
+    const bool small = n_points <= SASA_SMALL_POINTS;
+    sasa_tiles st;
+    if (!packed || n) { int rc = st.reserve(ctx, packed, n, rows); if (rc) return rc; }
+    span_guard sg(ctx, "sasa");
+    if (packed) {
+        hipLaunchKernelGGL(k_sasa_fill, dim3((uint32_t)std::min<uint64_t>(((uint64_t)rows + BLOCK - 1) / BLOCK, max_blocks)), dim3(BLOCK), 0, ctx->stream, g);
+        if (n == 0) { HIP_TRY(hipGetLastError()); return FCZ_OK; }
+        int rc = st.scan(ctx, bound_dev, n, rows); if (rc) return rc;
+        if (small) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_sasa_points<true, true>), dim3((uint32_t)st.blocks), dim3(BLOCK), 0, ctx->stream, g, tab, st.tile_off, 0u, (uint64_t)0);
+        else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_sasa_points<true, false>), dim3((uint32_t)st.blocks), dim3(BLOCK), 0, ctx->stream, g, tab, st.tile_off, 0u, (uint64_t)0);
+    } else {
+        if (small) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_sasa_points<false, true>), dim3((uint32_t)st.blocks), dim3(BLOCK), 0, ctx->stream, g, tab, (const uint64_t*)nullptr,
+                                      st.tiles_per_entry, st.n_padded);
+        else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_sasa_points<false, false>), dim3((uint32_t)st.blocks), dim3(BLOCK), 0, ctx->stream, g, tab, (const uint64_t*)nullptr,
+                                st.tiles_per_entry, st.n_padded);
+    }
+    HIP_TRY(hipGetLastError());
+    return FCZ_OK;
+}
+
+int fcz_sasa_dev(fcz_ctx* ctx, const float* pos_dev, const uint8_t* mask_dev, const uint8_t* aatype_dev, const uint32_t* length_dev, uint32_t n, uint32_t L,
+                 int layout, const float* radius_table, float probe, const float* points_dev, uint32_t n_points, int16_t* sasa_points_dev, float* sasa_dev,
+                 uint8_t* sasa_mask_dev) {
+    sasa_table tab;
+    if (!sasa_args_ok(ctx, pos_dev, mask_dev, aatype_dev, layout, L, radius_table, probe, points_dev, n_points, {sasa_points_dev, sasa_dev, sasa_mask_dev}, &tab) ||
+        L == 0)
+        return FCZ_E_INVALID_ARG;
+    return sasa_rows(ctx, pos_dev, mask_dev, aatype_dev, length_dev, false, n, L, layout, tab, probe, points_dev, n_points, sasa_points_dev, sasa_dev, sasa_mask_dev);
+}
+
+int fcz_sasa_packed_dev(fcz_ctx* ctx, const float* pos_dev, const uint8_t* mask_dev, const uint8_t* aatype_dev, const uint32_t* row_off_dev, uint32_t n, uint32_t R,
+                        int layout, const float* radius_table, float probe, const float* points_dev, uint32_t n_points, int16_t* sasa_points_dev,
+                        float* sasa_dev, uint8_t* sasa_mask_dev) {
+    sasa_table tab;
+    if (!sasa_args_ok(ctx, pos_dev, mask_dev, aatype_dev, layout, R, radius_table, probe, points_dev, n_points, {sasa_points_dev, sasa_dev, sasa_mask_dev}, &tab) ||
+        (n && !row_off_dev))
+        return FCZ_E_INVALID_ARG;
+    return sasa_rows(ctx, pos_dev, mask_dev, aatype_dev, row_off_dev, true, n, R, layout, tab, probe, points_dev, n_points, sasa_points_dev, sasa_dev, sasa_mask_dev);
+}
+
+// fcz_sasa and fcz_sasa_packed: the host arrays through DENSE_IN 0 .. 3, SASA_POINTS 4 and SASA_OUT 10 .. 12
+static int sasa_host(fcz_ctx* ctx, const float* pos, const uint8_t* mask, const uint8_t* aatype, const uint32_t* bound, bool packed, uint32_t n, uint32_t rows_per,
+                     int layout, const sasa_table& tab, float probe, const float* points, uint32_t n_points, int16_t* sasa_points, float* sasa, uint8_t* sasa_mask) {
+    HIP_TRY(hipSetDevice(ctx->device));
+    claim_staging(ctx);
+    const size_t rows = packed ? (size_t)rows_per : (size_t)n * rows_per, A = (size_t)fcz_dense_width(layout);
+    if (rows == 0) return FCZ_OK;
+    const size_t nb = bound ? sizeof(uint32_t) * ((size_t)n + (packed ? 1 : 0)) : 0, np = rows * A * 3 * sizeof(float), nm = rows * A, nu = (size_t)n_points * 3 * sizeof(float);
+    int rc;
+    if ((rc = ctx->pool[DENSE_IN].ensure(np)) || (rc = ctx->pool[DENSE_IN + 1].ensure(nm)) || (rc = ctx->pool[DENSE_IN + 2].ensure(aatype ? rows : 0)) ||
+        (rc = ctx->pool[DENSE_IN + 3].ensure(nb)) || (rc = ctx->pool[SASA_POINTS].ensure(nu)) || (rc = ctx->pool[SASA_OUT].ensure(nm * sizeof(int16_t))) ||
+        (rc = ctx->pool[SASA_OUT + 1].ensure(rows * sizeof(float))) || (rc = ctx->pool[SASA_OUT + 2].ensure(rows)))
+        return rc;
+    HIP_TRY(hipMemcpyAsync(ctx->pool[DENSE_IN].p, pos, np, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(ctx->pool[DENSE_IN + 1].p, mask, nm, hipMemcpyHostToDevice, ctx->stream));
+    if (aatype) HIP_TRY(hipMemcpyAsync(ctx->pool[DENSE_IN + 2].p, aatype, rows, hipMemcpyHostToDevice, ctx->stream));
+    if (nb) HIP_TRY(hipMemcpyAsync(ctx->pool[DENSE_IN + 3].p, bound, nb, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(ctx->pool[SASA_POINTS].p, points, nu, hipMemcpyHostToDevice, ctx->stream));
+    rc = sasa_rows(ctx, ctx->pool[DENSE_IN].as<float>(), ctx->pool[DENSE_IN + 1].as<uint8_t>(), aatype ? ctx->pool[DENSE_IN + 2].as<uint8_t>() : nullptr,
+                   nb ? ctx->pool[DENSE_IN + 3].as<uint32_t>() : nullptr, packed, n, rows_per, layout, tab, probe, ctx->pool[SASA_POINTS].as<float>(), n_points,
+                   ctx->pool[SASA_OUT].as<int16_t>(), ctx->pool[SASA_OUT + 1].as<float>(), ctx->pool[SASA_OUT + 2].as<uint8_t>());
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(sasa_points, ctx->pool[SASA_OUT].p, nm * sizeof(int16_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(sasa, ctx->pool[SASA_OUT + 1].p, rows * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(sasa_mask, ctx->pool[SASA_OUT + 2].p, rows, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return FCZ_OK;
+}
+
+int fcz_sasa(fcz_ctx* ctx, const float* pos, const uint8_t* mask, const uint8_t* aatype, const uint32_t* length, uint32_t n, uint32_t L, int layout,
+             const float* radius_table, float probe, const float* points, uint32_t n_points, int16_t* sasa_points, float* sasa, uint8_t* sasa_mask) {
+    sasa_table tab;
+    if (!sasa_args_ok(ctx, pos, mask, aatype, layout, L, radius_table, probe, points, n_points, {sasa_points, sasa, sasa_mask}, &tab) || L == 0)
+        return FCZ_E_INVALID_ARG;
+    return sasa_host(ctx, pos, mask, aatype, length, false, n, L, layout, tab, probe, points, n_points, sasa_points, sasa, sasa_mask);
+}
+
+int fcz_sasa_packed(fcz_ctx* ctx, const float* pos, const uint8_t* mask, const uint8_t* aatype, const uint32_t* row_off, uint32_t n, uint32_t R, int layout,
+                    const float* radius_table, float probe, const float* points, uint32_t n_points, int16_t* sasa_points, float* sasa, uint8_t* sasa_mask) {
+    sasa_table tab;
+    if (!sasa_args_ok(ctx, pos, mask, aatype, layout, R, radius_table, probe, points, n_points, {sasa_points, sasa, sasa_mask}, &tab) || (n && !row_off))
+        return FCZ_E_INVALID_ARG;
+    return sasa_host(ctx, pos, mask, aatype, row_off, true, n, R, layout, tab, probe, points, n_points, sasa_points, sasa, sasa_mask);
 }
 
 // ------------------------------------------------------------------------------------------------

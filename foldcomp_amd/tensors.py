@@ -21,6 +21,8 @@
                                    [.., 2]): DSSP's four H-bond columns, the two best acceptors and donors of every residue
     secondary_structure(either dict, or the tensors as keywords) -> dict(ss [..] uint8, ss_mask [..] bool, the four tables): the DSSP
                                    label of every residue (foldcomp.SS_CLASSES); decode_tensors(secondary_structure=True) adds ss / ss_mask
+    solvent_accessibility(either dict, or the tensors as keywords) -> dict(sasa [..] float32, rsa, sasa_mask bool, sasa_points [.., A] int16):
+                                   the Shrake-Rupley accessible surface of every residue; decode_tensors(sasa=True) adds sasa / rsa / sasa_mask
     rigid_frames(either dict, or the tensors as keywords, groups="backbone" | "all") -> dict(rot [.., 3, 3], trans [.., 3], frame_mask):
                                    every residue's backbone frame, or the eight rigid groups; decode_tensors(frames=...) adds them
 
@@ -46,7 +48,7 @@ from .codec import ANGLE_COLUMNS, Codec, dense_layout
 from .structure import CAtomsOut, CDenseIn, CDenseOut, CPackedOut, CSuperposeOut
 
 __all__ = ["decode_tensors", "encode_tensors", "decode_angles", "crop_starts", "neighbor_graph", "rigid_frames", "lddt", "superpose", "apply_transform",
-           "backbone_hbonds", "secondary_structure"]
+           "backbone_hbonds", "secondary_structure", "solvent_accessibility"]
 
 
 def crop_starts(length, L: int, how, generator=None):
@@ -250,7 +252,7 @@ def decode_angles(entries: Sequence[bytes], *, max_len: Optional[int] = None, pa
 def decode_tensors(entries: Sequence[bytes], *, layout="atom37", max_len: Optional[int] = None, device="cuda:0",
                    codec: Optional[Codec] = None, packed: bool = False, angles: bool = False, crop=None, generator=None,
                    neighbors: Optional[int] = None, neighbor_atom="CA", frames: Optional[str] = None,
-                   secondary_structure: bool = False) -> dict:
+                   secondary_structure: bool = False, sasa: bool = False) -> dict:
     """[fcz, ...] -> dict of torch tensors on `device` plus `names` (the records' titles, a Python list).
 
     layout: "atom37" (A = 37, AlphaFold / OpenFold atom order, the chain's OXT in slot 36 of its last residue), "atom14" (A = 14,
@@ -288,6 +290,11 @@ def decode_tensors(entries: Sequence[bytes], *, layout="atom37", max_len: Option
     secondary_structure describes them (which also returns the H-bond tables). With crop the labels are the window's own.
     False: the dict has no new key.
 
+    sasa=True adds the solvent accessibility of the tensors just written, in either form, with no host round trip (fcz_sasa_dev on the
+    codec's stream behind the dense call, with the defaults of solvent_accessibility: probe 1.4, 128 points, Bondi radii): sasa
+    [n, L] / [R] float32, rsa float32 and sasa_mask bool, as solvent_accessibility describes them (which also returns the per-atom
+    counts). With crop the values are the window's own: atoms outside the window bury nothing. False: the dict has no new key.
+
     Ordering against torch: the uploads and allocations are made on torch's current stream, which is synchronised before the
     codec's calls; the codec works on its own stream, which is synchronised before the tensors are returned. No output byte
     visits the host.
@@ -299,6 +306,8 @@ def decode_tensors(entries: Sequence[bytes], *, layout="atom37", max_len: Option
     fgroups = None if frames is None else api.check_frames(frames)
     api.check_secondary_structure_flag(secondary_structure)
     want_ss = bool(secondary_structure)
+    api.check_sasa_flag(sasa)
+    want_sasa = bool(sasa)
     torch, dev = _torch_device(device)
     c = codec or api.default_codec()
     if int(c.device) != dev.index:
@@ -345,12 +354,15 @@ def decode_tensors(entries: Sequence[bytes], *, layout="atom37", max_len: Option
     def ss_alloc(*rows):   # secondary_structure=False: no key
         return _ss_alloc(torch, dev, rows) if want_ss else {}
 
+    def sasa_alloc(*rows):   # sasa=False: no key
+        return _sasa_alloc(torch, dev, rows) if want_sasa else {}
+
     if n == 0:
         if packed:
-            d = dict(packed_result(0, torch.zeros(1, dtype=torch.int32, device=dev), 0)[1], **nbr_alloc(0), **frames_alloc(0), **ss_alloc(0))
+            d = dict(packed_result(0, torch.zeros(1, dtype=torch.int32, device=dev), 0)[1], **nbr_alloc(0), **frames_alloc(0), **ss_alloc(0), **sasa_alloc(0))
             return dict(d, **no_angles(0)) if angles else d
         L = int(max_len or 0)
-        d = dict(result(L, *alloc(L)), **nbr_alloc(0, L), **frames_alloc(0, L), **ss_alloc(0, L))
+        d = dict(result(L, *alloc(L)), **nbr_alloc(0, L), **frames_alloc(0, L), **ss_alloc(0, L), **sasa_alloc(0, L))
         if crop is not None:
             d["crop_start"] = crop_starts(d["length"], L, crop, generator)
         return dict(d, **no_angles(0, L)) if angles else d
@@ -360,7 +372,7 @@ def decode_tensors(entries: Sequence[bytes], *, layout="atom37", max_len: Option
         # (the angle call is enqueued in front of the decode and leaves it the sizes memo; _decode_packed synchronises the codec)
         extra = _angles_into(c, torch, dev, n, blob_t, off_t, res_off_t, 0, Rv) if angles else {}
         d = _decode_packed(c, torch, dev, lay, n, Rv, Mv, blob_t, off_t, res_off_t, atom_off_t, packed_result, nbr, nbr_alloc, fgroups, frames_alloc,
-                           ss_alloc)
+                           ss_alloc, sasa_alloc)
         return dict(d, **extra)
     if max_len is None:
         ro = res_off_t.cpu().numpy().view(np.uint32).astype(np.int64)      # n + 1 offsets: the only words that come back
@@ -369,7 +381,7 @@ def decode_tensors(entries: Sequence[bytes], *, layout="atom37", max_len: Option
         L = int(max_len)
     out = alloc(L)
     if L == 0:                                                             # nothing decodes and no width was asked for
-        d = dict(result(L, *out), **nbr_alloc(n, 0), **frames_alloc(n, 0), **ss_alloc(n, 0))
+        d = dict(result(L, *out), **nbr_alloc(n, 0), **frames_alloc(n, 0), **ss_alloc(n, 0), **sasa_alloc(n, 0))
         return dict(d, **no_angles(n, 0)) if angles else d
     start_t = None if crop is None else crop_starts(_entry_lengths(res_off_t), L, crop, generator)
     extra = _angles_into(c, torch, dev, n, blob_t, off_t, res_off_t, L, start_t=start_t) if angles else {}
@@ -379,6 +391,8 @@ def decode_tensors(entries: Sequence[bytes], *, layout="atom37", max_len: Option
     extra.update(frames_alloc(n, L))
     extra.update(ss_alloc(n, L))
     tables = _hbond_alloc(torch, dev, (n, L)) if want_ss else None
+    extra.update(sasa_alloc(n, L))
+    sasa_work = _sasa_work(torch, dev, (n, L, A)) if want_sasa else None
     x, y, z = (torch.empty(max(M.value, 1), dtype=torch.float32, device=dev) for _ in range(3))
     bfac = torch.empty(max(R.value, 1), dtype=torch.float32, device=dev)
     res_code = torch.empty(max(R.value, 1), dtype=torch.uint8, device=dev)
@@ -402,15 +416,19 @@ def decode_tensors(entries: Sequence[bytes], *, layout="atom37", max_len: Option
                                         lay, fgroups, extra["rot"].data_ptr(), extra["trans"].data_ptr(), extra["frame_mask"].data_ptr()), "fcz_frames_dev")
     if want_ss:   # (as above: a window needs no length)
         _dssp_into(c, out[0], out[1], out[2], out[5] if crop is None else None, n, L, lay, False, tables, extra)
+    if want_sasa:   # (as above: a window needs no length)
+        _sasa_into(c, out[0], out[1], out[2], out[5] if crop is None else None, n, L, lay, False, None, api.SASA_PROBE, *sasa_work, extra)
     c.synchronize()
+    if want_sasa:
+        extra["rsa"] = _rsa(torch, extra["sasa"], extra["sasa_mask"], out[2])
     return dict(result(L, *out), **extra)
 
 
 def _decode_packed(c, torch, dev, lay, n, R, M, blob_t, off_t, res_off_t, atom_off_t, packed_result, nbr=None, nbr_alloc=None, fgroups=None,
-                   frames_alloc=None, ss_alloc=None):
+                   frames_alloc=None, ss_alloc=None, sasa_alloc=None):
     """the packed leg of decode_tensors behind fcz_decompress_sizes_dev: R and M are its totals, res_off_t becomes cu_seqlens;
     nbr = (k, slot): the neighbour graph of the rows behind the dense call (nbr_alloc makes its tensors); fgroups: their rigid
-    frames (frames_alloc makes the tensors); ss_alloc: the DSSP labels of the rows, or no key"""
+    frames (frames_alloc makes the tensors); ss_alloc: the DSSP labels of the rows, or no key; sasa_alloc: their solvent accessibility, or no key"""
     if R > 2 ** 31 - 1:
         raise api.error(f"decode_tensors: {R} residues do not fit the int32 cu_seqlens; split the batch")
     ro = res_off_t.cpu().numpy().view(np.uint32).astype(np.int64)          # n + 1 offsets: the only words that come back
@@ -422,6 +440,9 @@ def _decode_packed(c, torch, dev, lay, n, R, M, blob_t, off_t, res_off_t, atom_o
     ss = ss_alloc(R) if ss_alloc is not None else {}
     d.update(ss)
     tables = _hbond_alloc(torch, dev, (R,)) if ss and R else None
+    sa = sasa_alloc(R) if sasa_alloc is not None else {}
+    d.update(sa)
+    sasa_work = _sasa_work(torch, dev, (R, out[1].shape[-1])) if sa and R else None
     if R == 0:                                                             # nothing decodes: no row, length stays 0
         return d
     x, y, z = (torch.empty(max(M, 1), dtype=torch.float32, device=dev) for _ in range(3))
@@ -442,7 +463,11 @@ def _decode_packed(c, torch, dev, lay, n, R, M, blob_t, off_t, res_off_t, atom_o
                                         d["rot"].data_ptr(), d["trans"].data_ptr(), d["frame_mask"].data_ptr()), "fcz_frames_dev")
     if ss:
         _dssp_into(c, out[0], out[1], out[2], res_off_t, n, R, lay, True, tables, ss)
+    if sa:
+        _sasa_into(c, out[0], out[1], out[2], res_off_t, n, R, lay, True, None, api.SASA_PROBE, *sasa_work, d)
     c.synchronize()
+    if sa:
+        d["rsa"] = _rsa(torch, d["sasa"], d["sasa_mask"], out[2])
     return d
 
 
@@ -796,12 +821,12 @@ def _dssp_into(c, pos, mask, aatype, bound, n, rows, lay, is_packed, tables, out
     _labels_into(c, pos, mask, aatype, bound, n, rows, lay, is_packed, tables, out)
 
 
-def _dssp_inputs(what, batch, tensors, codec, hbonds=None):
-    """the checked inputs of backbone_hbonds / secondary_structure -> (c, torch, dev, pos, mask, aatype, lead, n, rows, bound,
-    is_packed, lay, hbonds)"""
+def _dssp_inputs(what, batch, tensors, codec, hbonds=None, numpy_form="Codec.secondary_structure", check=None):
+    """the checked inputs of backbone_hbonds / secondary_structure / solvent_accessibility -> (c, torch, dev, pos, mask, aatype, lead,
+    n, rows, bound, is_packed, lay, hbonds); check(d) -> (shape, packed) replaces api.check_dssp, numpy_form names the host form"""
     d = dict(batch) if batch is not None else {}
     d.update(tensors)
-    shape, is_packed = api.check_dssp(what, d, hbonds)
+    shape, is_packed = api.check_dssp(what, d, hbonds) if check is None else check(d)
     pos = d["pos"]
     c = codec or api.default_codec()
     try:
@@ -809,7 +834,7 @@ def _dssp_inputs(what, batch, tensors, codec, hbonds=None):
     except ImportError as e:
         raise api.error(f"{what} needs PyTorch (ROCm build): {e}") from None
     if not isinstance(pos, torch.Tensor):
-        raise api.error(f"{what} takes torch tensors on the GPU (numpy arrays: Codec.secondary_structure)")
+        raise api.error(f"{what} takes torch tensors on the GPU (numpy arrays: {numpy_form})")
     if pos.device.type != "cuda" or pos.device.index != int(c.device):
         raise api.error(f"{what}: pos lies on {pos.device}, the codec works on cuda:{int(c.device)}; there is no CPU path")
     dev = pos.device
@@ -872,6 +897,77 @@ def secondary_structure(batch=None, *, hbonds: Optional[dict] = None, codec: Opt
         _labels_into(c, pos, mask, aatype, bound, n, rows, lay, is_packed, tables, out)
         c.synchronize()
     return dict(out, **tables)
+
+
+def _sasa_alloc(torch, dev, rows):
+    """sasa, rsa and sasa_mask for the leading shape `rows`; sasa_mask is written as 0 / 1 bytes, rsa by _rsa behind the call"""
+    return dict(sasa=torch.empty(tuple(rows), dtype=torch.float32, device=dev), rsa=torch.zeros(tuple(rows), dtype=torch.float32, device=dev),
+                sasa_mask=torch.empty(tuple(rows), dtype=torch.uint8, device=dev).view(torch.bool))
+
+
+def _sasa_work(torch, dev, shape, points=None):
+    """what fcz_sasa_dev needs beside the outputs -> (the surface points on the device, the per-atom counts of `shape`)"""
+    pts = api.sphere_points(api.SASA_POINTS) if points is None else points
+    return torch.from_numpy(pts).to(dev), torch.empty(tuple(shape), dtype=torch.int16, device=dev)
+
+
+def _sasa_into(c, pos, mask, aatype, bound, n, rows, lay, is_packed, table, probe, points_t, counts_t, out):
+    """fcz_sasa_dev / _packed_dev on checked device tensors into counts_t, out["sasa"], out["sasa_mask"], enqueued on the codec's stream;
+    table: the radii as a contiguous float32 [21, A] array on the host, or None"""
+    fn, name = (c.lib.fcz_sasa_packed_dev, "fcz_sasa_packed_dev") if is_packed else (c.lib.fcz_sasa_dev, "fcz_sasa_dev")
+    _lib.check(fn(c.ctx, pos.data_ptr(), mask.data_ptr(), None if aatype is None else aatype.data_ptr(), None if bound is None else bound.data_ptr(),
+                  n, rows, lay, None if table is None else table.ctypes.data, float(probe), points_t.data_ptr(), int(points_t.shape[0]),
+                  counts_t.data_ptr(), out["sasa"].data_ptr(), out["sasa_mask"].data_ptr()), name)
+
+
+def _rsa(torch, sasa, sasa_mask, aatype):
+    """sasa / foldcomp.MAX_ASA[aatype]: one division on the device; 0 where the maximum is 0, where sasa_mask is off, without aatype"""
+    if aatype is None or not sasa.numel():
+        return torch.zeros_like(sasa)
+    mx = torch.from_numpy(api.MAX_ASA).to(sasa.device)[aatype.clamp(max=20).long()]
+    return torch.where((mx > 0) & sasa_mask, sasa / mx, torch.zeros_like(sasa))
+
+
+def solvent_accessibility(batch=None, *, probe: float = 1.4, n_points: int = 128, points=None, radii="bondi", codec: Optional[Codec] = None,
+                          **tensors) -> dict:
+    """dense tensors on the GPU -> the solvent-accessible surface of every residue (Shrake & Rupley 1973), every atom of a chain
+    against every other atom of it, with no atoms x atoms array.
+
+    The inputs are secondary_structure's: `batch` is the dict decode_tensors / tensor_batches return, padded or packed, or the
+    tensors come as keywords: pos [n, L, A, 3] float32, mask [n, L, A], aatype [n, L] uint8 (needed for atom14, where a slot's
+    atom depends on the type; without it rsa is 0) and optionally length [n]; or the packed pos [R, A, 3], mask [R, A], aatype [R]
+    with cu_seqlens [n + 1]. `length` is ignored beside crop_start. Every slot whose mask is set and whose coordinates are finite is
+    an atom; only atoms of the same chain bury each other.
+        sasa [n, L] / [R] float32   the accessible surface of the residue in square Angstrom
+        rsa float32                 sasa / foldcomp.MAX_ASA[aatype] (Tien et al. 2013): the relative accessibility, usually cut at
+                                    0.05 (buried) .. 0.5 (exposed); 0 where the maximum is 0 (aatype 20), sasa_mask is off or
+                                    there is no aatype. One torch division, not part of the kernel.
+        sasa_mask bool              True where the row has an atom
+        sasa_points [.., A] int16   the surface points of every atom that no other atom buries, 0 .. P
+    probe: the radius of the solvent sphere (water: 1.4). n_points: the surface points per atom, foldcomp.sphere_points(n_points);
+    points: the unit directions [P, 3] themselves instead, 1 <= P <= 1024 (an array or tensor; used as given). radii: "bondi" (C
+    1.70, N 1.55, O 1.52, S 1.80 by the atom's element; the chain's OXT is left out, so the layouts agree) or an array [21, A] indexed
+    [aatype][slot], 0 for a slot that holds no atom; radius + probe must lie in [0.5, 8). The arithmetic is fixed (include/fcz_hip.h,
+    fcz_sasa_dev): atom37 and atom14 give the same bits. A cropped window's values are the window's own: atoms outside it bury
+    nothing, so residues at the cut look more exposed than in the whole chain. Reproducible bit for bit; NOT differentiable. The
+    arguments are checked first, without torch or a device (api.check_sasa)."""
+    checked = {}
+
+    def check(d):
+        checked["v"] = api.check_sasa("solvent_accessibility", d, probe, n_points, points, radii)
+        return checked["v"][:2]
+
+    c, torch, dev, pos, mask, aatype, lead, n, rows, bound, is_packed, lay, _ = _dssp_inputs("solvent_accessibility", batch, tensors, codec,
+                                                                                             numpy_form="Codec.solvent_accessibility", check=check)
+    _, _, pts, table = checked["v"]
+    out = _sasa_alloc(torch, dev, lead)
+    points_t, counts = _sasa_work(torch, dev, lead + (pos.shape[-2],), pts)
+    if out["sasa"].numel():
+        torch.cuda.current_stream(dev).synchronize()
+        _sasa_into(c, pos, mask, aatype, bound, n, rows, lay, is_packed, table, probe, points_t, counts, out)
+        c.synchronize()
+        out["rsa"] = _rsa(torch, out["sasa"], out["sasa_mask"], aatype)
+    return dict(out, sasa_points=counts)
 
 
 def _frames_alloc(torch, dev, rows, fgroups):

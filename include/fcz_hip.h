@@ -20,6 +20,7 @@
  *   (none: no neighbour graph of the decoded chain)        fcz_knn_dev / fcz_knn_packed_dev, fcz_knn / fcz_knn_packed
  *   (none: no score of one structure against another)      fcz_lddt_dev / fcz_lddt_packed_dev, fcz_lddt / fcz_lddt_packed
  *   (none: no secondary structure)                         fcz_hbond_dev, fcz_dssp_labels_dev, fcz_dssp (+ _packed forms)
+ *   (none: no solvent accessibility)                       fcz_sasa_dev / fcz_sasa_packed_dev, fcz_sasa / fcz_sasa_packed
  *   (none: `rmsd` compares two files unsuperposed)         fcz_superpose_dev / fcz_superpose_packed_dev, fcz_superpose_apply_dev /
  *                                                          fcz_superpose_apply_packed_dev and their host forms
  *   (none: no rigid frames of the decoded chain)           fcz_frames_dev / fcz_frames
@@ -521,6 +522,71 @@ int fcz_dssp(fcz_ctx* ctx, const float* pos, const uint8_t* mask, const uint8_t*
 int fcz_dssp_packed(fcz_ctx* ctx, const float* pos, const uint8_t* mask, const uint8_t* aatype, const uint32_t* row_off, uint32_t n,
                     uint32_t R, int layout, int32_t* acc_index, float* acc_energy, int32_t* don_index, float* don_energy, uint8_t* ss,
                     uint8_t* ss_mask);
+
+/* ---- per-residue solvent accessibility of the dense tensors ------------------------------------------------ */
+/* The Shrake-Rupley accessible surface of every chain of a dense batch, for a whole batch on the device, without a rows x rows or an
+ * atoms x atoms array. The reference has no such output: like fcz_hbond_dev these stand beside Foldcomp::decompress
+ * (src/foldcomp.cpp:779) and read what the dense calls wrote, or any tensors of those shapes. Padded: pos [n][L][A][3] float32, mask
+ * [n][L][A] uint8, aatype [n][L] uint8 or NULL, length [n] uint32 (may be NULL). Packed: pos [R][A][3], mask [R][A], aatype [R] or
+ * NULL, row_off [n + 1] uint32. A = fcz_dense_width(layout); every slot is read. All arithmetic is float32 with every operation
+ * rounded, no FMA; d2(p, q) = (dx*dx + dy*dy) + dz*dz (fcz_knn_dev's d2).
+ *   atom          a slot (row, a) of a row inside its chain (fcz_hbond_dev's rules for length / row_off) whose mask is non-zero,
+ *                 whose three coordinates are finite and whose radius is non-zero. Only atoms of the same chain bury each other;
+ *                 a slot that is no atom has 0 points, 0 area and buries nothing. Nothing else is read as data.
+ *   radius        radius_table[21][A] float32, a HOST table indexed [aatype][slot]; aatype is what fcz_dense_dev writes, 0 .. 20,
+ *                 and a value above 20 uses row 20. aatype_dev == NULL: every row uses row 0. The table goes to the kernel by
+ *                 value. NULL selects the default, fcz_sasa_default_radii(layout, ..): the Bondi radius of the element (the first
+ *                 letter of the atom's name: C 1.70, N 1.55, O 1.52, S 1.80) of the atom that fcz_dense_slot puts into the slot. In
+ *                 atom14 that depends on the type: row t < 20 holds the atoms of residue code t, row 20 those of the backbone-only
+ *                 codes (N, CA, C), and a slot the type does not own holds 0. In atom37 and backbone4 a slot holds the same atom in
+ *                 every type that has it, so all 21 rows are the same (the mask says which atoms a residue has) and a NULL aatype
+ *                 is harmless; in atom14 a NULL aatype is refused. OXT (slot 36 of atom37) is in no residue's table and holds 0, so
+ *                 atom37 and atom14 describe the same atoms.
+ *   R             R = radius + probe (one float32 addition). The host refuses a call when R is outside [0.5, 8) for some entry of
+ *                 the table whose radius is non-zero.
+ *   points        points_dev [P][3] float32, 1 <= P <= 1024: the directions u_k, used as given (the library generates none and
+ *                 does not normalise them, so no transcendental function enters the contract). Point k of atom i is
+ *                 t_k = c_i + Ri * u_k, per component one multiplication and one addition.
+ *   candidate     atom j is a candidate of atom i when (row, slot) of j differs from that of i and d2(c_i, c_j) < S * S with
+ *                 S = Ri + Rj. The cull is part of the definition, so that coordinates like 3e19 or duplicated atoms cannot make
+ *                 two evaluations disagree; geometrically it changes nothing (a sphere further away cannot reach a point).
+ *   buried        point k of atom i is buried when some candidate j has d2(t_k, c_j) < Rj * Rj.
+ *   sasa_points [rows][A] int16   the points of the slot's atom that are not buried, 0 .. P: an integer that does not depend on
+ *                                 the order the candidates are met in
+ *   sasa [rows] float32           (float)(sum_a (double)sasa_points[row][a] * (double)(Ra * Ra) * (4 pi / P)): the sum in float64
+ *                                 over the row's atoms with Ra * Ra the float32 product, then ONE double multiplication by
+ *                                 0x1.921fb54442d18p+3 / P and one rounding to float32; in square Angstrom when the inputs are
+ *                                 in Angstrom. Every term is an integer of at most 11 bits times a float32 in [0.25, 64) and at
+ *                                 most 37 terms are summed, so the float64 sum is EXACT: the result does not depend on the order
+ *                                 of the slots, and atom37 and atom14 give the same bits for the same atoms.
+ *   sasa_mask [rows] uint8        1 when the row has at least one atom, else 0
+ * rows = n * L (padded) or R (packed). Rows behind length and packed rows no chain covers hold 0 everywhere. Every byte of the
+ * outputs is written whatever the inputs hold, nothing outside them is written, and nothing outside the inputs is read, whatever
+ * row_off or aatype holds (ranges that overlap are each computed and a shared row's values are then unspecified). Every index that
+ * scales with rows * A is 64-bit. A chain's atoms are staged in passes of at most fcz_sasa_pass() (pure host, > 0): a chain with
+ * more takes several, with the same result.
+ * Enqueued on the ctx stream, no synchronisation (the packed forms share fcz_knn_packed_dev's scratch in the ctx).
+ * FCZ_E_INVALID_ARG with nothing launched: NULL ctx / pos / mask / points / any output, NULL row_off with n > 0, unknown layout,
+ * L == 0, L (padded) or R (packed) above 2^31 - 1, n_points outside 1 .. 1024, probe not finite or negative, the rule on R above,
+ * atom14 without aatype. n == 0 or R == 0: FCZ_OK (packed, n == 0 < R: every row is uncovered and is filled). The time goes to a
+ * group of its own, "sasa". The results are counts and sums of counts: reproducible bit for bit, NOT differentiable. */
+int fcz_sasa_pass(void);
+/* out [21][A] float32 (host): the default radius table of the layout. Pure host. Unknown layout or NULL out: FCZ_E_INVALID_ARG. */
+int fcz_sasa_default_radii(int layout, float* out);
+int fcz_sasa_dev(fcz_ctx* ctx, const float* pos_dev, const uint8_t* mask_dev, const uint8_t* aatype_dev, const uint32_t* length_dev,
+                 uint32_t n, uint32_t L, int layout, const float* radius_table /* host, or NULL */, float probe,
+                 const float* points_dev, uint32_t n_points, int16_t* sasa_points_dev, float* sasa_dev, uint8_t* sasa_mask_dev);
+int fcz_sasa_packed_dev(fcz_ctx* ctx, const float* pos_dev, const uint8_t* mask_dev, const uint8_t* aatype_dev,
+                        const uint32_t* row_off_dev, uint32_t n, uint32_t R, int layout, const float* radius_table /* host, or NULL */,
+                        float probe, const float* points_dev, uint32_t n_points, int16_t* sasa_points_dev, float* sasa_dev,
+                        uint8_t* sasa_mask_dev);
+/* Host-pointer conveniences: the same arrays on the host (points too), staged through the ctx like fcz_dssp; synchronous. */
+int fcz_sasa(fcz_ctx* ctx, const float* pos, const uint8_t* mask, const uint8_t* aatype, const uint32_t* length, uint32_t n, uint32_t L,
+             int layout, const float* radius_table, float probe, const float* points, uint32_t n_points, int16_t* sasa_points,
+             float* sasa, uint8_t* sasa_mask);
+int fcz_sasa_packed(fcz_ctx* ctx, const float* pos, const uint8_t* mask, const uint8_t* aatype, const uint32_t* row_off, uint32_t n,
+                    uint32_t R, int layout, const float* radius_table, float probe, const float* points, uint32_t n_points,
+                    int16_t* sasa_points, float* sasa, uint8_t* sasa_mask);
 
 /* ---- least-squares (Kabsch) superposition of two dense tensor batches ------------------------------------ */
 /* The superposition-based half of what a validation loop logs, per chain, for a whole batch on the device: the rigid motion that

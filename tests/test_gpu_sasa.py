@@ -1,0 +1,396 @@
+"""GPU: per-residue solvent accessibility of dense tensors (fcz_sasa_dev, its packed and host forms, Codec.solvent_accessibility,
+foldcomp.solvent_accessibility, decode_tensors(sasa=True), tensor_batches(sasa=True)) against the numpy restatement of the contract
+(tests/_sasa.py). Counts are compared exactly and areas on bits; the device calls write into arrays pre-filled with 0xA5 with guard
+bytes on both sides."""
+import numpy as np
+import pytest
+
+import _dense as DN
+import _dssp as D
+import _knn as K
+import _sasa as S
+from _cases import compress_cases, db_cases
+from _devpath import to_dev
+from _window import Decoded
+from foldcomp_amd import _lib, api
+
+pytestmark = pytest.mark.gpu
+
+L_GOLD = 1400
+NAN_BITS = np.uint32(0x7FC00123)
+F = np.float32
+TABLE = {A: S.default_table(A) for A in (37, 14, 4)}
+PTS = api.sphere_points(128)
+
+
+@pytest.fixture(scope="module")
+def records(golden):
+    z, index = golden
+    names = compress_cases(index) + db_cases(index)
+    assert len(names) == 56
+    return [z[f"{n}/fcz"].tobytes() for n in names]
+
+
+def _to14(c37, aatype):
+    """per-slot values of atom37 [.., 37] -> atom14 [.., 14] through the slot map of every row's type"""
+    slot = np.full((21, 14), -1, np.int64)
+    for ty in range(21):
+        for j, code in enumerate(DN.RES_ATOMS[ty]):
+            slot[ty, j] = DN.expected_slot("atom37", ty, code)
+    s = slot[np.minimum(aatype, 20)]
+    return np.where(s >= 0, np.take_along_axis(c37, np.maximum(s, 0), axis=-1), 0).astype(c37.dtype)
+
+
+@pytest.fixture(scope="module")
+def gold(codec, records):
+    """the 56 golden records as atom37 / atom14 / backbone4 at L = 1400 on the host and the device, and the restatement on atom37 and
+    on backbone4: computed once, never changed"""
+    dec = Decoded(codec, records)
+    host = {lay: dec.dense(lay, L_GOLD, want=("pos", "mask", "aatype", "length")) for lay in DN.LAYOUTS}
+    dev = {lay: {k: to_dev(v) for k, v in host[lay].items()} for lay in DN.LAYOUTS}
+    a, b = host["atom37"], host["backbone4"]
+    assert a["length"].max() == L_GOLD
+    exp37 = S.sasa(a["pos"], a["mask"], a["aatype"], a["length"], TABLE[37], S.PROBE, PTS)
+    exp4 = S.sasa(b["pos"], b["mask"], b["aatype"], b["length"], TABLE[4], S.PROBE, PTS)
+    exp = dict(atom37=exp37, atom14=[_to14(exp37[0], a["aatype"]), exp37[1], exp37[2]], backbone4=exp4)
+    return dict(host=host, dev=dev, n=len(records), exp=exp, pts=to_dev(PTS))
+
+
+def _rsa(sasa, sasa_mask, aatype):
+    mx = api.MAX_ASA[np.minimum(aatype, 20)]
+    ok = (mx > 0) & sasa_mask
+    out = np.zeros(sasa.shape, F)
+    out[ok] = sasa[ok] / mx[ok]
+    return out
+
+
+def test_golden_padded(codec, gold):
+    n = gold["n"]
+    got = {}
+    for lay in DN.LAYOUTS:
+        d = gold["dev"][lay]
+        got[lay] = S.run_sasa(codec, d["pos"], d["mask"], d["aatype"], d["length"], n, L_GOLD, DN.LAYOUTS[lay], False, gold["pts"])
+        S.same_sasa(got[lay], gold["exp"][lay], lay)
+    assert np.array_equal(K.bits(got["atom37"][1]), K.bits(got["atom14"][1]))           # the same atoms, the same bits
+    assert not got["atom37"][0][..., 36].any() and gold["host"]["atom37"]["mask"][..., 36].sum() > 0   # OXT is there and is left out
+    a = gold["host"]["atom37"]
+    c, sasa, sm = gold["exp"]["atom37"]
+    for e, m in enumerate(a["length"]):
+        assert not c[e, m:].any() and not K.bits(sasa[e, m:]).any() and not sm[e, m:].any()
+    rsa = _rsa(sasa, sm, a["aatype"])
+    known = sm & (a["aatype"] < 20)
+    buried, exposed = int((rsa[known] < 0.05).sum()), int((rsa[known] > 0.5).sum())
+    assert buried > 100 and exposed > 100 and rsa[known].max() < 2.5, (buried, exposed, rsa[known].max())   # real chains have a core and a surface
+    # aatype NULL in atom37: the same result (every row of the default table is the same); outputs that are not 16-byte aligned
+    d = gold["dev"]["atom37"]
+    S.same_sasa(S.run_sasa(codec, d["pos"], d["mask"], None, d["length"], n, L_GOLD, 0, False, gold["pts"], guard=6), gold["exp"]["atom37"], "aatype NULL")
+
+
+def test_golden_packed(codec, gold):
+    lens = np.minimum(gold["host"]["atom37"]["length"].astype(np.int64), L_GOLD)
+    row_off = np.concatenate([[0], np.cumsum(lens)]).astype(np.uint32)
+    R = int(row_off[-1])
+    cat = lambda a: np.concatenate([a[e, :m] for e, m in enumerate(lens)])
+    for lay in DN.LAYOUTS:
+        hh = gold["host"][lay]
+        got = S.run_sasa(codec, to_dev(cat(hh["pos"])), to_dev(cat(hh["mask"])), to_dev(cat(hh["aatype"])), to_dev(row_off), gold["n"], R, DN.LAYOUTS[lay], True,
+                         gold["pts"])
+        S.same_sasa(got, [cat(a) for a in gold["exp"][lay]], f"packed {lay}")
+
+
+# ---- synthetic tensors ----------------------------------------------------------------------------------------------------------
+
+def _helix(rng, m, A):
+    """m rows of A atoms: an ideal alpha helix (backbone4) with a jitter of 0.05, for A = 14 ten more atoms scattered about every CA"""
+    if m == 0:
+        return np.zeros((0, A, 3), F)
+    bb = D.ideal_backbone(-57, -47, m)[0] + (rng.standard_normal((m, 4, 3)) * 0.05).astype(F)
+    if A == 4:
+        return bb
+    side = bb[:, 1:2] + (rng.standard_normal((m, A - 4, 3)) * 2.0).astype(F)
+    return np.concatenate([bb, side], axis=1)
+
+
+def _synthetic(lens, clear, A, seed, hostile=True):
+    """chains [n, L, A, 3] of jittered helices with every mask set but `clear[e]` slots of chain e (NaN patterns under the cleared
+    masks) and NaN patterns in every row behind the length; hostile: ~1 % further masks cleared in the chains without an entry in
+    `clear`, and per such chain of 12 rows or more a NaN, +inf, -inf and two 3e19 coordinates under set masks. aatype random 0 .. 24
+    and 255"""
+    rng = np.random.default_rng(seed)
+    n, L = len(lens), max(max(lens), 1)
+    pos, mask = np.zeros((n, L, A, 3), F), np.ones((n, L, A), np.uint8)
+    for e, m in enumerate(lens):
+        pos[e, :m] = _helix(rng, m, A)
+        if e in clear:
+            flat = rng.choice(m * A, size=clear[e], replace=False)
+            mask[e].reshape(-1)[flat] = 0
+        elif hostile:
+            mask[e, :m][rng.random((m, A)) < 0.01] = 0
+            if m >= 12:
+                r = rng.choice(m, size=5, replace=False)
+                pos[e, r[0], 0, 0] = np.nan; pos[e, r[1], 1, 1] = np.inf; pos[e, r[2], 3, 2] = -np.inf
+                pos[e, r[3], 2, 0] = 3e19; pos[e, r[4], 0, 1] = -3e19
+                mask[e, r, :4] = 1
+        pos[e, m:] = np.nan
+    pos.view(np.uint32)[mask == 0] = NAN_BITS
+    aatype = rng.integers(0, 25, size=(n, L)).astype(np.uint8)
+    aatype[rng.random((n, L)) < 0.05] = 255
+    return pos, mask, aatype
+
+
+def _pack(arrays, lens):
+    return [np.concatenate([a[e, :m] for e, m in enumerate(lens)]) for a in arrays]
+
+
+@pytest.fixture(scope="module")
+def synthetic():
+    """backbone4 chains of 0 .. 7 rows (the row tile is 3) and of Q - 1, Q, Q + 1 and 2 Q + 3 ATOMS for the pass size Q, each with
+    every mask set but the slots that give that count, and two hostile chains; one padded and one packed batch"""
+    Q = _lib.load().fcz_sasa_pass()
+    assert Q % 4 == 0
+    r = Q // 4
+    lens = [0, 1, 2, 3, 4, 5, 6, 7, r, r, r + 1, 2 * r + 1, 40, 300]
+    clear = {8: 1, 9: 0, 10: 3, 11: 1}
+    pos, mask, aa = _synthetic(lens, clear, 4, 21)
+    atoms = [int(S.atoms_of(pos[e, :m], mask[e, :m], aa[e, :m], TABLE[4])[0].sum()) for e, m in enumerate(lens)]
+    assert atoms[8:12] == [Q - 1, Q, Q + 1, 2 * Q + 3], atoms
+    ln = np.asarray(lens, np.uint32)
+    return dict(lens=ln, L=max(lens), arrays=(pos, mask, aa), row_off=np.concatenate([[0], np.cumsum(lens)]).astype(np.uint32), exp={})
+
+
+def _expect(s, P, table=None, probe=S.PROBE):
+    key = (P, None if table is None else table.tobytes(), float(probe))
+    if key not in s["exp"]:
+        s["exp"][key] = S.sasa(*s["arrays"], s["lens"], TABLE[4] if table is None else table, probe, api.sphere_points(P))
+    return s["exp"][key]
+
+
+@pytest.mark.parametrize("P", [1, 63, 64, 65, 128, 1024])
+def test_synthetic_padded_and_packed(codec, synthetic, P):
+    s = synthetic
+    n = len(s["lens"])
+    exp = _expect(s, P)
+    pts = to_dev(api.sphere_points(P))
+    pos, mask, aa = (to_dev(a) for a in s["arrays"])
+    got = S.run_sasa(codec, pos, mask, aa, to_dev(s["lens"]), n, s["L"], 2, False, pts)
+    S.same_sasa(got, exp, "padded")
+    assert (exp[0] == P).any() and ((exp[0] > 0) & (exp[0] < P)).any() == (P > 1) and exp[2][-1].sum() > 290
+    for e, m in enumerate(s["lens"]):
+        assert not got[0][e, m:].any() and not K.bits(got[1][e, m:]).any() and not got[2][e, m:].any()
+    S.same_sasa(S.run_sasa(codec, pos, mask, aa, to_dev(s["lens"]), n, s["L"], 2, False, pts), got, "again")   # two calls give the same bits
+    packed = _pack(s["arrays"], s["lens"])
+    R = int(s["row_off"][-1])
+    exp_packed = _pack(exp, s["lens"])
+    gp = S.run_sasa(codec, *(to_dev(a) for a in packed), to_dev(s["row_off"]), n, R, 2, True, pts)
+    S.same_sasa(gp, exp_packed, "packed")
+    if P in (65, 1024):                                                       # the host-pointer forms against the device forms
+        h = codec.solvent_accessibility(*s["arrays"], length=s["lens"], n_points=P)
+        S.same_sasa((h["sasa_points"], h["sasa"], h["sasa_mask"]), got, "fcz_sasa")
+        h = codec.solvent_accessibility(*packed, row_off=s["row_off"], n_points=P)
+        S.same_sasa((h["sasa_points"], h["sasa"], h["sasa_mask"]), gp, "fcz_sasa_packed")
+        assert np.array_equal(K.bits(h["rsa"]), K.bits(_rsa(h["sasa"], h["sasa_mask"], packed[2])))
+
+
+def test_atom14_types_custom_radii_and_probe(codec):
+    """atom14 rows with every mask set: which slots are atoms follows from aatype through the table (values above 20 use row 20); a
+    custom table and probe; lengths around the row tile and enough rows for two passes of atom14"""
+    lens = [1, 2, 3, 4, 5, 6, 7, 33, 260]
+    pos, mask, aa = _synthetic(lens, {}, 14, 22)
+    ln = np.asarray(lens, np.uint32)
+    n, L = len(lens), max(lens)
+    dev = [to_dev(a) for a in (pos, mask, aa)]
+    assert (aa > 20).sum() > 20 and int(S.atoms_of(pos[-1], mask[-1], aa[-1], TABLE[14])[0].sum()) > _lib.load().fcz_sasa_pass()
+    for P in (65, 128):
+        pts = api.sphere_points(P)
+        S.same_sasa(S.run_sasa(codec, *dev, to_dev(ln), n, L, 1, False, to_dev(pts)), S.sasa(pos, mask, aa, ln, TABLE[14], S.PROBE, pts), f"atom14 P = {P}")
+    rng = np.random.default_rng(3)
+    table = (rng.integers(4, 12, size=(21, 14)) * 0.25).astype(F)              # 1.0 .. 2.75
+    table[rng.random((21, 14)) < 0.2] = 0
+    pts = rng.standard_normal((77, 3)).astype(F)                               # directions used as given: not normalised
+    exp = S.sasa(pos, mask, aa, ln, table, F(0.75), pts)
+    got = S.run_sasa(codec, *dev, to_dev(ln), n, L, 1, False, to_dev(pts), table=table, probe=0.75)
+    S.same_sasa(got, exp, "custom table, probe and points")
+    assert not got[0][..., :][np.broadcast_to((table[np.minimum(aa, 20)] == 0), got[0].shape)].any() and (got[0] > 0).sum() > 1000
+    packed = _pack((pos, mask, aa), lens)
+    row_off = np.concatenate([[0], np.cumsum(lens)]).astype(np.uint32)
+    S.same_sasa(S.run_sasa(codec, *(to_dev(a) for a in packed), to_dev(row_off), n, int(row_off[-1]), 1, True, to_dev(pts), table=table, probe=0.75),
+                _pack(exp, lens), "custom, packed")
+
+
+def test_lattice_ties(codec):
+    """integer-lattice chains with R = 2.5 for every atom: duplicated atoms, d2(c_i, c_j) == S * S = 25 (no candidate) and, with the six
+    axis directions among the points, d2(t_k, c_j) == Rj * Rj = 6.25 (not buried), all exact in float32"""
+    rng = np.random.default_rng(8)
+    lens = [3, 17, 40, 60]
+    n, L = len(lens), max(lens)
+    pos = rng.integers(0, 8, size=(n, L, 4, 3)).astype(F)
+    mask = (rng.random((n, L, 4)) < 0.9).astype(np.uint8)
+    pos[2, 5] = pos[2, 4]                                                      # a row of duplicates
+    aa = np.zeros((n, L), np.uint8)
+    table = np.ones((21, 4), F)
+    axes = np.concatenate([np.eye(3), -np.eye(3)]).astype(F)
+    pts = np.concatenate([axes, api.sphere_points(90)])
+    c = pos[3, :60].reshape(-1, 3)
+    d2 = S._d2(c[:, None], c[None])
+    t = c + F(2.5) * axes[0]
+    assert (d2 == 25).sum() > 100 and (d2 == 0).sum() > len(c) and (S._d2(t[:, None], c[None]) == F(6.25)).sum() > 50
+    ln = np.asarray(lens, np.uint32)
+    exp = S.sasa(pos, mask, aa, ln, table, F(1.5), pts)
+    got = S.run_sasa(codec, to_dev(pos), to_dev(mask), to_dev(aa), to_dev(ln), n, L, 2, False, to_dev(pts), table=table, probe=1.5)
+    S.same_sasa(got, exp, "lattice")
+    assert (exp[0] == 0)[mask != 0].sum() > 50 and (exp[0] > 0).sum() > 50
+
+
+def test_length_null_and_clamped(codec):
+    lens = [40, 100, 77]
+    L = 100
+    pos, mask, aa = _synthetic([L] * 3, {}, 4, 23)                            # finite rows behind every length below
+    dev = [to_dev(a) for a in (pos, mask, aa)]
+    pts = to_dev(PTS)
+    whole = S.sasa(pos, mask, aa, None, TABLE[4], S.PROBE, PTS)
+    S.same_sasa(S.run_sasa(codec, *dev, None, 3, L, 2, False, pts), whole, "NULL")
+    S.same_sasa(S.run_sasa(codec, *dev, to_dev(np.asarray([L + 1, 65535, 0xFFFFFFFF], np.uint32)), 3, L, 2, False, pts), whole, "length > L")
+    exp = S.sasa(pos, mask, aa, lens, TABLE[4], S.PROBE, PTS)
+    assert exp[0].sum() < whole[0].sum() and exp[1][0, 36:40].sum() > whole[1][0, 36:40].sum()   # the chain's new end is more exposed
+    S.same_sasa(S.run_sasa(codec, *dev, to_dev(np.asarray(lens, np.uint32)), 3, L, 2, False, pts), exp, "length < L")
+
+
+def test_hostile_row_off(codec):
+    R = 700
+    pos, mask, aa = (a[0] for a in _synthetic([R], {}, 4, 24))
+    dev = [to_dev(a) for a in (pos, mask, aa)]
+    pts = to_dev(PTS)
+    # chain 0 runs backwards (empty), rows 0 .. 39 are left uncovered, chain 4 runs past R (clamped to the rows that exist)
+    row_off = np.asarray([300, 40, 120, 400, 401, 950], np.uint32)
+    exp = S.sasa(pos, mask, aa, row_off, TABLE[4], S.PROBE, PTS, packed=True)
+    got = S.run_sasa(codec, *dev, to_dev(row_off), 5, R, 2, True, pts)
+    S.same_sasa(got, exp, "hostile row_off")
+    assert not got[0][:40].any() and not K.bits(got[1][:40]).any() and not got[2][:40].any() and got[2][40:].sum() > 640
+    # no chain at all: every row is uncovered
+    got = S.run_sasa(codec, *dev, to_dev(row_off), 0, R, 2, True, pts)
+    assert not got[0].any() and not K.bits(got[1]).any() and not got[2].any()
+
+
+def test_refusals_leave_the_outputs_untouched(codec):
+    import torch
+    n, L, A = 2, 8, 37
+    pos = torch.zeros((n, L, A, 3), dtype=torch.float32, device="cuda:0")
+    mask = torch.ones((n, L, A), dtype=torch.uint8, device="cuda:0")
+    aa = torch.zeros((n, L), dtype=torch.uint8, device="cuda:0")
+    off = to_dev(np.asarray([0, 8, 16], np.uint32))
+    pts = to_dev(PTS)
+    g = [D.Guarded(n * L * A, (np.int16,)), D.Guarded(n * L, (np.float32, np.uint8))]
+    o = g[0].ptrs() + g[1].ptrs()
+    big, nan_tab = TABLE[37].copy(), TABLE[37].copy()
+    big[3, 5], nan_tab[20, 0] = 6.7, np.nan
+    lib, ctx = codec.lib, codec.ctx
+    ok = dict(ctx=ctx, pos=pos.data_ptr(), mask=mask.data_ptr(), aa=aa.data_ptr(), bound=None, n=n, L=L, layout=0, table=None, probe=1.4,
+              points=pts.data_ptr(), P=128, o0=o[0], o1=o[1], o2=o[2])
+    bad = [dict(ctx=None), dict(pos=None), dict(mask=None), dict(points=None), dict(o0=None), dict(o1=None), dict(o2=None), dict(layout=3), dict(layout=-1),
+           dict(L=2 ** 31), dict(P=0), dict(P=1025), dict(probe=float("nan")), dict(probe=float("inf")), dict(probe=-0.5), dict(probe=6.6),
+           dict(table=big.ctypes.data), dict(table=nan_tab.ctypes.data), dict(layout=1, aa=None), dict(L=0)]
+    torch.cuda.synchronize()
+    for b in bad:
+        assert lib.fcz_sasa_dev(*dict(ok, **b).values()) == -1, b
+    for b in bad[:-1]:
+        a = dict(ok, bound=off.data_ptr(), L=n * L)
+        a.update(b)
+        assert lib.fcz_sasa_packed_dev(*a.values()) == -1, b
+    assert lib.fcz_sasa_packed_dev(*dict(ok, L=n * L).values()) == -1          # chains without a row_off
+    assert lib.fcz_sasa_dev(*dict(ok, n=0).values()) == 0 and lib.fcz_sasa_packed_dev(*dict(ok, bound=off.data_ptr(), L=0).values()) == 0
+    codec.synchronize()
+    assert all(x.untouched() for x in g)
+
+
+# ---- Python surface -------------------------------------------------------------------------------------------------------------
+
+def _triple(d):
+    return d["sasa_points"].cpu().numpy(), d["sasa"].cpu().numpy(), d["sasa_mask"].cpu().numpy()
+
+
+def _pair(d, exp, what):
+    S.same_sasa((exp[0], d["sasa"].cpu().numpy(), d["sasa_mask"].cpu().numpy()), exp, what)
+
+
+def test_foldcomp_solvent_accessibility(codec, gold, records):
+    import torch
+    import foldcomp_amd as foldcomp
+    n = len(records)
+    exp = gold["exp"]["atom37"]
+    t = foldcomp.decode_tensors(records, codec=codec, sasa=True)
+    assert t["sasa"].shape == (n, L_GOLD) and t["sasa"].dtype == t["rsa"].dtype == torch.float32 and t["sasa_mask"].dtype == torch.bool
+    assert t["sasa"].device.type == "cuda" and "sasa_points" not in t
+    _pair(t, exp, "decode_tensors(sasa=True)")
+    aa = gold["host"]["atom37"]["aatype"]
+    rsa = _rsa(exp[1], exp[2], aa)
+    assert np.allclose(t["rsa"].cpu().numpy(), rsa, rtol=2.0 ** -22, atol=0) and not t["rsa"].cpu().numpy()[~exp[2] | (aa == 20)].any()
+    plain = foldcomp.decode_tensors(records, codec=codec)
+    assert not {"sasa", "rsa", "sasa_mask"} & set(plain)
+    out = foldcomp.solvent_accessibility(plain, codec=codec)
+    assert set(out) == {"sasa", "rsa", "sasa_mask", "sasa_points"} and out["sasa_points"].dtype == torch.int16 and out["sasa_points"].shape == (n, L_GOLD, 37)
+    S.same_sasa(_triple(out), exp, "solvent_accessibility")
+    assert torch.equal(out["rsa"], t["rsa"])
+    kw = foldcomp.solvent_accessibility(pos=plain["pos"], mask=plain["mask"], aatype=plain["aatype"], length=plain["length"], points=PTS, codec=codec)
+    S.same_sasa(_triple(kw), exp, "keywords, points=")
+    none = foldcomp.solvent_accessibility(pos=plain["pos"], mask=plain["mask"], length=plain["length"], codec=codec)    # no aatype: no rsa
+    S.same_sasa(_triple(none), exp, "no aatype")
+    assert not none["rsa"].any()
+    # the numpy form, a custom table and probe
+    h14 = gold["host"]["atom14"]
+    sub = [h14[k][:6, :300] for k in ("pos", "mask", "aatype")]
+    table = TABLE[14] * F(1.1)
+    h = codec.solvent_accessibility(*sub, length=h14["length"][:6], radii=table, probe=1.2, n_points=96)
+    p14 = foldcomp.decode_tensors(records[:6], codec=codec, layout="atom14", max_len=300)
+    dev = foldcomp.solvent_accessibility(p14, radii=table, probe=1.2, n_points=96, codec=codec)
+    S.same_sasa((h["sasa_points"], h["sasa"], h["sasa_mask"]), _triple(dev), "Codec.solvent_accessibility")
+    assert np.allclose(h["rsa"], dev["rsa"].cpu().numpy(), rtol=2.0 ** -22, atol=0) and h["sasa"].sum() > 10000
+    # packed
+    p = foldcomp.decode_tensors(records, codec=codec, packed=True, sasa=True)
+    cu = p["cu_seqlens"].cpu().numpy()
+    lens = np.diff(cu)
+    cat = lambda a: np.concatenate([a[e, :m] for e, m in enumerate(lens)])
+    _pair(p, [cat(a) for a in exp], "packed decode_tensors")
+    po = foldcomp.solvent_accessibility(p, codec=codec)
+    S.same_sasa(_triple(po), [cat(a) for a in exp], "packed solvent_accessibility")
+    assert torch.equal(po["rsa"], p["rsa"])
+    # a cropped window's values are the window's own: the restatement of the window alone, with no length
+    w = foldcomp.decode_tensors(records, codec=codec, max_len=64, crop="center", layout="atom14", sasa=True)
+    wp, wm, wa = w["pos"].cpu().numpy(), w["mask"].cpu().numpy().view(np.uint8), w["aatype"].cpu().numpy()
+    wexp = S.sasa(wp, wm, wa, None, TABLE[14], S.PROBE, PTS)
+    _pair(w, wexp, "window")
+    S.same_sasa(_triple(foldcomp.solvent_accessibility(w, codec=codec)), wexp, "window, separate call")
+    st = w["crop_start"].cpu().numpy()
+    more = [e for e in range(n) if st[e] > 0 and wexp[1][e].sum() > exp[1][e, st[e]:st[e] + 64].sum()]
+    assert len(more) > 10, "a window cut out of a chain loses the atoms that bury its ends"
+    # nothing to compute
+    e = foldcomp.decode_tensors([], codec=codec, max_len=8, sasa=True)
+    assert e["sasa"].shape == e["rsa"].shape == e["sasa_mask"].shape == (0, 8) and foldcomp.solvent_accessibility(e, codec=codec)["sasa_points"].shape == (0, 8, 37)
+    e = foldcomp.decode_tensors([], codec=codec, packed=True, sasa=True)
+    assert e["sasa"].shape == (0,) and foldcomp.solvent_accessibility(e, codec=codec)["sasa_points"].shape == (0, 37)
+    with pytest.raises(ValueError):
+        foldcomp.solvent_accessibility(dict(plain, pos=plain["pos"].transpose(0, 1).contiguous().transpose(0, 1)), codec=codec)   # not contiguous
+    with pytest.raises(foldcomp.error):
+        foldcomp.solvent_accessibility(dict(pos=plain["pos"].cpu(), mask=plain["mask"].cpu()), codec=codec)
+
+
+def test_tensor_batches_sasa(codec, records, tmp_path):
+    import foldcomp_amd as foldcomp
+    from foldcomp_amd.database import DatabaseWriter
+    path = str(tmp_path / "db")
+    w = DatabaseWriter(path)
+    for k, e in enumerate(records[:6]):
+        w.append(e, k, f"entry_{k:02d}")
+    w.close()
+    api.set_codec(codec)
+    try:
+        with foldcomp.open(path) as db:
+            for packed in (False, True):
+                batches = list(db.tensor_batches(4, packed=packed, sasa=True))
+                assert len(batches) == 2 and all({"sasa", "rsa", "sasa_mask"} <= set(b) and "sasa_points" not in b for b in batches)
+                sep = foldcomp.solvent_accessibility(batches[0])
+                for k in ("sasa", "rsa", "sasa_mask"):
+                    assert np.array_equal(batches[0][k].cpu().numpy().view(np.uint8), sep[k].cpu().numpy().view(np.uint8)), (packed, k)
+                assert float(batches[0]["sasa"].sum()) > 1000
+            assert not {"sasa", "rsa", "sasa_mask"} & set(next(iter(db.tensor_batches(4))))
+    finally:
+        api.set_codec(None)

@@ -9,7 +9,7 @@ from __future__ import annotations
 import ctypes
 import os
 
-from .structure import CAtomsOut, CChainBatch, CDenseIn, CDenseOut, CEntryInfo, CIngestResult, CPackedOut, CSuperposeOut
+from .structure import CAtomsOut, CChainBatch, CDenseIn, CDenseOut, CEntryInfo, CIngestResult, CPackedOut, CSuperposeOut, CTmScoreOut
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # FCZ_HIP_LIB selects another build of the same library (A/B timing of kernel variants); it is still a HIP build
@@ -111,6 +111,12 @@ def load():
         "fcz_superpose_apply_packed_dev": (i32, [vp, vp, vp, vp, u32, u32, i32, vp, vp, vp]),
         "fcz_superpose_apply": (i32, [vp, vp, vp, vp, u32, u32, i32, vp, vp, vp]),
         "fcz_superpose_apply_packed": (i32, [vp, vp, vp, vp, u32, u32, i32, vp, vp, vp]),
+        "fcz_tmscore_seeds": (u64, [u32, u32]),
+        "fcz_tmscore_seed_fragment": (i32, [u32, u32, u64, ctypes.POINTER(u32), ctypes.POINTER(u32)]),
+        "fcz_tmscore_dev": (i32, [vp, vp, vp, vp, vp, vp, u32, u32, i32, i32, u32, u32, ctypes.POINTER(CTmScoreOut)]),
+        "fcz_tmscore_packed_dev": (i32, [vp, vp, vp, vp, vp, vp, u32, u32, i32, i32, u32, u32, ctypes.POINTER(CTmScoreOut)]),
+        "fcz_tmscore": (i32, [vp, vp, vp, vp, vp, vp, u32, u32, i32, i32, u32, u32, ctypes.POINTER(CTmScoreOut)]),
+        "fcz_tmscore_packed": (i32, [vp, vp, vp, vp, vp, vp, u32, u32, i32, i32, u32, u32, ctypes.POINTER(CTmScoreOut)]),
         "fcz_frames_width": (i32, [i32]),
         "fcz_frame_atom": (i32, [i32, i32, i32]),
         "fcz_frame_ambiguous": (i32, [i32, i32]),
@@ -178,6 +184,7 @@ EXPORTS = ["fcz_ctx_create", "fcz_ctx_destroy", "fcz_ctx_stream", "fcz_ctx_synch
            "fcz_sasa_pass", "fcz_sasa_default_radii", "fcz_sasa_dev", "fcz_sasa_packed_dev", "fcz_sasa", "fcz_sasa_packed",
            "fcz_superpose_dev", "fcz_superpose_packed_dev", "fcz_superpose", "fcz_superpose_packed",
            "fcz_superpose_apply_dev", "fcz_superpose_apply_packed_dev", "fcz_superpose_apply", "fcz_superpose_apply_packed",
+           "fcz_tmscore_seeds", "fcz_tmscore_seed_fragment", "fcz_tmscore_dev", "fcz_tmscore_packed_dev", "fcz_tmscore", "fcz_tmscore_packed",
            "fcz_frames_width", "fcz_frame_atom", "fcz_frame_ambiguous", "fcz_frames_dev", "fcz_frames",
            "fcz_extract_sizes", "fcz_extract",
            "fcz_extract_sizes_dev", "fcz_extract_dev", "fcz_ingest_pdb_dev", "fcz_ingest_pdb_begin", "fcz_ingest_pdb_fetch", "fcz_ingest_chain_names_fetch",

@@ -406,6 +406,24 @@ def check_superpose(atom, shape, pred_shape, pred_mask_shape=None):
     return slot
 
 
+TM_MAX_ITERATIONS = 64                                                     # what fcz_tmscore_dev accepts (include/fcz_hip.h)
+
+
+def check_tm_score(atom, shape, pred_shape, pred_mask_shape=None, iterations=20, levels=None):
+    """the argument rules of tm_score that need no torch and no GPU -> (slot, iterations, levels as the C call takes it: 0 = every
+    fragment length): check_superpose's rules, iterations an integer 0 .. 64, levels None or an integer >= 1"""
+    return (check_superpose(atom, shape, pred_shape, pred_mask_shape),) + check_tm_search(iterations, levels)
+
+
+def check_tm_search(iterations=20, levels=None):
+    """iterations an integer 0 .. 64, levels None or an integer >= 1 -> (iterations, levels as the C call takes it: 0 = every length)"""
+    if isinstance(iterations, (bool, np.bool_)) or not isinstance(iterations, (int, np.integer)) or not 0 <= int(iterations) <= TM_MAX_ITERATIONS:
+        raise ValueError(f"iterations must be an integer 0 .. {TM_MAX_ITERATIONS}, not {iterations!r}")
+    if levels is not None and (isinstance(levels, (bool, np.bool_)) or not isinstance(levels, (int, np.integer)) or not 1 <= int(levels) < 2 ** 32):
+        raise ValueError(f"levels must be None (every fragment length) or an integer >= 1, not {levels!r}")
+    return int(iterations), 0 if levels is None else int(levels)
+
+
 # the labels of `ss`, in the order of their codes (include/fcz_hip.h, fcz_dssp_labels_dev), and the usual reduction to three states
 # (helix 0: H, G, I; strand 1: E, B; coil 2: the rest) as a table to index with `ss`
 SS_CLASSES = ("-", "H", "B", "E", "G", "I", "T", "S")

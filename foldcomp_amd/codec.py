@@ -15,7 +15,7 @@ from typing import Optional
 import numpy as np
 
 from . import _lib
-from .structure import CAtomsOut, CChainBatch, CDenseIn, CDenseOut, CEntryInfo, ChainBatch, CPackedOut, CSuperposeOut, batch_as_c
+from .structure import CAtomsOut, CChainBatch, CDenseIn, CDenseOut, CEntryInfo, ChainBatch, CPackedOut, CSuperposeOut, CTmScoreOut, batch_as_c
 
 
 # the columns of the angle tensors (FCZ_ANGLE_COLUMNS, include/fcz_hip.h), degrees
@@ -390,6 +390,42 @@ class Codec:
         (x_true ~ rot @ x_pred + trans), rmsd [n], sites int32 [n], gdt_counts int32 [n, 5] (dev <= 0.5, 1, 2, 4, 8), tm [n] (the
         TM-score at this superposition, a lower bound of the maximised one) and dev float32 [n, L] / [R], every site's deviation.
         The arrays are those of Codec.lddt. The sums are float64 in a fixed order: reproducible bit for bit, not differentiable."""
+        pos_true, masks, pos_pred, lay, slot, packed, n, rows, bound = self._superpose_inputs(pos_true, mask_true, pos_pred, mask_pred, slot, length, row_off)
+        d = self._superpose_outputs(n, pos_true.shape[:-2])
+        if n and rows:
+            out = CSuperposeOut(*(d[k].ctypes.data for k in ("rot", "trans", "rmsd", "sites", "gdt_counts", "tm", "dev")))
+            fn = self.lib.fcz_superpose_packed if packed else self.lib.fcz_superpose
+            _lib.check(fn(self.ctx, pos_true.ctypes.data, masks[0].ctypes.data, pos_pred.ctypes.data, None if masks[1] is None else masks[1].ctypes.data,
+                          None if bound is None else bound.ctypes.data, n, rows, lay, slot, ctypes.byref(out)), "fcz_superpose_packed" if packed else "fcz_superpose")
+        return d
+
+    def tm_score(self, pos_true: np.ndarray, mask_true: np.ndarray, pos_pred: np.ndarray, mask_pred=None, slot: int = 1, length=None, row_off=None,
+                 iterations: int = 20, levels=None):
+        """two sets of dense arrays of one shape on the host -> per chain the superposition that maximises the TM-score over the
+        seeded iterative search of fcz_tmscore (fcz_tmscore_packed when row_off is given; the definition: include/fcz_hip.h), and
+        Codec.superpose's outputs at it: rot, trans, rmsd, sites, gdt_counts, tm, dev; beside them seed int32 [n], the winning
+        seed's number, and selected int32 [n], the size of the winning selection. tm >= Codec.superpose's tm. iterations: rounds of
+        refinement per seed, 0 .. 64; levels: only the first so many fragment lengths (None: all). Reproducible bit for bit."""
+        pos_true, masks, pos_pred, lay, slot, packed, n, rows, bound = self._superpose_inputs(pos_true, mask_true, pos_pred, mask_pred, slot, length, row_off)
+        from .api import check_tm_search
+        iterations, levels = check_tm_search(iterations, levels)
+        d = self._superpose_outputs(n, pos_true.shape[:-2])
+        d.update(seed=np.zeros(n, np.int32), selected=np.zeros(n, np.int32))
+        if n and rows:
+            out = CTmScoreOut(*(d[k].ctypes.data for k in ("rot", "trans", "rmsd", "sites", "gdt_counts", "tm", "dev", "seed", "selected")))
+            fn = self.lib.fcz_tmscore_packed if packed else self.lib.fcz_tmscore
+            _lib.check(fn(self.ctx, pos_true.ctypes.data, masks[0].ctypes.data, pos_pred.ctypes.data, None if masks[1] is None else masks[1].ctypes.data,
+                          None if bound is None else bound.ctypes.data, n, rows, lay, slot, levels, iterations, ctypes.byref(out)),
+                       "fcz_tmscore_packed" if packed else "fcz_tmscore")
+        return d
+
+    @staticmethod
+    def _superpose_outputs(n, rows_shape):
+        return dict(rot=np.tile(np.eye(3, dtype=np.float32), (n, 1, 1)), trans=np.zeros((n, 3), np.float32), rmsd=np.zeros(n, np.float32),
+                    sites=np.zeros(n, np.int32), gdt_counts=np.zeros((n, 5), np.int32), tm=np.zeros(n, np.float32), dev=np.zeros(rows_shape, np.float32))
+
+    def _superpose_inputs(self, pos_true, mask_true, pos_pred, mask_pred, slot, length, row_off):
+        """the checked arrays of superpose / tm_score -> (pos_true, [mask_true, mask_pred], pos_pred, layout, slot, packed, n, rows, bound)"""
         pos_true = np.ascontiguousarray(pos_true, np.float32)
         pos_pred = np.ascontiguousarray(pos_pred, np.float32)
         packed = row_off is not None
@@ -412,14 +448,7 @@ class Codec:
         if not 0 <= slot < A:
             raise ValueError(f"slot must be 0 .. {A - 1}")
         n, rows, bound = self._chain_rows(pos_true, packed, length, row_off)
-        d = dict(rot=np.tile(np.eye(3, dtype=np.float32), (n, 1, 1)), trans=np.zeros((n, 3), np.float32), rmsd=np.zeros(n, np.float32),
-                 sites=np.zeros(n, np.int32), gdt_counts=np.zeros((n, 5), np.int32), tm=np.zeros(n, np.float32), dev=np.zeros(pos_true.shape[:-2], np.float32))
-        if n and rows:
-            out = CSuperposeOut(*(d[k].ctypes.data for k in ("rot", "trans", "rmsd", "sites", "gdt_counts", "tm", "dev")))
-            fn = self.lib.fcz_superpose_packed if packed else self.lib.fcz_superpose
-            _lib.check(fn(self.ctx, pos_true.ctypes.data, masks[0].ctypes.data, pos_pred.ctypes.data, None if masks[1] is None else masks[1].ctypes.data,
-                          None if bound is None else bound.ctypes.data, n, rows, lay, slot, ctypes.byref(out)), "fcz_superpose_packed" if packed else "fcz_superpose")
-        return d
+        return pos_true, masks, pos_pred, lay, slot, packed, n, rows, bound
 
     def apply_transform(self, pos: np.ndarray, rot: np.ndarray, trans: np.ndarray, mask=None, length=None, row_off=None):
         """dense coordinates on the host moved by one rigid transform per chain (fcz_superpose_apply, or fcz_superpose_apply_packed

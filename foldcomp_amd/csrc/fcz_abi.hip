@@ -38,6 +38,7 @@
 #include "fcz_dssp.h"
 #include "fcz_sasa.h"
 #include "fcz_superpose.h"
+#include "fcz_tmscore.h"
 #include "fcz_frames.h"
 #include "fcz_angles.h"
 
@@ -94,12 +95,12 @@ struct timed_span { std::string name; hipEvent_t a, b; };
 // (C + 1 u64 offsets, the bytes, C i32 status); LDDT_PRED: pos and mask of the second tensor batch of fcz_lddt, LDDT_OUT: score, pairs, hits;
 // DSSP_OUT: acc_index, acc_energy, don_index, don_energy, ss, ss_mask of fcz_dssp; SASA_POINTS: the directions of fcz_sasa, SASA_OUT: sasa_points, sasa, sasa_mask;
 // SUPERPOSE_OUT: the seven arrays of a fcz_superpose_out in the struct's order; APPLY_ROT, APPLY_TRANS, APPLY_OUT: the transforms and the moved
-// coordinates of fcz_superpose_apply (its pos and mask go through LDDT_PRED)
+// coordinates of fcz_superpose_apply (its pos and mask go through LDDT_PRED); TM_SEED, TM_SELECTED: the two arrays a fcz_tmscore_out adds to those seven
 enum { REC_BLOB, REC_OFF, REC_RES_OFF, REC_ATOM_OFF, REC_X, REC_Y, REC_Z, REC_BFAC, REC_RES_CODE, REC_ATOM_CODE,
        FILES_TEXT = 0, FILES_OFF, FILES_NAMES, FILES_NAME_OFF, FILES_STEM_LEN, BATCH_IN = 0, DENSE_IN = 0, LDDT_PRED = 4, DENSE_OUT = 10, LDDT_OUT = 10, SUPERPOSE_OUT = 10, DSSP_OUT = 10,
        SASA_POINTS = 4, SASA_OUT = 10,
        APPLY_ROT = 10, APPLY_TRANS, APPLY_OUT,
-       PACKED_OUT = 10, ANGLES_OUT = 10, KEPT_OFF = 13, KEPT_BYTES, KEPT_STATUS, PACKED_OUT_LAST, WINDOW_START = PACKED_OUT_LAST, POOL_COUNT };
+       PACKED_OUT = 10, ANGLES_OUT = 10, KEPT_OFF = 13, KEPT_BYTES, KEPT_STATUS, PACKED_OUT_LAST, WINDOW_START = PACKED_OUT_LAST, TM_SEED, TM_SELECTED, POOL_COUNT };
 
 // what the device reports to the host in the middle of a call: one pinned allocation, a member per reader
 struct pinned_words {
@@ -149,6 +150,7 @@ struct fcz_ctx {
     dev_buf sizes_res_off;   // decompress: the res_off of a batch call that has to run its own sizes pass (ensure_sizes)
     dev_buf selftest_out;    // fcz_selftest_math
     dev_buf knn_tiles;       // fcz_knn_packed_dev, fcz_lddt_packed_dev, fcz_superpose_apply_packed_dev (chain_tile_scan), fcz_sasa_packed_dev (sasa_tiles): n u64 tile counts, then their n + 1 offsets
+    dev_buf tm_scratch;      // fcz_tmscore_dev / _packed_dev: n u64 item counts, their n + 1 offsets, a double per seed (tm_items_bound), n u32 site counts
     dev_buf dssp_flags;      // fcz_dssp_labels_dev / _packed_dev: a byte per row (k_dssp_flags -> k_dssp_labels)
     dev_buf fast_scratch;    // decompress, FCZ_NUMERICS_FAST: forward atoms of segments longer than one chunk
     // Staging of the host-pointer entry points. Every entry point that writes it calls claim_staging first. Nothing outlives the call
@@ -172,6 +174,7 @@ struct fcz_ctx {
     //   fcz_knn / fcz_knn_packed                    DENSE_IN 0, 1, 3 (pos, mask, length / row_off), DENSE_OUT 10 .. 11 (index, dist)
     //   fcz_lddt / fcz_lddt_packed                  DENSE_IN 0, 1, 3 (pos_true, mask_true, length / row_off), LDDT_PRED 4 .. 5 (pos_pred, mask_pred), LDDT_OUT 10 .. 12
     //   fcz_superpose / fcz_superpose_packed        DENSE_IN 0, 1, 3 and LDDT_PRED 4 .. 5 as fcz_lddt, SUPERPOSE_OUT 10 .. 16
+    //   fcz_tmscore / fcz_tmscore_packed            the same, then TM_SEED 17, TM_SELECTED 18
     //   fcz_superpose_apply[_packed]                LDDT_PRED 4 .. 5 (pos, mask), DENSE_IN 3 (length / row_off), APPLY_ROT 10, APPLY_TRANS 11, APPLY_OUT 12
     //   fcz_dssp / fcz_dssp_packed                  DENSE_IN 0 .. 3 (pos, mask, aatype, length / row_off), DSSP_OUT 10 .. 15 (the four tables, ss, ss_mask)
     //   fcz_frames                                  DENSE_IN 0 .. 3 (pos, mask, aatype, length), DENSE_OUT 10 .. 12 (rot, trans, frame_mask)
@@ -2277,24 +2280,24 @@ int fcz_superpose_apply_packed_dev(fcz_ctx* ctx, const float* pos_dev, const uin
     return superpose_apply_rows(ctx, pos_dev, mask_dev, row_off_dev, true, n, R, layout, rot_dev, trans_dev, pos_out_dev);
 }
 
-// fcz_superpose and fcz_superpose_packed: the host arrays through DENSE_IN 0, 1, 3, LDDT_PRED 4, 5 and SUPERPOSE_OUT 10 .. 16
-static int superpose_host(fcz_ctx* ctx, const float* pos_true, const uint8_t* mask_true, const float* pos_pred, const uint8_t* mask_pred, const uint32_t* bound,
-                          bool packed, uint32_t n, uint32_t rows_per, int layout, int slot, const fcz_superpose_out& out) {
+// The host arrays of a superposition call through DENSE_IN 0, 1, 3 and LDDT_PRED 4, 5, its n_out outputs (host[i] may be NULL: not wanted) through
+// pool[slots[i]]; run(pos_true, mask_true, pos_pred, mask_pred, bound, d) enqueues the call on the staged arrays, d[i] the device side of host[i]
+extern "C++" template <class Run>
+static int superpose_staged(fcz_ctx* ctx, const float* pos_true, const uint8_t* mask_true, const float* pos_pred, const uint8_t* mask_pred, const uint32_t* bound,
+                            bool packed, uint32_t n, uint32_t rows_per, int layout, int n_out, void* const* host, const size_t* bytes, const int* slots, Run run) {
     HIP_TRY(hipSetDevice(ctx->device));
     claim_staging(ctx);
     const size_t rows = packed ? (size_t)rows_per : (size_t)n * rows_per, A = (size_t)fcz_dense_width(layout);
     if (n == 0 && rows == 0) return FCZ_OK;
     const size_t nb = bound ? sizeof(uint32_t) * ((size_t)n + (packed ? 1 : 0)) : 0, np = rows * A * 3 * sizeof(float), nm = rows * A;
-    void* host[7] = {out.rot, out.trans, out.rmsd, out.sites, out.gdt_counts, out.tm, out.dev};
-    const size_t bytes[7] = {36 * (size_t)n, 12 * (size_t)n, 4 * (size_t)n, 4 * (size_t)n, 20 * (size_t)n, 4 * (size_t)n, 4 * rows};
     int rc;
     if ((rc = ctx->pool[DENSE_IN].ensure(np)) || (rc = ctx->pool[DENSE_IN + 1].ensure(nm)) || (rc = ctx->pool[DENSE_IN + 3].ensure(nb)) ||
         (rc = ctx->pool[LDDT_PRED].ensure(np)) || (rc = ctx->pool[LDDT_PRED + 1].ensure(mask_pred ? nm : 0)))
         return rc;
-    void* d[7];
-    for (int i = 0; i < 7; i++) {
-        if ((rc = ctx->pool[SUPERPOSE_OUT + i].ensure(host[i] ? bytes[i] : 0))) return rc;
-        d[i] = host[i] ? ctx->pool[SUPERPOSE_OUT + i].p : nullptr;
+    void* d[9];
+    for (int i = 0; i < n_out; i++) {
+        if ((rc = ctx->pool[slots[i]].ensure(host[i] ? bytes[i] : 0))) return rc;
+        d[i] = host[i] ? ctx->pool[slots[i]].p : nullptr;
     }
     if (np) {
         HIP_TRY(hipMemcpyAsync(ctx->pool[DENSE_IN].p, pos_true, np, hipMemcpyHostToDevice, ctx->stream));
@@ -2304,15 +2307,27 @@ static int superpose_host(fcz_ctx* ctx, const float* pos_true, const uint8_t* ma
     }
     if (nb) HIP_TRY(hipMemcpyAsync(ctx->pool[DENSE_IN + 3].p, bound, nb, hipMemcpyHostToDevice, ctx->stream));
     // (R == 0 with chains: the arrays have no allocation and every chain is empty, so nothing of them is read)
-    const fcz_superpose_out o{(float*)d[0], (float*)d[1], (float*)d[2], (int32_t*)d[3], (int32_t*)d[4], (float*)d[5], (float*)d[6]};
-    rc = superpose_rows(ctx, ctx->pool[DENSE_IN].as<float>(), ctx->pool[DENSE_IN + 1].as<uint8_t>(), ctx->pool[LDDT_PRED].as<float>(),
-                        mask_pred && np ? ctx->pool[LDDT_PRED + 1].as<uint8_t>() : nullptr, nb ? ctx->pool[DENSE_IN + 3].as<uint32_t>() : nullptr, packed, n,
-                        rows_per, layout, slot, o);
+    rc = run(ctx->pool[DENSE_IN].as<float>(), ctx->pool[DENSE_IN + 1].as<uint8_t>(), ctx->pool[LDDT_PRED].as<float>(),
+             mask_pred && np ? ctx->pool[LDDT_PRED + 1].as<uint8_t>() : nullptr, nb ? ctx->pool[DENSE_IN + 3].as<uint32_t>() : nullptr, d);
     if (rc) return rc;
-    for (int i = 0; i < 7; i++)
+    for (int i = 0; i < n_out; i++)
         if (host[i] && bytes[i]) HIP_TRY(hipMemcpyAsync(host[i], d[i], bytes[i], hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return FCZ_OK;
+}
+
+// fcz_superpose and fcz_superpose_packed: SUPERPOSE_OUT 10 .. 16
+static int superpose_host(fcz_ctx* ctx, const float* pos_true, const uint8_t* mask_true, const float* pos_pred, const uint8_t* mask_pred, const uint32_t* bound,
+                          bool packed, uint32_t n, uint32_t rows_per, int layout, int slot, const fcz_superpose_out& out) {
+    const size_t rows = packed ? (size_t)rows_per : (size_t)n * rows_per;
+    void* host[7] = {out.rot, out.trans, out.rmsd, out.sites, out.gdt_counts, out.tm, out.dev};
+    const size_t bytes[7] = {36 * (size_t)n, 12 * (size_t)n, 4 * (size_t)n, 4 * (size_t)n, 20 * (size_t)n, 4 * (size_t)n, 4 * rows};
+    const int slots[7] = {SUPERPOSE_OUT, SUPERPOSE_OUT + 1, SUPERPOSE_OUT + 2, SUPERPOSE_OUT + 3, SUPERPOSE_OUT + 4, SUPERPOSE_OUT + 5, SUPERPOSE_OUT + 6};
+    return superpose_staged(ctx, pos_true, mask_true, pos_pred, mask_pred, bound, packed, n, rows_per, layout, 7, host, bytes, slots,
+                            [&](const float* pt, const uint8_t* mt, const float* pp, const uint8_t* mp, const uint32_t* bd, void** d) {
+        const fcz_superpose_out o{(float*)d[0], (float*)d[1], (float*)d[2], (int32_t*)d[3], (int32_t*)d[4], (float*)d[5], (float*)d[6]};
+        return superpose_rows(ctx, pt, mt, pp, mp, bd, packed, n, rows_per, layout, slot, o);
+    });
 }
 
 int fcz_superpose(fcz_ctx* ctx, const float* pos_true, const uint8_t* mask_true, const float* pos_pred, const uint8_t* mask_pred, const uint32_t* length,
@@ -2365,6 +2380,105 @@ int fcz_superpose_apply_packed(fcz_ctx* ctx, const float* pos, const uint8_t* ma
                                const float* trans, float* pos_out) {
     if (!superpose_apply_args_ok(ctx, pos, layout, R, rot, trans, pos_out) || (n && !row_off)) return FCZ_E_INVALID_ARG;
     return superpose_apply_host(ctx, pos, mask, row_off, true, n, R, layout, rot, trans, pos_out);
+}
+
+// ------------------------------------------------------------------------------------------------
+// maximised TM-score by seeded iterative superposition (fcz_tmscore.h; no counterpart in the reference)
+// ------------------------------------------------------------------------------------------------
+uint64_t fcz_tmscore_seeds(uint32_t sites, uint32_t levels) { return tm_seed_count(sites, levels); }
+
+int fcz_tmscore_seed_fragment(uint32_t sites, uint32_t levels, uint64_t seed, uint32_t* start, uint32_t* length) {
+    if (!start || !length || seed >= tm_seed_count(sites, levels)) return FCZ_E_INVALID_ARG;
+    tm_seed_fragment(sites, seed, start, length);
+    return FCZ_OK;
+}
+
+static bool tmscore_args_ok(const fcz_ctx* ctx, const float* pos_true, const uint8_t* mask_true, const float* pos_pred, int layout, int slot, uint32_t rows,
+                            uint32_t iterations, const fcz_tmscore_out* out) {
+    if (!ctx || !pos_true || !mask_true || !pos_pred || !out || !out->rot || !out->trans) return false;
+    if (fcz_dense_width(layout) <= 0 || slot < 0 || slot >= fcz_dense_width(layout)) return false;
+    return rows <= SUPERPOSE_MAX_ROWS && iterations <= TM_MAX_ITERATIONS;
+}
+
+// fcz_tmscore_dev (bound_dev is length [n] or NULL, rows = L) and fcz_tmscore_packed_dev (bound_dev = row_off [n + 1], rows = R)
+static int tmscore_rows(fcz_ctx* ctx, const float* pos_true_dev, const uint8_t* mask_true_dev, const float* pos_pred_dev, const uint8_t* mask_pred_dev,
+                        const uint32_t* bound_dev, bool packed, uint32_t n, uint32_t rows, int layout, int slot, uint32_t levels, uint32_t iterations,
+                        const fcz_tmscore_out& o) {
+    HIP_TRY(hipSetDevice(ctx->device));
+    const bool fill = packed && rows && o.dev;
+    if (n == 0 && !fill) return FCZ_OK;
+    tmscore_args g{{pos_true_dev, mask_true_dev, pos_pred_dev, mask_pred_dev, bound_dev, n, rows, (uint32_t)fcz_dense_width(layout), (uint32_t)slot,
+                    o.rot, o.trans, o.rmsd, o.sites, o.gdt_counts, o.tm, o.dev},
+                   o.seed, o.selected, levels, iterations, nullptr, nullptr, nullptr, 0};
+    const uint32_t max_blocks = (uint32_t)ctx->n_cu * 16u;
+    // the seeds are counted on the device: at most this many items of WAVES_PER_BLOCK seeds, a double per seed
+    const uint64_t items = tm_items_bound(packed ? (uint64_t)rows : (uint64_t)n * rows, n);
+    uint64_t* counts = nullptr;
+    if (n) {
+        int rc = ctx->tm_scratch.ensure(sizeof(uint64_t) * (2 * (size_t)n + 1) + sizeof(double) * WAVES_PER_BLOCK * (size_t)items + sizeof(uint32_t) * (size_t)n);
+        if (rc) return rc;
+        counts = ctx->tm_scratch.as<uint64_t>();
+        g.item_off = counts + n;
+        g.score = reinterpret_cast<double*>(g.item_off + n + 1); g.score_cap = WAVES_PER_BLOCK * items;
+        g.nsites = reinterpret_cast<uint32_t*>(g.score + g.score_cap);
+    }
+    span_guard sg(ctx, "tmscore");
+    if (fill)
+        hipLaunchKernelGGL(k_superpose_fill, dim3((uint32_t)std::min<uint64_t>(((uint64_t)rows + BLOCK - 1) / BLOCK, max_blocks)), dim3(BLOCK), 0, ctx->stream, g.s);
+    if (n) {
+        const dim3 chains(std::min(grid_for(n, WAVES_PER_BLOCK), max_blocks)), search((uint32_t)std::min<uint64_t>(items, max_blocks));
+        if (packed) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tm_count<true>), chains, dim3(BLOCK), 0, ctx->stream, g, counts);
+        else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tm_count<false>), chains, dim3(BLOCK), 0, ctx->stream, g, counts);
+        int rc = device_scan<uint64_t>(ctx, counts, g.item_off, n); if (rc) return rc;
+        if (packed) {
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tm_search<true>), search, dim3(BLOCK), 0, ctx->stream, g);
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tm_final<true>), chains, dim3(BLOCK), 0, ctx->stream, g);
+        } else {
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tm_search<false>), search, dim3(BLOCK), 0, ctx->stream, g);
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tm_final<false>), chains, dim3(BLOCK), 0, ctx->stream, g);
+        }
+    }
+    HIP_TRY(hipGetLastError());
+    return FCZ_OK;
+}
+
+int fcz_tmscore_dev(fcz_ctx* ctx, const float* pos_true_dev, const uint8_t* mask_true_dev, const float* pos_pred_dev, const uint8_t* mask_pred_dev,
+                    const uint32_t* length_dev, uint32_t n, uint32_t L, int layout, int slot, uint32_t levels, uint32_t iterations, const fcz_tmscore_out* out_dev) {
+    if (!tmscore_args_ok(ctx, pos_true_dev, mask_true_dev, pos_pred_dev, layout, slot, L, iterations, out_dev) || L == 0) return FCZ_E_INVALID_ARG;
+    return tmscore_rows(ctx, pos_true_dev, mask_true_dev, pos_pred_dev, mask_pred_dev, length_dev, false, n, L, layout, slot, levels, iterations, *out_dev);
+}
+
+int fcz_tmscore_packed_dev(fcz_ctx* ctx, const float* pos_true_dev, const uint8_t* mask_true_dev, const float* pos_pred_dev, const uint8_t* mask_pred_dev,
+                           const uint32_t* row_off_dev, uint32_t n, uint32_t R, int layout, int slot, uint32_t levels, uint32_t iterations,
+                           const fcz_tmscore_out* out_dev) {
+    if (!tmscore_args_ok(ctx, pos_true_dev, mask_true_dev, pos_pred_dev, layout, slot, R, iterations, out_dev) || (n && !row_off_dev)) return FCZ_E_INVALID_ARG;
+    return tmscore_rows(ctx, pos_true_dev, mask_true_dev, pos_pred_dev, mask_pred_dev, row_off_dev, true, n, R, layout, slot, levels, iterations, *out_dev);
+}
+
+// fcz_tmscore and fcz_tmscore_packed: SUPERPOSE_OUT 10 .. 16, TM_SEED, TM_SELECTED
+static int tmscore_host(fcz_ctx* ctx, const float* pos_true, const uint8_t* mask_true, const float* pos_pred, const uint8_t* mask_pred, const uint32_t* bound,
+                        bool packed, uint32_t n, uint32_t rows_per, int layout, int slot, uint32_t levels, uint32_t iterations, const fcz_tmscore_out& out) {
+    const size_t rows = packed ? (size_t)rows_per : (size_t)n * rows_per;
+    void* host[9] = {out.rot, out.trans, out.rmsd, out.sites, out.gdt_counts, out.tm, out.dev, out.seed, out.selected};
+    const size_t bytes[9] = {36 * (size_t)n, 12 * (size_t)n, 4 * (size_t)n, 4 * (size_t)n, 20 * (size_t)n, 4 * (size_t)n, 4 * rows, 4 * (size_t)n, 4 * (size_t)n};
+    const int slots[9] = {SUPERPOSE_OUT, SUPERPOSE_OUT + 1, SUPERPOSE_OUT + 2, SUPERPOSE_OUT + 3, SUPERPOSE_OUT + 4, SUPERPOSE_OUT + 5, SUPERPOSE_OUT + 6, TM_SEED, TM_SELECTED};
+    return superpose_staged(ctx, pos_true, mask_true, pos_pred, mask_pred, bound, packed, n, rows_per, layout, 9, host, bytes, slots,
+                            [&](const float* pt, const uint8_t* mt, const float* pp, const uint8_t* mp, const uint32_t* bd, void** d) {
+        const fcz_tmscore_out o{(float*)d[0], (float*)d[1], (float*)d[2], (int32_t*)d[3], (int32_t*)d[4], (float*)d[5], (float*)d[6], (int32_t*)d[7], (int32_t*)d[8]};
+        return tmscore_rows(ctx, pt, mt, pp, mp, bd, packed, n, rows_per, layout, slot, levels, iterations, o);
+    });
+}
+
+int fcz_tmscore(fcz_ctx* ctx, const float* pos_true, const uint8_t* mask_true, const float* pos_pred, const uint8_t* mask_pred, const uint32_t* length,
+                uint32_t n, uint32_t L, int layout, int slot, uint32_t levels, uint32_t iterations, const fcz_tmscore_out* out) {
+    if (!tmscore_args_ok(ctx, pos_true, mask_true, pos_pred, layout, slot, L, iterations, out) || L == 0) return FCZ_E_INVALID_ARG;
+    return tmscore_host(ctx, pos_true, mask_true, pos_pred, mask_pred, length, false, n, L, layout, slot, levels, iterations, *out);
+}
+
+int fcz_tmscore_packed(fcz_ctx* ctx, const float* pos_true, const uint8_t* mask_true, const float* pos_pred, const uint8_t* mask_pred, const uint32_t* row_off,
+                       uint32_t n, uint32_t R, int layout, int slot, uint32_t levels, uint32_t iterations, const fcz_tmscore_out* out) {
+    if (!tmscore_args_ok(ctx, pos_true, mask_true, pos_pred, layout, slot, R, iterations, out) || (n && !row_off)) return FCZ_E_INVALID_ARG;
+    return tmscore_host(ctx, pos_true, mask_true, pos_pred, mask_pred, row_off, true, n, R, layout, slot, levels, iterations, *out);
 }
 
 // ------------------------------------------------------------------------------------------------

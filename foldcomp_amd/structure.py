@@ -980,6 +980,11 @@ class CSuperposeOut(ctypes.Structure):
                 ("gdt_counts", ctypes.c_void_p), ("tm", ctypes.c_void_p), ("dev", ctypes.c_void_p)]
 
 
+class CTmScoreOut(ctypes.Structure):
+    """fcz_tmscore_out (include/fcz_hip.h): fcz_superpose_out's seven arrays, then seed and selected; all but rot and trans may be None"""
+    _fields_ = CSuperposeOut._fields_ + [("seed", ctypes.c_void_p), ("selected", ctypes.c_void_p)]
+
+
 class CDenseIn(ctypes.Structure):
     """fcz_dense_in (include/fcz_hip.h): dense tensors + per-chain header fields handed to the undense / compress_dense calls"""
     _fields_ = [("pos", ctypes.c_void_p), ("mask", ctypes.c_void_p), ("aatype", ctypes.c_void_p), ("length", ctypes.c_void_p),

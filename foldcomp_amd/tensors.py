@@ -17,6 +17,8 @@
     superpose(pred, true, atom="CA", apply=False) -> dict(rot [n, 3, 3], trans [n, 3], rmsd [n], sites [n], dev [..], gdt_counts [n, 5],
                                    gdt_ts, gdt_ha, tm [n]): the least-squares superposition of every chain of pred onto true;
                                    apply=True adds pos_aligned; apply_transform(pos, rot, trans, batch) is that step alone
+    tm_score(pred, true, atom="CA", apply=False, iterations=20, levels=None) -> the same dict at the superposition that MAXIMISES the
+                                   TM-score over a seeded iterative search, plus seed [n] and selected [n]
     backbone_hbonds(either dict, or the tensors as keywords) -> dict(hbond_acc_index, hbond_acc_energy, hbond_don_index, hbond_don_energy
                                    [.., 2]): DSSP's four H-bond columns, the two best acceptors and donors of every residue
     secondary_structure(either dict, or the tensors as keywords) -> dict(ss [..] uint8, ss_mask [..] bool, the four tables): the DSSP
@@ -45,9 +47,9 @@ import numpy as np
 from . import _lib, api, fczfile
 from ._aa_tables import RES1
 from .codec import ANGLE_COLUMNS, Codec, dense_layout
-from .structure import CAtomsOut, CDenseIn, CDenseOut, CPackedOut, CSuperposeOut
+from .structure import CAtomsOut, CDenseIn, CDenseOut, CPackedOut, CSuperposeOut, CTmScoreOut
 
-__all__ = ["decode_tensors", "encode_tensors", "decode_angles", "crop_starts", "neighbor_graph", "rigid_frames", "lddt", "superpose", "apply_transform",
+__all__ = ["decode_tensors", "encode_tensors", "decode_angles", "crop_starts", "neighbor_graph", "rigid_frames", "lddt", "superpose", "tm_score", "apply_transform",
            "backbone_hbonds", "secondary_structure", "solvent_accessibility"]
 
 
@@ -676,6 +678,32 @@ def superpose(pred, true, *, atom="CA", apply: bool = False, codec: Optional[Cod
     apply=True adds pos_aligned, pred's pos moved onto true (apply_transform), enqueued behind the solve with no host round trip.
     It is NOT differentiable. The tensors must be contiguous and lie on the codec's device; ordering against torch is
     decode_tensors'. atom and shapes that differ are checked first, without torch or a device (api.check_superpose)."""
+    return _superpose(pred, true, atom, apply, codec, "superpose", None)
+
+
+def tm_score(pred, true, *, atom="CA", apply: bool = False, iterations: int = 20, levels=None, codec: Optional[Codec] = None) -> dict:
+    """predicted coordinates against true ones, both dense tensors on the GPU -> per chain the superposition of `pred` onto `true`
+    that MAXIMISES the TM-score over a seeded iterative search, the number TM-score programs report, and the scores at it.
+
+    superpose's `tm` is the TM-score at the least-squares fit, a lower bound: one domain placed right and one swung about a hinge
+    spread their error over both. Here every chain is searched from fragments of its sites (the whole chain, halves, quarters, ..
+    down to four sites, at half-length steps: 480 seeds for 350 sites); a seed is superposed on its fragment, then up to
+    `iterations` times on the sites that lie within a cut of d0 +- 1 A (clamped to 4.5 .. 8 A) of the target, until that set repeats;
+    the (seed, round) of the largest TM wins, of equal ones the lowest seed and the earliest round. The definition, deterministic
+    to the bit, is fcz_tmscore_dev's in include/fcz_hip.h; the inputs, the site rule and `atom` are superpose's. Per chain:
+        rot, trans, rmsd, sites, dev, gdt_counts, gdt_ts, gdt_ha   as superpose returns them, at the winning superposition
+        tm [n] float32          the maximised TM-score, normalised by the sites; >= superpose's tm
+        seed [n] int32          the number of the winning seed (0: the whole chain)
+        selected [n] int32      the sites the winning fit was made on
+    levels=k keeps only the first k fragment lengths (None: all); levels=1, iterations=0 is superpose, bit for bit. GDT is NOT
+    maximised: gdt_counts are the counts at the TM-maximising superposition. apply=True adds pos_aligned as in superpose.
+    It is NOT differentiable. Cost: the seeds times a handful of superpositions per chain, where superpose does one.
+    atom, shapes, iterations and levels are checked first, without torch or a device (api.check_tm_score)."""
+    return _superpose(pred, true, atom, apply, codec, "tm_score", (iterations, levels))
+
+
+def _superpose(pred, true, atom, apply, codec, what, search):
+    """superpose (search None) and tm_score (search = (iterations, levels)): the shared checks, outputs and apply step"""
     t = dict(true) if isinstance(true, dict) else {"pos": true}
     p = dict(pred) if isinstance(pred, dict) else {"pos": pred}
     pos = t.get("pos")
@@ -684,47 +712,62 @@ def superpose(pred, true, *, atom="CA", apply: bool = False, codec: Optional[Cod
     for name, d, keys in (("true", t, ("pos", "mask")), ("pred", p, ("pos",))):
         for key in keys:
             if d.get(key) is None:
-                raise TypeError(f"superpose needs the tensor {key!r} of {name}")
+                raise TypeError(f"{what} needs the tensor {key!r} of {name}")
     ppos, pmask = p["pos"], p.get("mask")
-    slot = api.check_superpose(atom, shape, getattr(ppos, "shape", ()), None if pmask is None else getattr(pmask, "shape", ()))
+    pshape, mshape = getattr(ppos, "shape", ()), None if pmask is None else getattr(pmask, "shape", ())
+    if search is None:
+        slot = api.check_superpose(atom, shape, pshape, mshape)
+    else:
+        slot, iterations, levels = api.check_tm_score(atom, shape, pshape, mshape, *search)
     c = codec or api.default_codec()
     try:
         import torch
     except ImportError as e:
-        raise api.error(f"superpose needs PyTorch (ROCm build): {e}") from None
+        raise api.error(f"{what} needs PyTorch (ROCm build): {e}") from None
     if not isinstance(pos, torch.Tensor):
-        raise api.error("superpose takes torch tensors on the GPU (numpy arrays: Codec.superpose)")
+        raise api.error(f"{what} takes torch tensors on the GPU (numpy arrays: Codec.{what})")
     if pos.device.type != "cuda" or pos.device.index != int(c.device):
-        raise api.error(f"superpose: pos lies on {pos.device}, the codec works on cuda:{int(c.device)}; there is no CPU path")
+        raise api.error(f"{what}: pos lies on {pos.device}, the codec works on cuda:{int(c.device)}; there is no CPU path")
     dev = pos.device
     if len(shape) != (3 if is_packed else 4) or shape[-1] != 3 or pos.dtype != torch.float32:
         raise ValueError(f"pos must be float32 [n, L, A, 3], or [R, A, 3] beside cu_seqlens, not {pos.dtype} {shape}")
     lay = dense_layout(_WIDTH_LAYOUT[shape[-2]])
-    _on_device(torch, "superpose", dev, "pos", pos, shape, (torch.float32,))
-    mask = _on_device(torch, "superpose", dev, "mask", t["mask"], shape[:-1], (torch.bool, torch.uint8)).view(torch.uint8)
-    _on_device(torch, "superpose", dev, "pred pos", ppos, shape, (torch.float32,))
+    _on_device(torch, what, dev, "pos", pos, shape, (torch.float32,))
+    mask = _on_device(torch, what, dev, "mask", t["mask"], shape[:-1], (torch.bool, torch.uint8)).view(torch.uint8)
+    _on_device(torch, what, dev, "pred pos", ppos, shape, (torch.float32,))
     if pmask is not None:
-        pmask = _on_device(torch, "superpose", dev, "pred mask", pmask, shape[:-1], (torch.bool, torch.uint8)).view(torch.uint8)
-    n, rows, bound = _chain_bound(torch, "superpose", dev, t, shape, is_packed)
+        pmask = _on_device(torch, what, dev, "pred mask", pmask, shape[:-1], (torch.bool, torch.uint8)).view(torch.uint8)
+    n, rows, bound = _chain_bound(torch, what, dev, t, shape, is_packed)
     if rows > 2 ** 31 - 1:
         raise ValueError("sites must fit int32: at most 2^31 - 1 rows per chain")
     out = dict(rot=torch.empty((n, 3, 3), dtype=torch.float32, device=dev), trans=torch.empty((n, 3), dtype=torch.float32, device=dev),
                rmsd=torch.empty((n,), dtype=torch.float32, device=dev), sites=torch.empty((n,), dtype=torch.int32, device=dev),
                dev=torch.zeros(shape[:-2], dtype=torch.float32, device=dev), gdt_counts=torch.empty((n, 5), dtype=torch.int32, device=dev),
                tm=torch.empty((n,), dtype=torch.float32, device=dev))
+    keys = ("rot", "trans", "rmsd", "sites", "gdt_counts", "tm", "dev")
+    if search is not None:
+        out.update(seed=torch.empty((n,), dtype=torch.int32, device=dev), selected=torch.empty((n,), dtype=torch.int32, device=dev))
+        keys += ("seed", "selected")
     if apply:
         out["pos_aligned"] = torch.empty_like(ppos)
     solve = bool(n and rows)
     if n and not solve:                                                       # chains of no rows: what a chain without sites gets
         out["rot"].copy_(torch.eye(3, device=dev).expand(n, 3, 3))
-        for k in ("trans", "rmsd", "sites", "gdt_counts", "tm"):
-            out[k].zero_()
+        for k in keys:
+            if k not in ("rot", "dev"):
+                out[k].zero_()
     torch.cuda.current_stream(dev).synchronize()
     if solve:
-        s = CSuperposeOut(*(out[k].data_ptr() for k in ("rot", "trans", "rmsd", "sites", "gdt_counts", "tm", "dev")))
-        fn, name = (c.lib.fcz_superpose_packed_dev, "fcz_superpose_packed_dev") if is_packed else (c.lib.fcz_superpose_dev, "fcz_superpose_dev")
-        _lib.check(fn(c.ctx, pos.data_ptr(), mask.data_ptr(), ppos.data_ptr(), None if pmask is None else pmask.data_ptr(),
-                      None if bound is None else bound.data_ptr(), n, rows, lay, slot, ctypes.byref(s)), name)
+        args = (c.ctx, pos.data_ptr(), mask.data_ptr(), ppos.data_ptr(), None if pmask is None else pmask.data_ptr(), None if bound is None else bound.data_ptr(),
+                n, rows, lay, slot)
+        if search is None:
+            s = CSuperposeOut(*(out[k].data_ptr() for k in keys))
+            fn, name = (c.lib.fcz_superpose_packed_dev, "fcz_superpose_packed_dev") if is_packed else (c.lib.fcz_superpose_dev, "fcz_superpose_dev")
+            _lib.check(fn(*args, ctypes.byref(s)), name)
+        else:
+            s = CTmScoreOut(*(out[k].data_ptr() for k in keys))
+            fn, name = (c.lib.fcz_tmscore_packed_dev, "fcz_tmscore_packed_dev") if is_packed else (c.lib.fcz_tmscore_dev, "fcz_tmscore_dev")
+            _lib.check(fn(*args, levels, iterations, ctypes.byref(s)), name)
     if apply:
         _apply_transform(c, ppos, pmask, out["rot"], out["trans"], n, rows, bound, is_packed, lay, out["pos_aligned"])
     c.synchronize()

@@ -23,6 +23,7 @@
  *   (none: no solvent accessibility)                       fcz_sasa_dev / fcz_sasa_packed_dev, fcz_sasa / fcz_sasa_packed
  *   (none: `rmsd` compares two files unsuperposed)         fcz_superpose_dev / fcz_superpose_packed_dev, fcz_superpose_apply_dev /
  *                                                          fcz_superpose_apply_packed_dev and their host forms
+ *   (none: no TM-score)                                    fcz_tmscore_dev / fcz_tmscore_packed_dev and their host forms
  *   (none: no rigid frames of the decoded chain)           fcz_frames_dev / fcz_frames
  *   Foldcomp::decompress, the dequantisation :784-804     fcz_angles_dev / fcz_angles_packed_dev, fcz_decompress_angles[_packed],
  *                                                          fcz_angles_window_dev / fcz_decompress_angles_window
@@ -666,6 +667,70 @@ int fcz_superpose_apply(fcz_ctx* ctx, const float* pos, const uint8_t* mask, con
 int fcz_superpose_apply_packed(fcz_ctx* ctx, const float* pos, const uint8_t* mask, const uint32_t* row_off, uint32_t n, uint32_t R,
                                int layout, const float* rot, const float* trans, float* pos_out);
 
+/* ---- maximised TM-score: seeded iterative superposition of two dense tensor batches ------------------------ */
+/* fcz_superpose_dev's tm is the TM-score AT the least-squares superposition, a lower bound. TM-score programs report the maximum over
+ * superpositions, found by a search that is seeded with fragments and refined iteratively; these calls run that search per chain for
+ * a whole batch on the device and return the superposition it ends at. The reference has no such output. The inputs, the two forms
+ * (padded / packed), the layouts and slots, the site rule, d0(S), the float64 arithmetic (every operation rounded, no FMA) and the
+ * refusals are those of fcz_superpose_dev above. This is the definition; it is deterministic, so an implementation is checked
+ * against it, not against a TM-score program.
+ * Per chain with S sites, numbered 0 .. S - 1 in row order, and d_search = min(max(d0, 4.5), 8.0):
+ *   fragment lengths   l = S; while l > 4: take l, then l = l / 2 (rounded down); finally take min(S, 4). levels > 0 keeps only the
+ *                      first `levels` of these lengths (levels == 0: all).
+ *   seeds              for each length in that order the starts 0, step, 2 step, .. while start + l <= S, step = max(l / 2, 1), then
+ *                      the start S - l if it is not the last one already taken. The seeds are numbered in this order, so seed 0 is
+ *                      the whole chain; fcz_tmscore_seeds(S, levels) is their number (S = 350: 480). S = 0: no seed.
+ *   one seed           The selection starts as the fragment's sites. (1) Superpose the selection exactly as fcz_superpose_dev
+ *                      superposes all sites: centroids, centred cross sums, Horn's matrix by Jacobi sweeps, t = cb - R ca; a sum over
+ *                      the selection keeps that call's order BY CHAIN ROW (lane l adds rows l, l + 64, .., a row outside the
+ *                      selection adds nothing, then the xor-butterfly). (2) dev_j for all S sites. (3) tm = (1 / S) sum
+ *                      1 / (1 + (dev_j / d0)^2) over all S sites, in the same order. That is round 0. Then at most `iterations`
+ *                      further rounds: cut = d_search - 1 in round 1 and d_search + 1 in the later ones; the new selection is
+ *                      {j : dev_j < cut}, compared in float64, and while it holds fewer than min(3, S) sites, cut += 0.5 and select
+ *                      again (after 16 384 such steps, a deviation beyond 8 000 A, cut = +inf: every site); stop if the new selection
+ *                      equals the previous one, otherwise superpose on it and score as above.
+ *   the result         the (seed, round) with the largest float64 tm; of equal ones the lowest seed, then the earliest round.
+ * Outputs per chain: rot, trans, rmsd (over all S sites), sites, gdt_counts, tm as fcz_superpose_dev defines them, at that
+ * superposition; seed [n] int32, the winning seed's number, and selected [n] int32, the size of the winning selection; per row dev.
+ * Floats are rounded once from float64. S = 0: the identity, 0, every score 0, seed 0, selected 0. All but rot / trans may be NULL.
+ * Seed 0, round 0 is fcz_superpose_dev's fit: with levels = 1, iterations = 0 every shared output holds that call's bytes, and for any
+ * levels and iterations tm >= that call's tm, as float32 bits. The result depends on neither the launch geometry, the scratch nor
+ * the form: two calls, and padded against packed, give the same bytes. Work: about fcz_tmscore_seeds(S) seeds of a handful of
+ * superpositions each, where fcz_superpose_dev does one. Scratch in the ctx: a double per seed (at most 1.7 rows + 70 n + 4 of
+ * them, sized on the host from the rows alone), no transform per seed. That size bounds the seeds of chains that do NOT overlap. A packed row_off
+ * whose ranges overlap (fcz_superpose_packed_dev computes each such chain fully) may hold more seeds than the scratch: nothing is
+ * read or written outside it, but the seeds beyond it are left out, so for overlapping ranges -- and only for them -- a chain's result
+ * is the maximum over the seeds that fit (seed 0 alone when none does), and is then no longer independent of the scratch.
+ * Enqueued on the ctx stream, no synchronisation. FCZ_E_INVALID_ARG with nothing launched: what fcz_superpose_dev refuses, and iterations > 64. FCZ_E_NOMEM: no room for the scratch. The time goes to a group of its own, "tmscore". */
+typedef struct fcz_tmscore_out {
+    float*   rot;           /* [n][3][3] */
+    float*   trans;         /* [n][3] */
+    float*   rmsd;          /* [n] optional */
+    int32_t* sites;         /* [n] optional */
+    int32_t* gdt_counts;    /* [n][5] optional */
+    float*   tm;            /* [n] optional */
+    float*   dev;           /* [n][L] / [R] optional */
+    int32_t* seed;          /* [n] optional */
+    int32_t* selected;      /* [n] optional */
+} fcz_tmscore_out;
+uint64_t fcz_tmscore_seeds(uint32_t sites, uint32_t levels);   /* the seeds of a chain with that many sites; needs no device */
+/* what the output `seed` stands for: the first site and the number of sites of that seed's fragment; FCZ_E_INVALID_ARG for a seed
+ * the chain does not have. Needs no device. */
+int fcz_tmscore_seed_fragment(uint32_t sites, uint32_t levels, uint64_t seed, uint32_t* start, uint32_t* length);
+int fcz_tmscore_dev(fcz_ctx* ctx, const float* pos_true_dev, const uint8_t* mask_true_dev, const float* pos_pred_dev,
+                    const uint8_t* mask_pred_dev, const uint32_t* length_dev, uint32_t n, uint32_t L, int layout, int slot,
+                    uint32_t levels, uint32_t iterations, const fcz_tmscore_out* out_dev);
+int fcz_tmscore_packed_dev(fcz_ctx* ctx, const float* pos_true_dev, const uint8_t* mask_true_dev, const float* pos_pred_dev,
+                           const uint8_t* mask_pred_dev, const uint32_t* row_off_dev, uint32_t n, uint32_t R, int layout, int slot,
+                           uint32_t levels, uint32_t iterations, const fcz_tmscore_out* out_dev);
+/* Host-pointer conveniences: the same arrays on the host, staged through the ctx like fcz_superpose; synchronous. */
+int fcz_tmscore(fcz_ctx* ctx, const float* pos_true, const uint8_t* mask_true, const float* pos_pred, const uint8_t* mask_pred,
+                const uint32_t* length, uint32_t n, uint32_t L, int layout, int slot, uint32_t levels, uint32_t iterations,
+                const fcz_tmscore_out* out);
+int fcz_tmscore_packed(fcz_ctx* ctx, const float* pos_true, const uint8_t* mask_true, const float* pos_pred,
+                       const uint8_t* mask_pred, const uint32_t* row_off, uint32_t n, uint32_t R, int layout, int slot,
+                       uint32_t levels, uint32_t iterations, const fcz_tmscore_out* out);
+
 /* ---- torsion-angle tensors: the record's internal coordinates, no reconstruction ------------------------ */
 /* What Foldcomp::decompress dequantises before it places an atom (src/foldcomp.cpp:784-804: the backbone torsions and bond angles of
  * every packed word; :338-369 for the side-chain torsion bytes) and the FCZ branch of foldcomp.cxx's get_data returns as Python lists
@@ -1021,7 +1086,7 @@ int fcz_check(const uint8_t* entry, uint64_t len);
  * group since the last reset: "compress_sizes", "compress_index", "compress_angles", "compress_pack",
  * "decompress_sizes", "decompress_backbone", "decompress_index", "decompress_sidechain", "pdb_sizes", "pdb_format", "extract_sizes", "extract",
  * "ingest_parse", "ingest_parse_cif", "ingest_rows_cif", "ingest_frags", "ingest_fill", "inflate", "dense", "undense" (the counting and the fill
- * kernel of fcz_undense_dev: two launches per call), "angles" (fcz_angles_dev), "knn" (fcz_knn_dev and fcz_knn_packed_dev), "lddt" (fcz_lddt_dev and fcz_lddt_packed_dev), "superpose" (fcz_superpose_dev, fcz_superpose_apply_dev and their packed forms), "frames" (fcz_frames_dev). Every other packed or windowed entry point is timed under the
+ * kernel of fcz_undense_dev: two launches per call), "angles" (fcz_angles_dev), "knn" (fcz_knn_dev and fcz_knn_packed_dev), "lddt" (fcz_lddt_dev and fcz_lddt_packed_dev), "superpose" (fcz_superpose_dev, fcz_superpose_apply_dev and their packed forms), "tmscore" (fcz_tmscore_dev and fcz_tmscore_packed_dev), "frames" (fcz_frames_dev). Every other packed or windowed entry point is timed under the
  * group of its padded form: fcz_dense_packed_dev and fcz_dense_window_dev under "dense", fcz_undense_packed_dev under "undense",
  * fcz_angles_packed_dev and fcz_angles_window_dev under "angles". */
 int  fcz_ctx_enable_timing(fcz_ctx* ctx, int enable);

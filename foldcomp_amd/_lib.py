@@ -9,7 +9,7 @@ from __future__ import annotations
 import ctypes
 import os
 
-from .structure import CAtomsOut, CChainBatch, CDenseIn, CDenseOut, CEntryInfo, CIngestResult, CPackedOut, CSuperposeOut, CTmScoreOut
+from .structure import CAtomsOut, CChainBatch, CDenseIn, CDenseOut, CEntryInfo, CIngestResult, CPackedOut, CSuperposeOut, CTmScoreOut, CViolationsOut
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # FCZ_HIP_LIB selects another build of the same library (A/B timing of kernel variants); it is still a HIP build
@@ -103,6 +103,11 @@ def load():
         "fcz_sasa_packed_dev": (i32, [vp, vp, vp, vp, vp, u32, u32, i32, vp, f32, vp, u32, vp, vp, vp]),
         "fcz_sasa": (i32, [vp, vp, vp, vp, vp, u32, u32, i32, vp, f32, vp, u32, vp, vp, vp]),
         "fcz_sasa_packed": (i32, [vp, vp, vp, vp, vp, u32, u32, i32, vp, f32, vp, u32, vp, vp, vp]),
+        "fcz_violations_pass": (i32, []),
+        "fcz_violations_dev": (i32, [vp, vp, vp, vp, vp, u32, u32, i32, vp, f32, f32, ctypes.POINTER(CViolationsOut)]),
+        "fcz_violations_packed_dev": (i32, [vp, vp, vp, vp, vp, u32, u32, i32, vp, f32, f32, ctypes.POINTER(CViolationsOut)]),
+        "fcz_violations": (i32, [vp, vp, vp, vp, vp, u32, u32, i32, vp, f32, f32, ctypes.POINTER(CViolationsOut)]),
+        "fcz_violations_packed": (i32, [vp, vp, vp, vp, vp, u32, u32, i32, vp, f32, f32, ctypes.POINTER(CViolationsOut)]),
         "fcz_superpose_dev": (i32, [vp, vp, vp, vp, vp, vp, u32, u32, i32, i32, ctypes.POINTER(CSuperposeOut)]),
         "fcz_superpose_packed_dev": (i32, [vp, vp, vp, vp, vp, vp, u32, u32, i32, i32, ctypes.POINTER(CSuperposeOut)]),
         "fcz_superpose": (i32, [vp, vp, vp, vp, vp, vp, u32, u32, i32, i32, ctypes.POINTER(CSuperposeOut)]),
@@ -182,6 +187,7 @@ EXPORTS = ["fcz_ctx_create", "fcz_ctx_destroy", "fcz_ctx_stream", "fcz_ctx_synch
            "fcz_lddt_pass", "fcz_lddt_c2", "fcz_lddt_dev", "fcz_lddt_packed_dev", "fcz_lddt", "fcz_lddt_packed",
            "fcz_hbond_pass", "fcz_hbond_dev", "fcz_hbond_packed_dev", "fcz_dssp_labels_dev", "fcz_dssp_labels_packed_dev", "fcz_dssp", "fcz_dssp_packed",
            "fcz_sasa_pass", "fcz_sasa_default_radii", "fcz_sasa_dev", "fcz_sasa_packed_dev", "fcz_sasa", "fcz_sasa_packed",
+           "fcz_violations_pass", "fcz_violations_dev", "fcz_violations_packed_dev", "fcz_violations", "fcz_violations_packed",
            "fcz_superpose_dev", "fcz_superpose_packed_dev", "fcz_superpose", "fcz_superpose_packed",
            "fcz_superpose_apply_dev", "fcz_superpose_apply_packed_dev", "fcz_superpose_apply", "fcz_superpose_apply_packed",
            "fcz_tmscore_seeds", "fcz_tmscore_seed_fragment", "fcz_tmscore_dev", "fcz_tmscore_packed_dev", "fcz_tmscore", "fcz_tmscore_packed",

@@ -244,7 +244,7 @@ class FoldcompDatabase:
                        sort_by_length: bool = False, packed: bool = False, max_residues: Optional[int] = None,
                        angles: bool = False, crop: Optional[str] = None, seed: Optional[int] = None,
                        neighbors: Optional[int] = None, neighbor_atom="CA", frames: Optional[str] = None,
-                       secondary_structure: bool = False, sasa: bool = False):
+                       secondary_structure: bool = False, sasa: bool = False, violations: bool = False):
         """Generator over the database (its `ids` selection when it has one) in batches of dense model-input tensors on the GPU:
         the dicts of foldcomp_amd.tensors.decode_tensors, each with `names` (the records' titles) and `index` (int64 array: the
         entries' positions in this database, what db[i] takes). sort_by_length orders every window of 16 * batch_size entries by
@@ -260,10 +260,12 @@ class FoldcompDatabase:
         is read. frames="backbone" | "all" adds the rigid frames `rot` / `trans` / `frame_mask` (decode_tensors(frames=...)), checked
         at the first next() too. secondary_structure=True adds the DSSP labels `ss` / `ss_mask` of every chain
         (decode_tensors(secondary_structure=True)). sasa=True adds the solvent accessibility `sasa` / `rsa` / `sasa_mask` of every
-        residue (decode_tensors(sasa=True))."""
+        residue (decode_tensors(sasa=True)). violations=True adds `clash_count` / `link_violation` / `viol_mask`, the steric clashes
+        and peptide-link violations of every residue (decode_tensors(violations=True))."""
         from .tensors import decode_tensors
         check_secondary_structure_flag(secondary_structure)
         check_sasa_flag(sasa)
+        check_violations_flag(violations)
         if frames is not None:
             check_frames(frames)
         if neighbors is not None:
@@ -288,7 +290,7 @@ class FoldcompDatabase:
                 if packed:
                     d = decode_tensors([ents[k] for k in sel], layout=layout, device=device, packed=True, angles=angles,
                                        neighbors=neighbors, neighbor_atom=neighbor_atom, frames=frames, secondary_structure=secondary_structure,
-                                       sasa=sasa)
+                                       sasa=sasa, violations=violations)
                 else:
                     if crop == "random" and gen is None:
                         import torch
@@ -296,7 +298,7 @@ class FoldcompDatabase:
                         gen.manual_seed(int(seed)) if seed is not None else gen.seed()
                     d = decode_tensors([ents[k] for k in sel], layout=layout, max_len=max_len, device=device, angles=angles, crop=crop,
                                        generator=gen, neighbors=neighbors, neighbor_atom=neighbor_atom, frames=frames,
-                                       secondary_structure=secondary_structure, sasa=sasa)
+                                       secondary_structure=secondary_structure, sasa=sasa, violations=violations)
                 d["index"] = idx[sel]
                 yield d
 
@@ -523,6 +525,52 @@ def check_sasa(what, d, probe=SASA_PROBE, n_points=SASA_POINTS, points=None, rad
         if not ((R >= 0.5) & (R < 8.0)).all():
             raise ValueError("every non-zero radius plus the probe must lie in [0.5, 8)")
     return shape, packed, points, table
+
+
+# Structural violations (include/fcz_hip.h, fcz_violations_dev): the outputs of a call as (key, dtype, trailing shape; "A" = the layout
+# width, "n4" = per chain), in the order of fcz_violations_out
+VIOLATION_TOLERANCE = 1.5
+VIOLATION_LINK_FACTOR = 12.0
+VIOLATION_OUTPUTS = (("clash_atom", "uint8", "A"), ("clash_count", "int32", ()), ("clash_depth", "float32", ()), ("clash_partner", "int32", ()),
+                     ("viol_mask", "bool", ()), ("link_mask", "bool", ()), ("link_length", "float32", ()), ("link_cos", "float32", (2,)),
+                     ("link_violation", "uint8", ()), ("chain_counts", "int64", "n4"))
+VIOLATION_BATCH_KEYS = ("clash_count", "link_violation", "viol_mask")      # what violations=True adds to a decoded batch
+
+
+def check_violations_flag(flag):
+    """violations= of decode_tensors / tensor_batches is a switch"""
+    if not isinstance(flag, (bool, np.bool_)):
+        raise ValueError(f"violations must be True or False, not {flag!r}")
+
+
+def check_violations(what, d, tolerance=VIOLATION_TOLERANCE, link_factor=VIOLATION_LINK_FACTOR, radii="bondi"):
+    """the argument rules of violations that need no torch and no GPU, on the dict `d` of tensors or arrays -> (shape of pos, packed,
+    radii float32 [21, A] or None for the library's default): check_dssp's rules for pos, mask and aatype; atom14 needs aatype (a
+    slot's atom depends on the type there); tolerance and link_factor finite and not negative (as float32); every non-zero radius
+    in [0.5, 8)"""
+    shape, packed = check_dssp(what, d)
+    A = shape[-2]
+    if A == 14 and d.get("aatype") is None:
+        raise ValueError(f"{what}: atom14 needs aatype (which atom a slot holds depends on the residue type)")
+    for name, v in (("tolerance", tolerance), ("link_factor", link_factor)):
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)):
+            raise ValueError(f"{name} must be a number, not {v!r}")
+        with np.errstate(over="ignore"):
+            v32 = np.float32(v)
+        if not np.isfinite(v32) or v32 < 0:
+            raise ValueError(f"{name} must be finite and not negative (as float32), not {v!r}")
+    if isinstance(radii, str):
+        if radii != "bondi":
+            raise ValueError(f"radii must be 'bondi' or an array [21, {A}], not {radii!r}")
+        table = None
+    else:
+        table = np.ascontiguousarray(np.asarray(radii), np.float32)
+        if table.shape != (21, A):
+            raise ValueError(f"radii must have the shape (21, {A}), not {table.shape}")
+        R = table[table != 0]
+        if not ((R >= 0.5) & (R < 8.0)).all():
+            raise ValueError("every non-zero radius must lie in [0.5, 8)")
+    return shape, packed, table
 
 
 # the rigid groups of groups="all", indexed like AlphaFold / OpenFold rigidgroups_gt_frames (include/fcz_hip.h, fcz_frames_dev)

@@ -366,6 +366,49 @@ class Codec:
             out["rsa"][ok] = out["sasa"][ok] / mx[ok]
         return out
 
+    def violations(self, pos: np.ndarray, mask: np.ndarray, aatype=None, length=None, row_off=None, *, tolerance: float = 1.5,
+                   link_factor: float = 12.0, radii="bondi"):
+        """dense arrays on the host -> the steric clashes and peptide-link violations of every chain (fcz_violations, or
+        fcz_violations_packed when row_off is given): clash_atom uint8 [.., A], clash_count int32, clash_depth float32, clash_partner
+        int32 (-1 = none), viol_mask bool, link_mask bool, link_length float32, link_cos float32 [.., 2], link_violation uint8 (three
+        bits) per row [n, L] / [R], and chain_counts int64 [n, 4]. pos float32 [n, L, A, 3] with mask [n, L, A], aatype [n, L] uint8
+        (needed for atom14) and optionally length [n]; or pos [R, A, 3], mask [R, A], aatype [R], row_off [n + 1]. tolerance,
+        link_factor and radii are foldcomp.violations'. Reproducible bit for bit, not differentiable."""
+        from . import api
+        from .structure import CViolationsOut
+        pos = np.ascontiguousarray(pos, np.float32)
+        packed = row_off is not None
+        if pos.ndim != (3 if packed else 4) or pos.shape[-1] != 3 or pos.shape[-2] not in (37, 14, 4):
+            raise ValueError(f"pos must be float32 {'[R, A, 3]' if packed else '[n, L, A, 3]'} with A = 37, 14 or 4, not {pos.shape}")
+        lay = {37: 0, 14: 1, 4: 2}[pos.shape[-2]]
+        mask = np.ascontiguousarray(mask)
+        if mask.shape != pos.shape[:-1] or mask.dtype not in (np.bool_, np.uint8):
+            raise ValueError(f"mask must be bool / uint8 {pos.shape[:-1]}, not {mask.dtype} {mask.shape}")
+        lead = pos.shape[:-2]
+        if aatype is not None:
+            aatype = np.ascontiguousarray(aatype)
+            if aatype.shape != lead or aatype.dtype != np.uint8:
+                raise ValueError(f"aatype must be uint8 {lead}, not {aatype.dtype} {aatype.shape}")
+        d = dict(pos=pos, mask=mask, aatype=aatype)
+        if packed:
+            d["cu_seqlens"] = row_off
+        _, _, table = api.check_violations("Codec.violations", d, tolerance, link_factor, radii)
+        n, rows, bound = self._chain_rows(pos, packed, length, row_off)
+        out = {}
+        for key, dt, tail in api.VIOLATION_OUTPUTS:
+            shape = (n, 4) if tail == "n4" else lead + ((pos.shape[-2],) if tail == "A" else tail)
+            out[key] = np.full(shape, -1, np.int32) if key == "clash_partner" else np.zeros(shape, np.uint8 if dt == "bool" else dt)
+        if out["clash_count"].size:
+            fn = self.lib.fcz_violations_packed if packed else self.lib.fcz_violations
+            c_out = CViolationsOut(*(out[key].ctypes.data for key, _, _ in api.VIOLATION_OUTPUTS))
+            _lib.check(fn(self.ctx, pos.ctypes.data, mask.ctypes.data, None if aatype is None else aatype.ctypes.data,
+                          None if bound is None else bound.ctypes.data, n, rows, lay, None if table is None else table.ctypes.data, float(tolerance),
+                          float(link_factor), ctypes.byref(c_out)), "fcz_violations_packed" if packed else "fcz_violations")
+        for key, dt, _ in api.VIOLATION_OUTPUTS:
+            if dt == "bool":
+                out[key] = out[key].view(np.bool_)
+        return out
+
     @staticmethod
     def _chain_rows(pos, packed, length, row_off):
         """the chains of dense host arrays -> (n, rows, bound): row_off [n + 1] over the R rows, or length [n] / None over L"""

@@ -37,6 +37,7 @@
 #include "fcz_lddt.h"
 #include "fcz_dssp.h"
 #include "fcz_sasa.h"
+#include "fcz_violations.h"
 #include "fcz_superpose.h"
 #include "fcz_tmscore.h"
 #include "fcz_frames.h"
@@ -95,12 +96,14 @@ struct timed_span { std::string name; hipEvent_t a, b; };
 // (C + 1 u64 offsets, the bytes, C i32 status); LDDT_PRED: pos and mask of the second tensor batch of fcz_lddt, LDDT_OUT: score, pairs, hits;
 // DSSP_OUT: acc_index, acc_energy, don_index, don_energy, ss, ss_mask of fcz_dssp; SASA_POINTS: the directions of fcz_sasa, SASA_OUT: sasa_points, sasa, sasa_mask;
 // SUPERPOSE_OUT: the seven arrays of a fcz_superpose_out in the struct's order; APPLY_ROT, APPLY_TRANS, APPLY_OUT: the transforms and the moved
-// coordinates of fcz_superpose_apply (its pos and mask go through LDDT_PRED); TM_SEED, TM_SELECTED: the two arrays a fcz_tmscore_out adds to those seven
+// coordinates of fcz_superpose_apply (its pos and mask go through LDDT_PRED); TM_SEED, TM_SELECTED: the two arrays a fcz_tmscore_out adds to those seven;
+// VIOL_OUT .. VIOL_OUT_LAST: the ten arrays of a fcz_violations_out in the struct's order
 enum { REC_BLOB, REC_OFF, REC_RES_OFF, REC_ATOM_OFF, REC_X, REC_Y, REC_Z, REC_BFAC, REC_RES_CODE, REC_ATOM_CODE,
        FILES_TEXT = 0, FILES_OFF, FILES_NAMES, FILES_NAME_OFF, FILES_STEM_LEN, BATCH_IN = 0, DENSE_IN = 0, LDDT_PRED = 4, DENSE_OUT = 10, LDDT_OUT = 10, SUPERPOSE_OUT = 10, DSSP_OUT = 10,
        SASA_POINTS = 4, SASA_OUT = 10,
        APPLY_ROT = 10, APPLY_TRANS, APPLY_OUT,
-       PACKED_OUT = 10, ANGLES_OUT = 10, KEPT_OFF = 13, KEPT_BYTES, KEPT_STATUS, PACKED_OUT_LAST, WINDOW_START = PACKED_OUT_LAST, TM_SEED, TM_SELECTED, POOL_COUNT };
+       PACKED_OUT = 10, ANGLES_OUT = 10, KEPT_OFF = 13, KEPT_BYTES, KEPT_STATUS, PACKED_OUT_LAST, WINDOW_START = PACKED_OUT_LAST, TM_SEED, TM_SELECTED,
+       VIOL_OUT = 10, VIOL_OUT_LAST = 19, POOL_COUNT };
 
 // what the device reports to the host in the middle of a call: one pinned allocation, a member per reader
 struct pinned_words {
@@ -149,7 +152,7 @@ struct fcz_ctx {
     dev_buf res_sc;     // decompress: residue -> its side-chain torsion bytes, 3 x R dwords
     dev_buf sizes_res_off;   // decompress: the res_off of a batch call that has to run its own sizes pass (ensure_sizes)
     dev_buf selftest_out;    // fcz_selftest_math
-    dev_buf knn_tiles;       // fcz_knn_packed_dev, fcz_lddt_packed_dev, fcz_superpose_apply_packed_dev (chain_tile_scan), fcz_sasa_packed_dev (sasa_tiles): n u64 tile counts, then their n + 1 offsets
+    dev_buf knn_tiles;       // fcz_knn_packed_dev, fcz_lddt_packed_dev, fcz_superpose_apply_packed_dev (chain_tile_scan), fcz_sasa_packed_dev (sasa_tiles), fcz_violations_packed_dev (viol_tiles): n u64 tile counts, then their n + 1 offsets
     dev_buf tm_scratch;      // fcz_tmscore_dev / _packed_dev: n u64 item counts, their n + 1 offsets, a double per seed (tm_items_bound), n u32 site counts
     dev_buf dssp_flags;      // fcz_dssp_labels_dev / _packed_dev: a byte per row (k_dssp_flags -> k_dssp_labels)
     dev_buf fast_scratch;    // decompress, FCZ_NUMERICS_FAST: forward atoms of segments longer than one chunk
@@ -179,6 +182,7 @@ struct fcz_ctx {
     //   fcz_dssp / fcz_dssp_packed                  DENSE_IN 0 .. 3 (pos, mask, aatype, length / row_off), DSSP_OUT 10 .. 15 (the four tables, ss, ss_mask)
     //   fcz_frames                                  DENSE_IN 0 .. 3 (pos, mask, aatype, length), DENSE_OUT 10 .. 12 (rot, trans, frame_mask)
     //   fcz_sasa / fcz_sasa_packed                  DENSE_IN 0 .. 3 (pos, mask, aatype, length / row_off), SASA_POINTS 4, SASA_OUT 10 .. 12 (sasa_points, sasa, sasa_mask)
+    //   fcz_violations / fcz_violations_packed      DENSE_IN 0 .. 3 (pos, mask, aatype, length / row_off), VIOL_OUT 10 .. 19 (the arrays of fcz_violations_out)
     dev_buf pool[POOL_COUNT];
     // PDB text / extracted data: per-entry sizes (any call), offsets (n + 1 u64) and the text of the last fcz_decompress_pdb_begin,
     // which fcz_decompress_pdb_fetch reads: live until the next fcz_decompress_pdb_begin / _sizes or fcz_extract
@@ -2188,6 +2192,158 @@ int fcz_sasa_packed(fcz_ctx* ctx, const float* pos, const uint8_t* mask, const u
     if (!sasa_args_ok(ctx, pos, mask, aatype, layout, R, radius_table, probe, points, n_points, {sasa_points, sasa, sasa_mask}, &tab) || (n && !row_off))
         return FCZ_E_INVALID_ARG;
     return sasa_host(ctx, pos, mask, aatype, row_off, true, n, R, layout, tab, probe, points, n_points, sasa_points, sasa, sasa_mask);
+}
+
+// ------------------------------------------------------------------------------------------------
+// steric clashes and peptide-link violations of dense tensors (fcz_violations.h; no counterpart in the reference)
+// ------------------------------------------------------------------------------------------------
+int fcz_violations_pass(void) { return (int)VIOL_PASS; }
+
+static bool viol_out_ok(const fcz_violations_out* o) {
+    return o && o->clash_atom && o->clash_count && o->clash_depth && o->clash_partner && o->viol_mask && o->link_mask && o->link_length && o->link_cos &&
+           o->link_violation && o->chain_counts;
+}
+
+// rows: L (padded) or R (packed). Fills tab from radius_table (NULL: the default) when everything is acceptable.
+static bool viol_args_ok(const fcz_ctx* ctx, const float* pos, const uint8_t* mask, const uint8_t* aatype, int layout, uint32_t rows, const float* radius_table,
+                         float tolerance, float link_factor, const fcz_violations_out* out, sasa_table* tab) {
+    const int A = fcz_dense_width(layout);
+    if (!ctx || !pos || !mask || A <= 0 || rows > SASA_MAX_ROWS || !viol_out_ok(out)) return false;
+    if (!std::isfinite(tolerance) || tolerance < 0.0f || !std::isfinite(link_factor) || link_factor < 0.0f) return false;
+    if (layout == FCZ_DENSE_ATOM14 && !aatype) return false;                  // a slot's atom depends on the type there
+    memset(tab->radius, 0, sizeof tab->radius);
+    if (radius_table) memcpy(tab->radius, radius_table, sizeof(float) * SASA_TYPES * (size_t)A);
+    else if (fcz_sasa_default_radii(layout, tab->radius) != FCZ_OK) return false;
+    for (int i = 0; i < (int)SASA_TYPES * A; i++) {
+        const float r = tab->radius[i];
+        if (r == 0.0f) continue;                                              // no atom in this slot
+        if (!(r >= 0.5f && r < 8.0f)) return false;                           // (a NaN radius ends here)
+    }
+    return true;
+}
+
+// The query tiles of the clash sweep: chain_tiles with viol_tile_rows(A) rows a tile (fcz_violations.h), in the same scratch.
+struct viol_tiles {
+    uint64_t* tile_off = nullptr; uint32_t tile_rows = 0, tiles_per_entry = 0; uint64_t n_padded = 0, blocks = 0;
+    int reserve(fcz_ctx* ctx, bool packed, uint32_t n, uint32_t rows, uint32_t A) {
+        const uint32_t max_blocks = (uint32_t)ctx->n_cu * 12u;
+        tile_rows = viol_tile_rows(A);
+        tiles_per_entry = (uint32_t)(((uint64_t)rows + tile_rows - 1) / tile_rows);
+        if (packed) {
+            int rc = ctx->knn_tiles.ensure(sizeof(uint64_t) * (2 * (size_t)n + 1)); if (rc) return rc;
+            tile_off = ctx->knn_tiles.as<uint64_t>() + n;
+            tiles_per_entry = 0;
+            blocks = std::min<uint64_t>((uint64_t)rows / tile_rows + n, max_blocks);   // the tiles are counted on the device: at most this many
+        } else {
+            n_padded = (uint64_t)n * tiles_per_entry;
+            blocks = std::min<uint64_t>(n_padded, max_blocks);
+        }
+        return FCZ_OK;
+    }
+    int scan(fcz_ctx* ctx, const uint32_t* row_off_dev, uint32_t n, uint32_t R) {
+        const uint32_t max_blocks = (uint32_t)ctx->n_cu * 12u;
+        hipLaunchKernelGGL(k_viol_tiles, dim3(std::min(grid_for(n, BLOCK), max_blocks)), dim3(BLOCK), 0, ctx->stream, row_off_dev, n, R, tile_rows,
+                           ctx->knn_tiles.as<uint64_t>());
+        return device_scan<uint64_t>(ctx, ctx->knn_tiles.as<uint64_t>(), tile_off, n);
+    }
+};
+
+// fcz_violations_dev (bound_dev is length [n] or NULL, rows = L) and fcz_violations_packed_dev (bound_dev = row_off [n + 1], rows = R)
+static int viol_rows(fcz_ctx* ctx, const float* pos_dev, const uint8_t* mask_dev, const uint8_t* aatype_dev, const uint32_t* bound_dev, bool packed, uint32_t n,
+                     uint32_t rows, int layout, const sasa_table& tab, float tolerance, float link_factor, const fcz_violations_out& o) {
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (n == 0 && (rows == 0 || !packed)) return FCZ_OK;
+    viol_args g{};
+    g.pos = pos_dev; g.mask = mask_dev; g.aatype = aatype_dev; g.bound = bound_dev; g.n = n; g.L = rows;
+    g.A = (uint32_t)fcz_dense_width(layout);
+    g.n_slot = (uint32_t)fcz_dense_slot(layout, 0, fcz_atom_code_from_name("N")); g.ca_slot = (uint32_t)fcz_dense_slot(layout, 0, fcz_atom_code_from_name("CA"));
+    g.c_slot = (uint32_t)fcz_dense_slot(layout, 0, fcz_atom_code_from_name("C"));
+    g.sg_slot = fcz_dense_slot(layout, (int)VIOL_CYS, fcz_atom_code_from_name("SG"));   // (-1 in backbone4)
+    g.tolerance = tolerance; g.link_factor = link_factor;
+    g.clash_atom = o.clash_atom; g.clash_count = o.clash_count; g.clash_depth = o.clash_depth; g.clash_partner = o.clash_partner; g.viol_mask = o.viol_mask;
+    g.link_mask = o.link_mask; g.link_length = o.link_length; g.link_cos = o.link_cos; g.link_violation = o.link_violation;
+    g.chain_counts = reinterpret_cast<unsigned long long*>(o.chain_counts);
+    const uint32_t max_blocks = (uint32_t)ctx->n_cu * 12u;
+    viol_tiles vt;
+    if (n) { int rc = vt.reserve(ctx, packed, n, rows, g.A); if (rc) return rc; }
+    span_guard sg(ctx, "violations");
+    if (n) HIP_TRY(hipMemsetAsync(o.chain_counts, 0, sizeof(int64_t) * 4 * (size_t)n, ctx->stream));
+    if (rows == 0) return FCZ_OK;                                             // (packed, chains without a row: their counters are 0)
+    if (packed) {
+        hipLaunchKernelGGL(k_viol_fill, dim3((uint32_t)std::min<uint64_t>(((uint64_t)rows + BLOCK - 1) / BLOCK, max_blocks)), dim3(BLOCK), 0, ctx->stream, g);
+        if (n == 0) { HIP_TRY(hipGetLastError()); return FCZ_OK; }
+        int rc = vt.scan(ctx, bound_dev, n, rows); if (rc) return rc;
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_violations<true>), dim3((uint32_t)vt.blocks), dim3(BLOCK), 0, ctx->stream, g, tab, vt.tile_off, 0u, (uint64_t)0);
+    } else {
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_violations<false>), dim3((uint32_t)vt.blocks), dim3(BLOCK), 0, ctx->stream, g, tab, (const uint64_t*)nullptr,
+                           vt.tiles_per_entry, vt.n_padded);
+    }
+    HIP_TRY(hipGetLastError());
+    return FCZ_OK;
+}
+
+int fcz_violations_dev(fcz_ctx* ctx, const float* pos_dev, const uint8_t* mask_dev, const uint8_t* aatype_dev, const uint32_t* length_dev, uint32_t n, uint32_t L,
+                       int layout, const float* radius_table, float tolerance, float link_factor, const fcz_violations_out* out_dev) {
+    sasa_table tab;
+    if (!viol_args_ok(ctx, pos_dev, mask_dev, aatype_dev, layout, L, radius_table, tolerance, link_factor, out_dev, &tab) || L == 0) return FCZ_E_INVALID_ARG;
+    return viol_rows(ctx, pos_dev, mask_dev, aatype_dev, length_dev, false, n, L, layout, tab, tolerance, link_factor, *out_dev);
+}
+
+int fcz_violations_packed_dev(fcz_ctx* ctx, const float* pos_dev, const uint8_t* mask_dev, const uint8_t* aatype_dev, const uint32_t* row_off_dev, uint32_t n,
+                              uint32_t R, int layout, const float* radius_table, float tolerance, float link_factor, const fcz_violations_out* out_dev) {
+    sasa_table tab;
+    if (!viol_args_ok(ctx, pos_dev, mask_dev, aatype_dev, layout, R, radius_table, tolerance, link_factor, out_dev, &tab) || (n && !row_off_dev))
+        return FCZ_E_INVALID_ARG;
+    return viol_rows(ctx, pos_dev, mask_dev, aatype_dev, row_off_dev, true, n, R, layout, tab, tolerance, link_factor, *out_dev);
+}
+
+// fcz_violations and fcz_violations_packed: the host arrays through DENSE_IN 0 .. 3 and VIOL_OUT 10 .. 19
+static int viol_host(fcz_ctx* ctx, const float* pos, const uint8_t* mask, const uint8_t* aatype, const uint32_t* bound, bool packed, uint32_t n, uint32_t rows_per,
+                     int layout, const sasa_table& tab, float tolerance, float link_factor, const fcz_violations_out& o) {
+    HIP_TRY(hipSetDevice(ctx->device));
+    claim_staging(ctx);
+    const size_t rows = packed ? (size_t)rows_per : (size_t)n * rows_per, A = (size_t)fcz_dense_width(layout);
+    if (rows == 0 && n == 0) return FCZ_OK;
+    const size_t nb = bound ? sizeof(uint32_t) * ((size_t)n + (packed ? 1 : 0)) : 0, np = rows * A * 3 * sizeof(float), nm = rows * A;
+    // the ten outputs in the struct's order: the host array and its bytes
+    void* const host[10] = {o.clash_atom, o.clash_count, o.clash_depth, o.clash_partner, o.viol_mask, o.link_mask, o.link_length, o.link_cos, o.link_violation,
+                            o.chain_counts};
+    const size_t bytes[10] = {nm, rows * 4, rows * 4, rows * 4, rows, rows, rows * 4, rows * 8, rows, (size_t)n * 4 * sizeof(int64_t)};
+    int rc;
+    if ((rc = ctx->pool[DENSE_IN].ensure(np)) || (rc = ctx->pool[DENSE_IN + 1].ensure(nm)) || (rc = ctx->pool[DENSE_IN + 2].ensure(aatype ? rows : 0)) ||
+        (rc = ctx->pool[DENSE_IN + 3].ensure(nb)))
+        return rc;
+    for (int k = 0; k < 10; k++) if ((rc = ctx->pool[VIOL_OUT + k].ensure(bytes[k]))) return rc;
+    if (np) HIP_TRY(hipMemcpyAsync(ctx->pool[DENSE_IN].p, pos, np, hipMemcpyHostToDevice, ctx->stream));
+    if (nm) HIP_TRY(hipMemcpyAsync(ctx->pool[DENSE_IN + 1].p, mask, nm, hipMemcpyHostToDevice, ctx->stream));
+    if (aatype && rows) HIP_TRY(hipMemcpyAsync(ctx->pool[DENSE_IN + 2].p, aatype, rows, hipMemcpyHostToDevice, ctx->stream));
+    if (nb) HIP_TRY(hipMemcpyAsync(ctx->pool[DENSE_IN + 3].p, bound, nb, hipMemcpyHostToDevice, ctx->stream));
+    fcz_violations_out d{};
+    d.clash_atom = ctx->pool[VIOL_OUT].as<uint8_t>(); d.clash_count = ctx->pool[VIOL_OUT + 1].as<int32_t>(); d.clash_depth = ctx->pool[VIOL_OUT + 2].as<float>();
+    d.clash_partner = ctx->pool[VIOL_OUT + 3].as<int32_t>(); d.viol_mask = ctx->pool[VIOL_OUT + 4].as<uint8_t>(); d.link_mask = ctx->pool[VIOL_OUT + 5].as<uint8_t>();
+    d.link_length = ctx->pool[VIOL_OUT + 6].as<float>(); d.link_cos = ctx->pool[VIOL_OUT + 7].as<float>(); d.link_violation = ctx->pool[VIOL_OUT + 8].as<uint8_t>();
+    d.chain_counts = ctx->pool[VIOL_OUT + 9].as<int64_t>();
+    rc = viol_rows(ctx, ctx->pool[DENSE_IN].as<float>(), ctx->pool[DENSE_IN + 1].as<uint8_t>(), aatype ? ctx->pool[DENSE_IN + 2].as<uint8_t>() : nullptr,
+                   nb ? ctx->pool[DENSE_IN + 3].as<uint32_t>() : nullptr, packed, n, rows_per, layout, tab, tolerance, link_factor, d);
+    if (rc) return rc;
+    for (int k = 0; k < 10; k++)
+        if (bytes[k]) HIP_TRY(hipMemcpyAsync(host[k], ctx->pool[VIOL_OUT + k].p, bytes[k], hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return FCZ_OK;
+}
+
+int fcz_violations(fcz_ctx* ctx, const float* pos, const uint8_t* mask, const uint8_t* aatype, const uint32_t* length, uint32_t n, uint32_t L, int layout,
+                   const float* radius_table, float tolerance, float link_factor, const fcz_violations_out* out) {
+    sasa_table tab;
+    if (!viol_args_ok(ctx, pos, mask, aatype, layout, L, radius_table, tolerance, link_factor, out, &tab) || L == 0) return FCZ_E_INVALID_ARG;
+    return viol_host(ctx, pos, mask, aatype, length, false, n, L, layout, tab, tolerance, link_factor, *out);
+}
+
+int fcz_violations_packed(fcz_ctx* ctx, const float* pos, const uint8_t* mask, const uint8_t* aatype, const uint32_t* row_off, uint32_t n, uint32_t R, int layout,
+                          const float* radius_table, float tolerance, float link_factor, const fcz_violations_out* out) {
+    sasa_table tab;
+    if (!viol_args_ok(ctx, pos, mask, aatype, layout, R, radius_table, tolerance, link_factor, out, &tab) || (n && !row_off)) return FCZ_E_INVALID_ARG;
+    return viol_host(ctx, pos, mask, aatype, row_off, true, n, R, layout, tab, tolerance, link_factor, *out);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -980,6 +980,12 @@ class CSuperposeOut(ctypes.Structure):
                 ("gdt_counts", ctypes.c_void_p), ("tm", ctypes.c_void_p), ("dev", ctypes.c_void_p)]
 
 
+class CViolationsOut(ctypes.Structure):
+    """fcz_violations_out (include/fcz_hip.h): the ten outputs of the violation calls, every one required"""
+    _fields_ = [(k, ctypes.c_void_p) for k in ("clash_atom", "clash_count", "clash_depth", "clash_partner", "viol_mask", "link_mask", "link_length",
+                                               "link_cos", "link_violation", "chain_counts")]
+
+
 class CTmScoreOut(ctypes.Structure):
     """fcz_tmscore_out (include/fcz_hip.h): fcz_superpose_out's seven arrays, then seed and selected; all but rot and trans may be None"""
     _fields_ = CSuperposeOut._fields_ + [("seed", ctypes.c_void_p), ("selected", ctypes.c_void_p)]

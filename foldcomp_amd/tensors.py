@@ -25,6 +25,10 @@
                                    label of every residue (foldcomp.SS_CLASSES); decode_tensors(secondary_structure=True) adds ss / ss_mask
     solvent_accessibility(either dict, or the tensors as keywords) -> dict(sasa [..] float32, rsa, sasa_mask bool, sasa_points [.., A] int16):
                                    the Shrake-Rupley accessible surface of every residue; decode_tensors(sasa=True) adds sasa / rsa / sasa_mask
+    violations(either dict, or the tensors as keywords) -> dict(clash_atom [.., A] uint8, clash_count, clash_depth, clash_partner, viol_mask,
+                                   link_mask, link_length, link_cos [.., 2], link_violation [..], chain_counts [n, 4] int64): steric clashes
+                                   between residues and broken peptide links; decode_tensors(violations=True) adds clash_count /
+                                   link_violation / viol_mask
     rigid_frames(either dict, or the tensors as keywords, groups="backbone" | "all") -> dict(rot [.., 3, 3], trans [.., 3], frame_mask):
                                    every residue's backbone frame, or the eight rigid groups; decode_tensors(frames=...) adds them
 
@@ -47,10 +51,10 @@ import numpy as np
 from . import _lib, api, fczfile
 from ._aa_tables import RES1
 from .codec import ANGLE_COLUMNS, Codec, dense_layout
-from .structure import CAtomsOut, CDenseIn, CDenseOut, CPackedOut, CSuperposeOut, CTmScoreOut
+from .structure import CAtomsOut, CDenseIn, CDenseOut, CPackedOut, CSuperposeOut, CTmScoreOut, CViolationsOut
 
 __all__ = ["decode_tensors", "encode_tensors", "decode_angles", "crop_starts", "neighbor_graph", "rigid_frames", "lddt", "superpose", "tm_score", "apply_transform",
-           "backbone_hbonds", "secondary_structure", "solvent_accessibility"]
+           "backbone_hbonds", "secondary_structure", "solvent_accessibility", "violations"]
 
 
 def crop_starts(length, L: int, how, generator=None):
@@ -254,7 +258,7 @@ def decode_angles(entries: Sequence[bytes], *, max_len: Optional[int] = None, pa
 def decode_tensors(entries: Sequence[bytes], *, layout="atom37", max_len: Optional[int] = None, device="cuda:0",
                    codec: Optional[Codec] = None, packed: bool = False, angles: bool = False, crop=None, generator=None,
                    neighbors: Optional[int] = None, neighbor_atom="CA", frames: Optional[str] = None,
-                   secondary_structure: bool = False, sasa: bool = False) -> dict:
+                   secondary_structure: bool = False, sasa: bool = False, violations: bool = False) -> dict:
     """[fcz, ...] -> dict of torch tensors on `device` plus `names` (the records' titles, a Python list).
 
     layout: "atom37" (A = 37, AlphaFold / OpenFold atom order, the chain's OXT in slot 36 of its last residue), "atom14" (A = 14,
@@ -297,6 +301,12 @@ def decode_tensors(entries: Sequence[bytes], *, layout="atom37", max_len: Option
     [n, L] / [R] float32, rsa float32 and sasa_mask bool, as solvent_accessibility describes them (which also returns the per-atom
     counts). With crop the values are the window's own: atoms outside the window bury nothing. False: the dict has no new key.
 
+    violations=True adds the structural violations of the tensors just written, in either form, with no host round trip
+    (fcz_violations_dev on the codec's stream behind the dense call, with the defaults of foldcomp.violations: tolerance 1.5, link
+    factor 12, Bondi radii): clash_count [n, L] / [R] int32, link_violation uint8 and viol_mask bool, as violations describes them
+    (which also returns the per-atom flags, depths, partners, link geometry and per-chain counts). With crop the values are the
+    window's own. False: the dict has no new key.
+
     Ordering against torch: the uploads and allocations are made on torch's current stream, which is synchronised before the
     codec's calls; the codec works on its own stream, which is synchronised before the tensors are returned. No output byte
     visits the host.
@@ -310,6 +320,8 @@ def decode_tensors(entries: Sequence[bytes], *, layout="atom37", max_len: Option
     want_ss = bool(secondary_structure)
     api.check_sasa_flag(sasa)
     want_sasa = bool(sasa)
+    api.check_violations_flag(violations)
+    want_viol = bool(violations)
     torch, dev = _torch_device(device)
     c = codec or api.default_codec()
     if int(c.device) != dev.index:
@@ -359,12 +371,19 @@ def decode_tensors(entries: Sequence[bytes], *, layout="atom37", max_len: Option
     def sasa_alloc(*rows):   # sasa=False: no key
         return _sasa_alloc(torch, dev, rows) if want_sasa else {}
 
+    def viol_alloc(*rows):   # violations=False: no tensor
+        return _viol_alloc(torch, dev, rows, A, n) if want_viol else None
+
+    def viol_keys(v):
+        return {} if v is None else {k: v[k] for k in api.VIOLATION_BATCH_KEYS}
+
     if n == 0:
         if packed:
-            d = dict(packed_result(0, torch.zeros(1, dtype=torch.int32, device=dev), 0)[1], **nbr_alloc(0), **frames_alloc(0), **ss_alloc(0), **sasa_alloc(0))
+            d = dict(packed_result(0, torch.zeros(1, dtype=torch.int32, device=dev), 0)[1], **nbr_alloc(0), **frames_alloc(0), **ss_alloc(0), **sasa_alloc(0),
+                     **viol_keys(viol_alloc(0)))
             return dict(d, **no_angles(0)) if angles else d
         L = int(max_len or 0)
-        d = dict(result(L, *alloc(L)), **nbr_alloc(0, L), **frames_alloc(0, L), **ss_alloc(0, L), **sasa_alloc(0, L))
+        d = dict(result(L, *alloc(L)), **nbr_alloc(0, L), **frames_alloc(0, L), **ss_alloc(0, L), **sasa_alloc(0, L), **viol_keys(viol_alloc(0, L)))
         if crop is not None:
             d["crop_start"] = crop_starts(d["length"], L, crop, generator)
         return dict(d, **no_angles(0, L)) if angles else d
@@ -374,7 +393,7 @@ def decode_tensors(entries: Sequence[bytes], *, layout="atom37", max_len: Option
         # (the angle call is enqueued in front of the decode and leaves it the sizes memo; _decode_packed synchronises the codec)
         extra = _angles_into(c, torch, dev, n, blob_t, off_t, res_off_t, 0, Rv) if angles else {}
         d = _decode_packed(c, torch, dev, lay, n, Rv, Mv, blob_t, off_t, res_off_t, atom_off_t, packed_result, nbr, nbr_alloc, fgroups, frames_alloc,
-                           ss_alloc, sasa_alloc)
+                           ss_alloc, sasa_alloc, viol_alloc if want_viol else None)
         return dict(d, **extra)
     if max_len is None:
         ro = res_off_t.cpu().numpy().view(np.uint32).astype(np.int64)      # n + 1 offsets: the only words that come back
@@ -383,7 +402,7 @@ def decode_tensors(entries: Sequence[bytes], *, layout="atom37", max_len: Option
         L = int(max_len)
     out = alloc(L)
     if L == 0:                                                             # nothing decodes and no width was asked for
-        d = dict(result(L, *out), **nbr_alloc(n, 0), **frames_alloc(n, 0), **ss_alloc(n, 0), **sasa_alloc(n, 0))
+        d = dict(result(L, *out), **nbr_alloc(n, 0), **frames_alloc(n, 0), **ss_alloc(n, 0), **sasa_alloc(n, 0), **viol_keys(viol_alloc(n, 0)))
         return dict(d, **no_angles(n, 0)) if angles else d
     start_t = None if crop is None else crop_starts(_entry_lengths(res_off_t), L, crop, generator)
     extra = _angles_into(c, torch, dev, n, blob_t, off_t, res_off_t, L, start_t=start_t) if angles else {}
@@ -395,6 +414,8 @@ def decode_tensors(entries: Sequence[bytes], *, layout="atom37", max_len: Option
     tables = _hbond_alloc(torch, dev, (n, L)) if want_ss else None
     extra.update(sasa_alloc(n, L))
     sasa_work = _sasa_work(torch, dev, (n, L, A)) if want_sasa else None
+    viol = viol_alloc(n, L)
+    extra.update(viol_keys(viol))
     x, y, z = (torch.empty(max(M.value, 1), dtype=torch.float32, device=dev) for _ in range(3))
     bfac = torch.empty(max(R.value, 1), dtype=torch.float32, device=dev)
     res_code = torch.empty(max(R.value, 1), dtype=torch.uint8, device=dev)
@@ -420,6 +441,8 @@ def decode_tensors(entries: Sequence[bytes], *, layout="atom37", max_len: Option
         _dssp_into(c, out[0], out[1], out[2], out[5] if crop is None else None, n, L, lay, False, tables, extra)
     if want_sasa:   # (as above: a window needs no length)
         _sasa_into(c, out[0], out[1], out[2], out[5] if crop is None else None, n, L, lay, False, None, api.SASA_PROBE, *sasa_work, extra)
+    if want_viol:   # (as above: a window needs no length)
+        _viol_into(c, out[0], out[1], out[2], out[5] if crop is None else None, n, L, lay, False, None, api.VIOLATION_TOLERANCE, api.VIOLATION_LINK_FACTOR, viol)
     c.synchronize()
     if want_sasa:
         extra["rsa"] = _rsa(torch, extra["sasa"], extra["sasa_mask"], out[2])
@@ -427,10 +450,11 @@ def decode_tensors(entries: Sequence[bytes], *, layout="atom37", max_len: Option
 
 
 def _decode_packed(c, torch, dev, lay, n, R, M, blob_t, off_t, res_off_t, atom_off_t, packed_result, nbr=None, nbr_alloc=None, fgroups=None,
-                   frames_alloc=None, ss_alloc=None, sasa_alloc=None):
+                   frames_alloc=None, ss_alloc=None, sasa_alloc=None, viol_alloc=None):
     """the packed leg of decode_tensors behind fcz_decompress_sizes_dev: R and M are its totals, res_off_t becomes cu_seqlens;
     nbr = (k, slot): the neighbour graph of the rows behind the dense call (nbr_alloc makes its tensors); fgroups: their rigid
-    frames (frames_alloc makes the tensors); ss_alloc: the DSSP labels of the rows, or no key; sasa_alloc: their solvent accessibility, or no key"""
+    frames (frames_alloc makes the tensors); ss_alloc: the DSSP labels of the rows, or no key; sasa_alloc: their solvent accessibility, or no key;
+    viol_alloc: their structural violations, or no key"""
     if R > 2 ** 31 - 1:
         raise api.error(f"decode_tensors: {R} residues do not fit the int32 cu_seqlens; split the batch")
     ro = res_off_t.cpu().numpy().view(np.uint32).astype(np.int64)          # n + 1 offsets: the only words that come back
@@ -445,6 +469,9 @@ def _decode_packed(c, torch, dev, lay, n, R, M, blob_t, off_t, res_off_t, atom_o
     sa = sasa_alloc(R) if sasa_alloc is not None else {}
     d.update(sa)
     sasa_work = _sasa_work(torch, dev, (R, out[1].shape[-1])) if sa and R else None
+    viol = viol_alloc(R) if viol_alloc is not None else None
+    if viol is not None:
+        d.update({k: viol[k] for k in api.VIOLATION_BATCH_KEYS})
     if R == 0:                                                             # nothing decodes: no row, length stays 0
         return d
     x, y, z = (torch.empty(max(M, 1), dtype=torch.float32, device=dev) for _ in range(3))
@@ -467,6 +494,8 @@ def _decode_packed(c, torch, dev, lay, n, R, M, blob_t, off_t, res_off_t, atom_o
         _dssp_into(c, out[0], out[1], out[2], res_off_t, n, R, lay, True, tables, ss)
     if sa:
         _sasa_into(c, out[0], out[1], out[2], res_off_t, n, R, lay, True, None, api.SASA_PROBE, *sasa_work, d)
+    if viol is not None:
+        _viol_into(c, out[0], out[1], out[2], res_off_t, n, R, lay, True, None, api.VIOLATION_TOLERANCE, api.VIOLATION_LINK_FACTOR, viol)
     c.synchronize()
     if sa:
         d["rsa"] = _rsa(torch, d["sasa"], d["sasa_mask"], out[2])
@@ -1011,6 +1040,72 @@ def solvent_accessibility(batch=None, *, probe: float = 1.4, n_points: int = 128
         c.synchronize()
         out["rsa"] = _rsa(torch, out["sasa"], out["sasa_mask"], aatype)
     return dict(out, sasa_points=counts)
+
+
+def _viol_alloc(torch, dev, rows, A, n):
+    """the ten output tensors of fcz_violations_dev (api.VIOLATION_OUTPUTS) for the leading shape `rows`, width A and n chains; the masks
+    are written as 0 / 1 bytes"""
+    out = {}
+    for key, dt, tail in api.VIOLATION_OUTPUTS:
+        shape = (n, 4) if tail == "n4" else tuple(rows) + ((A,) if tail == "A" else tail)
+        make = torch.zeros if tail == "n4" else torch.empty                 # (chains without a row: the call is not made and the counts are 0)
+        t = make(shape, dtype=torch.uint8 if dt == "bool" else getattr(torch, dt), device=dev)
+        out[key] = t.view(torch.bool) if dt == "bool" else t
+    return out
+
+
+def _viol_into(c, pos, mask, aatype, bound, n, rows, lay, is_packed, table, tolerance, link_factor, out):
+    """fcz_violations_dev / _packed_dev on checked device tensors into the tensors of _viol_alloc, enqueued on the codec's stream; table: the
+    radii as a contiguous float32 [21, A] array on the host, or None"""
+    fn, name = (c.lib.fcz_violations_packed_dev, "fcz_violations_packed_dev") if is_packed else (c.lib.fcz_violations_dev, "fcz_violations_dev")
+    c_out = CViolationsOut(*(out[key].data_ptr() for key, _, _ in api.VIOLATION_OUTPUTS))
+    _lib.check(fn(c.ctx, pos.data_ptr(), mask.data_ptr(), None if aatype is None else aatype.data_ptr(), None if bound is None else bound.data_ptr(),
+                  n, rows, lay, None if table is None else table.ctypes.data, float(tolerance), float(link_factor), ctypes.byref(c_out)), name)
+
+
+def violations(batch=None, *, tolerance: float = 1.5, link_factor: float = 12.0, radii="bondi", codec: Optional[Codec] = None, **tensors) -> dict:
+    """dense tensors on the GPU -> the structural violations of every chain: atoms of different residues that sit inside each other,
+    and peptide links whose length or angles are far from a peptide's, with no atoms x atoms array.
+
+    The inputs are solvent_accessibility's: `batch` is the dict decode_tensors / tensor_batches return, padded or packed, or the
+    tensors come as keywords: pos [n, L, A, 3] float32, mask [n, L, A], aatype [n, L] uint8 (needed for atom14; without it no
+    disulfide is excluded and no link is a proline's) and optionally length [n]; or the packed pos [R, A, 3], mask [R, A], aatype [R]
+    with cu_seqlens [n + 1]. `length` is ignored beside crop_start. Every slot whose mask is set, whose coordinates are finite and
+    whose radius is not 0 is an atom; only atoms of the same chain are compared.
+        clash_atom [.., A] uint8     1 where the slot's atom clashes: it lies closer than (Ri + Rj) - tolerance to an atom of
+                                     another residue that is neither its peptide-bond partner (C and the next N) nor, SG to SG
+                                     between two CYS, its disulfide partner
+        clash_count [..] int32       the clashing (atom of the residue, atom of another residue) pairs
+        clash_depth [..] float32     the deepest overlap (Ri + Rj) - tolerance - distance among them; 0 when none
+        clash_partner [..] int32     the row, counted inside the chain, of the atom at that depth (the smallest on a tie); -1 when none
+        viol_mask [..] bool          True where the row has an atom
+        link_mask [..] bool          True where the link to the NEXT row exists: CA and C here, N and CA there
+        link_length [..] float32     the C-N' distance
+        link_cos [.., 2] float32     the cosines of the angles CA-C-N' and C-N'-CA'
+        link_violation [..] uint8    bit 0: the length is further than link_factor sigmas from 1.329 (1.341 before a PRO); bit 1 / bit
+                                     2: the first / second cosine is further than link_factor sigmas from -0.4473 / -0.5203
+        chain_counts [n, 4] int64    per chain: atoms, clashing pairs (each once), links with bit 0, links with bit 1 or 2
+    tolerance: how far two atoms may overlap (AlphaFold: 1.5). link_factor: the sigmas a link may deviate (AlphaFold: 12). radii:
+    "bondi" (solvent_accessibility's table, the chain's OXT left out) or an array [21, A] indexed [aatype][slot], 0 for a slot that
+    holds no atom, every other radius in [0.5, 8). The arithmetic is fixed (include/fcz_hip.h, fcz_violations_dev): atom37 and atom14
+    give the same values. Bonds and angles inside a residue are not checked. A cropped window's values are the window's own.
+    Reproducible bit for bit; NOT differentiable. The arguments are checked first, without torch or a device
+    (api.check_violations)."""
+    checked = {}
+
+    def check(d):
+        checked["v"] = api.check_violations("violations", d, tolerance, link_factor, radii)
+        return checked["v"][:2]
+
+    c, torch, dev, pos, mask, aatype, lead, n, rows, bound, is_packed, lay, _ = _dssp_inputs("violations", batch, tensors, codec,
+                                                                                             numpy_form="Codec.violations", check=check)
+    table = checked["v"][2]
+    out = _viol_alloc(torch, dev, lead, pos.shape[-2], n)
+    if out["clash_count"].numel():
+        torch.cuda.current_stream(dev).synchronize()
+        _viol_into(c, pos, mask, aatype, bound, n, rows, lay, is_packed, table, tolerance, link_factor, out)
+        c.synchronize()
+    return out
 
 
 def _frames_alloc(torch, dev, rows, fgroups):

@@ -21,6 +21,7 @@
  *   (none: no score of one structure against another)      fcz_lddt_dev / fcz_lddt_packed_dev, fcz_lddt / fcz_lddt_packed
  *   (none: no secondary structure)                         fcz_hbond_dev, fcz_dssp_labels_dev, fcz_dssp (+ _packed forms)
  *   (none: no solvent accessibility)                       fcz_sasa_dev / fcz_sasa_packed_dev, fcz_sasa / fcz_sasa_packed
+ *   (none: no structural violations)                       fcz_violations_dev / fcz_violations_packed_dev, fcz_violations / fcz_violations_packed
  *   (none: `rmsd` compares two files unsuperposed)         fcz_superpose_dev / fcz_superpose_packed_dev, fcz_superpose_apply_dev /
  *                                                          fcz_superpose_apply_packed_dev and their host forms
  *   (none: no TM-score)                                    fcz_tmscore_dev / fcz_tmscore_packed_dev and their host forms
@@ -588,6 +589,90 @@ int fcz_sasa(fcz_ctx* ctx, const float* pos, const uint8_t* mask, const uint8_t*
 int fcz_sasa_packed(fcz_ctx* ctx, const float* pos, const uint8_t* mask, const uint8_t* aatype, const uint32_t* row_off, uint32_t n,
                     uint32_t R, int layout, const float* radius_table, float probe, const float* points, uint32_t n_points,
                     int16_t* sasa_points, float* sasa, uint8_t* sasa_mask);
+
+/* ---- steric clashes and peptide-link violations of the dense tensors ------------------------------------- */
+/* Is the structure physically possible: do atoms of different residues sit inside each other, and is the chain still connected? The
+ * two between-residue terms of AlphaFold's "structural violations", for a whole batch on the device, without a rows x rows or an
+ * atoms x atoms array. The reference has no such output: like fcz_sasa_dev these stand beside Foldcomp::decompress
+ * (src/foldcomp.cpp:779) and read what the dense calls wrote, or any tensors of those shapes. The inputs are fcz_sasa_dev's: padded
+ * pos [n][L][A][3] float32, mask [n][L][A] uint8, aatype [n][L] uint8 or NULL, length [n] uint32 (may be NULL); packed pos [R][A][3],
+ * mask [R][A], aatype [R] or NULL, row_off [n + 1] uint32. A = fcz_dense_width(layout); every slot is read. All arithmetic is float32
+ * with every operation rounded, no FMA; d2(p, q) = (dx*dx + dy*dy) + dz*dz (fcz_knn_dev's d2); sqrt is the correctly rounded one.
+ *   atom          exactly fcz_sasa_dev's atom with probe 0: a slot (row, a) of a row inside its chain whose mask is non-zero, whose
+ *                 three coordinates are finite and whose radius R = radius_table[min(aatype, 20)][a] is non-zero. radius_table is
+ *                 fcz_sasa_dev's HOST table [21][A], NULL for fcz_sasa_default_radii(layout, ..) (Bondi; OXT holds 0 and is left
+ *                 out, so atom37 and atom14 describe the same atoms); aatype NULL: every row uses row 0 (refused in atom14). Only
+ *                 atoms of the same chain are compared. Nothing else is read as data.
+ *   clash         atoms i and j of DIFFERENT ROWS clash when T = (Ri + Rj) - tolerance (one addition, one subtraction) is > 0 and
+ *                 d2(c_i, c_j) < T * T. Ri + Rj commutes and d2(p, q) == d2(q, p) bit for bit, so the predicate is SYMMETRIC in
+ *                 float32: j clashes with i whenever i clashes with j. d2 = +inf (coordinates like 3e19) or NaN is no clash. Two
+ *                 kinds of pair never clash: the peptide bond, C of row r with N of row r + 1 of the same chain, and the
+ *                 disulfide, SG with SG when both rows have aatype == 4 (CYS). N and C are the slots fcz_dense_slot(layout, 0, ..)
+ *                 gives them, SG the slot fcz_dense_slot(layout, 4, SG) gives; in backbone4, or with a NULL aatype, the disulfide
+ *                 exclusion never applies. The kernel uses NO cull: every pair of atoms of a chain is put to this test.
+ *   clash_atom [rows][A] uint8    1 when the slot's atom clashes with some atom, else 0
+ *   clash_count [rows] int32      the (atom of this row, atom of another row) clashing pairs; every pair is therefore counted once
+ *                                 from each side, and the sum over a chain is even (modulo 2^32 for a row with more)
+ *   clash_depth [rows] float32    the largest T - sqrt(d2) (one subtraction) over those pairs, 0 when none. It is >= 0 (sqrt is
+ *                                 monotone and sqrt(T * T) == T) and a maximum, so no order of evaluation changes it
+ *   clash_partner [rows] int32    the CHAIN-RELATIVE row of the other atom of the pair behind clash_depth; of equal depths the
+ *                                 smallest row; -1 when none
+ *   viol_mask [rows] uint8        1 when the row has at least one atom, else 0
+ *   link          between rows r and r + 1 of a chain, stored at row r; the chain's last row has none. It exists when CA and C of r
+ *                 and N and CA of r + 1 are set in the mask and finite; the radius table plays no part here.
+ *   link_mask [rows] uint8        1 when the link exists. Where it does not, the three fields below are 0.
+ *   link_length [rows] float32    sqrt(d2(C, N'))
+ *   link_cos [rows][2] float32    the cosines of the angles CA-C-N' and C-N'-CA'. The angle at b between a and c: u = a - b,
+ *                                 v = c - b, dot = (ux*vx + uy*vy) + uz*vz, |u| = sqrt((ux*ux + uy*uy) + uz*uz), |v| alike, and
+ *                                 cos = dot / (|u| * |v|): one multiplication, one division. A zero norm gives what IEEE gives
+ *                                 (NaN or +-inf); NaN compares false below, so it is no violation
+ *   link_violation [rows] uint8   bit 0: |link_length - l0| > link_factor * sl, with (l0, sl) = (1.341, 0.016) when row r + 1 has
+ *                                 aatype == 14 (PRO; never with a NULL aatype), else (1.329, 0.014);
+ *                                 bit 1: |cos0 - (-0.4473)| > link_factor * 0.0311; bit 2: |cos1 - (-0.5203)| > link_factor * 0.0353.
+ *                                 Each constant is the float32 nearest to the decimal, each product link_factor * s one float32
+ *                                 multiplication, each difference one subtraction. The constants are the Engh & Huber peptide
+ *                                 geometry that AlphaFold's violation terms use: defaults of this definition, not measurements.
+ *   chain_counts [n][4] int64     per chain: its atoms; its clashing pairs, each ONCE (the pairs counted from the side with the
+ *                                 smaller row, which by the symmetry is exactly half the sum of the chain's clash_count); its rows
+ *                                 with bit 0; its rows with bit 1 or bit 2. Integer sums: no order changes them.
+ * rows = n * L (padded) or R (packed). Rows behind length and packed rows no chain covers hold 0 everywhere (-1 in clash_partner).
+ * Every byte of the outputs is written whatever the inputs hold, nothing outside them is written, and nothing outside the inputs is
+ * read, whatever row_off or aatype holds (ranges that overlap are each computed and a shared row's values are then unspecified).
+ * Every index that scales with rows * A is 64-bit. A chain's atoms are staged in passes of at most fcz_violations_pass() (pure host,
+ * > 0): a chain with more takes several, with the same result. Within-residue bond and angle bounds, AlphaFold's third term, are
+ * not computed. Every output needs the alignment of its type (chain_counts is added to with 64-bit atomics) and no more.
+ * Enqueued on the ctx stream, no synchronisation (the packed forms share fcz_knn_packed_dev's scratch in the ctx).
+ * FCZ_E_INVALID_ARG with nothing launched: NULL ctx / pos / mask / out / any of out's ten pointers, NULL row_off with n > 0, unknown
+ * layout, L == 0, L (padded) or R (packed) above 2^31 - 1, tolerance or link_factor not finite or negative, a table with a non-zero
+ * radius outside [0.5, 8), atom14 without aatype. n == 0 or R == 0: FCZ_OK (packed, n == 0 < R: every row is uncovered and is
+ * filled). The time goes to a group of its own, "violations". The results are integers, maxima and values of single rows:
+ * reproducible bit for bit, the same for the same atoms in atom37 and atom14, NOT differentiable. */
+typedef struct fcz_violations_out {
+    uint8_t* clash_atom;        /* [rows][A] */
+    int32_t* clash_count;       /* [rows] */
+    float*   clash_depth;       /* [rows] */
+    int32_t* clash_partner;     /* [rows] */
+    uint8_t* viol_mask;         /* [rows] */
+    uint8_t* link_mask;         /* [rows] */
+    float*   link_length;       /* [rows] */
+    float*   link_cos;          /* [rows][2] */
+    uint8_t* link_violation;    /* [rows] */
+    int64_t* chain_counts;      /* [n][4] */
+} fcz_violations_out;
+int fcz_violations_pass(void);
+int fcz_violations_dev(fcz_ctx* ctx, const float* pos_dev, const uint8_t* mask_dev, const uint8_t* aatype_dev, const uint32_t* length_dev,
+                       uint32_t n, uint32_t L, int layout, const float* radius_table /* host, or NULL */, float tolerance,
+                       float link_factor, const fcz_violations_out* out_dev);
+int fcz_violations_packed_dev(fcz_ctx* ctx, const float* pos_dev, const uint8_t* mask_dev, const uint8_t* aatype_dev,
+                              const uint32_t* row_off_dev, uint32_t n, uint32_t R, int layout,
+                              const float* radius_table /* host, or NULL */, float tolerance, float link_factor,
+                              const fcz_violations_out* out_dev);
+/* Host-pointer conveniences: the same arrays on the host, staged through the ctx like fcz_sasa; synchronous. */
+int fcz_violations(fcz_ctx* ctx, const float* pos, const uint8_t* mask, const uint8_t* aatype, const uint32_t* length, uint32_t n,
+                   uint32_t L, int layout, const float* radius_table, float tolerance, float link_factor, const fcz_violations_out* out);
+int fcz_violations_packed(fcz_ctx* ctx, const float* pos, const uint8_t* mask, const uint8_t* aatype, const uint32_t* row_off,
+                          uint32_t n, uint32_t R, int layout, const float* radius_table, float tolerance, float link_factor,
+                          const fcz_violations_out* out);
 
 /* ---- least-squares (Kabsch) superposition of two dense tensor batches ------------------------------------ */
 /* The superposition-based half of what a validation loop logs, per chain, for a whole batch on the device: the rigid motion that

@@ -152,7 +152,7 @@ struct fcz_ctx {
     dev_buf res_sc;     // decompress: residue -> its side-chain torsion bytes, 3 x R dwords
     dev_buf sizes_res_off;   // decompress: the res_off of a batch call that has to run its own sizes pass (ensure_sizes)
     dev_buf selftest_out;    // fcz_selftest_math
-    dev_buf knn_tiles;       // fcz_knn_packed_dev, fcz_lddt_packed_dev, fcz_superpose_apply_packed_dev (chain_tile_scan), fcz_sasa_packed_dev (sasa_tiles), fcz_violations_packed_dev (viol_tiles): n u64 tile counts, then their n + 1 offsets
+    dev_buf sweep_tiles;     // the packed form of every per-chain sweep (chain_tiles): n u64 tile counts, then their n + 1 offsets
     dev_buf tm_scratch;      // fcz_tmscore_dev / _packed_dev: n u64 item counts, their n + 1 offsets, a double per seed (tm_items_bound), n u32 site counts
     dev_buf dssp_flags;      // fcz_dssp_labels_dev / _packed_dev: a byte per row (k_dssp_flags -> k_dssp_labels)
     dev_buf fast_scratch;    // decompress, FCZ_NUMERICS_FAST: forward atoms of segments longer than one chunk
@@ -1663,125 +1663,190 @@ int fcz_decompress_angles_packed(fcz_ctx* ctx, const uint8_t* blob, const uint64
     return decompress_angles_impl(ctx, blob, off, n, true, 0u, R_out, row_off, angles, mask, status);
 }
 
-// ------------------------------------------------------------------------------------------------
-// k-nearest-neighbour residue graph of dense tensors (fcz_knn.h; no counterpart in the reference)
-// ------------------------------------------------------------------------------------------------
-int fcz_knn_pass(void) { return (int)KNN_PASS; }
+}  // extern "C"
 
-static bool knn_args_ok(const fcz_ctx* ctx, const float* pos, const uint8_t* mask, int layout, int slot, uint32_t k, const int32_t* index, const float* dist) {
-    return ctx && pos && mask && index && dist && fcz_dense_width(layout) > 0 && slot >= 0 && slot < fcz_dense_width(layout) && k >= 1 && k <= KNN_MAX_K;
-}
+// ------------------------------------------------------------------------------------------------
+// analyses of dense tensors: what they share (no counterpart in the reference)
+// ------------------------------------------------------------------------------------------------
+// What every form refuses beside its analysis' own *_args_ok: the padded form (bound = length [n] or NULL, rows = L) an entry without a
+// row, the packed form (bound = row_off [n + 1], rows = R) chains without a row_off.
+static bool bound_ok(bool packed, const uint32_t* bound, uint32_t n, uint32_t rows) { return packed ? n == 0 || bound : rows != 0; }
 
-// The query tiles of a per-chain sweep (fcz_chains.h) and the blocks that run them. Padded: n * tiles_per_entry tiles. Packed (n > 0):
-// reserve() makes room for n tile counts and their n + 1 offsets in ctx->knn_tiles, scan() counts them on the device behind whatever
-// the caller has enqueued -- the scratch is dead when the sweep that reads tile_off has run, so the sweeps share it.
+// The query tiles of a per-chain sweep (fcz_chains.h) and the blocks that run them: tile_rows rows a tile, at most blocks_per_cu blocks a
+// CU. Padded: n * tiles_per_entry tiles. Packed (n > 0): reserve() makes room for n tile counts and their n + 1 offsets in
+// ctx->sweep_tiles, scan() counts them on the device behind whatever the caller has enqueued -- the scratch is dead when the sweep that
+// reads tile_off has run, so the sweeps share it. A *_rows function calls reserve(), opens its span and calls run(): every allocation
+// lies in front of the span and every launch inside it.
 struct chain_tiles {
+    fcz_ctx* ctx; bool packed; uint32_t n, rows, tile_rows, max_blocks;
     uint64_t* tile_off = nullptr; uint32_t tiles_per_entry = 0; uint64_t n_padded = 0, blocks = 0;
-    int reserve(fcz_ctx* ctx, bool packed, uint32_t n, uint32_t rows) {
-        const uint32_t max_blocks = (uint32_t)ctx->n_cu * 16u;
-        tiles_per_entry = (uint32_t)(((uint64_t)rows + CHAIN_TILE - 1) / CHAIN_TILE);   // (rows + 255 may pass 2^32)
+    chain_tiles(fcz_ctx* c, bool p, uint32_t n_, uint32_t rows_, uint32_t tile_rows_ = CHAIN_TILE, uint32_t blocks_per_cu = 16u)
+        : ctx(c), packed(p), n(n_), rows(rows_), tile_rows(tile_rows_), max_blocks((uint32_t)c->n_cu * blocks_per_cu) {}
+    int reserve() {
         if (packed) {
-            int rc = ctx->knn_tiles.ensure(sizeof(uint64_t) * (2 * (size_t)n + 1)); if (rc) return rc;
-            tile_off = ctx->knn_tiles.as<uint64_t>() + n;
-            tiles_per_entry = 0;
-            blocks = std::min<uint64_t>((uint64_t)rows / CHAIN_TILE + n, max_blocks);   // the tiles are counted on the device: at most this many
+            if (n == 0) return FCZ_OK;                                            // no chain, no tile: run() ends behind the fill
+            int rc = ctx->sweep_tiles.ensure(sizeof(uint64_t) * (2 * (size_t)n + 1)); if (rc) return rc;
+            tile_off = ctx->sweep_tiles.as<uint64_t>() + n;
+            blocks = std::min<uint64_t>((uint64_t)rows / tile_rows + n, max_blocks);   // the tiles are counted on the device: at most this many
         } else {
+            tiles_per_entry = (uint32_t)(((uint64_t)rows + tile_rows - 1) / tile_rows);   // (rows + 255 may pass 2^32)
             n_padded = (uint64_t)n * tiles_per_entry;
             blocks = std::min<uint64_t>(n_padded, max_blocks);
         }
         return FCZ_OK;
     }
-    int scan(fcz_ctx* ctx, const uint32_t* row_off_dev, uint32_t n, uint32_t R) {
-        const uint32_t max_blocks = (uint32_t)ctx->n_cu * 16u;
-        hipLaunchKernelGGL(k_chain_tiles, dim3(std::min(grid_for(n, BLOCK), max_blocks)), dim3(BLOCK), 0, ctx->stream, row_off_dev, n, R, ctx->knn_tiles.as<uint64_t>());
-        return device_scan<uint64_t>(ctx, ctx->knn_tiles.as<uint64_t>(), tile_off, n);
+    int scan(const uint32_t* row_off_dev) {
+        hipLaunchKernelGGL(k_chain_tiles, dim3(std::min(grid_for(n, BLOCK), max_blocks)), dim3(BLOCK), 0, ctx->stream, row_off_dev, n, rows, tile_rows,
+                           ctx->sweep_tiles.as<uint64_t>());
+        return device_scan<uint64_t>(ctx, ctx->sweep_tiles.as<uint64_t>(), tile_off, n);
+    }
+    // the grid of a fill kernel over `items` elements, a thread each
+    dim3 fill_grid(uint64_t items) const { return dim3((uint32_t)std::min<uint64_t>((items + BLOCK - 1) / BLOCK, max_blocks)); }
+    // The launches of a sweep. Packed: fill() launches the analysis' fill kernel over the rows no chain covers, then the tiles are
+    // scanned; sweep(std::bool_constant<PACKED>, grid, tile_off, tiles_per_entry, n_padded) launches its kernel or kernels with those
+    // as their last three arguments.
+    template <class Fill, class Sweep> int run(const uint32_t* bound_dev, Fill fill, Sweep sweep) {
+        if (packed) {
+            fill();
+            if (n == 0) { HIP_TRY(hipGetLastError()); return FCZ_OK; }
+            int rc = scan(bound_dev); if (rc) return rc;
+            sweep(std::true_type{}, dim3((uint32_t)blocks), (const uint64_t*)tile_off, 0u, (uint64_t)0);
+        } else
+            sweep(std::false_type{}, dim3((uint32_t)blocks), (const uint64_t*)nullptr, tiles_per_entry, n_padded);
+        HIP_TRY(hipGetLastError());
+        return FCZ_OK;
     }
 };
 
-// fcz_knn_dev (row_off_dev == NULL: bound_dev is length [n] or NULL, rows = L) and fcz_knn_packed_dev (bound_dev = row_off [n + 1], rows = R)
+// the bytes of the host arrays of a call: its rows in all, pos [rows][A][3], mask [rows][A], bound (length [n] / row_off [n + 1]; NULL: 0)
+struct dense_bytes {
+    size_t rows, pos, mask, bound;
+    dense_bytes(bool packed, uint32_t n, uint32_t rows_per, int layout, const uint32_t* b)
+        : rows(packed ? (size_t)rows_per : (size_t)n * rows_per), pos(rows * (size_t)fcz_dense_width(layout) * 3 * sizeof(float)),
+          mask(rows * (size_t)fcz_dense_width(layout)), bound(b ? sizeof(uint32_t) * ((size_t)n + (packed ? 1 : 0)) : 0) {}
+};
+
+// An array of a host-pointer call: the caller's pointer (NULL: an input that is absent, an output that is not wanted), its bytes, and
+// the slot of fcz_ctx::pool it goes through (table in fcz_ctx).
+struct staged_in { const void* host; size_t bytes; int slot; };
+struct staged_out { void* host; size_t bytes; int slot; };
+constexpr int STAGED_MAX = 10;
+
+// The host-pointer form of an analysis: its inputs to the device, run(in, out) on the device pointers in the order of the lists (it
+// enqueues the *_rows call), the outputs back, and the stream drained. One set of rules for every analysis:
+//   * A call whose wanted outputs have no byte returns FCZ_OK with nothing enqueued: there is nothing it could write. That is rows == 0
+//     for the per-row analyses, and rows == 0 with n == 0 for violations, superpose and TM-score: they have per-chain outputs, so chains
+//     without a row (packed, R == 0) go on and get the counters and the transform of an empty chain.
+//   * An array of zero bytes is not copied, in either direction: hipMemcpyAsync is given no NULL or unallocated pointer.
+//   * An input that is absent or has zero bytes reaches run() as NULL. Absent is what the *_rows functions take NULL to mean (no
+//     length, no aatype, no second mask); of a zero-byte array no kernel reads an element -- every chain is clamped to the rows that
+//     exist and a launch without chains (n == 0: the fill kernels) reads no per-chain array such as the transforms of apply.
+//   * An output that is not wanted reaches run() as NULL, which is what the optional members of the out structs mean.
+//   * Every buffer is made large enough before the first copy is enqueued, so FCZ_E_NOMEM leaves nothing in flight.
+template <class Run>
+static int staged_call(fcz_ctx* ctx, std::initializer_list<staged_in> in, std::initializer_list<staged_out> out, Run run) {
+    HIP_TRY(hipSetDevice(ctx->device));
+    claim_staging(ctx);
+    size_t wanted = 0;
+    for (const staged_out& o : out) wanted += o.host ? o.bytes : 0;
+    if (wanted == 0) return FCZ_OK;
+    const void* din[STAGED_MAX]; void* dout[STAGED_MAX];
+    int rc, i = 0;
+    for (const staged_in& a : in) {
+        const size_t nb = a.host ? a.bytes : 0;
+        if ((rc = ctx->pool[a.slot].ensure(nb))) return rc;
+        din[i++] = nb ? ctx->pool[a.slot].p : nullptr;
+    }
+    i = 0;
+    for (const staged_out& o : out) {
+        if ((rc = ctx->pool[o.slot].ensure(o.host ? o.bytes : 0))) return rc;
+        dout[i++] = o.host ? ctx->pool[o.slot].p : nullptr;
+    }
+    i = 0;
+    for (const staged_in& a : in) {
+        if (din[i]) HIP_TRY(hipMemcpyAsync(ctx->pool[a.slot].p, a.host, a.bytes, hipMemcpyHostToDevice, ctx->stream));
+        i++;
+    }
+    if ((rc = run(din, dout))) return rc;
+    for (const staged_out& o : out)
+        if (o.host && o.bytes) HIP_TRY(hipMemcpyAsync(o.host, ctx->pool[o.slot].p, o.bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return FCZ_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// k-nearest-neighbour residue graph of dense tensors (fcz_knn.h; no counterpart in the reference)
+// ------------------------------------------------------------------------------------------------
+static bool knn_args_ok(const fcz_ctx* ctx, const float* pos, const uint8_t* mask, int layout, int slot, uint32_t k, const int32_t* index, const float* dist) {
+    return ctx && pos && mask && index && dist && fcz_dense_width(layout) > 0 && slot >= 0 && slot < fcz_dense_width(layout) && k >= 1 && k <= KNN_MAX_K;
+}
+
+// fcz_knn_dev (bound_dev is length [n] or NULL, rows = L) and fcz_knn_packed_dev (bound_dev = row_off [n + 1], rows = R)
 static int knn_rows(fcz_ctx* ctx, const float* pos_dev, const uint8_t* mask_dev, const uint32_t* bound_dev, bool packed, uint32_t n, uint32_t rows,
                     int layout, int slot, uint32_t k, int32_t* index_dev, float* dist_dev) {
     HIP_TRY(hipSetDevice(ctx->device));
     if (rows == 0 || (n == 0 && !packed)) return FCZ_OK;
     const knn_args g{pos_dev, mask_dev, bound_dev, n, rows, (uint32_t)fcz_dense_width(layout), (uint32_t)slot, k, index_dev, dist_dev};
-    const uint32_t max_blocks = (uint32_t)ctx->n_cu * 16u;
-    chain_tiles ct;
-    if (!packed || n) { int rc = ct.reserve(ctx, packed, n, rows); if (rc) return rc; }
+    chain_tiles ct(ctx, packed, n, rows);
+    int rc = ct.reserve(); if (rc) return rc;
     span_guard sg(ctx, "knn");
-    if (packed) {
-        hipLaunchKernelGGL(k_knn_fill, dim3((uint32_t)std::min<uint64_t>(((uint64_t)rows + BLOCK - 1) / BLOCK, max_blocks)), dim3(BLOCK), 0, ctx->stream, g);
-        if (n == 0) { HIP_TRY(hipGetLastError()); return FCZ_OK; }
-        int rc = ct.scan(ctx, bound_dev, n, rows); if (rc) return rc;
-    }
-    auto launch = [&](auto KCAP) {
-        if (packed)
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_knn<decltype(KCAP)::value, true>), dim3((uint32_t)ct.blocks), dim3(BLOCK), 0, ctx->stream, g, ct.tile_off, 0u, (uint64_t)0);
-        else
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_knn<decltype(KCAP)::value, false>), dim3((uint32_t)ct.blocks), dim3(BLOCK), 0, ctx->stream, g, (const uint64_t*)nullptr,
-                               ct.tiles_per_entry, ct.n_padded);
-    };
-    if (k <= 16) launch(std::integral_constant<int, 16>{});
-    else if (k <= 32) launch(std::integral_constant<int, 32>{});
-    else if (k <= 48) launch(std::integral_constant<int, 48>{});
-    else launch(std::integral_constant<int, 64>{});
-    HIP_TRY(hipGetLastError());
-    return FCZ_OK;
-}
-
-int fcz_knn_dev(fcz_ctx* ctx, const float* pos_dev, const uint8_t* mask_dev, const uint32_t* length_dev, uint32_t n, uint32_t L, int layout, int slot,
-                uint32_t k, int32_t* index_dev, float* dist_dev) {
-    if (!knn_args_ok(ctx, pos_dev, mask_dev, layout, slot, k, index_dev, dist_dev) || L == 0) return FCZ_E_INVALID_ARG;
-    return knn_rows(ctx, pos_dev, mask_dev, length_dev, false, n, L, layout, slot, k, index_dev, dist_dev);
-}
-
-int fcz_knn_packed_dev(fcz_ctx* ctx, const float* pos_dev, const uint8_t* mask_dev, const uint32_t* row_off_dev, uint32_t n, uint32_t R, int layout,
-                       int slot, uint32_t k, int32_t* index_dev, float* dist_dev) {
-    if (!knn_args_ok(ctx, pos_dev, mask_dev, layout, slot, k, index_dev, dist_dev) || (n && !row_off_dev) || R > 0x7FFFFFFFu) return FCZ_E_INVALID_ARG;   // (index holds global rows as int32)
-    return knn_rows(ctx, pos_dev, mask_dev, row_off_dev, true, n, R, layout, slot, k, index_dev, dist_dev);
+    return ct.run(bound_dev, [&] { hipLaunchKernelGGL(k_knn_fill, ct.fill_grid(rows), dim3(BLOCK), 0, ctx->stream, g); },
+                  [&](auto P, dim3 grid, const uint64_t* tile_off, uint32_t tiles_per_entry, uint64_t n_padded) {
+        auto launch = [&](auto KCAP) {
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_knn<decltype(KCAP)::value, decltype(P)::value>), grid, dim3(BLOCK), 0, ctx->stream, g, tile_off, tiles_per_entry, n_padded);
+        };
+        if (k <= 16) launch(std::integral_constant<int, 16>{});
+        else if (k <= 32) launch(std::integral_constant<int, 32>{});
+        else if (k <= 48) launch(std::integral_constant<int, 48>{});
+        else launch(std::integral_constant<int, 64>{});
+    });
 }
 
 // fcz_knn and fcz_knn_packed: the host arrays through DENSE_IN 0, 1, 3 and DENSE_OUT 10, 11
 static int knn_host(fcz_ctx* ctx, const float* pos, const uint8_t* mask, const uint32_t* bound, bool packed, uint32_t n, uint32_t rows_per, int layout,
                     int slot, uint32_t k, int32_t* index, float* dist) {
-    HIP_TRY(hipSetDevice(ctx->device));
-    claim_staging(ctx);
-    const size_t rows = packed ? (size_t)rows_per : (size_t)n * rows_per, A = (size_t)fcz_dense_width(layout);
-    if (rows == 0) return FCZ_OK;
-    const size_t nb = bound ? sizeof(uint32_t) * ((size_t)n + (packed ? 1 : 0)) : 0, no = rows * k * sizeof(int32_t);
-    int rc;
-    if ((rc = ctx->pool[DENSE_IN].ensure(rows * A * 3 * sizeof(float))) || (rc = ctx->pool[DENSE_IN + 1].ensure(rows * A)) ||
-        (rc = ctx->pool[DENSE_IN + 3].ensure(nb)) || (rc = ctx->pool[DENSE_OUT].ensure(no)) || (rc = ctx->pool[DENSE_OUT + 1].ensure(no)))
-        return rc;
-    HIP_TRY(hipMemcpyAsync(ctx->pool[DENSE_IN].p, pos, rows * A * 3 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(ctx->pool[DENSE_IN + 1].p, mask, rows * A, hipMemcpyHostToDevice, ctx->stream));
-    if (nb) HIP_TRY(hipMemcpyAsync(ctx->pool[DENSE_IN + 3].p, bound, nb, hipMemcpyHostToDevice, ctx->stream));
-    rc = knn_rows(ctx, ctx->pool[DENSE_IN].as<float>(), ctx->pool[DENSE_IN + 1].as<uint8_t>(), nb ? ctx->pool[DENSE_IN + 3].as<uint32_t>() : nullptr, packed, n,
-                  rows_per, layout, slot, k, ctx->pool[DENSE_OUT].as<int32_t>(), ctx->pool[DENSE_OUT + 1].as<float>());
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(index, ctx->pool[DENSE_OUT].p, no, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(dist, ctx->pool[DENSE_OUT + 1].p, no, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return FCZ_OK;
+    const dense_bytes b(packed, n, rows_per, layout, bound);
+    const size_t no = b.rows * k * sizeof(int32_t);
+    return staged_call(ctx, {{pos, b.pos, DENSE_IN}, {mask, b.mask, DENSE_IN + 1}, {bound, b.bound, DENSE_IN + 3}}, {{index, no, DENSE_OUT}, {dist, no, DENSE_OUT + 1}},
+                       [&](const void* const* in, void* const* out) {
+        return knn_rows(ctx, (const float*)in[0], (const uint8_t*)in[1], (const uint32_t*)in[2], packed, n, rows_per, layout, slot, k, (int32_t*)out[0], (float*)out[1]);
+    });
+}
+
+extern "C" {
+
+int fcz_knn_pass(void) { return (int)KNN_PASS; }
+
+int fcz_knn_dev(fcz_ctx* ctx, const float* pos_dev, const uint8_t* mask_dev, const uint32_t* length_dev, uint32_t n, uint32_t L, int layout, int slot,
+                uint32_t k, int32_t* index_dev, float* dist_dev) {
+    if (!knn_args_ok(ctx, pos_dev, mask_dev, layout, slot, k, index_dev, dist_dev) || !bound_ok(false, length_dev, n, L)) return FCZ_E_INVALID_ARG;
+    return knn_rows(ctx, pos_dev, mask_dev, length_dev, false, n, L, layout, slot, k, index_dev, dist_dev);
+}
+
+int fcz_knn_packed_dev(fcz_ctx* ctx, const float* pos_dev, const uint8_t* mask_dev, const uint32_t* row_off_dev, uint32_t n, uint32_t R, int layout,
+                       int slot, uint32_t k, int32_t* index_dev, float* dist_dev) {
+    if (!knn_args_ok(ctx, pos_dev, mask_dev, layout, slot, k, index_dev, dist_dev) || !bound_ok(true, row_off_dev, n, R) || R > 0x7FFFFFFFu)
+        return FCZ_E_INVALID_ARG;                                             // (index holds global rows as int32)
+    return knn_rows(ctx, pos_dev, mask_dev, row_off_dev, true, n, R, layout, slot, k, index_dev, dist_dev);
 }
 
 int fcz_knn(fcz_ctx* ctx, const float* pos, const uint8_t* mask, const uint32_t* length, uint32_t n, uint32_t L, int layout, int slot, uint32_t k,
             int32_t* index, float* dist) {
-    if (!knn_args_ok(ctx, pos, mask, layout, slot, k, index, dist) || L == 0) return FCZ_E_INVALID_ARG;
+    if (!knn_args_ok(ctx, pos, mask, layout, slot, k, index, dist) || !bound_ok(false, length, n, L)) return FCZ_E_INVALID_ARG;
     return knn_host(ctx, pos, mask, length, false, n, L, layout, slot, k, index, dist);
 }
 
 int fcz_knn_packed(fcz_ctx* ctx, const float* pos, const uint8_t* mask, const uint32_t* row_off, uint32_t n, uint32_t R, int layout, int slot, uint32_t k,
                    int32_t* index, float* dist) {
-    if (!knn_args_ok(ctx, pos, mask, layout, slot, k, index, dist) || (n && !row_off) || R > 0x7FFFFFFFu) return FCZ_E_INVALID_ARG;
+    if (!knn_args_ok(ctx, pos, mask, layout, slot, k, index, dist) || !bound_ok(true, row_off, n, R) || R > 0x7FFFFFFFu) return FCZ_E_INVALID_ARG;
     return knn_host(ctx, pos, mask, row_off, true, n, R, layout, slot, k, index, dist);
 }
+
+}  // extern "C"
 
 // ------------------------------------------------------------------------------------------------
 // per-residue lDDT of two dense tensor batches (fcz_lddt.h; no counterpart in the reference)
 // ------------------------------------------------------------------------------------------------
-int fcz_lddt_pass(void) { return (int)LDDT_PASS; }
-float fcz_lddt_c2(float cutoff) { return std::isfinite(cutoff) && cutoff > 0.0f ? lddt_c2(cutoff) : NAN; }
-
 static const float LDDT_THRESHOLDS[4] = {0.5f, 1.0f, 2.0f, 4.0f};
 
 // rows: L (padded) or R (packed)
@@ -1803,27 +1868,39 @@ static int lddt_rows(fcz_ctx* ctx, const float* pos_true_dev, const uint8_t* mas
     const float* th = thresholds ? thresholds : LDDT_THRESHOLDS;
     const lddt_args g{pos_true_dev, mask_true_dev, pos_pred_dev, mask_pred_dev, bound_dev, n, rows, (uint32_t)fcz_dense_width(layout), (uint32_t)slot,
                       lddt_c2(cutoff), th[0], th[1], th[2], th[3], score_dev, pairs_dev, hits_dev};
-    const uint32_t max_blocks = (uint32_t)ctx->n_cu * 16u;
-    chain_tiles ct;
-    if (!packed || n) { int rc = ct.reserve(ctx, packed, n, rows); if (rc) return rc; }
+    chain_tiles ct(ctx, packed, n, rows);
+    int rc = ct.reserve(); if (rc) return rc;
     span_guard sg(ctx, "lddt");
-    if (packed) {
-        hipLaunchKernelGGL(k_lddt_fill, dim3((uint32_t)std::min<uint64_t>(((uint64_t)rows + BLOCK - 1) / BLOCK, max_blocks)), dim3(BLOCK), 0, ctx->stream, g);
-        if (n == 0) { HIP_TRY(hipGetLastError()); return FCZ_OK; }
-        int rc = ct.scan(ctx, bound_dev, n, rows); if (rc) return rc;
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_lddt<true>), dim3((uint32_t)ct.blocks), dim3(BLOCK), 0, ctx->stream, g, ct.tile_off, 0u, (uint64_t)0);
-    } else {
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_lddt<false>), dim3((uint32_t)ct.blocks), dim3(BLOCK), 0, ctx->stream, g, (const uint64_t*)nullptr, ct.tiles_per_entry,
-                           ct.n_padded);
-    }
-    HIP_TRY(hipGetLastError());
-    return FCZ_OK;
+    return ct.run(bound_dev, [&] { hipLaunchKernelGGL(k_lddt_fill, ct.fill_grid(rows), dim3(BLOCK), 0, ctx->stream, g); },
+                  [&](auto P, dim3 grid, const uint64_t* tile_off, uint32_t tiles_per_entry, uint64_t n_padded) {
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_lddt<decltype(P)::value>), grid, dim3(BLOCK), 0, ctx->stream, g, tile_off, tiles_per_entry, n_padded);
+    });
 }
+
+// fcz_lddt and fcz_lddt_packed: the host arrays through DENSE_IN 0, 1, 3, LDDT_PRED 4, 5 and LDDT_OUT 10 .. 12
+static int lddt_host(fcz_ctx* ctx, const float* pos_true, const uint8_t* mask_true, const float* pos_pred, const uint8_t* mask_pred, const uint32_t* bound,
+                     bool packed, uint32_t n, uint32_t rows_per, int layout, int slot, float cutoff, const float* thresholds, float* score, int32_t* pairs,
+                     int32_t* hits) {
+    const dense_bytes b(packed, n, rows_per, layout, bound);
+    const size_t no = b.rows * 4;
+    return staged_call(ctx, {{pos_true, b.pos, DENSE_IN}, {mask_true, b.mask, DENSE_IN + 1}, {bound, b.bound, DENSE_IN + 3}, {pos_pred, b.pos, LDDT_PRED},
+                             {mask_pred, b.mask, LDDT_PRED + 1}},
+                       {{score, no, LDDT_OUT}, {pairs, no, LDDT_OUT + 1}, {hits, no, LDDT_OUT + 2}}, [&](const void* const* in, void* const* out) {
+        return lddt_rows(ctx, (const float*)in[0], (const uint8_t*)in[1], (const float*)in[3], (const uint8_t*)in[4], (const uint32_t*)in[2], packed, n, rows_per,
+                         layout, slot, cutoff, thresholds, (float*)out[0], (int32_t*)out[1], (int32_t*)out[2]);
+    });
+}
+
+extern "C" {
+
+int fcz_lddt_pass(void) { return (int)LDDT_PASS; }
+float fcz_lddt_c2(float cutoff) { return std::isfinite(cutoff) && cutoff > 0.0f ? lddt_c2(cutoff) : NAN; }
 
 int fcz_lddt_dev(fcz_ctx* ctx, const float* pos_true_dev, const uint8_t* mask_true_dev, const float* pos_pred_dev, const uint8_t* mask_pred_dev,
                  const uint32_t* length_dev, uint32_t n, uint32_t L, int layout, int slot, float cutoff, const float* thresholds, float* score_dev,
                  int32_t* pairs_dev, int32_t* hits_dev) {
-    if (!lddt_args_ok(ctx, pos_true_dev, mask_true_dev, pos_pred_dev, layout, slot, cutoff, thresholds, L, score_dev, pairs_dev, hits_dev) || L == 0)
+    if (!lddt_args_ok(ctx, pos_true_dev, mask_true_dev, pos_pred_dev, layout, slot, cutoff, thresholds, L, score_dev, pairs_dev, hits_dev) ||
+        !bound_ok(false, length_dev, n, L))
         return FCZ_E_INVALID_ARG;
     return lddt_rows(ctx, pos_true_dev, mask_true_dev, pos_pred_dev, mask_pred_dev, length_dev, false, n, L, layout, slot, cutoff, thresholds, score_dev,
                      pairs_dev, hits_dev);
@@ -1833,60 +1910,31 @@ int fcz_lddt_packed_dev(fcz_ctx* ctx, const float* pos_true_dev, const uint8_t* 
                         const uint32_t* row_off_dev, uint32_t n, uint32_t R, int layout, int slot, float cutoff, const float* thresholds, float* score_dev,
                         int32_t* pairs_dev, int32_t* hits_dev) {
     if (!lddt_args_ok(ctx, pos_true_dev, mask_true_dev, pos_pred_dev, layout, slot, cutoff, thresholds, R, score_dev, pairs_dev, hits_dev) ||
-        (n && !row_off_dev))
+        !bound_ok(true, row_off_dev, n, R))
         return FCZ_E_INVALID_ARG;
     return lddt_rows(ctx, pos_true_dev, mask_true_dev, pos_pred_dev, mask_pred_dev, row_off_dev, true, n, R, layout, slot, cutoff, thresholds, score_dev,
                      pairs_dev, hits_dev);
 }
 
-// fcz_lddt and fcz_lddt_packed: the host arrays through DENSE_IN 0, 1, 3, LDDT_PRED 4, 5 and LDDT_OUT 10 .. 12
-static int lddt_host(fcz_ctx* ctx, const float* pos_true, const uint8_t* mask_true, const float* pos_pred, const uint8_t* mask_pred, const uint32_t* bound,
-                     bool packed, uint32_t n, uint32_t rows_per, int layout, int slot, float cutoff, const float* thresholds, float* score, int32_t* pairs,
-                     int32_t* hits) {
-    HIP_TRY(hipSetDevice(ctx->device));
-    claim_staging(ctx);
-    const size_t rows = packed ? (size_t)rows_per : (size_t)n * rows_per, A = (size_t)fcz_dense_width(layout);
-    if (rows == 0) return FCZ_OK;
-    const size_t nb = bound ? sizeof(uint32_t) * ((size_t)n + (packed ? 1 : 0)) : 0, np = rows * A * 3 * sizeof(float), nm = rows * A, no = rows * 4;
-    int rc;
-    if ((rc = ctx->pool[DENSE_IN].ensure(np)) || (rc = ctx->pool[DENSE_IN + 1].ensure(nm)) || (rc = ctx->pool[DENSE_IN + 3].ensure(nb)) ||
-        (rc = ctx->pool[LDDT_PRED].ensure(np)) || (rc = ctx->pool[LDDT_PRED + 1].ensure(mask_pred ? nm : 0)) || (rc = ctx->pool[LDDT_OUT].ensure(no)) ||
-        (rc = ctx->pool[LDDT_OUT + 1].ensure(no)) || (rc = ctx->pool[LDDT_OUT + 2].ensure(no)))
-        return rc;
-    HIP_TRY(hipMemcpyAsync(ctx->pool[DENSE_IN].p, pos_true, np, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(ctx->pool[DENSE_IN + 1].p, mask_true, nm, hipMemcpyHostToDevice, ctx->stream));
-    if (nb) HIP_TRY(hipMemcpyAsync(ctx->pool[DENSE_IN + 3].p, bound, nb, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(ctx->pool[LDDT_PRED].p, pos_pred, np, hipMemcpyHostToDevice, ctx->stream));
-    if (mask_pred) HIP_TRY(hipMemcpyAsync(ctx->pool[LDDT_PRED + 1].p, mask_pred, nm, hipMemcpyHostToDevice, ctx->stream));
-    rc = lddt_rows(ctx, ctx->pool[DENSE_IN].as<float>(), ctx->pool[DENSE_IN + 1].as<uint8_t>(), ctx->pool[LDDT_PRED].as<float>(),
-                   mask_pred ? ctx->pool[LDDT_PRED + 1].as<uint8_t>() : nullptr, nb ? ctx->pool[DENSE_IN + 3].as<uint32_t>() : nullptr, packed, n, rows_per,
-                   layout, slot, cutoff, thresholds, ctx->pool[LDDT_OUT].as<float>(), ctx->pool[LDDT_OUT + 1].as<int32_t>(), ctx->pool[LDDT_OUT + 2].as<int32_t>());
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(score, ctx->pool[LDDT_OUT].p, no, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(pairs, ctx->pool[LDDT_OUT + 1].p, no, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(hits, ctx->pool[LDDT_OUT + 2].p, no, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return FCZ_OK;
-}
-
 int fcz_lddt(fcz_ctx* ctx, const float* pos_true, const uint8_t* mask_true, const float* pos_pred, const uint8_t* mask_pred, const uint32_t* length,
              uint32_t n, uint32_t L, int layout, int slot, float cutoff, const float* thresholds, float* score, int32_t* pairs, int32_t* hits) {
-    if (!lddt_args_ok(ctx, pos_true, mask_true, pos_pred, layout, slot, cutoff, thresholds, L, score, pairs, hits) || L == 0) return FCZ_E_INVALID_ARG;
+    if (!lddt_args_ok(ctx, pos_true, mask_true, pos_pred, layout, slot, cutoff, thresholds, L, score, pairs, hits) || !bound_ok(false, length, n, L))
+        return FCZ_E_INVALID_ARG;
     return lddt_host(ctx, pos_true, mask_true, pos_pred, mask_pred, length, false, n, L, layout, slot, cutoff, thresholds, score, pairs, hits);
 }
 
 int fcz_lddt_packed(fcz_ctx* ctx, const float* pos_true, const uint8_t* mask_true, const float* pos_pred, const uint8_t* mask_pred, const uint32_t* row_off,
                     uint32_t n, uint32_t R, int layout, int slot, float cutoff, const float* thresholds, float* score, int32_t* pairs, int32_t* hits) {
-    if (!lddt_args_ok(ctx, pos_true, mask_true, pos_pred, layout, slot, cutoff, thresholds, R, score, pairs, hits) || (n && !row_off))
+    if (!lddt_args_ok(ctx, pos_true, mask_true, pos_pred, layout, slot, cutoff, thresholds, R, score, pairs, hits) || !bound_ok(true, row_off, n, R))
         return FCZ_E_INVALID_ARG;
     return lddt_host(ctx, pos_true, mask_true, pos_pred, mask_pred, row_off, true, n, R, layout, slot, cutoff, thresholds, score, pairs, hits);
 }
 
+}  // extern "C"
+
 // ------------------------------------------------------------------------------------------------
 // backbone hydrogen bonds and DSSP secondary structure of dense tensors (fcz_dssp.h; no counterpart in the reference)
 // ------------------------------------------------------------------------------------------------
-int fcz_hbond_pass(void) { return (int)HBOND_PASS; }
-
 // rows: L (padded) or R (packed); out: every output pointer of the call
 static bool dssp_args_ok(const fcz_ctx* ctx, const float* pos, const uint8_t* mask, int layout, uint32_t rows, std::initializer_list<const void*> out) {
     if (!ctx || !pos || !mask || fcz_dense_width(layout) <= 0 || rows > DSSP_MAX_ROWS) return false;
@@ -1908,21 +1956,13 @@ static int hbond_rows(fcz_ctx* ctx, const float* pos_dev, const uint8_t* mask_de
     if (rows == 0 || (n == 0 && !packed)) return FCZ_OK;
     dssp_args g = dssp_pack(pos_dev, mask_dev, aatype_dev, bound_dev, n, rows, layout);
     g.acc_index = acc_index_dev; g.acc_energy = acc_energy_dev; g.don_index = don_index_dev; g.don_energy = don_energy_dev;
-    const uint32_t max_blocks = (uint32_t)ctx->n_cu * 16u;
-    chain_tiles ct;
-    if (!packed || n) { int rc = ct.reserve(ctx, packed, n, rows); if (rc) return rc; }
+    chain_tiles ct(ctx, packed, n, rows);
+    int rc = ct.reserve(); if (rc) return rc;
     span_guard sg(ctx, "dssp");
-    if (packed) {
-        hipLaunchKernelGGL(k_dssp_fill, dim3((uint32_t)std::min<uint64_t>(((uint64_t)rows + BLOCK - 1) / BLOCK, max_blocks)), dim3(BLOCK), 0, ctx->stream, g, 1);
-        if (n == 0) { HIP_TRY(hipGetLastError()); return FCZ_OK; }
-        int rc = ct.scan(ctx, bound_dev, n, rows); if (rc) return rc;
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_hbond<true>), dim3((uint32_t)ct.blocks), dim3(BLOCK), 0, ctx->stream, g, ct.tile_off, 0u, (uint64_t)0);
-    } else {
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_hbond<false>), dim3((uint32_t)ct.blocks), dim3(BLOCK), 0, ctx->stream, g, (const uint64_t*)nullptr, ct.tiles_per_entry,
-                           ct.n_padded);
-    }
-    HIP_TRY(hipGetLastError());
-    return FCZ_OK;
+    return ct.run(bound_dev, [&] { hipLaunchKernelGGL(k_dssp_fill, ct.fill_grid(rows), dim3(BLOCK), 0, ctx->stream, g, 1); },
+                  [&](auto P, dim3 grid, const uint64_t* tile_off, uint32_t tiles_per_entry, uint64_t n_padded) {
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_hbond<decltype(P)::value>), grid, dim3(BLOCK), 0, ctx->stream, g, tile_off, tiles_per_entry, n_padded);
+    });
 }
 
 // fcz_dssp_labels_dev and fcz_dssp_labels_packed_dev: the flags of every row into ctx->dssp_flags, then the labels from them and the table
@@ -1932,125 +1972,93 @@ static int dssp_label_rows(fcz_ctx* ctx, const float* pos_dev, const uint8_t* ma
     if (rows == 0 || (n == 0 && !packed)) return FCZ_OK;
     dssp_args g = dssp_pack(pos_dev, mask_dev, aatype_dev, bound_dev, n, rows, layout);
     g.acc_index = const_cast<int32_t*>(acc_index_dev); g.acc_energy = const_cast<float*>(acc_energy_dev); g.ss = ss_dev; g.ss_mask = ss_mask_dev;
-    const uint32_t max_blocks = (uint32_t)ctx->n_cu * 16u;
-    chain_tiles ct;
-    if (!packed || n) {
-        int rc = ct.reserve(ctx, packed, n, rows); if (rc) return rc;
+    chain_tiles ct(ctx, packed, n, rows);
+    int rc = ct.reserve(); if (rc) return rc;
+    if (!packed || n) {                                                       // (no chain: the fill alone runs, and it writes no flag)
         if ((rc = ctx->dssp_flags.ensure(packed ? (size_t)rows : (size_t)n * rows))) return rc;
         g.flags = ctx->dssp_flags.as<uint8_t>();
     }
     span_guard sg(ctx, "dssp");
-    if (packed) {
-        hipLaunchKernelGGL(k_dssp_fill, dim3((uint32_t)std::min<uint64_t>(((uint64_t)rows + BLOCK - 1) / BLOCK, max_blocks)), dim3(BLOCK), 0, ctx->stream, g, 2);
-        if (n == 0) { HIP_TRY(hipGetLastError()); return FCZ_OK; }
-        int rc = ct.scan(ctx, bound_dev, n, rows); if (rc) return rc;
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_dssp_flags<true>), dim3((uint32_t)ct.blocks), dim3(BLOCK), 0, ctx->stream, g, ct.tile_off, 0u, (uint64_t)0);
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_dssp_labels<true>), dim3((uint32_t)ct.blocks), dim3(BLOCK), 0, ctx->stream, g, ct.tile_off, 0u, (uint64_t)0);
-    } else {
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_dssp_flags<false>), dim3((uint32_t)ct.blocks), dim3(BLOCK), 0, ctx->stream, g, (const uint64_t*)nullptr, ct.tiles_per_entry,
-                           ct.n_padded);
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_dssp_labels<false>), dim3((uint32_t)ct.blocks), dim3(BLOCK), 0, ctx->stream, g, (const uint64_t*)nullptr, ct.tiles_per_entry,
-                           ct.n_padded);
-    }
-    HIP_TRY(hipGetLastError());
-    return FCZ_OK;
+    return ct.run(bound_dev, [&] { hipLaunchKernelGGL(k_dssp_fill, ct.fill_grid(rows), dim3(BLOCK), 0, ctx->stream, g, 2); },
+                  [&](auto P, dim3 grid, const uint64_t* tile_off, uint32_t tiles_per_entry, uint64_t n_padded) {
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_dssp_flags<decltype(P)::value>), grid, dim3(BLOCK), 0, ctx->stream, g, tile_off, tiles_per_entry, n_padded);
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_dssp_labels<decltype(P)::value>), grid, dim3(BLOCK), 0, ctx->stream, g, tile_off, tiles_per_entry, n_padded);
+    });
 }
+
+// fcz_dssp and fcz_dssp_packed: the host arrays through DENSE_IN 0 .. 3 and DSSP_OUT 10 .. 15, both steps
+static int dssp_host(fcz_ctx* ctx, const float* pos, const uint8_t* mask, const uint8_t* aatype, const uint32_t* bound, bool packed, uint32_t n, uint32_t rows_per,
+                     int layout, int32_t* acc_index, float* acc_energy, int32_t* don_index, float* don_energy, uint8_t* ss, uint8_t* ss_mask) {
+    const dense_bytes b(packed, n, rows_per, layout, bound);
+    const size_t nt = b.rows * 2 * 4;
+    return staged_call(ctx, {{pos, b.pos, DENSE_IN}, {mask, b.mask, DENSE_IN + 1}, {aatype, b.rows, DENSE_IN + 2}, {bound, b.bound, DENSE_IN + 3}},
+                       {{acc_index, nt, DSSP_OUT}, {acc_energy, nt, DSSP_OUT + 1}, {don_index, nt, DSSP_OUT + 2}, {don_energy, nt, DSSP_OUT + 3},
+                        {ss, b.rows, DSSP_OUT + 4}, {ss_mask, b.rows, DSSP_OUT + 5}},
+                       [&](const void* const* in, void* const* out) {
+        const float* pos_dev = (const float*)in[0];
+        const uint8_t* mask_dev = (const uint8_t*)in[1], * aatype_dev = (const uint8_t*)in[2];
+        const uint32_t* bound_dev = (const uint32_t*)in[3];
+        int rc = hbond_rows(ctx, pos_dev, mask_dev, aatype_dev, bound_dev, packed, n, rows_per, layout, (int32_t*)out[0], (float*)out[1], (int32_t*)out[2], (float*)out[3]);
+        if (rc) return rc;
+        return dssp_label_rows(ctx, pos_dev, mask_dev, aatype_dev, bound_dev, packed, n, rows_per, layout, (int32_t*)out[0], (float*)out[1], (uint8_t*)out[4],
+                               (uint8_t*)out[5]);
+    });
+}
+
+extern "C" {
+
+int fcz_hbond_pass(void) { return (int)HBOND_PASS; }
 
 int fcz_hbond_dev(fcz_ctx* ctx, const float* pos_dev, const uint8_t* mask_dev, const uint8_t* aatype_dev, const uint32_t* length_dev, uint32_t n, uint32_t L,
                   int layout, int32_t* acc_index_dev, float* acc_energy_dev, int32_t* don_index_dev, float* don_energy_dev) {
-    if (!dssp_args_ok(ctx, pos_dev, mask_dev, layout, L, {acc_index_dev, acc_energy_dev, don_index_dev, don_energy_dev}) || L == 0) return FCZ_E_INVALID_ARG;
+    if (!dssp_args_ok(ctx, pos_dev, mask_dev, layout, L, {acc_index_dev, acc_energy_dev, don_index_dev, don_energy_dev}) || !bound_ok(false, length_dev, n, L))
+        return FCZ_E_INVALID_ARG;
     return hbond_rows(ctx, pos_dev, mask_dev, aatype_dev, length_dev, false, n, L, layout, acc_index_dev, acc_energy_dev, don_index_dev, don_energy_dev);
 }
 
 int fcz_hbond_packed_dev(fcz_ctx* ctx, const float* pos_dev, const uint8_t* mask_dev, const uint8_t* aatype_dev, const uint32_t* row_off_dev, uint32_t n,
                          uint32_t R, int layout, int32_t* acc_index_dev, float* acc_energy_dev, int32_t* don_index_dev, float* don_energy_dev) {
-    if (!dssp_args_ok(ctx, pos_dev, mask_dev, layout, R, {acc_index_dev, acc_energy_dev, don_index_dev, don_energy_dev}) || (n && !row_off_dev))
+    if (!dssp_args_ok(ctx, pos_dev, mask_dev, layout, R, {acc_index_dev, acc_energy_dev, don_index_dev, don_energy_dev}) || !bound_ok(true, row_off_dev, n, R))
         return FCZ_E_INVALID_ARG;
     return hbond_rows(ctx, pos_dev, mask_dev, aatype_dev, row_off_dev, true, n, R, layout, acc_index_dev, acc_energy_dev, don_index_dev, don_energy_dev);
 }
 
 int fcz_dssp_labels_dev(fcz_ctx* ctx, const float* pos_dev, const uint8_t* mask_dev, const uint8_t* aatype_dev, const uint32_t* length_dev, uint32_t n,
                         uint32_t L, int layout, const int32_t* acc_index_dev, const float* acc_energy_dev, uint8_t* ss_dev, uint8_t* ss_mask_dev) {
-    if (!dssp_args_ok(ctx, pos_dev, mask_dev, layout, L, {acc_index_dev, acc_energy_dev, ss_dev, ss_mask_dev}) || L == 0) return FCZ_E_INVALID_ARG;
+    if (!dssp_args_ok(ctx, pos_dev, mask_dev, layout, L, {acc_index_dev, acc_energy_dev, ss_dev, ss_mask_dev}) || !bound_ok(false, length_dev, n, L))
+        return FCZ_E_INVALID_ARG;
     return dssp_label_rows(ctx, pos_dev, mask_dev, aatype_dev, length_dev, false, n, L, layout, acc_index_dev, acc_energy_dev, ss_dev, ss_mask_dev);
 }
 
 int fcz_dssp_labels_packed_dev(fcz_ctx* ctx, const float* pos_dev, const uint8_t* mask_dev, const uint8_t* aatype_dev, const uint32_t* row_off_dev, uint32_t n,
                                uint32_t R, int layout, const int32_t* acc_index_dev, const float* acc_energy_dev, uint8_t* ss_dev, uint8_t* ss_mask_dev) {
-    if (!dssp_args_ok(ctx, pos_dev, mask_dev, layout, R, {acc_index_dev, acc_energy_dev, ss_dev, ss_mask_dev}) || (n && !row_off_dev)) return FCZ_E_INVALID_ARG;
+    if (!dssp_args_ok(ctx, pos_dev, mask_dev, layout, R, {acc_index_dev, acc_energy_dev, ss_dev, ss_mask_dev}) || !bound_ok(true, row_off_dev, n, R))
+        return FCZ_E_INVALID_ARG;
     return dssp_label_rows(ctx, pos_dev, mask_dev, aatype_dev, row_off_dev, true, n, R, layout, acc_index_dev, acc_energy_dev, ss_dev, ss_mask_dev);
-}
-
-// fcz_dssp and fcz_dssp_packed: the host arrays through DENSE_IN 0 .. 3 and DSSP_OUT 10 .. 15, both steps
-static int dssp_host(fcz_ctx* ctx, const float* pos, const uint8_t* mask, const uint8_t* aatype, const uint32_t* bound, bool packed, uint32_t n, uint32_t rows_per,
-                     int layout, int32_t* acc_index, float* acc_energy, int32_t* don_index, float* don_energy, uint8_t* ss, uint8_t* ss_mask) {
-    HIP_TRY(hipSetDevice(ctx->device));
-    claim_staging(ctx);
-    const size_t rows = packed ? (size_t)rows_per : (size_t)n * rows_per, A = (size_t)fcz_dense_width(layout);
-    if (rows == 0) return FCZ_OK;
-    const size_t nb = bound ? sizeof(uint32_t) * ((size_t)n + (packed ? 1 : 0)) : 0, np = rows * A * 3 * sizeof(float), nm = rows * A, nt = rows * 2 * 4;
-    int rc;
-    if ((rc = ctx->pool[DENSE_IN].ensure(np)) || (rc = ctx->pool[DENSE_IN + 1].ensure(nm)) || (rc = ctx->pool[DENSE_IN + 2].ensure(aatype ? rows : 0)) ||
-        (rc = ctx->pool[DENSE_IN + 3].ensure(nb)))
-        return rc;
-    for (int k = 0; k < 4; k++) if ((rc = ctx->pool[DSSP_OUT + k].ensure(nt))) return rc;
-    if ((rc = ctx->pool[DSSP_OUT + 4].ensure(rows)) || (rc = ctx->pool[DSSP_OUT + 5].ensure(rows))) return rc;
-    HIP_TRY(hipMemcpyAsync(ctx->pool[DENSE_IN].p, pos, np, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(ctx->pool[DENSE_IN + 1].p, mask, nm, hipMemcpyHostToDevice, ctx->stream));
-    if (aatype) HIP_TRY(hipMemcpyAsync(ctx->pool[DENSE_IN + 2].p, aatype, rows, hipMemcpyHostToDevice, ctx->stream));
-    if (nb) HIP_TRY(hipMemcpyAsync(ctx->pool[DENSE_IN + 3].p, bound, nb, hipMemcpyHostToDevice, ctx->stream));
-    const float* pos_dev = ctx->pool[DENSE_IN].as<float>();
-    const uint8_t* mask_dev = ctx->pool[DENSE_IN + 1].as<uint8_t>();
-    const uint8_t* aatype_dev = aatype ? ctx->pool[DENSE_IN + 2].as<uint8_t>() : nullptr;
-    const uint32_t* bound_dev = nb ? ctx->pool[DENSE_IN + 3].as<uint32_t>() : nullptr;
-    rc = hbond_rows(ctx, pos_dev, mask_dev, aatype_dev, bound_dev, packed, n, rows_per, layout, ctx->pool[DSSP_OUT].as<int32_t>(), ctx->pool[DSSP_OUT + 1].as<float>(),
-                    ctx->pool[DSSP_OUT + 2].as<int32_t>(), ctx->pool[DSSP_OUT + 3].as<float>());
-    if (rc) return rc;
-    rc = dssp_label_rows(ctx, pos_dev, mask_dev, aatype_dev, bound_dev, packed, n, rows_per, layout, ctx->pool[DSSP_OUT].as<int32_t>(),
-                         ctx->pool[DSSP_OUT + 1].as<float>(), ctx->pool[DSSP_OUT + 4].as<uint8_t>(), ctx->pool[DSSP_OUT + 5].as<uint8_t>());
-    if (rc) return rc;
-    void* host[6] = {acc_index, acc_energy, don_index, don_energy, ss, ss_mask};
-    for (int k = 0; k < 6; k++) HIP_TRY(hipMemcpyAsync(host[k], ctx->pool[DSSP_OUT + k].p, k < 4 ? nt : rows, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return FCZ_OK;
 }
 
 int fcz_dssp(fcz_ctx* ctx, const float* pos, const uint8_t* mask, const uint8_t* aatype, const uint32_t* length, uint32_t n, uint32_t L, int layout,
              int32_t* acc_index, float* acc_energy, int32_t* don_index, float* don_energy, uint8_t* ss, uint8_t* ss_mask) {
-    if (!dssp_args_ok(ctx, pos, mask, layout, L, {acc_index, acc_energy, don_index, don_energy, ss, ss_mask}) || L == 0) return FCZ_E_INVALID_ARG;
+    if (!dssp_args_ok(ctx, pos, mask, layout, L, {acc_index, acc_energy, don_index, don_energy, ss, ss_mask}) || !bound_ok(false, length, n, L))
+        return FCZ_E_INVALID_ARG;
     return dssp_host(ctx, pos, mask, aatype, length, false, n, L, layout, acc_index, acc_energy, don_index, don_energy, ss, ss_mask);
 }
 
 int fcz_dssp_packed(fcz_ctx* ctx, const float* pos, const uint8_t* mask, const uint8_t* aatype, const uint32_t* row_off, uint32_t n, uint32_t R, int layout,
                     int32_t* acc_index, float* acc_energy, int32_t* don_index, float* don_energy, uint8_t* ss, uint8_t* ss_mask) {
-    if (!dssp_args_ok(ctx, pos, mask, layout, R, {acc_index, acc_energy, don_index, don_energy, ss, ss_mask}) || (n && !row_off)) return FCZ_E_INVALID_ARG;
+    if (!dssp_args_ok(ctx, pos, mask, layout, R, {acc_index, acc_energy, don_index, don_energy, ss, ss_mask}) || !bound_ok(true, row_off, n, R))
+        return FCZ_E_INVALID_ARG;
     return dssp_host(ctx, pos, mask, aatype, row_off, true, n, R, layout, acc_index, acc_energy, don_index, don_energy, ss, ss_mask);
 }
+
+}  // extern "C"
 
 // ------------------------------------------------------------------------------------------------
 // per-residue solvent accessibility of dense tensors (fcz_sasa.h; no counterpart in the reference)
 // ------------------------------------------------------------------------------------------------
-int fcz_sasa_pass(void) { return (int)SASA_PASS; }
-
 // Bondi's radius of the element an atom's name begins with; 0: no such element among the twenty types
 static float sasa_element_radius(const char* name) {
     switch (name[0]) { case 'C': return 1.70f; case 'N': return 1.55f; case 'O': return 1.52f; case 'S': return 1.80f; default: return 0.0f; }
-}
-
-int fcz_sasa_default_radii(int layout, float* out) {
-    const int A = fcz_dense_width(layout);
-    if (A <= 0 || !out) return FCZ_E_INVALID_ARG;
-    float own[FCZ_N_RES_CODES][DN_MAX_WIDTH] = {}, any[DN_MAX_WIDTH] = {};    // per residue code, and over all of them
-    for (int rc = 0; rc < FCZ_N_RES_CODES; rc++)
-        for (int j = 0; j < host_tab::h_res_natoms[rc]; j++) {
-            const int ac = host_tab::h_res_atom[rc][j], slot = fcz_dense_slot(layout, rc, ac);
-            if (slot >= 0) own[rc][slot] = any[slot] = sasa_element_radius(host_tab::h_atom_name[ac]);
-        }
-    // atom14: a slot's atom depends on the type (row 20: the backbone-only codes). atom37 / backbone4: a slot holds the same atom in
-    // every type, so every row is the same and the mask alone says which atoms a residue has. OXT is in no residue's table: 0.
-    for (int ty = 0; ty < (int)SASA_TYPES; ty++)
-        for (int a = 0; a < A; a++) out[ty * A + a] = layout == FCZ_DENSE_ATOM14 ? own[ty][a] : any[a];
-    return FCZ_OK;
 }
 
 // rows: L (padded) or R (packed). Fills tab from radius_table (NULL: the default) when everything is acceptable.
@@ -2073,30 +2081,6 @@ static bool sasa_args_ok(const fcz_ctx* ctx, const float* pos, const uint8_t* ma
     return true;
 }
 
-// The query tiles of the accessibility sweep: chain_tiles with SASA_TILE_ROWS rows a tile (fcz_sasa.h), in the same scratch.
-struct sasa_tiles {
-    uint64_t* tile_off = nullptr; uint32_t tiles_per_entry = 0; uint64_t n_padded = 0, blocks = 0;
-    int reserve(fcz_ctx* ctx, bool packed, uint32_t n, uint32_t rows) {
-        const uint32_t max_blocks = (uint32_t)ctx->n_cu * 16u;
-        tiles_per_entry = (uint32_t)(((uint64_t)rows + SASA_TILE_ROWS - 1) / SASA_TILE_ROWS);
-        if (packed) {
-            int rc = ctx->knn_tiles.ensure(sizeof(uint64_t) * (2 * (size_t)n + 1)); if (rc) return rc;
-            tile_off = ctx->knn_tiles.as<uint64_t>() + n;
-            tiles_per_entry = 0;
-            blocks = std::min<uint64_t>((uint64_t)rows / SASA_TILE_ROWS + n, max_blocks);   // the tiles are counted on the device: at most this many
-        } else {
-            n_padded = (uint64_t)n * tiles_per_entry;
-            blocks = std::min<uint64_t>(n_padded, max_blocks);
-        }
-        return FCZ_OK;
-    }
-    int scan(fcz_ctx* ctx, const uint32_t* row_off_dev, uint32_t n, uint32_t R) {
-        const uint32_t max_blocks = (uint32_t)ctx->n_cu * 16u;
-        hipLaunchKernelGGL(k_sasa_tiles, dim3(std::min(grid_for(n, BLOCK), max_blocks)), dim3(BLOCK), 0, ctx->stream, row_off_dev, n, R, ctx->knn_tiles.as<uint64_t>());
-        return device_scan<uint64_t>(ctx, ctx->knn_tiles.as<uint64_t>(), tile_off, n);
-    }
-};
-
 // fcz_sasa_dev (bound_dev is length [n] or NULL, rows = L) and fcz_sasa_packed_dev (bound_dev = row_off [n + 1], rows = R)
 static int sasa_rows(fcz_ctx* ctx, const float* pos_dev, const uint8_t* mask_dev, const uint8_t* aatype_dev, const uint32_t* bound_dev, bool packed, uint32_t n,
                      uint32_t rows, int layout, const sasa_table& tab, float probe, const float* points_dev, uint32_t n_points, int16_t* sasa_points_dev,
@@ -2108,24 +2092,47 @@ static int sasa_rows(fcz_ctx* ctx, const float* pos_dev, const uint8_t* mask_dev
     g.A = (uint32_t)fcz_dense_width(layout); g.P = n_points; g.probe = probe; g.points = points_dev;
     g.scale = 0x1.921fb54442d18p+3 / (double)n_points;                        // 4 pi / P: one double division
     g.sasa_points = sasa_points_dev; g.sasa = sasa_dev; g.sasa_mask = sasa_mask_dev;
-    const uint32_t max_blocks = (uint32_t)ctx->n_cu * 16u;
     const bool small = n_points <= SASA_SMALL_POINTS;
-    sasa_tiles st;
-    if (!packed || n) { int rc = st.reserve(ctx, packed, n, rows); if (rc) return rc; }
+    chain_tiles ct(ctx, packed, n, rows, SASA_TILE_ROWS);
+    int rc = ct.reserve(); if (rc) return rc;
     span_guard sg(ctx, "sasa");
-    if (packed) {
-        hipLaunchKernelGGL(k_sasa_fill, dim3((uint32_t)std::min<uint64_t>(((uint64_t)rows + BLOCK - 1) / BLOCK, max_blocks)), dim3(BLOCK), 0, ctx->stream, g);
-        if (n == 0) { HIP_TRY(hipGetLastError()); return FCZ_OK; }
-        int rc = st.scan(ctx, bound_dev, n, rows); if (rc) return rc;
-        if (small) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_sasa_points<true, true>), dim3((uint32_t)st.blocks), dim3(BLOCK), 0, ctx->stream, g, tab, st.tile_off, 0u, (uint64_t)0);
-        else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_sasa_points<true, false>), dim3((uint32_t)st.blocks), dim3(BLOCK), 0, ctx->stream, g, tab, st.tile_off, 0u, (uint64_t)0);
-    } else {
-        if (small) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_sasa_points<false, true>), dim3((uint32_t)st.blocks), dim3(BLOCK), 0, ctx->stream, g, tab, (const uint64_t*)nullptr,
-                                      st.tiles_per_entry, st.n_padded);
-        else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_sasa_points<false, false>), dim3((uint32_t)st.blocks), dim3(BLOCK), 0, ctx->stream, g, tab, (const uint64_t*)nullptr,
-                                st.tiles_per_entry, st.n_padded);
-    }
-    HIP_TRY(hipGetLastError());
+    return ct.run(bound_dev, [&] { hipLaunchKernelGGL(k_sasa_fill, ct.fill_grid(rows), dim3(BLOCK), 0, ctx->stream, g); },
+                  [&](auto P, dim3 grid, const uint64_t* tile_off, uint32_t tiles_per_entry, uint64_t n_padded) {
+        if (small) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_sasa_points<decltype(P)::value, true>), grid, dim3(BLOCK), 0, ctx->stream, g, tab, tile_off, tiles_per_entry, n_padded);
+        else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_sasa_points<decltype(P)::value, false>), grid, dim3(BLOCK), 0, ctx->stream, g, tab, tile_off, tiles_per_entry, n_padded);
+    });
+}
+
+// fcz_sasa and fcz_sasa_packed: the host arrays through DENSE_IN 0 .. 3, SASA_POINTS 4 and SASA_OUT 10 .. 12
+static int sasa_host(fcz_ctx* ctx, const float* pos, const uint8_t* mask, const uint8_t* aatype, const uint32_t* bound, bool packed, uint32_t n, uint32_t rows_per,
+                     int layout, const sasa_table& tab, float probe, const float* points, uint32_t n_points, int16_t* sasa_points, float* sasa, uint8_t* sasa_mask) {
+    const dense_bytes b(packed, n, rows_per, layout, bound);
+    return staged_call(ctx, {{pos, b.pos, DENSE_IN}, {mask, b.mask, DENSE_IN + 1}, {aatype, b.rows, DENSE_IN + 2}, {bound, b.bound, DENSE_IN + 3},
+                             {points, (size_t)n_points * 3 * sizeof(float), SASA_POINTS}},
+                       {{sasa_points, b.mask * sizeof(int16_t), SASA_OUT}, {sasa, b.rows * sizeof(float), SASA_OUT + 1}, {sasa_mask, b.rows, SASA_OUT + 2}},
+                       [&](const void* const* in, void* const* out) {
+        return sasa_rows(ctx, (const float*)in[0], (const uint8_t*)in[1], (const uint8_t*)in[2], (const uint32_t*)in[3], packed, n, rows_per, layout, tab, probe,
+                         (const float*)in[4], n_points, (int16_t*)out[0], (float*)out[1], (uint8_t*)out[2]);
+    });
+}
+
+extern "C" {
+
+int fcz_sasa_pass(void) { return (int)SASA_PASS; }
+
+int fcz_sasa_default_radii(int layout, float* out) {
+    const int A = fcz_dense_width(layout);
+    if (A <= 0 || !out) return FCZ_E_INVALID_ARG;
+    float own[FCZ_N_RES_CODES][DN_MAX_WIDTH] = {}, any[DN_MAX_WIDTH] = {};    // per residue code, and over all of them
+    for (int rc = 0; rc < FCZ_N_RES_CODES; rc++)
+        for (int j = 0; j < host_tab::h_res_natoms[rc]; j++) {
+            const int ac = host_tab::h_res_atom[rc][j], slot = fcz_dense_slot(layout, rc, ac);
+            if (slot >= 0) own[rc][slot] = any[slot] = sasa_element_radius(host_tab::h_atom_name[ac]);
+        }
+    // atom14: a slot's atom depends on the type (row 20: the backbone-only codes). atom37 / backbone4: a slot holds the same atom in
+    // every type, so every row is the same and the mask alone says which atoms a residue has. OXT is in no residue's table: 0.
+    for (int ty = 0; ty < (int)SASA_TYPES; ty++)
+        for (int a = 0; a < A; a++) out[ty * A + a] = layout == FCZ_DENSE_ATOM14 ? own[ty][a] : any[a];
     return FCZ_OK;
 }
 
@@ -2134,7 +2141,7 @@ int fcz_sasa_dev(fcz_ctx* ctx, const float* pos_dev, const uint8_t* mask_dev, co
                  uint8_t* sasa_mask_dev) {
     sasa_table tab;
     if (!sasa_args_ok(ctx, pos_dev, mask_dev, aatype_dev, layout, L, radius_table, probe, points_dev, n_points, {sasa_points_dev, sasa_dev, sasa_mask_dev}, &tab) ||
-        L == 0)
+        !bound_ok(false, length_dev, n, L))
         return FCZ_E_INVALID_ARG;
     return sasa_rows(ctx, pos_dev, mask_dev, aatype_dev, length_dev, false, n, L, layout, tab, probe, points_dev, n_points, sasa_points_dev, sasa_dev, sasa_mask_dev);
 }
@@ -2144,44 +2151,15 @@ int fcz_sasa_packed_dev(fcz_ctx* ctx, const float* pos_dev, const uint8_t* mask_
                         float* sasa_dev, uint8_t* sasa_mask_dev) {
     sasa_table tab;
     if (!sasa_args_ok(ctx, pos_dev, mask_dev, aatype_dev, layout, R, radius_table, probe, points_dev, n_points, {sasa_points_dev, sasa_dev, sasa_mask_dev}, &tab) ||
-        (n && !row_off_dev))
+        !bound_ok(true, row_off_dev, n, R))
         return FCZ_E_INVALID_ARG;
     return sasa_rows(ctx, pos_dev, mask_dev, aatype_dev, row_off_dev, true, n, R, layout, tab, probe, points_dev, n_points, sasa_points_dev, sasa_dev, sasa_mask_dev);
-}
-
-// fcz_sasa and fcz_sasa_packed: the host arrays through DENSE_IN 0 .. 3, SASA_POINTS 4 and SASA_OUT 10 .. 12
-static int sasa_host(fcz_ctx* ctx, const float* pos, const uint8_t* mask, const uint8_t* aatype, const uint32_t* bound, bool packed, uint32_t n, uint32_t rows_per,
-                     int layout, const sasa_table& tab, float probe, const float* points, uint32_t n_points, int16_t* sasa_points, float* sasa, uint8_t* sasa_mask) {
-    HIP_TRY(hipSetDevice(ctx->device));
-    claim_staging(ctx);
-    const size_t rows = packed ? (size_t)rows_per : (size_t)n * rows_per, A = (size_t)fcz_dense_width(layout);
-    if (rows == 0) return FCZ_OK;
-    const size_t nb = bound ? sizeof(uint32_t) * ((size_t)n + (packed ? 1 : 0)) : 0, np = rows * A * 3 * sizeof(float), nm = rows * A, nu = (size_t)n_points * 3 * sizeof(float);
-    int rc;
-    if ((rc = ctx->pool[DENSE_IN].ensure(np)) || (rc = ctx->pool[DENSE_IN + 1].ensure(nm)) || (rc = ctx->pool[DENSE_IN + 2].ensure(aatype ? rows : 0)) ||
-        (rc = ctx->pool[DENSE_IN + 3].ensure(nb)) || (rc = ctx->pool[SASA_POINTS].ensure(nu)) || (rc = ctx->pool[SASA_OUT].ensure(nm * sizeof(int16_t))) ||
-        (rc = ctx->pool[SASA_OUT + 1].ensure(rows * sizeof(float))) || (rc = ctx->pool[SASA_OUT + 2].ensure(rows)))
-        return rc;
-    HIP_TRY(hipMemcpyAsync(ctx->pool[DENSE_IN].p, pos, np, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(ctx->pool[DENSE_IN + 1].p, mask, nm, hipMemcpyHostToDevice, ctx->stream));
-    if (aatype) HIP_TRY(hipMemcpyAsync(ctx->pool[DENSE_IN + 2].p, aatype, rows, hipMemcpyHostToDevice, ctx->stream));
-    if (nb) HIP_TRY(hipMemcpyAsync(ctx->pool[DENSE_IN + 3].p, bound, nb, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(ctx->pool[SASA_POINTS].p, points, nu, hipMemcpyHostToDevice, ctx->stream));
-    rc = sasa_rows(ctx, ctx->pool[DENSE_IN].as<float>(), ctx->pool[DENSE_IN + 1].as<uint8_t>(), aatype ? ctx->pool[DENSE_IN + 2].as<uint8_t>() : nullptr,
-                   nb ? ctx->pool[DENSE_IN + 3].as<uint32_t>() : nullptr, packed, n, rows_per, layout, tab, probe, ctx->pool[SASA_POINTS].as<float>(), n_points,
-                   ctx->pool[SASA_OUT].as<int16_t>(), ctx->pool[SASA_OUT + 1].as<float>(), ctx->pool[SASA_OUT + 2].as<uint8_t>());
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(sasa_points, ctx->pool[SASA_OUT].p, nm * sizeof(int16_t), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(sasa, ctx->pool[SASA_OUT + 1].p, rows * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(sasa_mask, ctx->pool[SASA_OUT + 2].p, rows, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return FCZ_OK;
 }
 
 int fcz_sasa(fcz_ctx* ctx, const float* pos, const uint8_t* mask, const uint8_t* aatype, const uint32_t* length, uint32_t n, uint32_t L, int layout,
              const float* radius_table, float probe, const float* points, uint32_t n_points, int16_t* sasa_points, float* sasa, uint8_t* sasa_mask) {
     sasa_table tab;
-    if (!sasa_args_ok(ctx, pos, mask, aatype, layout, L, radius_table, probe, points, n_points, {sasa_points, sasa, sasa_mask}, &tab) || L == 0)
+    if (!sasa_args_ok(ctx, pos, mask, aatype, layout, L, radius_table, probe, points, n_points, {sasa_points, sasa, sasa_mask}, &tab) || !bound_ok(false, length, n, L))
         return FCZ_E_INVALID_ARG;
     return sasa_host(ctx, pos, mask, aatype, length, false, n, L, layout, tab, probe, points, n_points, sasa_points, sasa, sasa_mask);
 }
@@ -2189,16 +2167,16 @@ int fcz_sasa(fcz_ctx* ctx, const float* pos, const uint8_t* mask, const uint8_t*
 int fcz_sasa_packed(fcz_ctx* ctx, const float* pos, const uint8_t* mask, const uint8_t* aatype, const uint32_t* row_off, uint32_t n, uint32_t R, int layout,
                     const float* radius_table, float probe, const float* points, uint32_t n_points, int16_t* sasa_points, float* sasa, uint8_t* sasa_mask) {
     sasa_table tab;
-    if (!sasa_args_ok(ctx, pos, mask, aatype, layout, R, radius_table, probe, points, n_points, {sasa_points, sasa, sasa_mask}, &tab) || (n && !row_off))
+    if (!sasa_args_ok(ctx, pos, mask, aatype, layout, R, radius_table, probe, points, n_points, {sasa_points, sasa, sasa_mask}, &tab) || !bound_ok(true, row_off, n, R))
         return FCZ_E_INVALID_ARG;
     return sasa_host(ctx, pos, mask, aatype, row_off, true, n, R, layout, tab, probe, points, n_points, sasa_points, sasa, sasa_mask);
 }
 
+}  // extern "C"
+
 // ------------------------------------------------------------------------------------------------
 // steric clashes and peptide-link violations of dense tensors (fcz_violations.h; no counterpart in the reference)
 // ------------------------------------------------------------------------------------------------
-int fcz_violations_pass(void) { return (int)VIOL_PASS; }
-
 static bool viol_out_ok(const fcz_violations_out* o) {
     return o && o->clash_atom && o->clash_count && o->clash_depth && o->clash_partner && o->viol_mask && o->link_mask && o->link_length && o->link_cos &&
            o->link_violation && o->chain_counts;
@@ -2222,32 +2200,6 @@ static bool viol_args_ok(const fcz_ctx* ctx, const float* pos, const uint8_t* ma
     return true;
 }
 
-// The query tiles of the clash sweep: chain_tiles with viol_tile_rows(A) rows a tile (fcz_violations.h), in the same scratch.
-struct viol_tiles {
-    uint64_t* tile_off = nullptr; uint32_t tile_rows = 0, tiles_per_entry = 0; uint64_t n_padded = 0, blocks = 0;
-    int reserve(fcz_ctx* ctx, bool packed, uint32_t n, uint32_t rows, uint32_t A) {
-        const uint32_t max_blocks = (uint32_t)ctx->n_cu * 12u;
-        tile_rows = viol_tile_rows(A);
-        tiles_per_entry = (uint32_t)(((uint64_t)rows + tile_rows - 1) / tile_rows);
-        if (packed) {
-            int rc = ctx->knn_tiles.ensure(sizeof(uint64_t) * (2 * (size_t)n + 1)); if (rc) return rc;
-            tile_off = ctx->knn_tiles.as<uint64_t>() + n;
-            tiles_per_entry = 0;
-            blocks = std::min<uint64_t>((uint64_t)rows / tile_rows + n, max_blocks);   // the tiles are counted on the device: at most this many
-        } else {
-            n_padded = (uint64_t)n * tiles_per_entry;
-            blocks = std::min<uint64_t>(n_padded, max_blocks);
-        }
-        return FCZ_OK;
-    }
-    int scan(fcz_ctx* ctx, const uint32_t* row_off_dev, uint32_t n, uint32_t R) {
-        const uint32_t max_blocks = (uint32_t)ctx->n_cu * 12u;
-        hipLaunchKernelGGL(k_viol_tiles, dim3(std::min(grid_for(n, BLOCK), max_blocks)), dim3(BLOCK), 0, ctx->stream, row_off_dev, n, R, tile_rows,
-                           ctx->knn_tiles.as<uint64_t>());
-        return device_scan<uint64_t>(ctx, ctx->knn_tiles.as<uint64_t>(), tile_off, n);
-    }
-};
-
 // fcz_violations_dev (bound_dev is length [n] or NULL, rows = L) and fcz_violations_packed_dev (bound_dev = row_off [n + 1], rows = R)
 static int viol_rows(fcz_ctx* ctx, const float* pos_dev, const uint8_t* mask_dev, const uint8_t* aatype_dev, const uint32_t* bound_dev, bool packed, uint32_t n,
                      uint32_t rows, int layout, const sasa_table& tab, float tolerance, float link_factor, const fcz_violations_out& o) {
@@ -2263,88 +2215,69 @@ static int viol_rows(fcz_ctx* ctx, const float* pos_dev, const uint8_t* mask_dev
     g.clash_atom = o.clash_atom; g.clash_count = o.clash_count; g.clash_depth = o.clash_depth; g.clash_partner = o.clash_partner; g.viol_mask = o.viol_mask;
     g.link_mask = o.link_mask; g.link_length = o.link_length; g.link_cos = o.link_cos; g.link_violation = o.link_violation;
     g.chain_counts = reinterpret_cast<unsigned long long*>(o.chain_counts);
-    const uint32_t max_blocks = (uint32_t)ctx->n_cu * 12u;
-    viol_tiles vt;
-    if (n) { int rc = vt.reserve(ctx, packed, n, rows, g.A); if (rc) return rc; }
+    chain_tiles ct(ctx, packed, n, rows, viol_tile_rows(g.A), 12u);
+    int rc = ct.reserve(); if (rc) return rc;
     span_guard sg(ctx, "violations");
     if (n) HIP_TRY(hipMemsetAsync(o.chain_counts, 0, sizeof(int64_t) * 4 * (size_t)n, ctx->stream));
     if (rows == 0) return FCZ_OK;                                             // (packed, chains without a row: their counters are 0)
-    if (packed) {
-        hipLaunchKernelGGL(k_viol_fill, dim3((uint32_t)std::min<uint64_t>(((uint64_t)rows + BLOCK - 1) / BLOCK, max_blocks)), dim3(BLOCK), 0, ctx->stream, g);
-        if (n == 0) { HIP_TRY(hipGetLastError()); return FCZ_OK; }
-        int rc = vt.scan(ctx, bound_dev, n, rows); if (rc) return rc;
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_violations<true>), dim3((uint32_t)vt.blocks), dim3(BLOCK), 0, ctx->stream, g, tab, vt.tile_off, 0u, (uint64_t)0);
-    } else {
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_violations<false>), dim3((uint32_t)vt.blocks), dim3(BLOCK), 0, ctx->stream, g, tab, (const uint64_t*)nullptr,
-                           vt.tiles_per_entry, vt.n_padded);
-    }
-    HIP_TRY(hipGetLastError());
-    return FCZ_OK;
+    return ct.run(bound_dev, [&] { hipLaunchKernelGGL(k_viol_fill, ct.fill_grid(rows), dim3(BLOCK), 0, ctx->stream, g); },
+                  [&](auto P, dim3 grid, const uint64_t* tile_off, uint32_t tiles_per_entry, uint64_t n_padded) {
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_violations<decltype(P)::value>), grid, dim3(BLOCK), 0, ctx->stream, g, tab, tile_off, tiles_per_entry, n_padded);
+    });
 }
+
+// fcz_violations and fcz_violations_packed: the host arrays through DENSE_IN 0 .. 3 and VIOL_OUT 10 .. 19, the outputs in the struct's order
+static int viol_host(fcz_ctx* ctx, const float* pos, const uint8_t* mask, const uint8_t* aatype, const uint32_t* bound, bool packed, uint32_t n, uint32_t rows_per,
+                     int layout, const sasa_table& tab, float tolerance, float link_factor, const fcz_violations_out& o) {
+    const dense_bytes b(packed, n, rows_per, layout, bound);
+    const size_t r = b.rows;
+    return staged_call(ctx, {{pos, b.pos, DENSE_IN}, {mask, b.mask, DENSE_IN + 1}, {aatype, r, DENSE_IN + 2}, {bound, b.bound, DENSE_IN + 3}},
+                       {{o.clash_atom, b.mask, VIOL_OUT}, {o.clash_count, r * 4, VIOL_OUT + 1}, {o.clash_depth, r * 4, VIOL_OUT + 2}, {o.clash_partner, r * 4, VIOL_OUT + 3},
+                        {o.viol_mask, r, VIOL_OUT + 4}, {o.link_mask, r, VIOL_OUT + 5}, {o.link_length, r * 4, VIOL_OUT + 6}, {o.link_cos, r * 8, VIOL_OUT + 7},
+                        {o.link_violation, r, VIOL_OUT + 8}, {o.chain_counts, (size_t)n * 4 * sizeof(int64_t), VIOL_OUT + 9}},
+                       [&](const void* const* in, void* const* out) {
+        const fcz_violations_out d{(uint8_t*)out[0], (int32_t*)out[1], (float*)out[2], (int32_t*)out[3], (uint8_t*)out[4], (uint8_t*)out[5], (float*)out[6],
+                                   (float*)out[7], (uint8_t*)out[8], (int64_t*)out[9]};
+        return viol_rows(ctx, (const float*)in[0], (const uint8_t*)in[1], (const uint8_t*)in[2], (const uint32_t*)in[3], packed, n, rows_per, layout, tab, tolerance,
+                         link_factor, d);
+    });
+}
+
+extern "C" {
+
+int fcz_violations_pass(void) { return (int)VIOL_PASS; }
 
 int fcz_violations_dev(fcz_ctx* ctx, const float* pos_dev, const uint8_t* mask_dev, const uint8_t* aatype_dev, const uint32_t* length_dev, uint32_t n, uint32_t L,
                        int layout, const float* radius_table, float tolerance, float link_factor, const fcz_violations_out* out_dev) {
     sasa_table tab;
-    if (!viol_args_ok(ctx, pos_dev, mask_dev, aatype_dev, layout, L, radius_table, tolerance, link_factor, out_dev, &tab) || L == 0) return FCZ_E_INVALID_ARG;
+    if (!viol_args_ok(ctx, pos_dev, mask_dev, aatype_dev, layout, L, radius_table, tolerance, link_factor, out_dev, &tab) || !bound_ok(false, length_dev, n, L))
+        return FCZ_E_INVALID_ARG;
     return viol_rows(ctx, pos_dev, mask_dev, aatype_dev, length_dev, false, n, L, layout, tab, tolerance, link_factor, *out_dev);
 }
 
 int fcz_violations_packed_dev(fcz_ctx* ctx, const float* pos_dev, const uint8_t* mask_dev, const uint8_t* aatype_dev, const uint32_t* row_off_dev, uint32_t n,
                               uint32_t R, int layout, const float* radius_table, float tolerance, float link_factor, const fcz_violations_out* out_dev) {
     sasa_table tab;
-    if (!viol_args_ok(ctx, pos_dev, mask_dev, aatype_dev, layout, R, radius_table, tolerance, link_factor, out_dev, &tab) || (n && !row_off_dev))
+    if (!viol_args_ok(ctx, pos_dev, mask_dev, aatype_dev, layout, R, radius_table, tolerance, link_factor, out_dev, &tab) || !bound_ok(true, row_off_dev, n, R))
         return FCZ_E_INVALID_ARG;
     return viol_rows(ctx, pos_dev, mask_dev, aatype_dev, row_off_dev, true, n, R, layout, tab, tolerance, link_factor, *out_dev);
-}
-
-// fcz_violations and fcz_violations_packed: the host arrays through DENSE_IN 0 .. 3 and VIOL_OUT 10 .. 19
-static int viol_host(fcz_ctx* ctx, const float* pos, const uint8_t* mask, const uint8_t* aatype, const uint32_t* bound, bool packed, uint32_t n, uint32_t rows_per,
-                     int layout, const sasa_table& tab, float tolerance, float link_factor, const fcz_violations_out& o) {
-    HIP_TRY(hipSetDevice(ctx->device));
-    claim_staging(ctx);
-    const size_t rows = packed ? (size_t)rows_per : (size_t)n * rows_per, A = (size_t)fcz_dense_width(layout);
-    if (rows == 0 && n == 0) return FCZ_OK;
-    const size_t nb = bound ? sizeof(uint32_t) * ((size_t)n + (packed ? 1 : 0)) : 0, np = rows * A * 3 * sizeof(float), nm = rows * A;
-    // the ten outputs in the struct's order: the host array and its bytes
-    void* const host[10] = {o.clash_atom, o.clash_count, o.clash_depth, o.clash_partner, o.viol_mask, o.link_mask, o.link_length, o.link_cos, o.link_violation,
-                            o.chain_counts};
-    const size_t bytes[10] = {nm, rows * 4, rows * 4, rows * 4, rows, rows, rows * 4, rows * 8, rows, (size_t)n * 4 * sizeof(int64_t)};
-    int rc;
-    if ((rc = ctx->pool[DENSE_IN].ensure(np)) || (rc = ctx->pool[DENSE_IN + 1].ensure(nm)) || (rc = ctx->pool[DENSE_IN + 2].ensure(aatype ? rows : 0)) ||
-        (rc = ctx->pool[DENSE_IN + 3].ensure(nb)))
-        return rc;
-    for (int k = 0; k < 10; k++) if ((rc = ctx->pool[VIOL_OUT + k].ensure(bytes[k]))) return rc;
-    if (np) HIP_TRY(hipMemcpyAsync(ctx->pool[DENSE_IN].p, pos, np, hipMemcpyHostToDevice, ctx->stream));
-    if (nm) HIP_TRY(hipMemcpyAsync(ctx->pool[DENSE_IN + 1].p, mask, nm, hipMemcpyHostToDevice, ctx->stream));
-    if (aatype && rows) HIP_TRY(hipMemcpyAsync(ctx->pool[DENSE_IN + 2].p, aatype, rows, hipMemcpyHostToDevice, ctx->stream));
-    if (nb) HIP_TRY(hipMemcpyAsync(ctx->pool[DENSE_IN + 3].p, bound, nb, hipMemcpyHostToDevice, ctx->stream));
-    fcz_violations_out d{};
-    d.clash_atom = ctx->pool[VIOL_OUT].as<uint8_t>(); d.clash_count = ctx->pool[VIOL_OUT + 1].as<int32_t>(); d.clash_depth = ctx->pool[VIOL_OUT + 2].as<float>();
-    d.clash_partner = ctx->pool[VIOL_OUT + 3].as<int32_t>(); d.viol_mask = ctx->pool[VIOL_OUT + 4].as<uint8_t>(); d.link_mask = ctx->pool[VIOL_OUT + 5].as<uint8_t>();
-    d.link_length = ctx->pool[VIOL_OUT + 6].as<float>(); d.link_cos = ctx->pool[VIOL_OUT + 7].as<float>(); d.link_violation = ctx->pool[VIOL_OUT + 8].as<uint8_t>();
-    d.chain_counts = ctx->pool[VIOL_OUT + 9].as<int64_t>();
-    rc = viol_rows(ctx, ctx->pool[DENSE_IN].as<float>(), ctx->pool[DENSE_IN + 1].as<uint8_t>(), aatype ? ctx->pool[DENSE_IN + 2].as<uint8_t>() : nullptr,
-                   nb ? ctx->pool[DENSE_IN + 3].as<uint32_t>() : nullptr, packed, n, rows_per, layout, tab, tolerance, link_factor, d);
-    if (rc) return rc;
-    for (int k = 0; k < 10; k++)
-        if (bytes[k]) HIP_TRY(hipMemcpyAsync(host[k], ctx->pool[VIOL_OUT + k].p, bytes[k], hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return FCZ_OK;
 }
 
 int fcz_violations(fcz_ctx* ctx, const float* pos, const uint8_t* mask, const uint8_t* aatype, const uint32_t* length, uint32_t n, uint32_t L, int layout,
                    const float* radius_table, float tolerance, float link_factor, const fcz_violations_out* out) {
     sasa_table tab;
-    if (!viol_args_ok(ctx, pos, mask, aatype, layout, L, radius_table, tolerance, link_factor, out, &tab) || L == 0) return FCZ_E_INVALID_ARG;
+    if (!viol_args_ok(ctx, pos, mask, aatype, layout, L, radius_table, tolerance, link_factor, out, &tab) || !bound_ok(false, length, n, L)) return FCZ_E_INVALID_ARG;
     return viol_host(ctx, pos, mask, aatype, length, false, n, L, layout, tab, tolerance, link_factor, *out);
 }
 
 int fcz_violations_packed(fcz_ctx* ctx, const float* pos, const uint8_t* mask, const uint8_t* aatype, const uint32_t* row_off, uint32_t n, uint32_t R, int layout,
                           const float* radius_table, float tolerance, float link_factor, const fcz_violations_out* out) {
     sasa_table tab;
-    if (!viol_args_ok(ctx, pos, mask, aatype, layout, R, radius_table, tolerance, link_factor, out, &tab) || (n && !row_off)) return FCZ_E_INVALID_ARG;
+    if (!viol_args_ok(ctx, pos, mask, aatype, layout, R, radius_table, tolerance, link_factor, out, &tab) || !bound_ok(true, row_off, n, R)) return FCZ_E_INVALID_ARG;
     return viol_host(ctx, pos, mask, aatype, row_off, true, n, R, layout, tab, tolerance, link_factor, *out);
 }
+
+}  // extern "C"
 
 // ------------------------------------------------------------------------------------------------
 // least-squares superposition of two dense tensor batches (fcz_superpose.h; no counterpart in the reference)
@@ -2378,16 +2311,20 @@ static int superpose_rows(fcz_ctx* ctx, const float* pos_true_dev, const uint8_t
     return FCZ_OK;
 }
 
-int fcz_superpose_dev(fcz_ctx* ctx, const float* pos_true_dev, const uint8_t* mask_true_dev, const float* pos_pred_dev, const uint8_t* mask_pred_dev,
-                      const uint32_t* length_dev, uint32_t n, uint32_t L, int layout, int slot, const fcz_superpose_out* out_dev) {
-    if (!superpose_args_ok(ctx, pos_true_dev, mask_true_dev, pos_pred_dev, layout, slot, L, out_dev) || L == 0) return FCZ_E_INVALID_ARG;
-    return superpose_rows(ctx, pos_true_dev, mask_true_dev, pos_pred_dev, mask_pred_dev, length_dev, false, n, L, layout, slot, *out_dev);
-}
-
-int fcz_superpose_packed_dev(fcz_ctx* ctx, const float* pos_true_dev, const uint8_t* mask_true_dev, const float* pos_pred_dev, const uint8_t* mask_pred_dev,
-                             const uint32_t* row_off_dev, uint32_t n, uint32_t R, int layout, int slot, const fcz_superpose_out* out_dev) {
-    if (!superpose_args_ok(ctx, pos_true_dev, mask_true_dev, pos_pred_dev, layout, slot, R, out_dev) || (n && !row_off_dev)) return FCZ_E_INVALID_ARG;
-    return superpose_rows(ctx, pos_true_dev, mask_true_dev, pos_pred_dev, mask_pred_dev, row_off_dev, true, n, R, layout, slot, *out_dev);
+// fcz_superpose and fcz_superpose_packed: the host arrays through DENSE_IN 0, 1, 3, LDDT_PRED 4, 5 and SUPERPOSE_OUT 10 .. 16, the outputs in the struct's order
+static int superpose_host(fcz_ctx* ctx, const float* pos_true, const uint8_t* mask_true, const float* pos_pred, const uint8_t* mask_pred, const uint32_t* bound,
+                          bool packed, uint32_t n, uint32_t rows_per, int layout, int slot, const fcz_superpose_out& o) {
+    const dense_bytes b(packed, n, rows_per, layout, bound);
+    const size_t c = n;
+    return staged_call(ctx, {{pos_true, b.pos, DENSE_IN}, {mask_true, b.mask, DENSE_IN + 1}, {bound, b.bound, DENSE_IN + 3}, {pos_pred, b.pos, LDDT_PRED},
+                             {mask_pred, b.mask, LDDT_PRED + 1}},
+                       {{o.rot, 36 * c, SUPERPOSE_OUT}, {o.trans, 12 * c, SUPERPOSE_OUT + 1}, {o.rmsd, 4 * c, SUPERPOSE_OUT + 2}, {o.sites, 4 * c, SUPERPOSE_OUT + 3},
+                        {o.gdt_counts, 20 * c, SUPERPOSE_OUT + 4}, {o.tm, 4 * c, SUPERPOSE_OUT + 5}, {o.dev, 4 * b.rows, SUPERPOSE_OUT + 6}},
+                       [&](const void* const* in, void* const* out) {
+        const fcz_superpose_out d{(float*)out[0], (float*)out[1], (float*)out[2], (int32_t*)out[3], (int32_t*)out[4], (float*)out[5], (float*)out[6]};
+        return superpose_rows(ctx, (const float*)in[0], (const uint8_t*)in[1], (const float*)in[3], (const uint8_t*)in[4], (const uint32_t*)in[2], packed, n, rows_per,
+                              layout, slot, d);
+    });
 }
 
 static bool superpose_apply_args_ok(const fcz_ctx* ctx, const float* pos, int layout, uint32_t rows, const float* rot, const float* trans, const float* pos_out) {
@@ -2400,155 +2337,87 @@ static int superpose_apply_rows(fcz_ctx* ctx, const float* pos_dev, const uint8_
     HIP_TRY(hipSetDevice(ctx->device));
     if (rows == 0 || (n == 0 && !packed)) return FCZ_OK;
     const superpose_apply_args g{pos_dev, mask_dev, bound_dev, n, rows, rot_dev, trans_dev, pos_out_dev};
-    const uint32_t max_blocks = (uint32_t)ctx->n_cu * 16u;
-    chain_tiles ct;
-    if (!packed || n) { int rc = ct.reserve(ctx, packed, n, rows); if (rc) return rc; }
+    chain_tiles ct(ctx, packed, n, rows);
+    int rc = ct.reserve(); if (rc) return rc;
     span_guard sg(ctx, "superpose");
-    int rc = FCZ_OK;
     dispatch_layout(layout, [&](auto W) {
         constexpr int A = decltype(W)::value;
-        if (packed) {
-            const uint64_t floats = (uint64_t)rows * (A * 3u);
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_superpose_apply_fill<A>), dim3((uint32_t)std::min<uint64_t>((floats + BLOCK - 1) / BLOCK, max_blocks)), dim3(BLOCK), 0,
-                               ctx->stream, g);
-            if (n == 0) return;
-            if ((rc = ct.scan(ctx, bound_dev, n, rows))) return;
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_superpose_apply<A, true>), dim3((uint32_t)ct.blocks), dim3(BLOCK), 0, ctx->stream, g, ct.tile_off, 0u, (uint64_t)0);
-        } else {
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_superpose_apply<A, false>), dim3((uint32_t)ct.blocks), dim3(BLOCK), 0, ctx->stream, g, (const uint64_t*)nullptr,
-                               ct.tiles_per_entry, ct.n_padded);
-        }
+        rc = ct.run(bound_dev, [&] { hipLaunchKernelGGL(HIP_KERNEL_NAME(k_superpose_apply_fill<A>), ct.fill_grid((uint64_t)rows * (A * 3u)), dim3(BLOCK), 0, ctx->stream, g); },
+                    [&](auto P, dim3 grid, const uint64_t* tile_off, uint32_t tiles_per_entry, uint64_t n_padded) {
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_superpose_apply<A, decltype(P)::value>), grid, dim3(BLOCK), 0, ctx->stream, g, tile_off, tiles_per_entry, n_padded);
+        });
     });
-    if (rc) return rc;
-    HIP_TRY(hipGetLastError());
-    return FCZ_OK;
+    return rc;
 }
 
-int fcz_superpose_apply_dev(fcz_ctx* ctx, const float* pos_dev, const uint8_t* mask_dev, const uint32_t* length_dev, uint32_t n, uint32_t L, int layout,
-                            const float* rot_dev, const float* trans_dev, float* pos_out_dev) {
-    if (!superpose_apply_args_ok(ctx, pos_dev, layout, L, rot_dev, trans_dev, pos_out_dev) || L == 0) return FCZ_E_INVALID_ARG;
-    return superpose_apply_rows(ctx, pos_dev, mask_dev, length_dev, false, n, L, layout, rot_dev, trans_dev, pos_out_dev);
-}
-
-int fcz_superpose_apply_packed_dev(fcz_ctx* ctx, const float* pos_dev, const uint8_t* mask_dev, const uint32_t* row_off_dev, uint32_t n, uint32_t R, int layout,
-                                   const float* rot_dev, const float* trans_dev, float* pos_out_dev) {
-    if (!superpose_apply_args_ok(ctx, pos_dev, layout, R, rot_dev, trans_dev, pos_out_dev) || (n && !row_off_dev)) return FCZ_E_INVALID_ARG;
-    return superpose_apply_rows(ctx, pos_dev, mask_dev, row_off_dev, true, n, R, layout, rot_dev, trans_dev, pos_out_dev);
-}
-
-// The host arrays of a superposition call through DENSE_IN 0, 1, 3 and LDDT_PRED 4, 5, its n_out outputs (host[i] may be NULL: not wanted) through
-// pool[slots[i]]; run(pos_true, mask_true, pos_pred, mask_pred, bound, d) enqueues the call on the staged arrays, d[i] the device side of host[i]
-extern "C++" template <class Run>
-static int superpose_staged(fcz_ctx* ctx, const float* pos_true, const uint8_t* mask_true, const float* pos_pred, const uint8_t* mask_pred, const uint32_t* bound,
-                            bool packed, uint32_t n, uint32_t rows_per, int layout, int n_out, void* const* host, const size_t* bytes, const int* slots, Run run) {
-    HIP_TRY(hipSetDevice(ctx->device));
-    claim_staging(ctx);
-    const size_t rows = packed ? (size_t)rows_per : (size_t)n * rows_per, A = (size_t)fcz_dense_width(layout);
-    if (n == 0 && rows == 0) return FCZ_OK;
-    const size_t nb = bound ? sizeof(uint32_t) * ((size_t)n + (packed ? 1 : 0)) : 0, np = rows * A * 3 * sizeof(float), nm = rows * A;
-    int rc;
-    if ((rc = ctx->pool[DENSE_IN].ensure(np)) || (rc = ctx->pool[DENSE_IN + 1].ensure(nm)) || (rc = ctx->pool[DENSE_IN + 3].ensure(nb)) ||
-        (rc = ctx->pool[LDDT_PRED].ensure(np)) || (rc = ctx->pool[LDDT_PRED + 1].ensure(mask_pred ? nm : 0)))
-        return rc;
-    void* d[9];
-    for (int i = 0; i < n_out; i++) {
-        if ((rc = ctx->pool[slots[i]].ensure(host[i] ? bytes[i] : 0))) return rc;
-        d[i] = host[i] ? ctx->pool[slots[i]].p : nullptr;
-    }
-    if (np) {
-        HIP_TRY(hipMemcpyAsync(ctx->pool[DENSE_IN].p, pos_true, np, hipMemcpyHostToDevice, ctx->stream));
-        HIP_TRY(hipMemcpyAsync(ctx->pool[DENSE_IN + 1].p, mask_true, nm, hipMemcpyHostToDevice, ctx->stream));
-        HIP_TRY(hipMemcpyAsync(ctx->pool[LDDT_PRED].p, pos_pred, np, hipMemcpyHostToDevice, ctx->stream));
-        if (mask_pred) HIP_TRY(hipMemcpyAsync(ctx->pool[LDDT_PRED + 1].p, mask_pred, nm, hipMemcpyHostToDevice, ctx->stream));
-    }
-    if (nb) HIP_TRY(hipMemcpyAsync(ctx->pool[DENSE_IN + 3].p, bound, nb, hipMemcpyHostToDevice, ctx->stream));
-    // (R == 0 with chains: the arrays have no allocation and every chain is empty, so nothing of them is read)
-    rc = run(ctx->pool[DENSE_IN].as<float>(), ctx->pool[DENSE_IN + 1].as<uint8_t>(), ctx->pool[LDDT_PRED].as<float>(),
-             mask_pred && np ? ctx->pool[LDDT_PRED + 1].as<uint8_t>() : nullptr, nb ? ctx->pool[DENSE_IN + 3].as<uint32_t>() : nullptr, d);
-    if (rc) return rc;
-    for (int i = 0; i < n_out; i++)
-        if (host[i] && bytes[i]) HIP_TRY(hipMemcpyAsync(host[i], d[i], bytes[i], hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return FCZ_OK;
-}
-
-// fcz_superpose and fcz_superpose_packed: SUPERPOSE_OUT 10 .. 16
-static int superpose_host(fcz_ctx* ctx, const float* pos_true, const uint8_t* mask_true, const float* pos_pred, const uint8_t* mask_pred, const uint32_t* bound,
-                          bool packed, uint32_t n, uint32_t rows_per, int layout, int slot, const fcz_superpose_out& out) {
-    const size_t rows = packed ? (size_t)rows_per : (size_t)n * rows_per;
-    void* host[7] = {out.rot, out.trans, out.rmsd, out.sites, out.gdt_counts, out.tm, out.dev};
-    const size_t bytes[7] = {36 * (size_t)n, 12 * (size_t)n, 4 * (size_t)n, 4 * (size_t)n, 20 * (size_t)n, 4 * (size_t)n, 4 * rows};
-    const int slots[7] = {SUPERPOSE_OUT, SUPERPOSE_OUT + 1, SUPERPOSE_OUT + 2, SUPERPOSE_OUT + 3, SUPERPOSE_OUT + 4, SUPERPOSE_OUT + 5, SUPERPOSE_OUT + 6};
-    return superpose_staged(ctx, pos_true, mask_true, pos_pred, mask_pred, bound, packed, n, rows_per, layout, 7, host, bytes, slots,
-                            [&](const float* pt, const uint8_t* mt, const float* pp, const uint8_t* mp, const uint32_t* bd, void** d) {
-        const fcz_superpose_out o{(float*)d[0], (float*)d[1], (float*)d[2], (int32_t*)d[3], (int32_t*)d[4], (float*)d[5], (float*)d[6]};
-        return superpose_rows(ctx, pt, mt, pp, mp, bd, packed, n, rows_per, layout, slot, o);
+// fcz_superpose_apply and fcz_superpose_apply_packed: the host arrays through LDDT_PRED 4, 5, DENSE_IN 3 and APPLY_ROT, APPLY_TRANS, APPLY_OUT.
+// (Without a chain rot and trans have no byte and are NULL on the device: the fill, the only launch then, reads neither.)
+static int superpose_apply_host(fcz_ctx* ctx, const float* pos, const uint8_t* mask, const uint32_t* bound, bool packed, uint32_t n, uint32_t rows_per,
+                                int layout, const float* rot, const float* trans, float* pos_out) {
+    const dense_bytes b(packed, n, rows_per, layout, bound);
+    return staged_call(ctx, {{pos, b.pos, LDDT_PRED}, {mask, b.mask, LDDT_PRED + 1}, {bound, b.bound, DENSE_IN + 3}, {rot, 36 * (size_t)n, APPLY_ROT},
+                             {trans, 12 * (size_t)n, APPLY_TRANS}},
+                       {{pos_out, b.pos, APPLY_OUT}}, [&](const void* const* in, void* const* out) {
+        return superpose_apply_rows(ctx, (const float*)in[0], (const uint8_t*)in[1], (const uint32_t*)in[2], packed, n, rows_per, layout, (const float*)in[3],
+                                    (const float*)in[4], (float*)out[0]);
     });
+}
+
+extern "C" {
+
+int fcz_superpose_dev(fcz_ctx* ctx, const float* pos_true_dev, const uint8_t* mask_true_dev, const float* pos_pred_dev, const uint8_t* mask_pred_dev,
+                      const uint32_t* length_dev, uint32_t n, uint32_t L, int layout, int slot, const fcz_superpose_out* out_dev) {
+    if (!superpose_args_ok(ctx, pos_true_dev, mask_true_dev, pos_pred_dev, layout, slot, L, out_dev) || !bound_ok(false, length_dev, n, L)) return FCZ_E_INVALID_ARG;
+    return superpose_rows(ctx, pos_true_dev, mask_true_dev, pos_pred_dev, mask_pred_dev, length_dev, false, n, L, layout, slot, *out_dev);
+}
+
+int fcz_superpose_packed_dev(fcz_ctx* ctx, const float* pos_true_dev, const uint8_t* mask_true_dev, const float* pos_pred_dev, const uint8_t* mask_pred_dev,
+                             const uint32_t* row_off_dev, uint32_t n, uint32_t R, int layout, int slot, const fcz_superpose_out* out_dev) {
+    if (!superpose_args_ok(ctx, pos_true_dev, mask_true_dev, pos_pred_dev, layout, slot, R, out_dev) || !bound_ok(true, row_off_dev, n, R)) return FCZ_E_INVALID_ARG;
+    return superpose_rows(ctx, pos_true_dev, mask_true_dev, pos_pred_dev, mask_pred_dev, row_off_dev, true, n, R, layout, slot, *out_dev);
 }
 
 int fcz_superpose(fcz_ctx* ctx, const float* pos_true, const uint8_t* mask_true, const float* pos_pred, const uint8_t* mask_pred, const uint32_t* length,
                   uint32_t n, uint32_t L, int layout, int slot, const fcz_superpose_out* out) {
-    if (!superpose_args_ok(ctx, pos_true, mask_true, pos_pred, layout, slot, L, out) || L == 0) return FCZ_E_INVALID_ARG;
+    if (!superpose_args_ok(ctx, pos_true, mask_true, pos_pred, layout, slot, L, out) || !bound_ok(false, length, n, L)) return FCZ_E_INVALID_ARG;
     return superpose_host(ctx, pos_true, mask_true, pos_pred, mask_pred, length, false, n, L, layout, slot, *out);
 }
 
 int fcz_superpose_packed(fcz_ctx* ctx, const float* pos_true, const uint8_t* mask_true, const float* pos_pred, const uint8_t* mask_pred, const uint32_t* row_off,
                          uint32_t n, uint32_t R, int layout, int slot, const fcz_superpose_out* out) {
-    if (!superpose_args_ok(ctx, pos_true, mask_true, pos_pred, layout, slot, R, out) || (n && !row_off)) return FCZ_E_INVALID_ARG;
+    if (!superpose_args_ok(ctx, pos_true, mask_true, pos_pred, layout, slot, R, out) || !bound_ok(true, row_off, n, R)) return FCZ_E_INVALID_ARG;
     return superpose_host(ctx, pos_true, mask_true, pos_pred, mask_pred, row_off, true, n, R, layout, slot, *out);
 }
 
-// fcz_superpose_apply and fcz_superpose_apply_packed: the host arrays through LDDT_PRED 4, 5, DENSE_IN 3 and APPLY_ROT, APPLY_TRANS, APPLY_OUT
-static int superpose_apply_host(fcz_ctx* ctx, const float* pos, const uint8_t* mask, const uint32_t* bound, bool packed, uint32_t n, uint32_t rows_per,
-                                int layout, const float* rot, const float* trans, float* pos_out) {
-    HIP_TRY(hipSetDevice(ctx->device));
-    claim_staging(ctx);
-    const size_t rows = packed ? (size_t)rows_per : (size_t)n * rows_per, A = (size_t)fcz_dense_width(layout);
-    if (rows == 0) return FCZ_OK;
-    const size_t nb = bound ? sizeof(uint32_t) * ((size_t)n + (packed ? 1 : 0)) : 0, np = rows * A * 3 * sizeof(float), nm = rows * A;
-    int rc;
-    if ((rc = ctx->pool[LDDT_PRED].ensure(np)) || (rc = ctx->pool[LDDT_PRED + 1].ensure(mask ? nm : 0)) || (rc = ctx->pool[DENSE_IN + 3].ensure(nb)) ||
-        (rc = ctx->pool[APPLY_ROT].ensure(36 * (size_t)n + 4)) || (rc = ctx->pool[APPLY_TRANS].ensure(12 * (size_t)n + 4)) || (rc = ctx->pool[APPLY_OUT].ensure(np)))
-        return rc;
-    HIP_TRY(hipMemcpyAsync(ctx->pool[LDDT_PRED].p, pos, np, hipMemcpyHostToDevice, ctx->stream));
-    if (mask) HIP_TRY(hipMemcpyAsync(ctx->pool[LDDT_PRED + 1].p, mask, nm, hipMemcpyHostToDevice, ctx->stream));
-    if (nb) HIP_TRY(hipMemcpyAsync(ctx->pool[DENSE_IN + 3].p, bound, nb, hipMemcpyHostToDevice, ctx->stream));
-    if (n) {
-        HIP_TRY(hipMemcpyAsync(ctx->pool[APPLY_ROT].p, rot, 36 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-        HIP_TRY(hipMemcpyAsync(ctx->pool[APPLY_TRANS].p, trans, 12 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-    }
-    rc = superpose_apply_rows(ctx, ctx->pool[LDDT_PRED].as<float>(), mask ? ctx->pool[LDDT_PRED + 1].as<uint8_t>() : nullptr,
-                              nb ? ctx->pool[DENSE_IN + 3].as<uint32_t>() : nullptr, packed, n, rows_per, layout, ctx->pool[APPLY_ROT].as<float>(),
-                              ctx->pool[APPLY_TRANS].as<float>(), ctx->pool[APPLY_OUT].as<float>());
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(pos_out, ctx->pool[APPLY_OUT].p, np, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return FCZ_OK;
+int fcz_superpose_apply_dev(fcz_ctx* ctx, const float* pos_dev, const uint8_t* mask_dev, const uint32_t* length_dev, uint32_t n, uint32_t L, int layout,
+                            const float* rot_dev, const float* trans_dev, float* pos_out_dev) {
+    if (!superpose_apply_args_ok(ctx, pos_dev, layout, L, rot_dev, trans_dev, pos_out_dev) || !bound_ok(false, length_dev, n, L)) return FCZ_E_INVALID_ARG;
+    return superpose_apply_rows(ctx, pos_dev, mask_dev, length_dev, false, n, L, layout, rot_dev, trans_dev, pos_out_dev);
+}
+
+int fcz_superpose_apply_packed_dev(fcz_ctx* ctx, const float* pos_dev, const uint8_t* mask_dev, const uint32_t* row_off_dev, uint32_t n, uint32_t R, int layout,
+                                   const float* rot_dev, const float* trans_dev, float* pos_out_dev) {
+    if (!superpose_apply_args_ok(ctx, pos_dev, layout, R, rot_dev, trans_dev, pos_out_dev) || !bound_ok(true, row_off_dev, n, R)) return FCZ_E_INVALID_ARG;
+    return superpose_apply_rows(ctx, pos_dev, mask_dev, row_off_dev, true, n, R, layout, rot_dev, trans_dev, pos_out_dev);
 }
 
 int fcz_superpose_apply(fcz_ctx* ctx, const float* pos, const uint8_t* mask, const uint32_t* length, uint32_t n, uint32_t L, int layout, const float* rot,
                         const float* trans, float* pos_out) {
-    if (!superpose_apply_args_ok(ctx, pos, layout, L, rot, trans, pos_out) || L == 0) return FCZ_E_INVALID_ARG;
+    if (!superpose_apply_args_ok(ctx, pos, layout, L, rot, trans, pos_out) || !bound_ok(false, length, n, L)) return FCZ_E_INVALID_ARG;
     return superpose_apply_host(ctx, pos, mask, length, false, n, L, layout, rot, trans, pos_out);
 }
 
 int fcz_superpose_apply_packed(fcz_ctx* ctx, const float* pos, const uint8_t* mask, const uint32_t* row_off, uint32_t n, uint32_t R, int layout, const float* rot,
                                const float* trans, float* pos_out) {
-    if (!superpose_apply_args_ok(ctx, pos, layout, R, rot, trans, pos_out) || (n && !row_off)) return FCZ_E_INVALID_ARG;
+    if (!superpose_apply_args_ok(ctx, pos, layout, R, rot, trans, pos_out) || !bound_ok(true, row_off, n, R)) return FCZ_E_INVALID_ARG;
     return superpose_apply_host(ctx, pos, mask, row_off, true, n, R, layout, rot, trans, pos_out);
 }
+
+}  // extern "C"
 
 // ------------------------------------------------------------------------------------------------
 // maximised TM-score by seeded iterative superposition (fcz_tmscore.h; no counterpart in the reference)
 // ------------------------------------------------------------------------------------------------
-uint64_t fcz_tmscore_seeds(uint32_t sites, uint32_t levels) { return tm_seed_count(sites, levels); }
-
-int fcz_tmscore_seed_fragment(uint32_t sites, uint32_t levels, uint64_t seed, uint32_t* start, uint32_t* length) {
-    if (!start || !length || seed >= tm_seed_count(sites, levels)) return FCZ_E_INVALID_ARG;
-    tm_seed_fragment(sites, seed, start, length);
-    return FCZ_OK;
-}
-
 static bool tmscore_args_ok(const fcz_ctx* ctx, const float* pos_true, const uint8_t* mask_true, const float* pos_pred, int layout, int slot, uint32_t rows,
                             uint32_t iterations, const fcz_tmscore_out* out) {
     if (!ctx || !pos_true || !mask_true || !pos_pred || !out || !out->rot || !out->trans) return false;
@@ -2598,67 +2467,66 @@ static int tmscore_rows(fcz_ctx* ctx, const float* pos_true_dev, const uint8_t* 
     return FCZ_OK;
 }
 
+// fcz_tmscore and fcz_tmscore_packed: the host arrays as fcz_superpose's, then TM_SEED, TM_SELECTED, the outputs in the struct's order
+static int tmscore_host(fcz_ctx* ctx, const float* pos_true, const uint8_t* mask_true, const float* pos_pred, const uint8_t* mask_pred, const uint32_t* bound,
+                        bool packed, uint32_t n, uint32_t rows_per, int layout, int slot, uint32_t levels, uint32_t iterations, const fcz_tmscore_out& o) {
+    const dense_bytes b(packed, n, rows_per, layout, bound);
+    const size_t c = n;
+    return staged_call(ctx, {{pos_true, b.pos, DENSE_IN}, {mask_true, b.mask, DENSE_IN + 1}, {bound, b.bound, DENSE_IN + 3}, {pos_pred, b.pos, LDDT_PRED},
+                             {mask_pred, b.mask, LDDT_PRED + 1}},
+                       {{o.rot, 36 * c, SUPERPOSE_OUT}, {o.trans, 12 * c, SUPERPOSE_OUT + 1}, {o.rmsd, 4 * c, SUPERPOSE_OUT + 2}, {o.sites, 4 * c, SUPERPOSE_OUT + 3},
+                        {o.gdt_counts, 20 * c, SUPERPOSE_OUT + 4}, {o.tm, 4 * c, SUPERPOSE_OUT + 5}, {o.dev, 4 * b.rows, SUPERPOSE_OUT + 6}, {o.seed, 4 * c, TM_SEED},
+                        {o.selected, 4 * c, TM_SELECTED}},
+                       [&](const void* const* in, void* const* out) {
+        const fcz_tmscore_out d{(float*)out[0], (float*)out[1], (float*)out[2], (int32_t*)out[3], (int32_t*)out[4], (float*)out[5], (float*)out[6], (int32_t*)out[7],
+                                (int32_t*)out[8]};
+        return tmscore_rows(ctx, (const float*)in[0], (const uint8_t*)in[1], (const float*)in[3], (const uint8_t*)in[4], (const uint32_t*)in[2], packed, n, rows_per,
+                            layout, slot, levels, iterations, d);
+    });
+}
+
+extern "C" {
+
+uint64_t fcz_tmscore_seeds(uint32_t sites, uint32_t levels) { return tm_seed_count(sites, levels); }
+
+int fcz_tmscore_seed_fragment(uint32_t sites, uint32_t levels, uint64_t seed, uint32_t* start, uint32_t* length) {
+    if (!start || !length || seed >= tm_seed_count(sites, levels)) return FCZ_E_INVALID_ARG;
+    tm_seed_fragment(sites, seed, start, length);
+    return FCZ_OK;
+}
+
 int fcz_tmscore_dev(fcz_ctx* ctx, const float* pos_true_dev, const uint8_t* mask_true_dev, const float* pos_pred_dev, const uint8_t* mask_pred_dev,
                     const uint32_t* length_dev, uint32_t n, uint32_t L, int layout, int slot, uint32_t levels, uint32_t iterations, const fcz_tmscore_out* out_dev) {
-    if (!tmscore_args_ok(ctx, pos_true_dev, mask_true_dev, pos_pred_dev, layout, slot, L, iterations, out_dev) || L == 0) return FCZ_E_INVALID_ARG;
+    if (!tmscore_args_ok(ctx, pos_true_dev, mask_true_dev, pos_pred_dev, layout, slot, L, iterations, out_dev) || !bound_ok(false, length_dev, n, L))
+        return FCZ_E_INVALID_ARG;
     return tmscore_rows(ctx, pos_true_dev, mask_true_dev, pos_pred_dev, mask_pred_dev, length_dev, false, n, L, layout, slot, levels, iterations, *out_dev);
 }
 
 int fcz_tmscore_packed_dev(fcz_ctx* ctx, const float* pos_true_dev, const uint8_t* mask_true_dev, const float* pos_pred_dev, const uint8_t* mask_pred_dev,
                            const uint32_t* row_off_dev, uint32_t n, uint32_t R, int layout, int slot, uint32_t levels, uint32_t iterations,
                            const fcz_tmscore_out* out_dev) {
-    if (!tmscore_args_ok(ctx, pos_true_dev, mask_true_dev, pos_pred_dev, layout, slot, R, iterations, out_dev) || (n && !row_off_dev)) return FCZ_E_INVALID_ARG;
+    if (!tmscore_args_ok(ctx, pos_true_dev, mask_true_dev, pos_pred_dev, layout, slot, R, iterations, out_dev) || !bound_ok(true, row_off_dev, n, R))
+        return FCZ_E_INVALID_ARG;
     return tmscore_rows(ctx, pos_true_dev, mask_true_dev, pos_pred_dev, mask_pred_dev, row_off_dev, true, n, R, layout, slot, levels, iterations, *out_dev);
-}
-
-// fcz_tmscore and fcz_tmscore_packed: SUPERPOSE_OUT 10 .. 16, TM_SEED, TM_SELECTED
-static int tmscore_host(fcz_ctx* ctx, const float* pos_true, const uint8_t* mask_true, const float* pos_pred, const uint8_t* mask_pred, const uint32_t* bound,
-                        bool packed, uint32_t n, uint32_t rows_per, int layout, int slot, uint32_t levels, uint32_t iterations, const fcz_tmscore_out& out) {
-    const size_t rows = packed ? (size_t)rows_per : (size_t)n * rows_per;
-    void* host[9] = {out.rot, out.trans, out.rmsd, out.sites, out.gdt_counts, out.tm, out.dev, out.seed, out.selected};
-    const size_t bytes[9] = {36 * (size_t)n, 12 * (size_t)n, 4 * (size_t)n, 4 * (size_t)n, 20 * (size_t)n, 4 * (size_t)n, 4 * rows, 4 * (size_t)n, 4 * (size_t)n};
-    const int slots[9] = {SUPERPOSE_OUT, SUPERPOSE_OUT + 1, SUPERPOSE_OUT + 2, SUPERPOSE_OUT + 3, SUPERPOSE_OUT + 4, SUPERPOSE_OUT + 5, SUPERPOSE_OUT + 6, TM_SEED, TM_SELECTED};
-    return superpose_staged(ctx, pos_true, mask_true, pos_pred, mask_pred, bound, packed, n, rows_per, layout, 9, host, bytes, slots,
-                            [&](const float* pt, const uint8_t* mt, const float* pp, const uint8_t* mp, const uint32_t* bd, void** d) {
-        const fcz_tmscore_out o{(float*)d[0], (float*)d[1], (float*)d[2], (int32_t*)d[3], (int32_t*)d[4], (float*)d[5], (float*)d[6], (int32_t*)d[7], (int32_t*)d[8]};
-        return tmscore_rows(ctx, pt, mt, pp, mp, bd, packed, n, rows_per, layout, slot, levels, iterations, o);
-    });
 }
 
 int fcz_tmscore(fcz_ctx* ctx, const float* pos_true, const uint8_t* mask_true, const float* pos_pred, const uint8_t* mask_pred, const uint32_t* length,
                 uint32_t n, uint32_t L, int layout, int slot, uint32_t levels, uint32_t iterations, const fcz_tmscore_out* out) {
-    if (!tmscore_args_ok(ctx, pos_true, mask_true, pos_pred, layout, slot, L, iterations, out) || L == 0) return FCZ_E_INVALID_ARG;
+    if (!tmscore_args_ok(ctx, pos_true, mask_true, pos_pred, layout, slot, L, iterations, out) || !bound_ok(false, length, n, L)) return FCZ_E_INVALID_ARG;
     return tmscore_host(ctx, pos_true, mask_true, pos_pred, mask_pred, length, false, n, L, layout, slot, levels, iterations, *out);
 }
 
 int fcz_tmscore_packed(fcz_ctx* ctx, const float* pos_true, const uint8_t* mask_true, const float* pos_pred, const uint8_t* mask_pred, const uint32_t* row_off,
                        uint32_t n, uint32_t R, int layout, int slot, uint32_t levels, uint32_t iterations, const fcz_tmscore_out* out) {
-    if (!tmscore_args_ok(ctx, pos_true, mask_true, pos_pred, layout, slot, R, iterations, out) || (n && !row_off)) return FCZ_E_INVALID_ARG;
+    if (!tmscore_args_ok(ctx, pos_true, mask_true, pos_pred, layout, slot, R, iterations, out) || !bound_ok(true, row_off, n, R)) return FCZ_E_INVALID_ARG;
     return tmscore_host(ctx, pos_true, mask_true, pos_pred, mask_pred, row_off, true, n, R, layout, slot, levels, iterations, *out);
 }
+
+}  // extern "C"
 
 // ------------------------------------------------------------------------------------------------
 // rigid frames of dense tensors (fcz_frames.h; no counterpart in the reference)
 // ------------------------------------------------------------------------------------------------
-int fcz_frames_width(int groups) { return groups == FCZ_FRAMES_BACKBONE ? 1 : groups == FCZ_FRAMES_ALL ? 8 : -1; }
-
-int fcz_frame_atom(int rc, int group, int j) {
-    if (rc < 0 || rc >= FCZ_N_RES_CODES || group < 0 || group >= (int)FR_GROUPS || j < 0 || j > 2) return -1;
-    static const int backbone[3] = {2, 1, 0}, psi[3] = {1, 2, 3};             // (C, CA, N) and (CA, C, O): atom codes 0 .. 3 are N, CA, C, O
-    if (group == 0) return backbone[j];
-    if (group == 3) return psi[j];
-    if (group < 4) return -1;
-    const int k = group - 4;
-    if (fcz_chi_atom(rc, k) < 0) return -1;
-    const int c = k + 1 + j;                                                  // position in the chain N, CA, CB, X1 .. X4
-    return c == 0 ? 0 : c == 1 ? 1 : c == 2 ? 4 : fcz_chi_atom(rc, c - 3);    // (atom code 4 is CB)
-}
-
-int fcz_frame_ambiguous(int rc, int group) {
-    // the types whose chi ends in two atoms that a 180-degree turn exchanges: ASP OD1 / OD2, PHE and TYR CD1 / CD2 (chi2), GLU OE1 / OE2 (chi3)
-    return ((rc == 3 || rc == 13 || rc == 18) && group == 5) || (rc == 6 && group == 6) ? 1 : 0;
-}
-
 // the kernel's table: slots of the three defining atoms per (type, group) in the layout
 static frames_table frames_make_table(int layout) {
     frames_table t;
@@ -2703,6 +2571,27 @@ static int frames_rows(fcz_ctx* ctx, const float* pos_dev, const uint8_t* mask_d
     return FCZ_OK;
 }
 
+extern "C" {
+
+int fcz_frames_width(int groups) { return groups == FCZ_FRAMES_BACKBONE ? 1 : groups == FCZ_FRAMES_ALL ? 8 : -1; }
+
+int fcz_frame_atom(int rc, int group, int j) {
+    if (rc < 0 || rc >= FCZ_N_RES_CODES || group < 0 || group >= (int)FR_GROUPS || j < 0 || j > 2) return -1;
+    static const int backbone[3] = {2, 1, 0}, psi[3] = {1, 2, 3};             // (C, CA, N) and (CA, C, O): atom codes 0 .. 3 are N, CA, C, O
+    if (group == 0) return backbone[j];
+    if (group == 3) return psi[j];
+    if (group < 4) return -1;
+    const int k = group - 4;
+    if (fcz_chi_atom(rc, k) < 0) return -1;
+    const int c = k + 1 + j;                                                  // position in the chain N, CA, CB, X1 .. X4
+    return c == 0 ? 0 : c == 1 ? 1 : c == 2 ? 4 : fcz_chi_atom(rc, c - 3);    // (atom code 4 is CB)
+}
+
+int fcz_frame_ambiguous(int rc, int group) {
+    // the types whose chi ends in two atoms that a 180-degree turn exchanges: ASP OD1 / OD2, PHE and TYR CD1 / CD2 (chi2), GLU OE1 / OE2 (chi3)
+    return ((rc == 3 || rc == 13 || rc == 18) && group == 5) || (rc == 6 && group == 6) ? 1 : 0;
+}
+
 int fcz_frames_dev(fcz_ctx* ctx, const float* pos_dev, const uint8_t* mask_dev, const uint8_t* aatype_dev, const uint32_t* length_dev, uint32_t n, uint32_t L,
                    int layout, int groups, float* rot_dev, float* trans_dev, uint8_t* frame_mask_dev) {
     if (!frames_args_ok(ctx, pos_dev, mask_dev, aatype_dev, L, layout, groups, rot_dev, trans_dev, frame_mask_dev)) return FCZ_E_INVALID_ARG;
@@ -2713,28 +2602,14 @@ int fcz_frames_dev(fcz_ctx* ctx, const float* pos_dev, const uint8_t* mask_dev, 
 int fcz_frames(fcz_ctx* ctx, const float* pos, const uint8_t* mask, const uint8_t* aatype, const uint32_t* length, uint32_t n, uint32_t L, int layout,
                int groups, float* rot, float* trans, uint8_t* frame_mask) {
     if (!frames_args_ok(ctx, pos, mask, aatype, L, layout, groups, rot, trans, frame_mask)) return FCZ_E_INVALID_ARG;
-    HIP_TRY(hipSetDevice(ctx->device));
-    claim_staging(ctx);
-    const size_t rows = (size_t)n * L, A = (size_t)fcz_dense_width(layout), G = (size_t)fcz_frames_width(groups);
-    if (rows == 0) return FCZ_OK;
-    const size_t in_bytes[4] = {rows * A * 3 * sizeof(float), rows * A, aatype ? rows : 0, length ? sizeof(uint32_t) * (size_t)n : 0};
-    const void* in_host[4] = {pos, mask, aatype, length};
-    const size_t out_bytes[3] = {rows * G * 9 * sizeof(float), rows * G * 3 * sizeof(float), rows * G};
-    void* out_host[3] = {rot, trans, frame_mask};
-    int rc;
-    for (int i = 0; i < 4; i++) {
-        if ((rc = ctx->pool[DENSE_IN + i].ensure(in_bytes[i]))) return rc;
-        if (in_bytes[i]) HIP_TRY(hipMemcpyAsync(ctx->pool[DENSE_IN + i].p, in_host[i], in_bytes[i], hipMemcpyHostToDevice, ctx->stream));
-    }
-    for (int i = 0; i < 3; i++)
-        if ((rc = ctx->pool[DENSE_OUT + i].ensure(out_bytes[i]))) return rc;
-    rc = frames_rows(ctx, ctx->pool[DENSE_IN].as<float>(), ctx->pool[DENSE_IN + 1].as<uint8_t>(), aatype ? ctx->pool[DENSE_IN + 2].as<uint8_t>() : nullptr,
-                     length ? ctx->pool[DENSE_IN + 3].as<uint32_t>() : nullptr, n, L, layout, groups, ctx->pool[DENSE_OUT].as<float>(),
-                     ctx->pool[DENSE_OUT + 1].as<float>(), ctx->pool[DENSE_OUT + 2].as<uint8_t>());
-    if (rc) return rc;
-    for (int i = 0; i < 3; i++) HIP_TRY(hipMemcpyAsync(out_host[i], ctx->pool[DENSE_OUT + i].p, out_bytes[i], hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return FCZ_OK;
+    const dense_bytes b(false, n, L, layout, length);
+    const size_t items = b.rows * (size_t)fcz_frames_width(groups);
+    return staged_call(ctx, {{pos, b.pos, DENSE_IN}, {mask, b.mask, DENSE_IN + 1}, {aatype, b.rows, DENSE_IN + 2}, {length, b.bound, DENSE_IN + 3}},
+                       {{rot, items * 9 * sizeof(float), DENSE_OUT}, {trans, items * 3 * sizeof(float), DENSE_OUT + 1}, {frame_mask, items, DENSE_OUT + 2}},
+                       [&](const void* const* in, void* const* out) {
+        return frames_rows(ctx, (const float*)in[0], (const uint8_t*)in[1], (const uint8_t*)in[2], (const uint32_t*)in[3], n, L, layout, groups, (float*)out[0],
+                           (float*)out[1], (uint8_t*)out[2]);
+    });
 }
 
 // ------------------------------------------------------------------------------------------------

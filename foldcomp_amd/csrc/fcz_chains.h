@@ -1,12 +1,13 @@
-// fcz_chains.h -- what the per-chain sweeps over dense tensors share (fcz_knn.h: the neighbour graph, fcz_lddt.h: lDDT): which rows
+// fcz_chains.h -- what the per-chain sweeps over dense tensors share (k-NN, lDDT, DSSP, SASA, violations, superpose apply): which rows
 // of the arrays are chain e's, which chain a query tile belongs to, and which packed rows no chain covers.
 //
 // Padded form: bound is length [n] or NULL, L the rows per entry; chain e is rows e * L .. e * L + min(length[e], L) and every one
 // of the entry's L rows is written. Packed form: bound is row_off [n + 1], L = R, the rows of the arrays; a chain's range is clamped
 // to the R rows that exist and a range that runs backwards is empty, so no read leaves the arrays whatever row_off holds.
-// A sweep runs persistent blocks over QUERY TILES of CHAIN_TILE rows of one chain, a lane per query: padded, tile -> (entry, tile
-// of the entry) by division; packed, the chains' tile counts are scanned on the device (k_chain_tiles, device_scan) and a tile finds
-// its chain by binary search, as k_dense_packed's rows do.
+// A sweep runs persistent blocks over QUERY TILES of whole rows of one chain (CHAIN_TILE rows, a lane per query, unless the sweep
+// has a tile size of its own: fcz_sasa.h, fcz_violations.h): padded, tile -> (entry, tile of the entry) by division; packed, the
+// chains' tile counts are scanned on the device (k_chain_tiles with the sweep's rows per tile, device_scan) and a tile finds its
+// chain by binary search, as k_dense_packed's rows do.
 #pragma once
 #include "fcz_dense.h"
 
@@ -28,12 +29,12 @@ __device__ __forceinline__ void chain_range(const uint32_t* __restrict__ bound, 
     }
 }
 
-// packed form: tiles of every chain, for the scan that gives each tile its chain
-__global__ __launch_bounds__(BLOCK) void k_chain_tiles(const uint32_t* __restrict__ row_off, uint32_t n, uint32_t R, uint64_t* __restrict__ tiles) {
+// packed form: tiles of tile_rows rows of every chain, for the scan that gives each tile its chain
+__global__ __launch_bounds__(BLOCK) void k_chain_tiles(const uint32_t* __restrict__ row_off, uint32_t n, uint32_t R, uint32_t tile_rows, uint64_t* __restrict__ tiles) {
     for (uint64_t e = (uint64_t)blockIdx.x * BLOCK + threadIdx.x; e < n; e += (uint64_t)gridDim.x * BLOCK) {
         uint64_t row0; uint32_t len, rows;
         chain_range<true>(row_off, R, (uint32_t)e, &row0, &len, &rows);
-        tiles[e] = rows / CHAIN_TILE + (rows % CHAIN_TILE ? 1u : 0u);
+        tiles[e] = rows / tile_rows + (rows % tile_rows ? 1u : 0u);
     }
 }
 

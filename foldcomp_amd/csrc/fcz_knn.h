@@ -20,7 +20,7 @@
 //                         Padded form: tile -> (entry, tile of the entry) by division; every row of the entry is written,
 //                         -1 / 0 where it is no site. Packed form: the chains' tile counts are scanned on the device
 //                         (k_chain_tiles, device_scan) and a tile finds its chain by binary search (fcz_chains.h, shared
-//                         with fcz_lddt.h).
+//                         with every other per-chain sweep).
 //   k_knn_fill            packed form only, in front of k_knn: -1 / 0 into every row that no chain is seen to cover (a search of
 //                         row_off that a hostile row_off may mislead: a covered row it misses is rewritten by k_knn behind it).
 //

@@ -11,8 +11,8 @@
 // result of an atom is the number of its points no candidate buries: an integer that no order of evaluation changes.
 //
 //   k_sasa_points<PACKED, SMALL>
-//       Persistent blocks over QUERY TILES of SASA_TILE_ROWS = 3 rows of one chain (tiles are counted in rows by k_sasa_tiles and the
-//       scan of fcz_chains.h's pattern, with this header's own constant: CHAIN_TILE is a lane per row and does not fit). A tile's
+//       Persistent blocks over QUERY TILES of SASA_TILE_ROWS = 3 rows of one chain (tiles are counted in rows by k_chain_tiles and the
+//       scan of fcz_chains.h, with this header's own rows per tile: CHAIN_TILE is a lane per row and does not fit). A tile's
 //       atoms are compacted into LDS (at most 3 * 37 = 111) and taken in ROUNDS of SASA_GROUP = 32: the four wavefronts of the block
 //       take a round's atoms round-robin, SASA_Q = 8 each. A WAVEFRONT PER QUERY ATOM, the lanes over two things in turn:
 //         * the chain's atoms are staged in LDS in passes of at most SASA_PASS = 1536, compacted: float4 (x, y, z, Rj), the chain row
@@ -43,7 +43,6 @@
 //       CHAIN_TILE rows, and would read the counts back from HBM.) Every term is an integer of at most 11 bits times a float32 in
 //       [0.25, 64) and at most 37 are summed, so the float64 sum is exact and does not depend on the order the compaction gave.
 //       HBM sees the inputs, 2 bytes a slot and 5 bytes a row: no rows x rows and no atoms x atoms array.
-//   k_sasa_tiles  packed form: tiles of every chain, for the scan that gives each tile its chain.
 //   k_sasa_fill   packed form only, in front of the sweep: 0 into every row that no chain is seen to cover (chain_covers: a covered
 //                 row it misses is rewritten by the sweep behind it).
 //
@@ -100,14 +99,6 @@ __device__ __forceinline__ bool sasa_atom(const sasa_args& g, const sasa_table& 
     if (!(isfinite(x) && isfinite(y) && isfinite(z))) return false;
     *c = make_float4(x, y, z, __fadd_rn(radius, g.probe));
     return true;
-}
-
-__global__ __launch_bounds__(BLOCK) void k_sasa_tiles(const uint32_t* __restrict__ row_off, uint32_t n, uint32_t R, uint64_t* __restrict__ tiles) {
-    for (uint64_t e = (uint64_t)blockIdx.x * BLOCK + threadIdx.x; e < n; e += (uint64_t)gridDim.x * BLOCK) {
-        uint64_t row0; uint32_t len, rows;
-        chain_range<true>(row_off, R, (uint32_t)e, &row0, &len, &rows);
-        tiles[e] = rows / SASA_TILE_ROWS + (rows % SASA_TILE_ROWS ? 1u : 0u);
-    }
 }
 
 __global__ __launch_bounds__(BLOCK) void k_sasa_fill(sasa_args g) {

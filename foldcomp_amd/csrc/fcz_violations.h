@@ -12,7 +12,7 @@
 //
 //   k_violations<PACKED>
 //       Persistent blocks over QUERY TILES of whole rows of one chain: 20 rows in atom37, 18 in atom14, 64 in backbone4
-//       (viol_tile_rows; tiles are counted in rows by k_viol_tiles and the scan of fcz_chains.h's pattern). A tile's atoms are
+//       (viol_tile_rows; tiles are counted in rows by k_chain_tiles and the scan of fcz_chains.h). A tile's atoms are
 //       compacted into LDS (at most VIOL_TILE_SLOTS = 20 * 37 = 740) and taken in ROUNDS of BLOCK = 256: A LANE PER QUERY ATOM.
 //       The chain's atoms are staged in LDS in passes of at most VIOL_PASS = 1536, compacted as k_sasa_points stages them: float4
 //       (x, y, z, R), the chain row (uint32) and a kind byte (0, 1 = N, 2 = C, 3 = SG of a CYS row: all the exclusions need), 21
@@ -41,7 +41,6 @@
 //       The chain's four counters get the tile's sums by one 64-bit atomic add each (ordinary vector atomics on integers; the host
 //       clears them in front). Pairs are counted once as the hits with partner row > own row, which the symmetry makes exactly half.
 //       HBM sees the inputs, one byte a slot and 23 bytes a row: no rows x rows and no atoms x atoms array.
-//   k_viol_tiles  packed form: tiles of every chain, for the scan that gives each tile its chain.
 //   k_viol_fill   packed form only, in front of the sweep: 0 (-1 for clash_partner) into every row that no chain is seen to cover.
 //
 // Every index that scales with rows * A is 64-bit. A chain's range is clamped to the R rows that exist and a range that runs
@@ -106,14 +105,6 @@ __device__ __forceinline__ float viol_cos(const float* a, const float* b, const 
     const float nu = f32_sqrt_rn(__fadd_rn(__fadd_rn(__fmul_rn(ux, ux), __fmul_rn(uy, uy)), __fmul_rn(uz, uz)));
     const float nv = f32_sqrt_rn(__fadd_rn(__fadd_rn(__fmul_rn(vx, vx), __fmul_rn(vy, vy)), __fmul_rn(vz, vz)));
     return __fdiv_rn(dot, __fmul_rn(nu, nv));
-}
-
-__global__ __launch_bounds__(BLOCK) void k_viol_tiles(const uint32_t* __restrict__ row_off, uint32_t n, uint32_t R, uint32_t tile_rows, uint64_t* __restrict__ tiles) {
-    for (uint64_t e = (uint64_t)blockIdx.x * BLOCK + threadIdx.x; e < n; e += (uint64_t)gridDim.x * BLOCK) {
-        uint64_t row0; uint32_t len, rows;
-        chain_range<true>(row_off, R, (uint32_t)e, &row0, &len, &rows);
-        tiles[e] = rows / tile_rows + (rows % tile_rows ? 1u : 0u);
-    }
 }
 
 // row r of the arrays holds nothing

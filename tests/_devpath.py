@@ -24,6 +24,43 @@ def to_dev(a, dev="cuda:0"):
     return torch.from_numpy(a).to(dev)
 
 
+class HostGuarded:
+    """host outputs of a host-pointer entry point, {name: (dtype, shape)} in the call's order: 0xA5 everywhere, `guard` bytes in
+    front of and behind each, which must survive the call"""
+    FILL = 0xA5
+
+    def __init__(self, spec, guard=256):
+        self.spec = {k: (np.dtype(d), tuple(shape)) for k, (d, shape) in spec.items()}
+        self.guard = guard
+        self.raw = {k: np.full(2 * guard + d.itemsize * int(np.prod(shape)), self.FILL, np.uint8) for k, (d, shape) in self.spec.items()}
+
+    def ptr(self, k):
+        return self.raw[k].ctypes.data + self.guard
+
+    def ptrs(self):
+        return [self.ptr(k) for k in self.spec]
+
+    def fetch(self, k):
+        a, g = self.raw[k], self.guard
+        assert (a[:g] == self.FILL).all() and (a[len(a) - g:] == self.FILL).all(), f"guard bytes of {k} overwritten"
+        d, shape = self.spec[k]
+        return a[g:len(a) - g].copy().view(d).reshape(shape)
+
+    def all(self):
+        return [self.fetch(k) for k in self.spec]
+
+    def untouched(self):
+        return all(bool((a == self.FILL).all()) for a in self.raw.values())
+
+
+def host_ptr(a):
+    """address of a C-contiguous host array the caller keeps alive, None for None"""
+    if a is None:
+        return None
+    assert a.flags["C_CONTIGUOUS"]
+    return a.ctypes.data
+
+
 def dev_batch(b: ChainBatch, dev="cuda:0"):
     """-> (fcz_chain_batch of device pointers, the tensors that own them)"""
     t = {k: to_dev(getattr(b, k), dev) for k in _FIELDS}

@@ -9,7 +9,7 @@ import _dense as DN
 import _dssp as D
 import _knn as K
 from _cases import compress_cases, db_cases
-from _devpath import to_dev
+from _devpath import HostGuarded, host_ptr, to_dev
 from _window import Decoded
 from foldcomp_amd import _lib
 
@@ -229,6 +229,17 @@ def test_hostile_row_off(codec):
     lab = D.run_labels(codec, *dev, to_dev(row_off), 5, R, 2, True, to_dev(got[0]), to_dev(got[1]))
     D.same_labels(lab, D.labels(pos, mask, row_off, exp[0], exp[1], packed=True), "hostile row_off labels")
     assert not lab[0][:40].any() and not lab[1][:40].any() and (lab[0][401:] == 1).sum() > 100
+
+    def host_form(n, tables, labels):
+        """fcz_dssp_packed on the same host arrays, its outputs between guard bytes: what the two device steps gave"""
+        h = HostGuarded(dict(acc_index=(np.int32, (R, 2)), acc_energy=(F, (R, 2)), don_index=(np.int32, (R, 2)), don_energy=(F, (R, 2)),
+                             ss=(np.uint8, (R,)), ss_mask=(np.uint8, (R,))))
+        assert codec.lib.fcz_dssp_packed(codec.ctx, host_ptr(pos), host_ptr(mask), host_ptr(aa), host_ptr(row_off), n, R, 2, *h.ptrs()) == 0
+        out = h.all()
+        D.same_tables(out[:4], tables, f"fcz_dssp_packed n={n}")
+        D.same_labels(out[4:], labels, f"fcz_dssp_packed n={n} labels")
+
+    host_form(5, got, lab)
     # a table that points anywhere: indices outside the chain, outside the arrays, negative -- compared, never followed
     wild = np.random.default_rng(5).integers(-2 ** 31, 2 ** 31, size=(R, 2)).astype(np.int32)
     wild[::3] = got[0][::3]
@@ -240,6 +251,7 @@ def test_hostile_row_off(codec):
     assert (got[0] == -1).all() and (got[2] == -1).all() and not K.bits(got[1]).any() and not K.bits(got[3]).any()
     lab = D.run_labels(codec, *dev, to_dev(row_off), 0, R, 2, True, to_dev(wild), to_dev(ae))
     assert not lab[0].any() and not lab[1].any()
+    host_form(0, got, lab)
 
 
 def test_label_kernel_alone_on_random_tables(codec):

@@ -7,7 +7,7 @@ import pytest
 import _dense as D
 import _frames as F
 from _cases import compress_cases, db_cases
-from _devpath import to_dev
+from _devpath import HostGuarded, host_ptr, to_dev
 from _window import Decoded
 
 pytestmark = pytest.mark.gpu
@@ -148,6 +148,10 @@ def test_no_entries(codec, pools):
     assert codec.lib.fcz_frames_dev(codec.ctx, pos.data_ptr(), mask.data_ptr(), aa.data_ptr(), None, 0, 8, 0, ALL, rp, tp, fp) == 0
     codec.synchronize()
     assert g.untouched()
+    h = HostGuarded(dict(rot=(np.float32, (64, 3, 3)), trans=(np.float32, (64, 3)), frame_mask=(np.uint8, (64,))))
+    host = [host_ptr(np.ascontiguousarray(pools[0][k])) for k in ("pos", "mask", "aa")]
+    assert codec.lib.fcz_frames(codec.ctx, *host, None, 0, 8, 0, ALL, *h.ptrs()) == 0
+    assert h.untouched()
 
 
 # ---- length and outputs -------------------------------------------------------------------------------------------------------------

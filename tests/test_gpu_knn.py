@@ -7,7 +7,7 @@ import pytest
 import _dense as D
 import _knn as K
 from _cases import compress_cases, db_cases
-from _devpath import to_dev
+from _devpath import HostGuarded, host_ptr, to_dev
 from _window import Decoded
 from foldcomp_amd import _lib
 
@@ -157,8 +157,13 @@ def test_hostile_row_off(codec):
     assert (got[0][:40] == -1).all() and not K.bits(got[1][:40]).any() and (got[0][400] == -1).all()
     assert (got[0][40:120, 0] >= 40).sum() > 50 and got[0][401:].max() < R and (got[0][401:, 0] >= 401).sum() > 250
     # no chain at all: every row is uncovered
-    got = K.run_dev(codec, to_dev(pos), to_dev(mask), to_dev(row_off), 0, R, 2, 1, k, True)
-    assert (got[0] == -1).all() and not K.bits(got[1]).any()
+    none = K.run_dev(codec, to_dev(pos), to_dev(mask), to_dev(row_off), 0, R, 2, 1, k, True)
+    assert (none[0] == -1).all() and not K.bits(none[1]).any()
+    # fcz_knn_packed on the same host arrays, its outputs between guard bytes: what the device form gave
+    for n, dev_form in ((5, got), (0, none)):
+        h = HostGuarded(dict(index=(np.int32, (R, k)), dist=(np.float32, (R, k))))
+        assert codec.lib.fcz_knn_packed(codec.ctx, host_ptr(pos), host_ptr(mask), host_ptr(row_off), n, R, 2, 1, k, *h.ptrs()) == 0
+        K.same(h.all(), dev_form, f"fcz_knn_packed n={n}")
 
 
 def test_refusals_leave_the_outputs_untouched(codec):

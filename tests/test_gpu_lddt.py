@@ -10,7 +10,7 @@ import _dense as D
 import _knn as K
 import _lddt as Q
 from _cases import compress_cases, db_cases
-from _devpath import to_dev
+from _devpath import HostGuarded, host_ptr, to_dev
 from _window import Decoded
 from foldcomp_amd import _lib
 
@@ -236,8 +236,13 @@ def test_hostile_row_off(codec):
     assert not got[1][:40].any() and not K.bits(got[0][:40]).any() and got[1][400] == 0
     assert (got[1][40:120] > 0).sum() > 40 and (got[1][401:] > 0).sum() > 200 and got[1][401:].max() < R - 401
     # no chain at all: every row is uncovered
-    got = Q.run_dev(codec, *dev, to_dev(row_off), 0, R, 2, 1, True)
-    assert not got[1].any() and not got[2].any() and not K.bits(got[0]).any()
+    none = Q.run_dev(codec, *dev, to_dev(row_off), 0, R, 2, 1, True)
+    assert not none[1].any() and not none[2].any() and not K.bits(none[0]).any()
+    # fcz_lddt_packed on the same host arrays, its outputs between guard bytes: what the device form gave
+    for n, dev_form in ((5, got), (0, none)):
+        h = HostGuarded(dict(score=(F, (R,)), pairs=(np.int32, (R,)), hits=(np.int32, (R,))))
+        assert codec.lib.fcz_lddt_packed(codec.ctx, *(host_ptr(a) for a in arrays), host_ptr(row_off), n, R, 2, 1, 15.0, None, *h.ptrs()) == 0
+        Q.same(h.all(), dev_form, f"fcz_lddt_packed n={n}")
 
 
 def test_refusals_leave_the_outputs_untouched(codec):

@@ -10,7 +10,7 @@ import _dssp as D
 import _knn as K
 import _sasa as S
 from _cases import compress_cases, db_cases
-from _devpath import to_dev
+from _devpath import HostGuarded, host_ptr, to_dev
 from _window import Decoded
 from foldcomp_amd import _lib, api
 
@@ -267,8 +267,14 @@ def test_hostile_row_off(codec):
     S.same_sasa(got, exp, "hostile row_off")
     assert not got[0][:40].any() and not K.bits(got[1][:40]).any() and not got[2][:40].any() and got[2][40:].sum() > 640
     # no chain at all: every row is uncovered
-    got = S.run_sasa(codec, *dev, to_dev(row_off), 0, R, 2, True, pts)
-    assert not got[0].any() and not K.bits(got[1]).any() and not got[2].any()
+    none = S.run_sasa(codec, *dev, to_dev(row_off), 0, R, 2, True, pts)
+    assert not none[0].any() and not K.bits(none[1]).any() and not none[2].any()
+    # fcz_sasa_packed on the same host arrays, its outputs between guard bytes: what the device form gave
+    for n, dev_form in ((5, got), (0, none)):
+        h = HostGuarded(dict(sasa_points=(np.int16, (R, 4)), sasa=(F, (R,)), sasa_mask=(np.uint8, (R,))))
+        assert codec.lib.fcz_sasa_packed(codec.ctx, host_ptr(pos), host_ptr(mask), host_ptr(aa), host_ptr(row_off), n, R, 2, None, float(S.PROBE),
+                                         host_ptr(PTS), len(PTS), *h.ptrs()) == 0
+        S.same_sasa(h.all(), dev_form, f"fcz_sasa_packed n={n}")
 
 
 def test_refusals_leave_the_outputs_untouched(codec):

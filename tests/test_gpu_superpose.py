@@ -12,7 +12,7 @@ import pytest
 
 import _superpose as S
 from _cases import compress_cases, db_cases
-from _devpath import to_dev
+from _devpath import HostGuarded, host_ptr, to_dev
 from _window import Decoded
 
 pytestmark = pytest.mark.gpu
@@ -188,10 +188,47 @@ def test_hostile_row_off(codec):
     out = S.run_apply(codec, dev[2], None, to_dev(row_off), 5, R, 2, to_dev(got["rot"]), to_dev(got["trans"]), True)
     assert out.tobytes() == S.apply_expected(pos_p, None, got["rot"], got["trans"], row_off=row_off).tobytes() and not out[:40].any() and out[40:].any()
     # no chain at all: every row is uncovered
-    got = S.run_dev(codec, *dev, None, to_dev(row_off), 0, R, 2, 1, True, want=("rot", "trans", "dev"))
-    assert not got["dev"].view(np.uint32).any()
-    out = S.run_apply(codec, dev[2], None, to_dev(row_off), 0, R, 2, dev[2], dev[2], True)
-    assert not out.view(np.uint32).any()
+    none = S.run_dev(codec, *dev, None, to_dev(row_off), 0, R, 2, 1, True, want=("rot", "trans", "dev"))
+    assert not none["dev"].view(np.uint32).any()
+    out_none = S.run_apply(codec, dev[2], None, to_dev(row_off), 0, R, 2, dev[2], dev[2], True)
+    assert not out_none.view(np.uint32).any()
+
+    def host_form(arrays, off, n, rows):
+        """fcz_superpose_packed on host arrays (pos_true, mask_true, pos_pred), its outputs between guard bytes"""
+        import ctypes
+        from foldcomp_amd.structure import CSuperposeOut
+        shapes = S.out_shapes(n, rows, True)
+        h = HostGuarded({k: (S.DTYPES[k], shapes[k]) for k in S.KEYS})
+        o = CSuperposeOut(*h.ptrs())
+        assert codec.lib.fcz_superpose_packed(codec.ctx, *(host_ptr(a) for a in arrays), None, host_ptr(off), n, rows, 2, 1, ctypes.byref(o)) == 0
+        return {k: h.fetch(k) for k in S.KEYS}
+
+    def host_apply(pos, off, n, rows, rot, trans):
+        """fcz_superpose_apply_packed on host arrays, pos_out between guard bytes"""
+        h = HostGuarded(dict(out=(F, (rows, 4, 3))))
+        assert codec.lib.fcz_superpose_apply_packed(codec.ctx, host_ptr(pos), None, host_ptr(off), n, rows, 2, host_ptr(rot), host_ptr(trans), h.ptr("out")) == 0
+        return h
+
+    # the host forms on the same arrays: what the device forms gave
+    S.same_bytes(host_form((pos_t, mask, pos_p), row_off, 5, R), got, "fcz_superpose_packed n=5")
+    host = host_form((pos_t, mask, pos_p), row_off, 0, R)
+    S.same_bytes({k: host[k] for k in none}, none, "fcz_superpose_packed n=0")
+    assert host_apply(pos_p, row_off, 5, R, got["rot"], got["trans"]).fetch("out").tobytes() == out.tobytes()
+    assert host_apply(pos_p, row_off, 0, R, pos_p, pos_p).fetch("out").tobytes() == out_none.tobytes()
+    # chains without a row (R = 0): the per-chain outputs of an empty chain in both forms, and apply writes nothing
+    one, zeros = (pos_t[:1], mask[:1], pos_p[:1]), np.zeros(4, np.uint32)
+    empty = S.run_dev(codec, *(to_dev(a) for a in one), None, to_dev(zeros), 3, 0, 2, 1, True)
+    S.close(empty, S._empty(3, (0,)), "R = 0")
+    assert not empty["rmsd"].view(np.uint32).any() and not empty["tm"].view(np.uint32).any()
+    S.same_bytes(host_form(one, zeros, 3, 0), empty, "fcz_superpose_packed R=0")
+    import torch
+    g, tensors = S.Guarded({"out": 48}), [to_dev(a) for a in (zeros, empty["rot"], empty["trans"])]
+    torch.cuda.synchronize()
+    assert codec.lib.fcz_superpose_apply_packed_dev(codec.ctx, dev[2].data_ptr(), None, tensors[0].data_ptr(), 3, 0, 2, tensors[1].data_ptr(),
+                                                    tensors[2].data_ptr(), g.ptr("out")) == 0
+    codec.synchronize()
+    assert g.untouched()
+    assert host_apply(pos_p[:1], zeros, 3, 0, empty["rot"], empty["trans"]).untouched()
 
 
 def test_apply_on_bits(codec, walk):

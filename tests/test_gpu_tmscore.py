@@ -15,7 +15,7 @@ import pytest
 import _superpose as SP
 import _tmscore as T
 from _cases import compress_cases, db_cases
-from _devpath import to_dev
+from _devpath import HostGuarded, host_ptr, to_dev
 from _window import Decoded
 
 pytestmark = pytest.mark.gpu
@@ -244,8 +244,29 @@ def test_hostile_row_off(codec):
     SP.close(got, ref, "hostile row_off", compare_rot=got["sites"] >= 3)
     assert got["seed"][4] > 0                                                 # (the hinge lies in chain 4)
     # no chain at all: every row is uncovered
-    got = T.run_dev(codec, *dev, None, to_dev(row_off), 0, R, 2, 1, True, want=("rot", "trans", "dev"))
-    assert not got["dev"].view(np.uint32).any()
+    none = T.run_dev(codec, *dev, None, to_dev(row_off), 0, R, 2, 1, True, want=("rot", "trans", "dev"))
+    assert not none["dev"].view(np.uint32).any()
+
+    def host_form(arrays, off, n, rows):
+        """fcz_tmscore_packed on host arrays (pos_true, mask_true, pos_pred), its outputs between guard bytes"""
+        import ctypes
+        from foldcomp_amd.structure import CTmScoreOut
+        shapes = T.out_shapes(n, rows, True)
+        h = HostGuarded({k: (T.DTYPES[k], shapes[k]) for k in T.KEYS})
+        o = CTmScoreOut(*h.ptrs())
+        assert codec.lib.fcz_tmscore_packed(codec.ctx, *(host_ptr(a) for a in arrays), None, host_ptr(off), n, rows, 2, 1, 0, 20, ctypes.byref(o)) == 0
+        return {k: h.fetch(k) for k in T.KEYS}
+
+    # the host form on the same arrays: what the device form gave
+    SP.same_bytes(host_form((pos_t, mask, pos_p), row_off, 5, R), got, "fcz_tmscore_packed n=5")
+    host = host_form((pos_t, mask, pos_p), row_off, 0, R)
+    SP.same_bytes({k: host[k] for k in none}, none, "fcz_tmscore_packed n=0")
+    # chains without a row (R = 0): the per-chain outputs of an empty chain in both forms
+    one, zeros = (pos_t[:1], mask[:1], pos_p[:1]), np.zeros(4, np.uint32)
+    empty = T.run_dev(codec, *(to_dev(a) for a in one), None, to_dev(zeros), 3, 0, 2, 1, True)
+    SP.close(empty, T._empty(3, (0,)), "R = 0")
+    assert not any(empty[k].view(np.uint32).any() for k in ("rmsd", "tm", "seed", "selected"))
+    SP.same_bytes(host_form(one, zeros, 3, 0), empty, "fcz_tmscore_packed R=0")
     # ranges that overlap hold more seeds than the scratch, which is sized from R: nothing outside the outputs is written, the chain
     # whose seeds all fit has its full result, and the other the maximum over the seeds that fit (the header says so)
     lone = T.run_dev(codec, *dev, None, to_dev(np.asarray([0, R], np.uint32)), 1, R, 2, 1, True)

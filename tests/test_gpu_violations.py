@@ -11,7 +11,7 @@ import _dense as DN
 import _dssp as D
 import _violations as V
 from _cases import compress_cases, db_cases
-from _devpath import to_dev
+from _devpath import HostGuarded, host_ptr, to_dev
 from _window import Decoded
 from foldcomp_amd import _lib, api
 
@@ -249,8 +249,26 @@ def test_hostile_row_off(codec):
         assert (got[k][:40] == (-1 if k == "clash_partner" else 0)).all(), k
     assert not got["clash_atom"][:40].any() and got["viol_mask"][40:].sum() > 640
     # no chain at all: every row is uncovered
-    got = V.run_violations(codec, *dev, to_dev(row_off), 0, R, 2, True)
-    assert not got["clash_atom"].any() and not got["viol_mask"].any() and (got["clash_partner"] == -1).all() and not got["link_cos"].view(np.uint32).any()
+    none = V.run_violations(codec, *dev, to_dev(row_off), 0, R, 2, True)
+    assert not none["clash_atom"].any() and not none["viol_mask"].any() and (none["clash_partner"] == -1).all() and not none["link_cos"].view(np.uint32).any()
+
+    def host_form(arrays, off, n, rows):
+        """fcz_violations_packed on host arrays, its outputs between guard bytes"""
+        from foldcomp_amd.structure import CViolationsOut
+        shape = dict(clash_atom=(rows, 4), link_cos=(rows, 2), chain_counts=(n, 4))
+        h = HostGuarded({k: (V.DTYPES[k], shape.get(k, (rows,))) for k in V.KEYS})
+        out = CViolationsOut(*h.ptrs())
+        assert codec.lib.fcz_violations_packed(codec.ctx, *(host_ptr(a) for a in arrays), host_ptr(off), n, rows, 2, None, float(V.TOL), float(V.FACTOR),
+                                               ctypes.byref(out)) == 0
+        return {k: h.fetch(k) for k in V.KEYS}
+
+    # the host form on the same arrays: what the device form gave
+    V.same_violations(host_form((pos, mask, aa), row_off, 5, R), got, "fcz_violations_packed n=5")
+    V.same_violations(host_form((pos, mask, aa), row_off, 0, R), none, "fcz_violations_packed n=0")
+    # chains without a row (R = 0): their counters are 0 and nothing else is written (every other output has no element: all guard)
+    one, zeros = (pos[:1], mask[:1], aa[:1]), np.zeros(4, np.uint32)
+    for form in (V.run_violations(codec, *(to_dev(a) for a in one), to_dev(zeros), 3, 0, 2, True), host_form(one, zeros, 3, 0)):
+        assert form["chain_counts"].shape == (3, 4) and form["chain_counts"].dtype == np.int64 and not form["chain_counts"].any()
 
 
 def test_refusals_leave_the_outputs_untouched(codec):

@@ -9,7 +9,8 @@ from __future__ import annotations
 import ctypes
 import os
 
-from .structure import CAtomsOut, CChainBatch, CDenseIn, CDenseOut, CEntryInfo, CIngestResult, CPackedOut, CSuperposeOut, CTmScoreOut, CViolationsOut
+from .structure import (CAtomsOut, CChainBatch, CDenseIn, CDenseOut, CEntryInfo, CIngestResult, CLddtAtomsOut, CPackedOut, CSuperposeOut, CTmScoreOut,
+                        CViolationsOut)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # FCZ_HIP_LIB selects another build of the same library (A/B timing of kernel variants); it is still a HIP build
@@ -90,6 +91,13 @@ def load():
         "fcz_lddt_packed_dev": (i32, [vp, vp, vp, vp, vp, vp, u32, u32, i32, i32, f32, vp, vp, vp, vp]),
         "fcz_lddt": (i32, [vp, vp, vp, vp, vp, vp, u32, u32, i32, i32, f32, vp, vp, vp, vp]),
         "fcz_lddt_packed": (i32, [vp, vp, vp, vp, vp, vp, u32, u32, i32, i32, f32, vp, vp, vp, vp]),
+        "fcz_lddt_atoms_pass": (i32, []),
+        "fcz_lddt_atoms_max_rows": (i32, [i32]),
+        "fcz_lddt_default_swaps": (i32, [i32, vp]),
+        "fcz_lddt_atoms_dev": (i32, [vp, vp, vp, vp, vp, vp, vp, u32, u32, i32, f32, vp, vp, ctypes.POINTER(CLddtAtomsOut)]),
+        "fcz_lddt_atoms_packed_dev": (i32, [vp, vp, vp, vp, vp, vp, vp, u32, u32, i32, f32, vp, vp, ctypes.POINTER(CLddtAtomsOut)]),
+        "fcz_lddt_atoms": (i32, [vp, vp, vp, vp, vp, vp, vp, u32, u32, i32, f32, vp, vp, ctypes.POINTER(CLddtAtomsOut)]),
+        "fcz_lddt_atoms_packed": (i32, [vp, vp, vp, vp, vp, vp, vp, u32, u32, i32, f32, vp, vp, ctypes.POINTER(CLddtAtomsOut)]),
         "fcz_hbond_pass": (i32, []),
         "fcz_hbond_dev": (i32, [vp, vp, vp, vp, vp, u32, u32, i32, vp, vp, vp, vp]),
         "fcz_hbond_packed_dev": (i32, [vp, vp, vp, vp, vp, u32, u32, i32, vp, vp, vp, vp]),
@@ -185,6 +193,8 @@ EXPORTS = ["fcz_ctx_create", "fcz_ctx_destroy", "fcz_ctx_stream", "fcz_ctx_synch
            "fcz_dense_window_dev", "fcz_decompress_dense_window", "fcz_angles_window_dev", "fcz_decompress_angles_window",
            "fcz_knn_pass", "fcz_knn_dev", "fcz_knn_packed_dev", "fcz_knn", "fcz_knn_packed",
            "fcz_lddt_pass", "fcz_lddt_c2", "fcz_lddt_dev", "fcz_lddt_packed_dev", "fcz_lddt", "fcz_lddt_packed",
+           "fcz_lddt_atoms_pass", "fcz_lddt_atoms_max_rows", "fcz_lddt_default_swaps", "fcz_lddt_atoms_dev", "fcz_lddt_atoms_packed_dev", "fcz_lddt_atoms",
+           "fcz_lddt_atoms_packed",
            "fcz_hbond_pass", "fcz_hbond_dev", "fcz_hbond_packed_dev", "fcz_dssp_labels_dev", "fcz_dssp_labels_packed_dev", "fcz_dssp", "fcz_dssp_packed",
            "fcz_sasa_pass", "fcz_sasa_default_radii", "fcz_sasa_dev", "fcz_sasa_packed_dev", "fcz_sasa", "fcz_sasa_packed",
            "fcz_violations_pass", "fcz_violations_dev", "fcz_violations_packed_dev", "fcz_violations", "fcz_violations_packed",

@@ -392,6 +392,60 @@ def check_lddt(cutoff, thresholds, atom, width=None):
         return slot, float(np.float32(cutoff)), tuple(float(np.float32(v)) for v in th)
 
 
+_LAYOUT_WIDTHS = {"atom37": (0, 37), "atom14": (1, 14), "backbone4": (2, 4)}  # name -> (enum fcz_dense_layout, A)
+
+
+def lddt_swaps(layout="atom37"):
+    """the default swap table of lddt_atoms as uint8 [21, A] (fcz_lddt_default_swaps): table[aatype][slot] is the slot that holds the
+    other naming of a chemically equivalent atom (ASP OD1 / OD2, GLU OE1 / OE2, PHE and TYR CD1 / CD2 and CE1 / CE2), the slot
+    itself everywhere else; backbone4 has none"""
+    if layout not in _LAYOUT_WIDTHS:
+        raise ValueError(f"unknown dense layout {layout!r}: one of {', '.join(_LAYOUT_WIDTHS)}")
+    lay, A = _LAYOUT_WIDTHS[layout]
+    table = np.zeros((21, A), np.uint8)
+    _lib.check(_lib.load().fcz_lddt_default_swaps(lay, table.ctypes.data), "fcz_lddt_default_swaps")
+    return table
+
+
+def check_lddt_atoms(cutoff, thresholds, swaps, shape, pred_shape, pred_mask_shape=None, has_aatype=True, per_atom=False):
+    """the argument rules of lddt_atoms that need no torch and no GPU -> (cutoff, thresholds, table): cutoff and thresholds as
+    check_lddt reads them; pos [n, L, A, 3] or [R, A, 3] with A = 37, 14 or 4, pred's pos of that shape and pred's mask, when there
+    is one, of the shape without its last axis; a chain bound of at most fcz_lddt_atoms_max_rows rows. swaps: "alphafold" (table
+    None: the library's default), None (no renaming: table False) or an integer array [21, A] that is an involution within each row
+    with entries < A (table: uint8 [21, A]); anything but None needs aatype. per_atom is a switch."""
+    _, cutoff, th = check_lddt(cutoff, thresholds, 1)
+    shape = tuple(shape)
+    if len(shape) not in (3, 4) or shape[-1] != 3 or shape[-2] not in (37, 14, 4):
+        raise ValueError(f"pos must be float32 [n, L, A, 3] or [R, A, 3] with A = 37, 14 or 4, not {shape}")
+    if tuple(pred_shape) != shape:
+        raise ValueError(f"pred pos must have the shape of true pos, {shape}, not {tuple(pred_shape)}")
+    if pred_mask_shape is not None and tuple(pred_mask_shape) != shape[:-1]:
+        raise ValueError(f"pred mask must have the shape of true mask, {shape[:-1]}, not {tuple(pred_mask_shape)}")
+    if not isinstance(per_atom, (bool, np.bool_)):
+        raise ValueError(f"per_atom must be True or False, not {per_atom!r}")
+    A = shape[-2]
+    limit = (2 ** 31 - 1) // (4 * A * A)
+    if shape[-3] > limit:
+        raise ValueError(f"lddt_hits must fit int32: at most {limit} rows per chain in a layout of {A} slots")
+    if swaps is None:
+        return cutoff, th, False
+    if not has_aatype:
+        raise ValueError("lddt_atoms needs aatype in `true` to rename side chains (swaps=None: no renaming)")
+    if isinstance(swaps, str):
+        if swaps != "alphafold":
+            raise ValueError(f"swaps must be 'alphafold', None or an integer array [21, {A}], not {swaps!r}")
+        return cutoff, th, None
+    table = np.asarray(swaps)
+    if table.shape != (21, A) or table.dtype.kind not in "iu":
+        raise ValueError(f"swaps must be an integer array of the shape (21, {A}), not {table.dtype} {table.shape}")
+    if (table < 0).any() or (table >= A).any():
+        raise ValueError(f"every entry of swaps must be a slot 0 .. {A - 1}")
+    table = np.ascontiguousarray(table, np.uint8)
+    if not np.array_equal(np.take_along_axis(table, table.astype(np.int64), axis=1), np.broadcast_to(np.arange(A, dtype=np.uint8), (21, A))):
+        raise ValueError("swaps must be an involution within each row: the partner of a slot's partner is the slot")
+    return cutoff, th, table
+
+
 GDT_THRESHOLDS = (0.5, 1.0, 2.0, 4.0, 8.0)                                  # the five counters of gdt_counts (include/fcz_hip.h, fcz_superpose_dev)
 
 

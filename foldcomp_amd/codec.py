@@ -292,6 +292,53 @@ class Codec:
                           score.ctypes.data, pairs.ctypes.data, hits.ctypes.data), "fcz_lddt_packed" if packed else "fcz_lddt")
         return dict(score=score, pairs=pairs, hits=hits)
 
+    def lddt_atoms(self, pos_true: np.ndarray, mask_true: np.ndarray, pos_pred: np.ndarray, mask_pred=None, aatype=None, length=None, row_off=None, *,
+                   cutoff: float = 15.0, thresholds=None, swaps="alphafold", per_atom: bool = False):
+        """two sets of dense arrays of one shape on the host -> the all-atom lDDT of `pred` against `true` after the symmetric
+        side-chain namings of the truth have been resolved (fcz_lddt_atoms, or fcz_lddt_atoms_packed when row_off is given): score
+        float32 [n, L] / [R], pairs int32, hits int32, swapped bool and, with per_atom, atom_pairs / atom_hits int32 [.., A]. The
+        arrays are Codec.lddt's, with aatype uint8 [n, L] / [R] (needed unless swaps=None); cutoff, thresholds, swaps and per_atom
+        are foldcomp.lddt_atoms'. These are counts: reproducible bit for bit and not differentiable."""
+        from . import api
+        from .structure import CLddtAtomsOut
+        pos_true = np.ascontiguousarray(pos_true, np.float32)
+        pos_pred = np.ascontiguousarray(pos_pred, np.float32)
+        packed = row_off is not None
+        if pos_true.ndim != (3 if packed else 4):
+            raise ValueError(f"pos_true must be float32 {'[R, A, 3]' if packed else '[n, L, A, 3]'} with A = 37, 14 or 4, not {pos_true.shape}")
+        masks = []
+        for name, m in (("mask_true", mask_true), ("mask_pred", mask_pred)):
+            if m is not None:
+                m = np.ascontiguousarray(m)
+                if m.shape != pos_true.shape[:-1] or m.dtype not in (np.bool_, np.uint8):
+                    raise ValueError(f"{name} must be bool / uint8 {pos_true.shape[:-1]}, not {m.dtype} {m.shape}")
+            masks.append(m)
+        if masks[0] is None:
+            raise ValueError("mask_true is needed")
+        cutoff, th, table = api.check_lddt_atoms(cutoff, thresholds, swaps, pos_true.shape, pos_pred.shape, None, aatype is not None, per_atom)
+        A, lead = pos_true.shape[-2], pos_true.shape[:-2]
+        lay = {37: 0, 14: 1, 4: 2}[A]
+        if table is False:
+            aatype = None
+        else:
+            aatype = np.ascontiguousarray(aatype)
+            if aatype.shape != lead or aatype.dtype != np.uint8:
+                raise ValueError(f"aatype must be uint8 {lead}, not {aatype.dtype} {aatype.shape}")
+        n, rows, bound = self._chain_rows(pos_true, packed, length, row_off)
+        out = dict(score=np.zeros(lead, np.float32), pairs=np.zeros(lead, np.int32), hits=np.zeros(lead, np.int32), swapped=np.zeros(lead, np.uint8))
+        if per_atom:
+            out.update(atom_pairs=np.zeros(lead + (A,), np.int32), atom_hits=np.zeros(lead + (A,), np.int32))
+        if out["score"].size:
+            th = np.asarray(th, np.float32)
+            c_out = CLddtAtomsOut(*(out[k].ctypes.data if k in out else None for k in ("score", "pairs", "hits", "swapped", "atom_pairs", "atom_hits")))
+            fn = self.lib.fcz_lddt_atoms_packed if packed else self.lib.fcz_lddt_atoms
+            _lib.check(fn(self.ctx, pos_true.ctypes.data, masks[0].ctypes.data, pos_pred.ctypes.data, None if masks[1] is None else masks[1].ctypes.data,
+                          None if aatype is None else aatype.ctypes.data, None if bound is None else bound.ctypes.data, n, rows, lay, cutoff,
+                          th.ctypes.data, table.ctypes.data if isinstance(table, np.ndarray) else None, ctypes.byref(c_out)),
+                       "fcz_lddt_atoms_packed" if packed else "fcz_lddt_atoms")
+        out["swapped"] = out["swapped"].view(np.bool_)
+        return out
+
     def secondary_structure(self, pos: np.ndarray, mask: np.ndarray, aatype=None, length=None, row_off=None):
         """dense arrays on the host -> the DSSP labels and backbone hydrogen bonds of every chain (fcz_dssp, or fcz_dssp_packed when
         row_off is given): ss uint8 [n, L] / [R] (codes in the order of foldcomp.SS_CLASSES), ss_mask bool, and the tables

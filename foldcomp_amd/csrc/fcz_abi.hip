@@ -38,6 +38,7 @@
 #include "fcz_dssp.h"
 #include "fcz_sasa.h"
 #include "fcz_violations.h"
+#include "fcz_lddt_atoms.h"
 #include "fcz_superpose.h"
 #include "fcz_tmscore.h"
 #include "fcz_frames.h"
@@ -97,13 +98,14 @@ struct timed_span { std::string name; hipEvent_t a, b; };
 // DSSP_OUT: acc_index, acc_energy, don_index, don_energy, ss, ss_mask of fcz_dssp; SASA_POINTS: the directions of fcz_sasa, SASA_OUT: sasa_points, sasa, sasa_mask;
 // SUPERPOSE_OUT: the seven arrays of a fcz_superpose_out in the struct's order; APPLY_ROT, APPLY_TRANS, APPLY_OUT: the transforms and the moved
 // coordinates of fcz_superpose_apply (its pos and mask go through LDDT_PRED); TM_SEED, TM_SELECTED: the two arrays a fcz_tmscore_out adds to those seven;
-// VIOL_OUT .. VIOL_OUT_LAST: the ten arrays of a fcz_violations_out in the struct's order
+// VIOL_OUT .. VIOL_OUT_LAST: the ten arrays of a fcz_violations_out in the struct's order; LDDTA_OUT: the six of a fcz_lddt_atoms_out
 enum { REC_BLOB, REC_OFF, REC_RES_OFF, REC_ATOM_OFF, REC_X, REC_Y, REC_Z, REC_BFAC, REC_RES_CODE, REC_ATOM_CODE,
        FILES_TEXT = 0, FILES_OFF, FILES_NAMES, FILES_NAME_OFF, FILES_STEM_LEN, BATCH_IN = 0, DENSE_IN = 0, LDDT_PRED = 4, DENSE_OUT = 10, LDDT_OUT = 10, SUPERPOSE_OUT = 10, DSSP_OUT = 10,
        SASA_POINTS = 4, SASA_OUT = 10,
        APPLY_ROT = 10, APPLY_TRANS, APPLY_OUT,
        PACKED_OUT = 10, ANGLES_OUT = 10, KEPT_OFF = 13, KEPT_BYTES, KEPT_STATUS, PACKED_OUT_LAST, WINDOW_START = PACKED_OUT_LAST, TM_SEED, TM_SELECTED,
-       VIOL_OUT = 10, VIOL_OUT_LAST = 19, POOL_COUNT };
+       VIOL_OUT = 10, LDDTA_OUT = 10, VIOL_OUT_LAST = 19, POOL_COUNT };
+static_assert(POOL_COUNT == VIOL_OUT_LAST + 1 && LDDTA_OUT + 6 <= POOL_COUNT && TM_SELECTED < POOL_COUNT, "the last name of the enum sizes fcz_ctx::pool");
 
 // what the device reports to the host in the middle of a call: one pinned allocation, a member per reader
 struct pinned_words {
@@ -176,6 +178,7 @@ struct fcz_ctx {
     //   fcz_compress_dense_packed_begin[_dev]       as the two above (DENSE_IN 3 = row_off)     the same
     //   fcz_knn / fcz_knn_packed                    DENSE_IN 0, 1, 3 (pos, mask, length / row_off), DENSE_OUT 10 .. 11 (index, dist)
     //   fcz_lddt / fcz_lddt_packed                  DENSE_IN 0, 1, 3 (pos_true, mask_true, length / row_off), LDDT_PRED 4 .. 5 (pos_pred, mask_pred), LDDT_OUT 10 .. 12
+    //   fcz_lddt_atoms / fcz_lddt_atoms_packed      DENSE_IN 0 .. 3 (pos_true, mask_true, aatype, length / row_off), LDDT_PRED 4 .. 5, LDDTA_OUT 10 .. 15
     //   fcz_superpose / fcz_superpose_packed        DENSE_IN 0, 1, 3 and LDDT_PRED 4 .. 5 as fcz_lddt, SUPERPOSE_OUT 10 .. 16
     //   fcz_tmscore / fcz_tmscore_packed            the same, then TM_SEED 17, TM_SELECTED 18
     //   fcz_superpose_apply[_packed]                LDDT_PRED 4 .. 5 (pos, mask), DENSE_IN 3 (length / row_off), APPLY_ROT 10, APPLY_TRANS 11, APPLY_OUT 12
@@ -1928,6 +1931,133 @@ int fcz_lddt_packed(fcz_ctx* ctx, const float* pos_true, const uint8_t* mask_tru
     if (!lddt_args_ok(ctx, pos_true, mask_true, pos_pred, layout, slot, cutoff, thresholds, R, score, pairs, hits) || !bound_ok(true, row_off, n, R))
         return FCZ_E_INVALID_ARG;
     return lddt_host(ctx, pos_true, mask_true, pos_pred, mask_pred, row_off, true, n, R, layout, slot, cutoff, thresholds, score, pairs, hits);
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------------
+// all-atom lDDT with symmetric side-chain renaming (fcz_lddt_atoms.h; no counterpart in the reference)
+// ------------------------------------------------------------------------------------------------
+// rows: L (padded) or R (packed). Fills tab from swap_table (NULL: the default) when everything is acceptable.
+static bool lddta_args_ok(const fcz_ctx* ctx, const float* pos_true, const uint8_t* mask_true, const float* pos_pred, int layout, float cutoff,
+                          const float* thresholds, const uint8_t* swap_table, uint32_t rows, const fcz_lddt_atoms_out* out, lddta_table* tab) {
+    const int A = fcz_dense_width(layout);
+    if (!ctx || !pos_true || !mask_true || !pos_pred || !out || !out->score || !out->pairs || !out->hits || !out->swapped || A <= 0) return false;
+    if (!std::isfinite(cutoff) || !(cutoff > 0.0f) || rows > (uint32_t)fcz_lddt_atoms_max_rows(layout)) return false;
+    if (thresholds) for (int t = 0; t < 4; t++) if (std::isnan(thresholds[t])) return false;
+    memset(tab->partner, 0, sizeof tab->partner);
+    if (swap_table) memcpy(tab->partner, swap_table, LDDTA_TYPES * (size_t)A);
+    else if (fcz_lddt_default_swaps(layout, tab->partner) != FCZ_OK) return false;
+    for (int ty = 0; ty < (int)LDDTA_TYPES; ty++)
+        for (int a = 0; a < A; a++) {
+            const int p = tab->partner[ty * A + a];
+            if (p >= A || tab->partner[ty * A + p] != a) return false;        // inside the row, and an involution
+        }
+    return true;
+}
+
+// fcz_lddt_atoms_dev (bound_dev is length [n] or NULL, rows = L) and fcz_lddt_atoms_packed_dev (bound_dev = row_off [n + 1], rows = R):
+// the fill (packed), then the decide sweep over tiles of its own, then the score sweep, in stream order
+static int lddta_rows(fcz_ctx* ctx, const float* pos_true_dev, const uint8_t* mask_true_dev, const float* pos_pred_dev, const uint8_t* mask_pred_dev,
+                      const uint8_t* aatype_dev, const uint32_t* bound_dev, bool packed, uint32_t n, uint32_t rows, int layout, float cutoff,
+                      const float* thresholds, const lddta_table& tab, const fcz_lddt_atoms_out& o) {
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (rows == 0 || (n == 0 && !packed)) return FCZ_OK;
+    const float* th = thresholds ? thresholds : LDDT_THRESHOLDS;
+    const lddta_args g{pos_true_dev, mask_true_dev, pos_pred_dev, mask_pred_dev, aatype_dev, bound_dev, n, rows, (uint32_t)fcz_dense_width(layout),
+                       lddt_c2(cutoff), th[0], th[1], th[2], th[3], o.score, o.pairs, o.hits, o.swapped, o.atom_pairs, o.atom_hits};
+    chain_tiles decide(ctx, packed, n, rows, lddta_tile_rows(g.A, true), 12u), score(ctx, packed, n, rows, lddta_tile_rows(g.A, false), 12u);
+    int rc = decide.reserve(); if (rc) return rc;
+    rc = score.reserve(); if (rc) return rc;                                  // (the same scratch: the decide sweep has read its tiles by then)
+    span_guard sg(ctx, "lddt_atoms");
+    rc = decide.run(bound_dev, [&] { hipLaunchKernelGGL(k_lddt_atoms_fill, decide.fill_grid(rows), dim3(BLOCK), 0, ctx->stream, g); },
+                    [&](auto P, dim3 grid, const uint64_t* tile_off, uint32_t tiles_per_entry, uint64_t n_padded) {
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_lddt_atoms<decltype(P)::value, true>), grid, dim3(BLOCK), 0, ctx->stream, g, tab, tile_off, tiles_per_entry, n_padded);
+    });
+    if (rc) return rc;
+    return score.run(bound_dev, [] {}, [&](auto P, dim3 grid, const uint64_t* tile_off, uint32_t tiles_per_entry, uint64_t n_padded) {
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_lddt_atoms<decltype(P)::value, false>), grid, dim3(BLOCK), 0, ctx->stream, g, tab, tile_off, tiles_per_entry, n_padded);
+    });
+}
+
+// fcz_lddt_atoms and fcz_lddt_atoms_packed: the host arrays through DENSE_IN 0 .. 3, LDDT_PRED 4, 5 and LDDTA_OUT 10 .. 15
+static int lddta_host(fcz_ctx* ctx, const float* pos_true, const uint8_t* mask_true, const float* pos_pred, const uint8_t* mask_pred, const uint8_t* aatype,
+                      const uint32_t* bound, bool packed, uint32_t n, uint32_t rows_per, int layout, float cutoff, const float* thresholds,
+                      const lddta_table& tab, const fcz_lddt_atoms_out& o) {
+    const dense_bytes b(packed, n, rows_per, layout, bound);
+    const size_t r = b.rows;
+    return staged_call(ctx, {{pos_true, b.pos, DENSE_IN}, {mask_true, b.mask, DENSE_IN + 1}, {aatype, r, DENSE_IN + 2}, {bound, b.bound, DENSE_IN + 3},
+                             {pos_pred, b.pos, LDDT_PRED}, {mask_pred, b.mask, LDDT_PRED + 1}},
+                       {{o.score, r * 4, LDDTA_OUT}, {o.pairs, r * 4, LDDTA_OUT + 1}, {o.hits, r * 4, LDDTA_OUT + 2}, {o.swapped, r, LDDTA_OUT + 3},
+                        {o.atom_pairs, b.mask * 4, LDDTA_OUT + 4}, {o.atom_hits, b.mask * 4, LDDTA_OUT + 5}},
+                       [&](const void* const* in, void* const* out) {
+        const fcz_lddt_atoms_out d{(float*)out[0], (int32_t*)out[1], (int32_t*)out[2], (uint8_t*)out[3], (int32_t*)out[4], (int32_t*)out[5]};
+        return lddta_rows(ctx, (const float*)in[0], (const uint8_t*)in[1], (const float*)in[4], (const uint8_t*)in[5], (const uint8_t*)in[2],
+                          (const uint32_t*)in[3], packed, n, rows_per, layout, cutoff, thresholds, tab, d);
+    });
+}
+
+extern "C" {
+
+int fcz_lddt_atoms_pass(void) { return (int)LDDTA_PASS; }
+
+int fcz_lddt_atoms_max_rows(int layout) {
+    const int A = fcz_dense_width(layout);
+    return A > 0 ? (int)lddta_max_rows((uint32_t)A) : -1;
+}
+
+int fcz_lddt_default_swaps(int layout, uint8_t* out) {
+    const int A = fcz_dense_width(layout);
+    if (A <= 0 || !out) return FCZ_E_INVALID_ARG;
+    for (int ty = 0; ty < (int)LDDTA_TYPES; ty++)
+        for (int a = 0; a < A; a++) out[ty * A + a] = (uint8_t)a;
+    // the renamings of AlphaFold's residue_atom_renaming_swaps: ASP, GLU, PHE, TYR by their aatype (= residue code)
+    static const struct { int type; const char* a; const char* b; } swaps[] = {{3, "OD1", "OD2"}, {6, "OE1", "OE2"}, {13, "CD1", "CD2"}, {13, "CE1", "CE2"},
+                                                                               {18, "CD1", "CD2"}, {18, "CE1", "CE2"}};
+    for (const auto& s : swaps) {
+        const int x = fcz_dense_slot(layout, s.type, fcz_atom_code_from_name(s.a)), y = fcz_dense_slot(layout, s.type, fcz_atom_code_from_name(s.b));
+        if (x < 0 || y < 0) continue;                                         // (backbone4 holds neither)
+        out[s.type * A + x] = (uint8_t)y; out[s.type * A + y] = (uint8_t)x;
+    }
+    return FCZ_OK;
+}
+
+int fcz_lddt_atoms_dev(fcz_ctx* ctx, const float* pos_true_dev, const uint8_t* mask_true_dev, const float* pos_pred_dev, const uint8_t* mask_pred_dev,
+                       const uint8_t* aatype_dev, const uint32_t* length_dev, uint32_t n, uint32_t L, int layout, float cutoff, const float* thresholds,
+                       const uint8_t* swap_table, const fcz_lddt_atoms_out* out_dev) {
+    lddta_table tab;
+    if (!lddta_args_ok(ctx, pos_true_dev, mask_true_dev, pos_pred_dev, layout, cutoff, thresholds, swap_table, L, out_dev, &tab) ||
+        !bound_ok(false, length_dev, n, L))
+        return FCZ_E_INVALID_ARG;
+    return lddta_rows(ctx, pos_true_dev, mask_true_dev, pos_pred_dev, mask_pred_dev, aatype_dev, length_dev, false, n, L, layout, cutoff, thresholds, tab, *out_dev);
+}
+
+int fcz_lddt_atoms_packed_dev(fcz_ctx* ctx, const float* pos_true_dev, const uint8_t* mask_true_dev, const float* pos_pred_dev, const uint8_t* mask_pred_dev,
+                              const uint8_t* aatype_dev, const uint32_t* row_off_dev, uint32_t n, uint32_t R, int layout, float cutoff, const float* thresholds,
+                              const uint8_t* swap_table, const fcz_lddt_atoms_out* out_dev) {
+    lddta_table tab;
+    if (!lddta_args_ok(ctx, pos_true_dev, mask_true_dev, pos_pred_dev, layout, cutoff, thresholds, swap_table, R, out_dev, &tab) ||
+        !bound_ok(true, row_off_dev, n, R))
+        return FCZ_E_INVALID_ARG;
+    return lddta_rows(ctx, pos_true_dev, mask_true_dev, pos_pred_dev, mask_pred_dev, aatype_dev, row_off_dev, true, n, R, layout, cutoff, thresholds, tab, *out_dev);
+}
+
+int fcz_lddt_atoms(fcz_ctx* ctx, const float* pos_true, const uint8_t* mask_true, const float* pos_pred, const uint8_t* mask_pred, const uint8_t* aatype,
+                   const uint32_t* length, uint32_t n, uint32_t L, int layout, float cutoff, const float* thresholds, const uint8_t* swap_table,
+                   const fcz_lddt_atoms_out* out) {
+    lddta_table tab;
+    if (!lddta_args_ok(ctx, pos_true, mask_true, pos_pred, layout, cutoff, thresholds, swap_table, L, out, &tab) || !bound_ok(false, length, n, L))
+        return FCZ_E_INVALID_ARG;
+    return lddta_host(ctx, pos_true, mask_true, pos_pred, mask_pred, aatype, length, false, n, L, layout, cutoff, thresholds, tab, *out);
+}
+
+int fcz_lddt_atoms_packed(fcz_ctx* ctx, const float* pos_true, const uint8_t* mask_true, const float* pos_pred, const uint8_t* mask_pred,
+                          const uint8_t* aatype, const uint32_t* row_off, uint32_t n, uint32_t R, int layout, float cutoff, const float* thresholds,
+                          const uint8_t* swap_table, const fcz_lddt_atoms_out* out) {
+    lddta_table tab;
+    if (!lddta_args_ok(ctx, pos_true, mask_true, pos_pred, layout, cutoff, thresholds, swap_table, R, out, &tab) || !bound_ok(true, row_off, n, R))
+        return FCZ_E_INVALID_ARG;
+    return lddta_host(ctx, pos_true, mask_true, pos_pred, mask_pred, aatype, row_off, true, n, R, layout, cutoff, thresholds, tab, *out);
 }
 
 }  // extern "C"

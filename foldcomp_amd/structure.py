@@ -986,6 +986,11 @@ class CViolationsOut(ctypes.Structure):
                                                "link_cos", "link_violation", "chain_counts")]
 
 
+class CLddtAtomsOut(ctypes.Structure):
+    """fcz_lddt_atoms_out (include/fcz_hip.h): the outputs of the all-atom lDDT calls; atom_pairs and atom_hits may be None"""
+    _fields_ = [(k, ctypes.c_void_p) for k in ("score", "pairs", "hits", "swapped", "atom_pairs", "atom_hits")]
+
+
 class CTmScoreOut(ctypes.Structure):
     """fcz_tmscore_out (include/fcz_hip.h): fcz_superpose_out's seven arrays, then seed and selected; all but rot and trans may be None"""
     _fields_ = CSuperposeOut._fields_ + [("seed", ctypes.c_void_p), ("selected", ctypes.c_void_p)]

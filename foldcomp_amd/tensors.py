@@ -14,6 +14,9 @@
                                    the k nearest CA / CB sites of every residue inside its chain; decode_tensors(neighbors=k) adds them
     lddt(pred, true, atom="CA", cutoff=15.0) -> dict(lddt [..] float32, lddt_pairs, lddt_hits int32, lddt_chain [n] float32): the per-residue
                                    lDDT of predicted coordinates against a decoded batch, and its chain mean
+    lddt_atoms(pred, true, swaps="alphafold", per_atom=False) -> dict(lddt, lddt_pairs, lddt_hits, swapped [..] bool, lddt_chain [n]
+                                   float64, atom_pairs / atom_hits [.., A]): the all-atom lDDT of every residue after the symmetric
+                                   side-chain namings of the truth have been resolved towards the prediction
     superpose(pred, true, atom="CA", apply=False) -> dict(rot [n, 3, 3], trans [n, 3], rmsd [n], sites [n], dev [..], gdt_counts [n, 5],
                                    gdt_ts, gdt_ha, tm [n]): the least-squares superposition of every chain of pred onto true;
                                    apply=True adds pos_aligned; apply_transform(pos, rot, trans, batch) is that step alone
@@ -51,9 +54,9 @@ import numpy as np
 from . import _lib, api, fczfile
 from ._aa_tables import RES1
 from .codec import ANGLE_COLUMNS, Codec, dense_layout
-from .structure import CAtomsOut, CDenseIn, CDenseOut, CPackedOut, CSuperposeOut, CTmScoreOut, CViolationsOut
+from .structure import CAtomsOut, CDenseIn, CDenseOut, CLddtAtomsOut, CPackedOut, CSuperposeOut, CTmScoreOut, CViolationsOut
 
-__all__ = ["decode_tensors", "encode_tensors", "decode_angles", "crop_starts", "neighbor_graph", "rigid_frames", "lddt", "superpose", "tm_score", "apply_transform",
+__all__ = ["decode_tensors", "encode_tensors", "decode_angles", "crop_starts", "neighbor_graph", "rigid_frames", "lddt", "lddt_atoms", "superpose", "tm_score", "apply_transform",
            "backbone_hbonds", "secondary_structure", "solvent_accessibility", "violations"]
 
 
@@ -675,6 +678,90 @@ def lddt(pred, true, *, atom="CA", cutoff: float = 15.0, thresholds=(0.5, 1.0, 2
         ch, cp = hits.to(torch.int64).sum(dim=1), pairs.to(torch.int64).sum(dim=1)
     chain = torch.where(cp > 0, ch.to(torch.float64) / (4 * cp).clamp(min=1).to(torch.float64), torch.zeros((), dtype=torch.float64, device=dev))
     return dict(lddt=score, lddt_pairs=pairs, lddt_hits=hits, lddt_chain=chain.to(torch.float32))
+
+
+def lddt_atoms(pred, true, *, cutoff: float = 15.0, thresholds=(0.5, 1.0, 2.0, 4.0), swaps="alphafold", per_atom: bool = False,
+               codec: Optional[Codec] = None) -> dict:
+    """predicted coordinates against true ones, both dense tensors on the GPU -> the all-atom lDDT of every residue, after the
+    chemically equivalent side-chain namings of the truth have been resolved towards the prediction; no atoms x atoms matrix.
+
+    `true` and `pred` are lddt's: `true` the dict decode_tensors / tensor_batches return, padded or packed, `pred` a dict with `pos`
+    and optionally `mask`, or just the pos tensor, of the same shape. `true` must carry `aatype` unless swaps=None. An atom is a slot
+    of a row inside its chain with both masks set and six finite coordinates. For an atom i the pairs are the atoms j of the OTHER
+    residues of its chain with d_true(i, j) < cutoff; a pair scores one hit for every threshold |d_true - d_pred| lies under.
+        swapped      [n, L] / [R] bool       True where the truth of the residue is read under its other naming: the residue has
+                                             atoms with one (ASP OD1 / OD2, GLU OE1 / OE2, PHE and TYR CD1 / CD2 with CE1 / CE2), all of
+                                             them are present, and against the atoms without one of the chain's other residues the
+                                             other naming scores the strictly larger hits / pairs (AlphaFold's alt_naming_is_better)
+        lddt         float32                 hits / (4 * pairs) over the residue's atoms, 0 where it has no pair
+        lddt_pairs   int32, lddt_hits int32  the two sums
+        lddt_chain   [n] float64             sum of hits / (4 * sum of pairs) over the chain's rows (float64 from int64 sums, so
+                                             exact whatever the order), 0 where the chain has no pair
+        atom_pairs, atom_hits [.., A] int32  with per_atom=True: the two counts of every atom, at the prediction's slot
+    swaps: "alphafold" (foldcomp.lddt_swaps(layout)), None (no renaming) or an integer array [21, A]: swaps[aatype][slot] is the
+    slot of the other naming, the slot itself where there is none. Distances are sqrt((dx*dx + dy*dy) + dz*dz) in float32 and all
+    counters integers (include/fcz_hip.h, fcz_lddt_atoms_dev): reproducible bit for bit, the same in atom37 and atom14, NOT
+    differentiable. The tensors must be contiguous and lie on the codec's device; the arguments are checked first, without torch or a
+    device (api.check_lddt_atoms)."""
+    t = dict(true) if isinstance(true, dict) else {"pos": true}
+    p = dict(pred) if isinstance(pred, dict) else {"pos": pred}
+    for name, d, keys in (("true", t, ("pos", "mask")), ("pred", p, ("pos",))):
+        for key in keys:
+            if d.get(key) is None:
+                raise TypeError(f"lddt_atoms needs the tensor {key!r} of {name}")
+    pos, ppos, pmask = t["pos"], p["pos"], p.get("mask")
+    shape = tuple(getattr(pos, "shape", ()))
+    is_packed = t.get("cu_seqlens") is not None and len(shape) == 3
+    cutoff, th, table = api.check_lddt_atoms(cutoff, thresholds, swaps, shape, tuple(getattr(ppos, "shape", ())),
+                                             None if pmask is None else tuple(getattr(pmask, "shape", ())), t.get("aatype") is not None, per_atom)
+    c = codec or api.default_codec()
+    try:
+        import torch
+    except ImportError as e:
+        raise api.error(f"lddt_atoms needs PyTorch (ROCm build): {e}") from None
+    if not isinstance(pos, torch.Tensor):
+        raise api.error("lddt_atoms takes torch tensors on the GPU (numpy arrays: Codec.lddt_atoms)")
+    if pos.device.type != "cuda" or pos.device.index != int(c.device):
+        raise api.error(f"lddt_atoms: pos lies on {pos.device}, the codec works on cuda:{int(c.device)}; there is no CPU path")
+    dev = pos.device
+    if len(shape) != (3 if is_packed else 4):
+        raise ValueError(f"pos must be float32 [n, L, A, 3], or [R, A, 3] beside cu_seqlens, not {pos.dtype} {shape}")
+    A, lead = shape[-2], shape[:-2]
+    lay = dense_layout(_WIDTH_LAYOUT[A])
+    _on_device(torch, "lddt_atoms", dev, "pos", pos, shape, (torch.float32,))
+    mask = _on_device(torch, "lddt_atoms", dev, "mask", t["mask"], shape[:-1], (torch.bool, torch.uint8)).view(torch.uint8)
+    _on_device(torch, "lddt_atoms", dev, "pred pos", ppos, shape, (torch.float32,))
+    if pmask is not None:
+        pmask = _on_device(torch, "lddt_atoms", dev, "pred mask", pmask, shape[:-1], (torch.bool, torch.uint8)).view(torch.uint8)
+    aatype = None
+    if table is not False:
+        aatype = _on_device(torch, "lddt_atoms", dev, "aatype", t["aatype"], lead, (torch.uint8,))
+    n, rows, bound = _chain_bound(torch, "lddt_atoms", dev, t, shape, is_packed)
+    score = torch.zeros(lead, dtype=torch.float32, device=dev)
+    pairs = torch.zeros(lead, dtype=torch.int32, device=dev)
+    hits = torch.zeros(lead, dtype=torch.int32, device=dev)
+    swapped = torch.zeros(lead, dtype=torch.uint8, device=dev)
+    atom = [torch.zeros(lead + (A,), dtype=torch.int32, device=dev) for _ in range(2)] if per_atom else None
+    if score.numel():
+        th_c = (ctypes.c_float * 4)(*th)
+        c_out = CLddtAtomsOut(score.data_ptr(), pairs.data_ptr(), hits.data_ptr(), swapped.data_ptr(), *((a.data_ptr() for a in atom) if atom else (None, None)))
+        torch.cuda.current_stream(dev).synchronize()
+        fn, name = (c.lib.fcz_lddt_atoms_packed_dev, "fcz_lddt_atoms_packed_dev") if is_packed else (c.lib.fcz_lddt_atoms_dev, "fcz_lddt_atoms_dev")
+        _lib.check(fn(c.ctx, pos.data_ptr(), mask.data_ptr(), ppos.data_ptr(), None if pmask is None else pmask.data_ptr(),
+                      None if aatype is None else aatype.data_ptr(), None if bound is None else bound.data_ptr(), n, rows, lay, cutoff,
+                      ctypes.addressof(th_c), table.ctypes.data if isinstance(table, np.ndarray) else None, ctypes.byref(c_out)), name)
+        c.synchronize()
+    if is_packed:   # a cumulative sum differenced at cu_seqlens
+        zero = torch.zeros(1, dtype=torch.int64, device=dev)
+        at = bound.to(torch.int64)
+        ch, cp = (torch.cat([zero, x.to(torch.int64).cumsum(0)])[at].diff() for x in (hits, pairs))
+    else:
+        ch, cp = hits.to(torch.int64).sum(dim=1), pairs.to(torch.int64).sum(dim=1)
+    chain = torch.where(cp > 0, ch.to(torch.float64) / (4 * cp).clamp(min=1).to(torch.float64), torch.zeros((), dtype=torch.float64, device=dev))
+    out = dict(lddt=score, lddt_pairs=pairs, lddt_hits=hits, swapped=swapped.view(torch.bool), lddt_chain=chain)
+    if atom:
+        out.update(atom_pairs=atom[0], atom_hits=atom[1])
+    return out
 
 
 def _apply_transform(c, pos, mask, rot, trans, n, rows, bound, is_packed, lay, out):

@@ -19,6 +19,7 @@
  *                                                          fcz_dense_window_dev / fcz_decompress_dense_window
  *   (none: no neighbour graph of the decoded chain)        fcz_knn_dev / fcz_knn_packed_dev, fcz_knn / fcz_knn_packed
  *   (none: no score of one structure against another)      fcz_lddt_dev / fcz_lddt_packed_dev, fcz_lddt / fcz_lddt_packed
+ *   (none: no all-atom score, no side-chain renaming)      fcz_lddt_atoms_dev / fcz_lddt_atoms_packed_dev, fcz_lddt_atoms / fcz_lddt_atoms_packed
  *   (none: no secondary structure)                         fcz_hbond_dev, fcz_dssp_labels_dev, fcz_dssp (+ _packed forms)
  *   (none: no solvent accessibility)                       fcz_sasa_dev / fcz_sasa_packed_dev, fcz_sasa / fcz_sasa_packed
  *   (none: no structural violations)                       fcz_violations_dev / fcz_violations_packed_dev, fcz_violations / fcz_violations_packed
@@ -444,6 +445,84 @@ int fcz_lddt(fcz_ctx* ctx, const float* pos_true, const uint8_t* mask_true, cons
 int fcz_lddt_packed(fcz_ctx* ctx, const float* pos_true, const uint8_t* mask_true, const float* pos_pred, const uint8_t* mask_pred,
                     const uint32_t* row_off, uint32_t n, uint32_t R, int layout, int slot, float cutoff, const float* thresholds,
                     float* score, int32_t* pairs, int32_t* hits);
+
+/* ---- all-atom lDDT with symmetric side-chain renaming ------------------------------------------------------ */
+/* The lDDT that CASP, CAMEO and model papers report: every heavy atom against every heavy atom of the other residues of its chain,
+ * after the chemically equivalent namings of the truth's side chains (ASP OD1 / OD2, GLU OE1 / OE2, PHE and TYR CD1 / CD2 with
+ * CE1 / CE2) have been resolved towards the prediction, so that a ring flipped by 180 degrees is not punished. The renaming decision
+ * is an output of its own (AlphaFold's alt_naming_is_better). For a whole batch on the device, without a rows x rows or an
+ * atoms x atoms array. The reference has no such output: like fcz_lddt_dev these stand beside Foldcomp::decompress
+ * (src/foldcomp.cpp:779). The inputs are fcz_lddt_dev's: two tensors of ONE shape and layout, pos_true / mask_true and pos_pred /
+ * mask_pred (mask_pred may be NULL: every slot present); padded pos [n][L][A][3] float32, mask [n][L][A] uint8, length [n] uint32 (may
+ * be NULL); packed pos [R][A][3], mask [R][A], row_off [n + 1] uint32; and with them
+ *   aatype        [n][L] / [R] uint8 or NULL. NULL: no slot has another naming, nothing is renamed. A type above 20 uses row 20.
+ *   swap_table    a HOST table [21][A] uint8, handed to the kernel by value: swap_table[t][a] is the PARTNER slot of slot a in a
+ *                 residue of type t, a itself where the slot has no other naming. NULL selects fcz_lddt_default_swaps(layout, ..)
+ *                 (pure host): the four AlphaFold swaps above at the slots fcz_dense_slot gives the atoms, so atom37 and atom14
+ *                 describe the same atoms, and none in backbone4. A table must be an involution within each row with entries < A.
+ *   cutoff, thresholds   as for fcz_lddt_dev (thresholds: four float32 on the HOST, NULL: 0.5, 1, 2, 4).
+ * All arithmetic is float32 with every operation rounded and no FMA: d2 = (dx*dx + dy*dy) + dz*dz, d its correctly rounded root;
+ * d_true < cutoff is decided as d2 < fcz_lddt_c2(cutoff), which is the same. A row is inside its chain by fcz_lddt_dev's rules. A
+ * slot (row, a) is PRESENT when mask_true and mask_pred are set at a and the six coordinates at a are finite.
+ *   1. renaming   Row r inside its chain is AMBIGUOUS when some slot a has partner(a) != a under its type, and DECIDABLE when every
+ *                 such slot is present. Its ANCHORS are the present slots (j, b) of the rows j != r of its chain where b has no
+ *                 partner under row j's type. Under naming v = 0 the true coordinate of (r, a) is true[r][a], under v = 1 it is
+ *                 true[r][partner(a)]; the prediction is pred[r][a] under both. P_v = the (ambiguous slot a of r, anchor) pairs
+ *                 with d_true_v < cutoff, H_v = the sum over those pairs and the four thresholds t of
+ *                 [|d_true_v - d_pred| < thresholds[t]], d_pred between pred[r][a] and the anchor's prediction.
+ *                 swapped[r] = 1 exactly when (uint64)H_1 * P_0 > (uint64)H_0 * P_1: naming 1 has the strictly larger H / P, compared
+ *                 without a division. 0 otherwise, for rows that are not decidable, and everywhere when aatype is NULL.
+ *   2. score      The RENAMED TRUTH reads pos_true and mask_true of row r at partner(a) where swapped[r], at a elsewhere. An ATOM
+ *                 is a slot (row, a) of a row inside its chain whose renamed-true mask and pred mask are set and whose six
+ *                 coordinates are finite. For atoms i, j of DIFFERENT rows of one chain: j is a pair of i when d_true'(i, j) <
+ *                 cutoff; a pair scores one hit per threshold that |d_true' - d_pred| lies under (one rounded subtraction; a NaN
+ *                 or +inf difference is a pair with no hit).
+ *   score [rows] float32      (float)hits / (float)(4 * pairs), a single rounded division; 0.0 where pairs == 0
+ *   pairs [rows] int32, hits [rows] int32     the sums over the row's atoms
+ *   swapped [rows] uint8
+ *   atom_pairs, atom_hits [rows][A] int32     optional (NULL: not wanted): the two counts of the atom at the PREDICTION's slot, 0
+ *                                             where the slot holds no atom
+ * rows = n * L (padded) or R (packed). Rows that are not inside a chain, rows behind length and packed rows no chain covers hold 0
+ * everywhere. Every element of every wanted output is written whatever the inputs hold, nothing outside them is written, and
+ * nothing outside the inputs is read, whatever row_off or aatype holds (ranges that overlap are each computed and a shared row's
+ * values are then unspecified). Every index that scales with rows * A is 64-bit. All counters are integers, so no order of
+ * evaluation changes a result: reproducible bit for bit, the same for the same atoms in atom37 and atom14, NOT differentiable.
+ * A row's hits, at most 4 * A * A * (rows of the chain), must fit int32: fcz_lddt_atoms_max_rows(layout) (pure host) is
+ * floor((2^31 - 1) / (4 * A * A)), -1 for an unknown layout. A chain's candidates are staged in passes of at most
+ * fcz_lddt_atoms_pass() (pure host, > 0): a chain with more takes several, with the same result. The work is two sweeps in stream
+ * order, the renaming of every row of a chain before the score of any. Enqueued on the ctx stream, no synchronisation (the packed
+ * forms share fcz_knn_packed_dev's scratch in the ctx). FCZ_E_INVALID_ARG with nothing launched: NULL ctx / pos_true / mask_true /
+ * pos_pred / out / score / pairs / hits / swapped, NULL row_off with n > 0, unknown layout, L == 0, a cutoff that is not finite and
+ * > 0, a threshold that is NaN, L (padded) or R (packed) above fcz_lddt_atoms_max_rows(layout), a swap_table with an entry >= A or
+ * a row that is no involution. n == 0 or R == 0: FCZ_OK (packed, n == 0 < R: every row is uncovered and is filled). The time goes
+ * to a group of its own, "lddt_atoms", for both forms. */
+typedef struct fcz_lddt_atoms_out {
+    float*   score;             /* [rows] */
+    int32_t* pairs;             /* [rows] */
+    int32_t* hits;              /* [rows] */
+    uint8_t* swapped;           /* [rows] */
+    int32_t* atom_pairs;        /* [rows][A] optional */
+    int32_t* atom_hits;         /* [rows][A] optional */
+} fcz_lddt_atoms_out;
+int fcz_lddt_atoms_pass(void);
+int fcz_lddt_atoms_max_rows(int layout);
+/* pure host: out [21][A] uint8, the default swap_table; FCZ_E_INVALID_ARG for an unknown layout or a NULL out */
+int fcz_lddt_default_swaps(int layout, uint8_t* out);
+int fcz_lddt_atoms_dev(fcz_ctx* ctx, const float* pos_true_dev, const uint8_t* mask_true_dev, const float* pos_pred_dev,
+                       const uint8_t* mask_pred_dev, const uint8_t* aatype_dev, const uint32_t* length_dev, uint32_t n, uint32_t L,
+                       int layout, float cutoff, const float* thresholds, const uint8_t* swap_table /* host, or NULL */,
+                       const fcz_lddt_atoms_out* out_dev);
+int fcz_lddt_atoms_packed_dev(fcz_ctx* ctx, const float* pos_true_dev, const uint8_t* mask_true_dev, const float* pos_pred_dev,
+                              const uint8_t* mask_pred_dev, const uint8_t* aatype_dev, const uint32_t* row_off_dev, uint32_t n,
+                              uint32_t R, int layout, float cutoff, const float* thresholds,
+                              const uint8_t* swap_table /* host, or NULL */, const fcz_lddt_atoms_out* out_dev);
+/* Host-pointer conveniences: the same arrays on the host, staged through the ctx like fcz_lddt; synchronous. */
+int fcz_lddt_atoms(fcz_ctx* ctx, const float* pos_true, const uint8_t* mask_true, const float* pos_pred, const uint8_t* mask_pred,
+                   const uint8_t* aatype, const uint32_t* length, uint32_t n, uint32_t L, int layout, float cutoff,
+                   const float* thresholds, const uint8_t* swap_table, const fcz_lddt_atoms_out* out);
+int fcz_lddt_atoms_packed(fcz_ctx* ctx, const float* pos_true, const uint8_t* mask_true, const float* pos_pred,
+                          const uint8_t* mask_pred, const uint8_t* aatype, const uint32_t* row_off, uint32_t n, uint32_t R, int layout,
+                          float cutoff, const float* thresholds, const uint8_t* swap_table, const fcz_lddt_atoms_out* out);
 
 /* ---- backbone hydrogen bonds and DSSP secondary structure of the dense tensors ------------------------------ */
 /* The per-residue secondary structure of Kabsch & Sander (1983) and the backbone hydrogen bonds it rests on, for a whole batch on
@@ -1171,7 +1250,7 @@ int fcz_check(const uint8_t* entry, uint64_t len);
  * group since the last reset: "compress_sizes", "compress_index", "compress_angles", "compress_pack",
  * "decompress_sizes", "decompress_backbone", "decompress_index", "decompress_sidechain", "pdb_sizes", "pdb_format", "extract_sizes", "extract",
  * "ingest_parse", "ingest_parse_cif", "ingest_rows_cif", "ingest_frags", "ingest_fill", "inflate", "dense", "undense" (the counting and the fill
- * kernel of fcz_undense_dev: two launches per call), "angles" (fcz_angles_dev), "knn" (fcz_knn_dev and fcz_knn_packed_dev), "lddt" (fcz_lddt_dev and fcz_lddt_packed_dev), "superpose" (fcz_superpose_dev, fcz_superpose_apply_dev and their packed forms), "tmscore" (fcz_tmscore_dev and fcz_tmscore_packed_dev), "frames" (fcz_frames_dev). Every other packed or windowed entry point is timed under the
+ * kernel of fcz_undense_dev: two launches per call), "angles" (fcz_angles_dev), "knn" (fcz_knn_dev and fcz_knn_packed_dev), "lddt" (fcz_lddt_dev and fcz_lddt_packed_dev), "lddt_atoms" (fcz_lddt_atoms_dev and fcz_lddt_atoms_packed_dev), "superpose" (fcz_superpose_dev, fcz_superpose_apply_dev and their packed forms), "tmscore" (fcz_tmscore_dev and fcz_tmscore_packed_dev), "frames" (fcz_frames_dev). Every other packed or windowed entry point is timed under the
  * group of its padded form: fcz_dense_packed_dev and fcz_dense_window_dev under "dense", fcz_undense_packed_dev under "undense",
  * fcz_angles_packed_dev and fcz_angles_window_dev under "angles". */
 int  fcz_ctx_enable_timing(fcz_ctx* ctx, int enable);

@@ -10,7 +10,7 @@ points used by bench.py take raw device pointers (e.g. torch tensors' .data_ptr(
 from __future__ import annotations
 
 import ctypes
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import numpy as np
 
@@ -21,6 +21,7 @@ from .structure import CAtomsOut, CChainBatch, CDenseIn, CDenseOut, CEntryInfo, 
 # the columns of the angle tensors (FCZ_ANGLE_COLUMNS, include/fcz_hip.h), degrees
 ANGLE_COLUMNS = ("phi", "psi", "omega", "n_ca_c", "ca_c_n", "c_n_ca", "chi1", "chi2", "chi3", "chi4")
 DENSE_LAYOUTS = {"atom37": 0, "atom14": 1, "backbone4": 2}     # enum fcz_dense_layout
+WIDTH_LAYOUTS = {37: 0, 14: 1, 4: 2}                           # slots per residue A -> enum fcz_dense_layout
 
 
 def dense_layout(layout) -> int:
@@ -30,6 +31,95 @@ def dense_layout(layout) -> int:
     if isinstance(layout, int) and layout in DENSE_LAYOUTS.values():
         return layout
     raise ValueError(f"unknown dense layout {layout!r}: one of {', '.join(DENSE_LAYOUTS)}")
+
+
+class _Arrays(NamedTuple):
+    """checked dense arrays on the host, what every analysis call reads: pos contiguous float32 [.., A, 3] with lead = its shape without
+    (A, 3), mask bool / uint8 or None, aatype uint8 or None, `lay` the enum fcz_dense_layout of A; n chains of `rows` rows each (padded:
+    bound = length as uint32 or None) or over `rows` rows in all (packed: bound = row_off as uint32)"""
+    pos: np.ndarray
+    mask: Optional[np.ndarray]
+    aatype: Optional[np.ndarray]
+    lay: int
+    lead: tuple
+    A: int
+    packed: bool
+    n: int
+    rows: int
+    bound: Optional[np.ndarray]
+
+    def as_dict(self, row_off):
+        """the arrays as the dict the device-free checks of foldcomp_amd.api read"""
+        d = dict(pos=self.pos, mask=self.mask, aatype=self.aatype)
+        if self.packed:
+            d["cu_seqlens"] = row_off
+        return d
+
+
+def _pos_error(name, packed, shape):
+    return ValueError(f"{name} must be float32 {'[R, A, 3]' if packed else '[n, L, A, 3]'} with A = 37, 14 or 4, not {shape}")
+
+
+def _mask_array(mask, shape, name="mask"):
+    mask = np.ascontiguousarray(mask)
+    if mask.shape != shape or mask.dtype not in (np.bool_, np.uint8):
+        raise ValueError(f"{name} must be bool / uint8 {shape}, not {mask.dtype} {mask.shape}")
+    return mask
+
+
+def _addr(a):
+    return None if a is None else a.ctypes.data
+
+
+def _dense_arrays(pos, mask, aatype, length, row_off, *, name="pos", mask_name="mask", mask_optional=False,
+                  limit=(2 ** 31 - 1, "at most 2^31 - 1 rows per chain")):
+    """the one prelude of the analyses on dense host arrays -> _Arrays: pos [n, L, A, 3] beside length [n] or None, or [R, A, 3] beside
+    row_off [n + 1] (which makes the form packed), A = 37, 14 or 4; mask of pos's shape without its last axis (None passes only with
+    mask_optional); aatype, when given, uint8 without the last two. limit = (rows, message): the most rows the caller's counters hold,
+    or None"""
+    pos = np.ascontiguousarray(pos, np.float32)
+    packed = row_off is not None
+    if pos.ndim != (3 if packed else 4) or pos.shape[-1] != 3 or pos.shape[-2] not in WIDTH_LAYOUTS:
+        raise _pos_error(name, packed, pos.shape)
+    lead, A = pos.shape[:-2], pos.shape[-2]
+    if mask is not None or not mask_optional:
+        mask = _mask_array(mask, pos.shape[:-1], mask_name)
+    if aatype is not None:
+        aatype = np.ascontiguousarray(aatype)
+        if aatype.shape != lead or aatype.dtype != np.uint8:
+            raise ValueError(f"aatype must be uint8 {lead}, not {aatype.dtype} {aatype.shape}")
+    if packed:
+        bound = np.ascontiguousarray(row_off, np.uint32)
+        if bound.ndim != 1 or len(bound) < 1:
+            raise ValueError("row_off must be [n + 1]")
+        n, rows = len(bound) - 1, pos.shape[0]
+    else:
+        n, rows, bound = pos.shape[0], pos.shape[1], None
+        if length is not None:
+            bound = np.ascontiguousarray(length, np.uint32)
+            if bound.shape != (n,):
+                raise ValueError(f"length must be [{n}], not {bound.shape}")
+    if limit is not None and rows > limit[0]:
+        raise ValueError(limit[1])
+    return _Arrays(pos, mask, aatype, WIDTH_LAYOUTS[A], lead, A, packed, n, rows, bound)
+
+
+def _pair_arrays(pos_true, mask_true, pos_pred, mask_pred, aatype, length, row_off, slot=None, **rules):
+    """the one prelude of the analyses of a prediction against its truth -> (_Arrays of true, pos_pred contiguous float32 of its shape,
+    mask_pred of its mask's shape or None, slot): mask_true is needed, slot (when the analysis has one) lies in 0 .. A - 1"""
+    a = _dense_arrays(pos_true, mask_true, aatype, length, row_off, name="pos_true", mask_name="mask_true", mask_optional=True, **rules)
+    pos_pred = np.ascontiguousarray(pos_pred, np.float32)
+    if pos_pred.shape != a.pos.shape:
+        raise ValueError(f"pos_pred must have the shape of pos_true, {a.pos.shape}, not {pos_pred.shape}")
+    if mask_pred is not None:
+        mask_pred = _mask_array(mask_pred, a.pos.shape[:-1], "mask_pred")
+    if a.mask is None:
+        raise ValueError("mask_true is needed")
+    if slot is not None:
+        slot = int(slot)
+        if not 0 <= slot < a.A:
+            raise ValueError(f"slot must be 0 .. {a.A - 1}")
+    return a, pos_pred, mask_pred, slot
 
 
 class Codec:
@@ -198,39 +288,21 @@ class Codec:
         """dense arrays on the host -> the k-nearest-neighbour graph of every chain on the sites at `slot` (fcz_knn, or
         fcz_knn_packed when row_off is given): index int32 [n, L, k] / [R, k] (-1 = none) and dist float32 of the same shape.
         pos float32 [n, L, A, 3] with mask [n, L, A] and optionally length [n]; or pos [R, A, 3], mask [R, A], row_off [n + 1]."""
-        pos = np.ascontiguousarray(pos, np.float32)
-        packed = row_off is not None
-        if pos.ndim != (3 if packed else 4) or pos.shape[-1] != 3 or pos.shape[-2] not in (37, 14, 4):
-            raise ValueError(f"pos must be float32 {'[R, A, 3]' if packed else '[n, L, A, 3]'} with A = 37, 14 or 4, not {pos.shape}")
-        A = pos.shape[-2]
-        lay = {37: 0, 14: 1, 4: 2}[A]
-        mask = np.ascontiguousarray(mask)
-        if mask.shape != pos.shape[:-1] or mask.dtype not in (np.bool_, np.uint8):
-            raise ValueError(f"mask must be bool / uint8 {pos.shape[:-1]}, not {mask.dtype} {mask.shape}")
+        a = _dense_arrays(pos, mask, None, length, row_off,
+                          limit=None if row_off is None else (2 ** 31 - 1, "the packed index holds global rows as int32: at most 2^31 - 1 rows"))
         k, slot = int(k), int(slot)
-        if not 1 <= k <= 64 or not 0 <= slot < A:
-            raise ValueError(f"k must be 1 .. 64 and slot 0 .. {A - 1}")
-        bound = None
-        if packed:
-            bound = np.ascontiguousarray(row_off, np.uint32)
-            n, rows = len(bound) - 1, pos.shape[0]
-            if bound.ndim != 1 or n < 0:
-                raise ValueError("row_off must be [n + 1]")
-            if rows > 2 ** 31 - 1:
-                raise ValueError("the packed index holds global rows as int32: at most 2^31 - 1 rows")
-        else:
-            n, rows = pos.shape[0], pos.shape[1]
-            if length is not None:
-                bound = np.ascontiguousarray(length, np.uint32)
-                if bound.shape != (n,):
-                    raise ValueError(f"length must be [{n}], not {bound.shape}")
-        index = np.full(pos.shape[:-2] + (k,), -1, np.int32)
-        dist = np.zeros(pos.shape[:-2] + (k,), np.float32)
+        if not 1 <= k <= 64 or not 0 <= slot < a.A:
+            raise ValueError(f"k must be 1 .. 64 and slot 0 .. {a.A - 1}")
+        index = np.full(a.lead + (k,), -1, np.int32)
+        dist = np.zeros(a.lead + (k,), np.float32)
         if index.size:
-            fn = self.lib.fcz_knn_packed if packed else self.lib.fcz_knn
-            _lib.check(fn(self.ctx, pos.ctypes.data, mask.ctypes.data, None if bound is None else bound.ctypes.data, n, rows, lay, slot, k,
-                          index.ctypes.data, dist.ctypes.data), "fcz_knn_packed" if packed else "fcz_knn")
+            self._call("fcz_knn", a.packed, a.pos.ctypes.data, a.mask.ctypes.data, _addr(a.bound), a.n, a.rows, a.lay, slot, k, index.ctypes.data, dist.ctypes.data)
         return dict(index=index, dist=dist)
+
+    def _call(self, name, packed, *args):
+        """the packed or the padded host entry point of one analysis, checked under its own name"""
+        name += "_packed" if packed else ""
+        _lib.check(getattr(self.lib, name)(self.ctx, *args), name)
 
     def lddt(self, pos_true: np.ndarray, mask_true: np.ndarray, pos_pred: np.ndarray, mask_pred=None, slot: int = 1, length=None, row_off=None,
              cutoff: float = 15.0, thresholds=None):
@@ -239,27 +311,8 @@ class Codec:
         score = hits / (4 * pairs), 0 where a row has no pair. pos float32 [n, L, A, 3] with mask [n, L, A] and optionally length [n];
         or pos [R, A, 3], mask [R, A], row_off [n + 1]. mask_pred=None: every slot of pred is present. These are counts: the result
         is reproducible bit for bit and not differentiable."""
-        pos_true = np.ascontiguousarray(pos_true, np.float32)
-        pos_pred = np.ascontiguousarray(pos_pred, np.float32)
-        packed = row_off is not None
-        if pos_true.ndim != (3 if packed else 4) or pos_true.shape[-1] != 3 or pos_true.shape[-2] not in (37, 14, 4):
-            raise ValueError(f"pos_true must be float32 {'[R, A, 3]' if packed else '[n, L, A, 3]'} with A = 37, 14 or 4, not {pos_true.shape}")
-        if pos_pred.shape != pos_true.shape:
-            raise ValueError(f"pos_pred must have the shape of pos_true, {pos_true.shape}, not {pos_pred.shape}")
-        A = pos_true.shape[-2]
-        lay = {37: 0, 14: 1, 4: 2}[A]
-        masks = []
-        for name, m in (("mask_true", mask_true), ("mask_pred", mask_pred)):
-            if m is not None:
-                m = np.ascontiguousarray(m)
-                if m.shape != pos_true.shape[:-1] or m.dtype not in (np.bool_, np.uint8):
-                    raise ValueError(f"{name} must be bool / uint8 {pos_true.shape[:-1]}, not {m.dtype} {m.shape}")
-            masks.append(m)
-        if masks[0] is None:
-            raise ValueError("mask_true is needed")
-        slot = int(slot)
-        if not 0 <= slot < A:
-            raise ValueError(f"slot must be 0 .. {A - 1}")
+        a, pos_pred, mask_pred, slot = _pair_arrays(pos_true, mask_true, pos_pred, mask_pred, None, length, row_off, slot,
+                                                    limit=(2 ** 29, "hits must fit int32: at most 2^29 rows per chain"))
         cutoff = np.float32(cutoff)
         if not np.isfinite(cutoff) or not cutoff > 0:
             raise ValueError("cutoff must be finite and > 0")
@@ -268,28 +321,12 @@ class Codec:
             th = np.ascontiguousarray(thresholds, np.float32)
             if th.shape != (4,) or np.isnan(th).any():
                 raise ValueError("thresholds must be four numbers, none of them NaN")
-        bound = None
-        if packed:
-            bound = np.ascontiguousarray(row_off, np.uint32)
-            n, rows = len(bound) - 1, pos_true.shape[0]
-            if bound.ndim != 1 or n < 0:
-                raise ValueError("row_off must be [n + 1]")
-        else:
-            n, rows = pos_true.shape[0], pos_true.shape[1]
-            if length is not None:
-                bound = np.ascontiguousarray(length, np.uint32)
-                if bound.shape != (n,):
-                    raise ValueError(f"length must be [{n}], not {bound.shape}")
-        if rows > 2 ** 29:
-            raise ValueError("hits must fit int32: at most 2^29 rows per chain")
-        score = np.zeros(pos_true.shape[:-2], np.float32)
-        pairs = np.zeros(pos_true.shape[:-2], np.int32)
-        hits = np.zeros(pos_true.shape[:-2], np.int32)
+        score = np.zeros(a.lead, np.float32)
+        pairs = np.zeros(a.lead, np.int32)
+        hits = np.zeros(a.lead, np.int32)
         if score.size:
-            fn = self.lib.fcz_lddt_packed if packed else self.lib.fcz_lddt
-            _lib.check(fn(self.ctx, pos_true.ctypes.data, masks[0].ctypes.data, pos_pred.ctypes.data, None if masks[1] is None else masks[1].ctypes.data,
-                          None if bound is None else bound.ctypes.data, n, rows, lay, slot, float(cutoff), None if th is None else th.ctypes.data,
-                          score.ctypes.data, pairs.ctypes.data, hits.ctypes.data), "fcz_lddt_packed" if packed else "fcz_lddt")
+            self._call("fcz_lddt", a.packed, a.pos.ctypes.data, a.mask.ctypes.data, pos_pred.ctypes.data, _addr(mask_pred), _addr(a.bound), a.n, a.rows, a.lay, slot,
+                       float(cutoff), _addr(th), score.ctypes.data, pairs.ctypes.data, hits.ctypes.data)
         return dict(score=score, pairs=pairs, hits=hits)
 
     def lddt_atoms(self, pos_true: np.ndarray, mask_true: np.ndarray, pos_pred: np.ndarray, mask_pred=None, aatype=None, length=None, row_off=None, *,
@@ -301,41 +338,19 @@ class Codec:
         are foldcomp.lddt_atoms'. These are counts: reproducible bit for bit and not differentiable."""
         from . import api
         from .structure import CLddtAtomsOut
-        pos_true = np.ascontiguousarray(pos_true, np.float32)
-        pos_pred = np.ascontiguousarray(pos_pred, np.float32)
-        packed = row_off is not None
-        if pos_true.ndim != (3 if packed else 4):
-            raise ValueError(f"pos_true must be float32 {'[R, A, 3]' if packed else '[n, L, A, 3]'} with A = 37, 14 or 4, not {pos_true.shape}")
-        masks = []
-        for name, m in (("mask_true", mask_true), ("mask_pred", mask_pred)):
-            if m is not None:
-                m = np.ascontiguousarray(m)
-                if m.shape != pos_true.shape[:-1] or m.dtype not in (np.bool_, np.uint8):
-                    raise ValueError(f"{name} must be bool / uint8 {pos_true.shape[:-1]}, not {m.dtype} {m.shape}")
-            masks.append(m)
-        if masks[0] is None:
-            raise ValueError("mask_true is needed")
+        pos_true, pos_pred = np.ascontiguousarray(pos_true, np.float32), np.ascontiguousarray(pos_pred, np.float32)
+        if pos_true.ndim != (3 if row_off is not None else 4):
+            raise _pos_error("pos_true", row_off is not None, pos_true.shape)
         cutoff, th, table = api.check_lddt_atoms(cutoff, thresholds, swaps, pos_true.shape, pos_pred.shape, None, aatype is not None, per_atom)
-        A, lead = pos_true.shape[-2], pos_true.shape[:-2]
-        lay = {37: 0, 14: 1, 4: 2}[A]
-        if table is False:
-            aatype = None
-        else:
-            aatype = np.ascontiguousarray(aatype)
-            if aatype.shape != lead or aatype.dtype != np.uint8:
-                raise ValueError(f"aatype must be uint8 {lead}, not {aatype.dtype} {aatype.shape}")
-        n, rows, bound = self._chain_rows(pos_true, packed, length, row_off)
-        out = dict(score=np.zeros(lead, np.float32), pairs=np.zeros(lead, np.int32), hits=np.zeros(lead, np.int32), swapped=np.zeros(lead, np.uint8))
+        a, pos_pred, mask_pred, _ = _pair_arrays(pos_true, mask_true, pos_pred, mask_pred, None if table is False else aatype, length, row_off)
+        out = dict(score=np.zeros(a.lead, np.float32), pairs=np.zeros(a.lead, np.int32), hits=np.zeros(a.lead, np.int32), swapped=np.zeros(a.lead, np.uint8))
         if per_atom:
-            out.update(atom_pairs=np.zeros(lead + (A,), np.int32), atom_hits=np.zeros(lead + (A,), np.int32))
+            out.update(atom_pairs=np.zeros(a.lead + (a.A,), np.int32), atom_hits=np.zeros(a.lead + (a.A,), np.int32))
         if out["score"].size:
             th = np.asarray(th, np.float32)
             c_out = CLddtAtomsOut(*(out[k].ctypes.data if k in out else None for k in ("score", "pairs", "hits", "swapped", "atom_pairs", "atom_hits")))
-            fn = self.lib.fcz_lddt_atoms_packed if packed else self.lib.fcz_lddt_atoms
-            _lib.check(fn(self.ctx, pos_true.ctypes.data, masks[0].ctypes.data, pos_pred.ctypes.data, None if masks[1] is None else masks[1].ctypes.data,
-                          None if aatype is None else aatype.ctypes.data, None if bound is None else bound.ctypes.data, n, rows, lay, cutoff,
-                          th.ctypes.data, table.ctypes.data if isinstance(table, np.ndarray) else None, ctypes.byref(c_out)),
-                       "fcz_lddt_atoms_packed" if packed else "fcz_lddt_atoms")
+            self._call("fcz_lddt_atoms", a.packed, a.pos.ctypes.data, a.mask.ctypes.data, pos_pred.ctypes.data, _addr(mask_pred), _addr(a.aatype), _addr(a.bound),
+                       a.n, a.rows, a.lay, cutoff, th.ctypes.data, table.ctypes.data if isinstance(table, np.ndarray) else None, ctypes.byref(c_out))
         out["swapped"] = out["swapped"].view(np.bool_)
         return out
 
@@ -345,29 +360,14 @@ class Codec:
         hbond_acc_index / hbond_don_index int32 [.., 2] (-1 = none) with hbond_acc_energy / hbond_don_energy float32. pos float32
         [n, L, A, 3] with mask [n, L, A], optionally aatype [n, L] uint8 (proline has no amide hydrogen) and length [n]; or pos
         [R, A, 3], mask [R, A], aatype [R], row_off [n + 1]. Reproducible bit for bit, not differentiable."""
-        pos = np.ascontiguousarray(pos, np.float32)
-        packed = row_off is not None
-        if pos.ndim != (3 if packed else 4) or pos.shape[-1] != 3 or pos.shape[-2] not in (37, 14, 4):
-            raise ValueError(f"pos must be float32 {'[R, A, 3]' if packed else '[n, L, A, 3]'} with A = 37, 14 or 4, not {pos.shape}")
-        lay = {37: 0, 14: 1, 4: 2}[pos.shape[-2]]
-        mask = np.ascontiguousarray(mask)
-        if mask.shape != pos.shape[:-1] or mask.dtype not in (np.bool_, np.uint8):
-            raise ValueError(f"mask must be bool / uint8 {pos.shape[:-1]}, not {mask.dtype} {mask.shape}")
-        lead = pos.shape[:-2]
-        if aatype is not None:
-            aatype = np.ascontiguousarray(aatype)
-            if aatype.shape != lead or aatype.dtype != np.uint8:
-                raise ValueError(f"aatype must be uint8 {lead}, not {aatype.dtype} {aatype.shape}")
-        n, rows, bound = self._chain_rows(pos, packed, length, row_off)
-        out = dict(ss=np.zeros(lead, np.uint8), ss_mask=np.zeros(lead, np.uint8),
-                   hbond_acc_index=np.full(lead + (2,), -1, np.int32), hbond_acc_energy=np.zeros(lead + (2,), np.float32),
-                   hbond_don_index=np.full(lead + (2,), -1, np.int32), hbond_don_energy=np.zeros(lead + (2,), np.float32))
+        a = _dense_arrays(pos, mask, aatype, length, row_off)
+        out = dict(ss=np.zeros(a.lead, np.uint8), ss_mask=np.zeros(a.lead, np.uint8),
+                   hbond_acc_index=np.full(a.lead + (2,), -1, np.int32), hbond_acc_energy=np.zeros(a.lead + (2,), np.float32),
+                   hbond_don_index=np.full(a.lead + (2,), -1, np.int32), hbond_don_energy=np.zeros(a.lead + (2,), np.float32))
         if out["ss"].size:
-            fn = self.lib.fcz_dssp_packed if packed else self.lib.fcz_dssp
-            _lib.check(fn(self.ctx, pos.ctypes.data, mask.ctypes.data, None if aatype is None else aatype.ctypes.data,
-                          None if bound is None else bound.ctypes.data, n, rows, lay, out["hbond_acc_index"].ctypes.data,
-                          out["hbond_acc_energy"].ctypes.data, out["hbond_don_index"].ctypes.data, out["hbond_don_energy"].ctypes.data,
-                          out["ss"].ctypes.data, out["ss_mask"].ctypes.data), "fcz_dssp_packed" if packed else "fcz_dssp")
+            self._call("fcz_dssp", a.packed, a.pos.ctypes.data, a.mask.ctypes.data, _addr(a.aatype), _addr(a.bound), a.n, a.rows, a.lay,
+                       out["hbond_acc_index"].ctypes.data, out["hbond_acc_energy"].ctypes.data, out["hbond_don_index"].ctypes.data,
+                       out["hbond_don_energy"].ctypes.data, out["ss"].ctypes.data, out["ss_mask"].ctypes.data)
         out["ss_mask"] = out["ss_mask"].view(np.bool_)
         return out
 
@@ -380,35 +380,16 @@ class Codec:
         optionally length [n]; or pos [R, A, 3], mask [R, A], aatype [R], row_off [n + 1]. probe, n_points, points and radii are
         foldcomp.solvent_accessibility's. Reproducible bit for bit, not differentiable."""
         from . import api
-        pos = np.ascontiguousarray(pos, np.float32)
-        packed = row_off is not None
-        if pos.ndim != (3 if packed else 4) or pos.shape[-1] != 3 or pos.shape[-2] not in (37, 14, 4):
-            raise ValueError(f"pos must be float32 {'[R, A, 3]' if packed else '[n, L, A, 3]'} with A = 37, 14 or 4, not {pos.shape}")
-        lay = {37: 0, 14: 1, 4: 2}[pos.shape[-2]]
-        mask = np.ascontiguousarray(mask)
-        if mask.shape != pos.shape[:-1] or mask.dtype not in (np.bool_, np.uint8):
-            raise ValueError(f"mask must be bool / uint8 {pos.shape[:-1]}, not {mask.dtype} {mask.shape}")
-        lead = pos.shape[:-2]
-        if aatype is not None:
-            aatype = np.ascontiguousarray(aatype)
-            if aatype.shape != lead or aatype.dtype != np.uint8:
-                raise ValueError(f"aatype must be uint8 {lead}, not {aatype.dtype} {aatype.shape}")
-        d = dict(pos=pos, mask=mask, aatype=aatype)
-        if packed:
-            d["cu_seqlens"] = row_off
-        _, _, pts, table = api.check_sasa("Codec.solvent_accessibility", d, probe, n_points, points, radii)
-        n, rows, bound = self._chain_rows(pos, packed, length, row_off)
-        out = dict(sasa=np.zeros(lead, np.float32), rsa=np.zeros(lead, np.float32), sasa_mask=np.zeros(lead, np.uint8),
-                   sasa_points=np.zeros(lead + (pos.shape[-2],), np.int16))
+        a = _dense_arrays(pos, mask, aatype, length, row_off)
+        _, _, pts, table = api.check_sasa("Codec.solvent_accessibility", a.as_dict(row_off), probe, n_points, points, radii)
+        out = dict(sasa=np.zeros(a.lead, np.float32), rsa=np.zeros(a.lead, np.float32), sasa_mask=np.zeros(a.lead, np.uint8),
+                   sasa_points=np.zeros(a.lead + (a.A,), np.int16))
         if out["sasa"].size:
-            fn = self.lib.fcz_sasa_packed if packed else self.lib.fcz_sasa
-            _lib.check(fn(self.ctx, pos.ctypes.data, mask.ctypes.data, None if aatype is None else aatype.ctypes.data,
-                          None if bound is None else bound.ctypes.data, n, rows, lay, None if table is None else table.ctypes.data, float(probe),
-                          pts.ctypes.data, len(pts), out["sasa_points"].ctypes.data, out["sasa"].ctypes.data, out["sasa_mask"].ctypes.data),
-                       "fcz_sasa_packed" if packed else "fcz_sasa")
+            self._call("fcz_sasa", a.packed, a.pos.ctypes.data, a.mask.ctypes.data, _addr(a.aatype), _addr(a.bound), a.n, a.rows, a.lay, _addr(table), float(probe),
+                       pts.ctypes.data, len(pts), out["sasa_points"].ctypes.data, out["sasa"].ctypes.data, out["sasa_mask"].ctypes.data)
         out["sasa_mask"] = out["sasa_mask"].view(np.bool_)
-        if aatype is not None:
-            mx = api.MAX_ASA[np.minimum(aatype, 20)]
+        if a.aatype is not None:
+            mx = api.MAX_ASA[np.minimum(a.aatype, 20)]
             ok = (mx > 0) & out["sasa_mask"]
             out["rsa"][ok] = out["sasa"][ok] / mx[ok]
         return out
@@ -423,56 +404,20 @@ class Codec:
         link_factor and radii are foldcomp.violations'. Reproducible bit for bit, not differentiable."""
         from . import api
         from .structure import CViolationsOut
-        pos = np.ascontiguousarray(pos, np.float32)
-        packed = row_off is not None
-        if pos.ndim != (3 if packed else 4) or pos.shape[-1] != 3 or pos.shape[-2] not in (37, 14, 4):
-            raise ValueError(f"pos must be float32 {'[R, A, 3]' if packed else '[n, L, A, 3]'} with A = 37, 14 or 4, not {pos.shape}")
-        lay = {37: 0, 14: 1, 4: 2}[pos.shape[-2]]
-        mask = np.ascontiguousarray(mask)
-        if mask.shape != pos.shape[:-1] or mask.dtype not in (np.bool_, np.uint8):
-            raise ValueError(f"mask must be bool / uint8 {pos.shape[:-1]}, not {mask.dtype} {mask.shape}")
-        lead = pos.shape[:-2]
-        if aatype is not None:
-            aatype = np.ascontiguousarray(aatype)
-            if aatype.shape != lead or aatype.dtype != np.uint8:
-                raise ValueError(f"aatype must be uint8 {lead}, not {aatype.dtype} {aatype.shape}")
-        d = dict(pos=pos, mask=mask, aatype=aatype)
-        if packed:
-            d["cu_seqlens"] = row_off
-        _, _, table = api.check_violations("Codec.violations", d, tolerance, link_factor, radii)
-        n, rows, bound = self._chain_rows(pos, packed, length, row_off)
+        a = _dense_arrays(pos, mask, aatype, length, row_off)
+        _, _, table = api.check_violations("Codec.violations", a.as_dict(row_off), tolerance, link_factor, radii)
         out = {}
         for key, dt, tail in api.VIOLATION_OUTPUTS:
-            shape = (n, 4) if tail == "n4" else lead + ((pos.shape[-2],) if tail == "A" else tail)
+            shape = (a.n, 4) if tail == "n4" else a.lead + ((a.A,) if tail == "A" else tail)
             out[key] = np.full(shape, -1, np.int32) if key == "clash_partner" else np.zeros(shape, np.uint8 if dt == "bool" else dt)
         if out["clash_count"].size:
-            fn = self.lib.fcz_violations_packed if packed else self.lib.fcz_violations
             c_out = CViolationsOut(*(out[key].ctypes.data for key, _, _ in api.VIOLATION_OUTPUTS))
-            _lib.check(fn(self.ctx, pos.ctypes.data, mask.ctypes.data, None if aatype is None else aatype.ctypes.data,
-                          None if bound is None else bound.ctypes.data, n, rows, lay, None if table is None else table.ctypes.data, float(tolerance),
-                          float(link_factor), ctypes.byref(c_out)), "fcz_violations_packed" if packed else "fcz_violations")
+            self._call("fcz_violations", a.packed, a.pos.ctypes.data, a.mask.ctypes.data, _addr(a.aatype), _addr(a.bound), a.n, a.rows, a.lay, _addr(table),
+                       float(tolerance), float(link_factor), ctypes.byref(c_out))
         for key, dt, _ in api.VIOLATION_OUTPUTS:
             if dt == "bool":
                 out[key] = out[key].view(np.bool_)
         return out
-
-    @staticmethod
-    def _chain_rows(pos, packed, length, row_off):
-        """the chains of dense host arrays -> (n, rows, bound): row_off [n + 1] over the R rows, or length [n] / None over L"""
-        if packed:
-            bound = np.ascontiguousarray(row_off, np.uint32)
-            if bound.ndim != 1 or len(bound) < 1:
-                raise ValueError("row_off must be [n + 1]")
-            n, rows = len(bound) - 1, pos.shape[0]
-        else:
-            n, rows, bound = pos.shape[0], pos.shape[1], None
-            if length is not None:
-                bound = np.ascontiguousarray(length, np.uint32)
-                if bound.shape != (n,):
-                    raise ValueError(f"length must be [{n}], not {bound.shape}")
-        if rows > 2 ** 31 - 1:
-            raise ValueError("at most 2^31 - 1 rows per chain")
-        return n, rows, bound
 
     def superpose(self, pos_true: np.ndarray, mask_true: np.ndarray, pos_pred: np.ndarray, mask_pred=None, slot: int = 1, length=None, row_off=None):
         """two sets of dense arrays of one shape on the host -> the least-squares superposition of every chain of `pred` onto `true`
@@ -480,13 +425,12 @@ class Codec:
         (x_true ~ rot @ x_pred + trans), rmsd [n], sites int32 [n], gdt_counts int32 [n, 5] (dev <= 0.5, 1, 2, 4, 8), tm [n] (the
         TM-score at this superposition, a lower bound of the maximised one) and dev float32 [n, L] / [R], every site's deviation.
         The arrays are those of Codec.lddt. The sums are float64 in a fixed order: reproducible bit for bit, not differentiable."""
-        pos_true, masks, pos_pred, lay, slot, packed, n, rows, bound = self._superpose_inputs(pos_true, mask_true, pos_pred, mask_pred, slot, length, row_off)
-        d = self._superpose_outputs(n, pos_true.shape[:-2])
-        if n and rows:
+        a, pos_pred, mask_pred, slot = _pair_arrays(pos_true, mask_true, pos_pred, mask_pred, None, length, row_off, slot)
+        d = self._superpose_outputs(a.n, a.lead)
+        if a.n and a.rows:
             out = CSuperposeOut(*(d[k].ctypes.data for k in ("rot", "trans", "rmsd", "sites", "gdt_counts", "tm", "dev")))
-            fn = self.lib.fcz_superpose_packed if packed else self.lib.fcz_superpose
-            _lib.check(fn(self.ctx, pos_true.ctypes.data, masks[0].ctypes.data, pos_pred.ctypes.data, None if masks[1] is None else masks[1].ctypes.data,
-                          None if bound is None else bound.ctypes.data, n, rows, lay, slot, ctypes.byref(out)), "fcz_superpose_packed" if packed else "fcz_superpose")
+            self._call("fcz_superpose", a.packed, a.pos.ctypes.data, a.mask.ctypes.data, pos_pred.ctypes.data, _addr(mask_pred), _addr(a.bound), a.n, a.rows, a.lay,
+                       slot, ctypes.byref(out))
         return d
 
     def tm_score(self, pos_true: np.ndarray, mask_true: np.ndarray, pos_pred: np.ndarray, mask_pred=None, slot: int = 1, length=None, row_off=None,
@@ -496,17 +440,15 @@ class Codec:
         Codec.superpose's outputs at it: rot, trans, rmsd, sites, gdt_counts, tm, dev; beside them seed int32 [n], the winning
         seed's number, and selected int32 [n], the size of the winning selection. tm >= Codec.superpose's tm. iterations: rounds of
         refinement per seed, 0 .. 64; levels: only the first so many fragment lengths (None: all). Reproducible bit for bit."""
-        pos_true, masks, pos_pred, lay, slot, packed, n, rows, bound = self._superpose_inputs(pos_true, mask_true, pos_pred, mask_pred, slot, length, row_off)
+        a, pos_pred, mask_pred, slot = _pair_arrays(pos_true, mask_true, pos_pred, mask_pred, None, length, row_off, slot)
         from .api import check_tm_search
         iterations, levels = check_tm_search(iterations, levels)
-        d = self._superpose_outputs(n, pos_true.shape[:-2])
-        d.update(seed=np.zeros(n, np.int32), selected=np.zeros(n, np.int32))
-        if n and rows:
+        d = self._superpose_outputs(a.n, a.lead)
+        d.update(seed=np.zeros(a.n, np.int32), selected=np.zeros(a.n, np.int32))
+        if a.n and a.rows:
             out = CTmScoreOut(*(d[k].ctypes.data for k in ("rot", "trans", "rmsd", "sites", "gdt_counts", "tm", "dev", "seed", "selected")))
-            fn = self.lib.fcz_tmscore_packed if packed else self.lib.fcz_tmscore
-            _lib.check(fn(self.ctx, pos_true.ctypes.data, masks[0].ctypes.data, pos_pred.ctypes.data, None if masks[1] is None else masks[1].ctypes.data,
-                          None if bound is None else bound.ctypes.data, n, rows, lay, slot, levels, iterations, ctypes.byref(out)),
-                       "fcz_tmscore_packed" if packed else "fcz_tmscore")
+            self._call("fcz_tmscore", a.packed, a.pos.ctypes.data, a.mask.ctypes.data, pos_pred.ctypes.data, _addr(mask_pred), _addr(a.bound), a.n, a.rows, a.lay,
+                       slot, levels, iterations, ctypes.byref(out))
         return d
 
     @staticmethod
@@ -514,54 +456,19 @@ class Codec:
         return dict(rot=np.tile(np.eye(3, dtype=np.float32), (n, 1, 1)), trans=np.zeros((n, 3), np.float32), rmsd=np.zeros(n, np.float32),
                     sites=np.zeros(n, np.int32), gdt_counts=np.zeros((n, 5), np.int32), tm=np.zeros(n, np.float32), dev=np.zeros(rows_shape, np.float32))
 
-    def _superpose_inputs(self, pos_true, mask_true, pos_pred, mask_pred, slot, length, row_off):
-        """the checked arrays of superpose / tm_score -> (pos_true, [mask_true, mask_pred], pos_pred, layout, slot, packed, n, rows, bound)"""
-        pos_true = np.ascontiguousarray(pos_true, np.float32)
-        pos_pred = np.ascontiguousarray(pos_pred, np.float32)
-        packed = row_off is not None
-        if pos_true.ndim != (3 if packed else 4) or pos_true.shape[-1] != 3 or pos_true.shape[-2] not in (37, 14, 4):
-            raise ValueError(f"pos_true must be float32 {'[R, A, 3]' if packed else '[n, L, A, 3]'} with A = 37, 14 or 4, not {pos_true.shape}")
-        if pos_pred.shape != pos_true.shape:
-            raise ValueError(f"pos_pred must have the shape of pos_true, {pos_true.shape}, not {pos_pred.shape}")
-        A = pos_true.shape[-2]
-        lay = {37: 0, 14: 1, 4: 2}[A]
-        masks = []
-        for name, m in (("mask_true", mask_true), ("mask_pred", mask_pred)):
-            if m is not None:
-                m = np.ascontiguousarray(m)
-                if m.shape != pos_true.shape[:-1] or m.dtype not in (np.bool_, np.uint8):
-                    raise ValueError(f"{name} must be bool / uint8 {pos_true.shape[:-1]}, not {m.dtype} {m.shape}")
-            masks.append(m)
-        if masks[0] is None:
-            raise ValueError("mask_true is needed")
-        slot = int(slot)
-        if not 0 <= slot < A:
-            raise ValueError(f"slot must be 0 .. {A - 1}")
-        n, rows, bound = self._chain_rows(pos_true, packed, length, row_off)
-        return pos_true, masks, pos_pred, lay, slot, packed, n, rows, bound
-
     def apply_transform(self, pos: np.ndarray, rot: np.ndarray, trans: np.ndarray, mask=None, length=None, row_off=None):
         """dense coordinates on the host moved by one rigid transform per chain (fcz_superpose_apply, or fcz_superpose_apply_packed
         when row_off is given) -> pos_out float32 of the shape of pos: rot[e] @ x + trans[e] for every slot whose mask is set (None:
         every slot) in the rows of chain e, 0 elsewhere; float32 in the order x' = ((r00 x + r01 y) + r02 z) + tx."""
-        pos = np.ascontiguousarray(pos, np.float32)
-        packed = row_off is not None
-        if pos.ndim != (3 if packed else 4) or pos.shape[-1] != 3 or pos.shape[-2] not in (37, 14, 4):
-            raise ValueError(f"pos must be float32 {'[R, A, 3]' if packed else '[n, L, A, 3]'} with A = 37, 14 or 4, not {pos.shape}")
-        lay = {37: 0, 14: 1, 4: 2}[pos.shape[-2]]
-        if mask is not None:
-            mask = np.ascontiguousarray(mask)
-            if mask.shape != pos.shape[:-1] or mask.dtype not in (np.bool_, np.uint8):
-                raise ValueError(f"mask must be bool / uint8 {pos.shape[:-1]}, not {mask.dtype} {mask.shape}")
-        n, rows, bound = self._chain_rows(pos, packed, length, row_off)
+        a = _dense_arrays(pos, mask, None, length, row_off, mask_optional=True)
+        n = a.n
         rot, trans = np.ascontiguousarray(rot, np.float32), np.ascontiguousarray(trans, np.float32)
         if rot.shape != (n, 3, 3) or trans.shape != (n, 3):
             raise ValueError(f"rot must be [{n}, 3, 3] and trans [{n}, 3], one transform per chain, not {rot.shape} and {trans.shape}")
-        out = np.zeros(pos.shape, np.float32)
+        out = np.zeros(a.pos.shape, np.float32)
         if n and out.size:
-            fn = self.lib.fcz_superpose_apply_packed if packed else self.lib.fcz_superpose_apply
-            _lib.check(fn(self.ctx, pos.ctypes.data, None if mask is None else mask.ctypes.data, None if bound is None else bound.ctypes.data, n, rows, lay,
-                          rot.ctypes.data, trans.ctypes.data, out.ctypes.data), "fcz_superpose_apply_packed" if packed else "fcz_superpose_apply")
+            self._call("fcz_superpose_apply", a.packed, a.pos.ctypes.data, _addr(a.mask), _addr(a.bound), n, a.rows, a.lay, rot.ctypes.data, trans.ctypes.data,
+                       out.ctypes.data)
         return out
 
     def frames(self, pos: np.ndarray, mask: np.ndarray, aatype=None, length=None, layout=None, groups="backbone"):
@@ -570,18 +477,16 @@ class Codec:
         [n, L, A, 3] with mask [n, L, A], aatype [n, L] and optionally length [n]; or the packed pos [R, A, 3], mask [R, A], aatype [R].
         layout: inferred from A when None."""
         pos = np.ascontiguousarray(pos, np.float32)
-        if pos.ndim not in (3, 4) or pos.shape[-1] != 3 or pos.shape[-2] not in (37, 14, 4):
+        if pos.ndim not in (3, 4) or pos.shape[-1] != 3 or pos.shape[-2] not in WIDTH_LAYOUTS:
             raise ValueError(f"pos must be float32 [n, L, A, 3] or [R, A, 3] with A = 37, 14 or 4, not {pos.shape}")
         A = pos.shape[-2]
-        lay = {37: 0, 14: 1, 4: 2}[A]
+        lay = WIDTH_LAYOUTS[A]
         if layout is not None and dense_layout(layout) != lay:
             raise ValueError(f"layout {layout!r} does not have {A} slots per residue")
         if groups not in ("backbone", "all"):
             raise ValueError(f"groups must be 'backbone' or 'all', not {groups!r}")
         fgroups = 1 if groups == "all" else 0
-        mask = np.ascontiguousarray(mask)
-        if mask.shape != pos.shape[:-1] or mask.dtype not in (np.bool_, np.uint8):
-            raise ValueError(f"mask must be bool / uint8 {pos.shape[:-1]}, not {mask.dtype} {mask.shape}")
+        mask = _mask_array(mask, pos.shape[:-1])
         rows = pos.shape[:-2]
         if aatype is None:
             if fgroups:
@@ -604,9 +509,8 @@ class Codec:
         trans = np.zeros(rows + g + (3,), np.float32)
         fm = np.zeros(rows + g, np.uint8)
         if fm.size:
-            _lib.check(self.lib.fcz_frames(self.ctx, pos.ctypes.data, mask.ctypes.data, None if aatype is None else aatype.ctypes.data,
-                                           None if bound is None else bound.ctypes.data, n, L, lay, fgroups, rot.ctypes.data, trans.ctypes.data,
-                                           fm.ctypes.data), "fcz_frames")
+            self._call("fcz_frames", False, pos.ctypes.data, mask.ctypes.data, _addr(aatype), _addr(bound), n, L, lay, fgroups, rot.ctypes.data, trans.ctypes.data,
+                       fm.ctypes.data)
         return dict(rot=rot, trans=trans, frame_mask=fm.view(np.bool_))
 
     def decompress_angles(self, blob: np.ndarray, off: np.ndarray, L: int = 0, packed: bool = False, start=None):

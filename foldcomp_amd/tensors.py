@@ -47,13 +47,13 @@ torch is imported inside the functions only: `import foldcomp` does not touch it
 from __future__ import annotations
 
 import ctypes
-from typing import Optional, Sequence
+from typing import Callable, NamedTuple, Optional, Sequence
 
 import numpy as np
 
 from . import _lib, api, fczfile
 from ._aa_tables import RES1
-from .codec import ANGLE_COLUMNS, Codec, dense_layout
+from .codec import ANGLE_COLUMNS, WIDTH_LAYOUTS, Codec, dense_layout
 from .structure import CAtomsOut, CDenseIn, CDenseOut, CLddtAtomsOut, CPackedOut, CSuperposeOut, CTmScoreOut, CViolationsOut
 
 __all__ = ["decode_tensors", "encode_tensors", "decode_angles", "crop_starts", "neighbor_graph", "rigid_frames", "lddt", "lddt_atoms", "superpose", "tm_score", "apply_transform",
@@ -157,8 +157,7 @@ def _angles_into(c, torch, dev, n, blob_t, off_t, res_off_t, L, R=None, start_t=
         if ang.numel():
             torch.cuda.current_stream(dev).synchronize()
             _lib.check(c.lib.fcz_angles_window_dev(c.ctx, blob_t.data_ptr(), off_t.data_ptr(), n, res_off_t.data_ptr(), L,
-                                                   None if start_t is None else start_t.data_ptr(), ang.data_ptr(), msk.data_ptr(),
-                                                   None if aa is None else aa.data_ptr()), "fcz_angles_window_dev")
+                                                   _ptr(start_t), ang.data_ptr(), msk.data_ptr(), _ptr(aa)), "fcz_angles_window_dev")
         d = dict(angles=ang, angle_mask=msk.view(torch.bool))
         return dict(d, aatype=aa) if aatype else d
     if ang.numel():
@@ -320,11 +319,8 @@ def decode_tensors(entries: Sequence[bytes], *, layout="atom37", max_len: Option
         nbr = (int(neighbors), api.check_neighbors(neighbors, neighbor_atom, _LAYOUT_WIDTH[dense_layout(layout)]))
     fgroups = None if frames is None else api.check_frames(frames)
     api.check_secondary_structure_flag(secondary_structure)
-    want_ss = bool(secondary_structure)
     api.check_sasa_flag(sasa)
-    want_sasa = bool(sasa)
     api.check_violations_flag(violations)
-    want_viol = bool(violations)
     torch, dev = _torch_device(device)
     c = codec or api.default_codec()
     if int(c.device) != dev.index:
@@ -338,6 +334,7 @@ def decode_tensors(entries: Sequence[bytes], *, layout="atom37", max_len: Option
     entries = [bytes(e) for e in entries]
     n = len(entries)
     names = [_title(e) for e in entries]
+    riders = _riders(torch, dev, A, n, nbr, fgroups, bool(secondary_structure), bool(sasa), bool(violations))
 
     def packed_result(R, cu_seqlens, max_seqlen):
         out = (torch.empty((R, A, 3), dtype=torch.float32, device=dev), torch.empty((R, A), dtype=torch.uint8, device=dev),
@@ -360,33 +357,12 @@ def decode_tensors(entries: Sequence[bytes], *, layout="atom37", max_len: Option
         W = len(ANGLE_COLUMNS)
         return dict(angles=torch.empty(rows + (W,), dtype=torch.float32, device=dev), angle_mask=torch.empty(rows + (W,), dtype=torch.bool, device=dev))
 
-    def nbr_alloc(*rows):   # neighbors=None: no key
-        if nbr is None:
-            return {}
-        return dict(nbr_index=torch.empty(rows + (nbr[0],), dtype=torch.int32, device=dev), nbr_dist=torch.empty(rows + (nbr[0],), dtype=torch.float32, device=dev))
-
-    def frames_alloc(*rows):   # frames=None: no key
-        return {} if fgroups is None else _frames_alloc(torch, dev, rows, fgroups)
-
-    def ss_alloc(*rows):   # secondary_structure=False: no key
-        return _ss_alloc(torch, dev, rows) if want_ss else {}
-
-    def sasa_alloc(*rows):   # sasa=False: no key
-        return _sasa_alloc(torch, dev, rows) if want_sasa else {}
-
-    def viol_alloc(*rows):   # violations=False: no tensor
-        return _viol_alloc(torch, dev, rows, A, n) if want_viol else None
-
-    def viol_keys(v):
-        return {} if v is None else {k: v[k] for k in api.VIOLATION_BATCH_KEYS}
-
     if n == 0:
         if packed:
-            d = dict(packed_result(0, torch.zeros(1, dtype=torch.int32, device=dev), 0)[1], **nbr_alloc(0), **frames_alloc(0), **ss_alloc(0), **sasa_alloc(0),
-                     **viol_keys(viol_alloc(0)))
+            d = dict(packed_result(0, torch.zeros(1, dtype=torch.int32, device=dev), 0)[1], **_ride(riders, (0,))[1])
             return dict(d, **no_angles(0)) if angles else d
         L = int(max_len or 0)
-        d = dict(result(L, *alloc(L)), **nbr_alloc(0, L), **frames_alloc(0, L), **ss_alloc(0, L), **sasa_alloc(0, L), **viol_keys(viol_alloc(0, L)))
+        d = dict(result(L, *alloc(L)), **_ride(riders, (0, L))[1])
         if crop is not None:
             d["crop_start"] = crop_starts(d["length"], L, crop, generator)
         return dict(d, **no_angles(0, L)) if angles else d
@@ -395,8 +371,7 @@ def decode_tensors(entries: Sequence[bytes], *, layout="atom37", max_len: Option
     if packed:
         # (the angle call is enqueued in front of the decode and leaves it the sizes memo; _decode_packed synchronises the codec)
         extra = _angles_into(c, torch, dev, n, blob_t, off_t, res_off_t, 0, Rv) if angles else {}
-        d = _decode_packed(c, torch, dev, lay, n, Rv, Mv, blob_t, off_t, res_off_t, atom_off_t, packed_result, nbr, nbr_alloc, fgroups, frames_alloc,
-                           ss_alloc, sasa_alloc, viol_alloc if want_viol else None)
+        d = _decode_packed(c, torch, dev, lay, n, Rv, Mv, blob_t, off_t, res_off_t, atom_off_t, packed_result, riders)
         return dict(d, **extra)
     if max_len is None:
         ro = res_off_t.cpu().numpy().view(np.uint32).astype(np.int64)      # n + 1 offsets: the only words that come back
@@ -405,20 +380,14 @@ def decode_tensors(entries: Sequence[bytes], *, layout="atom37", max_len: Option
         L = int(max_len)
     out = alloc(L)
     if L == 0:                                                             # nothing decodes and no width was asked for
-        d = dict(result(L, *out), **nbr_alloc(n, 0), **frames_alloc(n, 0), **ss_alloc(n, 0), **sasa_alloc(n, 0), **viol_keys(viol_alloc(n, 0)))
+        d = dict(result(L, *out), **_ride(riders, (n, 0))[1])
         return dict(d, **no_angles(n, 0)) if angles else d
     start_t = None if crop is None else crop_starts(_entry_lengths(res_off_t), L, crop, generator)
     extra = _angles_into(c, torch, dev, n, blob_t, off_t, res_off_t, L, start_t=start_t) if angles else {}
     if crop is not None:
         extra["crop_start"] = start_t
-    extra.update(nbr_alloc(n, L))
-    extra.update(frames_alloc(n, L))
-    extra.update(ss_alloc(n, L))
-    tables = _hbond_alloc(torch, dev, (n, L)) if want_ss else None
-    extra.update(sasa_alloc(n, L))
-    sasa_work = _sasa_work(torch, dev, (n, L, A)) if want_sasa else None
-    viol = viol_alloc(n, L)
-    extra.update(viol_keys(viol))
+    made, keys = _ride(riders, (n, L))
+    extra.update(keys)
     x, y, z = (torch.empty(max(M.value, 1), dtype=torch.float32, device=dev) for _ in range(3))
     bfac = torch.empty(max(R.value, 1), dtype=torch.float32, device=dev)
     res_code = torch.empty(max(R.value, 1), dtype=torch.uint8, device=dev)
@@ -434,47 +403,63 @@ def decode_tensors(entries: Sequence[bytes], *, layout="atom37", max_len: Option
     else:
         _lib.check(c.lib.fcz_dense_window_dev(c.ctx, blob_t.data_ptr(), off_t.data_ptr(), n, res_off_t.data_ptr(), atom_off_t.data_ptr(),
                                               ctypes.byref(atoms), 0, lay, L, start_t.data_ptr(), ctypes.byref(dense)), "fcz_dense_window_dev")
-    if nbr is not None:   # (a window's padding rows have a cleared mask: no length; otherwise the length the dense call just wrote)
-        _lib.check(c.lib.fcz_knn_dev(c.ctx, out[0].data_ptr(), out[1].data_ptr(), out[5].data_ptr() if crop is None else None, n, L, lay, nbr[1], nbr[0],
-                                     extra["nbr_index"].data_ptr(), extra["nbr_dist"].data_ptr()), "fcz_knn_dev")
-    if fgroups is not None:   # (as above: a window needs no length)
-        _lib.check(c.lib.fcz_frames_dev(c.ctx, out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(), out[5].data_ptr() if crop is None else None, n, L,
-                                        lay, fgroups, extra["rot"].data_ptr(), extra["trans"].data_ptr(), extra["frame_mask"].data_ptr()), "fcz_frames_dev")
-    if want_ss:   # (as above: a window needs no length)
-        _dssp_into(c, out[0], out[1], out[2], out[5] if crop is None else None, n, L, lay, False, tables, extra)
-    if want_sasa:   # (as above: a window needs no length)
-        _sasa_into(c, out[0], out[1], out[2], out[5] if crop is None else None, n, L, lay, False, None, api.SASA_PROBE, *sasa_work, extra)
-    if want_viol:   # (as above: a window needs no length)
-        _viol_into(c, out[0], out[1], out[2], out[5] if crop is None else None, n, L, lay, False, None, api.VIOLATION_TOLERANCE, api.VIOLATION_LINK_FACTOR, viol)
+    # (a window's padding rows have a cleared mask: no length; otherwise the length the dense call just wrote)
+    written = _dense_written(c, torch, dev, out[0], out[1], out[2], lay, n, L, out[5] if crop is None else None, False)
+    for rider, t in made:
+        rider.enqueue(written, t)
     c.synchronize()
-    if want_sasa:
+    if "sasa" in extra:
         extra["rsa"] = _rsa(torch, extra["sasa"], extra["sasa_mask"], out[2])
     return dict(result(L, *out), **extra)
 
 
-def _decode_packed(c, torch, dev, lay, n, R, M, blob_t, off_t, res_off_t, atom_off_t, packed_result, nbr=None, nbr_alloc=None, fgroups=None,
-                   frames_alloc=None, ss_alloc=None, sasa_alloc=None, viol_alloc=None):
-    """the packed leg of decode_tensors behind fcz_decompress_sizes_dev: R and M are its totals, res_off_t becomes cu_seqlens;
-    nbr = (k, slot): the neighbour graph of the rows behind the dense call (nbr_alloc makes its tensors); fgroups: their rigid
-    frames (frames_alloc makes the tensors); ss_alloc: the DSSP labels of the rows, or no key; sasa_alloc: their solvent accessibility, or no key;
-    viol_alloc: their structural violations, or no key"""
+class _Rider(NamedTuple):
+    """one optional analysis of decode_tensors: alloc(lead) makes its tensors for the leading shape `lead`, `keys` are those of them the
+    batch gains, enqueue(written, tensors) puts its calls on the codec's stream behind the dense call"""
+    alloc: Callable
+    keys: tuple
+    enqueue: Callable
+
+
+def _riders(torch, dev, A, n, nbr, fgroups, want_ss, want_sasa, want_viol):
+    """the analyses decode_tensors was asked to add, in the order of their keys: neighbours (nbr = (k, slot)), frames, DSSP labels, solvent
+    accessibility and violations, the last three with the defaults of their functions"""
+    riders = []
+    if nbr is not None:
+        k, slot = nbr
+        riders.append(_Rider(lambda lead: dict(nbr_index=torch.empty(lead + (k,), dtype=torch.int32, device=dev),
+                                               nbr_dist=torch.empty(lead + (k,), dtype=torch.float32, device=dev)),
+                             ("nbr_index", "nbr_dist"), lambda w, t: _knn_into(w, slot, k, t["nbr_index"], t["nbr_dist"])))
+    if fgroups is not None:
+        riders.append(_Rider(lambda lead: _frames_alloc(torch, dev, lead, fgroups), ("rot", "trans", "frame_mask"), lambda w, t: _frames_into(w, fgroups, t)))
+    if want_ss:
+        riders.append(_Rider(lambda lead: dict(_ss_alloc(torch, dev, lead), **_hbond_alloc(torch, dev, lead)), ("ss", "ss_mask"), lambda w, t: _dssp_into(w, t, t)))
+    if want_sasa:
+        def sasa_alloc(lead):
+            points, counts = _sasa_work(torch, dev, lead + (A,))
+            return dict(_sasa_alloc(torch, dev, lead), points=points, counts=counts)
+        riders.append(_Rider(sasa_alloc, ("sasa", "rsa", "sasa_mask"), lambda w, t: _sasa_into(w, None, api.SASA_PROBE, t["points"], t["counts"], t)))
+    if want_viol:
+        riders.append(_Rider(lambda lead: _viol_alloc(torch, dev, lead, A, n), api.VIOLATION_BATCH_KEYS,
+                             lambda w, t: _viol_into(w, None, api.VIOLATION_TOLERANCE, api.VIOLATION_LINK_FACTOR, t)))
+    return riders
+
+
+def _ride(riders, lead):
+    """every rider's tensors for the leading shape `lead` -> ([(rider, its tensors)], the keys the batch gains)"""
+    made = [(r, r.alloc(lead)) for r in riders]
+    return made, {k: t[k] for r, t in made for k in r.keys}
+
+
+def _decode_packed(c, torch, dev, lay, n, R, M, blob_t, off_t, res_off_t, atom_off_t, packed_result, riders):
+    """the packed leg of decode_tensors behind fcz_decompress_sizes_dev: R and M are its totals, res_off_t becomes cu_seqlens; the
+    riders' analyses follow the dense call on the rows just written"""
     if R > 2 ** 31 - 1:
         raise api.error(f"decode_tensors: {R} residues do not fit the int32 cu_seqlens; split the batch")
     ro = res_off_t.cpu().numpy().view(np.uint32).astype(np.int64)          # n + 1 offsets: the only words that come back
     out, d = packed_result(R, res_off_t, int(np.diff(ro).max()))
-    if nbr is not None:
-        d.update(nbr_alloc(R))
-    if fgroups is not None:
-        d.update(frames_alloc(R))
-    ss = ss_alloc(R) if ss_alloc is not None else {}
-    d.update(ss)
-    tables = _hbond_alloc(torch, dev, (R,)) if ss and R else None
-    sa = sasa_alloc(R) if sasa_alloc is not None else {}
-    d.update(sa)
-    sasa_work = _sasa_work(torch, dev, (R, out[1].shape[-1])) if sa and R else None
-    viol = viol_alloc(R) if viol_alloc is not None else None
-    if viol is not None:
-        d.update({k: viol[k] for k in api.VIOLATION_BATCH_KEYS})
+    made, keys = _ride(riders, (R,))
+    d.update(keys)
     if R == 0:                                                             # nothing decodes: no row, length stays 0
         return d
     x, y, z = (torch.empty(max(M, 1), dtype=torch.float32, device=dev) for _ in range(3))
@@ -487,20 +472,11 @@ def _decode_packed(c, torch, dev, lay, n, R, M, blob_t, off_t, res_off_t, atom_o
                                               0, ctypes.byref(atoms)), "fcz_decompress_batch_dev")
     _lib.check(c.lib.fcz_dense_packed_dev(c.ctx, blob_t.data_ptr(), off_t.data_ptr(), n, res_off_t.data_ptr(), atom_off_t.data_ptr(),
                                           ctypes.byref(atoms), 0, lay, ctypes.byref(dense)), "fcz_dense_packed_dev")
-    if nbr is not None:
-        _lib.check(c.lib.fcz_knn_packed_dev(c.ctx, out[0].data_ptr(), out[1].data_ptr(), res_off_t.data_ptr(), n, R, lay, nbr[1], nbr[0],
-                                            d["nbr_index"].data_ptr(), d["nbr_dist"].data_ptr()), "fcz_knn_packed_dev")
-    if fgroups is not None:   # (the packed form: one entry of R rows, no length)
-        _lib.check(c.lib.fcz_frames_dev(c.ctx, out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(), None, 1, R, lay, fgroups,
-                                        d["rot"].data_ptr(), d["trans"].data_ptr(), d["frame_mask"].data_ptr()), "fcz_frames_dev")
-    if ss:
-        _dssp_into(c, out[0], out[1], out[2], res_off_t, n, R, lay, True, tables, ss)
-    if sa:
-        _sasa_into(c, out[0], out[1], out[2], res_off_t, n, R, lay, True, None, api.SASA_PROBE, *sasa_work, d)
-    if viol is not None:
-        _viol_into(c, out[0], out[1], out[2], res_off_t, n, R, lay, True, None, api.VIOLATION_TOLERANCE, api.VIOLATION_LINK_FACTOR, viol)
+    written = _dense_written(c, torch, dev, out[0], out[1], out[2], lay, n, R, res_off_t, True)
+    for rider, t in made:
+        rider.enqueue(written, t)
     c.synchronize()
-    if sa:
+    if "sasa" in d:
         d["rsa"] = _rsa(torch, d["sasa"], d["sasa_mask"], out[2])
     return d
 
@@ -524,50 +500,22 @@ def neighbor_graph(batch=None, *, k: int = 48, atom="CA", codec: Optional[Codec]
     Padded: `length` is used when the dict has no crop_start (a window's padding rows carry a cleared mask and `length` is the
     uncropped size). Packed: cu_seqlens must be non-decreasing and end at R (checked on the device). The tensors must be contiguous
     and lie on the codec's device; ordering against torch is decode_tensors'. k and atom are checked first, without a device."""
-    d = dict(batch) if batch is not None else {}
-    d.update(tensors)
-    pos = d.get("pos")
-    shape = tuple(getattr(pos, "shape", ()))
-    is_packed = d.get("cu_seqlens") is not None and len(shape) == 3
-    slot = api.check_neighbors(k, atom, shape[-2] if len(shape) in (3, 4) else None)
-    k = int(k)
-    for key in ("pos", "mask"):
-        if d.get(key) is None:
-            raise TypeError(f"neighbor_graph needs the tensor {key!r}")
-    c = codec or api.default_codec()
-    try:
-        import torch
-    except ImportError as e:
-        raise api.error(f"neighbor_graph needs PyTorch (ROCm build): {e}") from None
-    if not isinstance(pos, torch.Tensor):
-        raise api.error("neighbor_graph takes torch tensors on the GPU (numpy arrays: Codec.neighbors)")
-    if pos.device.type != "cuda" or pos.device.index != int(c.device):
-        raise api.error(f"neighbor_graph: pos lies on {pos.device}, the codec works on cuda:{int(c.device)}; there is no CPU path")
-    dev = pos.device
-    if len(shape) != (3 if is_packed else 4) or shape[-1] != 3 or pos.dtype != torch.float32:
-        raise ValueError(f"pos must be float32 [n, L, A, 3], or [R, A, 3] beside cu_seqlens, not {pos.dtype} {shape}")
-    A = shape[-2]
-    lay = dense_layout(_WIDTH_LAYOUT[A])
+    def check(d):
+        shape = tuple(getattr(d.get("pos"), "shape", ()))
+        slot = api.check_neighbors(k, atom, shape[-2] if len(shape) in (3, 4) else None)
+        _need("neighbor_graph", d)
+        return shape, d.get("cu_seqlens") is not None and len(shape) == 3, slot
 
-    def on_device(key, t, want, dtypes):
-        return _on_device(torch, "neighbor_graph", dev, key, t, want, dtypes)
-
-    on_device("pos", pos, shape, (torch.float32,))
-    mask = on_device("mask", d["mask"], shape[:-1], (torch.bool, torch.uint8)).view(torch.uint8)
-    index = torch.empty(shape[:-2] + (k,), dtype=torch.int32, device=dev)
-    dist = torch.empty(shape[:-2] + (k,), dtype=torch.float32, device=dev)
+    x, checked = _inputs("neighbor_graph", "Codec.neighbors", batch, tensors, codec, check, pos_rule="full", aatype=False)
+    k, torch, dev = int(k), x.torch, x.dev
+    index = torch.empty(x.lead + (k,), dtype=torch.int32, device=dev)
+    dist = torch.empty(x.lead + (k,), dtype=torch.float32, device=dev)
     out = dict(nbr_index=index, nbr_dist=dist)
-    n, rows, bound = _chain_bound(torch, "neighbor_graph", dev, d, shape, is_packed)
-    if n == 0 and not is_packed or rows == 0:
+    if x.n == 0 and not x.is_packed or x.rows == 0:
         return out
     torch.cuda.current_stream(dev).synchronize()
-    if is_packed:
-        _lib.check(c.lib.fcz_knn_packed_dev(c.ctx, pos.data_ptr(), mask.data_ptr(), bound.data_ptr(), n, rows, lay, slot, k, index.data_ptr(), dist.data_ptr()),
-                   "fcz_knn_packed_dev")
-    else:
-        _lib.check(c.lib.fcz_knn_dev(c.ctx, pos.data_ptr(), mask.data_ptr(), None if bound is None else bound.data_ptr(), n, rows, lay, slot, k,
-                                     index.data_ptr(), dist.data_ptr()), "fcz_knn_dev")
-    c.synchronize()
+    _knn_into(x, checked[2], k, index, dist)
+    x.codec.synchronize()
     return out
 
 
@@ -576,17 +524,21 @@ def _on_device(torch, what, dev, key, t, want, dtypes):
     if not isinstance(t, torch.Tensor) or t.device != dev:
         where = t.device if isinstance(t, torch.Tensor) else type(t).__name__
         raise api.error(f"{what}: {key} lies on {where}, pos on {dev}; every tensor must be on the codec's device")
-    if tuple(t.shape) != want or t.dtype not in dtypes:
+    if t.shape != want or t.dtype not in dtypes:
         raise ValueError(f"{key} must be {' / '.join(str(x) for x in dtypes)} {want}, not {t.dtype} {tuple(t.shape)}")
     if not t.is_contiguous():
         raise ValueError(f"{what}: {key} must be contiguous")
     return t
 
 
-def _chain_bound(torch, what, dev, d, shape, is_packed):
+def _chain_bound(torch, what, dev, d, shape, is_packed, one_entry=False):
     """the chains of the dense dict `d` whose pos has `shape` -> (n, rows, bound): packed, rows = R and bound = cu_seqlens as int32
     (non-decreasing and ending at R, checked on the device); padded, rows = L and bound = length as int32, or None when the dict has
-    none or carries crop_start (a window's padding rows carry a cleared mask and `length` is the uncropped size)"""
+    none or carries crop_start (a window's padding rows carry a cleared mask and `length` is the uncropped size). one_entry: what
+    rigid_frames reads, which uses atoms of a row's own only -- the packed form is one entry of R rows and cu_seqlens is not looked
+    at, and length is clamped at both ends"""
+    if is_packed and one_entry:
+        return 1, shape[0], None
     if is_packed:
         cu = d["cu_seqlens"]
         if not isinstance(cu, torch.Tensor) or cu.dim() != 1 or cu.shape[0] < 1:
@@ -600,8 +552,134 @@ def _chain_bound(torch, what, dev, d, shape, is_packed):
     bound = None
     if d.get("length") is not None and d.get("crop_start") is None:
         # (int32 >= 0 and uint32 share their bits; a negative length reads as a large one and is clamped to L)
-        bound = _on_device(torch, what, dev, "length", d["length"], (n,), (torch.int32, torch.int64)).clamp(min=0).to(torch.int32)
+        bound = _on_device(torch, what, dev, "length", d["length"], (n,), (torch.int32, torch.int64))
+        bound = (bound.clamp(min=0, max=2 ** 31 - 1) if one_entry else bound.clamp(min=0)).to(torch.int32)
     return n, L, bound
+
+
+class _Dense(NamedTuple):
+    """checked dense tensors on the device, what every analysis call reads: pos [.., A, 3] float32 of `shape` = lead + (A, 3), mask
+    viewed as uint8 (None only for apply_transform), aatype uint8 or None, `lay` the enum fcz_dense_layout of A; n chains of `rows`
+    rows each (padded: rows = L, bound = length as int32 or None) or over `rows` rows in all (packed: rows = R, bound = cu_seqlens)"""
+    codec: Codec
+    torch: object
+    dev: object
+    pos: object
+    mask: object
+    aatype: object
+    shape: tuple
+    lead: tuple
+    A: int
+    lay: int
+    n: int
+    rows: int
+    bound: object
+    is_packed: bool
+
+
+def _dense_written(c, torch, dev, pos, mask, aatype, lay, n, rows, bound, is_packed):
+    """the record of tensors decode_tensors allocated and had written: nothing to check"""
+    shape = tuple(pos.shape)
+    return _Dense(c, torch, dev, pos, mask, aatype, shape, shape[:-2], shape[-2], lay, n, rows, bound, is_packed)
+
+
+def _dense_checked(what, numpy_form, codec, d, shape, is_packed, pos_rule=None, aatype=True, one_entry=False):
+    """the record of the dense dict `d` a user gave, behind the device-free checks that found `shape` and `is_packed`: the codec, torch,
+    where pos lies, then every tensor on that device, of its shape and dtype, contiguous, and the chains (_chain_bound). pos_rule: the
+    shape rule of the functions whose device-free check leaves pos alone, "full" (rank, last axis, dtype) or "rank"; aatype=False: the
+    function reads no residue types, whatever the dict holds; numpy_form names the host form in the refusal of numpy arrays"""
+    pos = d["pos"]
+    c = codec or api.default_codec()
+    try:
+        import torch
+    except ImportError as e:
+        raise api.error(f"{what} needs PyTorch (ROCm build): {e}") from None
+    if not isinstance(pos, torch.Tensor):
+        raise api.error(f"{what} takes torch tensors on the GPU (numpy arrays: {numpy_form})")
+    dev = pos.device
+    if dev.type != "cuda" or dev.index != int(c.device):
+        raise api.error(f"{what}: pos lies on {dev}, the codec works on cuda:{int(c.device)}; there is no CPU path")
+    if pos_rule and (len(shape) != (3 if is_packed else 4) or pos_rule == "full" and (shape[-1] != 3 or pos.dtype != torch.float32)):
+        raise ValueError(f"pos must be float32 [n, L, A, 3], or [R, A, 3] beside cu_seqlens, not {pos.dtype} {shape}")
+    lead, A = shape[:-2], shape[-2]
+    if pos.dtype != torch.float32 or not pos.is_contiguous():                 # (pos lies where it lies and has its own shape: the rest of
+        _on_device(torch, what, dev, "pos", pos, shape, (torch.float32,))     # its rule, which raises with the rule's message)
+    mask = d.get("mask")
+    if mask is not None:
+        mask = _on_device(torch, what, dev, "mask", mask, shape[:-1], (torch.bool, torch.uint8)).view(torch.uint8)
+    aa = d.get("aatype") if aatype else None
+    if aa is not None:
+        aa = _on_device(torch, what, dev, "aatype", aa, lead, (torch.uint8,))
+    n, rows, bound = _chain_bound(torch, what, dev, d, shape, is_packed, one_entry)
+    return _Dense(c, torch, dev, pos, mask, aa, shape, lead, A, WIDTH_LAYOUTS[A], n, rows, bound, is_packed)
+
+
+def _need(what, d, keys=("pos", "mask"), of=""):
+    for key in keys:
+        if d.get(key) is None:
+            raise TypeError(f"{what} needs the tensor {key!r}{of}")
+
+
+def _inputs(what, numpy_form, batch, tensors, codec, check, pos_rule=None, aatype=True, one_entry=False):
+    """the one prelude of the functions on a dense batch: `batch` merged with the keyword tensors, the caller's device-free
+    check(d) -> (shape of pos, packed, ...) before a codec is made, then _dense_checked under the same rules -> (the record, what
+    check returned)"""
+    d = dict(batch) if batch is not None else {}
+    d.update(tensors)
+    checked = check(d)
+    return _dense_checked(what, numpy_form, codec, d, checked[0], checked[1], pos_rule, aatype, one_entry), checked
+
+
+def _pair_inputs(what, pred, true, codec, check, pos_rule="full", aatype=False):
+    """the one prelude of the functions on a prediction and its truth: both as dicts (pred may be its bare pos), the tensors that must
+    be there, pred's shapes against true's, the caller's device-free check(shape, pred pos shape, pred mask shape or None, true) before
+    a codec is made, _dense_checked on `true`, then pred's tensors on its device -> (the record of true, pred pos, pred mask viewed as
+    uint8 or None, what check returned)"""
+    t = dict(true) if isinstance(true, dict) else {"pos": true}
+    p = dict(pred) if isinstance(pred, dict) else {"pos": pred}
+    _need(what, t, of=" of true")
+    _need(what, p, ("pos",), " of pred")
+    ppos, pmask = p["pos"], p.get("mask")
+    shape, pshape = tuple(getattr(t["pos"], "shape", ())), tuple(getattr(ppos, "shape", ()))
+    mshape = None if pmask is None else tuple(getattr(pmask, "shape", ()))
+    if pshape != shape:
+        raise ValueError(f"pred pos must have the shape of true pos, {shape}, not {pshape}")
+    if mshape is not None and mshape != shape[:-1]:
+        raise ValueError(f"pred mask must have the shape of true mask, {shape[:-1]}, not {mshape}")
+    checked = check(shape, pshape, mshape, t)
+    x = _dense_checked(what, f"Codec.{what}", codec, t, shape, t.get("cu_seqlens") is not None and len(shape) == 3, pos_rule, aatype)
+    _on_device(x.torch, what, x.dev, "pred pos", ppos, shape, (x.torch.float32,))
+    if pmask is not None:
+        pmask = _on_device(x.torch, what, x.dev, "pred mask", pmask, shape[:-1], (x.torch.bool, x.torch.uint8)).view(x.torch.uint8)
+    return x, ppos, pmask, checked
+
+
+def _ptr(t):
+    return None if t is None else t.data_ptr()
+
+
+def _call(c, name, is_packed, *args):
+    """the packed or the padded entry point of one analysis, checked under its own name"""
+    name += "_packed_dev" if is_packed else "_dev"
+    _lib.check(getattr(c.lib, name)(c.ctx, *args), name)
+
+
+def _chain_score(hits, pairs, bound, is_packed):
+    """sum of hits / (4 * sum of pairs) over every chain's rows -> float64 [n], from int64 sums, 0 where the chain has no pair: a
+    cumulative sum differenced at cu_seqlens (packed) or a row sum (padded)"""
+    import torch
+    if is_packed:
+        zero = torch.zeros(1, dtype=torch.int64, device=hits.device)
+        at = bound.to(torch.int64)
+        ch, cp = (torch.cat([zero, x.to(torch.int64).cumsum(0)])[at].diff() for x in (hits, pairs))
+    else:
+        ch, cp = hits.to(torch.int64).sum(dim=1), pairs.to(torch.int64).sum(dim=1)
+    return torch.where(cp > 0, ch.to(torch.float64) / (4 * cp).clamp(min=1).to(torch.float64), torch.zeros((), dtype=torch.float64, device=hits.device))
+
+
+def _knn_into(x, slot, k, index, dist):
+    """fcz_knn_dev / _packed_dev on a record into index and dist [.., k], enqueued on the codec's stream"""
+    _call(x.codec, "fcz_knn", x.is_packed, x.pos.data_ptr(), x.mask.data_ptr(), _ptr(x.bound), x.n, x.rows, x.lay, slot, k, index.data_ptr(), dist.data_ptr())
 
 
 def lddt(pred, true, *, atom="CA", cutoff: float = 15.0, thresholds=(0.5, 1.0, 2.0, 4.0), codec: Optional[Codec] = None) -> dict:
@@ -623,61 +701,21 @@ def lddt(pred, true, *, atom="CA", cutoff: float = 15.0, thresholds=(0.5, 1.0, 2
 
     The tensors must be contiguous and lie on the codec's device; ordering against torch is decode_tensors'. cutoff, thresholds,
     atom and shapes that differ are checked first, without torch or a device (api.check_lddt)."""
-    t = dict(true) if isinstance(true, dict) else {"pos": true}
-    p = dict(pred) if isinstance(pred, dict) else {"pos": pred}
-    pos = t.get("pos")
-    shape = tuple(getattr(pos, "shape", ()))
-    is_packed = t.get("cu_seqlens") is not None and len(shape) == 3
-    slot, cutoff, th = api.check_lddt(cutoff, thresholds, atom, shape[-2] if len(shape) in (3, 4) else None)
-    for name, d, keys in (("true", t, ("pos", "mask")), ("pred", p, ("pos",))):
-        for key in keys:
-            if d.get(key) is None:
-                raise TypeError(f"lddt needs the tensor {key!r} of {name}")
-    ppos, pmask = p["pos"], p.get("mask")
-    if tuple(getattr(ppos, "shape", ())) != shape:
-        raise ValueError(f"pred pos must have the shape of true pos, {shape}, not {tuple(getattr(ppos, 'shape', ()))}")
-    if pmask is not None and tuple(getattr(pmask, "shape", ())) != shape[:-1]:
-        raise ValueError(f"pred mask must have the shape of true mask, {shape[:-1]}, not {tuple(getattr(pmask, 'shape', ()))}")
-    c = codec or api.default_codec()
-    try:
-        import torch
-    except ImportError as e:
-        raise api.error(f"lddt needs PyTorch (ROCm build): {e}") from None
-    if not isinstance(pos, torch.Tensor):
-        raise api.error("lddt takes torch tensors on the GPU (numpy arrays: Codec.lddt)")
-    if pos.device.type != "cuda" or pos.device.index != int(c.device):
-        raise api.error(f"lddt: pos lies on {pos.device}, the codec works on cuda:{int(c.device)}; there is no CPU path")
-    dev = pos.device
-    if len(shape) != (3 if is_packed else 4) or shape[-1] != 3 or pos.dtype != torch.float32:
-        raise ValueError(f"pos must be float32 [n, L, A, 3], or [R, A, 3] beside cu_seqlens, not {pos.dtype} {shape}")
-    lay = dense_layout(_WIDTH_LAYOUT[shape[-2]])
-    _on_device(torch, "lddt", dev, "pos", pos, shape, (torch.float32,))
-    mask = _on_device(torch, "lddt", dev, "mask", t["mask"], shape[:-1], (torch.bool, torch.uint8)).view(torch.uint8)
-    _on_device(torch, "lddt", dev, "pred pos", ppos, shape, (torch.float32,))
-    if pmask is not None:
-        pmask = _on_device(torch, "lddt", dev, "pred mask", pmask, shape[:-1], (torch.bool, torch.uint8)).view(torch.uint8)
-    n, rows, bound = _chain_bound(torch, "lddt", dev, t, shape, is_packed)
-    if rows > 2 ** 29:
+    x, ppos, pmask, (slot, cutoff, th) = _pair_inputs(
+        "lddt", pred, true, codec, lambda shape, pshape, mshape, t: api.check_lddt(cutoff, thresholds, atom, shape[-2] if len(shape) in (3, 4) else None))
+    if x.rows > 2 ** 29:
         raise ValueError("lddt_hits must fit int32: at most 2^29 rows per chain")
-    score = torch.zeros(shape[:-2], dtype=torch.float32, device=dev)
-    pairs = torch.zeros(shape[:-2], dtype=torch.int32, device=dev)
-    hits = torch.zeros(shape[:-2], dtype=torch.int32, device=dev)
+    torch, dev = x.torch, x.dev
+    score = torch.zeros(x.lead, dtype=torch.float32, device=dev)
+    pairs = torch.zeros(x.lead, dtype=torch.int32, device=dev)
+    hits = torch.zeros(x.lead, dtype=torch.int32, device=dev)
     if score.numel():
         th_c = (ctypes.c_float * 4)(*th)
         torch.cuda.current_stream(dev).synchronize()
-        fn, name = (c.lib.fcz_lddt_packed_dev, "fcz_lddt_packed_dev") if is_packed else (c.lib.fcz_lddt_dev, "fcz_lddt_dev")
-        _lib.check(fn(c.ctx, pos.data_ptr(), mask.data_ptr(), ppos.data_ptr(), None if pmask is None else pmask.data_ptr(),
-                      None if bound is None else bound.data_ptr(), n, rows, lay, slot, cutoff, ctypes.addressof(th_c), score.data_ptr(), pairs.data_ptr(),
-                      hits.data_ptr()), name)
-        c.synchronize()
-    if is_packed:   # a cumulative sum differenced at cu_seqlens
-        zero = torch.zeros(1, dtype=torch.int64, device=dev)
-        at = bound.to(torch.int64)
-        ch, cp = (torch.cat([zero, x.to(torch.int64).cumsum(0)])[at].diff() for x in (hits, pairs))
-    else:
-        ch, cp = hits.to(torch.int64).sum(dim=1), pairs.to(torch.int64).sum(dim=1)
-    chain = torch.where(cp > 0, ch.to(torch.float64) / (4 * cp).clamp(min=1).to(torch.float64), torch.zeros((), dtype=torch.float64, device=dev))
-    return dict(lddt=score, lddt_pairs=pairs, lddt_hits=hits, lddt_chain=chain.to(torch.float32))
+        _call(x.codec, "fcz_lddt", x.is_packed, x.pos.data_ptr(), x.mask.data_ptr(), ppos.data_ptr(), _ptr(pmask), _ptr(x.bound), x.n, x.rows, x.lay, slot, cutoff,
+              ctypes.addressof(th_c), score.data_ptr(), pairs.data_ptr(), hits.data_ptr())
+        x.codec.synchronize()
+    return dict(lddt=score, lddt_pairs=pairs, lddt_hits=hits, lddt_chain=_chain_score(hits, pairs, x.bound, x.is_packed).to(torch.float32))
 
 
 def lddt_atoms(pred, true, *, cutoff: float = 15.0, thresholds=(0.5, 1.0, 2.0, 4.0), swaps="alphafold", per_atom: bool = False,
@@ -703,75 +741,30 @@ def lddt_atoms(pred, true, *, cutoff: float = 15.0, thresholds=(0.5, 1.0, 2.0, 4
     counters integers (include/fcz_hip.h, fcz_lddt_atoms_dev): reproducible bit for bit, the same in atom37 and atom14, NOT
     differentiable. The tensors must be contiguous and lie on the codec's device; the arguments are checked first, without torch or a
     device (api.check_lddt_atoms)."""
-    t = dict(true) if isinstance(true, dict) else {"pos": true}
-    p = dict(pred) if isinstance(pred, dict) else {"pos": pred}
-    for name, d, keys in (("true", t, ("pos", "mask")), ("pred", p, ("pos",))):
-        for key in keys:
-            if d.get(key) is None:
-                raise TypeError(f"lddt_atoms needs the tensor {key!r} of {name}")
-    pos, ppos, pmask = t["pos"], p["pos"], p.get("mask")
-    shape = tuple(getattr(pos, "shape", ()))
-    is_packed = t.get("cu_seqlens") is not None and len(shape) == 3
-    cutoff, th, table = api.check_lddt_atoms(cutoff, thresholds, swaps, shape, tuple(getattr(ppos, "shape", ())),
-                                             None if pmask is None else tuple(getattr(pmask, "shape", ())), t.get("aatype") is not None, per_atom)
-    c = codec or api.default_codec()
-    try:
-        import torch
-    except ImportError as e:
-        raise api.error(f"lddt_atoms needs PyTorch (ROCm build): {e}") from None
-    if not isinstance(pos, torch.Tensor):
-        raise api.error("lddt_atoms takes torch tensors on the GPU (numpy arrays: Codec.lddt_atoms)")
-    if pos.device.type != "cuda" or pos.device.index != int(c.device):
-        raise api.error(f"lddt_atoms: pos lies on {pos.device}, the codec works on cuda:{int(c.device)}; there is no CPU path")
-    dev = pos.device
-    if len(shape) != (3 if is_packed else 4):
-        raise ValueError(f"pos must be float32 [n, L, A, 3], or [R, A, 3] beside cu_seqlens, not {pos.dtype} {shape}")
-    A, lead = shape[-2], shape[:-2]
-    lay = dense_layout(_WIDTH_LAYOUT[A])
-    _on_device(torch, "lddt_atoms", dev, "pos", pos, shape, (torch.float32,))
-    mask = _on_device(torch, "lddt_atoms", dev, "mask", t["mask"], shape[:-1], (torch.bool, torch.uint8)).view(torch.uint8)
-    _on_device(torch, "lddt_atoms", dev, "pred pos", ppos, shape, (torch.float32,))
-    if pmask is not None:
-        pmask = _on_device(torch, "lddt_atoms", dev, "pred mask", pmask, shape[:-1], (torch.bool, torch.uint8)).view(torch.uint8)
-    aatype = None
-    if table is not False:
-        aatype = _on_device(torch, "lddt_atoms", dev, "aatype", t["aatype"], lead, (torch.uint8,))
-    n, rows, bound = _chain_bound(torch, "lddt_atoms", dev, t, shape, is_packed)
+    def check(shape, pshape, mshape, t):
+        checked = api.check_lddt_atoms(cutoff, thresholds, swaps, shape, pshape, mshape, t.get("aatype") is not None, per_atom)
+        if checked[2] is False:
+            t["aatype"] = None                                                # (no renaming: the residue types are not looked at)
+        return checked
+
+    x, ppos, pmask, (cutoff, th, table) = _pair_inputs("lddt_atoms", pred, true, codec, check, pos_rule="rank", aatype=True)
+    torch, dev, lead = x.torch, x.dev, x.lead
     score = torch.zeros(lead, dtype=torch.float32, device=dev)
     pairs = torch.zeros(lead, dtype=torch.int32, device=dev)
     hits = torch.zeros(lead, dtype=torch.int32, device=dev)
     swapped = torch.zeros(lead, dtype=torch.uint8, device=dev)
-    atom = [torch.zeros(lead + (A,), dtype=torch.int32, device=dev) for _ in range(2)] if per_atom else None
+    atom = [torch.zeros(lead + (x.A,), dtype=torch.int32, device=dev) for _ in range(2)] if per_atom else None
     if score.numel():
         th_c = (ctypes.c_float * 4)(*th)
         c_out = CLddtAtomsOut(score.data_ptr(), pairs.data_ptr(), hits.data_ptr(), swapped.data_ptr(), *((a.data_ptr() for a in atom) if atom else (None, None)))
         torch.cuda.current_stream(dev).synchronize()
-        fn, name = (c.lib.fcz_lddt_atoms_packed_dev, "fcz_lddt_atoms_packed_dev") if is_packed else (c.lib.fcz_lddt_atoms_dev, "fcz_lddt_atoms_dev")
-        _lib.check(fn(c.ctx, pos.data_ptr(), mask.data_ptr(), ppos.data_ptr(), None if pmask is None else pmask.data_ptr(),
-                      None if aatype is None else aatype.data_ptr(), None if bound is None else bound.data_ptr(), n, rows, lay, cutoff,
-                      ctypes.addressof(th_c), table.ctypes.data if isinstance(table, np.ndarray) else None, ctypes.byref(c_out)), name)
-        c.synchronize()
-    if is_packed:   # a cumulative sum differenced at cu_seqlens
-        zero = torch.zeros(1, dtype=torch.int64, device=dev)
-        at = bound.to(torch.int64)
-        ch, cp = (torch.cat([zero, x.to(torch.int64).cumsum(0)])[at].diff() for x in (hits, pairs))
-    else:
-        ch, cp = hits.to(torch.int64).sum(dim=1), pairs.to(torch.int64).sum(dim=1)
-    chain = torch.where(cp > 0, ch.to(torch.float64) / (4 * cp).clamp(min=1).to(torch.float64), torch.zeros((), dtype=torch.float64, device=dev))
-    out = dict(lddt=score, lddt_pairs=pairs, lddt_hits=hits, swapped=swapped.view(torch.bool), lddt_chain=chain)
+        _call(x.codec, "fcz_lddt_atoms", x.is_packed, x.pos.data_ptr(), x.mask.data_ptr(), ppos.data_ptr(), _ptr(pmask), _ptr(x.aatype), _ptr(x.bound), x.n, x.rows,
+              x.lay, cutoff, ctypes.addressof(th_c), table.ctypes.data if isinstance(table, np.ndarray) else None, ctypes.byref(c_out))
+        x.codec.synchronize()
+    out = dict(lddt=score, lddt_pairs=pairs, lddt_hits=hits, swapped=swapped.view(torch.bool), lddt_chain=_chain_score(hits, pairs, x.bound, x.is_packed))
     if atom:
         out.update(atom_pairs=atom[0], atom_hits=atom[1])
     return out
-
-
-def _apply_transform(c, pos, mask, rot, trans, n, rows, bound, is_packed, lay, out):
-    """fcz_superpose_apply_dev / _packed_dev on checked device tensors into `out`, enqueued on the codec's stream"""
-    if n == 0:                                                                # (packed rows without a chain: covered by none)
-        out.zero_()
-    elif out.numel():
-        fn, name = (c.lib.fcz_superpose_apply_packed_dev, "fcz_superpose_apply_packed_dev") if is_packed else (c.lib.fcz_superpose_apply_dev, "fcz_superpose_apply_dev")
-        _lib.check(fn(c.ctx, pos.data_ptr(), None if mask is None else mask.data_ptr(), None if bound is None else bound.data_ptr(), n, rows, lay,
-                      rot.data_ptr(), trans.data_ptr(), out.data_ptr()), name)
 
 
 def superpose(pred, true, *, atom="CA", apply: bool = False, codec: Optional[Codec] = None) -> dict:
@@ -820,45 +813,17 @@ def tm_score(pred, true, *, atom="CA", apply: bool = False, iterations: int = 20
 
 def _superpose(pred, true, atom, apply, codec, what, search):
     """superpose (search None) and tm_score (search = (iterations, levels)): the shared checks, outputs and apply step"""
-    t = dict(true) if isinstance(true, dict) else {"pos": true}
-    p = dict(pred) if isinstance(pred, dict) else {"pos": pred}
-    pos = t.get("pos")
-    shape = tuple(getattr(pos, "shape", ()))
-    is_packed = t.get("cu_seqlens") is not None and len(shape) == 3
-    for name, d, keys in (("true", t, ("pos", "mask")), ("pred", p, ("pos",))):
-        for key in keys:
-            if d.get(key) is None:
-                raise TypeError(f"{what} needs the tensor {key!r} of {name}")
-    ppos, pmask = p["pos"], p.get("mask")
-    pshape, mshape = getattr(ppos, "shape", ()), None if pmask is None else getattr(pmask, "shape", ())
     if search is None:
-        slot = api.check_superpose(atom, shape, pshape, mshape)
+        x, ppos, pmask, slot = _pair_inputs(what, pred, true, codec, lambda shape, pshape, mshape, t: api.check_superpose(atom, shape, pshape, mshape))
     else:
-        slot, iterations, levels = api.check_tm_score(atom, shape, pshape, mshape, *search)
-    c = codec or api.default_codec()
-    try:
-        import torch
-    except ImportError as e:
-        raise api.error(f"{what} needs PyTorch (ROCm build): {e}") from None
-    if not isinstance(pos, torch.Tensor):
-        raise api.error(f"{what} takes torch tensors on the GPU (numpy arrays: Codec.{what})")
-    if pos.device.type != "cuda" or pos.device.index != int(c.device):
-        raise api.error(f"{what}: pos lies on {pos.device}, the codec works on cuda:{int(c.device)}; there is no CPU path")
-    dev = pos.device
-    if len(shape) != (3 if is_packed else 4) or shape[-1] != 3 or pos.dtype != torch.float32:
-        raise ValueError(f"pos must be float32 [n, L, A, 3], or [R, A, 3] beside cu_seqlens, not {pos.dtype} {shape}")
-    lay = dense_layout(_WIDTH_LAYOUT[shape[-2]])
-    _on_device(torch, what, dev, "pos", pos, shape, (torch.float32,))
-    mask = _on_device(torch, what, dev, "mask", t["mask"], shape[:-1], (torch.bool, torch.uint8)).view(torch.uint8)
-    _on_device(torch, what, dev, "pred pos", ppos, shape, (torch.float32,))
-    if pmask is not None:
-        pmask = _on_device(torch, what, dev, "pred mask", pmask, shape[:-1], (torch.bool, torch.uint8)).view(torch.uint8)
-    n, rows, bound = _chain_bound(torch, what, dev, t, shape, is_packed)
-    if rows > 2 ** 31 - 1:
+        x, ppos, pmask, (slot, iterations, levels) = _pair_inputs(
+            what, pred, true, codec, lambda shape, pshape, mshape, t: api.check_tm_score(atom, shape, pshape, mshape, *search))
+    if x.rows > 2 ** 31 - 1:
         raise ValueError("sites must fit int32: at most 2^31 - 1 rows per chain")
+    torch, dev, n = x.torch, x.dev, x.n
     out = dict(rot=torch.empty((n, 3, 3), dtype=torch.float32, device=dev), trans=torch.empty((n, 3), dtype=torch.float32, device=dev),
                rmsd=torch.empty((n,), dtype=torch.float32, device=dev), sites=torch.empty((n,), dtype=torch.int32, device=dev),
-               dev=torch.zeros(shape[:-2], dtype=torch.float32, device=dev), gdt_counts=torch.empty((n, 5), dtype=torch.int32, device=dev),
+               dev=torch.zeros(x.lead, dtype=torch.float32, device=dev), gdt_counts=torch.empty((n, 5), dtype=torch.int32, device=dev),
                tm=torch.empty((n,), dtype=torch.float32, device=dev))
     keys = ("rot", "trans", "rmsd", "sites", "gdt_counts", "tm", "dev")
     if search is not None:
@@ -866,7 +831,7 @@ def _superpose(pred, true, atom, apply, codec, what, search):
         keys += ("seed", "selected")
     if apply:
         out["pos_aligned"] = torch.empty_like(ppos)
-    solve = bool(n and rows)
+    solve = bool(n and x.rows)
     if n and not solve:                                                       # chains of no rows: what a chain without sites gets
         out["rot"].copy_(torch.eye(3, device=dev).expand(n, 3, 3))
         for k in keys:
@@ -874,23 +839,29 @@ def _superpose(pred, true, atom, apply, codec, what, search):
                 out[k].zero_()
     torch.cuda.current_stream(dev).synchronize()
     if solve:
-        args = (c.ctx, pos.data_ptr(), mask.data_ptr(), ppos.data_ptr(), None if pmask is None else pmask.data_ptr(), None if bound is None else bound.data_ptr(),
-                n, rows, lay, slot)
+        args = (x.pos.data_ptr(), x.mask.data_ptr(), ppos.data_ptr(), _ptr(pmask), _ptr(x.bound), n, x.rows, x.lay, slot)
         if search is None:
             s = CSuperposeOut(*(out[k].data_ptr() for k in keys))
-            fn, name = (c.lib.fcz_superpose_packed_dev, "fcz_superpose_packed_dev") if is_packed else (c.lib.fcz_superpose_dev, "fcz_superpose_dev")
-            _lib.check(fn(*args, ctypes.byref(s)), name)
+            _call(x.codec, "fcz_superpose", x.is_packed, *args, ctypes.byref(s))
         else:
             s = CTmScoreOut(*(out[k].data_ptr() for k in keys))
-            fn, name = (c.lib.fcz_tmscore_packed_dev, "fcz_tmscore_packed_dev") if is_packed else (c.lib.fcz_tmscore_dev, "fcz_tmscore_dev")
-            _lib.check(fn(*args, levels, iterations, ctypes.byref(s)), name)
+            _call(x.codec, "fcz_tmscore", x.is_packed, *args, levels, iterations, ctypes.byref(s))
     if apply:
-        _apply_transform(c, ppos, pmask, out["rot"], out["trans"], n, rows, bound, is_packed, lay, out["pos_aligned"])
-    c.synchronize()
+        _apply_transform(x._replace(pos=ppos, mask=pmask), out["rot"], out["trans"], out["pos_aligned"])
+    x.codec.synchronize()
     counts, S = out["gdt_counts"].to(torch.float64), out["sites"].to(torch.float64).clamp(min=1.0)
     out["gdt_ts"] = (counts[:, 1:5].sum(dim=1) / (4.0 * S)).to(torch.float32)
     out["gdt_ha"] = (counts[:, 0:4].sum(dim=1) / (4.0 * S)).to(torch.float32)
     return out
+
+
+def _apply_transform(x, rot, trans, out):
+    """fcz_superpose_apply_dev / _packed_dev on a record, whose mask may be None, into `out`, enqueued on the codec's stream"""
+    if x.n == 0:                                                              # (packed rows without a chain: covered by none)
+        out.zero_()
+    elif out.numel():
+        _call(x.codec, "fcz_superpose_apply", x.is_packed, x.pos.data_ptr(), _ptr(x.mask), _ptr(x.bound), x.n, x.rows, x.lay, rot.data_ptr(), trans.data_ptr(),
+              out.data_ptr())
 
 
 def apply_transform(pos, rot, trans, batch=None, *, mask=None, length=None, cu_seqlens=None, codec: Optional[Codec] = None):
@@ -911,8 +882,8 @@ def apply_transform(pos, rot, trans, batch=None, *, mask=None, length=None, cu_s
         d["length"] = length
     if cu_seqlens is not None:
         d["cu_seqlens"] = cu_seqlens
-    if pos is None:
-        raise TypeError("apply_transform needs the tensor 'pos'")
+    d.update(pos=pos, mask=mask)
+    _need("apply_transform", d, ("pos",))
     shape = tuple(getattr(pos, "shape", ()))
     is_packed = d.get("cu_seqlens") is not None and len(shape) == 3
     if len(shape) != (3 if is_packed else 4) or shape[-1] != 3 or shape[-2] not in _WIDTH_LAYOUT:
@@ -923,29 +894,15 @@ def apply_transform(pos, rot, trans, batch=None, *, mask=None, length=None, cu_s
             raise ValueError(f"{key} must be float32 {want}, one transform per chain, not {tuple(getattr(v, 'shape', ()))}")
     if mask is not None and tuple(getattr(mask, "shape", ())) != shape[:-1]:
         raise ValueError(f"mask must have the shape {shape[:-1]}, not {tuple(getattr(mask, 'shape', ()))}")
-    c = codec or api.default_codec()
-    try:
-        import torch
-    except ImportError as e:
-        raise api.error(f"apply_transform needs PyTorch (ROCm build): {e}") from None
-    if not isinstance(pos, torch.Tensor):
-        raise api.error("apply_transform takes torch tensors on the GPU (numpy arrays: Codec.apply_transform)")
-    if pos.device.type != "cuda" or pos.device.index != int(c.device):
-        raise api.error(f"apply_transform: pos lies on {pos.device}, the codec works on cuda:{int(c.device)}; there is no CPU path")
-    dev = pos.device
-    lay = dense_layout(_WIDTH_LAYOUT[shape[-2]])
-    _on_device(torch, "apply_transform", dev, "pos", pos, shape, (torch.float32,))
-    _on_device(torch, "apply_transform", dev, "rot", rot, (n, 3, 3), (torch.float32,))
-    _on_device(torch, "apply_transform", dev, "trans", trans, (n, 3), (torch.float32,))
-    if mask is not None:
-        mask = _on_device(torch, "apply_transform", dev, "mask", mask, shape[:-1], (torch.bool, torch.uint8)).view(torch.uint8)
-    n, rows, bound = _chain_bound(torch, "apply_transform", dev, d, shape, is_packed)
-    if rows > 2 ** 31 - 1:
+    x = _dense_checked("apply_transform", "Codec.apply_transform", codec, d, shape, is_packed, aatype=False)
+    _on_device(x.torch, "apply_transform", x.dev, "rot", rot, (n, 3, 3), (x.torch.float32,))
+    _on_device(x.torch, "apply_transform", x.dev, "trans", trans, (n, 3), (x.torch.float32,))
+    if x.rows > 2 ** 31 - 1:
         raise ValueError("at most 2^31 - 1 rows per chain")
-    out = torch.empty_like(pos)
-    torch.cuda.current_stream(dev).synchronize()
-    _apply_transform(c, pos, mask, rot, trans, n, rows, bound, is_packed, lay, out)
-    c.synchronize()
+    out = x.torch.empty_like(pos)
+    x.torch.cuda.current_stream(x.dev).synchronize()
+    _apply_transform(x, rot, trans, out)
+    x.codec.synchronize()
     return out
 
 
@@ -959,55 +916,22 @@ def _ss_alloc(torch, dev, rows):
     return dict(ss=torch.empty(tuple(rows), dtype=torch.uint8, device=dev), ss_mask=torch.empty(tuple(rows), dtype=torch.uint8, device=dev).view(torch.bool))
 
 
-def _hbonds_into(c, pos, mask, aatype, bound, n, rows, lay, is_packed, tables):
-    """fcz_hbond_dev / _packed_dev on checked device tensors into the four `tables`, enqueued on the codec's stream"""
-    fn, name = (c.lib.fcz_hbond_packed_dev, "fcz_hbond_packed_dev") if is_packed else (c.lib.fcz_hbond_dev, "fcz_hbond_dev")
-    _lib.check(fn(c.ctx, pos.data_ptr(), mask.data_ptr(), None if aatype is None else aatype.data_ptr(), None if bound is None else bound.data_ptr(),
-                  n, rows, lay, *(tables[k].data_ptr() for k, _ in api.HBOND_TABLES)), name)
+def _hbonds_into(x, tables):
+    """fcz_hbond_dev / _packed_dev on a record into the four `tables`, enqueued on the codec's stream"""
+    _call(x.codec, "fcz_hbond", x.is_packed, x.pos.data_ptr(), x.mask.data_ptr(), _ptr(x.aatype), _ptr(x.bound), x.n, x.rows, x.lay,
+          *(tables[k].data_ptr() for k, _ in api.HBOND_TABLES))
 
 
-def _labels_into(c, pos, mask, aatype, bound, n, rows, lay, is_packed, tables, out):
+def _labels_into(x, tables, out):
     """fcz_dssp_labels_dev / _packed_dev from the acceptor tables of `tables` into out["ss"], out["ss_mask"], enqueued alike"""
-    fn, name = (c.lib.fcz_dssp_labels_packed_dev, "fcz_dssp_labels_packed_dev") if is_packed else (c.lib.fcz_dssp_labels_dev, "fcz_dssp_labels_dev")
-    _lib.check(fn(c.ctx, pos.data_ptr(), mask.data_ptr(), None if aatype is None else aatype.data_ptr(), None if bound is None else bound.data_ptr(),
-                  n, rows, lay, tables["hbond_acc_index"].data_ptr(), tables["hbond_acc_energy"].data_ptr(), out["ss"].data_ptr(),
-                  out["ss_mask"].data_ptr()), name)
+    _call(x.codec, "fcz_dssp_labels", x.is_packed, x.pos.data_ptr(), x.mask.data_ptr(), _ptr(x.aatype), _ptr(x.bound), x.n, x.rows, x.lay,
+          tables["hbond_acc_index"].data_ptr(), tables["hbond_acc_energy"].data_ptr(), out["ss"].data_ptr(), out["ss_mask"].data_ptr())
 
 
-def _dssp_into(c, pos, mask, aatype, bound, n, rows, lay, is_packed, tables, out):
+def _dssp_into(x, tables, out):
     """both steps behind one another on the codec's stream"""
-    _hbonds_into(c, pos, mask, aatype, bound, n, rows, lay, is_packed, tables)
-    _labels_into(c, pos, mask, aatype, bound, n, rows, lay, is_packed, tables, out)
-
-
-def _dssp_inputs(what, batch, tensors, codec, hbonds=None, numpy_form="Codec.secondary_structure", check=None):
-    """the checked inputs of backbone_hbonds / secondary_structure / solvent_accessibility -> (c, torch, dev, pos, mask, aatype, lead,
-    n, rows, bound, is_packed, lay, hbonds); check(d) -> (shape, packed) replaces api.check_dssp, numpy_form names the host form"""
-    d = dict(batch) if batch is not None else {}
-    d.update(tensors)
-    shape, is_packed = api.check_dssp(what, d, hbonds) if check is None else check(d)
-    pos = d["pos"]
-    c = codec or api.default_codec()
-    try:
-        import torch
-    except ImportError as e:
-        raise api.error(f"{what} needs PyTorch (ROCm build): {e}") from None
-    if not isinstance(pos, torch.Tensor):
-        raise api.error(f"{what} takes torch tensors on the GPU (numpy arrays: {numpy_form})")
-    if pos.device.type != "cuda" or pos.device.index != int(c.device):
-        raise api.error(f"{what}: pos lies on {pos.device}, the codec works on cuda:{int(c.device)}; there is no CPU path")
-    dev = pos.device
-    lay = dense_layout(_WIDTH_LAYOUT[shape[-2]])
-    lead = shape[:-2]
-    _on_device(torch, what, dev, "pos", pos, shape, (torch.float32,))
-    mask = _on_device(torch, what, dev, "mask", d["mask"], shape[:-1], (torch.bool, torch.uint8)).view(torch.uint8)
-    aatype = None if d.get("aatype") is None else _on_device(torch, what, dev, "aatype", d["aatype"], lead, (torch.uint8,))
-    if hbonds is not None:
-        hbonds = dict(hbonds)
-        for key, dt in api.HBOND_TABLES[:2]:
-            hbonds[key] = _on_device(torch, what, dev, key, hbonds[key], lead + (2,), (getattr(torch, dt),))
-    n, rows, bound = _chain_bound(torch, what, dev, d, shape, is_packed)
-    return c, torch, dev, pos, mask, aatype, lead, n, rows, bound, is_packed, lay, hbonds
+    _hbonds_into(x, tables)
+    _labels_into(x, tables, out)
 
 
 def backbone_hbonds(batch=None, *, codec: Optional[Codec] = None, **tensors) -> dict:
@@ -1024,12 +948,12 @@ def backbone_hbonds(batch=None, *, codec: Optional[Codec] = None, **tensors) -> 
     energy is Kabsch and Sander's electrostatic one in kcal/mol (include/fcz_hip.h, fcz_hbond_dev), in float32 with every operation
     rounded and no rounding to 0.001; an entry is listed when its energy is below 0, and is a hydrogen bond when below -0.5.
     Reproducible bit for bit; NOT differentiable. The shapes are checked first, without torch or a device (api.check_dssp)."""
-    c, torch, dev, pos, mask, aatype, lead, n, rows, bound, is_packed, lay, _ = _dssp_inputs("backbone_hbonds", batch, tensors, codec)
-    out = _hbond_alloc(torch, dev, lead)
+    x, _ = _inputs("backbone_hbonds", "Codec.secondary_structure", batch, tensors, codec, lambda d: api.check_dssp("backbone_hbonds", d))
+    out = _hbond_alloc(x.torch, x.dev, x.lead)
     if out["hbond_acc_index"].numel():
-        torch.cuda.current_stream(dev).synchronize()
-        _hbonds_into(c, pos, mask, aatype, bound, n, rows, lay, is_packed, out)
-        c.synchronize()
+        x.torch.cuda.current_stream(x.dev).synchronize()
+        _hbonds_into(x, out)
+        x.codec.synchronize()
     return out
 
 
@@ -1046,15 +970,20 @@ def secondary_structure(batch=None, *, hbonds: Optional[dict] = None, codec: Opt
     The priority is the 1983 one, H > B, E > G > I > T > S; the rules are in include/fcz_hip.h (fcz_dssp_labels_dev). Sheet labels,
     bridge partners, accessibility and bonds between chains are not computed. A cropped window's labels are the window's own: a
     strand whose partner lies outside the window is not seen. Reproducible bit for bit; NOT differentiable."""
-    c, torch, dev, pos, mask, aatype, lead, n, rows, bound, is_packed, lay, hbonds = _dssp_inputs("secondary_structure", batch, tensors, codec, hbonds)
-    tables = _hbond_alloc(torch, dev, lead) if hbonds is None else hbonds
-    out = _ss_alloc(torch, dev, lead)
+    what = "secondary_structure"
+    x, _ = _inputs(what, "Codec.secondary_structure", batch, tensors, codec, lambda d: api.check_dssp(what, d, hbonds))
+    if hbonds is not None:
+        hbonds = dict(hbonds)
+        for key, dt in api.HBOND_TABLES[:2]:
+            hbonds[key] = _on_device(x.torch, what, x.dev, key, hbonds[key], x.lead + (2,), (getattr(x.torch, dt),))
+    tables = _hbond_alloc(x.torch, x.dev, x.lead) if hbonds is None else hbonds
+    out = _ss_alloc(x.torch, x.dev, x.lead)
     if out["ss"].numel():
-        torch.cuda.current_stream(dev).synchronize()
+        x.torch.cuda.current_stream(x.dev).synchronize()
         if hbonds is None:
-            _hbonds_into(c, pos, mask, aatype, bound, n, rows, lay, is_packed, tables)
-        _labels_into(c, pos, mask, aatype, bound, n, rows, lay, is_packed, tables, out)
-        c.synchronize()
+            _hbonds_into(x, tables)
+        _labels_into(x, tables, out)
+        x.codec.synchronize()
     return dict(out, **tables)
 
 
@@ -1070,13 +999,12 @@ def _sasa_work(torch, dev, shape, points=None):
     return torch.from_numpy(pts).to(dev), torch.empty(tuple(shape), dtype=torch.int16, device=dev)
 
 
-def _sasa_into(c, pos, mask, aatype, bound, n, rows, lay, is_packed, table, probe, points_t, counts_t, out):
-    """fcz_sasa_dev / _packed_dev on checked device tensors into counts_t, out["sasa"], out["sasa_mask"], enqueued on the codec's stream;
-    table: the radii as a contiguous float32 [21, A] array on the host, or None"""
-    fn, name = (c.lib.fcz_sasa_packed_dev, "fcz_sasa_packed_dev") if is_packed else (c.lib.fcz_sasa_dev, "fcz_sasa_dev")
-    _lib.check(fn(c.ctx, pos.data_ptr(), mask.data_ptr(), None if aatype is None else aatype.data_ptr(), None if bound is None else bound.data_ptr(),
-                  n, rows, lay, None if table is None else table.ctypes.data, float(probe), points_t.data_ptr(), int(points_t.shape[0]),
-                  counts_t.data_ptr(), out["sasa"].data_ptr(), out["sasa_mask"].data_ptr()), name)
+def _sasa_into(x, table, probe, points_t, counts_t, out):
+    """fcz_sasa_dev / _packed_dev on a record into counts_t, out["sasa"], out["sasa_mask"], enqueued on the codec's stream; table: the radii
+    as a contiguous float32 [21, A] array on the host, or None"""
+    _call(x.codec, "fcz_sasa", x.is_packed, x.pos.data_ptr(), x.mask.data_ptr(), _ptr(x.aatype), _ptr(x.bound), x.n, x.rows, x.lay,
+          None if table is None else table.ctypes.data, float(probe), points_t.data_ptr(), int(points_t.shape[0]), counts_t.data_ptr(),
+          out["sasa"].data_ptr(), out["sasa_mask"].data_ptr())
 
 
 def _rsa(torch, sasa, sasa_mask, aatype):
@@ -1110,22 +1038,15 @@ def solvent_accessibility(batch=None, *, probe: float = 1.4, n_points: int = 128
     fcz_sasa_dev): atom37 and atom14 give the same bits. A cropped window's values are the window's own: atoms outside it bury
     nothing, so residues at the cut look more exposed than in the whole chain. Reproducible bit for bit; NOT differentiable. The
     arguments are checked first, without torch or a device (api.check_sasa)."""
-    checked = {}
-
-    def check(d):
-        checked["v"] = api.check_sasa("solvent_accessibility", d, probe, n_points, points, radii)
-        return checked["v"][:2]
-
-    c, torch, dev, pos, mask, aatype, lead, n, rows, bound, is_packed, lay, _ = _dssp_inputs("solvent_accessibility", batch, tensors, codec,
-                                                                                             numpy_form="Codec.solvent_accessibility", check=check)
-    _, _, pts, table = checked["v"]
-    out = _sasa_alloc(torch, dev, lead)
-    points_t, counts = _sasa_work(torch, dev, lead + (pos.shape[-2],), pts)
+    x, (_, _, pts, table) = _inputs("solvent_accessibility", "Codec.solvent_accessibility", batch, tensors, codec,
+                                    lambda d: api.check_sasa("solvent_accessibility", d, probe, n_points, points, radii))
+    out = _sasa_alloc(x.torch, x.dev, x.lead)
+    points_t, counts = _sasa_work(x.torch, x.dev, x.lead + (x.A,), pts)
     if out["sasa"].numel():
-        torch.cuda.current_stream(dev).synchronize()
-        _sasa_into(c, pos, mask, aatype, bound, n, rows, lay, is_packed, table, probe, points_t, counts, out)
-        c.synchronize()
-        out["rsa"] = _rsa(torch, out["sasa"], out["sasa_mask"], aatype)
+        x.torch.cuda.current_stream(x.dev).synchronize()
+        _sasa_into(x, table, probe, points_t, counts, out)
+        x.codec.synchronize()
+        out["rsa"] = _rsa(x.torch, out["sasa"], out["sasa_mask"], x.aatype)
     return dict(out, sasa_points=counts)
 
 
@@ -1141,13 +1062,12 @@ def _viol_alloc(torch, dev, rows, A, n):
     return out
 
 
-def _viol_into(c, pos, mask, aatype, bound, n, rows, lay, is_packed, table, tolerance, link_factor, out):
-    """fcz_violations_dev / _packed_dev on checked device tensors into the tensors of _viol_alloc, enqueued on the codec's stream; table: the
-    radii as a contiguous float32 [21, A] array on the host, or None"""
-    fn, name = (c.lib.fcz_violations_packed_dev, "fcz_violations_packed_dev") if is_packed else (c.lib.fcz_violations_dev, "fcz_violations_dev")
+def _viol_into(x, table, tolerance, link_factor, out):
+    """fcz_violations_dev / _packed_dev on a record into the tensors of _viol_alloc, enqueued on the codec's stream; table: the radii as a
+    contiguous float32 [21, A] array on the host, or None"""
     c_out = CViolationsOut(*(out[key].data_ptr() for key, _, _ in api.VIOLATION_OUTPUTS))
-    _lib.check(fn(c.ctx, pos.data_ptr(), mask.data_ptr(), None if aatype is None else aatype.data_ptr(), None if bound is None else bound.data_ptr(),
-                  n, rows, lay, None if table is None else table.ctypes.data, float(tolerance), float(link_factor), ctypes.byref(c_out)), name)
+    _call(x.codec, "fcz_violations", x.is_packed, x.pos.data_ptr(), x.mask.data_ptr(), _ptr(x.aatype), _ptr(x.bound), x.n, x.rows, x.lay,
+          None if table is None else table.ctypes.data, float(tolerance), float(link_factor), ctypes.byref(c_out))
 
 
 def violations(batch=None, *, tolerance: float = 1.5, link_factor: float = 12.0, radii="bondi", codec: Optional[Codec] = None, **tensors) -> dict:
@@ -1178,20 +1098,12 @@ def violations(batch=None, *, tolerance: float = 1.5, link_factor: float = 12.0,
     give the same values. Bonds and angles inside a residue are not checked. A cropped window's values are the window's own.
     Reproducible bit for bit; NOT differentiable. The arguments are checked first, without torch or a device
     (api.check_violations)."""
-    checked = {}
-
-    def check(d):
-        checked["v"] = api.check_violations("violations", d, tolerance, link_factor, radii)
-        return checked["v"][:2]
-
-    c, torch, dev, pos, mask, aatype, lead, n, rows, bound, is_packed, lay, _ = _dssp_inputs("violations", batch, tensors, codec,
-                                                                                             numpy_form="Codec.violations", check=check)
-    table = checked["v"][2]
-    out = _viol_alloc(torch, dev, lead, pos.shape[-2], n)
+    x, checked = _inputs("violations", "Codec.violations", batch, tensors, codec, lambda d: api.check_violations("violations", d, tolerance, link_factor, radii))
+    out = _viol_alloc(x.torch, x.dev, x.lead, x.A, x.n)
     if out["clash_count"].numel():
-        torch.cuda.current_stream(dev).synchronize()
-        _viol_into(c, pos, mask, aatype, bound, n, rows, lay, is_packed, table, tolerance, link_factor, out)
-        c.synchronize()
+        x.torch.cuda.current_stream(x.dev).synchronize()
+        _viol_into(x, checked[2], tolerance, link_factor, out)
+        x.codec.synchronize()
     return out
 
 
@@ -1201,6 +1113,14 @@ def _frames_alloc(torch, dev, rows, fgroups):
     return dict(rot=torch.empty(tuple(rows) + g + (3, 3), dtype=torch.float32, device=dev),
                 trans=torch.empty(tuple(rows) + g + (3,), dtype=torch.float32, device=dev),
                 frame_mask=torch.empty(tuple(rows) + g, dtype=torch.uint8, device=dev).view(torch.bool))
+
+
+def _frames_into(x, fgroups, out):
+    """fcz_frames_dev on a record into the tensors of _frames_alloc, enqueued on the codec's stream. Frames use atoms of their own row
+    only, so the packed form goes as one entry of R rows with no length"""
+    bound, n = (None, 1) if x.is_packed else (x.bound, x.n)
+    _lib.check(x.codec.lib.fcz_frames_dev(x.codec.ctx, x.pos.data_ptr(), x.mask.data_ptr(), _ptr(x.aatype), _ptr(bound), n, x.rows, x.lay, fgroups,
+                                          out["rot"].data_ptr(), out["trans"].data_ptr(), out["frame_mask"].data_ptr()), "fcz_frames_dev")
 
 
 def rigid_frames(batch=None, *, groups="backbone", codec: Optional[Codec] = None, **tensors) -> dict:
@@ -1219,60 +1139,23 @@ def rigid_frames(batch=None, *, groups="backbone", codec: Optional[Codec] = None
 
     Padded: `length` is used when the dict has no crop_start (as neighbor_graph does). The tensors must be contiguous and lie on
     the codec's device; ordering against torch is decode_tensors'. groups is checked first, without a device."""
-    d = dict(batch) if batch is not None else {}
-    d.update(tensors)
-    fgroups = api.check_frames(groups, d.get("aatype") is not None)
-    pos = d.get("pos")
-    for key in ("pos", "mask"):
-        if d.get(key) is None:
-            raise TypeError(f"rigid_frames needs the tensor {key!r}")
-    shape = tuple(getattr(pos, "shape", ()))
-    if len(shape) not in (3, 4) or shape[-1] != 3 or shape[-2] not in _WIDTH_LAYOUT:
-        raise ValueError(f"pos must be float32 [n, L, A, 3] or [R, A, 3] with A = 37, 14 or 4, not {shape}")
-    c = codec or api.default_codec()
-    try:
-        import torch
-    except ImportError as e:
-        raise api.error(f"rigid_frames needs PyTorch (ROCm build): {e}") from None
-    if not isinstance(pos, torch.Tensor):
-        raise api.error("rigid_frames takes torch tensors on the GPU (numpy arrays: Codec.frames)")
-    if pos.device.type != "cuda" or pos.device.index != int(c.device):
-        raise api.error(f"rigid_frames: pos lies on {pos.device}, the codec works on cuda:{int(c.device)}; there is no CPU path")
-    dev = pos.device
-    lay = dense_layout(_WIDTH_LAYOUT[shape[-2]])
-    rows = shape[:-2]
+    def check(d):
+        fgroups = api.check_frames(groups, d.get("aatype") is not None)
+        _need("rigid_frames", d)
+        shape = tuple(getattr(d["pos"], "shape", ()))
+        if len(shape) not in (3, 4) or shape[-1] != 3 or shape[-2] not in _WIDTH_LAYOUT:
+            raise ValueError(f"pos must be float32 [n, L, A, 3] or [R, A, 3] with A = 37, 14 or 4, not {shape}")
+        if fgroups == 0:
+            d["aatype"] = None                                                # (the backbone frame reads no residue type: aatype is not looked at)
+        return shape, len(shape) == 3, fgroups                                # (the packed form: recognised by the shape of pos alone)
 
-    def on_device(key, t, want, dtypes):
-        if not isinstance(t, torch.Tensor) or t.device != dev:
-            where = t.device if isinstance(t, torch.Tensor) else type(t).__name__
-            raise api.error(f"rigid_frames: {key} lies on {where}, pos on {dev}; every tensor must be on the codec's device")
-        if tuple(t.shape) != want or t.dtype not in dtypes:
-            raise ValueError(f"{key} must be {' / '.join(str(x) for x in dtypes)} {want}, not {t.dtype} {tuple(t.shape)}")
-        if not t.is_contiguous():
-            raise ValueError(f"rigid_frames: {key} must be contiguous")
-        return t
-
-    on_device("pos", pos, shape, (torch.float32,))
-    mask = on_device("mask", d["mask"], shape[:-1], (torch.bool, torch.uint8)).view(torch.uint8)
-    aatype = None
-    if fgroups != 0:
-        aatype = on_device("aatype", d["aatype"], rows, (torch.uint8,))
-    out = _frames_alloc(torch, dev, rows, fgroups)
-    if len(rows) == 1:
-        n, L, bound = 1, rows[0], None
-    else:
-        n, L = rows
-        bound = None
-        if d.get("length") is not None and d.get("crop_start") is None:
-            # (int32 >= 0 and uint32 share their bits; a negative length is no row)
-            bound = on_device("length", d["length"], (n,), (torch.int32, torch.int64)).clamp(min=0, max=2 ** 31 - 1).to(torch.int32)
-    if n == 0 or L == 0:
+    x, (_, _, fgroups) = _inputs("rigid_frames", "Codec.frames", batch, tensors, codec, check, one_entry=True)
+    out = _frames_alloc(x.torch, x.dev, x.lead, fgroups)
+    if x.n == 0 or x.rows == 0:
         return out
-    torch.cuda.current_stream(dev).synchronize()
-    _lib.check(c.lib.fcz_frames_dev(c.ctx, pos.data_ptr(), mask.data_ptr(), None if aatype is None else aatype.data_ptr(),
-                                    None if bound is None else bound.data_ptr(), n, L, lay, fgroups, out["rot"].data_ptr(), out["trans"].data_ptr(),
-                                    out["frame_mask"].data_ptr()), "fcz_frames_dev")
-    c.synchronize()
+    x.torch.cuda.current_stream(x.dev).synchronize()
+    _frames_into(x, fgroups, out)
+    x.codec.synchronize()
     return out
 
 
@@ -1340,28 +1223,18 @@ def encode_tensors(batch=None, *, names=None, layout=None, anchor_residue_thresh
     if names is not None and len(names) != n:
         raise ValueError(f"{len(names)} names for {n} chains")
 
-    def on_device(key, t, shape, dtypes):
-        if not isinstance(t, torch.Tensor) or t.device != dev:
-            where = t.device if isinstance(t, torch.Tensor) else type(t).__name__
-            raise api.error(f"encode_tensors: {key} lies on {where}, pos on {dev}; every tensor must be on the codec's device")
-        if tuple(t.shape) != shape or t.dtype not in dtypes:
-            raise ValueError(f"{key} must be {' / '.join(str(x) for x in dtypes)} {shape}, not {t.dtype} {tuple(t.shape)}")
-        if not t.is_contiguous():
-            raise ValueError(f"encode_tensors: {key} must be contiguous")
-        return t
-
-    rows = (L,) if is_packed else (n, L)
-    on_device("pos", pos, rows + (A, 3), (torch.float32,))
-    mask = on_device("mask", d["mask"], rows + (A,), (torch.bool, torch.uint8))
-    aatype = on_device("aatype", d["aatype"], rows, (torch.uint8,))
-    length = on_device("cu_seqlens" if is_packed else "length", d["cu_seqlens" if is_packed else "length"], (n + 1,) if is_packed else (n,),
-                       (torch.int32, torch.int64))
-    plddt = on_device("plddt", d["plddt"], rows, (torch.float32,)) if d.get("plddt") is not None else None
+    rows, what = (L,) if is_packed else (n, L), "encode_tensors"
+    _on_device(torch, what, dev, "pos", pos, rows + (A, 3), (torch.float32,))
+    mask = _on_device(torch, what, dev, "mask", d["mask"], rows + (A,), (torch.bool, torch.uint8))
+    aatype = _on_device(torch, what, dev, "aatype", d["aatype"], rows, (torch.uint8,))
+    length = _on_device(torch, what, dev, "cu_seqlens" if is_packed else "length", d["cu_seqlens" if is_packed else "length"],
+                        (n + 1,) if is_packed else (n,), (torch.int32, torch.int64))
+    plddt = _on_device(torch, what, dev, "plddt", d["plddt"], rows, (torch.float32,)) if d.get("plddt") is not None else None
     first = None
     if d.get("first_res_index") is not None:
-        first = on_device("first_res_index", d["first_res_index"], (n,), (torch.int32, torch.int64)).to(torch.int32)
+        first = _on_device(torch, what, dev, "first_res_index", d["first_res_index"], (n,), (torch.int32, torch.int64)).to(torch.int32)
     elif d.get("res_index") is not None and L:
-        ri = on_device("res_index", d["res_index"], rows, (torch.int32,))
+        ri = _on_device(torch, what, dev, "res_index", d["res_index"], rows, (torch.int32,))
         # (packed: a chain without rows may start at R; its record is refused or empty, any row serves)
         first = ri[length[:-1].to(torch.int64).clamp(0, L - 1)].contiguous() if is_packed else ri[:, 0].contiguous()
     if n == 0:

@@ -63,7 +63,7 @@ def run_step(args, layout):
         sys.exit("violations_rate: no HIP device; a time is measured on the GPU or not at all")
     import foldcomp_amd as foldcomp
     from foldcomp_amd import _lib, api, synthetic
-    from foldcomp_amd.tensors import _sasa_into, _viol_alloc, _viol_into
+    from foldcomp_amd.tensors import _dense_written, _sasa_into, _viol_alloc, _viol_into
     dev = torch.device("cuda:0")
     codec = api.default_codec()
     codec.enable_timing(True)
@@ -86,12 +86,13 @@ def run_step(args, layout):
     A = pos.shape[2]
     lay = {37: 0, 14: 1, 4: 2}[A]
     out = _viol_alloc(torch, dev, (n, L), A, n)
+    dense = _dense_written(codec, torch, dev, pos, mask, aatype, lay, n, L, None, False)
 
     def sync():
         torch.cuda.synchronize(); codec.synchronize()
 
     def call():
-        _viol_into(codec, pos, mask, aatype, None, n, L, lay, False, None, api.VIOLATION_TOLERANCE, api.VIOLATION_LINK_FACTOR, out)
+        _viol_into(dense, None, api.VIOLATION_TOLERANCE, api.VIOLATION_LINK_FACTOR, out)
 
     ev = []
 
@@ -109,7 +110,7 @@ def run_step(args, layout):
 
     def sasa_once():
         codec.reset_timing()
-        _sasa_into(codec, pos, mask, aatype, None, n, L, lay, False, None, api.SASA_PROBE, pts, sasa_counts, sasa_out)
+        _sasa_into(dense, None, api.SASA_PROBE, pts, sasa_counts, sasa_out)
         codec.synchronize(); sev.append(codec.kernel_time("sasa")[0])
 
     swall = timed(sasa_once, sync, args.warmup, args.reps)

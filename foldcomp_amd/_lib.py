@@ -9,7 +9,7 @@ from __future__ import annotations
 import ctypes
 import os
 
-from .structure import (CAtomsOut, CChainBatch, CDenseIn, CDenseOut, CEntryInfo, CIngestResult, CLddtAtomsOut, CPackedOut, CSuperposeOut, CTmScoreOut,
+from .structure import (CAtomsOut, CChainBatch, CDenseIn, CDenseOut, CEntryInfo, CIngestResult, CLddtAtomsOut, CPackedOut, CSuperposeOut, CTmScoreOut, CChainSet, CTmAlignParams, CTmAlignOut,
                         CViolationsOut)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -130,6 +130,15 @@ def load():
         "fcz_tmscore_packed_dev": (i32, [vp, vp, vp, vp, vp, vp, u32, u32, i32, i32, u32, u32, ctypes.POINTER(CTmScoreOut)]),
         "fcz_tmscore": (i32, [vp, vp, vp, vp, vp, vp, u32, u32, i32, i32, u32, u32, ctypes.POINTER(CTmScoreOut)]),
         "fcz_tmscore_packed": (i32, [vp, vp, vp, vp, vp, vp, u32, u32, i32, i32, u32, u32, ctypes.POINTER(CTmScoreOut)]),
+        "fcz_tmalign_seeds": (u64, [u32, u32, u32]),
+        "fcz_tmalign_seed": (i32, [u32, u32, u32, u64, ctypes.POINTER(i32), ctypes.POINTER(i32), ctypes.POINTER(u32), ctypes.POINTER(u32), ctypes.POINTER(u32)]),
+        "fcz_tmalign_last_work": (i32, [vp, ctypes.POINTER(u64), ctypes.POINTER(u64)]),
+        "fcz_tmalign_dev": (i32, [vp, ctypes.POINTER(CChainSet), ctypes.POINTER(CChainSet), vp, u32, u32, u32, i32, i32, ctypes.POINTER(CTmAlignParams),
+                            ctypes.POINTER(CTmAlignOut)]),
+        "fcz_tmalign": (i32, [vp, ctypes.POINTER(CChainSet), ctypes.POINTER(CChainSet), vp, u32, u32, u32, i32, i32, ctypes.POINTER(CTmAlignParams),
+                        ctypes.POINTER(CTmAlignOut)]),
+        "fcz_tmalign_dp_dev": (i32, [vp, ctypes.POINTER(CChainSet), ctypes.POINTER(CChainSet), vp, u32, u32, u32, i32, i32, vp, vp, ctypes.c_double, vp, vp]),
+        "fcz_tmalign_dp": (i32, [vp, ctypes.POINTER(CChainSet), ctypes.POINTER(CChainSet), vp, u32, u32, u32, i32, i32, vp, vp, ctypes.c_double, vp, vp]),
         "fcz_frames_width": (i32, [i32]),
         "fcz_frame_atom": (i32, [i32, i32, i32]),
         "fcz_frame_ambiguous": (i32, [i32, i32]),
@@ -201,6 +210,7 @@ EXPORTS = ["fcz_ctx_create", "fcz_ctx_destroy", "fcz_ctx_stream", "fcz_ctx_synch
            "fcz_superpose_dev", "fcz_superpose_packed_dev", "fcz_superpose", "fcz_superpose_packed",
            "fcz_superpose_apply_dev", "fcz_superpose_apply_packed_dev", "fcz_superpose_apply", "fcz_superpose_apply_packed",
            "fcz_tmscore_seeds", "fcz_tmscore_seed_fragment", "fcz_tmscore_dev", "fcz_tmscore_packed_dev", "fcz_tmscore", "fcz_tmscore_packed",
+           "fcz_tmalign_seeds", "fcz_tmalign_seed", "fcz_tmalign_last_work", "fcz_tmalign_dev", "fcz_tmalign", "fcz_tmalign_dp_dev", "fcz_tmalign_dp",
            "fcz_frames_width", "fcz_frame_atom", "fcz_frame_ambiguous", "fcz_frames_dev", "fcz_frames",
            "fcz_extract_sizes", "fcz_extract",
            "fcz_extract_sizes_dev", "fcz_extract_dev", "fcz_ingest_pdb_dev", "fcz_ingest_pdb_begin", "fcz_ingest_pdb_fetch", "fcz_ingest_chain_names_fetch",

@@ -480,6 +480,60 @@ def check_tm_search(iterations=20, levels=None):
     return int(iterations), 0 if levels is None else int(levels)
 
 
+TM_ALIGN_MAX_WIDTH = 1024                                                  # FCZ_TMALIGN_MAX_WIDTH (include/fcz_hip.h)
+TM_ALIGN_MAX_ROUNDS = 64
+TM_ALIGN_MAX_GAP = 16.0
+
+
+def check_tm_align(atom, shape_a, shape_b, wa, wb, pairs_shape=None, fragments=True, refine=4, dp_rounds=20, gaps=(0.6, 0.0), iterations=20, levels=None,
+                   transform=None):
+    """the argument rules of tm_align that need no torch and no GPU -> (slot, fragments 0 / 1, refine, dp_rounds, gaps as a tuple of
+    floats, iterations, levels as the C call takes it). shape_a / shape_b: pos of the two chain sets, each [n, L, A, 3] or [R, A, 3], of
+    one width A; wa / wb: the widths (L of a padded set, the longest chain of a packed one, None while unknown), at most 1024;
+    pairs_shape: the shape of pairs, [m, 2], when pairs are given; fragments a switch; refine and dp_rounds integers 0 .. 64; gaps one
+    to four numbers in [0, 16]; iterations and levels as tm_score's; transform, when given, the shapes of (rot, trans): [m, 3, 3] and
+    [m, 3] with pairs' m"""
+    shape_a, shape_b = tuple(shape_a), tuple(shape_b)
+    for name, shape in (("a", shape_a), ("b", shape_b)):
+        if len(shape) not in (3, 4) or shape[-1] != 3 or shape[-2] not in (37, 14, 4):
+            raise ValueError(f"pos of {name} must be float32 [n, L, A, 3], or [R, A, 3] beside cu_seqlens, with A = 37, 14 or 4, not {shape}")
+    if shape_a[-2] != shape_b[-2]:
+        raise ValueError(f"a and b must share one layout, not widths {shape_a[-2]} and {shape_b[-2]}")
+    slot = check_neighbors(1, atom, shape_a[-2])
+    for name, w in (("a", wa), ("b", wb)):
+        if w is not None and int(w) > TM_ALIGN_MAX_WIDTH:
+            raise ValueError(f"tm_align handles chains of at most {TM_ALIGN_MAX_WIDTH} rows; {name} has one of {int(w)} (crop it, or align windows)")
+    if pairs_shape is not None and (len(tuple(pairs_shape)) != 2 or tuple(pairs_shape)[1] != 2):
+        raise ValueError(f"pairs must be int32 [m, 2] (chain of a, chain of b), not {tuple(pairs_shape)}")
+    if not isinstance(fragments, (bool, np.bool_)):
+        raise ValueError(f"fragments must be True or False, not {fragments!r}")
+    for name, v in (("refine", refine), ("dp_rounds", dp_rounds)):
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or not 0 <= int(v) <= TM_ALIGN_MAX_ROUNDS:
+            raise ValueError(f"{name} must be an integer 0 .. {TM_ALIGN_MAX_ROUNDS}, not {v!r}")
+    number = lambda v: isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, (bool, np.bool_))
+    try:
+        gs = tuple(gaps)
+    except TypeError:
+        gs = (gaps,)
+    if not 1 <= len(gs) <= 4 or not all(number(g) and 0.0 <= float(g) <= TM_ALIGN_MAX_GAP for g in gs):
+        raise ValueError(f"gaps must be one to four numbers in [0, {TM_ALIGN_MAX_GAP:g}], not {gaps!r}")
+    iterations, levels = check_tm_search(iterations, levels)
+    if transform is not None:
+        rs, ts = (tuple(x) for x in transform)
+        if len(rs) != 3 or rs[1:] != (3, 3) or ts != (rs[0], 3) or (pairs_shape is not None and rs[0] != tuple(pairs_shape)[0]):
+            raise ValueError(f"transform must be (rot [m, 3, 3], trans [m, 3]) with one transform per pair, not {rs} and {ts}")
+    return slot, int(bool(fragments)), int(refine), int(dp_rounds), tuple(float(g) for g in gs), iterations, levels
+
+
+def tm_align_pairs(n_a, n_b, same):
+    """the pairs tm_align takes when none are given -> int32 [m, 2]: every i < j of one set, or every (i, j) of two, a-major"""
+    if same:
+        i, j = np.triu_indices(n_a, 1)
+    else:
+        i, j = (x.ravel() for x in np.meshgrid(np.arange(n_a), np.arange(n_b), indexing="ij"))
+    return np.ascontiguousarray(np.stack([i, j], axis=1), np.int32)
+
+
 # the labels of `ss`, in the order of their codes (include/fcz_hip.h, fcz_dssp_labels_dev), and the usual reduction to three states
 # (helix 0: H, G, I; strand 1: E, B; coil 2: the rest) as a table to index with `ss`
 SS_CLASSES = ("-", "H", "B", "E", "G", "I", "T", "S")

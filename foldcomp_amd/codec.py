@@ -122,6 +122,25 @@ def _pair_arrays(pos_true, mask_true, pos_pred, mask_pred, aatype, length, row_o
     return a, pos_pred, mask_pred, slot
 
 
+def _tm_align_inputs(pos_a, mask_a, pos_b, mask_b, pairs, slot, length_a, row_off_a, length_b, row_off_b, fragments, refine, dp_rounds, gaps,
+                     iterations, levels, transform):
+    """the prelude of Codec.tm_align and Codec.tm_align_dp -> (CChainSet a, CChainSet b, pairs int32 [m, 2], wa, wb, the layout, api.check_tm_align's
+    tuple (the slot first), the arrays the two structs point into: the caller keeps them until its call returns)"""
+    from . import api
+    from .structure import CChainSet
+    xa = _dense_arrays(pos_a, mask_a, None, length_a, row_off_a, name="pos_a", mask_name="mask_a")
+    same = pos_b is None
+    xb = xa if same else _dense_arrays(pos_b, mask_b, None, length_b, row_off_b, name="pos_b", mask_name="mask_b")
+    pairs = api.tm_align_pairs(xa.n, xb.n, same) if pairs is None else np.ascontiguousarray(pairs, np.int32)
+    width = lambda x: int(np.diff(x.bound.astype(np.int64)).clip(min=0).max(initial=1)) if x.packed else x.rows
+    wa, wb = max(min(width(xa), max(xa.rows, 1)), 1), max(min(width(xb), max(xb.rows, 1)), 1)
+    shapes = None if transform is None else (np.shape(transform[0]), np.shape(transform[1]))
+    par = api.check_tm_align(int(slot), xa.pos.shape, xb.pos.shape, wa, wb, pairs.shape, fragments, refine, dp_rounds, gaps, iterations, levels, shapes)
+    sets = [CChainSet(x.pos.ctypes.data, x.mask.ctypes.data, None if x.packed else _addr(x.bound), _addr(x.bound) if x.packed else None, x.n, x.rows)
+            for x in (xa, xb)]
+    return sets[0], sets[1], pairs, wa, wb, xa.lay, par, (xa, xb)
+
+
 class Codec:
     def __init__(self, device: int = 0):
         self.lib = _lib.load()
@@ -449,6 +468,46 @@ class Codec:
             out = CTmScoreOut(*(d[k].ctypes.data for k in ("rot", "trans", "rmsd", "sites", "gdt_counts", "tm", "dev", "seed", "selected")))
             self._call("fcz_tmscore", a.packed, a.pos.ctypes.data, a.mask.ctypes.data, pos_pred.ctypes.data, _addr(mask_pred), _addr(a.bound), a.n, a.rows, a.lay,
                        slot, levels, iterations, ctypes.byref(out))
+        return d
+
+    def tm_align(self, pos_a: np.ndarray, mask_a: np.ndarray, pos_b=None, mask_b=None, pairs=None, slot: int = 1, *, length_a=None, row_off_a=None,
+                 length_b=None, row_off_b=None, fragments: bool = True, refine: int = 4, dp_rounds: int = 20, gaps=(0.6, 0.0), iterations: int = 20,
+                 levels=None):
+        """two sets of chains on the host, each padded (pos [n, L, A, 3], mask [n, L, A], length [n] or None) or packed (pos [R, A, 3],
+        mask [R, A], row_off [n + 1]), and pairs int32 [m, 2] of chain indices -> the TM-align-style alignment of every pair (fcz_tmalign;
+        the definition: include/fcz_hip.h): rot [m, 3, 3], trans [m, 3] (x_b ~ rot @ x_a + trans), tm (by the shorter chain), tm_a, tm_b,
+        rmsd float32 [m], aligned, sites_a, sites_b, seed, status int32 [m], map int32 [m, wa] (the chain-relative row of b of every row of
+        a, -1 = unaligned) and dev float32 [m, wa], wa being L or the longest chain of a packed a. pos_b None: b is a; pairs None: every
+        i < j of a, or every (i, j) of a and b. The other arguments are foldcomp.tm_align's. Reproducible bit for bit."""
+        a, b, pairs, wa, wb, lay, par, _kept = _tm_align_inputs(pos_a, mask_a, pos_b, mask_b, pairs, slot, length_a, row_off_a, length_b, row_off_b,
+                                                                fragments, refine, dp_rounds, gaps, iterations, levels, None)
+        from .structure import TM_ALIGN_OUTPUTS, CTmAlignOut, CTmAlignParams
+        m = len(pairs)
+        d = {k: np.zeros((m,) + ((wa,) if tail == "wa" else tail), dt) for k, dt, tail in TM_ALIGN_OUTPUTS}
+        d["rot"][:] = np.eye(3, dtype=np.float32)
+        d["map"][:] = -1
+        if m:
+            slot, frag, refine, dp_rounds, gs, iterations, levels = par
+            p = CTmAlignParams(frag, refine, dp_rounds, len(gs), (ctypes.c_double * 4)(*gs), levels, iterations)
+            out = CTmAlignOut(*(d[k].ctypes.data for k, _, _ in TM_ALIGN_OUTPUTS))
+            _lib.check(self.lib.fcz_tmalign(self.ctx, ctypes.byref(a), ctypes.byref(b), pairs.ctypes.data, m, wa, wb, lay, slot, ctypes.byref(p),
+                                            ctypes.byref(out)), "fcz_tmalign")
+        d["pairs"] = pairs
+        return d
+
+    def tm_align_dp(self, pos_a: np.ndarray, mask_a: np.ndarray, pos_b, mask_b, pairs, rot, trans, gap: float = 0.6, slot: int = 1, *, length_a=None,
+                    row_off_a=None, length_b=None, row_off_b=None):
+        """the dynamic programme of tm_align alone (fcz_tmalign_dp), once per pair from the caller's transforms rot float32 [m, 3, 3],
+        trans [m, 3] (x_b ~ rot @ x_a + trans) and one gap penalty -> map int32 [m, wa], aligned int32 [m], pairs. The integer DP is exact:
+        numpy reproduces it bit for bit from the same transforms (include/fcz_hip.h)."""
+        a, b, pairs, wa, wb, lay, par, _kept = _tm_align_inputs(pos_a, mask_a, pos_b, mask_b, pairs, slot, length_a, row_off_a, length_b, row_off_b,
+                                                                True, 4, 20, (gap,), 20, None, (rot, trans))
+        m = len(pairs)
+        rot, trans = np.ascontiguousarray(rot, np.float32), np.ascontiguousarray(trans, np.float32)
+        d = dict(map=np.full((m, wa), -1, np.int32), aligned=np.zeros(m, np.int32), pairs=pairs)
+        if m:
+            _lib.check(self.lib.fcz_tmalign_dp(self.ctx, ctypes.byref(a), ctypes.byref(b), pairs.ctypes.data, m, wa, wb, lay, par[0], rot.ctypes.data,
+                                               trans.ctypes.data, float(gap), d["map"].ctypes.data, d["aligned"].ctypes.data), "fcz_tmalign_dp")
         return d
 
     @staticmethod

@@ -41,6 +41,7 @@
 #include "fcz_lddt_atoms.h"
 #include "fcz_superpose.h"
 #include "fcz_tmscore.h"
+#include "fcz_tmalign.h"
 #include "fcz_frames.h"
 #include "fcz_angles.h"
 
@@ -98,14 +99,17 @@ struct timed_span { std::string name; hipEvent_t a, b; };
 // DSSP_OUT: acc_index, acc_energy, don_index, don_energy, ss, ss_mask of fcz_dssp; SASA_POINTS: the directions of fcz_sasa, SASA_OUT: sasa_points, sasa, sasa_mask;
 // SUPERPOSE_OUT: the seven arrays of a fcz_superpose_out in the struct's order; APPLY_ROT, APPLY_TRANS, APPLY_OUT: the transforms and the moved
 // coordinates of fcz_superpose_apply (its pos and mask go through LDDT_PRED); TM_SEED, TM_SELECTED: the two arrays a fcz_tmscore_out adds to those seven;
-// VIOL_OUT .. VIOL_OUT_LAST: the ten arrays of a fcz_violations_out in the struct's order; LDDTA_OUT: the six of a fcz_lddt_atoms_out
+// VIOL_OUT .. VIOL_OUT_LAST: the ten arrays of a fcz_violations_out in the struct's order; LDDTA_OUT: the six of a fcz_lddt_atoms_out;
+// TA_SETS: pos, mask, length / row_off of the two fcz_chain_set of fcz_tmalign, TA_PAIRS: its pairs, TA_OUT: the thirteen arrays of a fcz_tmalign_out in the
+// struct's order; TA_DP_*: the transforms, map and aligned of fcz_tmalign_dp
 enum { REC_BLOB, REC_OFF, REC_RES_OFF, REC_ATOM_OFF, REC_X, REC_Y, REC_Z, REC_BFAC, REC_RES_CODE, REC_ATOM_CODE,
        FILES_TEXT = 0, FILES_OFF, FILES_NAMES, FILES_NAME_OFF, FILES_STEM_LEN, BATCH_IN = 0, DENSE_IN = 0, LDDT_PRED = 4, DENSE_OUT = 10, LDDT_OUT = 10, SUPERPOSE_OUT = 10, DSSP_OUT = 10,
        SASA_POINTS = 4, SASA_OUT = 10,
        APPLY_ROT = 10, APPLY_TRANS, APPLY_OUT,
        PACKED_OUT = 10, ANGLES_OUT = 10, KEPT_OFF = 13, KEPT_BYTES, KEPT_STATUS, PACKED_OUT_LAST, WINDOW_START = PACKED_OUT_LAST, TM_SEED, TM_SELECTED,
-       VIOL_OUT = 10, LDDTA_OUT = 10, VIOL_OUT_LAST = 19, POOL_COUNT };
-static_assert(POOL_COUNT == VIOL_OUT_LAST + 1 && LDDTA_OUT + 6 <= POOL_COUNT && TM_SELECTED < POOL_COUNT, "the last name of the enum sizes fcz_ctx::pool");
+       VIOL_OUT = 10, LDDTA_OUT = 10, TA_SETS = 0, TA_PAIRS = 6, TA_OUT = 7, TA_DP_ROT = 7, TA_DP_TRANS, TA_DP_MAP, TA_DP_ALIGNED, VIOL_OUT_LAST = 19, POOL_COUNT };
+static_assert(POOL_COUNT == VIOL_OUT_LAST + 1 && LDDTA_OUT + 6 <= POOL_COUNT && TM_SELECTED < POOL_COUNT && TA_OUT + 13 <= POOL_COUNT && TA_SETS + 6 == TA_PAIRS &&
+              TA_PAIRS < TA_OUT && TA_DP_ALIGNED < POOL_COUNT, "the last name of the enum sizes fcz_ctx::pool");
 
 // what the device reports to the host in the middle of a call: one pinned allocation, a member per reader
 struct pinned_words {
@@ -155,6 +159,8 @@ struct fcz_ctx {
     dev_buf sizes_res_off;   // decompress: the res_off of a batch call that has to run its own sizes pass (ensure_sizes)
     dev_buf selftest_out;    // fcz_selftest_math
     dev_buf sweep_tiles;     // the packed form of every per-chain sweep (chain_tiles): n u64 tile counts, then their n + 1 offsets
+    dev_buf ta_work;              // fcz_tmalign_dev: two u64, the DPs and DP cells of the last call (fcz_tmalign_last_work)
+    dev_buf ta_scratch, ta_dir;   // fcz_tmalign_dev: m u64 item counts, their m + 1 offsets, a double per seed, 2 m u32 site counts; the traceback bits, wa * 256 bytes a resident wavefront
     dev_buf tm_scratch;      // fcz_tmscore_dev / _packed_dev: n u64 item counts, their n + 1 offsets, a double per seed (tm_items_bound), n u32 site counts
     dev_buf dssp_flags;      // fcz_dssp_labels_dev / _packed_dev: a byte per row (k_dssp_flags -> k_dssp_labels)
     dev_buf fast_scratch;    // decompress, FCZ_NUMERICS_FAST: forward atoms of segments longer than one chunk
@@ -186,6 +192,8 @@ struct fcz_ctx {
     //   fcz_frames                                  DENSE_IN 0 .. 3 (pos, mask, aatype, length), DENSE_OUT 10 .. 12 (rot, trans, frame_mask)
     //   fcz_sasa / fcz_sasa_packed                  DENSE_IN 0 .. 3 (pos, mask, aatype, length / row_off), SASA_POINTS 4, SASA_OUT 10 .. 12 (sasa_points, sasa, sasa_mask)
     //   fcz_violations / fcz_violations_packed      DENSE_IN 0 .. 3 (pos, mask, aatype, length / row_off), VIOL_OUT 10 .. 19 (the arrays of fcz_violations_out)
+    //   fcz_tmalign                                 TA_SETS 0 .. 5 (pos, mask, length / row_off of a, then of b), TA_PAIRS 6, TA_OUT 7 .. 19
+    //   fcz_tmalign_dp                              TA_SETS 0 .. 5, TA_PAIRS 6, TA_DP_ROT 7, TA_DP_TRANS 8, TA_DP_MAP 9, TA_DP_ALIGNED 10
     dev_buf pool[POOL_COUNT];
     // PDB text / extracted data: per-entry sizes (any call), offsets (n + 1 u64) and the text of the last fcz_decompress_pdb_begin,
     // which fcz_decompress_pdb_fetch reads: live until the next fcz_decompress_pdb_begin / _sizes or fcz_extract
@@ -1733,7 +1741,7 @@ struct dense_bytes {
 // the slot of fcz_ctx::pool it goes through (table in fcz_ctx).
 struct staged_in { const void* host; size_t bytes; int slot; };
 struct staged_out { void* host; size_t bytes; int slot; };
-constexpr int STAGED_MAX = 10;
+constexpr int STAGED_MAX = 13;
 
 // The host-pointer form of an analysis: its inputs to the device, run(in, out) on the device pointers in the order of the lists (it
 // enqueues the *_rows call), the outputs back, and the stream drained. One set of rules for every analysis:
@@ -2650,6 +2658,179 @@ int fcz_tmscore_packed(fcz_ctx* ctx, const float* pos_true, const uint8_t* mask_
                        uint32_t n, uint32_t R, int layout, int slot, uint32_t levels, uint32_t iterations, const fcz_tmscore_out* out) {
     if (!tmscore_args_ok(ctx, pos_true, mask_true, pos_pred, layout, slot, R, iterations, out) || !bound_ok(true, row_off, n, R)) return FCZ_E_INVALID_ARG;
     return tmscore_host(ctx, pos_true, mask_true, pos_pred, mask_pred, row_off, true, n, R, layout, slot, levels, iterations, *out);
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------------
+// TM-align-style structural alignment of chain pairs (fcz_tmalign.h; no counterpart in the reference)
+// ------------------------------------------------------------------------------------------------
+constexpr size_t TMALIGN_DIR_BUDGET = (size_t)256 << 20;   // bytes of traceback bits a call may hold: it bounds the resident wavefronts
+
+static bool tmalign_set_ok(const fcz_chain_set* s) {
+    return s && s->pos && s->mask && (s->row_off ? true : s->rows != 0) && s->rows <= SUPERPOSE_MAX_ROWS;
+}
+
+static bool tmalign_common_ok(const fcz_ctx* ctx, const fcz_chain_set* a, const fcz_chain_set* b, const int32_t* pairs, uint32_t m, uint32_t wa, uint32_t wb,
+                              int layout, int slot) {
+    if (!ctx || !tmalign_set_ok(a) || !tmalign_set_ok(b) || (m && !pairs)) return false;
+    if (fcz_dense_width(layout) <= 0 || slot < 0 || slot >= fcz_dense_width(layout)) return false;
+    return wa >= 1 && wa <= TMALIGN_MAX_WIDTH && wb >= 1 && wb <= TMALIGN_MAX_WIDTH;
+}
+
+static bool tmalign_gap_ok(double g) { return g >= 0.0 && g <= TMALIGN_MAX_GAP; }   // (false for a NaN)
+
+static bool tmalign_params_ok(const fcz_tmalign_params* p) {
+    if (!p || p->n_gaps < 1 || p->n_gaps > TMALIGN_MAX_GAPS || p->refine > TMALIGN_MAX_ROUNDS || p->dp_rounds > TMALIGN_MAX_ROUNDS ||
+        p->iterations > TM_MAX_ITERATIONS)
+        return false;
+    for (uint32_t i = 0; i < p->n_gaps; i++) if (!tmalign_gap_ok(p->gaps[i])) return false;
+    return true;
+}
+
+static tmalign_set tmalign_set_of(const fcz_chain_set& s) { return tmalign_set{s.pos, s.mask, s.length, s.row_off, s.n, s.rows}; }
+
+// the wavefront slots of traceback bits a call gets: as many as `want`, within the budget, at least one
+static uint32_t tmalign_dir_slots(uint64_t want, uint32_t wa) {
+    const uint64_t fit = TMALIGN_DIR_BUDGET / ((size_t)wa * WAVE * sizeof(uint32_t));
+    return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(want, fit));
+}
+
+// fcz_tmalign_dev (params, o) and fcz_tmalign_dp_dev (params NULL: rot_in, trans_in, gap, o.map, o.aligned)
+static int tmalign_rows(fcz_ctx* ctx, const fcz_chain_set& a, const fcz_chain_set& b, const int32_t* pairs_dev, uint32_t m, uint32_t wa, uint32_t wb, int layout,
+                        int slot, const fcz_tmalign_params* params, const fcz_tmalign_out& o, const float* rot_in, const float* trans_in, double gap) {
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (m == 0) return FCZ_OK;
+    tmalign_args g{};
+    g.a = tmalign_set_of(a); g.b = tmalign_set_of(b);
+    g.pairs = pairs_dev; g.m = m; g.wa = wa; g.wb = wb; g.A = (uint32_t)fcz_dense_width(layout); g.slot = (uint32_t)slot;
+    g.rot = o.rot; g.trans = o.trans; g.tm = o.tm; g.tm_a = o.tm_a; g.tm_b = o.tm_b; g.aligned = o.aligned; g.rmsd = o.rmsd; g.sites_a = o.sites_a;
+    g.sites_b = o.sites_b; g.seed = o.seed; g.status = o.status; g.map = o.map; g.dev = o.dev;
+    g.rot_in = rot_in; g.trans_in = trans_in;
+    if (!params) {
+        g.n_gaps = 1; g.G[0] = (int32_t)rint(gap * (double)TMALIGN_Q);
+        g.dir_slots = tmalign_dir_slots(std::min<uint64_t>(m, (uint64_t)ctx->n_cu * 4u), wa);
+        int rc = ctx->ta_dir.ensure((size_t)g.dir_slots * wa * WAVE * sizeof(uint32_t)); if (rc) return rc;
+        g.dir = ctx->ta_dir.as<uint32_t>();
+        span_guard sg(ctx, "tmalign");
+        hipLaunchKernelGGL(k_ta_dp, dim3(g.dir_slots), dim3(BLOCK), 0, ctx->stream, g);
+        HIP_TRY(hipGetLastError());
+        return FCZ_OK;
+    }
+    g.fragments = params->fragments ? 1u : 0u; g.refine = params->refine; g.dp_rounds = params->dp_rounds; g.n_gaps = params->n_gaps;
+    for (uint32_t i = 0; i < params->n_gaps; i++) g.G[i] = (int32_t)rint(params->gaps[i] * (double)TMALIGN_Q);
+    g.levels = params->levels; g.iterations = params->iterations;
+    // the seeds are counted on the device: at most this many items of WAVES_PER_BLOCK seeds a pair, a double per seed
+    const uint64_t items = (uint64_t)m * ((ta_seed_bound(wa, wb, g.fragments) + WAVES_PER_BLOCK - 1u) / WAVES_PER_BLOCK);
+    const uint32_t search = std::max<uint32_t>(1u, tmalign_dir_slots(std::min<uint64_t>(items, (uint64_t)ctx->n_cu * 2u) * WAVES_PER_BLOCK, wa) / WAVES_PER_BLOCK);
+    const uint32_t final_blocks = (uint32_t)std::min<uint64_t>(m, (uint64_t)search * WAVES_PER_BLOCK);
+    g.dir_slots = search * WAVES_PER_BLOCK;
+    int rc = ctx->ta_dir.ensure((size_t)g.dir_slots * wa * WAVE * sizeof(uint32_t)); if (rc) return rc;
+    rc = ctx->ta_scratch.ensure(sizeof(uint64_t) * (2 * (size_t)m + 1) + sizeof(double) * WAVES_PER_BLOCK * (size_t)items + sizeof(uint32_t) * 2 * (size_t)m);
+    if (rc) return rc;
+    g.dir = ctx->ta_dir.as<uint32_t>();
+    uint64_t* counts = ctx->ta_scratch.as<uint64_t>();
+    g.item_off = counts + m;
+    g.score = reinterpret_cast<double*>(g.item_off + m + 1); g.score_cap = WAVES_PER_BLOCK * items;
+    g.nsites = reinterpret_cast<uint32_t*>(g.score + g.score_cap);
+    rc = ctx->ta_work.ensure(2 * sizeof(unsigned long long)); if (rc) return rc;
+    g.work = ctx->ta_work.as<unsigned long long>();
+    HIP_TRY(hipMemsetAsync(g.work, 0, 2 * sizeof(unsigned long long), ctx->stream));
+    span_guard sg(ctx, "tmalign");
+    hipLaunchKernelGGL(k_ta_count, dim3(std::min(grid_for(m, WAVES_PER_BLOCK), (uint32_t)ctx->n_cu * 16u)), dim3(BLOCK), 0, ctx->stream, g, counts);
+    rc = device_scan<uint64_t>(ctx, counts, g.item_off, m); if (rc) return rc;
+    hipLaunchKernelGGL(k_ta_search, dim3(search), dim3(BLOCK), 0, ctx->stream, g, 0u);
+    hipLaunchKernelGGL(k_ta_search, dim3(search), dim3(BLOCK), 0, ctx->stream, g, 1u);
+    hipLaunchKernelGGL(k_ta_final, dim3(final_blocks), dim3(BLOCK), 0, ctx->stream, g);
+    HIP_TRY(hipGetLastError());
+    return FCZ_OK;
+}
+
+// the host forms: the sets' arrays through TA_SETS .. + 5, pairs through TA_PAIRS, then (dp) rot, trans in and map, aligned out through TA_DP_*, or the
+// thirteen outputs through TA_OUT .. + 12
+static int tmalign_host(fcz_ctx* ctx, const fcz_chain_set& a, const fcz_chain_set& b, const int32_t* pairs, uint32_t m, uint32_t wa, uint32_t wb, int layout, int slot,
+                        const fcz_tmalign_params* params, const fcz_tmalign_out& o, const float* rot, const float* trans, double gap) {
+    const dense_bytes ba(a.row_off != nullptr, a.n, a.rows, layout, a.row_off ? a.row_off : a.length);
+    const dense_bytes bb(b.row_off != nullptr, b.n, b.rows, layout, b.row_off ? b.row_off : b.length);
+    const size_t c = m, w = (size_t)m * wa;
+    // an array without a byte has no copy on the device (staged_call). No kernel reads an element of it -- its chains are empty or do not exist -- so the
+    // pairs, which exist whenever m > 0, stand in where a pointer must not be NULL
+    auto sets = [&](const void* const* in, fcz_chain_set* da, fcz_chain_set* db) {
+        auto at = [&](int i) { return in[i] ? in[i] : in[6]; };   // (in[6]: the pairs, the seventh input of both lists)
+        *da = fcz_chain_set{(const float*)at(0), (const uint8_t*)at(1), a.row_off ? nullptr : (const uint32_t*)in[2], a.row_off ? (const uint32_t*)at(2) : nullptr, a.n, a.rows};
+        *db = fcz_chain_set{(const float*)at(3), (const uint8_t*)at(4), b.row_off ? nullptr : (const uint32_t*)in[5], b.row_off ? (const uint32_t*)at(5) : nullptr, b.n, b.rows};
+    };
+    if (!params)
+        return staged_call(ctx, {{a.pos, ba.pos, TA_SETS}, {a.mask, ba.mask, TA_SETS + 1}, {a.row_off ? a.row_off : a.length, ba.bound, TA_SETS + 2}, {b.pos, bb.pos, TA_SETS + 3},
+                             {b.mask, bb.mask, TA_SETS + 4},
+                                 {b.row_off ? b.row_off : b.length, bb.bound, TA_SETS + 5}, {pairs, 8 * c, TA_PAIRS}, {rot, 36 * c, TA_DP_ROT}, {trans, 12 * c, TA_DP_TRANS}},
+                           {{o.map, 4 * w, TA_DP_MAP}, {o.aligned, 4 * c, TA_DP_ALIGNED}}, [&](const void* const* in, void* const* out) {
+            fcz_chain_set da, db; sets(in, &da, &db);
+            fcz_tmalign_out d{}; d.map = (int32_t*)out[0]; d.aligned = (int32_t*)out[1];
+            return tmalign_rows(ctx, da, db, (const int32_t*)in[6], m, wa, wb, layout, slot, nullptr, d, (const float*)in[7], (const float*)in[8], gap);
+        });
+    return staged_call(ctx, {{a.pos, ba.pos, TA_SETS}, {a.mask, ba.mask, TA_SETS + 1}, {a.row_off ? a.row_off : a.length, ba.bound, TA_SETS + 2}, {b.pos, bb.pos, TA_SETS + 3},
+                             {b.mask, bb.mask, TA_SETS + 4},
+                             {b.row_off ? b.row_off : b.length, bb.bound, TA_SETS + 5}, {pairs, 8 * c, TA_PAIRS}},
+                       {{o.rot, 36 * c, TA_OUT}, {o.trans, 12 * c, TA_OUT + 1}, {o.tm, 4 * c, TA_OUT + 2}, {o.tm_a, 4 * c, TA_OUT + 3}, {o.tm_b, 4 * c, TA_OUT + 4},
+                        {o.aligned, 4 * c, TA_OUT + 5}, {o.rmsd, 4 * c, TA_OUT + 6}, {o.sites_a, 4 * c, TA_OUT + 7}, {o.sites_b, 4 * c, TA_OUT + 8}, {o.seed, 4 * c, TA_OUT + 9},
+                        {o.status, 4 * c, TA_OUT + 10}, {o.map, 4 * w, TA_OUT + 11}, {o.dev, 4 * w, TA_OUT + 12}},
+                       [&](const void* const* in, void* const* out) {
+        fcz_chain_set da, db; sets(in, &da, &db);
+        const fcz_tmalign_out d{(float*)out[0], (float*)out[1], (float*)out[2], (float*)out[3], (float*)out[4], (int32_t*)out[5], (float*)out[6], (int32_t*)out[7],
+                                (int32_t*)out[8], (int32_t*)out[9], (int32_t*)out[10], (int32_t*)out[11], (float*)out[12]};
+        return tmalign_rows(ctx, da, db, (const int32_t*)in[6], m, wa, wb, layout, slot, params, d, nullptr, nullptr, 0.0);
+    });
+}
+
+extern "C" {
+
+uint64_t fcz_tmalign_seeds(uint32_t sites_a, uint32_t sites_b, uint32_t fragments) { return ta_seed_count(sites_a, sites_b, fragments); }
+
+int fcz_tmalign_seed(uint32_t sites_a, uint32_t sites_b, uint32_t fragments, uint64_t seed, int32_t* kind, int32_t* shift, uint32_t* start_a, uint32_t* start_b,
+                     uint32_t* length) {
+    if (!kind || !shift || !start_a || !start_b || !length || seed >= ta_seed_count(sites_a, sites_b, fragments)) return FCZ_E_INVALID_ARG;
+    ta_seed_what(sites_a, sites_b, seed, kind, shift, start_a, start_b, length);
+    return FCZ_OK;
+}
+
+int fcz_tmalign_last_work(fcz_ctx* ctx, uint64_t* dps, uint64_t* cells) {
+    if (!ctx || !dps || !cells) return FCZ_E_INVALID_ARG;
+    unsigned long long w[2] = {0, 0};
+    if (ctx->ta_work.p) {
+        HIP_TRY(hipSetDevice(ctx->device));
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        HIP_TRY(hipMemcpy(w, ctx->ta_work.p, sizeof w, hipMemcpyDeviceToHost));
+    }
+    *dps = w[0]; *cells = w[1];
+    return FCZ_OK;
+}
+
+int fcz_tmalign_dev(fcz_ctx* ctx, const fcz_chain_set* a_dev, const fcz_chain_set* b_dev, const int32_t* pairs_dev, uint32_t m, uint32_t wa, uint32_t wb, int layout,
+                    int slot, const fcz_tmalign_params* params, const fcz_tmalign_out* out_dev) {
+    if (!tmalign_common_ok(ctx, a_dev, b_dev, pairs_dev, m, wa, wb, layout, slot) || !tmalign_params_ok(params) || !out_dev || !out_dev->rot || !out_dev->trans)
+        return FCZ_E_INVALID_ARG;
+    return tmalign_rows(ctx, *a_dev, *b_dev, pairs_dev, m, wa, wb, layout, slot, params, *out_dev, nullptr, nullptr, 0.0);
+}
+
+int fcz_tmalign_dp_dev(fcz_ctx* ctx, const fcz_chain_set* a_dev, const fcz_chain_set* b_dev, const int32_t* pairs_dev, uint32_t m, uint32_t wa, uint32_t wb, int layout,
+                       int slot, const float* rot_dev, const float* trans_dev, double gap, int32_t* map_dev, int32_t* aligned_dev) {
+    if (!tmalign_common_ok(ctx, a_dev, b_dev, pairs_dev, m, wa, wb, layout, slot) || !tmalign_gap_ok(gap) || !rot_dev || !trans_dev || !map_dev) return FCZ_E_INVALID_ARG;
+    fcz_tmalign_out o{}; o.map = map_dev; o.aligned = aligned_dev;
+    return tmalign_rows(ctx, *a_dev, *b_dev, pairs_dev, m, wa, wb, layout, slot, nullptr, o, rot_dev, trans_dev, gap);
+}
+
+int fcz_tmalign(fcz_ctx* ctx, const fcz_chain_set* a, const fcz_chain_set* b, const int32_t* pairs, uint32_t m, uint32_t wa, uint32_t wb, int layout, int slot,
+                const fcz_tmalign_params* params, const fcz_tmalign_out* out) {
+    if (!tmalign_common_ok(ctx, a, b, pairs, m, wa, wb, layout, slot) || !tmalign_params_ok(params) || !out || !out->rot || !out->trans) return FCZ_E_INVALID_ARG;
+    return tmalign_host(ctx, *a, *b, pairs, m, wa, wb, layout, slot, params, *out, nullptr, nullptr, 0.0);
+}
+
+int fcz_tmalign_dp(fcz_ctx* ctx, const fcz_chain_set* a, const fcz_chain_set* b, const int32_t* pairs, uint32_t m, uint32_t wa, uint32_t wb, int layout, int slot,
+                   const float* rot, const float* trans, double gap, int32_t* map, int32_t* aligned) {
+    if (!tmalign_common_ok(ctx, a, b, pairs, m, wa, wb, layout, slot) || !tmalign_gap_ok(gap) || !rot || !trans || !map) return FCZ_E_INVALID_ARG;
+    fcz_tmalign_out o{}; o.map = map; o.aligned = aligned;
+    return tmalign_host(ctx, *a, *b, pairs, m, wa, wb, layout, slot, nullptr, o, rot, trans, gap);
 }
 
 }  // extern "C"

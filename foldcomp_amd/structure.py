@@ -996,6 +996,28 @@ class CTmScoreOut(ctypes.Structure):
     _fields_ = CSuperposeOut._fields_ + [("seed", ctypes.c_void_p), ("selected", ctypes.c_void_p)]
 
 
+class CChainSet(ctypes.Structure):
+    """fcz_chain_set (include/fcz_hip.h): one set of chains of the alignment calls, padded (length or None, rows = L) or packed (row_off, rows = R)"""
+    _fields_ = [("pos", ctypes.c_void_p), ("mask", ctypes.c_void_p), ("length", ctypes.c_void_p), ("row_off", ctypes.c_void_p),
+                ("n", ctypes.c_uint32), ("rows", ctypes.c_uint32)]
+
+
+class CTmAlignParams(ctypes.Structure):
+    """fcz_tmalign_params (include/fcz_hip.h)"""
+    _fields_ = [("fragments", ctypes.c_uint32), ("refine", ctypes.c_uint32), ("dp_rounds", ctypes.c_uint32), ("n_gaps", ctypes.c_uint32),
+                ("gaps", ctypes.c_double * 4), ("levels", ctypes.c_uint32), ("iterations", ctypes.c_uint32)]
+
+
+TM_ALIGN_OUTPUTS = (("rot", "float32", (3, 3)), ("trans", "float32", (3,)), ("tm", "float32", ()), ("tm_a", "float32", ()), ("tm_b", "float32", ()),
+                    ("aligned", "int32", ()), ("rmsd", "float32", ()), ("sites_a", "int32", ()), ("sites_b", "int32", ()), ("seed", "int32", ()),
+                    ("status", "int32", ()), ("map", "int32", "wa"), ("dev", "float32", "wa"))
+
+
+class CTmAlignOut(ctypes.Structure):
+    """fcz_tmalign_out (include/fcz_hip.h): the thirteen outputs of the alignment calls in the order of TM_ALIGN_OUTPUTS; all but rot and trans may be None"""
+    _fields_ = [(k, ctypes.c_void_p) for k, _, _ in TM_ALIGN_OUTPUTS]
+
+
 class CDenseIn(ctypes.Structure):
     """fcz_dense_in (include/fcz_hip.h): dense tensors + per-chain header fields handed to the undense / compress_dense calls"""
     _fields_ = [("pos", ctypes.c_void_p), ("mask", ctypes.c_void_p), ("aatype", ctypes.c_void_p), ("length", ctypes.c_void_p),

@@ -54,9 +54,9 @@ import numpy as np
 from . import _lib, api, fczfile
 from ._aa_tables import RES1
 from .codec import ANGLE_COLUMNS, WIDTH_LAYOUTS, Codec, dense_layout
-from .structure import CAtomsOut, CDenseIn, CDenseOut, CLddtAtomsOut, CPackedOut, CSuperposeOut, CTmScoreOut, CViolationsOut
+from .structure import CAtomsOut, CDenseIn, CDenseOut, CLddtAtomsOut, CPackedOut, CSuperposeOut, CTmScoreOut, CViolationsOut, CChainSet, CTmAlignOut, CTmAlignParams, TM_ALIGN_OUTPUTS
 
-__all__ = ["decode_tensors", "encode_tensors", "decode_angles", "crop_starts", "neighbor_graph", "rigid_frames", "lddt", "lddt_atoms", "superpose", "tm_score", "apply_transform",
+__all__ = ["decode_tensors", "encode_tensors", "decode_angles", "crop_starts", "neighbor_graph", "rigid_frames", "lddt", "lddt_atoms", "superpose", "tm_score", "tm_align", "apply_transform",
            "backbone_hbonds", "secondary_structure", "solvent_accessibility", "violations"]
 
 
@@ -809,6 +809,84 @@ def tm_score(pred, true, *, atom="CA", apply: bool = False, iterations: int = 20
     It is NOT differentiable. Cost: the seeds times a handful of superpositions per chain, where superpose does one.
     atom, shapes, iterations and levels are checked first, without torch or a device (api.check_tm_score)."""
     return _superpose(pred, true, atom, apply, codec, "tm_score", (iterations, levels))
+
+
+def tm_align(a, b=None, pairs=None, *, atom="CA", fragments: bool = True, refine: int = 4, dp_rounds: int = 20, gaps=(0.6, 0.0), iterations: int = 20,
+             levels=None, transform=None, codec: Optional[Codec] = None) -> dict:
+    """two sets of chains as dense tensors on the GPU -> for every requested pair of DIFFERENT chains a TM-align-style structural
+    alignment: which residues of a correspond to which of b, the rigid motion that lays a onto b, and the TM-scores.
+
+    lddt, superpose and tm_score compare two tensors row for row. Here the chains differ in length and sequence and the
+    correspondence is what is looked for. `a` and `b` are dicts as decode_tensors / tensor_batches return, each padded (pos
+    [n, L, A, 3], mask, optionally length) or packed (pos [R, A, 3], mask, cu_seqlens), each in its own form, of one layout; b=None:
+    b is a. pairs: int32 [m, 2] on the device, (chain of a, chain of b); None: every i < j of a (b=None) or every (i, j). A site is
+    a row inside its chain whose mask at `atom` is set and whose coordinates are finite. Chains of at most 1024 rows.
+    The search (the definition, deterministic to the bit: include/fcz_hip.h, fcz_tmalign_dev): gapless shifts and, with fragments,
+    pairs of fragments seed a transform; a Needleman-Wunsch over the scores 1 / (1 + d^2 / d0^2) with free end gaps and the gap
+    penalties `gaps` in turn gives an alignment, its TM-maximising fit (refine rounds) the next transform, for up to dp_rounds rounds;
+    the best alignment then gets tm_score's full search (iterations, levels). Per pair:
+        rot [m, 3, 3], trans [m, 3] float32   x_b ~ rot @ x_a + trans
+        tm [m] float32                        the TM-score normalised by the shorter chain; tm_a, tm_b: by a's and by b's sites.
+                                              LOWER BOUNDS of what TM-align prints (no secondary-structure seed, one search for all three)
+        aligned, sites_a, sites_b [m] int32   the aligned pairs and the sites of the two chains; rmsd [m] over the pairs
+        map [m, wa] int32                     for every row of chain a the chain-relative row of b it is aligned with, -1 elsewhere
+        dev [m, wa] float32                   the deviation of an aligned row; wa = L, or the longest chain of a packed a
+        seed [m] int32                        the winning seed; status [m] int32: 0, 1 (a chain longer than its width), 2 (no such chain)
+        pairs [m, 2] int32                    the pairs that were aligned
+    transform=(rot [m, 3, 3], trans [m, 3]) runs ONE dynamic programme per pair from the caller's transforms instead, with the gap
+    gaps[0] (fcz_tmalign_dp_dev), and returns map, aligned and pairs alone; numpy reproduces that integer DP bit for bit.
+    It is NOT differentiable. The arguments are checked first, without torch or a device (api.check_tm_align)."""
+    what = "tm_align"
+    da = dict(a) if isinstance(a, dict) else {"pos": a}
+    same = b is None
+    db = da if same else (dict(b) if isinstance(b, dict) else {"pos": b})
+    _need(what, da, of=" of a")
+    _need(what, db, of=" of b")
+    shape_a, shape_b = tuple(getattr(da["pos"], "shape", ())), tuple(getattr(db["pos"], "shape", ()))
+    tshapes = None if transform is None else tuple(tuple(getattr(t, "shape", ())) for t in transform)
+    pshape = None if pairs is None else tuple(getattr(pairs, "shape", ()))
+    width = lambda d, s: s[1] if len(s) == 4 and d.get("cu_seqlens") is None else None
+    checked = api.check_tm_align(atom, shape_a, shape_b, width(da, shape_a), width(db, shape_b), pshape, fragments, refine, dp_rounds, gaps, iterations, levels, tshapes)
+    slot, frag, refine, dp_rounds, gs, iterations, levels = checked
+    packed = lambda d, s: d.get("cu_seqlens") is not None and len(s) == 3
+    xa = _dense_checked(what, "Codec.tm_align", codec, da, shape_a, packed(da, shape_a), "full", False)
+    xb = xa if same else _dense_checked(what, "Codec.tm_align", xa.codec, db, shape_b, packed(db, shape_b), "full", False)
+    torch, dev = xa.torch, xa.dev
+
+    def width_of(x):
+        if not x.is_packed:
+            return max(x.rows, 1)
+        return max(int((x.bound[1:] - x.bound[:-1]).max()) if x.n else 1, 1)
+    wa, wb = width_of(xa), width_of(xb)
+    api.check_tm_align(atom, shape_a, shape_b, wa, wb)
+    if pairs is None:
+        pairs = torch.from_numpy(api.tm_align_pairs(xa.n, xb.n, same)).to(dev)
+    else:
+        pairs = _on_device(torch, what, dev, "pairs", pairs, pshape, (torch.int32,))
+    m = int(pairs.shape[0])
+    sets = [CChainSet(x.pos.data_ptr(), x.mask.data_ptr(), None if x.is_packed else _ptr(x.bound), _ptr(x.bound) if x.is_packed else None, x.n, x.rows)
+            for x in (xa, xb)]
+    c = xa.codec
+    if transform is not None:
+        rot = _on_device(torch, what, dev, "rot", transform[0], (m, 3, 3), (torch.float32,))
+        trans = _on_device(torch, what, dev, "trans", transform[1], (m, 3), (torch.float32,))
+        out = dict(map=torch.full((m, wa), -1, dtype=torch.int32, device=dev), aligned=torch.zeros((m,), dtype=torch.int32, device=dev), pairs=pairs)
+        if m:
+            torch.cuda.current_stream(dev).synchronize()
+            _lib.check(c.lib.fcz_tmalign_dp_dev(c.ctx, ctypes.byref(sets[0]), ctypes.byref(sets[1]), pairs.data_ptr(), m, wa, wb, xa.lay, slot, rot.data_ptr(),
+                                                trans.data_ptr(), gs[0], out["map"].data_ptr(), out["aligned"].data_ptr()), "fcz_tmalign_dp_dev")
+            c.synchronize()
+        return out
+    out = {k: torch.empty((m,) + ((wa,) if tail == "wa" else tail), dtype=getattr(torch, dt), device=dev) for k, dt, tail in TM_ALIGN_OUTPUTS}
+    if m:
+        par = CTmAlignParams(frag, refine, dp_rounds, len(gs), (ctypes.c_double * 4)(*gs), levels, iterations)
+        s = CTmAlignOut(*(out[k].data_ptr() for k, _, _ in TM_ALIGN_OUTPUTS))
+        torch.cuda.current_stream(dev).synchronize()
+        _lib.check(c.lib.fcz_tmalign_dev(c.ctx, ctypes.byref(sets[0]), ctypes.byref(sets[1]), pairs.data_ptr(), m, wa, wb, xa.lay, slot, ctypes.byref(par),
+                                         ctypes.byref(s)), "fcz_tmalign_dev")
+        c.synchronize()
+    out["pairs"] = pairs
+    return out
 
 
 def _superpose(pred, true, atom, apply, codec, what, search):

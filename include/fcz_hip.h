@@ -895,6 +895,119 @@ int fcz_tmscore_packed(fcz_ctx* ctx, const float* pos_true, const uint8_t* mask_
                        const uint8_t* mask_pred, const uint32_t* row_off, uint32_t n, uint32_t R, int layout, int slot,
                        uint32_t levels, uint32_t iterations, const fcz_tmscore_out* out);
 
+/* ---- TM-align-style structural alignment of chain pairs ------------------------------------------------- */
+/* Everything above compares two tensors row for row. These calls compare two DIFFERENT chains, of different lengths and with the
+ * correspondence unknown: for every requested pair (chain i of set a, chain j of set b) they find an alignment -- a monotone partial
+ * map of a's residues onto b's -- by a dynamic programme that alternates with superposition, and return it with the rigid motion that
+ * lays a onto b (x_b ~ rot @ x_a + trans) and the TM-scores normalised by either chain. The reference has no such output. The search
+ * follows TM-align's structure but is a definition of its own, given here; it is deterministic, and an implementation is checked
+ * against it, not against any program. There is no secondary-structure seed and no search per normalisation, so tm, tm_a and tm_b are
+ * LOWER BOUNDS of what TM-align prints.
+ * A chain set is padded (pos [n][L][A][3], mask [n][L][A], length [n] or NULL, rows = L) or packed (pos [R][A][3], mask [R][A],
+ * row_off [n + 1], rows = R); row_off != NULL means packed. Each set has its own n, form and rows; layout and slot are shared; b may be
+ * the same set as a. pairs [m][2] int32 holds chain indices. A chain's rows are those of fcz_superpose_dev (a packed range is clamped
+ * to the R rows that exist, one that runs backwards is empty). A SITE is fcz_superpose_dev's site restricted to one tensor: a row
+ * inside the chain whose mask is set at the slot and whose three coordinates are finite. Sa and Sb are the sites of the two chains,
+ * numbered in row order; Lmin = min(Sa, Sb). wa and wb are the widths: L for a padded set, the largest chain (max_seqlen) for a packed
+ * one; both at most FCZ_TMALIGN_MAX_WIDTH. status [m]: 0; 1 for a pair with a chain of more rows than its width; 2 for a pair with an
+ * index outside either set. For status 1 and 2 the outputs are the empty result (Lmin = 0 below) and no row of the pair is read.
+ * All arithmetic is float64, every operation rounded, no FMA; fits and deviations are fcz_superpose_dev's expressions.
+ *   (1) fit of an alignment with P pairs: fcz_tmscore_dev's "one seed" procedure with the pairs in the part of the sites, taken in the
+ *       order of a's site number (lane l of the wavefront adds a's sites l, l + 64, .., a site without a partner adds nothing, then the
+ *       xor-butterfly), the selection starting as all P pairs, tm = (1 / Lmin) sum_pairs 1 / (1 + (dev / d0)^2) with d0 = d0(Lmin),
+ *       d_search from that d0, and at most `refine` rounds of re-selection after round 0 (fewer than min(3, Lmin) selected: the cut
+ *       grows as there). The round with the largest tm gives the fit; of equal ones the earliest.
+ *   (2) one DP, given (R, t) and a gap g: Q = 65536; d2_ij = |R a_i + t - b_j|^2 in fcz_superpose_dev's order of operations;
+ *       q_ij = (int32) floor(Q / (1 + d2_ij / (d0 d0))), 0 for a non-finite d2_ij; G = (int32) rint(g Q) (ties to even).
+ *       H[0][j] = H[i][0] = 0 and H[i][j] = max(H[i-1][j-1] + q_ij, H[i-1][j] - G, H[i][j-1] - G) in int32 for i = 1 .. Sa, j = 1 .. Sb
+ *       (with widths up to 1024 and g <= 16, |H| <= 2^30 + 2^20: it cannot overflow). End gaps are free: the end cell is the first
+ *       maximum of H over (0 .. Sa, Sb) in ascending i, then over (Sa, 0 .. Sb - 1) in ascending j. Trace back from it until i = 0 or
+ *       j = 0, at every cell taking the diagonal if H[i][j] == H[i-1][j-1] + q_ij, else up if H[i][j] == H[i-1][j] - G, else left. The
+ *       diagonal steps (i, j) align a's site i - 1 with b's site j - 1. Being integer, the DP is exact in whatever order its cells
+ *       are evaluated, and a caller reproduces it bit for bit from the same (R, t).
+ *   (3) DP iteration from a transform: cur = the transform; for each g of gaps, in order, for up to dp_rounds rounds: the alignment is
+ *       DP(cur, g); stop this g if it has fewer than min(3, Lmin) pairs or equals the previous alignment of this g; otherwise fit it
+ *       (1) -- a CANDIDATE -- and cur becomes that fit. cur carries over to the next g.
+ *   (4) seeds, numbered in this order. Gapless: every shift k with pairs (i, i + k) and an overlap of at least
+ *       max(Lmin / 2, min(Lmin, 5)) pairs, in ascending k (k = max(..) - Sa .. Sb - max(..)); each is one fit of the overlap with round 0
+ *       only, and a candidate. Then ONE seed: the best gapless seed's transform (largest tm, of equal ones the lowest k) runs (3). Then,
+ *       when `fragments` is set: f = min(Lmin, clamp(Lmin / 5, 8, 32)); the starts in each chain are 0, f, 2 f, .. while start + f <= S,
+ *       then S - f if it is not the last taken; each pair of starts (a-major) gives the least-squares fit of the f pairs
+ *       (sa + u, sb + u), which is no candidate itself, then (3). fcz_tmalign_seeds / fcz_tmalign_seed restate this on the host.
+ *   (5) the candidate with the largest float64 tm wins; of equal ones the lowest seed, then the earliest (g, round). On its alignment
+ *       run fcz_tmscore_dev's full search over the P pairs (levels, iterations; fragments are ranges of pair numbers), normalised by
+ *       Lmin as in (1). The result is the search's fit if its tm is strictly larger than the candidate's, else the candidate's fit: the
+ *       final tm is never below any candidate's.
+ * Outputs per pair, floats rounded once from float64: rot [m][3][3], trans [m][3] (required); tm (by Lmin); tm_a, tm_b: the same pairs
+ * and transform with d0 and the divisor of Sa and of Sb; aligned = P; rmsd = sqrt(sum dev^2 / P) over the pairs; sites_a, sites_b;
+ * seed: the winning candidate's seed; status; map [m][wa] int32: for every row of chain a the chain-relative row of b it is aligned
+ * with, -1 elsewhere; dev [m][wa] float32: the deviation of an aligned row, 0 elsewhere. Lmin = 0: the identity, zeros, seed 0, map all
+ * -1. One and two sites: what fcz_superpose_dev does for them. All but rot / trans may be NULL. Every byte of every output given is
+ * written; nothing outside the inputs is read, whatever pairs, length or row_off hold. The result depends on neither the launch
+ * geometry nor the form of either set. Scratch in the ctx, sized on the host from m, wa and wb alone: a double per seed and 256 wa
+ * bytes of traceback bits per resident wavefront. Enqueued on the ctx stream, no synchronisation. FCZ_E_INVALID_ARG with nothing
+ * launched: NULL ctx / a / b / params / out / rot / trans, a set without pos or mask, a padded set with rows == 0, rows above
+ * 2^31 - 1, NULL pairs with m > 0, unknown layout, slot outside it, wa or wb of 0 or above FCZ_TMALIGN_MAX_WIDTH,
+ * n_gaps outside 1 .. 4, a gap that is not in [0, 16], refine or dp_rounds above 64, iterations above 64. m == 0: FCZ_OK.
+ * FCZ_E_NOMEM: no room for the scratch. The time goes to a group of its own, "tmalign". */
+#define FCZ_TMALIGN_MAX_WIDTH 1024
+typedef struct fcz_chain_set {
+    const float*    pos;
+    const uint8_t*  mask;
+    const uint32_t* length;     /* padded: [n] or NULL */
+    const uint32_t* row_off;    /* packed: [n + 1]; NULL: the set is padded */
+    uint32_t        n;
+    uint32_t        rows;       /* L (padded) or R (packed) */
+} fcz_chain_set;
+typedef struct fcz_tmalign_params {
+    uint32_t fragments;         /* 0 / 1; default 1 */
+    uint32_t refine;            /* default 4 */
+    uint32_t dp_rounds;         /* default 20 */
+    uint32_t n_gaps;            /* default 2 */
+    double   gaps[4];           /* default 0.6, 0.0 */
+    uint32_t levels;            /* of the final search; 0: all */
+    uint32_t iterations;        /* of the final search; default 20 */
+} fcz_tmalign_params;
+typedef struct fcz_tmalign_out {
+    float*   rot;               /* [m][3][3] */
+    float*   trans;             /* [m][3] */
+    float*   tm;                /* [m] optional, as all below */
+    float*   tm_a;
+    float*   tm_b;
+    int32_t* aligned;
+    float*   rmsd;
+    int32_t* sites_a;
+    int32_t* sites_b;
+    int32_t* seed;
+    int32_t* status;
+    int32_t* map;               /* [m][wa] */
+    float*   dev;               /* [m][wa] */
+} fcz_tmalign_out;
+uint64_t fcz_tmalign_seeds(uint32_t sites_a, uint32_t sites_b, uint32_t fragments);   /* the seeds of a pair; needs no device */
+/* what the output `seed` stands for: kind 0 a gapless shift, 1 the DP iteration from the best gapless seed, 2 a fragment pair; shift
+ * (kinds 0 and 2: start_b - start_a), the first site in a and in b and the number of pairs of the seed's fit (kind 1: zeros).
+ * FCZ_E_INVALID_ARG for a seed the pair does not have. Needs no device. */
+int fcz_tmalign_seed(uint32_t sites_a, uint32_t sites_b, uint32_t fragments, uint64_t seed, int32_t* kind, int32_t* shift,
+                     uint32_t* start_a, uint32_t* start_b, uint32_t* length);
+int fcz_tmalign_dev(fcz_ctx* ctx, const fcz_chain_set* a_dev, const fcz_chain_set* b_dev, const int32_t* pairs_dev, uint32_t m,
+                    uint32_t wa, uint32_t wb, int layout, int slot, const fcz_tmalign_params* params, const fcz_tmalign_out* out_dev);
+/* What the last fcz_tmalign_dev / fcz_tmalign call of this ctx did in step (3): the dynamic programmes it ran (the winner's second
+ * run included) and the sum of their Sa * Sb cells; zeros before the first call. Waits for the ctx stream. For measurements. */
+int fcz_tmalign_last_work(fcz_ctx* ctx, uint64_t* dps, uint64_t* cells);
+/* The DP of (2) alone, once per pair, from caller-given float32 transforms rot [m][3][3], trans [m][3] (promoted exactly to float64),
+ * with d0(Lmin) and the gap `gap`: map [m][wa] (required) and aligned [m] (may be NULL) as above; a pair with a status gets a map of
+ * -1 and aligned 0. For callers who superposed some other way. Refusals as above (NULL rot / trans / map). */
+int fcz_tmalign_dp_dev(fcz_ctx* ctx, const fcz_chain_set* a_dev, const fcz_chain_set* b_dev, const int32_t* pairs_dev, uint32_t m,
+                       uint32_t wa, uint32_t wb, int layout, int slot, const float* rot_dev, const float* trans_dev, double gap,
+                       int32_t* map_dev, int32_t* aligned_dev);
+/* Host-pointer conveniences: the sets' arrays, pairs and the outputs on the host (the structs themselves always are), staged through
+ * the ctx; synchronous. */
+int fcz_tmalign(fcz_ctx* ctx, const fcz_chain_set* a, const fcz_chain_set* b, const int32_t* pairs, uint32_t m, uint32_t wa,
+                uint32_t wb, int layout, int slot, const fcz_tmalign_params* params, const fcz_tmalign_out* out);
+int fcz_tmalign_dp(fcz_ctx* ctx, const fcz_chain_set* a, const fcz_chain_set* b, const int32_t* pairs, uint32_t m, uint32_t wa,
+                   uint32_t wb, int layout, int slot, const float* rot, const float* trans, double gap, int32_t* map,
+                   int32_t* aligned);
+
 /* ---- torsion-angle tensors: the record's internal coordinates, no reconstruction ------------------------ */
 /* What Foldcomp::decompress dequantises before it places an atom (src/foldcomp.cpp:784-804: the backbone torsions and bond angles of
  * every packed word; :338-369 for the side-chain torsion bytes) and the FCZ branch of foldcomp.cxx's get_data returns as Python lists
@@ -1250,7 +1363,7 @@ int fcz_check(const uint8_t* entry, uint64_t len);
  * group since the last reset: "compress_sizes", "compress_index", "compress_angles", "compress_pack",
  * "decompress_sizes", "decompress_backbone", "decompress_index", "decompress_sidechain", "pdb_sizes", "pdb_format", "extract_sizes", "extract",
  * "ingest_parse", "ingest_parse_cif", "ingest_rows_cif", "ingest_frags", "ingest_fill", "inflate", "dense", "undense" (the counting and the fill
- * kernel of fcz_undense_dev: two launches per call), "angles" (fcz_angles_dev), "knn" (fcz_knn_dev and fcz_knn_packed_dev), "lddt" (fcz_lddt_dev and fcz_lddt_packed_dev), "lddt_atoms" (fcz_lddt_atoms_dev and fcz_lddt_atoms_packed_dev), "superpose" (fcz_superpose_dev, fcz_superpose_apply_dev and their packed forms), "tmscore" (fcz_tmscore_dev and fcz_tmscore_packed_dev), "frames" (fcz_frames_dev). Every other packed or windowed entry point is timed under the
+ * kernel of fcz_undense_dev: two launches per call), "angles" (fcz_angles_dev), "knn" (fcz_knn_dev and fcz_knn_packed_dev), "lddt" (fcz_lddt_dev and fcz_lddt_packed_dev), "lddt_atoms" (fcz_lddt_atoms_dev and fcz_lddt_atoms_packed_dev), "superpose" (fcz_superpose_dev, fcz_superpose_apply_dev and their packed forms), "tmscore" (fcz_tmscore_dev and fcz_tmscore_packed_dev), "tmalign" (fcz_tmalign_dev and fcz_tmalign_dp_dev), "frames" (fcz_frames_dev). Every other packed or windowed entry point is timed under the
  * group of its padded form: fcz_dense_packed_dev and fcz_dense_window_dev under "dense", fcz_undense_packed_dev under "undense",
  * fcz_angles_packed_dev and fcz_angles_window_dev under "angles". */
 int  fcz_ctx_enable_timing(fcz_ctx* ctx, int enable);

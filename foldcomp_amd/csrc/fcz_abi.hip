@@ -93,7 +93,7 @@ struct timed_span { std::string name; hipEvent_t a, b; };
 // never live together (table in fcz_ctx). REC_*: uploaded FCZ records (n + 1 u64 offsets), their res_off / atom_off (n + 1 u32) and
 // the fcz_atoms_out decoded from them; FILES_*: structure files of an ingest call; BATCH_IN / DENSE_IN / DENSE_OUT: first of the 13
 // arrays of a fcz_chain_batch, the 10 of a fcz_dense_in (slot 3, length, holds row_off [n + 1] in the packed form), the 6 of a
-// fcz_dense_out, the 7 of a fcz_packed_out (PACKED_OUT .. PACKED_OUT_LAST), in the struct's order; ANGLES_OUT: the angles, their mask and
+// fcz_dense_out in the struct's order, DENSE_CHAIN_INDEX: the chain_index a fcz_packed_out adds to them; ANGLES_OUT: the angles, their mask and
 // (windowed form) aatype; WINDOW_START: the n u32 starts of a windowed host call; KEPT_*: the records a *_begin call leaves for its fetch
 // (C + 1 u64 offsets, the bytes, C i32 status); LDDT_PRED: pos and mask of the second tensor batch of fcz_lddt, LDDT_OUT: score, pairs, hits;
 // DSSP_OUT: acc_index, acc_energy, don_index, don_energy, ss, ss_mask of fcz_dssp; SASA_POINTS: the directions of fcz_sasa, SASA_OUT: sasa_points, sasa, sasa_mask;
@@ -106,9 +106,9 @@ enum { REC_BLOB, REC_OFF, REC_RES_OFF, REC_ATOM_OFF, REC_X, REC_Y, REC_Z, REC_BF
        FILES_TEXT = 0, FILES_OFF, FILES_NAMES, FILES_NAME_OFF, FILES_STEM_LEN, BATCH_IN = 0, DENSE_IN = 0, LDDT_PRED = 4, DENSE_OUT = 10, LDDT_OUT = 10, SUPERPOSE_OUT = 10, DSSP_OUT = 10,
        SASA_POINTS = 4, SASA_OUT = 10,
        APPLY_ROT = 10, APPLY_TRANS, APPLY_OUT,
-       PACKED_OUT = 10, ANGLES_OUT = 10, KEPT_OFF = 13, KEPT_BYTES, KEPT_STATUS, PACKED_OUT_LAST, WINDOW_START = PACKED_OUT_LAST, TM_SEED, TM_SELECTED,
+       ANGLES_OUT = 10, KEPT_OFF = 13, KEPT_BYTES, KEPT_STATUS, DENSE_CHAIN_INDEX, WINDOW_START = DENSE_CHAIN_INDEX, TM_SEED, TM_SELECTED,
        VIOL_OUT = 10, LDDTA_OUT = 10, TA_SETS = 0, TA_PAIRS = 6, TA_OUT = 7, TA_DP_ROT = 7, TA_DP_TRANS, TA_DP_MAP, TA_DP_ALIGNED, VIOL_OUT_LAST = 19, POOL_COUNT };
-static_assert(POOL_COUNT == VIOL_OUT_LAST + 1 && LDDTA_OUT + 6 <= POOL_COUNT && TM_SELECTED < POOL_COUNT && TA_OUT + 13 <= POOL_COUNT && TA_SETS + 6 == TA_PAIRS &&
+static_assert(POOL_COUNT == VIOL_OUT_LAST + 1 && DENSE_OUT + 6 == DENSE_CHAIN_INDEX && LDDTA_OUT + 6 <= POOL_COUNT && TM_SELECTED < POOL_COUNT && TA_OUT + 13 <= POOL_COUNT && TA_SETS + 6 == TA_PAIRS &&
               TA_PAIRS < TA_OUT && TA_DP_ALIGNED < POOL_COUNT, "the last name of the enum sizes fcz_ctx::pool");
 
 // what the device reports to the host in the middle of a call: one pinned allocation, a member per reader
@@ -145,7 +145,8 @@ struct fcz_ctx {
     dev_buf tile_work;
     // decompress: the totals and the length order computed by fcz_decompress_sizes_dev are reused by the
     // fcz_decompress_batch_dev call that follows on the same entries
-    const void* sized_blob = nullptr; const void* sized_off = nullptr; uint32_t sized_n = 0, sized_R = 0, sized_maxseg = 0, sized_maxnseg = 0, sized_nlong = 0;
+    struct { const void* blob = nullptr; const void* off = nullptr; uint32_t n = 0; } sizes_key;
+    sizes_totals sizes_memo{};
     bool sizes_fresh = false;
     dev_buf cnt;        // decompress: 2 x n u32 counts (residues, atoms) + n i32 status (cnt_status) + n u32 segment info; kept for the sizes memo
     dev_buf fwd;        // decompress: per-group ring of forward atoms (one segment deep)
@@ -171,7 +172,7 @@ struct fcz_ctx {
     //   fcz_decompress_pdb_begin / _sizes           REC_* 0 .. 8                                (pdb_text, pdb_bytes)
     //   fcz_extract                                 REC_BLOB, REC_OFF
     //   fcz_decompress_dense                        REC_* 0 .. 8, DENSE_OUT 10 .. 15
-    //   fcz_decompress_dense_packed                 REC_* 0 .. 8, PACKED_OUT 10 .. 16
+    //   fcz_decompress_dense_packed                 REC_* 0 .. 8, DENSE_OUT 10 .. 15, DENSE_CHAIN_INDEX 16
     //   fcz_decompress_angles[_packed]              REC_* 0 .. 3, ANGLES_OUT 10 .. 11
     //   fcz_decompress_dense_window                 REC_* 0 .. 8, DENSE_OUT 10 .. 15, WINDOW_START 16
     //   fcz_decompress_angles_window                REC_* 0 .. 3, ANGLES_OUT 10 .. 12, WINDOW_START 16
@@ -326,6 +327,81 @@ int fetch_resident(fcz_ctx* ctx, uint32_t C, uint64_t n_bytes, uint64_t* out_off
     return FCZ_OK;
 }
 
+// An array of a host-pointer call: the caller's pointer (NULL: an input that is absent, an output that is not wanted), its bytes, and
+// the slot of fcz_ctx::pool it goes through (table in fcz_ctx).
+struct staged_in { const void* host; size_t bytes; int slot; };
+struct staged_out { void* host; size_t bytes; int slot; };
+constexpr int STAGED_MAX = 13;
+
+// The three steps of staging, for the rules below. Room for every input, then their upload; dev[] gets the device pointers in the
+// list's order. floor: what a present array is given at least (fcz_compress_dense_begin).
+int stage_in(fcz_ctx* ctx, std::initializer_list<staged_in> in, const void** dev, size_t floor = 0) {
+    int rc, i = 0;
+    for (const staged_in& a : in) {
+        const size_t nb = a.host ? std::max(a.bytes, floor) : 0;
+        if ((rc = ctx->pool[a.slot].ensure(nb))) return rc;
+        dev[i++] = nb ? ctx->pool[a.slot].p : nullptr;
+    }
+    for (const staged_in& a : in)
+        if (a.host && a.bytes) HIP_TRY(hipMemcpyAsync(ctx->pool[a.slot].p, a.host, a.bytes, hipMemcpyHostToDevice, ctx->stream));
+    return FCZ_OK;
+}
+// room for every wanted output; dev[] gets the device pointers in the list's order
+int reserve_out(fcz_ctx* ctx, std::initializer_list<staged_out> out, void** dev) {
+    int rc, i = 0;
+    for (const staged_out& o : out) {
+        if ((rc = ctx->pool[o.slot].ensure(o.host ? o.bytes : 0))) return rc;
+        dev[i++] = o.host ? ctx->pool[o.slot].p : nullptr;
+    }
+    return FCZ_OK;
+}
+// the wanted outputs back to the caller (enqueued: the caller drains the stream)
+int fetch_out(fcz_ctx* ctx, std::initializer_list<staged_out> out) {
+    for (const staged_out& o : out)
+        if (o.host && o.bytes) HIP_TRY(hipMemcpyAsync(o.host, ctx->pool[o.slot].p, o.bytes, hipMemcpyDeviceToHost, ctx->stream));
+    return FCZ_OK;
+}
+
+// The host-pointer form of an analysis: its inputs to the device, run(in, out) on the device pointers in the order of the lists (it
+// enqueues the *_rows call), the outputs back, and the stream drained. The host forms of the record decode put the same three steps
+// behind a preamble of their own (the sizes pass, which decides what there is to write) and say where they differ. One set of rules:
+//   * A call whose wanted outputs have no byte returns FCZ_OK with nothing enqueued: there is nothing it could write. That is rows == 0
+//     for the per-row analyses, and rows == 0 with n == 0 for violations, superpose and TM-score: they have per-chain outputs, so chains
+//     without a row (packed, R == 0) go on and get the counters and the transform of an empty chain.
+//   * An array of zero bytes is not copied, in either direction: hipMemcpyAsync is given no NULL or unallocated pointer.
+//   * An input that is absent or has zero bytes reaches run() as NULL. Absent is what the *_rows functions take NULL to mean (no
+//     length, no aatype, no second mask); of a zero-byte array no kernel reads an element -- every chain is clamped to the rows that
+//     exist and a launch without chains (n == 0: the fill kernels) reads no per-chain array such as the transforms of apply.
+//   * An output that is not wanted reaches run() as NULL, which is what the optional members of the out structs mean.
+//   * Every buffer is made large enough before the first copy is enqueued, so FCZ_E_NOMEM leaves nothing in flight.
+template <class Run>
+int staged_call(fcz_ctx* ctx, std::initializer_list<staged_in> in, std::initializer_list<staged_out> out, Run run) {
+    HIP_TRY(hipSetDevice(ctx->device));
+    claim_staging(ctx);
+    size_t wanted = 0;
+    for (const staged_out& o : out) wanted += o.host ? o.bytes : 0;
+    if (wanted == 0) return FCZ_OK;
+    const void* din[STAGED_MAX]; void* dout[STAGED_MAX];
+    int rc;
+    if ((rc = reserve_out(ctx, out, dout)) || (rc = stage_in(ctx, in, din)) || (rc = run(din, dout)) || (rc = fetch_out(ctx, out))) return rc;
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return FCZ_OK;
+}
+
+// the rows a dense or an angle call writes: n x L, n x L from the entry's start on, or the R residues back to back
+enum rows_form { ROWS_PADDED, ROWS_WINDOW, ROWS_PACKED };
+
+// per-entry byte counts into ctx->pdb_size by launch(sizes), which is not called for n == 0, then their exclusive prefix into off_dev[n + 1]
+template <class Launch> int sizes_then_scan(fcz_ctx* ctx, uint32_t n, const char* span, uint64_t* off_dev, Launch launch) {
+    HIP_TRY(hipSetDevice(ctx->device));
+    int rc = ctx->pdb_size.ensure(sizeof(uint64_t) * (size_t)std::max<uint32_t>(n, 1)); if (rc) return rc;
+    span_guard g(ctx, span);
+    if (n) launch(ctx->pdb_size.as<uint64_t>());
+    if ((rc = device_scan<uint64_t>(ctx, ctx->pdb_size.as<uint64_t>(), off_dev, n))) return rc;
+    HIP_TRY(hipGetLastError());
+    return FCZ_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -424,14 +500,10 @@ int fcz_ctx_synchronize(fcz_ctx* c) {
 static int pdb_sizes_impl(fcz_ctx* ctx, const uint8_t* blob_dev, const uint64_t* off_dev, uint32_t n, const uint32_t* res_off_dev,
                           const uint32_t* atom_off_dev, const fcz_atoms_out* atoms_dev, uint32_t pad, uint64_t* text_off_dev) {
     if (!ctx || !blob_dev || !off_dev || !res_off_dev || !atom_off_dev || !atoms_out_ok(atoms_dev) || !text_off_dev) return FCZ_E_INVALID_ARG;
-    HIP_TRY(hipSetDevice(ctx->device));
-    int rc = ctx->pdb_size.ensure(sizeof(uint64_t) * (size_t)std::max<uint32_t>(n, 1)); if (rc) return rc;
-    span_guard g(ctx, "pdb_sizes");
-    if (n) hipLaunchKernelGGL(k_pdb_sizes, dim3(grid_for(n, WAVES_PER_BLOCK)), dim3(BLOCK), 0, ctx->stream, blob_dev, off_dev, n,
-                              res_off_dev, atom_off_dev, *atoms_dev, pad, ctx->pdb_size.as<uint64_t>());
-    if ((rc = device_scan<uint64_t>(ctx, ctx->pdb_size.as<uint64_t>(), text_off_dev, n))) return rc;
-    HIP_TRY(hipGetLastError());
-    return FCZ_OK;
+    return sizes_then_scan(ctx, n, "pdb_sizes", text_off_dev, [&](uint64_t* sizes) {
+        hipLaunchKernelGGL(k_pdb_sizes, dim3(grid_for(n, WAVES_PER_BLOCK)), dim3(BLOCK), 0, ctx->stream, blob_dev, off_dev, n, res_off_dev, atom_off_dev,
+                           *atoms_dev, pad, sizes);
+    });
 }
 int fcz_pdb_sizes_dev(fcz_ctx* ctx, const uint8_t* blob_dev, const uint64_t* off_dev, uint32_t n, const uint32_t* res_off_dev,
                       const uint32_t* atom_off_dev, const fcz_atoms_out* atoms_dev, uint64_t* text_off_dev) {
@@ -479,6 +551,21 @@ static int decode_records(fcz_ctx* ctx, uint32_t n, int alt_order, const fcz_ato
                                     ctx->pool[REC_ATOM_OFF].as<uint32_t>(), alt_order, dv);
 }
 
+// What the host forms that size what they upload begin with: the records and the sizes pass over them (upload_records: *R residues,
+// *M atoms), the per-entry status into the caller's array (may be NULL), res_off [n + 1] into res_off -- NULL: into a vector of its
+// own when *longest, the residues of the longest entry, is asked for (may be NULL), else not at all -- and the stream drained.
+static int upload_sized(fcz_ctx* ctx, const uint8_t* blob, const uint64_t* off, uint32_t n, int32_t* status, uint32_t* res_off, uint32_t* R, uint32_t* M,
+                        uint32_t* longest = nullptr) {
+    int rc = upload_records(ctx, blob, off, n, R, M); if (rc) return rc;
+    std::vector<uint32_t> own(res_off || !longest ? 0 : (size_t)n + 1);
+    if (!res_off && longest) res_off = own.data();
+    if (res_off) HIP_TRY(hipMemcpyAsync(res_off, ctx->pool[REC_RES_OFF].p, sizeof(uint32_t) * ((size_t)n + 1), hipMemcpyDeviceToHost, ctx->stream));
+    if (status) HIP_TRY(hipMemcpyAsync(status, cnt_status(ctx, n), sizeof(int32_t) * n, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    if (longest) { *longest = 0; for (uint32_t i = 0; i < n; i++) *longest = std::max(*longest, res_off[i + 1] - res_off[i]); }
+    return FCZ_OK;
+}
+
 // Host-pointer convenience: FCZ entries in, PDB text out, everything in between on the device. begin() leaves the text in
 // the ctx and reports the per-entry text offsets; fetch() copies it out.
 static int pdb_begin_impl(fcz_ctx* ctx, const uint8_t* blob, const uint64_t* off, uint32_t n, int alt_order, uint64_t* text_off,
@@ -491,8 +578,7 @@ static int pdb_begin_impl(fcz_ctx* ctx, const uint8_t* blob, const uint64_t* off
     ctx->pdb_bytes = 0;
     if (n == 0) { text_off[0] = 0; return FCZ_OK; }
     uint32_t R = 0, M = 0;
-    int rc = upload_records(ctx, blob, off, n, &R, &M); if (rc) return rc;
-    if (status) HIP_TRY(hipMemcpyAsync(status, cnt_status(ctx, n), sizeof(int32_t) * n, hipMemcpyDeviceToHost, ctx->stream));
+    int rc = upload_sized(ctx, blob, off, n, status, nullptr, &R, &M); if (rc) return rc;
     fcz_atoms_out dv;
     if ((rc = stage_atoms(ctx, R, M, false, &dv))) return rc;
     if ((rc = ctx->pdb_off.ensure(sizeof(uint64_t) * ((size_t)n + 1)))) return rc;
@@ -544,14 +630,9 @@ int fcz_extract_sizes(const uint8_t* blob, const uint64_t* off, uint32_t n, int 
 int fcz_extract_sizes_dev(fcz_ctx* ctx, const uint8_t* blob_dev, const uint64_t* off_dev, uint32_t n, int mode, int digits,
                           uint64_t* data_off_dev) {
     if (!ctx || !blob_dev || !off_dev || !data_off_dev || !extract_args_ok(mode, digits)) return FCZ_E_INVALID_ARG;
-    HIP_TRY(hipSetDevice(ctx->device));
-    int rc = ctx->pdb_size.ensure(sizeof(uint64_t) * (size_t)std::max<uint32_t>(n, 1)); if (rc) return rc;
-    span_guard g(ctx, "extract_sizes");
-    if (n) hipLaunchKernelGGL(k_extract_sizes, dim3(grid_for(n, BLOCK)), dim3(BLOCK), 0, ctx->stream, blob_dev, off_dev, n, mode, digits,
-                              ctx->pdb_size.as<uint64_t>());
-    if ((rc = device_scan<uint64_t>(ctx, ctx->pdb_size.as<uint64_t>(), data_off_dev, n))) return rc;
-    HIP_TRY(hipGetLastError());
-    return FCZ_OK;
+    return sizes_then_scan(ctx, n, "extract_sizes", data_off_dev, [&](uint64_t* sizes) {
+        hipLaunchKernelGGL(k_extract_sizes, dim3(grid_for(n, BLOCK)), dim3(BLOCK), 0, ctx->stream, blob_dev, off_dev, n, mode, digits, sizes);
+    });
 }
 
 int fcz_extract_dev(fcz_ctx* ctx, const uint8_t* blob_dev, const uint64_t* off_dev, uint32_t n, int mode, int digits,
@@ -1192,25 +1273,23 @@ int fcz_decompress_sizes_dev(fcz_ctx* ctx, const uint8_t* blob_dev, const uint64
     if (total_res) *total_res = tot.residues;
     if (total_atoms) *total_atoms = tot.atoms;
     // the fcz_decompress_batch_dev call that follows on the same entries reuses the totals and the length order
-    ctx->sized_blob = blob_dev; ctx->sized_off = off_dev; ctx->sized_n = n;
-    ctx->sized_R = tot.residues; ctx->sized_maxseg = tot.max_seg; ctx->sized_maxnseg = tot.max_nseg; ctx->sized_nlong = tot.n_long;
+    ctx->sizes_key = {blob_dev, off_dev, n};
+    ctx->sizes_memo = tot;
     ctx->sizes_fresh = true;
     return FCZ_OK;
 }
 
 // Totals and length order for a batch call: taken from the preceding sizes call on the same entries, else recomputed.
-static int ensure_sizes(fcz_ctx* ctx, const uint8_t* blob_dev, const uint64_t* off_dev, uint32_t n, uint32_t* total_res, uint32_t* max_seg_len,
-                        uint32_t* max_nseg, uint32_t* n_long) {
-    if (ctx->sizes_fresh && ctx->sized_blob == blob_dev && ctx->sized_off == off_dev && ctx->sized_n == n) {
+static int ensure_sizes(fcz_ctx* ctx, const uint8_t* blob_dev, const uint64_t* off_dev, uint32_t n, sizes_totals* tot) {
+    if (ctx->sizes_fresh && ctx->sizes_key.blob == blob_dev && ctx->sizes_key.off == off_dev && ctx->sizes_key.n == n) {
         ctx->sizes_fresh = false;   // single use: the records may be rewritten before the next call
-        *total_res = ctx->sized_R; *max_seg_len = ctx->sized_maxseg; *max_nseg = ctx->sized_maxnseg; *n_long = ctx->sized_nlong;
+        *tot = ctx->sizes_memo;
         return FCZ_OK;
     }
     ctx->sizes_fresh = false;   // the pass below overwrites what a remembered sizes call left (length order, residue codes)
     int rc = ctx->sizes_res_off.ensure(sizeof(uint32_t) * ((size_t)n + 1)); if (rc) return rc;
     if ((rc = run_entry_sizes(ctx, blob_dev, off_dev, n, ctx->sizes_res_off.as<uint32_t>(), nullptr))) return rc;
-    const sizes_totals& tot = ctx->pinned->sizes;
-    *total_res = tot.residues; *max_seg_len = tot.max_seg; *max_nseg = tot.max_nseg; *n_long = tot.n_long;
+    *tot = ctx->pinned->sizes;
     return FCZ_OK;
 }
 
@@ -1220,9 +1299,10 @@ int fcz_decompress_batch_dev(fcz_ctx* ctx, const uint8_t* blob_dev, const uint64
     if (!ctx || !blob_dev || !off_dev || !res_off_dev || !atom_off_dev || !atoms_out_ok(out_dev, false)) return FCZ_E_INVALID_ARG;
     HIP_TRY(hipSetDevice(ctx->device));
     if (n == 0) return FCZ_OK;
-    uint32_t R = 0, max_seg = 0, max_nseg = 0, n_long = 0;
-    int rc = ensure_sizes(ctx, blob_dev, off_dev, n, &R, &max_seg, &max_nseg, &n_long);
+    sizes_totals tot;
+    int rc = ensure_sizes(ctx, blob_dev, off_dev, n, &tot);
     if (rc) return rc;
+    const uint32_t R = tot.residues, max_seg = tot.max_seg, max_nseg = tot.max_nseg, n_long = tot.n_long;
     if (R == 0) return FCZ_OK;
     rc = ctx->bb.ensure(sizeof(v3) * 3 * (size_t)R); if (rc) return rc;
     const uint32_t* perm = ctx->len_perm.as<uint32_t>();
@@ -1345,24 +1425,19 @@ int fcz_decompress_batch(fcz_ctx* ctx, const uint8_t* blob, const uint64_t* off,
     int rc;
     const uint32_t R = res_off[n], M = atom_off[n];
     fcz_atoms_out dv;
-    if ((rc = ctx->pool[REC_RES_OFF].ensure(sizeof(uint32_t) * ((size_t)n + 1))) || (rc = ctx->pool[REC_ATOM_OFF].ensure(sizeof(uint32_t) * ((size_t)n + 1))) ||
-        (rc = stage_atoms(ctx, R, M, true, &dv)) || (rc = upload_records(ctx, blob, off, n)))
+    const size_t offs = sizeof(uint32_t) * ((size_t)n + 1), fM = sizeof(float) * (size_t)M, fR = sizeof(float) * (size_t)R;
+    const void* unused[2];
+    // room for the atoms by stage_atoms, not reserve_out: the decode takes no NULL x, y, z or bfac_res, so an array without a byte (no
+    // record decodes) still gets its 16 bytes. Only res_code and atom_code reach it as NULL when they are not wanted.
+    if ((rc = stage_atoms(ctx, R, M, true, &dv)) || (rc = upload_records(ctx, blob, off, n)) ||
+        (rc = stage_in(ctx, {{res_off, offs, REC_RES_OFF}, {atom_off, offs, REC_ATOM_OFF}}, unused)))
         return rc;
-    HIP_TRY(hipMemcpyAsync(ctx->pool[REC_RES_OFF].p, res_off, sizeof(uint32_t) * ((size_t)n + 1), hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(ctx->pool[REC_ATOM_OFF].p, atom_off, sizeof(uint32_t) * ((size_t)n + 1), hipMemcpyHostToDevice, ctx->stream));
     if (!out->res_code) dv.res_code = nullptr;
     if (!out->atom_code) dv.atom_code = nullptr;
-    if ((rc = decode_records(ctx, n, alt_order, &dv))) return rc;
-    if (M) {
-        HIP_TRY(hipMemcpyAsync(out->x, dv.x, sizeof(float) * (size_t)M, hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(hipMemcpyAsync(out->y, dv.y, sizeof(float) * (size_t)M, hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(hipMemcpyAsync(out->z, dv.z, sizeof(float) * (size_t)M, hipMemcpyDeviceToHost, ctx->stream));
-        if (out->atom_code) HIP_TRY(hipMemcpyAsync(out->atom_code, dv.atom_code, (size_t)M, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    if (R) {
-        HIP_TRY(hipMemcpyAsync(out->bfac_res, dv.bfac_res, sizeof(float) * (size_t)R, hipMemcpyDeviceToHost, ctx->stream));
-        if (out->res_code) HIP_TRY(hipMemcpyAsync(out->res_code, dv.res_code, (size_t)R, hipMemcpyDeviceToHost, ctx->stream));
-    }
+    if ((rc = decode_records(ctx, n, alt_order, &dv)) ||
+        (rc = fetch_out(ctx, {{out->x, fM, REC_X}, {out->y, fM, REC_Y}, {out->z, fM, REC_Z}, {out->bfac_res, fR, REC_BFAC}, {out->res_code, R, REC_RES_CODE},
+                              {out->atom_code, M, REC_ATOM_CODE}})))
+        return rc;
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return FCZ_OK;
 }
@@ -1404,27 +1479,31 @@ static dense_table dense_make_table(int layout, int alt_order) {
     return t;
 }
 
-// fcz_dense_dev (k_dense) and fcz_dense_window_dev (window: k_dense_window with start_dev, which may be NULL)
+// fcz_dense_dev (k_dense), fcz_dense_window_dev (k_dense_window with start_dev, which may be NULL) and fcz_dense_packed_dev (k_dense_packed:
+// no L, and chain_index_dev beside the arrays the three share)
 static int dense_rows(fcz_ctx* ctx, const uint8_t* blob_dev, const uint64_t* off_dev, uint32_t n, const uint32_t* res_off_dev,
-                      const uint32_t* atom_off_dev, const fcz_atoms_out* atoms_dev, int alt_order, int layout, uint32_t L, bool window,
-                      const uint32_t* start_dev, const fcz_dense_out* out_dev) {
+                      const uint32_t* atom_off_dev, const fcz_atoms_out* atoms_dev, int alt_order, int layout, rows_form form, uint32_t L,
+                      const uint32_t* start_dev, const fcz_dense_out* out_dev, int32_t* chain_index_dev) {
     if (!ctx || !blob_dev || !off_dev || !res_off_dev || !atom_off_dev || !atoms_out_ok(atoms_dev) || !out_dev) return FCZ_E_INVALID_ARG;
-    if (fcz_dense_width(layout) < 0 || L == 0 || !out_dev->pos || !out_dev->mask) return FCZ_E_INVALID_ARG;
+    if (fcz_dense_width(layout) < 0 || (L == 0 && form != ROWS_PACKED) || !out_dev->pos || !out_dev->mask) return FCZ_E_INVALID_ARG;
     HIP_TRY(hipSetDevice(ctx->device));
     if (n == 0) return FCZ_OK;
     const dense_table tab = dense_make_table(layout, alt_order ? 1 : 0);
     const dense_args g{off_dev, res_off_dev, atom_off_dev, atoms_dev->x, atoms_dev->y, atoms_dev->z, atoms_dev->bfac_res, atoms_dev->res_code,
                        out_dev->pos, out_dev->mask, out_dev->aatype, out_dev->plddt, out_dev->res_index, out_dev->length};
-    const uint32_t tiles_per_entry = grid_for(L, DN_TILE);
+    // packed: the tiles are counted on the device (res_off[n] / DN_TILE), at most 1 024 per entry, a record holds 65 535 residues
+    const uint32_t tiles_per_entry = form == ROWS_PACKED ? 1024u : grid_for(L, DN_TILE);
     const uint64_t n_tiles = (uint64_t)n * tiles_per_entry;                  // every index behind it is 64-bit: n * L * A may pass 2^32
     const uint32_t blocks = (uint32_t)std::min<uint64_t>(n_tiles, (uint64_t)ctx->n_cu * 32u);
     span_guard sg(ctx, "dense");
     dispatch_layout(layout, [&](auto A) {
-        if (window)
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_dense_window<decltype(A)::value>), dim3(blocks), dim3(BLOCK), 0, ctx->stream, blob_dev, g, start_dev, n, L,
-                               tiles_per_entry, n_tiles, tab);
+        constexpr int W = decltype(A)::value;
+        if (form == ROWS_PACKED)
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_dense_packed<W>), dim3(blocks), dim3(BLOCK), 0, ctx->stream, blob_dev, g, chain_index_dev, n, tab);
+        else if (form == ROWS_WINDOW)
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_dense_window<W>), dim3(blocks), dim3(BLOCK), 0, ctx->stream, blob_dev, g, start_dev, n, L, tiles_per_entry, n_tiles, tab);
         else
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_dense<decltype(A)::value>), dim3(blocks), dim3(BLOCK), 0, ctx->stream, blob_dev, g, n, L, tiles_per_entry, n_tiles, tab);
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_dense<W>), dim3(blocks), dim3(BLOCK), 0, ctx->stream, blob_dev, g, n, L, tiles_per_entry, n_tiles, tab);
     });
     HIP_TRY(hipGetLastError());
     return FCZ_OK;
@@ -1433,137 +1512,80 @@ static int dense_rows(fcz_ctx* ctx, const uint8_t* blob_dev, const uint64_t* off
 int fcz_dense_dev(fcz_ctx* ctx, const uint8_t* blob_dev, const uint64_t* off_dev, uint32_t n, const uint32_t* res_off_dev,
                   const uint32_t* atom_off_dev, const fcz_atoms_out* atoms_dev, int alt_order, int layout, uint32_t L,
                   const fcz_dense_out* out_dev) {
-    return dense_rows(ctx, blob_dev, off_dev, n, res_off_dev, atom_off_dev, atoms_dev, alt_order, layout, L, false, nullptr, out_dev);
+    return dense_rows(ctx, blob_dev, off_dev, n, res_off_dev, atom_off_dev, atoms_dev, alt_order, layout, ROWS_PADDED, L, nullptr, out_dev, nullptr);
 }
 
 int fcz_dense_window_dev(fcz_ctx* ctx, const uint8_t* blob_dev, const uint64_t* off_dev, uint32_t n, const uint32_t* res_off_dev,
                          const uint32_t* atom_off_dev, const fcz_atoms_out* atoms_dev, int alt_order, int layout, uint32_t L,
                          const uint32_t* start_dev, const fcz_dense_out* out_dev) {
-    return dense_rows(ctx, blob_dev, off_dev, n, res_off_dev, atom_off_dev, atoms_dev, alt_order, layout, L, true, start_dev, out_dev);
+    return dense_rows(ctx, blob_dev, off_dev, n, res_off_dev, atom_off_dev, atoms_dev, alt_order, layout, ROWS_WINDOW, L, start_dev, out_dev, nullptr);
+}
+
+// the arrays a fcz_packed_out shares with a fcz_dense_out (NULL: none)
+static fcz_dense_out padded_part(const fcz_packed_out* o) {
+    return o ? fcz_dense_out{o->pos, o->mask, o->aatype, o->plddt, o->res_index, o->length} : fcz_dense_out{};
 }
 
 int fcz_dense_packed_dev(fcz_ctx* ctx, const uint8_t* blob_dev, const uint64_t* off_dev, uint32_t n, const uint32_t* res_off_dev,
                          const uint32_t* atom_off_dev, const fcz_atoms_out* atoms_dev, int alt_order, int layout, const fcz_packed_out* out_dev) {
-    if (!ctx || !blob_dev || !off_dev || !res_off_dev || !atom_off_dev || !atoms_out_ok(atoms_dev) || !out_dev) return FCZ_E_INVALID_ARG;
-    if (fcz_dense_width(layout) < 0 || !out_dev->pos || !out_dev->mask) return FCZ_E_INVALID_ARG;
-    HIP_TRY(hipSetDevice(ctx->device));
-    if (n == 0) return FCZ_OK;
-    const dense_table tab = dense_make_table(layout, alt_order ? 1 : 0);
-    const dense_args g{off_dev, res_off_dev, atom_off_dev, atoms_dev->x, atoms_dev->y, atoms_dev->z, atoms_dev->bfac_res, atoms_dev->res_code,
-                       out_dev->pos, out_dev->mask, out_dev->aatype, out_dev->plddt, out_dev->res_index, out_dev->length};
-    // the tiles are counted on the device (res_off[n] / DN_TILE): at most 1 024 per entry, a record holds 65 535 residues
-    const uint32_t blocks = (uint32_t)std::min<uint64_t>((uint64_t)n * 1024u, (uint64_t)ctx->n_cu * 32u);
-    span_guard sg(ctx, "dense");
-    dispatch_layout(layout, [&](auto A) {
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_dense_packed<decltype(A)::value>), dim3(blocks), dim3(BLOCK), 0, ctx->stream, blob_dev, g, out_dev->chain_index, n, tab);
-    });
-    HIP_TRY(hipGetLastError());
-    return FCZ_OK;
+    const fcz_dense_out d = padded_part(out_dev);
+    return dense_rows(ctx, blob_dev, off_dev, n, res_off_dev, atom_off_dev, atoms_dev, alt_order, layout, ROWS_PACKED, 0u, nullptr, out_dev ? &d : nullptr,
+                      out_dev ? out_dev->chain_index : nullptr);
 }
 
-int fcz_decompress_dense_packed(fcz_ctx* ctx, const uint8_t* blob, const uint64_t* off, uint32_t n, int layout, uint32_t* R_out, uint32_t* row_off,
-                                const fcz_packed_out* out, int32_t* status) {
-    const int A = fcz_dense_width(layout);
-    if (!ctx || !blob || !off || A < 0 || (!out && !R_out) || (out && (!out->pos || !out->mask))) return FCZ_E_INVALID_ARG;
+// The three host-pointer forms. width_out is L_out (padded, windowed) or R_out (packed), row_off and chain_index are the packed form's;
+// windowed: the starts of the host array `start`, which may be NULL. Staged by the rules of staged_call.
+static int decompress_dense_impl(fcz_ctx* ctx, const uint8_t* blob, const uint64_t* off, uint32_t n, int layout, rows_form form, uint32_t L,
+                                 const uint32_t* start, uint32_t* width_out, uint32_t* row_off, const fcz_dense_out* out, int32_t* chain_index,
+                                 int32_t* status) {
+    const bool packed = form == ROWS_PACKED;
+    const size_t A = (size_t)fcz_dense_width(layout);
+    if (!ctx || !blob || !off || fcz_dense_width(layout) < 0 || (!out && !width_out) || (out && (!out->pos || !out->mask))) return FCZ_E_INVALID_ARG;
     HIP_TRY(hipSetDevice(ctx->device));
     claim_staging(ctx);
-    if (R_out) *R_out = 0;
+    if (width_out && (packed || n == 0)) *width_out = packed ? 0u : L;
     if (n == 0) { if (row_off) row_off[0] = 0; return FCZ_OK; }
-    uint32_t R = 0, M = 0;
-    int rc = upload_records(ctx, blob, off, n, &R, &M); if (rc) return rc;
-    if (row_off) HIP_TRY(hipMemcpyAsync(row_off, ctx->pool[REC_RES_OFF].p, sizeof(uint32_t) * ((size_t)n + 1), hipMemcpyDeviceToHost, ctx->stream));
-    if (status) HIP_TRY(hipMemcpyAsync(status, cnt_status(ctx, n), sizeof(int32_t) * n, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    if (R_out) *R_out = R;
+    uint32_t R = 0, M = 0, longest = 0;
+    int rc = upload_sized(ctx, blob, off, n, status, row_off, &R, &M, packed ? nullptr : &longest); if (rc) return rc;
+    if (!packed && L == 0) L = longest;
+    if (width_out) *width_out = packed ? R : L;
     if (!out) return FCZ_OK;
-    if (R == 0) {               // no entry decodes: no row
-        if (out->length) memset(out->length, 0, sizeof(uint32_t) * n);
-        return FCZ_OK;
-    }
-    fcz_atoms_out dv;
-    if ((rc = stage_atoms(ctx, R, M, false, &dv)) || (rc = decode_records(ctx, n, 0, &dv))) return rc;
-    const size_t rows = R;
-    const size_t bytes[7] = {rows * A * 3 * sizeof(float), rows * A, out->aatype ? rows : 0, out->plddt ? rows * sizeof(float) : 0,
-                             out->res_index ? rows * sizeof(int32_t) : 0, out->chain_index ? rows * sizeof(int32_t) : 0, out->length ? sizeof(uint32_t) * n : 0};
-    void* host[7] = {out->pos, out->mask, out->aatype, out->plddt, out->res_index, out->chain_index, out->length};
-    void* dev[7];
-    for (int i = 0; i < 7; i++) {
-        dev[i] = nullptr;
-        if (!bytes[i]) continue;
-        if ((rc = ctx->pool[PACKED_OUT + i].ensure(bytes[i]))) return rc;
-        dev[i] = ctx->pool[PACKED_OUT + i].p;
-    }
-    const fcz_packed_out dd{(float*)dev[0], (uint8_t*)dev[1], (uint8_t*)dev[2], (float*)dev[3], (int32_t*)dev[4], (int32_t*)dev[5], (uint32_t*)dev[6]};
-    rc = fcz_dense_packed_dev(ctx, ctx->pool[REC_BLOB].as<uint8_t>(), ctx->pool[REC_OFF].as<uint64_t>(), n, ctx->pool[REC_RES_OFF].as<uint32_t>(),
-                              ctx->pool[REC_ATOM_OFF].as<uint32_t>(), &dv, 0, layout, &dd);
-    if (rc) return rc;
-    for (int i = 0; i < 7; i++)
-        if (bytes[i]) HIP_TRY(hipMemcpyAsync(host[i], dev[i], bytes[i], hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return FCZ_OK;
-}
-
-// fcz_decompress_dense and fcz_decompress_dense_window (window: the starts of the host array `start`, which may be NULL)
-static int decompress_dense_impl(fcz_ctx* ctx, const uint8_t* blob, const uint64_t* off, uint32_t n, int layout, uint32_t L, bool window,
-                                 const uint32_t* start, uint32_t* L_out, const fcz_dense_out* out, int32_t* status) {
-    const int A = fcz_dense_width(layout);
-    if (!ctx || !blob || !off || A < 0 || (!out && !L_out) || (out && (!out->pos || !out->mask))) return FCZ_E_INVALID_ARG;
-    HIP_TRY(hipSetDevice(ctx->device));
-    claim_staging(ctx);
-    if (n == 0) { if (L_out) *L_out = L; return FCZ_OK; }
-    uint32_t R = 0, M = 0;
-    int rc = upload_records(ctx, blob, off, n, &R, &M); if (rc) return rc;
-    std::vector<uint32_t> res_off((size_t)n + 1);
-    HIP_TRY(hipMemcpyAsync(res_off.data(), ctx->pool[REC_RES_OFF].p, sizeof(uint32_t) * ((size_t)n + 1), hipMemcpyDeviceToHost, ctx->stream));
-    if (status) HIP_TRY(hipMemcpyAsync(status, cnt_status(ctx, n), sizeof(int32_t) * n, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    uint32_t longest = 0;
-    for (uint32_t i = 0; i < n; i++) longest = std::max(longest, res_off[i + 1] - res_off[i]);
-    if (L == 0) L = longest;
-    if (L_out) *L_out = L;
-    if (!out) return FCZ_OK;
-    if (L == 0) {               // no entry decodes and no width was asked for: the padded arrays are empty
+    const size_t rows = packed ? (size_t)R : (size_t)n * L;
+    if (rows == 0) {            // no entry decodes and (padded) no width was asked for: the arrays are empty
         if (out->length) memset(out->length, 0, sizeof(uint32_t) * n);
         return FCZ_OK;
     }
     fcz_atoms_out dv;
     if ((rc = stage_atoms(ctx, R, M, false, &dv))) return rc;
-    if (R && (rc = decode_records(ctx, n, 0, &dv))) return rc;
-    const size_t rows = (size_t)n * L;
-    const size_t bytes[6] = {rows * A * 3 * sizeof(float), rows * A, out->aatype ? rows : 0, out->plddt ? rows * sizeof(float) : 0,
-                             out->res_index ? rows * sizeof(int32_t) : 0, out->length ? sizeof(uint32_t) * n : 0};
-    void* host[6] = {out->pos, out->mask, out->aatype, out->plddt, out->res_index, out->length};
-    void* dev[6];
-    for (int i = 0; i < 6; i++) {
-        dev[i] = nullptr;
-        if (!bytes[i]) continue;
-        if ((rc = ctx->pool[DENSE_OUT + i].ensure(bytes[i]))) return rc;
-        dev[i] = ctx->pool[DENSE_OUT + i].p;
-    }
-    const fcz_dense_out dd{(float*)dev[0], (uint8_t*)dev[1], (uint8_t*)dev[2], (float*)dev[3], (int32_t*)dev[4], (uint32_t*)dev[5]};
-    const uint32_t* start_dev = nullptr;
-    if (window && start) {
-        if ((rc = ctx->pool[WINDOW_START].ensure(sizeof(uint32_t) * n))) return rc;
-        HIP_TRY(hipMemcpyAsync(ctx->pool[WINDOW_START].p, start, sizeof(uint32_t) * n, hipMemcpyHostToDevice, ctx->stream));
-        start_dev = ctx->pool[WINDOW_START].as<uint32_t>();
-    }
-    rc = dense_rows(ctx, ctx->pool[REC_BLOB].as<uint8_t>(), ctx->pool[REC_OFF].as<uint64_t>(), n, ctx->pool[REC_RES_OFF].as<uint32_t>(),
-                    ctx->pool[REC_ATOM_OFF].as<uint32_t>(), &dv, 0, layout, L, window, start_dev, &dd);
-    if (rc) return rc;
-    for (int i = 0; i < 6; i++)
-        if (bytes[i]) HIP_TRY(hipMemcpyAsync(host[i], dev[i], bytes[i], hipMemcpyDeviceToHost, ctx->stream));
+    if (R && (rc = decode_records(ctx, n, 0, &dv))) return rc;             // R == 0 (padded): the dense kernel still writes every row as padding
+    const std::initializer_list<staged_out> outs = {{out->pos, rows * A * 3 * sizeof(float), DENSE_OUT}, {out->mask, rows * A, DENSE_OUT + 1},
+        {out->aatype, rows, DENSE_OUT + 2}, {out->plddt, rows * sizeof(float), DENSE_OUT + 3}, {out->res_index, rows * sizeof(int32_t), DENSE_OUT + 4},
+        {out->length, sizeof(uint32_t) * n, DENSE_OUT + 5}, {chain_index, rows * sizeof(int32_t), DENSE_CHAIN_INDEX}};
+    void* d[7]; const void* start_dev = nullptr;
+    if ((rc = reserve_out(ctx, outs, d)) || (form == ROWS_WINDOW && (rc = stage_in(ctx, {{start, sizeof(uint32_t) * n, WINDOW_START}}, &start_dev)))) return rc;
+    const fcz_dense_out dd{(float*)d[0], (uint8_t*)d[1], (uint8_t*)d[2], (float*)d[3], (int32_t*)d[4], (uint32_t*)d[5]};
+    if ((rc = dense_rows(ctx, ctx->pool[REC_BLOB].as<uint8_t>(), ctx->pool[REC_OFF].as<uint64_t>(), n, ctx->pool[REC_RES_OFF].as<uint32_t>(),
+                         ctx->pool[REC_ATOM_OFF].as<uint32_t>(), &dv, 0, layout, form, L, (const uint32_t*)start_dev, &dd, (int32_t*)d[6])) ||
+        (rc = fetch_out(ctx, outs)))
+        return rc;
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return FCZ_OK;
 }
 
 int fcz_decompress_dense(fcz_ctx* ctx, const uint8_t* blob, const uint64_t* off, uint32_t n, int layout, uint32_t L, uint32_t* L_out,
                          const fcz_dense_out* out, int32_t* status) {
-    return decompress_dense_impl(ctx, blob, off, n, layout, L, false, nullptr, L_out, out, status);
+    return decompress_dense_impl(ctx, blob, off, n, layout, ROWS_PADDED, L, nullptr, L_out, nullptr, out, nullptr, status);
 }
 
 int fcz_decompress_dense_window(fcz_ctx* ctx, const uint8_t* blob, const uint64_t* off, uint32_t n, int layout, uint32_t L, const uint32_t* start,
                                 uint32_t* L_out, const fcz_dense_out* out, int32_t* status) {
-    return decompress_dense_impl(ctx, blob, off, n, layout, L, true, start, L_out, out, status);
+    return decompress_dense_impl(ctx, blob, off, n, layout, ROWS_WINDOW, L, start, L_out, nullptr, out, nullptr, status);
+}
+
+int fcz_decompress_dense_packed(fcz_ctx* ctx, const uint8_t* blob, const uint64_t* off, uint32_t n, int layout, uint32_t* R_out, uint32_t* row_off,
+                                const fcz_packed_out* out, int32_t* status) {
+    const fcz_dense_out d = padded_part(out);
+    return decompress_dense_impl(ctx, blob, off, n, layout, ROWS_PACKED, 0u, nullptr, R_out, row_off, out ? &d : nullptr, out ? out->chain_index : nullptr, status);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1575,103 +1597,82 @@ int fcz_chi_atom(int rc, int k) {
     return slot ? host_tab::h_res_atom[rc][slot] : -1;
 }
 
-int fcz_angles_dev(fcz_ctx* ctx, const uint8_t* blob_dev, const uint64_t* off_dev, uint32_t n, const uint32_t* res_off_dev, uint32_t L,
-                   float* angles_dev, uint8_t* mask_dev) {
-    if (!ctx || !blob_dev || !off_dev || !res_off_dev || !angles_dev || !mask_dev || L == 0) return FCZ_E_INVALID_ARG;
+// fcz_angles_dev (k_angles), fcz_angles_window_dev (k_angles_window with start_dev and aatype_dev, either may be NULL) and
+// fcz_angles_packed_dev (k_angles_packed: no L)
+static int angles_rows(fcz_ctx* ctx, const uint8_t* blob_dev, const uint64_t* off_dev, uint32_t n, const uint32_t* res_off_dev, rows_form form, uint32_t L,
+                       const uint32_t* start_dev, float* angles_dev, uint8_t* mask_dev, uint8_t* aatype_dev) {
+    if (!ctx || !blob_dev || !off_dev || !res_off_dev || !angles_dev || !mask_dev || (L == 0 && form != ROWS_PACKED)) return FCZ_E_INVALID_ARG;
     HIP_TRY(hipSetDevice(ctx->device));
     if (n == 0) return FCZ_OK;
     // one wavefront per entry on a persistent grid
-    const uint32_t blocks = std::min<uint32_t>(grid_for(n, WAVES_PER_BLOCK), (uint32_t)ctx->n_cu * 32u);
+    const dim3 blocks(std::min<uint32_t>(grid_for(n, WAVES_PER_BLOCK), (uint32_t)ctx->n_cu * 32u));
     span_guard sg(ctx, "angles");
-    hipLaunchKernelGGL(k_angles, dim3(blocks), dim3(BLOCK), 0, ctx->stream, blob_dev, off_dev, res_off_dev, n, L, angles_dev, mask_dev);
+    if (form == ROWS_PACKED)
+        hipLaunchKernelGGL(k_angles_packed, blocks, dim3(BLOCK), 0, ctx->stream, blob_dev, off_dev, res_off_dev, n, angles_dev, mask_dev);
+    else if (form == ROWS_WINDOW)
+        hipLaunchKernelGGL(k_angles_window, blocks, dim3(BLOCK), 0, ctx->stream, blob_dev, off_dev, res_off_dev, n, L, start_dev, angles_dev, mask_dev, aatype_dev);
+    else
+        hipLaunchKernelGGL(k_angles, blocks, dim3(BLOCK), 0, ctx->stream, blob_dev, off_dev, res_off_dev, n, L, angles_dev, mask_dev);
     HIP_TRY(hipGetLastError());
     return FCZ_OK;
+}
+
+int fcz_angles_dev(fcz_ctx* ctx, const uint8_t* blob_dev, const uint64_t* off_dev, uint32_t n, const uint32_t* res_off_dev, uint32_t L,
+                   float* angles_dev, uint8_t* mask_dev) {
+    return angles_rows(ctx, blob_dev, off_dev, n, res_off_dev, ROWS_PADDED, L, nullptr, angles_dev, mask_dev, nullptr);
 }
 
 int fcz_angles_window_dev(fcz_ctx* ctx, const uint8_t* blob_dev, const uint64_t* off_dev, uint32_t n, const uint32_t* res_off_dev, uint32_t L,
                           const uint32_t* start_dev, float* angles_dev, uint8_t* mask_dev, uint8_t* aatype_dev) {
-    if (!ctx || !blob_dev || !off_dev || !res_off_dev || !angles_dev || !mask_dev || L == 0) return FCZ_E_INVALID_ARG;
-    HIP_TRY(hipSetDevice(ctx->device));
-    if (n == 0) return FCZ_OK;
-    const uint32_t blocks = std::min<uint32_t>(grid_for(n, WAVES_PER_BLOCK), (uint32_t)ctx->n_cu * 32u);
-    span_guard sg(ctx, "angles");
-    hipLaunchKernelGGL(k_angles_window, dim3(blocks), dim3(BLOCK), 0, ctx->stream, blob_dev, off_dev, res_off_dev, n, L, start_dev, angles_dev, mask_dev,
-                       aatype_dev);
-    HIP_TRY(hipGetLastError());
-    return FCZ_OK;
+    return angles_rows(ctx, blob_dev, off_dev, n, res_off_dev, ROWS_WINDOW, L, start_dev, angles_dev, mask_dev, aatype_dev);
 }
 
 int fcz_angles_packed_dev(fcz_ctx* ctx, const uint8_t* blob_dev, const uint64_t* off_dev, uint32_t n, const uint32_t* res_off_dev,
                           float* angles_dev, uint8_t* mask_dev) {
-    if (!ctx || !blob_dev || !off_dev || !res_off_dev || !angles_dev || !mask_dev) return FCZ_E_INVALID_ARG;
-    HIP_TRY(hipSetDevice(ctx->device));
-    if (n == 0) return FCZ_OK;
-    const uint32_t blocks = std::min<uint32_t>(grid_for(n, WAVES_PER_BLOCK), (uint32_t)ctx->n_cu * 32u);
-    span_guard sg(ctx, "angles");
-    hipLaunchKernelGGL(k_angles_packed, dim3(blocks), dim3(BLOCK), 0, ctx->stream, blob_dev, off_dev, res_off_dev, n, angles_dev, mask_dev);
-    HIP_TRY(hipGetLastError());
-    return FCZ_OK;
+    return angles_rows(ctx, blob_dev, off_dev, n, res_off_dev, ROWS_PACKED, 0u, nullptr, angles_dev, mask_dev, nullptr);
 }
 
-// the three host-pointer forms; width_out is L_out (padded, windowed) or R_out (packed); window: the starts of the host array `start`
-// (may be NULL) and the optional host array aatype
-static int decompress_angles_impl(fcz_ctx* ctx, const uint8_t* blob, const uint64_t* off, uint32_t n, bool packed, uint32_t L, uint32_t* width_out,
-                                  uint32_t* row_off, float* angles, uint8_t* mask, int32_t* status, bool window = false, const uint32_t* start = nullptr,
-                                  uint8_t* aatype = nullptr) {
+// The three host-pointer forms. width_out is L_out (padded, windowed) or R_out (packed), row_off is the packed form's; windowed: the
+// starts of the host array `start` (may be NULL) and the optional host array aatype. Staged by the rules of staged_call.
+static int decompress_angles_impl(fcz_ctx* ctx, const uint8_t* blob, const uint64_t* off, uint32_t n, rows_form form, uint32_t L, const uint32_t* start,
+                                  uint32_t* width_out, uint32_t* row_off, float* angles, uint8_t* mask, uint8_t* aatype, int32_t* status) {
+    const bool packed = form == ROWS_PACKED;
     if (!ctx || !blob || !off || (!angles != !mask) || (!angles && !width_out)) return FCZ_E_INVALID_ARG;
     HIP_TRY(hipSetDevice(ctx->device));
     claim_staging(ctx);
     if (width_out) *width_out = packed ? 0u : L;
     if (n == 0) { if (row_off) row_off[0] = 0; return FCZ_OK; }
-    uint32_t R = 0, M = 0;
-    int rc = upload_records(ctx, blob, off, n, &R, &M); if (rc) return rc;
-    std::vector<uint32_t> res_off((size_t)n + 1);
-    HIP_TRY(hipMemcpyAsync(res_off.data(), ctx->pool[REC_RES_OFF].p, sizeof(uint32_t) * ((size_t)n + 1), hipMemcpyDeviceToHost, ctx->stream));
-    if (status) HIP_TRY(hipMemcpyAsync(status, cnt_status(ctx, n), sizeof(int32_t) * n, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    if (row_off) memcpy(row_off, res_off.data(), sizeof(uint32_t) * ((size_t)n + 1));
-    if (!packed && L == 0)
-        for (uint32_t i = 0; i < n; i++) L = std::max(L, res_off[i + 1] - res_off[i]);
+    uint32_t R = 0, M = 0, longest = 0;
+    int rc = upload_sized(ctx, blob, off, n, status, row_off, &R, &M, packed ? nullptr : &longest); if (rc) return rc;
+    if (!packed && L == 0) L = longest;
     if (width_out) *width_out = packed ? R : L;
     const size_t rows = packed ? (size_t)R : (size_t)n * L;
     if (!angles || rows == 0) return FCZ_OK;                      // a sizing call, or no row to fill
     const size_t elems = rows * FCZ_ANGLE_COLUMNS;
-    if ((rc = ctx->pool[ANGLES_OUT].ensure(elems * sizeof(float))) || (rc = ctx->pool[ANGLES_OUT + 1].ensure(elems))) return rc;
-    const uint8_t* b = ctx->pool[REC_BLOB].as<uint8_t>(); const uint64_t* o = ctx->pool[REC_OFF].as<uint64_t>(); const uint32_t* ro = ctx->pool[REC_RES_OFF].as<uint32_t>();
-    if (window) {
-        const uint32_t* start_dev = nullptr;
-        if (start) {
-            if ((rc = ctx->pool[WINDOW_START].ensure(sizeof(uint32_t) * n))) return rc;
-            HIP_TRY(hipMemcpyAsync(ctx->pool[WINDOW_START].p, start, sizeof(uint32_t) * n, hipMemcpyHostToDevice, ctx->stream));
-            start_dev = ctx->pool[WINDOW_START].as<uint32_t>();
-        }
-        if (aatype && (rc = ctx->pool[ANGLES_OUT + 2].ensure(rows))) return rc;
-        rc = fcz_angles_window_dev(ctx, b, o, n, ro, L, start_dev, ctx->pool[ANGLES_OUT].as<float>(), ctx->pool[ANGLES_OUT + 1].as<uint8_t>(),
-                                   aatype ? ctx->pool[ANGLES_OUT + 2].as<uint8_t>() : nullptr);
-        if (!rc && aatype) HIP_TRY(hipMemcpyAsync(aatype, ctx->pool[ANGLES_OUT + 2].p, rows, hipMemcpyDeviceToHost, ctx->stream));
-    } else
-        rc = packed ? fcz_angles_packed_dev(ctx, b, o, n, ro, ctx->pool[ANGLES_OUT].as<float>(), ctx->pool[ANGLES_OUT + 1].as<uint8_t>())
-                    : fcz_angles_dev(ctx, b, o, n, ro, L, ctx->pool[ANGLES_OUT].as<float>(), ctx->pool[ANGLES_OUT + 1].as<uint8_t>());
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(angles, ctx->pool[ANGLES_OUT].p, elems * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(mask, ctx->pool[ANGLES_OUT + 1].p, elems, hipMemcpyDeviceToHost, ctx->stream));
+    const std::initializer_list<staged_out> outs = {{angles, elems * sizeof(float), ANGLES_OUT}, {mask, elems, ANGLES_OUT + 1}, {aatype, rows, ANGLES_OUT + 2}};
+    void* d[3]; const void* start_dev = nullptr;
+    if ((rc = reserve_out(ctx, outs, d)) || (form == ROWS_WINDOW && (rc = stage_in(ctx, {{start, sizeof(uint32_t) * n, WINDOW_START}}, &start_dev))) ||
+        (rc = angles_rows(ctx, ctx->pool[REC_BLOB].as<uint8_t>(), ctx->pool[REC_OFF].as<uint64_t>(), n, ctx->pool[REC_RES_OFF].as<uint32_t>(), form, L,
+                          (const uint32_t*)start_dev, (float*)d[0], (uint8_t*)d[1], (uint8_t*)d[2])) ||
+        (rc = fetch_out(ctx, outs)))
+        return rc;
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return FCZ_OK;
 }
 
 int fcz_decompress_angles(fcz_ctx* ctx, const uint8_t* blob, const uint64_t* off, uint32_t n, uint32_t L, uint32_t* L_out, float* angles,
                           uint8_t* mask, int32_t* status) {
-    return decompress_angles_impl(ctx, blob, off, n, false, L, L_out, nullptr, angles, mask, status);
+    return decompress_angles_impl(ctx, blob, off, n, ROWS_PADDED, L, nullptr, L_out, nullptr, angles, mask, nullptr, status);
 }
 
 int fcz_decompress_angles_window(fcz_ctx* ctx, const uint8_t* blob, const uint64_t* off, uint32_t n, uint32_t L, const uint32_t* start,
                                  uint32_t* L_out, float* angles, uint8_t* mask, uint8_t* aatype, int32_t* status) {
-    return decompress_angles_impl(ctx, blob, off, n, false, L, L_out, nullptr, angles, mask, status, true, start, aatype);
+    return decompress_angles_impl(ctx, blob, off, n, ROWS_WINDOW, L, start, L_out, nullptr, angles, mask, aatype, status);
 }
 
 int fcz_decompress_angles_packed(fcz_ctx* ctx, const uint8_t* blob, const uint64_t* off, uint32_t n, uint32_t* R_out, uint32_t* row_off,
                                  float* angles, uint8_t* mask, int32_t* status) {
-    return decompress_angles_impl(ctx, blob, off, n, true, 0u, R_out, row_off, angles, mask, status);
+    return decompress_angles_impl(ctx, blob, off, n, ROWS_PACKED, 0u, nullptr, R_out, row_off, angles, mask, nullptr, status);
 }
 
 }  // extern "C"
@@ -1736,54 +1737,6 @@ struct dense_bytes {
         : rows(packed ? (size_t)rows_per : (size_t)n * rows_per), pos(rows * (size_t)fcz_dense_width(layout) * 3 * sizeof(float)),
           mask(rows * (size_t)fcz_dense_width(layout)), bound(b ? sizeof(uint32_t) * ((size_t)n + (packed ? 1 : 0)) : 0) {}
 };
-
-// An array of a host-pointer call: the caller's pointer (NULL: an input that is absent, an output that is not wanted), its bytes, and
-// the slot of fcz_ctx::pool it goes through (table in fcz_ctx).
-struct staged_in { const void* host; size_t bytes; int slot; };
-struct staged_out { void* host; size_t bytes; int slot; };
-constexpr int STAGED_MAX = 13;
-
-// The host-pointer form of an analysis: its inputs to the device, run(in, out) on the device pointers in the order of the lists (it
-// enqueues the *_rows call), the outputs back, and the stream drained. One set of rules for every analysis:
-//   * A call whose wanted outputs have no byte returns FCZ_OK with nothing enqueued: there is nothing it could write. That is rows == 0
-//     for the per-row analyses, and rows == 0 with n == 0 for violations, superpose and TM-score: they have per-chain outputs, so chains
-//     without a row (packed, R == 0) go on and get the counters and the transform of an empty chain.
-//   * An array of zero bytes is not copied, in either direction: hipMemcpyAsync is given no NULL or unallocated pointer.
-//   * An input that is absent or has zero bytes reaches run() as NULL. Absent is what the *_rows functions take NULL to mean (no
-//     length, no aatype, no second mask); of a zero-byte array no kernel reads an element -- every chain is clamped to the rows that
-//     exist and a launch without chains (n == 0: the fill kernels) reads no per-chain array such as the transforms of apply.
-//   * An output that is not wanted reaches run() as NULL, which is what the optional members of the out structs mean.
-//   * Every buffer is made large enough before the first copy is enqueued, so FCZ_E_NOMEM leaves nothing in flight.
-template <class Run>
-static int staged_call(fcz_ctx* ctx, std::initializer_list<staged_in> in, std::initializer_list<staged_out> out, Run run) {
-    HIP_TRY(hipSetDevice(ctx->device));
-    claim_staging(ctx);
-    size_t wanted = 0;
-    for (const staged_out& o : out) wanted += o.host ? o.bytes : 0;
-    if (wanted == 0) return FCZ_OK;
-    const void* din[STAGED_MAX]; void* dout[STAGED_MAX];
-    int rc, i = 0;
-    for (const staged_in& a : in) {
-        const size_t nb = a.host ? a.bytes : 0;
-        if ((rc = ctx->pool[a.slot].ensure(nb))) return rc;
-        din[i++] = nb ? ctx->pool[a.slot].p : nullptr;
-    }
-    i = 0;
-    for (const staged_out& o : out) {
-        if ((rc = ctx->pool[o.slot].ensure(o.host ? o.bytes : 0))) return rc;
-        dout[i++] = o.host ? ctx->pool[o.slot].p : nullptr;
-    }
-    i = 0;
-    for (const staged_in& a : in) {
-        if (din[i]) HIP_TRY(hipMemcpyAsync(ctx->pool[a.slot].p, a.host, a.bytes, hipMemcpyHostToDevice, ctx->stream));
-        i++;
-    }
-    if ((rc = run(din, dout))) return rc;
-    for (const staged_out& o : out)
-        if (o.host && o.bytes) HIP_TRY(hipMemcpyAsync(o.host, ctx->pool[o.slot].p, o.bytes, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return FCZ_OK;
-}
 
 // ------------------------------------------------------------------------------------------------
 // k-nearest-neighbour residue graph of dense tensors (fcz_knn.h; no counterpart in the reference)
@@ -3115,20 +3068,16 @@ int fcz_compress_dense_fetch_dev(fcz_ctx* ctx, uint64_t* out_off_dev, int32_t* s
 
 // the host arrays of a fcz_dense_in of `rows` rows -> DENSE_IN 0 .. 9 (slot 3: length [n], or row_off [n + 1] of the packed form) -> *dv
 static int upload_dense_in(fcz_ctx* ctx, const fcz_dense_in* in, const uint32_t* row_off, uint32_t n, size_t rows, int layout, fcz_dense_in* dv) {
-    int rc;
     const size_t C = n, A = (size_t)fcz_dense_width(layout);
     const size_t title_bytes = in->title_off ? in->title_off[n] : 0;
-    const void* host[10] = {in->pos, in->mask, in->aatype, row_off ? row_off : in->length, in->plddt, in->first_res_index, in->first_atom_index,
-                            in->chain_id, in->titles, in->title_off};
-    const size_t bytes[10] = {rows * A * 3 * sizeof(float), rows * A, rows, row_off ? 4 * (C + 1) : 4 * C, rows * sizeof(float), 4 * C, 4 * C, C, title_bytes, 4 * (C + 1)};
+    // floor 16: a present array of zero bytes still gets a device pointer -- undense_rows tells "absent" from "empty" by the pointer, where
+    // the rules of staged_call would give it NULL
     const void* dev[10];
-    for (int i = 0; i < 10; i++) {
-        dev[i] = nullptr;
-        if (!host[i]) continue;
-        if ((rc = ctx->pool[DENSE_IN + i].ensure(std::max<size_t>(bytes[i], 16)))) return rc;
-        dev[i] = ctx->pool[DENSE_IN + i].p;
-        if (bytes[i]) HIP_TRY(hipMemcpyAsync(ctx->pool[DENSE_IN + i].p, host[i], bytes[i], hipMemcpyHostToDevice, ctx->stream));
-    }
+    int rc = stage_in(ctx, {{in->pos, rows * A * 3 * sizeof(float), DENSE_IN}, {in->mask, rows * A, DENSE_IN + 1}, {in->aatype, rows, DENSE_IN + 2},
+                            {row_off ? row_off : in->length, row_off ? 4 * (C + 1) : 4 * C, DENSE_IN + 3}, {in->plddt, rows * sizeof(float), DENSE_IN + 4},
+                            {in->first_res_index, 4 * C, DENSE_IN + 5}, {in->first_atom_index, 4 * C, DENSE_IN + 6}, {in->chain_id, C, DENSE_IN + 7},
+                            {in->titles, title_bytes, DENSE_IN + 8}, {in->title_off, 4 * (C + 1), DENSE_IN + 9}}, dev, 16);
+    if (rc) return rc;
     *dv = {(const float*)dev[0], (const uint8_t*)dev[1], (const uint8_t*)dev[2], (const uint32_t*)dev[3], (const float*)dev[4],
            (const int32_t*)dev[5], (const int32_t*)dev[6], (const char*)dev[7], (const char*)dev[8], (const uint32_t*)dev[9]};
     return FCZ_OK;

@@ -9,11 +9,13 @@ import zlib
 import numpy as np
 import pytest
 
+import _angles as A
 import _dense as D
 import _harness as H
 import _undense as U
 from _cases import entries_blob
 from _devpath import DevRecords, compress_dev
+from _window import same, sweep_starts, window_of
 from foldcomp_amd import synthetic
 from foldcomp_amd.structure import ChainBatch
 from test_gpu_launch_plan import _backbone_dev_per_chain, _segments
@@ -171,6 +173,51 @@ class _Calls:
         for k in ("mask", "aatype", "res_index", "length"):
             assert np.array_equal(got[k].astype(np.int64), want[k].astype(np.int64)), (layout, L, k)
 
+    def _gold_full(self, layout):
+        """(residues per golden record, the uncropped expectation a decode_dense step left)"""
+        lens = np.asarray([len(D.record_fields(f)[0]) for f in self.gold], np.int64)
+        return lens, self.dense_want[layout, int(lens.max())]
+
+    def decode_dense_form(self, form, layout="atom37"):
+        """the host forms beside fcz_decompress_dense: a window of 64 rows per entry, or the rows without padding"""
+        lens, full = self._gold_full(layout)
+        if form == "window":
+            starts = sweep_starts(lens, 64, 3)
+            got = self.codec.decompress_dense(*entries_blob(self.gold), layout=layout, max_len=64, start=starts)
+            want = window_of(full, starts, 64)
+        else:
+            got = self.codec.decompress_dense(*entries_blob(self.gold), layout=layout, packed=True)
+            want = {k: np.concatenate([full[k][e, :n] for e, n in enumerate(lens)]) for k in ("pos", "mask", "aatype", "plddt", "res_index")}
+            want["length"] = full["length"]
+            assert np.array_equal(got["row_off"], np.concatenate([[0], np.cumsum(lens)])) and np.array_equal(got["chain_index"], np.repeat(np.arange(len(lens)), lens))
+        assert not got["status"].any()
+        same(got, want, f"dense {form}")
+
+    def decode_angles(self, form):
+        """the three angle host forms against the numpy restatement tests/test_gpu_angles.py uses"""
+        exp = [A.entry_expected(f) for f in self.gold]
+        lens, full = self._gold_full("atom37")
+        Lf = int(lens.max())
+        blob, off = entries_blob(self.gold)
+        if form == "packed":
+            got = self.codec.decompress_angles(blob, off, packed=True)
+            e_ang, e_msk, e_off = A.packed_expected(exp)
+            assert np.array_equal(got["row_off"], e_off)
+        elif form == "padded":
+            got = self.codec.decompress_angles(blob, off)
+            e_ang, e_msk = A.padded_expected(exp, Lf)
+        else:
+            starts = sweep_starts(lens, 64, 5)
+            got = self.codec.decompress_angles(blob, off, L=64, start=starts)
+            f_ang, f_msk = A.padded_expected(exp, Lf)
+            e_ang, e_msk = np.zeros((len(lens), 64, A.COLS), np.float32), np.zeros((len(lens), 64, A.COLS), np.uint8)
+            for e, s in enumerate(int(x) for x in starts):
+                m = max(min(64, Lf - s), 0)
+                e_ang[e, :m] = f_ang[e, s:s + m]; e_msk[e, :m] = f_msk[e, s:s + m]
+            assert np.array_equal(got["aatype"], window_of(full, starts, 64)["aatype"])
+        assert not got["status"].any() and got["angles"].shape == e_ang.shape
+        assert np.array_equal(got["angle_mask"].view(np.uint8), e_msk) and np.array_equal(_bits(got["angles"]), _bits(e_ang)), form
+
     def pdb_text(self, alt=False):
         blob, off = entries_blob(self.gold)
         texts, status = self.codec.decompress_pdb(blob, off)
@@ -257,6 +304,8 @@ def _sequence(seed):
     # (not among the draws: the history above stays what it was)
     seq += [("encode_dense", "small", "atom37"), ("decompress", "tiny"), ("decode_dense", "atom37"), ("pdb_text",), ("compress_gz",),
             ("encode_dense", "small", "atom14"), ("decode_dense", "atom14"), ("decode_dense", "atom37", True)]
+    # the host forms of the decode the history above lacks, alternating dense and angles (they share ANGLES_OUT / DENSE_OUT and WINDOW_START)
+    seq += [("decode_dense_form", "packed"), ("decode_angles", "padded"), ("decode_dense_form", "window"), ("decode_angles", "packed"), ("decode_angles", "window")]
     seq += [("numerics", False), ("decompress", "large", True), ("decompress", "tiny")]
     return seq
 

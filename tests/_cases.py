@@ -399,15 +399,18 @@ def payload_mutations(records, per_record=10, seed=20260927, temp_params=False):
     return out
 
 
-def golden_records(golden):
-    """the FCZ records of the goldens, cut to their own size (the database entries end in a NUL)"""
-    from foldcomp_amd import fczfile
+def golden_records_raw(golden):
+    """-> (the names of the 56 goldens, their FCZ records as stored: the database entries end in a NUL)"""
     z, index = golden
-    recs = []
-    for n in compress_cases(index) + db_cases(index):
-        e = z[f"{n}/fcz"].tobytes()
-        recs.append(e[:fczfile.record_size(e)])
-    return recs
+    names = compress_cases(index) + db_cases(index)
+    assert len(names) == 56
+    return names, [z[f"{n}/fcz"].tobytes() for n in names]
+
+
+def golden_records(golden):
+    """the FCZ records of the goldens, cut to their own size"""
+    from foldcomp_amd import fczfile
+    return [e[:fczfile.record_size(e)] for e in golden_records_raw(golden)[1]]
 
 
 # ---- mutated mmCIF files --------------------------------------------------------------------------------------------------

@@ -96,7 +96,3 @@ def stack_expected(per_entry, L, A, keys=("pos", "mask", "aatype", "res_index", 
     d = {k: np.stack([e[k] for e in per_entry]) for k in keys if all(k in e for e in per_entry)}
     d["length"] = np.asarray([e["length"] for e in per_entry], np.uint32)
     return d
-
-
-def bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)

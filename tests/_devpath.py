@@ -24,25 +24,38 @@ def to_dev(a, dev="cuda:0"):
     return torch.from_numpy(a).to(dev)
 
 
+FILL = 0xA5          # the byte every guarded output holds before the call
+GUARD = 256          # bytes of FILL on both sides of an output that must survive (a multiple of 16: the outputs stay aligned)
+
+
 class HostGuarded:
     """host outputs of a host-pointer entry point, {name: (dtype, shape)} in the call's order: 0xA5 everywhere, `guard` bytes in
     front of and behind each, which must survive the call"""
-    FILL = 0xA5
 
-    def __init__(self, spec, guard=256):
+    def __init__(self, spec, guard=GUARD):
         self.spec = {k: (np.dtype(d), tuple(shape)) for k, (d, shape) in spec.items()}
         self.guard = guard
-        self.raw = {k: np.full(2 * guard + d.itemsize * int(np.prod(shape)), self.FILL, np.uint8) for k, (d, shape) in self.spec.items()}
+        self.raw = {k: self._filled(2 * guard + d.itemsize * int(np.prod(shape))) for k, (d, shape) in self.spec.items()}
+
+    def _filled(self, nbytes):
+        return np.full(nbytes, FILL, np.uint8)
+
+    def _address(self, buf):
+        return buf.ctypes.data
+
+    def _bytes(self, buf):
+        """the buffer as a host uint8 array"""
+        return buf
 
     def ptr(self, k):
-        return self.raw[k].ctypes.data + self.guard
+        return self._address(self.raw[k]) + self.guard
 
     def ptrs(self):
         return [self.ptr(k) for k in self.spec]
 
     def fetch(self, k):
-        a, g = self.raw[k], self.guard
-        assert (a[:g] == self.FILL).all() and (a[len(a) - g:] == self.FILL).all(), f"guard bytes of {k} overwritten"
+        a, g = self._bytes(self.raw[k]), self.guard
+        assert (a[:g] == FILL).all() and (a[len(a) - g:] == FILL).all(), f"guard bytes of {k} overwritten"
         d, shape = self.spec[k]
         return a[g:len(a) - g].copy().view(d).reshape(shape)
 
@@ -50,7 +63,26 @@ class HostGuarded:
         return [self.fetch(k) for k in self.spec]
 
     def untouched(self):
-        return all(bool((a == self.FILL).all()) for a in self.raw.values())
+        return all(bool((self._bytes(a) == FILL).all()) for a in self.raw.values())
+
+
+class DevGuarded(HostGuarded):
+    """the same for the device outputs of a device-pointer entry point: a byte the call leaves unwritten stays 0xA5 and fails the
+    comparison that follows (device: for the CPU test of this class, nothing else passes it)"""
+
+    def __init__(self, spec, guard=GUARD, device="cuda:0"):
+        self.device = device
+        super().__init__(spec, guard)
+
+    def _filled(self, nbytes):
+        import torch
+        return torch.full((nbytes,), FILL, dtype=torch.uint8, device=self.device)
+
+    def _address(self, buf):
+        return buf.data_ptr()
+
+    def _bytes(self, buf):
+        return buf.cpu().numpy()
 
 
 def host_ptr(a):

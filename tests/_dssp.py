@@ -7,9 +7,9 @@ from the ACCEPTOR table alone, the labels: a list of bridges, ladders grown from
 H > E > B > G > I > T > S. Nothing here is shared with the kernel's row-local formulation."""
 import numpy as np
 
-import _knn as K
+from _analysis import bits, chains_of, ptr
+from _devpath import GUARD, DevGuarded
 
-FILL, GUARD = K.FILL, K.GUARD
 F = np.float32
 SS = "-HBEGITS"
 O_SLOT = {37: 4, 14: 3, 4: 3}
@@ -196,26 +196,12 @@ def labels_chain(pos, mask, acc_index, acc_energy):
     return ss, ch.bb.copy()
 
 
-def _chains(shape, bound, packed):
-    """-> [(index of the chain's rows, first row, rows of the chain)]"""
-    if packed:
-        R = shape[0]
-        out = []
-        for e in range(len(bound) - 1):
-            lo, hi = min(int(bound[e]), R), min(int(bound[e + 1]), R)
-            if hi > lo:
-                out.append((slice(lo, hi), lo, hi - lo))
-        return out
-    n, L = shape[:2]
-    return [((e, slice(0, L if bound is None else min(int(bound[e]), L))), 0, L if bound is None else min(int(bound[e]), L)) for e in range(n)]
-
-
 def hbonds(pos, mask, aatype, bound, packed=False):
     """pos [n, L, A, 3] / [R, A, 3], mask, aatype or None, length [n] / None or row_off [n + 1] -> the four tables [.., 2]; the index
     is the row of the entry (padded) or the global row (packed)"""
     lead = pos.shape[:-2]
     out = [np.full(lead + (2,), -1, np.int32), np.zeros(lead + (2,), F), np.full(lead + (2,), -1, np.int32), np.zeros(lead + (2,), F)]
-    for sel, base, m in _chains(pos.shape, bound, packed):
+    for sel, base, m in chains_of(pos.shape, bound, packed):
         if m == 0:
             continue
         t = hbond_chain(pos[sel], mask[sel], None if aatype is None else aatype[sel])
@@ -228,7 +214,7 @@ def labels(pos, mask, bound, acc_index, acc_energy, packed=False):
     """the same arrays and an acceptor table of the form hbonds() returns -> ss uint8 [n, L] / [R], ss_mask bool"""
     lead = pos.shape[:-2]
     ss, ss_mask = np.zeros(lead, np.uint8), np.zeros(lead, bool)
-    for sel, base, m in _chains(pos.shape, bound, packed):
+    for sel, base, m in chains_of(pos.shape, bound, packed):
         if m == 0:
             continue
         ai = acc_index[sel].astype(np.int64) - base
@@ -244,7 +230,7 @@ def same_tables(got, exp, what=""):
     for name, g, e in zip(("acc_index", "acc_energy", "don_index", "don_energy"), got, exp):
         assert g.shape == e.shape and g.dtype == e.dtype, (what, name, g.shape, e.shape, g.dtype, e.dtype)
         if g.dtype == np.float32:
-            g, e = K.bits(g), K.bits(e)
+            g, e = bits(g), bits(e)
         assert np.array_equal(g, e), (what, name, np.argwhere(g != e)[:4])
 
 
@@ -255,59 +241,36 @@ def same_labels(got, exp, what=""):
         assert np.array_equal(g, e), (what, name, np.argwhere(g != e)[:4], g[g != e][:4], e[g != e][:4])
 
 
-class Guarded:
-    """device outputs of `count` elements of the given item sizes, 0xA5 everywhere, `guard` bytes in front and behind"""
-
-    def __init__(self, count, dtypes, guard=GUARD):
-        import torch
-        self.count, self.guard, self.dtypes = count, guard, [np.dtype(d) for d in dtypes]
-        self.raw = [torch.full((guard + d.itemsize * count + guard,), FILL, dtype=torch.uint8, device="cuda:0") for d in self.dtypes]
-
-    def ptrs(self):
-        return [t.data_ptr() + self.guard for t in self.raw]
-
-    def fetch(self, shape):
-        out = []
-        for t, d in zip(self.raw, self.dtypes):
-            a = t.cpu().numpy()
-            nb = d.itemsize * self.count
-            assert (a[:self.guard] == FILL).all() and (a[self.guard + nb:] == FILL).all(), "guard bytes overwritten"
-            out.append(a[self.guard:self.guard + nb].copy().view(d).reshape(shape))
-        return out
-
-    def untouched(self):
-        return all(bool((t == FILL).all()) for t in self.raw)
-
-
-def _ptr(t):
-    return None if t is None else t.data_ptr()
+def table_spec(lead):
+    """the four tables of rows shaped `lead` as a guard's spec"""
+    shape = tuple(lead) + (2,)
+    return dict(acc_index=(np.int32, shape), acc_energy=(np.float32, shape), don_index=(np.int32, shape), don_energy=(np.float32, shape))
 
 
 def run_hbond(codec, pos_t, mask_t, aa_t, bound_t, n, rows, layout, packed, guard=GUARD, expect=0):
     """fcz_hbond_dev (rows = L) or fcz_hbond_packed_dev (rows = R) on device tensors -> the four tables as numpy, guards checked"""
     import torch
-    total = rows if packed else n * rows
-    g = Guarded(total * 2, (np.int32, np.float32, np.int32, np.float32), guard)
+    g = DevGuarded(table_spec((rows,) if packed else (n, rows)), guard)
     fn = codec.lib.fcz_hbond_packed_dev if packed else codec.lib.fcz_hbond_dev
     torch.cuda.synchronize()
-    rc = fn(codec.ctx, pos_t.data_ptr(), mask_t.data_ptr(), _ptr(aa_t), _ptr(bound_t), n, rows, layout, *g.ptrs())
+    rc = fn(codec.ctx, pos_t.data_ptr(), mask_t.data_ptr(), ptr(aa_t), ptr(bound_t), n, rows, layout, *g.ptrs())
     codec.synchronize()
     assert rc == expect, rc
-    return g.fetch((total, 2) if packed else (n, rows, 2))
+    return g.all()
 
 
 def run_labels(codec, pos_t, mask_t, aa_t, bound_t, n, rows, layout, packed, acc_index_t, acc_energy_t, guard=GUARD, expect=0):
     """fcz_dssp_labels_dev / _packed_dev on device tensors -> (ss, ss_mask) as numpy uint8, guards checked"""
     import torch
-    total = rows if packed else n * rows
-    g = Guarded(total, (np.uint8, np.uint8), guard)
+    shape = (rows,) if packed else (n, rows)
+    g = DevGuarded(dict(ss=(np.uint8, shape), ss_mask=(np.uint8, shape)), guard)
     fn = codec.lib.fcz_dssp_labels_packed_dev if packed else codec.lib.fcz_dssp_labels_dev
     torch.cuda.synchronize()
-    rc = fn(codec.ctx, pos_t.data_ptr(), mask_t.data_ptr(), _ptr(aa_t), _ptr(bound_t), n, rows, layout, acc_index_t.data_ptr(),
+    rc = fn(codec.ctx, pos_t.data_ptr(), mask_t.data_ptr(), ptr(aa_t), ptr(bound_t), n, rows, layout, acc_index_t.data_ptr(),
             acc_energy_t.data_ptr(), *g.ptrs())
     codec.synchronize()
     assert rc == expect, rc
-    return g.fetch((total,) if packed else (n, rows))
+    return g.all()
 
 
 def random_label_case(rng, lens):

@@ -11,10 +11,10 @@ inside its chain, the type and the layout have the three atoms, their masks are 
 are finite and > 0; otherwise rot = identity, trans = 0, mask = 0. The same code evaluates the definition in float64 when asked."""
 import numpy as np
 
+from _analysis import bits, ptr
+from _devpath import GUARD, DevGuarded
 from foldcomp_amd import _lib
 
-FILL = 0xA5
-GUARD = 256          # bytes of 0xA5 on both sides of an output that must survive (a multiple of 16: the outputs stay aligned)
 LAYOUTS = {"atom37": 0, "atom14": 1, "backbone4": 2}
 WIDTH = {0: 37, 1: 14, 2: 4}
 GROUPS = {"backbone": 0, "all": 1}
@@ -106,11 +106,6 @@ def frames(pos, mask, aatype, length, layout, groups, dtype=np.float32):
     return rot.reshape(lead + (G, 3, 3)), trans.reshape(lead + (G, 3)), fm.reshape(lead + (G,))
 
 
-def bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint32) if a.dtype == np.float32 else a.view(np.uint8)
-
-
 def same(got, exp, what=""):
     for name, g, e in zip(("rot", "trans", "frame_mask"), got, exp):
         g, e = bits(g), bits(e)
@@ -118,43 +113,19 @@ def same(got, exp, what=""):
         assert np.array_equal(g, e), (what, name, np.argwhere(g != e)[:4])
 
 
-class Guarded:
-    """the three device outputs of `items` (row, group) items, 0xA5 everywhere, `guard` bytes in front and behind"""
-    PER = (36, 12, 1)                                                 # bytes per item: rot, trans, frame_mask
-    DT = (np.float32, np.float32, np.uint8)
-
-    def __init__(self, items, guard=GUARD):
-        import torch
-        self.items, self.guard = items, guard
-        self.raw = [torch.full((guard + per * items + guard,), FILL, dtype=torch.uint8, device="cuda:0") for per in self.PER]
-
-    def ptrs(self):
-        return [t.data_ptr() + self.guard for t in self.raw]
-
-    def fetch(self, lead, G):
-        """-> (rot, trans, frame_mask) after checking the guards"""
-        out = []
-        for t, per, dt, tail in zip(self.raw, self.PER, self.DT, ((G, 3, 3), (G, 3), (G,))):
-            a = t.cpu().numpy()
-            nb = per * self.items
-            assert (a[:self.guard] == FILL).all() and (a[self.guard + nb:] == FILL).all(), "guard bytes overwritten"
-            out.append(a[self.guard:self.guard + nb].copy().view(dt).reshape(tuple(lead) + tail))
-        return out
-
-    def untouched(self):
-        return all(bool((t == FILL).all()) for t in self.raw)
+def out_spec(lead, G):
+    """the three outputs of rows shaped `lead` and G groups as a guard's spec"""
+    lead = tuple(lead) + (G,)
+    return dict(rot=(np.float32, lead + (3, 3)), trans=(np.float32, lead + (3,)), frame_mask=(np.uint8, lead))
 
 
 def run_dev(codec, pos_t, mask_t, aatype_t, length_t, n, L, layout, groups, guard=GUARD, expect=0):
     """fcz_frames_dev on device tensors -> (rot [n, L, G, 3, 3], trans [n, L, G, 3], frame_mask [n, L, G]) as numpy, guards checked:
     a byte the call leaves unwritten stays 0xA5 and fails the comparison that follows"""
     import torch
-    G = 1 if groups == 0 else 8
-    g = Guarded(n * L * G, guard)
-    rp, tp, fp = g.ptrs()
+    g = DevGuarded(out_spec((n, L), 1 if groups == 0 else 8), guard)
     torch.cuda.synchronize()
-    rc = codec.lib.fcz_frames_dev(codec.ctx, pos_t.data_ptr(), mask_t.data_ptr(), None if aatype_t is None else aatype_t.data_ptr(),
-                                  None if length_t is None else length_t.data_ptr(), n, L, layout, groups, rp, tp, fp)
+    rc = codec.lib.fcz_frames_dev(codec.ctx, pos_t.data_ptr(), mask_t.data_ptr(), ptr(aatype_t), ptr(length_t), n, L, layout, groups, *g.ptrs())
     codec.synchronize()
     assert rc == expect, rc
-    return g.fetch((n, L), G)
+    return g.all()

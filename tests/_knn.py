@@ -5,8 +5,8 @@ d2 = (dx*dx + dy*dy) + dz*dz in float32 (numpy rounds every operation and fuses 
 sites ordered by np.lexsort on (j, bits of d2), dist is np.sqrt in float32 (correctly rounded)."""
 import numpy as np
 
-FILL = 0xA5
-GUARD = 256          # bytes of 0xA5 on both sides of an output that must survive (a multiple of 16: the outputs stay aligned)
+from _analysis import bits, ptr
+from _devpath import GUARD, DevGuarded
 
 
 def knn_chain(xyz, site, k):
@@ -72,10 +72,6 @@ def knn_packed(pos, mask, row_off, slot, k):
     return index, dist
 
 
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
 def same(got, exp, what=""):
     gi, gd = got
     ei, ed = exp
@@ -84,39 +80,18 @@ def same(got, exp, what=""):
     assert np.array_equal(bits(gd), bits(ed)), (what, "dist", np.argwhere(bits(gd) != bits(ed))[:4])
 
 
-class Guarded:
-    """an int32 and a float32 device output of `count` elements each, 0xA5 everywhere, `guard` bytes in front and behind"""
-
-    def __init__(self, count, guard=GUARD):
-        import torch
-        self.count, self.guard = count, guard
-        self.raw = [torch.full((guard + 4 * count + guard,), FILL, dtype=torch.uint8, device="cuda:0") for _ in range(2)]
-
-    def ptrs(self):
-        return [t.data_ptr() + self.guard for t in self.raw]
-
-    def fetch(self, shape):
-        """-> (index, dist) after checking the guards"""
-        out = []
-        for t, dt in zip(self.raw, (np.int32, np.float32)):
-            a = t.cpu().numpy()
-            assert (a[:self.guard] == FILL).all() and (a[self.guard + 4 * self.count:] == FILL).all(), "guard bytes overwritten"
-            out.append(a[self.guard:self.guard + 4 * self.count].copy().view(dt).reshape(shape))
-        return out
-
-    def untouched(self):
-        return all(bool((t == FILL).all()) for t in self.raw)
+def out_spec(shape):
+    """the two outputs [.., k] as a guard's spec"""
+    return dict(index=(np.int32, tuple(shape)), dist=(np.float32, tuple(shape)))
 
 
 def run_dev(codec, pos_t, mask_t, bound_t, n, rows, layout, slot, k, packed, guard=GUARD, expect=0):
     """fcz_knn_dev (rows = L) or fcz_knn_packed_dev (rows = R) on device tensors -> (index, dist) as numpy, guards checked"""
     import torch
-    total = rows if packed else n * rows
-    g = Guarded(total * k, guard)
-    ip, dp = g.ptrs()
+    g = DevGuarded(out_spec((rows, k) if packed else (n, rows, k)), guard)
     fn = codec.lib.fcz_knn_packed_dev if packed else codec.lib.fcz_knn_dev
     torch.cuda.synchronize()
-    rc = fn(codec.ctx, pos_t.data_ptr(), mask_t.data_ptr(), None if bound_t is None else bound_t.data_ptr(), n, rows, layout, slot, k, ip, dp)
+    rc = fn(codec.ctx, pos_t.data_ptr(), mask_t.data_ptr(), ptr(bound_t), n, rows, layout, slot, k, *g.ptrs())
     codec.synchronize()
     assert rc == expect, rc
-    return g.fetch((total, k) if packed else (n, rows, k))
+    return g.all()

@@ -6,9 +6,9 @@ rounded) in both tensors; j is a pair of i when j != i and d_true < cutoff in fl
 hit per threshold it lies under; score = float32(hits) / float32(4 * pairs), 0 where there is no pair."""
 import numpy as np
 
-import _knn as K
+from _analysis import bits, ptr
+from _devpath import GUARD, DevGuarded
 
-FILL, GUARD = K.FILL, K.GUARD
 THRESHOLDS = (0.5, 1.0, 2.0, 4.0)
 
 
@@ -96,32 +96,8 @@ def same(got, exp, what=""):
     for name, g, e in zip(("score", "pairs", "hits"), got, exp):
         assert g.shape == e.shape and g.dtype == e.dtype, (what, name, g.shape, e.shape, g.dtype, e.dtype)
         if name == "score":
-            g, e = K.bits(g), K.bits(e)
+            g, e = bits(g), bits(e)
         assert np.array_equal(g, e), (what, name, np.argwhere(g != e)[:4])
-
-
-class Guarded:
-    """a float32 and two int32 device outputs of `count` elements each, 0xA5 everywhere, `guard` bytes in front and behind"""
-
-    def __init__(self, count, guard=GUARD):
-        import torch
-        self.count, self.guard = count, guard
-        self.raw = [torch.full((guard + 4 * count + guard,), FILL, dtype=torch.uint8, device="cuda:0") for _ in range(3)]
-
-    def ptrs(self):
-        return [t.data_ptr() + self.guard for t in self.raw]
-
-    def fetch(self, shape):
-        """-> (score, pairs, hits) after checking the guards"""
-        out = []
-        for t, dt in zip(self.raw, (np.float32, np.int32, np.int32)):
-            a = t.cpu().numpy()
-            assert (a[:self.guard] == FILL).all() and (a[self.guard + 4 * self.count:] == FILL).all(), "guard bytes overwritten"
-            out.append(a[self.guard:self.guard + 4 * self.count].copy().view(dt).reshape(shape))
-        return out
-
-    def untouched(self):
-        return all(bool((t == FILL).all()) for t in self.raw)
 
 
 def thresholds_arg(thresholds):
@@ -132,16 +108,19 @@ def thresholds_arg(thresholds):
     return a, a.ctypes.data
 
 
+def out_spec(shape):
+    """the three per-row outputs as a guard's spec"""
+    return dict(score=(np.float32, tuple(shape)), pairs=(np.int32, tuple(shape)), hits=(np.int32, tuple(shape)))
+
+
 def run_dev(codec, pt, mt, pp, mp, bound_t, n, rows, layout, slot, packed, cutoff=15.0, thresholds=None, guard=GUARD, expect=0):
     """fcz_lddt_dev (rows = L) or fcz_lddt_packed_dev (rows = R) on device tensors -> (score, pairs, hits) as numpy, guards checked"""
     import torch
-    total = rows if packed else n * rows
-    g = Guarded(total, guard)
+    g = DevGuarded(out_spec((rows,) if packed else (n, rows)), guard)
     fn = codec.lib.fcz_lddt_packed_dev if packed else codec.lib.fcz_lddt_dev
     keep, th = thresholds_arg(thresholds)
     torch.cuda.synchronize()
-    rc = fn(codec.ctx, pt.data_ptr(), mt.data_ptr(), pp.data_ptr(), None if mp is None else mp.data_ptr(), None if bound_t is None else bound_t.data_ptr(),
-            n, rows, layout, slot, cutoff, th, *g.ptrs())
+    rc = fn(codec.ctx, pt.data_ptr(), mt.data_ptr(), pp.data_ptr(), ptr(mp), ptr(bound_t), n, rows, layout, slot, cutoff, th, *g.ptrs())
     codec.synchronize()
     assert rc == expect, rc
-    return g.fetch((total,) if packed else (n, rows))
+    return g.all()

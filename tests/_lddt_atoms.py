@@ -9,13 +9,12 @@ import ctypes
 
 import numpy as np
 
-import _knn as K
+from _analysis import bits, chains_of, ptr, to14  # noqa: F401  (to14: re-exported for the tests)
 from _dense import expected_slot
-from _dssp import Guarded, _chains, _ptr
+from _devpath import GUARD, DevGuarded
 from _lddt import THRESHOLDS, _d, score_of
-from foldcomp_amd._aa_tables import ATOM_NAMES, RES_ATOMS
+from foldcomp_amd._aa_tables import ATOM_NAMES
 
-FILL, GUARD = K.FILL, K.GUARD
 F = np.float32
 WIDTH_LAYOUT = {37: "atom37", 14: "atom14", 4: "backbone4"}
 LAYOUT = {37: 0, 14: 1, 4: 2}
@@ -117,7 +116,7 @@ def lddt_atoms(pos_t, mask_t, pos_p, mask_p, aatype, bound, table, cutoff=15.0, 
     overlap), table [21, A] or None -> dict of KEYS; rows outside every chain hold 0"""
     lead, A = pos_t.shape[:-2], pos_t.shape[-2]
     out = {k: np.zeros(lead + ((A,) if k.startswith("atom_") else ()), DTYPES[k]) for k in KEYS}
-    for sel, _, m in _chains(pos_t.shape, bound, packed):
+    for sel, _, m in chains_of(pos_t.shape, bound, packed):
         if m == 0:
             continue
         got = lddt_atoms_chain(pos_t[sel], mask_t[sel], pos_p[sel], None if mask_p is None else mask_p[sel], None if aatype is None else aatype[sel],
@@ -140,24 +139,12 @@ def same(got, exp, what="", keys=KEYS):
         assert g.shape == e.shape, (what, k, g.shape, e.shape)
         if k == "score":
             assert g.dtype == e.dtype == np.float32, (what, k, g.dtype, e.dtype)
-            g, e = K.bits(g), K.bits(e)
+            g, e = bits(g), bits(e)
         elif k == "swapped":
             g, e = g.view(np.uint8), e.view(np.uint8)
         else:
             assert g.dtype == e.dtype == DTYPES[k], (what, k, g.dtype, e.dtype)
         assert np.array_equal(g, e), (what, k, np.argwhere(g != e)[:4], g[g != e][:4], e[g != e][:4])
-
-
-def to14(v37, aatype):
-    """per-slot values of atom37 [.., 37] or [.., 37, 3] -> atom14 through the slot map of every row's type, 0 where a type has no atom"""
-    slot = np.full((21, 14), -1, np.int64)
-    for ty in range(21):
-        for j, code in enumerate(RES_ATOMS[ty]):
-            slot[ty, j] = expected_slot("atom37", ty, code)
-    s = slot[np.minimum(aatype, 20)]
-    if v37.ndim == s.ndim + 1:
-        return np.where(s[..., None] >= 0, np.take_along_axis(v37, np.maximum(s, 0)[..., None], axis=-2), 0).astype(v37.dtype)
-    return np.where(s >= 0, np.take_along_axis(v37, np.maximum(s, 0), axis=-1), 0).astype(v37.dtype)
 
 
 def exchange(pos, aatype, rows, table):
@@ -168,24 +155,28 @@ def exchange(pos, aatype, rows, table):
     return np.take_along_axis(pos, sel[..., None], axis=-2)
 
 
-class Outputs:
-    """the device outputs for `total` rows of width A, 0xA5 everywhere with guard bytes on both sides"""
+def out_spec(lead, A, keys=KEYS):
+    """the outputs in `keys` for rows shaped `lead` of width A as a guard's spec"""
+    return {k: (DTYPES[k], tuple(lead) + ((A,) if k.startswith("atom_") else ())) for k in keys}
 
-    def __init__(self, total, A, guard=GUARD):
-        self.total, self.A = total, A
-        self.rows = Guarded(total, [DTYPES[k] for k in ROW_KEYS], guard)
-        self.atoms = Guarded(total * A, [DTYPES[k] for k in KEYS[4:]], guard)
+
+class Outputs:
+    """the device outputs, 0xA5 everywhere with guard bytes on both sides"""
+
+    def __init__(self, lead, A, guard=GUARD):
+        self.rows = DevGuarded(out_spec(lead, A, ROW_KEYS), guard)
+        self.atoms = DevGuarded(out_spec(lead, A, KEYS[4:]), guard)
 
     def struct(self, per_atom=True, **replace):
         from foldcomp_amd.structure import CLddtAtomsOut
-        ptr = dict(zip(KEYS, self.rows.ptrs() + (self.atoms.ptrs() if per_atom else [None, None])))
-        ptr.update(replace)
-        return CLddtAtomsOut(*(ptr[k] for k in KEYS))
+        at = dict(zip(KEYS, self.rows.ptrs() + (self.atoms.ptrs() if per_atom else [None, None])))
+        at.update(replace)
+        return CLddtAtomsOut(*(at[k] for k in KEYS))
 
-    def fetch(self, lead, per_atom=True):
-        out = dict(zip(ROW_KEYS, self.rows.fetch(tuple(lead))))
+    def fetch(self, per_atom=True):
+        out = dict(zip(ROW_KEYS, self.rows.all()))
         if per_atom:
-            out.update(zip(KEYS[4:], self.atoms.fetch(tuple(lead) + (self.A,))))
+            out.update(zip(KEYS[4:], self.atoms.all()))
         else:
             assert self.atoms.untouched()
         return out
@@ -194,21 +185,18 @@ class Outputs:
         return self.rows.untouched() and self.atoms.untouched()
 
 
-def run_dev(codec, pt, mt, pp, mp, aa, bound_t, n, rows, layout, packed, table=None, cutoff=15.0, thresholds=None, per_atom=True, guard=GUARD, expect=0,
-            keep=None):
+def run_dev(codec, pt, mt, pp, mp, aa, bound_t, n, rows, layout, packed, table=None, cutoff=15.0, thresholds=None, per_atom=True, guard=GUARD, expect=0):
     """fcz_lddt_atoms_dev (rows = L) or fcz_lddt_atoms_packed_dev (rows = R) on device tensors -> dict of the outputs as numpy, guards
-    checked; table: uint8 [21, A] on the host or None; keep: an Outputs to write into instead of a fresh one"""
+    checked; table: uint8 [21, A] on the host or None"""
     import torch
-    A = {0: 37, 1: 14, 2: 4}[layout]
-    total = rows if packed else n * rows
-    o = keep if keep is not None else Outputs(total, A, guard)
+    o = Outputs((rows,) if packed else (n, rows), {0: 37, 1: 14, 2: 4}[layout], guard)
     fn = codec.lib.fcz_lddt_atoms_packed_dev if packed else codec.lib.fcz_lddt_atoms_dev
     tab = None if table is None else np.ascontiguousarray(table, np.uint8)
     th = None if thresholds is None else np.asarray(thresholds, np.float32)
     c_out = o.struct(per_atom)
     torch.cuda.synchronize()
-    rc = fn(codec.ctx, pt.data_ptr(), mt.data_ptr(), pp.data_ptr(), _ptr(mp), _ptr(aa), _ptr(bound_t), n, rows, layout, float(cutoff),
+    rc = fn(codec.ctx, pt.data_ptr(), mt.data_ptr(), pp.data_ptr(), ptr(mp), ptr(aa), ptr(bound_t), n, rows, layout, float(cutoff),
             None if th is None else th.ctypes.data, None if tab is None else tab.ctypes.data, ctypes.byref(c_out))
     codec.synchronize()
     assert rc == expect, rc
-    return o.fetch((total,) if packed else (n, rows), per_atom)
+    return o.fetch(per_atom)

@@ -7,10 +7,9 @@ The area of a row is summed in float64 slot by slot. Nothing here is shared with
 the same geometry in float64 without the cull, for the comparison of the two."""
 import numpy as np
 
-import _knn as K
-from _dssp import Guarded, _chains, _ptr
+from _analysis import bits, chains_of, ptr
+from _devpath import GUARD, DevGuarded
 
-FILL, GUARD = K.FILL, K.GUARD
 F = np.float32
 FOUR_PI = float.fromhex("0x1.921fb54442d18p+3")
 BONDI = {"C": F(1.70), "N": F(1.55), "O": F(1.52), "S": F(1.80)}
@@ -97,7 +96,7 @@ def sasa(pos, mask, aatype, bound, table, probe, points, packed=False):
     """pos [n, L, A, 3] / [R, A, 3], mask, aatype or None, length [n] / None or row_off [n + 1] -> (sasa_points, sasa, sasa_mask)"""
     lead = pos.shape[:-2]
     out = [np.zeros(lead + (pos.shape[-2],), np.int16), np.zeros(lead, F), np.zeros(lead, bool)]
-    for sel, _, m in _chains(pos.shape, bound, packed):
+    for sel, _, m in chains_of(pos.shape, bound, packed):
         if m == 0:
             continue
         got = sasa_chain(pos[sel], mask[sel], None if aatype is None else aatype[sel], table, probe, points)
@@ -113,7 +112,7 @@ def same_sasa(got, exp, what=""):
         assert g.shape == e.shape, (what, name, g.shape, e.shape)
         if name == "sasa":
             assert g.dtype == e.dtype == np.float32, (what, g.dtype, e.dtype)
-            g, e = K.bits(g), K.bits(e)
+            g, e = bits(g), bits(e)
         elif name == "sasa_mask":
             g, e = g.view(np.uint8), e.view(np.uint8)
         else:
@@ -139,22 +138,25 @@ def default_table(A):
     return t
 
 
-def run_sasa(codec, pos_t, mask_t, aa_t, bound_t, n, rows, layout, packed, points_t, table=None, probe=PROBE, n_points=None, guard=GUARD, expect=0, keep=None):
+def out_spec(lead, A):
+    """the three outputs of rows shaped `lead` and width A as a guard's spec"""
+    lead = tuple(lead)
+    return dict(sasa_points=(np.int16, lead + (A,)), sasa=(np.float32, lead), sasa_mask=(np.uint8, lead))
+
+
+def run_sasa(codec, pos_t, mask_t, aa_t, bound_t, n, rows, layout, packed, points_t, table=None, probe=PROBE, n_points=None, guard=GUARD, expect=0):
     """fcz_sasa_dev (rows = L) or fcz_sasa_packed_dev (rows = R) on device tensors -> (sasa_points, sasa, sasa_mask) as numpy, guards
-    checked; table: float32 [21, A] on the host or None; keep: a Guarded to write into instead of a fresh one (refusals)"""
+    checked; table: float32 [21, A] on the host or None"""
     import torch
-    A = {0: 37, 1: 14, 2: 4}[layout]
-    total = rows if packed else n * rows
-    g = keep if keep is not None else [Guarded(total * A, (np.int16,), guard), Guarded(total, (np.float32, np.uint8), guard)]
+    g = DevGuarded(out_spec((rows,) if packed else (n, rows), {0: 37, 1: 14, 2: 4}[layout]), guard)
     fn = codec.lib.fcz_sasa_packed_dev if packed else codec.lib.fcz_sasa_dev
     tab = None if table is None else np.ascontiguousarray(table, F)
     torch.cuda.synchronize()
-    rc = fn(codec.ctx, pos_t.data_ptr(), mask_t.data_ptr(), _ptr(aa_t), _ptr(bound_t), n, rows, layout, None if tab is None else tab.ctypes.data, float(probe),
-            points_t.data_ptr(), int(points_t.shape[0]) if n_points is None else n_points, g[0].ptrs()[0], *g[1].ptrs())
+    rc = fn(codec.ctx, pos_t.data_ptr(), mask_t.data_ptr(), ptr(aa_t), ptr(bound_t), n, rows, layout, None if tab is None else tab.ctypes.data, float(probe),
+            points_t.data_ptr(), int(points_t.shape[0]) if n_points is None else n_points, *g.ptrs())
     codec.synchronize()
     assert rc == expect, rc
-    lead = (total,) if packed else (n, rows)
-    return g[0].fetch(lead + (A,)) + g[1].fetch(lead)
+    return g.all()
 
 
 def globule(rng, m, A=4, spread=None):

@@ -8,9 +8,9 @@ import ctypes
 
 import numpy as np
 
-import _knn as K
+from _analysis import pack, ptr  # noqa: F401  (pack: re-exported for the tests)
+from _devpath import GUARD, DevGuarded
 
-FILL, GUARD = K.FILL, K.GUARD
 GDT = (0.5, 1.0, 2.0, 4.0, 8.0)
 KEYS = ("rot", "trans", "rmsd", "sites", "gdt_counts", "tm", "dev")
 DTYPES = dict(rot=np.float32, trans=np.float32, rmsd=np.float32, sites=np.int32, gdt_counts=np.int32, tm=np.float32, dev=np.float32)
@@ -86,10 +86,6 @@ def superpose_packed(pos_t, mask_t, pos_p, mask_p, row_off, slot):
             out[k][e] = c[k]
         out["dev"][lo:hi] = c["dev"]
     return out
-
-
-def pack(arrays, lens):
-    return [np.concatenate([a[e, :m] for e, m in enumerate(lens)]) for a in arrays]
 
 
 def gdt_scores(counts, sites):
@@ -258,29 +254,14 @@ def same_bytes(a, b, what=""):
 
 # ---- the device calls -------------------------------------------------------------------------------------------------------------
 
-class Guarded:
-    """device outputs of the given byte sizes, 0xA5 everywhere, `guard` bytes in front and behind"""
-
-    def __init__(self, sizes, guard=GUARD):
-        import torch
-        self.sizes, self.guard = dict(sizes), guard
-        self.raw = {k: torch.full((guard + v + guard,), FILL, dtype=torch.uint8, device="cuda:0") for k, v in self.sizes.items()}
-
-    def ptr(self, k):
-        return self.raw[k].data_ptr() + self.guard
-
-    def fetch(self, k, dtype, shape):
-        a = self.raw[k].cpu().numpy()
-        g, v = self.guard, self.sizes[k]
-        assert (a[:g] == FILL).all() and (a[g + v:] == FILL).all(), f"guard bytes of {k} overwritten"
-        return a[g:g + v].copy().view(dtype).reshape(shape)
-
-    def untouched(self):
-        return all(bool((t == FILL).all()) for t in self.raw.values())
-
-
 def out_shapes(n, rows, packed):
     return dict(rot=(n, 3, 3), trans=(n, 3), rmsd=(n,), sites=(n,), gdt_counts=(n, 5), tm=(n,), dev=(rows,) if packed else (n, rows))
+
+
+def out_spec(n, rows, packed, want=KEYS):
+    """the outputs in `want` as a guard's spec"""
+    shapes = out_shapes(n, rows, packed)
+    return {k: (DTYPES[k], shapes[k]) for k in want}
 
 
 def run_dev(codec, pt, mt, pp, mp, bound_t, n, rows, layout, slot, packed, want=KEYS, guard=GUARD, expect=0):
@@ -288,27 +269,23 @@ def run_dev(codec, pt, mt, pp, mp, bound_t, n, rows, layout, slot, packed, want=
     in `want` (the others are passed as NULL), guards checked"""
     import torch
     from foldcomp_amd.structure import CSuperposeOut
-    shapes = out_shapes(n, rows, packed)
-    g = Guarded({k: 4 * int(np.prod(shapes[k])) for k in want}, guard)
+    g = DevGuarded(out_spec(n, rows, packed, want), guard)
     out = CSuperposeOut(*(g.ptr(k) if k in want else None for k in KEYS))
     fn = codec.lib.fcz_superpose_packed_dev if packed else codec.lib.fcz_superpose_dev
     torch.cuda.synchronize()
-    rc = fn(codec.ctx, pt.data_ptr(), mt.data_ptr(), pp.data_ptr(), None if mp is None else mp.data_ptr(), None if bound_t is None else bound_t.data_ptr(),
-            n, rows, layout, slot, ctypes.byref(out))
+    rc = fn(codec.ctx, pt.data_ptr(), mt.data_ptr(), pp.data_ptr(), ptr(mp), ptr(bound_t), n, rows, layout, slot, ctypes.byref(out))
     codec.synchronize()
     assert rc == expect, rc
-    return {k: g.fetch(k, DTYPES[k], shapes[k]) for k in want}
+    return {k: g.fetch(k) for k in want}
 
 
 def run_apply(codec, pos_t, mask_t, bound_t, n, rows, layout, rot_t, trans_t, packed, guard=GUARD, expect=0):
     """fcz_superpose_apply_dev / _packed_dev on device tensors -> pos_out as numpy of the shape of pos, guards checked"""
     import torch
-    shape = tuple(pos_t.shape)
-    g = Guarded({"out": 4 * int(np.prod(shape))}, guard)
+    g = DevGuarded({"out": (F, tuple(pos_t.shape))}, guard)
     fn = codec.lib.fcz_superpose_apply_packed_dev if packed else codec.lib.fcz_superpose_apply_dev
     torch.cuda.synchronize()
-    rc = fn(codec.ctx, pos_t.data_ptr(), None if mask_t is None else mask_t.data_ptr(), None if bound_t is None else bound_t.data_ptr(), n, rows, layout,
-            rot_t.data_ptr(), trans_t.data_ptr(), g.ptr("out"))
+    rc = fn(codec.ctx, pos_t.data_ptr(), ptr(mask_t), ptr(bound_t), n, rows, layout, rot_t.data_ptr(), trans_t.data_ptr(), g.ptr("out"))
     codec.synchronize()
     assert rc == expect, rc
-    return g.fetch("out", F, shape)
+    return g.fetch("out")

@@ -11,6 +11,8 @@ import numpy as np
 
 import _superpose as SP
 import _tmscore as TM
+from _analysis import ptr
+from _devpath import DevGuarded
 
 F = np.float32
 Q = 65536
@@ -449,9 +451,14 @@ def to_device(s):
 def c_set(d):
     from foldcomp_amd.structure import CChainSet
     packed = d.get("row_off") is not None
-    ptr = lambda t: None if t is None else t.data_ptr()
     return CChainSet(d["pos"].data_ptr(), d["mask"].data_ptr(), None if packed else ptr(d.get("length")), ptr(d.get("row_off")) if packed else None,
                      len(d["row_off"]) - 1 if packed else d["pos"].shape[0], d["pos"].shape[0] if packed else d["pos"].shape[1])
+
+
+def out_spec(m, wa, want=KEYS):
+    """the outputs in `want` for m pairs of width wa as a guard's spec"""
+    spec = {k: (d, (m,) + ((wa,) if tail == "wa" else tail)) for k, d, tail in OUTPUTS}
+    return {k: spec[k] for k in want}
 
 
 def run_dev(codec, da, db, pairs_t, wa, wb, layout, slot, want=KEYS, expect=0, m=None, **params):
@@ -460,36 +467,32 @@ def run_dev(codec, da, db, pairs_t, wa, wb, layout, slot, want=KEYS, expect=0, m
     from foldcomp_amd.structure import CTmAlignOut, CTmAlignParams
     p = dict(DEFAULTS, **params)
     m = len(pairs_t) if m is None else m
-    shapes = {k: (m,) + ((wa,) if tail == "wa" else tail) for k, _, tail in OUTPUTS}
-    g = SP.Guarded({k: 4 * int(np.prod(shapes[k])) for k in want})
+    g = DevGuarded(out_spec(m, wa, want))
     out = CTmAlignOut(*(g.ptr(k) if k in want else None for k in KEYS))
     par = CTmAlignParams(int(p["fragments"]), p["refine"], p["dp_rounds"], len(p["gaps"]), (ctypes.c_double * 4)(*p["gaps"][:4]), p["levels"], p["iterations"])
     sa, sb = c_set(da), c_set(db)
     torch.cuda.synchronize()
-    rc = codec.lib.fcz_tmalign_dev(codec.ctx, ctypes.byref(sa), ctypes.byref(sb), None if pairs_t is None else pairs_t.data_ptr(), m, wa, wb, layout, slot,
-                                   ctypes.byref(par), ctypes.byref(out))
+    rc = codec.lib.fcz_tmalign_dev(codec.ctx, ctypes.byref(sa), ctypes.byref(sb), ptr(pairs_t), m, wa, wb, layout, slot, ctypes.byref(par), ctypes.byref(out))
     codec.synchronize()
     assert rc == expect, rc
     if expect:
         assert g.untouched()
         return None
-    dt = {k: d for k, d, _ in OUTPUTS}
-    return {k: g.fetch(k, dt[k], shapes[k]) for k in want}
+    return {k: g.fetch(k) for k in want}
 
 
 def run_dp_dev(codec, da, db, pairs_t, wa, wb, layout, slot, rot_t, trans_t, gap, expect=0, want_aligned=True):
     """fcz_tmalign_dp_dev -> (map, aligned), guards checked"""
     import torch
     m = len(pairs_t)
-    g = SP.Guarded(dict(map=4 * m * wa, aligned=4 * m))
+    g = DevGuarded(out_spec(m, wa, ("map", "aligned")))
     sa, sb = c_set(da), c_set(db)
     torch.cuda.synchronize()
-    rc = codec.lib.fcz_tmalign_dp_dev(codec.ctx, ctypes.byref(sa), ctypes.byref(sb), pairs_t.data_ptr(), m, wa, wb, layout, slot,
-                                      None if rot_t is None else rot_t.data_ptr(), None if trans_t is None else trans_t.data_ptr(), gap, g.ptr("map"),
-                                      g.ptr("aligned") if want_aligned else None)
+    rc = codec.lib.fcz_tmalign_dp_dev(codec.ctx, ctypes.byref(sa), ctypes.byref(sb), pairs_t.data_ptr(), m, wa, wb, layout, slot, ptr(rot_t), ptr(trans_t), gap,
+                                      g.ptr("map"), g.ptr("aligned") if want_aligned else None)
     codec.synchronize()
     assert rc == expect, rc
     if expect:
         assert g.untouched()
         return None
-    return g.fetch("map", np.int32, (m, wa)), g.fetch("aligned", np.int32, (m,))
+    return g.all()

@@ -9,6 +9,8 @@ import functools
 import numpy as np
 
 import _superpose as SP
+from _analysis import ptr
+from _devpath import GUARD, DevGuarded
 
 F = np.float32
 KEYS = SP.KEYS + ("seed", "selected")
@@ -256,21 +258,25 @@ def out_shapes(n, rows, packed):
     return dict(SP.out_shapes(n, rows, packed), seed=(n,), selected=(n,))
 
 
-def run_dev(codec, pt, mt, pp, mp, bound_t, n, rows, layout, slot, packed, iterations=20, levels=0, want=KEYS, guard=SP.GUARD, expect=0):
+def out_spec(n, rows, packed, want=KEYS):
+    """the outputs in `want` as a guard's spec"""
+    shapes = out_shapes(n, rows, packed)
+    return {k: (DTYPES[k], shapes[k]) for k in want}
+
+
+def run_dev(codec, pt, mt, pp, mp, bound_t, n, rows, layout, slot, packed, iterations=20, levels=0, want=KEYS, guard=GUARD, expect=0):
     """fcz_tmscore_dev (rows = L) or fcz_tmscore_packed_dev (rows = R) on device tensors -> dict of numpy arrays for the outputs in
     `want` (the others are passed as NULL), guards checked"""
     import torch
     from foldcomp_amd.structure import CTmScoreOut
-    shapes = out_shapes(n, rows, packed)
-    g = SP.Guarded({k: 4 * int(np.prod(shapes[k])) for k in want}, guard)
+    g = DevGuarded(out_spec(n, rows, packed, want), guard)
     out = CTmScoreOut(*(g.ptr(k) if k in want else None for k in KEYS))
     fn = codec.lib.fcz_tmscore_packed_dev if packed else codec.lib.fcz_tmscore_dev
     torch.cuda.synchronize()
-    rc = fn(codec.ctx, pt.data_ptr(), mt.data_ptr(), pp.data_ptr(), None if mp is None else mp.data_ptr(), None if bound_t is None else bound_t.data_ptr(),
-            n, rows, layout, slot, levels, iterations, ctypes.byref(out))
+    rc = fn(codec.ctx, pt.data_ptr(), mt.data_ptr(), pp.data_ptr(), ptr(mp), ptr(bound_t), n, rows, layout, slot, levels, iterations, ctypes.byref(out))
     codec.synchronize()
     assert rc == expect, rc
     if expect:
         assert g.untouched()
         return None
-    return {k: g.fetch(k, DTYPES[k], shapes[k]) for k in want}
+    return {k: g.fetch(k) for k in want}

@@ -8,12 +8,11 @@ import ctypes
 
 import numpy as np
 
-import _knn as K
+from _analysis import bits as bits_of, chains_of, ptr           # (violations_chain has a local `bits`)
 from _dense import ATOM37
-from _dssp import Guarded, _chains, _ptr
+from _devpath import GUARD, DevGuarded
 from _sasa import atoms_of, default_table  # noqa: F401  (default_table: the radii, re-exported for the tests)
 
-FILL, GUARD = K.FILL, K.GUARD
 F = np.float32
 TOL, FACTOR = F(1.5), F(12.0)
 CYS, PRO = 4, 14
@@ -123,7 +122,7 @@ def violations(pos, mask, aatype, bound, table, tol=TOL, factor=FACTOR, packed=F
     out = dict(clash_atom=np.zeros(lead + (A,), np.uint8), clash_count=np.zeros(lead, np.int32), clash_depth=np.zeros(lead, F),
                clash_partner=np.full(lead, -1, np.int32), viol_mask=np.zeros(lead, bool), link_mask=np.zeros(lead, bool), link_length=np.zeros(lead, F),
                link_cos=np.zeros(lead + (2,), F), link_violation=np.zeros(lead, np.uint8), chain_counts=np.zeros((n, 4), np.int64))
-    chains = _chains(pos.shape, bound, packed)
+    chains = chains_of(pos.shape, bound, packed)
     entries = [e for e in range(n) if not packed or min(int(bound[e + 1]), pos.shape[0]) > min(int(bound[e]), pos.shape[0])]
     assert len(entries) == len(chains)
     for e, (sel, _, m) in zip(entries, chains):
@@ -143,7 +142,7 @@ def same_violations(got, exp, what=""):
         assert g.shape == e.shape, (what, k, g.shape, e.shape)
         if DTYPES[k] == np.float32:
             assert g.dtype == e.dtype == np.float32, (what, k, g.dtype, e.dtype)
-            g, e = K.bits(g), K.bits(e)
+            g, e = bits_of(g), bits_of(e)
         elif DTYPES[k] == np.uint8:
             g, e = g.view(np.uint8), e.view(np.uint8)
         else:
@@ -155,7 +154,7 @@ def consistent(v, bound=None, packed=False):
     """chain_counts against the per-row outputs of the same dict"""
     lead = v["clash_count"].shape
     n = v["chain_counts"].shape[0]
-    chains = _chains(lead + (1, 3), bound, packed)
+    chains = chains_of(lead + (1, 3), bound, packed)
     entries = [e for e in range(n) if not packed or min(int(bound[e + 1]), lead[0]) > min(int(bound[e]), lead[0])]
     total = np.zeros((n, 4), np.int64)
     for e, (sel, _, m) in zip(entries, chains):
@@ -166,42 +165,43 @@ def consistent(v, bound=None, packed=False):
     assert np.array_equal(v["chain_counts"][:, 1:], total[:, 1:]), (v["chain_counts"], total)
 
 
-class Outputs:
-    """the ten device outputs for `total` rows of width A and n chains, 0xA5 everywhere with guard bytes on both sides"""
+def out_spec(lead, A, n):
+    """the ten outputs for rows shaped `lead` of width A and n chains as a guard's spec"""
+    tail = dict(clash_atom=(A,), link_cos=(2,))
+    return {k: (DTYPES[k], (n, 4) if k == "chain_counts" else tuple(lead) + tail.get(k, ())) for k in KEYS}
 
-    def __init__(self, total, A, n, guard=GUARD):
-        self.total, self.A, self.n = total, A, n
-        count = dict(clash_atom=total * A, link_cos=total * 2, chain_counts=n * 4)
-        self.g = {k: Guarded(count.get(k, total), (DTYPES[k],), guard) for k in KEYS}
+
+class Outputs:
+    """the ten device outputs, 0xA5 everywhere with guard bytes on both sides"""
+
+    def __init__(self, lead, A, n, guard=GUARD):
+        self.g = DevGuarded(out_spec(lead, A, n), guard)
 
     def struct(self, **replace):
         from foldcomp_amd.structure import CViolationsOut
-        return CViolationsOut(*(replace[k] if k in replace else self.g[k].ptrs()[0] for k in KEYS))
+        return CViolationsOut(*(replace[k] if k in replace else self.g.ptr(k) for k in KEYS))
 
-    def fetch(self, lead):
-        tail = dict(clash_atom=(self.A,), link_cos=(2,))
-        return {k: self.g[k].fetch((self.n, 4) if k == "chain_counts" else tuple(lead) + tail.get(k, ()))[0] for k in KEYS}
+    def fetch(self):
+        return {k: self.g.fetch(k) for k in KEYS}
 
     def untouched(self):
-        return all(g.untouched() for g in self.g.values())
+        return self.g.untouched()
 
 
-def run_violations(codec, pos_t, mask_t, aa_t, bound_t, n, rows, layout, packed, table=None, tol=TOL, factor=FACTOR, guard=GUARD, expect=0, keep=None):
+def run_violations(codec, pos_t, mask_t, aa_t, bound_t, n, rows, layout, packed, table=None, tol=TOL, factor=FACTOR, guard=GUARD, expect=0):
     """fcz_violations_dev (rows = L) or fcz_violations_packed_dev (rows = R) on device tensors -> dict of the ten outputs as numpy, guards
-    checked; table: float32 [21, A] on the host or None; keep: an Outputs to write into instead of a fresh one (refusals)"""
+    checked; table: float32 [21, A] on the host or None"""
     import torch
-    A = {0: 37, 1: 14, 2: 4}[layout]
-    total = rows if packed else n * rows
-    o = keep if keep is not None else Outputs(total, A, n, guard)
+    o = Outputs((rows,) if packed else (n, rows), {0: 37, 1: 14, 2: 4}[layout], n, guard)
     fn = codec.lib.fcz_violations_packed_dev if packed else codec.lib.fcz_violations_dev
     tab = None if table is None else np.ascontiguousarray(table, F)
     c_out = o.struct()
     torch.cuda.synchronize()
-    rc = fn(codec.ctx, pos_t.data_ptr(), mask_t.data_ptr(), _ptr(aa_t), _ptr(bound_t), n, rows, layout, None if tab is None else tab.ctypes.data, float(tol),
+    rc = fn(codec.ctx, pos_t.data_ptr(), mask_t.data_ptr(), ptr(aa_t), ptr(bound_t), n, rows, layout, None if tab is None else tab.ctypes.data, float(tol),
             float(factor), ctypes.byref(c_out))
     codec.synchronize()
     assert rc == expect, rc
-    return o.fetch((total,) if packed else (n, rows))
+    return o.fetch()
 
 
 def chain_of_text(text, aa3):

@@ -6,13 +6,12 @@ import numpy as np
 
 import _dense as D
 from _cases import entries_blob
-from _devpath import DevRecords, to_dev
+from _devpath import FILL, DevRecords, to_dev
 from foldcomp_amd import _lib
 from foldcomp_amd.structure import CAtomsOut, CDenseOut
 
 KEYS = ("pos", "mask", "aatype", "plddt", "res_index", "length")
 PAD = dict(pos=0, mask=0, aatype=20, plddt=0, res_index=0)
-FILL = 0xA5
 NO_START = object()                            # fcz_dense_dev itself, not the windowed call
 
 

@@ -13,6 +13,7 @@ import _angles as A
 import _dense as D
 import _harness as H
 import _undense as U
+from _analysis import bits
 from _cases import entries_blob
 from _devpath import DevRecords, compress_dev
 from _window import same, sweep_starts, window_of
@@ -169,7 +170,7 @@ class _Calls:
         got = self.codec.decompress_dense(*entries_blob(self.gold), layout=layout, max_len=L if crop else None)
         assert not got["status"].any() and got["pos"].shape == (len(self.gold), L, D.WIDTH[layout], 3)
         for k in ("pos", "plddt"):
-            assert np.array_equal(D.bits(got[k]), D.bits(want[k])), (layout, L, k)
+            assert np.array_equal(bits(got[k]), bits(want[k])), (layout, L, k)
         for k in ("mask", "aatype", "res_index", "length"):
             assert np.array_equal(got[k].astype(np.int64), want[k].astype(np.int64)), (layout, L, k)
 

@@ -10,7 +10,7 @@ import pytest
 
 import _dense as D
 from _cases import entries_blob
-from _devpath import HostGuarded, to_dev
+from _devpath import FILL, HostGuarded, to_dev
 from _window import KEYS, Decoded
 from foldcomp_amd import _lib, synthetic
 from foldcomp_amd.structure import CAtomsOut, CDenseOut, CPackedOut
@@ -22,7 +22,6 @@ WIDTHS = (0, 1, 64, 65, 200)            # 0: the longest entry
 INVALID = -1                            # FCZ_E_INVALID_ARG
 COLS = 10                               # FCZ_ANGLE_COLUMNS
 NUL = 0x100                             # FCZ_PDB_NUL_TERMINATED
-FILL = HostGuarded.FILL
 OPTIONAL = ("aatype", "plddt", "res_index", "length")
 DT = dict(pos=np.float32, mask=np.uint8, aatype=np.uint8, plddt=np.float32, res_index=np.int32, chain_index=np.int32, length=np.uint32)
 PACKED_KEYS = ("pos", "mask", "aatype", "plddt", "res_index", "chain_index", "length")

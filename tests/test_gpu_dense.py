@@ -8,7 +8,7 @@ import pytest
 
 import _dense as D
 import _harness as H
-from _cases import compress_cases, db_cases, entries_blob
+from _cases import db_cases, entries_blob, golden_records_raw
 from _devpath import DevRecords
 from foldcomp_amd import _lib, fczfile
 from foldcomp_amd._aa_tables import ATOM_NAMES, RES3, RES_NATOMS
@@ -60,10 +60,7 @@ def dense_dev(codec, entries, layout, L, alt_order=False, want=KEYS):
 
 @pytest.fixture(scope="module")
 def records(golden):
-    z, index = golden
-    names = compress_cases(index) + db_cases(index)
-    assert len(names) == 56
-    return names, [z[f"{n}/fcz"].tobytes() for n in names]
+    return golden_records_raw(golden)
 
 
 @pytest.fixture(scope="module")

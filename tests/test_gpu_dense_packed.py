@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 
 import _dense as D
-from _cases import compress_cases, db_cases, entries_blob
+from _cases import db_cases, entries_blob, golden_records_raw
 from _devpath import DevRecords
 from foldcomp_amd import _lib, fczfile
 from foldcomp_amd.structure import CAtomsOut, CDenseOut, CPackedOut
@@ -93,10 +93,7 @@ def padded_dev(codec, entries, layout, L):
 
 @pytest.fixture(scope="module")
 def records(golden):
-    z, index = golden
-    names = compress_cases(index) + db_cases(index)
-    assert len(names) == 56
-    return names, [z[f"{n}/fcz"].tobytes() for n in names]
+    return golden_records_raw(golden)
 
 
 @pytest.fixture(scope="module")

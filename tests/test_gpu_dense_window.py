@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 
 import _dense as D
-from _cases import compress_cases, db_cases, entries_blob
+from _cases import db_cases, entries_blob, golden_records_raw
 from _window import KEYS, Decoded, raw_bits, same, sweep_starts, window_of
 from foldcomp_amd import fczfile
 
@@ -17,10 +17,7 @@ pytestmark = pytest.mark.gpu
 
 @pytest.fixture(scope="module")
 def records(golden):
-    z, index = golden
-    names = compress_cases(index) + db_cases(index)
-    assert len(names) == 56
-    return names, [z[f"{n}/fcz"].tobytes() for n in names]
+    return golden_records_raw(golden)
 
 
 @pytest.fixture(scope="module")

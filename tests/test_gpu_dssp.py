@@ -5,36 +5,31 @@ write into arrays pre-filled with 0xA5 with guard bytes on both sides."""
 import numpy as np
 import pytest
 
+import _analysis as AN
 import _dense as DN
 import _dssp as D
 import _knn as K
-from _cases import compress_cases, db_cases
-from _devpath import HostGuarded, host_ptr, to_dev
-from _window import Decoded
+from _analysis import NAN_BITS
+from _cases import golden_records_raw
+from _devpath import DevGuarded, HostGuarded, host_ptr, to_dev
 from foldcomp_amd import _lib
 
 pytestmark = pytest.mark.gpu
 
 L_GOLD = 1400
-NAN_BITS = np.uint32(0x7FC00123)
 F = np.float32
 
 
 @pytest.fixture(scope="module")
 def records(golden):
-    z, index = golden
-    names = compress_cases(index) + db_cases(index)
-    assert len(names) == 56
-    return [z[f"{n}/fcz"].tobytes() for n in names]
+    return golden_records_raw(golden)[1]
 
 
 @pytest.fixture(scope="module")
 def gold(codec, records):
     """the 56 golden records as atom37 / atom14 / backbone4 at L = 1400 on the host and the device, and the restatement on atom37:
     computed once, never changed"""
-    dec = Decoded(codec, records)
-    host = {lay: dec.dense(lay, L_GOLD, want=("pos", "mask", "aatype", "length")) for lay in DN.LAYOUTS}
-    dev = {lay: {k: to_dev(v) for k, v in host[lay].items()} for lay in DN.LAYOUTS}
+    host, dev = AN.decoded_layouts(codec, records, L_GOLD, ("pos", "mask", "aatype", "length"))
     a = host["atom37"]
     assert a["length"].max() == L_GOLD
     tables = D.hbonds(a["pos"], a["mask"], a["aatype"], a["length"])
@@ -68,13 +63,11 @@ def test_golden_padded(codec, gold):
 def test_golden_packed(codec, gold):
     h = gold["host"]["atom37"]
     lens = np.minimum(h["length"].astype(np.int64), L_GOLD)
-    row_off = np.concatenate([[0], np.cumsum(lens)]).astype(np.uint32)
+    row_off = AN.row_off_of(lens)
     R = int(row_off[-1])
-    cat = lambda a: np.concatenate([a[e, :m] for e, m in enumerate(lens)])
+    cat = lambda a: AN.pack1(a, lens)
     exp = D.hbonds(cat(h["pos"]), cat(h["mask"]), cat(h["aatype"]), row_off, packed=True)
-    shifted = [np.concatenate([np.where(a[e, :m] >= 0, a[e, :m] + int(row_off[e]), -1).astype(np.int32) if a.dtype == np.int32 else a[e, :m]
-                               for e, m in enumerate(lens)]) for a in gold["tables"]]
-    D.same_tables(exp, shifted, "restatement, packed against padded")
+    D.same_tables(exp, _shift(gold["tables"], lens, row_off), "restatement, packed against padded")
     for lay in DN.LAYOUTS:
         hh = gold["host"][lay]
         pos, mask, aa, ro = to_dev(cat(hh["pos"])), to_dev(cat(hh["mask"])), to_dev(cat(hh["aatype"])), to_dev(row_off)
@@ -134,10 +127,6 @@ def _synthetic(lens, L, seed):
     return pos, mask, aatype
 
 
-def _pack(arrays, lens):
-    return [np.concatenate([a[e, :m] for e, m in enumerate(lens)]) for a in arrays]
-
-
 def _shift(tables, lens, row_off):
     return [np.concatenate([np.where(a[e, :m] >= 0, a[e, :m] + int(row_off[e]), -1).astype(np.int32) if a.dtype == np.int32 else a[e, :m]
                             for e, m in enumerate(lens)]) for a in tables]
@@ -152,7 +141,7 @@ def synthetic():
     L = max(lens)
     pos, mask, aa = _synthetic(lens, L, 11)
     ln = np.asarray(lens, np.uint32)
-    row_off = np.concatenate([[0], np.cumsum(lens)]).astype(np.uint32)
+    row_off = AN.row_off_of(lens)
     exp = D.hbonds(pos, mask, aa, ln)
     lab = D.labels(pos, mask, ln, exp[0], exp[1])
     ai, ae = exp[0], exp[1]
@@ -178,14 +167,14 @@ def test_synthetic_padded_and_packed(codec, synthetic):
     # two calls give the same bits
     D.same_tables(D.run_hbond(codec, pos, mask, aa, to_dev(s["lens"]), n, s["L"], 2, False), got, "again")
     # packed
-    packed = _pack(s["arrays"], s["lens"])
+    packed = AN.pack(s["arrays"], s["lens"])
     R = int(s["row_off"][-1])
     exp_packed = _shift(s["exp"], s["lens"], s["row_off"])
     D.same_tables(D.hbonds(*packed, s["row_off"], packed=True), exp_packed, "restatement, packed")
     pp, pm, pa = (to_dev(a) for a in packed)
     gp = D.run_hbond(codec, pp, pm, pa, to_dev(s["row_off"]), n, R, 2, True)
     D.same_tables(gp, exp_packed, "packed")
-    lab_packed = _pack(s["lab"], s["lens"])
+    lab_packed = AN.pack(s["lab"], s["lens"])
     D.same_labels(D.run_labels(codec, pp, pm, None, to_dev(s["row_off"]), n, R, 2, True, to_dev(gp[0]), to_dev(gp[1])), lab_packed, "packed labels")
     # the host-pointer forms run both steps
     h = codec.secondary_structure(*s["arrays"], length=s["lens"])
@@ -219,8 +208,7 @@ def test_hostile_row_off(codec):
     pos[:] = D.ideal_backbone(-57, -47, R)[0] * (mask[..., None] != 0)
     pos.view(np.uint32)[mask == 0] = NAN_BITS
     dev = [to_dev(a) for a in (pos, mask, aa)]
-    # chain 0 runs backwards (empty), rows 0 .. 39 are left uncovered, chain 4 runs past R (clamped to the rows that exist)
-    row_off = np.asarray([300, 40, 120, 400, 401, 950], np.uint32)
+    row_off = AN.HOSTILE_ROW_OFF
     exp = D.hbonds(pos, mask, aa, row_off, packed=True)
     got = D.run_hbond(codec, *dev, to_dev(row_off), 5, R, 2, True)
     D.same_tables(got, exp, "hostile row_off")
@@ -232,8 +220,7 @@ def test_hostile_row_off(codec):
 
     def host_form(n, tables, labels):
         """fcz_dssp_packed on the same host arrays, its outputs between guard bytes: what the two device steps gave"""
-        h = HostGuarded(dict(acc_index=(np.int32, (R, 2)), acc_energy=(F, (R, 2)), don_index=(np.int32, (R, 2)), don_energy=(F, (R, 2)),
-                             ss=(np.uint8, (R,)), ss_mask=(np.uint8, (R,))))
+        h = HostGuarded(dict(D.table_spec((R,)), ss=(np.uint8, (R,)), ss_mask=(np.uint8, (R,))))
         assert codec.lib.fcz_dssp_packed(codec.ctx, host_ptr(pos), host_ptr(mask), host_ptr(aa), host_ptr(row_off), n, R, 2, *h.ptrs()) == 0
         out = h.all()
         D.same_tables(out[:4], tables, f"fcz_dssp_packed n={n}")
@@ -281,10 +268,8 @@ def test_label_kernel_alone_on_random_tables(codec):
 def test_refusals_leave_the_outputs_untouched(codec):
     import torch
     n, L, A = 2, 8, 37
-    pos = torch.zeros((n, L, A, 3), dtype=torch.float32, device="cuda:0")
-    mask = torch.ones((n, L, A), dtype=torch.uint8, device="cuda:0")
-    off = to_dev(np.asarray([0, 8, 16], np.uint32))
-    g = D.Guarded(n * L * 2, (np.int32, np.float32, np.int32, np.float32))
+    pos, mask, _, off = AN.refusal_inputs(n, L, A)
+    g = DevGuarded(D.table_spec((n * L,)))
     o = g.ptrs()
     lib, ctx, P, M, O = codec.lib, codec.ctx, pos.data_ptr(), mask.data_ptr(), off.data_ptr()
     ok = dict(ctx=ctx, pos=P, mask=M, aa=None, bound=None, n=n, L=L, layout=0, o0=o[0], o1=o[1], o2=o[2], o3=o[3])
@@ -356,8 +341,7 @@ def test_foldcomp_secondary_structure(codec, gold, records):
     p = foldcomp.decode_tensors(records, codec=codec, packed=True, secondary_structure=True)
     cu = p["cu_seqlens"].cpu().numpy()
     lens = np.diff(cu)
-    cat = lambda a: np.concatenate([a[e, :m] for e, m in enumerate(lens)])
-    D.same_labels(_labels(p), [cat(a) for a in gold["labels"]], "packed decode_tensors")
+    D.same_labels(_labels(p), AN.pack(gold["labels"], lens), "packed decode_tensors")
     po = foldcomp.secondary_structure(p, codec=codec)
     D.same_labels(_labels(po), _labels(p), "packed secondary_structure")
     D.same_tables(_tables(po), _shift(gold["tables"], lens, cu), "packed tables")

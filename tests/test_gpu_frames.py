@@ -4,11 +4,11 @@ pre-filled with 0xA5 with guard bytes on both sides, so a byte the call leaves u
 import numpy as np
 import pytest
 
+import _analysis as AN
 import _dense as D
 import _frames as F
-from _cases import compress_cases, db_cases
-from _devpath import HostGuarded, host_ptr, to_dev
-from _window import Decoded
+from _cases import db_cases, golden_records_raw
+from _devpath import DevGuarded, HostGuarded, host_ptr, to_dev
 
 pytestmark = pytest.mark.gpu
 
@@ -19,19 +19,14 @@ TILE_ALL, TILE_BACKBONE = 32, 256                                    # rows per 
 
 @pytest.fixture(scope="module")
 def records(golden):
-    z, index = golden
-    names = compress_cases(index) + db_cases(index)
-    assert len(names) == 56
-    return [z[f"{n}/fcz"].tobytes() for n in names]
+    return golden_records_raw(golden)[1]
 
 
 @pytest.fixture(scope="module")
 def gold(codec, records):
     """the 56 golden records as atom37 / atom14 / backbone4 at L = 1400 (host and device) and the restatement with groups = all on
     each: computed once, never changed"""
-    dec = Decoded(codec, records)
-    host = {lay: dec.dense(lay, L_GOLD, want=("pos", "mask", "aatype", "length")) for lay in D.LAYOUTS}
-    dev = {lay: {k: to_dev(v) for k, v in host[lay].items()} for lay in D.LAYOUTS}
+    host, dev = AN.decoded_layouts(codec, records, L_GOLD, ("pos", "mask", "aatype", "length"))
     assert host["atom37"]["length"].max() == L_GOLD
     exp = {lay: F.frames(h["pos"], h["mask"], h["aatype"], h["length"], D.LAYOUTS[lay], ALL) for lay, h in host.items()}
     return dict(host=host, dev=dev, n=len(records), exp=exp)
@@ -68,7 +63,7 @@ def test_golden_backbone_is_column_0(codec, gold):
 def test_golden_packed(codec, gold):
     h = gold["host"]["atom37"]
     lens = np.minimum(h["length"].astype(np.int64), L_GOLD)
-    cat = lambda a: np.concatenate([a[e, :m] for e, m in enumerate(lens)])
+    cat = lambda a: AN.pack1(a, lens)
     pos, mask, aa = cat(h["pos"]), cat(h["mask"]), cat(h["aatype"])
     R = len(pos)
     exp = tuple(cat(x)[None] for x in gold["exp"]["atom37"])
@@ -143,12 +138,12 @@ def test_synthetic_row_counts(codec, pools, rows):
 
 def test_no_entries(codec, pools):
     pos, mask, aa = pools[0]["dev"]
-    g = F.Guarded(64)
+    g = DevGuarded(F.out_spec((8,), 8))
     rp, tp, fp = g.ptrs()
     assert codec.lib.fcz_frames_dev(codec.ctx, pos.data_ptr(), mask.data_ptr(), aa.data_ptr(), None, 0, 8, 0, ALL, rp, tp, fp) == 0
     codec.synchronize()
     assert g.untouched()
-    h = HostGuarded(dict(rot=(np.float32, (64, 3, 3)), trans=(np.float32, (64, 3)), frame_mask=(np.uint8, (64,))))
+    h = HostGuarded(F.out_spec((8,), 8))
     host = [host_ptr(np.ascontiguousarray(pools[0][k])) for k in ("pos", "mask", "aa")]
     assert codec.lib.fcz_frames(codec.ctx, *host, None, 0, 8, 0, ALL, *h.ptrs()) == 0
     assert h.untouched()
@@ -190,10 +185,8 @@ def test_length_and_unaligned_arrays(codec, pools, layout):
 def test_refusals_leave_the_outputs_untouched(codec):
     import torch
     n, L, A = 2, 8, 37
-    pos = torch.zeros((n, L, A, 3), dtype=torch.float32, device="cuda:0")
-    mask = torch.ones((n, L, A), dtype=torch.uint8, device="cuda:0")
-    aa = torch.zeros((n, L), dtype=torch.uint8, device="cuda:0")
-    g = F.Guarded(n * L * 8)
+    pos, mask, aa, _ = AN.refusal_inputs(n, L, A)
+    g = DevGuarded(F.out_spec((n, L), 8))
     rp, tp, fp = g.ptrs()
     lib, ctx, P, M, T = codec.lib, codec.ctx, pos.data_ptr(), mask.data_ptr(), aa.data_ptr()
     bad = [(None, P, M, T, None, n, L, 0, ALL, rp, tp, fp), (ctx, None, M, T, None, n, L, 0, ALL, rp, tp, fp), (ctx, P, None, T, None, n, L, 0, ALL, rp, tp, fp),
@@ -231,18 +224,11 @@ def test_host_forms(codec, pools):
 
 # ---- Python surface -------------------------------------------------------------------------------------------------------------
 
-def _teq(a, b):
-    import torch
-    if a.dtype == torch.float32:
-        a, b = a.view(torch.int32), b.view(torch.int32)
-    return a.shape == b.shape and a.dtype == b.dtype and bool((a == b).all())
+KEYS = ("rot", "trans", "frame_mask")
 
 
 def _np3(d):
-    return d["rot"].cpu().numpy(), d["trans"].cpu().numpy(), d["frame_mask"].cpu().numpy()
-
-
-KEYS = ("rot", "trans", "frame_mask")
+    return AN.to_numpy(d, KEYS)
 
 
 def test_rigid_frames_and_decode_tensors(codec, gold, records):
@@ -255,13 +241,13 @@ def test_rigid_frames_and_decode_tensors(codec, gold, records):
     assert t["rot"].shape == (56, L_GOLD, 8, 3, 3) and t["trans"].shape == (56, L_GOLD, 8, 3) and t["frame_mask"].shape == (56, L_GOLD, 8)
     F.same(_np3(t), gold["exp"]["atom37"], "decode_tensors all")
     r = foldcomp.rigid_frames(plain, groups="all", codec=codec)
-    assert all(_teq(r[k], t[k]) for k in KEYS)
+    assert all(AN.teq(r[k], t[k]) for k in KEYS)
     b = foldcomp.decode_tensors(records, codec=codec, frames="backbone", layout="backbone4")
     assert b["rot"].shape == (56, L_GOLD, 3, 3) and b["trans"].shape == (56, L_GOLD, 3) and b["frame_mask"].shape == (56, L_GOLD)
     e = _col0(gold["exp"]["atom37"])
     F.same(_np3(b), (e[0][..., 0, :, :], e[1][..., 0, :], e[2][..., 0]), "decode_tensors backbone")
     r = foldcomp.rigid_frames(pos=b["pos"], mask=b["mask"], length=b["length"], codec=codec)                 # keywords, no aatype
-    assert all(_teq(r[k], b[k]) for k in KEYS)
+    assert all(AN.teq(r[k], b[k]) for k in KEYS)
     # the alternative frames of the ambiguity table are one multiply away and exist only where the table says
     amb = torch.from_numpy(foldcomp.frame_ambiguous()).to(t["aatype"].device)[t["aatype"].long()]
     assert amb.shape == t["frame_mask"].shape and bool((amb & t["frame_mask"]).any()) and not bool(amb[..., :5].any())
@@ -270,20 +256,20 @@ def test_rigid_frames_and_decode_tensors(codec, gold, records):
     p = foldcomp.decode_tensors(records, codec=codec, packed=True, frames="all", layout="atom14")
     p37 = foldcomp.decode_tensors(records, codec=codec, packed=True, frames="all")
     assert set(p37) == set(pp) | set(KEYS) and p["rot"].shape == (p["pos"].shape[0], 8, 3, 3) and p["frame_mask"].shape == (p["pos"].shape[0], 8)
-    assert all(_teq(p[k], p37[k]) for k in KEYS)
+    assert all(AN.teq(p[k], p37[k]) for k in KEYS)
     lens = np.minimum(gold["host"]["atom37"]["length"].astype(np.int64), L_GOLD)
-    F.same(_np3(p37), tuple(np.concatenate([x[e, :m] for e, m in enumerate(lens)]) for x in gold["exp"]["atom37"]), "decode_tensors packed")
+    F.same(_np3(p37), AN.pack(gold["exp"]["atom37"], lens), "decode_tensors packed")
     r = foldcomp.rigid_frames(p37, groups="all", codec=codec)
-    assert all(_teq(r[k], p37[k]) for k in KEYS)
+    assert all(AN.teq(r[k], p37[k]) for k in KEYS)
     r = foldcomp.rigid_frames(p37, codec=codec)
-    assert r["rot"].shape == (p37["pos"].shape[0], 3, 3) and _teq(r["rot"], p37["rot"][:, 0].contiguous())
+    assert r["rot"].shape == (p37["pos"].shape[0], 3, 3) and AN.teq(r["rot"], p37["rot"][:, 0].contiguous())
     # a window: the restatement on the returned rows only (crop_start in the dict: length is not used)
     w = foldcomp.decode_tensors(records, codec=codec, max_len=64, crop="center", frames="all", layout="atom14")
     exp = F.frames(w["pos"].cpu().numpy(), w["mask"].cpu().numpy().view(np.uint8), w["aatype"].cpu().numpy(), None, 1, ALL)
     F.same(_np3(w), exp, "window")
     assert exp[2][gold["host"]["atom37"]["length"] > 64][:, :, 0].all()
     r = foldcomp.rigid_frames(w, groups="all", codec=codec)
-    assert all(_teq(r[k], w[k]) for k in KEYS)
+    assert all(AN.teq(r[k], w[k]) for k in KEYS)
     e = foldcomp.decode_tensors([], codec=codec, max_len=8, frames="all")
     assert e["rot"].shape == (0, 8, 8, 3, 3) and e["frame_mask"].shape == (0, 8, 8)
     assert foldcomp.decode_tensors([], codec=codec, packed=True, frames="backbone")["trans"].shape == (0, 3)
@@ -315,7 +301,7 @@ def test_tensor_batches_frames(codec, golden, tmp_path):
                 for b in db.tensor_batches(5, frames="backbone", **kw):
                     assert set(b) >= set(KEYS) and b["rot"].shape == b["pos"].shape[:-2] + (3, 3) and b["frame_mask"].shape == b["pos"].shape[:-2]
                     ref = foldcomp.rigid_frames(b)
-                    assert all(_teq(ref[k], b[k]) for k in KEYS)
+                    assert all(AN.teq(ref[k], b[k]) for k in KEYS)
                     seen += len(b["names"])
                 assert seen == 8
             assert set(next(iter(db.tensor_batches(5)))) == old and not set(KEYS) & old

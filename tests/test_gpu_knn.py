@@ -4,34 +4,29 @@ comparison is on bits; the device calls write into arrays pre-filled with 0xA5 w
 import numpy as np
 import pytest
 
+import _analysis as AN
 import _dense as D
 import _knn as K
-from _cases import compress_cases, db_cases
-from _devpath import HostGuarded, host_ptr, to_dev
-from _window import Decoded
+from _analysis import NAN_BITS
+from _cases import db_cases, golden_records_raw
+from _devpath import DevGuarded, HostGuarded, host_ptr, to_dev
 from foldcomp_amd import _lib
 
 pytestmark = pytest.mark.gpu
 
 L_GOLD = 1400
-NAN_BITS = np.uint32(0x7FC00123)
 
 
 @pytest.fixture(scope="module")
 def records(golden):
-    z, index = golden
-    names = compress_cases(index) + db_cases(index)
-    assert len(names) == 56
-    return [z[f"{n}/fcz"].tobytes() for n in names]
+    return golden_records_raw(golden)[1]
 
 
 @pytest.fixture(scope="module")
 def gold(codec, records):
     """the 56 golden records as atom37 / atom14 / backbone4 at L = 1400 (host and device), the restatement on CA at k = 64 and on
     CB at k = 48: computed once, never changed (a smaller k is the first k columns of the same order)"""
-    dec = Decoded(codec, records)
-    host = {lay: dec.dense(lay, L_GOLD, want=("pos", "mask", "length")) for lay in D.LAYOUTS}
-    dev = {lay: {k: to_dev(v) for k, v in host[lay].items()} for lay in D.LAYOUTS}
+    host, dev = AN.decoded_layouts(codec, records, L_GOLD, ("pos", "mask", "length"))
     a37 = host["atom37"]
     assert a37["length"].max() == L_GOLD
     return dict(host=host, dev=dev, n=len(records), ca=K.knn_padded(a37["pos"], a37["mask"], a37["length"], 1, 64),
@@ -65,13 +60,12 @@ def test_golden_padded_cb_and_the_other_layouts(codec, gold):
 def test_golden_packed(codec, gold):
     h = gold["host"]["atom37"]
     lens = np.minimum(h["length"].astype(np.int64), L_GOLD)
-    row_off = np.concatenate([[0], np.cumsum(lens)]).astype(np.uint32)
+    row_off = AN.row_off_of(lens)
     R = int(row_off[-1])
-    pos = np.concatenate([h["pos"][e, :n] for e, n in enumerate(lens)])
-    mask = np.concatenate([h["mask"][e, :n] for e, n in enumerate(lens)])
+    pos, mask = AN.pack((h["pos"], h["mask"]), lens)
     for slot, k, exp in ((1, 48, _first(gold["ca"], 48)), (3, 48, gold["cb"]), (1, 3, _first(gold["ca"], 3))):
         ei = np.concatenate([np.where(exp[0][e, :n] >= 0, exp[0][e, :n] + row_off[e], -1) for e, n in enumerate(lens)]).astype(np.int32)
-        ed = np.concatenate([exp[1][e, :n] for e, n in enumerate(lens)])
+        ed = AN.pack1(exp[1], lens)
         got = K.run_dev(codec, to_dev(pos), to_dev(mask), to_dev(row_off), gold["n"], R, 0, slot, k, True)
         K.same(got, (ei, ed), f"packed slot={slot} k={k}")
 
@@ -107,9 +101,8 @@ def synthetic():
     lens = [0, 1, 2, 3, 4, 63, 64, 65, 129] + ([2 * P + 3] if P else [])
     L = max(lens)
     pos, mask = _synthetic(lens, L, 4, 1, 11)
-    row_off = np.concatenate([[0], np.cumsum(lens)]).astype(np.uint32)
-    ppos = np.concatenate([pos[e, :m] for e, m in enumerate(lens)])
-    pmask = np.concatenate([mask[e, :m] for e, m in enumerate(lens)])
+    row_off = AN.row_off_of(lens)
+    ppos, pmask = AN.pack((pos, mask), lens)
     exp = K.knn_padded(pos, mask, np.asarray(lens), 1, 64)
     assert np.isinf(exp[1]).any() and (exp[1] == 0).sum() > 0 and (exp[0][-1, :, -1] >= 0).sum() > P
     return dict(lens=np.asarray(lens, np.uint32), L=L, pos=pos, mask=mask, row_off=row_off, ppos=ppos, pmask=pmask, exp=exp,
@@ -149,8 +142,7 @@ def test_hostile_row_off(codec):
     R, k = 700, 8
     pos, mask = _synthetic([R], R, 4, 1, 13)
     pos, mask = pos[0], mask[0]
-    # chain 0 runs backwards (empty), rows 0 .. 39 are left uncovered, chain 4 runs past R (clamped to the rows that exist)
-    row_off = np.asarray([300, 40, 120, 400, 401, 950], np.uint32)
+    row_off = AN.HOSTILE_ROW_OFF
     exp = K.knn_packed(pos, mask, row_off, 1, k)
     got = K.run_dev(codec, to_dev(pos), to_dev(mask), to_dev(row_off), 5, R, 2, 1, k, True)
     K.same(got, exp, "hostile row_off")
@@ -161,7 +153,7 @@ def test_hostile_row_off(codec):
     assert (none[0] == -1).all() and not K.bits(none[1]).any()
     # fcz_knn_packed on the same host arrays, its outputs between guard bytes: what the device form gave
     for n, dev_form in ((5, got), (0, none)):
-        h = HostGuarded(dict(index=(np.int32, (R, k)), dist=(np.float32, (R, k))))
+        h = HostGuarded(K.out_spec((R, k)))
         assert codec.lib.fcz_knn_packed(codec.ctx, host_ptr(pos), host_ptr(mask), host_ptr(row_off), n, R, 2, 1, k, *h.ptrs()) == 0
         K.same(h.all(), dev_form, f"fcz_knn_packed n={n}")
 
@@ -169,10 +161,8 @@ def test_hostile_row_off(codec):
 def test_refusals_leave_the_outputs_untouched(codec):
     import torch
     n, L, A, k = 2, 8, 37, 4
-    pos = torch.zeros((n, L, A, 3), dtype=torch.float32, device="cuda:0")
-    mask = torch.ones((n, L, A), dtype=torch.uint8, device="cuda:0")
-    off = to_dev(np.asarray([0, 8, 16], np.uint32))
-    g = K.Guarded(n * L * 8)
+    pos, mask, _, off = AN.refusal_inputs(n, L, A)
+    g = DevGuarded(K.out_spec((n * L * 8,)))
     ip, dp = g.ptrs()
     lib, ctx, P, M, O = codec.lib, codec.ctx, pos.data_ptr(), mask.data_ptr(), off.data_ptr()
     bad = [(None, P, M, None, n, L, 0, 1, k, ip, dp), (ctx, None, M, None, n, L, 0, 1, k, ip, dp), (ctx, P, None, None, n, L, 0, 1, k, ip, dp),
@@ -194,13 +184,6 @@ def test_refusals_leave_the_outputs_untouched(codec):
 
 # ---- Python surface -------------------------------------------------------------------------------------------------------------
 
-def _teq(a, b):
-    import torch
-    if a.dtype == torch.float32:
-        a, b = a.view(torch.int32), b.view(torch.int32)
-    return a.shape == b.shape and bool((a == b).all())
-
-
 def test_decode_tensors_neighbors(codec, gold, records):
     import torch
     import foldcomp_amd as foldcomp
@@ -210,7 +193,7 @@ def test_decode_tensors_neighbors(codec, gold, records):
     assert t["pos"].shape[1] == L_GOLD and t["nbr_index"].device.type == "cuda"
     K.same((t["nbr_index"].cpu().numpy(), t["nbr_dist"].cpu().numpy()), _first(gold["ca"], 48), "decode_tensors")
     again = foldcomp.decode_tensors(records, codec=codec, neighbors=48)
-    assert _teq(t["nbr_index"], again["nbr_index"]) and _teq(t["nbr_dist"], again["nbr_dist"])
+    assert AN.teq(t["nbr_index"], again["nbr_index"]) and AN.teq(t["nbr_dist"], again["nbr_dist"])
     # packed: the ABI call on the tensors it returns
     pp = foldcomp.decode_tensors(records, codec=codec, packed=True)
     p = foldcomp.decode_tensors(records, codec=codec, packed=True, neighbors=48, neighbor_atom="CB")
@@ -219,7 +202,7 @@ def test_decode_tensors_neighbors(codec, gold, records):
     abi = K.run_dev(codec, p["pos"], p["mask"].view(torch.uint8), p["cu_seqlens"], len(records), R, 0, 3, 48, True)
     K.same((p["nbr_index"].cpu().numpy(), p["nbr_dist"].cpu().numpy()), abi, "decode_tensors packed")
     g = foldcomp.neighbor_graph(p, k=48, atom="CB", codec=codec)
-    assert _teq(g["nbr_index"], p["nbr_index"]) and _teq(g["nbr_dist"], p["nbr_dist"])
+    assert AN.teq(g["nbr_index"], p["nbr_index"]) and AN.teq(g["nbr_dist"], p["nbr_dist"])
     # a window: the restatement on the returned rows only
     lens = gold["host"]["atom37"]["length"].astype(np.int64)
     starts = np.maximum(lens - 64, 0) // 2
@@ -228,7 +211,7 @@ def test_decode_tensors_neighbors(codec, gold, records):
     K.same((w["nbr_index"].cpu().numpy(), w["nbr_dist"].cpu().numpy()), exp, "window")
     assert (exp[0][lens > 64, :, -1] >= 0).all()
     g = foldcomp.neighbor_graph(w, k=30, codec=codec)                                      # crop_start in the dict: length is not used
-    assert _teq(g["nbr_index"], w["nbr_index"]) and _teq(g["nbr_dist"], w["nbr_dist"])
+    assert AN.teq(g["nbr_index"], w["nbr_index"]) and AN.teq(g["nbr_dist"], w["nbr_dist"])
     e = foldcomp.decode_tensors([], codec=codec, max_len=8, neighbors=5)
     assert e["nbr_index"].shape == (0, 8, 5) and foldcomp.decode_tensors([], codec=codec, packed=True, neighbors=5)["nbr_dist"].shape == (0, 5)
 
@@ -240,7 +223,7 @@ def test_neighbor_graph_model_style_call(codec, gold):
     pos, mask = d["pos"][:6, :200].contiguous(), d["mask"][:6, :200].contiguous().view(torch.bool)
     a = foldcomp.neighbor_graph(pos=pos, mask=mask, k=30, codec=codec)
     b = foldcomp.neighbor_graph(pos=pos, mask=mask, k=30, codec=codec)
-    assert _teq(a["nbr_index"], b["nbr_index"]) and _teq(a["nbr_dist"], b["nbr_dist"])
+    assert AN.teq(a["nbr_index"], b["nbr_index"]) and AN.teq(a["nbr_dist"], b["nbr_dist"])
     exp = K.knn_padded(pos.cpu().numpy(), mask.cpu().numpy().view(np.uint8), None, 1, 30)
     K.same((a["nbr_index"].cpu().numpy(), a["nbr_dist"].cpu().numpy()), exp, "keywords")
     c = foldcomp.neighbor_graph(pos=pos, mask=mask, length=torch.tensor([200, 5, 0, 1, 300, 64], device="cuda:0"), k=4, atom=0, codec=codec)
@@ -274,7 +257,7 @@ def test_tensor_batches_neighbors(codec, golden, tmp_path):
                 for b in db.tensor_batches(5, neighbors=30, **kw):
                     assert set(b) >= {"nbr_index", "nbr_dist"} and b["nbr_index"].shape == b["pos"].shape[:-2] + (30,)
                     ref = foldcomp.neighbor_graph(b, k=30)
-                    assert _teq(ref["nbr_index"], b["nbr_index"]) and _teq(ref["nbr_dist"], b["nbr_dist"])
+                    assert AN.teq(ref["nbr_index"], b["nbr_index"]) and AN.teq(ref["nbr_dist"], b["nbr_dist"])
                     seen += len(b["names"])
                 assert seen == 8
             assert set(next(iter(db.tensor_batches(5)))) == old and "nbr_index" not in old

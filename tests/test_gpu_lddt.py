@@ -6,18 +6,18 @@ import math
 import numpy as np
 import pytest
 
+import _analysis as AN
 import _dense as D
 import _knn as K
 import _lddt as Q
-from _cases import compress_cases, db_cases
-from _devpath import HostGuarded, host_ptr, to_dev
-from _window import Decoded
+from _analysis import NAN_BITS
+from _cases import golden_records_raw
+from _devpath import DevGuarded, HostGuarded, host_ptr, to_dev
 from foldcomp_amd import _lib
 
 pytestmark = pytest.mark.gpu
 
 L_GOLD = 1400
-NAN_BITS = np.uint32(0x7FC00123)
 F = np.float32
 CA = dict(atom37=1, atom14=1, backbone4=1)
 CB = dict(atom37=3, atom14=4)
@@ -25,10 +25,7 @@ CB = dict(atom37=3, atom14=4)
 
 @pytest.fixture(scope="module")
 def records(golden):
-    z, index = golden
-    names = compress_cases(index) + db_cases(index)
-    assert len(names) == 56
-    return [z[f"{n}/fcz"].tobytes() for n in names]
+    return golden_records_raw(golden)[1]
 
 
 @pytest.fixture(scope="module")
@@ -36,8 +33,7 @@ def gold(codec, records):
     """the 56 golden records as atom37 / atom14 / backbone4 at L = 1400: `true` is the decode, `pred` is true plus float32 noise of
     sigma 0.5 A made on the host (the same noise on CA and on CB in every layout; every seventh chain is `true` itself), both on the
     host and the device, and the restatement on CA and on CB: computed once, never changed"""
-    dec = Decoded(codec, records)
-    host = {lay: dec.dense(lay, L_GOLD, want=("pos", "mask", "length")) for lay in D.LAYOUTS}
+    host, dev = AN.decoded_layouts(codec, records, L_GOLD, ("pos", "mask", "length"))
     n = len(records)
     rng = np.random.default_rng(17)
     noise = {"CA": (rng.standard_normal((n, L_GOLD, 3)) * 0.5).astype(F), "CB": (rng.standard_normal((n, L_GOLD, 3)) * 0.5).astype(F)}
@@ -50,7 +46,8 @@ def gold(codec, records):
         if lay in CB:
             p[:, :, CB[lay]] += noise["CB"]
         pred[lay] = p
-    dev = {lay: dict({k: to_dev(v) for k, v in host[lay].items()}, pred=to_dev(pred[lay])) for lay in D.LAYOUTS}
+    for lay in D.LAYOUTS:
+        dev[lay]["pred"] = to_dev(pred[lay])
     a37 = host["atom37"]
     assert a37["length"].max() == L_GOLD
     ca = Q.lddt_padded(a37["pos"], a37["mask"], pred["atom37"], a37["mask"], a37["length"], 1)
@@ -88,9 +85,9 @@ def test_golden_padded(codec, gold):
 def test_golden_packed(codec, gold):
     h = gold["host"]["atom37"]
     lens = np.minimum(h["length"].astype(np.int64), L_GOLD)
-    row_off = np.concatenate([[0], np.cumsum(lens)]).astype(np.uint32)
+    row_off = AN.row_off_of(lens)
     R = int(row_off[-1])
-    cat = lambda a: np.concatenate([a[e, :n] for e, n in enumerate(lens)])
+    cat = lambda a: AN.pack1(a, lens)
     pos, mask, pred = to_dev(cat(h["pos"])), to_dev(cat(h["mask"])), to_dev(cat(gold["pred"]["atom37"]))
     for slot, exp in ((1, gold["ca"]), (3, gold["cb"])):
         got = Q.run_dev(codec, pos, mask, pred, mask, to_dev(row_off), gold["n"], R, 0, slot, True)
@@ -126,10 +123,6 @@ def _synthetic(lens, L, A, slot, seed, behind="nan"):
     return true, mt, pred, mp
 
 
-def _pack(arrays, lens):
-    return [np.concatenate([a[e, :m] for e, m in enumerate(lens)]) for a in arrays]
-
-
 @pytest.fixture(scope="module")
 def synthetic():
     """lengths 0, 1, 2, 63, 64, 65, 129, 255, 256, 257 and 2 * fcz_lddt_pass() + 3, as one padded and one packed batch on
@@ -139,13 +132,13 @@ def synthetic():
     lens = [0, 1, 2, 63, 64, 65, 129, 255, 256, 257, 2 * P + 3]
     L = max(lens)
     t, mt, p, mp = _synthetic(lens, L, 4, 1, 11)
-    row_off = np.concatenate([[0], np.cumsum(lens)]).astype(np.uint32)
+    row_off = AN.row_off_of(lens)
     exp = Q.lddt_padded(t, mt, p, mp, np.asarray(lens), 1)
     score, pairs, hits = exp
     assert ((pairs > 0) & (hits == 0)).any() and (pairs[-1] > P).any() and (hits < 4 * pairs).any() and (hits > 0).any()
     filled = p.copy()
     filled[mp == 0] = 2.0
-    return dict(lens=np.asarray(lens, np.uint32), L=L, arrays=(t, mt, p, mp), row_off=row_off, packed=_pack((t, mt, p, mp), lens), exp=exp,
+    return dict(lens=np.asarray(lens, np.uint32), L=L, arrays=(t, mt, p, mp), row_off=row_off, packed=AN.pack((t, mt, p, mp), lens), exp=exp,
                 filled=filled, exp_nomask=Q.lddt_padded(t, mt, filled, None, np.asarray(lens), 1))
 
 
@@ -159,7 +152,7 @@ def test_synthetic_padded_and_packed(codec, synthetic):
         assert not got[1][e, m:].any() and not got[2][e, m:].any() and not K.bits(got[0][e, m:]).any()
     pt, pmt, pp, pmp = (to_dev(a) for a in s["packed"])
     R = int(s["row_off"][-1])
-    exp_packed = _pack(s["exp"], s["lens"])
+    exp_packed = AN.pack(s["exp"], s["lens"])
     Q.same(Q.run_dev(codec, pt, pmt, pp, pmp, to_dev(s["row_off"]), n, R, 2, 1, True), exp_packed, "packed")
     Q.same(Q.lddt_packed(*s["packed"], s["row_off"], 1), exp_packed, "restatement, packed")
     # the host-pointer forms give the same arrays
@@ -177,9 +170,9 @@ def test_mask_pred_null(codec, synthetic):
     Q.same(Q.run_dev(codec, t, mt, p, None, to_dev(s["lens"]), n, s["L"], 2, 1, False), s["exp_nomask"], "padded")
     # with the mask the filled values are not read as data
     Q.same(Q.run_dev(codec, t, mt, p, to_dev(s["arrays"][3]), to_dev(s["lens"]), n, s["L"], 2, 1, False), s["exp"], "padded, masked")
-    pt, pmt, pp = (to_dev(a) for a in _pack((s["arrays"][0], s["arrays"][1], s["filled"]), s["lens"]))
+    pt, pmt, pp = (to_dev(a) for a in AN.pack((s["arrays"][0], s["arrays"][1], s["filled"]), s["lens"]))
     got = Q.run_dev(codec, pt, pmt, pp, None, to_dev(s["row_off"]), n, int(s["row_off"][-1]), 2, 1, True)
-    Q.same(got, _pack(s["exp_nomask"], s["lens"]), "packed")
+    Q.same(got, AN.pack(s["exp_nomask"], s["lens"]), "packed")
     h = codec.lddt(s["arrays"][0], s["arrays"][1], s["filled"], None, 1, length=s["lens"])
     Q.same((h["score"], h["pairs"], h["hits"]), s["exp_nomask"], "fcz_lddt")
 
@@ -228,8 +221,7 @@ def test_hostile_row_off(codec):
     R = 700
     arrays = [a[0] for a in _synthetic([R], R, 4, 1, 13)]
     dev = [to_dev(a) for a in arrays]
-    # chain 0 runs backwards (empty), rows 0 .. 39 are left uncovered, chain 4 runs past R (clamped to the rows that exist)
-    row_off = np.asarray([300, 40, 120, 400, 401, 950], np.uint32)
+    row_off = AN.HOSTILE_ROW_OFF
     exp = Q.lddt_packed(*arrays, row_off, 1)
     got = Q.run_dev(codec, *dev, to_dev(row_off), 5, R, 2, 1, True)
     Q.same(got, exp, "hostile row_off")
@@ -240,7 +232,7 @@ def test_hostile_row_off(codec):
     assert not none[1].any() and not none[2].any() and not K.bits(none[0]).any()
     # fcz_lddt_packed on the same host arrays, its outputs between guard bytes: what the device form gave
     for n, dev_form in ((5, got), (0, none)):
-        h = HostGuarded(dict(score=(F, (R,)), pairs=(np.int32, (R,)), hits=(np.int32, (R,))))
+        h = HostGuarded(Q.out_spec((R,)))
         assert codec.lib.fcz_lddt_packed(codec.ctx, *(host_ptr(a) for a in arrays), host_ptr(row_off), n, R, 2, 1, 15.0, None, *h.ptrs()) == 0
         Q.same(h.all(), dev_form, f"fcz_lddt_packed n={n}")
 
@@ -248,10 +240,8 @@ def test_hostile_row_off(codec):
 def test_refusals_leave_the_outputs_untouched(codec):
     import torch
     n, L, A = 2, 8, 37
-    pos = torch.zeros((n, L, A, 3), dtype=torch.float32, device="cuda:0")
-    mask = torch.ones((n, L, A), dtype=torch.uint8, device="cuda:0")
-    off = to_dev(np.asarray([0, 8, 16], np.uint32))
-    g = Q.Guarded(n * L)
+    pos, mask, _, off = AN.refusal_inputs(n, L, A)
+    g = DevGuarded(Q.out_spec((n * L,)))
     sp, pp, hp = g.ptrs()
     lib, ctx, P, M, O = codec.lib, codec.ctx, pos.data_ptr(), mask.data_ptr(), off.data_ptr()
     nan_th = np.asarray([0.5, 1, np.nan, 4], F)
@@ -275,7 +265,7 @@ def test_refusals_leave_the_outputs_untouched(codec):
 # ---- Python surface -------------------------------------------------------------------------------------------------------------
 
 def _np(d):
-    return d["lddt"].cpu().numpy(), d["lddt_pairs"].cpu().numpy(), d["lddt_hits"].cpu().numpy()
+    return AN.to_numpy(d, ("lddt", "lddt_pairs", "lddt_hits"))
 
 
 def _noisy(t, seed):

@@ -6,17 +6,17 @@ import ctypes
 import numpy as np
 import pytest
 
+import _analysis as AN
 import _dense as DN
 import _lddt_atoms as LA
-from _cases import compress_cases, db_cases
+from _analysis import NAN_BITS
+from _cases import golden_records_raw
 from _devpath import HostGuarded, host_ptr, to_dev
-from _window import Decoded
 from foldcomp_amd import _lib
 
 pytestmark = pytest.mark.gpu
 
 L_GOLD = 256
-NAN_BITS = np.uint32(0x7FC00123)
 F = np.float32
 TABLE = {A: LA.default_table(A) for A in (37, 14, 4)}
 TILE = {37: 20, 14: 18, 4: 64}                                               # rows per query tile of the score sweep (fcz_lddt_atoms.h)
@@ -26,10 +26,7 @@ BB37 = [0, 1, 2, 4]                                                          # N
 
 @pytest.fixture(scope="module")
 def records(golden):
-    z, index = golden
-    names = compress_cases(index) + db_cases(index)
-    assert len(names) == 56
-    return [z[f"{n}/fcz"].tobytes() for n in names]
+    return golden_records_raw(golden)[1]
 
 
 def _capable(aatype, A):
@@ -50,8 +47,7 @@ def gold(codec, records):
     noise of 0.5 with the symmetric atoms of every second swap-capable row exchanged, drawn once in atom37 and carried to the other
     layouts atom by atom, and the restatement on atom37 and backbone4: computed once, never changed. The prediction's mask is the
     truth's without the chain's OXT (atom37 slot 36), which atom14 has no slot for, so that the layouts hold the same atoms."""
-    dec = Decoded(codec, records)
-    host = {lay: dec.dense(lay, L_GOLD, want=("pos", "mask", "aatype", "length")) for lay in DN.LAYOUTS}
+    host, _ = AN.decoded_layouts(codec, records, L_GOLD, ("pos", "mask", "aatype", "length"))
     a = host["atom37"]
     aa = a["aatype"]
     assert a["length"].max() >= L_GOLD and a["mask"][..., 36].sum() > 0
@@ -98,9 +94,9 @@ def test_golden_padded(codec, gold):
 
 def test_golden_packed(codec, gold):
     lens = np.minimum(gold["host"]["atom37"]["length"].astype(np.int64), L_GOLD)
-    row_off = np.concatenate([[0], np.cumsum(lens)]).astype(np.uint32)
+    row_off = AN.row_off_of(lens)
     R = int(row_off[-1])
-    cat = lambda a: np.concatenate([a[e, :m] for e, m in enumerate(lens)])
+    cat = lambda a: AN.pack1(a, lens)
     for lay in DN.LAYOUTS:
         h = gold["host"][lay]
         arrays = [to_dev(cat(x)) for x in (h["pos"], h["mask"], *gold["pred"][lay], h["aatype"])]
@@ -153,16 +149,12 @@ def _synthetic(lens, A, seed, hostile=True):
     return dict(pt=pt, mt=mt, pp=pp, mp=mp, aa=aa, lens=np.asarray(lens, np.uint32), L=L, n=n, A=A, layout=LA.LAYOUT[A])
 
 
-def _pack(a, lens):
-    return np.concatenate([a[e, :m] for e, m in enumerate(lens)])
-
-
 def _run(codec, s, packed=False, bound="lens", **kw):
     """the device form on the synthetic set `s`; replacements of its arrays and run_dev's arguments as keywords"""
     arr = {k: kw.pop(k, s[k]) for k in ("pt", "mt", "pp", "mp", "aa")}
     if packed:
-        arr = {k: None if v is None else _pack(v, s["lens"]) for k, v in arr.items()}
-        off = np.concatenate([[0], np.cumsum(s["lens"])]).astype(np.uint32)
+        arr = {k: None if v is None else AN.pack1(v, s["lens"]) for k, v in arr.items()}
+        off = AN.row_off_of(s["lens"])
         return LA.run_dev(codec, *(None if arr[k] is None else to_dev(arr[k]) for k in ("pt", "mt", "pp", "mp", "aa")), to_dev(off), s["n"], int(off[-1]),
                           s["layout"], True, **kw)
     b = s["lens"] if isinstance(bound, str) else bound
@@ -215,15 +207,15 @@ def test_synthetic_padded_and_packed(codec, synthetic):
     LA.same(got, exp, "padded")
     LA.same(_run(codec, s), got, "again")                                     # two calls give the same bytes
     gp = _run(codec, s, packed=True, guard=8)
-    LA.same(gp, {k: _pack(v, s["lens"]) for k, v in exp.items()}, "packed")    # padded and packed give the same values
+    LA.same(gp, {k: AN.pack1(v, s["lens"]) for k, v in exp.items()}, "packed")    # padded and packed give the same values
     # the optional outputs NULL: the others are what they were, the two arrays untouched
     LA.same(_run(codec, s, per_atom=False), exp, "per_atom NULL", LA.ROW_KEYS)
     LA.same(_run(codec, s, packed=True, per_atom=False), gp, "packed, per_atom NULL", LA.ROW_KEYS)
     # the host-pointer forms against the device forms
     h = codec.lddt_atoms(s["pt"], s["mt"], s["pp"], s["mp"], s["aa"], length=s["lens"], per_atom=True)
     LA.same(h, got, "fcz_lddt_atoms")
-    off = np.concatenate([[0], np.cumsum(s["lens"])]).astype(np.uint32)
-    h = codec.lddt_atoms(*(_pack(s[k], s["lens"]) for k in ("pt", "mt", "pp", "mp", "aa")), row_off=off)
+    off = AN.row_off_of(s["lens"])
+    h = codec.lddt_atoms(*(AN.pack1(s[k], s["lens"]) for k in ("pt", "mt", "pp", "mp", "aa")), row_off=off)
     LA.same(h, gp, "fcz_lddt_atoms_packed", LA.ROW_KEYS)
     assert "atom_pairs" not in h and h["swapped"].dtype == np.bool_
 
@@ -237,7 +229,7 @@ def test_masks_types_tables_and_thresholds(codec, synthetic):
     none = _restate(s, aa=None)
     assert not none["swapped"].any()
     LA.same(_run(codec, s, aa=None), none, "aatype NULL")
-    LA.same(_run(codec, s, aa=None, packed=True), {k: _pack(v, s["lens"]) for k, v in none.items()}, "aatype NULL, packed")
+    LA.same(_run(codec, s, aa=None, packed=True), {k: AN.pack1(v, s["lens"]) for k, v in none.items()}, "aatype NULL, packed")
     if A != 4:
         assert (none["hits"] < s["exp"]["hits"]).sum() > 10                   # the exchanged rings are punished without the renaming
         # a custom table: VAL CG1 / CG2 beside ASP; the other types have no partner any more
@@ -293,7 +285,7 @@ def test_hostile_row_off(codec):
     def host_form(n, rows):
         """fcz_lddt_atoms_packed on the host arrays, its outputs between guard bytes"""
         from foldcomp_amd.structure import CLddtAtomsOut
-        h = HostGuarded({k: (LA.DTYPES[k], (rows, 37) if k.startswith("atom_") else (rows,)) for k in LA.KEYS})
+        h = HostGuarded(LA.out_spec((rows,), 37))
         out = CLddtAtomsOut(*h.ptrs())
         assert codec.lib.fcz_lddt_atoms_packed(codec.ctx, *(host_ptr(a[:max(rows, 1)]) for a in arrays), host_ptr(row_off), n, rows, 0, 15.0, None, None,
                                                ctypes.byref(out)) == 0
@@ -307,11 +299,8 @@ def test_hostile_row_off(codec):
 def test_refusals_leave_the_outputs_untouched(codec):
     import torch
     n, L, A = 2, 8, 37
-    pos = torch.zeros((n, L, A, 3), dtype=torch.float32, device="cuda:0")
-    mask = torch.ones((n, L, A), dtype=torch.uint8, device="cuda:0")
-    aa = torch.zeros((n, L), dtype=torch.uint8, device="cuda:0")
-    off = to_dev(np.asarray([0, 8, 16], np.uint32))
-    o = LA.Outputs(n * L, A)
+    pos, mask, aa, off = AN.refusal_inputs(n, L, A)
+    o = LA.Outputs((n * L,), A)
     chain, outside, nan_th = TABLE[37].copy(), TABLE[37].copy(), np.asarray([0.5, np.nan, 2, 4], F)
     chain[5, 1], chain[5, 2], chain[5, 3] = 2, 3, 1
     outside[20, 0] = 37
@@ -399,8 +388,8 @@ def test_foldcomp_lddt_atoms(codec, records):
     full = foldcomp.decode_tensors(sub, codec=codec)
     fl = np.ascontiguousarray(LA.exchange(full["pos"].cpu().numpy(), full["aatype"].cpu().numpy(), _capable(full["aatype"].cpu().numpy(), 37), TABLE[37]))
     fo = foldcomp.lddt_atoms(torch.from_numpy(fl).to(full["pos"].device), full, per_atom=True, codec=codec)
-    po = foldcomp.lddt_atoms(torch.from_numpy(_pack(fl, lens)).to(p["pos"].device), p, per_atom=True, codec=codec)
-    LA.same(_np(po, LA.KEYS), {k: _pack(v, lens) for k, v in _np(fo, LA.KEYS).items()}, "packed against padded")
+    po = foldcomp.lddt_atoms(torch.from_numpy(AN.pack1(fl, lens)).to(p["pos"].device), p, per_atom=True, codec=codec)
+    LA.same(_np(po, LA.KEYS), {k: AN.pack1(v, lens) for k, v in _np(fo, LA.KEYS).items()}, "packed against padded")
     assert np.array_equal(po["lddt_chain"].cpu().numpy(), fo["lddt_chain"].cpu().numpy()) and po["swapped"].sum() > 100
     # nothing to compute, and what is refused
     e = foldcomp.decode_tensors([], codec=codec, max_len=8)

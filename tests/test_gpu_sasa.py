@@ -5,19 +5,18 @@ bytes on both sides."""
 import numpy as np
 import pytest
 
+import _analysis as AN
 import _dense as DN
-import _dssp as D
 import _knn as K
 import _sasa as S
-from _cases import compress_cases, db_cases
-from _devpath import HostGuarded, host_ptr, to_dev
-from _window import Decoded
+from _analysis import NAN_BITS
+from _cases import golden_records_raw
+from _devpath import DevGuarded, HostGuarded, host_ptr, to_dev
 from foldcomp_amd import _lib, api
 
 pytestmark = pytest.mark.gpu
 
 L_GOLD = 1400
-NAN_BITS = np.uint32(0x7FC00123)
 F = np.float32
 TABLE = {A: S.default_table(A) for A in (37, 14, 4)}
 PTS = api.sphere_points(128)
@@ -25,34 +24,19 @@ PTS = api.sphere_points(128)
 
 @pytest.fixture(scope="module")
 def records(golden):
-    z, index = golden
-    names = compress_cases(index) + db_cases(index)
-    assert len(names) == 56
-    return [z[f"{n}/fcz"].tobytes() for n in names]
-
-
-def _to14(c37, aatype):
-    """per-slot values of atom37 [.., 37] -> atom14 [.., 14] through the slot map of every row's type"""
-    slot = np.full((21, 14), -1, np.int64)
-    for ty in range(21):
-        for j, code in enumerate(DN.RES_ATOMS[ty]):
-            slot[ty, j] = DN.expected_slot("atom37", ty, code)
-    s = slot[np.minimum(aatype, 20)]
-    return np.where(s >= 0, np.take_along_axis(c37, np.maximum(s, 0), axis=-1), 0).astype(c37.dtype)
+    return golden_records_raw(golden)[1]
 
 
 @pytest.fixture(scope="module")
 def gold(codec, records):
     """the 56 golden records as atom37 / atom14 / backbone4 at L = 1400 on the host and the device, and the restatement on atom37 and
     on backbone4: computed once, never changed"""
-    dec = Decoded(codec, records)
-    host = {lay: dec.dense(lay, L_GOLD, want=("pos", "mask", "aatype", "length")) for lay in DN.LAYOUTS}
-    dev = {lay: {k: to_dev(v) for k, v in host[lay].items()} for lay in DN.LAYOUTS}
+    host, dev = AN.decoded_layouts(codec, records, L_GOLD, ("pos", "mask", "aatype", "length"))
     a, b = host["atom37"], host["backbone4"]
     assert a["length"].max() == L_GOLD
     exp37 = S.sasa(a["pos"], a["mask"], a["aatype"], a["length"], TABLE[37], S.PROBE, PTS)
     exp4 = S.sasa(b["pos"], b["mask"], b["aatype"], b["length"], TABLE[4], S.PROBE, PTS)
-    exp = dict(atom37=exp37, atom14=[_to14(exp37[0], a["aatype"]), exp37[1], exp37[2]], backbone4=exp4)
+    exp = dict(atom37=exp37, atom14=[AN.to14(exp37[0], a["aatype"]), exp37[1], exp37[2]], backbone4=exp4)
     return dict(host=host, dev=dev, n=len(records), exp=exp, pts=to_dev(PTS))
 
 
@@ -88,9 +72,9 @@ def test_golden_padded(codec, gold):
 
 def test_golden_packed(codec, gold):
     lens = np.minimum(gold["host"]["atom37"]["length"].astype(np.int64), L_GOLD)
-    row_off = np.concatenate([[0], np.cumsum(lens)]).astype(np.uint32)
+    row_off = AN.row_off_of(lens)
     R = int(row_off[-1])
-    cat = lambda a: np.concatenate([a[e, :m] for e, m in enumerate(lens)])
+    cat = lambda a: AN.pack1(a, lens)
     for lay in DN.LAYOUTS:
         hh = gold["host"][lay]
         got = S.run_sasa(codec, to_dev(cat(hh["pos"])), to_dev(cat(hh["mask"])), to_dev(cat(hh["aatype"])), to_dev(row_off), gold["n"], R, DN.LAYOUTS[lay], True,
@@ -99,17 +83,6 @@ def test_golden_packed(codec, gold):
 
 
 # ---- synthetic tensors ----------------------------------------------------------------------------------------------------------
-
-def _helix(rng, m, A):
-    """m rows of A atoms: an ideal alpha helix (backbone4) with a jitter of 0.05, for A = 14 ten more atoms scattered about every CA"""
-    if m == 0:
-        return np.zeros((0, A, 3), F)
-    bb = D.ideal_backbone(-57, -47, m)[0] + (rng.standard_normal((m, 4, 3)) * 0.05).astype(F)
-    if A == 4:
-        return bb
-    side = bb[:, 1:2] + (rng.standard_normal((m, A - 4, 3)) * 2.0).astype(F)
-    return np.concatenate([bb, side], axis=1)
-
 
 def _synthetic(lens, clear, A, seed, hostile=True):
     """chains [n, L, A, 3] of jittered helices with every mask set but `clear[e]` slots of chain e (NaN patterns under the cleared
@@ -120,7 +93,7 @@ def _synthetic(lens, clear, A, seed, hostile=True):
     n, L = len(lens), max(max(lens), 1)
     pos, mask = np.zeros((n, L, A, 3), F), np.ones((n, L, A), np.uint8)
     for e, m in enumerate(lens):
-        pos[e, :m] = _helix(rng, m, A)
+        pos[e, :m] = AN.helix(rng, m, A)
         if e in clear:
             flat = rng.choice(m * A, size=clear[e], replace=False)
             mask[e].reshape(-1)[flat] = 0
@@ -138,10 +111,6 @@ def _synthetic(lens, clear, A, seed, hostile=True):
     return pos, mask, aatype
 
 
-def _pack(arrays, lens):
-    return [np.concatenate([a[e, :m] for e, m in enumerate(lens)]) for a in arrays]
-
-
 @pytest.fixture(scope="module")
 def synthetic():
     """backbone4 chains of 0 .. 7 rows (the row tile is 3) and of Q - 1, Q, Q + 1 and 2 Q + 3 ATOMS for the pass size Q, each with
@@ -155,7 +124,7 @@ def synthetic():
     atoms = [int(S.atoms_of(pos[e, :m], mask[e, :m], aa[e, :m], TABLE[4])[0].sum()) for e, m in enumerate(lens)]
     assert atoms[8:12] == [Q - 1, Q, Q + 1, 2 * Q + 3], atoms
     ln = np.asarray(lens, np.uint32)
-    return dict(lens=ln, L=max(lens), arrays=(pos, mask, aa), row_off=np.concatenate([[0], np.cumsum(lens)]).astype(np.uint32), exp={})
+    return dict(lens=ln, L=max(lens), arrays=(pos, mask, aa), row_off=AN.row_off_of(lens), exp={})
 
 
 def _expect(s, P, table=None, probe=S.PROBE):
@@ -178,9 +147,9 @@ def test_synthetic_padded_and_packed(codec, synthetic, P):
     for e, m in enumerate(s["lens"]):
         assert not got[0][e, m:].any() and not K.bits(got[1][e, m:]).any() and not got[2][e, m:].any()
     S.same_sasa(S.run_sasa(codec, pos, mask, aa, to_dev(s["lens"]), n, s["L"], 2, False, pts), got, "again")   # two calls give the same bits
-    packed = _pack(s["arrays"], s["lens"])
+    packed = AN.pack(s["arrays"], s["lens"])
     R = int(s["row_off"][-1])
-    exp_packed = _pack(exp, s["lens"])
+    exp_packed = AN.pack(exp, s["lens"])
     gp = S.run_sasa(codec, *(to_dev(a) for a in packed), to_dev(s["row_off"]), n, R, 2, True, pts)
     S.same_sasa(gp, exp_packed, "packed")
     if P in (65, 1024):                                                       # the host-pointer forms against the device forms
@@ -211,10 +180,10 @@ def test_atom14_types_custom_radii_and_probe(codec):
     got = S.run_sasa(codec, *dev, to_dev(ln), n, L, 1, False, to_dev(pts), table=table, probe=0.75)
     S.same_sasa(got, exp, "custom table, probe and points")
     assert not got[0][..., :][np.broadcast_to((table[np.minimum(aa, 20)] == 0), got[0].shape)].any() and (got[0] > 0).sum() > 1000
-    packed = _pack((pos, mask, aa), lens)
-    row_off = np.concatenate([[0], np.cumsum(lens)]).astype(np.uint32)
+    packed = AN.pack((pos, mask, aa), lens)
+    row_off = AN.row_off_of(lens)
     S.same_sasa(S.run_sasa(codec, *(to_dev(a) for a in packed), to_dev(row_off), n, int(row_off[-1]), 1, True, to_dev(pts), table=table, probe=0.75),
-                _pack(exp, lens), "custom, packed")
+                AN.pack(exp, lens), "custom, packed")
 
 
 def test_lattice_ties(codec):
@@ -260,8 +229,7 @@ def test_hostile_row_off(codec):
     pos, mask, aa = (a[0] for a in _synthetic([R], {}, 4, 24))
     dev = [to_dev(a) for a in (pos, mask, aa)]
     pts = to_dev(PTS)
-    # chain 0 runs backwards (empty), rows 0 .. 39 are left uncovered, chain 4 runs past R (clamped to the rows that exist)
-    row_off = np.asarray([300, 40, 120, 400, 401, 950], np.uint32)
+    row_off = AN.HOSTILE_ROW_OFF
     exp = S.sasa(pos, mask, aa, row_off, TABLE[4], S.PROBE, PTS, packed=True)
     got = S.run_sasa(codec, *dev, to_dev(row_off), 5, R, 2, True, pts)
     S.same_sasa(got, exp, "hostile row_off")
@@ -271,7 +239,7 @@ def test_hostile_row_off(codec):
     assert not none[0].any() and not K.bits(none[1]).any() and not none[2].any()
     # fcz_sasa_packed on the same host arrays, its outputs between guard bytes: what the device form gave
     for n, dev_form in ((5, got), (0, none)):
-        h = HostGuarded(dict(sasa_points=(np.int16, (R, 4)), sasa=(F, (R,)), sasa_mask=(np.uint8, (R,))))
+        h = HostGuarded(S.out_spec((R,), 4))
         assert codec.lib.fcz_sasa_packed(codec.ctx, host_ptr(pos), host_ptr(mask), host_ptr(aa), host_ptr(row_off), n, R, 2, None, float(S.PROBE),
                                          host_ptr(PTS), len(PTS), *h.ptrs()) == 0
         S.same_sasa(h.all(), dev_form, f"fcz_sasa_packed n={n}")
@@ -280,13 +248,10 @@ def test_hostile_row_off(codec):
 def test_refusals_leave_the_outputs_untouched(codec):
     import torch
     n, L, A = 2, 8, 37
-    pos = torch.zeros((n, L, A, 3), dtype=torch.float32, device="cuda:0")
-    mask = torch.ones((n, L, A), dtype=torch.uint8, device="cuda:0")
-    aa = torch.zeros((n, L), dtype=torch.uint8, device="cuda:0")
-    off = to_dev(np.asarray([0, 8, 16], np.uint32))
+    pos, mask, aa, off = AN.refusal_inputs(n, L, A)
     pts = to_dev(PTS)
-    g = [D.Guarded(n * L * A, (np.int16,)), D.Guarded(n * L, (np.float32, np.uint8))]
-    o = g[0].ptrs() + g[1].ptrs()
+    g = DevGuarded(S.out_spec((n * L,), A))
+    o = g.ptrs()
     big, nan_tab = TABLE[37].copy(), TABLE[37].copy()
     big[3, 5], nan_tab[20, 0] = 6.7, np.nan
     lib, ctx = codec.lib, codec.ctx
@@ -305,13 +270,13 @@ def test_refusals_leave_the_outputs_untouched(codec):
     assert lib.fcz_sasa_packed_dev(*dict(ok, L=n * L).values()) == -1          # chains without a row_off
     assert lib.fcz_sasa_dev(*dict(ok, n=0).values()) == 0 and lib.fcz_sasa_packed_dev(*dict(ok, bound=off.data_ptr(), L=0).values()) == 0
     codec.synchronize()
-    assert all(x.untouched() for x in g)
+    assert g.untouched()
 
 
 # ---- Python surface -------------------------------------------------------------------------------------------------------------
 
 def _triple(d):
-    return d["sasa_points"].cpu().numpy(), d["sasa"].cpu().numpy(), d["sasa_mask"].cpu().numpy()
+    return AN.to_numpy(d, ("sasa_points", "sasa", "sasa_mask"))
 
 
 def _pair(d, exp, what):
@@ -354,10 +319,9 @@ def test_foldcomp_solvent_accessibility(codec, gold, records):
     p = foldcomp.decode_tensors(records, codec=codec, packed=True, sasa=True)
     cu = p["cu_seqlens"].cpu().numpy()
     lens = np.diff(cu)
-    cat = lambda a: np.concatenate([a[e, :m] for e, m in enumerate(lens)])
-    _pair(p, [cat(a) for a in exp], "packed decode_tensors")
+    _pair(p, AN.pack(exp, lens), "packed decode_tensors")
     po = foldcomp.solvent_accessibility(p, codec=codec)
-    S.same_sasa(_triple(po), [cat(a) for a in exp], "packed solvent_accessibility")
+    S.same_sasa(_triple(po), AN.pack(exp, lens), "packed solvent_accessibility")
     assert torch.equal(po["rsa"], p["rsa"])
     # a cropped window's values are the window's own: the restatement of the window alone, with no length
     w = foldcomp.decode_tensors(records, codec=codec, max_len=64, crop="center", layout="atom14", sasa=True)

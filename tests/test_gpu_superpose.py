@@ -10,9 +10,10 @@ reference differ by one rounding flip at most (2 ulps allowed), and no deviation
 import numpy as np
 import pytest
 
+import _analysis as AN
 import _superpose as S
-from _cases import compress_cases, db_cases
-from _devpath import HostGuarded, host_ptr, to_dev
+from _cases import golden_records_raw
+from _devpath import DevGuarded, HostGuarded, host_ptr, to_dev
 from _window import Decoded
 
 pytestmark = pytest.mark.gpu
@@ -28,7 +29,7 @@ def walk():
     and packed, with the reference: computed once, never changed"""
     lens, pos_t, mask, pos_p = S.walk_batch()
     ref = S.superpose_padded(pos_t, mask, pos_p, mask, lens, 1)
-    row_off = np.concatenate([[0], np.cumsum(lens)]).astype(np.uint32)
+    row_off = AN.row_off_of(lens)
     return dict(lens=lens.astype(np.uint32), n=len(lens), L=pos_t.shape[1], arrays=(pos_t, mask, pos_p), ref=ref, row_off=row_off,
                 packed=S.pack((pos_t, mask, pos_p), lens), solved=lens >= 3)
 
@@ -178,8 +179,7 @@ def test_hostile_row_off(codec):
     pos_t, pos_p = S.in_slot(x.astype(F), 4, 1), S.in_slot(y.astype(F), 4, 1)
     mask = np.ones((R, 4), np.uint8)
     dev = [to_dev(a) for a in (pos_t, mask, pos_p)]
-    # chain 0 runs backwards (empty), rows 0 .. 39 are left uncovered, chain 4 runs past R (clamped to the rows that exist)
-    row_off = np.asarray([300, 40, 120, 400, 401, 950], np.uint32)
+    row_off = AN.HOSTILE_ROW_OFF
     ref = S.superpose_packed(pos_t, mask, pos_p, None, row_off, 1)
     got = S.run_dev(codec, *dev, None, to_dev(row_off), 5, R, 2, 1, True)
     assert list(got["sites"]) == [0, 80, 280, 1, 299] == list(ref["sites"])
@@ -197,8 +197,7 @@ def test_hostile_row_off(codec):
         """fcz_superpose_packed on host arrays (pos_true, mask_true, pos_pred), its outputs between guard bytes"""
         import ctypes
         from foldcomp_amd.structure import CSuperposeOut
-        shapes = S.out_shapes(n, rows, True)
-        h = HostGuarded({k: (S.DTYPES[k], shapes[k]) for k in S.KEYS})
+        h = HostGuarded(S.out_spec(n, rows, True))
         o = CSuperposeOut(*h.ptrs())
         assert codec.lib.fcz_superpose_packed(codec.ctx, *(host_ptr(a) for a in arrays), None, host_ptr(off), n, rows, 2, 1, ctypes.byref(o)) == 0
         return {k: h.fetch(k) for k in S.KEYS}
@@ -222,7 +221,7 @@ def test_hostile_row_off(codec):
     assert not empty["rmsd"].view(np.uint32).any() and not empty["tm"].view(np.uint32).any()
     S.same_bytes(host_form(one, zeros, 3, 0), empty, "fcz_superpose_packed R=0")
     import torch
-    g, tensors = S.Guarded({"out": 48}), [to_dev(a) for a in (zeros, empty["rot"], empty["trans"])]
+    g, tensors = DevGuarded({"out": (F, (1, 4, 3))}), [to_dev(a) for a in (zeros, empty["rot"], empty["trans"])]
     torch.cuda.synchronize()
     assert codec.lib.fcz_superpose_apply_packed_dev(codec.ctx, dev[2].data_ptr(), None, tensors[0].data_ptr(), 3, 0, 2, tensors[1].data_ptr(),
                                                     tensors[2].data_ptr(), g.ptr("out")) == 0
@@ -259,7 +258,7 @@ def test_apply_on_bits(codec, walk):
         assert exp.any() and not exp[mask == 0].any()
         # packed, mask NULL, transforms that are no rotations
         any_rot, any_trans = rng.uniform(-2, 2, (n, 3, 3)).astype(F), rng.uniform(-100, 100, (n, 3)).astype(F)
-        row_off = np.concatenate([[0], np.cumsum(ln)]).astype(np.uint32)
+        row_off = AN.row_off_of(ln)
         ppos, pmask = S.pack((pos, mask), ln)
         got = S.run_apply(codec, to_dev(ppos), None, to_dev(row_off), n, len(ppos), layout, to_dev(any_rot), to_dev(any_trans), True)
         assert got.tobytes() == S.apply_expected(ppos, None, any_rot, any_trans, row_off=row_off).tobytes(), layout
@@ -276,12 +275,9 @@ def test_refusals_leave_the_outputs_untouched(codec):
     import torch
     from foldcomp_amd.structure import CSuperposeOut
     n, L, A = 2, 8, 37
-    pos = torch.zeros((n, L, A, 3), dtype=torch.float32, device="cuda:0")
-    mask = torch.ones((n, L, A), dtype=torch.uint8, device="cuda:0")
-    off = to_dev(np.asarray([0, 8, 16], np.uint32))
-    shapes = S.out_shapes(n, L, False)
-    g = S.Guarded({k: 4 * int(np.prod(shapes[k])) for k in S.KEYS})
-    g2 = S.Guarded({"out": 4 * n * L * A * 3})
+    pos, mask, _, off = AN.refusal_inputs(n, L, A)
+    g = DevGuarded(S.out_spec(n, L, False))
+    g2 = DevGuarded({"out": (F, (n, L, A, 3))})
     out = CSuperposeOut(*(g.ptr(k) for k in S.KEYS))
     no_rot = CSuperposeOut(None, *(g.ptr(k) for k in S.KEYS[1:]))
     no_trans = CSuperposeOut(g.ptr("rot"), None, *(g.ptr(k) for k in S.KEYS[2:]))
@@ -317,10 +313,7 @@ def test_refusals_leave_the_outputs_untouched(codec):
 
 @pytest.fixture(scope="module")
 def records(golden):
-    z, index = golden
-    names = compress_cases(index) + db_cases(index)
-    assert len(names) == 56
-    return [z[f"{n}/fcz"].tobytes() for n in names]
+    return golden_records_raw(golden)[1]
 
 
 def _moved(pos, rng, noise):
@@ -356,7 +349,7 @@ def test_golden_records(codec, records):
         S.proper(got["rot"], name)
         assert got["rmsd"][::7].max() < 1e-3 and np.median(got["rmsd"]) > 0.5 and (got["sites"] > 0).sum() >= 50
         lens = np.minimum(h["length"].astype(np.int64), L_GOLD)
-        row_off = np.concatenate([[0], np.cumsum(lens)]).astype(np.uint32)
+        row_off = AN.row_off_of(lens)
         pk = S.run_dev(codec, *(to_dev(a) for a in S.pack((h["pos"], h["mask"], pred), lens)), None, to_dev(row_off), n, int(row_off[-1]), 0, slot, True)
         S.same_bytes({k: pk[k] for k in S.KEYS[:-1]}, {k: got[k] for k in S.KEYS[:-1]}, f"packed {name}")
         assert pk["dev"].tobytes() == S.pack((got["dev"],), lens)[0].tobytes()

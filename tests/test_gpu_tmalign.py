@@ -11,7 +11,8 @@ import pytest
 
 import _superpose as SP
 import _tmalign as TA
-from _cases import compress_cases, db_cases
+from _cases import golden_records_raw
+from _devpath import DevGuarded, HostGuarded
 
 pytestmark = pytest.mark.gpu
 
@@ -222,9 +223,6 @@ def test_refusals_leave_the_outputs_untouched(codec, batch, batch_dev):
     assert TA.run_dev(codec, da, db, pt[:0], b["wa"], b["wb"], LAY, SLOT, want=("rot", "trans"))["rot"].shape == (0, 3, 3)
 
 
-FILL = 0xA5
-
-
 def _refused(codec, bt, host, dp, **change):
     """one call of fcz_tmalign_dev / fcz_tmalign (host) / fcz_tmalign_dp_dev / fcz_tmalign_dp (dp) on the seeded batch with ONE argument
     changed: it must return FCZ_E_INVALID_ARG and leave every output byte, guards included, as it was. change: a / b = None or a dict
@@ -250,15 +248,9 @@ def _refused(codec, bt, host, dp, **change):
         return c
     sa, sb = cset(bt["sa"], change.get("a", {})), cset(bt["sb"], change.get("b", {}))
     pairs = put(bt["pairs"])
-    shapes = {k: (m,) + ((wa,) if tail == "wa" else tail) for k, _, tail in TA.OUTPUTS}
-    sizes = {k: 4 * int(np.prod(shapes[k])) for k in (("map", "aligned", "rot", "trans") if dp else TA.KEYS)}
-    if host:
-        raw = {k: np.full(v + 128, FILL, np.uint8) for k, v in sizes.items()}
-        ptr = lambda k: raw[k].ctypes.data + 64
-        untouched = lambda: all((r == FILL).all() for r in raw.values())
-    else:
-        g = SP.Guarded(sizes)
-        ptr, untouched = g.ptr, g.untouched
+    spec = TA.out_spec(m, wa, ("map", "aligned", "rot", "trans") if dp else TA.KEYS)
+    g = HostGuarded(spec, guard=64) if host else DevGuarded(spec)
+    ptr, untouched = g.ptr, g.untouched
     nulls = change.get("nulls", ())
     ref = lambda o: None if o is None else ctypes.byref(o)
     args = [codec.ctx, ref(sa), ref(sb), None if "pairs" in change else addr(pairs), m, change.get("wa", wa), change.get("wb", bt["wb"]),
@@ -308,10 +300,10 @@ def test_every_refusal_of_the_four_entry_points(codec, batch, host):
 
 @pytest.fixture(scope="module")
 def records(golden):
-    z, index = golden
-    names = [n for n in compress_cases(index) + db_cases(index) if 40 <= len(z[f"{n}/fasta"]) <= 160][:6]
-    assert len(names) == 6
-    return [z[f"{n}/fcz"].tobytes() for n in names], min(len(z[f"{n}/fasta"]) for n in names)
+    z = golden[0]
+    six = [(e, len(z[f"{n}/fasta"])) for n, e in zip(*golden_records_raw(golden)) if 40 <= len(z[f"{n}/fasta"]) <= 160][:6]
+    assert len(six) == 6
+    return [e for e, _ in six], min(m for _, m in six)
 
 
 def test_foldcomp_tm_align_on_windows_of_the_golden_records(codec, records):

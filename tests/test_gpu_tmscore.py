@@ -12,10 +12,11 @@ the same selections, and the winning fit is one Kabsch on a known set: what _sup
 import numpy as np
 import pytest
 
+import _analysis as AN
 import _superpose as SP
 import _tmscore as T
-from _cases import compress_cases, db_cases
-from _devpath import HostGuarded, host_ptr, to_dev
+from _cases import golden_records_raw
+from _devpath import DevGuarded, HostGuarded, host_ptr, to_dev
 from _window import Decoded
 
 pytestmark = pytest.mark.gpu
@@ -30,7 +31,7 @@ def walk():
     packed, with the reference: computed once, never changed"""
     lens, hinged, pos_t, mask, pos_p = (a.copy() for a in T.tm_batch())          # (copies: torch takes no read-only array)
     ref, _ = T.tm_batch_reference()
-    row_off = np.concatenate([[0], np.cumsum(lens)]).astype(np.uint32)
+    row_off = AN.row_off_of(lens)
     return dict(lens=lens.astype(np.uint32), hinged=hinged, n=len(lens), L=pos_t.shape[1], arrays=(pos_t, mask, pos_p), ref=ref, row_off=row_off,
                 packed=SP.pack((pos_t, mask, pos_p), lens), solved=lens >= 3)
 
@@ -89,7 +90,7 @@ def test_host_forms_give_the_same_bytes(codec, walk, walk_dev):
     got = {k: v[keep] for k, v in walk_dev[1].items()}
     h = codec.tm_score(arrays[0], arrays[1], arrays[2], None, 1, length=lens)
     SP.same_bytes({k: h[k] for k in T.KEYS}, got, "fcz_tmscore")
-    row_off = np.concatenate([[0], np.cumsum(lens)]).astype(np.uint32)
+    row_off = AN.row_off_of(lens)
     h = codec.tm_score(*SP.pack(arrays, lens), None, 1, row_off=row_off)
     SP.same_bytes({k: h[k] for k in T.KEYS if k != "dev"}, {k: got[k] for k in T.KEYS if k != "dev"}, "fcz_tmscore_packed")
     assert h["dev"].tobytes() == SP.pack((got["dev"],), lens)[0].tobytes()
@@ -233,8 +234,7 @@ def test_hostile_row_off(codec):
     pos_t, pos_p = SP.in_slot(x.astype(F), 4, 1), SP.in_slot(y.astype(F), 4, 1)
     mask = np.ones((R, 4), np.uint8)
     dev = [to_dev(a) for a in (pos_t, mask, pos_p)]
-    # chain 0 runs backwards (empty), rows 0 .. 39 are left uncovered, chain 4 runs past R (clamped to the rows that exist)
-    row_off = np.asarray([300, 40, 120, 400, 401, 950], np.uint32)
+    row_off = AN.HOSTILE_ROW_OFF
     traces = []
     ref = T.tm_packed(pos_t, mask, pos_p, None, row_off, 1, traces=traces)
     T.assert_fair(pos_t, pos_p, 1, traces, "hostile row_off")
@@ -251,8 +251,7 @@ def test_hostile_row_off(codec):
         """fcz_tmscore_packed on host arrays (pos_true, mask_true, pos_pred), its outputs between guard bytes"""
         import ctypes
         from foldcomp_amd.structure import CTmScoreOut
-        shapes = T.out_shapes(n, rows, True)
-        h = HostGuarded({k: (T.DTYPES[k], shapes[k]) for k in T.KEYS})
+        h = HostGuarded(T.out_spec(n, rows, True))
         o = CTmScoreOut(*h.ptrs())
         assert codec.lib.fcz_tmscore_packed(codec.ctx, *(host_ptr(a) for a in arrays), None, host_ptr(off), n, rows, 2, 1, 0, 20, ctypes.byref(o)) == 0
         return {k: h.fetch(k) for k in T.KEYS}
@@ -285,11 +284,8 @@ def test_refusals_leave_the_outputs_untouched(codec):
     import torch
     from foldcomp_amd.structure import CTmScoreOut
     n, L, A = 2, 8, 37
-    pos = torch.zeros((n, L, A, 3), dtype=torch.float32, device="cuda:0")
-    mask = torch.ones((n, L, A), dtype=torch.uint8, device="cuda:0")
-    off = to_dev(np.asarray([0, 8, 16], np.uint32))
-    shapes = T.out_shapes(n, L, False)
-    g = SP.Guarded({k: 4 * int(np.prod(shapes[k])) for k in T.KEYS})
+    pos, mask, _, off = AN.refusal_inputs(n, L, A)
+    g = DevGuarded(T.out_spec(n, L, False))
     out = CTmScoreOut(*(g.ptr(k) for k in T.KEYS))
     no_rot = CTmScoreOut(None, *(g.ptr(k) for k in T.KEYS[1:]))
     no_trans = CTmScoreOut(g.ptr("rot"), None, *(g.ptr(k) for k in T.KEYS[2:]))
@@ -323,10 +319,10 @@ L_GOLD = 160
 @pytest.fixture(scope="module")
 def records(golden):
     """the first sixteen golden records of at most L_GOLD residues (2 .. 129): a reference of the whole search costs seeds x rounds"""
-    z, index = golden
-    names = [n for n in compress_cases(index) + db_cases(index) if len(z[f"{n}/fasta"]) <= L_GOLD][:16]
-    assert len(names) == 16
-    return [z[f"{n}/fcz"].tobytes() for n in names]
+    z = golden[0]
+    short = [e for n, e in zip(*golden_records_raw(golden)) if len(z[f"{n}/fasta"]) <= L_GOLD][:16]
+    assert len(short) == 16
+    return short
 
 
 def _moved(pos, length, rng, noise):
@@ -363,7 +359,7 @@ def test_golden_records(codec, records):
         _show(f"golden records, {name}", SP.close(got, ref, name, compare_rot=ref["selected"] >= 3))
         SP.proper(got["rot"], name)
         lens = np.minimum(h["length"].astype(np.int64), L_GOLD)
-        row_off = np.concatenate([[0], np.cumsum(lens)]).astype(np.uint32)
+        row_off = AN.row_off_of(lens)
         pk = T.run_dev(codec, *(to_dev(a) for a in SP.pack((h["pos"], h["mask"], pred), lens)), None, to_dev(row_off), n, int(row_off[-1]), 0, slot, True)
         SP.same_bytes({k: pk[k] for k in T.KEYS if k != "dev"}, {k: got[k] for k in T.KEYS if k != "dev"}, f"packed {name}")
         assert pk["dev"].tobytes() == SP.pack((got["dev"],), lens)[0].tobytes()

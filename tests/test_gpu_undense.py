@@ -9,7 +9,7 @@ import pytest
 import _dense as D
 import _harness as H
 import _undense as U
-from _cases import compress_cases, db_cases, entries_blob, golden_batch
+from _cases import compress_cases, entries_blob, golden_batch, golden_records_raw
 from foldcomp_amd import _lib, fczfile
 from foldcomp_amd._aa_tables import ATOM_NAMES, RES3, RES_NATOMS
 from foldcomp_amd.structure import AtomTable, CChainBatch, CDenseIn, ChainBatch, batch_as_c
@@ -113,10 +113,7 @@ def resident_batch(codec, d, layout, thr=25, titles=None):
 
 @pytest.fixture(scope="module")
 def records(golden):
-    z, index = golden
-    names = compress_cases(index) + db_cases(index)
-    assert len(names) == 56
-    return names, [z[f"{n}/fcz"].tobytes() for n in names]
+    return golden_records_raw(golden)
 
 
 def golden_dense(records, layout, L, rng=None):

@@ -8,7 +8,7 @@ import pytest
 
 import _dense as D
 import _undense as U
-from _cases import compress_cases, db_cases, golden_batch
+from _cases import compress_cases, golden_batch, golden_records_raw
 from foldcomp_amd import _lib
 from foldcomp_amd.structure import CChainBatch, CDenseIn
 
@@ -101,10 +101,7 @@ def padded_records(codec, d, layout, thr=25, titles=None):
 
 @pytest.fixture(scope="module")
 def records(golden):
-    z, index = golden
-    names = compress_cases(index) + db_cases(index)
-    assert len(names) == 56
-    return names, [z[f"{n}/fcz"].tobytes() for n in names]
+    return golden_records_raw(golden)
 
 
 def test_round_trip_gives_the_records_of_the_padded_path(codec, records, golden):

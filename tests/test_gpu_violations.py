@@ -7,18 +7,17 @@ import ctypes
 import numpy as np
 import pytest
 
+import _analysis as AN
 import _dense as DN
-import _dssp as D
 import _violations as V
-from _cases import compress_cases, db_cases
+from _analysis import NAN_BITS
+from _cases import golden_records_raw
 from _devpath import HostGuarded, host_ptr, to_dev
-from _window import Decoded
 from foldcomp_amd import _lib, api
 
 pytestmark = pytest.mark.gpu
 
 L_GOLD = 256
-NAN_BITS = np.uint32(0x7FC00123)
 F = np.float32
 TABLE = {A: V.default_table(A) for A in (37, 14, 4)}
 TILE = {37: 20, 14: 18, 4: 64}                                               # rows per query tile (fcz_violations.h, viol_tile_rows)
@@ -27,34 +26,19 @@ ROW_KEYS = V.KEYS[1:-1]
 
 @pytest.fixture(scope="module")
 def records(golden):
-    z, index = golden
-    names = compress_cases(index) + db_cases(index)
-    assert len(names) == 56
-    return [z[f"{n}/fcz"].tobytes() for n in names]
-
-
-def _to14(c37, aatype):
-    """per-slot values of atom37 [.., 37] -> atom14 [.., 14] through the slot map of every row's type"""
-    slot = np.full((21, 14), -1, np.int64)
-    for ty in range(21):
-        for j, code in enumerate(DN.RES_ATOMS[ty]):
-            slot[ty, j] = DN.expected_slot("atom37", ty, code)
-    s = slot[np.minimum(aatype, 20)]
-    return np.where(s >= 0, np.take_along_axis(c37, np.maximum(s, 0), axis=-1), 0).astype(c37.dtype)
+    return golden_records_raw(golden)[1]
 
 
 @pytest.fixture(scope="module")
 def gold(codec, records):
     """the 56 golden records as atom37 / atom14 / backbone4 at L = 256 on the host and the device, and the restatement on atom37 and
     on backbone4: computed once, never changed"""
-    dec = Decoded(codec, records)
-    host = {lay: dec.dense(lay, L_GOLD, want=("pos", "mask", "aatype", "length")) for lay in DN.LAYOUTS}
-    dev = {lay: {k: to_dev(v) for k, v in host[lay].items()} for lay in DN.LAYOUTS}
+    host, dev = AN.decoded_layouts(codec, records, L_GOLD, ("pos", "mask", "aatype", "length"))
     a, b = host["atom37"], host["backbone4"]
     assert a["length"].max() >= L_GOLD
     exp37 = V.violations(a["pos"], a["mask"], a["aatype"], a["length"], TABLE[37])
     exp4 = V.violations(b["pos"], b["mask"], b["aatype"], b["length"], TABLE[4])
-    exp = dict(atom37=exp37, atom14=dict(exp37, clash_atom=_to14(exp37["clash_atom"], a["aatype"])), backbone4=exp4)
+    exp = dict(atom37=exp37, atom14=dict(exp37, clash_atom=AN.to14(exp37["clash_atom"], a["aatype"])), backbone4=exp4)
     return dict(host=host, dev=dev, n=len(records), exp=exp)
 
 
@@ -84,9 +68,9 @@ def test_golden_padded(codec, gold):
 
 def test_golden_packed(codec, gold):
     lens = np.minimum(gold["host"]["atom37"]["length"].astype(np.int64), L_GOLD)
-    row_off = np.concatenate([[0], np.cumsum(lens)]).astype(np.uint32)
+    row_off = AN.row_off_of(lens)
     R = int(row_off[-1])
-    cat = lambda a: np.concatenate([a[e, :m] for e, m in enumerate(lens)])
+    cat = lambda a: AN.pack1(a, lens)
     for lay in DN.LAYOUTS:
         hh = gold["host"][lay]
         got = V.run_violations(codec, to_dev(cat(hh["pos"])), to_dev(cat(hh["mask"])), to_dev(cat(hh["aatype"])), to_dev(row_off), gold["n"], R, DN.LAYOUTS[lay], True)
@@ -96,20 +80,6 @@ def test_golden_packed(codec, gold):
 
 # ---- synthetic tensors ----------------------------------------------------------------------------------------------------------
 
-def _helix(rng, m, A):
-    """m rows of A atoms: an ideal alpha helix (backbone4) with a jitter of 0.05, for A > 4 the other atoms scattered about every CA"""
-    if m == 0:
-        return np.zeros((0, A, 3), F)
-    bb = D.ideal_backbone(-57, -47, m)[0] + (rng.standard_normal((m, 4, 3)) * 0.05).astype(F)
-    if A == 4:
-        return bb
-    side = bb[:, 1:2] + (rng.standard_normal((m, A - 4, 3)) * 2.0).astype(F)
-    full = np.concatenate([bb, side], axis=1)
-    if A == 37:                                                               # O is slot 4 there, slot 3 the CB
-        full[:, [3, 4]] = full[:, [4, 3]]
-    return full
-
-
 def _synthetic(lens, A, seed, full=(), hostile=True):
     """chains [n, L, A, 3] of jittered helices; the chains in `full` keep every mask set, the others lose ~1 % of their masks (NaN
     patterns under the cleared masks) and, from 12 rows on and with hostile, get a NaN, +inf, -inf and two 3e19 coordinates under
@@ -118,7 +88,7 @@ def _synthetic(lens, A, seed, full=(), hostile=True):
     n, L = len(lens), max(max(lens), 1)
     pos, mask = np.zeros((n, L, A, 3), F), np.ones((n, L, A), np.uint8)
     for e, m in enumerate(lens):
-        pos[e, :m] = _helix(rng, m, A)
+        pos[e, :m] = AN.helix(rng, m, A)
         if e not in full:
             mask[e, :m][rng.random((m, A)) < 0.01] = 0
             if hostile and m >= 12:
@@ -133,12 +103,8 @@ def _synthetic(lens, A, seed, full=(), hostile=True):
     return pos, mask, aatype
 
 
-def _pack(arrays, lens):
-    return [np.concatenate([a[e, :m] for e, m in enumerate(lens)]) for a in arrays]
-
-
 def _pack_dict(exp, lens):
-    return {k: (v if k == "chain_counts" else np.concatenate([v[e, :m] for e, m in enumerate(lens)])) for k, v in exp.items()}
+    return {k: (v if k == "chain_counts" else AN.pack1(v, lens)) for k, v in exp.items()}
 
 
 @pytest.fixture(scope="module", params=[37, 14, 4])
@@ -175,7 +141,7 @@ def synthetic(request):
     assert exp["clash_depth"][e, 5].view(np.uint32) == exp["clash_depth"][e, 7].view(np.uint32) == exp["clash_depth"][e, 9].view(np.uint32)
     assert exp["link_violation"][e, 19] & 1 and exp["link_violation"][e, 29] & 4 and exp["chain_counts"][e, 2] >= 1 and exp["chain_counts"][e, 3] >= 1
     return dict(A=A, layout={37: 0, 14: 1, 4: 2}[A], lens=ln, L=max(lens), arrays=(pos, mask, aa),
-                row_off=np.concatenate([[0], np.cumsum(lens)]).astype(np.uint32), exp=exp)
+                row_off=AN.row_off_of(lens), exp=exp)
 
 
 def test_synthetic_padded_and_packed(codec, synthetic):
@@ -187,7 +153,7 @@ def test_synthetic_padded_and_packed(codec, synthetic):
     V.consistent(got, s["lens"])
     assert got["clash_count"].sum() > 0 and got["link_violation"].any() and got["viol_mask"].sum() > 200
     V.same_violations(V.run_violations(codec, pos, mask, aa, to_dev(s["lens"]), n, s["L"], s["layout"], False), got, "again")   # two calls give the same bytes
-    packed = _pack(s["arrays"], s["lens"])
+    packed = AN.pack(s["arrays"], s["lens"])
     R = int(s["row_off"][-1])
     gp = V.run_violations(codec, *(to_dev(a) for a in packed), to_dev(s["row_off"]), n, R, s["layout"], True, guard=8)
     V.same_violations(gp, _pack_dict(s["exp"], s["lens"]), "packed")           # padded and packed give the same values
@@ -237,8 +203,7 @@ def test_hostile_row_off(codec):
     pos[20, 1], pos[60, 1] = pos[500, 1], pos[600, 1]                         # ... and none with an uncovered row or across chains
     mask[[350, 130, 20, 60, 500, 600], 1] = 1
     dev = [to_dev(a) for a in (pos, mask, aa)]
-    # chain 0 runs backwards (empty), rows 0 .. 39 are left uncovered, chain 4 runs past R (clamped to the rows that exist)
-    row_off = np.asarray([300, 40, 120, 400, 401, 950], np.uint32)
+    row_off = AN.HOSTILE_ROW_OFF
     exp = V.violations(pos, mask, aa, row_off, TABLE[4], packed=True)
     assert exp["chain_counts"][0, 0] == 0 and exp["chain_counts"][3, 0] <= 4 and exp["clash_partner"][350] == 130 - 120 and exp["clash_partner"][130] == 350 - 120
     assert not exp["clash_count"][[20, 60, 500, 600]].any()
@@ -255,8 +220,7 @@ def test_hostile_row_off(codec):
     def host_form(arrays, off, n, rows):
         """fcz_violations_packed on host arrays, its outputs between guard bytes"""
         from foldcomp_amd.structure import CViolationsOut
-        shape = dict(clash_atom=(rows, 4), link_cos=(rows, 2), chain_counts=(n, 4))
-        h = HostGuarded({k: (V.DTYPES[k], shape.get(k, (rows,))) for k in V.KEYS})
+        h = HostGuarded(V.out_spec((rows,), 4, n))
         out = CViolationsOut(*h.ptrs())
         assert codec.lib.fcz_violations_packed(codec.ctx, *(host_ptr(a) for a in arrays), host_ptr(off), n, rows, 2, None, float(V.TOL), float(V.FACTOR),
                                                ctypes.byref(out)) == 0
@@ -274,11 +238,8 @@ def test_hostile_row_off(codec):
 def test_refusals_leave_the_outputs_untouched(codec):
     import torch
     n, L, A = 2, 8, 37
-    pos = torch.zeros((n, L, A, 3), dtype=torch.float32, device="cuda:0")
-    mask = torch.ones((n, L, A), dtype=torch.uint8, device="cuda:0")
-    aa = torch.zeros((n, L), dtype=torch.uint8, device="cuda:0")
-    off = to_dev(np.asarray([0, 8, 16], np.uint32))
-    o = V.Outputs(n * L, A, n)
+    pos, mask, aa, off = AN.refusal_inputs(n, L, A)
+    o = V.Outputs((n * L,), A, n)
     big, nan_tab = TABLE[37].copy(), TABLE[37].copy()
     big[3, 5], nan_tab[20, 0] = 8.0, np.nan
     lib, ctx = codec.lib, codec.ctx

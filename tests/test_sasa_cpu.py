@@ -108,7 +108,7 @@ def test_order_and_layout_do_not_show(chain):
     t37, t14 = S.default_table(37), S.default_table(14)
     c37, s37, m37 = S.sasa_chain(*views[37], aa, t37, S.PROBE, pts)
     c14, s14, m14 = S.sasa_chain(*views[14], aa, t14, S.PROBE, pts)
-    assert np.array_equal(S.K.bits(s37), S.K.bits(s14)) and np.array_equal(m37, m14) and m37.all()
+    assert np.array_equal(S.bits(s37), S.bits(s14)) and np.array_equal(m37, m14) and m37.all()
     for r in range(len(aa)):                                                  # the counts agree through the slot map
         for j, code in enumerate(DN.RES_ATOMS[int(aa[r])]):
             assert c14[r, j] == c37[r, DN.expected_slot("atom37", int(aa[r]), code)]
@@ -119,7 +119,7 @@ def test_order_and_layout_do_not_show(chain):
     assert np.array_equal(S.counts_chain(*views[14], aa, t14, S.PROBE, pts, order=rng.permutation(N)), c14)
     perm = rng.permutation(len(aa))                                           # the rows of the chain in another order
     cp, sp, _ = S.sasa_chain(views[14][0][perm], views[14][1][perm], aa[perm], t14, S.PROBE, pts)
-    assert np.array_equal(cp, c14[perm]) and np.array_equal(S.K.bits(sp), S.K.bits(s14[perm]))
+    assert np.array_equal(cp, c14[perm]) and np.array_equal(S.bits(sp), S.bits(s14[perm]))
     # aatype NULL is harmless in atom37 (every row of the default table is the same) and row 0 for every row in atom14
     S.same_sasa(S.sasa_chain(*views[37], None, t37, S.PROBE, pts), (c37, s37, m37), "atom37 without aatype")
     assert S.sasa_chain(*views[14], None, t14, S.PROBE, pts)[1].sum() < s14.sum()

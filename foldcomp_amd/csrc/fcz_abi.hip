@@ -1754,7 +1754,7 @@ static int knn_rows(fcz_ctx* ctx, const float* pos_dev, const uint8_t* mask_dev,
     chain_tiles ct(ctx, packed, n, rows);
     int rc = ct.reserve(); if (rc) return rc;
     span_guard sg(ctx, "knn");
-    return ct.run(bound_dev, [&] { hipLaunchKernelGGL(k_knn_fill, ct.fill_grid(rows), dim3(BLOCK), 0, ctx->stream, g); },
+    return ct.run(bound_dev, [&] { hipLaunchKernelGGL(k_chain_fill<knn_args>, ct.fill_grid(rows), dim3(BLOCK), 0, ctx->stream, g); },
                   [&](auto P, dim3 grid, const uint64_t* tile_off, uint32_t tiles_per_entry, uint64_t n_padded) {
         auto launch = [&](auto KCAP) {
             hipLaunchKernelGGL(HIP_KERNEL_NAME(k_knn<decltype(KCAP)::value, decltype(P)::value>), grid, dim3(BLOCK), 0, ctx->stream, g, tile_off, tiles_per_entry, n_padded);
@@ -1835,7 +1835,7 @@ static int lddt_rows(fcz_ctx* ctx, const float* pos_true_dev, const uint8_t* mas
     chain_tiles ct(ctx, packed, n, rows);
     int rc = ct.reserve(); if (rc) return rc;
     span_guard sg(ctx, "lddt");
-    return ct.run(bound_dev, [&] { hipLaunchKernelGGL(k_lddt_fill, ct.fill_grid(rows), dim3(BLOCK), 0, ctx->stream, g); },
+    return ct.run(bound_dev, [&] { hipLaunchKernelGGL(k_chain_fill<lddt_args>, ct.fill_grid(rows), dim3(BLOCK), 0, ctx->stream, g); },
                   [&](auto P, dim3 grid, const uint64_t* tile_off, uint32_t tiles_per_entry, uint64_t n_padded) {
         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_lddt<decltype(P)::value>), grid, dim3(BLOCK), 0, ctx->stream, g, tile_off, tiles_per_entry, n_padded);
     });
@@ -1931,7 +1931,7 @@ static int lddta_rows(fcz_ctx* ctx, const float* pos_true_dev, const uint8_t* ma
     int rc = decide.reserve(); if (rc) return rc;
     rc = score.reserve(); if (rc) return rc;                                  // (the same scratch: the decide sweep has read its tiles by then)
     span_guard sg(ctx, "lddt_atoms");
-    rc = decide.run(bound_dev, [&] { hipLaunchKernelGGL(k_lddt_atoms_fill, decide.fill_grid(rows), dim3(BLOCK), 0, ctx->stream, g); },
+    rc = decide.run(bound_dev, [&] { hipLaunchKernelGGL(k_chain_fill<lddta_args>, decide.fill_grid(rows), dim3(BLOCK), 0, ctx->stream, g); },
                     [&](auto P, dim3 grid, const uint64_t* tile_off, uint32_t tiles_per_entry, uint64_t n_padded) {
         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_lddt_atoms<decltype(P)::value, true>), grid, dim3(BLOCK), 0, ctx->stream, g, tab, tile_off, tiles_per_entry, n_padded);
     });
@@ -2050,7 +2050,7 @@ static int hbond_rows(fcz_ctx* ctx, const float* pos_dev, const uint8_t* mask_de
     chain_tiles ct(ctx, packed, n, rows);
     int rc = ct.reserve(); if (rc) return rc;
     span_guard sg(ctx, "dssp");
-    return ct.run(bound_dev, [&] { hipLaunchKernelGGL(k_dssp_fill, ct.fill_grid(rows), dim3(BLOCK), 0, ctx->stream, g, 1); },
+    return ct.run(bound_dev, [&] { hipLaunchKernelGGL(k_chain_fill<hbond_fill_args>, ct.fill_grid(rows), dim3(BLOCK), 0, ctx->stream, hbond_fill_args{g}); },
                   [&](auto P, dim3 grid, const uint64_t* tile_off, uint32_t tiles_per_entry, uint64_t n_padded) {
         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_hbond<decltype(P)::value>), grid, dim3(BLOCK), 0, ctx->stream, g, tile_off, tiles_per_entry, n_padded);
     });
@@ -2070,7 +2070,7 @@ static int dssp_label_rows(fcz_ctx* ctx, const float* pos_dev, const uint8_t* ma
         g.flags = ctx->dssp_flags.as<uint8_t>();
     }
     span_guard sg(ctx, "dssp");
-    return ct.run(bound_dev, [&] { hipLaunchKernelGGL(k_dssp_fill, ct.fill_grid(rows), dim3(BLOCK), 0, ctx->stream, g, 2); },
+    return ct.run(bound_dev, [&] { hipLaunchKernelGGL(k_chain_fill<label_fill_args>, ct.fill_grid(rows), dim3(BLOCK), 0, ctx->stream, label_fill_args{g}); },
                   [&](auto P, dim3 grid, const uint64_t* tile_off, uint32_t tiles_per_entry, uint64_t n_padded) {
         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_dssp_flags<decltype(P)::value>), grid, dim3(BLOCK), 0, ctx->stream, g, tile_off, tiles_per_entry, n_padded);
         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_dssp_labels<decltype(P)::value>), grid, dim3(BLOCK), 0, ctx->stream, g, tile_off, tiles_per_entry, n_padded);
@@ -2154,16 +2154,16 @@ static float sasa_element_radius(const char* name) {
 
 // rows: L (padded) or R (packed). Fills tab from radius_table (NULL: the default) when everything is acceptable.
 static bool sasa_args_ok(const fcz_ctx* ctx, const float* pos, const uint8_t* mask, const uint8_t* aatype, int layout, uint32_t rows, const float* radius_table,
-                         float probe, const float* points, uint32_t n_points, std::initializer_list<const void*> out, sasa_table* tab) {
+                         float probe, const float* points, uint32_t n_points, std::initializer_list<const void*> out, chain_radii* tab) {
     const int A = fcz_dense_width(layout);
     if (!ctx || !pos || !mask || !points || A <= 0 || rows > SASA_MAX_ROWS) return false;
     for (const void* p : out) if (!p) return false;
     if (n_points < 1 || n_points > SASA_MAX_POINTS || !std::isfinite(probe) || probe < 0.0f) return false;
     if (layout == FCZ_DENSE_ATOM14 && !aatype) return false;                  // a slot's atom depends on the type there
     memset(tab->radius, 0, sizeof tab->radius);
-    if (radius_table) memcpy(tab->radius, radius_table, sizeof(float) * SASA_TYPES * (size_t)A);
+    if (radius_table) memcpy(tab->radius, radius_table, sizeof(float) * CHAIN_TYPES * (size_t)A);
     else if (fcz_sasa_default_radii(layout, tab->radius) != FCZ_OK) return false;
-    for (int i = 0; i < (int)SASA_TYPES * A; i++) {
+    for (int i = 0; i < (int)CHAIN_TYPES * A; i++) {
         const float r = tab->radius[i];
         if (r == 0.0f) continue;                                              // no atom in this slot
         const volatile float R = r + probe;                                   // (one float32 addition, as the kernel's)
@@ -2174,7 +2174,7 @@ static bool sasa_args_ok(const fcz_ctx* ctx, const float* pos, const uint8_t* ma
 
 // fcz_sasa_dev (bound_dev is length [n] or NULL, rows = L) and fcz_sasa_packed_dev (bound_dev = row_off [n + 1], rows = R)
 static int sasa_rows(fcz_ctx* ctx, const float* pos_dev, const uint8_t* mask_dev, const uint8_t* aatype_dev, const uint32_t* bound_dev, bool packed, uint32_t n,
-                     uint32_t rows, int layout, const sasa_table& tab, float probe, const float* points_dev, uint32_t n_points, int16_t* sasa_points_dev,
+                     uint32_t rows, int layout, const chain_radii& tab, float probe, const float* points_dev, uint32_t n_points, int16_t* sasa_points_dev,
                      float* sasa_dev, uint8_t* sasa_mask_dev) {
     HIP_TRY(hipSetDevice(ctx->device));
     if (rows == 0 || (n == 0 && !packed)) return FCZ_OK;
@@ -2187,7 +2187,7 @@ static int sasa_rows(fcz_ctx* ctx, const float* pos_dev, const uint8_t* mask_dev
     chain_tiles ct(ctx, packed, n, rows, SASA_TILE_ROWS);
     int rc = ct.reserve(); if (rc) return rc;
     span_guard sg(ctx, "sasa");
-    return ct.run(bound_dev, [&] { hipLaunchKernelGGL(k_sasa_fill, ct.fill_grid(rows), dim3(BLOCK), 0, ctx->stream, g); },
+    return ct.run(bound_dev, [&] { hipLaunchKernelGGL(k_chain_fill<sasa_args>, ct.fill_grid(rows), dim3(BLOCK), 0, ctx->stream, g); },
                   [&](auto P, dim3 grid, const uint64_t* tile_off, uint32_t tiles_per_entry, uint64_t n_padded) {
         if (small) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_sasa_points<decltype(P)::value, true>), grid, dim3(BLOCK), 0, ctx->stream, g, tab, tile_off, tiles_per_entry, n_padded);
         else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_sasa_points<decltype(P)::value, false>), grid, dim3(BLOCK), 0, ctx->stream, g, tab, tile_off, tiles_per_entry, n_padded);
@@ -2196,7 +2196,7 @@ static int sasa_rows(fcz_ctx* ctx, const float* pos_dev, const uint8_t* mask_dev
 
 // fcz_sasa and fcz_sasa_packed: the host arrays through DENSE_IN 0 .. 3, SASA_POINTS 4 and SASA_OUT 10 .. 12
 static int sasa_host(fcz_ctx* ctx, const float* pos, const uint8_t* mask, const uint8_t* aatype, const uint32_t* bound, bool packed, uint32_t n, uint32_t rows_per,
-                     int layout, const sasa_table& tab, float probe, const float* points, uint32_t n_points, int16_t* sasa_points, float* sasa, uint8_t* sasa_mask) {
+                     int layout, const chain_radii& tab, float probe, const float* points, uint32_t n_points, int16_t* sasa_points, float* sasa, uint8_t* sasa_mask) {
     const dense_bytes b(packed, n, rows_per, layout, bound);
     return staged_call(ctx, {{pos, b.pos, DENSE_IN}, {mask, b.mask, DENSE_IN + 1}, {aatype, b.rows, DENSE_IN + 2}, {bound, b.bound, DENSE_IN + 3},
                              {points, (size_t)n_points * 3 * sizeof(float), SASA_POINTS}},
@@ -2222,7 +2222,7 @@ int fcz_sasa_default_radii(int layout, float* out) {
         }
     // atom14: a slot's atom depends on the type (row 20: the backbone-only codes). atom37 / backbone4: a slot holds the same atom in
     // every type, so every row is the same and the mask alone says which atoms a residue has. OXT is in no residue's table: 0.
-    for (int ty = 0; ty < (int)SASA_TYPES; ty++)
+    for (int ty = 0; ty < (int)CHAIN_TYPES; ty++)
         for (int a = 0; a < A; a++) out[ty * A + a] = layout == FCZ_DENSE_ATOM14 ? own[ty][a] : any[a];
     return FCZ_OK;
 }
@@ -2230,7 +2230,7 @@ int fcz_sasa_default_radii(int layout, float* out) {
 int fcz_sasa_dev(fcz_ctx* ctx, const float* pos_dev, const uint8_t* mask_dev, const uint8_t* aatype_dev, const uint32_t* length_dev, uint32_t n, uint32_t L,
                  int layout, const float* radius_table, float probe, const float* points_dev, uint32_t n_points, int16_t* sasa_points_dev, float* sasa_dev,
                  uint8_t* sasa_mask_dev) {
-    sasa_table tab;
+    chain_radii tab;
     if (!sasa_args_ok(ctx, pos_dev, mask_dev, aatype_dev, layout, L, radius_table, probe, points_dev, n_points, {sasa_points_dev, sasa_dev, sasa_mask_dev}, &tab) ||
         !bound_ok(false, length_dev, n, L))
         return FCZ_E_INVALID_ARG;
@@ -2240,7 +2240,7 @@ int fcz_sasa_dev(fcz_ctx* ctx, const float* pos_dev, const uint8_t* mask_dev, co
 int fcz_sasa_packed_dev(fcz_ctx* ctx, const float* pos_dev, const uint8_t* mask_dev, const uint8_t* aatype_dev, const uint32_t* row_off_dev, uint32_t n, uint32_t R,
                         int layout, const float* radius_table, float probe, const float* points_dev, uint32_t n_points, int16_t* sasa_points_dev,
                         float* sasa_dev, uint8_t* sasa_mask_dev) {
-    sasa_table tab;
+    chain_radii tab;
     if (!sasa_args_ok(ctx, pos_dev, mask_dev, aatype_dev, layout, R, radius_table, probe, points_dev, n_points, {sasa_points_dev, sasa_dev, sasa_mask_dev}, &tab) ||
         !bound_ok(true, row_off_dev, n, R))
         return FCZ_E_INVALID_ARG;
@@ -2249,7 +2249,7 @@ int fcz_sasa_packed_dev(fcz_ctx* ctx, const float* pos_dev, const uint8_t* mask_
 
 int fcz_sasa(fcz_ctx* ctx, const float* pos, const uint8_t* mask, const uint8_t* aatype, const uint32_t* length, uint32_t n, uint32_t L, int layout,
              const float* radius_table, float probe, const float* points, uint32_t n_points, int16_t* sasa_points, float* sasa, uint8_t* sasa_mask) {
-    sasa_table tab;
+    chain_radii tab;
     if (!sasa_args_ok(ctx, pos, mask, aatype, layout, L, radius_table, probe, points, n_points, {sasa_points, sasa, sasa_mask}, &tab) || !bound_ok(false, length, n, L))
         return FCZ_E_INVALID_ARG;
     return sasa_host(ctx, pos, mask, aatype, length, false, n, L, layout, tab, probe, points, n_points, sasa_points, sasa, sasa_mask);
@@ -2257,7 +2257,7 @@ int fcz_sasa(fcz_ctx* ctx, const float* pos, const uint8_t* mask, const uint8_t*
 
 int fcz_sasa_packed(fcz_ctx* ctx, const float* pos, const uint8_t* mask, const uint8_t* aatype, const uint32_t* row_off, uint32_t n, uint32_t R, int layout,
                     const float* radius_table, float probe, const float* points, uint32_t n_points, int16_t* sasa_points, float* sasa, uint8_t* sasa_mask) {
-    sasa_table tab;
+    chain_radii tab;
     if (!sasa_args_ok(ctx, pos, mask, aatype, layout, R, radius_table, probe, points, n_points, {sasa_points, sasa, sasa_mask}, &tab) || !bound_ok(true, row_off, n, R))
         return FCZ_E_INVALID_ARG;
     return sasa_host(ctx, pos, mask, aatype, row_off, true, n, R, layout, tab, probe, points, n_points, sasa_points, sasa, sasa_mask);
@@ -2275,15 +2275,15 @@ static bool viol_out_ok(const fcz_violations_out* o) {
 
 // rows: L (padded) or R (packed). Fills tab from radius_table (NULL: the default) when everything is acceptable.
 static bool viol_args_ok(const fcz_ctx* ctx, const float* pos, const uint8_t* mask, const uint8_t* aatype, int layout, uint32_t rows, const float* radius_table,
-                         float tolerance, float link_factor, const fcz_violations_out* out, sasa_table* tab) {
+                         float tolerance, float link_factor, const fcz_violations_out* out, chain_radii* tab) {
     const int A = fcz_dense_width(layout);
     if (!ctx || !pos || !mask || A <= 0 || rows > SASA_MAX_ROWS || !viol_out_ok(out)) return false;
     if (!std::isfinite(tolerance) || tolerance < 0.0f || !std::isfinite(link_factor) || link_factor < 0.0f) return false;
     if (layout == FCZ_DENSE_ATOM14 && !aatype) return false;                  // a slot's atom depends on the type there
     memset(tab->radius, 0, sizeof tab->radius);
-    if (radius_table) memcpy(tab->radius, radius_table, sizeof(float) * SASA_TYPES * (size_t)A);
+    if (radius_table) memcpy(tab->radius, radius_table, sizeof(float) * CHAIN_TYPES * (size_t)A);
     else if (fcz_sasa_default_radii(layout, tab->radius) != FCZ_OK) return false;
-    for (int i = 0; i < (int)SASA_TYPES * A; i++) {
+    for (int i = 0; i < (int)CHAIN_TYPES * A; i++) {
         const float r = tab->radius[i];
         if (r == 0.0f) continue;                                              // no atom in this slot
         if (!(r >= 0.5f && r < 8.0f)) return false;                           // (a NaN radius ends here)
@@ -2293,7 +2293,7 @@ static bool viol_args_ok(const fcz_ctx* ctx, const float* pos, const uint8_t* ma
 
 // fcz_violations_dev (bound_dev is length [n] or NULL, rows = L) and fcz_violations_packed_dev (bound_dev = row_off [n + 1], rows = R)
 static int viol_rows(fcz_ctx* ctx, const float* pos_dev, const uint8_t* mask_dev, const uint8_t* aatype_dev, const uint32_t* bound_dev, bool packed, uint32_t n,
-                     uint32_t rows, int layout, const sasa_table& tab, float tolerance, float link_factor, const fcz_violations_out& o) {
+                     uint32_t rows, int layout, const chain_radii& tab, float tolerance, float link_factor, const fcz_violations_out& o) {
     HIP_TRY(hipSetDevice(ctx->device));
     if (n == 0 && (rows == 0 || !packed)) return FCZ_OK;
     viol_args g{};
@@ -2311,7 +2311,7 @@ static int viol_rows(fcz_ctx* ctx, const float* pos_dev, const uint8_t* mask_dev
     span_guard sg(ctx, "violations");
     if (n) HIP_TRY(hipMemsetAsync(o.chain_counts, 0, sizeof(int64_t) * 4 * (size_t)n, ctx->stream));
     if (rows == 0) return FCZ_OK;                                             // (packed, chains without a row: their counters are 0)
-    return ct.run(bound_dev, [&] { hipLaunchKernelGGL(k_viol_fill, ct.fill_grid(rows), dim3(BLOCK), 0, ctx->stream, g); },
+    return ct.run(bound_dev, [&] { hipLaunchKernelGGL(k_chain_fill<viol_args>, ct.fill_grid(rows), dim3(BLOCK), 0, ctx->stream, g); },
                   [&](auto P, dim3 grid, const uint64_t* tile_off, uint32_t tiles_per_entry, uint64_t n_padded) {
         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_violations<decltype(P)::value>), grid, dim3(BLOCK), 0, ctx->stream, g, tab, tile_off, tiles_per_entry, n_padded);
     });
@@ -2319,7 +2319,7 @@ static int viol_rows(fcz_ctx* ctx, const float* pos_dev, const uint8_t* mask_dev
 
 // fcz_violations and fcz_violations_packed: the host arrays through DENSE_IN 0 .. 3 and VIOL_OUT 10 .. 19, the outputs in the struct's order
 static int viol_host(fcz_ctx* ctx, const float* pos, const uint8_t* mask, const uint8_t* aatype, const uint32_t* bound, bool packed, uint32_t n, uint32_t rows_per,
-                     int layout, const sasa_table& tab, float tolerance, float link_factor, const fcz_violations_out& o) {
+                     int layout, const chain_radii& tab, float tolerance, float link_factor, const fcz_violations_out& o) {
     const dense_bytes b(packed, n, rows_per, layout, bound);
     const size_t r = b.rows;
     return staged_call(ctx, {{pos, b.pos, DENSE_IN}, {mask, b.mask, DENSE_IN + 1}, {aatype, r, DENSE_IN + 2}, {bound, b.bound, DENSE_IN + 3}},
@@ -2340,7 +2340,7 @@ int fcz_violations_pass(void) { return (int)VIOL_PASS; }
 
 int fcz_violations_dev(fcz_ctx* ctx, const float* pos_dev, const uint8_t* mask_dev, const uint8_t* aatype_dev, const uint32_t* length_dev, uint32_t n, uint32_t L,
                        int layout, const float* radius_table, float tolerance, float link_factor, const fcz_violations_out* out_dev) {
-    sasa_table tab;
+    chain_radii tab;
     if (!viol_args_ok(ctx, pos_dev, mask_dev, aatype_dev, layout, L, radius_table, tolerance, link_factor, out_dev, &tab) || !bound_ok(false, length_dev, n, L))
         return FCZ_E_INVALID_ARG;
     return viol_rows(ctx, pos_dev, mask_dev, aatype_dev, length_dev, false, n, L, layout, tab, tolerance, link_factor, *out_dev);
@@ -2348,7 +2348,7 @@ int fcz_violations_dev(fcz_ctx* ctx, const float* pos_dev, const uint8_t* mask_d
 
 int fcz_violations_packed_dev(fcz_ctx* ctx, const float* pos_dev, const uint8_t* mask_dev, const uint8_t* aatype_dev, const uint32_t* row_off_dev, uint32_t n,
                               uint32_t R, int layout, const float* radius_table, float tolerance, float link_factor, const fcz_violations_out* out_dev) {
-    sasa_table tab;
+    chain_radii tab;
     if (!viol_args_ok(ctx, pos_dev, mask_dev, aatype_dev, layout, R, radius_table, tolerance, link_factor, out_dev, &tab) || !bound_ok(true, row_off_dev, n, R))
         return FCZ_E_INVALID_ARG;
     return viol_rows(ctx, pos_dev, mask_dev, aatype_dev, row_off_dev, true, n, R, layout, tab, tolerance, link_factor, *out_dev);
@@ -2356,14 +2356,14 @@ int fcz_violations_packed_dev(fcz_ctx* ctx, const float* pos_dev, const uint8_t*
 
 int fcz_violations(fcz_ctx* ctx, const float* pos, const uint8_t* mask, const uint8_t* aatype, const uint32_t* length, uint32_t n, uint32_t L, int layout,
                    const float* radius_table, float tolerance, float link_factor, const fcz_violations_out* out) {
-    sasa_table tab;
+    chain_radii tab;
     if (!viol_args_ok(ctx, pos, mask, aatype, layout, L, radius_table, tolerance, link_factor, out, &tab) || !bound_ok(false, length, n, L)) return FCZ_E_INVALID_ARG;
     return viol_host(ctx, pos, mask, aatype, length, false, n, L, layout, tab, tolerance, link_factor, *out);
 }
 
 int fcz_violations_packed(fcz_ctx* ctx, const float* pos, const uint8_t* mask, const uint8_t* aatype, const uint32_t* row_off, uint32_t n, uint32_t R, int layout,
                           const float* radius_table, float tolerance, float link_factor, const fcz_violations_out* out) {
-    sasa_table tab;
+    chain_radii tab;
     if (!viol_args_ok(ctx, pos, mask, aatype, layout, R, radius_table, tolerance, link_factor, out, &tab) || !bound_ok(true, row_off, n, R)) return FCZ_E_INVALID_ARG;
     return viol_host(ctx, pos, mask, aatype, row_off, true, n, R, layout, tab, tolerance, link_factor, *out);
 }
@@ -2392,7 +2392,7 @@ static int superpose_rows(fcz_ctx* ctx, const float* pos_true_dev, const uint8_t
     const uint32_t max_blocks = (uint32_t)ctx->n_cu * 16u;
     span_guard sg(ctx, "superpose");
     if (fill)
-        hipLaunchKernelGGL(k_superpose_fill, dim3((uint32_t)std::min<uint64_t>(((uint64_t)rows + BLOCK - 1) / BLOCK, max_blocks)), dim3(BLOCK), 0, ctx->stream, g);
+        hipLaunchKernelGGL(k_chain_fill<superpose_args>, dim3((uint32_t)std::min<uint64_t>(((uint64_t)rows + BLOCK - 1) / BLOCK, max_blocks)), dim3(BLOCK), 0, ctx->stream, g);
     if (n) {
         const dim3 grid(std::min(grid_for(n, WAVES_PER_BLOCK), max_blocks));
         if (packed) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_superpose<true>), grid, dim3(BLOCK), 0, ctx->stream, g);
@@ -2427,13 +2427,13 @@ static int superpose_apply_rows(fcz_ctx* ctx, const float* pos_dev, const uint8_
                                 int layout, const float* rot_dev, const float* trans_dev, float* pos_out_dev) {
     HIP_TRY(hipSetDevice(ctx->device));
     if (rows == 0 || (n == 0 && !packed)) return FCZ_OK;
-    const superpose_apply_args g{pos_dev, mask_dev, bound_dev, n, rows, rot_dev, trans_dev, pos_out_dev};
+    const superpose_apply_args g{pos_dev, mask_dev, bound_dev, n, rows, (uint32_t)fcz_dense_width(layout), rot_dev, trans_dev, pos_out_dev};
     chain_tiles ct(ctx, packed, n, rows);
     int rc = ct.reserve(); if (rc) return rc;
     span_guard sg(ctx, "superpose");
     dispatch_layout(layout, [&](auto W) {
         constexpr int A = decltype(W)::value;
-        rc = ct.run(bound_dev, [&] { hipLaunchKernelGGL(HIP_KERNEL_NAME(k_superpose_apply_fill<A>), ct.fill_grid((uint64_t)rows * (A * 3u)), dim3(BLOCK), 0, ctx->stream, g); },
+        rc = ct.run(bound_dev, [&] { hipLaunchKernelGGL(k_chain_fill<superpose_apply_args>, ct.fill_grid(rows), dim3(BLOCK), 0, ctx->stream, g); },
                     [&](auto P, dim3 grid, const uint64_t* tile_off, uint32_t tiles_per_entry, uint64_t n_padded) {
             hipLaunchKernelGGL(HIP_KERNEL_NAME(k_superpose_apply<A, decltype(P)::value>), grid, dim3(BLOCK), 0, ctx->stream, g, tile_off, tiles_per_entry, n_padded);
         });
@@ -2540,7 +2540,7 @@ static int tmscore_rows(fcz_ctx* ctx, const float* pos_true_dev, const uint8_t* 
     }
     span_guard sg(ctx, "tmscore");
     if (fill)
-        hipLaunchKernelGGL(k_superpose_fill, dim3((uint32_t)std::min<uint64_t>(((uint64_t)rows + BLOCK - 1) / BLOCK, max_blocks)), dim3(BLOCK), 0, ctx->stream, g.s);
+        hipLaunchKernelGGL(k_chain_fill<superpose_args>, dim3((uint32_t)std::min<uint64_t>(((uint64_t)rows + BLOCK - 1) / BLOCK, max_blocks)), dim3(BLOCK), 0, ctx->stream, g.s);
     if (n) {
         const dim3 chains(std::min(grid_for(n, WAVES_PER_BLOCK), max_blocks)), search((uint32_t)std::min<uint64_t>(items, max_blocks));
         if (packed) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tm_count<true>), chains, dim3(BLOCK), 0, ctx->stream, g, counts);

@@ -8,12 +8,76 @@
 // has a tile size of its own: fcz_sasa.h, fcz_violations.h): padded, tile -> (entry, tile of the entry) by division; packed, the
 // chains' tile counts are scanned on the device (k_chain_tiles with the sweep's rows per tile, device_scan) and a tile finds its
 // chain by binary search, as k_dense_packed's rows do.
+//
+// The skeleton every sweep kernel is built on lives here once; the kernels keep their LDS arrays, their sweep over the staged
+// candidates and their epilogue:
+//   chain_tile<PACKED>     the head of a kernel's tile loop: the tile's chain, its rows and the tile's first row (chain_tile_count
+//                          ends the loop).
+//   chain_stage_rows       one candidate pass of PASS chain rows, a row a lane and step (k_knn, k_lddt, k_hbond).
+//   chain_stage_slots      one candidate pass of at most PASS atoms, staged in steps of the rows that hold at most STEP slots
+//                          (k_sasa_points, k_violations, k_lddt_atoms).
+//                          Both hand the caller's functor a row (and slot) and a chain_slots; the functor decides whether that is a
+//                          candidate, claims a slot with next() and writes its own LDS arrays. Both hold barriers, so all BLOCK
+//                          threads call them under block-uniform control flow and no functor holds a barrier. The barrier that
+//                          closes a pass, behind the caller's sweep, stays in the caller.
+//   chain_tile_slots       the slots of a query tile of whole rows, strided over the block.
+//   k_chain_fill<Args>     packed form only, in front of a sweep: chain_empty_row(g, r), which every analysis defines beside its
+//                          args, for every row that no chain is seen to cover.
+//   chain_d2, chain_div_a, chain_site, chain_site2, chain_atom     the arithmetic and the "is this a site / an atom" rules.
 #pragma once
 #include "fcz_dense.h"
 
 namespace fcz {
 
 constexpr uint32_t CHAIN_TILE = BLOCK;      // query rows per tile (a lane per query)
+constexpr uint32_t CHAIN_TYPES = 21;
+
+struct chain_radii { float radius[CHAIN_TYPES * DN_MAX_WIDTH]; };   // [min(aatype, 20)][slot] with rows of A floats
+
+// x / A for the three widths there are, without a division by a variable
+__device__ __forceinline__ uint32_t chain_div_a(uint32_t x, uint32_t A) { return A == 37u ? x / 37u : A == 14u ? x / 14u : x / 4u; }
+
+// float32, every operation rounded, no FMA. d2(a, b) == d2(b, a) bit for bit: the differences are negated, the squares are the same.
+__device__ __forceinline__ float chain_d2(float ax, float ay, float az, float bx, float by, float bz) {
+    const float dx = __fsub_rn(ax, bx), dy = __fsub_rn(ay, by), dz = __fsub_rn(az, bz);
+    return __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
+}
+__device__ __forceinline__ float chain_d2(const float* a, const float* b) { return chain_d2(a[0], a[1], a[2], b[0], b[1], b[2]); }
+
+// the three coordinates of element o (= row * A + slot) of a tensor -> true when they are finite
+__device__ __forceinline__ bool chain_xyz(const float* pos, uint64_t o, float* c) {
+    const float* p = pos + o * 3u;
+    c[0] = p[0]; c[1] = p[1]; c[2] = p[2];
+    return isfinite(c[0]) && isfinite(c[1]) && isfinite(c[2]);
+}
+
+// element o of one tensor -> true when its mask is set and its three coordinates are finite
+__device__ __forceinline__ bool chain_site(const float* pos, const uint8_t* mask, uint64_t o, float* c) { return mask[o] != 0 && chain_xyz(pos, o, c); }
+
+// element ot of the truth and op of the prediction -> true when both masks are set (a NULL mask_pred is all set) and the six
+// coordinates are finite; with both masks set the six are loaded whatever they hold
+__device__ __forceinline__ bool chain_site2(const float* pos_true, const uint8_t* mask_true, uint64_t ot, const float* pos_pred, const uint8_t* mask_pred,
+                                            uint64_t op, float* t, float* p) {
+    if (mask_true[ot] == 0) return false;
+    if (mask_pred && mask_pred[op] == 0) return false;
+    const bool ft = chain_xyz(pos_true, ot, t), fp = chain_xyz(pos_pred, op, p);
+    return ft && fp;
+}
+
+// slot a of array row r (a row inside its chain) of g.pos / g.mask / g.aatype -> true when it is an ATOM: mask set, a non-zero radius
+// in tab[min(aatype, 20)][a] and three finite coordinates. c = (x, y, z, that radius), ty = the clamped aatype (0 without aatype).
+template <class Args>
+__device__ __forceinline__ bool chain_atom(const Args& g, const chain_radii& tab, uint64_t r, uint32_t a, float4* c, uint32_t* ty) {
+    if (g.mask[r * g.A + a] == 0) return false;
+    const uint32_t aa = g.aatype ? g.aatype[r] : 0u;
+    *ty = aa > 20u ? 20u : aa;
+    const float radius = tab.radius[*ty * g.A + a];
+    if (radius == 0.0f) return false;
+    float p[3];
+    if (!chain_xyz(g.pos, r * g.A + a, p)) return false;
+    *c = make_float4(p[0], p[1], p[2], radius);
+    return true;
+}
 
 // chain e: its first row in the arrays, the rows that may hold a site, the rows the sweep writes
 template <bool PACKED>
@@ -56,6 +120,97 @@ __device__ __forceinline__ bool chain_covers(const uint32_t* __restrict__ row_of
     if (n == 0) return false;
     const uint32_t e = dn_entry_of(row_off, 0u, n, (uint32_t)r);
     return row_off[e] <= r && r < row_off[e + 1];                     // (r < R: chain e's clamped range holds the row)
+}
+
+// packed form only, in front of a sweep: what an empty row holds into every row that no chain is seen to cover
+template <class Args>
+__global__ __launch_bounds__(BLOCK) void k_chain_fill(Args g) {
+    for (uint64_t r = (uint64_t)blockIdx.x * BLOCK + threadIdx.x; r < g.L; r += (uint64_t)gridDim.x * BLOCK) {
+        if (chain_covers(g.bound, g.n, r)) continue;
+        chain_empty_row(g, r);
+    }
+}
+
+// the tiles of a launch: a sweep kernel's last three arguments are tile_off, tiles_per_entry and the padded form's tile count
+template <bool PACKED>
+__device__ __forceinline__ uint64_t chain_tile_count(const uint64_t* __restrict__ tile_off, uint32_t n, uint64_t n_tiles_padded) {
+    return PACKED ? tile_off[n] : n_tiles_padded;
+}
+
+// query tile `tile` of tile_rows rows: its chain e and number t inside the chain, the chain's range (chain_range) and q0, the tile's
+// first row of the chain
+template <bool PACKED>
+struct chain_tile {
+    uint32_t e, t, len, rows;
+    uint64_t row0, q0;
+    __device__ __forceinline__ chain_tile(const uint64_t* __restrict__ tile_off, uint32_t n, uint32_t tiles_per_entry, const uint32_t* __restrict__ bound,
+                                          uint32_t L, uint64_t tile, uint32_t tile_rows) {
+        chain_of_tile<PACKED>(tile_off, n, tiles_per_entry, tile, &e, &t);
+        chain_range<PACKED>(bound, L, e, &row0, &len, &rows);
+        q0 = (uint64_t)t * tile_rows;
+    }
+};
+
+// The slots of a candidate pass, handed out by an LDS counter: the order inside a pass is free, because every result of a sweep is
+// an integer or a key with a total order.
+struct chain_slots {
+    uint32_t* count;
+    __device__ __forceinline__ uint32_t next() const { return atomicAdd(count, 1u); }
+};
+
+// One candidate pass of PASS chain rows from row *c0 of a chain of len rows: site(r, slots) for every row r of the pass, a row a lane
+// and step. A site claims at most one slot, so next() stays below PASS. -> the staged count; *c0 becomes the next pass' first row.
+// The caller sweeps the pass and closes it with a barrier before it stages the next.
+template <uint32_t PASS, class Site>
+__device__ __forceinline__ uint32_t chain_stage_rows(uint32_t* s_count, uint32_t len, uint32_t* c0, Site site) {
+    const uint32_t c1 = len - *c0 < PASS ? len : *c0 + PASS;
+    if (threadIdx.x == 0) *s_count = 0;
+    __syncthreads();
+    for (uint64_t r = (uint64_t)*c0 + threadIdx.x; r < c1; r += BLOCK) site(r, chain_slots{s_count});
+    __syncthreads();
+    *c0 = c1;
+    return *s_count;
+}
+
+// One candidate pass of at most PASS atoms from row *r0 of a chain of len rows of A slots: atom(r, a, slots) for every slot a of every
+// row r of the pass. The pass is staged in steps of the rows that hold at most STEP slots, STEP / BLOCK slots a lane, and is closed
+// when another step might not fit, so next() stays below PASS (backbone4 with every mask set fills a pass of 1536 exactly). The
+// functor keeps the identity of a candidate as (r, a): r * A + a in one word would wrap for chains above 2^32 / 37 rows.
+// -> the staged count; *r0 becomes the next pass' first row. The caller sweeps the pass and closes it with a barrier.
+template <uint32_t PASS, uint32_t STEP, class Atom>
+__device__ __forceinline__ uint32_t chain_stage_slots(uint32_t* s_count, uint32_t A, uint32_t len, uint32_t* r0, Atom atom) {
+    static_assert(STEP % BLOCK == 0 && PASS % STEP == 0, "chain_stage_slots");
+    const uint32_t tid = threadIdx.x;
+    const uint32_t step_rows = chain_div_a(STEP, A);                  // rows a staging step examines: 13, 36, 128 at two slots a lane
+    if (tid == 0) *s_count = 0;
+    __syncthreads();
+    for (;;) {                                                        // steps of step_rows rows until the pass is full or the chain ends
+        const uint32_t nr = len - *r0 < step_rows ? len - *r0 : step_rows;
+#pragma unroll
+        for (uint32_t h = 0; h < STEP / BLOCK; h++) {
+            const uint32_t x = tid + h * BLOCK;
+            if (x < nr * A) {
+                const uint32_t rr = chain_div_a(x, A);
+                atom(*r0 + rr, x - rr * A, chain_slots{s_count});
+            }
+        }
+        *r0 += nr;
+        __syncthreads();
+        const uint32_t staged = *s_count;
+        __syncthreads();                                              // (every lane has read the count before the next step adds to it)
+        if (*r0 >= len || staged + step_rows * A > PASS) break;
+    }
+    return *s_count;
+}
+
+// the slots of a query tile of tile_rows rows that begins at row q0 of its chain, strided over the block: slot(x, rr, a, q) with x the
+// slot's number in the tile, rr = x / A its row of the tile, a its slot of the row and q = q0 + rr its row of the chain
+template <class Slot>
+__device__ __forceinline__ void chain_tile_slots(uint32_t tile_rows, uint32_t A, uint64_t q0, Slot slot) {
+    for (uint32_t x = threadIdx.x; x < tile_rows * A; x += BLOCK) {
+        const uint32_t rr = chain_div_a(x, A);
+        slot(x, rr, x - rr * A, q0 + rr);
+    }
 }
 
 }  // namespace fcz

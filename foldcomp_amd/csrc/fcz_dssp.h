@@ -22,7 +22,7 @@
 //                         HBOND_PASS = 480 rows is 30 KiB of LDS a block (and the counter's word), so five blocks (20 wavefronts,
 //                         five per SIMD) share a CU's 160 KiB, as for k_lddt -- 512 rows would be 32 KiB and that word, and the
 //                         fifth block would no longer fit. Five wavefronts per SIMD may hold 96 VGPRs each: the padded form
-//                         compiles to 82 and gets them, the packed form to 105 (the tile search's 64-bit state stays live) and
+//                         compiles to 74 and gets them, the packed form to 100 (the tile search's 64-bit state stays live) and
 //                         runs four (`make asm` prints both). 1024 rows would be 64 KiB and two blocks. Chains of up to 480
 //                         residues, most there are, take one pass; a longer chain pays three barriers per further pass.
 //                         No L x L array is written: HBM sees the 48 bytes of a backbone row and 32 bytes of tables.
@@ -35,8 +35,9 @@
 //                         acc[r + 1] + 1; a ladder has two bridges when the bridge one step along it exists; a bulge link is
 //                         searched in the 5 x 5 window of gaps at a ladder's end. O(rows), not hot, no atomics, no scratch but the
 //                         flags. dssp_label is integer code and compiles for the host as well.
-//   k_dssp_fill           packed form only, in front of the sweeps: -1 / 0 (tables) or 0 / 0 (labels) into every row that no chain is
-//                         seen to cover (chain_covers: a covered row it misses is rewritten by the sweep behind it).
+//   k_chain_fill<hbond_fill_args>, k_chain_fill<label_fill_args>   (fcz_chains.h) packed form only, in front of the sweeps: -1 / 0
+//                         (tables) or 0 / 0 (labels) into every row that no chain is seen to cover (chain_covers: a covered row it
+//                         misses is rewritten by the sweep behind it).
 //
 // Every index that scales with rows * A is 64-bit. A chain's range is clamped to the R rows that exist and a range that runs
 // backwards is empty (chain_range), so no read leaves the inputs whatever row_off holds; an index read from an acceptor table is only
@@ -82,11 +83,7 @@ __device__ __forceinline__ bool dssp_backbone(const dssp_args& g, uint64_t r, bb
     return ok;
 }
 
-__device__ __forceinline__ float dssp_d2(const float* a, const float* b) {
-    const float dx = __fsub_rn(a[0], b[0]), dy = __fsub_rn(a[1], b[1]), dz = __fsub_rn(a[2], b[2]);
-    return __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
-}
-__device__ __forceinline__ float dssp_d(const float* a, const float* b) { return f32_sqrt_rn(dssp_d2(a, b)); }
+__device__ __forceinline__ float dssp_d(const float* a, const float* b) { return f32_sqrt_rn(chain_d2(a, b)); }
 
 // the amide hydrogen of row q (> 0 rows into its chain, a backbone row b) -> true when it has one
 __device__ __forceinline__ bool dssp_amide_h(const dssp_args& g, uint64_t row0, uint64_t q, const bb_row& b, float* h) {
@@ -123,19 +120,16 @@ __device__ __forceinline__ void hb_decode(uint64_t key, uint32_t base, int32_t* 
     *e = none ? 0.0f : __uint_as_float(~(uint32_t)(key >> 32));
 }
 
-// what: 1 the four tables, 2 the labels
-__global__ __launch_bounds__(BLOCK) void k_dssp_fill(dssp_args g, int what) {
-    for (uint64_t r = (uint64_t)blockIdx.x * BLOCK + threadIdx.x; r < g.L; r += (uint64_t)gridDim.x * BLOCK) {
-        if (chain_covers(g.bound, g.n, r)) continue;
-        if (what == 1) {
-            for (uint32_t s = 0; s < 2; s++) {
-                g.acc_index[r * 2 + s] = -1; g.acc_energy[r * 2 + s] = 0.0f; g.don_index[r * 2 + s] = -1; g.don_energy[r * 2 + s] = 0.0f;
-            }
-        } else {
-            g.ss[r] = 0; g.ss_mask[r] = 0;
-        }
+// what a fill in front of k_hbond (the four tables) and in front of k_dssp_flags (the labels) works on: k_chain_fill picks the empty
+// row by the type
+struct hbond_fill_args : dssp_args {};
+struct label_fill_args : dssp_args {};
+__device__ __forceinline__ void chain_empty_row(const hbond_fill_args& g, uint64_t r) {
+    for (uint32_t s = 0; s < 2; s++) {
+        g.acc_index[r * 2 + s] = -1; g.acc_energy[r * 2 + s] = 0.0f; g.don_index[r * 2 + s] = -1; g.don_energy[r * 2 + s] = 0.0f;
     }
 }
+__device__ __forceinline__ void chain_empty_row(const label_fill_args& g, uint64_t r) { g.ss[r] = 0; g.ss_mask[r] = 0; }
 
 template <bool PACKED>
 __global__ __launch_bounds__(BLOCK) void k_hbond(dssp_args g, const uint64_t* __restrict__ tile_off, uint32_t tiles_per_entry, uint64_t n_tiles_padded) {
@@ -143,41 +137,33 @@ __global__ __launch_bounds__(BLOCK) void k_hbond(dssp_args g, const uint64_t* __
     __shared__ uint32_t s_j[HBOND_PASS];
     __shared__ uint32_t s_count;
     const uint32_t tid = threadIdx.x;
-    const uint64_t n_tiles = PACKED ? tile_off[g.n] : n_tiles_padded;
+    const uint64_t n_tiles = chain_tile_count<PACKED>(tile_off, g.n, n_tiles_padded);
     for (uint64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-        uint32_t e, t;
-        chain_of_tile<PACKED>(tile_off, g.n, tiles_per_entry, tile, &e, &t);
-        uint64_t row0; uint32_t len, rows;
-        chain_range<PACKED>(g.bound, g.L, e, &row0, &len, &rows);
-        const uint64_t q = (uint64_t)t * CHAIN_TILE + tid;            // this lane's row of the chain
+        const chain_tile<PACKED> ct(tile_off, g.n, tiles_per_entry, g.bound, g.L, tile, CHAIN_TILE);
+        const uint64_t q = ct.q0 + tid;                               // this lane's row of the chain
         bb_row me{};
         float my_h[3] = {0.0f, 0.0f, 0.0f};
-        const bool active = q < len && dssp_backbone(g, row0 + q, &me);
-        const bool has_h = active && dssp_amide_h(g, row0, q, me, my_h);
+        const bool active = q < ct.len && dssp_backbone(g, ct.row0 + q, &me);
+        const bool has_h = active && dssp_amide_h(g, ct.row0, q, me, my_h);
         const uint32_t qj = (uint32_t)q;
         uint64_t acc0 = HB_NONE, acc1 = HB_NONE, don0 = HB_NONE, don1 = HB_NONE;
-        for (uint32_t c0 = 0; c0 < len;) {
-            const uint32_t c1 = len - c0 < HBOND_PASS ? len : c0 + HBOND_PASS;
-            if (tid == 0) s_count = 0;
-            __syncthreads();
-            for (uint64_t r = (uint64_t)c0 + tid; r < c1; r += BLOCK) {
+        for (uint32_t c0 = 0; c0 < ct.len;) {
+            const uint32_t count = chain_stage_rows<HBOND_PASS>(&s_count, ct.len, &c0, [&](uint64_t r, chain_slots slots) __attribute__((always_inline)) {
                 bb_row b;
-                if (dssp_backbone(g, row0 + r, &b)) {
+                if (dssp_backbone(g, ct.row0 + r, &b)) {
                     float h[3] = {0.0f, 0.0f, 0.0f};
-                    const bool hh = dssp_amide_h(g, row0, r, b, h);
-                    const uint32_t i = atomicAdd(&s_count, 1u);       // (< HBOND_PASS: one slot per row of the pass)
+                    const bool hh = dssp_amide_h(g, ct.row0, r, b, h);
+                    const uint32_t i = slots.next();
 #pragma unroll
                     for (int k = 0; k < 3; k++) { s_n[k][i] = b.n[k]; s_h[k][i] = h[k]; s_ca[k][i] = b.ca[k]; s_c[k][i] = b.c[k]; s_o[k][i] = b.o[k]; }
                     s_j[i] = (uint32_t)r | (hh ? HB_HAS_H : 0u);
                 }
-            }
-            __syncthreads();
-            const uint32_t count = s_count;
+            });
             if (__any(active)) {
                 for (uint32_t c = 0; c < count; c++) {
                     const uint32_t jw = s_j[c], j = jw & ~HB_HAS_H;
                     const float cca[3] = {s_ca[0][c], s_ca[1][c], s_ca[2][c]};
-                    const bool near = active && j != qj && dssp_d2(cca, me.ca) < 81.0f;
+                    const bool near = active && j != qj && chain_d2(cca, me.ca) < 81.0f;
                     if (__any(near)) {
                         const bool as_donor = near && has_h && j + 1u != qj;              // the lane's N-H onto the candidate's C=O (j != i - 1)
                         const bool as_acceptor = near && (jw & HB_HAS_H) != 0u && qj + 1u != j;   // the candidate's N-H onto the lane's C=O
@@ -196,11 +182,10 @@ __global__ __launch_bounds__(BLOCK) void k_hbond(dssp_args g, const uint64_t* __
                 }
             }
             __syncthreads();                                          // the next pass (or tile) rewrites the staging
-            c0 = c1;
         }
-        if (q < rows) {
-            const uint32_t base = PACKED ? (uint32_t)row0 : 0u;
-            const uint64_t o = (row0 + q) * 2u;
+        if (q < ct.rows) {
+            const uint32_t base = PACKED ? (uint32_t)ct.row0 : 0u;
+            const uint64_t o = (ct.row0 + q) * 2u;
             hb_decode(acc0, base, &g.acc_index[o], &g.acc_energy[o]);
             hb_decode(acc1, base, &g.acc_index[o + 1], &g.acc_energy[o + 1]);
             hb_decode(don0, base, &g.don_index[o], &g.don_energy[o]);
@@ -211,22 +196,19 @@ __global__ __launch_bounds__(BLOCK) void k_hbond(dssp_args g, const uint64_t* __
 
 template <bool PACKED>
 __global__ __launch_bounds__(BLOCK) void k_dssp_flags(dssp_args g, const uint64_t* __restrict__ tile_off, uint32_t tiles_per_entry, uint64_t n_tiles_padded) {
-    const uint64_t n_tiles = PACKED ? tile_off[g.n] : n_tiles_padded;
+    const uint64_t n_tiles = chain_tile_count<PACKED>(tile_off, g.n, n_tiles_padded);
     for (uint64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-        uint32_t e, t;
-        chain_of_tile<PACKED>(tile_off, g.n, tiles_per_entry, tile, &e, &t);
-        uint64_t row0; uint32_t len, rows;
-        chain_range<PACKED>(g.bound, g.L, e, &row0, &len, &rows);
-        const uint64_t q = (uint64_t)t * CHAIN_TILE + threadIdx.x;
-        if (q >= rows) continue;
+        const chain_tile<PACKED> ct(tile_off, g.n, tiles_per_entry, g.bound, g.L, tile, CHAIN_TILE);
+        const uint64_t q = ct.q0 + threadIdx.x;
+        if (q >= ct.rows) continue;
         uint8_t f = 0;
         bb_row b, o;
-        if (q < len && dssp_backbone(g, row0 + q, &b)) {
+        if (q < ct.len && dssp_backbone(g, ct.row0 + q, &b)) {
             f = DSSP_BB;
-            if (q + 1 < len && dssp_backbone(g, row0 + q + 1, &o) && !(dssp_d(b.c, o.n) > 2.5f)) f |= DSSP_LINK;
-            if (q >= 2 && q + 2 < len && dssp_backbone(g, row0 + q - 2, &o)) {
+            if (q + 1 < ct.len && dssp_backbone(g, ct.row0 + q + 1, &o) && !(dssp_d(b.c, o.n) > 2.5f)) f |= DSSP_LINK;
+            if (q >= 2 && q + 2 < ct.len && dssp_backbone(g, ct.row0 + q - 2, &o)) {
                 const float u[3] = {__fsub_rn(b.ca[0], o.ca[0]), __fsub_rn(b.ca[1], o.ca[1]), __fsub_rn(b.ca[2], o.ca[2])};
-                if (dssp_backbone(g, row0 + q + 2, &o)) {
+                if (dssp_backbone(g, ct.row0 + q + 2, &o)) {
                     const float v[3] = {__fsub_rn(o.ca[0], b.ca[0]), __fsub_rn(o.ca[1], b.ca[1]), __fsub_rn(o.ca[2], b.ca[2])};
                     const float dot = __fadd_rn(__fadd_rn(__fmul_rn(u[0], v[0]), __fmul_rn(u[1], v[1])), __fmul_rn(u[2], v[2]));
                     const float nu = f32_sqrt_rn(__fadd_rn(__fadd_rn(__fmul_rn(u[0], u[0]), __fmul_rn(u[1], u[1])), __fmul_rn(u[2], u[2])));
@@ -235,8 +217,8 @@ __global__ __launch_bounds__(BLOCK) void k_dssp_flags(dssp_args g, const uint64_
                 }
             }
         }
-        g.flags[row0 + q] = f;
-        g.ss_mask[row0 + q] = f & DSSP_BB;
+        g.flags[ct.row0 + q] = f;
+        g.ss_mask[ct.row0 + q] = f & DSSP_BB;
     }
 }
 
@@ -348,16 +330,13 @@ __host__ __device__ inline uint8_t dssp_label(const dssp_view& v, int64_t r) {
 
 template <bool PACKED>
 __global__ __launch_bounds__(BLOCK) void k_dssp_labels(dssp_args g, const uint64_t* __restrict__ tile_off, uint32_t tiles_per_entry, uint64_t n_tiles_padded) {
-    const uint64_t n_tiles = PACKED ? tile_off[g.n] : n_tiles_padded;
+    const uint64_t n_tiles = chain_tile_count<PACKED>(tile_off, g.n, n_tiles_padded);
     for (uint64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-        uint32_t e, t;
-        chain_of_tile<PACKED>(tile_off, g.n, tiles_per_entry, tile, &e, &t);
-        uint64_t row0; uint32_t len, rows;
-        chain_range<PACKED>(g.bound, g.L, e, &row0, &len, &rows);
-        const uint64_t q = (uint64_t)t * CHAIN_TILE + threadIdx.x;
-        if (q >= rows) continue;
-        const dssp_view v{g.flags + row0, g.acc_index + row0 * 2u, g.acc_energy + row0 * 2u, PACKED ? (int64_t)row0 : 0, (int64_t)len};
-        g.ss[row0 + q] = q < len ? dssp_label(v, (int64_t)q) : (uint8_t)SS_LOOP;
+        const chain_tile<PACKED> ct(tile_off, g.n, tiles_per_entry, g.bound, g.L, tile, CHAIN_TILE);
+        const uint64_t q = ct.q0 + threadIdx.x;
+        if (q >= ct.rows) continue;
+        const dssp_view v{g.flags + ct.row0, g.acc_index + ct.row0 * 2u, g.acc_energy + ct.row0 * 2u, PACKED ? (int64_t)ct.row0 : 0, (int64_t)ct.len};
+        g.ss[ct.row0 + q] = q < ct.len ? dssp_label(v, (int64_t)q) : (uint8_t)SS_LOOP;
     }
 }
 

@@ -21,8 +21,9 @@
 //                         -1 / 0 where it is no site. Packed form: the chains' tile counts are scanned on the device
 //                         (k_chain_tiles, device_scan) and a tile finds its chain by binary search (fcz_chains.h, shared
 //                         with every other per-chain sweep).
-//   k_knn_fill            packed form only, in front of k_knn: -1 / 0 into every row that no chain is seen to cover (a search of
-//                         row_off that a hostile row_off may mislead: a covered row it misses is rewritten by k_knn behind it).
+//   k_chain_fill<knn_args>   (fcz_chains.h) packed form only, in front of k_knn: -1 / 0 (chain_empty_row) into every row that no
+//                         chain is seen to cover (a search of row_off that a hostile row_off may mislead: a covered row it misses is
+//                         rewritten by k_knn behind it).
 //
 // Every index that scales with rows * k or rows * A is 64-bit. A chain's range is clamped to the R rows that exist and a range
 // that runs backwards is empty, so no read leaves pos / mask whatever row_off holds.
@@ -47,19 +48,8 @@ struct knn_args {
     int32_t* index; float* dist;
 };
 
-// chain e: its first row in the arrays, the rows that may hold a site, the rows k_knn writes
-template <bool PACKED>
-__device__ __forceinline__ void knn_chain(const knn_args& g, uint32_t e, uint64_t* row0, uint32_t* len, uint32_t* rows) {
-    chain_range<PACKED>(g.bound, g.L, e, row0, len, rows);
-}
-
 // the slot's coordinates of array row r -> true when the row is a site (mask set, three finite values)
-__device__ __forceinline__ bool knn_site(const knn_args& g, uint64_t r, float* x, float* y, float* z) {
-    if (g.mask[r * g.A + g.slot] == 0) return false;
-    const float* p = g.pos + (r * g.A + g.slot) * 3u;
-    *x = p[0]; *y = p[1]; *z = p[2];
-    return isfinite(*x) && isfinite(*y) && isfinite(*z);
-}
+__device__ __forceinline__ bool knn_site(const knn_args& g, uint64_t r, float* c) { return chain_site(g.pos, g.mask, r * g.A + g.slot, c); }
 
 __device__ __forceinline__ void knn_decode(uint64_t key, uint32_t base, int32_t* idx, float* d) {
     const bool none = key == KNN_NONE;
@@ -67,11 +57,9 @@ __device__ __forceinline__ void knn_decode(uint64_t key, uint32_t base, int32_t*
     *d = none ? 0.0f : f32_sqrt_rn(__uint_as_float((uint32_t)(key >> 32)));
 }
 
-__global__ __launch_bounds__(BLOCK) void k_knn_fill(knn_args g) {
-    for (uint64_t r = (uint64_t)blockIdx.x * BLOCK + threadIdx.x; r < g.L; r += (uint64_t)gridDim.x * BLOCK) {
-        if (chain_covers(g.bound, g.n, r)) continue;
-        for (uint32_t s = 0; s < g.k; s++) { g.index[r * g.k + s] = -1; g.dist[r * g.k + s] = 0.0f; }
-    }
+// row r of the arrays holds nothing
+__device__ __forceinline__ void chain_empty_row(const knn_args& g, uint64_t r) {
+    for (uint32_t s = 0; s < g.k; s++) { g.index[r * g.k + s] = -1; g.dist[r * g.k + s] = 0.0f; }
 }
 
 template <int KCAP, bool PACKED>
@@ -80,38 +68,29 @@ __global__ __launch_bounds__(BLOCK) void k_knn(knn_args g, const uint64_t* __res
     __shared__ uint32_t s_j[KNN_PASS];
     __shared__ uint32_t s_count;
     const uint32_t tid = threadIdx.x;
-    const uint64_t n_tiles = PACKED ? tile_off[g.n] : n_tiles_padded;
+    const uint64_t n_tiles = chain_tile_count<PACKED>(tile_off, g.n, n_tiles_padded);
     const bool wide = (g.k & 3u) == 0 && (((uintptr_t)g.index | (uintptr_t)g.dist) & 15u) == 0;   // 16-byte stores of four columns
     for (uint64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-        uint32_t e, t;
-        chain_of_tile<PACKED>(tile_off, g.n, tiles_per_entry, tile, &e, &t);
-        uint64_t row0; uint32_t len, rows;
-        knn_chain<PACKED>(g, e, &row0, &len, &rows);
-        const uint64_t q = (uint64_t)t * KNN_TILE + tid;              // this lane's row of the chain
-        float qx = 0.0f, qy = 0.0f, qz = 0.0f;
-        const bool query = q < len && knn_site(g, row0 + q, &qx, &qy, &qz);
+        const chain_tile<PACKED> ct(tile_off, g.n, tiles_per_entry, g.bound, g.L, tile, KNN_TILE);
+        const uint64_t q = ct.q0 + tid;                               // this lane's row of the chain
+        float qc[3] = {0.0f, 0.0f, 0.0f};
+        const bool query = q < ct.len && knn_site(g, ct.row0 + q, qc);
         const uint32_t qj = (uint32_t)q;
         uint64_t list[KCAP];
 #pragma unroll
         for (int s = 0; s < KCAP; s++) list[s] = KNN_NONE;
-        for (uint32_t c0 = 0; c0 < len;) {
-            const uint32_t c1 = len - c0 < KNN_PASS ? len : c0 + KNN_PASS;
-            if (tid == 0) s_count = 0;
-            __syncthreads();
-            for (uint64_t r = (uint64_t)c0 + tid; r < c1; r += BLOCK) {
-                float x, y, z;
-                if (knn_site(g, row0 + r, &x, &y, &z)) {
-                    const uint32_t i = atomicAdd(&s_count, 1u);       // (< KNN_PASS: one slot per row of the pass)
-                    s_x[i] = x; s_y[i] = y; s_z[i] = z; s_j[i] = (uint32_t)r;
+        for (uint32_t c0 = 0; c0 < ct.len;) {
+            const uint32_t count = chain_stage_rows<KNN_PASS>(&s_count, ct.len, &c0, [&](uint64_t r, chain_slots slots) __attribute__((always_inline)) {
+                float c[3];
+                if (knn_site(g, ct.row0 + r, c)) {
+                    const uint32_t i = slots.next();
+                    s_x[i] = c[0]; s_y[i] = c[1]; s_z[i] = c[2]; s_j[i] = (uint32_t)r;
                 }
-            }
-            __syncthreads();
-            const uint32_t count = s_count;
+            });
             if (__any(query)) {
                 for (uint32_t c = 0; c < count; c++) {
                     const uint32_t j = s_j[c];
-                    const float dx = __fsub_rn(s_x[c], qx), dy = __fsub_rn(s_y[c], qy), dz = __fsub_rn(s_z[c], qz);
-                    const float d2 = __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
+                    const float d2 = chain_d2(s_x[c], s_y[c], s_z[c], qc[0], qc[1], qc[2]);
                     uint64_t key = ((uint64_t)__float_as_uint(d2) << 32) | j;
                     if (!query || j == qj) key = KNN_NONE;
                     if (__any(key < list[KCAP - 1])) {
@@ -126,11 +105,10 @@ __global__ __launch_bounds__(BLOCK) void k_knn(knn_args g, const uint64_t* __res
                 }
             }
             __syncthreads();                                          // the next pass (or tile) rewrites the staging
-            c0 = c1;
         }
-        if (q < rows) {
-            const uint32_t base = PACKED ? (uint32_t)row0 : 0u;
-            const uint64_t o = (row0 + q) * (uint64_t)g.k;
+        if (q < ct.rows) {
+            const uint32_t base = PACKED ? (uint32_t)ct.row0 : 0u;
+            const uint64_t o = (ct.row0 + q) * (uint64_t)g.k;
             if (wide) {
 #pragma unroll
                 for (int s = 0; s < KCAP; s += 4)

@@ -25,8 +25,8 @@
 //                         there are, still take one pass; a longer chain pays three barriers per further pass.
 //                         The L x L matrices are never written: HBM sees the slot's 24 bytes per row and 12 bytes of output.
 //                         Padded form: every row of the entry is written, 0 / 0 / 0 where it is no site.
-//   k_lddt_fill           packed form only, in front of k_lddt: 0 / 0 / 0 into every row that no chain is seen to cover
-//                         (chain_covers: a covered row it misses is rewritten by k_lddt behind it).
+//   k_chain_fill<lddt_args>   (fcz_chains.h) packed form only, in front of k_lddt: 0 / 0 / 0 (chain_empty_row) into every row that
+//                         no chain is seen to cover (chain_covers: a covered row it misses is rewritten by k_lddt behind it).
 //
 // Every index that scales with rows * A is 64-bit. A chain's range is clamped to the R rows that exist and a range that runs
 // backwards is empty (chain_range), so no read leaves the inputs whatever row_off holds. hits <= 4 * (rows of a chain - 1) fits
@@ -60,22 +60,19 @@ inline float lddt_c2(float cutoff) {
 }
 
 // the slot's coordinates of array row r in both tensors -> true when the row is a site (both masks set, six finite values)
-__device__ __forceinline__ bool lddt_site(const lddt_args& g, uint64_t r, float* tx, float* ty, float* tz, float* px, float* py, float* pz) {
-    const uint64_t o = r * g.A + g.slot;
-    if (g.mask_true[o] == 0) return false;
-    if (g.mask_pred && g.mask_pred[o] == 0) return false;
-    const float* t = g.pos_true + o * 3u;
-    const float* p = g.pos_pred + o * 3u;
-    *tx = t[0]; *ty = t[1]; *tz = t[2]; *px = p[0]; *py = p[1]; *pz = p[2];
-    return isfinite(*tx) && isfinite(*ty) && isfinite(*tz) && isfinite(*px) && isfinite(*py) && isfinite(*pz);
+__device__ __forceinline__ bool lddt_site(const lddt_args& g, uint64_t r, float* t, float* p) {
+    return chain_site2(g.pos_true, g.mask_true, r * g.A + g.slot, g.pos_pred, g.mask_pred, r * g.A + g.slot, t, p);
 }
 
-__global__ __launch_bounds__(BLOCK) void k_lddt_fill(lddt_args g) {
-    for (uint64_t r = (uint64_t)blockIdx.x * BLOCK + threadIdx.x; r < g.L; r += (uint64_t)gridDim.x * BLOCK) {
-        if (chain_covers(g.bound, g.n, r)) continue;
-        g.score[r] = 0.0f; g.pairs[r] = 0; g.hits[r] = 0;
-    }
+// the hits of a pair: the thresholds of g (lddt_args or lddta_args) that |d_true - d_pred| lies under, from d2_true and d_pred
+template <class Args>
+__device__ __forceinline__ uint32_t lddt_hits(const Args& g, float d2, float sp) {
+    const float diff = fabsf(__fsub_rn(f32_sqrt_rn(d2), sp));                 // +inf or NaN when d_pred is +inf: under no threshold
+    return (diff < g.t0 ? 1u : 0u) + (diff < g.t1 ? 1u : 0u) + (diff < g.t2 ? 1u : 0u) + (diff < g.t3 ? 1u : 0u);
 }
+
+// row r of the arrays holds nothing
+__device__ __forceinline__ void chain_empty_row(const lddt_args& g, uint64_t r) { g.score[r] = 0.0f; g.pairs[r] = 0; g.hits[r] = 0; }
 
 template <bool PACKED>
 __global__ __launch_bounds__(BLOCK) void k_lddt(lddt_args g, const uint64_t* __restrict__ tile_off, uint32_t tiles_per_entry, uint64_t n_tiles_padded) {
@@ -83,50 +80,37 @@ __global__ __launch_bounds__(BLOCK) void k_lddt(lddt_args g, const uint64_t* __r
     __shared__ uint32_t s_j[LDDT_PASS];
     __shared__ uint32_t s_count;
     const uint32_t tid = threadIdx.x;
-    const uint64_t n_tiles = PACKED ? tile_off[g.n] : n_tiles_padded;
+    const uint64_t n_tiles = chain_tile_count<PACKED>(tile_off, g.n, n_tiles_padded);
     for (uint64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-        uint32_t e, t;
-        chain_of_tile<PACKED>(tile_off, g.n, tiles_per_entry, tile, &e, &t);
-        uint64_t row0; uint32_t len, rows;
-        chain_range<PACKED>(g.bound, g.L, e, &row0, &len, &rows);
-        const uint64_t q = (uint64_t)t * CHAIN_TILE + tid;            // this lane's row of the chain
-        float qtx = 0.0f, qty = 0.0f, qtz = 0.0f, qpx = 0.0f, qpy = 0.0f, qpz = 0.0f;
-        const bool query = q < len && lddt_site(g, row0 + q, &qtx, &qty, &qtz, &qpx, &qpy, &qpz);
+        const chain_tile<PACKED> ct(tile_off, g.n, tiles_per_entry, g.bound, g.L, tile, CHAIN_TILE);
+        const uint64_t q = ct.q0 + tid;                               // this lane's row of the chain
+        float qt[3] = {0.0f, 0.0f, 0.0f}, qp[3] = {0.0f, 0.0f, 0.0f};
+        const bool query = q < ct.len && lddt_site(g, ct.row0 + q, qt, qp);
         const uint32_t qj = (uint32_t)q;
         uint32_t pairs = 0, hits = 0;
-        for (uint32_t c0 = 0; c0 < len;) {
-            const uint32_t c1 = len - c0 < LDDT_PASS ? len : c0 + LDDT_PASS;
-            if (tid == 0) s_count = 0;
-            __syncthreads();
-            for (uint64_t r = (uint64_t)c0 + tid; r < c1; r += BLOCK) {
-                float tx, ty, tz, px, py, pz;
-                if (lddt_site(g, row0 + r, &tx, &ty, &tz, &px, &py, &pz)) {
-                    const uint32_t i = atomicAdd(&s_count, 1u);       // (< LDDT_PASS: one slot per row of the pass)
-                    s_tx[i] = tx; s_ty[i] = ty; s_tz[i] = tz; s_px[i] = px; s_py[i] = py; s_pz[i] = pz; s_j[i] = (uint32_t)r;
+        for (uint32_t c0 = 0; c0 < ct.len;) {
+            const uint32_t count = chain_stage_rows<LDDT_PASS>(&s_count, ct.len, &c0, [&](uint64_t r, chain_slots slots) __attribute__((always_inline)) {
+                float t[3], p[3];
+                if (lddt_site(g, ct.row0 + r, t, p)) {
+                    const uint32_t i = slots.next();
+                    s_tx[i] = t[0]; s_ty[i] = t[1]; s_tz[i] = t[2]; s_px[i] = p[0]; s_py[i] = p[1]; s_pz[i] = p[2]; s_j[i] = (uint32_t)r;
                 }
-            }
-            __syncthreads();
-            const uint32_t count = s_count;
+            });
             if (__any(query)) {
                 for (uint32_t c = 0; c < count; c++) {
-                    const float dx = __fsub_rn(s_tx[c], qtx), dy = __fsub_rn(s_ty[c], qty), dz = __fsub_rn(s_tz[c], qtz);
-                    const float d2 = __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
+                    const float d2 = chain_d2(s_tx[c], s_ty[c], s_tz[c], qt[0], qt[1], qt[2]);
                     const bool pair = query && s_j[c] != qj && d2 < g.c2;   // (a d2 of +inf is no pair: c2 <= +inf)
                     if (__any(pair)) {
-                        const float ex = __fsub_rn(s_px[c], qpx), ey = __fsub_rn(s_py[c], qpy), ez = __fsub_rn(s_pz[c], qpz);
-                        const float p2 = __fadd_rn(__fadd_rn(__fmul_rn(ex, ex), __fmul_rn(ey, ey)), __fmul_rn(ez, ez));
-                        const float diff = fabsf(__fsub_rn(f32_sqrt_rn(d2), f32_sqrt_rn(p2)));   // +inf when d_pred is: under no threshold
-                        const uint32_t h = (diff < g.t0 ? 1u : 0u) + (diff < g.t1 ? 1u : 0u) + (diff < g.t2 ? 1u : 0u) + (diff < g.t3 ? 1u : 0u);
+                        const uint32_t h = lddt_hits(g, d2, f32_sqrt_rn(chain_d2(s_px[c], s_py[c], s_pz[c], qp[0], qp[1], qp[2])));
                         pairs += pair ? 1u : 0u;
                         hits += pair ? h : 0u;
                     }
                 }
             }
             __syncthreads();                                          // the next pass (or tile) rewrites the staging
-            c0 = c1;
         }
-        if (q < rows) {
-            const uint64_t o = row0 + q;
+        if (q < ct.rows) {
+            const uint64_t o = ct.row0 + q;
             g.score[o] = pairs ? f32_div_rn((float)hits, (float)(4u * pairs)) : 0.0f;
             g.pairs[o] = (int32_t)pairs; g.hits[o] = (int32_t)hits;
         }

@@ -29,10 +29,10 @@
 //       the truth (decide: under both namings), the prediction, and its two (decide: four) counters. Keeping only the slot numbers in
 //       LDS is what leaves room for the candidates.
 //       The chain's candidates (score: its atoms under the renamed truth; decide: its anchors) are staged COMPACTED in passes of at most
-//       LDDTA_PASS = 1536 as SoA true x / y / z, pred x / y / z and the chain row, 28 bytes each, in steps of two slots a lane as
-//       k_violations stages them (slots are handed out by an LDS counter: the order inside a pass is free, see above). Every lane walks
-//       the pass; all 64 lanes of a wavefront read the SAME candidate (broadcast reads, no bank conflict), compute the true d2 (decide:
-//       two of them) and compare with c2. Only when some lane of the wavefront has a pair (__any) does the wavefront pay for the pred
+//       LDDTA_PASS = 1536 as SoA true x / y / z, pred x / y / z and the chain row, 28 bytes each, in steps of two slots a lane
+//       (chain_stage_slots, fcz_chains.h, as k_violations stages them; slots are handed out by an LDS counter: the order inside a
+//       pass is free, see above). Every lane walks the pass; all 64 lanes of a wavefront read the SAME candidate (broadcast reads,
+//       no bank conflict), compute the true d2 (decide: two of them) and compare with c2. Only when some lane of the wavefront has a pair (__any) does the wavefront pay for the pred
 //       d2, the roots and the four compares, as k_lddt does. A wavefront without a query atom in the round skips the sweep
 //       (wave-uniform) and keeps the barriers; a tile without a query atom (decide: most tiles of a batch without aatype, all of them)
 //       stages nothing.
@@ -41,13 +41,13 @@
 //       a lane per row writes swapped, or score / pairs / hits.
 //       LDS: 1536 * 28 = 43008 bytes of candidates, 64 * 37 * 2 = 4736 of query slots, 64 * 16 = 1024 of per-row counters, 256 of row
 //       flags, 8 of counters: 49032 bytes a block, so THREE blocks (12 wavefronts, three per SIMD) share a CU's 160 KiB and a
-//       wavefront may hold 170 VGPRs. `make asm` prints the VGPRs: score padded 58, packed 56; decide padded 62, packed 60; no scratch
+//       wavefront may hold 170 VGPRs. `make asm` prints the VGPRs: score padded 54, packed 54; decide padded 58, packed 56; no scratch
 //       (LDS is the limit; a pass of 1024 candidates would buy the fourth block and cost a 350-residue chain of 2730 atoms a third pass).
 //       NOBODY HAS MEASURED tile rows or pass size: tools/lddt_atoms_rate.py reports the rate of the constants as they stand.
 //       HBM sees the inputs, one byte and twelve bytes a row, and eight bytes a slot when the per-atom counts are wanted: no rows x rows
 //       and no atoms x atoms array.
-//   k_lddt_atoms_fill   packed form only, in front of the sweeps: 0 into every row that no chain is seen to cover (chain_covers: a
-//                       covered row it misses is rewritten by the sweeps behind it), as k_lddt_fill does.
+//   k_chain_fill<lddta_args>   (fcz_chains.h) packed form only, in front of the sweeps: 0 (chain_empty_row) into every row that no
+//                       chain is seen to cover (chain_covers: a covered row it misses is rewritten by the sweeps behind it).
 //
 // Every index that scales with rows * A is 64-bit. A chain's range is clamped to the R rows that exist and a range that runs
 // backwards is empty (chain_range), so no read leaves the inputs whatever row_off holds; aatype is clamped to 20 before the table is
@@ -55,7 +55,6 @@
 // ABI refuses more than lddta_max_rows(A) rows per chain.
 #pragma once
 #include "fcz_lddt.h"
-#include "fcz_sasa.h"
 
 namespace fcz {
 
@@ -98,12 +97,7 @@ __device__ __forceinline__ uint32_t lddta_partner(const lddta_args& g, const ldd
 
 // slot `at` of the truth and slot a of the prediction of array row r -> true when the slot is present (both masks set, six finite values)
 __device__ __forceinline__ bool lddta_present(const lddta_args& g, uint64_t r, uint32_t at, uint32_t a, float* t, float* p) {
-    if (g.mask_true[r * g.A + at] == 0) return false;
-    if (g.mask_pred && g.mask_pred[r * g.A + a] == 0) return false;
-    const float* ft = g.pos_true + (r * g.A + at) * 3u;
-    const float* fp = g.pos_pred + (r * g.A + a) * 3u;
-    t[0] = ft[0]; t[1] = ft[1]; t[2] = ft[2]; p[0] = fp[0]; p[1] = fp[1]; p[2] = fp[2];
-    return isfinite(t[0]) && isfinite(t[1]) && isfinite(t[2]) && isfinite(p[0]) && isfinite(p[1]) && isfinite(p[2]);
+    return chain_site2(g.pos_true, g.mask_true, r * g.A + at, g.pos_pred, g.mask_pred, r * g.A + a, t, p);
 }
 
 // A candidate of the sweep at slot a of array row r (a row inside its chain). DECIDE: an anchor, a present slot without a partner.
@@ -115,19 +109,12 @@ __device__ __forceinline__ bool lddta_candidate(const lddta_args& g, const lddta
     else return lddta_present(g, r, pa != a && g.swapped[r] ? pa : a, a, t, p);
 }
 
-__device__ __forceinline__ uint32_t lddta_hits(const lddta_args& g, float d2, float sp) {
-    const float diff = fabsf(__fsub_rn(f32_sqrt_rn(d2), sp));                 // +inf or NaN when d_pred is +inf: under no threshold
-    return (diff < g.t0 ? 1u : 0u) + (diff < g.t1 ? 1u : 0u) + (diff < g.t2 ? 1u : 0u) + (diff < g.t3 ? 1u : 0u);
-}
-
-__global__ __launch_bounds__(BLOCK) void k_lddt_atoms_fill(lddta_args g) {
-    for (uint64_t r = (uint64_t)blockIdx.x * BLOCK + threadIdx.x; r < g.L; r += (uint64_t)gridDim.x * BLOCK) {
-        if (chain_covers(g.bound, g.n, r)) continue;
-        g.score[r] = 0.0f; g.pairs[r] = 0; g.hits[r] = 0; g.swapped[r] = 0;
-        for (uint32_t a = 0; a < g.A; a++) {
-            if (g.atom_pairs) g.atom_pairs[r * g.A + a] = 0;
-            if (g.atom_hits) g.atom_hits[r * g.A + a] = 0;
-        }
+// row r of the arrays holds nothing
+__device__ __forceinline__ void chain_empty_row(const lddta_args& g, uint64_t r) {
+    g.score[r] = 0.0f; g.pairs[r] = 0; g.hits[r] = 0; g.swapped[r] = 0;
+    for (uint32_t a = 0; a < g.A; a++) {
+        if (g.atom_pairs) g.atom_pairs[r * g.A + a] = 0;
+        if (g.atom_hits) g.atom_hits[r * g.A + a] = 0;
     }
 }
 
@@ -143,52 +130,41 @@ __global__ __launch_bounds__(BLOCK) void k_lddt_atoms(lddta_args g, const lddta_
     const uint32_t tid = threadIdx.x;
     const uint32_t A = g.A;
     const uint32_t TR = lddta_tile_rows(A, DECIDE);
-    const uint32_t step_rows = LDDTA_STEP / A;                        // rows a staging step examines: 13, 36, 128
-    const uint64_t n_tiles = PACKED ? tile_off[g.n] : n_tiles_padded;
+    const uint64_t n_tiles = chain_tile_count<PACKED>(tile_off, g.n, n_tiles_padded);
     for (uint64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-        uint32_t e, t;
-        chain_of_tile<PACKED>(tile_off, g.n, tiles_per_entry, tile, &e, &t);
-        uint64_t row0; uint32_t len, rows;
-        chain_range<PACKED>(g.bound, g.L, e, &row0, &len, &rows);
-        const uint64_t tq0 = (uint64_t)t * TR;                        // the tile's first row of the chain
+        const chain_tile<PACKED> ct(tile_off, g.n, tiles_per_entry, g.bound, g.L, tile, TR);
         if (tid == 0) s_nq = 0;
         if (tid < TR) { r_cnt[tid][0] = 0; r_cnt[tid][1] = 0; r_cnt[tid][2] = 0; r_cnt[tid][3] = 0; r_flag[tid] = 0; }
         __syncthreads();
         // ---- the tile's query atoms, compacted ----
         if constexpr (DECIDE) {
             if (g.aatype) {                                           // (uniform; without aatype no row is ambiguous)
-                for (uint32_t x = tid; x < TR * A; x += BLOCK) {
-                    const uint32_t rr = sasa_div_a(x, A), a = x - rr * A;
-                    const uint64_t q = tq0 + rr;
-                    if (q < len && lddta_partner(g, tab, row0 + q, a) != a) {
+                chain_tile_slots(TR, A, ct.q0, [&](uint32_t, uint32_t rr, uint32_t a, uint64_t q) __attribute__((always_inline)) {
+                    if (q < ct.len && lddta_partner(g, tab, ct.row0 + q, a) != a) {
                         float c[3], p[3];
-                        atomicOr(&r_flag[rr], lddta_present(g, row0 + q, a, a, c, p) ? 1u : 3u);
+                        atomicOr(&r_flag[rr], lddta_present(g, ct.row0 + q, a, a, c, p) ? 1u : 3u);
                     }
-                }
+                });
             }
             __syncthreads();
             if (g.aatype) {
-                for (uint32_t x = tid; x < TR * A; x += BLOCK) {
-                    const uint32_t rr = sasa_div_a(x, A), a = x - rr * A;
-                    const uint64_t q = tq0 + rr;
-                    if (q < len && r_flag[rr] == 1u && lddta_partner(g, tab, row0 + q, a) != a) q_at[atomicAdd(&s_nq, 1u)] = (uint16_t)x;
-                }
+                chain_tile_slots(TR, A, ct.q0, [&](uint32_t x, uint32_t rr, uint32_t a, uint64_t q) __attribute__((always_inline)) {
+                    if (q < ct.len && r_flag[rr] == 1u && lddta_partner(g, tab, ct.row0 + q, a) != a) q_at[atomicAdd(&s_nq, 1u)] = (uint16_t)x;
+                });
             }
         } else {
             // every slot that holds no atom gets its two counts here, every atom at the end of its round
-            for (uint32_t x = tid; x < TR * A; x += BLOCK) {
-                const uint32_t rr = sasa_div_a(x, A), a = x - rr * A;
-                const uint64_t q = tq0 + rr;
-                if (q < rows) {
+            chain_tile_slots(TR, A, ct.q0, [&](uint32_t x, uint32_t, uint32_t a, uint64_t q) __attribute__((always_inline)) {
+                if (q < ct.rows) {
                     float c[3], p[3];
-                    if (q < len && lddta_candidate<false>(g, tab, row0 + q, a, c, p)) {
-                        q_at[atomicAdd(&s_nq, 1u)] = (uint16_t)x;     // (< LDDTA_TILE_SLOTS: one slot per iteration here)
+                    if (q < ct.len && lddta_candidate<false>(g, tab, ct.row0 + q, a, c, p)) {
+                        q_at[atomicAdd(&s_nq, 1u)] = (uint16_t)x;     // (< LDDTA_TILE_SLOTS: one slot per slot of the tile)
                     } else {
-                        if (g.atom_pairs) g.atom_pairs[(row0 + q) * A + a] = 0;
-                        if (g.atom_hits) g.atom_hits[(row0 + q) * A + a] = 0;
+                        if (g.atom_pairs) g.atom_pairs[(ct.row0 + q) * A + a] = 0;
+                        if (g.atom_hits) g.atom_hits[(ct.row0 + q) * A + a] = 0;
                     }
                 }
-            }
+            });
         }
         __syncthreads();
         const uint32_t nq = s_nq;
@@ -197,12 +173,12 @@ __global__ __launch_bounds__(BLOCK) void k_lddt_atoms(lddta_args g, const lddta_
             const bool have = qi < nq;
             const bool wave_has = base + (tid & ~63u) < nq;           // wave-uniform: some lane of this wavefront holds a query atom
             const uint32_t at = have ? q_at[qi] : 0u;
-            const uint32_t rr = sasa_div_a(at, A), a = at - rr * A;
-            const uint32_t ri = (uint32_t)tq0 + rr;                   // the query atom's row of the chain
+            const uint32_t rr = chain_div_a(at, A), a = at - rr * A;
+            const uint32_t ri = (uint32_t)ct.q0 + rr;                 // the query atom's row of the chain
             // the truth as it is named (score: as it is renamed), the truth under the other naming (decide only), the prediction
             float qt[3] = {0.0f, 0.0f, 0.0f}, qu[3] = {0.0f, 0.0f, 0.0f}, qp[3] = {0.0f, 0.0f, 0.0f};
             if (have) {
-                const uint64_t r = row0 + ri;
+                const uint64_t r = ct.row0 + ri;
                 const uint32_t pa = lddta_partner(g, tab, r, a);
                 if constexpr (DECIDE) {
                     (void)lddta_present(g, r, a, a, qt, qp);
@@ -214,50 +190,34 @@ __global__ __launch_bounds__(BLOCK) void k_lddt_atoms(lddta_args g, const lddta_
             }
             uint32_t n0 = 0, h0 = 0, n1 = 0, h1 = 0;                  // pairs and hits (decide: of naming 0, and of naming 1)
             // ---- the chain's candidates in passes ----
-            for (uint32_t r0 = 0; r0 < len;) {
-                if (tid == 0) s_count = 0;
-                __syncthreads();
-                for (;;) {                                            // steps of step_rows rows until the pass is full or the chain ends
-                    const uint32_t nr = len - r0 < step_rows ? len - r0 : step_rows;
-#pragma unroll
-                    for (uint32_t h = 0; h < 2; h++) {
-                        const uint32_t x = tid + h * BLOCK;
-                        if (x < nr * A) {
-                            const uint32_t sr = sasa_div_a(x, A), sa = x - sr * A;
-                            float c[3], p[3];
-                            if (lddta_candidate<DECIDE>(g, tab, row0 + r0 + sr, sa, c, p)) {
-                                const uint32_t i = atomicAdd(&s_count, 1u);   // (< LDDTA_PASS: the step was let in below)
-                                s_tx[i] = c[0]; s_ty[i] = c[1]; s_tz[i] = c[2]; s_px[i] = p[0]; s_py[i] = p[1]; s_pz[i] = p[2]; s_row[i] = r0 + sr;
-                            }
-                        }
+            for (uint32_t r0 = 0; r0 < ct.len;) {
+                const uint32_t count = chain_stage_slots<LDDTA_PASS, LDDTA_STEP>(&s_count, A, ct.len, &r0, [&](uint32_t r, uint32_t a, chain_slots slots) __attribute__((always_inline)) {
+                    float c[3], p[3];
+                    if (lddta_candidate<DECIDE>(g, tab, ct.row0 + r, a, c, p)) {
+                        const uint32_t i = slots.next();
+                        s_tx[i] = c[0]; s_ty[i] = c[1]; s_tz[i] = c[2]; s_px[i] = p[0]; s_py[i] = p[1]; s_pz[i] = p[2]; s_row[i] = r;
                     }
-                    r0 += nr;
-                    __syncthreads();
-                    const uint32_t staged = s_count;
-                    __syncthreads();                                  // (every lane has read the count before the next step adds to it)
-                    if (r0 >= len || staged + step_rows * A > LDDTA_PASS) break;
-                }
-                const uint32_t count = s_count;
+                });
                 // ---- the sweep: every lane meets every staged candidate, all lanes of a wavefront the same one at a time ----
                 if (wave_has) {
                     for (uint32_t j = 0; j < count; j++) {
                         const float cx = s_tx[j], cy = s_ty[j], cz = s_tz[j];
                         const bool other = have && s_row[j] != ri;
-                        const float d0 = sasa_d2(cx, cy, cz, qt[0], qt[1], qt[2]);
+                        const float d0 = chain_d2(cx, cy, cz, qt[0], qt[1], qt[2]);
                         const bool pair0 = other && d0 < g.c2;        // (a d2 of +inf or NaN is no pair: c2 <= +inf)
                         if constexpr (DECIDE) {
-                            const float d1 = sasa_d2(cx, cy, cz, qu[0], qu[1], qu[2]);
+                            const float d1 = chain_d2(cx, cy, cz, qu[0], qu[1], qu[2]);
                             const bool pair1 = other && d1 < g.c2;
                             if (__any(pair0 || pair1)) {
-                                const float sp = f32_sqrt_rn(sasa_d2(s_px[j], s_py[j], s_pz[j], qp[0], qp[1], qp[2]));
-                                const uint32_t k0 = lddta_hits(g, d0, sp), k1 = lddta_hits(g, d1, sp);
+                                const float sp = f32_sqrt_rn(chain_d2(s_px[j], s_py[j], s_pz[j], qp[0], qp[1], qp[2]));
+                                const uint32_t k0 = lddt_hits(g, d0, sp), k1 = lddt_hits(g, d1, sp);
                                 n0 += pair0 ? 1u : 0u; h0 += pair0 ? k0 : 0u;
                                 n1 += pair1 ? 1u : 0u; h1 += pair1 ? k1 : 0u;
                             }
                         } else {
                             if (__any(pair0)) {
-                                const float sp = f32_sqrt_rn(sasa_d2(s_px[j], s_py[j], s_pz[j], qp[0], qp[1], qp[2]));
-                                const uint32_t k0 = lddta_hits(g, d0, sp);
+                                const float sp = f32_sqrt_rn(chain_d2(s_px[j], s_py[j], s_pz[j], qp[0], qp[1], qp[2]));
+                                const uint32_t k0 = lddt_hits(g, d0, sp);
                                 n0 += pair0 ? 1u : 0u; h0 += pair0 ? k0 : 0u;
                             }
                         }
@@ -271,15 +231,15 @@ __global__ __launch_bounds__(BLOCK) void k_lddt_atoms(lddta_args g, const lddta_
                 if constexpr (DECIDE) {
                     if (n1) { atomicAdd(&r_cnt[rr][2], n1); atomicAdd(&r_cnt[rr][3], h1); }
                 } else {
-                    if (g.atom_pairs) g.atom_pairs[(row0 + ri) * A + a] = (int32_t)n0;
-                    if (g.atom_hits) g.atom_hits[(row0 + ri) * A + a] = (int32_t)h0;
+                    if (g.atom_pairs) g.atom_pairs[(ct.row0 + ri) * A + a] = (int32_t)n0;
+                    if (g.atom_hits) g.atom_hits[(ct.row0 + ri) * A + a] = (int32_t)h0;
                 }
             }
         }
         __syncthreads();
         // ---- the tile's rows (rows behind the chain's length have no query atom: 0) ----
-        if (tid < TR && tq0 + tid < rows) {
-            const uint64_t o = row0 + tq0 + tid;
+        if (tid < TR && ct.q0 + tid < ct.rows) {
+            const uint64_t o = ct.row0 + ct.q0 + tid;
             if constexpr (DECIDE) {
                 const unsigned long long P0 = r_cnt[tid][0], H0 = r_cnt[tid][1], P1 = r_cnt[tid][2], H1 = r_cnt[tid][3];
                 g.swapped[o] = H1 * P0 > H0 * P1 ? 1 : 0;

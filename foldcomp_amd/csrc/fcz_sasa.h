@@ -18,7 +18,8 @@
 //         * the chain's atoms are staged in LDS in passes of at most SASA_PASS = 1536, compacted: float4 (x, y, z, Rj), the chain row
 //           (uint32) and the slot (uint8), 21 bytes an atom (row * A + slot in one word would wrap for chains above 2^32 / 37 rows, so
 //           the identity keeps both). A pass is staged in steps of the rows that hold at most 512 slots, two slots a lane, and is
-//           closed when another step might not fit; in backbone4 with every mask set that is exactly 1536 atoms;
+//           closed when another step might not fit; in backbone4 with every mask set that is exactly 1536 atoms
+//           (chain_stage_slots, fcz_chains.h, which k_violations and k_lddt_atoms stage through as well);
 //         * per 64 staged candidates lane = candidate: one d2(c_i, c_j) < S * S test a lane, and the ballot of that test is the
 //           wavefront's candidate set for this query atom. The candidate is read once for all eight query atoms of the wavefront;
 //         * for every set bit the candidate comes back as one broadcast LDS read and lane = point: lane l owns points l, l + 64, ..
@@ -36,15 +37,15 @@
 //       LDS: 1536 * 21 = 32256 bytes of candidates, 112 * 25 = 2800 bytes of query atoms (float4, row, slot, count), 8 of counters:
 //       35064 bytes a block, so FOUR blocks (16 wavefronts, four per SIMD) share a CU's 160 KiB and a wavefront may hold 128 VGPRs
 //       (k_lddt / k_hbond run five blocks at 30 KiB; the slot byte and the query list cost the fifth). `make asm` prints the VGPRs:
-//       padded SMALL 66, padded large 61, packed SMALL 66, packed large 60, no scratch (all run four blocks; LDS is the limit, and
+//       padded SMALL 59, padded large 53, packed SMALL 56, packed large 53, no scratch (all run four blocks; LDS is the limit, and
 //       1280 atoms a pass would buy the fifth).
 //       The tile's epilogue also writes the per-residue outputs: a tile is whole rows, so the block has every count of the row in LDS
 //       and one lane per row does the float64 sum. (A separate lane-per-row kernel would need a second tiling of the packed form,
 //       CHAIN_TILE rows, and would read the counts back from HBM.) Every term is an integer of at most 11 bits times a float32 in
 //       [0.25, 64) and at most 37 are summed, so the float64 sum is exact and does not depend on the order the compaction gave.
 //       HBM sees the inputs, 2 bytes a slot and 5 bytes a row: no rows x rows and no atoms x atoms array.
-//   k_sasa_fill   packed form only, in front of the sweep: 0 into every row that no chain is seen to cover (chain_covers: a covered
-//                 row it misses is rewritten by the sweep behind it).
+//   k_chain_fill<sasa_args>   (fcz_chains.h) packed form only, in front of the sweep: 0 (chain_empty_row) into every row that no
+//                 chain is seen to cover (chain_covers: a covered row it misses is rewritten by the sweep behind it).
 //
 // Every index that scales with rows * A is 64-bit. A chain's range is clamped to the R rows that exist and a range that runs
 // backwards is empty (chain_range), so no read leaves the inputs whatever row_off holds; aatype is clamped to 20 before the table
@@ -63,10 +64,7 @@ constexpr uint32_t SASA_TILE_ATOMS = 112;   // >= SASA_TILE_ROWS * DN_MAX_WIDTH
 constexpr uint32_t SASA_MAX_POINTS = 1024;  // 16 points a lane
 constexpr uint32_t SASA_SMALL_POINTS = 128; // two points a lane: their directions stay in registers
 constexpr uint32_t SASA_MAX_ROWS = 0x7FFFFFFFu;
-constexpr uint32_t SASA_TYPES = 21;
 static_assert(SASA_TILE_ATOMS >= SASA_TILE_ROWS * DN_MAX_WIDTH && SASA_PASS % SASA_STEP == 0 && SASA_GROUP == 32, "fcz_sasa.h");
-
-struct sasa_table { float radius[SASA_TYPES * DN_MAX_WIDTH]; };   // [min(aatype, 20)][slot] with rows of A floats
 
 struct sasa_args {
     const float* pos; const uint8_t* mask; const uint8_t* aatype;   // aatype may be NULL: every row uses row 0 of the table
@@ -79,34 +77,18 @@ struct sasa_args {
     int16_t* sasa_points; float* sasa; uint8_t* sasa_mask;
 };
 
-// x / A for the three widths there are, without a division by a variable
-__device__ __forceinline__ uint32_t sasa_div_a(uint32_t x, uint32_t A) { return A == 37u ? x / 37u : A == 14u ? x / 14u : x / 4u; }
-
-__device__ __forceinline__ float sasa_d2(float ax, float ay, float az, float bx, float by, float bz) {
-    const float dx = __fsub_rn(ax, bx), dy = __fsub_rn(ay, by), dz = __fsub_rn(az, bz);
-    return __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
-}
-
-// slot a of array row r (a row inside its chain) -> true when it is an atom; c = (x, y, z, R)
-__device__ __forceinline__ bool sasa_atom(const sasa_args& g, const sasa_table& tab, uint64_t r, uint32_t a, float4* c) {
-    if (g.mask[r * g.A + a] == 0) return false;
-    uint32_t ty = g.aatype ? g.aatype[r] : 0u;
-    if (ty > 20u) ty = 20u;
-    const float radius = tab.radius[ty * g.A + a];
-    if (radius == 0.0f) return false;
-    const float* p = g.pos + (r * g.A + a) * 3u;
-    const float x = p[0], y = p[1], z = p[2];
-    if (!(isfinite(x) && isfinite(y) && isfinite(z))) return false;
-    *c = make_float4(x, y, z, __fadd_rn(radius, g.probe));
+// slot a of array row r (a row inside its chain) -> true when it is an atom (chain_atom); c = (x, y, z, R) with R = radius + probe
+__device__ __forceinline__ bool sasa_atom(const sasa_args& g, const chain_radii& tab, uint64_t r, uint32_t a, float4* c) {
+    uint32_t ty;
+    if (!chain_atom(g, tab, r, a, c, &ty)) return false;
+    c->w = __fadd_rn(c->w, g.probe);
     return true;
 }
 
-__global__ __launch_bounds__(BLOCK) void k_sasa_fill(sasa_args g) {
-    for (uint64_t r = (uint64_t)blockIdx.x * BLOCK + threadIdx.x; r < g.L; r += (uint64_t)gridDim.x * BLOCK) {
-        if (chain_covers(g.bound, g.n, r)) continue;
-        for (uint32_t a = 0; a < g.A; a++) g.sasa_points[r * g.A + a] = 0;
-        g.sasa[r] = 0.0f; g.sasa_mask[r] = 0;
-    }
+// row r of the arrays holds nothing
+__device__ __forceinline__ void chain_empty_row(const sasa_args& g, uint64_t r) {
+    for (uint32_t a = 0; a < g.A; a++) g.sasa_points[r * g.A + a] = 0;
+    g.sasa[r] = 0.0f; g.sasa_mask[r] = 0;
 }
 
 // the lane's p-th point (number p * 64 + lane) of the query atom ci against the candidates `hits` of the 64 staged at c0: clears the
@@ -118,13 +100,13 @@ __device__ __forceinline__ uint32_t sasa_point(uint32_t bits, uint32_t p, float4
         const uint32_t b = (uint32_t)__ffsll((unsigned long long)hits) - 1u;
         hits &= hits - 1u;
         const float4 cj = s_c[c0 + b];                                // one broadcast read
-        buried = buried || sasa_d2(tx, ty, tz, cj.x, cj.y, cj.z) < __fmul_rn(cj.w, cj.w);
+        buried = buried || chain_d2(tx, ty, tz, cj.x, cj.y, cj.z) < __fmul_rn(cj.w, cj.w);
     }
     return buried ? bits & ~(1u << p) : bits;
 }
 
 template <bool PACKED, bool SMALL>
-__global__ __launch_bounds__(BLOCK) void k_sasa_points(sasa_args g, const sasa_table tab, const uint64_t* __restrict__ tile_off, uint32_t tiles_per_entry,
+__global__ __launch_bounds__(BLOCK) void k_sasa_points(sasa_args g, const chain_radii tab, const uint64_t* __restrict__ tile_off, uint32_t tiles_per_entry,
                                                        uint64_t n_tiles_padded) {
     __shared__ float4 s_c[SASA_PASS];
     __shared__ uint32_t s_row[SASA_PASS];
@@ -138,7 +120,6 @@ __global__ __launch_bounds__(BLOCK) void k_sasa_points(sasa_args g, const sasa_t
     const uint32_t per_lane = (P + 63u) / 64u;                        // points a lane may own, 1 .. 16
     const uint32_t mine = lane < P ? (P - lane + 63u) / 64u : 0u;     // points this lane owns
     const uint32_t full = mine ? (0xFFFFFFFFu >> (32u - mine)) : 0u;
-    const uint32_t step_rows = SASA_STEP / A;                         // rows a staging step examines: 13, 36, 128
     float u0[3] = {0.0f, 0.0f, 0.0f}, u1[3] = {0.0f, 0.0f, 0.0f};
     if constexpr (SMALL) {
 #pragma unroll
@@ -147,29 +128,23 @@ __global__ __launch_bounds__(BLOCK) void k_sasa_points(sasa_args g, const sasa_t
             if (lane + 64u < P) u1[k] = g.points[(lane + 64u) * 3u + k];
         }
     }
-    const uint64_t n_tiles = PACKED ? tile_off[g.n] : n_tiles_padded;
+    const uint64_t n_tiles = chain_tile_count<PACKED>(tile_off, g.n, n_tiles_padded);
     for (uint64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-        uint32_t e, t;
-        chain_of_tile<PACKED>(tile_off, g.n, tiles_per_entry, tile, &e, &t);
-        uint64_t row0; uint32_t len, rows;
-        chain_range<PACKED>(g.bound, g.L, e, &row0, &len, &rows);
-        const uint64_t tq0 = (uint64_t)t * SASA_TILE_ROWS;           // the tile's first row of the chain
+        const chain_tile<PACKED> ct(tile_off, g.n, tiles_per_entry, g.bound, g.L, tile, SASA_TILE_ROWS);
         // ---- the tile's atoms, compacted; every slot that is none is written 0 here, every atom at the end of its round ----
         if (tid == 0) s_nq = 0;
         __syncthreads();
-        if (tid < SASA_TILE_ROWS * A) {
-            const uint32_t rr = sasa_div_a(tid, A), a = tid - rr * A;
-            const uint64_t q = tq0 + rr;
-            if (q < rows) {
+        chain_tile_slots(SASA_TILE_ROWS, A, ct.q0, [&](uint32_t, uint32_t, uint32_t a, uint64_t q) __attribute__((always_inline)) {
+            if (q < ct.rows) {
                 float4 c;
-                if (q < len && sasa_atom(g, tab, row0 + q, a, &c)) {
-                    const uint32_t i = atomicAdd(&s_nq, 1u);          // (< SASA_TILE_ATOMS: one slot per lane here)
+                if (q < ct.len && sasa_atom(g, tab, ct.row0 + q, a, &c)) {
+                    const uint32_t i = atomicAdd(&s_nq, 1u);          // (< SASA_TILE_ATOMS: one slot per slot of the tile)
                     q_c[i] = c; q_row[i] = (uint32_t)q; q_slot[i] = (uint8_t)a; q_cnt[i] = 0;
                 } else {
-                    g.sasa_points[(row0 + q) * A + a] = 0;
+                    g.sasa_points[(ct.row0 + q) * A + a] = 0;
                 }
             }
-        }
+        });
         __syncthreads();
         const uint32_t nq = s_nq;
         for (uint32_t base = 0; base < nq; base += SASA_GROUP) {
@@ -177,30 +152,14 @@ __global__ __launch_bounds__(BLOCK) void k_sasa_points(sasa_args g, const sasa_t
 #pragma unroll
             for (uint32_t k = 0; k < SASA_Q; k++) bits[k] = base + wave + 4u * k < nq ? full : 0u;
             // ---- the chain's atoms in passes ----
-            for (uint32_t r0 = 0; r0 < len;) {
-                if (tid == 0) s_count = 0;
-                __syncthreads();
-                for (;;) {                                            // steps of step_rows rows until the pass is full or the chain ends
-                    const uint32_t nr = len - r0 < step_rows ? len - r0 : step_rows;
-#pragma unroll
-                    for (uint32_t h = 0; h < 2; h++) {
-                        const uint32_t x = tid + h * BLOCK;
-                        if (x < nr * A) {
-                            const uint32_t rr = sasa_div_a(x, A), a = x - rr * A;
-                            float4 c;
-                            if (sasa_atom(g, tab, row0 + r0 + rr, a, &c)) {
-                                const uint32_t i = atomicAdd(&s_count, 1u);   // (< SASA_PASS: the step was let in below)
-                                s_c[i] = c; s_row[i] = r0 + rr; s_slot[i] = (uint8_t)a;
-                            }
-                        }
+            for (uint32_t r0 = 0; r0 < ct.len;) {
+                const uint32_t count = chain_stage_slots<SASA_PASS, SASA_STEP>(&s_count, A, ct.len, &r0, [&](uint32_t r, uint32_t a, chain_slots slots) __attribute__((always_inline)) {
+                    float4 c;
+                    if (sasa_atom(g, tab, ct.row0 + r, a, &c)) {
+                        const uint32_t i = slots.next();
+                        s_c[i] = c; s_row[i] = r; s_slot[i] = (uint8_t)a;
                     }
-                    r0 += nr;
-                    __syncthreads();
-                    const uint32_t staged = s_count;
-                    __syncthreads();                                  // (every lane has read the count before the next step adds to it)
-                    if (r0 >= len || staged + step_rows * A > SASA_PASS) break;
-                }
-                const uint32_t count = s_count;
+                });
                 // ---- the sweep: 64 candidates at a time, the wavefront's query atoms in turn ----
                 for (uint32_t c0 = 0; c0 < count; c0 += 64u) {
                     const uint32_t j = c0 + lane;
@@ -214,7 +173,7 @@ __global__ __launch_bounds__(BLOCK) void k_sasa_points(sasa_args g, const sasa_t
                         const float4 ci = q_c[qi];
                         const float S = __fadd_rn(ci.w, cj.w);
                         const bool near = have && !(jrow == q_row[qi] && jslot == q_slot[qi]) &&
-                                          sasa_d2(ci.x, ci.y, ci.z, cj.x, cj.y, cj.z) < __fmul_rn(S, S);
+                                          chain_d2(ci.x, ci.y, ci.z, cj.x, cj.y, cj.z) < __fmul_rn(S, S);
                         const uint64_t hits = __ballot(near);
                         if (hits == 0) continue;
                         if constexpr (SMALL) {
@@ -241,20 +200,20 @@ __global__ __launch_bounds__(BLOCK) void k_sasa_points(sasa_args g, const sasa_t
                 for (uint32_t p = 0; p < per_lane; p++) total += (uint32_t)__popcll(__ballot((bits[k] >> p) & 1u));
                 if (lane == 0) {
                     q_cnt[qi] = total;
-                    g.sasa_points[(row0 + q_row[qi]) * A + q_slot[qi]] = (int16_t)total;
+                    g.sasa_points[(ct.row0 + q_row[qi]) * A + q_slot[qi]] = (int16_t)total;
                 }
             }
         }
         __syncthreads();
         // ---- the tile's rows: the float64 sum of count * R * R is exact, so the compaction's order does not show ----
-        if (tid < SASA_TILE_ROWS && tq0 + tid < rows) {
-            const uint32_t q = (uint32_t)(tq0 + tid);
+        if (tid < SASA_TILE_ROWS && ct.q0 + tid < ct.rows) {
+            const uint32_t q = (uint32_t)(ct.q0 + tid);
             double sum = 0.0;
             bool any = false;
             for (uint32_t i = 0; i < nq; i++)
                 if (q_row[i] == q) { sum += (double)q_cnt[i] * (double)__fmul_rn(q_c[i].w, q_c[i].w); any = true; }
-            g.sasa[row0 + q] = (float)(sum * g.scale);
-            g.sasa_mask[row0 + q] = any ? 1 : 0;
+            g.sasa[ct.row0 + q] = (float)(sum * g.scale);
+            g.sasa_mask[ct.row0 + q] = any ? 1 : 0;
         }
         __syncthreads();                                              // the next tile rewrites the query list
     }

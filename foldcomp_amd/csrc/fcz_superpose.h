@@ -21,7 +21,7 @@
 //                              identity, so a chain with no or one site (Horn's matrix is zero) gets the identity quaternion.
 //                              t = cb - R ca. Pass 3: dev = |R a + t - b|, its squared sum, the five GDT counters and the TM sum.
 //                              Lane 0 writes the chain's outputs; dev is written for every row of the entry (0 where no site).
-//   k_superpose_fill           packed form only, in front of k_superpose: dev = 0 in every row that no chain is seen to cover
+//   k_chain_fill<superpose_args>   (fcz_chains.h) packed form only, in front of k_superpose: dev = 0 in every row that no chain is seen to cover
 //                              (chain_covers: a covered row it misses is rewritten by k_superpose behind it).
 //   k_superpose_apply<A, PACKED>   pos_out = rot_e @ pos_pred + trans_e in float32, x' = ((r00 x + r01 y) + r02 z) + tx, every
 //                              operation rounded, no FMA, for every slot whose mask_pred is set in rows inside the chain; 0
@@ -29,7 +29,7 @@
 //                              rows of ONE chain, so the chain's twelve floats are read once per tile through wave-uniform
 //                              addresses, and the tile's rows x A x 3 floats leave through dn_emit (fcz_dense.h): 16-byte
 //                              stores over the aligned middle, consecutive lanes on consecutive addresses.
-//   k_superpose_apply_fill     packed form only: 0 into every row of pos_out that no chain is seen to cover.
+//   k_chain_fill<superpose_apply_args>   packed form only: 0 into every row of pos_out that no chain is seen to cover.
 //
 // Every index that scales with rows * A is 64-bit. A chain's range is clamped to the rows that exist and a range that runs
 // backwards is empty (chain_range), so no read leaves the inputs whatever row_off holds.
@@ -52,10 +52,16 @@ struct superpose_args {
 
 struct superpose_apply_args {
     const float* pos; const uint8_t* mask;  // mask may be NULL: every slot present
-    const uint32_t* bound; uint32_t n, L;
+    const uint32_t* bound; uint32_t n, L, A;
     const float* rot; const float* trans;
     float* out;
 };
+
+// row r of the arrays holds nothing
+__device__ __forceinline__ void chain_empty_row(const superpose_args& g, uint64_t r) { g.dev[r] = 0.0f; }
+__device__ __forceinline__ void chain_empty_row(const superpose_apply_args& g, uint64_t r) {
+    for (uint32_t i = 0; i < g.A * 3u; i++) g.out[r * (g.A * 3u) + i] = 0.0f;
+}
 
 // the slot's coordinates of array row r: a = pred, b = true -> true when the row is a site (both masks set, six finite values)
 __device__ __forceinline__ bool superpose_site(const superpose_args& g, uint64_t r, double* a, double* b) {
@@ -134,13 +140,6 @@ __device__ __forceinline__ void superpose_solve(const double* m, double* R) {
     R[0] = ((ww + xx) - yy) - zz; R[1] = 2.0 * (xy - wz);       R[2] = 2.0 * (xz + wy);
     R[3] = 2.0 * (xy + wz);       R[4] = ((ww - xx) + yy) - zz; R[5] = 2.0 * (yz - wx);
     R[6] = 2.0 * (xz - wy);       R[7] = 2.0 * (yz + wx);       R[8] = ((ww - xx) - yy) + zz;
-}
-
-__global__ __launch_bounds__(BLOCK) void k_superpose_fill(superpose_args g) {
-    for (uint64_t r = (uint64_t)blockIdx.x * BLOCK + threadIdx.x; r < g.L; r += (uint64_t)gridDim.x * BLOCK) {
-        if (chain_covers(g.bound, g.n, r)) continue;
-        g.dev[r] = 0.0f;
-    }
 }
 
 template <bool PACKED>
@@ -226,32 +225,20 @@ __global__ __launch_bounds__(BLOCK) void k_superpose(superpose_args g) {
     }
 }
 
-template <int A>
-__global__ __launch_bounds__(BLOCK) void k_superpose_apply_fill(superpose_apply_args g) {
-    const uint64_t total = (uint64_t)g.L * (A * 3u);
-    for (uint64_t i = (uint64_t)blockIdx.x * BLOCK + threadIdx.x; i < total; i += (uint64_t)gridDim.x * BLOCK) {
-        if (chain_covers(g.bound, g.n, i / (A * 3u))) continue;
-        g.out[i] = 0.0f;
-    }
-}
-
 template <int A, bool PACKED>
 __global__ __launch_bounds__(BLOCK) void k_superpose_apply(superpose_apply_args g, const uint64_t* __restrict__ tile_off, uint32_t tiles_per_entry,
                                                            uint64_t n_tiles_padded) {
-    const uint64_t n_tiles = PACKED ? tile_off[g.n] : n_tiles_padded;
+    const uint64_t n_tiles = chain_tile_count<PACKED>(tile_off, g.n, n_tiles_padded);
     for (uint64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-        uint32_t e, t;
-        chain_of_tile<PACKED>(tile_off, g.n, tiles_per_entry, tile, &e, &t);
-        uint64_t row0; uint32_t len, rows;
-        chain_range<PACKED>(g.bound, g.L, e, &row0, &len, &rows);
-        const uint32_t q0 = t * CHAIN_TILE;                                    // the tile's first row of the chain (< rows)
-        const uint32_t nq = rows - q0 < CHAIN_TILE ? rows - q0 : CHAIN_TILE;
-        const uint32_t inside = len > q0 ? len - q0 : 0u;                      // rows of the tile that lie inside the chain
-        const float* rt = g.rot + (uint64_t)e * 9u;
-        const float* tr = g.trans + (uint64_t)e * 3u;
+        const chain_tile<PACKED> ct(tile_off, g.n, tiles_per_entry, g.bound, g.L, tile, CHAIN_TILE);
+        const uint32_t q0 = (uint32_t)ct.q0;                                   // the tile's first row of the chain (< rows)
+        const uint32_t nq = ct.rows - q0 < CHAIN_TILE ? ct.rows - q0 : CHAIN_TILE;
+        const uint32_t inside = ct.len > q0 ? ct.len - q0 : 0u;                // rows of the tile that lie inside the chain
+        const float* rt = g.rot + (uint64_t)ct.e * 9u;
+        const float* tr = g.trans + (uint64_t)ct.e * 3u;
         const float r00 = rt[0], r01 = rt[1], r02 = rt[2], r10 = rt[3], r11 = rt[4], r12 = rt[5], r20 = rt[6], r21 = rt[7], r22 = rt[8];
         const float t0 = tr[0], t1 = tr[1], t2 = tr[2];
-        const uint64_t atom0 = (row0 + q0) * A;                                // the tile's first atom slot in the arrays
+        const uint64_t atom0 = (ct.row0 + q0) * A;                             // the tile's first atom slot in the arrays
         const float* src = g.pos + atom0 * 3u;
         const uint8_t* msk = g.mask ? g.mask + atom0 : nullptr;
         dn_emit(g.out + atom0 * 3u, nq * (A * 3u), [=](uint32_t f) __attribute__((always_inline)) -> float {

@@ -25,7 +25,7 @@
 //   k_tm_final<PACKED>     a wavefront per chain: the largest score, of equal ones the lowest seed; that seed is run again (the search
 //                          is deterministic), now keeping the fit of its best round (of equal ones the earliest), and the outputs
 //                          and dev are written as k_superpose's pass 3 writes them.
-//   k_superpose_fill       (fcz_superpose.h) packed form only, in front: dev = 0 in every row that no chain is seen to cover.
+//   k_chain_fill<superpose_args>   (fcz_chains.h) packed form only, in front: dev = 0 in every row that no chain is seen to cover.
 //
 // Every index that scales with rows * A is 64-bit; a chain's range is clamped to the rows that exist (chain_range).
 #pragma once

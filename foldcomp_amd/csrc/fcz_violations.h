@@ -14,8 +14,8 @@
 //       Persistent blocks over QUERY TILES of whole rows of one chain: 20 rows in atom37, 18 in atom14, 64 in backbone4
 //       (viol_tile_rows; tiles are counted in rows by k_chain_tiles and the scan of fcz_chains.h). A tile's atoms are
 //       compacted into LDS (at most VIOL_TILE_SLOTS = 20 * 37 = 740) and taken in ROUNDS of BLOCK = 256: A LANE PER QUERY ATOM.
-//       The chain's atoms are staged in LDS in passes of at most VIOL_PASS = 1536, compacted as k_sasa_points stages them: float4
-//       (x, y, z, R), the chain row (uint32) and a kind byte (0, 1 = N, 2 = C, 3 = SG of a CYS row: all the exclusions need), 21
+//       The chain's atoms are staged in LDS in passes of at most VIOL_PASS = 1536, compacted as k_sasa_points stages them
+//       (chain_stage_slots, fcz_chains.h): float4 (x, y, z, R), the chain row (uint32) and a kind byte (0, 1 = N, 2 = C, 3 = SG of a CYS row: all the exclusions need), 21
 //       bytes an atom. Every lane then walks the pass from its first atom to its last: all 64 lanes of a wavefront read the SAME
 //       candidate, one broadcast ds_read_b128 and one ds_read_b32 (no bank conflict: a single address), and do one d2 and one
 //       compare each. The kind byte is read only behind a hit.
@@ -31,7 +31,7 @@
 //       There is NO CULL: every (query atom, candidate) pair of a chain is tested, so nothing but the definition decides a result.
 //       LDS: 1536 * 21 = 32256 bytes of candidates, 740 * 19 = 14060 of query atoms (float4, tile slot uint16, kind), 64 * 16 = 1024
 //       of per-row results, 24 of counters: 47376 bytes a block with the alignment, so THREE blocks (12 wavefronts, three per SIMD)
-//       share a CU's 160 KiB and a wavefront may hold 170 VGPRs. `make asm` prints the VGPRs: padded 93, packed 89, no scratch (LDS
+//       share a CU's 160 KiB and a wavefront may hold 170 VGPRs. `make asm` prints the VGPRs: padded 79, packed 75, no scratch (LDS
 //       is the limit; a pass of 1024 atoms would buy the fourth block).
 //       The tile's epilogue writes the per-row outputs: a lane's count goes to its row by an LDS atomic add, its best pair to the
 //       row by an LDS atomic max of the 64-bit key (bits of depth << 32) | (0xFFFFFFFF - partner row) -- depth >= 0 orders as an
@@ -41,13 +41,14 @@
 //       The chain's four counters get the tile's sums by one 64-bit atomic add each (ordinary vector atomics on integers; the host
 //       clears them in front). Pairs are counted once as the hits with partner row > own row, which the symmetry makes exactly half.
 //       HBM sees the inputs, one byte a slot and 23 bytes a row: no rows x rows and no atoms x atoms array.
-//   k_viol_fill   packed form only, in front of the sweep: 0 (-1 for clash_partner) into every row that no chain is seen to cover.
+//   k_chain_fill<viol_args>   (fcz_chains.h) packed form only, in front of the sweep: 0, -1 for clash_partner (chain_empty_row),
+//                 into every row that no chain is seen to cover.
 //
 // Every index that scales with rows * A is 64-bit. A chain's range is clamped to the R rows that exist and a range that runs
 // backwards is empty (chain_range), so no read leaves the inputs whatever row_off holds; aatype is clamped to 20 before the table
 // is read. Rows behind a padded entry's length are written 0 without being read.
 #pragma once
-#include "fcz_sasa.h"
+#include "fcz_chains.h"
 
 namespace fcz {
 
@@ -75,27 +76,16 @@ struct viol_args {
     unsigned long long* chain_counts;       // [n][4], cleared by the host in front of the sweep
 };
 
-// slot a of array row r (a row inside its chain) -> true when it is an atom; c = (x, y, z, R), kind = what the exclusions ask
-__device__ __forceinline__ bool viol_atom(const viol_args& g, const sasa_table& tab, uint64_t r, uint32_t a, float4* c, uint32_t* kind) {
-    if (g.mask[r * g.A + a] == 0) return false;
-    const uint32_t aa = g.aatype ? g.aatype[r] : 0u;
-    const float radius = tab.radius[(aa > 20u ? 20u : aa) * g.A + a];
-    if (radius == 0.0f) return false;
-    const float* p = g.pos + (r * g.A + a) * 3u;
-    const float x = p[0], y = p[1], z = p[2];
-    if (!(isfinite(x) && isfinite(y) && isfinite(z))) return false;
-    *c = make_float4(x, y, z, radius);
+// slot a of array row r (a row inside its chain) -> true when it is an atom (chain_atom); c = (x, y, z, R), kind = what the exclusions ask
+__device__ __forceinline__ bool viol_atom(const viol_args& g, const chain_radii& tab, uint64_t r, uint32_t a, float4* c, uint32_t* kind) {
+    uint32_t aa;
+    if (!chain_atom(g, tab, r, a, c, &aa)) return false;
     *kind = a == g.n_slot ? VIOL_KIND_N : a == g.c_slot ? VIOL_KIND_C : ((int32_t)a == g.sg_slot && g.aatype && aa == VIOL_CYS) ? VIOL_KIND_SG : 0u;
     return true;
 }
 
 // slot a of array row r -> true when mask and finiteness make it an atom of a link (the radius table plays no part)
-__device__ __forceinline__ bool viol_link_atom(const viol_args& g, uint64_t r, uint32_t a, float* c) {
-    if (g.mask[r * g.A + a] == 0) return false;
-    const float* p = g.pos + (r * g.A + a) * 3u;
-    c[0] = p[0]; c[1] = p[1]; c[2] = p[2];
-    return isfinite(c[0]) && isfinite(c[1]) && isfinite(c[2]);
-}
+__device__ __forceinline__ bool viol_link_atom(const viol_args& g, uint64_t r, uint32_t a, float* c) { return chain_site(g.pos, g.mask, r * g.A + a, c); }
 
 // the cosine of the angle at b between a and c: u = a - b, v = c - b, dot / (|u| * |v|)
 __device__ __forceinline__ float viol_cos(const float* a, const float* b, const float* c) {
@@ -107,22 +97,19 @@ __device__ __forceinline__ float viol_cos(const float* a, const float* b, const 
     return __fdiv_rn(dot, __fmul_rn(nu, nv));
 }
 
-// row r of the arrays holds nothing
+// row r of the arrays holds nothing: the per-row outputs, which the sweep's epilogue also writes behind a chain's length, and with
+// the row's slots what the fill in front of the sweep writes
 __device__ __forceinline__ void viol_empty_row(const viol_args& g, uint64_t r) {
     g.clash_count[r] = 0; g.clash_depth[r] = 0.0f; g.clash_partner[r] = -1; g.viol_mask[r] = 0;
     g.link_mask[r] = 0; g.link_length[r] = 0.0f; g.link_cos[r * 2u] = 0.0f; g.link_cos[r * 2u + 1u] = 0.0f; g.link_violation[r] = 0;
 }
-
-__global__ __launch_bounds__(BLOCK) void k_viol_fill(viol_args g) {
-    for (uint64_t r = (uint64_t)blockIdx.x * BLOCK + threadIdx.x; r < g.L; r += (uint64_t)gridDim.x * BLOCK) {
-        if (chain_covers(g.bound, g.n, r)) continue;
-        for (uint32_t a = 0; a < g.A; a++) g.clash_atom[r * g.A + a] = 0;
-        viol_empty_row(g, r);
-    }
+__device__ __forceinline__ void chain_empty_row(const viol_args& g, uint64_t r) {
+    for (uint32_t a = 0; a < g.A; a++) g.clash_atom[r * g.A + a] = 0;
+    viol_empty_row(g, r);
 }
 
 template <bool PACKED>
-__global__ __launch_bounds__(BLOCK) void k_violations(viol_args g, const sasa_table tab, const uint64_t* __restrict__ tile_off, uint32_t tiles_per_entry,
+__global__ __launch_bounds__(BLOCK) void k_violations(viol_args g, const chain_radii tab, const uint64_t* __restrict__ tile_off, uint32_t tiles_per_entry,
                                                       uint64_t n_tiles_padded) {
     __shared__ float4 s_c[VIOL_PASS];
     __shared__ uint32_t s_row[VIOL_PASS];
@@ -136,34 +123,27 @@ __global__ __launch_bounds__(BLOCK) void k_violations(viol_args g, const sasa_ta
     const uint32_t tid = threadIdx.x;
     const uint32_t A = g.A;
     const uint32_t TR = viol_tile_rows(A);
-    const uint32_t step_rows = VIOL_STEP / A;                         // rows a staging step examines: 13, 36, 128
     const float tol = g.tolerance;
-    const uint64_t n_tiles = PACKED ? tile_off[g.n] : n_tiles_padded;
+    const uint64_t n_tiles = chain_tile_count<PACKED>(tile_off, g.n, n_tiles_padded);
     for (uint64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-        uint32_t e, t;
-        chain_of_tile<PACKED>(tile_off, g.n, tiles_per_entry, tile, &e, &t);
-        uint64_t row0; uint32_t len, rows;
-        chain_range<PACKED>(g.bound, g.L, e, &row0, &len, &rows);
-        const uint64_t tq0 = (uint64_t)t * TR;                        // the tile's first row of the chain
+        const chain_tile<PACKED> ct(tile_off, g.n, tiles_per_entry, g.bound, g.L, tile, TR);
         // ---- the tile's atoms, compacted; every slot that is none is written 0 here, every atom at the end of its round ----
         if (tid == 0) s_nq = 0;
         if (tid < 4) s_sum[tid] = 0;
         if (tid < TR) { r_key[tid] = 0ull; r_cnt[tid] = 0; r_any[tid] = 0; }
         __syncthreads();
-        for (uint32_t x = tid; x < TR * A; x += BLOCK) {
-            const uint32_t rr = sasa_div_a(x, A), a = x - rr * A;
-            const uint64_t q = tq0 + rr;
-            if (q < rows) {
+        chain_tile_slots(TR, A, ct.q0, [&](uint32_t x, uint32_t rr, uint32_t a, uint64_t q) __attribute__((always_inline)) {
+            if (q < ct.rows) {
                 float4 c; uint32_t kind;
-                if (q < len && viol_atom(g, tab, row0 + q, a, &c, &kind)) {
-                    const uint32_t i = atomicAdd(&s_nq, 1u);          // (< VIOL_TILE_SLOTS: one slot per iteration here)
+                if (q < ct.len && viol_atom(g, tab, ct.row0 + q, a, &c, &kind)) {
+                    const uint32_t i = atomicAdd(&s_nq, 1u);          // (< VIOL_TILE_SLOTS: one slot per slot of the tile)
                     q_c[i] = c; q_at[i] = (uint16_t)x; q_kind[i] = (uint8_t)kind;
                     r_any[rr] = 1u;                                   // (every writer stores the same value)
                 } else {
-                    g.clash_atom[(row0 + q) * A + a] = 0;
+                    g.clash_atom[(ct.row0 + q) * A + a] = 0;
                 }
             }
-        }
+        });
         __syncthreads();
         const uint32_t nq = s_nq;
         for (uint32_t base = 0; base < nq; base += BLOCK) {
@@ -172,42 +152,26 @@ __global__ __launch_bounds__(BLOCK) void k_violations(viol_args g, const sasa_ta
             const bool wave_has = base + (tid & ~63u) < nq;           // wave-uniform: some lane of this wavefront holds a query atom
             const float4 ci = have ? q_c[qi] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
             const uint32_t at = have ? q_at[qi] : 0u, ki = have ? q_kind[qi] : 0u;
-            const uint32_t rr = sasa_div_a(at, A);
-            const uint32_t ri = (uint32_t)tq0 + rr;                   // the query atom's row of the chain (< len <= 2^31 - 1)
+            const uint32_t rr = chain_div_a(at, A);
+            const uint32_t ri = (uint32_t)ct.q0 + rr;                 // the query atom's row of the chain (< len <= 2^31 - 1)
             uint32_t cnt = 0, cnt_up = 0;
             unsigned long long key = 0ull;
             // ---- the chain's atoms in passes ----
-            for (uint32_t r0 = 0; r0 < len;) {
-                if (tid == 0) s_count = 0;
-                __syncthreads();
-                for (;;) {                                            // steps of step_rows rows until the pass is full or the chain ends
-                    const uint32_t nr = len - r0 < step_rows ? len - r0 : step_rows;
-#pragma unroll
-                    for (uint32_t h = 0; h < 2; h++) {
-                        const uint32_t x = tid + h * BLOCK;
-                        if (x < nr * A) {
-                            const uint32_t sr = sasa_div_a(x, A), a = x - sr * A;
-                            float4 c; uint32_t kind;
-                            if (viol_atom(g, tab, row0 + r0 + sr, a, &c, &kind)) {
-                                const uint32_t i = atomicAdd(&s_count, 1u);   // (< VIOL_PASS: the step was let in below)
-                                s_c[i] = c; s_row[i] = r0 + sr; s_kind[i] = (uint8_t)kind;
-                            }
-                        }
+            for (uint32_t r0 = 0; r0 < ct.len;) {
+                const uint32_t count = chain_stage_slots<VIOL_PASS, VIOL_STEP>(&s_count, A, ct.len, &r0, [&](uint32_t r, uint32_t a, chain_slots slots) __attribute__((always_inline)) {
+                    float4 c; uint32_t kind;
+                    if (viol_atom(g, tab, ct.row0 + r, a, &c, &kind)) {
+                        const uint32_t i = slots.next();
+                        s_c[i] = c; s_row[i] = r; s_kind[i] = (uint8_t)kind;
                     }
-                    r0 += nr;
-                    __syncthreads();
-                    const uint32_t staged = s_count;
-                    __syncthreads();                                  // (every lane has read the count before the next step adds to it)
-                    if (r0 >= len || staged + step_rows * A > VIOL_PASS) break;
-                }
-                const uint32_t count = s_count;
+                });
                 // ---- the sweep: every lane meets every staged atom, all lanes of a wavefront the same one at a time ----
                 if (wave_has) {
                     for (uint32_t j = 0; j < count; j++) {
                         const float4 cj = s_c[j];                     // one broadcast read
                         const uint32_t rj = s_row[j];
                         const float T = __fsub_rn(__fadd_rn(ci.w, cj.w), tol);
-                        const float d2 = sasa_d2(ci.x, ci.y, ci.z, cj.x, cj.y, cj.z);
+                        const float d2 = chain_d2(ci.x, ci.y, ci.z, cj.x, cj.y, cj.z);
                         if (have && rj != ri && T > 0.0f && d2 < __fmul_rn(T, T)) {
                             const uint32_t kj = s_kind[j];
                             const bool bonded = (ki == VIOL_KIND_C && kj == VIOL_KIND_N && rj == ri + 1u) ||
@@ -226,17 +190,17 @@ __global__ __launch_bounds__(BLOCK) void k_violations(viol_args g, const sasa_ta
             }
             // ---- the round's atoms ----
             if (have) {
-                g.clash_atom[(row0 + ri) * A + (at - rr * A)] = cnt ? 1 : 0;
+                g.clash_atom[(ct.row0 + ri) * A + (at - rr * A)] = cnt ? 1 : 0;
                 if (cnt) { atomicAdd(&r_cnt[rr], cnt); atomicMax(&r_key[rr], key); }
                 if (cnt_up) atomicAdd(&s_sum[1], cnt_up);
             }
         }
         __syncthreads();
         // ---- the tile's rows: the clash summary and the link to the next row ----
-        if (tid < TR && tq0 + tid < rows) {
-            const uint32_t q = (uint32_t)(tq0 + tid);
-            const uint64_t r = row0 + q;
-            if (q >= len) {
+        if (tid < TR && ct.q0 + tid < ct.rows) {
+            const uint32_t q = (uint32_t)(ct.q0 + tid);
+            const uint64_t r = ct.row0 + q;
+            if (q >= ct.len) {
                 viol_empty_row(g, r);
             } else {
                 const unsigned long long key = r_key[tid];
@@ -245,7 +209,7 @@ __global__ __launch_bounds__(BLOCK) void k_violations(viol_args g, const sasa_ta
                 g.clash_partner[r] = key ? (int32_t)(0xFFFFFFFFu - (uint32_t)key) : -1;
                 g.viol_mask[r] = r_any[tid] ? 1 : 0;
                 float ca[3], c[3], n1[3], ca1[3];
-                bool link = q + 1u < len;
+                bool link = q + 1u < ct.len;
                 if (link) {                                           // (row r + 1 is a row of the chain: inside the arrays)
                     const bool a0 = viol_link_atom(g, r, g.ca_slot, ca), a1 = viol_link_atom(g, r, g.c_slot, c);
                     const bool a2 = viol_link_atom(g, r + 1u, g.n_slot, n1), a3 = viol_link_atom(g, r + 1u, g.ca_slot, ca1);
@@ -255,7 +219,7 @@ __global__ __launch_bounds__(BLOCK) void k_violations(viol_args g, const sasa_ta
                 uint32_t bits = 0;
                 if (link) {
                     const bool pro = g.aatype && g.aatype[r + 1u] == VIOL_PRO;
-                    length = f32_sqrt_rn(sasa_d2(c[0], c[1], c[2], n1[0], n1[1], n1[2]));
+                    length = f32_sqrt_rn(chain_d2(c[0], c[1], c[2], n1[0], n1[1], n1[2]));
                     cos0 = viol_cos(ca, c, n1);
                     cos1 = viol_cos(c, n1, ca1);
                     const float l0 = pro ? 1.341f : 1.329f, sl = pro ? 0.016f : 0.014f;
@@ -272,7 +236,7 @@ __global__ __launch_bounds__(BLOCK) void k_violations(viol_args g, const sasa_ta
         __syncthreads();
         if (tid < 4) {
             const uint32_t v = tid == 0 ? nq : s_sum[tid];
-            if (v) atomicAdd(&g.chain_counts[(uint64_t)e * 4u + tid], (unsigned long long)v);
+            if (v) atomicAdd(&g.chain_counts[(uint64_t)ct.e * 4u + tid], (unsigned long long)v);
         }
         __syncthreads();                                              // the next tile rewrites the query list and the sums
     }

@@ -9,7 +9,7 @@ from __future__ import annotations
 import ctypes
 import os
 
-from .structure import (CAtomsOut, CChainBatch, CDenseIn, CDenseOut, CEntryInfo, CIngestResult, CLddtAtomsOut, CPackedOut, CSuperposeOut, CTmScoreOut, CChainSet, CTmAlignParams, CTmAlignOut,
+from .structure import (CAtomsOut, CChainBatch, CDenseIn, CDenseOut, CEntryInfo, CIngestResult, CLddtAtomsOut, CPackedOut, CSuperposeOut, CTmScoreOut, CGdtOut, CChainSet, CTmAlignParams, CTmAlignOut,
                         CViolationsOut)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -130,6 +130,10 @@ def load():
         "fcz_tmscore_packed_dev": (i32, [vp, vp, vp, vp, vp, vp, u32, u32, i32, i32, u32, u32, ctypes.POINTER(CTmScoreOut)]),
         "fcz_tmscore": (i32, [vp, vp, vp, vp, vp, vp, u32, u32, i32, i32, u32, u32, ctypes.POINTER(CTmScoreOut)]),
         "fcz_tmscore_packed": (i32, [vp, vp, vp, vp, vp, vp, u32, u32, i32, i32, u32, u32, ctypes.POINTER(CTmScoreOut)]),
+        "fcz_gdt_dev": (i32, [vp, vp, vp, vp, vp, vp, u32, u32, i32, i32, u32, u32, u32, ctypes.POINTER(CGdtOut)]),
+        "fcz_gdt_packed_dev": (i32, [vp, vp, vp, vp, vp, vp, u32, u32, i32, i32, u32, u32, u32, ctypes.POINTER(CGdtOut)]),
+        "fcz_gdt": (i32, [vp, vp, vp, vp, vp, vp, u32, u32, i32, i32, u32, u32, u32, ctypes.POINTER(CGdtOut)]),
+        "fcz_gdt_packed": (i32, [vp, vp, vp, vp, vp, vp, u32, u32, i32, i32, u32, u32, u32, ctypes.POINTER(CGdtOut)]),
         "fcz_tmalign_seeds": (u64, [u32, u32, u32]),
         "fcz_tmalign_seed": (i32, [u32, u32, u32, u64, ctypes.POINTER(i32), ctypes.POINTER(i32), ctypes.POINTER(u32), ctypes.POINTER(u32), ctypes.POINTER(u32)]),
         "fcz_tmalign_last_work": (i32, [vp, ctypes.POINTER(u64), ctypes.POINTER(u64)]),
@@ -210,6 +214,7 @@ EXPORTS = ["fcz_ctx_create", "fcz_ctx_destroy", "fcz_ctx_stream", "fcz_ctx_synch
            "fcz_superpose_dev", "fcz_superpose_packed_dev", "fcz_superpose", "fcz_superpose_packed",
            "fcz_superpose_apply_dev", "fcz_superpose_apply_packed_dev", "fcz_superpose_apply", "fcz_superpose_apply_packed",
            "fcz_tmscore_seeds", "fcz_tmscore_seed_fragment", "fcz_tmscore_dev", "fcz_tmscore_packed_dev", "fcz_tmscore", "fcz_tmscore_packed",
+           "fcz_gdt_dev", "fcz_gdt_packed_dev", "fcz_gdt", "fcz_gdt_packed",
            "fcz_tmalign_seeds", "fcz_tmalign_seed", "fcz_tmalign_last_work", "fcz_tmalign_dev", "fcz_tmalign", "fcz_tmalign_dp_dev", "fcz_tmalign_dp",
            "fcz_frames_width", "fcz_frame_atom", "fcz_frame_ambiguous", "fcz_frames_dev", "fcz_frames",
            "fcz_extract_sizes", "fcz_extract",

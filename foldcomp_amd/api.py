@@ -480,6 +480,40 @@ def check_tm_search(iterations=20, levels=None):
     return int(iterations), 0 if levels is None else int(levels)
 
 
+GDT_CUTOFFS = GDT_THRESHOLDS                                               # the cutoffs of gdt; run 1 + k of its search has the constant cut GDT_CUTOFFS[k]
+GDT_RUNS_ALL, GDT_RUNS_TM = 63, 1                                          # FCZ_GDT_RUNS_ALL, FCZ_GDT_RUNS_TM (include/fcz_hip.h)
+
+
+def check_gdt_runs(runs="all"):
+    """runs of gdt -> the bit mask the C call takes (bit 0: the TM cuts; bit 1 + k: the constant cut GDT_CUTOFFS[k]): "all", "tm", or
+    an iterable, not empty, of "tm" and cutoffs out of GDT_CUTOFFS"""
+    if isinstance(runs, str):
+        if runs not in ("all", "tm"):
+            raise ValueError(f"runs must be 'all', 'tm' or an iterable of 'tm' and cutoffs out of {GDT_CUTOFFS}, not {runs!r}")
+        return GDT_RUNS_ALL if runs == "all" else GDT_RUNS_TM
+    try:
+        items = list(runs)
+    except TypeError:
+        raise ValueError(f"runs must be 'all', 'tm' or an iterable of 'tm' and cutoffs out of {GDT_CUTOFFS}, not {runs!r}") from None
+    mask = 0
+    for r in items:
+        if isinstance(r, str) and r == "tm":
+            mask |= 1
+        elif isinstance(r, (int, float, np.integer, np.floating)) and not isinstance(r, (bool, np.bool_)) and float(r) in GDT_CUTOFFS:
+            mask |= 2 << GDT_CUTOFFS.index(float(r))
+        else:
+            raise ValueError(f"a run must be 'tm' or a cutoff out of {GDT_CUTOFFS}, not {r!r}")
+    if not mask:
+        raise ValueError("runs must name at least one run")
+    return mask
+
+
+def check_gdt(atom, shape, pred_shape, pred_mask_shape=None, iterations=20, levels=None, runs="all"):
+    """the argument rules of gdt that need no torch and no GPU -> (slot, iterations, levels as the C call takes it, runs as its bit
+    mask): check_tm_score's rules, and check_gdt_runs' for runs"""
+    return check_tm_score(atom, shape, pred_shape, pred_mask_shape, iterations, levels) + (check_gdt_runs(runs),)
+
+
 TM_ALIGN_MAX_WIDTH = 1024                                                  # FCZ_TMALIGN_MAX_WIDTH (include/fcz_hip.h)
 TM_ALIGN_MAX_ROUNDS = 64
 TM_ALIGN_MAX_GAP = 16.0

@@ -15,7 +15,7 @@ from typing import NamedTuple, Optional
 import numpy as np
 
 from . import _lib
-from .structure import CAtomsOut, CChainBatch, CDenseIn, CDenseOut, CEntryInfo, ChainBatch, CPackedOut, CSuperposeOut, CTmScoreOut, batch_as_c
+from .structure import CAtomsOut, CChainBatch, CDenseIn, CDenseOut, CEntryInfo, ChainBatch, CPackedOut, CGdtOut, CSuperposeOut, CTmScoreOut, batch_as_c
 
 
 # the columns of the angle tensors (FCZ_ANGLE_COLUMNS, include/fcz_hip.h), degrees
@@ -468,6 +468,28 @@ class Codec:
             out = CTmScoreOut(*(d[k].ctypes.data for k in ("rot", "trans", "rmsd", "sites", "gdt_counts", "tm", "dev", "seed", "selected")))
             self._call("fcz_tmscore", a.packed, a.pos.ctypes.data, a.mask.ctypes.data, pos_pred.ctypes.data, _addr(mask_pred), _addr(a.bound), a.n, a.rows, a.lay,
                        slot, levels, iterations, ctypes.byref(out))
+        return d
+
+    def gdt(self, pos_true: np.ndarray, mask_true: np.ndarray, pos_pred: np.ndarray, mask_pred=None, slot: int = 1, length=None, row_off=None,
+            iterations: int = 20, levels=None, runs="all"):
+        """two sets of dense arrays of one shape on the host -> per chain and per cutoff of 0.5, 1, 2, 4, 8 A the largest number of sites
+        that a superposition of the seeded search of fcz_gdt brings under it (fcz_gdt_packed when row_off is given; the definition:
+        include/fcz_hip.h): gdt_counts int32 [n, 5], sites int32 [n], rot float32 [n, 5, 3, 3] and trans [n, 5, 3] (the
+        superposition behind each count), seed, run, selected int32 [n, 5] and within uint8 [n, L] / [R] (bit k: the row lies
+        within cutoff k under transform k). gdt_counts >= Codec.superpose's. iterations and levels are Codec.tm_score's; runs:
+        "all", "tm" or an iterable of "tm" and cutoffs. Reproducible bit for bit."""
+        a, pos_pred, mask_pred, slot = _pair_arrays(pos_true, mask_true, pos_pred, mask_pred, None, length, row_off, slot)
+        from .api import check_gdt_runs, check_tm_search
+        iterations, levels = check_tm_search(iterations, levels)
+        runs = check_gdt_runs(runs)
+        n = a.n
+        d = dict(gdt_counts=np.zeros((n, 5), np.int32), sites=np.zeros(n, np.int32), rot=np.tile(np.eye(3, dtype=np.float32), (n, 5, 1, 1)),
+                 trans=np.zeros((n, 5, 3), np.float32), seed=np.zeros((n, 5), np.int32), run=np.zeros((n, 5), np.int32),
+                 selected=np.zeros((n, 5), np.int32), within=np.zeros(a.lead, np.uint8))
+        if a.n and a.rows:
+            out = CGdtOut(*(d[k].ctypes.data for k in ("gdt_counts", "sites", "rot", "trans", "seed", "run", "selected", "within")))
+            self._call("fcz_gdt", a.packed, a.pos.ctypes.data, a.mask.ctypes.data, pos_pred.ctypes.data, _addr(mask_pred), _addr(a.bound), a.n, a.rows, a.lay,
+                       slot, levels, iterations, runs, ctypes.byref(out))
         return d
 
     def tm_align(self, pos_a: np.ndarray, mask_a: np.ndarray, pos_b=None, mask_b=None, pairs=None, slot: int = 1, *, length_a=None, row_off_a=None,

@@ -41,6 +41,7 @@
 #include "fcz_lddt_atoms.h"
 #include "fcz_superpose.h"
 #include "fcz_tmscore.h"
+#include "fcz_gdt.h"
 #include "fcz_tmalign.h"
 #include "fcz_frames.h"
 #include "fcz_angles.h"
@@ -99,6 +100,7 @@ struct timed_span { std::string name; hipEvent_t a, b; };
 // DSSP_OUT: acc_index, acc_energy, don_index, don_energy, ss, ss_mask of fcz_dssp; SASA_POINTS: the directions of fcz_sasa, SASA_OUT: sasa_points, sasa, sasa_mask;
 // SUPERPOSE_OUT: the seven arrays of a fcz_superpose_out in the struct's order; APPLY_ROT, APPLY_TRANS, APPLY_OUT: the transforms and the moved
 // coordinates of fcz_superpose_apply (its pos and mask go through LDDT_PRED); TM_SEED, TM_SELECTED: the two arrays a fcz_tmscore_out adds to those seven;
+// GDT_OUT: the eight arrays of a fcz_gdt_out in the struct's order;
 // VIOL_OUT .. VIOL_OUT_LAST: the ten arrays of a fcz_violations_out in the struct's order; LDDTA_OUT: the six of a fcz_lddt_atoms_out;
 // TA_SETS: pos, mask, length / row_off of the two fcz_chain_set of fcz_tmalign, TA_PAIRS: its pairs, TA_OUT: the thirteen arrays of a fcz_tmalign_out in the
 // struct's order; TA_DP_*: the transforms, map and aligned of fcz_tmalign_dp
@@ -107,8 +109,8 @@ enum { REC_BLOB, REC_OFF, REC_RES_OFF, REC_ATOM_OFF, REC_X, REC_Y, REC_Z, REC_BF
        SASA_POINTS = 4, SASA_OUT = 10,
        APPLY_ROT = 10, APPLY_TRANS, APPLY_OUT,
        ANGLES_OUT = 10, KEPT_OFF = 13, KEPT_BYTES, KEPT_STATUS, DENSE_CHAIN_INDEX, WINDOW_START = DENSE_CHAIN_INDEX, TM_SEED, TM_SELECTED,
-       VIOL_OUT = 10, LDDTA_OUT = 10, TA_SETS = 0, TA_PAIRS = 6, TA_OUT = 7, TA_DP_ROT = 7, TA_DP_TRANS, TA_DP_MAP, TA_DP_ALIGNED, VIOL_OUT_LAST = 19, POOL_COUNT };
-static_assert(POOL_COUNT == VIOL_OUT_LAST + 1 && DENSE_OUT + 6 == DENSE_CHAIN_INDEX && LDDTA_OUT + 6 <= POOL_COUNT && TM_SELECTED < POOL_COUNT && TA_OUT + 13 <= POOL_COUNT && TA_SETS + 6 == TA_PAIRS &&
+       VIOL_OUT = 10, LDDTA_OUT = 10, GDT_OUT = 10, TA_SETS = 0, TA_PAIRS = 6, TA_OUT = 7, TA_DP_ROT = 7, TA_DP_TRANS, TA_DP_MAP, TA_DP_ALIGNED, VIOL_OUT_LAST = 19, POOL_COUNT };
+static_assert(POOL_COUNT == VIOL_OUT_LAST + 1 && DENSE_OUT + 6 == DENSE_CHAIN_INDEX && LDDTA_OUT + 6 <= POOL_COUNT && TM_SELECTED < POOL_COUNT && GDT_OUT + 8 <= POOL_COUNT && TA_OUT + 13 <= POOL_COUNT && TA_SETS + 6 == TA_PAIRS &&
               TA_PAIRS < TA_OUT && TA_DP_ALIGNED < POOL_COUNT, "the last name of the enum sizes fcz_ctx::pool");
 
 // what the device reports to the host in the middle of a call: one pinned allocation, a member per reader
@@ -163,6 +165,7 @@ struct fcz_ctx {
     dev_buf ta_work;              // fcz_tmalign_dev: two u64, the DPs and DP cells of the last call (fcz_tmalign_last_work)
     dev_buf ta_scratch, ta_dir;   // fcz_tmalign_dev: m u64 item counts, their m + 1 offsets, a double per seed, 2 m u32 site counts; the traceback bits, wa * 256 bytes a resident wavefront
     dev_buf tm_scratch;      // fcz_tmscore_dev / _packed_dev: n u64 item counts, their n + 1 offsets, a double per seed (tm_items_bound), n u32 site counts
+    dev_buf gdt_scratch;     // fcz_gdt_dev / _packed_dev: n u64 item counts, their n + 1 offsets, 5 n u64 best words (count << 32 | ~seed), n u32 site counts
     dev_buf dssp_flags;      // fcz_dssp_labels_dev / _packed_dev: a byte per row (k_dssp_flags -> k_dssp_labels)
     dev_buf fast_scratch;    // decompress, FCZ_NUMERICS_FAST: forward atoms of segments longer than one chunk
     // Staging of the host-pointer entry points. Every entry point that writes it calls claim_staging first. Nothing outlives the call
@@ -188,6 +191,7 @@ struct fcz_ctx {
     //   fcz_lddt_atoms / fcz_lddt_atoms_packed      DENSE_IN 0 .. 3 (pos_true, mask_true, aatype, length / row_off), LDDT_PRED 4 .. 5, LDDTA_OUT 10 .. 15
     //   fcz_superpose / fcz_superpose_packed        DENSE_IN 0, 1, 3 and LDDT_PRED 4 .. 5 as fcz_lddt, SUPERPOSE_OUT 10 .. 16
     //   fcz_tmscore / fcz_tmscore_packed            the same, then TM_SEED 17, TM_SELECTED 18
+    //   fcz_gdt / fcz_gdt_packed                    DENSE_IN 0, 1, 3 and LDDT_PRED 4 .. 5 as fcz_lddt, GDT_OUT 10 .. 17
     //   fcz_superpose_apply[_packed]                LDDT_PRED 4 .. 5 (pos, mask), DENSE_IN 3 (length / row_off), APPLY_ROT 10, APPLY_TRANS 11, APPLY_OUT 12
     //   fcz_dssp / fcz_dssp_packed                  DENSE_IN 0 .. 3 (pos, mask, aatype, length / row_off), DSSP_OUT 10 .. 15 (the four tables, ss, ss_mask)
     //   fcz_frames                                  DENSE_IN 0 .. 3 (pos, mask, aatype, length), DENSE_OUT 10 .. 12 (rot, trans, frame_mask)
@@ -2611,6 +2615,107 @@ int fcz_tmscore_packed(fcz_ctx* ctx, const float* pos_true, const uint8_t* mask_
                        uint32_t n, uint32_t R, int layout, int slot, uint32_t levels, uint32_t iterations, const fcz_tmscore_out* out) {
     if (!tmscore_args_ok(ctx, pos_true, mask_true, pos_pred, layout, slot, R, iterations, out) || !bound_ok(true, row_off, n, R)) return FCZ_E_INVALID_ARG;
     return tmscore_host(ctx, pos_true, mask_true, pos_pred, mask_pred, row_off, true, n, R, layout, slot, levels, iterations, *out);
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------------
+// maximised GDT counts by seeded superposition search (fcz_gdt.h; no counterpart in the reference)
+// ------------------------------------------------------------------------------------------------
+static bool gdt_args_ok(const fcz_ctx* ctx, const float* pos_true, const uint8_t* mask_true, const float* pos_pred, int layout, int slot, uint32_t rows,
+                        uint32_t iterations, uint32_t runs, const fcz_gdt_out* out) {
+    if (!ctx || !pos_true || !mask_true || !pos_pred || !out || !out->gdt_counts) return false;
+    if (fcz_dense_width(layout) <= 0 || slot < 0 || slot >= fcz_dense_width(layout)) return false;
+    return rows <= SUPERPOSE_MAX_ROWS && iterations <= TM_MAX_ITERATIONS && runs != 0 && runs < (1u << GDT_RUNS);
+}
+
+// fcz_gdt_dev (bound_dev is length [n] or NULL, rows = L) and fcz_gdt_packed_dev (bound_dev = row_off [n + 1], rows = R)
+static int gdt_rows(fcz_ctx* ctx, const float* pos_true_dev, const uint8_t* mask_true_dev, const float* pos_pred_dev, const uint8_t* mask_pred_dev,
+                    const uint32_t* bound_dev, bool packed, uint32_t n, uint32_t rows, int layout, int slot, uint32_t levels, uint32_t iterations, uint32_t runs,
+                    const fcz_gdt_out& o) {
+    HIP_TRY(hipSetDevice(ctx->device));
+    const bool fill = packed && rows && o.within;
+    if (n == 0 && !fill) return FCZ_OK;
+    const uint32_t max_blocks = (uint32_t)ctx->n_cu * 16u;
+    span_guard sg(ctx, "gdt");
+    if (fill) {
+        const gdt_fill_args f{bound_dev, n, rows, o.within};
+        hipLaunchKernelGGL(k_chain_fill<gdt_fill_args>, dim3((uint32_t)std::min<uint64_t>(((uint64_t)rows + BLOCK - 1) / BLOCK, max_blocks)), dim3(BLOCK), 0, ctx->stream, f);
+    }
+    if (n) {
+        // k_tm_count as fcz_tmscore_dev launches it: S and the work items of every chain, counted on the device and scanned
+        int rc = ctx->gdt_scratch.ensure(sizeof(uint64_t) * (2 * (size_t)n + 1 + GDT_CUTOFFS * (size_t)n) + sizeof(uint32_t) * (size_t)n);
+        if (rc) return rc;
+        uint64_t* counts = ctx->gdt_scratch.as<uint64_t>();
+        uint64_t* item_off = counts + n;
+        unsigned long long* best = reinterpret_cast<unsigned long long*>(item_off + n + 1);
+        uint32_t* nsites = reinterpret_cast<uint32_t*>(best + GDT_CUTOFFS * (size_t)n);
+        const superpose_args in{pos_true_dev, mask_true_dev, pos_pred_dev, mask_pred_dev, bound_dev, n, rows, (uint32_t)fcz_dense_width(layout), (uint32_t)slot,
+                                nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+        const tmscore_args tc{in, nullptr, nullptr, levels, iterations, nsites, item_off, nullptr, 0};
+        const gdt_args g{in, o.gdt_counts, o.sites, o.rot, o.trans, o.seed, o.run, o.selected, o.within, levels, iterations, runs, nsites, item_off, best};
+        const uint64_t items = tm_items_bound(packed ? (uint64_t)rows : (uint64_t)n * rows, n);
+        const dim3 chains(std::min(grid_for(n, WAVES_PER_BLOCK), max_blocks)), search((uint32_t)std::min<uint64_t>(items, max_blocks)), final_grid(std::min(n, max_blocks));
+        HIP_TRY(hipMemsetAsync(best, 0, sizeof(unsigned long long) * GDT_CUTOFFS * (size_t)n, ctx->stream));
+        if (packed) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tm_count<true>), chains, dim3(BLOCK), 0, ctx->stream, tc, counts);
+        else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tm_count<false>), chains, dim3(BLOCK), 0, ctx->stream, tc, counts);
+        rc = device_scan<uint64_t>(ctx, counts, item_off, n); if (rc) return rc;
+        if (packed) {
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_gdt_search<true>), search, dim3(BLOCK), 0, ctx->stream, g);
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_gdt_final<true>), final_grid, dim3(BLOCK), 0, ctx->stream, g);
+        } else {
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_gdt_search<false>), search, dim3(BLOCK), 0, ctx->stream, g);
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_gdt_final<false>), final_grid, dim3(BLOCK), 0, ctx->stream, g);
+        }
+    }
+    HIP_TRY(hipGetLastError());
+    return FCZ_OK;
+}
+
+// fcz_gdt and fcz_gdt_packed: the host arrays as fcz_superpose's inputs, then GDT_OUT 10 .. 17, the outputs in the struct's order
+static int gdt_host(fcz_ctx* ctx, const float* pos_true, const uint8_t* mask_true, const float* pos_pred, const uint8_t* mask_pred, const uint32_t* bound,
+                    bool packed, uint32_t n, uint32_t rows_per, int layout, int slot, uint32_t levels, uint32_t iterations, uint32_t runs, const fcz_gdt_out& o) {
+    const dense_bytes b(packed, n, rows_per, layout, bound);
+    const size_t c = n;
+    return staged_call(ctx, {{pos_true, b.pos, DENSE_IN}, {mask_true, b.mask, DENSE_IN + 1}, {bound, b.bound, DENSE_IN + 3}, {pos_pred, b.pos, LDDT_PRED},
+                             {mask_pred, b.mask, LDDT_PRED + 1}},
+                       {{o.gdt_counts, 20 * c, GDT_OUT}, {o.sites, 4 * c, GDT_OUT + 1}, {o.rot, 180 * c, GDT_OUT + 2}, {o.trans, 60 * c, GDT_OUT + 3},
+                        {o.seed, 20 * c, GDT_OUT + 4}, {o.run, 20 * c, GDT_OUT + 5}, {o.selected, 20 * c, GDT_OUT + 6}, {o.within, b.rows, GDT_OUT + 7}},
+                       [&](const void* const* in, void* const* out) {
+        const fcz_gdt_out d{(int32_t*)out[0], (int32_t*)out[1], (float*)out[2], (float*)out[3], (int32_t*)out[4], (int32_t*)out[5], (int32_t*)out[6], (uint8_t*)out[7]};
+        return gdt_rows(ctx, (const float*)in[0], (const uint8_t*)in[1], (const float*)in[3], (const uint8_t*)in[4], (const uint32_t*)in[2], packed, n, rows_per,
+                        layout, slot, levels, iterations, runs, d);
+    });
+}
+
+extern "C" {
+
+int fcz_gdt_dev(fcz_ctx* ctx, const float* pos_true_dev, const uint8_t* mask_true_dev, const float* pos_pred_dev, const uint8_t* mask_pred_dev,
+                const uint32_t* length_dev, uint32_t n, uint32_t L, int layout, int slot, uint32_t levels, uint32_t iterations, uint32_t runs,
+                const fcz_gdt_out* out_dev) {
+    if (!gdt_args_ok(ctx, pos_true_dev, mask_true_dev, pos_pred_dev, layout, slot, L, iterations, runs, out_dev) || !bound_ok(false, length_dev, n, L))
+        return FCZ_E_INVALID_ARG;
+    return gdt_rows(ctx, pos_true_dev, mask_true_dev, pos_pred_dev, mask_pred_dev, length_dev, false, n, L, layout, slot, levels, iterations, runs, *out_dev);
+}
+
+int fcz_gdt_packed_dev(fcz_ctx* ctx, const float* pos_true_dev, const uint8_t* mask_true_dev, const float* pos_pred_dev, const uint8_t* mask_pred_dev,
+                       const uint32_t* row_off_dev, uint32_t n, uint32_t R, int layout, int slot, uint32_t levels, uint32_t iterations, uint32_t runs,
+                       const fcz_gdt_out* out_dev) {
+    if (!gdt_args_ok(ctx, pos_true_dev, mask_true_dev, pos_pred_dev, layout, slot, R, iterations, runs, out_dev) || !bound_ok(true, row_off_dev, n, R))
+        return FCZ_E_INVALID_ARG;
+    return gdt_rows(ctx, pos_true_dev, mask_true_dev, pos_pred_dev, mask_pred_dev, row_off_dev, true, n, R, layout, slot, levels, iterations, runs, *out_dev);
+}
+
+int fcz_gdt(fcz_ctx* ctx, const float* pos_true, const uint8_t* mask_true, const float* pos_pred, const uint8_t* mask_pred, const uint32_t* length,
+            uint32_t n, uint32_t L, int layout, int slot, uint32_t levels, uint32_t iterations, uint32_t runs, const fcz_gdt_out* out) {
+    if (!gdt_args_ok(ctx, pos_true, mask_true, pos_pred, layout, slot, L, iterations, runs, out) || !bound_ok(false, length, n, L)) return FCZ_E_INVALID_ARG;
+    return gdt_host(ctx, pos_true, mask_true, pos_pred, mask_pred, length, false, n, L, layout, slot, levels, iterations, runs, *out);
+}
+
+int fcz_gdt_packed(fcz_ctx* ctx, const float* pos_true, const uint8_t* mask_true, const float* pos_pred, const uint8_t* mask_pred, const uint32_t* row_off,
+                   uint32_t n, uint32_t R, int layout, int slot, uint32_t levels, uint32_t iterations, uint32_t runs, const fcz_gdt_out* out) {
+    if (!gdt_args_ok(ctx, pos_true, mask_true, pos_pred, layout, slot, R, iterations, runs, out) || !bound_ok(true, row_off, n, R)) return FCZ_E_INVALID_ARG;
+    return gdt_host(ctx, pos_true, mask_true, pos_pred, mask_pred, row_off, true, n, R, layout, slot, levels, iterations, runs, *out);
 }
 
 }  // extern "C"

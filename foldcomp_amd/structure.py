@@ -996,6 +996,11 @@ class CTmScoreOut(ctypes.Structure):
     _fields_ = CSuperposeOut._fields_ + [("seed", ctypes.c_void_p), ("selected", ctypes.c_void_p)]
 
 
+class CGdtOut(ctypes.Structure):
+    """fcz_gdt_out (include/fcz_hip.h): the outputs of the maximised-GDT calls; all but gdt_counts may be None"""
+    _fields_ = [(k, ctypes.c_void_p) for k in ("gdt_counts", "sites", "rot", "trans", "seed", "run", "selected", "within")]
+
+
 class CChainSet(ctypes.Structure):
     """fcz_chain_set (include/fcz_hip.h): one set of chains of the alignment calls, padded (length or None, rows = L) or packed (row_off, rows = R)"""
     _fields_ = [("pos", ctypes.c_void_p), ("mask", ctypes.c_void_p), ("length", ctypes.c_void_p), ("row_off", ctypes.c_void_p),

@@ -22,6 +22,9 @@
                                    apply=True adds pos_aligned; apply_transform(pos, rot, trans, batch) is that step alone
     tm_score(pred, true, atom="CA", apply=False, iterations=20, levels=None) -> the same dict at the superposition that MAXIMISES the
                                    TM-score over a seeded iterative search, plus seed [n] and selected [n]
+    gdt(pred, true, atom="CA", iterations=20, levels=None, runs="all") -> dict(gdt_counts [n, 5], gdt_ts, gdt_ha, sites [n], rot
+                                   [n, 5, 3, 3], trans [n, 5, 3], seed, run, selected [n, 5], within [..] uint8): the MAXIMISED GDT, per
+                                   cutoff the largest count over the same seeds searched with six cut schedules, and its superposition
     backbone_hbonds(either dict, or the tensors as keywords) -> dict(hbond_acc_index, hbond_acc_energy, hbond_don_index, hbond_don_energy
                                    [.., 2]): DSSP's four H-bond columns, the two best acceptors and donors of every residue
     secondary_structure(either dict, or the tensors as keywords) -> dict(ss [..] uint8, ss_mask [..] bool, the four tables): the DSSP
@@ -54,9 +57,9 @@ import numpy as np
 from . import _lib, api, fczfile
 from ._aa_tables import RES1
 from .codec import ANGLE_COLUMNS, WIDTH_LAYOUTS, Codec, dense_layout
-from .structure import CAtomsOut, CDenseIn, CDenseOut, CLddtAtomsOut, CPackedOut, CSuperposeOut, CTmScoreOut, CViolationsOut, CChainSet, CTmAlignOut, CTmAlignParams, TM_ALIGN_OUTPUTS
+from .structure import CAtomsOut, CDenseIn, CDenseOut, CLddtAtomsOut, CPackedOut, CSuperposeOut, CTmScoreOut, CGdtOut, CViolationsOut, CChainSet, CTmAlignOut, CTmAlignParams, TM_ALIGN_OUTPUTS
 
-__all__ = ["decode_tensors", "encode_tensors", "decode_angles", "crop_starts", "neighbor_graph", "rigid_frames", "lddt", "lddt_atoms", "superpose", "tm_score", "tm_align", "apply_transform",
+__all__ = ["decode_tensors", "encode_tensors", "decode_angles", "crop_starts", "neighbor_graph", "rigid_frames", "lddt", "lddt_atoms", "superpose", "tm_score", "gdt", "tm_align", "apply_transform",
            "backbone_hbonds", "secondary_structure", "solvent_accessibility", "violations"]
 
 
@@ -779,7 +782,8 @@ def superpose(pred, true, *, atom="CA", apply: bool = False, codec: Optional[Cod
         rmsd [n] float32                      the RMSD of the sites after the superposition
         sites [n] int32                       the number of sites
         dev [n, L] / [R] float32              every site's deviation after the superposition, 0 where the row is no site
-        gdt_counts [n, 5] int32               the sites with dev <= 0.5, 1, 2, 4, 8
+        gdt_counts [n, 5] int32               the sites with dev <= 0.5, 1, 2, 4, 8 AT THIS SUPERPOSITION: GDT is NOT maximised here
+                                              (`gdt` searches for the largest count per cutoff, the published kind of number)
         gdt_ts, gdt_ha [n] float32            the mean fraction at 1, 2, 4, 8 and at 0.5, 1, 2, 4 (in float64 from the integers)
         tm [n] float32                        the TM-score AT THIS SUPERPOSITION, normalised by the sites: a lower bound of what
                                               TM-score programs report, which search for the superposition that maximises it
@@ -805,10 +809,53 @@ def tm_score(pred, true, *, atom="CA", apply: bool = False, iterations: int = 20
         seed [n] int32          the number of the winning seed (0: the whole chain)
         selected [n] int32      the sites the winning fit was made on
     levels=k keeps only the first k fragment lengths (None: all); levels=1, iterations=0 is superpose, bit for bit. GDT is NOT
-    maximised: gdt_counts are the counts at the TM-maximising superposition. apply=True adds pos_aligned as in superpose.
+    maximised here: gdt_counts are the counts at the TM-maximising superposition, and `gdt` searches for the maximum per cutoff. apply=True adds pos_aligned as in superpose.
     It is NOT differentiable. Cost: the seeds times a handful of superpositions per chain, where superpose does one.
     atom, shapes, iterations and levels are checked first, without torch or a device (api.check_tm_score)."""
     return _superpose(pred, true, atom, apply, codec, "tm_score", (iterations, levels))
+
+
+def gdt(pred, true, *, atom="CA", iterations: int = 20, levels=None, runs="all", codec: Optional[Codec] = None) -> dict:
+    """predicted coordinates against true ones, both dense tensors on the GPU -> per chain the MAXIMISED GDT counts: for each cutoff of
+    0.5, 1, 2, 4 and 8 A (GDT_CUTOFFS) the largest number of sites that some superposition of a seeded search brings under it, the
+    kind of number LGA and the TM-score program print and CASP tables hold.
+
+    superpose counts the five cutoffs at the least-squares fit and tm_score at the TM-maximising fit; GDT is defined as a maximum
+    per cutoff. Every seed of tm_score's schedule (levels) is searched in up to six runs of at most `iterations` rounds each: one
+    with tm_score's cuts ("tm") and one per cutoff c with the constant cut c, the selection of a round being the sites within the
+    cut of the target under the fit before. Every fit visited is scored by its five counts, and per cutoff the largest wins, of equal
+    ones the lowest seed, then run, then round. The definition, deterministic to the bit, is fcz_gdt_dev's in include/fcz_hip.h;
+    the inputs, the site rule and `atom` are superpose's. runs: "all"; "tm" (what the TM-score program's GDT lines amount to, at
+    about tm_score's cost); or an iterable of "tm" and cutoffs. Per chain:
+        gdt_counts [n, 5] int32               the maxima; >= superpose's, and with the "tm" run >= tm_score's
+        gdt_ts, gdt_ha [n] float32            the mean fraction at 1, 2, 4, 8 and at 0.5, 1, 2, 4 (in float64 from the integers)
+        sites [n] int32                       the number of sites
+        rot [n, 5, 3, 3], trans [n, 5, 3]     float32: the superposition behind each cutoff's count, x_true ~ rot @ x_pred + trans
+        seed, run, selected [n, 5] int32      the winning seed, its run (0: "tm", 1 + k: cutoff k) and the sites that fit was made on
+        within [n, L] / [R] uint8             bit k: the row is a site within cutoff k under transform k; its popcount is gdt_counts
+    There is no `apply`, as there are five transforms per chain:
+    apply_transform(pos, out["rot"][:, k].contiguous(), out["trans"][:, k].contiguous(), batch) moves a prediction by the k-th.
+    It is NOT differentiable. Cost with runs="all": several times tm_score's. The arguments are checked first, without torch or a
+    device (api.check_gdt)."""
+    x, ppos, pmask, (slot, iterations, levels, runs) = _pair_inputs(
+        "gdt", pred, true, codec, lambda shape, pshape, mshape, t: api.check_gdt(atom, shape, pshape, mshape, iterations, levels, runs))
+    if x.rows > 2 ** 31 - 1:
+        raise ValueError("sites must fit int32: at most 2^31 - 1 rows per chain")
+    torch, dev, n = x.torch, x.dev, x.n
+    i32 = lambda *shape: torch.zeros(shape, dtype=torch.int32, device=dev)
+    out = dict(gdt_counts=i32(n, 5), sites=i32(n), rot=torch.eye(3, dtype=torch.float32, device=dev).repeat(n, 5, 1, 1),
+               trans=torch.zeros((n, 5, 3), dtype=torch.float32, device=dev), seed=i32(n, 5), run=i32(n, 5), selected=i32(n, 5),
+               within=torch.zeros(x.lead, dtype=torch.uint8, device=dev))
+    if n and x.rows:                                                          # (chains of no rows keep what a chain without sites gets)
+        s = CGdtOut(*(out[k].data_ptr() for k in ("gdt_counts", "sites", "rot", "trans", "seed", "run", "selected", "within")))
+        torch.cuda.current_stream(dev).synchronize()
+        _call(x.codec, "fcz_gdt", x.is_packed, x.pos.data_ptr(), x.mask.data_ptr(), ppos.data_ptr(), _ptr(pmask), _ptr(x.bound), n, x.rows, x.lay, slot,
+              levels, iterations, runs, ctypes.byref(s))
+        x.codec.synchronize()
+    counts, S = out["gdt_counts"].to(torch.float64), out["sites"].to(torch.float64).clamp(min=1.0)
+    out["gdt_ts"] = (counts[:, 1:5].sum(dim=1) / (4.0 * S)).to(torch.float32)
+    out["gdt_ha"] = (counts[:, 0:4].sum(dim=1) / (4.0 * S)).to(torch.float32)
+    return out
 
 
 def tm_align(a, b=None, pairs=None, *, atom="CA", fragments: bool = True, refine: int = 4, dp_rounds: int = 20, gaps=(0.6, 0.0), iterations: int = 20,

@@ -26,6 +26,7 @@
  *   (none: `rmsd` compares two files unsuperposed)         fcz_superpose_dev / fcz_superpose_packed_dev, fcz_superpose_apply_dev /
  *                                                          fcz_superpose_apply_packed_dev and their host forms
  *   (none: no TM-score)                                    fcz_tmscore_dev / fcz_tmscore_packed_dev and their host forms
+ *   (none: no GDT)                                         fcz_gdt_dev / fcz_gdt_packed_dev and their host forms
  *   (none: no rigid frames of the decoded chain)           fcz_frames_dev / fcz_frames
  *   Foldcomp::decompress, the dequantisation :784-804     fcz_angles_dev / fcz_angles_packed_dev, fcz_decompress_angles[_packed],
  *                                                          fcz_angles_window_dev / fcz_decompress_angles_window
@@ -894,6 +895,67 @@ int fcz_tmscore(fcz_ctx* ctx, const float* pos_true, const uint8_t* mask_true, c
 int fcz_tmscore_packed(fcz_ctx* ctx, const float* pos_true, const uint8_t* mask_true, const float* pos_pred,
                        const uint8_t* mask_pred, const uint32_t* row_off, uint32_t n, uint32_t R, int layout, int slot,
                        uint32_t levels, uint32_t iterations, const fcz_tmscore_out* out);
+
+/* ---- maximised GDT-TS / GDT-HA: a seeded superposition search per cutoff ---------------------------------- */
+/* fcz_superpose_dev counts the sites under 0.5, 1, 2, 4 and 8 A at the least-squares fit and fcz_tmscore_dev at the TM-maximising
+ * fit. GDT is defined as a MAXIMUM: for each cutoff the largest number of residues that some superposition brings under it, which
+ * is what LGA and the TM-score program print. These calls search for it per chain and per cutoff, for a whole batch on the device.
+ * The reference has no such output. The inputs, the two forms (padded / packed), the layouts and slots, the site rule, the float64
+ * arithmetic (every operation rounded, no FMA) and the refusals are those of fcz_superpose_dev; the seeds, `levels`,
+ * iterations <= 64 and the "one seed" procedure are those of fcz_tmscore_dev. This is the definition; it is deterministic, so an
+ * implementation is checked against it, not against LGA.
+ * Per chain with S sites and the cutoffs c = (0.5, 1, 2, 4, 8):
+ *   runs               Every seed is searched in up to six runs, in this order. Each run starts from the seed's fragment and follows
+ *                      fcz_tmscore_dev's rounds verbatim: the selection {j : dev_j < cut}, cut += 0.5 while it holds fewer than
+ *                      min(3, S) sites, +inf after 16 384 steps, stop when the selection repeats or after `iterations` rounds. Only
+ *                      the cut differs. Run 0 has the TM cuts, d_search - 1 in round 1 and d_search + 1 later; run 1 + k has the
+ *                      constant cut c_k in every round. `runs` is a bit mask of the six (bit r = run r).
+ *   score of a fit     g_k = #{j : dev_j <= c_k} over all S sites, compared in float64, k = 0 .. 4. No TM sum is formed.
+ *   result, cutoff k   the (seed, run, round) with the largest g_k among all fits visited; of equal ones the lowest seed, then the
+ *                      lowest run, then the earliest round. Round 0 of every run of a seed is one and the same fit (it belongs to
+ *                      the lowest run of the mask), so an implementation may skip whatever cannot change the result.
+ * Outputs per chain: gdt_counts [n][5] int32, the five maxima (GDT-TS is the mean of the fractions at 1, 2, 4, 8 and GDT-HA of those
+ * at 0.5, 1, 2, 4: integers over S, left to the caller); sites [n] int32; rot [n][5][3][3] and trans [n][5][3] float32, rounded
+ * once from float64, the superposition behind each cutoff's count (x_true ~ rot @ x_pred + trans); seed, run, selected [n][5]
+ * int32: the winning seed's number, the run, and the size of the selection the winning fit was made on. Per row: within [rows]
+ * uint8, bit k set iff the row is a site and its deviation under transform k, from the float64 transform, is <= c_k; 0 where the
+ * row is no site, lies behind length, or (packed) is covered by no chain, as dev is. The popcount of bit k over a chain is
+ * gdt_counts[k]. S = 0: identities and zeros. All outputs but gdt_counts may be NULL. Every byte of what is given is written
+ * whatever the inputs hold, and nothing outside it.
+ * It follows that levels = 1, iterations = 0 gives fcz_superpose_dev's gdt_counts, and its rot / trans in all five places; that
+ * gdt_counts >= fcz_superpose_dev's elementwise for any arguments; that with bit 0 of `runs` set gdt_counts >= fcz_tmscore_dev's at
+ * the same levels / iterations; and that gdt_counts[k] <= gdt_counts[k + 1] (a fit's own counts ascend). The result depends on
+ * neither the launch geometry nor the form: two calls, and padded against packed, give the same bytes; unlike fcz_tmscore_dev that
+ * also holds for packed ranges that overlap, because no scratch scales with the seeds. Work: the seeds times up to six runs of a
+ * handful of superpositions each. Scratch in the ctx: 7 n + 1 words of 8 bytes and n of 4.
+ * Enqueued on the ctx stream, no synchronisation. FCZ_E_INVALID_ARG with nothing launched: what fcz_tmscore_dev refuses (but rot and
+ * trans may be NULL), and runs == 0, runs >= 64, NULL out->gdt_counts. FCZ_E_NOMEM: no room for the scratch. n == 0: FCZ_OK (packed,
+ * n == 0 < R: `within` is filled). The time goes to a group of its own, "gdt". */
+#define FCZ_GDT_RUNS_ALL 63u   /* the TM cuts and the five constant cuts */
+#define FCZ_GDT_RUNS_TM  1u    /* run 0 alone: what a TM-score program's GDT lines amount to, at about fcz_tmscore_dev's cost */
+typedef struct fcz_gdt_out {
+    int32_t* gdt_counts;    /* [n][5] */
+    int32_t* sites;         /* [n] optional */
+    float*   rot;           /* [n][5][3][3] optional */
+    float*   trans;         /* [n][5][3] optional */
+    int32_t* seed;          /* [n][5] optional */
+    int32_t* run;           /* [n][5] optional */
+    int32_t* selected;      /* [n][5] optional */
+    uint8_t* within;        /* [n][L] / [R] optional */
+} fcz_gdt_out;
+int fcz_gdt_dev(fcz_ctx* ctx, const float* pos_true_dev, const uint8_t* mask_true_dev, const float* pos_pred_dev,
+                const uint8_t* mask_pred_dev, const uint32_t* length_dev, uint32_t n, uint32_t L, int layout, int slot,
+                uint32_t levels, uint32_t iterations, uint32_t runs, const fcz_gdt_out* out_dev);
+int fcz_gdt_packed_dev(fcz_ctx* ctx, const float* pos_true_dev, const uint8_t* mask_true_dev, const float* pos_pred_dev,
+                       const uint8_t* mask_pred_dev, const uint32_t* row_off_dev, uint32_t n, uint32_t R, int layout, int slot,
+                       uint32_t levels, uint32_t iterations, uint32_t runs, const fcz_gdt_out* out_dev);
+/* Host-pointer conveniences: the same arrays on the host, staged through the ctx like fcz_superpose; synchronous. */
+int fcz_gdt(fcz_ctx* ctx, const float* pos_true, const uint8_t* mask_true, const float* pos_pred, const uint8_t* mask_pred,
+            const uint32_t* length, uint32_t n, uint32_t L, int layout, int slot, uint32_t levels, uint32_t iterations, uint32_t runs,
+            const fcz_gdt_out* out);
+int fcz_gdt_packed(fcz_ctx* ctx, const float* pos_true, const uint8_t* mask_true, const float* pos_pred, const uint8_t* mask_pred,
+                   const uint32_t* row_off, uint32_t n, uint32_t R, int layout, int slot, uint32_t levels, uint32_t iterations,
+                   uint32_t runs, const fcz_gdt_out* out);
 
 /* ---- TM-align-style structural alignment of chain pairs ------------------------------------------------- */
 /* Everything above compares two tensors row for row. These calls compare two DIFFERENT chains, of different lengths and with the

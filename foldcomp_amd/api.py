@@ -392,6 +392,15 @@ def check_lddt(cutoff, thresholds, atom, width=None):
         return slot, float(np.float32(cutoff)), tuple(float(np.float32(v)) for v in th)
 
 
+def check_lddt_soft(cutoff, thresholds, atom, width=None):
+    """the argument rules of smooth_lddt that need no tensors' device and no GPU -> (slot, cutoff, thresholds): check_lddt's, and
+    every threshold finite as float32 (a sigmoid about an infinite threshold is a constant, which has no place in a loss)"""
+    slot, cutoff, th = check_lddt(cutoff, thresholds, atom, width)
+    if not all(np.isfinite(v) for v in th):
+        raise ValueError(f"thresholds must be four finite numbers (as float32), not {thresholds!r}")
+    return slot, cutoff, th
+
+
 _LAYOUT_WIDTHS = {"atom37": (0, 37), "atom14": (1, 14), "backbone4": (2, 4)}  # name -> (enum fcz_dense_layout, A)
 
 

@@ -348,6 +348,43 @@ class Codec:
                        float(cutoff), _addr(th), score.ctypes.data, pairs.ctypes.data, hits.ctypes.data)
         return dict(score=score, pairs=pairs, hits=hits)
 
+    def _lddt_soft_inputs(self, pos_true, mask_true, pos_pred, mask_pred, slot, length, row_off, cutoff, thresholds):
+        """the prelude of lddt_soft and lddt_soft_grad -> (_Arrays of true, pos_pred, mask_pred, slot, cutoff, thresholds float32 [4] or None)"""
+        from . import api
+        a, pos_pred, mask_pred, slot = _pair_arrays(pos_true, mask_true, pos_pred, mask_pred, None, length, row_off, slot,
+                                                    limit=(2 ** 29, "at most 2^29 rows per chain"))
+        _, cutoff, th = api.check_lddt_soft(cutoff, thresholds, slot, a.A)
+        return a, pos_pred, mask_pred, slot, cutoff, None if thresholds is None else np.asarray(th, np.float32)
+
+    def lddt_soft(self, pos_true: np.ndarray, mask_true: np.ndarray, pos_pred: np.ndarray, mask_pred=None, slot: int = 1, length=None, row_off=None,
+                  cutoff: float = 15.0, thresholds=None):
+        """two sets of dense arrays of one shape on the host -> the smooth lDDT sums of `pred` against `true` on the sites at `slot`
+        (fcz_lddt_soft, or fcz_lddt_soft_packed when row_off is given): soft float32 [n, L] / [R], the sum over a row's pairs of
+        1/4 sum_k sigmoid(t_k - |d_true - d_pred|) in float32 in ascending row order, and pairs int32, which is Codec.lddt's. The
+        arrays are Codec.lddt's; thresholds must be finite. soft / pairs is the per-residue smooth lDDT."""
+        a, pos_pred, mask_pred, slot, cutoff, th = self._lddt_soft_inputs(pos_true, mask_true, pos_pred, mask_pred, slot, length, row_off, cutoff, thresholds)
+        soft = np.zeros(a.lead, np.float32)
+        pairs = np.zeros(a.lead, np.int32)
+        if soft.size:
+            self._call("fcz_lddt_soft", a.packed, a.pos.ctypes.data, a.mask.ctypes.data, pos_pred.ctypes.data, _addr(mask_pred), _addr(a.bound), a.n, a.rows, a.lay,
+                       slot, cutoff, _addr(th), soft.ctypes.data, pairs.ctypes.data)
+        return dict(soft=soft, pairs=pairs)
+
+    def lddt_soft_grad(self, pos_true: np.ndarray, mask_true: np.ndarray, pos_pred: np.ndarray, weight: np.ndarray, mask_pred=None, slot: int = 1, length=None,
+                       row_off=None, cutoff: float = 15.0, thresholds=None):
+        """the gradient of sum_i weight[i] * soft[i] of lddt_soft with respect to pos_pred[.., slot, :] (fcz_lddt_soft_grad, or
+        fcz_lddt_soft_grad_packed when row_off is given): float32 [n, L, 3] / [R, 3], 0 where a row is no site. weight float32
+        [n, L] / [R]. Gathered per row in a fixed order without atomics: reproducible bit for bit."""
+        a, pos_pred, mask_pred, slot, cutoff, th = self._lddt_soft_inputs(pos_true, mask_true, pos_pred, mask_pred, slot, length, row_off, cutoff, thresholds)
+        weight = np.ascontiguousarray(weight, np.float32)
+        if weight.shape != a.lead:
+            raise ValueError(f"weight must be float32 {a.lead}, not {weight.shape}")
+        grad = np.zeros(a.lead + (3,), np.float32)
+        if grad.size:
+            self._call("fcz_lddt_soft_grad", a.packed, a.pos.ctypes.data, a.mask.ctypes.data, pos_pred.ctypes.data, _addr(mask_pred), _addr(a.bound), a.n, a.rows,
+                       a.lay, slot, cutoff, _addr(th), weight.ctypes.data, grad.ctypes.data)
+        return grad
+
     def lddt_atoms(self, pos_true: np.ndarray, mask_true: np.ndarray, pos_pred: np.ndarray, mask_pred=None, aatype=None, length=None, row_off=None, *,
                    cutoff: float = 15.0, thresholds=None, swaps="alphafold", per_atom: bool = False):
         """two sets of dense arrays of one shape on the host -> the all-atom lDDT of `pred` against `true` after the symmetric

@@ -35,6 +35,7 @@
 #include "fcz_undense.h"
 #include "fcz_knn.h"
 #include "fcz_lddt.h"
+#include "fcz_lddt_soft.h"
 #include "fcz_dssp.h"
 #include "fcz_sasa.h"
 #include "fcz_violations.h"
@@ -96,7 +97,8 @@ struct timed_span { std::string name; hipEvent_t a, b; };
 // arrays of a fcz_chain_batch, the 10 of a fcz_dense_in (slot 3, length, holds row_off [n + 1] in the packed form), the 6 of a
 // fcz_dense_out in the struct's order, DENSE_CHAIN_INDEX: the chain_index a fcz_packed_out adds to them; ANGLES_OUT: the angles, their mask and
 // (windowed form) aatype; WINDOW_START: the n u32 starts of a windowed host call; KEPT_*: the records a *_begin call leaves for its fetch
-// (C + 1 u64 offsets, the bytes, C i32 status); LDDT_PRED: pos and mask of the second tensor batch of fcz_lddt, LDDT_OUT: score, pairs, hits;
+// (C + 1 u64 offsets, the bytes, C i32 status); LDDT_PRED: pos and mask of the second tensor batch of fcz_lddt, LDDT_OUT: score, pairs, hits
+// (fcz_lddt_soft: soft, pairs; fcz_lddt_soft_grad: grad), LDDT_WEIGHT: the row weights of fcz_lddt_soft_grad;
 // DSSP_OUT: acc_index, acc_energy, don_index, don_energy, ss, ss_mask of fcz_dssp; SASA_POINTS: the directions of fcz_sasa, SASA_OUT: sasa_points, sasa, sasa_mask;
 // SUPERPOSE_OUT: the seven arrays of a fcz_superpose_out in the struct's order; APPLY_ROT, APPLY_TRANS, APPLY_OUT: the transforms and the moved
 // coordinates of fcz_superpose_apply (its pos and mask go through LDDT_PRED); TM_SEED, TM_SELECTED: the two arrays a fcz_tmscore_out adds to those seven;
@@ -105,7 +107,7 @@ struct timed_span { std::string name; hipEvent_t a, b; };
 // TA_SETS: pos, mask, length / row_off of the two fcz_chain_set of fcz_tmalign, TA_PAIRS: its pairs, TA_OUT: the thirteen arrays of a fcz_tmalign_out in the
 // struct's order; TA_DP_*: the transforms, map and aligned of fcz_tmalign_dp
 enum { REC_BLOB, REC_OFF, REC_RES_OFF, REC_ATOM_OFF, REC_X, REC_Y, REC_Z, REC_BFAC, REC_RES_CODE, REC_ATOM_CODE,
-       FILES_TEXT = 0, FILES_OFF, FILES_NAMES, FILES_NAME_OFF, FILES_STEM_LEN, BATCH_IN = 0, DENSE_IN = 0, LDDT_PRED = 4, DENSE_OUT = 10, LDDT_OUT = 10, SUPERPOSE_OUT = 10, DSSP_OUT = 10,
+       FILES_TEXT = 0, FILES_OFF, FILES_NAMES, FILES_NAME_OFF, FILES_STEM_LEN, BATCH_IN = 0, DENSE_IN = 0, LDDT_PRED = 4, LDDT_WEIGHT = 6, DENSE_OUT = 10, LDDT_OUT = 10, SUPERPOSE_OUT = 10, DSSP_OUT = 10,
        SASA_POINTS = 4, SASA_OUT = 10,
        APPLY_ROT = 10, APPLY_TRANS, APPLY_OUT,
        ANGLES_OUT = 10, KEPT_OFF = 13, KEPT_BYTES, KEPT_STATUS, DENSE_CHAIN_INDEX, WINDOW_START = DENSE_CHAIN_INDEX, TM_SEED, TM_SELECTED,
@@ -188,6 +190,8 @@ struct fcz_ctx {
     //   fcz_compress_dense_packed_begin[_dev]       as the two above (DENSE_IN 3 = row_off)     the same
     //   fcz_knn / fcz_knn_packed                    DENSE_IN 0, 1, 3 (pos, mask, length / row_off), DENSE_OUT 10 .. 11 (index, dist)
     //   fcz_lddt / fcz_lddt_packed                  DENSE_IN 0, 1, 3 (pos_true, mask_true, length / row_off), LDDT_PRED 4 .. 5 (pos_pred, mask_pred), LDDT_OUT 10 .. 12
+    //   fcz_lddt_soft / fcz_lddt_soft_packed        the inputs of fcz_lddt, LDDT_OUT 10 .. 11 (soft, pairs)
+    //   fcz_lddt_soft_grad / _grad_packed           the inputs of fcz_lddt, LDDT_WEIGHT 6, LDDT_OUT 10 (grad)
     //   fcz_lddt_atoms / fcz_lddt_atoms_packed      DENSE_IN 0 .. 3 (pos_true, mask_true, aatype, length / row_off), LDDT_PRED 4 .. 5, LDDTA_OUT 10 .. 15
     //   fcz_superpose / fcz_superpose_packed        DENSE_IN 0, 1, 3 and LDDT_PRED 4 .. 5 as fcz_lddt, SUPERPOSE_OUT 10 .. 16
     //   fcz_tmscore / fcz_tmscore_packed            the same, then TM_SEED 17, TM_SELECTED 18
@@ -1896,6 +1900,140 @@ int fcz_lddt_packed(fcz_ctx* ctx, const float* pos_true, const uint8_t* mask_tru
     if (!lddt_args_ok(ctx, pos_true, mask_true, pos_pred, layout, slot, cutoff, thresholds, R, score, pairs, hits) || !bound_ok(true, row_off, n, R))
         return FCZ_E_INVALID_ARG;
     return lddt_host(ctx, pos_true, mask_true, pos_pred, mask_pred, row_off, true, n, R, layout, slot, cutoff, thresholds, score, pairs, hits);
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------------
+// smooth lDDT and its gradient (fcz_lddt_soft.h; no counterpart in the reference)
+// ------------------------------------------------------------------------------------------------
+// fcz_lddt_dev's rules with finite thresholds; the outputs are checked by the caller. rows: L (padded) or R (packed)
+static bool lddt_soft_args_ok(const fcz_ctx* ctx, const float* pos_true, const uint8_t* mask_true, const float* pos_pred, int layout, int slot, float cutoff,
+                              const float* thresholds, uint32_t rows) {
+    if (!ctx || !pos_true || !mask_true || !pos_pred) return false;
+    if (fcz_dense_width(layout) <= 0 || slot < 0 || slot >= fcz_dense_width(layout)) return false;
+    if (!std::isfinite(cutoff) || !(cutoff > 0.0f) || rows > LDDT_MAX_ROWS) return false;
+    if (thresholds) for (int t = 0; t < 4; t++) if (!std::isfinite(thresholds[t])) return false;
+    return true;
+}
+
+// the device forms of the value (weight_dev and grad_dev NULL) and of the gradient (soft_dev and pairs_dev NULL); bound_dev is length [n]
+// or NULL with rows = L, or row_off [n + 1] with rows = R
+static int lddt_soft_rows(fcz_ctx* ctx, const float* pos_true_dev, const uint8_t* mask_true_dev, const float* pos_pred_dev, const uint8_t* mask_pred_dev,
+                          const uint32_t* bound_dev, bool packed, uint32_t n, uint32_t rows, int layout, int slot, float cutoff, const float* thresholds,
+                          float* soft_dev, int32_t* pairs_dev, const float* weight_dev, float* grad_dev) {
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (rows == 0 || (n == 0 && !packed)) return FCZ_OK;
+    const float* th = thresholds ? thresholds : LDDT_THRESHOLDS;
+    const uint32_t A = (uint32_t)fcz_dense_width(layout);
+    const float c2 = lddt_c2(cutoff);
+    chain_tiles ct(ctx, packed, n, rows);
+    int rc = ct.reserve(); if (rc) return rc;
+    if (grad_dev) {
+        const lddt_soft_grad_args g{pos_true_dev, mask_true_dev, pos_pred_dev, mask_pred_dev, bound_dev, n, rows, A, (uint32_t)slot, c2, th[0], th[1], th[2], th[3],
+                                    weight_dev, grad_dev};
+        span_guard sg(ctx, "lddt_soft_grad");
+        return ct.run(bound_dev, [&] { hipLaunchKernelGGL(k_chain_fill<lddt_soft_grad_args>, ct.fill_grid(rows), dim3(BLOCK), 0, ctx->stream, g); },
+                      [&](auto P, dim3 grid, const uint64_t* tile_off, uint32_t tiles_per_entry, uint64_t n_padded) {
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_lddt_soft_grad<decltype(P)::value>), grid, dim3(BLOCK), 0, ctx->stream, g, tile_off, tiles_per_entry, n_padded);
+        });
+    }
+    const lddt_soft_args g{pos_true_dev, mask_true_dev, pos_pred_dev, mask_pred_dev, bound_dev, n, rows, A, (uint32_t)slot, c2, th[0], th[1], th[2], th[3],
+                           soft_dev, pairs_dev};
+    span_guard sg(ctx, "lddt_soft");
+    return ct.run(bound_dev, [&] { hipLaunchKernelGGL(k_chain_fill<lddt_soft_args>, ct.fill_grid(rows), dim3(BLOCK), 0, ctx->stream, g); },
+                  [&](auto P, dim3 grid, const uint64_t* tile_off, uint32_t tiles_per_entry, uint64_t n_padded) {
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_lddt_soft<decltype(P)::value>), grid, dim3(BLOCK), 0, ctx->stream, g, tile_off, tiles_per_entry, n_padded);
+    });
+}
+
+// the host forms: the host arrays through DENSE_IN 0, 1, 3, LDDT_PRED 4, 5, LDDT_WEIGHT 6 and LDDT_OUT 10 .. 11 (soft, pairs) or 10 (grad)
+static int lddt_soft_host(fcz_ctx* ctx, const float* pos_true, const uint8_t* mask_true, const float* pos_pred, const uint8_t* mask_pred, const uint32_t* bound,
+                          bool packed, uint32_t n, uint32_t rows_per, int layout, int slot, float cutoff, const float* thresholds, float* soft, int32_t* pairs,
+                          const float* weight, float* grad) {
+    const dense_bytes b(packed, n, rows_per, layout, bound);
+    const size_t no = b.rows * 4;
+    auto run = [&](const void* const* in, void* const* out) {
+        return lddt_soft_rows(ctx, (const float*)in[0], (const uint8_t*)in[1], (const float*)in[3], (const uint8_t*)in[4], (const uint32_t*)in[2], packed, n, rows_per,
+                              layout, slot, cutoff, thresholds, grad ? nullptr : (float*)out[0], grad ? nullptr : (int32_t*)out[1], (const float*)in[5],
+                              grad ? (float*)out[0] : nullptr);
+    };
+    if (grad)
+        return staged_call(ctx, {{pos_true, b.pos, DENSE_IN}, {mask_true, b.mask, DENSE_IN + 1}, {bound, b.bound, DENSE_IN + 3}, {pos_pred, b.pos, LDDT_PRED},
+                                 {mask_pred, b.mask, LDDT_PRED + 1}, {weight, no, LDDT_WEIGHT}}, {{grad, 3 * no, LDDT_OUT}}, run);
+    return staged_call(ctx, {{pos_true, b.pos, DENSE_IN}, {mask_true, b.mask, DENSE_IN + 1}, {bound, b.bound, DENSE_IN + 3}, {pos_pred, b.pos, LDDT_PRED},
+                             {mask_pred, b.mask, LDDT_PRED + 1}, {nullptr, 0, LDDT_WEIGHT}}, {{soft, no, LDDT_OUT}, {pairs, no, LDDT_OUT + 1}}, run);
+}
+
+extern "C" {
+
+int fcz_lddt_soft_dev(fcz_ctx* ctx, const float* pos_true_dev, const uint8_t* mask_true_dev, const float* pos_pred_dev, const uint8_t* mask_pred_dev,
+                      const uint32_t* length_dev, uint32_t n, uint32_t L, int layout, int slot, float cutoff, const float* thresholds, float* soft_dev,
+                      int32_t* pairs_dev) {
+    if (!lddt_soft_args_ok(ctx, pos_true_dev, mask_true_dev, pos_pred_dev, layout, slot, cutoff, thresholds, L) || !soft_dev || !pairs_dev ||
+        !bound_ok(false, length_dev, n, L))
+        return FCZ_E_INVALID_ARG;
+    return lddt_soft_rows(ctx, pos_true_dev, mask_true_dev, pos_pred_dev, mask_pred_dev, length_dev, false, n, L, layout, slot, cutoff, thresholds, soft_dev,
+                          pairs_dev, nullptr, nullptr);
+}
+
+int fcz_lddt_soft_packed_dev(fcz_ctx* ctx, const float* pos_true_dev, const uint8_t* mask_true_dev, const float* pos_pred_dev, const uint8_t* mask_pred_dev,
+                             const uint32_t* row_off_dev, uint32_t n, uint32_t R, int layout, int slot, float cutoff, const float* thresholds, float* soft_dev,
+                             int32_t* pairs_dev) {
+    if (!lddt_soft_args_ok(ctx, pos_true_dev, mask_true_dev, pos_pred_dev, layout, slot, cutoff, thresholds, R) || !soft_dev || !pairs_dev ||
+        !bound_ok(true, row_off_dev, n, R))
+        return FCZ_E_INVALID_ARG;
+    return lddt_soft_rows(ctx, pos_true_dev, mask_true_dev, pos_pred_dev, mask_pred_dev, row_off_dev, true, n, R, layout, slot, cutoff, thresholds, soft_dev,
+                          pairs_dev, nullptr, nullptr);
+}
+
+int fcz_lddt_soft_grad_dev(fcz_ctx* ctx, const float* pos_true_dev, const uint8_t* mask_true_dev, const float* pos_pred_dev, const uint8_t* mask_pred_dev,
+                           const uint32_t* length_dev, uint32_t n, uint32_t L, int layout, int slot, float cutoff, const float* thresholds,
+                           const float* weight_dev, float* grad_dev) {
+    if (!lddt_soft_args_ok(ctx, pos_true_dev, mask_true_dev, pos_pred_dev, layout, slot, cutoff, thresholds, L) || !weight_dev || !grad_dev ||
+        !bound_ok(false, length_dev, n, L))
+        return FCZ_E_INVALID_ARG;
+    return lddt_soft_rows(ctx, pos_true_dev, mask_true_dev, pos_pred_dev, mask_pred_dev, length_dev, false, n, L, layout, slot, cutoff, thresholds, nullptr, nullptr,
+                          weight_dev, grad_dev);
+}
+
+int fcz_lddt_soft_grad_packed_dev(fcz_ctx* ctx, const float* pos_true_dev, const uint8_t* mask_true_dev, const float* pos_pred_dev, const uint8_t* mask_pred_dev,
+                                  const uint32_t* row_off_dev, uint32_t n, uint32_t R, int layout, int slot, float cutoff, const float* thresholds,
+                                  const float* weight_dev, float* grad_dev) {
+    if (!lddt_soft_args_ok(ctx, pos_true_dev, mask_true_dev, pos_pred_dev, layout, slot, cutoff, thresholds, R) || !weight_dev || !grad_dev ||
+        !bound_ok(true, row_off_dev, n, R))
+        return FCZ_E_INVALID_ARG;
+    return lddt_soft_rows(ctx, pos_true_dev, mask_true_dev, pos_pred_dev, mask_pred_dev, row_off_dev, true, n, R, layout, slot, cutoff, thresholds, nullptr, nullptr,
+                          weight_dev, grad_dev);
+}
+
+int fcz_lddt_soft(fcz_ctx* ctx, const float* pos_true, const uint8_t* mask_true, const float* pos_pred, const uint8_t* mask_pred, const uint32_t* length,
+                  uint32_t n, uint32_t L, int layout, int slot, float cutoff, const float* thresholds, float* soft, int32_t* pairs) {
+    if (!lddt_soft_args_ok(ctx, pos_true, mask_true, pos_pred, layout, slot, cutoff, thresholds, L) || !soft || !pairs || !bound_ok(false, length, n, L))
+        return FCZ_E_INVALID_ARG;
+    return lddt_soft_host(ctx, pos_true, mask_true, pos_pred, mask_pred, length, false, n, L, layout, slot, cutoff, thresholds, soft, pairs, nullptr, nullptr);
+}
+
+int fcz_lddt_soft_packed(fcz_ctx* ctx, const float* pos_true, const uint8_t* mask_true, const float* pos_pred, const uint8_t* mask_pred, const uint32_t* row_off,
+                         uint32_t n, uint32_t R, int layout, int slot, float cutoff, const float* thresholds, float* soft, int32_t* pairs) {
+    if (!lddt_soft_args_ok(ctx, pos_true, mask_true, pos_pred, layout, slot, cutoff, thresholds, R) || !soft || !pairs || !bound_ok(true, row_off, n, R))
+        return FCZ_E_INVALID_ARG;
+    return lddt_soft_host(ctx, pos_true, mask_true, pos_pred, mask_pred, row_off, true, n, R, layout, slot, cutoff, thresholds, soft, pairs, nullptr, nullptr);
+}
+
+int fcz_lddt_soft_grad(fcz_ctx* ctx, const float* pos_true, const uint8_t* mask_true, const float* pos_pred, const uint8_t* mask_pred, const uint32_t* length,
+                       uint32_t n, uint32_t L, int layout, int slot, float cutoff, const float* thresholds, const float* weight, float* grad) {
+    if (!lddt_soft_args_ok(ctx, pos_true, mask_true, pos_pred, layout, slot, cutoff, thresholds, L) || !weight || !grad || !bound_ok(false, length, n, L))
+        return FCZ_E_INVALID_ARG;
+    return lddt_soft_host(ctx, pos_true, mask_true, pos_pred, mask_pred, length, false, n, L, layout, slot, cutoff, thresholds, nullptr, nullptr, weight, grad);
+}
+
+int fcz_lddt_soft_grad_packed(fcz_ctx* ctx, const float* pos_true, const uint8_t* mask_true, const float* pos_pred, const uint8_t* mask_pred,
+                              const uint32_t* row_off, uint32_t n, uint32_t R, int layout, int slot, float cutoff, const float* thresholds, const float* weight,
+                              float* grad) {
+    if (!lddt_soft_args_ok(ctx, pos_true, mask_true, pos_pred, layout, slot, cutoff, thresholds, R) || !weight || !grad || !bound_ok(true, row_off, n, R))
+        return FCZ_E_INVALID_ARG;
+    return lddt_soft_host(ctx, pos_true, mask_true, pos_pred, mask_pred, row_off, true, n, R, layout, slot, cutoff, thresholds, nullptr, nullptr, weight, grad);
 }
 
 }  // extern "C"

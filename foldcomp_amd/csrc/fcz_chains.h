@@ -14,6 +14,8 @@
 //   chain_tile<PACKED>     the head of a kernel's tile loop: the tile's chain, its rows and the tile's first row (chain_tile_count
 //                          ends the loop).
 //   chain_stage_rows       one candidate pass of PASS chain rows, a row a lane and step (k_knn, k_lddt, k_hbond).
+//   chain_stage_ordered    the same pass with a row's slot fixed by its place in the pass, for a sweep that sums floats in row order
+//                          (k_lddt_soft, k_lddt_soft_grad).
 //   chain_stage_slots      one candidate pass of at most PASS atoms, staged in steps of the rows that hold at most STEP slots
 //                          (k_sasa_points, k_violations, k_lddt_atoms).
 //                          Both hand the caller's functor a row (and slot) and a chain_slots; the functor decides whether that is a
@@ -170,6 +172,20 @@ __device__ __forceinline__ uint32_t chain_stage_rows(uint32_t* s_count, uint32_t
     __syncthreads();
     *c0 = c1;
     return *s_count;
+}
+
+// The ordered sibling of chain_stage_rows, for a sweep whose result is a float sum and so depends on the order the candidates are met
+// in (k_lddt_soft): one candidate pass of PASS chain rows from row *c0, row(r, r - *c0) for EVERY row r of the pass, a row a lane and
+// step -- the slot is the row's place in the pass, and the functor marks in its own arrays a row that is no candidate. There is no
+// counter, so no barrier in front: the caller's barrier that closed the pass before has freed the staging. -> the rows staged; *c0
+// becomes the next pass' first row. The caller sweeps the pass and closes it with a barrier before it stages the next.
+template <uint32_t PASS, class Row>
+__device__ __forceinline__ uint32_t chain_stage_ordered(uint32_t len, uint32_t* c0, Row row) {
+    const uint32_t first = *c0, c1 = len - first < PASS ? len : first + PASS;
+    for (uint64_t r = (uint64_t)first + threadIdx.x; r < c1; r += BLOCK) row(r, (uint32_t)(r - first));
+    __syncthreads();
+    *c0 = c1;
+    return c1 - first;
 }
 
 // One candidate pass of at most PASS atoms from row *r0 of a chain of len rows of A slots: atom(r, a, slots) for every slot a of every

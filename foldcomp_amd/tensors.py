@@ -14,6 +14,9 @@
                                    the k nearest CA / CB sites of every residue inside its chain; decode_tensors(neighbors=k) adds them
     lddt(pred, true, atom="CA", cutoff=15.0) -> dict(lddt [..] float32, lddt_pairs, lddt_hits int32, lddt_chain [n] float32): the per-residue
                                    lDDT of predicted coordinates against a decoded batch, and its chain mean
+    smooth_lddt(pred, true, atom="CA", cutoff=15.0) -> dict(lddt_soft [..] float32, lddt_pairs int32, lddt_soft_chain [n] float32, loss):
+                                   the smooth lDDT of AlphaFold 3 on the same pairs, a loss: differentiable with respect to pred's
+                                   pos, with a fused backward on the GPU
     lddt_atoms(pred, true, swaps="alphafold", per_atom=False) -> dict(lddt, lddt_pairs, lddt_hits, swapped [..] bool, lddt_chain [n]
                                    float64, atom_pairs / atom_hits [.., A]): the all-atom lDDT of every residue after the symmetric
                                    side-chain namings of the truth have been resolved towards the prediction
@@ -59,7 +62,7 @@ from ._aa_tables import RES1
 from .codec import ANGLE_COLUMNS, WIDTH_LAYOUTS, Codec, dense_layout
 from .structure import CAtomsOut, CDenseIn, CDenseOut, CLddtAtomsOut, CPackedOut, CSuperposeOut, CTmScoreOut, CGdtOut, CViolationsOut, CChainSet, CTmAlignOut, CTmAlignParams, TM_ALIGN_OUTPUTS
 
-__all__ = ["decode_tensors", "encode_tensors", "decode_angles", "crop_starts", "neighbor_graph", "rigid_frames", "lddt", "lddt_atoms", "superpose", "tm_score", "gdt", "tm_align", "apply_transform",
+__all__ = ["decode_tensors", "encode_tensors", "decode_angles", "crop_starts", "neighbor_graph", "rigid_frames", "lddt", "smooth_lddt", "lddt_atoms", "superpose", "tm_score", "gdt", "tm_align", "apply_transform",
            "backbone_hbonds", "secondary_structure", "solvent_accessibility", "violations"]
 
 
@@ -633,7 +636,7 @@ def _inputs(what, numpy_form, batch, tensors, codec, check, pos_rule=None, aatyp
     return _dense_checked(what, numpy_form, codec, d, checked[0], checked[1], pos_rule, aatype, one_entry), checked
 
 
-def _pair_inputs(what, pred, true, codec, check, pos_rule="full", aatype=False):
+def _pair_inputs(what, pred, true, codec, check, pos_rule="full", aatype=False, numpy_form=None):
     """the one prelude of the functions on a prediction and its truth: both as dicts (pred may be its bare pos), the tensors that must
     be there, pred's shapes against true's, the caller's device-free check(shape, pred pos shape, pred mask shape or None, true) before
     a codec is made, _dense_checked on `true`, then pred's tensors on its device -> (the record of true, pred pos, pred mask viewed as
@@ -650,7 +653,7 @@ def _pair_inputs(what, pred, true, codec, check, pos_rule="full", aatype=False):
     if mshape is not None and mshape != shape[:-1]:
         raise ValueError(f"pred mask must have the shape of true mask, {shape[:-1]}, not {mshape}")
     checked = check(shape, pshape, mshape, t)
-    x = _dense_checked(what, f"Codec.{what}", codec, t, shape, t.get("cu_seqlens") is not None and len(shape) == 3, pos_rule, aatype)
+    x = _dense_checked(what, numpy_form or f"Codec.{what}", codec, t, shape, t.get("cu_seqlens") is not None and len(shape) == 3, pos_rule, aatype)
     _on_device(x.torch, what, x.dev, "pred pos", ppos, shape, (x.torch.float32,))
     if pmask is not None:
         pmask = _on_device(x.torch, what, x.dev, "pred mask", pmask, shape[:-1], (x.torch.bool, x.torch.uint8)).view(x.torch.uint8)
@@ -700,7 +703,8 @@ def lddt(pred, true, *, atom="CA", cutoff: float = 15.0, thresholds=(0.5, 1.0, 2
         lddt_chain  [n] float32            sum of hits / (4 * sum of pairs) over the chain's rows (in float64 from int64 sums, so
                                            exact whatever the order), 0 where the chain has no pair
     Distances are sqrt((dx*dx + dy*dy) + dz*dz) in float32 and the counters integers, so the result is reproducible bit for bit.
-    It is NOT differentiable: it returns counts (a training target or a validation metric, not a loss).
+    It is NOT differentiable: it returns counts (a training target or a validation metric, not a loss; smooth_lddt is the loss on
+    the same pairs).
 
     The tensors must be contiguous and lie on the codec's device; ordering against torch is decode_tensors'. cutoff, thresholds,
     atom and shapes that differ are checked first, without torch or a device (api.check_lddt)."""
@@ -719,6 +723,131 @@ def lddt(pred, true, *, atom="CA", cutoff: float = 15.0, thresholds=(0.5, 1.0, 2
               ctypes.addressof(th_c), score.data_ptr(), pairs.data_ptr(), hits.data_ptr())
         x.codec.synchronize()
     return dict(lddt=score, lddt_pairs=pairs, lddt_hits=hits, lddt_chain=_chain_score(hits, pairs, x.bound, x.is_packed).to(torch.float32))
+
+
+_autograd = {}
+
+
+def _autograd_functions(torch):
+    """the two torch.autograd.Function classes of smooth_lddt, made once torch is there (this module imports without it)"""
+    if _autograd:
+        return _autograd["soft"], _autograd["chain_sum"]
+    from torch.autograd.function import once_differentiable
+
+    class SoftLddt(torch.autograd.Function):
+        """pred pos -> soft [..] (fcz_lddt_soft_dev); `call` holds everything else of the call and receives pairs. The backward is
+        the gradient kernel (fcz_lddt_soft_grad_dev) on the saved pos: nothing else is kept from the forward."""
+
+        @staticmethod
+        def forward(ctx, ppos, call):
+            ctx.call = call
+            ctx.save_for_backward(ppos)
+            return call.value(ppos)
+
+        @staticmethod
+        @once_differentiable
+        def backward(ctx, grad_soft):
+            (ppos,) = ctx.saved_tensors
+            return ctx.call.gradient(ppos, grad_soft.contiguous()), None
+
+    class ChainSum(torch.autograd.Function):
+        """packed rows v [R] float64 -> their sums per chain [n], a cumulative sum differenced at cu_seqlens. The backward hands every
+        row its chain's gradient by a gather: torch's own backward of the indexing would scatter with float atomics."""
+
+        @staticmethod
+        def forward(ctx, v, at):
+            ctx.save_for_backward(at)
+            ctx.rows = v.shape[0]
+            return torch.cat([v.new_zeros(1), v.cumsum(0)])[at].diff()
+
+        @staticmethod
+        @once_differentiable
+        def backward(ctx, g):
+            (at,) = ctx.saved_tensors
+            r = torch.arange(ctx.rows, dtype=torch.int64, device=g.device)
+            if g.numel() == 0:
+                return g.new_zeros(ctx.rows), None
+            e = torch.searchsorted(at[1:].contiguous(), r, right=True).clamp(max=g.numel() - 1)     # the chain whose end lies behind row r
+            return torch.where((r >= at[0]) & (r < at[-1]), g[e], g.new_zeros(())), None
+
+    _autograd.update(soft=SoftLddt, chain_sum=ChainSum)
+    return SoftLddt, ChainSum
+
+
+class _SoftLddtCall:
+    """one call of smooth_lddt: the checked truth, pred's mask and the parameters; value() and gradient() enqueue the two kernels on
+    the codec's stream between a wait for torch's stream and codec.synchronize(), as every analysis function does"""
+
+    def __init__(self, x, pmask, slot, cutoff, th):
+        self.x, self.pmask, self.slot, self.cutoff, self.th = x, pmask, slot, cutoff, (ctypes.c_float * 4)(*th)
+        self.pairs = None
+
+    def _run(self, name, ppos, *outs):
+        x = self.x
+        x.torch.cuda.current_stream(x.dev).synchronize()
+        _call(x.codec, name, x.is_packed, x.pos.data_ptr(), x.mask.data_ptr(), ppos.data_ptr(), _ptr(self.pmask), _ptr(x.bound), x.n, x.rows, x.lay, self.slot,
+              self.cutoff, ctypes.addressof(self.th), *(o.data_ptr() for o in outs))
+        x.codec.synchronize()
+
+    def value(self, ppos):
+        x = self.x
+        soft = x.torch.zeros(x.lead, dtype=x.torch.float32, device=x.dev)
+        self.pairs = x.torch.zeros(x.lead, dtype=x.torch.int32, device=x.dev)
+        if soft.numel():
+            self._run("fcz_lddt_soft", ppos, soft, self.pairs)
+        return soft
+
+    def gradient(self, ppos, weight):
+        x = self.x
+        full = x.torch.zeros(x.shape, dtype=x.torch.float32, device=x.dev)
+        if weight.numel():
+            grad = x.torch.zeros(x.lead + (3,), dtype=x.torch.float32, device=x.dev)
+            self._run("fcz_lddt_soft_grad", ppos, weight, grad)
+            full[..., self.slot, :] = grad
+        return full
+
+
+def smooth_lddt(pred, true, *, atom="CA", cutoff: float = 15.0, thresholds=(0.5, 1.0, 2.0, 4.0), codec: Optional[Codec] = None) -> dict:
+    """predicted coordinates against true ones, both dense tensors on the GPU -> dict(lddt_soft, lddt_pairs, lddt_soft_chain, loss):
+    the smooth lDDT of AlphaFold 3 (Algorithm 27), a LOSS: differentiable with respect to pred's pos, with a fused backward on the
+    GPU and no L x L matrix in either direction.
+
+    `true` and `pred` are lddt's, padded, packed or a window with crop_start, `pred` a dict with `pos` and optionally `mask`, or the
+    bare pos tensor; sites and pairs are lddt's exactly (lddt_pairs equals lddt's). For a pair, delta = |d_true - d_pred| and
+    eps = 1/4 sum_k sigmoid(thresholds[k] - delta): lddt's four step functions, smoothed. thresholds must be finite.
+        lddt_soft        [n, L] / [R] float32   the mean of eps over the row's pairs, 0 where the row is no site or has no pair
+        lddt_pairs       int32                  the pairs of the row
+        lddt_soft_chain  [n] float32            the sum of eps over the sum of pairs of the chain's rows, 0 where it has no pair
+        loss             scalar float32         the mean of 1 - lddt_soft_chain over the chains that have a pair (0 without one)
+    When pred's pos requires a gradient (and gradients are enabled) the four carry a graph: loss.backward() runs the gradient kernel
+    once and leaves d loss / d pos in pos.grad, non-zero at the atom's slot of the site rows only. Gradients flow to pred's pos and
+    to nothing else; the graph can be walked once and not differentiated twice. Under torch.no_grad(), or for a pos that needs no
+    gradient, only the value kernel runs. Every sum has a fixed order (rows in float32 in ascending row order on the device, chains
+    in float64, no atomics in either direction): value and gradient are reproducible bit for bit.
+
+    The tensors must be contiguous and lie on the codec's device; ordering against torch is decode_tensors'. The arguments are
+    checked first, without torch or a device (api.check_lddt_soft)."""
+    x, ppos, pmask, (slot, cutoff, th) = _pair_inputs(
+        "smooth_lddt", pred, true, codec, lambda shape, pshape, mshape, t: api.check_lddt_soft(cutoff, thresholds, atom, shape[-2] if len(shape) in (3, 4) else None),
+        numpy_form="Codec.lddt_soft")
+    if x.rows > 2 ** 29:
+        raise ValueError("at most 2^29 rows per chain")
+    torch = x.torch
+    soft_fn, chain_sum = _autograd_functions(torch)
+    call = _SoftLddtCall(x, pmask, slot, cutoff, th)
+    soft = soft_fn.apply(ppos, call) if torch.is_grad_enabled() and ppos.requires_grad else call.value(ppos.detach())
+    pairs = call.pairs
+    has = pairs > 0
+    per_row = torch.where(has, soft / pairs.clamp(min=1).to(torch.float32), soft.new_zeros(()))
+    if x.is_packed:
+        at = x.bound.to(torch.int64)
+        cs, cp = chain_sum.apply(soft.to(torch.float64), at), torch.cat([at.new_zeros(1), pairs.to(torch.int64).cumsum(0)])[at].diff()
+    else:
+        cs, cp = soft.to(torch.float64).sum(dim=1), pairs.to(torch.int64).sum(dim=1)
+    scored = cp > 0
+    chain = torch.where(scored, cs / cp.clamp(min=1).to(torch.float64), cs.new_zeros(()))
+    loss = (torch.where(scored, 1.0 - chain, chain.new_zeros(())).sum() / scored.sum().clamp(min=1).to(torch.float64)).to(torch.float32)
+    return dict(lddt_soft=per_row, lddt_pairs=pairs, lddt_soft_chain=chain.to(torch.float32), loss=loss)
 
 
 def lddt_atoms(pred, true, *, cutoff: float = 15.0, thresholds=(0.5, 1.0, 2.0, 4.0), swaps="alphafold", per_atom: bool = False,

@@ -19,6 +19,7 @@
  *                                                          fcz_dense_window_dev / fcz_decompress_dense_window
  *   (none: no neighbour graph of the decoded chain)        fcz_knn_dev / fcz_knn_packed_dev, fcz_knn / fcz_knn_packed
  *   (none: no score of one structure against another)      fcz_lddt_dev / fcz_lddt_packed_dev, fcz_lddt / fcz_lddt_packed
+ *   (none: no loss, nothing with a gradient)               fcz_lddt_soft_dev / fcz_lddt_soft_grad_dev (+ _packed and host forms)
  *   (none: no all-atom score, no side-chain renaming)      fcz_lddt_atoms_dev / fcz_lddt_atoms_packed_dev, fcz_lddt_atoms / fcz_lddt_atoms_packed
  *   (none: no secondary structure)                         fcz_hbond_dev, fcz_dssp_labels_dev, fcz_dssp (+ _packed forms)
  *   (none: no solvent accessibility)                       fcz_sasa_dev / fcz_sasa_packed_dev, fcz_sasa / fcz_sasa_packed
@@ -446,6 +447,64 @@ int fcz_lddt(fcz_ctx* ctx, const float* pos_true, const uint8_t* mask_true, cons
 int fcz_lddt_packed(fcz_ctx* ctx, const float* pos_true, const uint8_t* mask_true, const float* pos_pred, const uint8_t* mask_pred,
                     const uint32_t* row_off, uint32_t n, uint32_t R, int layout, int slot, float cutoff, const float* thresholds,
                     float* score, int32_t* pairs, int32_t* hits);
+
+/* ---- smooth lDDT and its gradient ------------------------------------------------------------------------- */
+/* The differentiable form of fcz_lddt_dev: the smooth lDDT of AlphaFold 3 (Abramson et al. 2024, Algorithm 27), each step function
+ * of the score replaced by a sigmoid, with a fused backward pass, for a whole batch on the device without an L x L matrix in either
+ * direction. The reference has no such output. The inputs, the forms (padded / packed), sites, chains, distances (d2, d = the
+ * correctly rounded root) and the PAIRS are fcz_lddt_dev's, unchanged: j is a pair of i when j != i and d2_true < fcz_lddt_c2(cutoff).
+ * pairs [rows] int32 equals fcz_lddt_dev's pairs on the same inputs exactly. thresholds: four FINITE float32 on the host (NULL: 0.5,
+ * 1, 2, 4). For a pair
+ *   delta = |d_true - d_pred|                      one rounded float32 subtraction
+ *   eps(delta) = 1/4 sum_k sigmoid(t_k - delta)    over the four thresholds; 0 when delta is not finite (a d_pred of +inf)
+ * Value (fcz_lddt_soft_dev):
+ *   soft [rows] float32   the sum of eps over the pairs j of row i, in float32, in ASCENDING ROW ORDER of j within the chain. The
+ *                         order is fixed: it does not depend on the tile, the pass, the launch geometry or the other chains of the
+ *                         batch, so the same chain gives the same bytes alone, in any batch, padded or packed, call after call.
+ *                         0 where the row is no site or has no pair.
+ *   pairs [rows] int32
+ * Gradient (fcz_lddt_soft_grad_dev), for the caller's row weights weight [rows] float32, the upstream gradient of soft: with
+ * eps'(delta) = -1/4 sum_k s_k (1 - s_k), s_k = sigmoid(t_k - delta),
+ *   grad [rows][3] float32   grad[i] = sum over the pairs j of (w_i + w_j) eps'(delta_ij) sign(d_pred - d_true) (p_i - p_j) / d_pred,
+ *                         again in ascending j, in float32: the gradient of sum_i w_i soft[i] with respect to the predicted
+ *                         coordinates of row i at the slot. sign(0) = 0: a pair at delta == 0 adds nothing (the subgradient of
+ *                         |x| that torch takes). A pair whose d_pred is 0 or not finite adds nothing. The pair relation is
+ *                         symmetric, pair (i, j) stands in soft[i] and in soft[j]: hence (w_i + w_j), and row i gathers its whole
+ *                         gradient itself. No atomics, no scatter: the result is reproducible bit for bit. 0 where the row is no
+ *                         site. The weights of rows that are no site are not read as data.
+ * The sigmoid is 1 / (1 + e^-x) with the hardware's exp2 of a scaled argument and its reciprocal (foldcomp_amd/csrc/fcz_lddt_soft.h):
+ * a term is within 2^-19 of its exact value for distances under 64 A, |soft - exact| <= P 2^-19 + P^2 2^-24 for a row of P pairs.
+ * Everything behind soft (soft / pairs, the quotient of a chain, 1 - ...) is the caller's arithmetic.
+ * rows = n * L (padded) or R (packed). Every byte of the outputs is written whatever the inputs hold, nothing outside them, and
+ * nothing outside the inputs is read, whatever row_off holds (as for fcz_lddt_dev). Passes are fcz_lddt_pass() rows. Enqueued on the
+ * ctx stream, no synchronisation. FCZ_E_INVALID_ARG with nothing launched and no output touched: what fcz_lddt_dev refuses (its
+ * outputs here being soft / pairs, or weight / grad), and a threshold that is not finite. n == 0 or R == 0: FCZ_OK. The time goes to
+ * the groups "lddt_soft" and "lddt_soft_grad". */
+int fcz_lddt_soft_dev(fcz_ctx* ctx, const float* pos_true_dev, const uint8_t* mask_true_dev, const float* pos_pred_dev,
+                      const uint8_t* mask_pred_dev, const uint32_t* length_dev, uint32_t n, uint32_t L, int layout, int slot,
+                      float cutoff, const float* thresholds, float* soft_dev, int32_t* pairs_dev);
+int fcz_lddt_soft_packed_dev(fcz_ctx* ctx, const float* pos_true_dev, const uint8_t* mask_true_dev, const float* pos_pred_dev,
+                             const uint8_t* mask_pred_dev, const uint32_t* row_off_dev, uint32_t n, uint32_t R, int layout, int slot,
+                             float cutoff, const float* thresholds, float* soft_dev, int32_t* pairs_dev);
+int fcz_lddt_soft_grad_dev(fcz_ctx* ctx, const float* pos_true_dev, const uint8_t* mask_true_dev, const float* pos_pred_dev,
+                           const uint8_t* mask_pred_dev, const uint32_t* length_dev, uint32_t n, uint32_t L, int layout, int slot,
+                           float cutoff, const float* thresholds, const float* weight_dev, float* grad_dev);
+int fcz_lddt_soft_grad_packed_dev(fcz_ctx* ctx, const float* pos_true_dev, const uint8_t* mask_true_dev, const float* pos_pred_dev,
+                                  const uint8_t* mask_pred_dev, const uint32_t* row_off_dev, uint32_t n, uint32_t R, int layout,
+                                  int slot, float cutoff, const float* thresholds, const float* weight_dev, float* grad_dev);
+/* Host-pointer conveniences: the same arrays on the host, staged through the ctx like fcz_lddt; synchronous. */
+int fcz_lddt_soft(fcz_ctx* ctx, const float* pos_true, const uint8_t* mask_true, const float* pos_pred, const uint8_t* mask_pred,
+                  const uint32_t* length, uint32_t n, uint32_t L, int layout, int slot, float cutoff, const float* thresholds,
+                  float* soft, int32_t* pairs);
+int fcz_lddt_soft_packed(fcz_ctx* ctx, const float* pos_true, const uint8_t* mask_true, const float* pos_pred,
+                         const uint8_t* mask_pred, const uint32_t* row_off, uint32_t n, uint32_t R, int layout, int slot, float cutoff,
+                         const float* thresholds, float* soft, int32_t* pairs);
+int fcz_lddt_soft_grad(fcz_ctx* ctx, const float* pos_true, const uint8_t* mask_true, const float* pos_pred, const uint8_t* mask_pred,
+                       const uint32_t* length, uint32_t n, uint32_t L, int layout, int slot, float cutoff, const float* thresholds,
+                       const float* weight, float* grad);
+int fcz_lddt_soft_grad_packed(fcz_ctx* ctx, const float* pos_true, const uint8_t* mask_true, const float* pos_pred,
+                              const uint8_t* mask_pred, const uint32_t* row_off, uint32_t n, uint32_t R, int layout, int slot,
+                              float cutoff, const float* thresholds, const float* weight, float* grad);
 
 /* ---- all-atom lDDT with symmetric side-chain renaming ------------------------------------------------------ */
 /* The lDDT that CASP, CAMEO and model papers report: every heavy atom against every heavy atom of the other residues of its chain,

@@ -6,7 +6,8 @@ asserts from the records it built that the batch takes the branch it names, and 
 per-chain and stateless, hence blind to batch shape by construction).
 
 Not covered: the NON-split long route (n_long >= 2 * 4 * n_cu * 64, about 131 000 chains of >= 1 024 residues = more than 134 M
-residues) does not fit a test's time; long chains reach k_backbone<0> only through that route."""
+residues) does not fit a test's time; long chains reach k_backbone<0> only through that route.
+The persistent grids of the analyses over dense tensors are crossed in tests/test_gpu_sweep_grids.py."""
 import dataclasses
 import functools
 

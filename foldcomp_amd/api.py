@@ -401,6 +401,27 @@ def check_lddt_soft(cutoff, thresholds, atom, width=None):
     return slot, cutoff, th
 
 
+def check_fape(clamp, scale, eps, atom, width=None):
+    """the argument rules of fape that need no tensors' device and no GPU -> (slot, clamp, scale, eps): clamp a number > 0 (as
+    float32; +inf or None: unclamped, returned as +inf), scale and eps finite numbers > 0 (eps as float32, scale as a Python float);
+    atom as check_neighbors reads it (the slot is None while the layout width A is unknown)"""
+    slot = check_neighbors(1, atom, width)
+
+    def number(v):
+        return not isinstance(v, (bool, np.bool_)) and isinstance(v, (int, float, np.integer, np.floating))
+
+    with np.errstate(over="ignore", under="ignore"):
+        if clamp is None:
+            clamp = float("inf")
+        if not number(clamp) or np.isnan(np.float32(clamp)) or not np.float32(clamp) > 0:
+            raise ValueError(f"clamp must be a number > 0 (as float32), +inf or None for unclamped, not {clamp!r}")
+        if not number(scale) or not np.isfinite(float(scale)) or not float(scale) > 0:
+            raise ValueError(f"scale must be a finite number > 0, not {scale!r}")
+        if not number(eps) or not np.isfinite(np.float32(eps)) or not np.float32(eps) > 0:
+            raise ValueError(f"eps must be a finite number > 0 (as float32), not {eps!r}")
+        return slot, float(np.float32(clamp)), float(scale), float(np.float32(eps))
+
+
 _LAYOUT_WIDTHS = {"atom37": (0, 37), "atom14": (1, 14), "backbone4": (2, 4)}  # name -> (enum fcz_dense_layout, A)
 
 

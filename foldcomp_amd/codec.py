@@ -385,6 +385,57 @@ class Codec:
                        a.lay, slot, cutoff, _addr(th), weight.ctypes.data, grad.ctypes.data)
         return grad
 
+    def _fape_inputs(self, frames_true, pos_true, mask_true, frames_pred, pos_pred, mask_pred, slot, length, row_off, clamp, eps):
+        """the prelude of fape and fape_grad -> (_Arrays of true, the ten addresses of the call in its order, slot, clamp, eps, the arrays
+        the addresses point into). frames_*: (rot [.., 3, 3] float32, trans [.., 3] float32, frame_mask [..] bool / uint8; None for the
+        prediction's: every frame present)"""
+        from . import api
+        a, pos_pred, mask_pred, slot = _pair_arrays(pos_true, mask_true, pos_pred, mask_pred, None, length, row_off, slot,
+                                                    limit=(2 ** 29, "at most 2^29 rows per chain"))
+        _, clamp, _, eps = api.check_fape(clamp, 1.0, eps, slot, a.A)
+        keep = []
+        for which, (rot, trans, fmask) in (("true", frames_true), ("pred", frames_pred)):
+            rot, trans = np.ascontiguousarray(rot, np.float32), np.ascontiguousarray(trans, np.float32)
+            if rot.shape != a.lead + (3, 3) or trans.shape != a.lead + (3,):
+                raise ValueError(f"rot_{which} must be float32 {a.lead + (3, 3)} and trans_{which} {a.lead + (3,)}, not {rot.shape} and {trans.shape}")
+            if fmask is None and which == "true":
+                raise ValueError("frame_mask of the truth is needed")
+            keep += [rot, trans, None if fmask is None else _mask_array(fmask, a.lead, f"frame_mask_{which}")]
+        ptrs = [_addr(keep[0]), _addr(keep[1]), _addr(keep[2]), a.pos.ctypes.data, a.mask.ctypes.data, _addr(keep[3]), _addr(keep[4]), _addr(keep[5]),
+                pos_pred.ctypes.data, _addr(mask_pred)]
+        return a, ptrs, slot, clamp, eps, (keep, pos_pred, mask_pred)
+
+    def fape(self, frames_true, pos_true: np.ndarray, mask_true: np.ndarray, frames_pred, pos_pred: np.ndarray, mask_pred=None, slot: int = 1, length=None,
+             row_off=None, clamp=10.0, eps: float = 1e-4):
+        """frames and dense arrays of a truth and a prediction on the host -> the backbone FAPE sums (fcz_fape, or fcz_fape_packed when
+        row_off is given): sum float32 [n, L] / [R], at a frame row the sum over its chain's points at `slot` of min(sqrt(|R^T (x - t)
+        - R'^T (x' - t')|^2 + eps), clamp) in float32 in ascending row order, and points int32, the number of those points.
+        frames_true = (rot [.., 3, 3], trans [.., 3], frame_mask [..]) as Codec.frames gives them, frames_pred the same with a
+        frame_mask that may be None; the dense arrays are Codec.lddt's. clamp=None or +inf: unclamped. sum / points is the row's FAPE
+        before the scale."""
+        a, ptrs, slot, clamp, eps, keep = self._fape_inputs(frames_true, pos_true, mask_true, frames_pred, pos_pred, mask_pred, slot, length, row_off, clamp, eps)
+        total = np.zeros(a.lead, np.float32)
+        points = np.zeros(a.lead, np.int32)
+        if total.size:
+            self._call("fcz_fape", a.packed, *ptrs, _addr(a.bound), a.n, a.rows, a.lay, slot, clamp, eps, total.ctypes.data, points.ctypes.data)
+        return dict(sum=total, points=points)
+
+    def fape_grad(self, frames_true, pos_true: np.ndarray, mask_true: np.ndarray, frames_pred, pos_pred: np.ndarray, weight: np.ndarray, mask_pred=None,
+                  slot: int = 1, length=None, row_off=None, clamp=10.0, eps: float = 1e-4):
+        """the gradient of sum_i weight[i] * sum[i] of fape with respect to the prediction's rot, trans and pos_pred[.., slot, :]
+        (fcz_fape_grad, or fcz_fape_grad_packed when row_off is given): dict(grad_rot float32 [.., 3, 3], grad_trans [.., 3],
+        grad_pos [.., 3]), 0 where a row is no frame (grad_rot, grad_trans) or no point (grad_pos). weight float32 [n, L] / [R].
+        Gathered per row in a fixed order without atomics: reproducible bit for bit."""
+        a, ptrs, slot, clamp, eps, keep = self._fape_inputs(frames_true, pos_true, mask_true, frames_pred, pos_pred, mask_pred, slot, length, row_off, clamp, eps)
+        weight = np.ascontiguousarray(weight, np.float32)
+        if weight.shape != a.lead:
+            raise ValueError(f"weight must be float32 {a.lead}, not {weight.shape}")
+        out = dict(grad_rot=np.zeros(a.lead + (3, 3), np.float32), grad_trans=np.zeros(a.lead + (3,), np.float32), grad_pos=np.zeros(a.lead + (3,), np.float32))
+        if weight.size:
+            self._call("fcz_fape_grad", a.packed, *ptrs, _addr(a.bound), a.n, a.rows, a.lay, slot, clamp, eps, weight.ctypes.data,
+                       *(out[k].ctypes.data for k in ("grad_rot", "grad_trans", "grad_pos")))
+        return out
+
     def lddt_atoms(self, pos_true: np.ndarray, mask_true: np.ndarray, pos_pred: np.ndarray, mask_pred=None, aatype=None, length=None, row_off=None, *,
                    cutoff: float = 15.0, thresholds=None, swaps="alphafold", per_atom: bool = False):
         """two sets of dense arrays of one shape on the host -> the all-atom lDDT of `pred` against `true` after the symmetric

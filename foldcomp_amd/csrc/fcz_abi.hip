@@ -36,6 +36,7 @@
 #include "fcz_knn.h"
 #include "fcz_lddt.h"
 #include "fcz_lddt_soft.h"
+#include "fcz_fape.h"
 #include "fcz_dssp.h"
 #include "fcz_sasa.h"
 #include "fcz_violations.h"
@@ -99,6 +100,8 @@ struct timed_span { std::string name; hipEvent_t a, b; };
 // (windowed form) aatype; WINDOW_START: the n u32 starts of a windowed host call; KEPT_*: the records a *_begin call leaves for its fetch
 // (C + 1 u64 offsets, the bytes, C i32 status); LDDT_PRED: pos and mask of the second tensor batch of fcz_lddt, LDDT_OUT: score, pairs, hits
 // (fcz_lddt_soft: soft, pairs; fcz_lddt_soft_grad: grad), LDDT_WEIGHT: the row weights of fcz_lddt_soft_grad;
+// FAPE_FRAMES: rot, trans, frame_mask of the truth, then of the prediction, of fcz_fape (its pos, mask, bound and weight go through DENSE_IN, LDDT_PRED
+// and LDDT_WEIGHT), FAPE_OUT: sum, points (fcz_fape_grad: grad_rot, grad_trans, grad_pos);
 // DSSP_OUT: acc_index, acc_energy, don_index, don_energy, ss, ss_mask of fcz_dssp; SASA_POINTS: the directions of fcz_sasa, SASA_OUT: sasa_points, sasa, sasa_mask;
 // SUPERPOSE_OUT: the seven arrays of a fcz_superpose_out in the struct's order; APPLY_ROT, APPLY_TRANS, APPLY_OUT: the transforms and the moved
 // coordinates of fcz_superpose_apply (its pos and mask go through LDDT_PRED); TM_SEED, TM_SELECTED: the two arrays a fcz_tmscore_out adds to those seven;
@@ -107,13 +110,13 @@ struct timed_span { std::string name; hipEvent_t a, b; };
 // TA_SETS: pos, mask, length / row_off of the two fcz_chain_set of fcz_tmalign, TA_PAIRS: its pairs, TA_OUT: the thirteen arrays of a fcz_tmalign_out in the
 // struct's order; TA_DP_*: the transforms, map and aligned of fcz_tmalign_dp
 enum { REC_BLOB, REC_OFF, REC_RES_OFF, REC_ATOM_OFF, REC_X, REC_Y, REC_Z, REC_BFAC, REC_RES_CODE, REC_ATOM_CODE,
-       FILES_TEXT = 0, FILES_OFF, FILES_NAMES, FILES_NAME_OFF, FILES_STEM_LEN, BATCH_IN = 0, DENSE_IN = 0, LDDT_PRED = 4, LDDT_WEIGHT = 6, DENSE_OUT = 10, LDDT_OUT = 10, SUPERPOSE_OUT = 10, DSSP_OUT = 10,
+       FILES_TEXT = 0, FILES_OFF, FILES_NAMES, FILES_NAME_OFF, FILES_STEM_LEN, BATCH_IN = 0, DENSE_IN = 0, LDDT_PRED = 4, LDDT_WEIGHT = 6, FAPE_FRAMES = 7, FAPE_OUT = 13, DENSE_OUT = 10, LDDT_OUT = 10, SUPERPOSE_OUT = 10, DSSP_OUT = 10,
        SASA_POINTS = 4, SASA_OUT = 10,
        APPLY_ROT = 10, APPLY_TRANS, APPLY_OUT,
        ANGLES_OUT = 10, KEPT_OFF = 13, KEPT_BYTES, KEPT_STATUS, DENSE_CHAIN_INDEX, WINDOW_START = DENSE_CHAIN_INDEX, TM_SEED, TM_SELECTED,
        VIOL_OUT = 10, LDDTA_OUT = 10, GDT_OUT = 10, TA_SETS = 0, TA_PAIRS = 6, TA_OUT = 7, TA_DP_ROT = 7, TA_DP_TRANS, TA_DP_MAP, TA_DP_ALIGNED, VIOL_OUT_LAST = 19, POOL_COUNT };
 static_assert(POOL_COUNT == VIOL_OUT_LAST + 1 && DENSE_OUT + 6 == DENSE_CHAIN_INDEX && LDDTA_OUT + 6 <= POOL_COUNT && TM_SELECTED < POOL_COUNT && GDT_OUT + 8 <= POOL_COUNT && TA_OUT + 13 <= POOL_COUNT && TA_SETS + 6 == TA_PAIRS &&
-              TA_PAIRS < TA_OUT && TA_DP_ALIGNED < POOL_COUNT, "the last name of the enum sizes fcz_ctx::pool");
+              TA_PAIRS < TA_OUT && TA_DP_ALIGNED < POOL_COUNT && FAPE_FRAMES + 6 == FAPE_OUT && FAPE_OUT + 3 <= POOL_COUNT, "the last name of the enum sizes fcz_ctx::pool");
 
 // what the device reports to the host in the middle of a call: one pinned allocation, a member per reader
 struct pinned_words {
@@ -192,6 +195,8 @@ struct fcz_ctx {
     //   fcz_lddt / fcz_lddt_packed                  DENSE_IN 0, 1, 3 (pos_true, mask_true, length / row_off), LDDT_PRED 4 .. 5 (pos_pred, mask_pred), LDDT_OUT 10 .. 12
     //   fcz_lddt_soft / fcz_lddt_soft_packed        the inputs of fcz_lddt, LDDT_OUT 10 .. 11 (soft, pairs)
     //   fcz_lddt_soft_grad / _grad_packed           the inputs of fcz_lddt, LDDT_WEIGHT 6, LDDT_OUT 10 (grad)
+    //   fcz_fape / fcz_fape_packed                  the inputs of fcz_lddt, FAPE_FRAMES 7 .. 12, FAPE_OUT 13 .. 14 (sum, points)
+    //   fcz_fape_grad / fcz_fape_grad_packed        the same inputs, LDDT_WEIGHT 6, FAPE_OUT 13 .. 15 (grad_rot, grad_trans, grad_pos)
     //   fcz_lddt_atoms / fcz_lddt_atoms_packed      DENSE_IN 0 .. 3 (pos_true, mask_true, aatype, length / row_off), LDDT_PRED 4 .. 5, LDDTA_OUT 10 .. 15
     //   fcz_superpose / fcz_superpose_packed        DENSE_IN 0, 1, 3 and LDDT_PRED 4 .. 5 as fcz_lddt, SUPERPOSE_OUT 10 .. 16
     //   fcz_tmscore / fcz_tmscore_packed            the same, then TM_SEED 17, TM_SELECTED 18
@@ -2035,6 +2040,148 @@ int fcz_lddt_soft_grad_packed(fcz_ctx* ctx, const float* pos_true, const uint8_t
         return FCZ_E_INVALID_ARG;
     return lddt_soft_host(ctx, pos_true, mask_true, pos_pred, mask_pred, row_off, true, n, R, layout, slot, cutoff, thresholds, nullptr, nullptr, weight, grad);
 }
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------------
+// backbone FAPE and its gradient (fcz_fape.h; no counterpart in the reference)
+// ------------------------------------------------------------------------------------------------
+// the ten input arrays of a FAPE call, device or host pointers: frames and points of the truth, then of the prediction
+struct fape_in {
+    const float* rot_true; const float* trans_true; const uint8_t* fmask_true; const float* pos_true; const uint8_t* mask_true;
+    const float* rot_pred; const float* trans_pred; const uint8_t* fmask_pred; const float* pos_pred; const uint8_t* mask_pred;
+};
+
+// the outputs are checked by the caller. rows: L (padded) or R (packed)
+static bool fape_args_ok(const fcz_ctx* ctx, const fape_in& a, int layout, int slot, float clamp, float eps, uint32_t rows) {
+    if (!ctx || !a.rot_true || !a.trans_true || !a.fmask_true || !a.pos_true || !a.mask_true || !a.rot_pred || !a.trans_pred || !a.pos_pred) return false;
+    if (fcz_dense_width(layout) <= 0 || slot < 0 || slot >= fcz_dense_width(layout)) return false;
+    if (std::isnan(clamp) || !(clamp > 0.0f) || !std::isfinite(eps) || !(eps > 0.0f) || rows > FAPE_MAX_ROWS) return false;
+    return true;
+}
+
+// the device forms of the value (weight_dev and the gradients NULL) and of the gradient (sum_dev and points_dev NULL); bound_dev is
+// length [n] or NULL with rows = L, or row_off [n + 1] with rows = R. The gradient is two sweeps behind one fill, in one span.
+static int fape_rows(fcz_ctx* ctx, const fape_in& a, const uint32_t* bound_dev, bool packed, uint32_t n, uint32_t rows, int layout, int slot, float clamp,
+                     float eps, float* sum_dev, int32_t* points_dev, const float* weight_dev, float* grad_rot_dev, float* grad_trans_dev, float* grad_pos_dev) {
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (rows == 0 || (n == 0 && !packed)) return FCZ_OK;
+    const uint32_t A = (uint32_t)fcz_dense_width(layout);
+    chain_tiles ct(ctx, packed, n, rows);
+    int rc = ct.reserve(); if (rc) return rc;
+    if (grad_rot_dev) {
+        const fape_grad_args g{a.rot_true, a.trans_true, a.fmask_true, a.pos_true, a.mask_true, a.rot_pred, a.trans_pred, a.fmask_pred, a.pos_pred, a.mask_pred,
+                               bound_dev, n, rows, A, (uint32_t)slot, clamp, eps, weight_dev, grad_rot_dev, grad_trans_dev, grad_pos_dev};
+        span_guard sg(ctx, "fape_grad");
+        return ct.run(bound_dev, [&] { hipLaunchKernelGGL(k_chain_fill<fape_grad_args>, ct.fill_grid(rows), dim3(BLOCK), 0, ctx->stream, g); },
+                      [&](auto P, dim3 grid, const uint64_t* tile_off, uint32_t tiles_per_entry, uint64_t n_padded) {
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_fape_grad_frames<decltype(P)::value>), grid, dim3(BLOCK), 0, ctx->stream, g, tile_off, tiles_per_entry, n_padded);
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_fape_grad_points<decltype(P)::value>), grid, dim3(BLOCK), 0, ctx->stream, g, tile_off, tiles_per_entry, n_padded);
+        });
+    }
+    const fape_args g{a.rot_true, a.trans_true, a.fmask_true, a.pos_true, a.mask_true, a.rot_pred, a.trans_pred, a.fmask_pred, a.pos_pred, a.mask_pred,
+                      bound_dev, n, rows, A, (uint32_t)slot, clamp, eps, sum_dev, points_dev};
+    span_guard sg(ctx, "fape");
+    return ct.run(bound_dev, [&] { hipLaunchKernelGGL(k_chain_fill<fape_args>, ct.fill_grid(rows), dim3(BLOCK), 0, ctx->stream, g); },
+                  [&](auto P, dim3 grid, const uint64_t* tile_off, uint32_t tiles_per_entry, uint64_t n_padded) {
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_fape<decltype(P)::value>), grid, dim3(BLOCK), 0, ctx->stream, g, tile_off, tiles_per_entry, n_padded);
+    });
+}
+
+// the host forms: the host arrays through DENSE_IN 0, 1, 3, LDDT_PRED 4, 5, LDDT_WEIGHT 6, FAPE_FRAMES 7 .. 12 and FAPE_OUT 13 .. 14 (sum, points) or
+// 13 .. 15 (grad_rot, grad_trans, grad_pos)
+static int fape_host(fcz_ctx* ctx, const fape_in& a, const uint32_t* bound, bool packed, uint32_t n, uint32_t rows_per, int layout, int slot, float clamp, float eps,
+                     float* sum, int32_t* points, const float* weight, float* grad_rot, float* grad_trans, float* grad_pos) {
+    const dense_bytes b(packed, n, rows_per, layout, bound);
+    const size_t no = b.rows * 4;
+    auto run = [&](const void* const* in, void* const* out) {
+        const fape_in d{(const float*)in[6], (const float*)in[7], (const uint8_t*)in[8], (const float*)in[0], (const uint8_t*)in[1],
+                        (const float*)in[9], (const float*)in[10], (const uint8_t*)in[11], (const float*)in[3], (const uint8_t*)in[4]};
+        const bool grad = grad_rot != nullptr;
+        return fape_rows(ctx, d, (const uint32_t*)in[2], packed, n, rows_per, layout, slot, clamp, eps, grad ? nullptr : (float*)out[0],
+                         grad ? nullptr : (int32_t*)out[1], (const float*)in[5], grad ? (float*)out[0] : nullptr, grad ? (float*)out[1] : nullptr,
+                         grad ? (float*)out[2] : nullptr);
+    };
+    const std::initializer_list<staged_in> in = {
+        {a.pos_true, b.pos, DENSE_IN}, {a.mask_true, b.mask, DENSE_IN + 1}, {bound, b.bound, DENSE_IN + 3}, {a.pos_pred, b.pos, LDDT_PRED},
+        {a.mask_pred, b.mask, LDDT_PRED + 1}, {weight, no, LDDT_WEIGHT}, {a.rot_true, 9 * no, FAPE_FRAMES}, {a.trans_true, 3 * no, FAPE_FRAMES + 1},
+        {a.fmask_true, b.rows, FAPE_FRAMES + 2}, {a.rot_pred, 9 * no, FAPE_FRAMES + 3}, {a.trans_pred, 3 * no, FAPE_FRAMES + 4},
+        {a.fmask_pred, b.rows, FAPE_FRAMES + 5}};
+    if (grad_rot) return staged_call(ctx, in, {{grad_rot, 9 * no, FAPE_OUT}, {grad_trans, 3 * no, FAPE_OUT + 1}, {grad_pos, 3 * no, FAPE_OUT + 2}}, run);
+    return staged_call(ctx, in, {{sum, no, FAPE_OUT}, {points, no, FAPE_OUT + 1}}, run);
+}
+
+extern "C" {
+
+int fcz_fape_pass(void) { return (int)(FAPE_PASS > FAPE_FRAME_PASS ? FAPE_PASS : FAPE_FRAME_PASS); }
+
+#define FCZ_FAPE_INPUTS(S) const float* rot_true##S, const float* trans_true##S, const uint8_t* fmask_true##S, const float* pos_true##S, \
+    const uint8_t* mask_true##S, const float* rot_pred##S, const float* trans_pred##S, const uint8_t* fmask_pred##S, const float* pos_pred##S, \
+    const uint8_t* mask_pred##S
+#define FCZ_FAPE_IN(S) fape_in{rot_true##S, trans_true##S, fmask_true##S, pos_true##S, mask_true##S, rot_pred##S, trans_pred##S, fmask_pred##S, pos_pred##S, mask_pred##S}
+
+int fcz_fape_dev(fcz_ctx* ctx, FCZ_FAPE_INPUTS(_dev), const uint32_t* length_dev, uint32_t n, uint32_t L, int layout, int slot, float clamp, float eps,
+                 float* sum_dev, int32_t* points_dev) {
+    const fape_in a = FCZ_FAPE_IN(_dev);
+    if (!fape_args_ok(ctx, a, layout, slot, clamp, eps, L) || !sum_dev || !points_dev || !bound_ok(false, length_dev, n, L)) return FCZ_E_INVALID_ARG;
+    return fape_rows(ctx, a, length_dev, false, n, L, layout, slot, clamp, eps, sum_dev, points_dev, nullptr, nullptr, nullptr, nullptr);
+}
+
+int fcz_fape_packed_dev(fcz_ctx* ctx, FCZ_FAPE_INPUTS(_dev), const uint32_t* row_off_dev, uint32_t n, uint32_t R, int layout, int slot, float clamp, float eps,
+                        float* sum_dev, int32_t* points_dev) {
+    const fape_in a = FCZ_FAPE_IN(_dev);
+    if (!fape_args_ok(ctx, a, layout, slot, clamp, eps, R) || !sum_dev || !points_dev || !bound_ok(true, row_off_dev, n, R)) return FCZ_E_INVALID_ARG;
+    return fape_rows(ctx, a, row_off_dev, true, n, R, layout, slot, clamp, eps, sum_dev, points_dev, nullptr, nullptr, nullptr, nullptr);
+}
+
+int fcz_fape_grad_dev(fcz_ctx* ctx, FCZ_FAPE_INPUTS(_dev), const uint32_t* length_dev, uint32_t n, uint32_t L, int layout, int slot, float clamp, float eps,
+                      const float* weight_dev, float* grad_rot_dev, float* grad_trans_dev, float* grad_pos_dev) {
+    const fape_in a = FCZ_FAPE_IN(_dev);
+    if (!fape_args_ok(ctx, a, layout, slot, clamp, eps, L) || !weight_dev || !grad_rot_dev || !grad_trans_dev || !grad_pos_dev || !bound_ok(false, length_dev, n, L))
+        return FCZ_E_INVALID_ARG;
+    return fape_rows(ctx, a, length_dev, false, n, L, layout, slot, clamp, eps, nullptr, nullptr, weight_dev, grad_rot_dev, grad_trans_dev, grad_pos_dev);
+}
+
+int fcz_fape_grad_packed_dev(fcz_ctx* ctx, FCZ_FAPE_INPUTS(_dev), const uint32_t* row_off_dev, uint32_t n, uint32_t R, int layout, int slot, float clamp,
+                             float eps, const float* weight_dev, float* grad_rot_dev, float* grad_trans_dev, float* grad_pos_dev) {
+    const fape_in a = FCZ_FAPE_IN(_dev);
+    if (!fape_args_ok(ctx, a, layout, slot, clamp, eps, R) || !weight_dev || !grad_rot_dev || !grad_trans_dev || !grad_pos_dev || !bound_ok(true, row_off_dev, n, R))
+        return FCZ_E_INVALID_ARG;
+    return fape_rows(ctx, a, row_off_dev, true, n, R, layout, slot, clamp, eps, nullptr, nullptr, weight_dev, grad_rot_dev, grad_trans_dev, grad_pos_dev);
+}
+
+int fcz_fape(fcz_ctx* ctx, FCZ_FAPE_INPUTS(), const uint32_t* length, uint32_t n, uint32_t L, int layout, int slot, float clamp, float eps, float* sum,
+             int32_t* points) {
+    const fape_in a = FCZ_FAPE_IN();
+    if (!fape_args_ok(ctx, a, layout, slot, clamp, eps, L) || !sum || !points || !bound_ok(false, length, n, L)) return FCZ_E_INVALID_ARG;
+    return fape_host(ctx, a, length, false, n, L, layout, slot, clamp, eps, sum, points, nullptr, nullptr, nullptr, nullptr);
+}
+
+int fcz_fape_packed(fcz_ctx* ctx, FCZ_FAPE_INPUTS(), const uint32_t* row_off, uint32_t n, uint32_t R, int layout, int slot, float clamp, float eps, float* sum,
+                    int32_t* points) {
+    const fape_in a = FCZ_FAPE_IN();
+    if (!fape_args_ok(ctx, a, layout, slot, clamp, eps, R) || !sum || !points || !bound_ok(true, row_off, n, R)) return FCZ_E_INVALID_ARG;
+    return fape_host(ctx, a, row_off, true, n, R, layout, slot, clamp, eps, sum, points, nullptr, nullptr, nullptr, nullptr);
+}
+
+int fcz_fape_grad(fcz_ctx* ctx, FCZ_FAPE_INPUTS(), const uint32_t* length, uint32_t n, uint32_t L, int layout, int slot, float clamp, float eps,
+                  const float* weight, float* grad_rot, float* grad_trans, float* grad_pos) {
+    const fape_in a = FCZ_FAPE_IN();
+    if (!fape_args_ok(ctx, a, layout, slot, clamp, eps, L) || !weight || !grad_rot || !grad_trans || !grad_pos || !bound_ok(false, length, n, L))
+        return FCZ_E_INVALID_ARG;
+    return fape_host(ctx, a, length, false, n, L, layout, slot, clamp, eps, nullptr, nullptr, weight, grad_rot, grad_trans, grad_pos);
+}
+
+int fcz_fape_grad_packed(fcz_ctx* ctx, FCZ_FAPE_INPUTS(), const uint32_t* row_off, uint32_t n, uint32_t R, int layout, int slot, float clamp, float eps,
+                         const float* weight, float* grad_rot, float* grad_trans, float* grad_pos) {
+    const fape_in a = FCZ_FAPE_IN();
+    if (!fape_args_ok(ctx, a, layout, slot, clamp, eps, R) || !weight || !grad_rot || !grad_trans || !grad_pos || !bound_ok(true, row_off, n, R))
+        return FCZ_E_INVALID_ARG;
+    return fape_host(ctx, a, row_off, true, n, R, layout, slot, clamp, eps, nullptr, nullptr, weight, grad_rot, grad_trans, grad_pos);
+}
+
+#undef FCZ_FAPE_INPUTS
+#undef FCZ_FAPE_IN
 
 }  // extern "C"
 

@@ -17,6 +17,9 @@
     smooth_lddt(pred, true, atom="CA", cutoff=15.0) -> dict(lddt_soft [..] float32, lddt_pairs int32, lddt_soft_chain [n] float32, loss):
                                    the smooth lDDT of AlphaFold 3 on the same pairs, a loss: differentiable with respect to pred's
                                    pos, with a fused backward on the GPU
+    fape(pred, true, atom="CA", clamp=10.0, scale=10.0) -> dict(fape_frame [..] float32, fape_points int32, frame_mask bool, fape_chain [n]
+                                   float32, loss): the backbone FAPE of AlphaFold 2 (Algorithm 28) of predicted frames and points against
+                                   the truth's, a loss: differentiable with respect to pred's rot / trans / pos, with a fused backward
     lddt_atoms(pred, true, swaps="alphafold", per_atom=False) -> dict(lddt, lddt_pairs, lddt_hits, swapped [..] bool, lddt_chain [n]
                                    float64, atom_pairs / atom_hits [.., A]): the all-atom lDDT of every residue after the symmetric
                                    side-chain namings of the truth have been resolved towards the prediction
@@ -62,7 +65,7 @@ from ._aa_tables import RES1
 from .codec import ANGLE_COLUMNS, WIDTH_LAYOUTS, Codec, dense_layout
 from .structure import CAtomsOut, CDenseIn, CDenseOut, CLddtAtomsOut, CPackedOut, CSuperposeOut, CTmScoreOut, CGdtOut, CViolationsOut, CChainSet, CTmAlignOut, CTmAlignParams, TM_ALIGN_OUTPUTS
 
-__all__ = ["decode_tensors", "encode_tensors", "decode_angles", "crop_starts", "neighbor_graph", "rigid_frames", "lddt", "smooth_lddt", "lddt_atoms", "superpose", "tm_score", "gdt", "tm_align", "apply_transform",
+__all__ = ["decode_tensors", "encode_tensors", "decode_angles", "crop_starts", "neighbor_graph", "rigid_frames", "lddt", "smooth_lddt", "fape", "lddt_atoms", "superpose", "tm_score", "gdt", "tm_align", "apply_transform",
            "backbone_hbonds", "secondary_structure", "solvent_accessibility", "violations"]
 
 
@@ -848,6 +851,223 @@ def smooth_lddt(pred, true, *, atom="CA", cutoff: float = 15.0, thresholds=(0.5,
     chain = torch.where(scored, cs / cp.clamp(min=1).to(torch.float64), cs.new_zeros(()))
     loss = (torch.where(scored, 1.0 - chain, chain.new_zeros(())).sum() / scored.sum().clamp(min=1).to(torch.float64)).to(torch.float32)
     return dict(lddt_soft=per_row, lddt_pairs=pairs, lddt_soft_chain=chain.to(torch.float32), loss=loss)
+
+
+def backbone_frames_torch(pos, mask=None):
+    """pos [.., A, 3] (N, CA, C in slots 0, 1, 2 as in every layout), mask [.., A] bool / uint8 or None -> (rot [.., 3, 3], trans
+    [.., 3], frame_mask [..] bool): AlphaFold's Algorithm 21 as rigid_frames(groups="backbone") defines it (origin CA, x axis CA -> C,
+    N in the half-plane y > 0, columns are the axes), in plain differentiable torch operations on any device, O(rows). A residue
+    whose three atoms are masked, not finite, coincident or collinear has frame_mask False, the identity and 0, and gives pos a
+    gradient that is exactly 0: every normalisation is guarded by a torch.where in FRONT of the root and the division, and what a
+    row that is no frame feeds the next step is replaced by 0, so no 0 * inf arises in the backward pass."""
+    import torch
+    n_, ca, c = pos[..., 0, :], pos[..., 1, :], pos[..., 2, :]
+    ok = torch.isfinite(n_).all(-1) & torch.isfinite(ca).all(-1) & torch.isfinite(c).all(-1)
+    if mask is not None:
+        m = mask.to(torch.bool)
+        ok = ok & m[..., 0] & m[..., 1] & m[..., 2]
+    zero, one = pos.new_zeros(()), pos.new_ones(())
+    ca0 = torch.where(ok[..., None], ca, zero)
+    v1 = torch.where(ok[..., None], c, zero) - ca0
+    v2 = torch.where(ok[..., None], n_, zero) - ca0
+    s1 = (v1 * v1).sum(-1)
+    g1 = ok & torch.isfinite(s1) & (s1 > 0)
+    v1, v2 = torch.where(g1[..., None], v1, zero), torch.where(g1[..., None], v2, zero)
+    e1 = v1 / torch.sqrt(torch.where(g1, s1, one))[..., None]
+    d = (e1 * v2).sum(-1)
+    gd = g1 & torch.isfinite(d)
+    u = torch.where(gd[..., None], v2, zero) - e1 * torch.where(gd, d, zero)[..., None]
+    s2 = (u * u).sum(-1)
+    g2 = gd & torch.isfinite(s2) & (s2 > 0)
+    u = torch.where(g2[..., None], u, zero)
+    e2 = u / torch.sqrt(torch.where(g2, s2, one))[..., None]
+    e1 = torch.where(g2[..., None], e1, zero)
+    e3 = torch.cross(e1, e2, dim=-1)
+    eye = torch.eye(3, dtype=pos.dtype, device=pos.device)
+    rot = torch.where(g2[..., None, None], torch.stack([e1, e2, e3], dim=-1), eye)
+    return rot, torch.where(g2[..., None], ca0, zero), g2
+
+
+_fape_autograd = {}
+
+
+def _fape_function(torch):
+    """the torch.autograd.Function of fape, made once torch is there"""
+    if _fape_autograd:
+        return _fape_autograd["fape"]
+    from torch.autograd.function import once_differentiable
+
+    class Fape(torch.autograd.Function):
+        """(pred rot, pred trans, pred points [.., 3]) -> sum [..] (fcz_fape_dev); `call` holds everything else of the call and
+        receives points. The backward is one gradient call (fcz_fape_grad_dev) on the saved inputs: nothing else is kept."""
+
+        @staticmethod
+        def forward(ctx, rot, trans, pts, call):
+            ctx.call = call
+            ctx.save_for_backward(rot, trans, pts)
+            return call.value(rot, trans, pts)
+
+        @staticmethod
+        @once_differentiable
+        def backward(ctx, grad_sum):
+            rot, trans, pts = ctx.saved_tensors
+            return (*ctx.call.gradient(rot, trans, pts, grad_sum.contiguous()), None)
+
+    _fape_autograd["fape"] = Fape
+    return Fape
+
+
+class _FapeCall:
+    """one call of fape: the checked truth and its frames, the prediction's masks and the parameters; value() and gradient() enqueue
+    the kernels on the codec's stream between a wait for torch's stream and codec.synchronize(), as every analysis function does.
+    pos_full: the prediction's whole pos tensor (detached) when it has one, whose slot the points are; None: the points are embedded
+    in a tensor of the truth's shape for the call"""
+
+    def __init__(self, x, tframes, pfmask, pos_full, pmask, slot, clamp, eps):
+        self.x, self.tframes, self.pfmask, self.pos_full, self.pmask = x, tframes, pfmask, pos_full, pmask
+        self.slot, self.clamp, self.eps = slot, clamp, eps
+        self.points = None
+
+    def _run(self, name, rot, trans, pts, *rest):
+        x, torch = self.x, self.x.torch
+        pos = self.pos_full
+        if pos is None:
+            pos = torch.zeros(x.shape, dtype=torch.float32, device=x.dev)
+            pos[..., self.slot, :] = pts
+        trot, ttrans, tfm = self.tframes
+        torch.cuda.current_stream(x.dev).synchronize()
+        _call(x.codec, name, x.is_packed, trot.data_ptr(), ttrans.data_ptr(), tfm.data_ptr(), x.pos.data_ptr(), x.mask.data_ptr(), rot.data_ptr(), trans.data_ptr(),
+              _ptr(self.pfmask), pos.data_ptr(), _ptr(self.pmask), _ptr(x.bound), x.n, x.rows, x.lay, self.slot, self.clamp, self.eps, *(o.data_ptr() for o in rest))
+        x.codec.synchronize()
+
+    def value(self, rot, trans, pts):
+        x = self.x
+        total = x.torch.zeros(x.lead, dtype=x.torch.float32, device=x.dev)
+        self.points = x.torch.zeros(x.lead, dtype=x.torch.int32, device=x.dev)
+        if total.numel():
+            self._run("fcz_fape", rot.detach().contiguous(), trans.detach().contiguous(), pts.detach(), total, self.points)
+        return total
+
+    def gradient(self, rot, trans, pts, weight):
+        x = self.x
+        grads = [x.torch.zeros(x.lead + s, dtype=x.torch.float32, device=x.dev) for s in ((3, 3), (3,), (3,))]
+        if weight.numel():
+            self._run("fcz_fape_grad", rot.contiguous(), trans.contiguous(), pts, weight, *grads)
+        return grads
+
+
+def fape(pred, true, *, atom="CA", clamp=10.0, scale: float = 10.0, eps: float = 1e-4, codec: Optional[Codec] = None) -> dict:
+    """predicted frames and points against true ones, dense tensors on the GPU -> dict(fape_frame, fape_points, frame_mask, fape_chain,
+    loss): the backbone FAPE (frame aligned point error; AlphaFold 2 supplement, Algorithm 28), a LOSS with a fused backward on the GPU
+    and no L x L array in either direction.
+
+    `true` is the dict decode_tensors / tensor_batches return, padded, packed or a window with crop_start. Its frames are its rot /
+    trans / frame_mask when it carries the backbone ones (decode_tensors(..., frames="backbone")), and are computed inside the call
+    (fcz_frames_dev) otherwise. `pred` is either
+      * a dict with rot [.., 3, 3] and trans [.., 3], the model's own frames, optionally frame_mask [..] and optionally pos / mask
+        of true's shape: the points are pos at `atom`, or trans when there is no pos (AlphaFold's backbone FAPE; trans.grad then
+        receives both contributions); or
+      * a pos tensor of true's shape, or a dict with pos (and mask): the predicted frames are built from N, CA, C of pos by
+        Algorithm 21 in differentiable torch operations (backbone_frames_torch) and autograd carries the gradient on to pos; a
+        degenerate or masked residue is no frame and gets a gradient of exactly 0.
+    A row is a frame when it lies inside its chain, both frame masks are set and the 24 floats are finite; a point as lddt's site.
+    Every frame meets every point of its chain: d = sqrt(|R^T (x - t) - R'^T (x' - t')|^2 + eps), term = min(d, clamp).
+        fape_frame   [n, L] / [R] float32   the mean of term over the chain's points, over scale; 0 where there is no frame or no point
+        fape_points  int32                  the points a frame row met
+        frame_mask   bool                   the frame rows
+        fape_chain   [n] float32            the chain's sum of term over (frames * points * scale), summed in float64
+        loss         scalar float32         the mean of fape_chain over the chains that have a frame and a point (0 without one)
+    clamp=None (or +inf) is the unclamped FAPE. When any of the prediction's tensors requires a gradient (and gradients are enabled)
+    the results carry a graph: loss.backward() runs the gradient call once (one torch.autograd.Function over rot, trans and the
+    points); the graph can be walked once and not differentiated twice. Under torch.no_grad(), or with nothing that requires a
+    gradient, only the value kernel runs. Every sum has a fixed order (rows in float32 in ascending row order on the device, chains
+    in float64, no atomics): value and gradient are reproducible bit for bit.
+
+    The tensors must be contiguous and lie on the codec's device; ordering against torch is decode_tensors'. The arguments are
+    checked first, without torch or a device (api.check_fape)."""
+    what = "fape"
+    t = dict(true) if isinstance(true, dict) else {"pos": true}
+    p = dict(pred) if isinstance(pred, dict) else {"pos": pred}
+    _need(what, t, of=" of true")
+    shape = tuple(getattr(t["pos"], "shape", ()))
+    slot, clamp, scale, eps = api.check_fape(clamp, scale, eps, atom, shape[-2] if len(shape) in (3, 4) else None)
+    if len(shape) not in (3, 4) or shape[-1] != 3 or shape[-2] not in _WIDTH_LAYOUT:
+        raise ValueError(f"pos must be float32 [n, L, A, 3], or [R, A, 3] beside cu_seqlens, with A = 37, 14 or 4, not {shape}")
+    lead = shape[:-2]
+    given = p.get("rot") is not None or p.get("trans") is not None
+    if given:
+        _need(what, p, ("rot", "trans"), " of pred")
+        for key, want in (("rot", lead + (3, 3)), ("trans", lead + (3,)), ("frame_mask", lead)):
+            if p.get(key) is not None and tuple(getattr(p[key], "shape", ())) != want:
+                raise ValueError(f"pred {key} must have the shape {want}, not {tuple(getattr(p[key], 'shape', ()))}")
+    else:
+        _need(what, p, ("pos",), " of pred")
+    for key, want in (("pos", shape), ("mask", shape[:-1])):
+        if p.get(key) is not None and tuple(getattr(p[key], "shape", ())) != want:
+            raise ValueError(f"pred {key} must have the shape of true {key}, {want}, not {tuple(getattr(p[key], 'shape', ()))}")
+    x = _dense_checked(what, "Codec.fape", codec, t, shape, t.get("cu_seqlens") is not None and len(shape) == 3, "full", aatype=False)
+    if x.rows > 2 ** 29:
+        raise ValueError("at most 2^29 rows per chain")
+    torch, dev = x.torch, x.dev
+    # the truth's frames: the dict's backbone ones, or fcz_frames_dev here
+    if all(t.get(k) is not None for k in ("rot", "trans", "frame_mask")) and tuple(getattr(t["rot"], "shape", ())) == lead + (3, 3):
+        tframes = (_on_device(torch, what, dev, "rot", t["rot"], lead + (3, 3), (torch.float32,)),
+                   _on_device(torch, what, dev, "trans", t["trans"], lead + (3,), (torch.float32,)),
+                   _on_device(torch, what, dev, "frame_mask", t["frame_mask"], lead, (torch.bool, torch.uint8)).view(torch.uint8))
+    else:
+        made = _frames_alloc(torch, dev, lead, 0)
+        if x.n and x.rows:
+            torch.cuda.current_stream(dev).synchronize()
+            _frames_into(x, 0, made)
+            x.codec.synchronize()
+        tframes = (made["rot"], made["trans"], made["frame_mask"].view(torch.uint8))
+    ppos, pmask = p.get("pos"), p.get("mask")
+    if ppos is not None:
+        _on_device(torch, what, dev, "pred pos", ppos, shape, (torch.float32,))
+    if pmask is not None:
+        pmask = _on_device(torch, what, dev, "pred mask", pmask, shape[:-1], (torch.bool, torch.uint8)).view(torch.uint8)
+    if given:
+        rot = _on_device(torch, what, dev, "pred rot", p["rot"], lead + (3, 3), (torch.float32,))
+        trans = _on_device(torch, what, dev, "pred trans", p["trans"], lead + (3,), (torch.float32,))
+        pfm = p.get("frame_mask")
+        if pfm is not None:
+            pfm = _on_device(torch, what, dev, "pred frame_mask", pfm, lead, (torch.bool, torch.uint8)).view(torch.uint8)
+    else:
+        rot, trans, pfm = backbone_frames_torch(ppos, pmask)
+        pfm = pfm.view(torch.uint8)
+    pts = trans if ppos is None else ppos[..., slot, :]
+    call = _FapeCall(x, tframes, pfm, None if ppos is None else ppos.detach(), pmask, slot, clamp, eps)
+    if torch.is_grad_enabled() and (rot.requires_grad or trans.requires_grad or pts.requires_grad):
+        total = _fape_function(torch).apply(rot, trans, pts, call)
+    else:
+        total = call.value(rot, trans, pts)
+    points = call.points
+    # the frame rows: inside their chain, both masks, 24 finite floats
+    with torch.no_grad():
+        fm = tframes[2] != 0
+        if pfm is not None:
+            fm = fm & (pfm != 0)
+        for v in (tframes[0], rot.detach()):
+            fm = fm & torch.isfinite(v).all(-1).all(-1)
+        for v in (tframes[1], trans.detach()):
+            fm = fm & torch.isfinite(v).all(-1)
+        if x.is_packed:
+            r = torch.arange(x.rows, device=dev)
+            fm = fm & (r >= x.bound[0]) & (r < x.bound[-1])
+        elif x.bound is not None:
+            fm = fm & (torch.arange(x.rows, device=dev)[None, :] < x.bound[:, None])
+    has = points > 0
+    per_row = torch.where(has, total / (points.clamp(min=1).to(torch.float32) * scale), total.new_zeros(()))
+    if x.is_packed:
+        at = x.bound.to(torch.int64)
+        cs = _autograd_functions(torch)[1].apply(total.to(torch.float64), at)
+        cp = torch.cat([at.new_zeros(1), points.to(torch.int64).cumsum(0)])[at].diff()
+    else:
+        cs, cp = total.to(torch.float64).sum(dim=1), points.to(torch.int64).sum(dim=1)
+    scored = cp > 0                                                           # (sum of points over the frame rows = frames * points)
+    chain = torch.where(scored, cs / (cp.clamp(min=1).to(torch.float64) * scale), cs.new_zeros(()))
+    loss = (chain.sum() / scored.sum().clamp(min=1).to(torch.float64)).to(torch.float32)
+    return dict(fape_frame=per_row, fape_points=points, frame_mask=fm, fape_chain=chain.to(torch.float32), loss=loss)
 
 
 def lddt_atoms(pred, true, *, cutoff: float = 15.0, thresholds=(0.5, 1.0, 2.0, 4.0), swaps="alphafold", per_atom: bool = False,

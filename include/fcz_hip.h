@@ -20,6 +20,7 @@
  *   (none: no neighbour graph of the decoded chain)        fcz_knn_dev / fcz_knn_packed_dev, fcz_knn / fcz_knn_packed
  *   (none: no score of one structure against another)      fcz_lddt_dev / fcz_lddt_packed_dev, fcz_lddt / fcz_lddt_packed
  *   (none: no loss, nothing with a gradient)               fcz_lddt_soft_dev / fcz_lddt_soft_grad_dev (+ _packed and host forms)
+ *   (none: no loss on frames)                              fcz_fape_dev / fcz_fape_grad_dev (+ _packed and host forms)
  *   (none: no all-atom score, no side-chain renaming)      fcz_lddt_atoms_dev / fcz_lddt_atoms_packed_dev, fcz_lddt_atoms / fcz_lddt_atoms_packed
  *   (none: no secondary structure)                         fcz_hbond_dev, fcz_dssp_labels_dev, fcz_dssp (+ _packed forms)
  *   (none: no solvent accessibility)                       fcz_sasa_dev / fcz_sasa_packed_dev, fcz_sasa / fcz_sasa_packed
@@ -505,6 +506,85 @@ int fcz_lddt_soft_grad(fcz_ctx* ctx, const float* pos_true, const uint8_t* mask_
 int fcz_lddt_soft_grad_packed(fcz_ctx* ctx, const float* pos_true, const uint8_t* mask_true, const float* pos_pred,
                               const uint8_t* mask_pred, const uint32_t* row_off, uint32_t n, uint32_t R, int layout, int slot,
                               float cutoff, const float* thresholds, const float* weight, float* grad);
+
+/* ---- backbone FAPE and its gradient ----------------------------------------------------------------------- */
+/* The frame aligned point error that frame-based structure models train on (Jumper et al. 2021, supplement, Algorithm 28), of the
+ * rigid frames and the points of one slot of a prediction against the truth's, with a fused backward pass, for a whole batch on the
+ * device without an L x L array in either direction. The reference has no such output. Everything is per chain, padded or packed,
+ * with fcz_lddt_dev's chain rules (length / row_off, ranges clamped, a range that runs backwards empty).
+ * Frames: rot [rows][3][3], trans [rows][3] float32 with global = rot . local + trans (fcz_frames_dev's convention, columns are the
+ * axes) and frame_mask [rows] bytes, for the truth and for the prediction. Row i is a FRAME when it lies inside its chain,
+ * fmask_true[i] != 0, fmask_pred[i] != 0 (a NULL fmask_pred is all set) and all 24 floats are finite.
+ * Points: pos [rows][A][3], mask [rows][A] of both. Row j is a POINT when it lies inside its chain, both masks at `slot` are set (a
+ * NULL mask_pred is all set) and its six coordinates are finite (the site rule of fcz_lddt_dev).
+ * Term, for frame i and point j of the same chain, j == i included; unprimed is the prediction, primed the truth:
+ *   u  = x_j - t_i            u' = x'_j - t'_i          three subtractions each
+ *   l  = R_i^T u              l' = R'_i^T u'            l_k = (R[0][k]*u0 + R[1][k]*u1) + R[2][k]*u2
+ *   e  = l - l'               s = (e0*e0 + e1*e1) + e2*e2
+ *   d  = sqrt(s + eps)        correctly rounded         term = min(d, clamp)
+ * all float32, every operation a single rounded one, no FMA. eps is finite and > 0 (Algorithm 28: 1e-4 A^2), clamp > 0 with +inf
+ * for unclamped. A d that is not finite adds nothing and has no gradient.
+ * Value (fcz_fape_dev):
+ *   sum [rows] float32    at a frame row the sum of term over the chain's points, in float32, in ASCENDING ROW ORDER of j; 0 elsewhere
+ *   points [rows] int32   at a frame row the number of points of its chain (whatever their d); 0 elsewhere
+ * Dividing by points, by the scale Z and by the number of frames is the caller's arithmetic.
+ * Gradient (fcz_fape_grad_dev) of sum_i w_i sum[i] for the caller's weight [rows] float32, with respect to the prediction's rot
+ * (the unconstrained partial derivative of its nine entries), trans and the slot's coordinates. With inv = the hardware reciprocal
+ * of d (within an ulp) and h = (e0 * inv, e1 * inv, e2 * inv) where d is finite and d < clamp, and no term otherwise:
+ *   grad_rot [rows][3][3]   grad_rot[i][a][k] = w_i * M[a][k], M[a][k] the sum over j, ascending, of u_a * h_k
+ *   grad_trans [rows][3]    grad_trans[i][a] = -(w_i * ((R[a][0]*H0 + R[a][1]*H1) + R[a][2]*H2)), H the sum over j, ascending, of h
+ *   grad_pos [rows][3]      grad_pos[j][a] = the sum over i, ascending, of w_i * ((R_i[a][0]*h0 + R_i[a][1]*h1) + R_i[a][2]*h2)
+ * every product and sum one rounded float32 operation. grad_rot and grad_trans are 0 at rows that are no frame, grad_pos at rows that
+ * are no point; a point's gradient belongs to pos_pred[j][slot]. One writer per output, no atomics, no scatter: the same chain gives
+ * the same bytes alone, in any batch, padded or packed, call after call. Weights of rows that are no frame are not read as data.
+ * When the prediction's points ARE its translations (AlphaFold's backbone FAPE) the caller adds grad_pos to grad_trans.
+ * Error, for rotations with orthonormal columns: with X the largest of |u|_inf, |u'|_inf of a term, |d - exact| <= (26 X + 4 d) 2^-24
+ * (tests/_fape.py derives it and the bounds of the sums).
+ * rows = n * L (padded) or R (packed). Every byte of the outputs is written whatever the inputs hold, nothing outside them, and
+ * nothing outside the inputs is read, whatever row_off holds. Every index that scales with rows * A is 64-bit. Passes are at most
+ * fcz_fape_pass() rows. Enqueued on the ctx stream, no synchronisation; one gradient call enqueues both of its sweeps.
+ * FCZ_E_INVALID_ARG with nothing launched and no output touched: a NULL required pointer (everything but fmask_pred, mask_pred and
+ * the padded form's length), NULL row_off with n > 0, an unknown layout, a slot outside the layout's width, L == 0, L or R above
+ * 2^29, a clamp that is NaN or not > 0, an eps that is not finite or not > 0. n == 0 or R == 0: FCZ_OK. The time goes to the groups
+ * "fape" and "fape_grad". */
+int fcz_fape_pass(void);
+int fcz_fape_dev(fcz_ctx* ctx, const float* rot_true_dev, const float* trans_true_dev, const uint8_t* fmask_true_dev,
+                 const float* pos_true_dev, const uint8_t* mask_true_dev, const float* rot_pred_dev, const float* trans_pred_dev,
+                 const uint8_t* fmask_pred_dev, const float* pos_pred_dev, const uint8_t* mask_pred_dev, const uint32_t* length_dev,
+                 uint32_t n, uint32_t L, int layout, int slot, float clamp, float eps, float* sum_dev, int32_t* points_dev);
+int fcz_fape_packed_dev(fcz_ctx* ctx, const float* rot_true_dev, const float* trans_true_dev, const uint8_t* fmask_true_dev,
+                        const float* pos_true_dev, const uint8_t* mask_true_dev, const float* rot_pred_dev, const float* trans_pred_dev,
+                        const uint8_t* fmask_pred_dev, const float* pos_pred_dev, const uint8_t* mask_pred_dev,
+                        const uint32_t* row_off_dev, uint32_t n, uint32_t R, int layout, int slot, float clamp, float eps,
+                        float* sum_dev, int32_t* points_dev);
+int fcz_fape_grad_dev(fcz_ctx* ctx, const float* rot_true_dev, const float* trans_true_dev, const uint8_t* fmask_true_dev,
+                      const float* pos_true_dev, const uint8_t* mask_true_dev, const float* rot_pred_dev, const float* trans_pred_dev,
+                      const uint8_t* fmask_pred_dev, const float* pos_pred_dev, const uint8_t* mask_pred_dev,
+                      const uint32_t* length_dev, uint32_t n, uint32_t L, int layout, int slot, float clamp, float eps,
+                      const float* weight_dev, float* grad_rot_dev, float* grad_trans_dev, float* grad_pos_dev);
+int fcz_fape_grad_packed_dev(fcz_ctx* ctx, const float* rot_true_dev, const float* trans_true_dev, const uint8_t* fmask_true_dev,
+                             const float* pos_true_dev, const uint8_t* mask_true_dev, const float* rot_pred_dev,
+                             const float* trans_pred_dev, const uint8_t* fmask_pred_dev, const float* pos_pred_dev,
+                             const uint8_t* mask_pred_dev, const uint32_t* row_off_dev, uint32_t n, uint32_t R, int layout, int slot,
+                             float clamp, float eps, const float* weight_dev, float* grad_rot_dev, float* grad_trans_dev,
+                             float* grad_pos_dev);
+/* Host-pointer conveniences: the same arrays on the host, staged through the ctx like fcz_lddt_soft; synchronous. */
+int fcz_fape(fcz_ctx* ctx, const float* rot_true, const float* trans_true, const uint8_t* fmask_true, const float* pos_true,
+             const uint8_t* mask_true, const float* rot_pred, const float* trans_pred, const uint8_t* fmask_pred, const float* pos_pred,
+             const uint8_t* mask_pred, const uint32_t* length, uint32_t n, uint32_t L, int layout, int slot, float clamp, float eps,
+             float* sum, int32_t* points);
+int fcz_fape_packed(fcz_ctx* ctx, const float* rot_true, const float* trans_true, const uint8_t* fmask_true, const float* pos_true,
+                    const uint8_t* mask_true, const float* rot_pred, const float* trans_pred, const uint8_t* fmask_pred,
+                    const float* pos_pred, const uint8_t* mask_pred, const uint32_t* row_off, uint32_t n, uint32_t R, int layout,
+                    int slot, float clamp, float eps, float* sum, int32_t* points);
+int fcz_fape_grad(fcz_ctx* ctx, const float* rot_true, const float* trans_true, const uint8_t* fmask_true, const float* pos_true,
+                  const uint8_t* mask_true, const float* rot_pred, const float* trans_pred, const uint8_t* fmask_pred,
+                  const float* pos_pred, const uint8_t* mask_pred, const uint32_t* length, uint32_t n, uint32_t L, int layout, int slot,
+                  float clamp, float eps, const float* weight, float* grad_rot, float* grad_trans, float* grad_pos);
+int fcz_fape_grad_packed(fcz_ctx* ctx, const float* rot_true, const float* trans_true, const uint8_t* fmask_true, const float* pos_true,
+                         const uint8_t* mask_true, const float* rot_pred, const float* trans_pred, const uint8_t* fmask_pred,
+                         const float* pos_pred, const uint8_t* mask_pred, const uint32_t* row_off, uint32_t n, uint32_t R, int layout,
+                         int slot, float clamp, float eps, const float* weight, float* grad_rot, float* grad_trans, float* grad_pos);
 
 /* ---- all-atom lDDT with symmetric side-chain renaming ------------------------------------------------------ */
 /* The lDDT that CASP, CAMEO and model papers report: every heavy atom against every heavy atom of the other residues of its chain,

@@ -20,6 +20,7 @@ import numpy as np
 
 import _analysis as AN
 import _dssp as DS
+import _fape as FP
 import _frames as FRM
 import _gdt as GD
 import _knn as K
@@ -30,7 +31,7 @@ import _sasa as SA
 import _superpose as SP
 import _tmscore as TM
 import _violations as V
-from _devpath import FILL, to_dev
+from _devpath import FILL, GUARD, to_dev
 
 F = np.float32
 
@@ -246,10 +247,17 @@ class Analysis:
     tile_rows, per_cu = CHAIN_TILE, SWEEP_PER_CU
     chain_keys = frozenset()
     index_keys = frozenset()
+    guard = GUARD                                     # bytes of fill around every output of run(); 4: no output begins on 16 bytes
+    family = "pair"                                   # which generator of tests/_analysis_fuzz.py draws the inputs of fuzz_pool
 
     @property
     def layout(self):
         return LAYOUT[self.A]
+
+    def fuzz_pool(self, rng, lens, L, profile):
+        """the inputs of pool() for any lengths, drawn by tests/_analysis_fuzz.py from `profile` (a string per chain and one for the case)"""
+        import _analysis_fuzz as FZ
+        return FZ.draw(self, rng, lens, L, profile)
 
     def launches(self):
         """(what, tile rows, blocks per CU) of every sweep launch of one call"""
@@ -341,6 +349,7 @@ def lattice_pool(lens, L, A, slot, seed):
 
 
 class Knn(Analysis):
+    family = "site"
     index_keys = frozenset({"index"})
     K_REF = 17                                       # the restatement's k: a smaller k is the first k columns of the same order
 
@@ -356,7 +365,7 @@ class Knn(Analysis):
         return dict(index=index, dist=dist)
 
     def run(self, codec, dev, bound_t, n, rows, packed):
-        index, dist = K.run_dev(codec, dev["pos"], dev["mask"], bound_t, n, rows, self.layout, self.slot, self.k, packed)
+        index, dist = K.run_dev(codec, dev["pos"], dev["mask"], bound_t, n, rows, self.layout, self.slot, self.k, packed, guard=self.guard)
         return dict(index=index, dist=dist)
 
     def check(self, got, exp, what):
@@ -379,7 +388,7 @@ class Lddt(Analysis):
         return dict(zip(("score", "pairs", "hits"), Q.lddt_padded(inp["pt"], inp["mt"], inp["pp"], inp["mp"], lens, self.slot)))
 
     def run(self, codec, dev, bound_t, n, rows, packed):
-        got = Q.run_dev(codec, dev["pt"], dev["mt"], dev["pp"], dev["mp"], bound_t, n, rows, self.layout, self.slot, packed)
+        got = Q.run_dev(codec, dev["pt"], dev["mt"], dev["pp"], dev["mp"], bound_t, n, rows, self.layout, self.slot, packed, guard=self.guard)
         return dict(zip(("score", "pairs", "hits"), got))
 
     def check(self, got, exp, what):
@@ -412,8 +421,8 @@ class LddtSoft(Analysis):
 
     def run(self, codec, dev, bound_t, n, rows, packed):
         a = (dev["pt"], dev["mt"], dev["pp"], None, bound_t, n, rows, self.layout, self.slot, packed)
-        soft, pairs = S.run_value(codec, *a)
-        return dict(soft=soft, pairs=pairs, grad=S.run_grad(codec, *a, dev["w"]))
+        soft, pairs = S.run_value(codec, *a, guard=self.guard)
+        return dict(soft=soft, pairs=pairs, grad=S.run_grad(codec, *a, dev["w"], guard=self.guard))
 
     def check(self, got, exp, what):
         S.check_value((got["soft"], got["pairs"]), exp, what)
@@ -447,6 +456,7 @@ TABLE_KEYS = ("acc_index", "acc_energy", "don_index", "don_energy")
 
 
 class Hbond(Analysis):
+    family = "backbone"
     name = "hbond"
     index_keys = frozenset({"acc_index", "don_index"})
 
@@ -457,7 +467,7 @@ class Hbond(Analysis):
         return dict(zip(TABLE_KEYS, DS.hbonds(inp["pos"], inp["mask"], inp["aatype"], lens)))
 
     def run(self, codec, dev, bound_t, n, rows, packed):
-        return dict(zip(TABLE_KEYS, DS.run_hbond(codec, dev["pos"], dev["mask"], dev["aatype"], bound_t, n, rows, self.layout, packed)))
+        return dict(zip(TABLE_KEYS, DS.run_hbond(codec, dev["pos"], dev["mask"], dev["aatype"], bound_t, n, rows, self.layout, packed, guard=self.guard)))
 
     def check(self, got, exp, what):
         DS.same_tables([got[k] for k in TABLE_KEYS], [exp[k] for k in TABLE_KEYS], what)
@@ -465,6 +475,7 @@ class Hbond(Analysis):
 
 class Labels(Analysis):
     """the label kernels on the acceptor table of the restatement"""
+    family = "labels"
     name = "dssp labels"
     index_keys = frozenset({"acc_index"})
 
@@ -477,7 +488,7 @@ class Labels(Analysis):
         return dict(ss=ss, ss_mask=ss_mask.view(np.uint8))
 
     def run(self, codec, dev, bound_t, n, rows, packed):
-        ss, ss_mask = DS.run_labels(codec, dev["pos"], dev["mask"], dev["aatype"], bound_t, n, rows, self.layout, packed, dev["acc_index"], dev["acc_energy"])
+        ss, ss_mask = DS.run_labels(codec, dev["pos"], dev["mask"], dev["aatype"], bound_t, n, rows, self.layout, packed, dev["acc_index"], dev["acc_energy"], guard=self.guard)
         return dict(ss=ss, ss_mask=ss_mask)
 
     def check(self, got, exp, what):
@@ -487,6 +498,7 @@ class Labels(Analysis):
 class Apply(Analysis):
     """k_superpose_apply: a transform per chain on every atom of its rows (no non-finite coordinate under a set mask here: the payload
     of a NaN result is not part of the contract, and the comparison is on bytes)"""
+    family = "apply"
     name = "superpose_apply"
     chain_keys = frozenset({"rot", "trans"})
 
@@ -502,7 +514,7 @@ class Apply(Analysis):
         return dict(out=SP.apply_expected(inp["pos"], inp["mask"], inp["rot"], inp["trans"], length=lens))
 
     def run(self, codec, dev, bound_t, n, rows, packed):
-        return dict(out=SP.run_apply(codec, dev["pos"], dev["mask"], bound_t, n, rows, self.layout, dev["rot"], dev["trans"], packed))
+        return dict(out=SP.run_apply(codec, dev["pos"], dev["mask"], bound_t, n, rows, self.layout, dev["rot"], dev["trans"], packed, guard=self.guard))
 
     def check(self, got, exp, what):
         assert got["out"].shape == exp["out"].shape and got["out"].tobytes() == exp["out"].tobytes(), (what, np.argwhere(AN.bits(got["out"]) != AN.bits(exp["out"]))[:4])
@@ -551,6 +563,7 @@ SASA_KEYS = ("sasa_points", "sasa", "sasa_mask")
 
 
 class Sasa(Analysis):
+    family = "atoms"
     tile_rows = SASA_TILE_ROWS
     N_POINTS = 1                                       # the smallest point set test_gpu_sasa.py passes to run_sasa
 
@@ -574,13 +587,14 @@ class Sasa(Analysis):
         assert atoms > ATOM_PASS, (atoms, "the long chain takes one pass only")
 
     def run(self, codec, dev, bound_t, n, rows, packed):
-        return dict(zip(SASA_KEYS, SA.run_sasa(codec, dev["pos"], dev["mask"], dev["aatype"], bound_t, n, rows, self.layout, packed, to_dev(self.points()))))
+        return dict(zip(SASA_KEYS, SA.run_sasa(codec, dev["pos"], dev["mask"], dev["aatype"], bound_t, n, rows, self.layout, packed, to_dev(self.points()), guard=self.guard)))
 
     def check(self, got, exp, what):
         SA.same_sasa([got[k] for k in SASA_KEYS], [exp[k] for k in SASA_KEYS], what)
 
 
 class Violations(Analysis):
+    family = "atoms"
     per_cu = ATOMS_PER_CU
     chain_keys = frozenset({"chain_counts"})
 
@@ -597,7 +611,7 @@ class Violations(Analysis):
     fair = Sasa.fair
 
     def run(self, codec, dev, bound_t, n, rows, packed):
-        return V.run_violations(codec, dev["pos"], dev["mask"], dev["aatype"], bound_t, n, rows, self.layout, packed)
+        return V.run_violations(codec, dev["pos"], dev["mask"], dev["aatype"], bound_t, n, rows, self.layout, packed, guard=self.guard)
 
     def check(self, got, exp, what):
         V.same_violations(got, exp, what)
@@ -608,6 +622,7 @@ SWAP_TYPES = (LA.ASP, LA.GLU, LA.PHE, LA.TYR)
 
 
 class LddtAtoms(Analysis):
+    family = "atom_pair"
     per_cu = ATOMS_PER_CU
 
     def __init__(self, A=14):
@@ -661,7 +676,7 @@ class LddtAtoms(Analysis):
         assert sw.any() and (np.diff(sw.astype(np.int8), axis=1) != 0).any(), "no row was renamed"
 
     def run(self, codec, dev, bound_t, n, rows, packed):
-        return LA.run_dev(codec, dev["pt"], dev["mt"], dev["pp"], dev["mp"], dev["aatype"], bound_t, n, rows, self.layout, packed)
+        return LA.run_dev(codec, dev["pt"], dev["mt"], dev["pp"], dev["mp"], dev["aatype"], bound_t, n, rows, self.layout, packed, guard=self.guard)
 
     def check(self, got, exp, what):
         LA.same(got, exp, what)
@@ -707,7 +722,7 @@ class Superpose(Analysis):
                 assert SP.horn_gap(inp["pt"][e, :m, self.slot], inp["pp"][e, :m, self.slot], s) >= 1e-3, e
 
     def run(self, codec, dev, bound_t, n, rows, packed):
-        return SP.run_dev(codec, dev["pt"], dev["mt"], dev["pp"], dev["mp"], bound_t, n, rows, self.layout, self.slot, packed)
+        return SP.run_dev(codec, dev["pt"], dev["mt"], dev["pp"], dev["mp"], bound_t, n, rows, self.layout, self.slot, packed, guard=self.guard)
 
     def check(self, got, exp, what):
         SP.close(got, exp, what, compare_rot=exp["sites"] >= 3)
@@ -746,7 +761,7 @@ class TmScore(Superpose):
         print(f"{self.name} pool: margin, Horn gap, lead", TM.assert_fair(inp["pt"], inp["pp"], self.slot, self.traces, self.name))
 
     def run(self, codec, dev, bound_t, n, rows, packed):
-        return TM.run_dev(codec, dev["pt"], dev["mt"], dev["pp"], dev["mp"], bound_t, n, rows, self.layout, self.slot, packed)
+        return TM.run_dev(codec, dev["pt"], dev["mt"], dev["pp"], dev["mp"], bound_t, n, rows, self.layout, self.slot, packed, guard=self.guard)
 
     def check(self, got, exp, what):
         for k in ("seed", "selected"):
@@ -772,7 +787,7 @@ class Gdt(Superpose):
         print(f"{self.name} pool: (a), (b), (c)", GD.assert_fair(inp["pt"], inp["pp"], self.slot, self.traces, self.name))
 
     def run(self, codec, dev, bound_t, n, rows, packed):
-        return GD.run_dev(codec, dev["pt"], dev["mt"], dev["pp"], dev["mp"], bound_t, n, rows, self.layout, self.slot, packed)
+        return GD.run_dev(codec, dev["pt"], dev["mt"], dev["pp"], dev["mp"], bound_t, n, rows, self.layout, self.slot, packed, guard=self.guard)
 
     def check(self, got, exp, what):
         solved = exp["sites"] >= 3
@@ -784,6 +799,7 @@ class Gdt(Superpose):
 
 class Frames(Analysis):
     """k_frames: tiles of FR_ITEMS / G rows of the FLAT row space, so a tile spans entries; padded only"""
+    family = "atoms"
     A = 14
     per_cu = FRAMES_PER_CU
 
@@ -809,10 +825,42 @@ class Frames(Analysis):
         return dict(zip(("rot", "trans", "frame_mask"), FRM.frames(inp["pos"], inp["mask"], inp["aatype"], lens, self.layout, self.groups)))
 
     def run(self, codec, dev, bound_t, n, rows, packed):
-        return dict(zip(("rot", "trans", "frame_mask"), FRM.run_dev(codec, dev["pos"], dev["mask"], dev["aatype"], bound_t, n, rows, self.layout, self.groups)))
+        return dict(zip(("rot", "trans", "frame_mask"), FRM.run_dev(codec, dev["pos"], dev["mask"], dev["aatype"], bound_t, n, rows, self.layout, self.groups, guard=self.guard)))
 
     def check(self, got, exp, what):
         FRM.same([got[k] for k in ("rot", "trans", "frame_mask")], [exp[k] for k in ("rot", "trans", "frame_mask")], what)
+
+
+FAPE_PASS = 1024                # fcz_fape.h: constexpr uint32_t FAPE_PASS = 1024 (fcz_fape_pass(); k_fape_grad_points stages 256 frames a pass)
+FAPE_FRAME_PASS = 256           # fcz_fape.h: constexpr uint32_t FAPE_FRAME_PASS = 256
+
+
+class Fape(Analysis):
+    """the value and the two gradient sweeps of one call each: three launches over CHAIN_TILE rows a tile, 16 blocks a CU"""
+    name = "fape"
+    family = "fape"
+    clamp = FP.LATTICE_CLAMP
+
+    def launches(self):
+        return [(f"{self.name} {k}", self.tile_rows, self.per_cu) for k in ("value", "grad frames", "grad points")]
+
+    def pool(self, lens, L):
+        inp = FP.lattice(lens, L, self.A, self.slot, FP.SYNTH_SEED + 7, behind="data")
+        return dict(inp, w=FP.weights((len(lens), L), FP.SYNTH_SEED + 8))
+
+    def ref(self, inp, lens):
+        return FP.fape_padded(inp, lens, self.slot, inp["w"], self.clamp)
+
+    def fair(self, inp, ref, lens):
+        assert FP.tie_share(ref) == 0 and ref["frame"].any() and ref["point"].any()
+
+    def run(self, codec, dev, bound_t, n, rows, packed):
+        got = FP.run_both(codec, [dev[k] for k in FP.ORDER], bound_t, n, rows, self.layout, self.slot, packed, dev["w"], clamp=self.clamp, guard=self.guard)
+        return dict(zip(FP.OUT_KEYS, got))
+
+    def check(self, got, exp, what):
+        FP.check_value((got["sum"], got["points"]), exp, what)
+        FP.check_grad((got["grad_rot"], got["grad_trans"], got["grad_pos"]), exp, what)
 
 
 HBOND = Hbond()

@@ -7,39 +7,11 @@ without a device for 64, 256 and 304 CUs."""
 import numpy as np
 import pytest
 
-import _fape as FP
 import _sweep_grids as G
 
-FAPE_PASS = 1024                # fcz_fape.h: constexpr uint32_t FAPE_PASS = 1024 (fcz_fape_pass(); k_fape_grad_points stages 256 frames a pass)
+FAPE_PASS = G.FAPE_PASS         # fcz_fape.h, mirrored in tests/_sweep_grids.py beside the Fape analysis (tests/_analysis_fuzz.py shares it)
 
-
-class Fape(G.Analysis):
-    """the value and the two gradient sweeps of one call each: three launches over CHAIN_TILE rows a tile, 16 blocks a CU"""
-    name = "fape"
-
-    def launches(self):
-        return [(f"{self.name} {k}", self.tile_rows, self.per_cu) for k in ("value", "grad frames", "grad points")]
-
-    def pool(self, lens, L):
-        inp = FP.lattice(lens, L, self.A, self.slot, FP.SYNTH_SEED + 7, behind="data")
-        return dict(inp, w=FP.weights((len(lens), L), FP.SYNTH_SEED + 8))
-
-    def ref(self, inp, lens):
-        return FP.fape_padded(inp, lens, self.slot, inp["w"], FP.LATTICE_CLAMP)
-
-    def fair(self, inp, ref, lens):
-        assert FP.tie_share(ref) == 0 and ref["frame"].any() and ref["point"].any()
-
-    def run(self, codec, dev, bound_t, n, rows, packed):
-        got = FP.run_both(codec, [dev[k] for k in FP.ORDER], bound_t, n, rows, self.layout, self.slot, packed, dev["w"], clamp=FP.LATTICE_CLAMP)
-        return dict(zip(FP.OUT_KEYS, got))
-
-    def check(self, got, exp, what):
-        FP.check_value((got["sum"], got["points"]), exp, what)
-        FP.check_grad((got["grad_rot"], got["grad_trans"], got["grad_pos"]), exp, what)
-
-
-FAPE = Fape()
+FAPE = G.Fape()
 CASES = [G.Case(FAPE, "one", False), G.Case(FAPE, "one", True), G.Case(FAPE, "three"), G.Case(FAPE, "passes", own_pass=FAPE_PASS)]
 
 

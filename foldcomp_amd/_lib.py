@@ -129,6 +129,15 @@ def load():
         "fcz_violations_packed_dev": (i32, [vp, vp, vp, vp, vp, u32, u32, i32, vp, f32, f32, ctypes.POINTER(CViolationsOut)]),
         "fcz_violations": (i32, [vp, vp, vp, vp, vp, u32, u32, i32, vp, f32, f32, ctypes.POINTER(CViolationsOut)]),
         "fcz_violations_packed": (i32, [vp, vp, vp, vp, vp, u32, u32, i32, vp, f32, f32, ctypes.POINTER(CViolationsOut)]),
+        "fcz_violation_loss_pass": (i32, []),
+        "fcz_violation_loss_dev": (i32, [vp, vp, vp, vp, vp, u32, u32, i32, vp, f32, f32, vp, vp, vp]),
+        "fcz_violation_loss_packed_dev": (i32, [vp, vp, vp, vp, vp, u32, u32, i32, vp, f32, f32, vp, vp, vp]),
+        "fcz_violation_loss_grad_dev": (i32, [vp, vp, vp, vp, vp, u32, u32, i32, vp, f32, f32, vp, vp, vp]),
+        "fcz_violation_loss_grad_packed_dev": (i32, [vp, vp, vp, vp, vp, u32, u32, i32, vp, f32, f32, vp, vp, vp]),
+        "fcz_violation_loss": (i32, [vp, vp, vp, vp, vp, u32, u32, i32, vp, f32, f32, vp, vp, vp]),
+        "fcz_violation_loss_packed": (i32, [vp, vp, vp, vp, vp, u32, u32, i32, vp, f32, f32, vp, vp, vp]),
+        "fcz_violation_loss_grad": (i32, [vp, vp, vp, vp, vp, u32, u32, i32, vp, f32, f32, vp, vp, vp]),
+        "fcz_violation_loss_grad_packed": (i32, [vp, vp, vp, vp, vp, u32, u32, i32, vp, f32, f32, vp, vp, vp]),
         "fcz_superpose_dev": (i32, [vp, vp, vp, vp, vp, vp, u32, u32, i32, i32, ctypes.POINTER(CSuperposeOut)]),
         "fcz_superpose_packed_dev": (i32, [vp, vp, vp, vp, vp, vp, u32, u32, i32, i32, ctypes.POINTER(CSuperposeOut)]),
         "fcz_superpose": (i32, [vp, vp, vp, vp, vp, vp, u32, u32, i32, i32, ctypes.POINTER(CSuperposeOut)]),
@@ -228,6 +237,8 @@ EXPORTS = ["fcz_ctx_create", "fcz_ctx_destroy", "fcz_ctx_stream", "fcz_ctx_synch
            "fcz_hbond_pass", "fcz_hbond_dev", "fcz_hbond_packed_dev", "fcz_dssp_labels_dev", "fcz_dssp_labels_packed_dev", "fcz_dssp", "fcz_dssp_packed",
            "fcz_sasa_pass", "fcz_sasa_default_radii", "fcz_sasa_dev", "fcz_sasa_packed_dev", "fcz_sasa", "fcz_sasa_packed",
            "fcz_violations_pass", "fcz_violations_dev", "fcz_violations_packed_dev", "fcz_violations", "fcz_violations_packed",
+           "fcz_violation_loss_pass", "fcz_violation_loss_dev", "fcz_violation_loss_packed_dev", "fcz_violation_loss_grad_dev",
+           "fcz_violation_loss_grad_packed_dev", "fcz_violation_loss", "fcz_violation_loss_packed", "fcz_violation_loss_grad", "fcz_violation_loss_grad_packed",
            "fcz_superpose_dev", "fcz_superpose_packed_dev", "fcz_superpose", "fcz_superpose_packed",
            "fcz_superpose_apply_dev", "fcz_superpose_apply_packed_dev", "fcz_superpose_apply", "fcz_superpose_apply_packed",
            "fcz_tmscore_seeds", "fcz_tmscore_seed_fragment", "fcz_tmscore_dev", "fcz_tmscore_packed_dev", "fcz_tmscore", "fcz_tmscore_packed",

@@ -745,6 +745,13 @@ def check_violations(what, d, tolerance=VIOLATION_TOLERANCE, link_factor=VIOLATI
     return shape, packed, table
 
 
+def check_violation_loss(what, d, tolerance=VIOLATION_TOLERANCE, link_factor=VIOLATION_LINK_FACTOR, radii="bondi"):
+    """the argument rules of violation_loss that need no torch and no GPU, on the dict `d` that holds the prediction's pos beside the
+    truth's mask, aatype and length or cu_seqlens -> (shape of pos, packed, radii float32 [21, A] or None): check_violations' rules,
+    all of them (include/fcz_hip.h, fcz_violation_loss_dev refuses what fcz_violations_dev refuses)"""
+    return check_violations(what, d, tolerance, link_factor, radii)
+
+
 # the rigid groups of groups="all", indexed like AlphaFold / OpenFold rigidgroups_gt_frames (include/fcz_hip.h, fcz_frames_dev)
 FRAME_GROUPS = ("backbone", "unused_1", "unused_2", "psi", "chi1", "chi2", "chi3", "chi4")
 FRAME_GROUP_SETS = {"backbone": 0, "all": 1}                                 # enum fcz_frame_groups

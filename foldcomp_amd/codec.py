@@ -526,6 +526,40 @@ class Codec:
                 out[key] = out[key].view(np.bool_)
         return out
 
+    def violation_loss(self, pos: np.ndarray, mask: np.ndarray, aatype=None, length=None, row_off=None, *, tolerance: float = 1.5,
+                       link_factor: float = 12.0, radii="bondi"):
+        """dense arrays on the host -> the violation loss of every chain (fcz_violation_loss, or fcz_violation_loss_packed when
+        row_off is given): clash_loss float32 [.., A], for every atom the sum of (Ri + Rj) - tolerance - distance over the atoms of
+        other residues it clashes with, in ascending (row, slot); link_loss float32 [.., 3], how far the C-N' length and the two
+        peptide cosines of the link to the next row lie outside link_factor sigmas; counts int64 [n, 2], the chain's atoms and links.
+        The arrays and the parameters are Codec.violations'; atoms, pairs and links are its too. Reproducible bit for bit."""
+        from . import api
+        a = _dense_arrays(pos, mask, aatype, length, row_off)
+        _, _, table = api.check_violation_loss("Codec.violation_loss", a.as_dict(row_off), tolerance, link_factor, radii)
+        out = dict(clash_loss=np.zeros(a.lead + (a.A,), np.float32), link_loss=np.zeros(a.lead + (3,), np.float32), counts=np.zeros((a.n, 2), np.int64))
+        if out["link_loss"].size:
+            self._call("fcz_violation_loss", a.packed, a.pos.ctypes.data, a.mask.ctypes.data, _addr(a.aatype), _addr(a.bound), a.n, a.rows, a.lay, _addr(table),
+                       float(tolerance), float(link_factor), out["clash_loss"].ctypes.data, out["link_loss"].ctypes.data, out["counts"].ctypes.data)
+        return out
+
+    def violation_loss_grad(self, pos: np.ndarray, mask: np.ndarray, w_clash: np.ndarray, w_link: np.ndarray, aatype=None, length=None, row_off=None, *,
+                            tolerance: float = 1.5, link_factor: float = 12.0, radii="bondi"):
+        """the gradient of sum w_clash * clash_loss + sum w_link * link_loss of violation_loss with respect to pos
+        (fcz_violation_loss_grad, or fcz_violation_loss_grad_packed when row_off is given): float32 of pos' shape, 0 where a slot is
+        neither an atom nor a link atom. w_clash float32 [.., A], w_link float32 [.., 3]. Gathered per slot in a fixed order without
+        atomics: reproducible bit for bit."""
+        from . import api
+        a = _dense_arrays(pos, mask, aatype, length, row_off)
+        _, _, table = api.check_violation_loss("Codec.violation_loss_grad", a.as_dict(row_off), tolerance, link_factor, radii)
+        w_clash, w_link = np.ascontiguousarray(w_clash, np.float32), np.ascontiguousarray(w_link, np.float32)
+        if w_clash.shape != a.lead + (a.A,) or w_link.shape != a.lead + (3,):
+            raise ValueError(f"w_clash must be float32 {a.lead + (a.A,)} and w_link {a.lead + (3,)}, not {w_clash.shape} and {w_link.shape}")
+        grad = np.zeros(a.lead + (a.A, 3), np.float32)
+        if grad.size:
+            self._call("fcz_violation_loss_grad", a.packed, a.pos.ctypes.data, a.mask.ctypes.data, _addr(a.aatype), _addr(a.bound), a.n, a.rows, a.lay,
+                       _addr(table), float(tolerance), float(link_factor), w_clash.ctypes.data, w_link.ctypes.data, grad.ctypes.data)
+        return grad
+
     def superpose(self, pos_true: np.ndarray, mask_true: np.ndarray, pos_pred: np.ndarray, mask_pred=None, slot: int = 1, length=None, row_off=None):
         """two sets of dense arrays of one shape on the host -> the least-squares superposition of every chain of `pred` onto `true`
         on the sites at `slot` (fcz_superpose, or fcz_superpose_packed when row_off is given): rot float32 [n, 3, 3] and trans [n, 3]

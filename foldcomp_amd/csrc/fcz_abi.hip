@@ -40,6 +40,7 @@
 #include "fcz_dssp.h"
 #include "fcz_sasa.h"
 #include "fcz_violations.h"
+#include "fcz_violation_loss.h"
 #include "fcz_lddt_atoms.h"
 #include "fcz_superpose.h"
 #include "fcz_tmscore.h"
@@ -106,7 +107,8 @@ struct timed_span { std::string name; hipEvent_t a, b; };
 // SUPERPOSE_OUT: the seven arrays of a fcz_superpose_out in the struct's order; APPLY_ROT, APPLY_TRANS, APPLY_OUT: the transforms and the moved
 // coordinates of fcz_superpose_apply (its pos and mask go through LDDT_PRED); TM_SEED, TM_SELECTED: the two arrays a fcz_tmscore_out adds to those seven;
 // GDT_OUT: the eight arrays of a fcz_gdt_out in the struct's order;
-// VIOL_OUT .. VIOL_OUT_LAST: the ten arrays of a fcz_violations_out in the struct's order; LDDTA_OUT: the six of a fcz_lddt_atoms_out;
+// VIOL_OUT .. VIOL_OUT_LAST: the ten arrays of a fcz_violations_out in the struct's order; VLOSS_WEIGHT: w_clash, w_link of fcz_violation_loss_grad,
+// VLOSS_OUT: clash_loss, link_loss, counts of fcz_violation_loss (fcz_violation_loss_grad: grad); LDDTA_OUT: the six of a fcz_lddt_atoms_out;
 // TA_SETS: pos, mask, length / row_off of the two fcz_chain_set of fcz_tmalign, TA_PAIRS: its pairs, TA_OUT: the thirteen arrays of a fcz_tmalign_out in the
 // struct's order; TA_DP_*: the transforms, map and aligned of fcz_tmalign_dp
 enum { REC_BLOB, REC_OFF, REC_RES_OFF, REC_ATOM_OFF, REC_X, REC_Y, REC_Z, REC_BFAC, REC_RES_CODE, REC_ATOM_CODE,
@@ -114,7 +116,7 @@ enum { REC_BLOB, REC_OFF, REC_RES_OFF, REC_ATOM_OFF, REC_X, REC_Y, REC_Z, REC_BF
        SASA_POINTS = 4, SASA_OUT = 10,
        APPLY_ROT = 10, APPLY_TRANS, APPLY_OUT,
        ANGLES_OUT = 10, KEPT_OFF = 13, KEPT_BYTES, KEPT_STATUS, DENSE_CHAIN_INDEX, WINDOW_START = DENSE_CHAIN_INDEX, TM_SEED, TM_SELECTED,
-       VIOL_OUT = 10, LDDTA_OUT = 10, GDT_OUT = 10, TA_SETS = 0, TA_PAIRS = 6, TA_OUT = 7, TA_DP_ROT = 7, TA_DP_TRANS, TA_DP_MAP, TA_DP_ALIGNED, VIOL_OUT_LAST = 19, POOL_COUNT };
+       VIOL_OUT = 10, VLOSS_WEIGHT = 4, VLOSS_OUT = 10, LDDTA_OUT = 10, GDT_OUT = 10, TA_SETS = 0, TA_PAIRS = 6, TA_OUT = 7, TA_DP_ROT = 7, TA_DP_TRANS, TA_DP_MAP, TA_DP_ALIGNED, VIOL_OUT_LAST = 19, POOL_COUNT };
 static_assert(POOL_COUNT == VIOL_OUT_LAST + 1 && DENSE_OUT + 6 == DENSE_CHAIN_INDEX && LDDTA_OUT + 6 <= POOL_COUNT && TM_SELECTED < POOL_COUNT && GDT_OUT + 8 <= POOL_COUNT && TA_OUT + 13 <= POOL_COUNT && TA_SETS + 6 == TA_PAIRS &&
               TA_PAIRS < TA_OUT && TA_DP_ALIGNED < POOL_COUNT && FAPE_FRAMES + 6 == FAPE_OUT && FAPE_OUT + 3 <= POOL_COUNT, "the last name of the enum sizes fcz_ctx::pool");
 
@@ -206,6 +208,8 @@ struct fcz_ctx {
     //   fcz_frames                                  DENSE_IN 0 .. 3 (pos, mask, aatype, length), DENSE_OUT 10 .. 12 (rot, trans, frame_mask)
     //   fcz_sasa / fcz_sasa_packed                  DENSE_IN 0 .. 3 (pos, mask, aatype, length / row_off), SASA_POINTS 4, SASA_OUT 10 .. 12 (sasa_points, sasa, sasa_mask)
     //   fcz_violations / fcz_violations_packed      DENSE_IN 0 .. 3 (pos, mask, aatype, length / row_off), VIOL_OUT 10 .. 19 (the arrays of fcz_violations_out)
+    //   fcz_violation_loss / _packed                the inputs of fcz_violations, VLOSS_OUT 10 .. 12 (clash_loss, link_loss, counts)
+    //   fcz_violation_loss_grad / _grad_packed      the inputs of fcz_violations, VLOSS_WEIGHT 4 .. 5 (w_clash, w_link), VLOSS_OUT 10 (grad)
     //   fcz_tmalign                                 TA_SETS 0 .. 5 (pos, mask, length / row_off of a, then of b), TA_PAIRS 6, TA_OUT 7 .. 19
     //   fcz_tmalign_dp                              TA_SETS 0 .. 5, TA_PAIRS 6, TA_DP_ROT 7, TA_DP_TRANS 8, TA_DP_MAP 9, TA_DP_ALIGNED 10
     dev_buf pool[POOL_COUNT];
@@ -2563,10 +2567,11 @@ static bool viol_out_ok(const fcz_violations_out* o) {
 }
 
 // rows: L (padded) or R (packed). Fills tab from radius_table (NULL: the default) when everything is acceptable.
-static bool viol_args_ok(const fcz_ctx* ctx, const float* pos, const uint8_t* mask, const uint8_t* aatype, int layout, uint32_t rows, const float* radius_table,
-                         float tolerance, float link_factor, const fcz_violations_out* out, chain_radii* tab) {
+// (the outputs are checked by the caller: fcz_violation_loss_dev shares the rest)
+static bool viol_in_ok(const fcz_ctx* ctx, const float* pos, const uint8_t* mask, const uint8_t* aatype, int layout, uint32_t rows, const float* radius_table,
+                       float tolerance, float link_factor, chain_radii* tab) {
     const int A = fcz_dense_width(layout);
-    if (!ctx || !pos || !mask || A <= 0 || rows > SASA_MAX_ROWS || !viol_out_ok(out)) return false;
+    if (!ctx || !pos || !mask || A <= 0 || rows > SASA_MAX_ROWS) return false;
     if (!std::isfinite(tolerance) || tolerance < 0.0f || !std::isfinite(link_factor) || link_factor < 0.0f) return false;
     if (layout == FCZ_DENSE_ATOM14 && !aatype) return false;                  // a slot's atom depends on the type there
     memset(tab->radius, 0, sizeof tab->radius);
@@ -2578,6 +2583,11 @@ static bool viol_args_ok(const fcz_ctx* ctx, const float* pos, const uint8_t* ma
         if (!(r >= 0.5f && r < 8.0f)) return false;                           // (a NaN radius ends here)
     }
     return true;
+}
+
+static bool viol_args_ok(const fcz_ctx* ctx, const float* pos, const uint8_t* mask, const uint8_t* aatype, int layout, uint32_t rows, const float* radius_table,
+                         float tolerance, float link_factor, const fcz_violations_out* out, chain_radii* tab) {
+    return viol_out_ok(out) && viol_in_ok(ctx, pos, mask, aatype, layout, rows, radius_table, tolerance, link_factor, tab);
 }
 
 // fcz_violations_dev (bound_dev is length [n] or NULL, rows = L) and fcz_violations_packed_dev (bound_dev = row_off [n + 1], rows = R)
@@ -2655,6 +2665,147 @@ int fcz_violations_packed(fcz_ctx* ctx, const float* pos, const uint8_t* mask, c
     chain_radii tab;
     if (!viol_args_ok(ctx, pos, mask, aatype, layout, R, radius_table, tolerance, link_factor, out, &tab) || !bound_ok(true, row_off, n, R)) return FCZ_E_INVALID_ARG;
     return viol_host(ctx, pos, mask, aatype, row_off, true, n, R, layout, tab, tolerance, link_factor, *out);
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------------
+// the violation loss and its gradient (fcz_violation_loss.h; no counterpart in the reference)
+// ------------------------------------------------------------------------------------------------
+// the device forms of the value (w_clash_dev, w_link_dev and grad_dev NULL) and of the gradient (the three outputs of the value NULL);
+// bound_dev is length [n] or NULL with rows = L, or row_off [n + 1] with rows = R
+static int vloss_rows(fcz_ctx* ctx, const float* pos_dev, const uint8_t* mask_dev, const uint8_t* aatype_dev, const uint32_t* bound_dev, bool packed, uint32_t n,
+                      uint32_t rows, int layout, const chain_radii& tab, float tolerance, float link_factor, float* clash_loss_dev, float* link_loss_dev,
+                      int64_t* counts_dev, const float* w_clash_dev, const float* w_link_dev, float* grad_dev) {
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (n == 0 && (rows == 0 || !packed)) return FCZ_OK;
+    const uint32_t A = (uint32_t)fcz_dense_width(layout);
+    const uint32_t n_slot = (uint32_t)fcz_dense_slot(layout, 0, fcz_atom_code_from_name("N")), ca_slot = (uint32_t)fcz_dense_slot(layout, 0, fcz_atom_code_from_name("CA"));
+    const uint32_t c_slot = (uint32_t)fcz_dense_slot(layout, 0, fcz_atom_code_from_name("C"));
+    const int32_t sg_slot = fcz_dense_slot(layout, (int)VIOL_CYS, fcz_atom_code_from_name("SG"));   // (-1 in backbone4)
+    chain_tiles ct(ctx, packed, n, rows, viol_tile_rows(A), 12u);
+    int rc = ct.reserve(); if (rc) return rc;
+    if (grad_dev) {
+        if (rows == 0) return FCZ_OK;
+        const vloss_grad_args g{pos_dev, mask_dev, aatype_dev, bound_dev, n, rows, A, n_slot, ca_slot, c_slot, sg_slot, tolerance, link_factor, w_clash_dev, w_link_dev,
+                                grad_dev};
+        span_guard sg(ctx, "violation_loss_grad");
+        return ct.run(bound_dev, [&] { hipLaunchKernelGGL(k_chain_fill<vloss_grad_args>, ct.fill_grid(rows), dim3(BLOCK), 0, ctx->stream, g); },
+                      [&](auto P, dim3 grid, const uint64_t* tile_off, uint32_t tiles_per_entry, uint64_t n_padded) {
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_violation_loss_grad<decltype(P)::value>), grid, dim3(BLOCK), 0, ctx->stream, g, tab, tile_off, tiles_per_entry, n_padded);
+        });
+    }
+    const vloss_args g{pos_dev, mask_dev, aatype_dev, bound_dev, n, rows, A, n_slot, ca_slot, c_slot, sg_slot, tolerance, link_factor, clash_loss_dev, link_loss_dev,
+                       reinterpret_cast<unsigned long long*>(counts_dev)};
+    span_guard sg(ctx, "violation_loss");
+    if (n) HIP_TRY(hipMemsetAsync(counts_dev, 0, sizeof(int64_t) * 2 * (size_t)n, ctx->stream));
+    if (rows == 0) return FCZ_OK;                                             // (packed, chains without a row: their counters are 0)
+    return ct.run(bound_dev, [&] { hipLaunchKernelGGL(k_chain_fill<vloss_args>, ct.fill_grid(rows), dim3(BLOCK), 0, ctx->stream, g); },
+                  [&](auto P, dim3 grid, const uint64_t* tile_off, uint32_t tiles_per_entry, uint64_t n_padded) {
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_violation_loss<decltype(P)::value>), grid, dim3(BLOCK), 0, ctx->stream, g, tab, tile_off, tiles_per_entry, n_padded);
+    });
+}
+
+// the host forms: the host arrays through DENSE_IN 0 .. 3, VLOSS_WEIGHT 4 .. 5 and VLOSS_OUT 10 .. 12 (clash_loss, link_loss, counts) or 10 (grad)
+static int vloss_host(fcz_ctx* ctx, const float* pos, const uint8_t* mask, const uint8_t* aatype, const uint32_t* bound, bool packed, uint32_t n, uint32_t rows_per,
+                      int layout, const chain_radii& tab, float tolerance, float link_factor, float* clash_loss, float* link_loss, int64_t* counts,
+                      const float* w_clash, const float* w_link, float* grad) {
+    const dense_bytes b(packed, n, rows_per, layout, bound);
+    const size_t r = b.rows;
+    auto run = [&](const void* const* in, void* const* out) {
+        return vloss_rows(ctx, (const float*)in[0], (const uint8_t*)in[1], (const uint8_t*)in[2], (const uint32_t*)in[3], packed, n, rows_per, layout, tab, tolerance,
+                          link_factor, grad ? nullptr : (float*)out[0], grad ? nullptr : (float*)out[1], grad ? nullptr : (int64_t*)out[2], (const float*)in[4],
+                          (const float*)in[5], grad ? (float*)out[0] : nullptr);
+    };
+    if (grad)
+        return staged_call(ctx, {{pos, b.pos, DENSE_IN}, {mask, b.mask, DENSE_IN + 1}, {aatype, r, DENSE_IN + 2}, {bound, b.bound, DENSE_IN + 3},
+                                 {w_clash, b.mask * 4, VLOSS_WEIGHT}, {w_link, r * 12, VLOSS_WEIGHT + 1}}, {{grad, b.pos, VLOSS_OUT}}, run);
+    return staged_call(ctx, {{pos, b.pos, DENSE_IN}, {mask, b.mask, DENSE_IN + 1}, {aatype, r, DENSE_IN + 2}, {bound, b.bound, DENSE_IN + 3},
+                             {nullptr, 0, VLOSS_WEIGHT}, {nullptr, 0, VLOSS_WEIGHT + 1}},
+                       {{clash_loss, b.mask * 4, VLOSS_OUT}, {link_loss, r * 12, VLOSS_OUT + 1}, {counts, (size_t)n * 2 * sizeof(int64_t), VLOSS_OUT + 2}}, run);
+}
+
+extern "C" {
+
+int fcz_violation_loss_pass(void) { return (int)VLOSS_PASS; }
+
+int fcz_violation_loss_dev(fcz_ctx* ctx, const float* pos_dev, const uint8_t* mask_dev, const uint8_t* aatype_dev, const uint32_t* length_dev, uint32_t n, uint32_t L,
+                           int layout, const float* radius_table, float tolerance, float link_factor, float* clash_loss_dev, float* link_loss_dev,
+                           int64_t* counts_dev) {
+    chain_radii tab;
+    if (!clash_loss_dev || !link_loss_dev || !counts_dev || !viol_in_ok(ctx, pos_dev, mask_dev, aatype_dev, layout, L, radius_table, tolerance, link_factor, &tab) ||
+        !bound_ok(false, length_dev, n, L))
+        return FCZ_E_INVALID_ARG;
+    return vloss_rows(ctx, pos_dev, mask_dev, aatype_dev, length_dev, false, n, L, layout, tab, tolerance, link_factor, clash_loss_dev, link_loss_dev, counts_dev,
+                      nullptr, nullptr, nullptr);
+}
+
+int fcz_violation_loss_packed_dev(fcz_ctx* ctx, const float* pos_dev, const uint8_t* mask_dev, const uint8_t* aatype_dev, const uint32_t* row_off_dev, uint32_t n,
+                                  uint32_t R, int layout, const float* radius_table, float tolerance, float link_factor, float* clash_loss_dev,
+                                  float* link_loss_dev, int64_t* counts_dev) {
+    chain_radii tab;
+    if (!clash_loss_dev || !link_loss_dev || !counts_dev || !viol_in_ok(ctx, pos_dev, mask_dev, aatype_dev, layout, R, radius_table, tolerance, link_factor, &tab) ||
+        !bound_ok(true, row_off_dev, n, R))
+        return FCZ_E_INVALID_ARG;
+    return vloss_rows(ctx, pos_dev, mask_dev, aatype_dev, row_off_dev, true, n, R, layout, tab, tolerance, link_factor, clash_loss_dev, link_loss_dev, counts_dev,
+                      nullptr, nullptr, nullptr);
+}
+
+int fcz_violation_loss_grad_dev(fcz_ctx* ctx, const float* pos_dev, const uint8_t* mask_dev, const uint8_t* aatype_dev, const uint32_t* length_dev, uint32_t n,
+                                uint32_t L, int layout, const float* radius_table, float tolerance, float link_factor, const float* w_clash_dev,
+                                const float* w_link_dev, float* grad_dev) {
+    chain_radii tab;
+    if (!w_clash_dev || !w_link_dev || !grad_dev || !viol_in_ok(ctx, pos_dev, mask_dev, aatype_dev, layout, L, radius_table, tolerance, link_factor, &tab) ||
+        !bound_ok(false, length_dev, n, L))
+        return FCZ_E_INVALID_ARG;
+    return vloss_rows(ctx, pos_dev, mask_dev, aatype_dev, length_dev, false, n, L, layout, tab, tolerance, link_factor, nullptr, nullptr, nullptr, w_clash_dev,
+                      w_link_dev, grad_dev);
+}
+
+int fcz_violation_loss_grad_packed_dev(fcz_ctx* ctx, const float* pos_dev, const uint8_t* mask_dev, const uint8_t* aatype_dev, const uint32_t* row_off_dev,
+                                       uint32_t n, uint32_t R, int layout, const float* radius_table, float tolerance, float link_factor,
+                                       const float* w_clash_dev, const float* w_link_dev, float* grad_dev) {
+    chain_radii tab;
+    if (!w_clash_dev || !w_link_dev || !grad_dev || !viol_in_ok(ctx, pos_dev, mask_dev, aatype_dev, layout, R, radius_table, tolerance, link_factor, &tab) ||
+        !bound_ok(true, row_off_dev, n, R))
+        return FCZ_E_INVALID_ARG;
+    return vloss_rows(ctx, pos_dev, mask_dev, aatype_dev, row_off_dev, true, n, R, layout, tab, tolerance, link_factor, nullptr, nullptr, nullptr, w_clash_dev,
+                      w_link_dev, grad_dev);
+}
+
+int fcz_violation_loss(fcz_ctx* ctx, const float* pos, const uint8_t* mask, const uint8_t* aatype, const uint32_t* length, uint32_t n, uint32_t L, int layout,
+                       const float* radius_table, float tolerance, float link_factor, float* clash_loss, float* link_loss, int64_t* counts) {
+    chain_radii tab;
+    if (!clash_loss || !link_loss || !counts || !viol_in_ok(ctx, pos, mask, aatype, layout, L, radius_table, tolerance, link_factor, &tab) ||
+        !bound_ok(false, length, n, L))
+        return FCZ_E_INVALID_ARG;
+    return vloss_host(ctx, pos, mask, aatype, length, false, n, L, layout, tab, tolerance, link_factor, clash_loss, link_loss, counts, nullptr, nullptr, nullptr);
+}
+
+int fcz_violation_loss_packed(fcz_ctx* ctx, const float* pos, const uint8_t* mask, const uint8_t* aatype, const uint32_t* row_off, uint32_t n, uint32_t R,
+                              int layout, const float* radius_table, float tolerance, float link_factor, float* clash_loss, float* link_loss, int64_t* counts) {
+    chain_radii tab;
+    if (!clash_loss || !link_loss || !counts || !viol_in_ok(ctx, pos, mask, aatype, layout, R, radius_table, tolerance, link_factor, &tab) ||
+        !bound_ok(true, row_off, n, R))
+        return FCZ_E_INVALID_ARG;
+    return vloss_host(ctx, pos, mask, aatype, row_off, true, n, R, layout, tab, tolerance, link_factor, clash_loss, link_loss, counts, nullptr, nullptr, nullptr);
+}
+
+int fcz_violation_loss_grad(fcz_ctx* ctx, const float* pos, const uint8_t* mask, const uint8_t* aatype, const uint32_t* length, uint32_t n, uint32_t L, int layout,
+                            const float* radius_table, float tolerance, float link_factor, const float* w_clash, const float* w_link, float* grad) {
+    chain_radii tab;
+    if (!w_clash || !w_link || !grad || !viol_in_ok(ctx, pos, mask, aatype, layout, L, radius_table, tolerance, link_factor, &tab) || !bound_ok(false, length, n, L))
+        return FCZ_E_INVALID_ARG;
+    return vloss_host(ctx, pos, mask, aatype, length, false, n, L, layout, tab, tolerance, link_factor, nullptr, nullptr, nullptr, w_clash, w_link, grad);
+}
+
+int fcz_violation_loss_grad_packed(fcz_ctx* ctx, const float* pos, const uint8_t* mask, const uint8_t* aatype, const uint32_t* row_off, uint32_t n, uint32_t R,
+                                   int layout, const float* radius_table, float tolerance, float link_factor, const float* w_clash, const float* w_link,
+                                   float* grad) {
+    chain_radii tab;
+    if (!w_clash || !w_link || !grad || !viol_in_ok(ctx, pos, mask, aatype, layout, R, radius_table, tolerance, link_factor, &tab) || !bound_ok(true, row_off, n, R))
+        return FCZ_E_INVALID_ARG;
+    return vloss_host(ctx, pos, mask, aatype, row_off, true, n, R, layout, tab, tolerance, link_factor, nullptr, nullptr, nullptr, w_clash, w_link, grad);
 }
 
 }  // extern "C"

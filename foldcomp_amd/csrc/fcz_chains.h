@@ -18,8 +18,11 @@
 //                          (k_lddt_soft, k_lddt_soft_grad).
 //   chain_stage_slots      one candidate pass of at most PASS atoms, staged in steps of the rows that hold at most STEP slots
 //                          (k_sasa_points, k_violations, k_lddt_atoms).
-//                          Both hand the caller's functor a row (and slot) and a chain_slots; the functor decides whether that is a
-//                          candidate, claims a slot with next() and writes its own LDS arrays. Both hold barriers, so all BLOCK
+//   chain_stage_slots_ordered   the same pass compacted in ascending (row, slot) by ballots and a scan of the wavefronts' totals, for a
+//                          sweep that sums floats over atoms (k_violation_loss, k_violation_loss_grad).
+//                          chain_stage_rows and chain_stage_slots hand the caller's functor a row (and slot) and a chain_slots; the
+//                          functor decides whether that is a candidate, claims a slot with next() and writes its own LDS arrays;
+//                          the ordered two hand out the slot themselves. All four hold barriers, so all BLOCK
 //                          threads call them under block-uniform control flow and no functor holds a barrier. The barrier that
 //                          closes a pass, behind the caller's sweep, stays in the caller.
 //   chain_tile_slots       the slots of a query tile of whole rows, strided over the block.
@@ -217,6 +220,60 @@ __device__ __forceinline__ uint32_t chain_stage_slots(uint32_t* s_count, uint32_
         if (*r0 >= len || staged + step_rows * A > PASS) break;
     }
     return *s_count;
+}
+
+// The ordered sibling of chain_stage_slots, for a sweep whose result is a float sum over atoms and so depends on the order the
+// candidates are met in (k_violation_loss, k_violation_loss_grad): one candidate pass of at most PASS atoms from row *r0, compacted
+// in ASCENDING (row, slot). There is no counter to race for: is = test(r, a, h) says whether slot a of row r is a candidate and keeps
+// what it loaded in the caller's registers under h (< STEP / BLOCK, the lane's h-th slot of the step), a ballot and a popcount give
+// the candidate its place inside its wavefront, the wavefronts' totals of the step (s_wave [STEP / 64], one word a wavefront and h)
+// are scanned by every lane, and put(h, i) writes the candidate to slot i of the caller's LDS arrays. A lane's h-th slot of a step is
+// slot tid + h * BLOCK of the step, so (h, wavefront, lane) ascends with (row, slot). The steps, the rule that closes a pass and the
+// barriers are chain_stage_slots': two barriers a step, all BLOCK threads under block-uniform control flow, none in a functor. There
+// is no barrier in front: the caller's barrier that closed the pass before has freed the staging and s_wave.
+// -> the staged count; *r0 becomes the next pass' first row. The caller sweeps the pass and closes it with a barrier.
+template <uint32_t PASS, uint32_t STEP, class Test, class Put>
+__device__ __forceinline__ uint32_t chain_stage_slots_ordered(uint32_t* s_wave, uint32_t A, uint32_t len, uint32_t* r0, Test test, Put put) {
+    static_assert(STEP % BLOCK == 0 && BLOCK % 64 == 0 && STEP <= PASS, "chain_stage_slots_ordered");
+    constexpr uint32_t H = STEP / BLOCK, W = BLOCK / 64;
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const uint32_t step_rows = chain_div_a(STEP, A);
+    uint32_t staged = 0;
+    for (;;) {
+        const uint32_t nr = len - *r0 < step_rows ? len - *r0 : step_rows;
+        bool is[H];
+        uint32_t before[H];                                           // the candidates of this wavefront and h in front of the lane's
+#pragma unroll
+        for (uint32_t h = 0; h < H; h++) {
+            const uint32_t x = tid + h * BLOCK;
+            is[h] = false;
+            if (x < nr * A) {
+                const uint32_t rr = chain_div_a(x, A);
+                is[h] = test(*r0 + rr, x - rr * A, h);
+            }
+            const unsigned long long m = __ballot(is[h]);
+            before[h] = (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+            if (lane == 0) s_wave[h * W + wave] = (uint32_t)__popcll(m);
+        }
+        __syncthreads();
+        uint32_t run = staged;                                        // the place of (h, wave): the totals of every (h', w') in front of it
+#pragma unroll
+        for (uint32_t h = 0; h < H; h++) {
+            uint32_t mine = run;
+#pragma unroll
+            for (uint32_t w = 0; w < W; w++) {
+                const uint32_t t = s_wave[h * W + w];                 // (a broadcast read)
+                mine += w < wave ? t : 0u;
+                run += t;
+            }
+            if (is[h]) put(h, mine + before[h]);
+        }
+        staged = run;
+        *r0 += nr;
+        __syncthreads();                                              // (every lane has read s_wave before the next step rewrites it)
+        if (*r0 >= len || staged + step_rows * A > PASS) break;
+    }
+    return staged;
 }
 
 // the slots of a query tile of tile_rows rows that begins at row q0 of its chain, strided over the block: slot(x, rr, a, q) with x the

@@ -37,6 +37,9 @@
                                    label of every residue (foldcomp.SS_CLASSES); decode_tensors(secondary_structure=True) adds ss / ss_mask
     solvent_accessibility(either dict, or the tensors as keywords) -> dict(sasa [..] float32, rsa, sasa_mask bool, sasa_points [.., A] int16):
                                    the Shrake-Rupley accessible surface of every residue; decode_tensors(sasa=True) adds sasa / rsa / sasa_mask
+    violation_loss(pred, true, tolerance=1.5, link_factor=12.0) -> dict(clash_loss [.., A] float32, link_loss [.., 3], clash_chain [n],
+                                   bond_chain, angle_chain, violation_chain, loss): the clash energy and the peptide-link penalties of
+                                   violations' pairs and links as a LOSS, differentiable with a fused backward on the GPU
     violations(either dict, or the tensors as keywords) -> dict(clash_atom [.., A] uint8, clash_count, clash_depth, clash_partner, viol_mask,
                                    link_mask, link_length, link_cos [.., 2], link_violation [..], chain_counts [n, 4] int64): steric clashes
                                    between residues and broken peptide links; decode_tensors(violations=True) adds clash_count /
@@ -66,7 +69,7 @@ from .codec import ANGLE_COLUMNS, WIDTH_LAYOUTS, Codec, dense_layout
 from .structure import CAtomsOut, CDenseIn, CDenseOut, CLddtAtomsOut, CPackedOut, CSuperposeOut, CTmScoreOut, CGdtOut, CViolationsOut, CChainSet, CTmAlignOut, CTmAlignParams, TM_ALIGN_OUTPUTS
 
 __all__ = ["decode_tensors", "encode_tensors", "decode_angles", "crop_starts", "neighbor_graph", "rigid_frames", "lddt", "smooth_lddt", "fape", "lddt_atoms", "superpose", "tm_score", "gdt", "tm_align", "apply_transform",
-           "backbone_hbonds", "secondary_structure", "solvent_accessibility", "violations"]
+           "backbone_hbonds", "secondary_structure", "solvent_accessibility", "violations", "violation_loss"]
 
 
 def crop_starts(length, L: int, how, generator=None):
@@ -1570,8 +1573,8 @@ def violations(batch=None, *, tolerance: float = 1.5, link_factor: float = 12.0,
     "bondi" (solvent_accessibility's table, the chain's OXT left out) or an array [21, A] indexed [aatype][slot], 0 for a slot that
     holds no atom, every other radius in [0.5, 8). The arithmetic is fixed (include/fcz_hip.h, fcz_violations_dev): atom37 and atom14
     give the same values. Bonds and angles inside a residue are not checked. A cropped window's values are the window's own.
-    Reproducible bit for bit; NOT differentiable. The arguments are checked first, without torch or a device
-    (api.check_violations)."""
+    Reproducible bit for bit; NOT differentiable (violation_loss is the loss on the same atoms, pairs and links). The arguments are
+    checked first, without torch or a device (api.check_violations)."""
     x, checked = _inputs("violations", "Codec.violations", batch, tensors, codec, lambda d: api.check_violations("violations", d, tolerance, link_factor, radii))
     out = _viol_alloc(x.torch, x.dev, x.lead, x.A, x.n)
     if out["clash_count"].numel():
@@ -1579,6 +1582,144 @@ def violations(batch=None, *, tolerance: float = 1.5, link_factor: float = 12.0,
         _viol_into(x, checked[2], tolerance, link_factor, out)
         x.codec.synchronize()
     return out
+
+
+_violation_autograd = {}
+
+
+def _violation_function(torch):
+    """the torch.autograd.Function of violation_loss, made once torch is there (this module imports without it)"""
+    if _violation_autograd:
+        return _violation_autograd["loss"]
+    from torch.autograd.function import once_differentiable
+
+    class ViolationLoss(torch.autograd.Function):
+        """pred pos -> (clash_loss [.., A], link_loss [.., 3]) (fcz_violation_loss_dev); `call` holds everything else of the call and
+        receives counts. The backward is the gradient kernel (fcz_violation_loss_grad_dev) on the saved pos: nothing else is kept
+        from the forward."""
+
+        @staticmethod
+        def forward(ctx, ppos, call):
+            ctx.call = call
+            ctx.save_for_backward(ppos)
+            return call.value(ppos)
+
+        @staticmethod
+        @once_differentiable
+        def backward(ctx, grad_clash, grad_link):
+            (ppos,) = ctx.saved_tensors
+            return ctx.call.gradient(ppos, grad_clash, grad_link), None
+
+    _violation_autograd["loss"] = ViolationLoss
+    return ViolationLoss
+
+
+class _ViolationLossCall:
+    """one call of violation_loss: the checked tensors (mask: the two masks combined), the radii and the parameters; value() and
+    gradient() enqueue the two kernels on the codec's stream between a wait for torch's stream and codec.synchronize(), as every
+    analysis function does"""
+
+    def __init__(self, x, table, tolerance, link_factor):
+        self.x, self.table, self.tolerance, self.link_factor = x, table, float(tolerance), float(link_factor)
+        self.counts = None
+
+    def _run(self, name, ppos, *tensors):
+        x = self.x
+        x.torch.cuda.current_stream(x.dev).synchronize()
+        _call(x.codec, name, x.is_packed, ppos.data_ptr(), x.mask.data_ptr(), _ptr(x.aatype), _ptr(x.bound), x.n, x.rows, x.lay,
+              None if self.table is None else self.table.ctypes.data, self.tolerance, self.link_factor, *(t.data_ptr() for t in tensors))
+        x.codec.synchronize()
+
+    def value(self, ppos):
+        x, torch = self.x, self.x.torch
+        clash = torch.zeros(x.lead + (x.A,), dtype=torch.float32, device=x.dev)
+        link = torch.zeros(x.lead + (3,), dtype=torch.float32, device=x.dev)
+        self.counts = torch.zeros((x.n, 2), dtype=torch.int64, device=x.dev)
+        if link.numel():
+            self._run("fcz_violation_loss", ppos, clash, link, self.counts)
+        return clash, link
+
+    def gradient(self, ppos, w_clash, w_link):
+        x, torch = self.x, self.x.torch
+        grad = torch.zeros(x.shape, dtype=torch.float32, device=x.dev)
+        if grad.numel():
+            w_clash = torch.zeros(x.lead + (x.A,), dtype=torch.float32, device=x.dev) if w_clash is None else w_clash.contiguous()
+            w_link = torch.zeros(x.lead + (3,), dtype=torch.float32, device=x.dev) if w_link is None else w_link.contiguous()
+            self._run("fcz_violation_loss_grad", ppos, w_clash, w_link, grad)
+        return grad
+
+
+def violation_loss(pred, true, *, tolerance: float = 1.5, link_factor: float = 12.0, radii="bondi", codec: Optional[Codec] = None) -> dict:
+    """predicted coordinates on the GPU -> dict(clash_loss, link_loss, clash_chain, bond_chain, angle_chain, violation_chain, loss): the
+    between-residue part of AlphaFold's structural-violation loss, a LOSS: differentiable with respect to pred's pos, with a fused
+    backward on the GPU and no atoms x atoms array in either direction.
+
+    `pred` is the pos tensor, or a dict with `pos` and optionally `mask`. `true` is the dict decode_tensors / tensor_batches return,
+    padded (mask [n, L, A], aatype [n, L], optionally length [n]), packed (mask [R, A], aatype [R], cu_seqlens [n + 1]) or a window
+    with crop_start: it supplies mask, aatype (needed for atom14; without it no disulfide is excluded and no link is a proline's)
+    and the chains. Its pos is NOT read: the loss looks at the prediction alone. A slot is used when it is set in both masks. Atoms,
+    clashing pairs, links, tolerance, link_factor and radii are violations' exactly, on pred's pos.
+        clash_loss [.., A] float32     for every atom the sum of (Ri + Rj) - tolerance - distance over the atoms of other residues
+                                       it clashes with; every pair stands in both of its atoms (AlphaFold's per_atom_loss_sum)
+        link_loss [.., 3] float32      for the link to the NEXT row, how far the C-N' length and the cosines of CA-C-N' and C-N'-CA'
+                                       lie outside link_factor sigmas: (|x - x0| - link_factor * sigma)+, 0 where there is no link
+        clash_chain [n] float32        the sum of clash_loss over the chain's atoms, divided by max(atoms, 1)
+        bond_chain [n] float32         the mean of the length term over the chain's links (0 without a link)
+        angle_chain [n] float32        the mean of the first cosine term plus the mean of the second
+        violation_chain [n] float32    the three added
+        loss scalar float32            the mean of violation_chain over the chains that have an atom (0 without one)
+    When pred's pos requires a gradient (and gradients are enabled) all seven carry a graph: loss.backward() runs the gradient kernel
+    once and leaves d loss / d pos in pos.grad. Gradients flow to pred's pos and to nothing else; the graph can be walked once and
+    not differentiated twice. Under torch.no_grad(), or for a pos that needs no gradient, only the value kernel runs. Every sum has
+    a fixed order (an atom's partners in float32 in ascending (row, slot) on the device, chains in float64, no float atomics in
+    either direction): value and gradient are reproducible bit for bit. atom37 and atom14 agree to rounding, not on bits: the slot
+    order differs.
+
+    Two departures from AlphaFold's code: there are no epsilons (its sqrt(1e-10 + d2) and 1e-6 + norm), the few places where a
+    direction does not exist -- coincident atoms, a bond of length 0 -- have the gradient 0 instead; and the within-residue bounds,
+    its third term, are not computed (their tables are not part of this package).
+
+    The tensors must be contiguous and lie on the codec's device; ordering against torch is decode_tensors'. The arguments are
+    checked first, without torch or a device (api.check_violation_loss)."""
+    what = "violation_loss"
+    if not isinstance(true, dict):
+        raise TypeError(f"{what}: true must be a dict with mask, aatype and length or cu_seqlens")
+    p = dict(pred) if isinstance(pred, dict) else {"pos": pred}
+    _need(what, p, ("pos",), " of pred")
+    _need(what, true, ("mask",), " of true")
+    ppos, pmask = p["pos"], p.get("mask")
+    d = dict(true, pos=ppos)
+    shape = tuple(getattr(ppos, "shape", ()))
+    if pmask is not None and tuple(getattr(pmask, "shape", ())) != shape[:-1]:
+        raise ValueError(f"pred mask must have the shape {shape[:-1]}, not {tuple(getattr(pmask, 'shape', ()))}")
+    shape, is_packed, table = api.check_violation_loss(what, d, tolerance, link_factor, radii)
+    x = _dense_checked(what, "Codec.violation_loss", codec, d, shape, is_packed, pos_rule="full")
+    torch = x.torch
+    if pmask is not None:
+        pmask = _on_device(torch, what, x.dev, "pred mask", pmask, shape[:-1], (torch.bool, torch.uint8)).view(torch.uint8)
+        x = x._replace(mask=((x.mask != 0) & (pmask != 0)).view(torch.uint8))
+    call = _ViolationLossCall(x, table, tolerance, link_factor)
+    if torch.is_grad_enabled() and ppos.requires_grad:
+        clash, link = _violation_function(torch).apply(ppos, call)
+    else:
+        clash, link = call.value(ppos.detach())
+    atoms, links = call.counts[:, 0], call.counts[:, 1]
+    rows64 = torch.cat([clash.to(torch.float64).sum(dim=-1, keepdim=True), link.to(torch.float64)], dim=-1)      # [.., 4]: clash, bond, cos0, cos1
+    if x.is_packed:
+        _, chain_sum = _autograd_functions(torch)
+        at = x.bound.to(torch.int64)
+        sums = torch.stack([chain_sum.apply(rows64[:, k].contiguous(), at) for k in range(4)], dim=1)
+    else:
+        sums = rows64.sum(dim=1)
+    per_atom, per_link = atoms.clamp(min=1).to(torch.float64), links.clamp(min=1).to(torch.float64)
+    clash_chain, bond_chain = sums[:, 0] / per_atom, sums[:, 1] / per_link
+    angle_chain = sums[:, 2] / per_link + sums[:, 3] / per_link
+    chain = clash_chain + bond_chain + angle_chain
+    has = atoms > 0
+    loss = (torch.where(has, chain, chain.new_zeros(())).sum() / has.sum().clamp(min=1).to(torch.float64)).to(torch.float32)
+    f32 = torch.float32
+    return dict(clash_loss=clash, link_loss=link, clash_chain=clash_chain.to(f32), bond_chain=bond_chain.to(f32), angle_chain=angle_chain.to(f32),
+                violation_chain=chain.to(f32), loss=loss)
 
 
 def _frames_alloc(torch, dev, rows, fgroups):

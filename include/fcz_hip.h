@@ -25,6 +25,7 @@
  *   (none: no secondary structure)                         fcz_hbond_dev, fcz_dssp_labels_dev, fcz_dssp (+ _packed forms)
  *   (none: no solvent accessibility)                       fcz_sasa_dev / fcz_sasa_packed_dev, fcz_sasa / fcz_sasa_packed
  *   (none: no structural violations)                       fcz_violations_dev / fcz_violations_packed_dev, fcz_violations / fcz_violations_packed
+ *   (none: no loss on clashes and peptide links)           fcz_violation_loss_dev / fcz_violation_loss_grad_dev (+ _packed and host forms)
  *   (none: `rmsd` compares two files unsuperposed)         fcz_superpose_dev / fcz_superpose_packed_dev, fcz_superpose_apply_dev /
  *                                                          fcz_superpose_apply_packed_dev and their host forms
  *   (none: no TM-score)                                    fcz_tmscore_dev / fcz_tmscore_packed_dev and their host forms
@@ -892,6 +893,87 @@ int fcz_violations(fcz_ctx* ctx, const float* pos, const uint8_t* mask, const ui
 int fcz_violations_packed(fcz_ctx* ctx, const float* pos, const uint8_t* mask, const uint8_t* aatype, const uint32_t* row_off,
                           uint32_t n, uint32_t R, int layout, const float* radius_table, float tolerance, float link_factor,
                           const fcz_violations_out* out);
+
+/* ---- the violation loss: clashes and peptide links as a differentiable loss, and its gradient ------------- */
+/* The two between-residue terms of AlphaFold's structural-violation loss (between_residue_clash_loss and
+ * between_residue_bond_loss) on the geometry of fcz_violations_dev, as float32 values with a fused backward on the device: no atoms x
+ * atoms array in either direction. The reference has no such output. Inputs, forms (padded, packed; atom37, atom14, backbone4),
+ * chains, ATOMS, radii (radius_table on the host or NULL for Bondi; aatype may be NULL, except in atom14), exclusions and arithmetic
+ * rules are fcz_violations_dev's, unchanged: float32 throughout, every operation rounded, no FMA,
+ * d2(p, q) = (dx*dx + dy*dy) + dz*dz with dx = p.x - q.x, the correctly rounded sqrt and division.
+ *   clash pairs   fcz_violations_dev's pairs exactly: atoms i, j of different rows of a chain with T = (Ri + Rj) - tolerance > 0 and
+ *                 d2(c_i, c_j) < T * T, the peptide bond and the CYS-CYS SG pairs struck out. The relation is symmetric.
+ * Value (fcz_violation_loss_dev):
+ *   clash_loss [rows][A] float32  for atom i the float32 sum of T_ij - sqrt(d2_ij) (one subtraction; >= 0) over its clashing partners
+ *                                 j, added one after the other from 0 in ASCENDING (chain row of j, slot of j); 0 for a slot that is
+ *                                 no atom. Every pair stands in both of its atoms: AlphaFold's per_atom_loss_sum.
+ *   link_loss [rows][3] float32   at row r for the link r -> r + 1 where fcz_violations_dev's link exists (link_mask), else 0; with
+ *                                 x+ = x when x > 0, else 0:   (|length - l0| - link_factor * sl)+,
+ *                                 (|cos0 - (-0.4473)| - link_factor * 0.0311)+,   (|cos1 - (-0.5203)| - link_factor * 0.0353)+
+ *                                 with length, cos0, cos1, (l0, sl), the PRO case and every operation as link_length, link_cos and
+ *                                 link_violation have them; |x - x0| - bound is one more subtraction. A term whose length or cosine
+ *                                 is not finite is 0: the loss stays finite where the metric sets a bit for +-inf. So
+ *                                 link_loss[r][k] > 0 exactly where bit k of link_violation[r] is set and the quantity is finite.
+ *   counts [n][2] int64           per chain its atoms (chain_counts[.][0]) and its links: integer atomics, cleared by the call.
+ * Gradient (fcz_violation_loss_grad_dev) of  sum w_clash * clash_loss + sum w_link * link_loss  with respect to pos, for the caller's
+ * w_clash [rows][A] and w_link [rows][3] float32, the upstream gradients of the two outputs; the weight of a slot that is no atom and
+ * of a link that does not exist is not read as data. grad [rows][A][3] float32, per slot, every component x alike:
+ *   1. from 0, over the atom's clashing partners j in the same ascending order:  g = g + (w_i + w_j) * (-((p_i.x - p_j.x) / d)),
+ *      d = sqrt(d2): one addition of the weights, one subtraction, one division, an exact negation, one multiplication, one
+ *      addition. A pair with d == 0 adds nothing (no direction), and a pair with T - d == 0 adds nothing (the subgradient 0 of
+ *      x+ at 0, as torch's relu has it). A slot that is no atom starts from 0 and has no partners.
+ *   2. then the link terms, added one after the other: row r's N receives the bond, cos0 and cos1 terms of link r - 1, its CA the cos1
+ *      term of link r - 1 and then the cos0 term of link r, its C the bond, cos0 and cos1 terms of link r. Link atoms are defined by
+ *      mask and finiteness alone: a slot with a zero radius receives its link terms all the same. Only a term whose link_loss is > 0
+ *      (strictly positive, hence finite) contributes; every other term is 0. With k = w_link[r][t] * sign(x - x0) (that is w, -w, or
+ *      0 for a difference of 0):
+ *        bond   C:  k * ((C.x - N'.x) / length);  N': the exact negation of C's term. A length of 0 gives 0.
+ *        cos    of the angle at b between a and c (cos0: CA, C, N'; cos1: C, N', CA'), u = a - b, v = c - b, |u|, |v| and cos as
+ *               link_cos has them:  uh = u.x / |u|, vh = v.x / |v|,  ga = (vh - cos * uh) / |u|,  gc = (uh - cos * vh) / |v|,
+ *               gb = -(ga + gc);  a receives k * ga, b receives k * gb, c receives k * gc (one multiplication each).
+ * Every slot gathers its whole gradient itself: no float atomics, no scatter, one writer a slot. With every operation spelled out,
+ * numpy reproduces value and gradient bit for bit.
+ * rows = n * L (padded) or R (packed). Every byte of every output is written whatever the inputs hold and nothing outside the outputs
+ * is written; rows behind length and packed rows no chain covers hold 0; nothing outside the inputs is read, whatever row_off or
+ * aatype holds (ranges that overlap are each computed and a shared row's values are then unspecified). Every index that scales with
+ * rows * A is 64-bit. A chain's atoms are staged in passes of at most fcz_violation_loss_pass() (pure host, > 0). The result does
+ * not depend on tile, pass, launch geometry or the other chains of the batch: a chain gives the same bytes alone, in any batch,
+ * padded or packed, call after call. Bit agreement between atom37 and atom14 is NOT promised: the slot order inside a row differs,
+ * and with it the order of a float32 sum. Within-residue bounds are not computed, and there are no second derivatives.
+ * Enqueued on the ctx stream, no synchronisation (the packed forms share fcz_knn_packed_dev's scratch in the ctx).
+ * FCZ_E_INVALID_ARG with nothing launched and no output touched: everything fcz_violations_dev refuses (NULL ctx / pos / mask, NULL
+ * row_off with n > 0, unknown layout, L == 0, L or R above 2^31 - 1, tolerance or link_factor not finite or negative, a table with a
+ * non-zero radius outside [0.5, 8), atom14 without aatype), a NULL output or weight pointer. n == 0 or R == 0: FCZ_OK (packed,
+ * n == 0 < R: every row is uncovered and is filled). The time goes to the groups "violation_loss" and "violation_loss_grad". */
+int fcz_violation_loss_pass(void);
+int fcz_violation_loss_dev(fcz_ctx* ctx, const float* pos_dev, const uint8_t* mask_dev, const uint8_t* aatype_dev,
+                           const uint32_t* length_dev, uint32_t n, uint32_t L, int layout, const float* radius_table /* host, or NULL */,
+                           float tolerance, float link_factor, float* clash_loss_dev, float* link_loss_dev, int64_t* counts_dev);
+int fcz_violation_loss_packed_dev(fcz_ctx* ctx, const float* pos_dev, const uint8_t* mask_dev, const uint8_t* aatype_dev,
+                                  const uint32_t* row_off_dev, uint32_t n, uint32_t R, int layout,
+                                  const float* radius_table /* host, or NULL */, float tolerance, float link_factor,
+                                  float* clash_loss_dev, float* link_loss_dev, int64_t* counts_dev);
+int fcz_violation_loss_grad_dev(fcz_ctx* ctx, const float* pos_dev, const uint8_t* mask_dev, const uint8_t* aatype_dev,
+                                const uint32_t* length_dev, uint32_t n, uint32_t L, int layout,
+                                const float* radius_table /* host, or NULL */, float tolerance, float link_factor,
+                                const float* w_clash_dev, const float* w_link_dev, float* grad_dev);
+int fcz_violation_loss_grad_packed_dev(fcz_ctx* ctx, const float* pos_dev, const uint8_t* mask_dev, const uint8_t* aatype_dev,
+                                       const uint32_t* row_off_dev, uint32_t n, uint32_t R, int layout,
+                                       const float* radius_table /* host, or NULL */, float tolerance, float link_factor,
+                                       const float* w_clash_dev, const float* w_link_dev, float* grad_dev);
+/* Host-pointer conveniences: the same arrays on the host, staged through the ctx like fcz_violations; synchronous. */
+int fcz_violation_loss(fcz_ctx* ctx, const float* pos, const uint8_t* mask, const uint8_t* aatype, const uint32_t* length, uint32_t n,
+                       uint32_t L, int layout, const float* radius_table, float tolerance, float link_factor, float* clash_loss,
+                       float* link_loss, int64_t* counts);
+int fcz_violation_loss_packed(fcz_ctx* ctx, const float* pos, const uint8_t* mask, const uint8_t* aatype, const uint32_t* row_off,
+                              uint32_t n, uint32_t R, int layout, const float* radius_table, float tolerance, float link_factor,
+                              float* clash_loss, float* link_loss, int64_t* counts);
+int fcz_violation_loss_grad(fcz_ctx* ctx, const float* pos, const uint8_t* mask, const uint8_t* aatype, const uint32_t* length,
+                            uint32_t n, uint32_t L, int layout, const float* radius_table, float tolerance, float link_factor,
+                            const float* w_clash, const float* w_link, float* grad);
+int fcz_violation_loss_grad_packed(fcz_ctx* ctx, const float* pos, const uint8_t* mask, const uint8_t* aatype, const uint32_t* row_off,
+                                   uint32_t n, uint32_t R, int layout, const float* radius_table, float tolerance, float link_factor,
+                                   const float* w_clash, const float* w_link, float* grad);
 
 /* ---- least-squares (Kabsch) superposition of two dense tensor batches ------------------------------------ */
 /* The superposition-based half of what a validation loop logs, per chain, for a whole batch on the device: the rigid motion that

@@ -1,4 +1,4 @@
-"""A seeded differential fuzz of the dense-tensor analyses (DESIGN 6.8 to 6.20) over what their kernels' control flow depends on: masks,
+"""A seeded differential fuzz of the dense-tensor analyses (DESIGN 6.8 to 6.21) over what their kernels' control flow depends on: masks,
 residue types, non-finite values, geometry, lengths about every tile and pass edge, and the padded / packed forms. The generator is
 here; tests/test_gpu_analysis_fuzz.py runs it on the device, tests/test_analysis_fuzz_cpu.py asserts what the list covers, and
 tools/dbg/analysis_fuzz.py runs it at any seed and case count.
@@ -33,6 +33,22 @@ not fit (staged + step_rows * A > PASS). backbone4 and atom14 reach 1536 (every 
 reaches it on atom37 too (a candidate needs no radius). SASA and violations on atom37 reach 1055 + 13 * 36 = 1523, because OXT
 holds no radius. `design_counts` aims at that maximum and the CPU test asserts it through the mirror.
 
+The violation loss (fcz_violation_loss.h) has a pass of its own, `Spec.pass_atoms` = VLOSS_PASS = 1280 with the same step of 512,
+which does not divide it, and stages through chain_stage_slots_ordered: the same steps and the same rule that closes a pass, the
+places handed out in ascending (row, slot) by a ballot and a scan, because its outputs are float32 sums in that order. The mirror and
+the transcription take PASS and STEP and are held together at (1280, 512) as well. Its fullest passes are 1280 (backbone4), 1280
+(atom14, TRP rows) and 1280 - 13 * 37 + 13 * 36 = 1267 (atom37). With every mask set a pass closes at 1024 / 1008 / 936, so places
+1024 to 1279 of the staging arrays are reached by designed masks only. A sweep that sums can also go wrong by WHERE a partner is
+staged, so the designed chains of this analysis get two planted pairs (`plant_last_place`): the atom at the last place of the first
+pass (1279 / 1279 / 1266, one less in the chains that close one slot under the top) and the atom at place 1100 are moved next to
+atoms of row 0. Its family (`vloss_inputs`) adds the upstream weights: normal, a tenth zeros, one +-1e15 each, and NaN bit patterns
+wherever the contract reads no weight, the sets taken from the restatement. It runs at two parameter sets, `Case.param` 0 (tolerance
+0, factor 0.5: every term class occurs) and 1 (the defaults 1.5, 12.0); the comparator is _violation_loss.same, integers equal and
+floats on bits, with nothing redrawn. It keeps the `coincident` geometry that `violations` drops: the loss defines a value (T) and
+the gradient 0 at d == 0. The CPU test asserts through the restatement: the planted partners' places, a query atom whose partners
+lie in two passes and one with three partners in a staging step in every layout's long chains, every term class, a PRO link, a
+disulfide struck out (`plant_disulfide`), and that every restated number is finite.
+
 What the packed ABI cannot express: rows BETWEEN two chains that no chain covers. Chain e is row_off[e] .. row_off[e + 1], so two
 neighbours share their edge, and a row_off that runs backwards in the middle makes ranges overlap, which the ABI forbids. Uncovered
 rows are in front of row_off[0] and behind row_off[n] (k_chain_fill writes both); the fuzz has both and R beyond row_off[n].
@@ -59,7 +75,7 @@ Profiles dropped by name, with the reason:
   tmalign x geometry      the integer and degenerate geometries tie exactly or have a Horn gap of 0 at every seed, a long ideal helix
                           is nearly a line, and a plane of 120 rows misses the gap one seed in two: its chains walk or fill a globule.
   frames x no aatype      with groups = all the ABI refuses a NULL aatype; the backbone group runs without.
-  sasa, violations x no aatype on atom14
+  sasa, violations, violation_loss x no aatype on atom14
                           refused too (a slot's atom depends on the type there); atom37 and backbone4 run without.
   apply x non-finite      the payload of a NaN result is not part of the contract and the comparison is on bytes (Apply's docstring).
   violations x coincident link_cos of a link of coincident atoms is 0 / 0, a NaN whose sign bit is no part of the contract, and
@@ -72,11 +88,14 @@ Sizing. `an.ref` measured on the build machine's CPU, seconds for one chain of t
   sasa 150 x atom14: 0.06         violations 150 x atom14: 0.04         lddt_atoms 120 x atom14: 0.07         superpose 300: < 0.01
   tmscore 300: 0.16, 1025: 0.8    gdt 120: 0.35 (a coincident or collinear chain of 30 rows: 20 s, so GDT's take 12 rows)
 Building the inputs costs as much again (an ideal helix of 4 097 rows: 1.0 s). The counts that follow, as cases (seconds of build
-and restatement of an (analysis, group) test), 231 cases in all:
+and restatement of an (analysis, group) test), 250 cases in all:
   knn 18 (passes 2.5, the rest 0.3)      lddt 17 (passes 0.8)      lddt_soft 17 (passes 2.5)      hbond 17 (0.6)      labels 10 (0.7)
   apply 12 (0.7)      frames 12 (0.8)      fape 24 (passes256 1, passes1024 5 with seven cases to 2 049 rows, the rest 0.5)
   sasa 20, violations 19, lddt_atoms 19 (design 1.4, mix 0.8, each of long4 / long14 / long37 0.5 to 1.6 with four chains of
   1 250, 640 and 150 rows at the most)      superpose 13 (< 0.1)      tmscore 16 (long 1.7)      gdt 13 (0.5)      tmalign 4 (3.0)
+  violation_loss 19: its restatement holds dense atoms x atoms matrices of a whole chain, so the long chains are those of the other
+  sweeps times 1280 / 1536 (1 050, 540 and 125 rows at the most; each still takes three passes and more) and the six designed cases
+  run at parameter set 0 only: edges 0.1, design 3.5, long4 3.6, long14 3.4, long37 3.5, mix 4.7
 Every test stays under about 5 s of restatement. A MIX case has up to 9 chains of at most `cap` rows."""
 import dataclasses
 import zlib
@@ -94,11 +113,13 @@ import _superpose as SP
 import _sweep_grids as G
 import _tmalign as TA
 import _tmscore as TM
+import _violation_loss as VL
 import _violations as V
 from _devpath import FILL, GUARD, to_dev
 
 F = np.float32
 ATOM_STEP = 2 * G.BLOCK         # fcz_sasa.h SASA_STEP = fcz_violations.h VIOL_STEP = fcz_lddt_atoms.h LDDTA_STEP = 2 * BLOCK
+VLOSS_STEP = 2 * G.BLOCK        # fcz_violation_loss.h VLOSS_STEP = 2 * BLOCK: it does not divide VLOSS_PASS = 1280
 TM_LDS_ROWS = 1024              # fcz_tmscore.h: constexpr uint32_t TM_LDS_ROWS = 1024
 TIE_SHARE = 0.02                # _lddt_soft.py / _fape.py: tie_share() must stay at or below 0.02 on every noisy input
 GLY, LEU, TRP, ALA = 7, 10, 17, 0
@@ -121,9 +142,9 @@ def crc(s):
 
 # ---- chain_stage_slots, mirrored and transcribed ---------------------------------------------------------------------------------------
 
-def step_rows(A):
+def step_rows(A, STEP=ATOM_STEP):
     """chain_stage_slots: step_rows = chain_div_a(STEP, A): 13, 36, 128"""
-    return ATOM_STEP // A
+    return STEP // A
 
 
 def pass_split(counts, A, PASS=G.ATOM_PASS, STEP=ATOM_STEP):
@@ -164,17 +185,17 @@ def stage_slots_transcribed(atom, PASS=G.ATOM_PASS, STEP=ATOM_STEP, BLOCK=G.BLOC
     return out
 
 
-def fullest_pass(A, c_row, PASS=G.ATOM_PASS):
+def fullest_pass(A, c_row, PASS=G.ATOM_PASS, STEP=ATOM_STEP):
     """the most a pass can hold when a row has at most c_row candidates: the last step starts at PASS - step_rows * A at the most"""
-    return min(PASS, PASS - step_rows(A) * A + step_rows(A) * c_row)
+    return min(PASS, PASS - step_rows(A, STEP) * A + step_rows(A, STEP) * c_row)
 
 
-def design_counts(A, c_row, short, PASS=G.ATOM_PASS):
+def design_counts(A, c_row, short, PASS=G.ATOM_PASS, STEP=ATOM_STEP):
     """candidates to keep in each row so that the first pass closes holding fullest_pass (short: one less): whole steps, one step that
     brings the count to target - a step's worth, and a last whole step -> (counts, target)"""
-    sr = step_rows(A)
+    sr = step_rows(A, STEP)
     s, th = sr * c_row, PASS - sr * A
-    target = fullest_pass(A, c_row, PASS) - (1 if short else 0)
+    target = fullest_pass(A, c_row, PASS, STEP) - (1 if short else 0)
     before = target - s
     assert 0 <= before <= th < target
     q, rem = divmod(before, s)
@@ -435,7 +456,7 @@ def atom_inputs(an, rng, lens, L, profile, slots=None):
         aatype[e, :m] = aatype_of(rng, m, comp, A)
         if kind.startswith("design"):
             cand = candidate_slots(an)[min(int(aatype[e, 0]), 20)] if m else None
-            counts, _ = design_counts(A, int(cand.sum()), kind.split("-")[1] == "short")
+            counts, _ = design_counts(A, int(cand.sum()), kind.split("-")[1] == "short", *an.fz.pass_step)
             tail = kind.split("-")[2]
             assert m == len(counts) + DESIGN_TAILS[tail], (m, len(counts), tail)
             for r, c in enumerate(counts):
@@ -451,12 +472,12 @@ def atom_inputs(an, rng, lens, L, profile, slots=None):
             ty = np.zeros(m, np.int64) if aakind == "noaatype" else np.minimum(aatype[e, :m], 20)
             staged = lambda: (mask[e, :m] != 0) & candidate_slots(an)[ty] & np.isfinite(pos[e, :m]).all(axis=-1)
             if kind in ("head_pass", "tail_pass"):                             # a cleared run longer than any pass of the chain, with two passes left
-                span = max(b - a for a, b, _ in pass_split(staged().sum(axis=1), A)) + 1
+                span = max(b - a for a, b, _ in pass_split(staged().sum(axis=1), A, *an.fz.pass_step)) + 1
                 assert 3 * span < m, (m, span, "the chain is too short for a run of a pass and two passes")
                 mask[e, :span if kind == "head_pass" else 0] = 0
                 mask[e, m - span if kind == "tail_pass" else m:m] = 0
             if float(rate):                                                    # a non-finite value in the last row of every pass and in the first of the next
-                for _, end, _ in pass_split(staged().sum(axis=1), A)[:-1]:
+                for _, end, _ in pass_split(staged().sum(axis=1), A, *an.fz.pass_step)[:-1]:
                     for r in (end - 1, end):
                         slots = np.flatnonzero(staged()[r])
                         if len(slots):
@@ -490,6 +511,66 @@ def atom_pair_inputs(an, rng, lens, L, profile):
     return dict(pt=pt, mt=mt, pp=pp, mp=None if mpred == "null" else mp, aatype=aa)
 
 
+PLANT_PLACE = 1100               # a place of a designed pass behind every pass the hand-picked tests of the loss stage (1024 at the most)
+BIG_WEIGHT = F(1e15)             # finite through (w_i + w_j) * unit and a sum of a pass' worth of terms: 2e15 * 1280 < 3.4e38
+
+
+def plant_last_place(pos, atom, PASS, STEP):
+    """a designed chain of the violation loss, pos [m, A, 3] and its atoms bool [m, A]: the atom at the LAST place of the first pass is
+    moved next to the chain's first atom, the one at PLANT_PLACE next to its second, both of row 0 and so of another residue. A finite
+    move of an atom changes nothing that is staged; the places are those of the ascending (row, slot) order, np.argwhere's"""
+    idx = np.argwhere(atom)
+    staged = pass_split(atom.sum(axis=1), atom.shape[1], PASS, STEP)[0][2]
+    assert staged > PLANT_PLACE and idx[1][0] == 0 and idx[PLANT_PLACE][0] > 0
+    for place, near, shift in ((staged - 1, 0, (0.25, 0, 0)), (PLANT_PLACE, 1, (0, 0.25, 0))):
+        pos[tuple(idx[place])] = pos[tuple(idx[near])] + np.asarray(shift, F)
+
+
+def plant_disulfide(pos, atom, aatype, A):
+    """a chain that is not designed: the SG of its second CYS row that has one is moved next to the SG of the first (a helix brings no two
+    SG inside the clash distance), so that a pair passes the distance test and is struck out as a disulfide. Only ordinary coordinates
+    move: a +-3e19 placed at a pass edge stays"""
+    if A == 4 or aatype is None:
+        return
+    sg = V.SG_SLOT[A]
+    rows = np.flatnonzero(atom[:, sg] & (aatype == V.CYS) & (np.abs(pos[:, sg]) < 1e6).all(axis=-1))
+    if len(rows) >= 2:
+        pos[rows[1], sg] = pos[rows[0], sg] + np.asarray((0.25, 0, 0), F)
+
+
+def vloss_inputs(an, rng, lens, L, profile):
+    """the violation loss: atom_inputs and the upstream weights w_clash [n, L, A] and w_link [n, L, 3]: normal values of both signs, a
+    tenth of them exact zeros, one +-1e15 on an atom and one on a link of the first chain that has one, and NaN bit patterns wherever
+    the contract says that no weight is read: a slot that is no atom (atoms_of), a row whose link does not exist (_links), every row
+    behind a length. Both sets come from the restatement. A designed chain gets its two planted pairs (plant_last_place), every other
+    chain with two CYS a disulfide (plant_disulfide); neither changes what is staged"""
+    chains, _ = _split(profile)
+    d = atom_inputs(an, rng, lens, L, profile)
+    pos, mask, aatype = d["pos"], d["mask"], d["aatype"]
+    n, A = len(lens), an.A
+    atom, link = np.zeros((n, L, A), bool), np.zeros((n, L), bool)
+    for e, m in enumerate(lens):
+        aa = None if aatype is None else aatype[e, :m]
+        if m:
+            atom[e, :m] = SA.atoms_of(pos[e, :m], mask[e, :m], aa, SA.default_table(A))[0]
+        if chains[e][1].startswith("design"):
+            plant_last_place(pos[e, :m], atom[e, :m], *an.fz.pass_step)
+        elif m:
+            plant_disulfide(pos[e, :m], atom[e, :m], aa, A)
+        if m > 1:
+            link[e, :m - 1] = VL._links(pos[e, :m], mask[e, :m], aa, an.params[1])["exist"]
+    w = dict(w_clash=rng.standard_normal((n, L, A)).astype(F), w_link=rng.standard_normal((n, L, 3)).astype(F))
+    for k, live in (("w_clash", atom), ("w_link", np.repeat(link[..., None], 3, axis=-1))):
+        w[k][rng.random(w[k].shape) < 0.1] = 0
+        for e in range(n):
+            at = np.argwhere(live[e])
+            if len(at):
+                w[k][e][tuple(at[int(rng.integers(len(at)))])] = BIG_WEIGHT * (1 if rng.integers(2) else -1)
+                break
+        w[k].view(np.uint32)[~live] = AN.NAN_BITS
+    return dict(d, **w)
+
+
 def backbone_inputs(an, rng, lens, L, profile):
     d = atom_inputs(an, rng, lens, L, profile)
     if d["aatype"] is not None:
@@ -511,7 +592,7 @@ def apply_inputs(an, rng, lens, L, profile):
 
 
 FAMILIES = dict(pair=pair_inputs, site=site_inputs, soft=soft_inputs, fape=fape_inputs, atoms=atom_inputs, atom_pair=atom_pair_inputs, backbone=backbone_inputs,
-                labels=labels_inputs, apply=apply_inputs)
+                labels=labels_inputs, apply=apply_inputs, vloss=vloss_inputs)
 
 
 def draw(an, rng, lens, L, profile):
@@ -554,6 +635,10 @@ def _labels(A, slot, param):
     return _with(G.Labels(), A, 1, "dssp labels")
 
 
+LONG_LENS = ((4, (1250, 1250, 900, 700)), (14, (640, 640, 420, 300)), (37, (150, 150, 110, 90)))
+VLOSS_LONG_LENS = ((4, (1050, 1050, 750, 590)), (14, (540, 540, 350, 250)), (37, (125, 125, 92, 75)))       # the same chains at a pass of 1280 for 1536
+
+
 @dataclasses.dataclass(frozen=True)
 class Spec:
     make: object                # (A, slot, param) -> Analysis
@@ -572,9 +657,17 @@ class Spec:
     noises: tuple = NOISES
     bad: tuple = None           # the non-finite values under set masks, None: BAD
     still: bool = False         # at noise 0 the prediction is the truth itself, not a rigid motion of it
+    pass_atoms: int = G.ATOM_PASS   # the atoms of a pass of an atom-pass sweep
+    step: int = ATOM_STEP           # the slots its staging step examines
+    long_lens: tuple = LONG_LENS    # the rows of the four chains of the long4 / long14 / long37 cases, by layout
+
+    @property
+    def pass_step(self):
+        return self.pass_atoms, self.step
 
     def edges(self, A):
-        return (step_rows(A) if self.atom_pass else 64, self.tile(A), max(self.row_pass) if self.row_pass else (G.ATOM_PASS // A if self.atom_pass else 256))
+        return (step_rows(A, self.step) if self.atom_pass else 64, self.tile(A),
+                max(self.row_pass) if self.row_pass else (self.pass_atoms // A if self.atom_pass else 256))
 
 
 SLOTS = ((4, 1, 0), (14, 4, 0), (37, 36, 0), (14, 1, 0), (37, 3, 0), (4, 3, 0), (14, 13, 0), (37, 1, 0))     # CA, CB and the layout's last slot
@@ -591,6 +684,8 @@ SPECS = dict(
     sasa=Spec(_sasa, ((14, 0, 1), (4, 0, 1), (37, 0, 1)), lambda A: G.SASA_TILE_ROWS, atom_pass=True, mixes=8, cap=80),
     violations=Spec(lambda A, s, p: G.Violations(A), LAYOUTS3, G.viol_tile_rows, atom_pass=True, mixes=8, cap=80,
                     geoms=tuple(g for g in GEOMS if g != "coincident")),
+    violation_loss=Spec(lambda A, s, p: G.ViolationLoss(A, p), LAYOUTS3 + tuple((A, s, 1) for A, s, _ in LAYOUTS3), G.viol_tile_rows, atom_pass=True, mixes=8, cap=80,
+                        pass_atoms=G.VLOSS_PASS, step=VLOSS_STEP, long_lens=VLOSS_LONG_LENS),
     lddt_atoms=Spec(lambda A, s, p: G.LddtAtoms(A), LAYOUTS3, lambda A: G.lddta_tile_rows(A, False), atom_pass=True, mixes=8, cap=80),
     frames=Spec(_frames, ((14, 0, 1), (37, 0, 1), (4, 0, 0), (14, 0, 0)), lambda A: 32, packed=False, mixes=10, geoms=("helix", "lattice")),
     superpose=Spec(lambda A, s, p: _with(G.Superpose(), A, s, "superpose"), SLOTS, lambda A: 64, waves=True, geoms=WAVE_GEOMS, bad=BAD[:3], mixes=8),
@@ -598,7 +693,7 @@ SPECS = dict(
     gdt=Spec(lambda A, s, p: _with(G.Gdt(), A, s, "gdt"), SLOTS, lambda A: 64, waves=True, geoms=WAVE_GEOMS, bad=BAD[:3], noises=NOISES[1:], mixes=8, cap=80),
 )
 PAIRED = ("lddt", "lddt_soft", "fape", "lddt_atoms", "superpose", "tmscore", "gdt")            # the analyses that take mask_pred
-WITH_AATYPE = ("hbond", "labels", "sasa", "violations", "lddt_atoms", "frames")                 # the ABI takes NULL for aatype
+WITH_AATYPE = ("hbond", "labels", "sasa", "violations", "violation_loss", "lddt_atoms", "frames")              # the ABI takes NULL for aatype
 NEED_MARGIN = ("lddt_soft", "fape", "superpose", "tmscore", "gdt", "tmalign")                              # their comparators need a margin of the inputs: redrawn
 
 
@@ -659,7 +754,7 @@ def cases(seed=0, per=None):
             A, slot, param = variant or spec.variants[k % len(spec.variants)]
             form = form or _forms(spec, k, lens, rng)
             case_profile = case_profile or _case_profile(name, k)
-            if (name == "frames" and param == 1) or (name in ("sasa", "violations") and A == 14):     # (the ABI refuses a NULL aatype there)
+            if (name == "frames" and param == 1) or (name in ("sasa", "violations", "violation_loss") and A == 14):     # (the ABI refuses a NULL aatype there)
                 case_profile = case_profile.replace("noaatype", "aatype")
             if form[0] == "null":                                              # length NULL: every chain has L rows
                 lens = [max(list(lens) + [1])] * len(lens)
@@ -694,12 +789,12 @@ def cases(seed=0, per=None):
                 add(group, lens, [p for m in masks for p in profs(1, mask=m, geom=geom)], form, spec.variants[0] if name == "fape" else None)
         # 3. the atom-pass sweeps: for every layout a chain whose pass closes at its fullest, one slot under it, and what lies behind
         if spec.atom_pass:
-            for v in spec.variants:
+            for v in spec.variants[:3]:                                        # (a layout each; the variants behind them repeat the layouts at other parameters)
                 an = spec.make(*v)
                 comp = "ala" if an.family == "atom_pair" else "big"
                 c_row = int(candidate_slots(an)[ALA if comp == "ala" else G.biggest_type(v[0] if v[0] != 4 else 14)].sum())
                 for short, tails in ((False, ("end", "empty")), (True, ("plus1", "more"))):
-                    rows = len(design_counts(v[0], c_row, short)[0])
+                    rows = len(design_counts(v[0], c_row, short, *spec.pass_step)[0])
                     lens = [rows + DESIGN_TAILS[t] for t in tails]
                     ps = profs(2, geom="helix", rate="0", comp=comp)
                     ps = ["/".join(p.split("/")[:1] + [f"design-{'short' if short else 'full'}-{t}"] + p.split("/")[2:5] + ["equal"]) for p, t in zip(ps, tails)]
@@ -707,7 +802,7 @@ def cases(seed=0, per=None):
             # chains of several passes that are NOT designed: mixed types, runs, independent clearing, non-finite values at the pass edges
             # (placed through pass_split), a cleared run longer than any of the chain's passes at its start and at its end
             for v, form in zip(spec.variants, (("packed", 3, 2), ("padded", 1), ("packed", 0, 0))):
-                lens = {4: [1250, 1250, 900, 700], 14: [640, 640, 420, 300], 37: [150, 150, 110, 90]}[v[0]]
+                lens = list(dict(spec.long_lens)[v[0]])
                 ps = (profs(1, geom="helix", mask="head_pass", rate="0.01", comp="mix", mpred="equal") + profs(1, geom="helix", mask="tail_pass", rate="0.05", comp="alternate", mpred="equal")
                       + profs(1, geom="lattice", mask="gap_step" if v[0] == 4 else "runs64", rate="0.01", comp="mix", mpred="subset") + profs(1, geom="helix", mask="iid50", rate="0.05", comp="mix", mpred="equal"))
                 add(f"long{v[0]}", lens, ps, form, v, "mask/aatype/small")
@@ -880,7 +975,7 @@ def build(case):
     spec = SPECS[case.analysis]
     an = spec.make(case.A, case.slot, case.param)
     an.fz = spec
-    an.guard = GUARD if case.profile[-1].endswith("wide") else 8 if case.analysis == "violations" else 4      # (chain_counts is int64: 8)
+    an.guard = GUARD if case.profile[-1].endswith("wide") else 8 if case.analysis in ("violations", "violation_loss") else 4      # (chain_counts and counts are int64: 8)
     lens = list(case.lens)
     L = case.form[1] if case.form[0] == "clamped" else max(lens + [1]) + (case.form[1] if case.form[0] == "padded" else 0)
     eff = [min(m, L) for m in lens]

@@ -30,6 +30,7 @@ import _lddt_soft as S
 import _sasa as SA
 import _superpose as SP
 import _tmscore as TM
+import _violation_loss as VL
 import _violations as V
 from _devpath import FILL, GUARD, to_dev
 
@@ -45,6 +46,7 @@ KNN_PASS = 2048                 # fcz_knn.h: constexpr uint32_t KNN_PASS = 2048 
 LDDT_PASS = 1024                # fcz_lddt.h: constexpr uint32_t LDDT_PASS = 1024 (fcz_lddt_pass(); k_lddt_soft stages the same rows)
 HBOND_PASS = 480                # fcz_dssp.h: constexpr uint32_t HBOND_PASS = 480 (fcz_hbond_pass())
 ATOM_PASS = 1536                # fcz_sasa.h / fcz_violations.h / fcz_lddt_atoms.h: SASA_PASS = VIOL_PASS = LDDTA_PASS = 1536
+VLOSS_PASS = 1280               # fcz_violation_loss.h: constexpr uint32_t VLOSS_PASS = 1280 (fcz_violation_loss_pass())
 SWEEP_PER_CU = 16               # fcz_abi.hip, chain_tiles: uint32_t blocks_per_cu = 16u (knn, lddt, lddt_soft, dssp, sasa)
 ATOMS_PER_CU = 12               # fcz_abi.hip: chain_tiles ct(ctx, packed, n, rows, viol_tile_rows(g.A), 12u); lddt_atoms' decide and score alike
 WAVES_PER_CU = 16               # fcz_abi.hip, superpose / tmscore / gdt / k_ta_count: max_blocks = (uint32_t)ctx->n_cu * 16u
@@ -616,6 +618,42 @@ class Violations(Analysis):
     def check(self, got, exp, what):
         V.same_violations(got, exp, what)
         assert exp["clash_count"].any() and exp["link_violation"].any()
+
+
+class ViolationLoss(Analysis):
+    """the value and the gradient of one call each: two launches over viol_tile_rows(A) rows a tile, 12 blocks a CU (fcz_abi.hip,
+    vloss_rows). param 0: tolerance 0 and link factor 0.5, so that every term class is there; param 1: the defaults (1.5, 12.0)"""
+    family = "vloss"
+    per_cu = ATOMS_PER_CU
+    chain_keys = frozenset({"counts"})
+    PARAMS = ((F(0), F(0.5)), (VL.TOL, VL.FACTOR))
+
+    def __init__(self, A=14, param=0):
+        self.A, self.tile_rows, self.name, self.params = A, viol_tile_rows(A), f"violation_loss A={A}" + (" defaults" if param else ""), self.PARAMS[param]
+
+    def launches(self):
+        return [(f"{self.name} {k}", self.tile_rows, self.per_cu) for k in ("value", "grad")]
+
+    def pool(self, lens, L):
+        inp = dict(zip(("pos", "mask", "aatype"), atoms_pool(lens, L, self.A, 131)))
+        return dict(inp, w_clash=VL.weights((len(lens), L, self.A), 132), w_link=VL.weights((len(lens), L, 3), 133))
+
+    def ref(self, inp, lens):
+        table = V.default_table(self.A)
+        out = VL.loss(inp["pos"], inp["mask"], inp["aatype"], lens, table, *self.params)
+        return dict(out, grad=VL.grad(inp["pos"], inp["mask"], inp["aatype"], lens, table, inp["w_clash"], inp["w_link"], *self.params))
+
+    def fair(self, inp, ref, lens):
+        assert int(ref["counts"][:, 0].max()) > VLOSS_PASS, (ref["counts"][:, 0], "the long chain takes one pass only")
+        assert (ref["clash_loss"] > 0).any() and all((ref["link_loss"][..., k] > 0).any() for k in range(3)) and np.isfinite(ref["grad"]).all()
+
+    def run(self, codec, dev, bound_t, n, rows, packed):
+        a = (dev["pos"], dev["mask"], dev["aatype"], bound_t, n, rows, self.layout, packed)
+        kw = dict(tol=self.params[0], factor=self.params[1], guard=self.guard)
+        return dict(VL.run_value(codec, *a, **kw), grad=VL.run_grad(codec, *a, dev["w_clash"], dev["w_link"], **kw))
+
+    def check(self, got, exp, what):
+        VL.same(got, exp, what)
 
 
 SWAP_TYPES = (LA.ASP, LA.GLU, LA.PHE, LA.TYR)

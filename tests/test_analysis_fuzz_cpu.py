@@ -11,6 +11,8 @@ import pytest
 
 import _analysis_fuzz as FZ
 import _sweep_grids as G
+import _violation_loss as VL
+import _violations as V
 
 CASES = FZ.cases()
 BY = collections.defaultdict(list)
@@ -91,6 +93,8 @@ def test_row_pass_edges(name):
 def test_atom_pass_edges(name):
     """for every layout: a chain whose first pass closes holding the most a pass of the layout can hold, one whose pass closes one slot
     under it, a chain that ends on that pass edge, one that goes on for a row, and one whose final pass stages nothing"""
+    spec = FZ.SPECS[name]
+    PASS, STEP = spec.pass_step
     seen = collections.defaultdict(set)
     top = {}
     for c in BY[name]:
@@ -100,17 +104,17 @@ def test_atom_pass_edges(name):
             if m == 0:
                 continue
             atom = FZ.candidates(b, e)
-            passes = FZ.pass_split(atom.sum(axis=1), c.A)
+            passes = FZ.pass_split(atom.sum(axis=1), c.A, PASS, STEP)
             kind = c.profile[e].split("/")[1]
             if kind.startswith("design"):
                 c_row = int(cand[min(int(b.inp["aatype"][e, 0]), 20)].sum())
-                top[c.A] = FZ.fullest_pass(c.A, c_row)
-                assert passes == FZ.stage_slots_transcribed(atom), c.id
+                top[c.A] = FZ.fullest_pass(c.A, c_row, PASS, STEP)
+                assert passes == FZ.stage_slots_transcribed(atom, PASS, STEP), c.id
             first = passes[0][2]
-            seen[c.A] |= {("staged", first)} | ({"ends on the edge"} if len(passes) == 1 and first > G.ATOM_PASS - FZ.step_rows(c.A) * c.A else set())
+            seen[c.A] |= {("staged", first)} | ({"ends on the edge"} if len(passes) == 1 and first > PASS - FZ.step_rows(c.A, STEP) * c.A else set())
             if len(passes) > 1:
                 seen[c.A] |= {("behind", passes[1][1] - passes[1][0], passes[-1][2])}
-    assert top == {4: G.ATOM_PASS, 14: G.ATOM_PASS, 37: G.ATOM_PASS if name == "lddt_atoms" else 1523}, top
+    assert top == ({4: 1280, 14: 1280, 37: 1267} if name == "violation_loss" else {4: G.ATOM_PASS, 14: G.ATOM_PASS, 37: G.ATOM_PASS if name == "lddt_atoms" else 1523}), top
     # chains that are NOT designed, through the mirror on the built inputs (the profile's name proves nothing): three passes and more, a
     # cleared run longer than any pass of the chain at its start and at its end with two staged passes beside it, a cleared run longer
     # than a staging step inside a chain, and a non-finite coordinate under a set mask in a pass' last row and in the next pass' first
@@ -125,14 +129,14 @@ def test_atom_pass_edges(name):
                     continue
                 atom = FZ.candidates(b, e)
                 per_row = atom.sum(axis=1)
-                passes = FZ.pass_split(per_row, A)
+                passes = FZ.pass_split(per_row, A, PASS, STEP)
                 full = [p for p in passes if p[2]]
                 live = np.flatnonzero(per_row)
                 span = max(int(live[live < q][-1]) - int(live[live >= p][0]) + 1 for p, q, _ in full) if full else m      # rows from a pass' first atom to its last
                 head, tail = (int(live[0]), m - 1 - int(live[-1])) if len(live) else (m, 0)
                 gaps = np.diff(live) - 1 if len(live) > 1 else np.zeros(0, int)
                 wild |= {("passes", min(len(full), 3))} | ({"head"} if len(full) >= 2 and head > span else set()) | ({"tail"} if len(full) >= 2 and tail > span else set())
-                wild |= {"inner run"} if len(gaps) and gaps.max() > FZ.step_rows(A) else set()
+                wild |= {"inner run"} if len(gaps) and gaps.max() > FZ.step_rows(A, STEP) else set()
                 pos, mask = (b.inp["pt"], b.inp["mt"]) if "pt" in b.inp else (b.inp["pos"], b.inp["mask"])
                 with np.errstate(invalid="ignore"):
                     bad = ((mask[e, :m] != 0) & ~np.isfinite(pos[e, :m]).all(axis=-1)).any(axis=1)
@@ -166,7 +170,7 @@ def test_the_mirror_is_the_transcription():
     step of other sizes"""
     rng = np.random.default_rng(5)
     for A in (4, 14, 37):
-        for PASS, STEP in ((G.ATOM_PASS, FZ.ATOM_STEP), (1024, 256), (512, 512)):
+        for PASS, STEP in ((G.ATOM_PASS, FZ.ATOM_STEP), (G.VLOSS_PASS, FZ.VLOSS_STEP), (1024, 256), (512, 512)):     # (1280, 512): a step that does not divide the pass
             for m in (0, 1, STEP // A - 1, STEP // A, STEP // A + 1, 3 * (PASS // A) + 7, int(rng.integers(1, 400))):
                 for density in (0.0, 0.05, 0.5, 0.97, 1.0):
                     atom = rng.random((m, A)) < density
@@ -180,13 +184,15 @@ def test_the_mirror_is_the_transcription():
 
 
 def test_a_designed_pass_closes_where_it_was_aimed():
-    for A, c_row in ((4, 4), (14, 14), (37, 36), (37, 37)):
-        for short in (False, True):
-            counts, target = FZ.design_counts(A, c_row, short)
-            assert target == FZ.fullest_pass(A, c_row) - short and max(counts) <= c_row
-            assert FZ.pass_split(counts, A) == [(0, len(counts), target)]
-            assert FZ.pass_split(counts + [c_row], A) == [(0, len(counts), target), (len(counts), len(counts) + 1, c_row)]
-            assert FZ.pass_split(counts + [0] * 50, A)[-1][2] == 0
+    for P in ((G.ATOM_PASS, FZ.ATOM_STEP), (G.VLOSS_PASS, FZ.VLOSS_STEP)):
+        for A, c_row in ((4, 4), (14, 14), (37, 36), (37, 37)):
+            for short in (False, True):
+                counts, target = FZ.design_counts(A, c_row, short, *P)
+                assert target == FZ.fullest_pass(A, c_row, *P) - short and max(counts) <= c_row
+                assert FZ.pass_split(counts, A, *P) == [(0, len(counts), target)]
+                assert FZ.pass_split(counts + [c_row], A, *P) == [(0, len(counts), target), (len(counts), len(counts) + 1, c_row)]
+                assert FZ.pass_split(counts + [0] * 50, A, *P)[-1][2] == 0
+    assert [FZ.fullest_pass(A, c, G.VLOSS_PASS, FZ.VLOSS_STEP) for A, c in ((4, 4), (14, 14), (37, 36))] == [1280, 1280, 1267]
 
 
 def test_the_mirrored_constants_are_the_headers_():
@@ -205,7 +211,141 @@ def test_the_mirrored_constants_are_the_headers_():
     assert const("fcz_sasa.h", "SASA_STEP") == const("fcz_violations.h", "VIOL_STEP") == const("fcz_lddt_atoms.h", "LDDTA_STEP") == FZ.ATOM_STEP
     assert const("fcz_sasa.h", "SASA_PASS") == const("fcz_violations.h", "VIOL_PASS") == const("fcz_lddt_atoms.h", "LDDTA_PASS") == G.ATOM_PASS
     assert (const("fcz_knn.h", "KNN_PASS"), const("fcz_lddt.h", "LDDT_PASS"), const("fcz_dssp.h", "HBOND_PASS")) == (G.KNN_PASS, G.LDDT_PASS, G.HBOND_PASS)
+    assert const("fcz_violation_loss.h", "VLOSS_PASS") == G.VLOSS_PASS == FZ.SPECS["violation_loss"].pass_atoms
+    assert const("fcz_violation_loss.h", "VLOSS_STEP") == FZ.VLOSS_STEP == FZ.SPECS["violation_loss"].step and G.VLOSS_PASS % FZ.VLOSS_STEP != 0
     assert const("fcz_sasa.h", "SASA_TILE_ROWS") == G.SASA_TILE_ROWS and const("fcz_lddt_atoms.h", "LDDTA_DECIDE_ROWS") == G.LDDTA_DECIDE_ROWS
+
+
+# ---- the violation loss: a sweep that SUMS, so where a partner is staged matters -----------------------------------------------------------
+VLOSS_TOPS = {4: 1280, 14: 1280, 37: 1267}
+_PAIRS = {}
+
+
+def _vloss_chain(c, e):
+    """chain e of a violation-loss case through the restatement's dense matrices and the mirror -> dict: idx [N, 2] the atoms in
+    ascending (row, slot), clash bool [N, N] (exclusions struck out), T and d [N, N], and of every atom the pass that stages it, its
+    place in that pass and the staging step of the pass"""
+    if (c, e) not in _PAIRS:
+        b, spec = FZ.build(c), FZ.SPECS[c.analysis]
+        m = b.eff[e]
+        aa = None if b.inp["aatype"] is None else b.inp["aatype"][e, :m]
+        idx, _, clash, T, d = VL._pairs(b.inp["pos"][e, :m], b.inp["mask"][e, :m], aa, V.default_table(c.A), b.an.params[0])
+        assert np.array_equal(idx, np.argwhere(FZ.candidates(b, e)))
+        passes = FZ.pass_split(np.bincount(idx[:, 0], minlength=m), c.A, *spec.pass_step)
+        ends = np.asarray([q for _, q, _ in passes])
+        in_pass = np.searchsorted(ends, idx[:, 0], side="right")
+        first = np.searchsorted(idx[:, 0], [p for p, _, _ in passes])          # the atoms in front of every pass
+        place = np.arange(len(idx)) - first[in_pass]
+        step = (idx[:, 0] - np.asarray([p for p, _, _ in passes])[in_pass]) // FZ.step_rows(c.A, spec.step)
+        assert all(place[in_pass == k].tolist() == list(range(s)) for k, (_, _, s) in enumerate(passes))
+        _PAIRS[(c, e)] = dict(idx=idx, clash=clash, T=T, d=d, passes=passes, in_pass=in_pass, place=place, step=step)
+    return _PAIRS[(c, e)]
+
+
+def test_violation_loss_pairs_at_the_last_place():
+    """for every layout, in the chain whose first pass closes at the fullest it can be and in the one that closes one slot under it: a
+    clashing pair (no exclusion, a direction) whose partner is staged at the LAST place of that pass, and one whose partner sits at a
+    place of 1024 or more; the hand-picked tests of the loss stage 1024 atoms a pass at the most"""
+    seen = collections.defaultdict(set)
+    for c in BY["violation_loss"]:
+        if c.group != "design":
+            continue
+        ref = FZ.realise(c).ref
+        for e in range(len(c.lens)):
+            p = _vloss_chain(c, e)
+            staged = p["passes"][0][2]
+            last, other = staged - 1, FZ.PLANT_PLACE
+            assert staged in (VLOSS_TOPS[c.A], VLOSS_TOPS[c.A] - 1) and 1024 <= other < last
+            for j in (last, other):
+                assert p["in_pass"][j] == 0 and p["place"][j] == j
+                with np.errstate(invalid="ignore"):
+                    moves = p["clash"][:, j] & (p["d"][:, j] != 0) & ((p["T"][:, j] - p["d"][:, j]) != 0)
+                assert moves.any(), (c.id, e, j, "no clashing pair has its partner at this place")
+                i = int(np.flatnonzero(moves)[0])
+                assert p["idx"][i][0] != p["idx"][j][0] and ref["clash_loss"][(e,) + tuple(p["idx"][i])] > 0 and ref["grad"][(e,) + tuple(p["idx"][i])].any()
+            seen[c.A].add(staged)
+            print(f"A = {c.A}, {c.profile[e].split('/')[1]}: the pass stages {staged}, a partner at place {last} (row {p['idx'][last][0]}, slot {p['idx'][last][1]}) and at {other}")
+    assert {A: s for A, s in seen.items()} == {A: {t, t - 1} for A, t in VLOSS_TOPS.items()}, dict(seen)
+
+
+def test_violation_loss_sums_live_across_a_pass_edge():
+    """for every layout, in a long chain: a query atom whose clash partners are staged by two passes at least (its sum register lives
+    across the barrier that closes a pass), and a query atom with three partners and more inside one staging step"""
+    for A in (4, 14, 37):
+        across = within = 0
+        for c in BY["violation_loss"]:
+            if c.A != A or not c.group.startswith("long"):
+                continue
+            for e in range(len(c.lens)):
+                p = _vloss_chain(c, e)
+                in_passes = np.stack([p["clash"][:, p["in_pass"] == k].any(axis=1) for k in range(len(p["passes"]))])
+                across += int((in_passes.sum(axis=0) >= 2).sum())
+                key = p["in_pass"] * 1000 + p["step"]
+                within += sum(int((p["clash"][:, key == k].sum(axis=1) >= 3).sum()) for k in np.unique(key))
+        print(f"A = {A}: {across} query atoms with partners in two passes and more, {within} (atom, step) with three partners and more")
+        assert across and within, (A, across, within)
+
+
+def _sg_pairs(b, e):
+    """the SG - SG pairs of two CYS rows of chain e that pass the distance test and are struck out as disulfides"""
+    A, m = b.case.A, b.eff[e]
+    if A == 4 or b.inp["aatype"] is None or m < 2:
+        return 0
+    aa, pos = b.inp["aatype"][e, :m], b.inp["pos"][e, :m]
+    atom, radius = VL.atoms_of(pos, b.inp["mask"][e, :m], aa, V.default_table(A))
+    rows = np.flatnonzero(atom[:, V.SG_SLOT[A]] & (aa == V.CYS))
+    sg, R = pos[rows, V.SG_SLOT[A]], radius[rows, V.SG_SLOT[A]]
+    T = (R[:, None] + R[None, :]) - b.an.params[0]
+    with np.errstate(over="ignore", invalid="ignore"):
+        return int(((T > 0) & (V._d2(sg[:, None], sg[None, :]) < T * T) & ~np.eye(len(rows), dtype=bool)).sum()) // 2
+
+
+def test_violation_loss_term_classes():
+    """over the list, at tolerance 0 and factor 0.5: clash terms and each of the three link terms above 0 in every layout, a PRO link
+    with a term above 0, a coincident chain (every pair at d == 0: the value is the sum of the T in sequence, the gradient 0), and in
+    atom14 and atom37 an SG - SG pair of two CYS rows inside the clash distance, which is struck out. Every restated value and
+    gradient of every case, at either parameter set, is finite: the comparison on bits never rests on the payload of a NaN"""
+    terms, pro, sg, still = collections.defaultdict(set), 0, collections.Counter(), 0
+    assert {c.param for c in BY["violation_loss"]} == {0, 1}
+    for c in BY["violation_loss"]:
+        b = FZ.realise(c)
+        assert b.redrawn == 0 and all(np.isfinite(v).all() for v in b.ref.values()), c.id
+        if c.param:
+            continue
+        terms[c.A] |= ({"clash"} if (b.ref["clash_loss"] > 0).any() else set()) | {k for k in range(3) if (b.ref["link_loss"][..., k] > 0).any()}
+        for e, m in enumerate(b.eff):
+            sg[c.A] += _sg_pairs(b, e)
+            if b.inp["aatype"] is not None and m > 1:
+                pro += int(((b.inp["aatype"][e, 1:m] == V.PRO) & (b.ref["link_loss"][e, :m - 1] > 0).any(axis=-1)).sum())
+            if c.profile[e].startswith("coincident/") and b.ref["counts"][e, 0] >= 2:
+                p = _vloss_chain(c, e)
+                if p["clash"].any():
+                    assert (p["d"][p["clash"]] == 0).all() and not b.ref["grad"][e].any()
+                    want = VL._seq_sum(np.where(p["clash"], p["T"], np.float32(0)))
+                    assert np.array_equal(b.ref["clash_loss"][e][p["idx"][:, 0], p["idx"][:, 1]], want) and (want > 0).any()
+                    still += 1
+    print(f"PRO links with a term: {pro}; SG - SG pairs struck out: {dict(sg)}; coincident chains: {still}")
+    assert all(terms[A] == {"clash", 0, 1, 2} for A in (4, 14, 37)), dict(terms)
+    assert pro and still and sg[14] and sg[37], (pro, still, dict(sg))
+
+
+def test_violation_loss_weights():
+    """w_clash and w_link: exact zeros, both signs, one value of 1e15 in magnitude each in a case with atoms and links, and a NaN bit
+    pattern exactly where the restatement has no atom and no link; packed, the uncovered rows are finite"""
+    for c in BY["violation_loss"]:
+        b = FZ.build(c)
+        inp = b.inp
+        for e, m in enumerate(b.eff):
+            atom = FZ.candidates(b, e)
+            assert np.array_equal(np.isnan(inp["w_clash"][e, :m]), ~atom) and np.isnan(inp["w_clash"][e, m:]).all()
+            exist = VL._links(inp["pos"][e, :m], inp["mask"][e, :m], None if inp["aatype"] is None else inp["aatype"][e, :m], b.an.params[1])["exist"] if m > 1 else np.zeros(0, bool)
+            assert np.array_equal(~np.isnan(inp["w_link"][e, :max(m - 1, 0)]).any(axis=-1), exist) and np.isnan(inp["w_link"][e, max(m - 1, 0):]).all()
+        for k in ("w_clash", "w_link"):
+            w = inp[k][~np.isnan(inp[k])]
+            if len(w) > 100:
+                assert (w == 0).any() and (w > 0).any() and (w < 0).any() and (np.abs(w) == FZ.BIG_WEIGHT).sum() == 1, (c.id, k)
+            if b.packed:
+                assert all(np.isfinite(a).all() for a in (lambda f: (f[:c.form[1]], f[len(f) - c.form[2]:]))(FZ.form_arrays(b, {k: inp[k]})[k]))
 
 
 def test_tmalign_pairs():

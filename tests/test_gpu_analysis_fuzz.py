@@ -12,7 +12,9 @@ bounds. The groups: edges (0 to 3 rows and the tile edges), passes (the row-pass
 sites, coincident and collinear chains for the wave-per-chain kernels), long (TM_LDS_ROWS - 1 .. + 1; for the atom-pass sweeps long4 /
 long14 / long37: chains of three passes and more that are not designed, with cleared runs longer than a pass at either end and
 non-finite values at the pass edges), mix (everything by seed), and for TM-align pairs (every chain of a fuzzed set against a related
-or unrelated chain of a second set, 120 rows or under, through _sweep_grids.tmalign_check)."""
+or unrelated chain of a second set, 120 rows or under, through _sweep_grids.tmalign_check). The violation loss and its gradient run
+with their own pass of 1280 atoms, staged in ascending order: their designed chains hold a clash partner at the last place of the
+fullest pass, and their inputs carry upstream weights with zeros, a 1e15 and NaN patterns where no weight is read."""
 import pytest
 
 import _analysis_fuzz as FZ
@@ -30,6 +32,7 @@ def test_the_mirrored_constants_are_the_library_s(codec):
     assert lib.fcz_sasa_pass() == lib.fcz_violations_pass() == lib.fcz_lddt_atoms_pass() == G.ATOM_PASS
     assert (lib.fcz_knn_pass(), lib.fcz_lddt_pass(), lib.fcz_hbond_pass(), lib.fcz_fape_pass()) == (G.KNN_PASS, G.LDDT_PASS, G.HBOND_PASS, G.FAPE_PASS)
     assert FZ.ATOM_STEP == 2 * G.BLOCK and FZ.ATOM_STEP % G.BLOCK == 0 and G.ATOM_PASS % FZ.ATOM_STEP == 0
+    assert lib.fcz_violation_loss_pass() == G.VLOSS_PASS == 1280 and FZ.VLOSS_STEP == 2 * G.BLOCK and G.VLOSS_PASS % FZ.VLOSS_STEP != 0
 
 
 @pytest.mark.parametrize("analysis,group", GROUPS, ids=[f"{a}-{g}" for a, g in GROUPS])

@@ -36,7 +36,10 @@ def batch(request):
     tiles); in chain 8 two lone CA at exactly d == T of the tight run and two at d == T of the default run (no pair: d2 < T * T is
     strict), two coincident CA (d == 0: a value, no direction), a stretched link, a bent link, two PRO links and a link whose C
     coincides with N' (length 0, both cosines not finite). The weights hold NaN patterns where no atom and no link can be.
-    The restatements are computed once per configuration and shared."""
+    The restatements are computed once per configuration and shared.
+    The long chain's first pass closes at 1024 (backbone4), 1008 (atom14) and 936 (atom37) atoms: with every mask set the rule that
+    closes a pass is crossed on a whole staging step. The pass at its fullest (1280, 1280, 1267), one slot under it, and a clash
+    partner at its last place live in the fuzz (tests/_analysis_fuzz.py, the design group of violation_loss)."""
     A = request.param
     Q = _lib.load().fcz_violation_loss_pass()
     T = TILE[A]
@@ -307,6 +310,44 @@ def test_foldcomp_violation_loss(codec, batch, monkeypatch):
         foldcomp.violation_loss(x.detach(), dict(aatype=true["aatype"]), codec=codec)
     with pytest.raises(foldcomp.error):
         foldcomp.violation_loss(x.detach().cpu(), dict(true, mask=true["mask"].cpu(), aatype=true["aatype"].cpu(), length=None), codec=codec)
+
+
+def test_backward_from_one_output_alone(codec):
+    """every other backward here goes through out["loss"], whose upstream gradients are constant along a chain. Here the backward is
+    taken from clash_loss alone and from link_loss alone, under arbitrary elementwise weights, as a product and as an expanded
+    (stride 0 along the rows) gradient handed to backward() itself, so that what reaches the gradient kernel's wrapper is not
+    contiguous; each against the restatement with those weights and zeros for the other output, on bits"""
+    import torch
+    import foldcomp_amd as foldcomp
+    A, lens = 14, np.asarray([40, 23], np.uint32)
+    n, L = len(lens), int(lens.max())
+    rng = np.random.default_rng(77)
+    pos = np.stack([AN.helix(rng, L, A) for _ in range(n)])
+    mask = (rng.random((n, L, A)) > 0.03).astype(np.uint8)
+    aa = rng.integers(0, 21, size=(n, L)).astype(np.uint8)
+    aa[0, 5] = aa[1, 7] = V.PRO
+    true = dict(mask=to_dev(mask).bool(), aatype=to_dev(aa), length=to_dev(lens).to(torch.int32))
+    row = dict(clash_loss=VL.weights((n, 1, A), 78), link_loss=VL.weights((n, 1, 3), 79))
+    full = dict(clash_loss=VL.weights((n, L, A), 80), link_loss=VL.weights((n, L, 3), 81))
+    zeros = dict(clash_loss=np.zeros((n, L, A), F), link_loss=np.zeros((n, L, 3), F))
+    for key in ("clash_loss", "link_loss"):
+        for how in ("product", "expanded product", "expanded gradient"):
+            W = full[key] if how == "product" else np.ascontiguousarray(np.broadcast_to(row[key], full[key].shape))
+            x = to_dev(pos).requires_grad_(True)
+            out = foldcomp.violation_loss(x, true, tolerance=0.0, link_factor=0.5, codec=codec)
+            if how == "product":
+                (out[key] * to_dev(W)).sum().backward()
+            else:
+                Wt = to_dev(row[key]).expand(*full[key].shape)
+                assert Wt.stride(1) == 0 and not Wt.is_contiguous()
+                if how == "expanded product":
+                    (out[key] * Wt).sum().backward()
+                else:
+                    out[key].backward(gradient=Wt)
+            w = dict(zeros, **{key: W})
+            exp = VL.grad(pos, mask, aa, lens, TABLE[A], w["clash_loss"], w["link_loss"], *TIGHT)
+            assert np.abs(exp).max() > 0.1 and not exp[1, 23:].any()
+            VL.same(x.grad.cpu().numpy(), exp, f"pos.grad from {key} alone, {how}")
 
 
 def test_gradient_descent_lowers_the_loss(codec):

@@ -104,6 +104,12 @@ def load():
            for name in ("fcz_fape_dev", "fcz_fape_packed_dev", "fcz_fape", "fcz_fape_packed")},
         **{name: (i32, [vp] * 12 + [u32, u32, i32, i32, f32, f32, vp, vp, vp, vp])
            for name in ("fcz_fape_grad_dev", "fcz_fape_grad_packed_dev", "fcz_fape_grad", "fcz_fape_grad_packed")},
+        "fcz_fape_atoms_pass": (i32, []),
+        "fcz_fape_atoms_tile_rows": (i32, [i32]),
+        **{name: (i32, [vp] * 14 + [u32, u32, i32, f32, f32, vp, vp, vp])
+           for name in ("fcz_fape_atoms_dev", "fcz_fape_atoms_packed_dev", "fcz_fape_atoms", "fcz_fape_atoms_packed")},
+        **{name: (i32, [vp] * 14 + [u32, u32, i32, f32, f32, vp, vp, vp, vp, vp])
+           for name in ("fcz_fape_atoms_grad_dev", "fcz_fape_atoms_grad_packed_dev", "fcz_fape_atoms_grad", "fcz_fape_atoms_grad_packed")},
         "fcz_lddt_atoms_pass": (i32, []),
         "fcz_lddt_atoms_max_rows": (i32, [i32]),
         "fcz_lddt_default_swaps": (i32, [i32, vp]),
@@ -232,6 +238,8 @@ EXPORTS = ["fcz_ctx_create", "fcz_ctx_destroy", "fcz_ctx_stream", "fcz_ctx_synch
            "fcz_lddt_soft_grad", "fcz_lddt_soft_grad_packed",
            "fcz_fape_pass", "fcz_fape_dev", "fcz_fape_packed_dev", "fcz_fape_grad_dev", "fcz_fape_grad_packed_dev", "fcz_fape", "fcz_fape_packed", "fcz_fape_grad",
            "fcz_fape_grad_packed",
+           "fcz_fape_atoms_pass", "fcz_fape_atoms_tile_rows", "fcz_fape_atoms_dev", "fcz_fape_atoms_packed_dev", "fcz_fape_atoms_grad_dev",
+           "fcz_fape_atoms_grad_packed_dev", "fcz_fape_atoms", "fcz_fape_atoms_packed", "fcz_fape_atoms_grad", "fcz_fape_atoms_grad_packed",
            "fcz_lddt_atoms_pass", "fcz_lddt_atoms_max_rows", "fcz_lddt_default_swaps", "fcz_lddt_atoms_dev", "fcz_lddt_atoms_packed_dev", "fcz_lddt_atoms",
            "fcz_lddt_atoms_packed",
            "fcz_hbond_pass", "fcz_hbond_dev", "fcz_hbond_packed_dev", "fcz_dssp_labels_dev", "fcz_dssp_labels_packed_dev", "fcz_dssp", "fcz_dssp_packed",

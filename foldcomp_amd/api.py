@@ -422,6 +422,48 @@ def check_fape(clamp, scale, eps, atom, width=None):
         return slot, float(np.float32(clamp)), float(scale), float(np.float32(eps))
 
 
+def _swap_table(swaps, A, what="swaps"):
+    """an integer array [21, A] that is an involution within each row with entries < A -> uint8 [21, A] (lddt_atoms' rule)"""
+    table = np.asarray(swaps)
+    if table.shape != (21, A) or table.dtype.kind not in "iu":
+        raise ValueError(f"{what} must be an integer array of the shape (21, {A}), not {table.dtype} {table.shape}")
+    if (table < 0).any() or (table >= A).any():
+        raise ValueError(f"every entry of {what} must be a slot 0 .. {A - 1}")
+    table = np.ascontiguousarray(table, np.uint8)
+    if not np.array_equal(np.take_along_axis(table, table.astype(np.int64), axis=1), np.broadcast_to(np.arange(A, dtype=np.uint8), (21, A))):
+        raise ValueError(f"{what} must be an involution within each row: the partner of a slot's partner is the slot")
+    return table
+
+
+def check_fape_atoms(clamp, scale, eps, rename, shape, has_aatype=True, swaps="alphafold"):
+    """the argument rules of fape_atoms that need no torch and no GPU -> (clamp, scale, eps, rename, table): clamp, scale and eps as
+    check_fape reads them; pos [n, L, A, 3] or [R, A, 3] with A = 37, 14 or 4 and a chain bound of at most min(2^29, (2^31 - 1) // A)
+    rows, so that a frame's points fit int32. rename: "lddt_atoms" (decide inside the call), None (rename nothing) or an array /
+    tensor of the shape of pos without its last two axes, the decision already made (returned as it is); anything but None needs
+    aatype. swaps: "alphafold" (table None: the library's default) or lddt_atoms' integer array [21, A] (table: uint8 [21, A])."""
+    _, clamp, scale, eps = check_fape(clamp, scale, eps, 1)
+    shape = tuple(shape)
+    if len(shape) not in (3, 4) or shape[-1] != 3 or shape[-2] not in (37, 14, 4):
+        raise ValueError(f"pos must be float32 [n, L, A, 3] or [R, A, 3] with A = 37, 14 or 4, not {shape}")
+    A = shape[-2]
+    limit = min(2 ** 29, (2 ** 31 - 1) // A)
+    if shape[-3] > limit:
+        raise ValueError(f"fape_points must fit int32: at most {limit} rows per chain in a layout of {A} slots")
+    if isinstance(rename, str):
+        if rename != "lddt_atoms":
+            raise ValueError(f"rename must be 'lddt_atoms', None or a bool array {shape[:-2]}, not {rename!r}")
+    elif rename is not None:
+        if tuple(getattr(rename, "shape", ())) != shape[:-2] or isinstance(rename, (bool, int, float)):
+            raise ValueError(f"rename must be 'lddt_atoms', None or a bool array {shape[:-2]}, not {type(rename).__name__} {tuple(getattr(rename, 'shape', ()))}")
+    if rename is not None and not has_aatype:
+        raise ValueError("fape_atoms needs aatype in `true` to rename side chains (rename=None: no renaming)")
+    if isinstance(swaps, str):
+        if swaps != "alphafold":
+            raise ValueError(f"swaps must be 'alphafold' or an integer array [21, {A}], not {swaps!r}")
+        return clamp, scale, eps, rename, None
+    return clamp, scale, eps, rename, _swap_table(swaps, A)
+
+
 _LAYOUT_WIDTHS = {"atom37": (0, 37), "atom14": (1, 14), "backbone4": (2, 4)}  # name -> (enum fcz_dense_layout, A)
 
 
@@ -465,15 +507,7 @@ def check_lddt_atoms(cutoff, thresholds, swaps, shape, pred_shape, pred_mask_sha
         if swaps != "alphafold":
             raise ValueError(f"swaps must be 'alphafold', None or an integer array [21, {A}], not {swaps!r}")
         return cutoff, th, None
-    table = np.asarray(swaps)
-    if table.shape != (21, A) or table.dtype.kind not in "iu":
-        raise ValueError(f"swaps must be an integer array of the shape (21, {A}), not {table.dtype} {table.shape}")
-    if (table < 0).any() or (table >= A).any():
-        raise ValueError(f"every entry of swaps must be a slot 0 .. {A - 1}")
-    table = np.ascontiguousarray(table, np.uint8)
-    if not np.array_equal(np.take_along_axis(table, table.astype(np.int64), axis=1), np.broadcast_to(np.arange(A, dtype=np.uint8), (21, A))):
-        raise ValueError("swaps must be an involution within each row: the partner of a slot's partner is the slot")
-    return cutoff, th, table
+    return cutoff, th, _swap_table(swaps, A)
 
 
 GDT_THRESHOLDS = (0.5, 1.0, 2.0, 4.0, 8.0)                                  # the five counters of gdt_counts (include/fcz_hip.h, fcz_superpose_dev)

@@ -436,6 +436,61 @@ class Codec:
                        *(out[k].ctypes.data for k in ("grad_rot", "grad_trans", "grad_pos")))
         return out
 
+    def _fape_atoms_inputs(self, frames_true, pos_true, mask_true, frames_pred, pos_pred, mask_pred, aatype, swapped, length, row_off, clamp, eps, swaps):
+        """the prelude of fape_atoms and fape_atoms_grad -> (_Arrays of true, the twelve addresses of the call in its order, clamp, eps,
+        the swap table or None, the arrays the addresses point into). frames_*: (rot [.., 8, 3, 3] float32, trans [.., 8, 3] float32,
+        frame_mask [.., 8] bool / uint8; None for the prediction's: every frame present)"""
+        from . import api
+        a, pos_pred, mask_pred, _ = _pair_arrays(pos_true, mask_true, pos_pred, mask_pred, aatype, length, row_off)
+        if swapped is not None:
+            swapped = _mask_array(swapped, a.lead, "swapped")
+        clamp, _, eps, _, table = api.check_fape_atoms(clamp, 1.0, eps, swapped, a.pos.shape, a.aatype is not None, swaps)
+        keep = []
+        for which, (rot, trans, fmask) in (("true", frames_true), ("pred", frames_pred)):
+            rot, trans = np.ascontiguousarray(rot, np.float32), np.ascontiguousarray(trans, np.float32)
+            if rot.shape != a.lead + (8, 3, 3) or trans.shape != a.lead + (8, 3):
+                raise ValueError(f"rot_{which} must be float32 {a.lead + (8, 3, 3)} and trans_{which} {a.lead + (8, 3)}, not {rot.shape} and {trans.shape}")
+            if fmask is None and which == "true":
+                raise ValueError("frame_mask of the truth is needed")
+            keep += [rot, trans, None if fmask is None else _mask_array(fmask, a.lead + (8,), f"frame_mask_{which}")]
+        ptrs = [_addr(keep[0]), _addr(keep[1]), _addr(keep[2]), a.pos.ctypes.data, a.mask.ctypes.data, _addr(a.aatype), _addr(swapped), _addr(keep[3]),
+                _addr(keep[4]), _addr(keep[5]), pos_pred.ctypes.data, _addr(mask_pred)]
+        return a, ptrs, clamp, eps, table, (keep, pos_pred, mask_pred, swapped)
+
+    def fape_atoms(self, frames_true, pos_true: np.ndarray, mask_true: np.ndarray, frames_pred, pos_pred: np.ndarray, mask_pred=None, aatype=None, swapped=None,
+                   length=None, row_off=None, clamp=10.0, eps: float = 1e-4, swaps="alphafold"):
+        """frames of the eight rigid groups and dense arrays of a truth and a prediction on the host -> the all-atom FAPE sums
+        (fcz_fape_atoms, or fcz_fape_atoms_packed when row_off is given): sum float32 [n, L, 8] / [R, 8], at a frame the sum over
+        its chain's points (every atom of every residue) of min(sqrt(|R^T (x - t) - R'^T (x' - t')|^2 + eps), clamp) in float32 in
+        ascending (row, slot), and points int32, the number of those points. frames_* = (rot [.., 8, 3, 3], trans [.., 8, 3],
+        frame_mask [.., 8]) as Codec.frames(groups="all") gives them; swapped bool / uint8 [n, L] / [R] (Codec.lddt_atoms' output;
+        needs aatype) reads the truth of those rows under its other naming: the slots through `swaps`, the ambiguous groups turned
+        by 180 degrees. The dense arrays are Codec.lddt_atoms'."""
+        a, ptrs, clamp, eps, table, keep = self._fape_atoms_inputs(frames_true, pos_true, mask_true, frames_pred, pos_pred, mask_pred, aatype, swapped, length,
+                                                                   row_off, clamp, eps, swaps)
+        total = np.zeros(a.lead + (8,), np.float32)
+        points = np.zeros(a.lead + (8,), np.int32)
+        if total.size:
+            self._call("fcz_fape_atoms", a.packed, *ptrs, _addr(a.bound), a.n, a.rows, a.lay, clamp, eps, _addr(table), total.ctypes.data, points.ctypes.data)
+        return dict(sum=total, points=points)
+
+    def fape_atoms_grad(self, frames_true, pos_true: np.ndarray, mask_true: np.ndarray, frames_pred, pos_pred: np.ndarray, weight: np.ndarray, mask_pred=None,
+                        aatype=None, swapped=None, length=None, row_off=None, clamp=10.0, eps: float = 1e-4, swaps="alphafold"):
+        """the gradient of sum weight * sum of fape_atoms with respect to the prediction's rot, trans and pos_pred (fcz_fape_atoms_grad,
+        or fcz_fape_atoms_grad_packed when row_off is given): dict(grad_rot float32 [.., 8, 3, 3], grad_trans [.., 8, 3], grad_pos
+        [.., A, 3]), 0 where an item is no frame (grad_rot, grad_trans) or a slot no point (grad_pos). weight float32 [.., 8].
+        Gathered per element in a fixed order without atomics: reproducible bit for bit."""
+        a, ptrs, clamp, eps, table, keep = self._fape_atoms_inputs(frames_true, pos_true, mask_true, frames_pred, pos_pred, mask_pred, aatype, swapped, length,
+                                                                   row_off, clamp, eps, swaps)
+        weight = np.ascontiguousarray(weight, np.float32)
+        if weight.shape != a.lead + (8,):
+            raise ValueError(f"weight must be float32 {a.lead + (8,)}, not {weight.shape}")
+        out = dict(grad_rot=np.zeros(a.lead + (8, 3, 3), np.float32), grad_trans=np.zeros(a.lead + (8, 3), np.float32), grad_pos=np.zeros(a.pos.shape, np.float32))
+        if weight.size:
+            self._call("fcz_fape_atoms_grad", a.packed, *ptrs, _addr(a.bound), a.n, a.rows, a.lay, clamp, eps, _addr(table), weight.ctypes.data,
+                       *(out[k].ctypes.data for k in ("grad_rot", "grad_trans", "grad_pos")))
+        return out
+
     def lddt_atoms(self, pos_true: np.ndarray, mask_true: np.ndarray, pos_pred: np.ndarray, mask_pred=None, aatype=None, length=None, row_off=None, *,
                    cutoff: float = 15.0, thresholds=None, swaps="alphafold", per_atom: bool = False):
         """two sets of dense arrays of one shape on the host -> the all-atom lDDT of `pred` against `true` after the symmetric

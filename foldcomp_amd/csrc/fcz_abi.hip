@@ -37,6 +37,7 @@
 #include "fcz_lddt.h"
 #include "fcz_lddt_soft.h"
 #include "fcz_fape.h"
+#include "fcz_fape_atoms.h"
 #include "fcz_dssp.h"
 #include "fcz_sasa.h"
 #include "fcz_violations.h"
@@ -102,7 +103,8 @@ struct timed_span { std::string name; hipEvent_t a, b; };
 // (C + 1 u64 offsets, the bytes, C i32 status); LDDT_PRED: pos and mask of the second tensor batch of fcz_lddt, LDDT_OUT: score, pairs, hits
 // (fcz_lddt_soft: soft, pairs; fcz_lddt_soft_grad: grad), LDDT_WEIGHT: the row weights of fcz_lddt_soft_grad;
 // FAPE_FRAMES: rot, trans, frame_mask of the truth, then of the prediction, of fcz_fape (its pos, mask, bound and weight go through DENSE_IN, LDDT_PRED
-// and LDDT_WEIGHT), FAPE_OUT: sum, points (fcz_fape_grad: grad_rot, grad_trans, grad_pos);
+// and LDDT_WEIGHT), FAPE_OUT: sum, points (fcz_fape_grad: grad_rot, grad_trans, grad_pos); fcz_fape_atoms uses the same names for its arrays of eight
+// groups a row, DENSE_IN + 2 for aatype and FAPEA_SWAPPED for swapped;
 // DSSP_OUT: acc_index, acc_energy, don_index, don_energy, ss, ss_mask of fcz_dssp; SASA_POINTS: the directions of fcz_sasa, SASA_OUT: sasa_points, sasa, sasa_mask;
 // SUPERPOSE_OUT: the seven arrays of a fcz_superpose_out in the struct's order; APPLY_ROT, APPLY_TRANS, APPLY_OUT: the transforms and the moved
 // coordinates of fcz_superpose_apply (its pos and mask go through LDDT_PRED); TM_SEED, TM_SELECTED: the two arrays a fcz_tmscore_out adds to those seven;
@@ -116,9 +118,10 @@ enum { REC_BLOB, REC_OFF, REC_RES_OFF, REC_ATOM_OFF, REC_X, REC_Y, REC_Z, REC_BF
        SASA_POINTS = 4, SASA_OUT = 10,
        APPLY_ROT = 10, APPLY_TRANS, APPLY_OUT,
        ANGLES_OUT = 10, KEPT_OFF = 13, KEPT_BYTES, KEPT_STATUS, DENSE_CHAIN_INDEX, WINDOW_START = DENSE_CHAIN_INDEX, TM_SEED, TM_SELECTED,
+       FAPEA_SWAPPED = 16,
        VIOL_OUT = 10, VLOSS_WEIGHT = 4, VLOSS_OUT = 10, LDDTA_OUT = 10, GDT_OUT = 10, TA_SETS = 0, TA_PAIRS = 6, TA_OUT = 7, TA_DP_ROT = 7, TA_DP_TRANS, TA_DP_MAP, TA_DP_ALIGNED, VIOL_OUT_LAST = 19, POOL_COUNT };
 static_assert(POOL_COUNT == VIOL_OUT_LAST + 1 && DENSE_OUT + 6 == DENSE_CHAIN_INDEX && LDDTA_OUT + 6 <= POOL_COUNT && TM_SELECTED < POOL_COUNT && GDT_OUT + 8 <= POOL_COUNT && TA_OUT + 13 <= POOL_COUNT && TA_SETS + 6 == TA_PAIRS &&
-              TA_PAIRS < TA_OUT && TA_DP_ALIGNED < POOL_COUNT && FAPE_FRAMES + 6 == FAPE_OUT && FAPE_OUT + 3 <= POOL_COUNT, "the last name of the enum sizes fcz_ctx::pool");
+              TA_PAIRS < TA_OUT && TA_DP_ALIGNED < POOL_COUNT && FAPE_FRAMES + 6 == FAPE_OUT && FAPE_OUT + 3 <= FAPEA_SWAPPED && FAPEA_SWAPPED < POOL_COUNT, "the last name of the enum sizes fcz_ctx::pool");
 
 // what the device reports to the host in the middle of a call: one pinned allocation, a member per reader
 struct pinned_words {
@@ -199,6 +202,7 @@ struct fcz_ctx {
     //   fcz_lddt_soft_grad / _grad_packed           the inputs of fcz_lddt, LDDT_WEIGHT 6, LDDT_OUT 10 (grad)
     //   fcz_fape / fcz_fape_packed                  the inputs of fcz_lddt, FAPE_FRAMES 7 .. 12, FAPE_OUT 13 .. 14 (sum, points)
     //   fcz_fape_grad / fcz_fape_grad_packed        the same inputs, LDDT_WEIGHT 6, FAPE_OUT 13 .. 15 (grad_rot, grad_trans, grad_pos)
+    //   fcz_fape_atoms / _packed / _grad / _grad_packed   as fcz_fape / fcz_fape_grad, and DENSE_IN 2 (aatype), FAPEA_SWAPPED 16
     //   fcz_lddt_atoms / fcz_lddt_atoms_packed      DENSE_IN 0 .. 3 (pos_true, mask_true, aatype, length / row_off), LDDT_PRED 4 .. 5, LDDTA_OUT 10 .. 15
     //   fcz_superpose / fcz_superpose_packed        DENSE_IN 0, 1, 3 and LDDT_PRED 4 .. 5 as fcz_lddt, SUPERPOSE_OUT 10 .. 16
     //   fcz_tmscore / fcz_tmscore_packed            the same, then TM_SEED 17, TM_SELECTED 18
@@ -348,7 +352,7 @@ int fetch_resident(fcz_ctx* ctx, uint32_t C, uint64_t n_bytes, uint64_t* out_off
 // the slot of fcz_ctx::pool it goes through (table in fcz_ctx).
 struct staged_in { const void* host; size_t bytes; int slot; };
 struct staged_out { void* host; size_t bytes; int slot; };
-constexpr int STAGED_MAX = 13;
+constexpr int STAGED_MAX = 14;
 
 // The three steps of staging, for the rules below. Room for every input, then their upload; dev[] gets the device pointers in the
 // list's order. floor: what a present array is given at least (fcz_compress_dense_begin).
@@ -2192,13 +2196,10 @@ int fcz_fape_grad_packed(fcz_ctx* ctx, FCZ_FAPE_INPUTS(), const uint32_t* row_of
 // ------------------------------------------------------------------------------------------------
 // all-atom lDDT with symmetric side-chain renaming (fcz_lddt_atoms.h; no counterpart in the reference)
 // ------------------------------------------------------------------------------------------------
-// rows: L (padded) or R (packed). Fills tab from swap_table (NULL: the default) when everything is acceptable.
-static bool lddta_args_ok(const fcz_ctx* ctx, const float* pos_true, const uint8_t* mask_true, const float* pos_pred, int layout, float cutoff,
-                          const float* thresholds, const uint8_t* swap_table, uint32_t rows, const fcz_lddt_atoms_out* out, lddta_table* tab) {
+// tab from swap_table [21][A] (NULL: the default) -> true when every entry lies inside its row and the row is an involution
+static bool lddta_table_ok(int layout, const uint8_t* swap_table, lddta_table* tab) {
     const int A = fcz_dense_width(layout);
-    if (!ctx || !pos_true || !mask_true || !pos_pred || !out || !out->score || !out->pairs || !out->hits || !out->swapped || A <= 0) return false;
-    if (!std::isfinite(cutoff) || !(cutoff > 0.0f) || rows > (uint32_t)fcz_lddt_atoms_max_rows(layout)) return false;
-    if (thresholds) for (int t = 0; t < 4; t++) if (std::isnan(thresholds[t])) return false;
+    if (A <= 0) return false;
     memset(tab->partner, 0, sizeof tab->partner);
     if (swap_table) memcpy(tab->partner, swap_table, LDDTA_TYPES * (size_t)A);
     else if (fcz_lddt_default_swaps(layout, tab->partner) != FCZ_OK) return false;
@@ -2208,6 +2209,16 @@ static bool lddta_args_ok(const fcz_ctx* ctx, const float* pos_true, const uint8
             if (p >= A || tab->partner[ty * A + p] != a) return false;        // inside the row, and an involution
         }
     return true;
+}
+
+// rows: L (padded) or R (packed). Fills tab from swap_table (NULL: the default) when everything is acceptable.
+static bool lddta_args_ok(const fcz_ctx* ctx, const float* pos_true, const uint8_t* mask_true, const float* pos_pred, int layout, float cutoff,
+                          const float* thresholds, const uint8_t* swap_table, uint32_t rows, const fcz_lddt_atoms_out* out, lddta_table* tab) {
+    const int A = fcz_dense_width(layout);
+    if (!ctx || !pos_true || !mask_true || !pos_pred || !out || !out->score || !out->pairs || !out->hits || !out->swapped || A <= 0) return false;
+    if (!std::isfinite(cutoff) || !(cutoff > 0.0f) || rows > (uint32_t)fcz_lddt_atoms_max_rows(layout)) return false;
+    if (thresholds) for (int t = 0; t < 4; t++) if (std::isnan(thresholds[t])) return false;
+    return lddta_table_ok(layout, swap_table, tab);
 }
 
 // fcz_lddt_atoms_dev (bound_dev is length [n] or NULL, rows = L) and fcz_lddt_atoms_packed_dev (bound_dev = row_off [n + 1], rows = R):
@@ -2313,6 +2324,139 @@ int fcz_lddt_atoms_packed(fcz_ctx* ctx, const float* pos_true, const uint8_t* ma
         return FCZ_E_INVALID_ARG;
     return lddta_host(ctx, pos_true, mask_true, pos_pred, mask_pred, aatype, row_off, true, n, R, layout, cutoff, thresholds, tab, *out);
 }
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------------
+// all-atom FAPE over the eight rigid groups and its gradient (fcz_fape_atoms.h; no counterpart in the reference)
+// ------------------------------------------------------------------------------------------------
+// the fourteen input arrays of a call, device or host pointers, in the order of the entry points' arguments
+struct fapea_in {
+    const float* rot_true; const float* trans_true; const uint8_t* fmask_true; const float* pos_true; const uint8_t* mask_true;
+    const uint8_t* aatype; const uint8_t* swapped;
+    const float* rot_pred; const float* trans_pred; const uint8_t* fmask_pred; const float* pos_pred; const uint8_t* mask_pred;
+};
+
+// the outputs are checked by the caller. rows: L (padded) or R (packed). Fills tab when everything is acceptable.
+static bool fapea_args_ok(const fcz_ctx* ctx, const fapea_in& a, int layout, float clamp, float eps, const uint8_t* swap_table, uint32_t rows, fapea_table* tab) {
+    if (!ctx || !a.rot_true || !a.trans_true || !a.fmask_true || !a.pos_true || !a.mask_true || !a.rot_pred || !a.trans_pred || !a.pos_pred) return false;
+    const int A = fcz_dense_width(layout);
+    if (A <= 0 || (a.swapped && !a.aatype)) return false;
+    if (std::isnan(clamp) || !(clamp > 0.0f) || !std::isfinite(eps) || !(eps > 0.0f) || rows > fapea_max_rows((uint32_t)A)) return false;
+    if (!lddta_table_ok(layout, swap_table, &tab->swap)) return false;
+    for (int ty = 0; ty < (int)LDDTA_TYPES; ty++) {
+        tab->alt[ty] = 0;
+        if (ty >= 20 || layout == FCZ_DENSE_BACKBONE4) continue;              // (type 20 has no ambiguity; backbone4 renames nothing)
+        for (int g = 0; g < (int)FAPEA_GROUPS; g++) tab->alt[ty] |= (uint8_t)(fcz_frame_ambiguous(ty, g) ? 1u << g : 0u);
+    }
+    return true;
+}
+
+// the device forms of the value (weight_dev and the gradients NULL) and of the gradient (sum_dev and points_dev NULL). The gradient
+// is two sweeps over tiles of their own behind one fill, in one span.
+static int fapea_rows(fcz_ctx* ctx, const fapea_in& a, const uint32_t* bound_dev, bool packed, uint32_t n, uint32_t rows, int layout, float clamp, float eps,
+                      const fapea_table& tab, float* sum_dev, int32_t* points_dev, const float* weight_dev, float* grad_rot_dev, float* grad_trans_dev,
+                      float* grad_pos_dev) {
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (rows == 0 || (n == 0 && !packed)) return FCZ_OK;
+    const uint32_t A = (uint32_t)fcz_dense_width(layout);
+    chain_tiles frames(ctx, packed, n, rows, fapea_tile_rows(A), 12u);
+    int rc = frames.reserve(); if (rc) return rc;
+    if (grad_rot_dev) {
+        const fapea_grad_args g{a.rot_true, a.trans_true, a.fmask_true, a.pos_true, a.mask_true, a.aatype, a.swapped, a.rot_pred, a.trans_pred, a.fmask_pred,
+                                a.pos_pred, a.mask_pred, bound_dev, n, rows, A, clamp, eps, weight_dev, grad_rot_dev, grad_trans_dev, grad_pos_dev};
+        chain_tiles atoms(ctx, packed, n, rows, lddta_tile_rows(A, false), 12u);
+        rc = atoms.reserve(); if (rc) return rc;                              // (the same scratch: the frame sweep has read its tiles by then)
+        span_guard sg(ctx, "fape_atoms_grad");
+        rc = frames.run(bound_dev, [&] { hipLaunchKernelGGL(k_chain_fill<fapea_grad_args>, frames.fill_grid(rows), dim3(BLOCK), 0, ctx->stream, g); },
+                        [&](auto P, dim3 grid, const uint64_t* tile_off, uint32_t tiles_per_entry, uint64_t n_padded) {
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_fape_atoms_grad_frames<decltype(P)::value>), grid, dim3(BLOCK), 0, ctx->stream, g, tab, tile_off, tiles_per_entry, n_padded);
+        });
+        if (rc) return rc;
+        return atoms.run(bound_dev, [] {}, [&](auto P, dim3 grid, const uint64_t* tile_off, uint32_t tiles_per_entry, uint64_t n_padded) {
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_fape_atoms_grad_points<decltype(P)::value>), grid, dim3(BLOCK), 0, ctx->stream, g, tab, tile_off, tiles_per_entry, n_padded);
+        });
+    }
+    const fapea_args g{a.rot_true, a.trans_true, a.fmask_true, a.pos_true, a.mask_true, a.aatype, a.swapped, a.rot_pred, a.trans_pred, a.fmask_pred,
+                       a.pos_pred, a.mask_pred, bound_dev, n, rows, A, clamp, eps, sum_dev, points_dev};
+    span_guard sg(ctx, "fape_atoms");
+    return frames.run(bound_dev, [&] { hipLaunchKernelGGL(k_chain_fill<fapea_args>, frames.fill_grid(rows), dim3(BLOCK), 0, ctx->stream, g); },
+                      [&](auto P, dim3 grid, const uint64_t* tile_off, uint32_t tiles_per_entry, uint64_t n_padded) {
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_fape_atoms<decltype(P)::value>), grid, dim3(BLOCK), 0, ctx->stream, g, tab, tile_off, tiles_per_entry, n_padded);
+    });
+}
+
+// the host forms: the host arrays through DENSE_IN 0 .. 3, LDDT_PRED 4, 5, LDDT_WEIGHT 6, FAPE_FRAMES 7 .. 12, FAPEA_SWAPPED 16 and FAPE_OUT 13 .. 14
+// (sum, points) or 13 .. 15 (grad_rot, grad_trans, grad_pos)
+static int fapea_host(fcz_ctx* ctx, const fapea_in& a, const uint32_t* bound, bool packed, uint32_t n, uint32_t rows_per, int layout, float clamp, float eps,
+                      const fapea_table& tab, float* sum, int32_t* points, const float* weight, float* grad_rot, float* grad_trans, float* grad_pos) {
+    const dense_bytes b(packed, n, rows_per, layout, bound);
+    const size_t items = b.rows * FAPEA_GROUPS, no = items * 4;
+    auto run = [&](const void* const* in, void* const* out) {
+        const fapea_in d{(const float*)in[7], (const float*)in[8], (const uint8_t*)in[9], (const float*)in[0], (const uint8_t*)in[1], (const uint8_t*)in[2],
+                         (const uint8_t*)in[13], (const float*)in[10], (const float*)in[11], (const uint8_t*)in[12], (const float*)in[4], (const uint8_t*)in[5]};
+        const bool grad = grad_rot != nullptr;
+        return fapea_rows(ctx, d, (const uint32_t*)in[3], packed, n, rows_per, layout, clamp, eps, tab, grad ? nullptr : (float*)out[0],
+                          grad ? nullptr : (int32_t*)out[1], (const float*)in[6], grad ? (float*)out[0] : nullptr, grad ? (float*)out[1] : nullptr,
+                          grad ? (float*)out[2] : nullptr);
+    };
+    const std::initializer_list<staged_in> in = {
+        {a.pos_true, b.pos, DENSE_IN}, {a.mask_true, b.mask, DENSE_IN + 1}, {a.aatype, b.rows, DENSE_IN + 2}, {bound, b.bound, DENSE_IN + 3},
+        {a.pos_pred, b.pos, LDDT_PRED}, {a.mask_pred, b.mask, LDDT_PRED + 1}, {weight, no, LDDT_WEIGHT}, {a.rot_true, 9 * no, FAPE_FRAMES},
+        {a.trans_true, 3 * no, FAPE_FRAMES + 1}, {a.fmask_true, items, FAPE_FRAMES + 2}, {a.rot_pred, 9 * no, FAPE_FRAMES + 3},
+        {a.trans_pred, 3 * no, FAPE_FRAMES + 4}, {a.fmask_pred, items, FAPE_FRAMES + 5}, {a.swapped, b.rows, FAPEA_SWAPPED}};
+    if (grad_rot) return staged_call(ctx, in, {{grad_rot, 9 * no, FAPE_OUT}, {grad_trans, 3 * no, FAPE_OUT + 1}, {grad_pos, b.pos, FAPE_OUT + 2}}, run);
+    return staged_call(ctx, in, {{sum, no, FAPE_OUT}, {points, no, FAPE_OUT + 1}}, run);
+}
+
+extern "C" {
+
+int fcz_fape_atoms_pass(void) { return (int)FAPEA_PASS; }
+
+int fcz_fape_atoms_tile_rows(int layout) {
+    const int A = fcz_dense_width(layout);
+    return A > 0 ? (int)fapea_tile_rows((uint32_t)A) : -1;
+}
+
+#define FCZ_FAPEA_INPUTS(S) const float* rot_true##S, const float* trans_true##S, const uint8_t* fmask_true##S, const float* pos_true##S, \
+    const uint8_t* mask_true##S, const uint8_t* aatype##S, const uint8_t* swapped##S, const float* rot_pred##S, const float* trans_pred##S, \
+    const uint8_t* fmask_pred##S, const float* pos_pred##S, const uint8_t* mask_pred##S
+#define FCZ_FAPEA_IN(S) fapea_in{rot_true##S, trans_true##S, fmask_true##S, pos_true##S, mask_true##S, aatype##S, swapped##S, rot_pred##S, trans_pred##S, \
+                                 fmask_pred##S, pos_pred##S, mask_pred##S}
+// the eight entry points differ in the name of the bound, the form and the outputs
+#define FCZ_FAPEA_VALUE(NAME, S, BOUND, ROWS, PACKED, CALL) \
+    int NAME(fcz_ctx* ctx, FCZ_FAPEA_INPUTS(S), const uint32_t* BOUND, uint32_t n, uint32_t ROWS, int layout, float clamp, float eps, \
+             const uint8_t* swap_table, float* sum##S, int32_t* points##S) { \
+        const fapea_in a = FCZ_FAPEA_IN(S); \
+        fapea_table tab; \
+        if (!sum##S || !points##S || !bound_ok(PACKED, BOUND, n, ROWS) || !fapea_args_ok(ctx, a, layout, clamp, eps, swap_table, ROWS, &tab)) \
+            return FCZ_E_INVALID_ARG; \
+        return CALL(ctx, a, BOUND, PACKED, n, ROWS, layout, clamp, eps, tab, sum##S, points##S, nullptr, nullptr, nullptr, nullptr); \
+    }
+#define FCZ_FAPEA_GRAD(NAME, S, BOUND, ROWS, PACKED, CALL) \
+    int NAME(fcz_ctx* ctx, FCZ_FAPEA_INPUTS(S), const uint32_t* BOUND, uint32_t n, uint32_t ROWS, int layout, float clamp, float eps, \
+             const uint8_t* swap_table, const float* weight##S, float* grad_rot##S, float* grad_trans##S, float* grad_pos##S) { \
+        const fapea_in a = FCZ_FAPEA_IN(S); \
+        fapea_table tab; \
+        if (!weight##S || !grad_rot##S || !grad_trans##S || !grad_pos##S || !bound_ok(PACKED, BOUND, n, ROWS) || \
+            !fapea_args_ok(ctx, a, layout, clamp, eps, swap_table, ROWS, &tab)) \
+            return FCZ_E_INVALID_ARG; \
+        return CALL(ctx, a, BOUND, PACKED, n, ROWS, layout, clamp, eps, tab, nullptr, nullptr, weight##S, grad_rot##S, grad_trans##S, grad_pos##S); \
+    }
+
+FCZ_FAPEA_VALUE(fcz_fape_atoms_dev, _dev, length_dev, L, false, fapea_rows)
+FCZ_FAPEA_VALUE(fcz_fape_atoms_packed_dev, _dev, row_off_dev, R, true, fapea_rows)
+FCZ_FAPEA_GRAD(fcz_fape_atoms_grad_dev, _dev, length_dev, L, false, fapea_rows)
+FCZ_FAPEA_GRAD(fcz_fape_atoms_grad_packed_dev, _dev, row_off_dev, R, true, fapea_rows)
+FCZ_FAPEA_VALUE(fcz_fape_atoms, , length, L, false, fapea_host)
+FCZ_FAPEA_VALUE(fcz_fape_atoms_packed, , row_off, R, true, fapea_host)
+FCZ_FAPEA_GRAD(fcz_fape_atoms_grad, , length, L, false, fapea_host)
+FCZ_FAPEA_GRAD(fcz_fape_atoms_grad_packed, , row_off, R, true, fapea_host)
+
+#undef FCZ_FAPEA_INPUTS
+#undef FCZ_FAPEA_IN
+#undef FCZ_FAPEA_VALUE
+#undef FCZ_FAPEA_GRAD
 
 }  // extern "C"
 

@@ -41,6 +41,9 @@ struct chain_radii { float radius[CHAIN_TYPES * DN_MAX_WIDTH]; };   // [min(aaty
 
 // x / A for the three widths there are, without a division by a variable
 __device__ __forceinline__ uint32_t chain_div_a(uint32_t x, uint32_t A) { return A == 37u ? x / 37u : A == 14u ? x / 14u : x / 4u; }
+// the divider of a staging over the slots of a layout (chain_stage_slots_ordered's default); a sweep over rows of another width
+// brings its own (fcz_fape_atoms.h: the eight rigid groups of a row)
+struct chain_div_layout { __device__ __forceinline__ uint32_t operator()(uint32_t x, uint32_t A) const { return chain_div_a(x, A); } };
 
 // float32, every operation rounded, no FMA. d2(a, b) == d2(b, a) bit for bit: the differences are negated, the squares are the same.
 __device__ __forceinline__ float chain_d2(float ax, float ay, float az, float bx, float by, float bz) {
@@ -231,13 +234,14 @@ __device__ __forceinline__ uint32_t chain_stage_slots(uint32_t* s_count, uint32_
 // slot tid + h * BLOCK of the step, so (h, wavefront, lane) ascends with (row, slot). The steps, the rule that closes a pass and the
 // barriers are chain_stage_slots': two barriers a step, all BLOCK threads under block-uniform control flow, none in a functor. There
 // is no barrier in front: the caller's barrier that closed the pass before has freed the staging and s_wave.
+// div(x, A) = x / A: chain_div_a for the widths of the layouts, the caller's own for rows of another width.
 // -> the staged count; *r0 becomes the next pass' first row. The caller sweeps the pass and closes it with a barrier.
-template <uint32_t PASS, uint32_t STEP, class Test, class Put>
-__device__ __forceinline__ uint32_t chain_stage_slots_ordered(uint32_t* s_wave, uint32_t A, uint32_t len, uint32_t* r0, Test test, Put put) {
+template <uint32_t PASS, uint32_t STEP, class Test, class Put, class Div = chain_div_layout>
+__device__ __forceinline__ uint32_t chain_stage_slots_ordered(uint32_t* s_wave, uint32_t A, uint32_t len, uint32_t* r0, Test test, Put put, Div div = Div()) {
     static_assert(STEP % BLOCK == 0 && BLOCK % 64 == 0 && STEP <= PASS, "chain_stage_slots_ordered");
     constexpr uint32_t H = STEP / BLOCK, W = BLOCK / 64;
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-    const uint32_t step_rows = chain_div_a(STEP, A);
+    const uint32_t step_rows = div(STEP, A);
     uint32_t staged = 0;
     for (;;) {
         const uint32_t nr = len - *r0 < step_rows ? len - *r0 : step_rows;
@@ -248,7 +252,7 @@ __device__ __forceinline__ uint32_t chain_stage_slots_ordered(uint32_t* s_wave, 
             const uint32_t x = tid + h * BLOCK;
             is[h] = false;
             if (x < nr * A) {
-                const uint32_t rr = chain_div_a(x, A);
+                const uint32_t rr = div(x, A);
                 is[h] = test(*r0 + rr, x - rr * A, h);
             }
             const unsigned long long m = __ballot(is[h]);

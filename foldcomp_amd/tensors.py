@@ -20,6 +20,10 @@
     fape(pred, true, atom="CA", clamp=10.0, scale=10.0) -> dict(fape_frame [..] float32, fape_points int32, frame_mask bool, fape_chain [n]
                                    float32, loss): the backbone FAPE of AlphaFold 2 (Algorithm 28) of predicted frames and points against
                                    the truth's, a loss: differentiable with respect to pred's rot / trans / pos, with a fused backward
+    fape_atoms(pred, true, clamp=10.0, scale=10.0, rename="lddt_atoms") -> dict(fape_frame [.., 8] float32, fape_points int32, frame_mask
+                                   bool, swapped [..] bool, fape_chain [n] float32, loss): the all-atom FAPE of AlphaFold 2, the eight
+                                   rigid groups of every residue against every atom of the chain with the truth renamed first, a loss
+                                   with a fused backward; rigid_frames_torch(pos, mask, aatype) builds the eight groups differentiably
     lddt_atoms(pred, true, swaps="alphafold", per_atom=False) -> dict(lddt, lddt_pairs, lddt_hits, swapped [..] bool, lddt_chain [n]
                                    float64, atom_pairs / atom_hits [.., A]): the all-atom lDDT of every residue after the symmetric
                                    side-chain namings of the truth have been resolved towards the prediction
@@ -68,7 +72,7 @@ from ._aa_tables import RES1
 from .codec import ANGLE_COLUMNS, WIDTH_LAYOUTS, Codec, dense_layout
 from .structure import CAtomsOut, CDenseIn, CDenseOut, CLddtAtomsOut, CPackedOut, CSuperposeOut, CTmScoreOut, CGdtOut, CViolationsOut, CChainSet, CTmAlignOut, CTmAlignParams, TM_ALIGN_OUTPUTS
 
-__all__ = ["decode_tensors", "encode_tensors", "decode_angles", "crop_starts", "neighbor_graph", "rigid_frames", "lddt", "smooth_lddt", "fape", "lddt_atoms", "superpose", "tm_score", "gdt", "tm_align", "apply_transform",
+__all__ = ["decode_tensors", "encode_tensors", "decode_angles", "crop_starts", "neighbor_graph", "rigid_frames", "lddt", "smooth_lddt", "fape", "fape_atoms", "lddt_atoms", "superpose", "tm_score", "gdt", "tm_align", "apply_transform",
            "backbone_hbonds", "secondary_structure", "solvent_accessibility", "violations", "violation_loss"]
 
 
@@ -1071,6 +1075,266 @@ def fape(pred, true, *, atom="CA", clamp=10.0, scale: float = 10.0, eps: float =
     chain = torch.where(scored, cs / (cp.clamp(min=1).to(torch.float64) * scale), cs.new_zeros(()))
     loss = (chain.sum() / scored.sum().clamp(min=1).to(torch.float64)).to(torch.float32)
     return dict(fape_frame=per_row, fape_points=points, frame_mask=fm, fape_chain=chain.to(torch.float32), loss=loss)
+
+
+_frame_slots = {}
+
+
+def _frame_slot_table(lay):
+    """int64 [21, 8, 3] as nested lists: the slot of defining atom j (fcz_frame_atom's order p, o, q) of (type, group) in the layout
+    `lay` (the enum), -1 where the type or the layout has no such atom; type 20 = every other aatype value: groups 0 and 3 only"""
+    if lay not in _frame_slots:
+        lib = _lib.load()
+        t = np.full((21, 8, 3), -1, np.int64)
+        for ty in range(21):
+            for g in range(8):
+                if g >= 4 and ty >= 20:
+                    continue
+                atoms = [lib.fcz_frame_atom(ty if ty < 20 else 0, g, j) for j in range(3)]
+                if min(atoms) < 0:
+                    continue
+                slots = [lib.fcz_dense_slot(lay, ty if g >= 4 else 0, a) for a in atoms]   # (N, CA, C, O: the same slot in every type)
+                if min(slots) >= 0:
+                    t[ty, g] = slots
+        _frame_slots[lay] = t
+    return _frame_slots[lay]
+
+
+def rigid_frames_torch(pos, mask=None, aatype=None, layout=None):
+    """pos [.., A, 3], mask [.., A] bool / uint8 or None, aatype [..] uint8 or None (then only the backbone and the psi group can
+    exist), layout "atom37" / "atom14" / "backbone4" or None (read from A) -> (rot [.., 8, 3, 3], trans [.., 8, 3], frame_mask
+    [.., 8] bool): the eight rigid groups as rigid_frames(groups="all") defines them (the three atoms of fcz_frame_atom at the slots
+    of fcz_dense_slot; v1 = p - o for the backbone group and o - p for the others, v2 = q - o, origin o, columns are the axes), in
+    plain differentiable torch operations on any device, O(rows). It generalises backbone_frames_torch, guard for guard: a group
+    that does not exist (no such atoms in the type or the layout, a cleared mask, a coordinate that is not finite, coincident or
+    collinear atoms) has frame_mask False, the identity and 0, and gives pos a gradient that is exactly 0."""
+    import torch
+    A = pos.shape[-2]
+    lay = WIDTH_LAYOUTS.get(A) if layout is None else dense_layout(layout)
+    if lay is None or WIDTH_LAYOUTS.get(A) != lay:
+        raise ValueError(f"pos [.., {A}, 3] does not have the width of the layout {layout!r}: A = 37, 14 or 4")
+    table = torch.as_tensor(_frame_slot_table(lay), device=pos.device)
+    lead = tuple(pos.shape[:-2])
+    ty = torch.full(lead, 20, dtype=torch.int64, device=pos.device) if aatype is None else aatype.to(torch.int64).clamp(max=20)
+    sl = table[ty]                                                            # [.., 8, 3]
+    ok = (sl >= 0).all(-1)
+    idx = sl.clamp(min=0)
+    p_, o_, q_ = (torch.gather(pos, -2, idx[..., j, None].expand(lead + (8, 3))) for j in range(3))
+    ok = ok & torch.isfinite(p_).all(-1) & torch.isfinite(o_).all(-1) & torch.isfinite(q_).all(-1)
+    if mask is not None:
+        m = mask.to(torch.bool)
+        ok = ok & torch.gather(m, -1, idx[..., 0]) & torch.gather(m, -1, idx[..., 1]) & torch.gather(m, -1, idx[..., 2])
+    zero, one = pos.new_zeros(()), pos.new_ones(())
+    o0 = torch.where(ok[..., None], o_, zero)
+    p0, q0 = torch.where(ok[..., None], p_, zero), torch.where(ok[..., None], q_, zero)
+    backbone = (torch.arange(8, device=pos.device) == 0)[:, None]
+    v1 = torch.where(backbone, p0 - o0, o0 - p0)
+    v2 = q0 - o0
+    s1 = (v1 * v1).sum(-1)
+    g1 = ok & torch.isfinite(s1) & (s1 > 0)
+    v1, v2 = torch.where(g1[..., None], v1, zero), torch.where(g1[..., None], v2, zero)
+    e1 = v1 / torch.sqrt(torch.where(g1, s1, one))[..., None]
+    d = (e1 * v2).sum(-1)
+    gd = g1 & torch.isfinite(d)
+    u = torch.where(gd[..., None], v2, zero) - e1 * torch.where(gd, d, zero)[..., None]
+    s2 = (u * u).sum(-1)
+    g2 = gd & torch.isfinite(s2) & (s2 > 0)
+    u = torch.where(g2[..., None], u, zero)
+    e2 = u / torch.sqrt(torch.where(g2, s2, one))[..., None]
+    e1 = torch.where(g2[..., None], e1, zero)
+    e3 = torch.cross(e1, e2, dim=-1)
+    eye = torch.eye(3, dtype=pos.dtype, device=pos.device)
+    rot = torch.where(g2[..., None, None], torch.stack([e1, e2, e3], dim=-1), eye)
+    return rot, torch.where(g2[..., None], o0, zero), g2
+
+
+def _fape_atoms_function(torch):
+    """the torch.autograd.Function of fape_atoms, made once torch is there"""
+    if "fape_atoms" in _fape_autograd:
+        return _fape_autograd["fape_atoms"]
+    from torch.autograd.function import once_differentiable
+
+    class FapeAtoms(torch.autograd.Function):
+        """(pred rot [.., 8, 3, 3], pred trans [.., 8, 3], pred pos [.., A, 3]) -> sum [.., 8] (fcz_fape_atoms_dev); `call` holds
+        everything else of the call and receives points. The backward is one gradient call (fcz_fape_atoms_grad_dev) on the saved
+        inputs: nothing else is kept."""
+
+        @staticmethod
+        def forward(ctx, rot, trans, pos, call):
+            ctx.call = call
+            ctx.save_for_backward(rot, trans, pos)
+            return call.value(rot, trans, pos)
+
+        @staticmethod
+        @once_differentiable
+        def backward(ctx, grad_sum):
+            rot, trans, pos = ctx.saved_tensors
+            return (*ctx.call.gradient(rot, trans, pos, grad_sum.contiguous()), None)
+
+    _fape_autograd["fape_atoms"] = FapeAtoms
+    return FapeAtoms
+
+
+class _FapeAtomsCall:
+    """one call of fape_atoms: the checked truth and its eight-group frames, the renaming decision, the prediction's masks and the
+    parameters; value() and gradient() enqueue the kernels on the codec's stream between a wait for torch's stream and
+    codec.synchronize(), as every analysis function does"""
+
+    def __init__(self, x, tframes, swapped, pfmask, pmask, clamp, eps, table):
+        self.x, self.tframes, self.swapped, self.pfmask, self.pmask = x, tframes, swapped, pfmask, pmask
+        self.clamp, self.eps, self.table = clamp, eps, table
+        self.points = None
+
+    def _run(self, name, rot, trans, pos, *rest):
+        x, torch = self.x, self.x.torch
+        trot, ttrans, tfm = self.tframes
+        torch.cuda.current_stream(x.dev).synchronize()
+        _call(x.codec, name, x.is_packed, trot.data_ptr(), ttrans.data_ptr(), tfm.data_ptr(), x.pos.data_ptr(), x.mask.data_ptr(),
+              _ptr(x.aatype) if self.swapped is not None else None, _ptr(self.swapped), rot.data_ptr(), trans.data_ptr(), _ptr(self.pfmask), pos.data_ptr(),
+              _ptr(self.pmask), _ptr(x.bound), x.n, x.rows, x.lay, self.clamp, self.eps, None if self.table is None else self.table.ctypes.data,
+              *(o.data_ptr() for o in rest))
+        x.codec.synchronize()
+
+    def value(self, rot, trans, pos):
+        x = self.x
+        total = x.torch.zeros(x.lead + (8,), dtype=x.torch.float32, device=x.dev)
+        self.points = x.torch.zeros(x.lead + (8,), dtype=x.torch.int32, device=x.dev)
+        if total.numel():
+            self._run("fcz_fape_atoms", rot.detach().contiguous(), trans.detach().contiguous(), pos.detach().contiguous(), total, self.points)
+        return total
+
+    def gradient(self, rot, trans, pos, weight):
+        x = self.x
+        grads = [x.torch.zeros(x.lead + s, dtype=x.torch.float32, device=x.dev) for s in ((8, 3, 3), (8, 3), (x.A, 3))]
+        if weight.numel():
+            self._run("fcz_fape_atoms_grad", rot.contiguous(), trans.contiguous(), pos.contiguous(), weight, *grads)
+        return grads
+
+
+def fape_atoms(pred, true, *, clamp=10.0, scale: float = 10.0, eps: float = 1e-4, rename="lddt_atoms", swaps="alphafold",
+               codec: Optional[Codec] = None) -> dict:
+    """the eight rigid groups of every residue of a prediction against every atom of its chain, dense tensors on the GPU ->
+    dict(fape_frame, fape_points, frame_mask, swapped, fape_chain, loss): the all-atom ("side-chain") half of AlphaFold 2's structure
+    module FAPE, with the truth renamed towards the prediction first, a LOSS with a fused backward on the GPU and no frames x atoms
+    array in either direction. It stands beside fape, which is the backbone half.
+
+    `true` is the dict decode_tensors / tensor_batches return, padded, packed or a window with crop_start. Its frames are its rot /
+    trans / frame_mask when it carries the eight-group ones (decode_tensors(..., frames="all")), and are computed inside the call
+    (fcz_frames_dev, which needs aatype) otherwise. `pred` is either
+      * a dict with rot [.., 8, 3, 3], trans [.., 8, 3] and pos of true's shape, optionally frame_mask [.., 8] and mask: the model's
+        own side-chain frames and atoms; or
+      * a pos tensor of true's shape, or a dict with pos (and mask): the predicted frames are built from pos in differentiable
+        torch operations (rigid_frames_torch with true's aatype) and autograd carries the gradient on to pos.
+    rename: "lddt_atoms" runs lddt_atoms(pred.detach(), true)["swapped"] inside the call; a bool / uint8 tensor [..] is a decision
+    already made (one lddt_atoms call can serve both); None renames nothing. Where a residue is swapped the truth's atoms are read
+    at the slots of `swaps` (lddt_atoms' table) and its ambiguous groups (frame_ambiguous) turned by 180 degrees, AlphaFold's
+    rigidgroups_alt_gt_frames. An item (row, group) is a frame when the row lies inside its chain, both frame masks are set and the
+    24 floats are finite; a slot is a point as lddt_atoms' atom. Every frame meets every point of its chain, its own residue's
+    included: d = sqrt(|R^T (x - t) - R'^T (x' - t')|^2 + eps), term = min(d, clamp).
+        fape_frame   [n, L, 8] / [R, 8] float32   the mean of term over the chain's points, over scale; 0 without a frame or a point
+        fape_points  int32                        the points a frame met
+        frame_mask   bool                         the frames
+        swapped      [n, L] / [R] bool            the renaming that was applied
+        fape_chain   [n] float32                  the chain's sum of term over (the points summed over its frames * scale), in float64
+        loss         scalar float32               the mean of fape_chain over the chains that have a term (0 without one)
+    clamp=None (or +inf) is the unclamped FAPE. When any of the prediction's tensors requires a gradient (and gradients are enabled)
+    loss.backward() runs the gradient call once (one torch.autograd.Function over rot, trans and pos); the graph can be walked once
+    and not differentiated twice. Under torch.no_grad(), or with nothing that requires a gradient, only the value kernel runs. Every
+    sum has a fixed order (float32 in ascending (row, slot) on the device, chains in float64, no atomics): value and gradient are
+    reproducible bit for bit.
+
+    The tensors must be contiguous and lie on the codec's device; ordering against torch is decode_tensors'. The arguments are
+    checked first, without torch or a device (api.check_fape_atoms)."""
+    what = "fape_atoms"
+    t = dict(true) if isinstance(true, dict) else {"pos": true}
+    p = dict(pred) if isinstance(pred, dict) else {"pos": pred}
+    _need(what, t, of=" of true")
+    _need(what, p, ("pos",), " of pred")
+    shape = tuple(getattr(t["pos"], "shape", ()))
+    clamp, scale, eps, rename, table = api.check_fape_atoms(clamp, scale, eps, rename, shape, t.get("aatype") is not None, swaps)
+    lead = shape[:-2]
+    given = p.get("rot") is not None or p.get("trans") is not None
+    if given:
+        _need(what, p, ("rot", "trans"), " of pred")
+    for key, want in (("rot", lead + (8, 3, 3)), ("trans", lead + (8, 3)), ("frame_mask", lead + (8,))):
+        if given and p.get(key) is not None and tuple(getattr(p[key], "shape", ())) != want:
+            raise ValueError(f"pred {key} must have the shape {want}, not {tuple(getattr(p[key], 'shape', ()))}")
+    for key, want in (("pos", shape), ("mask", shape[:-1])):
+        if p.get(key) is not None and tuple(getattr(p[key], "shape", ())) != want:
+            raise ValueError(f"pred {key} must have the shape of true {key}, {want}, not {tuple(getattr(p[key], 'shape', ()))}")
+    own = all(t.get(k) is not None for k in ("rot", "trans", "frame_mask")) and tuple(getattr(t["rot"], "shape", ())) == lead + (8, 3, 3)
+    if not own and t.get("aatype") is None:
+        raise ValueError("fape_atoms needs aatype in `true` to build its eight-group frames (or rot / trans / frame_mask of frames='all')")
+    x = _dense_checked(what, "Codec.fape_atoms", codec, t, shape, t.get("cu_seqlens") is not None and len(shape) == 3, "full", aatype=True)
+    torch, dev = x.torch, x.dev
+    if own:
+        tframes = (_on_device(torch, what, dev, "rot", t["rot"], lead + (8, 3, 3), (torch.float32,)),
+                   _on_device(torch, what, dev, "trans", t["trans"], lead + (8, 3), (torch.float32,)),
+                   _on_device(torch, what, dev, "frame_mask", t["frame_mask"], lead + (8,), (torch.bool, torch.uint8)).view(torch.uint8))
+    else:
+        made = _frames_alloc(torch, dev, lead, 1)
+        if x.n and x.rows:
+            torch.cuda.current_stream(dev).synchronize()
+            _frames_into(x, 1, made)
+            x.codec.synchronize()
+        tframes = (made["rot"], made["trans"], made["frame_mask"].view(torch.uint8))
+    ppos, pmask = p["pos"], p.get("mask")
+    _on_device(torch, what, dev, "pred pos", ppos, shape, (torch.float32,))
+    if pmask is not None:
+        pmask = _on_device(torch, what, dev, "pred mask", pmask, shape[:-1], (torch.bool, torch.uint8)).view(torch.uint8)
+    if given:
+        rot = _on_device(torch, what, dev, "pred rot", p["rot"], lead + (8, 3, 3), (torch.float32,))
+        trans = _on_device(torch, what, dev, "pred trans", p["trans"], lead + (8, 3), (torch.float32,))
+        pfm = p.get("frame_mask")
+        if pfm is not None:
+            pfm = _on_device(torch, what, dev, "pred frame_mask", pfm, lead + (8,), (torch.bool, torch.uint8)).view(torch.uint8)
+    else:
+        rot, trans, pfm = rigid_frames_torch(ppos, pmask, x.aatype)
+        pfm = pfm.contiguous().view(torch.uint8)
+    # the renaming decision
+    if rename is None:
+        swapped = None
+    elif isinstance(rename, str):
+        with torch.no_grad():
+            swapped = lddt_atoms(dict(pos=ppos.detach(), mask=None if pmask is None else pmask), t, swaps=swaps, codec=x.codec)["swapped"].view(torch.uint8)
+    else:
+        swapped = _on_device(torch, what, dev, "rename", rename, lead, (torch.bool, torch.uint8)).view(torch.uint8)
+    call = _FapeAtomsCall(x, tframes, swapped, pfm, pmask, clamp, eps, table)
+    if torch.is_grad_enabled() and (rot.requires_grad or trans.requires_grad or ppos.requires_grad):
+        total = _fape_atoms_function(torch).apply(rot, trans, ppos, call)
+    else:
+        total = call.value(rot, trans, ppos)
+    points = call.points
+    # the frames: inside their chain, both masks, 24 finite floats; backbone4 holds groups 0 and 3 alone
+    with torch.no_grad():
+        fm = tframes[2] != 0
+        if pfm is not None:
+            fm = fm & (pfm != 0)
+        for v in (tframes[0], rot.detach()):
+            fm = fm & torch.isfinite(v).all(-1).all(-1)
+        for v in (tframes[1], trans.detach()):
+            fm = fm & torch.isfinite(v).all(-1)
+        if x.A == 4:
+            fm = fm & torch.tensor([True, False, False, True, False, False, False, False], device=dev)
+        if x.is_packed:
+            r = torch.arange(x.rows, device=dev)
+            fm = fm & ((r >= x.bound[0]) & (r < x.bound[-1]))[:, None]
+        elif x.bound is not None:
+            fm = fm & (torch.arange(x.rows, device=dev)[None, :] < x.bound[:, None])[..., None]
+    has = points > 0
+    per_item = torch.where(has, total / (points.clamp(min=1).to(torch.float32) * scale), total.new_zeros(()))
+    row_sum, row_points = total.to(torch.float64).sum(-1), points.to(torch.int64).sum(-1)
+    if x.is_packed:
+        at = x.bound.to(torch.int64)
+        cs = _autograd_functions(torch)[1].apply(row_sum, at)
+        cp = torch.cat([at.new_zeros(1), row_points.cumsum(0)])[at].diff()
+    else:
+        cs, cp = row_sum.sum(dim=1), row_points.sum(dim=1)
+    scored = cp > 0
+    chain = torch.where(scored, cs / (cp.clamp(min=1).to(torch.float64) * scale), cs.new_zeros(()))
+    loss = (chain.sum() / scored.sum().clamp(min=1).to(torch.float64)).to(torch.float32)
+    sw = torch.zeros(lead, dtype=torch.bool, device=dev) if swapped is None else swapped.view(torch.bool) if swapped.dtype == torch.uint8 else swapped
+    return dict(fape_frame=per_item, fape_points=points, frame_mask=fm, swapped=sw, fape_chain=chain.to(torch.float32), loss=loss)
 
 
 def lddt_atoms(pred, true, *, cutoff: float = 15.0, thresholds=(0.5, 1.0, 2.0, 4.0), swaps="alphafold", per_atom: bool = False,

@@ -21,6 +21,7 @@
  *   (none: no score of one structure against another)      fcz_lddt_dev / fcz_lddt_packed_dev, fcz_lddt / fcz_lddt_packed
  *   (none: no loss, nothing with a gradient)               fcz_lddt_soft_dev / fcz_lddt_soft_grad_dev (+ _packed and host forms)
  *   (none: no loss on frames)                              fcz_fape_dev / fcz_fape_grad_dev (+ _packed and host forms)
+ *   (none: no loss on side-chain frames)                   fcz_fape_atoms_dev / fcz_fape_atoms_grad_dev (+ _packed and host forms)
  *   (none: no all-atom score, no side-chain renaming)      fcz_lddt_atoms_dev / fcz_lddt_atoms_packed_dev, fcz_lddt_atoms / fcz_lddt_atoms_packed
  *   (none: no secondary structure)                         fcz_hbond_dev, fcz_dssp_labels_dev, fcz_dssp (+ _packed forms)
  *   (none: no solvent accessibility)                       fcz_sasa_dev / fcz_sasa_packed_dev, fcz_sasa / fcz_sasa_packed
@@ -586,6 +587,103 @@ int fcz_fape_grad_packed(fcz_ctx* ctx, const float* rot_true, const float* trans
                          const uint8_t* mask_true, const float* rot_pred, const float* trans_pred, const uint8_t* fmask_pred,
                          const float* pos_pred, const uint8_t* mask_pred, const uint32_t* row_off, uint32_t n, uint32_t R, int layout,
                          int slot, float clamp, float eps, const float* weight, float* grad_rot, float* grad_trans, float* grad_pos);
+
+/* ---- all-atom FAPE over the eight rigid groups and its gradient ------------------------------------------ */
+/* The other half of AlphaFold 2's structure-module FAPE (Jumper et al. 2021, supplement 1.9.2): the frame aligned point error of
+ * all eight rigid groups of every residue against every atom of the chain, after the truth has been renamed towards the prediction
+ * where a side chain has two equivalent namings. For a whole batch on the device with a fused backward pass and without a
+ * frames x atoms array in either direction. The reference has no such output. Chains follow fcz_fape_dev's rules, padded (length
+ * or NULL) or packed (row_off); the layout is atom37, atom14 or backbone4.
+ * Inputs: rot [rows][8][3][3], trans [rows][8][3] float32 and frame_mask [rows][8] bytes of the truth and of the prediction (what
+ * fcz_frames_dev writes for FCZ_FRAMES_ALL, global = rot . local + trans, columns are the axes); pos [rows][A][3], mask [rows][A]
+ * of both; aatype [rows] or NULL; swapped [rows] bytes or NULL (fcz_lddt_atoms_dev's output: rows whose truth is read under its
+ * other naming); swap_table host uint8 [21][A] or NULL for fcz_lddt_default_swaps, validated as fcz_lddt_atoms_dev validates it.
+ * With type = min(aatype[r], 20) and row r SWAPPED when swapped and aatype are given and swapped[r] != 0:
+ * FRAME. Item (r, g), g in 0 .. 7, is a FRAME when row r lies inside its chain, fmask_true[r][g] != 0, fmask_pred is NULL or
+ *   fmask_pred[r][g] != 0, and the 24 floats of both sides are finite; in backbone4 only g = 0 and g = 3 can be frames, whatever
+ *   the masks hold, and nothing is renamed. Where r is swapped and fcz_frame_ambiguous(type, g) (type 20: never) the truth's
+ *   rotation is read with its second and third columns negated, rot' . diag(1, -1, -1), AlphaFold's rigidgroups_alt_gt_frames:
+ *   R'[a][1] and R'[a][2] change sign, which is exact.
+ * POINT. Slot (r, a) is a POINT when row r lies inside its chain and, with s = swap_table[type][a] where r is swapped and s = a
+ *   elsewhere, mask_true[r][s] != 0, mask_pred is NULL or mask_pred[r][a] != 0, and pos_true[r][s] and pos_pred[r][a] are finite.
+ *   The point's true coordinates are pos_true[r][s], its predicted ones pos_pred[r][a].
+ * Term. Every frame of a chain meets every point of that chain, its own residue's included. The term is fcz_fape_dev's,
+ * operation for operation, unprimed the prediction and primed the truth:
+ *   u  = x - t                u' = x' - t'              three subtractions each
+ *   l  = R^T u                l' = R'^T u'              l_k = (R[0][k]*u0 + R[1][k]*u1) + R[2][k]*u2
+ *   e  = l - l'               s = (e0*e0 + e1*e1) + e2*e2
+ *   d  = sqrt(s + eps)        correctly rounded         term = min(d, clamp)
+ * all float32, every operation a single rounded one, no FMA. A d that is not finite counts as a point and adds nothing.
+ * Value (fcz_fape_atoms_dev):
+ *   sum [rows][8] float32    at a frame the sum of term over the chain's points in ASCENDING (row, slot), in float32; 0 elsewhere
+ *   points [rows][8] int32   at a frame the number of points of its chain (whatever their d); 0 elsewhere
+ * Gradient (fcz_fape_atoms_grad_dev) of sum_{r,g} w[r][g] * sum[r][g] for the caller's weight [rows][8] float32, with fcz_fape_grad_dev's
+ * h = (e0 * inv, e1 * inv, e2 * inv), inv the hardware reciprocal of d, where d is finite and d < clamp, and its operation orders:
+ *   grad_rot [rows][8][3][3]   grad_rot[r][g][a][k] = w * M[a][k], M[a][k] the sum over the points, ascending, of u_a * h_k
+ *   grad_trans [rows][8][3]    grad_trans[r][g][a] = -(w * ((R[a][0]*H0 + R[a][1]*H1) + R[a][2]*H2)), H the ascending sum of h
+ *   grad_pos [rows][A][3]      at a point the sum over the chain's frames in ASCENDING (row, group) of
+ *                              w * ((R[a][0]*h0 + R[a][1]*h1) + R[a][2]*h2), R the frame's predicted rotation
+ * with respect to the prediction's rot (the unconstrained partial derivative of its nine entries), trans and pos_pred[r][a]. Zeros
+ * at every item that is no frame, at every slot that is no point and in every row no chain covers. One writer per output element,
+ * no float atomics, nothing kept from the value pass: a chain gives the same bytes alone, in any batch, padded or packed, call
+ * after call. A weight is read only at a frame. The error bounds are fcz_fape_dev's with the longer sums (tests/_fape_atoms.py).
+ * rows = n * L (padded) or R (packed). Every byte of the outputs is written whatever the inputs hold, nothing outside them, and
+ * nothing outside the inputs is read, whatever row_off holds. Every index that scales with rows * A or rows * 8 is 64-bit. The
+ * points are staged in passes of at most fcz_fape_atoms_pass(); the frame sweeps run over tiles of fcz_fape_atoms_tile_rows(layout)
+ * rows. Enqueued on the ctx stream, no synchronisation; one gradient call enqueues both of its sweeps.
+ * FCZ_E_INVALID_ARG with nothing launched and no output touched: fcz_fape_dev's refusals (a NULL required pointer -- everything but
+ * aatype, swapped, fmask_pred, mask_pred, swap_table and the padded form's length --, NULL row_off with n > 0, an unknown layout,
+ * L == 0, a clamp that is NaN or not > 0, an eps that is not finite or not > 0), a swapped without an aatype, a swap_table with an
+ * entry >= A or a row that is no involution, and L or R above min(2^29, (2^31 - 1) / A): a frame's points must fit int32.
+ * n == 0 or R == 0: FCZ_OK. The time goes to the groups "fape_atoms" and "fape_atoms_grad". */
+int fcz_fape_atoms_pass(void);
+int fcz_fape_atoms_tile_rows(int layout);
+int fcz_fape_atoms_dev(fcz_ctx* ctx, const float* rot_true_dev, const float* trans_true_dev, const uint8_t* fmask_true_dev,
+                       const float* pos_true_dev, const uint8_t* mask_true_dev, const uint8_t* aatype_dev, const uint8_t* swapped_dev,
+                       const float* rot_pred_dev, const float* trans_pred_dev, const uint8_t* fmask_pred_dev, const float* pos_pred_dev,
+                       const uint8_t* mask_pred_dev, const uint32_t* length_dev, uint32_t n, uint32_t L, int layout, float clamp,
+                       float eps, const uint8_t* swap_table, float* sum_dev, int32_t* points_dev);
+int fcz_fape_atoms_packed_dev(fcz_ctx* ctx, const float* rot_true_dev, const float* trans_true_dev, const uint8_t* fmask_true_dev,
+                              const float* pos_true_dev, const uint8_t* mask_true_dev, const uint8_t* aatype_dev,
+                              const uint8_t* swapped_dev, const float* rot_pred_dev, const float* trans_pred_dev,
+                              const uint8_t* fmask_pred_dev, const float* pos_pred_dev, const uint8_t* mask_pred_dev,
+                              const uint32_t* row_off_dev, uint32_t n, uint32_t R, int layout, float clamp, float eps,
+                              const uint8_t* swap_table, float* sum_dev, int32_t* points_dev);
+int fcz_fape_atoms_grad_dev(fcz_ctx* ctx, const float* rot_true_dev, const float* trans_true_dev, const uint8_t* fmask_true_dev,
+                            const float* pos_true_dev, const uint8_t* mask_true_dev, const uint8_t* aatype_dev,
+                            const uint8_t* swapped_dev, const float* rot_pred_dev, const float* trans_pred_dev,
+                            const uint8_t* fmask_pred_dev, const float* pos_pred_dev, const uint8_t* mask_pred_dev,
+                            const uint32_t* length_dev, uint32_t n, uint32_t L, int layout, float clamp, float eps,
+                            const uint8_t* swap_table, const float* weight_dev, float* grad_rot_dev, float* grad_trans_dev,
+                            float* grad_pos_dev);
+int fcz_fape_atoms_grad_packed_dev(fcz_ctx* ctx, const float* rot_true_dev, const float* trans_true_dev, const uint8_t* fmask_true_dev,
+                                   const float* pos_true_dev, const uint8_t* mask_true_dev, const uint8_t* aatype_dev,
+                                   const uint8_t* swapped_dev, const float* rot_pred_dev, const float* trans_pred_dev,
+                                   const uint8_t* fmask_pred_dev, const float* pos_pred_dev, const uint8_t* mask_pred_dev,
+                                   const uint32_t* row_off_dev, uint32_t n, uint32_t R, int layout, float clamp, float eps,
+                                   const uint8_t* swap_table, const float* weight_dev, float* grad_rot_dev, float* grad_trans_dev,
+                                   float* grad_pos_dev);
+/* Host-pointer conveniences: the same arrays on the host, staged through the ctx like fcz_fape; synchronous. */
+int fcz_fape_atoms(fcz_ctx* ctx, const float* rot_true, const float* trans_true, const uint8_t* fmask_true, const float* pos_true,
+                   const uint8_t* mask_true, const uint8_t* aatype, const uint8_t* swapped, const float* rot_pred, const float* trans_pred,
+                   const uint8_t* fmask_pred, const float* pos_pred, const uint8_t* mask_pred, const uint32_t* length, uint32_t n,
+                   uint32_t L, int layout, float clamp, float eps, const uint8_t* swap_table, float* sum, int32_t* points);
+int fcz_fape_atoms_packed(fcz_ctx* ctx, const float* rot_true, const float* trans_true, const uint8_t* fmask_true, const float* pos_true,
+                          const uint8_t* mask_true, const uint8_t* aatype, const uint8_t* swapped, const float* rot_pred,
+                          const float* trans_pred, const uint8_t* fmask_pred, const float* pos_pred, const uint8_t* mask_pred,
+                          const uint32_t* row_off, uint32_t n, uint32_t R, int layout, float clamp, float eps,
+                          const uint8_t* swap_table, float* sum, int32_t* points);
+int fcz_fape_atoms_grad(fcz_ctx* ctx, const float* rot_true, const float* trans_true, const uint8_t* fmask_true, const float* pos_true,
+                        const uint8_t* mask_true, const uint8_t* aatype, const uint8_t* swapped, const float* rot_pred,
+                        const float* trans_pred, const uint8_t* fmask_pred, const float* pos_pred, const uint8_t* mask_pred,
+                        const uint32_t* length, uint32_t n, uint32_t L, int layout, float clamp, float eps, const uint8_t* swap_table,
+                        const float* weight, float* grad_rot, float* grad_trans, float* grad_pos);
+int fcz_fape_atoms_grad_packed(fcz_ctx* ctx, const float* rot_true, const float* trans_true, const uint8_t* fmask_true,
+                               const float* pos_true, const uint8_t* mask_true, const uint8_t* aatype, const uint8_t* swapped,
+                               const float* rot_pred, const float* trans_pred, const uint8_t* fmask_pred, const float* pos_pred,
+                               const uint8_t* mask_pred, const uint32_t* row_off, uint32_t n, uint32_t R, int layout, float clamp,
+                               float eps, const uint8_t* swap_table, const float* weight, float* grad_rot, float* grad_trans,
+                               float* grad_pos);
 
 /* ---- all-atom lDDT with symmetric side-chain renaming ------------------------------------------------------ */
 /* The lDDT that CASP, CAMEO and model papers report: every heavy atom against every heavy atom of the other residues of its chain,

@@ -1,4 +1,4 @@
-"""A seeded differential fuzz of the dense-tensor analyses (DESIGN 6.8 to 6.21) over what their kernels' control flow depends on: masks,
+"""A seeded differential fuzz of the dense-tensor analyses (DESIGN 6.8 to 6.22) over what their kernels' control flow depends on: masks,
 residue types, non-finite values, geometry, lengths about every tile and pass edge, and the padded / packed forms. The generator is
 here; tests/test_gpu_analysis_fuzz.py runs it on the device, tests/test_analysis_fuzz_cpu.py asserts what the list covers, and
 tools/dbg/analysis_fuzz.py runs it at any seed and case count.
@@ -49,11 +49,50 @@ the gradient 0 at d == 0. The CPU test asserts through the restatement: the plan
 lie in two passes and one with three partners in a staging step in every layout's long chains, every term class, a PRO link, a
 disulfide struck out (`plant_disulfide`), and that every restated number is finite.
 
+The all-atom FAPE (fcz_fape_atoms.h: k_fape_atoms, k_fape_atoms_grad_frames, k_fape_atoms_grad_points) has TWO stagings through
+chain_stage_slots_ordered and takes both through the mirror.
+  * POINTS: FAPEA_PASS = 1024 with the step of 512 (`Spec.pass_atoms`, `Spec.step`). A point needs no radius and OXT counts, so the
+    fullest pass is 1024 in all three layouts. With every mask set a pass closes at 1024 (backbone4), 2 * 36 * 14 = 1008 (atom14) and
+    2 * 13 * 37 = 962 (atom37), so places 1008 / 962 to 1023 of the six staging arrays are reached by designed masks only:
+    design_counts(A, A, short, 1024, 512) gives 256, 108 and 39 rows. Its one step that is neither whole nor empty is spread over
+    the step's rows (`respread`), and every second row of it is a swapped ASP / GLU / PHE / TYR row that holds one slot of a partnered
+    pair and lacks the other: which slot is a point then rests on the partner's mask, and the CPU test takes the points from the
+    restatement's `point`, never from the masks. The point at the pass' last place (1023, or 1022 one slot under the top) is planted
+    (`plant_last_point`): its prediction sits on the lattice where its term with every frame of the chain is 3 at least, above every
+    b_sum a chain within the item cap can have, and below the clamp with one frame at least, whose weight is set.
+  * FRAMES of k_fape_atoms_grad_points: FAPEA_FRAME_PASS = 256 with a step of 256 items (32 rows of 8 groups, the divider
+    fapea_div_groups), mirrored as pass_split(counts, 8, 256, 256). A pass closes behind the first step that stages anything, so it
+    spans more than a step only behind steps that stage nothing. `frame_steps` lays out: two such steps, a full pass (256; backbone4
+    64, 32 rows of groups 0 and 3), a pass one frame short, a pass of ONE frame, two empty steps and a full pass again, and two
+    empty steps that leave a final pass of nothing. The frame at every pass' last place carries a set weight.
+  * ROUNDS: a tile's frames or points are compacted into a list and taken in rounds of BLOCK, a wavefront without an item skipping
+    the sweep. Chains of one tile hold 1, 63, 64, 65, 255, 256, 257 and 512 frames (atom14: 64 rows of 8) and 1, 64, 65, 256, 257,
+    512, 513 and 740 points (atom37: 20 rows of 37), backbone4 256 of each.
+Its family (`fape_atoms_inputs`) draws the points as the all-atom lDDT's family does and the frames as the backbone FAPE's, with
+aatype / swapped / mask_pred / fmask_pred each NULL somewhere, non-finite values either side of every pass edge of the chain's own
+points, a swapped row that lacks a partner slot there too, and weights with NaN patterns at every item that is no frame. The item cap:
+the bounds of _fape.py rest on at most _fape_atoms.MAX_ITEMS = 2181 points and as many frames a chain (the restatement asserts it), so
+`Spec.max_items` keeps a chain of a MIX at 2181 / A rows (58 in atom37) and the long chains are sized for it: a cleared run of a pass
+and a row and then some 2 050 points (780 / 220 / 82 rows), a chain under a subset mask_pred (1 000 / 300 / 110 rows) and one that
+keeps half its rows (900 / 260 / 90). Chains of more than 128 rows are on the lattice (no tie); `restate` asks a tie share of 0 of every
+chain on an integer geometry and of 0.02 at the most of the case.
+
 What the packed ABI cannot express: rows BETWEEN two chains that no chain covers. Chain e is row_off[e] .. row_off[e + 1], so two
 neighbours share their edge, and a row_off that runs backwards in the middle makes ranges overlap, which the ABI forbids. Uncovered
 rows are in front of row_off[0] and behind row_off[n] (k_chain_fill writes both); the fuzz has both and R beyond row_off[n].
 
 Profiles dropped by name, with the reason:
+  fape_atoms x rate 0.05  fape's reason below; 1 % stays, with the first and last row and both sides of every pass edge besides.
+  fape_atoms x +-3e19 in rot
+                          fape's reason below.
+  fape_atoms x +-3e19 on the integer geometries
+                          a +-3e19 origin and a +-3e19 point cancel to a finite term whose bound is huge, a tie, and an integer chain
+                          is asked a tie share of exactly 0. The noisy geometries keep all five values in trans and in both pos.
+  fape_atoms x long noisy chains
+                          head_pass, tail_pass and iid50 of long4 / long14 / long37 and the designed chains are on the lattice, not
+                          on a helix: _fape_atoms.py measured the tie share of noisy chains up to 128 rows only.
+  fape_atoms x no aatype with swapped
+                          the ABI refuses swapped without aatype; no aatype and no swapped, and aatype without swapped, both run.
   fape x rate 0.05        a +-3e19 origin and a +-3e19 point cancel in e = l - l' to a finite term whose bound is huge: an honest tie
                           allowance (_fape.py), and at 5 % of the rows the share of such rows passes 0.02 at every seed. 1 % stays.
   fape x +-3e19 in rot    a finite entry that is no rotation's: _fape.py derives its bounds for columns of unit length. rot takes NaN
@@ -88,7 +127,7 @@ Sizing. `an.ref` measured on the build machine's CPU, seconds for one chain of t
   sasa 150 x atom14: 0.06         violations 150 x atom14: 0.04         lddt_atoms 120 x atom14: 0.07         superpose 300: < 0.01
   tmscore 300: 0.16, 1025: 0.8    gdt 120: 0.35 (a coincident or collinear chain of 30 rows: 20 s, so GDT's take 12 rows)
 Building the inputs costs as much again (an ideal helix of 4 097 rows: 1.0 s). The counts that follow, as cases (seconds of build
-and restatement of an (analysis, group) test), 250 cases in all:
+and restatement of an (analysis, group) test), 275 cases in all:
   knn 18 (passes 2.5, the rest 0.3)      lddt 17 (passes 0.8)      lddt_soft 17 (passes 2.5)      hbond 17 (0.6)      labels 10 (0.7)
   apply 12 (0.7)      frames 12 (0.8)      fape 24 (passes256 1, passes1024 5 with seven cases to 2 049 rows, the rest 0.5)
   sasa 20, violations 19, lddt_atoms 19 (design 1.4, mix 0.8, each of long4 / long14 / long37 0.5 to 1.6 with four chains of
@@ -96,6 +135,9 @@ and restatement of an (analysis, group) test), 250 cases in all:
   violation_loss 19: its restatement holds dense atoms x atoms matrices of a whole chain, so the long chains are those of the other
   sweeps times 1280 / 1536 (1 050, 540 and 125 rows at the most; each still takes three passes and more) and the six designed cases
   run at parameter set 0 only: edges 0.1, design 3.5, long4 3.6, long14 3.4, long37 3.5, mix 4.7
+  fape_atoms 25: a restatement costs frames x points, so the designed point chains keep some 150 frames and the designed frame chains
+  some 600 points: edges 2.2 (a chain of 129 rows with every mask set), design 2.6 (twelve cases), long4 2.1, long14 1.9, long37 0.8,
+  mix 1.3
 Every test stays under about 5 s of restatement. A MIX case has up to 9 chains of at most `cap` rows."""
 import dataclasses
 import zlib
@@ -105,6 +147,7 @@ import numpy as np
 import _analysis as AN
 import _dssp as DS
 import _fape as FP
+import _fape_atoms as FA
 import _gdt as GD
 import _lddt_atoms as LA
 import _lddt_soft as S
@@ -120,6 +163,9 @@ from _devpath import FILL, GUARD, to_dev
 F = np.float32
 ATOM_STEP = 2 * G.BLOCK         # fcz_sasa.h SASA_STEP = fcz_violations.h VIOL_STEP = fcz_lddt_atoms.h LDDTA_STEP = 2 * BLOCK
 VLOSS_STEP = 2 * G.BLOCK        # fcz_violation_loss.h VLOSS_STEP = 2 * BLOCK: it does not divide VLOSS_PASS = 1280
+FAPEA_STEP = 2 * G.BLOCK        # fcz_fape_atoms.h FAPEA_STEP = 2 * BLOCK: the points, two slots a lane; FAPEA_PASS = 1024 = _fape_atoms.FAPEA_PASS
+FAPEA_FRAME_PASS = 256          # fcz_fape_atoms.h: constexpr uint32_t FAPEA_FRAME_PASS = 256, the frames k_fape_atoms_grad_points stages a pass
+FAPEA_FRAME_STEP = G.BLOCK      # fcz_fape_atoms.h FAPEA_FRAME_STEP = BLOCK: 32 rows of 8 groups a step, so a pass closes once a step has staged anything
 TM_LDS_ROWS = 1024              # fcz_tmscore.h: constexpr uint32_t TM_LDS_ROWS = 1024
 TIE_SHARE = 0.02                # _lddt_soft.py / _fape.py: tie_share() must stay at or below 0.02 on every noisy input
 GLY, LEU, TRP, ALA = 7, 10, 17, 0
@@ -437,7 +483,7 @@ def fape_inputs(an, rng, lens, L, profile):
 
 def candidate_slots(an):
     """bool [21, A]: the slots of a row of every type that can be a candidate of the analysis' staging (the mask permitting)"""
-    if an.family == "atom_pair":
+    if an.family in ("atom_pair", "fape_atoms"):                               # (a candidate needs no radius: OXT counts)
         return np.ones((21, an.A), bool)
     return SA.default_table(an.A) != 0
 
@@ -571,6 +617,272 @@ def vloss_inputs(an, rng, lens, L, profile):
     return dict(d, **w)
 
 
+# ---- the all-atom FAPE: points as the all-atom lDDT has them, frames of eight groups as the backbone FAPE has them ---------------------------
+SWAP_TYPES = (FA.ASP, FA.GLU, FA.PHE, FA.TYR)
+FAPEA_OWN = ("design", "fpass", "rndf", "rndp")        # the mask kinds whose masks this family lays out itself, slot by slot and item by item
+FAPEA_ROUND_FRAMES = (1, 63, 64, 65, 255, 256, 257, 512)       # frames of one frame tile of atom14 (64 rows x 8): wavefront and round edges
+FAPEA_ROUND_POINTS = (1, 64, 65, 256, 257, 512, 513, 740)      # points of one point tile of atom37 (20 rows x 37)
+FAPEA_DESIGN_FRAMES, FAPEA_SPARSE_POINTS = 150, 600            # frames of a designed point chain, points of a designed frame chain: the restatement's time
+
+
+def frame_groups(A):
+    """the groups of a row that can be frames: backbone4 holds the atoms of groups 0 and 3 alone"""
+    return (0, 3) if A == 4 else tuple(range(FA.GROUPS))
+
+
+def frame_steps(A):
+    """the frames of every staging step (32 rows) of the designed frame chain: two steps that stage nothing at the chain's start, a
+    full pass right behind them, a pass one frame short of full, a pass of one frame, a frame-free run of two steps in the middle with
+    a full pass behind it, and two steps at the end that leave a final pass of nothing"""
+    top = FAPEA_FRAME_STEP // FA.GROUPS * len(frame_groups(A))
+    return (0, 0, top, top - 1, 1, 0, 0, top, 0, 0)
+
+
+def frame_design_rows(A):
+    return len(frame_steps(A)) * (FAPEA_FRAME_STEP // FA.GROUPS)
+
+
+def respread(counts, A, sr):
+    """design_counts' one step that is neither whole nor empty, its total spread evenly over its rows: where the pass closes rests on
+    the step's total alone, and every row of the step then holds some slots and lacks others"""
+    counts = list(counts)
+    for s0 in range(0, len(counts) - sr + 1, sr):
+        total = sum(counts[s0:s0 + sr])
+        if 0 < total < sr * A:
+            q, r = divmod(total, sr)
+            counts[s0:s0 + sr] = [q + (i < r) for i in range(sr)]
+    return counts
+
+
+def fapea_chain(inp, e, m):
+    return {k: None if inp.get(k) is None else inp[k][e, :m] for k in FA.ORDER}
+
+
+def fapea_items(inp, e, m):
+    """(frame bool [m, 8], point bool [m, A]) of chain e: the restatement's own predicate (_fape_atoms.items)"""
+    return FA.items(fapea_chain(inp, e, m))[3:]
+
+
+def _subset(rng, shape, count):
+    out = np.zeros(int(np.prod(shape)), np.uint8)
+    out[rng.permutation(out.size)[:count]] = 1
+    return out.reshape(shape)
+
+
+def plant_last_point(rng, d, e, m, target):
+    """a designed point chain: the point at the LAST place of its first pass (ascending (row, slot): np.argwhere's order) gets a
+    prediction on the lattice such that its term with EVERY frame of the chain is 3 at least (above any b_sum of a chain within
+    MAX_ITEMS: 2181 * 2^-24 * 2181 * 10.25 = 2.9) and below the clamp with one frame at least -> that frame's (row, group)"""
+    c = fapea_chain(d, e, m)
+    rot_t, pos_t, _, frame, point = FA.items(c)
+    r, a = np.argwhere(point)[target - 1]
+    fi = np.argwhere(frame)
+    Rt, tt = rot_t[frame].astype(np.float64), c["trans_t"][frame].astype(np.float64)
+    Rp, tp = c["rot_p"][frame].astype(np.float64), c["trans_p"][frame].astype(np.float64)
+    lt = np.einsum("fak,fa->fk", Rt, pos_t[r, a].astype(np.float64) - tt)
+    cube = np.stack(np.meshgrid(*[np.arange(-5, 6)] * 3, indexing="ij"), axis=-1).reshape(-1, 3)
+    xp = pos_t[r, a].astype(np.float64) + cube                                                   # [K, 3]
+    e2 = ((np.einsum("fak,cfa->cfk", Rp, xp[:, None, :] - tp[None]) - lt[None]) ** 2).sum(axis=-1)   # [offsets, frames]
+    ok = np.flatnonzero((e2.min(axis=1) >= 9) & ((e2 < FA.LATTICE_CLAMP ** 2 - 1).sum(axis=1) > 0))
+    assert len(ok), "no lattice offset keeps the planted point's term above every b_sum"
+    k = int(ok[np.argmax((e2[ok] < FA.LATTICE_CLAMP ** 2 - 1).sum(axis=1))])
+    d["pos_p"][e, r, a] = xp[k]
+    return tuple(fi[int(np.argmin(e2[k]))])
+
+
+def fape_atoms_inputs(an, rng, lens, L, profile):
+    """the all-atom FAPE. POINTS: the truth as atom_inputs draws it, the prediction the truth plus the chain's noise (integer steps on the
+    integer geometries, so that every e stays exact) with the partnered slots of every second capable row exchanged, mask_pred by the
+    chain's kind. FRAMES of all eight groups as fape_inputs draws them: signed permutations about integer origins on the integer
+    geometries, noisy rotations about origins near the row's atoms otherwise; the frame masks drawn afresh by the chain's mask kind,
+    groups 1 and 2 included, fmask_pred equal, a subset, disjoint or NULL. aatype by the chain's composition with a quarter of the
+    rows ASP, GLU, PHE or TYR, a third of the rows of every kind swapped; a case without aatype has no swapped, and one case in five
+    with aatype has none either. Non-finite values under set masks in trans, rot and both pos at the chain's first and last row, at
+    the chain's rate, and either side of every pass edge of the chain's own points (pass_split on the restatement's `point`); the
+    integer geometries take NaN and +-inf only. Weights [n, L, 8]: normal, a tenth zeros, one +-3e19 outside the designed chains (whose
+    sensitivities are measured against bounds that grow with |w|), NaN bit patterns at every item that is no frame and behind every
+    length. The kinds of FAPEA_OWN lay their masks out slot by slot: design-* (the point pass), fpass (frame_steps), rndf-N / rndp-N
+    (N frames / points in a chain of one tile)"""
+    chains, (mpred, aakind, _) = _split(profile)
+    n, A, NG = len(lens), an.A, FA.GROUPS
+    PASS, STEP = an.fz.pass_step
+    edges = edges_of(an)
+    head = [c[1].split("-")[0] for c in chains]
+    plain = tuple("/".join([c[0], "all" if h in FAPEA_OWN + ("head_pass", "tail_pass") else c[1], "0"] + c[3:]) for c, h in zip(chains, head))
+    t = atom_inputs(an, rng, lens, L, plain + (profile[-1],))
+    pt, mt, aa = t["pos"], t["mask"], t["aatype"]
+    designed = [h in FAPEA_OWN for h in head]
+    swapped = None
+    if aa is not None:
+        rows = rng.random((n, L)) < 0.25
+        aa[rows] = np.asarray(SWAP_TYPES, np.uint8)[rng.integers(0, 4, size=int(rows.sum()))]
+        swapped = (rng.random((n, L)) < 0.35).astype(np.uint8)
+        if rng.random() < 0.2 and not any(designed):
+            swapped = None
+    perms = FP.signed_permutations()
+    d = dict(rot_t=FP.random_rotations(rng, (n, L, NG)).astype(F), rot_p=FP.random_rotations(rng, (n, L, NG)).astype(F),
+             trans_t=(rng.standard_normal((n, L, NG, 3)) * 30).astype(F), trans_p=(rng.standard_normal((n, L, NG, 3)) * 30).astype(F),
+             fm_t=(rng.random((n, L, NG)) < 0.7).astype(np.uint8), fm_p=(rng.random((n, L, NG)) < 0.7).astype(np.uint8),
+             pos_t=pt, mask_t=mt, aatype=aa, swapped=swapped, pos_p=(rng.standard_normal(pt.shape) * 30).astype(F), mask_p=np.ones(mt.shape, np.uint8))
+    planted = {}
+    for e, m in enumerate(lens):
+        geom, kind, rate, _, noise, mkind = chains[e]
+        exact, h = geom in EXACT, head[e]
+        if m == 0:
+            continue
+        # ---- the masks of the points and of the frames
+        if designed[e]:                                                        # (atom_inputs left NaN patterns under the masks it cleared)
+            pt[e, :m], mt[e, :m] = atoms_chain(rng, m, A, geom), 1
+        keepf = row_keep(rng, m, "iid50" if h in FAPEA_OWN + ("head_pass", "tail_pass") else kind, edges)
+        d["fm_t"][e, :m] = keepf[:, None] & (rng.random((m, NG)) < 0.7)
+        fkind = MPREDS[int(rng.integers(3 if m <= edges[2] else 2))]           # (a chain of more than a pass keeps frames: not disjoint)
+        d["fm_p"][e, :m] = 1 if mpred == "null" else dict(equal=d["fm_t"][e, :m], disjoint=1 - d["fm_t"][e, :m], subset=d["fm_t"][e, :m] & (rng.random((m, NG)) < 0.5))[fkind]
+        sub = mt[e, :m] & (rng.random((m, A)) < 0.5)
+        d["mask_p"][e, :m] = 1 if mpred == "null" else dict(equal=mt[e, :m], disjoint=1 - mt[e, :m], subset=sub)[mkind]
+        if designed[e]:
+            d["fm_p"][e, :m], d["mask_p"][e, :m] = 1, 1
+            allowed = np.zeros((m, NG), np.uint8)
+            allowed[:, list(frame_groups(A))] = 1
+        if h == "design":                                                      # the truth's mask holds the counts: a swapped row reads it through the partner table
+            counts = respread(design_counts(A, A, kind.split("-")[1] == "short", PASS, STEP)[0], A, step_rows(A, STEP))
+            tail = kind.split("-")[2]
+            assert m == len(counts) + DESIGN_TAILS[tail], (m, len(counts), tail)
+            for r, c in enumerate(counts):
+                mt[e, r] = _subset(rng, (A,), c)
+            mt[e, len(counts):m] = 0 if tail == "empty" else (rng.random((m - len(counts), A)) < 0.5) if tail == "more" else 1
+            d["fm_t"][e, :m] = allowed & (rng.random((m, NG)) < FAPEA_DESIGN_FRAMES / allowed.sum())
+            if aa is not None and A != 4:                                      # the rows of the spread step: every second one a swapped row of a type with partners
+                part = [r for r, c in enumerate(counts) if 0 < c < A][::2]
+                aa[e, part], swapped[e, part] = np.asarray(SWAP_TYPES, np.uint8)[np.arange(len(part)) % 4], 1
+                table = LA.default_table(A)
+                for r in part:                                                 # ... that holds one slot of a partnered pair and lacks the other
+                    a = int(rng.choice(np.flatnonzero(table[aa[e, r]] != np.arange(A))))
+                    rest = np.setdiff1d(np.arange(A), [a, table[aa[e, r], a]])
+                    mt[e, r] = 0
+                    mt[e, r, [a] + list(rng.permutation(rest)[:counts[r] - 1])] = 1
+        elif h == "fpass":
+            sr = FAPEA_FRAME_STEP // NG
+            assert m == frame_design_rows(A)
+            for s, c in enumerate(frame_steps(A)):
+                top = sr * len(frame_groups(A))
+                fm = allowed[s * sr:(s + 1) * sr].copy()
+                if c == 1:
+                    fm = _one_of(rng, fm)
+                elif c == top - 1:
+                    fm = fm & (1 - _one_of(rng, fm))
+                elif c == 0:
+                    fm[:] = 0
+                d["fm_t"][e, s * sr:(s + 1) * sr] = fm
+            mt[e, :m] = rng.random((m, A)) < FAPEA_SPARSE_POINTS / (m * A)
+        elif h == "rndf":
+            d["fm_t"][e, :m] = 0
+            at = np.argwhere(allowed)
+            pick = at[rng.permutation(len(at))[:int(kind.split("-")[1])]]
+            d["fm_t"][e, pick[:, 0], pick[:, 1]] = 1
+            mt[e, :m] = rng.random((m, A)) < min(1.0, FAPEA_SPARSE_POINTS / 2 / (m * A))
+        elif h == "rndp":                                                      # the truth's mask all set, so the count is mask_pred's whatever the row's naming
+            d["mask_p"][e, :m] = _subset(rng, (m, A), int(kind.split("-")[1]))
+            d["fm_t"][e, :m] = allowed & (rng.random((m, NG)) < 0.5)
+        # ---- the prediction's points and the frames' geometry
+        x = pt[e, :m]
+        hole = np.isnan(x).any(axis=-1)
+        with np.errstate(invalid="ignore"):
+            y = x + (rng.integers(-2, 3, size=x.shape) if exact else rng.standard_normal(x.shape) * float(noise)).astype(F)
+        y[hole] = (rng.standard_normal((int(hole.sum()), 3)) * 30).astype(F)
+        if aa is not None and not designed[e]:                                 # a prediction under the other naming, as atom_pair_inputs has it
+            table = LA.default_table(A)
+            capable = (table != np.arange(A))[np.minimum(aa[e, :m], 20)].any(axis=-1)
+            rows = np.zeros(m, bool)
+            rows[np.flatnonzero(capable)[::2]] = True
+            y = LA.exchange(y[None], aa[e, :m][None], rows[None], table)[0]
+        d["pos_p"][e, :m] = y
+        with np.errstate(invalid="ignore"):
+            site = np.nan_to_num(np.where(hole[..., None], 0, x).sum(axis=1) / np.maximum((~hole).sum(axis=1), 1)[:, None]).astype(np.float64)
+        if exact:
+            d["rot_t"][e, :m], d["rot_p"][e, :m] = perms[rng.integers(0, 24, size=(m, NG))], perms[rng.integers(0, 24, size=(m, NG))]
+            d["trans_t"][e, :m] = np.rint(site)[:, None, :] + rng.integers(-6, 7, size=(m, NG, 3))
+            d["trans_p"][e, :m] = d["trans_t"][e, :m] + rng.integers(-2, 3, size=(m, NG, 3))
+        else:
+            rt = FP.random_rotations(rng, (m, NG))
+            d["rot_t"][e, :m], d["rot_p"][e, :m] = rt, FP.small_rotations(rng, (m, NG), 0.15) @ rt
+            d["trans_t"][e, :m] = site[:, None, :] + rng.standard_normal((m, NG, 3)) * 1.5 / FP.SQ3
+            d["trans_p"][e, :m] = d["trans_t"][e, :m] + (rng.standard_normal((m, NG, 3)) * max(float(noise), 0.05)).astype(F)
+        per_row = lambda: fapea_items(d, e, m)[1].sum(axis=1)
+        if h in ("head_pass", "tail_pass"):                                    # a cleared run longer than any pass of the chain's points, with two passes left
+            span = max(b - a for a, b, _ in pass_split(per_row(), A, PASS, STEP)) + 1
+            assert 3 * span < m, (m, span, "the chain is too short for a run of a pass and two passes")
+            mt[e, :span if h == "head_pass" else 0] = 0
+            mt[e, m - span if h == "tail_pass" else m:m] = 0
+        # ---- non-finite values under set masks
+        if float(rate) and not designed[e]:
+            at_edge = {r for _, end, _ in pass_split(per_row(), A, PASS, STEP)[:-1] for r in (end - 1, end)}
+            if swapped is not None and A != 4:                                 # either side of a pass edge: a swapped row of a type with partners that lacks one slot of a pair
+                table = LA.default_table(A)
+                for i, r in enumerate(sorted(at_edge)):
+                    aa[e, r], swapped[e, r] = SWAP_TYPES[i % 4], 1
+                    mt[e, r, int(rng.choice(np.flatnonzero(table[aa[e, r]] != np.arange(A))))] = 0
+            frame, point = fapea_items(d, e, m)
+            for r in sorted(set(np.flatnonzero(rng.random(m) < float(rate)).tolist()) | {0, m - 1} | at_edge):
+                bad = BAD[:3] if exact or r in at_edge else BAD
+                what = int(rng.integers(2, 4)) if r in at_edge else int(rng.integers(4))
+                value = bad[int(rng.integers(len(bad)))]
+                if what < 2 and frame[r].any():
+                    g = int(rng.choice(np.flatnonzero(frame[r])))
+                    side = "tp"[int(rng.integers(2))]
+                    if what == 0:
+                        d["trans_" + side][e, r, g, int(rng.integers(3))] = value
+                    else:                                                      # (a finite entry that is no rotation's has no bound: _fape.py)
+                        d["rot_" + side][e, r, g, int(rng.integers(3)), int(rng.integers(3))] = BAD[int(rng.integers(3))]
+                elif point[r].any():                                           # a point's prediction, or the truth's slot the point reads
+                    a = int(rng.choice(np.flatnonzero(point[r])))
+                    if what == 3 or swapped is None or not swapped[e, r]:
+                        d["pos_p" if what == 3 else "pos_t"][e, r, a, int(rng.integers(3))] = value
+                    else:
+                        d["pos_p"][e, r, a, int(rng.integers(3))] = value
+        if h == "design":
+            planted[e] = plant_last_point(rng, d, e, m, pass_split(per_row(), A, PASS, STEP)[0][2])
+    # ---- the weights, by the restatement's frames
+    frame = np.zeros((n, L, NG), bool)
+    for e, m in enumerate(lens):
+        if m:
+            frame[e, :m] = fapea_items(d, e, m)[0]
+    w = rng.standard_normal((n, L, NG)).astype(F)
+    w[rng.random(w.shape) < 0.1] = 0
+    for e in range(n):
+        at = np.argwhere(frame[e])
+        if len(at) and not designed[e]:
+            w[e][tuple(at[int(rng.integers(len(at)))])] = F(3e19) * (1 if rng.integers(2) else -1)
+            break
+    for e, m in enumerate(lens):
+        if head[e] == "fpass":                                                 # the frame at the last place of every pass carries a weight
+            at = np.argwhere(frame[e, :m])
+            first = 0
+            for _, _, staged in pass_split(frame[e, :m].sum(axis=1), NG, FAPEA_FRAME_PASS, FAPEA_FRAME_STEP):
+                first += staged
+                if staged:
+                    w[e][tuple(at[first - 1])] = F(1.5)
+        if e in planted:
+            w[e][planted[e]] = F(-1.25)
+    w.view(np.uint32)[~frame] = AN.NAN_BITS
+    # ---- NaN patterns under every cleared mask, the NULL forms
+    payload(d["pos_t"], d["mask_t"])
+    payload(d["pos_p"], d["mask_p"])
+    for side in "tp":
+        d["rot_" + side].view(np.uint32)[d["fm_" + side] == 0] = AN.NAN_BITS
+        d["trans_" + side].view(np.uint32)[d["fm_" + side] == 0] = AN.NAN_BITS
+    if mpred == "null":
+        d["fm_p"] = d["mask_p"] = None
+    return dict({k: (None if d[k] is None else np.ascontiguousarray(d[k])) for k in FA.ORDER}, w=w)
+
+
+def _one_of(rng, allowed):
+    """uint8 like `allowed` with one of its set items set"""
+    at = np.argwhere(allowed)
+    out = np.zeros_like(allowed)
+    out[tuple(at[int(rng.integers(len(at)))])] = 1
+    return out
+
+
 def backbone_inputs(an, rng, lens, L, profile):
     d = atom_inputs(an, rng, lens, L, profile)
     if d["aatype"] is not None:
@@ -592,7 +904,7 @@ def apply_inputs(an, rng, lens, L, profile):
 
 
 FAMILIES = dict(pair=pair_inputs, site=site_inputs, soft=soft_inputs, fape=fape_inputs, atoms=atom_inputs, atom_pair=atom_pair_inputs, backbone=backbone_inputs,
-                labels=labels_inputs, apply=apply_inputs, vloss=vloss_inputs)
+                labels=labels_inputs, apply=apply_inputs, vloss=vloss_inputs, fape_atoms=fape_atoms_inputs)
 
 
 def draw(an, rng, lens, L, profile):
@@ -637,6 +949,9 @@ def _labels(A, slot, param):
 
 LONG_LENS = ((4, (1250, 1250, 900, 700)), (14, (640, 640, 420, 300)), (37, (150, 150, 110, 90)))
 VLOSS_LONG_LENS = ((4, (1050, 1050, 750, 590)), (14, (540, 540, 350, 250)), (37, (125, 125, 92, 75)))       # the same chains at a pass of 1280 for 1536
+# the all-atom FAPE: at most _fape_atoms.MAX_ITEMS points (and frames) a chain, and still three passes of 1024 points. head_pass / tail_pass: a
+# cleared run of one pass and a row, then some 2 050 points; the third chain passes a subset mask_pred (half its slots), the fourth keeps half its rows
+FAPEA_LONG_LENS = ((4, (780, 780, 1000, 900)), (14, (220, 220, 300, 260)), (37, (82, 82, 110, 90)))
 
 
 @dataclasses.dataclass(frozen=True)
@@ -660,6 +975,7 @@ class Spec:
     pass_atoms: int = G.ATOM_PASS   # the atoms of a pass of an atom-pass sweep
     step: int = ATOM_STEP           # the slots its staging step examines
     long_lens: tuple = LONG_LENS    # the rows of the four chains of the long4 / long14 / long37 cases, by layout
+    max_items: int = 0              # where the comparator's bounds rest on it: the slots a chain may hold, so A * rows stays at or below it
 
     @property
     def pass_step(self):
@@ -691,10 +1007,12 @@ SPECS = dict(
     superpose=Spec(lambda A, s, p: _with(G.Superpose(), A, s, "superpose"), SLOTS, lambda A: 64, waves=True, geoms=WAVE_GEOMS, bad=BAD[:3], mixes=8),
     tmscore=Spec(lambda A, s, p: _with(G.TmScore(), A, s, "tmscore"), SLOTS, lambda A: 64, waves=True, geoms=WAVE_GEOMS, bad=BAD[:3], noises=NOISES[1:], mixes=8, cap=150),
     gdt=Spec(lambda A, s, p: _with(G.Gdt(), A, s, "gdt"), SLOTS, lambda A: 64, waves=True, geoms=WAVE_GEOMS, bad=BAD[:3], noises=NOISES[1:], mixes=8, cap=80),
+    fape_atoms=Spec(lambda A, s, p: FA.FapeAtoms(A), LAYOUTS3, FA.fapea_tile_rows, atom_pass=True, mixes=8, cap=80, rates=RATES[:2], pass_atoms=FA.FAPEA_PASS, step=FAPEA_STEP,
+                    long_lens=FAPEA_LONG_LENS, max_items=FA.MAX_ITEMS),
 )
-PAIRED = ("lddt", "lddt_soft", "fape", "lddt_atoms", "superpose", "tmscore", "gdt")            # the analyses that take mask_pred
-WITH_AATYPE = ("hbond", "labels", "sasa", "violations", "violation_loss", "lddt_atoms", "frames")              # the ABI takes NULL for aatype
-NEED_MARGIN = ("lddt_soft", "fape", "superpose", "tmscore", "gdt", "tmalign")                              # their comparators need a margin of the inputs: redrawn
+PAIRED = ("lddt", "lddt_soft", "fape", "lddt_atoms", "superpose", "tmscore", "gdt", "fape_atoms")            # the analyses that take mask_pred
+WITH_AATYPE = ("hbond", "labels", "sasa", "violations", "violation_loss", "lddt_atoms", "frames", "fape_atoms")              # the ABI takes NULL for aatype
+NEED_MARGIN = ("lddt_soft", "fape", "superpose", "tmscore", "gdt", "tmalign", "fape_atoms")                              # their comparators need a margin of the inputs: redrawn
 
 
 @dataclasses.dataclass(frozen=True)
@@ -756,7 +1074,7 @@ def cases(seed=0, per=None):
             case_profile = case_profile or _case_profile(name, k)
             if (name == "frames" and param == 1) or (name in ("sasa", "violations", "violation_loss") and A == 14):     # (the ABI refuses a NULL aatype there)
                 case_profile = case_profile.replace("noaatype", "aatype")
-            if form[0] == "null":                                              # length NULL: every chain has L rows
+            if form[0] == "null":                                             # length NULL: every chain has L rows
                 lens = [max(list(lens) + [1])] * len(lens)
             out.append(Case(name, A, slot, param, form, tuple(int(m) for m in lens), tuple(profs) + (case_profile,),
                             seed * 1000 + k, group))
@@ -796,15 +1114,24 @@ def cases(seed=0, per=None):
                 for short, tails in ((False, ("end", "empty")), (True, ("plus1", "more"))):
                     rows = len(design_counts(v[0], c_row, short, *spec.pass_step)[0])
                     lens = [rows + DESIGN_TAILS[t] for t in tails]
-                    ps = profs(2, geom="helix", rate="0", comp=comp)
+                    ps = profs(2, geom="lattice" if name == "fape_atoms" else "helix", rate="0", comp=comp)      # (a long noisy chain has a tie in most rows: _fape_atoms.py)
                     ps = ["/".join(p.split("/")[:1] + [f"design-{'short' if short else 'full'}-{t}"] + p.split("/")[2:5] + ["equal"]) for p, t in zip(ps, tails)]
                     add("design", lens, ps, ("packed", 2, 3) if short else ("padded", 1), v, "mask/aatype/wide")
+                if name == "fape_atoms":
+                    # the frame staging of k_fape_atoms_grad_points (frame_steps), and chains of ONE tile whose frames / points end on the
+                    # edges of a wavefront and of a round of BLOCK: frames in atom14 (a tile of 64 rows x 8), points in atom37 (20 rows x 37)
+                    own = lambda kind: profs(1, geom="lattice", mask=kind, rate="0", comp="mix", mpred="equal")
+                    add("design", [frame_design_rows(v[0])], own("fpass"), ("packed", 1, 2) if v[0] == 14 else ("padded", 0), v, "mask/aatype/small")
+                    rounds = {14: [(f"rndf-{q}", FA.fapea_tile_rows(14)) for q in FAPEA_ROUND_FRAMES], 37: [(f"rndp-{q}", G.lddta_tile_rows(37, False)) for q in FAPEA_ROUND_POINTS],
+                              4: [(f"rndf-{G.BLOCK}", FA.fapea_tile_rows(4)), (f"rndp-{G.BLOCK}", G.lddta_tile_rows(4, False))]}[v[0]]
+                    add("design", [m for _, m in rounds], [p for kind, _ in rounds for p in own(kind)], ("packed", 0, 0) if v[0] == 37 else ("padded", 2), v, "mask/aatype/wide")
             # chains of several passes that are NOT designed: mixed types, runs, independent clearing, non-finite values at the pass edges
             # (placed through pass_split), a cleared run longer than any of the chain's passes at its start and at its end
             for v, form in zip(spec.variants, (("packed", 3, 2), ("padded", 1), ("packed", 0, 0))):
                 lens = list(dict(spec.long_lens)[v[0]])
-                ps = (profs(1, geom="helix", mask="head_pass", rate="0.01", comp="mix", mpred="equal") + profs(1, geom="helix", mask="tail_pass", rate="0.05", comp="alternate", mpred="equal")
-                      + profs(1, geom="lattice", mask="gap_step" if v[0] == 4 else "runs64", rate="0.01", comp="mix", mpred="subset") + profs(1, geom="helix", mask="iid50", rate="0.05", comp="mix", mpred="equal"))
+                lg = "lattice" if name == "fape_atoms" else "helix"           # (the all-atom FAPE: noisy chains stay at 128 rows or under, _fape_atoms.py)
+                ps = (profs(1, geom=lg, mask="head_pass", rate="0.01", comp="mix", mpred="equal") + profs(1, geom=lg, mask="tail_pass", rate=spec.rates[-1], comp="alternate", mpred="equal")
+                      + profs(1, geom="lattice", mask="gap_step" if v[0] == 4 else "runs64", rate="0.01", comp="mix", mpred="subset") + profs(1, geom=lg, mask="iid50", rate=spec.rates[-1], comp="mix", mpred="equal"))
                 add(f"long{v[0]}", lens, ps, form, v, "mask/aatype/small")
         # 4. the wave-per-chain kernels: 0 to 3 sites anywhere in a long chain, coincident and collinear chains in an ordinary batch
         if spec.waves:
@@ -824,6 +1151,8 @@ def cases(seed=0, per=None):
             pool = [0, 1, 2, 3, T - 1, T, T + 1]
             lens = [int(pool[int(rng.integers(len(pool)))]) if rng.random() < 0.3 else int(rng.integers(4, spec.cap + 1)) for _ in range(n)]
             lens = [min(m, spec.cap) for m in lens]
+            if spec.max_items:                                                 # (a chain of the mix may have every mask set)
+                lens = [min(m, spec.max_items // spec.variants[k % len(spec.variants)][0]) for m in lens]
             add("mix", lens, profs(n))
         if name == "knn":                                                      # compact globules of fewer sites than k + 1 and of more
             add("mix", [3, 6, 12, 40, 0], profs(5, geom="globule", mask="all", rate="0"), ("packed", 1, 1), spec.variants[1])
@@ -995,6 +1324,10 @@ def restate(b):
         b.ref = an.ref(inp, eff)
     if name in ("lddt_soft", "fape"):
         return (S if name == "lddt_soft" else FP).tie_share(b.ref) <= TIE_SHARE
+    if name == "fape_atoms":                                                   # no tie at all on the integer geometries, few on the noisy ones
+        exact = [e for e, g in enumerate(geoms) if g in EXACT and (b.ref["tie_f"][e].any() or b.ref["tie_p"][e].any())]
+        b.why = (FA.tie_share(b.ref), "integer chains with a tie", exact)
+        return FA.tie_share(b.ref) <= TIE_SHARE and not exact
     if name not in ("superpose", "tmscore", "gdt"):
         return True
     loose, site = [], SP.site_of(inp["pt"], inp["mt"], inp["pp"], inp["mp"], an.slot)
@@ -1232,6 +1565,8 @@ def candidates(b, e):
     """bool [m, A]: the slots of chain e that its analysis stages as candidates (the score launch of the all-atom lDDT, where no row of
     the chain has a partnered slot)"""
     m, inp, an = b.eff[e], b.inp, b.an
+    if an.family == "fape_atoms":                                              # the restatement's own predicate: the renaming decides which slot is a point
+        return fapea_items(inp, e, m)[1]
     if an.family == "atom_pair":
         with np.errstate(invalid="ignore"):
             ok = (inp["mt"][e, :m] != 0) & np.isfinite(inp["pt"][e, :m]).all(axis=-1) & np.isfinite(inp["pp"][e, :m]).all(axis=-1)

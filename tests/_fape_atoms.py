@@ -83,14 +83,12 @@ def renamed(c, table, alt):
     return rot_t, c["pos_t"][rows, s], c["mask_t"][rows, s]
 
 
-def chain(c, w=None, clamp=10.0, eps=1e-4, table=None, alt=None):
-    """c: the twelve arrays of one chain of m rows (fm_p, mask_p, aatype, swapped may be None), w [m, 8] or None -> REF_KEYS"""
+def items(c, table=None, alt=None):
+    """one chain of ORDER's arrays -> (rot_t, pos_t, mask_t as the sweep reads them, frame bool [m, 8], point bool [m, A]): which item is a
+    FRAME and which slot a POINT, float32 facts of the inputs alone"""
     m, A = c["mask_t"].shape
     if table is None:
         table, alt = tables(A)
-    out = _empty(m, A)
-    if m == 0:
-        return out
     rot_t, pos_t, mask_t = renamed(c, table, alt)
     frame = c["fm_t"] != 0
     if c.get("fm_p") is not None:
@@ -105,6 +103,16 @@ def chain(c, w=None, clamp=10.0, eps=1e-4, table=None, alt=None):
         point &= c["mask_p"] != 0
     if A == 4:
         frame[:, [1, 2, 4, 5, 6, 7]] = False                              # backbone4 holds the atoms of groups 0 and 3 alone
+    return rot_t, pos_t, mask_t, frame, point
+
+
+def chain(c, w=None, clamp=10.0, eps=1e-4, table=None, alt=None):
+    """c: the twelve arrays of one chain of m rows (fm_p, mask_p, aatype, swapped may be None), w [m, 8] or None -> REF_KEYS"""
+    m, A = c["mask_t"].shape
+    out = _empty(m, A)
+    if m == 0:
+        return out
+    rot_t, pos_t, mask_t, frame, point = items(c, table, alt)
     nf, npt = GROUPS * m, A * m
     assert int(frame.sum()) <= MAX_ITEMS and int(point.sum()) <= MAX_ITEMS, (int(frame.sum()), int(point.sum()), "the factor 1.001 of the bounds")
     pad_f = lambda a: np.concatenate([a.reshape((nf,) + a.shape[2:]), np.zeros((npt,) + a.shape[2:], a.dtype)])

@@ -12,7 +12,7 @@
 //                   offset held by lane = length; the 512- / 256-entry fast tables are filled lane = entry;
 //                 * a code longer than the fast table is decoded by ONE ballot: lane l tests "is the l-bit prefix a code of
 //                   length l" (canonical codes: first[l] <= prefix < first[l] + count[l]);
-//                 * LZ77 copies move up to 64 bytes per LDS round trip through a 16 KB ring of the newest output (in-order LDS
+//                 * LZ77 copies move up to 64 bytes per LDS round trip through an 8 KB ring of the newest output (in-order LDS
 //                   pipeline: a later chunk reads what an earlier chunk wrote); matches farther back than the ring read the text
 //                   the wavefront already flushed to HBM;
 //                 * the ring leaves in rounds of 4 KB: 16-byte coalesced stores, and the CRC-32 of the round by 64 lanes x 64

@@ -2,7 +2,9 @@
 """k_inflate on texts the fixtures do not hold: the input variants of the differential fuzz rendered as PDB and mmCIF text, composite
 files, binary noise, long runs, texts of every size around the kernel's windows -- each compressed with a random level (0-9),
 strategy (default / filtered / Huffman only / RLE / fixed), window (9-15 bits) and memory level (1-9: many small blocks) -- against
-zlib: the member inflates to zlib's bytes or is refused (none of these should be). usage (GPU box): python tools/dbg/inflate_fuzz.py [n] [seed]"""
+zlib: the member inflates to zlib's bytes or is refused (none of these should be). A third argument adds the members of
+tests/_deflate.py stream_cases(that seed): streams written from explicit tokens, which no zlib encoder writes.
+usage (GPU box): python tools/dbg/inflate_fuzz.py [n] [seed] [stream seed]"""
 import os, sys, zlib
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests")); sys.path.insert(0, os.path.join(ROOT, "oracle"))
@@ -18,7 +20,7 @@ def gz(data, rng):
     return c.compress(data) + c.flush()
 
 
-def run(N, seed, codec=None):
+def run(N, seed, codec=None, streams=None):
     rng = np.random.default_rng(seed)
     own = codec is None
     if own: codec = Codec(0)
@@ -44,6 +46,10 @@ def run(N, seed, codec=None):
     texts += [(b"ATOM  %5d" % k) * int(n) for k, n in enumerate(rng.integers(1, 20000, N))]
     texts += [texts[0][:n] for n in (0, 1, 2, 3, 63, 64, 65, 255, 256, 257, 4095, 4096, 4097, 8191, 8192, 8193, 32767, 32768, 32769, 65535, 65536, 65537)]
     members = [gz(t, rng) for t in texts]
+    if streams is not None:
+        import _deflate
+        written = [e for e in _deflate.stream_cases(int(streams)) if e.kind]
+        texts += [e.text for e in written]; members += [e.data for e in written]
     got, st = codec.inflate(members)
     bad = 0
     for i, (t, g, s) in enumerate(zip(texts, got, st)):
@@ -56,4 +62,4 @@ def run(N, seed, codec=None):
 
 
 if __name__ == "__main__":
-    run(int(sys.argv[1]) if len(sys.argv) > 1 else 6, int(sys.argv[2]) if len(sys.argv) > 2 else 1)
+    run(int(sys.argv[1]) if len(sys.argv) > 1 else 6, int(sys.argv[2]) if len(sys.argv) > 2 else 1, streams=int(sys.argv[3]) if len(sys.argv) > 3 else None)
